@@ -35,6 +35,12 @@ N > 1 is launched by the driver as  python -m torch.distributed.run --nproc-per-
 
 cpu_baseline: the scalar C oracle (oracle/, test infrastructure) timed on this box's host cores on a bounded sample,
 rank 0, N=1 only.  It is a *port* (scalar restatement), not ISPC SIMD code: the reference cannot be built here.
+
+A plain run does only what the headline needs: set up, warm up, time --steps steps, print the line (metric / value / unit /
+higher_is_better / dtype / ms_per_step ...).  --full adds everything else described above: the gather verification of N > 1,
+the kernel-only HIP-event leg and the `roofline` built on it (with the committed profiling passes), `formats`, `weak_side`,
+`cpu_baseline` and the C++ job's scatter figure.  --dump-outputs DIR writes the block stream the last timed step produced
+(see dump_outputs) so that two builds can be compared output for output; the inputs are seeded, identical from run to run.
 """
 import argparse
 import datetime
@@ -481,6 +487,26 @@ def pmc_traffic(workload, cur_sha=None):
         return None
 
 
+DUMP_MAX_BLOCKS = 1 << 20      # 4096^2 surface: the whole stream; larger ones: a fixed sample of this many blocks
+DUMP_SEED = 20240607
+
+
+def dump_outputs(out_dir, stream, fmt):
+    """--dump-outputs: the BCn block stream a caller of the timed path receives, as float32 (exact) in out_dir/blocks.npy -- one row per
+    block, its bytes read as little-endian 16-bit words (so 16-byte blocks are 8 values).  Streams of more than DUMP_MAX_BLOCKS blocks
+    are sampled: a fixed, seeded choice of blocks in stream order, their indices in out_dir/block_index.npy (float64).  At most 40 MiB."""
+    from itw_amd import abi
+    os.makedirs(out_dir, exist_ok=True)
+    words = np.ascontiguousarray(stream.cpu().numpy()).view("<u2").reshape(-1, abi.BYTES_PER_BLOCK[fmt] // 2)
+    if words.shape[0] > DUMP_MAX_BLOCKS:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(words.shape[0], DUMP_MAX_BLOCKS, replace=False))
+        words = words[idx]
+        np.save(os.path.join(out_dir, "block_index.npy"), idx.astype(np.float64))
+    elif os.path.exists(os.path.join(out_dir, "block_index.npy")):
+        os.remove(os.path.join(out_dir, "block_index.npy"))          # (left by an earlier, sampled dump)
+    np.save(os.path.join(out_dir, "blocks.npy"), words.astype(np.float32))
+
+
 def _all_device_sync():
     for i in range(torch.cuda.device_count()):
         torch.cuda.synchronize(i)
@@ -562,7 +588,7 @@ def cpp_worker(args):
         # (ITW_BENCH_CPP_SHARE_DEVICES=1: ranks share devices, rank r on device r % count -- how the job is exercised on a 1-GPU box)
         raise SystemExit(f"cpp worker: {torch.cuda.device_count()} visible devices for {args.gpus} ranks")
     faulthandler.dump_traceback_later(int(os.environ.get("ITW_BENCH_CPP_TIMEOUT_S", "600")), exit=True)
-    res = cpp_job(itw_amd, fmt, prof, args.size, args.gpus, args.steps, args.warmup, scatter_steps=min(3, args.steps))
+    res = cpp_job(itw_amd, fmt, prof, args.size, args.gpus, args.steps, args.warmup, scatter_steps=min(3, args.steps) if args.full else 0)
     print(json.dumps(res), flush=True)
 
 
@@ -574,7 +600,7 @@ def run_cpp_child(args, world, size, steps, warmup):
            if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE", "GROUP_RANK", "GROUP_WORLD_SIZE", "ROLE_RANK", "ROLE_NAME",
                         "ROLE_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "OMP_NUM_THREADS") and not k.startswith("TORCHELASTIC_")}
     cmd = [sys.executable, os.path.abspath(__file__), "--cpp-worker", "--gpus", str(world), "--steps", str(steps), "--warmup", str(warmup),
-           "--workload", args.workload, "--size", str(size)]
+           "--workload", args.workload, "--size", str(size)] + (["--full"] if args.full else [])
     tmo = int(os.environ.get("ITW_BENCH_CPP_TIMEOUT_S", "600"))
     try:
         p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=tmo + 30)
@@ -653,6 +679,10 @@ def main():
                     help="default: strong when N > 1 (BASELINE configs[4]: one 16384^2 surface sharded over the ranks), else weak")
     ap.add_argument("--interleave", type=int, default=None, help="K sub-bands per rank of the strong-sharded job (content-aware partition, "
                     "include/itw_multigpu.h); default 4 where the surface's block rows divide by K * N, else 1")
+    ap.add_argument("--full", action="store_true", help="besides the headline: the N > 1 gather verification, the kernel-only leg and the "
+                    "roofline, formats, weak_side, cpu_baseline (off by default: a plain run times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the block stream of the last step "
+                    "as DIR/blocks.npy (float32; see dump_outputs)")
     ap.add_argument("--no-formats", action="store_true", help="skip the side measurements of the other formats")
     ap.add_argument("--no-16k", action="store_true", help="skip the 16384^2 BC1/BC3 side figures (tools/profile_gpu.sh: keeps the "
                     "per-kernel-name averages of rocprofv3 --stats those of the 4096^2 launches)")
@@ -764,48 +794,51 @@ def main():
     elapsed, geo, img, d_img, pipe = run_job(scaling, size, steps, warmup)
     d_band = pipe.band[0]
     nblocks = (geo["width"] // 4) * (geo["rows"] // 4)          # blocks this rank encodes per step (all its pieces)
+    if args.dump_outputs and rank == 0:
+        # N > 1: the whole image the last step's all-gather left on rank 0 (the C++ job, when it is the headline, is checked to give the same)
+        dump_outputs(args.dump_outputs, pipe.full[(pipe.steps - 1) % pipe.depth], fmt)
 
     # N > 1: is the gathered image the image?  (after the timed region; never inside it)
     verdict = None
-    if world > 1:
+    if world > 1 and args.full:
         verdict = verify_gather(itw_amd, dist, pipe.full[(pipe.steps - 1) % pipe.depth], scaling, size, world, rank, fmt, prof, dev, geo.get("pieces", 1))
 
-    # kernel-only duration on the launch stream (HIP events), for the roofline
-    k_avg_ms, k_min_ms = time_kernel(itw_amd, fmt, prof, d_img, d_band, steps=max(3, min(steps, 20)), warmup=1)
-    if geo.get("pieces", 1) > 1 and not FAKE:
-        # K sub-bands per rank: the rank's kernel time per step is the sum over its pieces (equal sizes; piece 0 measured above, the
-        # others re-derived from the same seeded surface here)
-        for k in range(1, geo["pieces"]):
-            gk = plan(scaling, size, world, rank, fmt, k, geo["pieces"])
-            dk = torch.from_numpy(make_band(fmt, scaling, size, gk, rank)).to(dev)
-            a, m = time_kernel(itw_amd, fmt, prof, dk, d_band, steps=max(3, min(steps, 20)), warmup=1)
-            k_avg_ms += a; k_min_ms += m
-            del dk
-    elif geo.get("pieces", 1) > 1:
-        k_avg_ms *= geo["pieces"]; k_min_ms *= geo["pieces"]
-    per_rank_ms = [round(k_avg_ms, 4)]
-    per_rank_gather_ms = None
-    if dist is not None:
-        # the gathers of one step on their own (nothing encoding): this rank's K in-place all-gathers, wall clock between synchronisations
-        dist.barrier()
-        _sync()
-        tg = time.perf_counter()
-        for k in range(pipe.pieces):
-            dist.all_gather_into_tensor(pipe.groups[0][k], pipe.piece[0][k])
-        _sync()
-        gather_ms = (time.perf_counter() - tg) * 1e3
-        t = torch.zeros(2 * world, dtype=torch.float64, device=dev)
-        t[rank] = k_avg_ms
-        t[world + rank] = gather_ms
-        dist.all_reduce(t, op=dist.ReduceOp.SUM)
-        per_rank_ms = [round(float(v), 4) for v in t[:world].tolist()]
-        per_rank_gather_ms = [round(float(v), 4) for v in t[world:].tolist()]
+    # --full: kernel-only duration on the launch stream (HIP events), for the roofline
+    k_avg_ms = k_min_ms = per_rank_ms = per_rank_gather_ms = None
+    if args.full:
+        k_avg_ms, k_min_ms = time_kernel(itw_amd, fmt, prof, d_img, d_band, steps=max(3, min(steps, 20)), warmup=1)
+        if geo.get("pieces", 1) > 1 and not FAKE:
+            # K sub-bands per rank: the rank's kernel time per step is the sum over its pieces (equal sizes; piece 0 measured above, the
+            # others re-derived from the same seeded surface here)
+            for k in range(1, geo["pieces"]):
+                gk = plan(scaling, size, world, rank, fmt, k, geo["pieces"])
+                dk = torch.from_numpy(make_band(fmt, scaling, size, gk, rank)).to(dev)
+                a, m = time_kernel(itw_amd, fmt, prof, dk, d_band, steps=max(3, min(steps, 20)), warmup=1)
+                k_avg_ms += a; k_min_ms += m
+                del dk
+        elif geo.get("pieces", 1) > 1:
+            k_avg_ms *= geo["pieces"]; k_min_ms *= geo["pieces"]
+        per_rank_ms = [round(k_avg_ms, 4)]
+        if dist is not None:
+            # the gathers of one step on their own (nothing encoding): this rank's K in-place all-gathers, wall clock between synchronisations
+            dist.barrier()
+            _sync()
+            tg = time.perf_counter()
+            for k in range(pipe.pieces):
+                dist.all_gather_into_tensor(pipe.groups[0][k], pipe.piece[0][k])
+            _sync()
+            gather_ms = (time.perf_counter() - tg) * 1e3
+            t = torch.zeros(2 * world, dtype=torch.float64, device=dev)
+            t[rank] = k_avg_ms
+            t[world + rank] = gather_ms
+            dist.all_reduce(t, op=dist.ReduceOp.SUM)
+            per_rank_ms = [round(float(v), 4) for v in t[:world].tolist()]
+            per_rank_gather_ms = [round(float(v), 4) for v in t[world:].tolist()]
 
     result = None
     if rank == 0:
         pixels = geo["width"] * geo["height"]                  # the whole job per step, all ranks
         alg = ALG_BYTES[fmt] * nblocks
-        achieved = alg / (k_avg_ms * 1e-3) / 1e9
         result = {
             "metric": "Mpixels/s encode (BC1/BC3/BC7/BC6H) at 4k x 4k; bit-exact vs the oracle under the pinned ISPC sse/avx-target "
                       "arithmetic model (no ispc binary exists here; sensitivity of that model: profiles/arith_sensitivity.txt)",
@@ -828,14 +861,16 @@ def main():
                                           "(modes 1/3 last, only where their exact lower bound allows) or the reference's for the rest of the call; two interleaved bands on two "
                                           "streams; same bytes either way; the time is content dependent: formats[*@baboon_tiled] is the natural-image end") if fmt == "bc7" else None,
                        "device": ("CONTROL-FLOW TEST ON CPU -- not a measurement" if FAKE else itw_amd.device_info()), "lib": itw_amd.version()},
-            "roofline": {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 5), "hbm_frac": round(achieved / HBM_PEAK_GBS, 5),
-                         "traffic": pmc_traffic(args.workload, cur_sha) if (world == 1 and size == 4096) else None,   # PMC passes were taken at 4096^2
-                         "kernel_ms_avg": round(k_avg_ms, 4), "kernel_ms_min": round(k_min_ms, 4),
-                         "algorithmic_bytes_per_launch": alg,
-                         "note": "BC7/BC6H are VALU-issue bound (no MFMA-shaped work); the HBM fraction is reported "
-                                 "because the contract asks for it; `valu` is the roofline that binds (DESIGN.md 3)"},
         }
+    if rank == 0 and args.full:
+        achieved = alg / (k_avg_ms * 1e-3) / 1e9
+        result["roofline"] = {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                              "frac": round(achieved / HBM_PEAK_GBS, 5), "hbm_frac": round(achieved / HBM_PEAK_GBS, 5),
+                              "traffic": pmc_traffic(args.workload, cur_sha) if (world == 1 and size == 4096) else None,   # PMC passes were taken at 4096^2
+                              "kernel_ms_avg": round(k_avg_ms, 4), "kernel_ms_min": round(k_min_ms, 4),
+                              "algorithmic_bytes_per_launch": alg,
+                              "note": "BC7/BC6H are VALU-issue bound (no MFMA-shaped work); the HBM fraction is reported "
+                                      "because the contract asks for it; `valu` is the roofline that binds (DESIGN.md 3)"}
         if verdict is not None:
             result.update(verdict)
             result["per_rank_kernel_ms"] = per_rank_ms
@@ -890,7 +925,7 @@ def main():
         else:
             insts = None
 
-    if rank == 0:
+    if rank == 0 and args.full:
         per_block, method = op_counts(args.workload)
         if per_block:
             # algorithmic roofline: the reference's own fp32 work (measured on the oracle) over this GPU's time
@@ -913,7 +948,7 @@ def main():
                 va["reference_ops_per_executed_lane_op"] = round(full * blocks_all / (insts * 64), 3)
             result["roofline"]["valu_algorithmic"] = va
 
-    if world > 1 and scaling == "strong":
+    if world > 1 and scaling == "strong" and args.full:
         # side figure: weak scaling, one 4096^2 band per rank (what round 1 reported); a few steps only
         del d_img, pipe
         if not FAKE:
@@ -968,7 +1003,7 @@ def main():
                 result["config"]["host"] = python_side["host"]
 
     size_side = 4096
-    if rank == 0 and world == 1 and not args.no_formats and size == 4096:
+    if rank == 0 and world == 1 and not args.no_formats and size == 4096 and args.full:
         size, nblocks = size_side, (size_side // 4) ** 2
         side = {}
         # the presets IntelPlugin.cpp:832-843 selects (veryfast / basic / alpha_veryfast / alpha_basic, BC6H fast / slow) ride along with the slow ones
@@ -1198,10 +1233,8 @@ def main():
                         side[wl]["cpu_baseline"] = {"error": repr(e)}
         result["formats"] = side
 
-    if rank == 0 and world == 1 and not args.no_cpu:
-        result["cpu_baseline"] = cpu_baseline(fmt, prof, img)
-    elif rank == 0:
-        result["cpu_baseline"] = None
+    if rank == 0 and args.full:
+        result["cpu_baseline"] = cpu_baseline(fmt, prof, img) if (world == 1 and not args.no_cpu) else None
 
     if rank == 0:
         result["abi_calls"] = ABI_CALLS[0]      # encode calls of this process (headline legs; tools/summarize_profiles.py normalises profiler counters by it)

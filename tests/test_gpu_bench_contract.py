@@ -1,7 +1,8 @@
 """The driver's contract with bench.py, on the GPU: `python bench.py --gpus 1 --steps K --warmup W` prints ONE JSON line with the
 keys the driver and the judge read (metric / value / unit / n_gpus / steps / warmup / ms_per_step / higher_is_better / scaling /
-vs_baseline / dtype / data / config.workload, a `roofline` object for the dominant kernel and a `cpu_baseline` object), K steps
-were timed, and the numbers are consistent with each other."""
+vs_baseline / dtype / data / config.workload), K steps were timed and nothing else ran, and --dump-outputs writes the stream of the
+last step; with --full the line also has a `roofline` object for the dominant kernel and a `cpu_baseline` object, and the numbers
+are consistent with each other."""
 import json
 import os
 import subprocess
@@ -14,7 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_one_json_line_with_the_contract_keys(gpu):
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--no-formats"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--no-formats", "--full"],
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -57,3 +58,31 @@ def test_one_json_line_with_the_contract_keys(gpu):
     for k in ("value", "unit", "cores", "kind", "sample"):
         assert k in cb, k
     assert cb["kind"] in ("reference", "port") and cb["cores"] >= 1 and cb["value"] > 0
+
+
+def test_plain_run_times_the_steps_and_dumps_the_last_one(itw, gpu, tmp_path):
+    """A plain run is lean: the headline keys, exactly K timed steps after W warm-up steps and no other encode call (abi_calls), none of
+    the --full figures; --dump-outputs holds the whole 4096^2 BC7 `slow` stream of the last step (float32 16-bit words), which is what
+    the library gives for the same seeded surface in this process."""
+    import numpy as np
+    import torch
+    import bench
+    d = str(tmp_path / "dump")
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--dump-outputs", d],
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    j = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "n_gpus", "steps", "warmup", "config"):
+        assert k in j, k
+    assert j["steps"] == 4 and j["warmup"] == 2 and j["abi_calls"] == 4 + 2 and j["unit"] == "Mpixels/s" and j["higher_is_better"] is True
+    assert "4096x4096" in j["config"]["workload"] and "BC7 GetProfile_slow" in j["config"]["workload"]
+    assert abs(j["value"] - 4096 * 4096 / (j["ms_per_step"] * 1e-3) / 1e6) / j["value"] < 1e-3
+    assert not {"roofline", "formats", "cpu_baseline"} & set(j), sorted(j)
+    a = np.load(os.path.join(d, "blocks.npy"))
+    assert a.dtype == np.float32 and a.shape == ((4096 // 4) ** 2, 8) and not os.path.exists(os.path.join(d, "block_index.npy"))
+    got = np.ascontiguousarray(a.astype("<u2")).view(np.uint8).reshape(-1)
+    want = itw.compress("bc7", torch.from_numpy(bench.make_surface("bc7", 4096, 0)).to(gpu), "slow")
+    torch.cuda.synchronize()
+    assert np.array_equal(got, want.cpu().numpy().reshape(-1))

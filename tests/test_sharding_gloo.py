@@ -196,7 +196,7 @@ def test_band_rule_keeps_partial_blocks_for_bc4_bc5(fmt, h, w, parts):
     assert covered == whole.size and np.array_equal(got, whole)
 
 
-def _run_bench_world2(extra_env, extra_args=()):
+def _run_bench_world2(extra_env, extra_args=(), full=True):
     import subprocess
     port = _free_port()
     procs = []
@@ -204,7 +204,8 @@ def _run_bench_world2(extra_env, extra_args=()):
         env = dict(os.environ, ITW_BENCH_CONTROL_FLOW_TEST="1", RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE="2",
                    MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), ITW_BENCH_DIST_TIMEOUT_S="120", **extra_env)
         procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                                       "--size", "512", "--no-formats", "--no-cpu", *extra_args], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
+                                       "--size", "512", "--no-formats", "--no-cpu", *(["--full"] if full else []), *extra_args],
+                                      env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
     outs = [p.communicate(timeout=600) for p in procs]
     assert all(p.returncode == 0 for p in procs), [o[1][-1500:] for o in outs]
     return outs
@@ -251,7 +252,7 @@ def test_bench_n_gt_1_control_flow_runs_end_to_end_on_cpu():
         env = dict(os.environ, ITW_BENCH_CONTROL_FLOW_TEST="1", RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE="2",
                    MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
         procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                                       "--size", "512", "--no-formats", "--no-cpu"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
+                                       "--size", "512", "--no-formats", "--no-cpu", "--full"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
     outs = [p.communicate(timeout=600) for p in procs]
     assert all(p.returncode == 0 for p in procs), [o[1][-1500:] for o in outs]
     line = [l for l in outs[0][0].splitlines() if l.startswith("{")][-1]
@@ -285,6 +286,63 @@ def test_bench_n_gt_1_cpp_host_job_control_flow(child):
     else:
         assert j["config"]["host"].startswith("python") and j["value"] == j["python_side"]["value"] and "note" in j["cpp_host"]
         assert ("error" in j["cpp_host"]) == (child == "crash")
+    assert not [l for l in outs[1][0].splitlines() if l.startswith("{")]
+
+
+def _fake_stream(fmt, size):
+    """What the control-flow test's stand-in encoder gives for the whole seeded surface, one row per block."""
+    import bench
+    from itw_amd import abi
+    return bench.fake_blocks(fmt, bench.make_surface(fmt, size, 0)).reshape(-1, abi.BYTES_PER_BLOCK[fmt])
+
+
+def _dumped_stream(d):
+    """--dump-outputs DIR read back as the block stream's bytes (float32 16-bit words -> uint8, one row per block)."""
+    a = np.load(os.path.join(d, "blocks.npy"))
+    assert a.dtype == np.float32 and not os.path.exists(os.path.join(d, "block_index.npy"))
+    assert np.array_equal(a, np.round(a)) and a.min() >= 0 and a.max() < 1 << 16
+    return np.ascontiguousarray(a.astype("<u2")).view(np.uint8)
+
+
+def _bench_line(stdout):
+    import json
+    lines = [l for l in stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    return json.loads(lines[0])
+
+
+def test_bench_plain_run_times_the_steps_and_dumps_the_last_one(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` (stand-in encoder on CPU): the headline keys, exactly K timed steps, nothing
+    else measured (no kernel-only leg, roofline, formats or CPU baseline: those are --full), and --dump-outputs writes the stream of
+    the last step -- the same file on a second run with the same arguments."""
+    import subprocess
+    env = dict(os.environ, ITW_BENCH_CONTROL_FLOW_TEST="1")
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
+        env.pop(k, None)
+    dumps = []
+    for run in range(2):
+        d = str(tmp_path / f"run{run}")
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--size", "256",
+                            "--dump-outputs", d], env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-1500:]
+        j = _bench_line(r.stdout)
+        for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert k in j, k
+        assert j["steps"] == 4 and j["warmup"] == 2 and j["unit"] == "Mpixels/s" and j["higher_is_better"] is True and j["dtype"] == "f32"
+        assert abs(j["value"] - 256 * 256 / (j["ms_per_step"] * 1e-3) / 1e6) / j["value"] < 1e-2
+        assert not {"roofline", "formats", "cpu_baseline", "weak_side"} & set(j), sorted(j)
+        dumps.append(_dumped_stream(d))
+    assert np.array_equal(dumps[0], _fake_stream("bc7", 256)) and np.array_equal(dumps[0], dumps[1])
+
+
+def test_bench_plain_n_gt_1_dumps_the_gathered_image(tmp_path):
+    """N = 2 (gloo, stand-in encoder), plain run: rank 0 writes the whole image the last step's all-gather left it -- every rank's
+    sub-bands in stream order -- and the side figures of --full are absent."""
+    d = str(tmp_path / "dump")
+    outs = _run_bench_world2({}, ("--dump-outputs", d), full=False)
+    j = _bench_line("\n".join(l for l in outs[0][0].splitlines() if l.startswith("{")))      # (gloo prints its own lines)
+    assert j["n_gpus"] == 2 and j["steps"] == 2 and "weak_side" not in j and "gather_verified" not in j
+    assert np.array_equal(_dumped_stream(d), _fake_stream("bc7", 512))
     assert not [l for l in outs[1][0].splitlines() if l.startswith("{")]
 
 

@@ -4,7 +4,7 @@
 #     tests    pytest -m gpu (whole suite), parity campaigns, settings fuzz                    -> gpurun_out/evidence_<tag>/{pytest_gpu.log, parity_*, gpu_settings_fuzz_*}
 #     tables   preset table, variant table, launch-shape probe, host-pointer calls, the plugin's slice loop (pipeline / literal / one call),
 #              the reference's own win32Threads.cpp driving the library, mode-order policy by content, one call's kernel timeline
-#     bench    python bench.py (default flags) and the 16384^2 geometry on one GPU
+#     bench    python bench.py --full (every side figure) and the 16384^2 geometry on one GPU
 #     profile  tools/profile_gpu.sh <tag>: rocprofv3 kernel stats, PMC traffic, SQ counters (every plugin preset included)
 #     long     the long campaigns: 16 Mpix of every format and preset, 64 Mpix per BC7 slow profile (4 M blocks per call), 1 200 + 1 200 random
 #              settings structs, and a second seed of the 4 Mpix campaign against the reference's own kernel source
@@ -49,8 +49,8 @@ tables)
     done )
   ;;
 bench)
-  timeout 1200 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err; tail -c 400 $OUT/bench_default.json
-  timeout 900 python bench.py --size 16384 --scaling strong --steps 5 --warmup 1 --no-formats --no-cpu > $OUT/bench_16384_strong_n1.json 2>> $OUT/bench_default.err
+  timeout 1200 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err; tail -c 400 $OUT/bench_default.json
+  timeout 900 python bench.py --size 16384 --scaling strong --steps 5 --warmup 1 --no-formats --no-cpu --full > $OUT/bench_16384_strong_n1.json 2>> $OUT/bench_default.err
   ;;
 profile)
   bash tools/profile_gpu.sh $TAG > gpurun_out/profile_gpu_$TAG.log 2>&1; tail -3 gpurun_out/profile_gpu_$TAG.log
