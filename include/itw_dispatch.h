@@ -111,6 +111,42 @@ int  itwSliceWindow(int dxgi_format, int width, int height, int64_t slice_pixels
  * twice the work per block) take windows twice as large; itwSliceWindow is this with NULL (every preset the plugin selects). */
 int  itwSliceWindowFor(int dxgi_format, const void* settings, int width, int height, int64_t slice_pixels);
 
+/* A whole mip chain, cube map or texture array in one call (IntelPlugin.cpp:229-255 makes one pad + CompressImageMT / DirectX::Compress call
+ * per image of the ScratchImage).
+ *
+ * itwChainBytes: bytes the chain encodes to: the sum over images of ceil(w/4)*ceil(h/4)*GetBytesPerBlock(fmt) (== itwDdsLevelBytes per image).
+ * -1 on bad arguments.  Host-only arithmetic, no device needed.
+ *
+ * itwCompressImageChain[Ex]: encodes `count` images (mip levels, cube faces, array items, in the caller's order) into `target`, one after
+ * another, tightly packed: image i starts at the sum of the sizes of images < i -- for a DirectXTex ScratchImage (array item, face, mip:
+ * DDS order) that is exactly imgCompressed[0].pixels and a DDS payload.  Same bytes as, for each image in order, the plugin's
+ * DoPaddingToMultiplesOf4 + CompressImageMT (ISPC formats) or DirectX::Compress (BC4/BC5: partial blocks kept).
+ *   * Formats: the ten DXGI values above (71, 72, 77, 78, 80, 83, 95, 96, 98, 99).  `settings` as in itwCompressImageSlicedEx:
+ *     bc7_enc_settings* (BC7), bc6h_enc_settings* (BC6H), ignored otherwise.
+ *   * Pixels: RGBA8, or RGBA16F for BC6H.
+ *   * Images: any width and height >= 1, any `stride` >= the row's bytes.  Sizes that are not multiples of 4 are padded as the plugin pads
+ *     them: edge replication for BC1, BC3, BC6H and BC7 (itwPadToMultipleOf4's rule), DirectXTex's partial-block fill for BC4 and BC5
+ *     (CompressBlocksBC4/5's rule).
+ *   * Pointers: all images host pointers, or all device pointers of the calling thread's current device; mixing them is an error.
+ *     `target` may be either kind.  Synchronous either way, like itwCompressImageSliced.
+ *   * One device: the calling thread's current device (a chain is not spread over several GPUs).
+ *   * Progress: progress(i, count, user) is called for i = 1 .. count, in order, each call only once every image < i is in `target`.  A false
+ *     return stops the job and the call returns false: images < i stay written, and so may images of work already in flight (as with the
+ *     slice pipeline's windows).  `progress` runs on the calling thread while later work is in flight: it must not call back into this library.
+ *   * Errors: count <= 0, a null pointer (images, target, an image's texels, null BC7 / BC6H settings), a width or height < 1, a stride below
+ *     the row's bytes, an unknown format, or mixed pointer kinds fail the call through the library's error mode before any device work
+ *     starts; under ITW_ON_ERROR_RETURN it returns false and itwLastError() holds the message.
+ *   * itwCompressImageChain with one of THIS library's CompressImage* trampolines resolves to the same path as the Ex call with the
+ *     trampoline's preset; any other `cmpFunc` gets the plugin's literal loop: pad (host; device images on the device), then `cmpFunc`, per image.
+ * How: consecutive images are gathered into groups of up to a slice-pipeline window of blocks (itwSliceWindowFor's ~131 072 / 262 144), each
+ * group packed into one surface on the device and encoded as one; the groups run as the windows of itwCompressImageSliced do.  An image of
+ * at least a window whose width and height are multiples of 4 is encoded in place as one whole-surface call. */
+int64_t itwChainBytes(const rgba_surface* images, int count, int dxgi_format);
+bool itwCompressImageChain(const rgba_surface* images, int count, uint8_t* target, CompressionFunc* cmpFunc,
+                           int dxgi_format, ItwProgressFunc* progress, void* user);
+bool itwCompressImageChainEx(const rgba_surface* images, int count, uint8_t* target, int dxgi_format,
+                             const void* settings, ItwProgressFunc* progress, void* user);
+
 /* Pad to multiples of 4 by edge replication (IntelPlugin.cpp:893-928): the step immediately before the ABI.
  * pixel_size = 4 (RGBA8) or 8 (RGBA16F).  Host version: returns a surface whose ptr was allocated with malloc()
  * (free with itwFreeSurface); the reference allocates with new[] and leaves ownership to the caller likewise.

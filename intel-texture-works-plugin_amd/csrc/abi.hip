@@ -755,6 +755,238 @@ int slices_of(const rgba_surface* s, int64_t slice_pixels)
     return (int)slices;
 }
 
+// ---- a whole mip chain / cube map in one call (include/itw_dispatch.h: itwCompressImageChainEx) -----------------------------------
+// IntelPlugin.cpp:229-255 pads and encodes every image of a ScratchImage -- each mip level of each face -- with its own call: upload, a
+// latency-bound launch chain over a few thousand blocks, download, synchronise (66 of them for a 1024^2 cube map with mips).  Here the
+// images are cut into GROUPS of consecutive images of up to a window's worth of blocks (slice_window's target), each group is gathered
+// into one packed surface (chain.hip) and encoded as one surface, and the groups run as the slice pipeline's windows do: group k's
+// kernels on kernel stream k % 2, its upload and the previous group's download on the copy stream.  An image of a window or more whose
+// size is a multiple of 4 needs no gather: it is encoded in place through the whole-surface path (compress() / launch()).
+constexpr int kChainPackedBlocks = 1024;              // P: blocks per packed row (the tail of the last row is encoded into scratch and dropped)
+
+int64_t chain_image_blocks(const rgba_surface& s) { return (int64_t)((s.width + 3) / 4) * ((s.height + 3) / 4); }
+
+int64_t chain_budget(const Job& j)                    // slice_window's target: ~131 072 blocks, 262 144 for BC1/3/4/5 and the heavy BC7 settings
+{
+    return ((j.fmt == Fmt::BC7 && !heavy_job(j)) || j.fmt == Fmt::BC6H) ? 131072 : 262144;
+}
+
+// everything a bad call can be told by before any device is touched (the pointer kinds come after this)
+Job chain_job(const rgba_surface* images, int count, const uint8_t* target, int dxgi_format, const void* settings)
+{
+    if (count <= 0) itw::fail_msg("itwCompressImageChain: %d images", count);
+    if (!images || !target) itw::fail_msg("itwCompressImageChain: null images or target pointer");
+    const Job j = job_of(dxgi_format, settings);
+    const int px = j.fmt == Fmt::BC6H ? 8 : 4;
+    for (int i = 0; i < count; i++) {
+        const rgba_surface& s = images[i];
+        if (!s.ptr) itw::fail_msg("itwCompressImageChain: image %d has a null texel pointer", i);
+        if (s.width < 1 || s.height < 1) itw::fail_msg("itwCompressImageChain: image %d is %d x %d", i, s.width, s.height);
+        if ((int64_t)s.stride < (int64_t)s.width * px) itw::fail_msg("itwCompressImageChain: image %d: stride %d < %d bytes per row", i, s.stride, s.width * px);
+    }
+    return j;
+}
+
+struct ChainUnit { int i0, i1; int64_t b0, nb; bool in_place; };   // images [i0, i1), blocks [b0, b0 + nb) of the chain
+
+// The gather groups units[u0, u1) of a chain whose pointer kinds are known, pipelined; `poll(i0, i1)` reports images [i0, i1) as written.
+template <class Poll>
+bool chain_groups(const Job& j, const rgba_surface* im, uint8_t* target, const std::vector<ChainUnit>& units, size_t u0, size_t u1,
+                  bool src_dev, bool dst_dev, Poll&& poll)
+{
+    const int px = j.fmt == Fmt::BC6H ? 8 : 4;
+    const int bpb = (j.fmt == Fmt::BC1 || j.fmt == Fmt::BC4) ? 8 : 16;
+    const bool fill45 = j.fmt == Fmt::BC4 || j.fmt == Fmt::BC5;
+    const int ngroups = (int)(u1 - u0);
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+
+    // layout: d_in = [staged texels (host images)] [packed surfaces] [descriptors], d_out = [encoded packed surfaces]
+    struct Group { int i0, i1; int64_t b0, nb; int pbx, pby; size_t packed_off, out_off; };
+    std::vector<Group> gs((size_t)ngroups);
+    std::vector<size_t> stage_off;
+    size_t in_bytes = 0, out_bytes = 0;
+    if (!src_dev) {
+        stage_off.resize((size_t)(units[u1 - 1].i1 - units[u0].i0));
+        for (int i = units[u0].i0; i < units[u1 - 1].i1; i++) {
+            stage_off[(size_t)(i - units[u0].i0)] = in_bytes;
+            in_bytes += up((((size_t)im[i].width * px + 15) & ~(size_t)15) * (size_t)im[i].height);
+        }
+    }
+    int tallest = 0, widest = 0;
+    for (int g = 0; g < ngroups; g++) {
+        const ChainUnit& u = units[u0 + (size_t)g];
+        Group& G = gs[(size_t)g];
+        G.i0 = u.i0; G.i1 = u.i1; G.b0 = u.b0; G.nb = u.nb;
+        G.pbx = (int)std::min<int64_t>(kChainPackedBlocks, u.nb);
+        G.pby = (int)((u.nb + G.pbx - 1) / G.pbx);
+        G.packed_off = in_bytes;
+        in_bytes += up((size_t)G.pby * 4 * ((size_t)G.pbx * 4 * px));
+        G.out_off = out_bytes;
+        out_bytes += up((size_t)G.pby * G.pbx * bpb);
+        if (G.pby > tallest || (G.pby == tallest && G.pbx > widest)) { tallest = G.pby; widest = G.pbx; }
+    }
+    const size_t desc_off = in_bytes;
+    const int nimg = units[u1 - 1].i1 - units[u0].i0;
+    in_bytes += (size_t)nimg * sizeof(itw::ChainImage);
+
+    ensure_device_ctx();
+    ensure_bc7_aux();
+    hipStream_t k0 = tls.own_stream, k1 = tls.aux.stream, cs = tls.copy_stream;
+    // whatever produced device images (or still reads the destination) on the caller's stream comes first
+    if ((src_dev || dst_dev) && tls.user_stream != k0) ITW_CHECK(hipStreamSynchronize(tls.user_stream));
+    uint8_t* d_in = (uint8_t*)grow(tls.d_in, tls.in_cap, in_bytes);
+    uint8_t* d_out = (uint8_t*)grow(tls.d_out, tls.out_cap, out_bytes);
+
+    // one lone group runs the ordinary call (launch shape by size, the second stream for its own parallel parts); several alternate
+    // between the two kernel streams, each BC7 group in its own slice of the workspace (deep shape), like the slice pipeline's windows
+    const bool lone = ngroups == 1;
+    size_t ws_off[2] = {0, 0};
+    if (j.fmt == Fmt::BC7 && !lone) {
+        const size_t b = (itw::bc7_workspace_bytes(widest * 4, tallest * 4, 1, j.s7) + 255) & ~(size_t)255;
+        ws_off[1] = b;
+        reserve_workspace(2 * b, k0);
+    }
+    // the descriptor table, one copy for every group, ahead of both kernel streams
+    std::vector<itw::ChainImage> desc((size_t)nimg);
+    for (int g = 0; g < ngroups; g++) {
+        const Group& G = gs[(size_t)g];
+        int64_t first = 0;
+        for (int i = G.i0; i < G.i1; i++) {
+            itw::ChainImage& d = desc[(size_t)(i - units[u0].i0)];
+            d.ptr = src_dev ? im[i].ptr : d_in + stage_off[(size_t)(i - units[u0].i0)];
+            d.stride = src_dev ? (int64_t)im[i].stride : (int64_t)(((size_t)im[i].width * px + 15) & ~(size_t)15);
+            d.width = im[i].width; d.height = im[i].height;
+            d.first_block = first;
+            first += chain_image_blocks(im[i]);
+        }
+    }
+    ITW_CHECK(hipMemcpyAsync(d_in + desc_off, desc.data(), desc.size() * sizeof(itw::ChainImage), hipMemcpyHostToDevice, k0));
+    ITW_CHECK(hipEventRecord(tls.aux.fork, k0));          // the second stream starts behind the table and whatever ordered the workspace
+    ITW_CHECK(hipStreamWaitEvent(k1, tls.aux.fork, 0));
+
+    // However this ends, nothing of this call is left in flight on the thread's streams and buffers (a failure is a C++ exception here)
+    struct Drain {
+        hipStream_t a, b, c; bool bc7;
+        ~Drain() {
+            (void)hipStreamSynchronize(a); (void)hipStreamSynchronize(b); (void)hipStreamSynchronize(c);
+            if (bc7 && tls.ws_event) (void)hipEventRecord(tls.ws_event, a);
+            (void)hipGetLastError();
+        }
+    } drain{k0, k1, cs, j.fmt == Fmt::BC7};
+
+    const itw::ChainImage* d_desc = reinterpret_cast<const itw::ChainImage*>(d_in + desc_off);
+    auto issue = [&](int g) {
+        const Group& G = gs[(size_t)g];
+        hipStream_t ks = (g & 1) ? k1 : k0;
+        if (!src_dev) {
+            for (int i = G.i0; i < G.i1; i++) {
+                const size_t row_bytes = (size_t)im[i].width * px;
+                upload_rows(d_in + stage_off[(size_t)(i - units[u0].i0)], (row_bytes + 15) & ~(size_t)15, im[i].ptr, im[i].stride, row_bytes,
+                            (size_t)im[i].height, cs);
+            }
+            ITW_CHECK(hipEventRecord(tls.ev_in[g & 7], cs));
+            ITW_CHECK(hipStreamWaitEvent(ks, tls.ev_in[g & 7], 0));
+        }
+        const int64_t pitch = (int64_t)G.pbx * 4 * px;
+        uint8_t* packed = d_in + G.packed_off;
+        itw::launch_chain_gather(d_desc + (G.i0 - units[u0].i0), G.i1 - G.i0, G.nb, G.pbx, G.pby, px, fill45, packed, pitch, ks);
+        if (lone) launch(j, packed, pitch, G.pbx * 4, G.pby * 4, d_out + G.out_off, ks, !src_dev && !dst_dev);
+        else      launch(j, packed, pitch, G.pbx * 4, G.pby * 4, d_out + G.out_off, ks, true, j.fmt == Fmt::BC7 ? 1 : -1, ws_off[g & 1]);
+        if (dst_dev) ITW_CHECK(hipMemcpyAsync(target + G.b0 * bpb, d_out + G.out_off, (size_t)G.nb * bpb, hipMemcpyDeviceToDevice, ks));
+        ITW_CHECK(hipEventRecord(tls.ev_done[g & 7], ks));
+    };
+    auto retire = [&](int g) {                               // the group's bytes into `target`; returns when they are there
+        const Group& G = gs[(size_t)g];
+        if (dst_dev) { ITW_CHECK(hipEventSynchronize(tls.ev_done[g & 7])); return; }
+        ITW_CHECK(hipStreamWaitEvent(cs, tls.ev_done[g & 7], 0));
+        ITW_CHECK(hipMemcpyAsync(target + G.b0 * bpb, d_out + G.out_off, (size_t)G.nb * bpb, hipMemcpyDeviceToHost, cs));
+        ITW_CHECK(hipStreamSynchronize(cs));
+    };
+    // two groups ahead of the one being retired, as the slice pipeline's windows (compress_sliced)
+    const int depth = 2;
+    for (int g = 0; g < depth && g < ngroups; g++) issue(g);
+    for (int g = 0; g < ngroups; g++) {
+        if (g + depth < ngroups) issue(g + depth);
+        retire(g);
+        if (!poll(gs[(size_t)g].i0, gs[(size_t)g].i1)) return false;   // the groups behind it are in flight: ~Drain waits for them
+    }
+    return true;
+}
+
+// `images` / `count` / `target` checked by chain_job.  Returns true when every image was encoded, false when `progress` stopped the job.
+bool compress_chain(const Job& j, const rgba_surface* im, int count, uint8_t* target, ItwProgressFunc* progress, void* user)
+{
+    const bool src_dev = is_device_pointer(im[0].ptr);
+    for (int i = 1; i < count; i++)
+        if (is_device_pointer(im[i].ptr) != src_dev)
+            itw::fail_msg("itwCompressImageChain: image %d is %s memory, image 0 %s: all images must be host or all device pointers", i,
+                          src_dev ? "host" : "device", src_dev ? "device" : "host");
+    if (src_dev) {
+        int cur = 0, dev = 0;
+        ITW_CHECK(hipGetDevice(&cur));
+        for (int i = 0; i < count; i++) {
+            hipPointerAttribute_t a;
+            std::memset(&a, 0, sizeof a);
+            ITW_CHECK(hipPointerGetAttributes(&a, im[i].ptr));
+            dev = a.device;
+            if (a.type == hipMemoryTypeDevice && dev != cur)
+                itw::fail_msg("itwCompressImageChain: image %d lives on device %d, the calling thread's current device is %d", i, dev, cur);
+        }
+    }
+    const bool dst_dev = is_device_pointer(target);
+    const int bpb = (j.fmt == Fmt::BC1 || j.fmt == Fmt::BC4) ? 8 : 16;
+
+    // units, in order: in-place images, and groups of consecutive images of up to `budget` blocks
+    const int64_t budget = chain_budget(j);
+    std::vector<ChainUnit> units;
+    int64_t off = 0;
+    bool open = false;
+    for (int i = 0; i < count; i++) {
+        const int64_t nb = chain_image_blocks(im[i]);
+        if (nb >= budget) {
+            const bool aligned = (im[i].width & 3) == 0 && (im[i].height & 3) == 0;
+            units.push_back(ChainUnit{i, i + 1, off, nb, aligned});            // in place, or (needs padding) a group of its own
+            open = false;
+        } else if (open && units.back().nb + nb <= budget) {
+            units.back().i1 = i + 1; units.back().nb += nb;
+        } else {
+            units.push_back(ChainUnit{i, i + 1, off, nb, false});
+            open = true;
+        }
+        off += nb;
+    }
+
+    bool stopped = false;
+    auto poll = [&](int i0, int i1) {                        // progress(i) once images < i are in `target`
+        for (int i = i0 + 1; i <= i1; i++)
+            if (progress && !progress(i, count, user)) { stopped = true; return false; }
+        return true;
+    };
+    size_t u = 0;
+    while (u < units.size()) {
+        const ChainUnit& U = units[u];
+        if (U.in_place) {
+            const rgba_surface& s = im[U.i0];
+            uint8_t* dst = target + U.b0 * bpb;
+            if (src_dev && dst_dev) {
+                ITW_CHECK(hipStreamSynchronize(tls.user_stream));
+                launch(j, s.ptr, s.stride, s.width, s.height, dst, tls.user_stream);
+                ITW_CHECK(hipStreamSynchronize(tls.user_stream));
+            } else {
+                compress(j, &s, dst, false);               // host pointers: compress()'s windows (synchronous)
+            }
+            if (!poll(U.i0, U.i1)) return false;
+            u++;
+            continue;
+        }
+        size_t v = u;
+        while (v < units.size() && !units[v].in_place) v++;
+        if (!chain_groups(j, im, target, units, u, v, src_dev, dst_dev, poll) || stopped) return false;
+        u = v;
+    }
+    return true;
+}
+
 // ---- joining concurrent small calls ----------------------------------------------------------------------------------
 // The reference's dispatch layer cuts every 0x40000-pixel slice into one band per pool thread and calls the ABI from all
 // of them at once (win32Threads.cpp:211-249: 64 threads -> 64 calls of 8 texel rows at 4096 wide).  Each such call alone
@@ -1019,6 +1251,12 @@ bool sliced_part(const rgba_surface* source, uint8_t* target, int dxgi_format, c
     return ok && done;
 }
 
+void chain_check(const rgba_surface* images, int count, const uint8_t* target, int dxgi_format)
+{
+    alignas(16) static const unsigned char any_settings[sizeof(bc7_enc_settings)] = {0};      // (the caller's own function takes none)
+    (void)chain_job(images, count, target, dxgi_format, any_settings);
+}
+
 int sliced_windows(int dxgi_format, const void* settings, int width, int height, int64_t slice_pixels, int* window_slices)
 {
     const int W = itwSliceWindowFor(dxgi_format, settings, width, height, slice_pixels);
@@ -1095,6 +1333,18 @@ bool itwCompressImageSlicedEx(const rgba_surface* source, uint8_t* target, int64
         const int64_t tight = (int64_t)(keep ? (source->width + 3) / 4 : source->width / 4) * ((j.fmt == Fmt::BC1 || j.fmt == Fmt::BC4) ? 8 : 16);
         if (block_row_pitch != tight) itw::fail_msg("itwCompressImageSlicedEx: block_row_pitch %lld != %lld (tight)", (long long)block_row_pitch, (long long)tight);
         done = compress_sliced(j, source, target, slices_of(source, slice_pixels), progress, user);
+    });
+    return ok && done;
+}
+
+bool itwCompressImageChainEx(const rgba_surface* images, int count, uint8_t* target, int dxgi_format, const void* settings,
+                             ItwProgressFunc* progress, void* user)
+{
+    bool done = false;
+    itw::clear_failure();
+    const bool ok = itw::guarded([&] {
+        const Job j = chain_job(images, count, target, dxgi_format, settings);
+        done = compress_chain(j, images, count, target, progress, user);
     });
     return ok && done;
 }

@@ -278,8 +278,7 @@ __device__ __forceinline__ uint2 encode_channel(const uint32_t (&P)[8], const St
 #endif
 
 // The sixteen texel words of channel-block `lane` (4 x dwordx4 when VEC16 and the block is whole).  Partial blocks: missing columns /
-// rows repeat source column / row {0,0,0,1}[i], itself wrapped to 0 when that one is missing too (DirectXTexCompress.cpp:140-168
-// applied in its own order).
+// rows repeat source column / row {0,0,0,1}[i], itself wrapped to 0 when that one is missing too (bc45_fill_index, kernels.hpp).
 template <int NCH, bool VEC16>
 __device__ __forceinline__ void load_words45(uint32_t (&w)[16], const uint8_t* __restrict__ src, int64_t stride, int32_t width, int32_t height,
                                              int32_t blocks_x, int32_t lane)
@@ -302,12 +301,10 @@ __device__ __forceinline__ void load_words45(uint32_t (&w)[16], const uint8_t* _
     } else {
 #pragma unroll
         for (int y = 0; y < 4; y++) {
-            int sy = y < ph ? y : (y == 3 ? 1 : 0);
-            if (sy >= ph) sy = 0;
+            const int sy = bc45_fill_index(y, ph);
 #pragma unroll
             for (int x = 0; x < 4; x++) {
-                int sx = x < pw ? x : (x == 3 ? 1 : 0);
-                if (sx >= pw) sx = 0;
+                const int sx = bc45_fill_index(x, pw);
                 w[4 * y + x] = *reinterpret_cast<const uint32_t*>(p + sy * stride + sx * 4);
             }
         }

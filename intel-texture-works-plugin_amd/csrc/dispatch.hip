@@ -8,6 +8,7 @@
 // stages and encodes its own band concurrently (H2D/D2H of different devices overlap on their own PCIe links);
 // a device-resident surface is encoded by the device that owns it, in one call.
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
@@ -385,6 +386,78 @@ bool itwCompressImageSliced(const rgba_surface* source, uint8_t* target, int64_t
         }
     }
     return true;
+}
+
+int64_t itwChainBytes(const rgba_surface* images, int count, int dxgi_format)
+{
+    switch (dxgi_format) {
+    case ITW_DXGI_FORMAT_BC1_UNORM: case ITW_DXGI_FORMAT_BC1_UNORM_SRGB: case ITW_DXGI_FORMAT_BC3_UNORM: case ITW_DXGI_FORMAT_BC3_UNORM_SRGB:
+    case ITW_DXGI_FORMAT_BC4_UNORM: case ITW_DXGI_FORMAT_BC5_UNORM: case ITW_DXGI_FORMAT_BC6H_UF16: case ITW_DXGI_FORMAT_BC6H_SF16:
+    case ITW_DXGI_FORMAT_BC7_UNORM: case ITW_DXGI_FORMAT_BC7_UNORM_SRGB: break;
+    default: return -1;
+    }
+    if (!images || count <= 0) return -1;
+    int64_t total = 0;
+    for (int i = 0; i < count; i++) {
+        if (images[i].width < 1 || images[i].height < 1) return -1;
+        total += (int64_t)((images[i].width + 3) / 4) * ((images[i].height + 3) / 4) * GetBytesPerBlock(dxgi_format);
+    }
+    return total;
+}
+
+// The library's own trampolines resolve to the one-call chain (abi.hip, compress_chain).  Any other function gets IntelPlugin.cpp:229-255
+// literally: per image, DoPaddingToMultiplesOf4 (ISPC formats whose size is not a multiple of 4; the device images of such a call are padded on
+// the device into a scratch buffer), then the function on the padded surface; BC4/BC5 images go to it unpadded, as DirectX::Compress takes them.
+bool itwCompressImageChain(const rgba_surface* images, int count, uint8_t* target, CompressionFunc* cmpFunc, int dxgi_format,
+                           ItwProgressFunc* progress, void* user)
+{
+    bc7_enc_settings s7;
+    bc6h_enc_settings s6;
+    const void* settings = nullptr;
+    if (cmpFunc && resolve_trampoline(cmpFunc, dxgi_format, &s7, &s6, &settings))
+        return itwCompressImageChainEx(images, count, target, dxgi_format, settings, progress, user);
+    itwClearError();
+    bool done = false;
+    const bool ok = itw::guarded([&] {
+        if (!cmpFunc) itw::fail_msg("itwCompressImageChain: null CompressionFunc");
+        itw::chain_check(images, count, target, dxgi_format);
+        const bool src_dev = is_device_pointer(images[0].ptr);
+        for (int i = 1; i < count; i++)
+            if (is_device_pointer(images[i].ptr) != src_dev) itw::fail_msg("itwCompressImageChain: mixed host and device images");
+        const int px = (dxgi_format == ITW_DXGI_FORMAT_BC6H_UF16 || dxgi_format == ITW_DXGI_FORMAT_BC6H_SF16) ? 8 : 4;
+        const int bpb = GetBytesPerBlock(dxgi_format);
+        uint8_t* scratch = nullptr;                         // device images: the largest padded image
+        struct Free { uint8_t*& p; ~Free() { if (p) (void)hipFree(p); } } free_scratch{scratch};
+        if (src_dev && !keeps_partial_blocks(dxgi_format)) {
+            size_t most = 0;
+            for (int i = 0; i < count; i++)
+                most = std::max(most, (size_t)((images[i].width + 3) & ~3) * px * (size_t)((images[i].height + 3) & ~3));
+            if (hipMalloc(&scratch, most) != hipSuccess) { (void)hipGetLastError(); itw::fail_msg("itwCompressImageChain: hipMalloc of %zu bytes", most); }
+        }
+        int64_t off = 0;
+        for (int i = 0; i < count; i++) {
+            const rgba_surface& s = images[i];
+            const bool pad = !keeps_partial_blocks(dxgi_format) && ((s.width & 3) || (s.height & 3));
+            if (!pad) {
+                cmpFunc(&s, target + off);
+            } else if (!src_dev) {
+                rgba_surface p = itwPadToMultipleOf4(&s, px);
+                cmpFunc(&p, target + off);
+                itwFreeSurface(&p);
+            } else {
+                itwPadToMultipleOf4Device(&s, px, scratch);
+                if (hipStreamSynchronize((hipStream_t)itwGetStream()) != hipSuccess) { (void)hipGetLastError(); itw::fail_msg("itwCompressImageChain: pad failed"); }
+                rgba_surface p{scratch, (s.width + 3) & ~3, (s.height + 3) & ~3, ((s.width + 3) & ~3) * px};
+                cmpFunc(&p, target + off);
+            }
+            if (src_dev && hipStreamSynchronize((hipStream_t)itwGetStream()) != hipSuccess) { (void)hipGetLastError(); itw::fail_msg("itwCompressImageChain: call failed"); }
+            if (const char* e = itwLastError()) itw::fail_msg("%s", e);
+            off += (int64_t)((s.width + 3) / 4) * ((s.height + 3) / 4) * bpb;
+            if (progress && !progress(i + 1, count, user)) return;
+        }
+        done = true;
+    });
+    return ok && done;
 }
 
 rgba_surface itwPadToMultipleOf4(const rgba_surface* input, int pixel_size)

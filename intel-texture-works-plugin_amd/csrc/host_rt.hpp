@@ -52,6 +52,10 @@ bool sliced_part(const rgba_surface* source, uint8_t* target, int dxgi_format, c
 // windows a call is cut into, and W (slices per window); 0 windows: the pipeline is off
 int sliced_windows(int dxgi_format, const void* settings, int width, int height, int64_t slice_pixels, int* window_slices);
 
+// the checks of itwCompressImageChain that need no device (counts, null pointers, sizes, strides, format), as a Failure; for the literal
+// loop of a caller's own CompressionFunc, which takes no settings
+void chain_check(const rgba_surface* images, int count, const uint8_t* target, int dxgi_format);
+
 // One predicate for "the kernels can dereference this pointer": device AND managed allocations (abi.hip and
 // dispatch.hip/decode.hip used to disagree on managed memory).  Unregistered host memory -> false.
 bool is_device_pointer(const void* p) noexcept;

@@ -56,4 +56,23 @@ void launch_bc6h(const uint8_t* src, int64_t stride, int width, int height, uint
                  const bc6h_enc_settings& s, hipStream_t st, void* workspace = nullptr);
 void set_bc6h_path(int path);         // 0 by size, 1 one kernel, 2 wide (tests / probes)
 
+// DirectXTex's partial-block fill (DirectXTexCompress.cpp:140-168 applied in its own order): texel column / row i of a block of which
+// only the first `valid` (1..4) columns / rows exist repeats source column / row {0,0,0,1}[i], itself wrapped to 0 when that one is
+// missing too.  Shared by the BC4/BC5 kernel's load (bc4_bc5.hip) and the chain gather (chain.hip).
+__device__ __forceinline__ int bc45_fill_index(int i, int valid)
+{
+    const int s = i < valid ? i : (i == 3 ? 1 : 0);
+    return s < valid ? s : 0;
+}
+
+// One image of a chain (chain.hip): texels at `ptr` (device memory), rows `stride` bytes apart, width x height >= 1, and the index of its
+// first block in its group's concatenated block list (ceil(w/4) x ceil(h/4) blocks per image, raster order).
+struct ChainImage { const uint8_t* ptr; int64_t stride; int32_t width, height; int64_t first_block; };
+// The gather of one group of a chain into a PACKED surface: `packed_bx` blocks wide, `packed_by` block rows high (4 * packed_bx texels x
+// 4 * packed_by rows, `dst_pitch` bytes apart, 16-B aligned rows), packed block j = block j of the group (j < nblocks; the tail of the last
+// packed row is zero).  `images`: device table of `nimg` descriptors, ascending first_block.  texel_bytes 4 (RGBA8) or 8 (RGBA16F);
+// `fill45`: partial blocks take bc45_fill_index (BC4/BC5) instead of edge replication (the ISPC formats' pad to multiples of 4).
+void launch_chain_gather(const ChainImage* images, int nimg, int64_t nblocks, int packed_bx, int packed_by, int texel_bytes, bool fill45,
+                         uint8_t* dst, int64_t dst_pitch, hipStream_t st);
+
 } // namespace itw

@@ -22,7 +22,7 @@ EXPORTED_SYMBOLS = tuple(
     + ["GetProcessorCount", "InitWin32Threads", "DestroyThreads", "GetBytesPerBlock", "CompressImageMT", "CompressImageST",
        "CompressImageBC1", "CompressImageBC3", "CompressImageBC4", "CompressImageBC5"]
     + ["CompressImageBC7_" + p for p in BC7_PROFILES] + ["CompressImageBC6H_" + p for p in BC6H_PROFILES]
-    + ["itwCompressImageSliced", "itwCompressImageSlicedEx", "itwSetSliceWindow", "itwSliceWindow", "itwSliceWindowFor", "itwPadToMultipleOf4", "itwFreeSurface", "itwPadToMultipleOf4Device",
+    + ["itwCompressImageSliced", "itwCompressImageSlicedEx", "itwChainBytes", "itwCompressImageChain", "itwCompressImageChainEx", "itwSetSliceWindow", "itwSliceWindow", "itwSliceWindowFor", "itwPadToMultipleOf4", "itwFreeSurface", "itwPadToMultipleOf4Device",
        "itwConvertToRGBA8Device", "itwConvertToRGBA16FDevice"]
     # include/itw_multigpu.h: one surface over all GPUs, one process
     + ["itwMultiGpuRanks", "itwMultiGpuTransport", "itwMultiGpuPeerLinks", "itwCompressImageMultiGPU", "itwCompressImageMultiGPUEx", "itwCompressImageMultiGPUBands",
@@ -184,6 +184,12 @@ def _load(path, hooks):
         L.itwCompressImageSliced.restype = C.c_bool
         L.itwCompressImageSlicedEx.argtypes = [C.POINTER(RgbaSurface), C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         L.itwCompressImageSlicedEx.restype = C.c_bool
+        L.itwChainBytes.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.itwChainBytes.restype = C.c_int64
+        L.itwCompressImageChain.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.itwCompressImageChain.restype = C.c_bool
+        L.itwCompressImageChainEx.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.itwCompressImageChainEx.restype = C.c_bool
         L.itwSetSliceWindow.argtypes = [C.c_int]
         L.itwSetSliceWindow.restype = None
         L.itwSliceWindow.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int64]
@@ -427,6 +433,79 @@ def compress_image(fmt, img, profile=None, multithreaded=True, slice_pixels=0, p
         ok = lib().itwCompressImageSliced(C.byref(surf), dst, pitch, image_func(fmt, profile),
                                           DXGI_FORMAT[fmt], multithreaded, slice_pixels, C.cast(cb, C.c_void_p) if cb else None, None)
     return bool(ok), out
+
+
+def _surfaces(images):
+    """ctypes array of rgba_surface for a list of host numpy arrays / CUDA torch tensors (H, W, 4), rows may be strided."""
+    surfs = []
+    for img in images:
+        if hasattr(img, "data_ptr"):
+            assert img.dim() == 3 and img.shape[2] == 4 and img.stride(2) == 1 and img.stride(1) == 4
+            surfs.append(RgbaSurface(img.data_ptr(), img.shape[1], img.shape[0], img.stride(0) * img.element_size()))
+        else:
+            assert img.ndim == 3 and img.shape[2] == 4 and img.strides[2] == img.itemsize and img.strides[1] == 4 * img.itemsize
+            surfs.append(RgbaSurface(img.ctypes.data, img.shape[1], img.shape[0], img.strides[0]))
+    return (RgbaSurface * max(1, len(surfs)))(*surfs)
+
+
+def chain_bytes(fmt, images):
+    """itwChainBytes: bytes a chain of images (arrays / tensors, or (height, width) tuples) encodes to; -1 on bad arguments."""
+    arr = (RgbaSurface * max(1, len(images)))(*[RgbaSurface(None, s[1], s[0], 0) if isinstance(s, tuple) else _surfaces([s])[0] for s in images])
+    return int(lib().itwChainBytes(C.cast(arr, C.c_void_p), len(images), DXGI_FORMAT[fmt]))
+
+
+def compress_chain(fmt, images, profile=None, settings=None, progress=None, out=None, cmp_func=None):
+    """A whole mip chain / cube map / array in one call (itwCompressImageChainEx; with `cmp_func` -- a CompressionFunc address, e.g.
+    image_func(fmt, profile) -- itwCompressImageChain).  images: list of host numpy arrays or CUDA torch tensors (H, W, 4), uint8 or
+    uint16 half bits for bc6h, all of one kind, any size >= 1.  `out` (optional): numpy array or CUDA uint8 tensor of chain_bytes() bytes;
+    by default the images' kind.  Returns (ok, blocks): the images' blocks one after another, tightly packed (a DDS payload)."""
+    import numpy as np
+    fmt_key = fmt
+    base = fmt.split("_")[0]
+    nbytes = sum(((img.shape[1] + 3) // 4) * ((img.shape[0] + 3) // 4) for img in images) * BYTES_PER_BLOCK[base]
+    on_device = bool(images) and hasattr(images[0], "data_ptr")
+    if out is None:
+        if on_device:
+            import torch
+            out = torch.zeros(nbytes, dtype=torch.uint8, device=images[0].device)
+        else:
+            out = np.zeros(nbytes, dtype=np.uint8)
+    if on_device or hasattr(out, "data_ptr"):
+        import torch
+        dev = images[0].device if on_device else out.device
+        lib().itwSetStream(torch.cuda.current_stream(dev).cuda_stream)
+    dst = out.data_ptr() if hasattr(out, "data_ptr") else out.ctypes.data
+    arr = _surfaces(images)
+    cb = PROGRESS_FUNC(progress) if progress else None
+    cbp = C.cast(cb, C.c_void_p) if cb else None
+    if cmp_func is not None:
+        ok = lib().itwCompressImageChain(C.cast(arr, C.c_void_p), len(images), dst, cmp_func, DXGI_FORMAT[fmt_key], cbp, None)
+    else:
+        if settings is None and base == "bc7":
+            settings = bc7_profile(profile or "slow")
+        elif settings is None and base == "bc6h":
+            settings = bc6h_profile(profile or "slow")
+        sp = C.cast(C.byref(settings), C.c_void_p) if settings is not None else None
+        ok = lib().itwCompressImageChainEx(C.cast(arr, C.c_void_p), len(images), dst, DXGI_FORMAT[fmt_key], sp, cbp, None)
+    return bool(ok), out
+
+
+def mip_chain(img):
+    """Test / tool content: the level list of a full mip chain of `img` (numpy (H, W, 4)), level l+1 of max(1, w >> 1) x max(1, h >> 1)
+    from level l by a plain 2x2 mean (an odd last row / column is repeated).  uint8 levels average as integers, uint16 half bits as float16.
+    Not a reproduction of any particular filter: GPU or DirectXTex mip generation is not part of this package."""
+    import numpy as np
+    levels = [np.ascontiguousarray(img)]
+    half = img.dtype == np.uint16
+    while levels[-1].shape[0] > 1 or levels[-1].shape[1] > 1:
+        a = levels[-1]
+        f = a.view(np.float16).astype(np.float32) if half else a.astype(np.float32)
+        h, w = a.shape[:2]
+        nh, nw = max(1, h >> 1), max(1, w >> 1)
+        f = np.pad(f, ((0, 2 * nh - h if 2 * nh > h else 0), (0, 2 * nw - w if 2 * nw > w else 0), (0, 0)), mode="edge")[:2 * nh, :2 * nw]
+        m = 0.25 * (f[0::2, 0::2] + f[1::2, 0::2] + f[0::2, 1::2] + f[1::2, 1::2])
+        levels.append(np.ascontiguousarray(m.astype(np.float16).view(np.uint16) if half else np.floor(m + 0.5).astype(np.uint8)))
+    return levels
 
 
 def multigpu_sub_bands(fmt, width, height, ranks, L=None):
