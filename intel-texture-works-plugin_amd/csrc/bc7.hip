@@ -27,6 +27,7 @@
 //     The slow profiles (every shape scanned) run the BOUNDED order instead (round 4: modes 1/3/7 last, only for the blocks an
 //     exact lower bound cannot exclude, compacted into lists) as two interleaved bands on two streams, and for the RGB
 //     profile a pilot kernel picks that order or the reference's per call, on the device (round 5; launch_bc7);
+//     under the RGB profile the list scan of that order fits only the (block, shape) pairs the bound leaves (PAIRS, bc7_pair_build);
 //   * the scans produce a candidate's ERROR and nothing else: the level a texel takes
 //     and the packed indices matter for a mode's winner alone, so the winner record is
 //     {error, shape} and the finish kernel recomputes endpoints and indices of the
@@ -1377,6 +1378,12 @@ __device__ __forceinline__ void merge_packed_parts(Win& w, Lane& ln, const uint3
     }
 }
 
+// the pair route of the RGB bounded order (PAIRS, below bc7_pilot_estimate)
+struct PairRegion { uint64_t* words; int32_t* buckets; int32_t* ctr; int32_t cap; };   // ctr: [0..63] bucket lengths, [64] overflow, [65] the second list's length
+constexpr int PAIR_CTR_OVERFLOW = 64, PAIR_CTR_REDO = 65, PAIR_CTR_WORDS = 68;
+constexpr int PAIR_MAX_PER_BLOCK = 32;
+constexpr unsigned long long PAIR_WORD_HEAVY = ~0ull - 1ull;        // no merged word takes this value: errors stay below 2^23
+
 struct ScanTasks { int n; int kind[3]; };      // WK_SCAN02 / WK_SCAN13 / WK_SCAN7 in launch order
 
 // Round 5, the BANDS and the PILOT of the bounded order (launch_bc7): which chunks (runs of TPB blocks) of the surface a launch of
@@ -1555,7 +1562,7 @@ bc7_finish_all(const uint8_t* __restrict__ src, int64_t stride, int32_t blocks_x
                int32_t* __restrict__ out_list7, int32_t* __restrict__ out_count7, const ChunkSel sel,
                const uint4* __restrict__ in_compact, uint4* __restrict__ out_compact)
 {
-    constexpr bool LISTED = PHASE == 2 || PHASE == 4 || PHASE == 5 || PHASE == 7;   // walks a compacted list of an earlier phase
+    constexpr bool LISTED = PHASE == 2 || PHASE == 4 || PHASE == 5 || PHASE == 7 || PHASE == 8;   // walks a compacted list of an earlier phase
     constexpr bool DO02 = PHASE == 0 || PHASE == 2 || PHASE == 3 || PHASE == 5;
     constexpr bool DO13 = PHASE == 0 || PHASE == 2 || PHASE == 4;
     constexpr bool DO7 = PHASE == 0 || PHASE == 1;
@@ -1590,7 +1597,7 @@ bc7_finish_all(const uint8_t* __restrict__ src, int64_t stride, int32_t blocks_x
     const bool on13 = S.mode_selection[1];
     int32_t e_alpha = ERR_MAX;
     if (PHASE == 2 || PHASE == 5) e_alpha = inc_err[b];      // every listed block has opaque_err <= e_alpha: its winners exist
-    if (PHASE == 4 || PHASE == 7) ln.best_err = inc_err[b];  // what modes 1/3 (mode 7) have to get strictly below
+    if (PHASE == 4 || PHASE == 7 || PHASE == 8) ln.best_err = inc_err[b];  // what modes 1/3 (mode 7) have to get strictly below
     Win w;
     if (DO02 && S.mode_selection[0]) {
         unpack_win(w, wins4[(int64_t)wide_win_slot(0) * nblocks + b]);
@@ -1606,6 +1613,35 @@ bc7_finish_all(const uint8_t* __restrict__ src, int64_t stride, int32_t blocks_x
         const int parts = list_scan_parts(nact, nblocks);
         if (S.fastSkipTreshold_mode1 > 0) { ln.tx.fence(); merge_packed_parts<3, 3>(w, ln, wins4 + (int64_t)wide_win_slot(1) * nblocks, nact, parts, slot); refine_and_commit<1>(ln, w, S.refineIterations[1], S.channels); }
         if (S.fastSkipTreshold_mode3 > 0) { ln.tx.fence(); merge_packed_parts<3, 3>(w, ln, wins4 + (int64_t)wide_win_slot(3) * nblocks, nact, parts, slot); refine_and_commit<3>(ln, w, S.refineIterations[3], S.channels); }
+    }
+    bool redo = false;
+    if (PHASE == 8) {
+        // PAIRS (bc7_pair_build's header): `wins4` is the band's merged words, two per listed block -- the ordered argmin (fast error << 32 |
+        // rank key) over the shapes the bound leaves, ~0 where it leaves none -- and `out_count7` its overflow word
+        const unsigned long long* pw = reinterpret_cast<const unsigned long long*>(wins4) + 2 * (int64_t)slot;
+        const int32_t inc = ln.best_err;
+        const bool heavy = pw[0] == PAIR_WORD_HEAVY;          // bc7_pair_build already put the block on the second list
+        redo = !heavy && *out_count7 != 0;                   // a bucket overflowed: the whole band takes the full list scan
+        const bool use = !heavy && !redo;
+        const unsigned long long v1 = (use && S.fastSkipTreshold_mode1 > 0) ? pw[0] : ~0ull, v3 = (use && S.fastSkipTreshold_mode3 > 0) ? pw[1] : ~0ull;
+        if (v1 != ~0ull) {
+            ln.tx.fence();
+            w.err = (int32_t)(v1 >> 32); w.key = (int32_t)(uint32_t)v1; w.shape = w.key & 63;
+            const bool open = w.err + ln.opaque_err >= inc;  // a shape the bound excluded may come before this one in the reference's order
+            const int32_t before = ln.best_err;
+            refine_and_commit<1>(ln, w, S.refineIterations[1], S.channels);
+            redo = redo || (open && ln.best_err < before);
+        }
+        if (v3 != ~0ull) {
+            ln.tx.fence();
+            w.err = (int32_t)(v3 >> 32); w.key = (int32_t)(uint32_t)v3; w.shape = w.key & 63;
+            const bool open = w.err + ln.opaque_err >= inc;
+            const int32_t before = ln.best_err;
+            refine_and_commit<3>(ln, w, S.refineIterations[3], S.channels);
+            redo = redo || (open && ln.best_err < before);
+        }
+        // deferred blocks keep their block and incumbent: the full list scan and bc7_finish_all<4> redo both modes for them
+        append_to_list(out_list, out_count, live && redo, b);
     }
     if (PHASE == 7) {                                        // the list scan left [part][slot] winners
         const int parts = list_scan_parts(nact, nblocks);
@@ -1668,7 +1704,8 @@ bc7_finish_all(const uint8_t* __restrict__ src, int64_t stride, int32_t blocks_x
     bool store = live;
     if (PHASE == 2 || PHASE == 5) store = store && ln.best_err <= e_alpha;   // else the alpha group's block stands (ties go to the earlier, RGB, group)
     if (PHASE == 4 || PHASE == 7) store = store && ln.improved;
-    if (PHASE == 4 && store) inc_err[b] = ln.best_err;         // mode 7 (PHASE 7, RGBA profiles) comes after modes 1/3: strictly below them
+    if (PHASE == 8) store = store && ln.improved && !redo;
+    if ((PHASE == 4 || PHASE == 8) && store) inc_err[b] = ln.best_err;         // mode 7 (PHASE 7, RGBA profiles) comes after modes 1/3: strictly below them
     if (store) {
         uint32_t* d = reinterpret_cast<uint32_t*>(dst + (int64_t)b * 16);
         if (VEC16) *reinterpret_cast<uint4*>(d) = make_uint4(ln.best[0], ln.best[1], ln.best[2], ln.best[3]);
@@ -1722,6 +1759,144 @@ bc7_pilot_estimate(const uint8_t* __restrict__ src, int64_t stride, int32_t bloc
             *flag = (listed * 256 <= (int64_t)thr256 * sampled) ? 1 : 0;
             if (host_counts) { host_counts[0] = (int32_t)listed; host_counts[1] = (int32_t)sampled; __threadfence_system(); }
         }
+    }
+}
+
+// ---- PAIRS: the list scan of the RGB bounded order, cut down to the (block, shape) pairs the bound cannot exclude ---------------
+// bc7_finish_all<3> lists a block as soon as ONE shape's two_subset_bound is below the incumbent `inc`; the list scan then fits all 64
+// shapes of it, both modes.  On the bench surface 1.6 of a listed block's 64 shapes have a bound below inc (profiles/bc7_pair_survival.txt).
+// A mode-1/3 encoding of shape s, fast or refined, has error >= LB(s), so with P1 = {s : LB(s) < inc - opaque - 0.5} (finish<3>'s rule):
+//   * the reference refines s* = first strict minimum of the FAST error in rank order (kernel.ispc:1299-1363).  If s* is outside P1 the
+//     mode cannot get below inc: it changes nothing.  If s* is in P1 it is also the ordered argmin over P1;
+//   * so only "is the ordered argmin over P1 (fast error E1) really s*?" is open.  A shape outside P1 has fast error >= inc; it can
+//     precede the P1 winner only if E1 >= inc.  E1 < inc: the P1 winner is s*, refined and committed as ever.  E1 >= inc: the P1 winner is
+//     refined all the same; if that does not get below the live best error the mode changes nothing whichever shape s* is (s* = the P1
+//     winner: the reference's refinement fails alike; s* outside P1: it cannot win).  Only where the refinement DOES get below although
+//     E1 >= inc is the answer needed, and those few blocks take the full route: they go to a second list, the full list scan
+//     (bc7_scan_all, split) and bc7_finish_all<4> run over it from the untouched incumbent.  Mode 3 is judged against the pre-mode-1 inc
+//     (a superset of its own P1) and commits against the live best error.
+// Three steps between finish<3> and the refinement, per band:
+//   bc7_pair_build   lanes = listed blocks: the 64 bounds again (the pilot's arithmetic), the survivors appended to one bucket per
+//                    shape -- counted per workgroup in LDS, one atomic per (workgroup, shape) -- so that every wave of the scan is
+//                    shape-uniform (scalar subset masks); clears the block's two merged words.  Blocks with more than 32 survivors go
+//                    to the second list at once;
+//   bc7_pair_scan    lanes = pairs of one shape, grid-stride over wave tiles of 64 pairs: search_two_subset over that one shape, its
+//                    rank key, and the ordered argmin (error, then key; keys are distinct) as a 64-bit atomicMin of (error << 32 | key)
+//                    into one word per (listed block, mode) -- no share table, no merge;
+//   bc7_finish_all<8> reads the words, refines, commits or defers the block to the second list.
+// A bucket that overflows (photograph-like content that slipped past the pilot: nearly every shape survives) raises the band's overflow
+// word: the pair scan returns at once and finish<8> defers every listed block, i.e. the band runs the full list scan.  Same bytes.
+
+__global__ void __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(4, 4)))
+bc7_pair_build(const uint8_t* __restrict__ src, int64_t stride, int32_t blocks_x, const int32_t* __restrict__ list, const int32_t* __restrict__ count,
+               const uint4* __restrict__ compact, const int32_t* __restrict__ inc_err, const int channels, const PairRegion P, int32_t* __restrict__ redo)
+{
+    __shared__ int32_t s_at[TPB / 64][64];                          // per (wave, shape): survivors, then where they go in the bucket
+    const int32_t nact = *count;
+    if ((int32_t)blockIdx.x * TPB >= nact) return;                   // whole workgroup: no barrier is pending
+    const int32_t gid = (int32_t)blockIdx.x * TPB + threadIdx.x;
+    const bool live = gid < nact;
+    const int32_t slot = live ? gid : nact - 1;
+    const int32_t b = list[slot];
+    Tex tx;
+    if (compact) load_block_compact(tx, compact, slot); else load_block<false>(tx, src, stride, blocks_x, b);
+    int32_t opaque = 0;
+    if (channels == 4) {
+        uint32_t e = 0;
+#pragma unroll
+        for (int d = 0; d < 4; d++) { const uint32_t x = ~tx.pl[3][d]; e = udot4(x, x, e); }
+        opaque = (int32_t)e;
+    }
+    if (live) { P.words[2 * (int64_t)slot] = ~0ull; P.words[2 * (int64_t)slot + 1] = ~0ull; }
+    IStats<3> full;
+    stats_int<3>(full, tx.pl, whole_block());
+    const float lim = (float)(inc_err[b] - opaque) - 0.5f;          // bc7_finish_all<3>'s rule
+    const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6);
+    // survivors of the lane's block as a bit per shape; per (wave, shape) their number.  No global atomic inside this loop: one per
+    // (wave, shape), each waited for, made the kernel latency bound (1.0 ms for 157 000 blocks instead of 0.1)
+    unsigned long long mine = 0;
+#pragma unroll 1
+    for (int shape = 0; shape < 64; shape++) {
+        const bool in = live && !(two_subset_bound(shape, tx.pl, full) >= lim);
+        mine |= in ? (1ull << shape) : 0ull;
+    }
+    // a block more than half of whose shapes survive (photograph-like content inside a surface the pilot gave the bounded order) is cheaper
+    // in the full list scan, which takes the 64 shapes without rank keys: straight to the second list, no pairs, its words say so
+    const bool heavy = __popcll(mine) > PAIR_MAX_PER_BLOCK;
+    if (heavy) { mine = 0; P.words[2 * (int64_t)slot] = PAIR_WORD_HEAVY; }
+    append_to_list(redo, P.ctr + PAIR_CTR_REDO, heavy, b);
+#pragma unroll 1
+    for (int shape = 0; shape < 64; shape++) {
+        const unsigned long long m = __ballot((mine >> shape) & 1ull);
+        if (lane == 0) s_at[wave][shape] = (int32_t)__popcll(m);
+    }
+    __syncthreads();
+    if (threadIdx.x < 64u) {                                         // the workgroup's stretch of each bucket: 64 atomics, one instruction
+        const int shape = (int)threadIdx.x;
+        int32_t k = 0;
+#pragma unroll
+        for (int w = 0; w < TPB / 64; w++) k += s_at[w][shape];
+        int32_t base = k ? atomicAdd(P.ctr + shape, k) : 0;
+        if (base + k > P.cap) { P.ctr[PAIR_CTR_OVERFLOW] = 1; base = -1; }
+#pragma unroll
+        for (int w = 0; w < TPB / 64; w++) { const int32_t c = s_at[w][shape]; s_at[w][shape] = base; base = base < 0 ? -1 : base + c; }
+    }
+    __syncthreads();
+#pragma unroll 1
+    for (int shape = 0; shape < 64; shape++) {
+        const bool in = (mine >> shape) & 1ull;
+        const unsigned long long m = __ballot(in);
+        const int32_t base = s_at[wave][shape];
+        if (in && base >= 0) P.buckets[(int64_t)shape * P.cap + base + (int32_t)__popcll(m & ((1ull << lane) - 1ull))] = slot;
+    }
+}
+
+__global__ void __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(4, 4)))
+bc7_pair_scan(const uint8_t* __restrict__ src, int64_t stride, int32_t blocks_x, const int32_t* __restrict__ list, const uint4* __restrict__ compact,
+              const bc7_enc_settings S, const PairRegion P)
+{
+    __shared__ unsigned short s_seed16[2048];
+    __shared__ uint32_t s_seed32[2048];
+    __shared__ uint2 s_pal[12 * TPB];                               // 8 + 4 levels per lane, as in the table-order scans
+    __shared__ int32_t s_first[65];                                 // first wave tile of each shape's bucket
+    if (P.ctr[PAIR_CTR_OVERFLOW]) return;                           // whole grid: the builder finished before this launch
+    if (threadIdx.x == 0) {
+        int32_t t = 0;
+        for (int s = 0; s < 64; s++) { s_first[s] = t; t += (P.ctr[s] + 63) >> 6; }
+        s_first[64] = t;
+    }
+    __syncthreads();
+    const int32_t total = s_first[64];
+    const int32_t wpb = TPB / 64;
+    if ((int32_t)blockIdx.x * wpb >= total) return;                 // whole workgroup: no barrier is pending
+    Lane ln;
+    ln.T = stage_seed_tables_fast(s_seed16, s_seed32, threadIdx.x, TPB);
+    __syncthreads();
+    ln.keys = nullptr;
+    ln.pal = s_pal + threadIdx.x;
+    const int lane = (int)(threadIdx.x & 63u);
+    const bool on_a = S.fastSkipTreshold_mode1 > 0, on_b = S.fastSkipTreshold_mode3 > 0;
+    int shape = 0;
+#pragma unroll 1
+    for (int32_t tile = (int32_t)blockIdx.x * wpb + (int32_t)(threadIdx.x >> 6); tile < total; tile += (int32_t)gridDim.x * wpb) {
+        while (s_first[shape + 1] <= tile) shape++;                  // tiles grow along the loop: the search never goes back
+        shape = __builtin_amdgcn_readfirstlane(shape);               // wave-uniform: subset masks stay scalars
+        const int32_t len = P.ctr[shape];
+        const int32_t at = (tile - s_first[shape]) * 64 + lane;
+        const bool live = at < len;
+        const int32_t slot = P.buckets[(int64_t)shape * P.cap + (live ? at : len - 1)];   // idle lanes redo the bucket's last pair, merge nothing
+        if (compact) load_block_compact(ln.tx, compact, slot); else load_block<false>(ln.tx, src, stride, blocks_x, list[slot]);
+        // the table-order scan's own code for exactly one shape (first = shape, step = 64): the fast errors of modes 1 / 3 ...
+        Win wa, wb;
+        search_two_subset<false, 3, 0>(ln, S, wa, wb, shape, 64);
+        const int32_t ea = wa.err, ec = wb.err;
+        // ... and the shape's rank key, which orders equal errors (the scan evaluates it on a tie only; here every pair carries it)
+        ln.tx.fence();
+        Stats<3> rfull;
+        whole_block_rank_stats<3, 3>(rfull, ln.tx);
+        const uint32_t key = (uint32_t)rank_key<3>(shape, ln.tx, rfull, ln.T);
+        if (live && on_a) atomicMin(reinterpret_cast<unsigned long long*>(P.words + 2 * (int64_t)slot),     ((unsigned long long)(uint32_t)ea << 32) | key);
+        if (live && on_b) atomicMin(reinterpret_cast<unsigned long long*>(P.words + 2 * (int64_t)slot + 1), ((unsigned long long)(uint32_t)ec << 32) | key);
     }
 }
 
@@ -2040,6 +2215,20 @@ static bool bc7_compact_lists()
     static const bool on = [] { const char* e = std::getenv("ITW_BC7_COMPACT"); return !(e && e[0] == '0'); }();
     return on;
 }
+// ITW_BC7_PAIRS=0: the RGB bounded order's list scan fits all 64 shapes of every listed block (round 4) instead of the (block, shape) pairs
+// the bound leaves (bc7_pair_build).  ITW_BC7_PAIR_CAP=<n>: lowers a shape bucket's capacity (never raises it): a small value forces the
+// overflow route.  Both are read at every call -- the workspace layout does not depend on them -- so one process can compare the routes.
+static bool bc7_pairs_on()
+{
+    const char* e = std::getenv("ITW_BC7_PAIRS");
+    return !(e && e[0] == '0');
+}
+static int32_t bc7_pair_cap(int32_t layout_cap)
+{
+    const char* e = std::getenv("ITW_BC7_PAIR_CAP");
+    const long v = e ? std::atol(e) : 0;
+    return (v > 0 && v < layout_cap) ? (int32_t)v : layout_cap;
+}
 static bool bc7_fused_on()
 {
     static const bool on = [] { const char* e = std::getenv("ITW_BC7_FUSED"); return !(e && e[0] == '0'); }();
@@ -2089,16 +2278,19 @@ static size_t wide_workspace_bytes(size_t n)
 // fused shape, in 4-byte words from the start of the workspace (every region starts on a 16-byte boundary)
 // a list of blocks for modes 1/3 with what its split scan and refinement need: block ids [cap], winners of the scan's shares [5 rows][cap]
 // (rows 2, 3 used: list_scan_parts x listed <= cap), the listed blocks' texels [cap] x 64 B in list order
-struct ListRegion { size_t list, wins, compact, cap; };
+// pairs (bc7_pair_build): per band the merged words [cap] x 2 x 8 B, the second list [cap], 64 shape buckets of cap / 8 listed slots and (behind the
+// 16 counters) PAIR_CTR_WORDS counters; each kind's two halves are contiguous, so a call without bands uses them as one
+struct ListRegion { size_t list, wins, compact, cap, pair_words, pair_redo, pair_buckets, pair_ctr, pair_cap; };
 struct FusedLayout { size_t inc, list0, list1, list2, counts, words; ListRegion band[2]; };
 // Which regions a call's settings can touch (a `basic` call was sized like a `slow` one, 124 B per block instead of 36):
 //   lists    the three block lists of the RGBA profiles' alpha-first order (and list13 of an RGB bounded call that runs as one band);
 //   bands    the per-band lists and share winners of the bounded order (modes 1/3, mode 7 scanned over lists);
-//   compact  the listed blocks' texels in list order (the RGB bounded order only).
-struct FusedNeeds { bool lists, bands, compact; };
+//   compact  the listed blocks' texels in list order (the RGB bounded order only);
+//   pairs    the pair route's words, second lists and buckets (the RGB bounded order only, whatever ITW_BC7_PAIRS says).
+struct FusedNeeds { bool lists, bands, compact, pairs; };
 static FusedNeeds fused_needs(const bc7_enc_settings* s)
 {
-    if (!s) return FusedNeeds{true, true, true};                  // unknown settings: everything
+    if (!s) return FusedNeeds{true, true, true, true};                  // unknown settings: everything
     bc7_enc_settings S = *s;
     S.channels = (s->channels == 4) ? 4 : 3;
     auto ranked = [](int t) { return t > 0 && t < 64; };
@@ -2107,7 +2299,8 @@ static FusedNeeds fused_needs(const bc7_enc_settings* s)
     const bool r13 = on13 && (ranked(S.fastSkipTreshold_mode1) || ranked(S.fastSkipTreshold_mode3));
     const bool bounded = bc7_bounded_order() && on02 && on13 && !r13;
     const bool alpha = bc7_alpha_first(S);
-    return FusedNeeds{alpha || bounded, bounded, bounded && !alpha && bc7_compact_lists()};
+    const bool on7 = S.mode_selection[1] && S.fastSkipTreshold_mode7 > 0;
+    return FusedNeeds{alpha || bounded, bounded, bounded && !alpha && bc7_compact_lists(), bounded && !alpha && !on7};
 }
 static FusedLayout fused_layout(size_t n, const FusedNeeds& need)
 {
@@ -2121,6 +2314,7 @@ static FusedLayout fused_layout(size_t n, const FusedNeeds& need)
     W.list1 = o;    o = up4(o + lcap);
     W.list2 = o;    o = up4(o + lcap);
     W.counts = o;   o += 16;                                       // list lengths, the pilot's verdict
+    for (int k = 0; k < 2; k++) { W.band[k].pair_ctr = o; o += PAIR_CTR_WORDS; }   // (contiguous with them: one memset)
     for (int k = 0; k < 2; k++) {                                  // the two bands: lists and share winners ...
         ListRegion& r = W.band[k];
         r.cap = (nchunks / 2 + 65) * TPB;                          // (a band is whole stripes of up to 64 chunks)
@@ -2129,6 +2323,9 @@ static FusedLayout fused_layout(size_t n, const FusedNeeds& need)
     }
     W.band[0].compact = o; o += need.compact ? 16 * W.band[0].cap : 0;   // ... and their texels, contiguous: a call without bands uses both as one
     W.band[1].compact = o; o += need.compact ? 16 * W.band[1].cap : 0;
+    for (int k = 0; k < 2; k++) { W.band[k].pair_words = o; o += need.pairs ? 4 * W.band[k].cap : 0; }
+    for (int k = 0; k < 2; k++) { W.band[k].pair_redo = o; o += need.pairs ? W.band[k].cap : 0; }
+    for (int k = 0; k < 2; k++) { W.band[k].pair_cap = W.band[k].cap / 8; W.band[k].pair_buckets = o; o += need.pairs ? 64 * W.band[k].pair_cap : 0; }
     W.words = o;
     return W;
 }
@@ -2419,17 +2616,20 @@ void launch_bc7(const uint8_t* src, int64_t stride, int width, int height, uint8
                 //    the pilot did not choose returns at once.  No host round trip, no block treated differently from its neighbours.
                 //    (A sample encoded ahead on a third stream was measured first: its chain of small launches could not get its share of a
                 //    chip the bands' scans fill, and the verdict arrived late: profiles/history/r05/r05d_bc7_pilot_timeline.txt.)
-                ITW_CHECK(hipMemsetAsync(rgb_count, 0, 16 * sizeof(int32_t), st));
+                ITW_CHECK(hipMemsetAsync(rgb_count, 0, (16 + 2 * PAIR_CTR_WORDS) * sizeof(int32_t), st));
                 const bool two = bc7_bands() > 1 && aux && !aux->single && aux->stream && nchunks >= 32;
+                const bool pairs = bc7_pairs_on();
                 const bool pilot = two && bc7_pilot_threshold() >= 0 && aux->mid;
                 int32_t stripe = nchunks / 16;                               // stripes of 64 chunks (16 block rows of a 4096-wide surface), fewer on small surfaces
                 stripe = stripe < 1 ? 1 : (stripe > 64 ? 64 : stripe);
                 const int32_t stripes = (nchunks + stripe - 1) / stripe;
-                struct Band { ChunkSel sel; int32_t cnt; hipStream_t s; int32_t* list; int32_t* count; uint32_t* wins; int32_t rows; uint4* compact; };
+                struct Band { ChunkSel sel; int32_t cnt; hipStream_t s; int32_t* list; int32_t* count; uint32_t* wins; int32_t rows; uint4* compact; PairRegion P; int32_t* redo; };
                 auto band = [&](int k, hipStream_t s) {
                     const ListRegion& r = W.band[k];
                     Band B{ChunkSel{two ? 1 : 0, stripe, k, nullptr, 0}, two ? ((stripes + 1 - k) / 2) * stripe : nchunks, s,
-                           reinterpret_cast<int32_t*>(wins4 + r.list), band_count + k, wins4 + r.wins, 0, compact_on ? reinterpret_cast<uint4*>(wins4 + r.compact) : nullptr};
+                           reinterpret_cast<int32_t*>(wins4 + r.list), band_count + k, wins4 + r.wins, 0, compact_on ? reinterpret_cast<uint4*>(wins4 + r.compact) : nullptr,
+                           PairRegion{reinterpret_cast<uint64_t*>(wins4 + r.pair_words), reinterpret_cast<int32_t*>(wins4 + r.pair_buckets), reinterpret_cast<int32_t*>(wins4 + r.pair_ctr),
+                                      bc7_pair_cap((int32_t)(two ? r.pair_cap : 2 * r.pair_cap))}, reinterpret_cast<int32_t*>(wins4 + r.pair_redo)};
                     B.rows = B.cnt * TPB;                                    // shares x listed blocks <= rows: the list scan's grid covers them (list_scan_parts)
                     if (!two) { B.list = list13; B.wins = wins4; B.rows = (int32_t)n; }     // one band: the global winner rows, both texel regions as one
                     return B;
@@ -2438,8 +2638,19 @@ void launch_bc7(const uint8_t* src, int64_t stride, int width, int height, uint8
                 auto head = [&](const Band& B) { scan_rgb(nullptr, nullptr, false, true, 0, B.sel, B.cnt, B.s); };
                 auto tail = [&](const Band& B) {
                     finish(std::integral_constant<int, 3>{}, nullptr, nullptr, B.list, B.count, nullptr, nullptr, gated(B, 1), B.cnt, B.s, nullptr, 0, nullptr, B.compact);
-                    scan_rgb(B.list, B.count, true, false, 1, ALL, B.cnt, B.s, B.wins, B.rows, B.compact);    // an empty list (the other order): returns at once
-                    finish(std::integral_constant<int, 4>{}, B.list, B.count, nullptr, nullptr, nullptr, nullptr, ALL, B.cnt, B.s, B.wins, B.rows, B.compact);
+                    if (pairs) {
+                        // the pairs the bound leaves (bc7_pair_build's header); the few blocks finish<8> defers take the full list scan behind it
+                        int32_t* redo_count = B.P.ctr + PAIR_CTR_REDO;
+                        hipLaunchKernelGGL(bc7_pair_build, dim3((unsigned)B.cnt), blk, 0, B.s, src, stride, bx, B.list, B.count, B.compact, alpha_err, S.channels, B.P, B.redo);
+                        hipLaunchKernelGGL(bc7_pair_scan, dim3((unsigned)((B.cnt + 1) / 2)), blk, 0, B.s, src, stride, bx, B.list, B.compact, S, B.P);
+                        finish(std::integral_constant<int, 8>{}, B.list, B.count, B.redo, redo_count, nullptr, B.P.ctr + PAIR_CTR_OVERFLOW, ALL, B.cnt, B.s,
+                               reinterpret_cast<const uint32_t*>(B.P.words), B.rows, B.compact);
+                        scan_rgb(B.redo, redo_count, true, false, 1, ALL, B.cnt, B.s, B.wins, B.rows);
+                        finish(std::integral_constant<int, 4>{}, B.redo, redo_count, nullptr, nullptr, nullptr, nullptr, ALL, B.cnt, B.s, B.wins, B.rows);
+                    } else {
+                        scan_rgb(B.list, B.count, true, false, 1, ALL, B.cnt, B.s, B.wins, B.rows, B.compact);    // an empty list (the other order): returns at once
+                        finish(std::integral_constant<int, 4>{}, B.list, B.count, nullptr, nullptr, nullptr, nullptr, ALL, B.cnt, B.s, B.wins, B.rows, B.compact);
+                    }
                     if (pilot) {
                         scan_rgb(nullptr, nullptr, true, false, 0, gated(B, 0), B.cnt, B.s);
                         finish(std::integral_constant<int, 0>{}, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, gated(B, 0), B.cnt, B.s);
@@ -2483,6 +2694,14 @@ void launch_bc7(const uint8_t* src, int64_t stride, int width, int height, uint8
                         ITW_CHECK(hipMemcpy(h, rgb_count, sizeof h, hipMemcpyDeviceToHost));
                         std::fprintf(stderr, "bc7 pilot: estimate %d of %d sampled blocks listed -> %s; lists %d + %d of %lld blocks\n", h[8], h[9], h[6] ? "bounded" : "reference order",
                                      h[3], h[4], (long long)n);
+                        for (int k = 0; k < 2 && pairs; k++) {
+                            int32_t c[PAIR_CTR_WORDS];
+                            ITW_CHECK(hipMemcpy(c, (k ? Bb : A).P.ctr, sizeof c, hipMemcpyDeviceToHost));
+                            long long sum = 0; int32_t top = 0;
+                            for (int i = 0; i < 64; i++) { sum += c[i]; top = c[i] > top ? c[i] : top; }
+                            std::fprintf(stderr, "bc7 pairs: band %d: %lld pairs, fullest bucket %d of %d, overflow %d, deferred to the full scan %d\n", k, sum, top, (k ? Bb : A).P.cap,
+                                         c[PAIR_CTR_OVERFLOW], c[PAIR_CTR_REDO]);
+                        }
                     }
                 }
             } else {
