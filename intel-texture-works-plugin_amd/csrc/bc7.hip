@@ -27,7 +27,10 @@
 //     The slow profiles (every shape scanned) run the BOUNDED order instead (round 4: modes 1/3/7 last, only for the blocks an
 //     exact lower bound cannot exclude, compacted into lists) as two interleaved bands on two streams, and for the RGB
 //     profile a pilot kernel picks that order or the reference's per call, on the device (round 5; launch_bc7);
-//     under the RGB profile the list scan of that order fits only the (block, shape) pairs the bound leaves (PAIRS, bc7_pair_build);
+//     under the RGB profile the list scan of that order fits only the (block, shape) pairs the bound leaves (PAIRS, above bc7_pair_scan):
+//     bc7_bounded_setup (counters, where the pairs go) -> bc7_scan_all {0,2} per band -> bc7_pilot_estimate -> bc7_finish_all<3> (modes 0,2,4,5,6,
+//     the 64 bounds once, the list, the compact texels and the pairs bucketed by shape) -> bc7_pair_scan -> bc7_finish_all<8> -> the full list
+//     scan and bc7_finish_all<4> for the few blocks it defers;
 //   * the scans produce a candidate's ERROR and nothing else: the level a texel takes
 //     and the packed indices matter for a mode's winner alone, so the winner record is
 //     {error, shape} and the finish kernel recomputes endpoints and indices of the
@@ -1379,8 +1382,15 @@ __device__ __forceinline__ void merge_packed_parts(Win& w, Lane& ln, const uint3
 }
 
 // the pair route of the RGB bounded order (PAIRS, below bc7_pilot_estimate)
-struct PairRegion { uint64_t* words; int32_t* buckets; int32_t* ctr; int32_t cap; };   // ctr: [0..63] bucket lengths, [64] overflow, [65] the second list's length
-constexpr int PAIR_CTR_OVERFLOW = 64, PAIR_CTR_REDO = 65, PAIR_CTR_WORDS = 68;
+// ctr, a band's counters: [0..63] bucket lengths, [64] overflow, [65] the second list's length, [66] the band's list length, [68..] its PairTarget
+struct PairRegion { uint64_t* words; int32_t* buckets; int32_t* ctr; int32_t cap; };
+constexpr int PAIR_CTR_OVERFLOW = 64, PAIR_CTR_REDO = 65, PAIR_CTR_LIST = 66, PAIR_CTR_TARGET = 68, PAIR_CTR_WORDS = 80;
+// where bc7_finish_all<3> leaves a band's pairs (words == nullptr: the pair route is off).  It lies in device memory at a fixed distance from the
+// list length the kernel is given anyway (bc7_bounded_setup writes it at the start of the call) and is read at the end of the kernel: as kernel
+// arguments the nine words are loaded at the kernel's entry and held in SGPRs through the whole refinement, which answers with more spills
+// (tools/kernel_resources.py)
+struct PairTarget { PairRegion P; int32_t* redo; };
+static_assert(sizeof(PairTarget) <= (PAIR_CTR_WORDS - PAIR_CTR_TARGET) * sizeof(int32_t) && PAIR_CTR_TARGET % 2 == 0 && PAIR_CTR_WORDS % 4 == 0, "PairTarget behind the counters");
 constexpr int PAIR_MAX_PER_BLOCK = 32;
 constexpr unsigned long long PAIR_WORD_HEAVY = ~0ull - 1ull;        // no merged word takes this value: errors stay below 2^23
 
@@ -1570,6 +1580,8 @@ bc7_finish_all(const uint8_t* __restrict__ src, int64_t stride, int32_t blocks_x
     __shared__ unsigned short s_seed16[2048];
     __shared__ uint32_t s_seed32[2048];
     __shared__ uint2 s_pal[(ITW_BC7_LANE_PAL ? LANE_PAL_LEVELS : 8) * TPB];   // refinement: a palette per subset of the lane's winner
+    __shared__ int32_t s_at[PHASE == 3 ? TPB / 64 : 1][64];         // PAIRS: per (wave, shape) the survivors, then where they go in the bucket (its own
+                                                                    // kilobyte: other waves of the workgroup still use s_pal when the first one gets here)
     if (sel.gate && *sel.gate != sel.want) return;                   // the pilot chose the other order (whole grid: no barrier is pending)
     const int32_t nact = LISTED ? *in_count : nblocks;
     const int32_t chunk = LISTED ? (int32_t)blockIdx.x : sel_chunk(sel, (int32_t)blockIdx.x);
@@ -1616,11 +1628,11 @@ bc7_finish_all(const uint8_t* __restrict__ src, int64_t stride, int32_t blocks_x
     }
     bool redo = false;
     if (PHASE == 8) {
-        // PAIRS (bc7_pair_build's header): `wins4` is the band's merged words, two per listed block -- the ordered argmin (fast error << 32 |
+        // PAIRS (bc7_pair_scan's header): `wins4` is the band's merged words, two per listed block -- the ordered argmin (fast error << 32 |
         // rank key) over the shapes the bound leaves, ~0 where it leaves none -- and `out_count7` its overflow word
         const unsigned long long* pw = reinterpret_cast<const unsigned long long*>(wins4) + 2 * (int64_t)slot;
         const int32_t inc = ln.best_err;
-        const bool heavy = pw[0] == PAIR_WORD_HEAVY;          // bc7_pair_build already put the block on the second list
+        const bool heavy = pw[0] == PAIR_WORD_HEAVY;          // bc7_finish_all<3> already put the block on the second list
         redo = !heavy && *out_count7 != 0;                   // a bucket overflowed: the whole band takes the full list scan
         const bool use = !heavy && !redo;
         const unsigned long long v1 = (use && S.fastSkipTreshold_mode1 > 0) ? pw[0] : ~0ull, v3 = (use && S.fastSkipTreshold_mode3 > 0) ? pw[1] : ~0ull;
@@ -1682,22 +1694,80 @@ bc7_finish_all(const uint8_t* __restrict__ src, int64_t stride, int32_t blocks_x
         const float lim = (float)(inc - ln.opaque_err) - 0.5f;      // errors are integers: a bound above inc - 1 already rules the shape out
         const float lim7 = (float)inc - 0.5f;                        // mode 7 carries no opaque term
         const bool with7 = PHASE == 5 && out_list7 != nullptr;       // wave-uniform
+        // PAIRS (header above bc7_pair_scan): this launch also leaves the (block, shape) pairs of the listed blocks, so every shape is
+        // bounded for every lane -- no early exit, no bail -- and the lane keeps a bit per shape instead of `need` alone
+        // CONTRACT of PHASE 3: `out_count` is word PAIR_CTR_LIST of a band's counter block that bc7_bounded_setup has filled in this call, so the
+        // band's PairTarget lies PAIR_CTR_TARGET - PAIR_CTR_LIST words behind it (launch_bc7's `finish` refuses any other pointer)
+        const PairTarget* target = nullptr;
+        if (PHASE == 3) target = reinterpret_cast<const PairTarget*>(out_count + (PAIR_CTR_TARGET - PAIR_CTR_LIST));
+        const bool pairs = PHASE == 3 && target->P.words != nullptr; // grid-uniform
         bool need = !live, need7 = !live || !with7;                  // idle lanes never hold the loop up
+        unsigned long long mine = 0, any = 0;                        // shapes whose bound is below `lim`: the lane's, the wave's (scalar)
 #pragma unroll 1
         for (int shape = 0; shape < 64; shape++) {
-            if (__all(need && need7)) break;
-            // a wave most of whose blocks need the modes anyway stops bounding the others (visiting a block is always allowed):
-            // content the bound does not separate pays for a few shapes, not for 64
-            if (shape == BOUND_BAIL_AFTER && __popcll(__ballot(need && need7)) >= BOUND_BAIL_LANES) { need = true; need7 = true; break; }
+            if (!pairs) {
+                if (__all(need && need7)) break;
+                // a wave most of whose blocks need the modes anyway stops bounding the others (visiting a block is always allowed):
+                // content the bound does not separate pays for a few shapes, not for 64
+                if (shape == BOUND_BAIL_AFTER && __popcll(__ballot(need && need7)) >= BOUND_BAIL_LANES) { need = true; need7 = true; break; }
+            }
             const float lb = two_subset_bound(shape, ln.tx.pl, full);
-            need = need || !(lb >= lim);
+            const bool in = !(lb >= lim);
+            need = need || in;
             need7 = need7 || !(lb >= lim7);
+            if (pairs) {
+                mine |= (live && in) ? (1ull << shape) : 0ull;
+                any |= __ballot(live && in) ? (1ull << shape) : 0ull;
+            }
         }
         const int32_t pos = append_to_list(out_list, out_count, live && need, b);
         if (out_compact && pos >= 0) {                              // the listed block's texels, in list order (load_block_compact)
             uint4* c = out_compact + (int64_t)pos * 4;
 #pragma unroll
             for (int y = 0; y < 4; y++) c[y] = make_uint4(ln.tx.w[y * 4 + 0], ln.tx.w[y * 4 + 1], ln.tx.w[y * 4 + 2], ln.tx.w[y * 4 + 3]);
+        }
+        if (pairs) {
+            // `pos` is the block's slot: its merged words, its compact texels, what the buckets hold.  Clear the words; a block more than
+            // half of whose shapes survive (photograph-like content inside a surface the pilot gave the bounded order) is cheaper in the
+            // full list scan, which takes the 64 shapes without rank keys: straight to the second list, no pairs, its words say so
+            // (lane and wave formed here, not from an expression of threadIdx the kernel's head also has: that one would be kept -- spilled --
+            // through the refinement)
+            const int lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+            const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+            const PairRegion P = target->P;
+            int32_t* pair_redo = target->redo;
+            const bool heavy = __popcll(mine) > PAIR_MAX_PER_BLOCK;
+            if (pos >= 0) { P.words[2 * (int64_t)pos] = heavy ? PAIR_WORD_HEAVY : ~0ull; P.words[2 * (int64_t)pos + 1] = ~0ull; }
+            if (heavy) mine = 0;
+            append_to_list(pair_redo, P.ctr + PAIR_CTR_REDO, heavy, b);
+            // survivors per (wave, shape): lane s carries shape s's count (shapes nobody in the wave keeps are not visited).  No global
+            // atomic per (wave, shape): each one waited for, that made the first builder latency bound (1.0 ms instead of 0.1)
+            int32_t k = 0;
+            for (unsigned long long rest = any; rest; rest &= rest - 1ull) {
+                const int shape = __builtin_amdgcn_readfirstlane((int)__builtin_ctzll(rest));
+                const int32_t c = (int32_t)__popcll(__ballot((mine >> shape) & 1ull));
+                k = (lane == shape) ? c : k;
+            }
+            s_at[wave][lane] = k;
+            __syncthreads();
+            if (threadIdx.x < 64u) {                                 // the workgroup's stretch of each bucket: 64 atomics, one instruction
+                int32_t t = 0;
+#pragma unroll
+                for (int w = 0; w < TPB / 64; w++) t += s_at[w][lane];
+                int32_t base = t ? atomicAdd(P.ctr + lane, t) : 0;
+                if (base + t > P.cap) { P.ctr[PAIR_CTR_OVERFLOW] = 1; base = -1; }
+#pragma unroll
+                for (int w = 0; w < TPB / 64; w++) { const int32_t c = s_at[w][lane]; s_at[w][lane] = base; base = base < 0 ? -1 : base + c; }
+            }
+            __syncthreads();
+            const int32_t at = s_at[wave][lane];                     // lane s: where the wave's survivors of shape s go
+            for (unsigned long long rest = any; rest; rest &= rest - 1ull) {
+                const int shape = __builtin_amdgcn_readfirstlane((int)__builtin_ctzll(rest));
+                const bool in = (mine >> shape) & 1ull;
+                const unsigned long long m = __ballot(in);
+                const int32_t base = __builtin_amdgcn_readlane(at, shape);
+                if (in && base >= 0) P.buckets[(int64_t)shape * P.cap + base + (int32_t)__popcll(m & ((1ull << lane) - 1ull))] = pos;
+            }
         }
         if (with7) append_to_list(out_list7, out_count7, live && need7, b);
     }
@@ -1762,6 +1832,20 @@ bc7_pilot_estimate(const uint8_t* __restrict__ src, int64_t stride, int32_t bloc
     }
 }
 
+// start of an RGB bounded call: the list lengths, the pilot's words and both bands' pair counters start at zero (`counters`: 16 words, then
+// PAIR_CTR_WORDS per band), and each band's PairTarget goes behind its pair counters
+__global__ void __launch_bounds__(TPB) bc7_bounded_setup(int32_t* __restrict__ counters, const PairTarget t0, const PairTarget t1)
+{
+    for (int i = (int)threadIdx.x; i < 16 + 2 * PAIR_CTR_WORDS; i += TPB) {
+        const int j = i < 16 ? 0 : (i - 16) % PAIR_CTR_WORDS;
+        if (i < 16 || j < PAIR_CTR_TARGET) counters[i] = 0;
+    }
+    if (threadIdx.x == 0) {
+        *reinterpret_cast<PairTarget*>(counters + 16 + PAIR_CTR_TARGET) = t0;
+        *reinterpret_cast<PairTarget*>(counters + 16 + PAIR_CTR_WORDS + PAIR_CTR_TARGET) = t1;
+    }
+}
+
 // ---- PAIRS: the list scan of the RGB bounded order, cut down to the (block, shape) pairs the bound cannot exclude ---------------
 // bc7_finish_all<3> lists a block as soon as ONE shape's two_subset_bound is below the incumbent `inc`; the list scan then fits all 64
 // shapes of it, both modes.  On the bench surface 1.6 of a listed block's 64 shapes have a bound below inc (profiles/bc7_pair_survival.txt).
@@ -1775,81 +1859,19 @@ bc7_pilot_estimate(const uint8_t* __restrict__ src, int64_t stride, int32_t bloc
 //     E1 >= inc is the answer needed, and those few blocks take the full route: they go to a second list, the full list scan
 //     (bc7_scan_all, split) and bc7_finish_all<4> run over it from the untouched incumbent.  Mode 3 is judged against the pre-mode-1 inc
 //     (a superset of its own P1) and commits against the live best error.
-// Three steps between finish<3> and the refinement, per band:
-//   bc7_pair_build   lanes = listed blocks: the 64 bounds again (the pilot's arithmetic), the survivors appended to one bucket per
-//                    shape -- counted per workgroup in LDS, one atomic per (workgroup, shape) -- so that every wave of the scan is
-//                    shape-uniform (scalar subset masks); clears the block's two merged words.  Blocks with more than 32 survivors go
-//                    to the second list at once;
+// Three steps, per band (a block's 64 bounds are evaluated once: a separate builder kernel behind finish<3> used to evaluate them again):
+//   bc7_finish_all<3> with the pair route on, its bound loop bounds every shape for every lane (no early exit and no bail: a listed
+//                    block needs all 64 answers, and a wave that bailed would have to send 64 blocks through the full list scan, which
+//                    costs more than the 60 bounds it saves) and keeps a bit per shape.  Behind the list append (the list position is
+//                    the block's slot) it clears the block's two merged words and appends the survivors to one bucket per shape --
+//                    counted per workgroup in LDS, one atomic per (workgroup, shape) -- so that every wave of the scan is shape-uniform
+//                    (scalar subset masks).  Blocks with more than 32 survivors go to the second list at once;
 //   bc7_pair_scan    lanes = pairs of one shape, grid-stride over wave tiles of 64 pairs: search_two_subset over that one shape, its
 //                    rank key, and the ordered argmin (error, then key; keys are distinct) as a 64-bit atomicMin of (error << 32 | key)
 //                    into one word per (listed block, mode) -- no share table, no merge;
 //   bc7_finish_all<8> reads the words, refines, commits or defers the block to the second list.
 // A bucket that overflows (photograph-like content that slipped past the pilot: nearly every shape survives) raises the band's overflow
 // word: the pair scan returns at once and finish<8> defers every listed block, i.e. the band runs the full list scan.  Same bytes.
-
-__global__ void __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(4, 4)))
-bc7_pair_build(const uint8_t* __restrict__ src, int64_t stride, int32_t blocks_x, const int32_t* __restrict__ list, const int32_t* __restrict__ count,
-               const uint4* __restrict__ compact, const int32_t* __restrict__ inc_err, const int channels, const PairRegion P, int32_t* __restrict__ redo)
-{
-    __shared__ int32_t s_at[TPB / 64][64];                          // per (wave, shape): survivors, then where they go in the bucket
-    const int32_t nact = *count;
-    if ((int32_t)blockIdx.x * TPB >= nact) return;                   // whole workgroup: no barrier is pending
-    const int32_t gid = (int32_t)blockIdx.x * TPB + threadIdx.x;
-    const bool live = gid < nact;
-    const int32_t slot = live ? gid : nact - 1;
-    const int32_t b = list[slot];
-    Tex tx;
-    if (compact) load_block_compact(tx, compact, slot); else load_block<false>(tx, src, stride, blocks_x, b);
-    int32_t opaque = 0;
-    if (channels == 4) {
-        uint32_t e = 0;
-#pragma unroll
-        for (int d = 0; d < 4; d++) { const uint32_t x = ~tx.pl[3][d]; e = udot4(x, x, e); }
-        opaque = (int32_t)e;
-    }
-    if (live) { P.words[2 * (int64_t)slot] = ~0ull; P.words[2 * (int64_t)slot + 1] = ~0ull; }
-    IStats<3> full;
-    stats_int<3>(full, tx.pl, whole_block());
-    const float lim = (float)(inc_err[b] - opaque) - 0.5f;          // bc7_finish_all<3>'s rule
-    const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6);
-    // survivors of the lane's block as a bit per shape; per (wave, shape) their number.  No global atomic inside this loop: one per
-    // (wave, shape), each waited for, made the kernel latency bound (1.0 ms for 157 000 blocks instead of 0.1)
-    unsigned long long mine = 0;
-#pragma unroll 1
-    for (int shape = 0; shape < 64; shape++) {
-        const bool in = live && !(two_subset_bound(shape, tx.pl, full) >= lim);
-        mine |= in ? (1ull << shape) : 0ull;
-    }
-    // a block more than half of whose shapes survive (photograph-like content inside a surface the pilot gave the bounded order) is cheaper
-    // in the full list scan, which takes the 64 shapes without rank keys: straight to the second list, no pairs, its words say so
-    const bool heavy = __popcll(mine) > PAIR_MAX_PER_BLOCK;
-    if (heavy) { mine = 0; P.words[2 * (int64_t)slot] = PAIR_WORD_HEAVY; }
-    append_to_list(redo, P.ctr + PAIR_CTR_REDO, heavy, b);
-#pragma unroll 1
-    for (int shape = 0; shape < 64; shape++) {
-        const unsigned long long m = __ballot((mine >> shape) & 1ull);
-        if (lane == 0) s_at[wave][shape] = (int32_t)__popcll(m);
-    }
-    __syncthreads();
-    if (threadIdx.x < 64u) {                                         // the workgroup's stretch of each bucket: 64 atomics, one instruction
-        const int shape = (int)threadIdx.x;
-        int32_t k = 0;
-#pragma unroll
-        for (int w = 0; w < TPB / 64; w++) k += s_at[w][shape];
-        int32_t base = k ? atomicAdd(P.ctr + shape, k) : 0;
-        if (base + k > P.cap) { P.ctr[PAIR_CTR_OVERFLOW] = 1; base = -1; }
-#pragma unroll
-        for (int w = 0; w < TPB / 64; w++) { const int32_t c = s_at[w][shape]; s_at[w][shape] = base; base = base < 0 ? -1 : base + c; }
-    }
-    __syncthreads();
-#pragma unroll 1
-    for (int shape = 0; shape < 64; shape++) {
-        const bool in = (mine >> shape) & 1ull;
-        const unsigned long long m = __ballot(in);
-        const int32_t base = s_at[wave][shape];
-        if (in && base >= 0) P.buckets[(int64_t)shape * P.cap + base + (int32_t)__popcll(m & ((1ull << lane) - 1ull))] = slot;
-    }
-}
 
 __global__ void __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(4, 4)))
 bc7_pair_scan(const uint8_t* __restrict__ src, int64_t stride, int32_t blocks_x, const int32_t* __restrict__ list, const uint4* __restrict__ compact,
@@ -2216,7 +2238,7 @@ static bool bc7_compact_lists()
     return on;
 }
 // ITW_BC7_PAIRS=0: the RGB bounded order's list scan fits all 64 shapes of every listed block (round 4) instead of the (block, shape) pairs
-// the bound leaves (bc7_pair_build).  ITW_BC7_PAIR_CAP=<n>: lowers a shape bucket's capacity (never raises it): a small value forces the
+// the bound leaves (bc7_pair_scan's header).  ITW_BC7_PAIR_CAP=<n>: lowers a shape bucket's capacity (never raises it): a small value forces the
 // overflow route.  Both are read at every call -- the workspace layout does not depend on them -- so one process can compare the routes.
 static bool bc7_pairs_on()
 {
@@ -2278,7 +2300,7 @@ static size_t wide_workspace_bytes(size_t n)
 // fused shape, in 4-byte words from the start of the workspace (every region starts on a 16-byte boundary)
 // a list of blocks for modes 1/3 with what its split scan and refinement need: block ids [cap], winners of the scan's shares [5 rows][cap]
 // (rows 2, 3 used: list_scan_parts x listed <= cap), the listed blocks' texels [cap] x 64 B in list order
-// pairs (bc7_pair_build): per band the merged words [cap] x 2 x 8 B, the second list [cap], 64 shape buckets of cap / 8 listed slots and (behind the
+// pairs (bc7_pair_scan's header): per band the merged words [cap] x 2 x 8 B, the second list [cap], 64 shape buckets of cap / 8 listed slots and (behind the
 // 16 counters) PAIR_CTR_WORDS counters; each kind's two halves are contiguous, so a call without bands uses them as one
 struct ListRegion { size_t list, wins, compact, cap, pair_words, pair_redo, pair_buckets, pair_ctr, pair_cap; };
 struct FusedLayout { size_t inc, list0, list1, list2, counts, words; ListRegion band[2]; };
@@ -2314,7 +2336,7 @@ static FusedLayout fused_layout(size_t n, const FusedNeeds& need)
     W.list1 = o;    o = up4(o + lcap);
     W.list2 = o;    o = up4(o + lcap);
     W.counts = o;   o += 16;                                       // list lengths, the pilot's verdict
-    for (int k = 0; k < 2; k++) { W.band[k].pair_ctr = o; o += PAIR_CTR_WORDS; }   // (contiguous with them: one memset)
+    for (int k = 0; k < 2; k++) { W.band[k].pair_ctr = o; o += PAIR_CTR_WORDS; }   // (contiguous with them: bc7_bounded_setup clears all of it)
     for (int k = 0; k < 2; k++) {                                  // the two bands: lists and share winners ...
         ListRegion& r = W.band[k];
         r.cap = (nchunks / 2 + 65) * TPB;                          // (a band is whole stripes of up to 64 chunks)
@@ -2493,7 +2515,6 @@ void launch_bc7(const uint8_t* src, int64_t stride, int width, int height, uint8
             int32_t* list7 = reinterpret_cast<int32_t*>(wins4 + W.list2);                      // [n] block ids (RGBA profiles, bounded order incl. mode 7)
             int32_t* rgb_count = reinterpret_cast<int32_t*>(wins4 + W.counts);                 // the lists' lengths, the pilot's list length and verdict
             int32_t* count13 = rgb_count + 1;
-            int32_t* band_count = rgb_count + 3;                                               // [2]: the bands' lists for modes 1/3
             int32_t* pilot_flag = rgb_count + 6;                                               // the pilot's verdict
             int32_t* pilot_ctr = rgb_count + 8;                                                // [3]: its counts (listed, sampled, workgroups done)
             const bool compact_on = bc7_compact_lists();
@@ -2546,6 +2567,9 @@ void launch_bc7(const uint8_t* src, int64_t stride, int width, int height, uint8
                               int32_t* out_list7 = nullptr, int32_t* out_count7 = nullptr, ChunkSel sel = ChunkSel{0, 1, 0, nullptr, 0}, int32_t cnt = -1,
                               hipStream_t s = nullptr, const uint32_t* wins = nullptr, int32_t rows = 0, const uint4* in_compact = nullptr, uint4* out_compact = nullptr) {
                 constexpr int PH = decltype(phase)::value;
+                // bc7_finish_all<3> reads its PairTarget at a fixed distance from the list length: only a band's own counter block will do
+                if (PH == 3 && out_count != rgb_count + 16 + PAIR_CTR_LIST && out_count != rgb_count + 16 + PAIR_CTR_WORDS + PAIR_CTR_LIST)
+                    fail_msg("bc7_finish_all<3>: the list length must be word %d of a band's counter block", PAIR_CTR_LIST);
                 if (cnt < 0) cnt = nchunks;
                 if (!s) s = st;
                 if (!wins) { wins = wins4; rows = (int32_t)n; }
@@ -2616,7 +2640,6 @@ void launch_bc7(const uint8_t* src, int64_t stride, int width, int height, uint8
                 //    the pilot did not choose returns at once.  No host round trip, no block treated differently from its neighbours.
                 //    (A sample encoded ahead on a third stream was measured first: its chain of small launches could not get its share of a
                 //    chip the bands' scans fill, and the verdict arrived late: profiles/history/r05/r05d_bc7_pilot_timeline.txt.)
-                ITW_CHECK(hipMemsetAsync(rgb_count, 0, (16 + 2 * PAIR_CTR_WORDS) * sizeof(int32_t), st));
                 const bool two = bc7_bands() > 1 && aux && !aux->single && aux->stream && nchunks >= 32;
                 const bool pairs = bc7_pairs_on();
                 const bool pilot = two && bc7_pilot_threshold() >= 0 && aux->mid;
@@ -2627,9 +2650,10 @@ void launch_bc7(const uint8_t* src, int64_t stride, int width, int height, uint8
                 auto band = [&](int k, hipStream_t s) {
                     const ListRegion& r = W.band[k];
                     Band B{ChunkSel{two ? 1 : 0, stripe, k, nullptr, 0}, two ? ((stripes + 1 - k) / 2) * stripe : nchunks, s,
-                           reinterpret_cast<int32_t*>(wins4 + r.list), band_count + k, wins4 + r.wins, 0, compact_on ? reinterpret_cast<uint4*>(wins4 + r.compact) : nullptr,
+                           reinterpret_cast<int32_t*>(wins4 + r.list), nullptr, wins4 + r.wins, 0, compact_on ? reinterpret_cast<uint4*>(wins4 + r.compact) : nullptr,
                            PairRegion{reinterpret_cast<uint64_t*>(wins4 + r.pair_words), reinterpret_cast<int32_t*>(wins4 + r.pair_buckets), reinterpret_cast<int32_t*>(wins4 + r.pair_ctr),
                                       bc7_pair_cap((int32_t)(two ? r.pair_cap : 2 * r.pair_cap))}, reinterpret_cast<int32_t*>(wins4 + r.pair_redo)};
+                    B.count = B.P.ctr + PAIR_CTR_LIST;
                     B.rows = B.cnt * TPB;                                    // shares x listed blocks <= rows: the list scan's grid covers them (list_scan_parts)
                     if (!two) { B.list = list13; B.wins = wins4; B.rows = (int32_t)n; }     // one band: the global winner rows, both texel regions as one
                     return B;
@@ -2637,11 +2661,11 @@ void launch_bc7(const uint8_t* src, int64_t stride, int width, int height, uint8
                 auto gated = [&](const Band& B, int32_t want) { ChunkSel g = B.sel; if (pilot) { g.gate = pilot_flag; g.want = want; } return g; };
                 auto head = [&](const Band& B) { scan_rgb(nullptr, nullptr, false, true, 0, B.sel, B.cnt, B.s); };
                 auto tail = [&](const Band& B) {
+                    // pairs: finish<3> also leaves the (block, shape) pairs the bound cannot exclude, bucketed by shape (header above bc7_pair_scan)
                     finish(std::integral_constant<int, 3>{}, nullptr, nullptr, B.list, B.count, nullptr, nullptr, gated(B, 1), B.cnt, B.s, nullptr, 0, nullptr, B.compact);
                     if (pairs) {
-                        // the pairs the bound leaves (bc7_pair_build's header); the few blocks finish<8> defers take the full list scan behind it
+                        // the few blocks finish<8> defers take the full list scan behind it
                         int32_t* redo_count = B.P.ctr + PAIR_CTR_REDO;
-                        hipLaunchKernelGGL(bc7_pair_build, dim3((unsigned)B.cnt), blk, 0, B.s, src, stride, bx, B.list, B.count, B.compact, alpha_err, S.channels, B.P, B.redo);
                         hipLaunchKernelGGL(bc7_pair_scan, dim3((unsigned)((B.cnt + 1) / 2)), blk, 0, B.s, src, stride, bx, B.list, B.compact, S, B.P);
                         finish(std::integral_constant<int, 8>{}, B.list, B.count, B.redo, redo_count, nullptr, B.P.ctr + PAIR_CTR_OVERFLOW, ALL, B.cnt, B.s,
                                reinterpret_cast<const uint32_t*>(B.P.words), B.rows, B.compact);
@@ -2656,8 +2680,14 @@ void launch_bc7(const uint8_t* src, int64_t stride, int width, int height, uint8
                         finish(std::integral_constant<int, 0>{}, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, gated(B, 0), B.cnt, B.s);
                     }
                 };
+                // the call's counters start at zero, each band's PairTarget behind its pair counters (one small launch where a memset was)
+                auto setup = [&](const Band& A, const Band& Bb) {
+                    const PairTarget off{PairRegion{nullptr, nullptr, nullptr, 0}, nullptr};
+                    hipLaunchKernelGGL(bc7_bounded_setup, dim3(1), blk, 0, st, rgb_count, pairs ? PairTarget{A.P, A.redo} : off, pairs ? PairTarget{Bb.P, Bb.redo} : off);
+                };
                 if (!two) {
                     const Band B = band(0, st);
+                    setup(B, B);
                     const bool probe = aux && aux->probe && aux->verdict && aux->verdict->event;
                     if (probe) scan_rgb(nullptr, nullptr, false, true, 0, ChunkSel{2, 1, 0, nullptr, 0}, (nchunks + 7) / 8, st);
                     else head(B);
@@ -2674,9 +2704,10 @@ void launch_bc7(const uint8_t* src, int64_t stride, int width, int height, uint8
                     tail(B);
                 } else {
                     hipStream_t s2 = aux->stream;
-                    ITW_CHECK(hipEventRecord(aux->fork, st));                // whatever feeds `src` on st (an upload), and the memset above
-                    ITW_CHECK(hipStreamWaitEvent(s2, aux->fork, 0));
                     const Band A = band(0, st), Bb = band(1, s2);
+                    setup(A, Bb);
+                    ITW_CHECK(hipEventRecord(aux->fork, st));                // whatever feeds `src` on st (an upload), and the setup above
+                    ITW_CHECK(hipStreamWaitEvent(s2, aux->fork, 0));
                     head(Bb); head(A);
                     if (pilot) {
                         const dim3 grid((unsigned)((A.cnt + 7) / 8));
@@ -2689,11 +2720,11 @@ void launch_bc7(const uint8_t* src, int64_t stride, int width, int height, uint8
                     ITW_CHECK(hipEventRecord(aux->join, s2));
                     ITW_CHECK(hipStreamWaitEvent(st, aux->join, 0));
                     if (bc7_pilot_debug()) {
-                        int32_t h[16];
+                        int32_t h[16 + 2 * PAIR_CTR_WORDS];
                         ITW_CHECK(hipStreamSynchronize(st));
                         ITW_CHECK(hipMemcpy(h, rgb_count, sizeof h, hipMemcpyDeviceToHost));
                         std::fprintf(stderr, "bc7 pilot: estimate %d of %d sampled blocks listed -> %s; lists %d + %d of %lld blocks\n", h[8], h[9], h[6] ? "bounded" : "reference order",
-                                     h[3], h[4], (long long)n);
+                                     h[16 + PAIR_CTR_LIST], h[16 + PAIR_CTR_WORDS + PAIR_CTR_LIST], (long long)n);
                         for (int k = 0; k < 2 && pairs; k++) {
                             int32_t c[PAIR_CTR_WORDS];
                             ITW_CHECK(hipMemcpy(c, (k ? Bb : A).P.ctr, sizeof c, hipMemcpyDeviceToHost));

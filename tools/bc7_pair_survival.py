@@ -2,7 +2,7 @@
 oracle's own functions: oracle_bc7_block without modes 1/3 for the incumbent `inc` (+ 1 when a mode 4/5/6 holds the block, as
 bc7_finish_all<3> does), oracle_bc7_two_subset_bound for LB, oracle_bc7_part_fast_errors for the fast errors and rank keys.
   listed        blocks with some LB(s) < inc - 0.5 (what finish<3> lists; the full list scan fits 64 shapes of each, both modes)
-  P1            the shapes of a listed block with LB(s) < inc - 0.5: what bc7_pair_build leaves (pass 1)
+  P1            the shapes of a listed block with LB(s) < inc - 0.5: what bc7_finish_all<3> leaves as pairs (pass 1)
   P2            per mode, where the P1 winner's fast error E1 >= inc: shapes outside P1 with LB(s) <= E1 (pass 2 of a two-pass scheme)
   open          (listed block, mode) with E1 >= inc: the kernels refine the P1 winner anyway and send the block to the full scan only if
                 that refinement gets below the incumbent (the count of those comes from the GPU: ITW_BC7_PILOT_DEBUG=1)
@@ -76,7 +76,7 @@ def main():
     z = np.load(os.path.join(ROOT, "tests", "golden", "inputs.npz"))
     print("# tools/bc7_pair_survival.py: `slow`, random blocks of each surface (seed 20261016); per listed block unless said otherwise")
     print("# left = (|P1| + (|P2(mode 1)| + |P2(mode 3)|) / 2) / 64: shape evaluations of a two-pass scheme against the full list scan's")
-    print("# kernels = what bc7_pair_build sends on: |P1| of the blocks with |P1| <= 32 as pairs, 64 shapes of the heavier ones, / 64")
+    print("# kernels = what bc7_finish_all<3> sends on: |P1| of the blocks with |P1| <= 32 as pairs, 64 shapes of the heavier ones, / 64")
     print(f"{'content':16s} {'blocks':>6s} {'listed':>7s} {'P1 mean':>8s} {'median':>6s} {'p90':>5s} {'P2 m1':>7s} {'P2 m3':>6s} {'left':>9s} {'open m1':>8s} {'m3':>6s} {'heavy':>7s} {'kernels':>9s}")
     for name, img, n in (("bench surface I3", surfaces.ldr_smooth(4096, 4096, surfaces.SEED), nb), ("baboon", z["baboon"], npic), ("monkey", z["monkey"], npic)):
         blocks = planar_blocks(img)
