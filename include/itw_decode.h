@@ -8,7 +8,9 @@
 #ifndef ITW_DECODE_H
 #define ITW_DECODE_H
 
+#include <stddef.h>
 #include <stdint.h>
+#include "ispc_texcomp.h"   /* rgba_surface */
 
 #ifdef __cplusplus
 extern "C" {
@@ -28,6 +30,54 @@ extern "C" {
  * Width and height must be multiples of 4, except for BC4 / BC5, whose streams may end in partial blocks (cropped on store).
  * Returns 0, or -1 for an unsupported format / misaligned sizes. */
 int itwDecodeBlocks(int dxgi_format, const uint8_t* blocks, int width, int height, uint8_t* out, int64_t out_stride, int32_t* modes);
+
+/* ---- measuring an encoded stream against its source ------------------------------------------------------------------------------
+ * What a caller would compute by decoding the stream (the decoders above, at the padded size) and comparing the texels of `source`
+ * with the decoded ones, code by code, as integers -- done in one kernel that decodes into registers, so the decoded surface never
+ * exists in memory.  A "code" is the 8-bit channel value for the LDR formats and the 16-bit half-float bit pattern, read as an
+ * unsigned integer, for BC6H (the space BC6H interpolates in).  All four channels are always reported, the values the decoders fill
+ * in included (BC4 / BC5: 0 / 0 / 255, BC6H: alpha 0x3C00, BC1: its decoded alpha); the caller picks the channels that mean something.
+ * Every field is an integer: the same stream and source give the same bits on every run. */
+typedef struct itw_error_stats {
+    int32_t  dxgi_format, width, height;  /* what was measured: texels per row / rows actually compared */
+    uint32_t reserved_blocks;             /* blocks whose mode is -1 (reserved prefix); they decode as itwDecodeBlocks decodes them */
+    uint64_t blocks;                      /* ceil(width/4) * ceil(height/4) */
+    uint64_t sse[4];                      /* per channel R,G,B,A: sum over compared texels of (source code - decoded code)^2 */
+    uint32_t max_abs[4];                  /* per channel: largest |source code - decoded code| */
+    uint64_t worst_block_sse;             /* largest per-block sum of the four channels' squared differences */
+    uint32_t worst_block;                 /* raster index of the FIRST block that reaches it */
+    uint32_t _pad;
+    uint64_t mode_hist[16];               /* blocks per mode: BC7 0..7, BC6H 0..13 (itwDecodeBlocks' numbering), others all in [0] */
+} itw_error_stats;
+
+/* The most blocks one image may have: the worst block is found with one 64-bit atomic maximum over (block sse, inverted index), and
+ * BC6H's largest block sum, 64 * 0xFFFF^2 < 2^39, leaves 25 bits for the index.  A 16384 x 16384 surface has 2^24 blocks. */
+#define ITW_MEASURE_MAX_BLOCKS 33554432
+
+/* itwMeasureBlocks: `blocks` holds ceil(w/4)*ceil(h/4) tightly packed blocks in raster order for the w x h texels of `source` (any
+ * w, h >= 1, for every format: what itwCompressImageChain emits for such an image); texels of edge blocks that lie outside the
+ * source are padding and are not compared.  source: RGBA8, or RGBA16F bit patterns for BC6H; stride: any value >= the row's bytes.
+ * block_sse (optional, may be NULL): one uint64 per block in raster order, that block's sum over the four channels; worst_block_sse
+ * is the maximum of exactly these values, worst_block the first index that has it.
+ * stats_bytes must be sizeof(itw_error_stats) (the struct may grow at its end).
+ * `blocks`, source->ptr, `stats`, `block_sse` may each be a host or a device pointer; stats and block_sse are 8-byte aligned.  With any
+ * host pointer the call stages and returns synchronised.  With all of them on the device it is asynchronous on the calling thread's
+ * stream (itwSetStream), allocates nothing, writes every field of *stats on the device in stream order, and can be captured into a graph.
+ * Returns 0; -1 before any device work for an unknown format, a null pointer, width or height < 1, a stride below the row's bytes,
+ * a wrong stats_bytes, a misaligned stats / block_sse or more than ITW_MEASURE_MAX_BLOCKS blocks; -1 after a device failure (reported
+ * through the library's error mode, itw_amd.h). */
+int itwMeasureBlocks(int dxgi_format, const uint8_t* blocks, const rgba_surface* source, itw_error_stats* stats, size_t stats_bytes,
+                     uint64_t* block_sse);
+
+/* itwMeasureChain: `images` and the packed `blocks` as itwCompressImageChain lays them out (itw_dispatch.h): image i's blocks start
+ * at the summed sizes of the images before it (itwChainBytes); stats[i] describes image i.  The images are all host or all device
+ * pointers; `blocks` and `stats` may each be either.  Per-image launches on one stream; all-device calls are asynchronous. */
+int itwMeasureChain(const rgba_surface* images, int count, const uint8_t* blocks, int dxgi_format, itw_error_stats* stats, size_t stats_bytes);
+
+/* itwStatsPsnr: host arithmetic in double: 10*log10(255^2 * n / sum of sse[c]) over the channels c in channel_mask (bit 0 = R ..
+ * bit 3 = A), n = width * height * number of selected channels.  +inf when the sum is 0; NaN for a BC6H stats (a code-space PSNR of
+ * half floats is not a quantity this library defines) and for an empty mask. */
+double itwStatsPsnr(const itw_error_stats* stats, uint32_t channel_mask);
 
 #pragma GCC visibility pop
 #ifdef __cplusplus

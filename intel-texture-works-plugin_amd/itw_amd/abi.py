@@ -30,7 +30,7 @@ EXPORTED_SYMBOLS = tuple(
     # include/itw_bc45.h: the DirectXTex formats of the plugin
     + ["CompressBlocksBC4", "CompressBlocksBC5", "itwWarmupBC45"]
     # include/itw_decode.h: device decoders
-    + ["itwDecodeBlocks"]
+    + ["itwDecodeBlocks", "itwMeasureBlocks", "itwMeasureChain", "itwStatsPsnr"]
     # include/itw_dds.h: DDS container
     + ["itwDdsLevelBytes", "itwDdsHeaderBytes", "itwDdsFileBytes", "itwDdsWriteHeader", "itwDdsReadHeader", "itwDdsWriteFile"])
 # include/itw_test_hooks.h: exported by libispc_texcomp_test.so only (the same sources built with -DITW_TEST_HOOKS), never by the product
@@ -93,6 +93,55 @@ class MultiGpuStats(C.Structure):
                               "upload_ms": round(float(r.upload_ms), 4), "encode_ms": round(float(r.encode_ms), 4),
                               "gather_ms": round(float(r.gather_ms), 4), "span_ms": round(float(r.span_ms), 4)} for r in self.rank[:n]]}
 
+
+# the channels of a decoded texel that carry a format's own data (the others are fill values: itw_decode.h)
+OWN_CHANNELS = {"bc1": "rgb", "bc3": "rgba", "bc4": "r", "bc5": "rg", "bc6h": "rgb", "bc7": "rgba"}
+_DXGI_BASE = {71: "bc1", 72: "bc1", 77: "bc3", 78: "bc3", 80: "bc4", 83: "bc5", 95: "bc6h", 96: "bc6h", 98: "bc7", 99: "bc7"}
+
+
+def _channel_mask(channels):
+    """Bit mask (bit 0 = R .. bit 3 = A) of `channels`: a string of the letters r, g, b, a or an iterable of indices 0..3."""
+    mask = 0
+    for c in channels:
+        mask |= 1 << ("rgba".index(c.lower()) if isinstance(c, str) else int(c))
+    assert 0 <= mask < 16
+    return mask
+
+
+class ErrorStats(C.Structure):
+    """struct itw_error_stats (itw_decode.h): what itwMeasureBlocks reports, all integers."""
+    _fields_ = [("dxgi_format", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("reserved_blocks", C.c_uint32),
+                ("blocks", C.c_uint64), ("sse", C.c_uint64 * 4), ("max_abs", C.c_uint32 * 4), ("worst_block_sse", C.c_uint64),
+                ("worst_block", C.c_uint32), ("_pad", C.c_uint32), ("mode_hist", C.c_uint64 * 16)]
+
+    def _mask(self, channels):
+        return _channel_mask(OWN_CHANNELS[_DXGI_BASE[int(self.dxgi_format)]] if channels is None else channels)
+
+    def mse(self, channels=None):
+        """Mean squared code difference over `channels` ('rgb', 'a', (0, 1), ...; default: the format's own channels)."""
+        mask = self._mask(channels)
+        picked = [c for c in range(4) if mask >> c & 1]
+        return sum(int(self.sse[c]) for c in picked) / float(int(self.width) * int(self.height) * len(picked))
+
+    def psnr(self, channels=None):
+        """itwStatsPsnr over `channels`; ValueError for BC6H, whose codes are half-float bit patterns."""
+        if _DXGI_BASE.get(int(self.dxgi_format)) == "bc6h":
+            raise ValueError("PSNR is not defined for BC6H code differences; use sse / max_abs")
+        return float(lib().itwStatsPsnr(C.byref(self), self._mask(channels)))
+
+    def as_dict(self):
+        return {"dxgi_format": int(self.dxgi_format), "width": int(self.width), "height": int(self.height),
+                "reserved_blocks": int(self.reserved_blocks), "blocks": int(self.blocks), "sse": [int(v) for v in self.sse],
+                "max_abs": [int(v) for v in self.max_abs], "worst_block_sse": int(self.worst_block_sse), "worst_block": int(self.worst_block),
+                "mode_hist": [int(v) for v in self.mode_hist]}
+
+    def __eq__(self, other):
+        return isinstance(other, ErrorStats) and bytes(self) == bytes(other)
+
+    __hash__ = None
+
+
+assert C.sizeof(ErrorStats) == 216
 
 COMPRESSION_FUNC = C.CFUNCTYPE(None, C.POINTER(RgbaSurface), C.c_void_p)
 PROGRESS_FUNC = C.CFUNCTYPE(C.c_bool, C.c_int, C.c_int, C.c_void_p)
@@ -223,6 +272,12 @@ def _load(path, hooks):
         L.itwConvertToRGBA16FDevice.restype = C.c_int
         L.itwDecodeBlocks.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]
         L.itwDecodeBlocks.restype = C.c_int
+        L.itwMeasureBlocks.argtypes = [C.c_int, C.c_void_p, C.POINTER(RgbaSurface), C.c_void_p, C.c_size_t, C.c_void_p]
+        L.itwMeasureBlocks.restype = C.c_int
+        L.itwMeasureChain.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
+        L.itwMeasureChain.restype = C.c_int
+        L.itwStatsPsnr.argtypes = [C.POINTER(ErrorStats), C.c_uint32]
+        L.itwStatsPsnr.restype = C.c_double
         # DDS container (itw_dds.h)
         L.itwDdsLevelBytes.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
         L.itwDdsLevelBytes.restype = C.c_size_t
@@ -631,3 +686,90 @@ def decode(fmt, blocks, width, height, want_modes=False):
     if rc != 0:
         raise ValueError("itwDecodeBlocks: unsupported format or size")
     return (out, modes) if want_modes else out
+
+
+def measure_async(fmt, blocks, img, stats_out, block_map=None):
+    """The all-device form of itwMeasureBlocks: asynchronous on torch's current stream, nothing allocated, capturable into a graph.
+    blocks: CUDA uint8 tensor; img: CUDA tensor (H, W, 4), rows may be strided; stats_out: CUDA uint8 tensor of sizeof(ErrorStats) bytes
+    (read it back with stats_from_tensor); block_map (optional): CUDA int64 tensor, one element per block."""
+    import torch
+    assert blocks.is_cuda and blocks.dtype == torch.uint8 and blocks.is_contiguous()
+    assert img.is_cuda and img.dim() == 3 and img.shape[2] == 4 and img.stride(2) == 1 and img.stride(1) == 4
+    assert img.element_size() == (2 if fmt.split("_")[0] == "bc6h" else 1), "texel type does not match the format"
+    assert stats_out.is_cuda and stats_out.dtype == torch.uint8 and stats_out.is_contiguous() and stats_out.numel() == C.sizeof(ErrorStats)
+    h, w = img.shape[:2]
+    nb = ((w + 3) // 4) * ((h + 3) // 4)
+    assert blocks.numel() >= nb * BYTES_PER_BLOCK[fmt.split("_")[0]]
+    assert block_map is None or (block_map.is_cuda and block_map.dtype == torch.int64 and block_map.is_contiguous() and block_map.numel() >= nb)
+    with torch.cuda.device(img.device):
+        lib().itwSetStream(torch.cuda.current_stream(img.device).cuda_stream)
+        surf = RgbaSurface(img.data_ptr(), w, h, img.stride(0) * img.element_size())
+        rc = lib().itwMeasureBlocks(DXGI_FORMAT[fmt], blocks.data_ptr(), C.byref(surf), stats_out.data_ptr(), C.sizeof(ErrorStats),
+                                    block_map.data_ptr() if block_map is not None else None)
+    if rc != 0:
+        raise ValueError("itwMeasureBlocks: " + (last_error() or "bad arguments"))
+
+
+def stats_from_tensor(t):
+    """ErrorStats (or a list of them) from the bytes a device-side measurement wrote; synchronises with the tensor's stream through the copy."""
+    raw = t.cpu().numpy().tobytes()
+    n = C.sizeof(ErrorStats)
+    out = [ErrorStats.from_buffer_copy(raw[i:i + n]) for i in range(0, len(raw), n)]
+    return out[0] if len(out) == 1 and t.dim() == 1 else out
+
+
+def measure(fmt, blocks, img, want_block_map=False):
+    """itwMeasureBlocks: the integer error statistics of the stream `blocks` against its source `img`, decoded and compared on the GPU in
+    one kernel.  numpy arrays (host pointers) or CUDA tensors (device pointers), as for decode(); img is (H, W, 4) uint8, or uint16 /
+    int16 / float16 half bit patterns for bc6h, any H, W >= 1, and blocks holds ceil(W/4)*ceil(H/4) blocks.  fmt: a key of DXGI_FORMAT.
+    Returns an ErrorStats; with want_block_map also the per-block sums (uint64 numpy array, or int64 CUDA tensor)."""
+    import numpy as np
+    base = fmt.split("_")[0]
+    h, w = img.shape[:2]
+    nb = ((w + 3) // 4) * ((h + 3) // 4)
+    if isinstance(blocks, np.ndarray):
+        assert isinstance(img, np.ndarray) and img.ndim == 3 and img.shape[2] == 4 and img.strides[2] == img.itemsize and img.strides[1] == 4 * img.itemsize
+        assert img.itemsize == (2 if base == "bc6h" else 1), "texel type does not match the format"
+        blk = np.ascontiguousarray(blocks, dtype=np.uint8).reshape(-1)
+        assert blk.size >= nb * BYTES_PER_BLOCK[base]
+        st = ErrorStats()
+        bmap = np.empty(nb, dtype=np.uint64) if want_block_map else None
+        surf = RgbaSurface(img.ctypes.data, w, h, img.strides[0])
+        rc = lib().itwMeasureBlocks(DXGI_FORMAT[fmt], blk.ctypes.data, C.byref(surf), C.addressof(st), C.sizeof(ErrorStats),
+                                    bmap.ctypes.data if want_block_map else None)
+        if rc != 0:
+            raise ValueError("itwMeasureBlocks: " + (last_error() or "bad arguments"))
+    else:
+        import torch
+        raw = torch.empty(C.sizeof(ErrorStats), dtype=torch.uint8, device=blocks.device)
+        bmap = torch.empty(nb, dtype=torch.int64, device=blocks.device) if want_block_map else None
+        measure_async(fmt, blocks, img, raw, bmap)
+        st = stats_from_tensor(raw)
+    return (st, bmap) if want_block_map else st
+
+
+def measure_chain(fmt, blocks, levels):
+    """itwMeasureChain: one ErrorStats per image of a chain encoded by compress_chain(fmt, levels): `blocks` is its packed stream.
+    levels and blocks: numpy arrays, or CUDA tensors (then the call runs on torch's current stream and the result is copied back)."""
+    import numpy as np
+    base = fmt.split("_")[0]
+    total = sum(((lv.shape[1] + 3) // 4) * ((lv.shape[0] + 3) // 4) for lv in levels) * BYTES_PER_BLOCK[base]
+    arr = _surfaces(levels)
+    n = len(levels)
+    if isinstance(blocks, np.ndarray):
+        blk = np.ascontiguousarray(blocks, dtype=np.uint8).reshape(-1)
+        assert blk.size >= total
+        out = (ErrorStats * max(1, n))()
+        rc = lib().itwMeasureChain(C.cast(arr, C.c_void_p), n, blk.ctypes.data, DXGI_FORMAT[fmt], C.addressof(out), C.sizeof(ErrorStats))
+        res = [ErrorStats.from_buffer_copy(bytes(out[i])) for i in range(n)]
+    else:
+        import torch
+        assert blocks.is_cuda and blocks.dtype == torch.uint8 and blocks.is_contiguous() and blocks.numel() >= total
+        raw = torch.empty((max(1, n), C.sizeof(ErrorStats)), dtype=torch.uint8, device=blocks.device)
+        with torch.cuda.device(blocks.device):
+            lib().itwSetStream(torch.cuda.current_stream(blocks.device).cuda_stream)
+            rc = lib().itwMeasureChain(C.cast(arr, C.c_void_p), n, blocks.data_ptr(), DXGI_FORMAT[fmt], raw.data_ptr(), C.sizeof(ErrorStats))
+        res = stats_from_tensor(raw)[:n] if rc == 0 else None
+    if rc != 0:
+        raise ValueError("itwMeasureChain: " + (last_error() or "bad arguments"))
+    return res
