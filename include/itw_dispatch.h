@@ -86,7 +86,9 @@ void CompressImageBC6H_veryslow(const rgba_surface* input, uint8_t* output);
  * has many windows), and progress(i) is called once slice i-1 -- and
  * every slice before it -- is in `target`.  What a caller can observe of the difference:
  *   * when progress(i) returns false, slices < i are written like in the reference, and so may be up to W-1 slices after them (the
- *     rest of slice i-1's window); the window being encoded at that moment is drained and NOT copied back;
+ *     rest of slice i-1's window); the window being encoded at that moment is drained and NOT copied back -- bytes of `target` behind slice
+ *     i-1's window are not written, whether `target` is host or device memory (with `progress` set, a device target receives each window as
+ *     it retires instead of being written by the kernels in flight);
  *   * progress calls of one window arrive back to back;
  *   * `progress` runs on the calling thread while later windows are in flight on that thread's streams and staging buffers: it must not
  *     call back into this library on the same thread (Photoshop's SetProgress does not).

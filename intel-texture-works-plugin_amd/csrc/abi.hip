@@ -642,7 +642,10 @@ bool compress_sliced(const Job& j, const rgba_surface* src, uint8_t* dst, int sl
     uint8_t* in = src_dev ? nullptr : (uint8_t*)grow(tls.d_in, tls.in_cap, pitch * rows);
     const uint8_t* d_src = src_dev ? src->ptr : in;
     const int64_t d_stride = src_dev ? (int64_t)src->stride : (int64_t)pitch;
-    uint8_t* d_dst = dst_dev ? dst : (uint8_t*)grow(tls.d_out, tls.out_cap, out_bytes);
+    // A device `target` is written by the kernels themselves -- unless `progress` can stop the job: the windows in flight at that moment must
+    // not reach `target` (itw_dispatch.h), so they are encoded into the staging buffer and copied over as they retire, like a host target's.
+    const bool direct = dst_dev && !(progress && !share);
+    uint8_t* d_dst = direct ? dst : (uint8_t*)grow(tls.d_out, tls.out_cap, out_bytes);
 
     // BC7: one slice of the per-thread workspace per kernel stream, sized for the tallest window (deep shape: `single` in launch())
     size_t ws_off[2] = {0, 0};
@@ -700,10 +703,10 @@ bool compress_sliced(const Job& j, const rgba_surface* src, uint8_t* dst, int sl
         const int k = i;
         const Window v = window(part + i * parts);
         if (v.y1 <= v.y0) return;
-        if (dst_dev) { ITW_CHECK(hipEventSynchronize(tls.ev_done[k & 7])); return; }
+        if (direct) { ITW_CHECK(hipEventSynchronize(tls.ev_done[k & 7])); return; }
         const size_t off = (size_t)v.row0 * bx * bpb, len = (size_t)v.nb * bx * bpb;
         ITW_CHECK(hipStreamWaitEvent(cs, tls.ev_done[k & 7], 0));
-        ITW_CHECK(hipMemcpyAsync(dst + off, d_dst + off, len, hipMemcpyDeviceToHost, cs));
+        ITW_CHECK(hipMemcpyAsync(dst + off, d_dst + off, len, dst_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, cs));
         ITW_CHECK(hipStreamSynchronize(cs));
     };
     // Two windows AHEAD of the one being retired are issued: when window k-1's kernels end, window k is running on the other stream and window
