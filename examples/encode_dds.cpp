@@ -2,16 +2,20 @@
 // raw texels -> pad to multiples of 4 -> CompressImageMT through the slice loop -> .DDS file.  Only include/*.h is used;
 // the program links libispc_texcomp.so like the plugin links ispc_texcomp.lib.
 //
-//   encode_dds [--measure] <format> <width> <height> <in.raw> <out.dds> [slice_pixels]
+//   encode_dds [--measure] [--refine <profile> <max_block_sse>] <format> <width> <height> <in.raw> <out.dds> [slice_pixels]
 //     format : bc1 | bc3 | bc4 | bc5 | bc7_<profile> | bc6h_<profile>      (profiles: the GetProfile_* names)
 //     in.raw : width*height tightly packed RGBA8 texels (RGBA16F bit patterns for bc6h_*)
 //     --measure : after encoding, one line on stdout per image: what the stream costs against the source (itwMeasureBlocks)
+//     --refine  : bc7_* / bc6h_* only: encode to an error budget (itwCompressImageRefined) -- <format>'s preset everywhere, then <profile>
+//                 (a preset of the same format: `slow`, `alpha_slow`, ...) on the blocks whose error is above <max_block_sse>, kept where
+//                 it is strictly better; one line on stdout with the call's statistics.  The slice loop is not used.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
 #include "../include/ispc_texcomp.h"
+#include "../include/itw_amd.h"
 #include "../include/itw_bc45.h"
 #include "../include/itw_dds.h"
 #include "../include/itw_decode.h"
@@ -43,6 +47,21 @@ const Format kFormats[] = {
     {"bc6h_veryslow", CompressImageBC6H_veryslow, ITW_DXGI_FORMAT_BC6H_UF16, 8, true, 7},
 };
 
+// GetProfile_<name> / GetProfile_bc6h_<name> into `settings` (room for either struct); false: no such preset
+bool profile_by_name(bool bc6h, const char* name, void* settings)
+{
+    struct P7 { const char* name; void (*get)(bc7_enc_settings*); };
+    struct P6 { const char* name; void (*get)(bc6h_enc_settings*); };
+    static const P7 k7[] = {{"ultrafast", GetProfile_ultrafast}, {"veryfast", GetProfile_veryfast}, {"fast", GetProfile_fast}, {"basic", GetProfile_basic},
+                            {"slow", GetProfile_slow}, {"alpha_ultrafast", GetProfile_alpha_ultrafast}, {"alpha_veryfast", GetProfile_alpha_veryfast},
+                            {"alpha_fast", GetProfile_alpha_fast}, {"alpha_basic", GetProfile_alpha_basic}, {"alpha_slow", GetProfile_alpha_slow}};
+    static const P6 k6[] = {{"veryfast", GetProfile_bc6h_veryfast}, {"fast", GetProfile_bc6h_fast}, {"basic", GetProfile_bc6h_basic},
+                            {"slow", GetProfile_bc6h_slow}, {"veryslow", GetProfile_bc6h_veryslow}};
+    if (bc6h) { for (const P6& p : k6) if (std::strcmp(p.name, name) == 0) { p.get(static_cast<bc6h_enc_settings*>(settings)); return true; } }
+    else      { for (const P7& p : k7) if (std::strcmp(p.name, name) == 0) { p.get(static_cast<bc7_enc_settings*>(settings)); return true; } }
+    return false;
+}
+
 bool on_progress(int done, int total, void*)
 {
     std::fprintf(stderr, "\rslice %d / %d", done, total);
@@ -54,14 +73,21 @@ bool on_progress(int done, int total, void*)
 int main(int argc, char** argv)
 {
     bool measure = false;
+    const char* refine_profile = nullptr;
+    unsigned long long max_block_sse = 0;
     for (int i = 1; i < argc; i++)
         if (std::strcmp(argv[i], "--measure") == 0) {
             measure = true;
             for (int k = i; k + 1 < argc; k++) argv[k] = argv[k + 1];
             argc--; i--;
+        } else if (std::strcmp(argv[i], "--refine") == 0 && i + 2 < argc) {
+            refine_profile = argv[i + 1];
+            max_block_sse = std::strtoull(argv[i + 2], nullptr, 10);
+            for (int k = i; k + 3 < argc; k++) argv[k] = argv[k + 3];
+            argc -= 3; i--;
         }
     if (argc < 6) {
-        std::fprintf(stderr, "usage: %s [--measure] <format> <width> <height> <in.raw> <out.dds> [slice_pixels]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s [--measure] [--refine <profile> <max_block_sse>] <format> <width> <height> <in.raw> <out.dds> [slice_pixels]\n", argv[0]);
         return 2;
     }
     const Format* f = nullptr;
@@ -82,8 +108,25 @@ int main(int argc, char** argv)
     ItwDdsDesc desc = { (uint32_t)padded.width, (uint32_t)padded.height, 1, (uint32_t)f->dxgi, 0, 1 };
     std::vector<uint8_t> blocks(itwDdsLevelBytes(desc.dxgi_format, desc.width, desc.height));
     const int64_t pitch = (int64_t)((padded.width + 3) / 4) * GetBytesPerBlock(f->dxgi);
-    const bool ok = itwCompressImageSliced(&padded, blocks.data(), pitch, f->fn, f->dxgi, /*multithreaded*/ true,
-                                           slice_pixels, slice_pixels ? on_progress : nullptr, nullptr);
+    bool ok;
+    if (refine_profile) {
+        const bool bc7 = std::strncmp(f->name, "bc7_", 4) == 0, bc6h = std::strncmp(f->name, "bc6h_", 5) == 0;
+        union { bc7_enc_settings s7; bc6h_enc_settings s6; } first, second;
+        if ((!bc7 && !bc6h) || !profile_by_name(bc6h, f->name + (bc7 ? 4 : 5), &first) || !profile_by_name(bc6h, refine_profile, &second)) {
+            std::fprintf(stderr, "--refine needs a bc7_* or bc6h_* format and a preset of the same format\n");
+            return 2;
+        }
+        itw_refine_stats rs;
+        itwSetErrorMode(ITW_ON_ERROR_RETURN);
+        ok = itwCompressImageRefined(&padded, blocks.data(), f->dxgi, &first, &second, f->own_channels, max_block_sse, &rs, sizeof rs, nullptr, nullptr);
+        if (!ok) std::fprintf(stderr, "%s\n", itwLastError() ? itwLastError() : "itwCompressImageRefined failed");
+        else std::printf("refined: %s -> %s budget %llu blocks %llu listed %llu replaced %llu sse %llu -> %llu worst %llu -> %llu\n", f->name, refine_profile,
+                         max_block_sse, (unsigned long long)rs.blocks, (unsigned long long)rs.listed, (unsigned long long)rs.replaced,
+                         (unsigned long long)rs.sse_first, (unsigned long long)rs.sse_final, (unsigned long long)rs.worst_first, (unsigned long long)rs.worst_final);
+    } else {
+        ok = itwCompressImageSliced(&padded, blocks.data(), pitch, f->fn, f->dxgi, /*multithreaded*/ true,
+                                    slice_pixels, slice_pixels ? on_progress : nullptr, nullptr);
+    }
     if (padded.ptr != source.ptr) itwFreeSurface(&padded);
     if (!ok) { std::fprintf(stderr, "\ncompression aborted\n"); return 1; }
     if (measure) {

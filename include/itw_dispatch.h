@@ -14,6 +14,7 @@
 #ifndef ITW_DISPATCH_H
 #define ITW_DISPATCH_H
 
+#include <stddef.h>
 #include "ispc_texcomp.h"
 
 #ifdef __cplusplus
@@ -148,6 +149,49 @@ bool itwCompressImageChain(const rgba_surface* images, int count, uint8_t* targe
                            int dxgi_format, ItwProgressFunc* progress, void* user);
 bool itwCompressImageChainEx(const rgba_surface* images, int count, uint8_t* target, int dxgi_format,
                              const void* settings, ItwProgressFunc* progress, void* user);
+
+/* Encode to an error budget: a cheap preset everywhere, an expensive one only where the cheap one misses.
+ *
+ * itwCompressImageRefined encodes `source` with `first_settings`, measures every block against its 16 source texels, and encodes with
+ * `refine_settings` only the blocks whose error is above `max_block_sse` (the LISTED blocks); a listed block takes the second encoding
+ * only where that is strictly better.  Blocks of a BCn stream depend on their own 16 texels alone, so EVERY block of `target` is, byte
+ * for byte, the block CompressBlocksBC7 / BC6H emits for the whole surface under one of the two settings -- the reference's block.
+ *   * Formats: BC7 (98, 99) with two bc7_enc_settings*, BC6H (95, 96) with two bc6h_enc_settings*.  Any other format is an error: only
+ *     these two have more than one encoder.
+ *   * Source: RGBA8, or RGBA16F for BC6H; width and height multiples of 4 and >= 4 (pad with itwPadToMultipleOf4[Device]); `stride` >= the
+ *     row's bytes; at most ITW_MEASURE_MAX_BLOCKS (itw_decode.h) blocks.
+ *   * Block error: what itwMeasureBlocks defines for block_sse -- squared code differences, integers, BC6H as 16-bit patterns -- summed
+ *     over the channels in `channel_mask` only (bit 0 = R .. bit 3 = A, as itwStatsPsnr; 1..15).  With mask 15 the values are
+ *     itwMeasureBlocks' own.  BC6H callers pass 7 (the decoders fill alpha with 0x3C00), and so do BC7 RGB presets on non-opaque sources.
+ *   * Rule: A = the first tier's block, eA its error.  eA <= max_block_sse: A is written, tier_map 0.  Otherwise the block is listed;
+ *     B = the refine tier's block, eB its error; eB < eA: B is written, tier_map 2; else A is written, tier_map 1 (ties keep the first
+ *     tier).  The error of a block of the result is never above the first tier's.  max_block_sse = UINT64_MAX lists nothing and launches
+ *     no second tier; 0 lists every block that is not exact.
+ *   * Outputs: `target`, tightly packed blocks in raster order; `stats` (required, 8-byte aligned, stats_bytes = sizeof); `block_sse`
+ *     (optional, one uint64 per block, 8-byte aligned): the error of the block written; `tier_map` (optional, one byte per block).
+ *   * Pointers: each of source->ptr, target, stats, block_sse and tier_map may be a host pointer or a device pointer of the calling
+ *     thread's current device.  One device; the calling thread's stream (itwSetStream).
+ *   * SYNCHRONOUS for every pointer kind: the host reads one word -- the number of listed blocks -- back from the device between the two
+ *     tiers.  For the same reason the call cannot be captured into a graph.
+ *   * Errors: a null pointer (source, texels, target, either settings, stats), a format other than the four above, a width or height that
+ *     is below 4 or no multiple of 4, a stride below the row's bytes, too many blocks, a mask of 0 or above 15, a stats_bytes other than
+ *     sizeof(itw_refine_stats), a misaligned stats or block_sse: all fail through the library's error mode before any device work starts
+ *     (under ITW_ON_ERROR_RETURN the call returns false and itwLastError() holds the message), and need no device.
+ * Scratch memory (the list, the listed blocks' texels and second encodings, the maps the caller did not pass device memory for) belongs
+ * to the calling thread and only grows; its worst case is the whole surface listed. */
+typedef struct itw_refine_stats {
+    uint64_t blocks;                   /* (width/4)*(height/4) */
+    uint64_t listed;                   /* blocks whose first-tier error was > max_block_sse */
+    uint64_t replaced;                 /* listed blocks whose second-tier encoding was STRICTLY better and was written */
+    uint64_t sse_first, sse_final;     /* sum of the per-block errors: after the first tier / of the stream written */
+    uint64_t worst_first, worst_final; /* largest per-block error: after the first tier / of the stream written */
+} itw_refine_stats;                    /* may grow at its end; stats_bytes must be sizeof */
+
+bool itwCompressImageRefined(const rgba_surface* source, uint8_t* target, int dxgi_format,
+                             const void* first_settings, const void* refine_settings,
+                             uint32_t channel_mask, uint64_t max_block_sse,
+                             itw_refine_stats* stats, size_t stats_bytes,
+                             uint64_t* block_sse, uint8_t* tier_map);
 
 /* Pad to multiples of 4 by edge replication (IntelPlugin.cpp:893-928): the step immediately before the ABI.
  * pixel_size = 4 (RGBA8) or 8 (RGBA16F).  Host version: returns a surface whose ptr was allocated with malloc()

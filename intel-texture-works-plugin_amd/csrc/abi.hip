@@ -112,6 +112,8 @@ struct ThreadCtx {
                                                     // BC7 calls, the second band of large ones, the second kernel stream of the window pipeline
     itw::Bc7Verdict verdict = {nullptr, nullptr, false, nullptr};   // the pilot's estimate of a staged host-pointer call's first run, left for the host (kernels.hpp)
     bool staged_wide = false;                       // what the last staged BC7 call's estimate said (the shape of this call's first run, until its own is in)
+    void*  d_refine[2] = {nullptr, nullptr}; size_t refine_cap[2] = {0, 0};   // itwCompressImageRefined (refine.hip): per-surface scratch, per-list scratch
+    uint32_t* refine_count = nullptr;               // ... and the pinned word its list count is read back through
     int    device = -1;
     char   info[256] = {0};
     ~ThreadCtx() {
@@ -119,6 +121,8 @@ struct ThreadCtx {
         if (d_in)  (void)hipFree(d_in);
         if (d_out) (void)hipFree(d_out);
         if (d_ws)  (void)hipFree(d_ws);
+        for (void* p : d_refine) if (p) (void)hipFree(p);
+        if (refine_count) (void)hipHostFree(refine_count);
         if (own_stream) (void)hipStreamDestroy(own_stream);
         if (copy_stream) (void)hipStreamDestroy(copy_stream);
         for (auto e : ev_in) if (e) (void)hipEventDestroy(e);
@@ -149,6 +153,8 @@ void bind_thread_to_current_device()
     if (tls.d_in)  { (void)hipFree(tls.d_in);  tls.d_in = nullptr;  tls.in_cap = 0; }
     if (tls.d_out) { (void)hipFree(tls.d_out); tls.d_out = nullptr; tls.out_cap = 0; }
     if (tls.d_ws)  { (void)hipFree(tls.d_ws);  tls.d_ws = nullptr;  tls.ws_cap = 0; tls.ws_used = false; }
+    for (int k = 0; k < 2; k++) if (tls.d_refine[k]) { (void)hipFree(tls.d_refine[k]); tls.d_refine[k] = nullptr; tls.refine_cap[k] = 0; }
+    if (tls.refine_count) { (void)hipHostFree(tls.refine_count); tls.refine_count = nullptr; }
     if (tls.own_stream) { (void)hipStreamDestroy(tls.own_stream); tls.own_stream = nullptr; }
     if (tls.copy_stream) { (void)hipStreamDestroy(tls.copy_stream); tls.copy_stream = nullptr; }
     for (auto& e : tls.ev_in) if (e) { (void)hipEventDestroy(e); e = nullptr; }
@@ -1258,6 +1264,29 @@ void chain_check(const rgba_surface* images, int count, const uint8_t* target, i
 {
     alignas(16) static const unsigned char any_settings[sizeof(bc7_enc_settings)] = {0};      // (the caller's own function takes none)
     (void)chain_job(images, count, target, dxgi_format, any_settings);
+}
+
+void encode_resident(int dxgi_format, const void* settings, const uint8_t* d_src, int64_t stride, int width, int height, uint8_t* d_dst)
+{
+    const Job j = job_of(dxgi_format, settings);
+    launch(j, d_src, stride, width, height, d_dst, tls.user_stream);
+}
+
+void* refine_scratch(int which, size_t bytes)
+{
+    bind_thread_to_current_device();
+    return grow(tls.d_refine[which], tls.refine_cap[which], bytes);
+}
+
+uint32_t* refine_count_word()
+{
+    bind_thread_to_current_device();
+    if (!tls.refine_count) {
+        void* h = nullptr;
+        ITW_CHECK(hipHostMalloc(&h, sizeof(uint32_t), hipHostMallocDefault));
+        tls.refine_count = static_cast<uint32_t*>(h);
+    }
+    return tls.refine_count;
 }
 
 int sliced_windows(int dxgi_format, const void* settings, int width, int height, int64_t slice_pixels, int* window_slices)

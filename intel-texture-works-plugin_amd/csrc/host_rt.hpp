@@ -56,6 +56,15 @@ int sliced_windows(int dxgi_format, const void* settings, int width, int height,
 // loop of a caller's own CompressionFunc, which takes no settings
 void chain_check(const rgba_surface* images, int count, const uint8_t* target, int dxgi_format);
 
+// What itwCompressImageRefined (refine.hip) needs of the calling thread's context.
+// encode_resident: the device-pointer path of CompressBlocksBC7 / BC6H -- same routing, same workspace -- for a format code and settings
+// pointer as itwCompressImageChainEx takes them; asynchronous on the thread's stream (itwSetStream).
+void encode_resident(int dxgi_format, const void* settings, const uint8_t* d_src, int64_t stride, int width, int height, uint8_t* d_dst);
+// refine_scratch: the thread's grow-only device scratch `which` (0: sized by the surface, 1: sized by the list), at least `bytes` bytes,
+// 256-B aligned; growing frees the old buffer, which waits for the device.  refine_count_word: the thread's pinned host word.
+void* refine_scratch(int which, size_t bytes);
+uint32_t* refine_count_word();
+
 // One predicate for "the kernels can dereference this pointer": device AND managed allocations (abi.hip and
 // dispatch.hip/decode.hip used to disagree on managed memory).  Unregistered host memory -> false.
 bool is_device_pointer(const void* p) noexcept;

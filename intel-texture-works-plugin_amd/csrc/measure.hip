@@ -20,6 +20,7 @@
 #include "../../include/itw_decode.h"
 #include "../../include/itw_amd.h"
 #include "decode_core.hpp"
+#include "texel_rows.hpp"
 #include "host_rt.hpp"
 
 static_assert(sizeof(itw_error_stats) == 216, "itw_error_stats layout");
@@ -30,47 +31,6 @@ constexpr int MEASURE_INDEX_BITS = 25;
 constexpr uint32_t MEASURE_INDEX_MASK = (1u << MEASURE_INDEX_BITS) - 1u;
 constexpr int MEASURE_MAX_GROUPS = 1024;      // 4 workgroups per CU; <= 2^25 / (1024 * 256) = 128 blocks per lane: 128 * 16 * 255^2 < 2^32
 static_assert((uint64_t)ITW_MEASURE_MAX_BLOCKS == (1ull << MEASURE_INDEX_BITS), "the key's index field is what limits the block count");
-
-// a dword from a source whose alignment is whatever the caller's pointer and stride make it
-__device__ __forceinline__ uint32_t measure_load_u32(const uint8_t* p)
-{
-    if (((uintptr_t)p & 3) == 0) return *reinterpret_cast<const uint32_t*>(p);
-    return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
-}
-
-// the DW dwords (4 texels) of one source row of a block; texels at and beyond column nx are not read (they come back as 0 and are not compared)
-template <int DW>
-__device__ __forceinline__ void measure_load_row(const uint8_t* p, int nx, uint32_t (&v)[DW])
-{
-    constexpr int PER = DW / 4;                                 // dwords per texel
-    if (nx == 4 && ((uintptr_t)p & 15) == 0) {
-#pragma unroll
-        for (int q = 0; q < DW / 4; q++) {
-            const uint4 t = reinterpret_cast<const uint4*>(p)[q];
-            v[4 * q] = t.x; v[4 * q + 1] = t.y; v[4 * q + 2] = t.z; v[4 * q + 3] = t.w;
-        }
-    } else {
-#pragma unroll
-        for (int c = 0; c < 4; c++)
-#pragma unroll
-            for (int q = 0; q < PER; q++) v[c * PER + q] = c < nx ? measure_load_u32(p + (c * PER + q) * 4) : 0u;
-    }
-}
-
-template <class T>
-__device__ __forceinline__ T wave_sum(T v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-template <class T>
-__device__ __forceinline__ T wave_max(T v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const T u = __shfl_xor(v, o); v = u > v ? u : v; }
-    return v;
-}
 
 // FMT: 1 BC1, 3 BC3, 4 BC4, 5 BC5, 7 BC7, 6 BC6H (decode_kernel's numbering)
 template <int FMT>

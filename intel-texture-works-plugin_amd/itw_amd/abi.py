@@ -22,7 +22,7 @@ EXPORTED_SYMBOLS = tuple(
     + ["GetProcessorCount", "InitWin32Threads", "DestroyThreads", "GetBytesPerBlock", "CompressImageMT", "CompressImageST",
        "CompressImageBC1", "CompressImageBC3", "CompressImageBC4", "CompressImageBC5"]
     + ["CompressImageBC7_" + p for p in BC7_PROFILES] + ["CompressImageBC6H_" + p for p in BC6H_PROFILES]
-    + ["itwCompressImageSliced", "itwCompressImageSlicedEx", "itwChainBytes", "itwCompressImageChain", "itwCompressImageChainEx", "itwSetSliceWindow", "itwSliceWindow", "itwSliceWindowFor", "itwPadToMultipleOf4", "itwFreeSurface", "itwPadToMultipleOf4Device",
+    + ["itwCompressImageSliced", "itwCompressImageSlicedEx", "itwChainBytes", "itwCompressImageChain", "itwCompressImageChainEx", "itwCompressImageRefined", "itwSetSliceWindow", "itwSliceWindow", "itwSliceWindowFor", "itwPadToMultipleOf4", "itwFreeSurface", "itwPadToMultipleOf4Device",
        "itwConvertToRGBA8Device", "itwConvertToRGBA16FDevice"]
     # include/itw_multigpu.h: one surface over all GPUs, one process
     + ["itwMultiGpuRanks", "itwMultiGpuTransport", "itwMultiGpuPeerLinks", "itwCompressImageMultiGPU", "itwCompressImageMultiGPUEx", "itwCompressImageMultiGPUBands",
@@ -143,6 +143,18 @@ class ErrorStats(C.Structure):
 
 assert C.sizeof(ErrorStats) == 216
 
+
+class RefineStats(C.Structure):
+    """struct itw_refine_stats (itw_dispatch.h): what itwCompressImageRefined reports, all integers."""
+    _fields_ = [("blocks", C.c_uint64), ("listed", C.c_uint64), ("replaced", C.c_uint64), ("sse_first", C.c_uint64), ("sse_final", C.c_uint64),
+                ("worst_first", C.c_uint64), ("worst_final", C.c_uint64)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
+assert C.sizeof(RefineStats) == 56
+
 COMPRESSION_FUNC = C.CFUNCTYPE(None, C.POINTER(RgbaSurface), C.c_void_p)
 PROGRESS_FUNC = C.CFUNCTYPE(C.c_bool, C.c_int, C.c_int, C.c_void_p)
 
@@ -239,6 +251,9 @@ def _load(path, hooks):
         L.itwCompressImageChain.restype = C.c_bool
         L.itwCompressImageChainEx.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.itwCompressImageChainEx.restype = C.c_bool
+        L.itwCompressImageRefined.argtypes = [C.POINTER(RgbaSurface), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64,
+                                              C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        L.itwCompressImageRefined.restype = C.c_bool
         L.itwSetSliceWindow.argtypes = [C.c_int]
         L.itwSetSliceWindow.restype = None
         L.itwSliceWindow.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int64]
@@ -773,3 +788,51 @@ def measure_chain(fmt, blocks, levels):
     if rc != 0:
         raise ValueError("itwMeasureChain: " + (last_error() or "bad arguments"))
     return res
+
+
+def compress_refined(fmt, img, first, refine, max_block_sse, channels=None, want_block_map=False, want_tier_map=False):
+    """itwCompressImageRefined: encode `img` with the preset `first`, then encode with `refine` only the blocks whose error is above
+    max_block_sse, keeping a second encoding only where it is strictly better (include/itw_dispatch.h).  fmt: 'bc7' / 'bc6h' (or another
+    key of DXGI_FORMAT for them); first, refine: profile names or Bc7Settings / Bc6hSettings; img: numpy (H, W, 4) uint8 -- uint16 half
+    bits for bc6h -- or a CUDA torch tensor of that shape (rows may be strided), H and W multiples of 4; channels: the channels the block
+    error sums ('rgb', 'rgba', (0, 1), ...; default 'rgb': right for BC6H and for the BC7 RGB presets -- pass 'rgba' with the alpha presets).
+    Synchronous.  Returns (blocks, RefineStats[, block_sse][, tier_map]) in the source's kind of container: uint8 / uint64 / uint8 numpy
+    arrays, or uint8 / int64 / uint8 CUDA tensors."""
+    import numpy as np
+    base = fmt.split("_")[0]
+    if base not in ("bc7", "bc6h"):
+        raise ValueError(f"{fmt}: only bc7 and bc6h have presets to refine with")
+    profile, settings_type = (bc7_profile, Bc7Settings) if base == "bc7" else (bc6h_profile, Bc6hSettings)
+    s1 = first if isinstance(first, settings_type) else profile(first)
+    s2 = refine if isinstance(refine, settings_type) else profile(refine)
+    mask = _channel_mask("rgb" if channels is None else channels)
+    h, w = img.shape[:2]
+    nb = (w // 4) * (h // 4)
+    st = RefineStats()
+    L = lib()
+    if isinstance(img, np.ndarray):
+        assert img.ndim == 3 and img.shape[2] == 4 and img.strides[2] == img.itemsize and img.strides[1] == 4 * img.itemsize
+        assert img.itemsize == (2 if base == "bc6h" else 1), "texel type does not match the format"
+        out = np.empty(nb * 16, dtype=np.uint8)
+        bmap = np.empty(nb, dtype=np.uint64) if want_block_map else None
+        tmap = np.empty(nb, dtype=np.uint8) if want_tier_map else None
+        surf = RgbaSurface(img.ctypes.data, w, h, img.strides[0])
+        ptr = lambda a: a.ctypes.data if a is not None else None
+        ok = L.itwCompressImageRefined(C.byref(surf), ptr(out), DXGI_FORMAT[fmt], C.addressof(s1), C.addressof(s2), mask, int(max_block_sse),
+                                       C.addressof(st), C.sizeof(RefineStats), ptr(bmap), ptr(tmap))
+    else:
+        import torch
+        assert img.is_cuda and img.dim() == 3 and img.shape[2] == 4 and img.stride(2) == 1 and img.stride(1) == 4
+        assert img.element_size() == (2 if base == "bc6h" else 1), "texel type does not match the format"
+        out = torch.empty(nb * 16, dtype=torch.uint8, device=img.device)
+        bmap = torch.empty(nb, dtype=torch.int64, device=img.device) if want_block_map else None
+        tmap = torch.empty(nb, dtype=torch.uint8, device=img.device) if want_tier_map else None
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        with torch.cuda.device(img.device):
+            L.itwSetStream(torch.cuda.current_stream(img.device).cuda_stream)
+            surf = RgbaSurface(img.data_ptr(), w, h, img.stride(0) * img.element_size())
+            ok = L.itwCompressImageRefined(C.byref(surf), ptr(out), DXGI_FORMAT[fmt], C.addressof(s1), C.addressof(s2), mask, int(max_block_sse),
+                                           C.addressof(st), C.sizeof(RefineStats), ptr(bmap), ptr(tmap))
+    if not ok:
+        raise ValueError("itwCompressImageRefined: " + (last_error() or "failed"))
+    return (out, st) + ((bmap,) if want_block_map else ()) + ((tmap,) if want_tier_map else ())
