@@ -3,8 +3,8 @@
 // the program links libispc_texcomp.so like the plugin links ispc_texcomp.lib.
 //
 //   encode_dds [--measure] [--refine <profile> <max_block_sse>] <format> <width> <height> <in.raw> <out.dds> [slice_pixels]
-//     format : bc1 | bc3 | bc4 | bc5 | bc7_<profile> | bc6h_<profile>      (profiles: the GetProfile_* names)
-//     in.raw : width*height tightly packed RGBA8 texels (RGBA16F bit patterns for bc6h_*)
+//     format : bc1 | bc3 | bc4 | bc5 | bc4_snorm | bc5_snorm | bc7_<profile> | bc6h_<profile>      (profiles: the GetProfile_* names)
+//     in.raw : width*height tightly packed RGBA8 texels (RGBA16F bit patterns for bc6h_*; RGBA8_SNORM, int8 codes, for bc4_snorm / bc5_snorm)
 //     --measure : after encoding, one line on stdout per image: what the stream costs against the source (itwMeasureBlocks)
 //     --refine  : bc7_* / bc6h_* only: encode to an error budget (itwCompressImageRefined) -- <format>'s preset everywhere, then <profile>
 //                 (a preset of the same format: `slow`, `alpha_slow`, ...) on the blocks whose error is above <max_block_sse>, kept where
@@ -30,6 +30,8 @@ const Format kFormats[] = {
     {"bc3", CompressImageBC3, ITW_DXGI_FORMAT_BC3_UNORM, 4, true, 15},
     {"bc4", CompressImageBC4, ITW_DXGI_FORMAT_BC4_UNORM, 4, false, 1},      // DirectXTex formats keep partial blocks
     {"bc5", CompressImageBC5, ITW_DXGI_FORMAT_BC5_UNORM, 4, false, 3},
+    {"bc4_snorm", CompressImageBC4S, ITW_DXGI_FORMAT_BC4_SNORM, 4, false, 1},   // the raw file's bytes are int8 codes (normal maps)
+    {"bc5_snorm", CompressImageBC5S, ITW_DXGI_FORMAT_BC5_SNORM, 4, false, 3},
     {"bc7_ultrafast", CompressImageBC7_ultrafast, ITW_DXGI_FORMAT_BC7_UNORM, 4, true, 7},
     {"bc7_veryfast", CompressImageBC7_veryfast, ITW_DXGI_FORMAT_BC7_UNORM, 4, true, 7},
     {"bc7_fast", CompressImageBC7_fast, ITW_DXGI_FORMAT_BC7_UNORM, 4, true, 7},

@@ -1,5 +1,5 @@
 /*
- * itw_bc45.h -- BC4_UNORM / BC5_UNORM block encoding on the GPU.
+ * itw_bc45.h -- BC4 / BC5 block encoding on the GPU, UNORM and SNORM.
  *
  * The two formats the plugin offers that bypass ispc_texcomp: IntelPlugin.cpp:120-141 converts the document to an
  * RGBA8 scratch image (BC4: the red plane in every colour channel, BC5: red and green) and IntelPlugin.cpp:271-273
@@ -16,6 +16,15 @@
  * dst     ceil(width/4) * ceil(height/4) blocks in raster order, 8 bytes (BC4) or 16 bytes (BC5: R block, G block),
  *         tightly packed (DirectXTex's pitch rule, DirectXTexUtil.cpp:601-619).
  * Host or device pointers, threading, streams and error behaviour: exactly as CompressBlocksBC1 (ispc_texcomp.h).
+ *
+ * The signed pair, CompressBlocksBC4S / CompressBlocksBC5S (DXGI_FORMAT_BC4_SNORM = 81 / BC5_SNORM = 84; what a tangent-space normal
+ * map is stored in: the centre is exact and the range symmetric), is D3DXEncodeBC4S / D3DXEncodeBC5S (BC4BC5.cpp:424, :515) under the
+ * same contract.  src is an RGBA8_SNORM surface: byte 0 (BC5S: bytes 0 and 1) of a texel is a two's-complement int8 code v, and the
+ * value the encoder sees is
+ *     t = max((float)v * (1.0f / 127.0f), -1.0f)          with 1.0f / 127.0f an fp32 constant
+ * which is DirectXMath's SSE XMLoadByteN4 (the conversion DirectX::Compress applies to an R8G8B8A8_SNORM image); DirectXMath is not
+ * part of the reference tree, so this line is the definition.  Codes -128 and -127 both are -1.0f, 127 is exactly 1.0f.  Endpoints
+ * are never stored as -128 (FloatToSNorm, BC4BC5.cpp:161-182).
  */
 #ifndef ITW_BC45_H
 #define ITW_BC45_H
@@ -33,6 +42,13 @@ void CompressBlocksBC5(const rgba_surface* src, uint8_t* dst);
 /* The first BC4 / BC5 call on a device builds a 1 MiB index table there (csrc/bc4_bc5.hip): that one call allocates device memory and is not
  * stream-capturable; itwWarmupBC45() does the same ahead of time (see itw_amd.h for the asynchronous contract of device-pointer calls). */
 void itwWarmupBC45(void);
+
+void CompressBlocksBC4S(const rgba_surface* src, uint8_t* dst);
+void CompressBlocksBC5S(const rgba_surface* src, uint8_t* dst);
+
+/* The signed encoders have an index table of their own, built by the first signed call on a device or by itwWarmupBC45S(), under the
+ * same rules; itwWarmupBC45() and the UNORM pair neither build nor need it. */
+void itwWarmupBC45S(void);
 
 #pragma GCC visibility pop
 #ifdef __cplusplus

@@ -2,7 +2,8 @@
  * itw_dds.h -- DDS container for the encoder's block streams: the header DirectXTex's _EncodeDDSHeader writes for
  * the formats the plugin saves (3rdParty/DirectXTex/DirectXTex/DDS.h:38-236, DirectXTexDDS.cpp:441-675, data
  * order :1611-1700, pitch rule DirectXTexUtil.cpp:601-619), restated portably.  BC1_UNORM / BC3_UNORM use the legacy
- * 'DXT1' / 'DXT5' FourCC header (128 bytes incl. magic); the _SRGB variants, BC7 and BC6H carry the 'DX10' extension
+ * 'DXT1' / 'DXT5' FourCC header (128 bytes incl. magic), BC4 / BC5 'BC4U' / 'BC5U' (UNORM; 'ATI1' / 'ATI2' are read as these) and
+ * 'BC4S' / 'BC5S' (SNORM; DDS.h:83-93, DirectXTexDDS.cpp:64-70, 480-483); the _SRGB variants, BC7 and BC6H carry the 'DX10' extension
  * (148 bytes).  Mip chains: top level first; cube maps: 6 faces, each with its full chain.
  */
 #ifndef ITW_DDS_H
@@ -19,7 +20,7 @@ extern "C" {
 typedef struct ItwDdsDesc {
     uint32_t width, height;     /* top mip, texels */
     uint32_t mip_levels;        /* >= 1 */
-    uint32_t dxgi_format;       /* DXGI_FORMAT_BCn_* value (71,72,77,78,80,83,95,96,98,99) */
+    uint32_t dxgi_format;       /* DXGI_FORMAT_BCn_* value (71,72,77,78,80,81,83,84,95,96,98,99) */
     uint32_t is_cubemap;        /* 0 / 1: six faces */
     uint32_t array_size;        /* number of textures (cubes when is_cubemap); >= 1 */
 } ItwDdsDesc;

@@ -1,5 +1,5 @@
 /*
- * itw_decode.h -- BC1 / BC3 / BC4 / BC5 / BC7 / BC6H(unsigned) block decoding on the GPU: the step immediately after the ABI in
+ * itw_decode.h -- BC1 / BC3 / BC4 / BC5 (UNORM and SNORM) / BC7 / BC6H(unsigned) block decoding on the GPU: the step immediately after the ABI in
  * the reference's preview and load paths, where DirectXTex's Decompress() (D3DXDecodeBC1/BC3/BC7/BC6HU,
  * 3rdParty/DirectXTex/DirectXTex/BC.cpp, BC6HBC7.cpp:1077-1210, 1937-2140) turns the blocks back into texels
  * (IntelPlugin.cpp:1059, 2558).  Written from the format definitions; used here for preview-style round trips and
@@ -22,12 +22,16 @@ extern "C" {
  * produce, BC4BC5.cpp:373-385, 449-462; 8-bit values by the format's integer definition, rounded to nearest),
  * RGBA16F bit patterns for BC6H (alpha = 1.0 = 0x3C00).  width and height are multiples of 4 (a BC4/BC5 stream of a
  * partial surface decodes to the padded size).
- * dxgi_format: one of the ITW_DXGI_FORMAT_BC* values of itw_dispatch.h (71,72,77,78,80,83,95,96,98,99).
+ * BC4_SNORM / BC5_SNORM decode to RGBA8_SNORM, int8 codes (R,0,0,127) / (R,G,0,127): the layout D3DXDecodeBC4S/BC5S produce
+ * (BC4BC5.cpp:388-400, 465-478) with R = rint(127 * its float).  As integers, with s0, s1 the endpoint bytes and -128 read as -127:
+ * levels 0, 1 = s0, s1; if the RAW bytes have r0 > r1, level 1+i = round(((7-i)*s0 + i*s1) / 7), i = 1..6; else level 1+i =
+ * round(((5-i)*s0 + i*s1) / 5), i = 1..4, and levels 6, 7 = -127, 127 (round to nearest; no ties with odd divisors).  Never -128.
+ * dxgi_format: one of the ITW_DXGI_FORMAT_BC* values of itw_dispatch.h (71,72,77,78,80,81,83,84,95,96,98,99).
  * `blocks`, `out`, `modes` are host or device pointers (host pointers are staged, the call then returns synchronised;
  * all-device calls are asynchronous on the calling thread's stream, itwSetStream).
  * `modes` (optional, may be NULL): one int32 per block -- BC7: mode 0..7, -1 for the reserved all-zero-prefix block;
  * BC6H: mode 0..13 in kernel.ispc's numbering, -1 for a reserved prefix; BC1/BC3: 0.
- * Width and height must be multiples of 4, except for BC4 / BC5, whose streams may end in partial blocks (cropped on store).
+ * Width and height must be multiples of 4, except for BC4 / BC5 (UNORM and SNORM), whose streams may end in partial blocks (cropped on store).
  * Returns 0, or -1 for an unsupported format / misaligned sizes. */
 int itwDecodeBlocks(int dxgi_format, const uint8_t* blocks, int width, int height, uint8_t* out, int64_t out_stride, int32_t* modes);
 
@@ -37,6 +41,8 @@ int itwDecodeBlocks(int dxgi_format, const uint8_t* blocks, int width, int heigh
  * exists in memory.  A "code" is the 8-bit channel value for the LDR formats and the 16-bit half-float bit pattern, read as an
  * unsigned integer, for BC6H (the space BC6H interpolates in).  All four channels are always reported, the values the decoders fill
  * in included (BC4 / BC5: 0 / 0 / 255, BC6H: alpha 0x3C00, BC1: its decoded alpha); the caller picks the channels that mean something.
+ * BC4_SNORM / BC5_SNORM: `source` is RGBA8_SNORM and a code is the int8 value, a source code of -128 read as -127 (both mean -1.0);
+ * the filled-in channels are 0 / 0 / 127, and max_abs is at most 254.
  * Every field is an integer: the same stream and source give the same bits on every run. */
 typedef struct itw_error_stats {
     int32_t  dxgi_format, width, height;  /* what was measured: texels per row / rows actually compared */
@@ -76,7 +82,8 @@ int itwMeasureChain(const rgba_surface* images, int count, const uint8_t* blocks
 
 /* itwStatsPsnr: host arithmetic in double: 10*log10(255^2 * n / sum of sse[c]) over the channels c in channel_mask (bit 0 = R ..
  * bit 3 = A), n = width * height * number of selected channels.  +inf when the sum is 0; NaN for a BC6H stats (a code-space PSNR of
- * half floats is not a quantity this library defines) and for an empty mask. */
+ * half floats is not a quantity this library defines) and for an empty mask.  For BC4_SNORM / BC5_SNORM stats the peak is 254, the width
+ * of the int8 code range -127..127, in place of 255. */
 double itwStatsPsnr(const itw_error_stats* stats, uint32_t channel_mask);
 
 #pragma GCC visibility pop

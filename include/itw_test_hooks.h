@@ -31,6 +31,12 @@ void itwTestBc7TwoSubsetBounds(const rgba_surface* d_src, float* d_out);
  * the top byte; indices of runs 0..3, one byte each; indices of runs 4..7} -- to host memory.  Returns 0, or -1 on failure (error mode "return"). */
 int itwTestBc45IndexTable(uint32_t* host_out);
 
+/* BC4_SNORM / BC5_SNORM (tests/test_gpu_bc45_snorm.py).  Runs the device function the signed encoders choose their indices with
+ * (csrc/bc4_bc5.hip closest_indices_snorm: the run table, and for the endpoint pairs whose entry says "more than 8 runs" the search as
+ * written) for all 65 536 endpoint pairs x 256 texel codes: host_out[(r0 << 8 | r1) * 256 + code], r0, r1 and code the int8 values as
+ * bytes, 16 MiB of host memory.  Returns 0, or -1 on failure (error mode "return"). */
+int itwTestBc45ClosestS(uint8_t* host_out);
+
 /* Multi-GPU (tests/test_gpu_multigpu_cpp.py): the NEXT itwCompressImageMultiGPU[Ex] call of this process fails inside rank `rank` at `stage`
  * (1 = while preparing, before any transfer is posted; 2 = after its first half-band was posted; 3 = the rank stalls for
  * `stall_ms` before posting anything, which is what the watchdog is for).  One-shot; nothing in the environment can set it. */

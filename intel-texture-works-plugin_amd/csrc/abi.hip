@@ -195,6 +195,7 @@ enum class Fmt { BC1, BC3, BC7, BC6H, BC4, BC5 };
 
 struct Job {
     Fmt fmt;
+    bool snorm = false;         // BC4 / BC5 only: the SNORM pair (same geometry, block size and staging; its own kernels)
     const bc7_enc_settings*  s7 = nullptr;
     const bc6h_enc_settings* s6 = nullptr;
 };
@@ -304,8 +305,8 @@ void launch(const Job& j, const uint8_t* d_src, int64_t stride, int w, int h, ui
         if (need) ITW_CHECK(hipEventRecord(tls.ws_event, st));
         break;
     }
-    case Fmt::BC4:  itw::launch_bc4(d_src, stride, w, h, d_dst, st); break;
-    case Fmt::BC5:  itw::launch_bc5(d_src, stride, w, h, d_dst, st); break;
+    case Fmt::BC4:  (j.snorm ? itw::launch_bc4s : itw::launch_bc4)(d_src, stride, w, h, d_dst, st); break;
+    case Fmt::BC5:  (j.snorm ? itw::launch_bc5s : itw::launch_bc5)(d_src, stride, w, h, d_dst, st); break;
     }
     ITW_CHECK(hipGetLastError());
 }
@@ -747,6 +748,8 @@ Job job_of(int dxgi_format, const void* settings)
     case ITW_DXGI_FORMAT_BC3_UNORM: case ITW_DXGI_FORMAT_BC3_UNORM_SRGB: j.fmt = Fmt::BC3; break;
     case ITW_DXGI_FORMAT_BC4_UNORM: j.fmt = Fmt::BC4; break;
     case ITW_DXGI_FORMAT_BC5_UNORM: j.fmt = Fmt::BC5; break;
+    case ITW_DXGI_FORMAT_BC4_SNORM: j.fmt = Fmt::BC4; j.snorm = true; break;
+    case ITW_DXGI_FORMAT_BC5_SNORM: j.fmt = Fmt::BC5; j.snorm = true; break;
     case ITW_DXGI_FORMAT_BC6H_UF16: case ITW_DXGI_FORMAT_BC6H_SF16: j.fmt = Fmt::BC6H; j.s6 = static_cast<const bc6h_enc_settings*>(settings); break;
     case ITW_DXGI_FORMAT_BC7_UNORM: case ITW_DXGI_FORMAT_BC7_UNORM_SRGB: j.fmt = Fmt::BC7; j.s7 = static_cast<const bc7_enc_settings*>(settings); break;
     default: itw::fail_msg("DXGI format %d is not one this library encodes", dxgi_format);
@@ -1058,7 +1061,7 @@ bool coalescing_enabled()
 
 bool same_settings(const Pending& a, const Pending& b)
 {
-    if (a.job.fmt != b.job.fmt) return false;
+    if (a.job.fmt != b.job.fmt || a.job.snorm != b.job.snorm) return false;
     if (a.job.fmt == Fmt::BC7) {
         // fields only: padding differs between stack objects, and refineIterations[7] is uninitialised storage in the RGB
         // presets (ispc_texcomp.cpp:20-189 never write it) -- it matters only when mode 7 runs (kernel.ispc:1419)
@@ -1352,6 +1355,14 @@ void CompressBlocksBC5(const rgba_surface* src, uint8_t* dst)
 {
     itw::guarded([&] { Job j; j.fmt = Fmt::BC5; compress(j, src, dst); });
 }
+void CompressBlocksBC4S(const rgba_surface* src, uint8_t* dst)
+{
+    itw::guarded([&] { Job j; j.fmt = Fmt::BC4; j.snorm = true; compress(j, src, dst); });
+}
+void CompressBlocksBC5S(const rgba_surface* src, uint8_t* dst)
+{
+    itw::guarded([&] { Job j; j.fmt = Fmt::BC5; j.snorm = true; compress(j, src, dst); });
+}
 
 bool itwCompressImageSlicedEx(const rgba_surface* source, uint8_t* target, int64_t block_row_pitch, int dxgi_format, const void* settings,
                               int64_t slice_pixels, ItwProgressFunc* progress, void* user)
@@ -1392,7 +1403,8 @@ int itwSliceWindowFor(int dxgi_format, const void* settings, int width, int heig
     int64_t slices = ((int64_t)width * height) / slice_pixels;
     if (slices < 1) slices = 1;
     if (slices > (1 << 24)) slices = 1 << 24;
-    const bool keep = dxgi_format == ITW_DXGI_FORMAT_BC4_UNORM || dxgi_format == ITW_DXGI_FORMAT_BC5_UNORM;
+    const bool keep = dxgi_format == ITW_DXGI_FORMAT_BC4_UNORM || dxgi_format == ITW_DXGI_FORMAT_BC5_UNORM ||
+                      dxgi_format == ITW_DXGI_FORMAT_BC4_SNORM || dxgi_format == ITW_DXGI_FORMAT_BC5_SNORM;
     const int64_t blocks = keep ? (int64_t)((width + 3) / 4) * ((height + 3) / 4) : (int64_t)(width / 4) * (height / 4);
     const bool heavy = dxgi_format == ITW_DXGI_FORMAT_BC7_UNORM || dxgi_format == ITW_DXGI_FORMAT_BC7_UNORM_SRGB ||
                        dxgi_format == ITW_DXGI_FORMAT_BC6H_UF16 || dxgi_format == ITW_DXGI_FORMAT_BC6H_SF16;
@@ -1467,11 +1479,23 @@ void itwWarmupBC45(void)
     itw::guarded([&] { bind_thread_to_current_device(); itw::warmup_bc45(); });
 }
 
+void itwWarmupBC45S(void)
+{
+    itwClearError();
+    itw::guarded([&] { bind_thread_to_current_device(); itw::warmup_bc45s(); });
+}
+
 #ifdef ITW_TEST_HOOKS      // libispc_texcomp_test.so only (include/itw_test_hooks.h)
 int itwTestBc45IndexTable(uint32_t* host_out)
 {
     itwClearError();
     return itw::guarded([&] { if (!host_out) itw::fail_msg("null pointer"); itw::copy_bc45_index_table(host_out, tls.user_stream); }) ? 0 : -1;
+}
+
+int itwTestBc45ClosestS(uint8_t* host_out)
+{
+    itwClearError();
+    return itw::guarded([&] { if (!host_out) itw::fail_msg("null pointer"); itw::copy_bc45_closest_snorm(host_out, tls.user_stream); }) ? 0 : -1;
 }
 
 void itwTestBc7TwoSubsetBounds(const rgba_surface* d_src, float* d_out)

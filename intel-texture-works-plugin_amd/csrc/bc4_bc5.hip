@@ -1,4 +1,4 @@
-// bc4_bc5.hip -- BC4_UNORM / BC5_UNORM encoders for gfx950.
+// bc4_bc5.hip -- BC4 / BC5 encoders for gfx950, UNORM and SNORM.
 //
 // These two formats are the only ones the plugin does not send through kernel.ispc: IntelPlugin.cpp:271-273 hands the
 // RGBA8 scratch image to DirectXTex (DirectX::Compress, TEX_COMPRESS_DEFAULT).  This file is the device replacement of
@@ -27,6 +27,14 @@
 //   * Minimum / maximum of the 16 codes on packed halves (v_pk_min/max_u16: two texels per instruction), also for the 6-step
 //     ramp's "smallest code above 0 / largest below 255" ((v + 255) & 255 and (v + 1) & 255 move the excluded code to the
 //     other end of the range).
+//
+// SNORM (template argument SGN; D3DXEncodeBC4S/BC5S, BC4BC5.cpp:240-292, 339-362, 424-442, 515-546; OptimizeAlpha<true>): the same
+// kernel over the texel codes BIASED by 128 (code ^ 0x80: signed order becomes unsigned order, so the packed minimum / maximum and the
+// run table work unchanged).  A texel is max((float)code * (1/127), -1): codes -128 and -127 (biased 0 and 1) are both -1.0.  What
+// differs is stated where it differs: the 6-step ramp's choice and start values, the loop's out-of-range sentinels, FloatToSNorm, the
+// decoded levels, and an ESCAPE in the run table: 30 endpoint pairs, all with red_0 == red_1, have 12-19 runs (their interpolated levels
+// sit an ulp apart, and the nearest one flips back and forth as the texel moves away).  Their entries carry the run count (> 8) and a
+// lane that meets one runs FindClosestSNORM as written over its eight levels.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <mutex>
@@ -44,6 +52,15 @@ __device__ __forceinline__ uint32_t pk_min_u16(uint32_t a, uint32_t b) { return 
 __device__ __forceinline__ uint32_t pk_max_u16(uint32_t a, uint32_t b) { return as_u32(__builtin_elementwise_max(as_u16x2(a), as_u16x2(b))); }
 
 constexpr float UNORM_SCALE = 1.0f / 255.0f;                     // XMLoadUByteN4's SSE path: integer * (1/255)
+constexpr float SNORM_SCALE = 1.0f / 127.0f;                     // XMLoadByteN4's SSE path: integer * (1/127), then max with -1
+
+// texel value of a code: UNORM code 0..255, SNORM the BIASED code (int8 code + 128)
+template <bool SGN>
+__device__ __forceinline__ float texel_of(float code)
+{
+    if (SGN) return fmaxf((code - 128.0f) * SNORM_SCALE, -1.0f);
+    return code * UNORM_SCALE;
+}
 
 // ---- FindClosestUNORM, tabulated ---------------------------------------------------------------------------------------------
 // BC4_UNORM::DecodeFromIndex (BC4BC5.cpp:50-72), as written
@@ -60,28 +77,50 @@ __device__ __forceinline__ void decoded_levels(float (&g)[8], uint32_t r0, uint3
     }
 }
 
+// BC4_SNORM::DecodeFromIndex (BC4BC5.cpp:106-131), as written; r0, r1 are the stored bytes
+__device__ __forceinline__ void decoded_levels_snorm(float (&g)[8], uint32_t r0, uint32_t r1)
+{
+    const int b0 = (int)(int8_t)r0, b1 = (int)(int8_t)r1;
+    const float f0 = (float)(b0 == -128 ? -127 : b0) / 127.0f, f1 = (float)(b1 == -128 ? -127 : b1) / 127.0f;
+    g[0] = f0; g[1] = f1;
+    const bool eight = b0 > b1;                                   // the raw bytes decide the form
+#pragma unroll
+    for (int k = 1; k <= 6; k++) {
+        const float v8 = (f0 * (float)(7 - k) + f1 * (float)k) / 7.0f;
+        const float v6 = (k <= 4) ? (f0 * (float)(5 - k) + f1 * (float)k) / 5.0f : (k == 5 ? -1.0f : 1.0f);
+        g[k + 1] = eight ? v8 : v6;
+    }
+}
+
+// FindClosestUNORM / FindClosestSNORM (BC4BC5.cpp:314-362): first index with the strictly smallest |g - t|
+__device__ __forceinline__ uint32_t closest_level(const float (&g)[8], float t)
+{
+    uint32_t best = 0;
+    float best_delta = 100000.0f;
+#pragma unroll
+    for (uint32_t k = 0; k < 8u; k++) {
+        const float d = fabsf(g[k] - t);
+        if (d < best_delta) { best = k; best_delta = d; }
+    }
+    return best;
+}
+
 // Entry of the run table for one endpoint pair: the index is constant on runs [T_j, T_j+1) of the texel code v, T_0 = 0.
 //   x, y   C_j = 256 - T_j for run j = 1..7, one byte each (C_1 in the low byte of x; 0 = no such run): v + C_j carries into
 //          bit 8 exactly when v >= T_j.  The top byte of y holds the number of runs (> 8 = the representation does not hold:
-//          checked once after the build)
+//          checked once after the build; SNORM: > 8 = the escape, allowed for red_0 == red_1 only).  SNORM: v is the biased code
 //   z, w   index of run j in byte j (z: runs 0..3, w: runs 4..7): a v_perm_b32 with run counts as selector bytes looks up four
 //          texels at once
+template <bool SGN>
 __global__ void __launch_bounds__(256) bc45_build_index_table(uint4* __restrict__ table)
 {
     const uint32_t r0 = blockIdx.x, r1 = threadIdx.x;
     float g[8];
-    decoded_levels(g, r0, r1);
+    if (SGN) decoded_levels_snorm(g, r0, r1);
+    else     decoded_levels(g, r0, r1);
     uint32_t c[2] = {0u, 0u}, order[2] = {0u, 0u}, runs = 0u, prev = 8u;
     for (uint32_t v = 0; v < 256u; v++) {
-        const float t = (float)v * UNORM_SCALE;
-        // FindClosestUNORM (BC4BC5.cpp:314-337): first index with the strictly smallest |g - t|
-        uint32_t best = 0;
-        float best_delta = 100000.0f;
-#pragma unroll
-        for (uint32_t k = 0; k < 8u; k++) {
-            const float d = fabsf(g[k] - t);
-            if (d < best_delta) { best = k; best_delta = d; }
-        }
+        const uint32_t best = closest_level(g, texel_of<SGN>((float)v));
         if (best != prev) {
             if (runs >= 1u && runs < 8u) c[(runs - 1u) >> 2] |= (256u - v) << (8u * ((runs - 1u) & 3u));
             if (runs < 8u) order[runs >> 2] |= best << (8u * (runs & 3u));
@@ -93,32 +132,36 @@ __global__ void __launch_bounds__(256) bc45_build_index_table(uint4* __restrict_
 }
 
 struct TableSlot { std::once_flag once; uint4* table = nullptr; };
-TableSlot g_tables[64];
+TableSlot g_tables[2][64];                                        // [0] UNORM, [1] SNORM: each built by the first call that needs it
 
 // Built once per device on a stream of the library's own (not on the caller's -- the first call used to synchronise the user's
 // stream): the first BC4 / BC5 call on a device, or itwWarmupBC45(), blocks its HOST thread until the table exists; the caller's stream is
 // never synchronised and later calls are plain asynchronous launches.  That one call allocates device memory, so it cannot run inside a
 // stream capture: warm up first (include/itw_bc45.h).
+template <bool SGN>
 const uint4* index_table()
 {
     int dev = 0;
     ITW_CHECK(hipGetDevice(&dev));
     if (dev < 0 || dev >= 64) fail_msg("BC4/BC5: device ordinal %d out of range", dev);
-    TableSlot& s = g_tables[dev];
+    TableSlot& s = g_tables[SGN ? 1 : 0][dev];
     std::call_once(s.once, [&] {                                  // an exception leaves the flag unset: the next call retries
         uint4* t = nullptr;
         hipStream_t own = nullptr;
         ITW_CHECK(hipStreamCreateWithFlags(&own, hipStreamNonBlocking));
         hipError_t e = hipMalloc(&t, 65536 * sizeof(uint4));
         if (e != hipSuccess) { (void)hipStreamDestroy(own); fail_hip("hipMalloc (BC4/BC5 index table)", e, __FILE__, __LINE__); }
-        hipLaunchKernelGGL(bc45_build_index_table, dim3(256), dim3(256), 0, own, t);
+        hipLaunchKernelGGL(bc45_build_index_table<SGN>, dim3(256), dim3(256), 0, own, t);
         std::vector<uint4> h(65536);
         e = hipMemcpyAsync(h.data(), t, 65536 * sizeof(uint4), hipMemcpyDeviceToHost, own);
         if (e == hipSuccess) e = hipStreamSynchronize(own);       // complete before any later launch, on whatever stream
         (void)hipStreamDestroy(own);
         if (e != hipSuccess) { (void)hipFree(t); fail_hip("bc45_build_index_table", e, __FILE__, __LINE__); }
-        for (const uint4& v : h)
-            if ((v.y >> 24) < 1u || (v.y >> 24) > 8u) { (void)hipFree(t); fail_msg("BC4/BC5 index table: an endpoint pair has %u runs (at most 8 expected)", v.y >> 24); }
+        for (size_t i = 0; i < h.size(); i++) {
+            const uint32_t n = h[i].y >> 24;
+            const bool escape_ok = SGN && (i >> 8) == (i & 255u);  // SNORM, red_0 == red_1: the lane searches the levels itself
+            if (n < 1u || (n > 8u && !escape_ok)) { (void)hipFree(t); fail_msg("BC4/BC5 index table: an endpoint pair has %u runs (at most 8 expected)", n); }
+        }
         s.table = t;
     });
     return s.table;
@@ -145,7 +188,7 @@ __device__ __forceinline__ StepWeights step_weights(int steps, int s)
 
 // One pass over the ramp for the lanes that are still iterating.  SIX = false: no lane of the wave has a 6-step block.
 // `six` (per lane) selects the 6-step ramp; t[] are the texels as floats.
-template <bool SIX>
+template <bool SIX, bool SGN>
 __device__ __forceinline__ void newton_loop(float& fx, float& fy, const float (&t)[16], bool six, const StepWeights* tab8, const StepWeights* tab6)
 {
     const float fsteps = (SIX && six) ? 5.0f : 7.0f;
@@ -157,8 +200,9 @@ __device__ __forceinline__ void newton_loop(float& fx, float& fy, const float (&
         const float scale = fsteps / (fy - fx);
         const float scale16 = scale * 16.0f;                      // exact: the step below comes out multiplied by 16 = its table offset
         // 6-step ramp: below the ramp the texel goes to "exactly 0" when it is nearer, above it to "exactly 1" (BC.h:789-804);
-        // for 8-step lanes the two bounds are out of the texels' range
-        const float to_zero = (SIX && six) ? fx * 0.5f : -1.0f;
+        // for 8-step lanes the two bounds are out of the texels' range ([0, 1], SNORM [-1, 1]).  SNORM keeps both rules as written
+        // (BC.h:817, 819): they are not symmetric about 0
+        const float to_zero = (SIX && six) ? fx * 0.5f : (SGN ? -2.0f : -1.0f);
         const float to_one  = (SIX && six) ? (fy + 1.0f) * 0.5f : 2.0f;
         float dx = 0.0f, dy = 0.0f, d2x = 0.0f, d2y = 0.0f;
         // four texels per batch: their steps first, then their four table reads in flight together, then the sums in texel order
@@ -234,8 +278,8 @@ __device__ __forceinline__ uint2 encode_channel(const uint32_t (&P)[8], const St
     }
     float fx = (float)cx * UNORM_SCALE, fy = (float)cy * UNORM_SCALE;
     if (six && fx == fy) fy = 1.0f;
-    if (any_six) newton_loop<true>(fx, fy, t, six, tab8, tab6);
-    else            newton_loop<false>(fx, fy, t, false, tab8, tab6);
+    if (any_six) newton_loop<true, false>(fx, fy, t, six, tab8, tab6);
+    else            newton_loop<false, false>(fx, fy, t, false, tab8, tab6);
     const float ox = (fx < 0.0f) ? 0.0f : (fx > 1.0f) ? 1.0f : fx;
     const float oy = (fy < 0.0f) ? 0.0f : (fy > 1.0f) ? 1.0f : fy;
     // BC4BC5.cpp:213-237: the 8-step ramp stores (max, min), the 6-step ramp (min, max)
@@ -266,6 +310,115 @@ __device__ __forceinline__ uint2 encode_channel(const uint32_t (&P)[8], const St
         uint32_t& acc = part[q >> 1];
         acc = (acc << 12) | four;
     }
+    return make_uint2(r0 | (r1 << 8) | (part[0] << 16), (part[0] >> 16) | (part[1] << 8));
+}
+
+// ---- the SNORM encoders (D3DXEncodeBC4S; the UNORM function above is kept as it was, instruction for instruction) ---------------------------
+// FindClosestSNORM through the run table: the sixteen 3-bit indices of the biased codes in P for the stored endpoint bytes r0, r1; texels
+// 0..7 in the low 24 bits of part[0], 8..15 in part[1].  The encoders and the test hook (itwTestBc45ClosestS) share it.
+__device__ __forceinline__ void closest_indices_snorm(uint32_t (&part)[2], const uint32_t (&P)[8], uint32_t r0, uint32_t r1, const uint4* __restrict__ runs)
+{
+    // count the run starts that are <= v, two texels per dword
+    const uint4 e = runs[(r0 << 8) | r1];
+    uint32_t C[7];
+#pragma unroll
+    for (int j = 0; j < 7; j++)
+        C[j] = __builtin_amdgcn_perm(0u, j < 4 ? e.x : e.y, 0x0c000c00u | (uint32_t)((j & 3) * 0x00010001));   // byte j -> both halves
+    // run indices as bytes (e.z: runs 0..3, e.w: runs 4..7): a v_perm_b32 whose selector bytes are the run counts (0..7) of FOUR
+    // texels looks all four up at once
+    const uint32_t tab_lo = e.z, tab_hi = e.w;
+    const uint32_t carry = 0x01000100u;
+    part[0] = 0u; part[1] = 0u;                                   // 3-bit indices of texels 0..7 / 8..15
+#pragma unroll
+    for (int q = 3; q >= 0; q--) {                                // four texels (two pairs) per step, from the last down: (acc << 12) | 12 bits
+        uint32_t sa = (P[2 * q] + C[0]) & carry, sb = (P[2 * q + 1] + C[0]) & carry;
+#pragma unroll
+        for (int k = 1; k < 7; k++) { sa += (P[2 * q] + C[k]) & carry; sb += (P[2 * q + 1] + C[k]) & carry; }
+        // the counts sit in bytes 1 and 3 of each sum: gather them in texel order, look the run indices up, squeeze 4 x 3 bits together
+        const uint32_t counts = __builtin_amdgcn_perm(sb, sa, 0x07050301u);
+        const uint32_t idx = __builtin_amdgcn_perm(tab_hi, tab_lo, counts);
+        const uint32_t two = (idx | (idx >> 5)) & 0x003f003fu;    // texels (0,1) in bits 0..5, (2,3) in bits 16..21
+        const uint32_t four = (two | (two >> 10)) & 0x0fffu;
+        uint32_t& acc = part[q >> 1];
+        acc = (acc << 12) | four;
+    }
+    // the escape: an entry with more than 8 runs (30 pairs, all red_0 == red_1) does not describe its pair; such a lane searches the
+    // eight decoded levels as written.  Rare (a wave skips it unless one of its 64 blocks landed on such a pair).
+    const bool escape = (e.y >> 24) > 8u;
+    if (__any(escape)) {
+        if (escape) {
+            float g[8];
+            decoded_levels_snorm(g, r0, r1);
+            part[0] = 0u; part[1] = 0u;
+#pragma unroll
+            for (int j = 0; j < 8; j++) {
+                const uint32_t lo = closest_level(g, texel_of<true>((float)(P[j] & 0xffu)));
+                const uint32_t hi = closest_level(g, texel_of<true>((float)(P[j] >> 16)));
+                part[j >> 2] |= (lo | (hi << 3)) << (6 * (j & 3));
+            }
+        }
+    }
+}
+
+// One channel of one block -> 8 bytes (D3DXEncodeBC4S, BC4BC5.cpp:424-442).  P[j] = biased code of texel 2j | biased code of texel 2j+1 << 16,
+// every code >= 1.
+__device__ __forceinline__ uint2 encode_channel_snorm(const uint32_t (&P)[8], const StepWeights* tab8, const StepWeights* tab6, const uint4* __restrict__ runs)
+{
+    // The kernel hands over biased codes >= 1: int8 -128 was read as -127 on packed halves as the codes were gathered (both are -1.0f, and
+    // -127 * (1/127) is exactly -1.0f), so the texel is the sign-extended byte times 1/127 with no clamp left to do.
+    float t[16];
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+        const uint32_t R = P[j] ^ 0x00800080u;                    // back to two's complement
+        t[2 * j] = (float)(int32_t)(int8_t)(R & 0xffu) * SNORM_SCALE;
+        t[2 * j + 1] = (float)(int32_t)(int8_t)((R >> 16) & 0xffu) * SNORM_SCALE;
+    }
+    // smallest / largest code, and for the 6-step ramp the smallest texel above -1.0 / largest below 1.0 (BC.h:742-766; fX starts at
+    // 1.0 = biased code 255 and fY at -1.0, which is also what "no such texel" leaves behind).  -1.0 is biased code 0 AND code 1 (int8 -128
+    // and -127): the ramp is chosen by "smallest <= 1 or largest == 255", fX is the smallest code above 1, and fY's start, -1.0, is what
+    // codes 0 and 1 both convert to.
+    uint32_t mn = P[0], mx = P[0];
+#pragma unroll
+    for (int j = 1; j < 8; j++) { mn = pk_min_u16(mn, P[j]); mx = pk_max_u16(mx, P[j]); }
+    const uint32_t cmin = min(mn & 0xffffu, mn >> 16), cmax = max(mx & 0xffffu, mx >> 16);
+    const bool six = (cmin <= 1u) || (cmax == 255u);                     // BC4BC5.cpp:267: -1.0f == fBlockMin || 1.0f == fBlockMax
+    const bool any_six = __any(six);                                     // wave-uniform: most waves have no 6-step block at all
+    uint32_t cx = cmin, cy = cmax;
+    if (any_six) {
+        constexpr uint32_t DOWN = 0x00fe00feu;                           // (v - 2) mod 256: the two excluded low codes become the largest
+        uint32_t lo6 = (P[0] + DOWN) & 0x00ff00ffu, hi6 = (P[0] + 0x00010001u) & 0x00ff00ffu;
+#pragma unroll
+        for (int j = 1; j < 8; j++) {
+            lo6 = pk_min_u16(lo6, (P[j] + DOWN) & 0x00ff00ffu);
+            hi6 = pk_max_u16(hi6, (P[j] + 0x00010001u) & 0x00ff00ffu);   // (v + 1) mod 256: code 255 becomes the smallest
+        }
+        if (six) {
+            const uint32_t l = min(lo6 & 0xffffu, lo6 >> 16), h = max(hi6 & 0xffffu, hi6 >> 16);
+            cx = min(l + 2u, 255u);
+            cy = h ? h - 1u : 0u;
+        }
+    }
+    float fx = texel_of<true>((float)cx), fy = texel_of<true>((float)cy);
+    if (six && fx == fy) fy = 1.0f;
+    if (any_six) newton_loop<true, true>(fx, fy, t, six, tab8, tab6);
+    else            newton_loop<false, true>(fx, fy, t, false, tab8, tab6);
+    const float ox = (fx < -1.0f) ? -1.0f : (fx > 1.0f) ? 1.0f : fx;
+    const float oy = (fy < -1.0f) ? -1.0f : (fy > 1.0f) ? 1.0f : fy;
+    // FloatToSNorm (BC4BC5.cpp:161-182): NaN -> 0, clamp (a second time), * 127, +-0.5 by sign, truncate: never -128
+    auto snorm = [](float f) -> uint32_t {
+        if (f != f) f = 0.0f;
+        else if (f > 1.0f) f = 1.0f;
+        else if (f < -1.0f) f = -1.0f;
+        f = f * 127.0f;
+        f = (f >= 0.0f) ? f + 0.5f : f - 0.5f;
+        return (uint32_t)(int32_t)f & 0xffu;
+    };
+    const uint32_t qx = snorm(ox), qy = snorm(oy);
+    // BC4BC5.cpp:267-291: the 8-step ramp stores (max, min), the 6-step ramp (min, max)
+    const uint32_t r0 = six ? qx : qy, r1 = six ? qy : qx;
+
+    uint32_t part[2];
+    closest_indices_snorm(part, P, r0, r1, runs);
     return make_uint2(r0 | (r1 << 8) | (part[0] << 16), (part[0] >> 16) | (part[1] << 8));
 }
 
@@ -317,7 +470,8 @@ __device__ __forceinline__ void load_words45(uint32_t (&w)[16], const uint8_t* _
 // WHOLE (the common case: width and height multiples of 4, the surface below 2 GiB): no partial blocks, and the walk keeps each
 // lane's block position and byte offset incrementally -- one division per workgroup instead of one per chunk, 32-bit offsets from the
 // uniform base instead of four 64-bit row pointers with their source-row / column selects (about 90 of the 630 instructions).
-template <int NCH, bool VEC16, bool WHOLE>
+// SGN (trailing, so that the UNORM instantiations keep their names): the SNORM encoders; the texel codes are biased as they are gathered.
+template <int NCH, bool VEC16, bool WHOLE, bool SGN = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BC45_WAVES, BC45_WAVES)))
 bc45_kernel(const uint8_t* __restrict__ src, int64_t stride, int32_t width, int32_t height, int32_t blocks_x,
             int32_t nlanes, uint8_t* __restrict__ dst, const uint4* __restrict__ runs)
@@ -364,7 +518,10 @@ bc45_kernel(const uint8_t* __restrict__ src, int64_t stride, int32_t width, int3
     for (;;) {
         uint32_t P[8];
 #pragma unroll
-        for (int j = 0; j < 8; j++) P[j] = __builtin_amdgcn_perm(w[2 * j + 1], w[2 * j], sel);
+        for (int j = 0; j < 8; j++) {
+            P[j] = __builtin_amdgcn_perm(w[2 * j + 1], w[2 * j], sel);
+            if (SGN) P[j] = pk_max_u16(P[j] ^ 0x00800080u, 0x00010001u);   // biased; code 0 (int8 -128) becomes code 1 (-127): the same texel, -1.0f
+        }
         const int32_t cur = lane;
         lane += step;
         const bool more = (lane - (int32_t)threadIdx.x) < nlanes;         // uniform per workgroup: some lane of the next chunk exists
@@ -379,47 +536,86 @@ bc45_kernel(const uint8_t* __restrict__ src, int64_t stride, int32_t width, int3
                 load_words45<NCH, VEC16>(w, src, stride, width, height, blocks_x, lane < nlanes ? lane : nlanes - 1);
             }
         }
-        const uint2 o = encode_channel(P, s_tab, s_tab + 8, runs);
+        const uint2 o = SGN ? encode_channel_snorm(P, s_tab, s_tab + 8, runs) : encode_channel(P, s_tab, s_tab + 8, runs);
         if (cur < nlanes) *reinterpret_cast<uint2*>(dst + (int64_t)cur * 8) = o;
         if (!more) break;
     }
 }
 
-template <int NCH>
+template <int NCH, bool SGN>
 void launch_bc45(const uint8_t* src, int64_t stride, int width, int height, uint8_t* dst, hipStream_t st)
 {
     if (width <= 0 || height <= 0) return;
     const int bx = (width + 3) / 4, by = (height + 3) / 4;       // DirectXTex keeps partial blocks
     const int64_t n = (int64_t)bx * by * NCH;
     const bool vec = ((reinterpret_cast<uintptr_t>(src) | (uintptr_t)stride) & 15) == 0;
-    const uint4* runs = index_table();
+    const uint4* runs = index_table<SGN>();
     const int64_t chunks = (n + 255) / 256;
     const dim3 grid((unsigned)(chunks < BC45_GRID ? chunks : BC45_GRID)), blk(256);
     // WHOLE: no partial blocks and every texel offset fits 31 bits (a non-negative stride; 16384^2 RGBA8 is 1 GiB)
     const bool whole = (width % 4 == 0) && (height % 4 == 0) && stride > 0 && (int64_t)height * stride < ((int64_t)1 << 31);
     if (whole) {
-        if (vec) hipLaunchKernelGGL((bc45_kernel<NCH, true, true>),  grid, blk, 0, st, src, stride, width, height, bx, (int32_t)n, dst, runs);
-        else     hipLaunchKernelGGL((bc45_kernel<NCH, false, true>), grid, blk, 0, st, src, stride, width, height, bx, (int32_t)n, dst, runs);
+        if (vec) hipLaunchKernelGGL((bc45_kernel<NCH, true, true, SGN>),  grid, blk, 0, st, src, stride, width, height, bx, (int32_t)n, dst, runs);
+        else     hipLaunchKernelGGL((bc45_kernel<NCH, false, true, SGN>), grid, blk, 0, st, src, stride, width, height, bx, (int32_t)n, dst, runs);
     } else {
-        if (vec) hipLaunchKernelGGL((bc45_kernel<NCH, true, false>),  grid, blk, 0, st, src, stride, width, height, bx, (int32_t)n, dst, runs);
-        else     hipLaunchKernelGGL((bc45_kernel<NCH, false, false>), grid, blk, 0, st, src, stride, width, height, bx, (int32_t)n, dst, runs);
+        if (vec) hipLaunchKernelGGL((bc45_kernel<NCH, true, false, SGN>),  grid, blk, 0, st, src, stride, width, height, bx, (int32_t)n, dst, runs);
+        else     hipLaunchKernelGGL((bc45_kernel<NCH, false, false, SGN>), grid, blk, 0, st, src, stride, width, height, bx, (int32_t)n, dst, runs);
     }
 }
 
+#ifdef ITW_TEST_HOOKS
+// test hook: closest_indices_snorm for every endpoint pair (one lane each) and every code, sixteen codes per call in biased order, which is
+// sixteen consecutive bytes of the pair's 256 once the bias is taken off the position
+__global__ void __launch_bounds__(256) bc45_closest_snorm_kernel(uint8_t* __restrict__ out, const uint4* __restrict__ runs)
+{
+    const uint32_t pair = blockIdx.x * 256u + threadIdx.x, r0 = pair >> 8, r1 = pair & 255u;
+    for (uint32_t c = 0; c < 256u; c += 16u) {
+        uint32_t P[8], part[2];
+#pragma unroll
+        for (uint32_t j = 0; j < 8u; j++) P[j] = (c + 2u * j) | ((c + 2u * j + 1u) << 16);
+        closest_indices_snorm(part, P, r0, r1, runs);
+        uint32_t o[4];
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            const uint32_t bits = part[q >> 1] >> (12 * (q & 1));
+            o[q] = (bits & 7u) | (((bits >> 3) & 7u) << 8) | (((bits >> 6) & 7u) << 16) | (((bits >> 9) & 7u) << 24);
+        }
+        *reinterpret_cast<uint4*>(out + (size_t)pair * 256u + (c ^ 0x80u)) = make_uint4(o[0], o[1], o[2], o[3]);
+    }
+}
+#endif
+
 } // namespace
 
-void launch_bc4(const uint8_t* src, int64_t stride, int width, int height, uint8_t* dst, hipStream_t st) { launch_bc45<1>(src, stride, width, height, dst, st); }
-void launch_bc5(const uint8_t* src, int64_t stride, int width, int height, uint8_t* dst, hipStream_t st) { launch_bc45<2>(src, stride, width, height, dst, st); }
+void launch_bc4(const uint8_t* src, int64_t stride, int width, int height, uint8_t* dst, hipStream_t st) { launch_bc45<1, false>(src, stride, width, height, dst, st); }
+void launch_bc5(const uint8_t* src, int64_t stride, int width, int height, uint8_t* dst, hipStream_t st) { launch_bc45<2, false>(src, stride, width, height, dst, st); }
+void launch_bc4s(const uint8_t* src, int64_t stride, int width, int height, uint8_t* dst, hipStream_t st) { launch_bc45<1, true>(src, stride, width, height, dst, st); }
+void launch_bc5s(const uint8_t* src, int64_t stride, int width, int height, uint8_t* dst, hipStream_t st) { launch_bc45<2, true>(src, stride, width, height, dst, st); }
 
-void warmup_bc45() { (void)index_table(); }
+void warmup_bc45() { (void)index_table<false>(); }
+void warmup_bc45s() { (void)index_table<true>(); }
 
 #ifdef ITW_TEST_HOOKS
 // test hook (include/itw_test_hooks.h): the run table of the current device, 65 536 entries x 4 words, to host memory
 void copy_bc45_index_table(uint32_t* host_out, hipStream_t st)
 {
-    const uint4* t = index_table();
+    const uint4* t = index_table<false>();
     ITW_CHECK(hipMemcpyAsync(host_out, t, 65536 * sizeof(uint4), hipMemcpyDeviceToHost, st));
     ITW_CHECK(hipStreamSynchronize(st));
+}
+
+// test hook: out[(r0 << 8 | r1) * 256 + code] = the index the SNORM encoders give int8 code `code` (as a byte) under endpoint bytes r0, r1; 16 MiB
+void copy_bc45_closest_snorm(uint8_t* host_out, hipStream_t st)
+{
+    const uint4* t = index_table<true>();
+    uint8_t* d = nullptr;
+    ITW_CHECK(hipMalloc(&d, (size_t)1 << 24));
+    hipLaunchKernelGGL(bc45_closest_snorm_kernel, dim3(256), dim3(256), 0, st, d, t);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(host_out, d, (size_t)1 << 24, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    (void)hipFree(d);
+    if (e != hipSuccess) fail_hip("bc45_closest_snorm_kernel", e, __FILE__, __LINE__);
 }
 #endif
 

@@ -13,7 +13,7 @@
 
 namespace itw {
 
-// FMT: 1 BC1, 3 BC3, 7 BC7, 6 BC6H
+// FMT: 1 BC1, 3 BC3, 4 BC4, 5 BC5, 14 BC4_SNORM, 15 BC5_SNORM, 7 BC7, 6 BC6H
 template <int FMT>
 __global__ void __launch_bounds__(256)
 decode_kernel(const uint8_t* __restrict__ blocks, int32_t blocks_x, int32_t nblocks, uint8_t* __restrict__ out, int64_t stride,
@@ -55,6 +55,17 @@ decode_kernel(const uint8_t* __restrict__ blocks, int32_t blocks_x, int32_t nblo
             for (int k = 0; k < 16; k++) px[k] = 0xff000000u;
             decode_scalar_block<0>(w.x, w.y, px);
             decode_scalar_block<8>(w.z, w.w, px);
+        } else if (FMT == 14) {                                  // BC4_SNORM -> int8 (R, 0, 0, 127) like D3DXDecodeBC4S (BC4BC5.cpp:388-400)
+            const uint2 w = *reinterpret_cast<const uint2*>(blocks + (int64_t)b * 8);
+#pragma unroll
+            for (int k = 0; k < 16; k++) px[k] = 0x7f000000u;
+            decode_scalar_block_snorm<0>(w.x, w.y, px);
+        } else if (FMT == 15) {                                  // BC5_SNORM -> int8 (R, G, 0, 127) (BC4BC5.cpp:465-478)
+            const uint4 w = *reinterpret_cast<const uint4*>(blocks + (int64_t)b * 16);
+#pragma unroll
+            for (int k = 0; k < 16; k++) px[k] = 0x7f000000u;
+            decode_scalar_block_snorm<0>(w.x, w.y, px);
+            decode_scalar_block_snorm<8>(w.z, w.w, px);
         } else {
             const uint4 w = *reinterpret_cast<const uint4*>(blocks + (int64_t)b * 16);
             Bits bs{(unsigned long long)w.x | ((unsigned long long)w.y << 32), (unsigned long long)w.z | ((unsigned long long)w.w << 32), 0};
@@ -62,7 +73,8 @@ decode_kernel(const uint8_t* __restrict__ blocks, int32_t blocks_x, int32_t nblo
         }
         uint8_t* o = out + (int64_t)yy * 4 * stride + (int64_t)xx * 16;
         // BC4 / BC5 streams may end in partial blocks (the encoder keeps them, itw_bc45.h): texels beyond the surface are cropped
-        const int ny = (FMT == 4 || FMT == 5) ? min(4, height - yy * 4) : 4, nx = (FMT == 4 || FMT == 5) ? min(4, width - xx * 4) : 4;
+        constexpr bool PARTIAL = FMT == 4 || FMT == 5 || FMT == 14 || FMT == 15;
+        const int ny = PARTIAL ? min(4, height - yy * 4) : 4, nx = PARTIAL ? min(4, width - xx * 4) : 4;
 #pragma unroll
         for (int y = 0; y < 4; y++) {
             if (y >= ny) break;
@@ -86,13 +98,13 @@ bool on_device(const void* p) { return itw::is_device_pointer(p); }     // devic
 
 extern "C" int itwDecodeBlocks(int f, const uint8_t* blocks, int width, int height, uint8_t* out, int64_t out_stride, int32_t* modes)
 {
-    const int kind = (f == 71 || f == 72) ? 1 : (f == 77 || f == 78) ? 3 : (f == 98 || f == 99) ? 7 : (f == 95 || f == 96) ? 6 : f == 80 ? 4 : f == 83 ? 5 : 0;
-    const bool partial_ok = (kind == 4 || kind == 5);            // the DirectXTex formats keep partial blocks
+    const int kind = (f == 71 || f == 72) ? 1 : (f == 77 || f == 78) ? 3 : (f == 98 || f == 99) ? 7 : (f == 95 || f == 96) ? 6 : f == 80 ? 4 : f == 83 ? 5 : f == 81 ? 14 : f == 84 ? 15 : 0;
+    const bool partial_ok = (kind == 4 || kind == 5 || kind == 14 || kind == 15);   // the DirectXTex formats keep partial blocks
     if (!kind || (out_stride & 3)) return -1;
     if (partial_ok ? (width < 1 || height < 1) : (width < 4 || height < 4 || (width & 3) || (height & 3))) return -1;
     const int bx = (width + 3) / 4, by = (height + 3) / 4;
     const int64_t n = (int64_t)bx * by;
-    const size_t in_bytes = (size_t)n * ((kind == 1 || kind == 4) ? 8 : 16), texel = kind == 6 ? 8 : 4;
+    const size_t in_bytes = (size_t)n * ((kind == 1 || kind == 4 || kind == 14) ? 8 : 16), texel = kind == 6 ? 8 : 4;
     const size_t row_bytes = (size_t)width * texel;
     if ((size_t)out_stride < row_bytes) return -1;
     hipStream_t st = (hipStream_t)itwGetStream();
@@ -111,6 +123,8 @@ extern "C" int itwDecodeBlocks(int f, const uint8_t* blocks, int width, int heig
     case 7: hipLaunchKernelGGL((itw::decode_kernel<7>), grid, blk, 0, st, d_in, bx, (int32_t)n, d_out, d_stride, d_modes, width, height); break;
     case 4: hipLaunchKernelGGL((itw::decode_kernel<4>), grid, blk, 0, st, d_in, bx, (int32_t)n, d_out, d_stride, d_modes, width, height); break;
     case 5: hipLaunchKernelGGL((itw::decode_kernel<5>), grid, blk, 0, st, d_in, bx, (int32_t)n, d_out, d_stride, d_modes, width, height); break;
+    case 14: hipLaunchKernelGGL((itw::decode_kernel<14>), grid, blk, 0, st, d_in, bx, (int32_t)n, d_out, d_stride, d_modes, width, height); break;
+    case 15: hipLaunchKernelGGL((itw::decode_kernel<15>), grid, blk, 0, st, d_in, bx, (int32_t)n, d_out, d_stride, d_modes, width, height); break;
     default: hipLaunchKernelGGL((itw::decode_kernel<6>), grid, blk, 0, st, d_in, bx, (int32_t)n, d_out, d_stride, d_modes, width, height); break;
     }
     DEC_CHECK(hipGetLastError());

@@ -90,6 +90,33 @@ __device__ __forceinline__ void decode_scalar_block(uint32_t w0, uint32_t w1, ui
         px[k] = (px[k] & ~(0xffu << SHIFT)) | ((uint32_t)v << SHIFT);
     }
 }
+// The same block with signed endpoints (BC4_SNORM, both halves of BC5_SNORM): int8 values, endpoint -128 read as -127 for the values while
+// the RAW bytes choose the form (BC4_SNORM::DecodeFromIndex, BC4BC5.cpp:106-131); levels 6 and 7 of the 6-level form are -127 and 127.
+// round(n / d) to nearest = floor((2n + d) / (2d)), n offset by 128 * d so that the division works on a non-negative number.
+template <int SHIFT>
+__device__ __forceinline__ void decode_scalar_block_snorm(uint32_t w0, uint32_t w1, uint32_t (&px)[16])
+{
+    const int r0 = (int)(int8_t)(w0 & 255u), r1 = (int)(int8_t)((w0 >> 8) & 255u);
+    int a[8];
+    a[0] = r0 == -128 ? -127 : r0; a[1] = r1 == -128 ? -127 : r1;
+    if (r0 > r1) {
+#pragma unroll
+        for (int i = 1; i < 7; i++) a[1 + i] = (2 * ((7 - i) * a[0] + i * a[1]) + 7 + 128 * 14) / 14 - 128;
+    } else {
+#pragma unroll
+        for (int i = 1; i < 5; i++) a[1 + i] = (2 * ((5 - i) * a[0] + i * a[1]) + 5 + 128 * 10) / 10 - 128;
+        a[6] = -127; a[7] = 127;
+    }
+    const unsigned long long bits = ((unsigned long long)(w0 >> 16)) | ((unsigned long long)w1 << 16);
+#pragma unroll
+    for (int k = 0; k < 16; k++) {
+        const uint32_t q = (uint32_t)(bits >> (3 * k)) & 7u;
+        int v = a[0];
+#pragma unroll
+        for (int i = 1; i < 8; i++) v = (q == (uint32_t)i) ? a[i] : v;
+        px[k] = (px[k] & ~(0xffu << SHIFT)) | (((uint32_t)v & 0xffu) << SHIFT);
+    }
+}
 __device__ __forceinline__ void decode_bc3_alpha(uint32_t w0, uint32_t w1, uint32_t (&px)[16]) { decode_scalar_block<24>(w0, w1, px); }
 
 // ---- BC7 ---------------------------------------------------------------------------------------------------

@@ -151,13 +151,16 @@ void DestroyThreads(void)
 }
 
 // The DirectXTex formats keep partial blocks (itw_bc45.h); the ISPC formats drop them (kernel.ispc:600-601).
-static bool keeps_partial_blocks(int f) { return f == ITW_DXGI_FORMAT_BC4_UNORM || f == ITW_DXGI_FORMAT_BC5_UNORM; }
+static bool keeps_partial_blocks(int f)
+{
+    return f == ITW_DXGI_FORMAT_BC4_UNORM || f == ITW_DXGI_FORMAT_BC5_UNORM || f == ITW_DXGI_FORMAT_BC4_SNORM || f == ITW_DXGI_FORMAT_BC5_SNORM;
+}
 static int blocks_across(int width, int f) { return keeps_partial_blocks(f) ? (width + 3) / 4 : width / 4; }
 
 int GetBytesPerBlock(int f)
 {
     switch (f) {
-    case ITW_DXGI_FORMAT_BC5_UNORM:                              // not in the reference's switch (BC5 never reaches it there)
+    case ITW_DXGI_FORMAT_BC5_UNORM: case ITW_DXGI_FORMAT_BC5_SNORM:   // not in the reference's switch (BC5 never reaches it there)
     case ITW_DXGI_FORMAT_BC3_UNORM_SRGB: case ITW_DXGI_FORMAT_BC3_UNORM:
     case ITW_DXGI_FORMAT_BC7_UNORM_SRGB: case ITW_DXGI_FORMAT_BC7_UNORM:
     case ITW_DXGI_FORMAT_BC6H_UF16: case ITW_DXGI_FORMAT_BC6H_SF16:
@@ -220,6 +223,8 @@ void CompressImageBC1(const rgba_surface* input, uint8_t* output) { CompressBloc
 void CompressImageBC3(const rgba_surface* input, uint8_t* output) { CompressBlocksBC3(input, output); }
 void CompressImageBC4(const rgba_surface* input, uint8_t* output) { CompressBlocksBC4(input, output); }
 void CompressImageBC5(const rgba_surface* input, uint8_t* output) { CompressBlocksBC5(input, output); }
+void CompressImageBC4S(const rgba_surface* input, uint8_t* output) { CompressBlocksBC4S(input, output); }
+void CompressImageBC5S(const rgba_surface* input, uint8_t* output) { CompressBlocksBC5S(input, output); }
 
 #define ITW_BC7_TRAMPOLINE(profile)                                                    \
     void CompressImageBC7_##profile(const rgba_surface* input, uint8_t* output)        \
@@ -253,6 +258,8 @@ static bool resolve_trampoline(CompressionFunc* fn, int dxgi_format, bc7_enc_set
     if (fn == &CompressImageBC3) return dxgi_format == ITW_DXGI_FORMAT_BC3_UNORM || dxgi_format == ITW_DXGI_FORMAT_BC3_UNORM_SRGB;
     if (fn == &CompressImageBC4) return dxgi_format == ITW_DXGI_FORMAT_BC4_UNORM;
     if (fn == &CompressImageBC5) return dxgi_format == ITW_DXGI_FORMAT_BC5_UNORM;
+    if (fn == &CompressImageBC4S) return dxgi_format == ITW_DXGI_FORMAT_BC4_SNORM;
+    if (fn == &CompressImageBC5S) return dxgi_format == ITW_DXGI_FORMAT_BC5_SNORM;
     struct P7 { CompressionFunc* fn; void (*get)(bc7_enc_settings*); };
     static const P7 p7[] = {
         {&CompressImageBC7_ultrafast, &GetProfile_ultrafast}, {&CompressImageBC7_veryfast, &GetProfile_veryfast}, {&CompressImageBC7_fast, &GetProfile_fast},
@@ -393,6 +400,7 @@ int64_t itwChainBytes(const rgba_surface* images, int count, int dxgi_format)
     switch (dxgi_format) {
     case ITW_DXGI_FORMAT_BC1_UNORM: case ITW_DXGI_FORMAT_BC1_UNORM_SRGB: case ITW_DXGI_FORMAT_BC3_UNORM: case ITW_DXGI_FORMAT_BC3_UNORM_SRGB:
     case ITW_DXGI_FORMAT_BC4_UNORM: case ITW_DXGI_FORMAT_BC5_UNORM: case ITW_DXGI_FORMAT_BC6H_UF16: case ITW_DXGI_FORMAT_BC6H_SF16:
+    case ITW_DXGI_FORMAT_BC4_SNORM: case ITW_DXGI_FORMAT_BC5_SNORM:
     case ITW_DXGI_FORMAT_BC7_UNORM: case ITW_DXGI_FORMAT_BC7_UNORM_SRGB: break;
     default: return -1;
     }

@@ -14,6 +14,10 @@ void launch_bc3 (const uint8_t* src, int64_t stride, int width, int height, uint
 // width/height >= 1: ceil(width/4) x ceil(height/4) blocks, partial blocks replicated by DirectXTex's rule.
 void launch_bc4 (const uint8_t* src, int64_t stride, int width, int height, uint8_t* dst, hipStream_t st);
 void launch_bc5 (const uint8_t* src, int64_t stride, int width, int height, uint8_t* dst, hipStream_t st);
+void launch_bc4s(const uint8_t* src, int64_t stride, int width, int height, uint8_t* dst, hipStream_t st);   // BC4_SNORM / BC5_SNORM of an RGBA8_SNORM surface
+void launch_bc5s(const uint8_t* src, int64_t stride, int width, int height, uint8_t* dst, hipStream_t st);
+void warmup_bc45s();                                              // the same for the SNORM encoders' table (FindClosestSNORM)
+void copy_bc45_closest_snorm(uint8_t* host_out, hipStream_t st);  // test hook: the SNORM encoders' index for every (endpoint pair, code), 16 MiB
 void warmup_bc45();                                               // builds the current device's FindClosestUNORM run table now (else: first call)
 void copy_bc45_index_table(uint32_t* host_out, hipStream_t st);   // test hook: the FindClosestUNORM run table of the current device
 // BC7 runs as up to seven kernels (search + finish per multi-subset mode family, one for modes 4/5/6) that hand

@@ -32,7 +32,8 @@ constexpr uint32_t MEASURE_INDEX_MASK = (1u << MEASURE_INDEX_BITS) - 1u;
 constexpr int MEASURE_MAX_GROUPS = 1024;      // 4 workgroups per CU; <= 2^25 / (1024 * 256) = 128 blocks per lane: 128 * 16 * 255^2 < 2^32
 static_assert((uint64_t)ITW_MEASURE_MAX_BLOCKS == (1ull << MEASURE_INDEX_BITS), "the key's index field is what limits the block count");
 
-// FMT: 1 BC1, 3 BC3, 4 BC4, 5 BC5, 7 BC7, 6 BC6H (decode_kernel's numbering)
+// FMT: 1 BC1, 3 BC3, 4 BC4, 5 BC5, 14 BC4_SNORM, 15 BC5_SNORM, 7 BC7, 6 BC6H (decode_kernel's numbering).  The SNORM pair compares
+// int8 codes, a source code of -128 read as -127 (both are -1.0; the decoder never emits -128)
 template <int FMT>
 __global__ void __launch_bounds__(256)
 measure_kernel(const uint8_t* __restrict__ blocks, int32_t blocks_x, int32_t nblocks, const uint8_t* __restrict__ src, int64_t stride,
@@ -98,6 +99,17 @@ measure_kernel(const uint8_t* __restrict__ blocks, int32_t blocks_x, int32_t nbl
                 for (int k = 0; k < 16; k++) px[k] = 0xff000000u;
                 decode_scalar_block<0>(w.x, w.y, px);
                 decode_scalar_block<8>(w.z, w.w, px);
+            } else if (FMT == 14) {
+                const uint2 w = *reinterpret_cast<const uint2*>(blocks + (int64_t)b * 8);
+#pragma unroll
+                for (int k = 0; k < 16; k++) px[k] = 0x7f000000u;
+                decode_scalar_block_snorm<0>(w.x, w.y, px);
+            } else if (FMT == 15) {
+                const uint4 w = *reinterpret_cast<const uint4*>(blocks + (int64_t)b * 16);
+#pragma unroll
+                for (int k = 0; k < 16; k++) px[k] = 0x7f000000u;
+                decode_scalar_block_snorm<0>(w.x, w.y, px);
+                decode_scalar_block_snorm<8>(w.z, w.w, px);
             } else {
                 const uint4 w = *reinterpret_cast<const uint4*>(blocks + (int64_t)b * 16);
                 Bits rd{(unsigned long long)w.x | ((unsigned long long)w.y << 32), (unsigned long long)w.z | ((unsigned long long)w.w << 32), 0};
@@ -114,7 +126,8 @@ measure_kernel(const uint8_t* __restrict__ blocks, int32_t blocks_x, int32_t nbl
                     if (x >= nx) continue;
 #pragma unroll
                     for (int c = 0; c < 4; c++) {
-                        const int a = (int)((s[x] >> (8 * c)) & 255u), e = (int)((px[y * 4 + x] >> (8 * c)) & 255u);
+                        int a = (int)((s[x] >> (8 * c)) & 255u), e = (int)((px[y * 4 + x] >> (8 * c)) & 255u);
+                        if (FMT == 14 || FMT == 15) { a = max((int)(int8_t)a, -127); e = (int)(int8_t)e; }
                         const uint32_t df = (uint32_t)abs(a - e);
                         bs[c] += df * df;
                         mx[c] = max(mx[c], df);
@@ -189,10 +202,11 @@ namespace {
 
 int kind_of(int f)
 {
-    return (f == 71 || f == 72) ? 1 : (f == 77 || f == 78) ? 3 : (f == 98 || f == 99) ? 7 : (f == 95 || f == 96) ? 6 : f == 80 ? 4 : f == 83 ? 5 : 0;
+    return (f == 71 || f == 72) ? 1 : (f == 77 || f == 78) ? 3 : (f == 98 || f == 99) ? 7 : (f == 95 || f == 96) ? 6 : f == 80 ? 4 : f == 83 ? 5 :
+           f == 81 ? 14 : f == 84 ? 15 : 0;
 }
 int64_t blocks_of(const rgba_surface& s) { return (int64_t)((s.width + 3) / 4) * ((s.height + 3) / 4); }
-int block_bytes(int kind) { return (kind == 1 || kind == 4) ? 8 : 16; }
+int block_bytes(int kind) { return (kind == 1 || kind == 4 || kind == 14) ? 8 : 16; }
 
 // the checks that need no device
 bool surface_ok(int kind, const rgba_surface* s)
@@ -219,6 +233,8 @@ void enqueue(int kind, int dxgi_format, const uint8_t* d_blocks, const uint8_t* 
     case 3: hipLaunchKernelGGL((itw::measure_kernel<3>), grid, blk, 0, st, d_blocks, bx, (int32_t)n, d_src, stride, width, height, d_stats, map); break;
     case 4: hipLaunchKernelGGL((itw::measure_kernel<4>), grid, blk, 0, st, d_blocks, bx, (int32_t)n, d_src, stride, width, height, d_stats, map); break;
     case 5: hipLaunchKernelGGL((itw::measure_kernel<5>), grid, blk, 0, st, d_blocks, bx, (int32_t)n, d_src, stride, width, height, d_stats, map); break;
+    case 14: hipLaunchKernelGGL((itw::measure_kernel<14>), grid, blk, 0, st, d_blocks, bx, (int32_t)n, d_src, stride, width, height, d_stats, map); break;
+    case 15: hipLaunchKernelGGL((itw::measure_kernel<15>), grid, blk, 0, st, d_blocks, bx, (int32_t)n, d_src, stride, width, height, d_stats, map); break;
     case 7: hipLaunchKernelGGL((itw::measure_kernel<7>), grid, blk, 0, st, d_blocks, bx, (int32_t)n, d_src, stride, width, height, d_stats, map); break;
     default: hipLaunchKernelGGL((itw::measure_kernel<6>), grid, blk, 0, st, d_blocks, bx, (int32_t)n, d_src, stride, width, height, d_stats, map); break;
     }
@@ -325,5 +341,7 @@ extern "C" double itwStatsPsnr(const itw_error_stats* stats, uint32_t channel_ma
         if (channel_mask & (1u << c)) { sum += (double)stats->sse[c]; channels++; }
     if (sum == 0.0) return std::numeric_limits<double>::infinity();
     const double n = (double)stats->width * (double)stats->height * (double)channels;
-    return 10.0 * std::log10(255.0 * 255.0 * n / sum);
+    const int kind = kind_of(stats->dxgi_format);
+    const double peak = (kind == 14 || kind == 15) ? 254.0 : 255.0;      // int8 codes -127..127
+    return 10.0 * std::log10(peak * peak * n / sum);
 }

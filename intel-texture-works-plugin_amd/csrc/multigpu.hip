@@ -608,7 +608,8 @@ bool compress_multi(const rgba_surface* input, uint8_t* output, CompressionFunc*
         if (g.wedged) itw::fail_msg("itwCompressImageMultiGPU: a rank thread never returned from an earlier call (watchdog); restart the process");
         Call k;
         k.input = *input; k.output = output; k.fn = cmpFunc; k.bands = bands;
-        k.keep_partial = dxgi_format == ITW_DXGI_FORMAT_BC4_UNORM || dxgi_format == ITW_DXGI_FORMAT_BC5_UNORM;
+        k.keep_partial = dxgi_format == ITW_DXGI_FORMAT_BC4_UNORM || dxgi_format == ITW_DXGI_FORMAT_BC5_UNORM ||
+                         dxgi_format == ITW_DXGI_FORMAT_BC4_SNORM || dxgi_format == ITW_DXGI_FORMAT_BC5_SNORM;
         k.bpb = GetBytesPerBlock(dxgi_format);
         k.texel_bytes = (dxgi_format == ITW_DXGI_FORMAT_BC6H_UF16 || dxgi_format == ITW_DXGI_FORMAT_BC6H_SF16) ? 8 : 4;
         const int by = k.keep_partial ? (input->height + 3) / 4 : input->height / 4;

@@ -6,8 +6,9 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 _LIB = os.path.normpath(os.path.join(_PKG, "..", "lib", "libispc_texcomp.so"))
 _TEST_LIB = os.path.normpath(os.path.join(_PKG, "..", "lib", "libispc_texcomp_test.so"))
 
-BYTES_PER_BLOCK = {"bc1": 8, "bc3": 16, "bc7": 16, "bc6h": 16, "bc4": 8, "bc5": 16}
-KEEPS_PARTIAL_BLOCKS = ("bc4", "bc5")     # DirectXTex formats: ceil(w/4) x ceil(h/4) blocks (include/itw_bc45.h)
+BYTES_PER_BLOCK = {"bc1": 8, "bc3": 16, "bc7": 16, "bc6h": 16, "bc4": 8, "bc5": 16, "bc4_snorm": 8, "bc5_snorm": 16}
+KEEPS_PARTIAL_BLOCKS = ("bc4", "bc5", "bc4_snorm", "bc5_snorm")     # DirectXTex formats: ceil(w/4) x ceil(h/4) blocks (include/itw_bc45.h)
+SIGNED_FORMATS = ("bc4_snorm", "bc5_snorm")     # RGBA8_SNORM sources: int8 arrays / tensors, never uint8 (include/itw_bc45.h)
 BC7_PROFILES = ("ultrafast", "veryfast", "fast", "basic", "slow",
                 "alpha_ultrafast", "alpha_veryfast", "alpha_fast", "alpha_basic", "alpha_slow")
 BC6H_PROFILES = ("veryfast", "fast", "basic", "slow", "veryslow")
@@ -20,7 +21,7 @@ EXPORTED_SYMBOLS = tuple(
        "itwDeviceInfo", "itwVersion", "itwBandForPart", "itwBandForPartEx"]
     # include/itw_dispatch.h: the reference's dispatch layer (win32Threads.h), slice loop, pad pre-pass
     + ["GetProcessorCount", "InitWin32Threads", "DestroyThreads", "GetBytesPerBlock", "CompressImageMT", "CompressImageST",
-       "CompressImageBC1", "CompressImageBC3", "CompressImageBC4", "CompressImageBC5"]
+       "CompressImageBC1", "CompressImageBC3", "CompressImageBC4", "CompressImageBC5", "CompressImageBC4S", "CompressImageBC5S"]
     + ["CompressImageBC7_" + p for p in BC7_PROFILES] + ["CompressImageBC6H_" + p for p in BC6H_PROFILES]
     + ["itwCompressImageSliced", "itwCompressImageSlicedEx", "itwChainBytes", "itwCompressImageChain", "itwCompressImageChainEx", "itwCompressImageRefined", "itwSetSliceWindow", "itwSliceWindow", "itwSliceWindowFor", "itwPadToMultipleOf4", "itwFreeSurface", "itwPadToMultipleOf4Device",
        "itwConvertToRGBA8Device", "itwConvertToRGBA16FDevice"]
@@ -28,13 +29,14 @@ EXPORTED_SYMBOLS = tuple(
     + ["itwMultiGpuRanks", "itwMultiGpuTransport", "itwMultiGpuPeerLinks", "itwCompressImageMultiGPU", "itwCompressImageMultiGPUEx", "itwCompressImageMultiGPUBands",
        "itwMultiGpuSetInterleave", "itwMultiGpuPieces"]
     # include/itw_bc45.h: the DirectXTex formats of the plugin
-    + ["CompressBlocksBC4", "CompressBlocksBC5", "itwWarmupBC45"]
+    + ["CompressBlocksBC4", "CompressBlocksBC5", "itwWarmupBC45", "CompressBlocksBC4S", "CompressBlocksBC5S", "itwWarmupBC45S"]
     # include/itw_decode.h: device decoders
     + ["itwDecodeBlocks", "itwMeasureBlocks", "itwMeasureChain", "itwStatsPsnr"]
     # include/itw_dds.h: DDS container
     + ["itwDdsLevelBytes", "itwDdsHeaderBytes", "itwDdsFileBytes", "itwDdsWriteHeader", "itwDdsReadHeader", "itwDdsWriteFile"])
 # include/itw_test_hooks.h: exported by libispc_texcomp_test.so only (the same sources built with -DITW_TEST_HOOKS), never by the product
-TEST_HOOK_SYMBOLS = ("itwTestRcp", "itwTestRsqrt", "itwTestF2I", "itwTestBc7TwoSubsetBounds", "itwTestBc45IndexTable", "itwMultiGpuTestInjectFailure")
+TEST_HOOK_SYMBOLS = ("itwTestRcp", "itwTestRsqrt", "itwTestF2I", "itwTestBc7TwoSubsetBounds", "itwTestBc45IndexTable", "itwTestBc45ClosestS",
+                     "itwMultiGpuTestInjectFailure")
 
 
 
@@ -61,7 +63,7 @@ class Bc6hSettings(C.Structure):
 
 assert C.sizeof(RgbaSurface) == 24 and C.sizeof(Bc7Settings) == 64 and C.sizeof(Bc6hSettings) == 16
 
-DXGI_FORMAT = {"bc1": 71, "bc1_srgb": 72, "bc3": 77, "bc3_srgb": 78, "bc4": 80, "bc5": 83, "bc6h": 95, "bc6h_sf16": 96, "bc7": 98, "bc7_srgb": 99}
+DXGI_FORMAT = {"bc1": 71, "bc1_srgb": 72, "bc3": 77, "bc3_srgb": 78, "bc4": 80, "bc4_snorm": 81, "bc5": 83, "bc5_snorm": 84, "bc6h": 95, "bc6h_sf16": 96, "bc7": 98, "bc7_srgb": 99}
 
 
 class DdsDesc(C.Structure):
@@ -95,8 +97,21 @@ class MultiGpuStats(C.Structure):
 
 
 # the channels of a decoded texel that carry a format's own data (the others are fill values: itw_decode.h)
-OWN_CHANNELS = {"bc1": "rgb", "bc3": "rgba", "bc4": "r", "bc5": "rg", "bc6h": "rgb", "bc7": "rgba"}
-_DXGI_BASE = {71: "bc1", 72: "bc1", 77: "bc3", 78: "bc3", 80: "bc4", 83: "bc5", 95: "bc6h", 96: "bc6h", 98: "bc7", 99: "bc7"}
+OWN_CHANNELS = {"bc1": "rgb", "bc3": "rgba", "bc4": "r", "bc5": "rg", "bc4_snorm": "r", "bc5_snorm": "rg", "bc6h": "rgb", "bc7": "rgba"}
+_DXGI_BASE = {71: "bc1", 72: "bc1", 77: "bc3", 78: "bc3", 80: "bc4", 81: "bc4_snorm", 83: "bc5", 84: "bc5_snorm", 95: "bc6h", 96: "bc6h",
+              98: "bc7", 99: "bc7"}
+
+
+def _base(fmt):
+    """Key of BYTES_PER_BLOCK for a key of DXGI_FORMAT: 'bc7_srgb' -> 'bc7'; the signed formats are their own base."""
+    return fmt if fmt in SIGNED_FORMATS else fmt.split("_")[0]
+
+
+def _check_texel_type(fmt, img):
+    """The signed formats take int8 texels and nothing else: a uint8 array reinterpreted as int8 would encode 200 as -56 without a word."""
+    if fmt in SIGNED_FORMATS and not str(img.dtype).endswith(".int8") and str(img.dtype) != "int8":     # numpy "int8", torch "torch.int8"
+        raise TypeError(f"{fmt} encodes RGBA8_SNORM: pass an int8 array / tensor, not {img.dtype} "
+                        "(view uint8 bytes as int8 if they are two's complement codes)")
 
 
 def _channel_mask(channels):
@@ -195,6 +210,10 @@ def _load(path, hooks):
         L.CompressBlocksBC5.argtypes = [C.POINTER(RgbaSurface), C.c_void_p]
         L.CompressBlocksBC4.restype = None
         L.itwWarmupBC45.restype = None
+        for n in ("CompressBlocksBC4S", "CompressBlocksBC5S", "CompressImageBC4S", "CompressImageBC5S"):
+            getattr(L, n).argtypes = [C.POINTER(RgbaSurface), C.c_void_p]
+            getattr(L, n).restype = None
+        L.itwWarmupBC45S.restype = None
         L.CompressBlocksBC5.restype = None
         L.CompressBlocksBC3.argtypes = [C.POINTER(RgbaSurface), C.c_void_p]
         L.CompressBlocksBC7.argtypes = [C.POINTER(RgbaSurface), C.c_void_p, C.POINTER(Bc7Settings)]
@@ -227,6 +246,8 @@ def _load(path, hooks):
             L.itwTestBc7TwoSubsetBounds.restype = None
             L.itwTestBc45IndexTable.argtypes = [C.c_void_p]
             L.itwTestBc45IndexTable.restype = C.c_int
+            L.itwTestBc45ClosestS.argtypes = [C.c_void_p]
+            L.itwTestBc45ClosestS.restype = C.c_int
             L.itwMultiGpuTestInjectFailure.argtypes = [C.c_int, C.c_int, C.c_int]
             L.itwMultiGpuTestInjectFailure.restype = None
         # dispatch layer (itw_dispatch.h)
@@ -397,6 +418,10 @@ def _call(fmt, surf, dst_ptr, settings):
         L.CompressBlocksBC4(C.byref(surf), dst_ptr)
     elif fmt == "bc5":
         L.CompressBlocksBC5(C.byref(surf), dst_ptr)
+    elif fmt == "bc4_snorm":
+        L.CompressBlocksBC4S(C.byref(surf), dst_ptr)
+    elif fmt == "bc5_snorm":
+        L.CompressBlocksBC5S(C.byref(surf), dst_ptr)
     elif fmt == "bc7":
         st = settings if isinstance(settings, Bc7Settings) else bc7_profile(settings or "slow")
         L.CompressBlocksBC7(C.byref(surf), dst_ptr, C.byref(st))
@@ -415,11 +440,12 @@ def block_count(fmt, width, height):
 
 
 def compress_numpy(fmt, img, settings=None):
-    """Host-pointer path (what the Photoshop plugin does): img (H, W, 4) uint8, or uint16 half bits for bc6h.
-    Synchronous; returns a uint8 numpy array of packed blocks."""
+    """Host-pointer path (what the Photoshop plugin does): img (H, W, 4) uint8, or uint16 half bits for bc6h, or int8 for the
+    signed formats (TypeError for uint8).  Synchronous; returns a uint8 numpy array of packed blocks."""
     import numpy as np
+    _check_texel_type(fmt, img)
     assert img.ndim == 3 and img.shape[2] == 4 and img.strides[2] == img.itemsize and img.strides[1] == 4 * img.itemsize
-    assert img.dtype == (np.uint16 if fmt == "bc6h" else np.uint8)
+    assert img.dtype == (np.uint16 if fmt == "bc6h" else np.int8 if fmt in SIGNED_FORMATS else np.uint8)
     h, w = img.shape[:2]
     out = np.empty(block_count(fmt, w, h) * BYTES_PER_BLOCK[fmt], dtype=np.uint8)
     surf = RgbaSurface(img.ctypes.data, w, h, img.strides[0])
@@ -428,9 +454,11 @@ def compress_numpy(fmt, img, settings=None):
 
 
 def compress(fmt, img, settings=None, out=None):
-    """Device-resident path: img is a CUDA(HIP) torch tensor (H, W, 4) uint8, or int16/uint16/float16 for bc6h;
-    rows may be strided.  Launches asynchronously on torch's current stream and returns a uint8 CUDA tensor."""
+    """Device-resident path: img is a CUDA(HIP) torch tensor (H, W, 4) uint8, or int16/uint16/float16 for bc6h, or int8 for the
+    signed formats (TypeError for uint8); rows may be strided.  Launches asynchronously on torch's current stream and returns a uint8
+    CUDA tensor."""
     import torch
+    _check_texel_type(fmt, img)
     assert img.is_cuda and img.dim() == 3 and img.shape[2] == 4
     es = img.element_size()
     assert es == (2 if fmt == "bc6h" else 1), "texel type does not match the format"
@@ -469,7 +497,8 @@ def bc7_two_subset_bounds(img):
 
 def image_func(fmt, profile=None, L=None):
     """Address of the CompressImage* trampoline (win32Threads.h:58-80) for a format / profile, as a void* (L: the library instance, default the product)."""
-    name = {"bc1": "CompressImageBC1", "bc3": "CompressImageBC3", "bc4": "CompressImageBC4", "bc5": "CompressImageBC5"}.get(fmt) or \
+    name = {"bc1": "CompressImageBC1", "bc3": "CompressImageBC3", "bc4": "CompressImageBC4", "bc5": "CompressImageBC5",
+            "bc4_snorm": "CompressImageBC4S", "bc5_snorm": "CompressImageBC5S"}.get(fmt) or \
         ("CompressImageBC7_" if fmt == "bc7" else "CompressImageBC6H_") + (profile or "slow")
     return C.cast(getattr(L or lib(), name), C.c_void_p)
 
@@ -480,6 +509,7 @@ def compress_image(fmt, img, profile=None, multithreaded=True, slice_pixels=0, p
     itwCompressImageSlicedEx).  img: host numpy (H, W, 4) uint8 / uint16 half bits, or a CUDA torch tensor of that shape
     (then `out` is a CUDA uint8 tensor too unless given).  Returns (ok, blocks)."""
     import numpy as np
+    _check_texel_type(fmt, img)
     h, w = img.shape[:2]
     nbytes = block_count(fmt, w, h) * BYTES_PER_BLOCK[fmt]
     on_device = hasattr(img, "data_ptr")
@@ -531,7 +561,9 @@ def compress_chain(fmt, images, profile=None, settings=None, progress=None, out=
     by default the images' kind.  Returns (ok, blocks): the images' blocks one after another, tightly packed (a DDS payload)."""
     import numpy as np
     fmt_key = fmt
-    base = fmt.split("_")[0]
+    base = _base(fmt)
+    for img in images:
+        _check_texel_type(fmt, img)
     nbytes = sum(((img.shape[1] + 3) // 4) * ((img.shape[0] + 3) // 4) for img in images) * BYTES_PER_BLOCK[base]
     on_device = bool(images) and hasattr(images[0], "data_ptr")
     if out is None:
@@ -677,22 +709,23 @@ def dds_file(fmt_key, width, height, levels, mip_levels=1, cubemap=False, array_
 
 def decode(fmt, blocks, width, height, want_modes=False):
     """GPU decode (itwDecodeBlocks).  blocks: uint8 numpy array or CUDA torch tensor of packed blocks.  Returns texels as
-    (H, W, 4) uint8 -- uint16 half bit patterns for bc6h -- in the same kind of container, plus the per-block modes
+    (H, W, 4) uint8 -- uint16 half bit patterns for bc6h, int8 for the signed formats -- in the same kind of container, plus the per-block modes
     (int32) when asked."""
     import numpy as np
-    key = {"bc1": 71, "bc3": 77, "bc7": 98, "bc6h": 95, "bc4": 80, "bc5": 83}[fmt]
+    key = {"bc1": 71, "bc3": 77, "bc7": 98, "bc6h": 95, "bc4": 80, "bc5": 83, "bc4_snorm": 81, "bc5_snorm": 84}[fmt]
+    signed = fmt in SIGNED_FORMATS                      # RGBA8_SNORM texels: int8
     nb = block_count(fmt, width, height)
     es = 2 if fmt == "bc6h" else 1
     if isinstance(blocks, np.ndarray):
         blk = np.ascontiguousarray(blocks, dtype=np.uint8).reshape(-1)
-        out = np.empty((height, width, 4), dtype=np.uint16 if fmt == "bc6h" else np.uint8)
+        out = np.empty((height, width, 4), dtype=np.uint16 if fmt == "bc6h" else np.int8 if signed else np.uint8)
         modes = np.empty(nb, dtype=np.int32) if want_modes else None
         rc = lib().itwDecodeBlocks(key, blk.ctypes.data, width, height, out.ctypes.data, width * 4 * es,
                                    modes.ctypes.data if want_modes else None)
     else:
         import torch
         assert blocks.is_cuda and blocks.dtype == torch.uint8 and blocks.is_contiguous()
-        out = torch.empty((height, width, 4), dtype=torch.int16 if fmt == "bc6h" else torch.uint8, device=blocks.device)
+        out = torch.empty((height, width, 4), dtype=torch.int16 if fmt == "bc6h" else torch.int8 if signed else torch.uint8, device=blocks.device)
         modes = torch.empty(nb, dtype=torch.int32, device=blocks.device) if want_modes else None
         with torch.cuda.device(blocks.device):
             lib().itwSetStream(torch.cuda.current_stream(blocks.device).cuda_stream)
@@ -708,13 +741,14 @@ def measure_async(fmt, blocks, img, stats_out, block_map=None):
     blocks: CUDA uint8 tensor; img: CUDA tensor (H, W, 4), rows may be strided; stats_out: CUDA uint8 tensor of sizeof(ErrorStats) bytes
     (read it back with stats_from_tensor); block_map (optional): CUDA int64 tensor, one element per block."""
     import torch
+    _check_texel_type(fmt, img)
     assert blocks.is_cuda and blocks.dtype == torch.uint8 and blocks.is_contiguous()
     assert img.is_cuda and img.dim() == 3 and img.shape[2] == 4 and img.stride(2) == 1 and img.stride(1) == 4
     assert img.element_size() == (2 if fmt.split("_")[0] == "bc6h" else 1), "texel type does not match the format"
     assert stats_out.is_cuda and stats_out.dtype == torch.uint8 and stats_out.is_contiguous() and stats_out.numel() == C.sizeof(ErrorStats)
     h, w = img.shape[:2]
     nb = ((w + 3) // 4) * ((h + 3) // 4)
-    assert blocks.numel() >= nb * BYTES_PER_BLOCK[fmt.split("_")[0]]
+    assert blocks.numel() >= nb * BYTES_PER_BLOCK[_base(fmt)]
     assert block_map is None or (block_map.is_cuda and block_map.dtype == torch.int64 and block_map.is_contiguous() and block_map.numel() >= nb)
     with torch.cuda.device(img.device):
         lib().itwSetStream(torch.cuda.current_stream(img.device).cuda_stream)
@@ -736,10 +770,11 @@ def stats_from_tensor(t):
 def measure(fmt, blocks, img, want_block_map=False):
     """itwMeasureBlocks: the integer error statistics of the stream `blocks` against its source `img`, decoded and compared on the GPU in
     one kernel.  numpy arrays (host pointers) or CUDA tensors (device pointers), as for decode(); img is (H, W, 4) uint8, or uint16 /
-    int16 / float16 half bit patterns for bc6h, any H, W >= 1, and blocks holds ceil(W/4)*ceil(H/4) blocks.  fmt: a key of DXGI_FORMAT.
+    int16 / float16 half bit patterns for bc6h, int8 for the signed formats, any H, W >= 1, and blocks holds ceil(W/4)*ceil(H/4) blocks.  fmt: a key of DXGI_FORMAT.
     Returns an ErrorStats; with want_block_map also the per-block sums (uint64 numpy array, or int64 CUDA tensor)."""
     import numpy as np
-    base = fmt.split("_")[0]
+    base = _base(fmt)
+    _check_texel_type(fmt, img)
     h, w = img.shape[:2]
     nb = ((w + 3) // 4) * ((h + 3) // 4)
     if isinstance(blocks, np.ndarray):
@@ -767,7 +802,9 @@ def measure_chain(fmt, blocks, levels):
     """itwMeasureChain: one ErrorStats per image of a chain encoded by compress_chain(fmt, levels): `blocks` is its packed stream.
     levels and blocks: numpy arrays, or CUDA tensors (then the call runs on torch's current stream and the result is copied back)."""
     import numpy as np
-    base = fmt.split("_")[0]
+    base = _base(fmt)
+    for lv in levels:
+        _check_texel_type(fmt, lv)
     total = sum(((lv.shape[1] + 3) // 4) * ((lv.shape[0] + 3) // 4) for lv in levels) * BYTES_PER_BLOCK[base]
     arr = _surfaces(levels)
     n = len(levels)

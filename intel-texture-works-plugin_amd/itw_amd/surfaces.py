@@ -1,7 +1,8 @@
 """Synthetic input surfaces for parity tests and benchmarks (SURVEY.md section 8d inputs I3/I3u/I4s/I4r).
 
 All generators are seeded and return numpy arrays laid out like an `rgba_surface`:
-(H, W, 4) uint8 for BC1/BC3/BC7, (H, W, 4) uint16 (IEEE half bit patterns) for BC6H.
+(H, W, 4) uint8 for BC1/BC3/BC7, (H, W, 4) uint16 (IEEE half bit patterns) for BC6H, (H, W, 4) int8 (RGBA8_SNORM) for
+BC4_SNORM / BC5_SNORM.
 """
 import hashlib
 import numpy as np
@@ -49,6 +50,21 @@ def ldr_alpha_variant(img, kind, seed=SEED + 7):
     opaque = rng.integers(0, 2, size=((h + 3) // 4, (w + 3) // 4), dtype=np.uint8).astype(bool)
     mask = np.repeat(np.repeat(opaque, 4, axis=0), 4, axis=1)[:h, :w]
     out[..., 3] = np.where(mask, np.uint8(255), img[..., 3])
+    return out
+
+
+def snorm_normal_map(h, w, seed=SEED + 5, strength=4.0):
+    """A tangent-space normal map as RGBA8_SNORM, (H, W, 4) int8: the unit normals (-s dH/dx, -s dH/dy, 1) / |.| of a seeded smooth
+    height field H (s = strength, slopes per texel), x and y in bytes 0 and 1 (what BC5_SNORM stores), z in byte 2, 127 in byte 3;
+    a component c is stored as rint(127 c).  Steep flanks reach +-127, so both ramp forms of the encoder occur."""
+    rng = np.random.default_rng(seed)
+    hgt = _smooth_fields(h, w, 1, rng)[0] * np.float32(w / 64.0)
+    dy, dx = (np.gradient(hgt, axis=0), np.gradient(hgt, axis=1)) if min(h, w) > 1 else (np.zeros_like(hgt), np.zeros_like(hgt))
+    n = np.stack([-np.float32(strength) * dx, -np.float32(strength) * dy, np.ones_like(hgt)], axis=-1).astype(np.float32)
+    n /= np.sqrt((n * n).sum(axis=-1, keepdims=True))
+    out = np.empty((h, w, 4), dtype=np.int8)
+    out[..., :3] = np.rint(n * np.float32(127.0)).astype(np.int8)
+    out[..., 3] = 127
     return out
 
 
