@@ -42,6 +42,15 @@ int itwTestBc45ClosestS(uint8_t* host_out);
  * `stall_ms` before posting anything, which is what the watchdog is for).  One-shot; nothing in the environment can set it. */
 void itwMultiGpuTestInjectFailure(int rank, int stage, int stall_ms);
 
+/* The call combiner (csrc/abi.hip coalesce_small_call; tests/test_gpu_call_combiner.py).  One-shot, for the calling thread's current device:
+ * the next leader of that device's combiner, before it takes the queue, waits -- without the mutex, like the burst wait, and in its place --
+ * until at least `requests` requests are queued or `timeout_ms` have passed.  With `requests` = the number of calling threads all of them
+ * reach one batch, whatever their arrival times; with fewer the burst is handed from leader to leader. */
+void itwTestCombinerHold(int requests, int timeout_ms);
+/* out[0..4] = bursts, batches (leader rounds), requests, merged calls run, holds that ended by their timeout: of this library instance, all
+ * devices, since it was loaded.  The hooks build counts always, not only under ITW_COALESCE_DEBUG. */
+void itwTestCombinerCounters(int64_t out[5]);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

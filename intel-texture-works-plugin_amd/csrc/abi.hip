@@ -1033,8 +1033,14 @@ bool combiner_debug()
         });
         return v;
     }();
+#ifdef ITW_TEST_HOOKS
+    if (!on) return true;              // the hooks build always counts (itwTestCombinerCounters); the report at exit stays the variable's
+#endif
     return on;
 }
+#ifdef ITW_TEST_HOOKS
+std::atomic<long long> g_hold_timeouts{0};            // itwTestCombinerHold: holds that ended by their timeout
+#endif
 
 struct Combiner {
     std::mutex m;
@@ -1045,6 +1051,9 @@ struct Combiner {
     int burst = 0;                     // requests served since the queue was last idle
     int expected = 1;                  // size of the previous burst: the reference's pool submits the same number of bands
                                        // for every slice (win32Threads.cpp:217-231), so the next burst will be this large too
+#ifdef ITW_TEST_HOOKS
+    int hold_requests = 0, hold_timeout_ms = 0;       // itwTestCombinerHold (one-shot): the next leader waits for this many queued requests
+#endif
 };
 constexpr int kMaxDevices = 64;
 Combiner g_combiner[kMaxDevices];
@@ -1096,22 +1105,30 @@ bool continues(const Pending& a, const Pending& b)
 void run_batch(std::vector<Pending*>& batch)
 {
     std::sort(batch.begin(), batch.end(), [](const Pending* a, const Pending* b) { return a->src.ptr < b->src.ptr; });
-    size_t i = 0;
-    while (i < batch.size()) {
-        size_t k = i + 1;
+    // A chain's next request starts where its last one ends, so it lies further on in the sorted order -- as a rule right behind it, but the
+    // bands of two surfaces that interleave in memory (the left and right halves of one image, two images sharing rows) alternate there:
+    // the search goes on past requests that belong to another chain, up to the address the chain would continue at.
+    std::vector<char> taken(batch.size(), 0);
+    std::vector<Pending*> chain;
+    for (size_t i = 0; i < batch.size(); i++) {
+        if (taken[i]) continue;
+        chain.assign(1, batch[i]);
         rgba_surface merged = batch[i]->src;
-        while (k < batch.size() && continues(*batch[k - 1], *batch[k]) && (int64_t)merged.height + batch[k]->src.height < (1 << 30)) {
+        for (size_t k = i + 1; k < batch.size() && merged.stride > 0; k++) {
+            const Pending& last = *chain.back();
+            if (batch[k]->src.ptr > last.src.ptr + (int64_t)last.src.height * last.src.stride) break;
+            if (taken[k] || !continues(last, *batch[k]) || (int64_t)merged.height + batch[k]->src.height >= (1 << 30)) continue;
+            taken[k] = 1;
+            chain.push_back(batch[k]);
             merged.height += batch[k]->src.height;
-            k++;
         }
         Job j = batch[i]->job;
         j.s7 = &batch[i]->s7; j.s6 = &batch[i]->s6;
         if (combiner_debug()) g_cstats.calls++;
         try { compress(j, &merged, batch[i]->dst, false); }
         catch (const itw::Failure& f) {
-            for (size_t t = i; t < k; t++) { batch[t]->failed = true; std::snprintf(batch[t]->msg, sizeof batch[t]->msg, "%s", f.msg); }
+            for (Pending* p : chain) { p->failed = true; std::snprintf(p->msg, sizeof p->msg, "%s", f.msg); }
         }
-        i = k;
     }
 }
 
@@ -1133,6 +1150,22 @@ bool coalesce_small_call(const Job& j, const rgba_surface* src, uint8_t* dst, in
     while (!me.done) {
         if (c.leader) { c.cv.wait(lk); continue; }
         c.leader = true;                                  // lead one batch (it contains this thread's request), then hand on
+#ifdef ITW_TEST_HOOKS
+        const bool held = c.hold_requests > 0;            // an armed hold takes the burst wait's place: the batch is what the test asked for
+        if (held) {
+            const int want = c.hold_requests;
+            const auto deadline = std::chrono::steady_clock::now() + std::chrono::milliseconds(c.hold_timeout_ms);
+            c.hold_requests = 0;                          // one-shot
+            while ((int)c.queue.size() < want) {
+                if (std::chrono::steady_clock::now() >= deadline) { g_hold_timeouts++; break; }
+                lk.unlock();
+                const auto until = std::chrono::steady_clock::now() + std::chrono::microseconds(8);
+                while (std::chrono::steady_clock::now() < until) std::this_thread::yield();
+                lk.lock();
+            }
+        }
+        if (!held)
+#endif
         if (c.burst == 0 && c.expected > 1) {
             // start of a burst from a pool of threads released by one event: they arrive over some tens of microseconds.
             // Wait for as many requests as the previous burst had, as long as the queue keeps growing, so that the whole
@@ -1525,6 +1558,24 @@ void itwTestF2I(const float* in, int32_t* out, int64_t n)
     if (n <= 0) return;
     hipLaunchKernelGGL(k_test_f2i, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, tls.user_stream, in, out, n);
     itw::guarded([&] { ITW_CHECK(hipGetLastError()); });
+}
+
+void itwTestCombinerHold(int requests, int timeout_ms)
+{
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return; }
+    if (dev < 0 || dev >= kMaxDevices) return;
+    Combiner& c = g_combiner[dev];
+    std::lock_guard<std::mutex> lk(c.m);
+    c.hold_requests = requests > 0 ? requests : 0;
+    c.hold_timeout_ms = timeout_ms > 0 ? timeout_ms : 0;
+}
+
+void itwTestCombinerCounters(int64_t out[5])
+{
+    if (!out) return;
+    out[0] = g_cstats.bursts.load(); out[1] = g_cstats.batches.load(); out[2] = g_cstats.requests.load(); out[3] = g_cstats.calls.load();
+    out[4] = g_hold_timeouts.load();
 }
 #endif // ITW_TEST_HOOKS
 

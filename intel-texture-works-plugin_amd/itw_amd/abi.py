@@ -36,7 +36,7 @@ EXPORTED_SYMBOLS = tuple(
     + ["itwDdsLevelBytes", "itwDdsHeaderBytes", "itwDdsFileBytes", "itwDdsWriteHeader", "itwDdsReadHeader", "itwDdsWriteFile"])
 # include/itw_test_hooks.h: exported by libispc_texcomp_test.so only (the same sources built with -DITW_TEST_HOOKS), never by the product
 TEST_HOOK_SYMBOLS = ("itwTestRcp", "itwTestRsqrt", "itwTestF2I", "itwTestBc7TwoSubsetBounds", "itwTestBc45IndexTable", "itwTestBc45ClosestS",
-                     "itwMultiGpuTestInjectFailure")
+                     "itwMultiGpuTestInjectFailure", "itwTestCombinerHold", "itwTestCombinerCounters")
 
 
 
@@ -250,6 +250,10 @@ def _load(path, hooks):
             L.itwTestBc45ClosestS.restype = C.c_int
             L.itwMultiGpuTestInjectFailure.argtypes = [C.c_int, C.c_int, C.c_int]
             L.itwMultiGpuTestInjectFailure.restype = None
+            L.itwTestCombinerHold.argtypes = [C.c_int, C.c_int]
+            L.itwTestCombinerHold.restype = None
+            L.itwTestCombinerCounters.argtypes = [C.POINTER(C.c_int64)]
+            L.itwTestCombinerCounters.restype = None
         # dispatch layer (itw_dispatch.h)
         L.GetProcessorCount.restype = C.c_int
         L.GetBytesPerBlock.argtypes = [C.c_int]
