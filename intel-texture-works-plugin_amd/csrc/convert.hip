@@ -6,7 +6,10 @@
 //   32 -> 8 : FloatToByte(v) in double; with gamma FloatToByte(pow(v, 1/2.2)) -- evaluated as "how many of the 255 code thresholds are <= v"
 //             (gamma_thresholds.h: the thresholds of the reference's own function compiled in the build container), eight comparisons, no
 //             pow: bit-exact with that function, where a device-library pow was +-1 code
-//   8 -> 16F: half(v / 255.f)    16 -> 16F: half((float)(v / 32768.0))    32 -> 16F: half(v)   (round to nearest even)
+//   8 -> 16F: half(v / 255.f)    16 -> 16F: half((float)(v / 32768.0))    32 -> 16F: half(v)
+//             half() is IEEE 754 round to nearest even over every float (the hardware conversion; half denormals, 0x7BFF below 65520, inf from
+//             there on).  The legacy DirectXMath software path differs per sign at 6 144 floats of 0x33000001 .. 0x387fffff and 4 095 of
+//             0x477fe001 .. 0x477fefff; no 8- or 16-bit source reaches either range (oracle/prepass.c)
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 #include <cstdio>

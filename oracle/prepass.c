@@ -3,10 +3,13 @@
  * run immediately before the ABI (IntelPlugin.cpp:741-810 ConvertToBCFrom8/16/32Bit, :291-366 ConvertToBC6From8/16/32Bit;
  * scalar helpers IntelPlugin.h:31-96).  Checker for csrc/convert.hip; never linked by the product.
  *
- * F32toF16 is DirectXMath's XMConvertFloatToHalf (not vendored in the reference tree): round to nearest even incl.
- * denormals for everything a half can hold -- restated below.  What it returns above 65504 differs between DirectXMath
- * releases (0x7FFF in the 2012-2015 ones, +-inf later); this restatement saturates to +-inf like the hardware conversion
- * and the fixtures' generator, and the parity tests stay inside the finite range ("parity unpinned" beyond it).
+ * F32toF16 is DirectXMath's XMConvertFloatToHalf (not vendored in the reference tree).  The pin here is IEEE 754 round to nearest
+ * even over every float -- what the hardware conversion of csrc/convert.hip, numpy's astype(float16) and the fixtures' generator do --
+ * restated below as integer code: 0 for |v| <= 2^-25, half denormals rounded with the shifted-out bits kept as a sticky bit, 0x7BFF
+ * for |v| < 65520, +-inf from 65520 on, a NaN pattern (payload unpinned) for NaN.  This departs from the legacy (2012-2015) DirectXMath
+ * software path, which drops the sticky bits and sends everything above 65504 to inf (0x7FFF in the oldest releases): per sign at
+ * 6 144 floats of the half-denormal range 0x33000001 .. 0x387fffff and at 4 095 floats of (65504, 65520) = 0x477fe001 .. 0x477fefff,
+ * and nowhere else among finite inputs; the 8- and 16-bit sources reach neither range.
  * The 32-bit -> 8-bit path applies pow(v, 1/2.2) in double precision with the C library's pow -- the same call the reference's own
  * ConvertTo8Bit makes where it is compiled here (tests/test_reference_pins.py).  The kernel does not call pow: it counts the code thresholds
  * of that function (csrc/gamma_thresholds.h, tools/gen_gamma_thresholds.py) and is compared bit for bit.  (On another platform's C library the
@@ -22,12 +25,15 @@ static uint16_t f32_to_f16(float value)
     const uint32_t sign = (x & 0x80000000u) >> 16;
     x &= 0x7fffffffu;
     uint32_t r;
-    if (x > 0x477fe000u) {                                   /* too large for a half (or inf / NaN) */
-        r = ((x & 0x7f800000u) == 0x7f800000u && (x & 0x7fffffu)) ? 0x7fffu : 0x7c00u;
+    if (x > 0x7f800000u) {                                   /* NaN */
+        r = 0x7fffu;
+    } else if (x >= 0x477ff000u) {                           /* |v| >= 65520 (halfway between 65504 and 2^16) or inf */
+        r = 0x7c00u;
     } else {
-        if (x < 0x38800000u) {                               /* becomes a half denormal */
+        if (x < 0x38800000u) {                               /* becomes a half denormal (or 0): bit 13 of x = 2^-24 */
             const uint32_t shift = 113u - (x >> 23);
-            x = shift < 32u ? (0x800000u | (x & 0x7fffffu)) >> shift : 0u;
+            const uint32_t m = 0x800000u | (x & 0x7fffffu);
+            x = shift < 24u ? (m >> shift) | ((m & ((1u << shift) - 1u)) != 0u) : (x != 0u);     /* shifted-out bits stay as sticky */
         } else {
             x += 0xc8000000u;                                /* rebias the exponent */
         }

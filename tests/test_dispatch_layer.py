@@ -252,6 +252,42 @@ def test_device_pad_kernel(itw, gpu):
         assert np.array_equal(d_out.cpu().numpy(), np.pad(img, ((0, H - h), (0, W - w), (0, 0)), mode="edge"))
 
 
+PAD_SIZES = [(1, 1), (1, 5), (5, 1), (4, 4), (3, 257), (6, 1021), (2, 256), (9, 253)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("pixel_size", [4, 8])
+@pytest.mark.parametrize("h,w", PAD_SIZES, ids=[f"{h}x{w}" for h, w in PAD_SIZES])
+def test_device_pad_kernel_across_its_block_boundary_from_a_strided_view(itw, gpu, h, w, pixel_size):
+    """pad_kernel runs 256 lanes of one output row per block: (4, 4) and (2, 256) are pure copies where they need no pad, 253 pads into one
+    block's last lanes, 256 fills one block exactly, 257 and 1021 reach blockIdx.x >= 1 with a partial last block (1021: the replicated
+    texels come from another block's column).  The source is a view inside a larger surface -- it starts behind a row and two texels, and its
+    rows lie further apart than they are long.  Equal to np.pad(mode="edge") and to the host itwPadToMultipleOf4; the output lies between
+    guard bands (tests/_guarded.py)."""
+    import torch
+    from _guarded import guarded
+    dtype = np.uint8 if pixel_size == 4 else np.uint16
+    rng = np.random.default_rng(h * 4096 + w + pixel_size)
+    big = rng.integers(0, np.iinfo(dtype).max + 1, size=(h + 2, w + 3, 4)).astype(dtype)
+    view = big[1:1 + h, 2:2 + w]
+    H, W = (h + 3) & ~3, (w + 3) & ~3
+    want = np.pad(view, ((0, H - h), (0, W - w), (0, 0)), mode="edge")
+    assert np.array_equal(itw.pad_to_multiple_of_4(view), want)
+    d_big = torch.from_numpy(big.view(np.int16) if pixel_size == 8 else big).to(gpu)
+    d_view = d_big[1:1 + h, 2:2 + w]
+    stride = d_big.stride(0) * d_big.element_size()
+    assert d_view.data_ptr() == d_big.data_ptr() + stride + 2 * pixel_size and stride == (w + 3) * pixel_size > w * pixel_size
+    out = guarded(H * W * pixel_size, device=gpu)
+    itw.lib().itwSetStream(torch.cuda.current_stream().cuda_stream)
+    surf = itw.RgbaSurface(d_view.data_ptr(), w, h, stride)
+    itw.lib().itwPadToMultipleOf4Device(C.byref(surf), pixel_size, out.ptr)
+    torch.cuda.synchronize()
+    got = out.host().view(dtype).reshape(H, W, 4)
+    assert np.array_equal(got, want), np.argwhere(got != want)[:4].tolist()
+    out.check(f"pad {h}x{w} px{pixel_size}")
+    assert np.array_equal(d_big.cpu().numpy().view(dtype), big)                     # the source is const
+
+
 @pytest.mark.gpu
 def test_pad_then_encode_device_resident(itw, gpu, oracle):
     """The pre-pass feeding the ABI without leaving HBM: a 127 x 339 surface (landscape-detail.jpg's size)."""

@@ -207,8 +207,12 @@ def test_prepass_oracle_equals_the_reference_scalar_conversions(oracle):
     oracle/_ref/libintelplugin_convert_ref.so is IntelPlugin.h:31-96 compiled from where it lies (F32toF16 / FloatToByte /
     ConvertTo8Bit x 3 / ConvertTo16Bit x 3; typedef shim for the Photoshop SDK's scalar types, DirectXMath half conversions
     from dxmath_stub/).  Exhaustive over the 8- and 16-bit sources, a dense sample incl. every special class for the 32-bit
-    ones -- byte for byte, the gamma path too (same libm on the same host)."""
-    L = C.CDLL(_ensure_ref("libintelplugin_convert_ref.so"))
+    ones -- byte for byte, the gamma path too (same libm on the same host).  float -> half: both restatements are project-written and
+    are held to IEEE round to nearest even at every rounding decision point, not only to each other."""
+    path = _ensure_ref("libintelplugin_convert_ref.so")
+    if os.path.exists(REFERENCE_TREE):          # nothing to do when up to date: the recipe keys dxmath_stub/ by content, a library from an
+        subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "oracle", "ref_build"), os.path.join("..", "_ref", "libintelplugin_convert_ref.so")], check=True)   # earlier stub is rebuilt
+    L = C.CDLL(path)
     L.ref_convert8_from8.argtypes = [C.c_uint8]; L.ref_convert8_from8.restype = C.c_uint8
     L.ref_convert8_from16.argtypes = [C.c_uint16]; L.ref_convert8_from16.restype = C.c_uint8
     L.ref_convert8_from32.argtypes = [C.c_float, C.c_int]; L.ref_convert8_from32.restype = C.c_uint8
@@ -241,8 +245,25 @@ def test_prepass_oracle_equals_the_reference_scalar_conversions(oracle):
     for gamma in (0, 1):
         src = f[f >= 0] if gamma else f                                 # pow of a negative base is NaN: its byte cast is unspecified
         assert np.array_equal(via_oracle8(src, 32, gamma), np.array([L.ref_convert8_from32(float(v), gamma) for v in src], np.uint8)), gamma
-    fin = f[np.abs(f) <= 65504.0]                                       # beyond: DirectXMath releases disagree (oracle/prepass.c header)
-    assert np.array_equal(via_oracle16(fin, 32), np.array([L.ref_convert16_from32(float(v)) for v in fin], np.uint16))
+    # float -> half: the pin is IEEE round to nearest even over every float (oracle/prepass.c header) and both
+    # restatements state it -- every non-NaN float of the sample, the values past 65504 and below 2^-24 the sample lacked, and every half
+    # and every midpoint between two halves +-3 floats in both signs (tests/_half_points.py)
+    import _half_points as HP
+    beyond = np.array([65504.0, 65505.0, 65519.996, 65520.0, 65536.0, 1e5, 3.4028235e38, np.inf, 2.0 ** -24, 2.0 ** -25, 2.9802326e-8, 1e-40, 1e-45], np.float32)
+    fin = np.concatenate([f, beyond, -beyond, HP.both_signs(HP.structured()).view(np.float32)])
+    assert not np.isnan(fin).any() and np.isinf(fin).sum() == 2 and fin.size > 2 * HP.STRUCTURED_PER_SIGN
+    assert L.ref_convert16_from32(float(np.array([0x33000001], np.uint32).view(np.float32)[0])) == 0x0001, \
+        "oracle/_ref/libintelplugin_convert_ref.so was built from an earlier dxmath_stub/ (sticky bits dropped): make -C oracle/ref_build"
+    ref16 = np.array([L.ref_convert16_from32(v) for v in fin.tolist()], np.uint16)
+    assert np.array_equal(via_oracle16(fin, 32), ref16)
+    assert np.array_equal(ref16, HP.ieee_half_bits(fin.view(np.uint32)))
+    # the two floats next to the rounding decisions that the earlier restatements got wrong (0x0000 and inf)
+    for bits, want in ((0x33000001, 0x0001), (0x477fe001, 0x7BFF), (0xb3000001, 0x8001), (0xc77fe001, 0xFBFF)):
+        v = np.array([bits], np.uint32).view(np.float32)
+        assert L.ref_convert16_from32(float(v[0])) == want and int(via_oracle16(v, 32)[0]) == want, hex(bits)
+    nan = np.array([0x7fc00000, 0x7f800001, 0xffc00000, 0xff801000], np.uint32).view(np.float32)      # NaN stays NaN; the payload is unpinned
+    for got in (via_oracle16(nan, 32), np.array([L.ref_convert16_from32(v) for v in nan.tolist()], np.uint16)):
+        assert ((got & 0x7c00) == 0x7c00).all() and ((got & 0x03ff) != 0).all()
 
 
 def test_committed_gamma_thresholds_are_what_the_reference_function_gives_now():

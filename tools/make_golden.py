@@ -32,8 +32,10 @@ def load_png_rgba(name):
 
 
 def float_to_half_bits(rgb):
-    """float32 -> half, round-to-nearest-even, like XMConvertFloatToHalf (the plugin's conversion,
-    IntelPlugin.cpp:343-366); alpha = 1.0."""
+    """float32 -> half for the plugin's conversion (XMConvertFloatToHalf, IntelPlugin.cpp:343-366); alpha = 1.0.  IEEE 754 round to
+    nearest even over every float, the project's pin (oracle/prepass.c).  The legacy DirectXMath software path
+    departs from it, per sign, at 6 144 floats of the half-denormal range 0x33000001 .. 0x387fffff and at 4 095 floats of
+    (65504, 65520) = 0x477fe001 .. 0x477fefff."""
     h = rgb.astype(np.float16).view(np.uint16)
     out = np.empty(rgb.shape[:2] + (4,), dtype=np.uint16)
     out[..., :3] = h
