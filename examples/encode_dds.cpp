@@ -9,6 +9,11 @@
 //     --refine  : bc7_* / bc6h_* only: encode to an error budget (itwCompressImageRefined) -- <format>'s preset everywhere, then <profile>
 //                 (a preset of the same format: `slow`, `alpha_slow`, ...) on the blocks whose error is above <max_block_sse>, kept where
 //                 it is strictly better; one line on stdout with the call's statistics.  The slice loop is not used.
+//
+//   encode_dds --decode <in.dds> <out.raw>
+//     the load path (IntelPlugin.cpp:2461-2561): header -> every image of the file through ONE itwDecodeChain -> texels.  out.raw holds
+//     every image's texels one after another in file order, tightly packed (RGBA8; RGBA16F bit patterns for BC6H; int8 codes for the
+//     SNORM pair); one line on stdout per image: index, width, height, min alpha (the smallest decoded alpha code: IsAlphaAllOpaque).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -70,10 +75,52 @@ bool on_progress(int done, int total, void*)
     return true;                                                   // false would abort like the plugin's cancel button
 }
 
+// encode_dds --decode: the whole file through one call
+int decode_file(const char* in_path, const char* out_path)
+{
+    FILE* in = std::fopen(in_path, "rb");
+    if (!in) { std::fprintf(stderr, "cannot read %s\n", in_path); return 1; }
+    std::vector<uint8_t> file;
+    uint8_t buf[65536];
+    for (size_t n; (n = std::fread(buf, 1, sizeof buf, in)) > 0;) file.insert(file.end(), buf, buf + n);
+    std::fclose(in);
+    ItwDdsDesc desc;
+    const size_t first = itwDdsReadHeader(file.data(), file.size(), &desc);
+    if (!first) { std::fprintf(stderr, "%s: not a BCn DDS file this library reads\n", in_path); return 1; }
+    const int texel_bytes = desc.dxgi_format == ITW_DXGI_FORMAT_BC6H_UF16 ? 8 : 4;
+    std::vector<rgba_surface> outs;
+    size_t texels_bytes = 0, end = first;
+    for (uint32_t i = 0;; i++) {                                   // the payload, image by image
+        uint32_t w = 0, h = 0; size_t off = 0;
+        const size_t n = itwDdsImage(&desc, i, &w, &h, &off);
+        if (!n) break;
+        outs.push_back(rgba_surface{nullptr, (int32_t)w, (int32_t)h, (int32_t)w * texel_bytes});
+        texels_bytes += (size_t)w * h * texel_bytes;
+        end = off + n;
+    }
+    if (outs.empty() || file.size() < end) { std::fprintf(stderr, "%s: truncated: %zu bytes, the header describes %zu\n", in_path, file.size(), end); return 1; }
+    std::vector<uint8_t> texels(texels_bytes);
+    size_t at = 0;
+    for (rgba_surface& s : outs) { s.ptr = texels.data() + at; at += (size_t)s.stride * s.height; }
+    std::vector<uint32_t> min_alpha(outs.size());
+    itwSetErrorMode(ITW_ON_ERROR_RETURN);
+    if (itwDecodeChain((int)desc.dxgi_format, file.data() + first, outs.data(), (int)outs.size(), nullptr, min_alpha.data()) != 0) {
+        std::fprintf(stderr, "%s\n", itwLastError() ? itwLastError() : "itwDecodeChain refused the file (BC6H_SF16 is not decoded)");
+        return 1;
+    }
+    for (size_t i = 0; i < outs.size(); i++) std::printf("image %zu: %d %d min_alpha %u\n", i, outs[i].width, outs[i].height, min_alpha[i]);
+    FILE* out = std::fopen(out_path, "wb");
+    if (!out || std::fwrite(texels.data(), 1, texels.size(), out) != texels.size()) { std::fprintf(stderr, "cannot write %s\n", out_path); return 1; }
+    std::fclose(out);
+    std::fprintf(stderr, "%s: %zu images -> %zu bytes\n", out_path, outs.size(), texels.size());
+    return 0;
+}
+
 } // namespace
 
 int main(int argc, char** argv)
 {
+    if (argc == 4 && std::strcmp(argv[1], "--decode") == 0) return decode_file(argv[2], argv[3]);
     bool measure = false;
     const char* refine_profile = nullptr;
     unsigned long long max_block_sse = 0;
@@ -89,7 +136,8 @@ int main(int argc, char** argv)
             argc -= 3; i--;
         }
     if (argc < 6) {
-        std::fprintf(stderr, "usage: %s [--measure] [--refine <profile> <max_block_sse>] <format> <width> <height> <in.raw> <out.dds> [slice_pixels]\n", argv[0]);
+        std::fprintf(stderr, "usage: %s [--measure] [--refine <profile> <max_block_sse>] <format> <width> <height> <in.raw> <out.dds> [slice_pixels]\n"
+                             "       %s --decode <in.dds> <out.raw>\n", argv[0], argv[0]);
         return 2;
     }
     const Format* f = nullptr;

@@ -38,6 +38,11 @@ size_t itwDdsReadHeader(const uint8_t* src, size_t size, ItwDdsDesc* desc);
 /* Whole file: `levels[i]` points at the blocks of image i in file order (array item major, then face, then mip).
  * Returns bytes written (== itwDdsFileBytes) or 0. */
 size_t itwDdsWriteFile(const ItwDdsDesc* desc, const uint8_t* const* levels, size_t nlevels, uint8_t* dst, size_t capacity);
+/* Image `index` in file order (array item, face, mip): its size in texels and the offset of its blocks from the start of the file.
+ * Returns the image's byte size, 0 when index is out of range or desc is not a format this library reads.  width, height and offset may
+ * each be NULL.  The images follow each other without gaps, so image 0's offset to the end of the last image is the packed stream
+ * itwDecodeChain (itw_decode.h) takes; host arithmetic only. */
+size_t itwDdsImage(const ItwDdsDesc* desc, uint32_t index, uint32_t* width, uint32_t* height, size_t* offset);
 
 #pragma GCC visibility pop
 #ifdef __cplusplus

@@ -35,6 +35,35 @@ extern "C" {
  * Returns 0, or -1 for an unsupported format / misaligned sizes. */
 int itwDecodeBlocks(int dxgi_format, const uint8_t* blocks, int width, int height, uint8_t* out, int64_t out_stride, int32_t* modes);
 
+/* (itwDecodeBlocks reads BC6H_SF16, 96, as unsigned: the signed decode is not built.  The chain entry points below refuse 96.)
+ *
+ * ---- a whole mip chain / cube map / array, any size, in one call -------------------------------------------------------------------
+ * The mirror image of itwCompressImageChain (itw_dispatch.h), and the load path's Decompress over every image of a file
+ * (IntelPlugin.cpp:2461-2561).  `blocks`: the packed stream of `count` images as itwCompressImageChain lays it out (image i starts at the
+ * summed sizes of the images before it, itwChainBytes; ceil(w/4)*ceil(h/4) blocks per image -- a DDS payload, itw_dds.h: itwDdsImage).
+ * outs[i]: where image i's texels go -- ptr, width, height (any >= 1), stride (bytes, a multiple of 4, at least the row); RGBA8, int8
+ * RGBA8_SNORM for BC4S / BC5S, RGBA16F bit patterns for BC6H_UF16.  ptr is 4-byte aligned (8 for RGBA16F).  Texels outside
+ * width x height are never written: edge blocks are cropped on store, for every format.
+ * dxgi_format: 71, 72, 77, 78, 80, 81, 83, 84, 95, 98, 99.  BC6H_SF16 (96) is refused.
+ * modes (optional, may be NULL): one int32 per block of the concatenated block list, numbered as itwDecodeBlocks numbers them.
+ * min_alpha (optional, may be NULL): one uint32 per image, the smallest decoded alpha code among the texels actually stored -- the load
+ * path's IsAlphaAllOpaque question (255 = opaque) without a second pass.  For the formats that fill alpha it is that constant: BC4 / BC5
+ * 255, BC4S / BC5S 127, BC6H 0x3C00.
+ * One launch decodes every image.  The outs[i].ptr are all host or all device pointers; `blocks`, `modes`, `min_alpha` may each be either
+ * (a device `blocks` pointer is at least 4-byte aligned).  With everything on the device the call is asynchronous on the calling thread's
+ * stream (itwSetStream) and allocates nothing from a thread's second call on (the descriptor table is copied into a buffer the thread
+ * keeps, so capturing the call into a graph is not supported).  With any host pointer it stages through the thread's grow-only buffer --
+ * one upload of the stream, one launch, one strided download per image -- and returns synchronised.
+ * Output surfaces may be views into one larger allocation.  Six cube faces of size s decoded straight into a 4s x 3s canvas at the cells
+ * {2,1},{0,1},{1,0},{1,2},{1,1},{3,1} (column, row; the reference's crossedCoords, IntelPlugin.cpp:1435) ARE its
+ * ConvertToHorizontalCrossFromCubeMap (:1421-1500), with no copy; mips to layers is the same with other offsets.
+ * Returns 0 (also for count == 0); -1 before any device work for an unknown or refused format, count < 0, a null blocks / outs / ptr,
+ * a width or height < 1, a stride below the row's bytes or not a multiple of 4, mixed host and device outputs, or more than
+ * ITW_MEASURE_MAX_BLOCKS blocks in one image; -1 after a device failure (reported through the library's error mode, itw_amd.h). */
+int itwDecodeChain(int dxgi_format, const uint8_t* blocks, const rgba_surface* outs, int count, int32_t* modes, uint32_t* min_alpha);
+/* a chain of one */
+int itwDecodeImage(int dxgi_format, const uint8_t* blocks, const rgba_surface* out, int32_t* modes, uint32_t* min_alpha);
+
 /* ---- measuring an encoded stream against its source ------------------------------------------------------------------------------
  * What a caller would compute by decoding the stream (the decoders above, at the padded size) and comparing the texels of `source`
  * with the decoded ones, code by code, as integers -- done in one kernel that decodes into registers, so the decoded surface never

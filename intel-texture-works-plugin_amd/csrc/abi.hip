@@ -114,6 +114,9 @@ struct ThreadCtx {
     bool staged_wide = false;                       // what the last staged BC7 call's estimate said (the shape of this call's first run, until its own is in)
     void*  d_refine[2] = {nullptr, nullptr}; size_t refine_cap[2] = {0, 0};   // itwCompressImageRefined (refine.hip): per-surface scratch, per-list scratch
     uint32_t* refine_count = nullptr;               // ... and the pinned word its list count is read back through
+    void*  d_decode = nullptr; size_t decode_cap = 0;   // itwDecodeChain (decode_chain.hip): descriptor table and, for host pointers, staging
+    hipStream_t decode_stream = nullptr; bool decode_used = false;
+    hipEvent_t  decode_event = nullptr;             // recorded after each chain decode: orders the table across streams, as ws_event does
     int    device = -1;
     char   info[256] = {0};
     ~ThreadCtx() {
@@ -123,6 +126,8 @@ struct ThreadCtx {
         if (d_ws)  (void)hipFree(d_ws);
         for (void* p : d_refine) if (p) (void)hipFree(p);
         if (refine_count) (void)hipHostFree(refine_count);
+        if (d_decode) (void)hipFree(d_decode);
+        if (decode_event) (void)hipEventDestroy(decode_event);
         if (own_stream) (void)hipStreamDestroy(own_stream);
         if (copy_stream) (void)hipStreamDestroy(copy_stream);
         for (auto e : ev_in) if (e) (void)hipEventDestroy(e);
@@ -155,6 +160,8 @@ void bind_thread_to_current_device()
     if (tls.d_ws)  { (void)hipFree(tls.d_ws);  tls.d_ws = nullptr;  tls.ws_cap = 0; tls.ws_used = false; }
     for (int k = 0; k < 2; k++) if (tls.d_refine[k]) { (void)hipFree(tls.d_refine[k]); tls.d_refine[k] = nullptr; tls.refine_cap[k] = 0; }
     if (tls.refine_count) { (void)hipHostFree(tls.refine_count); tls.refine_count = nullptr; }
+    if (tls.d_decode) { (void)hipFree(tls.d_decode); tls.d_decode = nullptr; tls.decode_cap = 0; tls.decode_used = false; }
+    if (tls.decode_event) { (void)hipEventDestroy(tls.decode_event); tls.decode_event = nullptr; }
     if (tls.own_stream) { (void)hipStreamDestroy(tls.own_stream); tls.own_stream = nullptr; }
     if (tls.copy_stream) { (void)hipStreamDestroy(tls.copy_stream); tls.copy_stream = nullptr; }
     for (auto& e : tls.ev_in) if (e) { (void)hipEventDestroy(e); e = nullptr; }
@@ -1324,6 +1331,18 @@ uint32_t* refine_count_word()
     }
     return tls.refine_count;
 }
+
+void* decode_scratch(size_t bytes, hipStream_t st)
+{
+    bind_thread_to_current_device();
+    if (!tls.decode_event) ITW_CHECK(hipEventCreateWithFlags(&tls.decode_event, hipEventDisableTiming));
+    if (tls.decode_used && tls.decode_stream != st) ITW_CHECK(hipStreamWaitEvent(st, tls.decode_event, 0));
+    void* p = grow(tls.d_decode, tls.decode_cap, bytes);
+    tls.decode_stream = st; tls.decode_used = true;
+    return p;
+}
+
+void decode_scratch_done(hipStream_t st) { ITW_CHECK(hipEventRecord(tls.decode_event, st)); }
 
 int sliced_windows(int dxgi_format, const void* settings, int width, int height, int64_t slice_pixels, int* window_slices)
 {

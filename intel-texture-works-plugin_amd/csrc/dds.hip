@@ -149,6 +149,25 @@ size_t itwDdsReadHeader(const uint8_t* src, size_t size, ItwDdsDesc* out)
     return off;
 }
 
+size_t itwDdsImage(const ItwDdsDesc* d, uint32_t index, uint32_t* width, uint32_t* height, size_t* offset)
+{
+    const size_t hdr = itwDdsHeaderBytes(d);
+    if (!hdr) return 0;
+    const uint64_t items = (uint64_t)(d->array_size ? d->array_size : 1) * (d->is_cubemap ? 6 : 1);
+    if ((uint64_t)index >= items * d->mip_levels) return 0;
+    const uint32_t item = index / d->mip_levels, mip = index - item * d->mip_levels;
+    size_t chain = 0, before = 0, bytes = 0;
+    uint32_t w = d->width, h = d->height;
+    for (uint32_t m = 0; m < d->mip_levels; m++) {
+        const size_t n = itwDdsLevelBytes(d->dxgi_format, w, h);
+        if (m == mip) { before = chain; bytes = n; if (width) *width = w; if (height) *height = h; }
+        chain += n;
+        w = w > 1 ? w / 2 : 1; h = h > 1 ? h / 2 : 1;
+    }
+    if (offset) *offset = hdr + (size_t)item * chain + before;
+    return bytes;
+}
+
 size_t itwDdsWriteFile(const ItwDdsDesc* d, const uint8_t* const* levels, size_t nlevels, uint8_t* dst, size_t capacity)
 {
     const size_t total = itwDdsFileBytes(d);

@@ -65,6 +65,12 @@ void encode_resident(int dxgi_format, const void* settings, const uint8_t* d_src
 void* refine_scratch(int which, size_t bytes);
 uint32_t* refine_count_word();
 
+// What itwDecodeChain (decode_chain.hip) needs: the thread's grow-only device buffer for the descriptor table and the staging of host
+// pointers, at least `bytes` bytes, 256-B aligned.  A call on another stream than the last one first waits for the event that
+// decode_scratch_done(st) recorded behind that call's work (the BC7 workspace's rule); growing frees the old buffer, which waits for the device.
+void* decode_scratch(size_t bytes, hipStream_t st);
+void decode_scratch_done(hipStream_t st);
+
 // One predicate for "the kernels can dereference this pointer": device AND managed allocations (abi.hip and
 // dispatch.hip/decode.hip used to disagree on managed memory).  Unregistered host memory -> false.
 bool is_device_pointer(const void* p) noexcept;

@@ -31,9 +31,9 @@ EXPORTED_SYMBOLS = tuple(
     # include/itw_bc45.h: the DirectXTex formats of the plugin
     + ["CompressBlocksBC4", "CompressBlocksBC5", "itwWarmupBC45", "CompressBlocksBC4S", "CompressBlocksBC5S", "itwWarmupBC45S"]
     # include/itw_decode.h: device decoders
-    + ["itwDecodeBlocks", "itwMeasureBlocks", "itwMeasureChain", "itwStatsPsnr"]
+    + ["itwDecodeBlocks", "itwDecodeChain", "itwDecodeImage", "itwMeasureBlocks", "itwMeasureChain", "itwStatsPsnr"]
     # include/itw_dds.h: DDS container
-    + ["itwDdsLevelBytes", "itwDdsHeaderBytes", "itwDdsFileBytes", "itwDdsWriteHeader", "itwDdsReadHeader", "itwDdsWriteFile"])
+    + ["itwDdsLevelBytes", "itwDdsHeaderBytes", "itwDdsFileBytes", "itwDdsWriteHeader", "itwDdsReadHeader", "itwDdsWriteFile", "itwDdsImage"])
 # include/itw_test_hooks.h: exported by libispc_texcomp_test.so only (the same sources built with -DITW_TEST_HOOKS), never by the product
 TEST_HOOK_SYMBOLS = ("itwTestRcp", "itwTestRsqrt", "itwTestF2I", "itwTestBc7TwoSubsetBounds", "itwTestBc45IndexTable", "itwTestBc45ClosestS",
                      "itwMultiGpuTestInjectFailure", "itwTestCombinerHold", "itwTestCombinerCounters")
@@ -312,6 +312,10 @@ def _load(path, hooks):
         L.itwConvertToRGBA16FDevice.restype = C.c_int
         L.itwDecodeBlocks.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]
         L.itwDecodeBlocks.restype = C.c_int
+        L.itwDecodeChain.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.itwDecodeChain.restype = C.c_int
+        L.itwDecodeImage.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.itwDecodeImage.restype = C.c_int
         L.itwMeasureBlocks.argtypes = [C.c_int, C.c_void_p, C.POINTER(RgbaSurface), C.c_void_p, C.c_size_t, C.c_void_p]
         L.itwMeasureBlocks.restype = C.c_int
         L.itwMeasureChain.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_size_t]
@@ -330,6 +334,8 @@ def _load(path, hooks):
         L.itwDdsReadHeader.restype = C.c_size_t
         L.itwDdsWriteFile.argtypes = [C.POINTER(DdsDesc), C.POINTER(C.c_void_p), C.c_size_t, C.c_void_p, C.c_size_t]
         L.itwDdsWriteFile.restype = C.c_size_t
+        L.itwDdsImage.argtypes = [C.POINTER(DdsDesc), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_size_t)]
+        L.itwDdsImage.restype = C.c_size_t
     return L
 
 
@@ -738,6 +744,148 @@ def decode(fmt, blocks, width, height, want_modes=False):
     if rc != 0:
         raise ValueError("itwDecodeBlocks: unsupported format or size")
     return (out, modes) if want_modes else out
+
+
+def _texel_dtype(fmt, torch_mod=None):
+    """Element type of a decoded (H, W, 4) array / tensor: uint16 (torch: int16) half bits for bc6h, int8 for the signed formats, else uint8."""
+    import numpy as np
+    base = _base(fmt)
+    if torch_mod is not None:
+        return torch_mod.int16 if base == "bc6h" else torch_mod.int8 if fmt in SIGNED_FORMATS else torch_mod.uint8
+    return np.uint16 if base == "bc6h" else np.int8 if fmt in SIGNED_FORMATS else np.uint8
+
+
+def decode_chain(fmt, blocks, sizes_or_outs, want_modes=False, want_min_alpha=False):
+    """itwDecodeChain: every image of the packed stream `blocks` (compress_chain's layout, a DDS payload) in one call, any size >= 1.
+    blocks: uint8 numpy array (host pointers) or CUDA uint8 tensor (device pointers, torch's current stream, asynchronous).
+    sizes_or_outs: a list of (h, w) to allocate, or a list of preallocated (H, W, 4) arrays / tensors of blocks' kind to fill; rows may
+    be strided views into a larger allocation.  fmt: a key of DXGI_FORMAT.  Returns the list of texel arrays -- uint8, uint16 (torch:
+    int16) half bits for bc6h, int8 for the signed formats -- followed by the modes (int32, one per block of the whole stream) and the
+    per-image minimum alpha codes (uint32 numpy array, or a CUDA int32 tensor holding the same bits) when asked for."""
+    import numpy as np
+    base = _base(fmt)
+    on_device = hasattr(blocks, "data_ptr")
+    if on_device:
+        import torch
+        assert blocks.is_cuda and blocks.dtype == torch.uint8 and blocks.is_contiguous()
+    else:
+        blocks = np.ascontiguousarray(blocks, dtype=np.uint8).reshape(-1)
+    outs = []
+    for s in sizes_or_outs:
+        if isinstance(s, tuple):
+            h, w = s
+            if on_device:
+                outs.append(torch.empty((h, w, 4), dtype=_texel_dtype(fmt, torch), device=blocks.device))
+            else:
+                outs.append(np.empty((h, w, 4), dtype=_texel_dtype(fmt)))
+        else:
+            assert hasattr(s, "data_ptr") == on_device, "outputs and blocks must be of one kind"
+            assert (s.element_size() if on_device else s.itemsize) == (2 if base == "bc6h" else 1), "texel type does not match the format"
+            outs.append(s)
+    n = len(outs)
+    total = sum(((o.shape[1] + 3) // 4) * ((o.shape[0] + 3) // 4) for o in outs)
+    assert (blocks.numel() if on_device else blocks.size) >= total * BYTES_PER_BLOCK[base]
+    arr = _surfaces(outs)
+    if on_device:
+        modes = torch.empty(total, dtype=torch.int32, device=blocks.device) if want_modes else None
+        amin = torch.empty(max(1, n), dtype=torch.int32, device=blocks.device) if want_min_alpha else None
+        with torch.cuda.device(blocks.device):
+            lib().itwSetStream(torch.cuda.current_stream(blocks.device).cuda_stream)
+            rc = lib().itwDecodeChain(DXGI_FORMAT[fmt], blocks.data_ptr(), C.cast(arr, C.c_void_p), n,
+                                      modes.data_ptr() if want_modes else None, amin.data_ptr() if want_min_alpha else None)
+        if want_min_alpha:
+            amin = amin[:n]
+    else:
+        modes = np.empty(total, dtype=np.int32) if want_modes else None
+        amin = np.empty(n, dtype=np.uint32) if want_min_alpha else None
+        rc = lib().itwDecodeChain(DXGI_FORMAT[fmt], blocks.ctypes.data, C.cast(arr, C.c_void_p), n,
+                                  modes.ctypes.data if want_modes else None, amin.ctypes.data if want_min_alpha else None)
+    if rc != 0:
+        raise ValueError("itwDecodeChain: " + (last_error() or "bad arguments"))
+    res = (outs,) + ((modes,) if want_modes else ()) + ((amin,) if want_min_alpha else ())
+    return res[0] if len(res) == 1 else res
+
+
+def decode_image(fmt, blocks, size_or_out, want_modes=False, want_min_alpha=False):
+    """itwDecodeImage: decode_chain for one image of any size; size_or_out is (h, w) or a preallocated array / tensor.  Returns the
+    texels, then modes and the image's minimum alpha code (an int for numpy, a one-element tensor on the device) when asked for."""
+    import numpy as np
+    base = _base(fmt)
+    on_device = hasattr(blocks, "data_ptr")
+    if isinstance(size_or_out, tuple):
+        h, w = size_or_out
+        if on_device:
+            import torch
+            out = torch.empty((h, w, 4), dtype=_texel_dtype(fmt, torch), device=blocks.device)
+        else:
+            out = np.empty((h, w, 4), dtype=_texel_dtype(fmt))
+    else:
+        out = size_or_out
+        assert hasattr(out, "data_ptr") == on_device, "output and blocks must be of one kind"
+    total = ((out.shape[1] + 3) // 4) * ((out.shape[0] + 3) // 4)
+    surf = _surfaces([out])
+    if on_device:
+        import torch
+        assert blocks.is_cuda and blocks.dtype == torch.uint8 and blocks.is_contiguous() and blocks.numel() >= total * BYTES_PER_BLOCK[base]
+        modes = torch.empty(total, dtype=torch.int32, device=blocks.device) if want_modes else None
+        amin = torch.empty(1, dtype=torch.int32, device=blocks.device) if want_min_alpha else None
+        with torch.cuda.device(blocks.device):
+            lib().itwSetStream(torch.cuda.current_stream(blocks.device).cuda_stream)
+            rc = lib().itwDecodeImage(DXGI_FORMAT[fmt], blocks.data_ptr(), C.cast(surf, C.c_void_p),
+                                      modes.data_ptr() if want_modes else None, amin.data_ptr() if want_min_alpha else None)
+    else:
+        blocks = np.ascontiguousarray(blocks, dtype=np.uint8).reshape(-1)
+        assert blocks.size >= total * BYTES_PER_BLOCK[base]
+        modes = np.empty(total, dtype=np.int32) if want_modes else None
+        word = np.empty(1, dtype=np.uint32) if want_min_alpha else None
+        rc = lib().itwDecodeImage(DXGI_FORMAT[fmt], blocks.ctypes.data, C.cast(surf, C.c_void_p),
+                                  modes.ctypes.data if want_modes else None, word.ctypes.data if want_min_alpha else None)
+        amin = int(word[0]) if want_min_alpha else None
+    if rc != 0:
+        raise ValueError("itwDecodeImage: " + (last_error() or "bad arguments"))
+    res = (out,) + ((modes,) if want_modes else ()) + ((amin,) if want_min_alpha else ())
+    return res[0] if len(res) == 1 else res
+
+
+def dds_images(desc):
+    """itwDdsImage over a DdsDesc: [(height, width, offset, bytes)] of every image in file order (array item, face, mip)."""
+    out = []
+    w, h, off = C.c_uint32(), C.c_uint32(), C.c_size_t()
+    i = 0
+    while True:
+        n = lib().itwDdsImage(C.byref(desc), i, C.byref(w), C.byref(h), C.byref(off))
+        if not n:
+            return out
+        out.append((int(h.value), int(w.value), int(off.value), int(n)))
+        i += 1
+
+
+def load_dds(data, device=None):
+    """The load path: a .dds file's bytes (bytes / uint8 numpy array) -> (DdsDesc, [texel arrays in file order], [min alpha per image]).
+    itwDdsReadHeader + itwDdsImage + one itwDecodeChain over the payload.  device None: numpy arrays through host pointers; a torch
+    device: the payload is uploaded and the texels are CUDA tensors.  Raises ValueError for a header this library does not read, a
+    BC6H_SF16 file (not decoded) and a file shorter than its header describes."""
+    import numpy as np
+    raw = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+    desc = DdsDesc()
+    first = lib().itwDdsReadHeader(raw.ctypes.data, raw.size, C.byref(desc))
+    if not first:
+        raise ValueError("not a BCn DDS file this library reads")
+    fmt = {v: k for k, v in DXGI_FORMAT.items()}[int(desc.dxgi_format)]
+    if fmt == "bc6h_sf16":
+        raise ValueError("BC6H_SF16 is not decoded")
+    images = dds_images(desc)
+    end = images[-1][2] + images[-1][3] if images else 0
+    if not images or images[0][2] != first or raw.size < end:
+        raise ValueError(f"truncated DDS file: {raw.size} bytes, the header describes {end}")
+    payload = raw[first:end]
+    sizes = [(h, w) for h, w, _, _ in images]
+    if device is None:
+        texels, amin = decode_chain(fmt, payload, sizes, want_min_alpha=True)
+        return desc, texels, [int(v) for v in amin]
+    import torch
+    texels, amin = decode_chain(fmt, torch.from_numpy(payload.copy()).to(device), sizes, want_min_alpha=True)
+    return desc, texels, [int(v) & 0xFFFFFFFF for v in amin.cpu().tolist()]
 
 
 def measure_async(fmt, blocks, img, stats_out, block_map=None):
