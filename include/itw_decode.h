@@ -27,24 +27,30 @@ extern "C" {
  * levels 0, 1 = s0, s1; if the RAW bytes have r0 > r1, level 1+i = round(((7-i)*s0 + i*s1) / 7), i = 1..6; else level 1+i =
  * round(((5-i)*s0 + i*s1) / 5), i = 1..4, and levels 6, 7 = -127, 127 (round to nearest; no ties with odd divisors).  Never -128.
  * dxgi_format: one of the ITW_DXGI_FORMAT_BC* values of itw_dispatch.h (71,72,77,78,80,81,83,84,95,96,98,99).
- * `blocks`, `out`, `modes` are host or device pointers (host pointers are staged, the call then returns synchronised;
- * all-device calls are asynchronous on the calling thread's stream, itwSetStream).
+ * `blocks`, `out`, `modes` are host or device pointers, in any mix.  With all of them on the device the call is one kernel launch,
+ * asynchronous on the calling thread's stream (itwSetStream): it allocates nothing, touches no buffer of the thread and can be captured
+ * into a graph.  With any host pointer it stages through the calling thread's grow-only device buffer (the one itwDecodeChain uses;
+ * no hipMalloc / hipFree per call) and returns synchronised.  A device `blocks` pointer is at least 4-byte aligned, `out` 4-byte (8 for
+ * RGBA16F); rows that are 16-byte aligned are stored as vectors.
  * `modes` (optional, may be NULL): one int32 per block -- BC7: mode 0..7, -1 for the reserved all-zero-prefix block;
  * BC6H: mode 0..13 in kernel.ispc's numbering, -1 for a reserved prefix; BC1/BC3: 0.
- * Width and height must be multiples of 4, except for BC4 / BC5 (UNORM and SNORM), whose streams may end in partial blocks (cropped on store).
- * Returns 0, or -1 for an unsupported format / misaligned sizes. */
+ * Width and height must be multiples of 4, except for BC4 / BC5 (UNORM and SNORM), whose streams may end in partial blocks (cropped on
+ * store; any size >= 1).  out_stride: a multiple of 4, at least the row's bytes, at most INT32_MAX.
+ * This is a chain of one image through the kernel of itwDecodeChain below, under its own, older argument rules: it reads BC6H_SF16 (96)
+ * as unsigned, and its size limit is not ITW_MEASURE_MAX_BLOCKS but what one launch covers, 2^31 - 1 blocks.
+ * Returns 0; -1 before any device work for an unsupported format, a size or stride outside the rules above or more blocks than one launch
+ * covers; -1 after a device failure, which is reported through the library's error mode (itw_amd.h: abort by default; in return mode the
+ * message is kept for itwLastError). */
 int itwDecodeBlocks(int dxgi_format, const uint8_t* blocks, int width, int height, uint8_t* out, int64_t out_stride, int32_t* modes);
 
-/* (itwDecodeBlocks reads BC6H_SF16, 96, as unsigned: the signed decode is not built.  The chain entry points below refuse 96.)
- *
- * ---- a whole mip chain / cube map / array, any size, in one call -------------------------------------------------------------------
+/* ---- a whole mip chain / cube map / array, any size, in one call -------------------------------------------------------------------
  * The mirror image of itwCompressImageChain (itw_dispatch.h), and the load path's Decompress over every image of a file
  * (IntelPlugin.cpp:2461-2561).  `blocks`: the packed stream of `count` images as itwCompressImageChain lays it out (image i starts at the
  * summed sizes of the images before it, itwChainBytes; ceil(w/4)*ceil(h/4) blocks per image -- a DDS payload, itw_dds.h: itwDdsImage).
  * outs[i]: where image i's texels go -- ptr, width, height (any >= 1), stride (bytes, a multiple of 4, at least the row); RGBA8, int8
  * RGBA8_SNORM for BC4S / BC5S, RGBA16F bit patterns for BC6H_UF16.  ptr is 4-byte aligned (8 for RGBA16F).  Texels outside
  * width x height are never written: edge blocks are cropped on store, for every format.
- * dxgi_format: 71, 72, 77, 78, 80, 81, 83, 84, 95, 98, 99.  BC6H_SF16 (96) is refused.
+ * dxgi_format: 71, 72, 77, 78, 80, 81, 83, 84, 95, 98, 99.  BC6H_SF16 (96) is refused: the signed decode is not built.
  * modes (optional, may be NULL): one int32 per block of the concatenated block list, numbered as itwDecodeBlocks numbers them.
  * min_alpha (optional, may be NULL): one uint32 per image, the smallest decoded alpha code among the texels actually stored -- the load
  * path's IsAlphaAllOpaque question (255 = opaque) without a second pass.  For the formats that fill alpha it is that constant: BC4 / BC5
@@ -52,7 +58,7 @@ int itwDecodeBlocks(int dxgi_format, const uint8_t* blocks, int width, int heigh
  * One launch decodes every image.  The outs[i].ptr are all host or all device pointers; `blocks`, `modes`, `min_alpha` may each be either
  * (a device `blocks` pointer is at least 4-byte aligned).  With everything on the device the call is asynchronous on the calling thread's
  * stream (itwSetStream) and allocates nothing from a thread's second call on (the descriptor table is copied into a buffer the thread
- * keeps, so capturing the call into a graph is not supported).  With any host pointer it stages through the thread's grow-only buffer --
+ * keeps, so capturing a call of more than one image into a graph is not supported; a chain of one has no table).  With any host pointer it stages through the thread's grow-only buffer --
  * one upload of the stream, one launch, one strided download per image -- and returns synchronised.
  * Output surfaces may be views into one larger allocation.  Six cube faces of size s decoded straight into a 4s x 3s canvas at the cells
  * {2,1},{0,1},{1,0},{1,2},{1,1},{3,1} (column, row; the reference's crossedCoords, IntelPlugin.cpp:1435) ARE its

@@ -1,11 +1,13 @@
 // decode_chain.hip -- every image of a mip chain / cube map / array decoded in ONE launch (include/itw_decode.h: itwDecodeChain, itwDecodeImage):
-// the mirror image of itwCompressImageChain.  The per-block decoders are decode_core.hpp's, as decode_kernel (decode.hip) uses them.
+// the mirror image of itwCompressImageChain.  itwDecodeBlocks, the older single-image entry, is a chain of one through the same kernel.
+// The block decoder is decode_core.hpp's decode_block.  One block per lane: 8 / 16 B in, 64 B (RGBA8) or 128 B (RGBA16F) out, HBM bound
+// by the output (4-8x the input).
 //
 // Lane = block of the chain's concatenated block list.  Its image is found by binary search over the first_block column of a small
 // descriptor table, the search chain_gather_kernel (chain.hip) does; a wave may span several block rows and, in the tail of a chain, several
 // whole images.  Stores are cropped to the image for every format: a block on the right / bottom edge writes min(4, w - 4x) x min(4, h - 4y)
-// texels.  A whole row of a block goes out as one 16-B store (two for RGBA16F) when its address is 16-byte aligned, as dwords otherwise, so an
-// output pointer or stride that is only 4-byte aligned works.  min_alpha[i] is the smallest alpha code among the texels stored for image i:
+// texels.  A row of a whole block goes out as one 16-B store (two for RGBA16F) at whatever dword address it has, the rows of a cropped block
+// as dwords, so an output pointer or stride that is only 4-byte aligned works.  min_alpha[i] is the smallest alpha code among the texels stored for image i:
 // a wave reduction per image the wave touches, then one atomicMin.
 #include <hip/hip_runtime.h>
 #include <cstdint>
@@ -18,20 +20,6 @@
 
 namespace itw {
 
-// a block's words from a stream whose base is 16-byte aligned (8 for the 8-byte formats) or only 4-byte aligned (the payload of a DDS file)
-__device__ __forceinline__ uint4 load_block16(const uint8_t* p)
-{
-    if (((uintptr_t)p & 15) == 0) return *reinterpret_cast<const uint4*>(p);
-    const uint32_t* q = reinterpret_cast<const uint32_t*>(p);
-    return make_uint4(q[0], q[1], q[2], q[3]);
-}
-__device__ __forceinline__ uint2 load_block8(const uint8_t* p)
-{
-    if (((uintptr_t)p & 7) == 0) return *reinterpret_cast<const uint2*>(p);
-    const uint32_t* q = reinterpret_cast<const uint32_t*>(p);
-    return make_uint2(q[0], q[1]);
-}
-
 // first on the stream, as measure_begin_kernel: every image's minimum starts at the largest word
 __global__ void __launch_bounds__(256) decode_chain_begin_kernel(uint32_t* __restrict__ min_alpha, int32_t nimg)
 {
@@ -39,77 +27,50 @@ __global__ void __launch_bounds__(256) decode_chain_begin_kernel(uint32_t* __res
     if (i < nimg) min_alpha[i] = 0xFFFFFFFFu;
 }
 
-// One block: decodes block j of the stream, stores the texels of it that lie inside `im`, returns the smallest alpha code among them.
-// FMT: decode_kernel's numbering -- 1 BC1, 3 BC3, 4 BC4, 5 BC5, 14 BC4_SNORM, 15 BC5_SNORM, 7 BC7, 6 BC6H
+// Four dwords that go out as one 16-byte store.  Global memory takes a multi-dword store at any dword address, so a whole row of a block
+// needs no more than the surface's own 4-byte alignment, and no test of it.
+struct alignas(4) Dwords4 { uint32_t v[4]; };
+
+// One block: decodes block j of the stream, stores the texels of it that lie inside `im`, returns the smallest alpha code among them
+// (`want_min`: the caller asked for min_alpha; without it the decoded alphas are not looked at).
 template <int FMT>
-__device__ __forceinline__ uint32_t decode_chain_block(const uint8_t* __restrict__ blocks, const DecodeImage& im, int64_t j, int32_t* __restrict__ modes)
+__device__ __forceinline__ uint32_t decode_chain_block(const uint8_t* __restrict__ blocks, const DecodeImage& im, int64_t j, int32_t* __restrict__ modes,
+                                                       bool want_min)
 {
-    uint32_t amin = 0xFFFFFFFFu;
-    const int32_t b = (int32_t)(j - im.first_block);        // < ITW_MEASURE_MAX_BLOCKS
+    const int32_t b = (int32_t)(j - im.first_block);        // <= DECODE_IMAGE_MAX_BLOCKS
     const int32_t yy = b / im.blocks_x, xx = b - yy * im.blocks_x;
     const int ny = min(4, im.height - yy * 4), nx = min(4, im.width - xx * 4);
-    int mode = 0;
-    if (FMT == 6) {
-        const uint4 w = load_block16(blocks + j * 16);
-        Bits bs{(unsigned long long)w.x | ((unsigned long long)w.y << 32), (unsigned long long)w.z | ((unsigned long long)w.w << 32), 0};
+    const uint4 w = load_block<FMT>(blocks, j);
+    int mode;
+    const bool alpha = filled_alpha(FMT) < 0 && want_min;       // only the formats whose alpha is decoded, not filled, have a minimum to find
+    uint32_t amin = filled_alpha(FMT) < 0 ? 0xFFFFFFFFu : (uint32_t)filled_alpha(FMT);
+    uint8_t* o = im.ptr + (int64_t)yy * 4 * im.stride + (int64_t)xx * 4 * texel_bytes(FMT);
+    const bool whole = nx == 4 && ny == 4;                      // an inner block: one branch for its four rows
+    if constexpr (FMT == BCN_BC6H) {
         uint32_t lo16[16], hi16[16];
-        mode = decode_bc6h(bs, lo16, hi16);
-        uint8_t* o = im.ptr + (int64_t)yy * 4 * im.stride + (int64_t)xx * 32;
-        if (nx == 4 && ny == 4 && (((uintptr_t)o | (uintptr_t)im.stride) & 15) == 0) {      // an inner block of an aligned surface: every row is whole and aligned
+        mode = decode_block<FMT>(w, lo16, hi16);
+        if (whole) {
 #pragma unroll
             for (int y = 0; y < 4; y++) {
-                uint4* r4 = reinterpret_cast<uint4*>(o + y * im.stride);
-                r4[0] = make_uint4(lo16[y * 4], hi16[y * 4], lo16[y * 4 + 1], hi16[y * 4 + 1]);
-                r4[1] = make_uint4(lo16[y * 4 + 2], hi16[y * 4 + 2], lo16[y * 4 + 3], hi16[y * 4 + 3]);
+                Dwords4* r4 = reinterpret_cast<Dwords4*>(o + y * im.stride);
+                r4[0] = Dwords4{{lo16[y * 4], hi16[y * 4], lo16[y * 4 + 1], hi16[y * 4 + 1]}};
+                r4[1] = Dwords4{{lo16[y * 4 + 2], hi16[y * 4 + 2], lo16[y * 4 + 3], hi16[y * 4 + 3]}};
             }
         } else
 #pragma unroll
         for (int y = 0; y < 4; y++) {
             if (y >= ny) break;
-            uint8_t* row = o + y * im.stride;
-            if (nx == 4 && ((uintptr_t)row & 15) == 0) {
-                uint4* r4 = reinterpret_cast<uint4*>(row);
-                r4[0] = make_uint4(lo16[y * 4], hi16[y * 4], lo16[y * 4 + 1], hi16[y * 4 + 1]);
-                r4[1] = make_uint4(lo16[y * 4 + 2], hi16[y * 4 + 2], lo16[y * 4 + 3], hi16[y * 4 + 3]);
-            } else {
-                uint32_t* r1 = reinterpret_cast<uint32_t*>(row);
+            uint32_t* r1 = reinterpret_cast<uint32_t*>(o + y * im.stride);
 #pragma unroll
-                for (int x = 0; x < 4; x++) if (x < nx) { r1[2 * x] = lo16[y * 4 + x]; r1[2 * x + 1] = hi16[y * 4 + x]; }
-            }
+            for (int x = 0; x < 4; x++) if (x < nx) { r1[2 * x] = lo16[y * 4 + x]; r1[2 * x + 1] = hi16[y * 4 + x]; }
         }
-        amin = 0x3C00u;                                     // alpha is filled: 1.0
     } else {
         uint32_t px[16];
-        if (FMT == 1) {
-            const uint2 w = load_block8(blocks + j * 8);
-            decode_color(w.x, w.y, true, px);
-        } else if (FMT == 3) {
-            const uint4 w = load_block16(blocks + j * 16);
-            decode_color(w.z, w.w, false, px);
-            decode_bc3_alpha(w.x, w.y, px);
-        } else if (FMT == 4 || FMT == 14) {                 // (R, 0, 0, 255), SNORM (R, 0, 0, 127)
-            const uint2 w = load_block8(blocks + j * 8);
+        mode = decode_block<FMT>(w, px);
+        if (whole) {
 #pragma unroll
-            for (int k = 0; k < 16; k++) px[k] = FMT == 4 ? 0xff000000u : 0x7f000000u;
-            if (FMT == 4) decode_scalar_block<0>(w.x, w.y, px); else decode_scalar_block_snorm<0>(w.x, w.y, px);
-        } else if (FMT == 5 || FMT == 15) {                 // (R, G, 0, 255), SNORM (R, G, 0, 127)
-            const uint4 w = load_block16(blocks + j * 16);
-#pragma unroll
-            for (int k = 0; k < 16; k++) px[k] = FMT == 5 ? 0xff000000u : 0x7f000000u;
-            if (FMT == 5) { decode_scalar_block<0>(w.x, w.y, px); decode_scalar_block<8>(w.z, w.w, px); }
-            else          { decode_scalar_block_snorm<0>(w.x, w.y, px); decode_scalar_block_snorm<8>(w.z, w.w, px); }
-        } else {
-            const uint4 w = load_block16(blocks + j * 16);
-            Bits bs{(unsigned long long)w.x | ((unsigned long long)w.y << 32), (unsigned long long)w.z | ((unsigned long long)w.w << 32), 0};
-            mode = decode_bc7(bs, px);
-        }
-        uint8_t* o = im.ptr + (int64_t)yy * 4 * im.stride + (int64_t)xx * 16;
-        constexpr bool ALPHA = FMT == 1 || FMT == 3 || FMT == 7;      // the formats whose alpha is decoded, not filled
-        if (!ALPHA) amin = (FMT == 4 || FMT == 5) ? 255u : 127u;
-        if (nx == 4 && ny == 4 && (((uintptr_t)o | (uintptr_t)im.stride) & 15) == 0) {      // an inner block of an aligned surface: every row is whole and aligned
-#pragma unroll
-            for (int y = 0; y < 4; y++) *reinterpret_cast<uint4*>(o + y * im.stride) = make_uint4(px[y * 4], px[y * 4 + 1], px[y * 4 + 2], px[y * 4 + 3]);
-            if (ALPHA) {
+            for (int y = 0; y < 4; y++) *reinterpret_cast<Dwords4*>(o + y * im.stride) = Dwords4{{px[y * 4], px[y * 4 + 1], px[y * 4 + 2], px[y * 4 + 3]}};
+            if (alpha) {
 #pragma unroll
                 for (int k = 0; k < 16; k++) amin = min(amin, px[k] >> 24);
             }
@@ -117,15 +78,10 @@ __device__ __forceinline__ uint32_t decode_chain_block(const uint8_t* __restrict
 #pragma unroll
         for (int y = 0; y < 4; y++) {
             if (y >= ny) break;
-            uint8_t* row = o + y * im.stride;
-            if (nx == 4 && ((uintptr_t)row & 15) == 0) {
-                *reinterpret_cast<uint4*>(row) = make_uint4(px[y * 4], px[y * 4 + 1], px[y * 4 + 2], px[y * 4 + 3]);
-            } else {
-                uint32_t* r1 = reinterpret_cast<uint32_t*>(row);
+            uint32_t* r1 = reinterpret_cast<uint32_t*>(o + y * im.stride);
 #pragma unroll
-                for (int x = 0; x < 4; x++) if (x < nx) r1[x] = px[y * 4 + x];
-            }
-            if (ALPHA) {
+            for (int x = 0; x < 4; x++) if (x < nx) r1[x] = px[y * 4 + x];
+            if (alpha) {
 #pragma unroll
                 for (int x = 0; x < 4; x++) if (x < nx) amin = min(amin, px[y * 4 + x] >> 24);
             }
@@ -135,8 +91,8 @@ __device__ __forceinline__ uint32_t decode_chain_block(const uint8_t* __restrict
     return amin;
 }
 
-// ONE: a chain of one image (itwDecodeImage).  Its descriptor is the kernel argument `one` -- uniform, so the address arithmetic stays
-// scalar as in decode_kernel -- and there is no table and no search.
+// ONE: a chain of one image (itwDecodeImage, itwDecodeBlocks).  Its descriptor is the kernel argument `one` -- uniform, so the address arithmetic stays
+// scalar -- and there is no table and no search.
 template <int FMT, bool ONE>
 __global__ void __launch_bounds__(256)
 decode_chain_kernel(const uint8_t* __restrict__ blocks, const DecodeImage* __restrict__ images, const DecodeImage one, int32_t nimg, int64_t nblocks,
@@ -148,7 +104,7 @@ decode_chain_kernel(const uint8_t* __restrict__ blocks, const DecodeImage* __res
     uint32_t amin = 0xFFFFFFFFu;
     if (live) {
         if (ONE) {
-            amin = decode_chain_block<FMT>(blocks, one, j, modes);
+            amin = decode_chain_block<FMT>(blocks, one, j, modes, min_alpha != nullptr);
         } else {
             int lo = 0, hi = nimg - 1;                          // the last image whose first block is <= j
             while (lo < hi) {
@@ -157,7 +113,7 @@ decode_chain_kernel(const uint8_t* __restrict__ blocks, const DecodeImage* __res
             }
             img = lo;
             const DecodeImage im = images[lo];
-            amin = decode_chain_block<FMT>(blocks, im, j, modes);
+            amin = decode_chain_block<FMT>(blocks, im, j, modes, min_alpha != nullptr);
         }
     }
     if (!min_alpha) return;                                     // (a kernel argument: the whole wave leaves or stays)
@@ -182,23 +138,17 @@ decode_chain_kernel(const uint8_t* __restrict__ blocks, const DecodeImage* __res
 
 namespace {
 
-template <int FMT>
-void launch_one(dim3 grid, hipStream_t st, const uint8_t* d_blocks, const itw::DecodeImage* d_desc, const itw::DecodeImage& first, int count,
-                int64_t total, int32_t* d_modes, uint32_t* d_min)
-{
-    if (count == 1) hipLaunchKernelGGL((itw::decode_chain_kernel<FMT, true>), grid, dim3(256), 0, st, d_blocks, d_desc, first, 1, total, d_modes, d_min);
-    else hipLaunchKernelGGL((itw::decode_chain_kernel<FMT, false>), grid, dim3(256), 0, st, d_blocks, d_desc, first, (int32_t)count, total, d_modes, d_min);
-}
-
-void decode_chain(int kind, const uint8_t* blocks, const rgba_surface* outs, int count, int64_t total, int32_t* modes, uint32_t* min_alpha, bool douts)
+// everything that needs the device, for `who` (the entry point's name): the `count` images of `total` blocks that its checks have passed
+void decode_chain(const char* who, int kind, const uint8_t* blocks, const rgba_surface* outs, int count, int64_t total, int32_t* modes,
+                  uint32_t* min_alpha, bool douts)
 {
     hipStream_t st = (hipStream_t)itwGetStream();
     const bool dblocks = itw::is_device_pointer(blocks), dmodes = !modes || itw::is_device_pointer(modes),
                dmin = !min_alpha || itw::is_device_pointer(min_alpha);
-    if (dblocks && ((uintptr_t)blocks & 3)) itw::fail_msg("itwDecodeChain: device block stream at %p is not 4-byte aligned", (const void*)blocks);
-    if ((dmodes && ((uintptr_t)modes & 3)) || (dmin && ((uintptr_t)min_alpha & 3))) itw::fail_msg("itwDecodeChain: misaligned modes / min_alpha");
-    if ((total + 255) / 256 > (int64_t)0x7fffffff) itw::fail_msg("itwDecodeChain: %lld blocks are more than one launch covers", (long long)total);
-    const size_t in_bytes = (size_t)total * (size_t)itw::decode_chain_block_bytes(kind);
+    if (dblocks && ((uintptr_t)blocks & 3)) itw::fail_msg("%s: device block stream at %p is not 4-byte aligned", who, (const void*)blocks);
+    if ((dmodes && ((uintptr_t)modes & 3)) || (dmin && ((uintptr_t)min_alpha & 3))) itw::fail_msg("%s: misaligned modes / min_alpha", who);
+    if ((total + 255) / 256 > (int64_t)0x7fffffff) itw::fail_msg("%s: %lld blocks are more than one launch covers", who, (long long)total);
+    const size_t in_bytes = (size_t)total * (size_t)itw::block_bytes(kind);
 
     static thread_local std::vector<itw::DecodeImage> desc;     // grow-only, like the device buffer it is copied into
     desc.resize((size_t)count);
@@ -221,22 +171,16 @@ void decode_chain(int kind, const uint8_t* blocks, const rgba_surface* outs, int
         ITW_CHECK(hipGetLastError());
     }
     const dim3 grid((unsigned)((total + 255) / 256));
-    switch (kind) {
-    case 1:  launch_one<1>(grid, st, d_blocks, d_desc, desc[0], count, total, d_modes, d_min); break;
-    case 3:  launch_one<3>(grid, st, d_blocks, d_desc, desc[0], count, total, d_modes, d_min); break;
-    case 4:  launch_one<4>(grid, st, d_blocks, d_desc, desc[0], count, total, d_modes, d_min); break;
-    case 5:  launch_one<5>(grid, st, d_blocks, d_desc, desc[0], count, total, d_modes, d_min); break;
-    case 14: launch_one<14>(grid, st, d_blocks, d_desc, desc[0], count, total, d_modes, d_min); break;
-    case 15: launch_one<15>(grid, st, d_blocks, d_desc, desc[0], count, total, d_modes, d_min); break;
-    case 7:  launch_one<7>(grid, st, d_blocks, d_desc, desc[0], count, total, d_modes, d_min); break;
-    default: launch_one<6>(grid, st, d_blocks, d_desc, desc[0], count, total, d_modes, d_min); break;
-    }
+    itw::with_kind(kind, [&](auto K) {
+        if (count == 1) hipLaunchKernelGGL((itw::decode_chain_kernel<K.value, true>), grid, dim3(256), 0, st, d_blocks, d_desc, desc[0], 1, total, d_modes, d_min);
+        else hipLaunchKernelGGL((itw::decode_chain_kernel<K.value, false>), grid, dim3(256), 0, st, d_blocks, d_desc, desc[0], (int32_t)count, total, d_modes, d_min);
+    });
     ITW_CHECK(hipGetLastError());
     if (resident) { if (buffer) itw::decode_scratch_done(st); return; }     // all on the device: asynchronous on the thread's stream
 
     if (!douts)
         for (int i = 0; i < count; i++) {                       // one strided download per image
-            const size_t row_bytes = (size_t)outs[i].width * (size_t)itw::decode_chain_texel_bytes(kind);
+            const size_t row_bytes = (size_t)outs[i].width * (size_t)itw::texel_bytes(kind);
             ITW_CHECK(hipMemcpy2DAsync(outs[i].ptr, (size_t)outs[i].stride, desc[(size_t)i].ptr, (size_t)desc[(size_t)i].stride, row_bytes,
                                        (size_t)outs[i].height, hipMemcpyDeviceToHost, st));
         }
@@ -250,17 +194,30 @@ void decode_chain(int kind, const uint8_t* blocks, const rgba_surface* outs, int
 
 extern "C" int itwDecodeChain(int dxgi_format, const uint8_t* blocks, const rgba_surface* outs, int count, int32_t* modes, uint32_t* min_alpha)
 {
-    const int kind = itw::decode_chain_kind(dxgi_format);
+    const int kind = dxgi_format == 96 ? 0 : itw::decode_kind(dxgi_format);      // BC6H_SF16: the signed decode is not built, and nothing here may pass for it
     const int64_t total = itw::decode_chain_check(kind, blocks, outs, count);
     if (total <= 0) return total < 0 ? -1 : 0;
     const bool douts = itw::is_device_pointer(outs[0].ptr);
     for (int i = 1; i < count; i++)
         if (itw::is_device_pointer(outs[i].ptr) != douts) return -1;      // all host or all device, as the chain encoder asks
-    const bool ok = itw::guarded([&] { decode_chain(kind, blocks, outs, count, total, modes, min_alpha, douts); });
+    const bool ok = itw::guarded([&] { decode_chain("itwDecodeChain", kind, blocks, outs, count, total, modes, min_alpha, douts); });
     return ok ? 0 : -1;
 }
 
 extern "C" int itwDecodeImage(int dxgi_format, const uint8_t* blocks, const rgba_surface* out, int32_t* modes, uint32_t* min_alpha)
 {
     return itwDecodeChain(dxgi_format, blocks, out, 1, modes, min_alpha);
+}
+
+// The older single-image entry: its own argument rules (decode_blocks_check; 96 reads as unsigned), then a chain of one without min_alpha
+extern "C" int itwDecodeBlocks(int dxgi_format, const uint8_t* blocks, int width, int height, uint8_t* out, int64_t out_stride, int32_t* modes)
+{
+    const int kind = itw::decode_kind(dxgi_format);
+    const int64_t total = itw::decode_blocks_check(kind, width, height, out_stride);
+    if (total < 0) return -1;
+    const rgba_surface surface{out, width, height, (int32_t)out_stride};
+    const bool ok = itw::guarded([&] {
+        decode_chain("itwDecodeBlocks", kind, blocks, &surface, 1, total, modes, nullptr, itw::is_device_pointer(out));
+    });
+    return ok ? 0 : -1;
 }

@@ -1,10 +1,14 @@
-// decode_core.hpp -- the per-block BCn decoders (decode_color, decode_scalar_block, decode_bc7, decode_bc6h) and their tables, shared by
-// decode.hip (blocks -> texels in memory) and measure.hip (blocks -> registers -> error sums).  Written from the format definitions;
-// the readable statement inside the reference tree is its decoder (see decode.hip).
+// decode_core.hpp -- BCn block decoding for gfx950, shared by everything that turns block words into texels: decode_chain.hip (blocks ->
+// texels in memory), measure.hip and refine.hip (blocks -> registers -> error sums).  decode_block<FMT> is the one block -> 16 texels
+// function; under it the per-format decoders (decode_color, decode_scalar_block, decode_bc7, decode_bc6h) and their tables.  Pure integer
+// work.  Written from the format definitions (the readable statement inside the reference tree is its decoder: BC.cpp for BC1/BC3,
+// BC4BC5.cpp for BC4/BC5, BC6HBC7.cpp:35-37 weights, :40 partitions, :247 fix-ups, :537 BC7 mode table, :1937-2140 BC7 decode,
+// :310-500 BC6H mode descriptors, :1077-1210 BC6H decode, :1313-1359 unquantisation).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "bc6h_layout.hpp"
+#include "bcn_format.hpp"
 
 namespace itw {
 
@@ -261,6 +265,66 @@ __device__ __forceinline__ int decode_bc6h(Bits& bs, uint32_t (&lo)[16], uint32_
         hi[k] = (uint32_t)v[2] | 0x3C000000u;
     }
     return mode;
+}
+
+// ---- any format: block words -> 16 texels -------------------------------------------------------------------------------------------
+// the 128 bits of a block as the LSB-first reader takes them
+__device__ __forceinline__ Bits block_bits(const uint4 w)
+{
+    return Bits{(unsigned long long)w.x | ((unsigned long long)w.y << 32), (unsigned long long)w.z | ((unsigned long long)w.w << 32), 0};
+}
+
+// Decodes the block whose words are `w` (the 8-byte formats use .x and .y) into RGBA8 dwords (int8 codes for the SNORM pair) and returns
+// its mode: BC7 0..7 or -1 for the reserved prefix, 0 for the formats without modes.  Alpha is filled where the format has none
+// (filled_alpha): BC4 / BC5 decode to (R, 0, 0, 255) / (R, G, 0, 255) like D3DXDecodeBC4U / BC5U (BC4BC5.cpp:373-385, 449-462), their
+// SNORM forms to int8 (R, 0, 0, 127) / (R, G, 0, 127) (:388-400, :465-478).
+template <int FMT>
+__device__ __forceinline__ int decode_block(const uint4 w, uint32_t (&px)[16])
+{
+    static_assert(FMT != BCN_BC6H, "BC6H decodes to RGBA16F: the overload below");
+    if (FMT == BCN_BC7) {
+        Bits bs = block_bits(w);
+        return decode_bc7(bs, px);
+    } else if (FMT == BCN_BC1) {
+        decode_color(w.x, w.y, true, px);
+    } else if (FMT == BCN_BC3) {
+        decode_color(w.z, w.w, false, px);
+        decode_bc3_alpha(w.x, w.y, px);
+    } else {
+        constexpr bool SNORM = FMT == BCN_BC4S || FMT == BCN_BC5S;
+#pragma unroll
+        for (int k = 0; k < 16; k++) px[k] = (uint32_t)filled_alpha(FMT) << 24;
+        if (SNORM) decode_scalar_block_snorm<0>(w.x, w.y, px); else decode_scalar_block<0>(w.x, w.y, px);
+        if (FMT == BCN_BC5) decode_scalar_block<8>(w.z, w.w, px);
+        if (FMT == BCN_BC5S) decode_scalar_block_snorm<8>(w.z, w.w, px);
+    }
+    return 0;
+}
+// BC6H: the two dwords of each RGBA16F texel, lo = R | G << 16, hi = B | A << 16 with alpha 1.0; mode 0..13, -1 for a reserved prefix
+template <int FMT>
+__device__ __forceinline__ int decode_block(const uint4 w, uint32_t (&lo)[16], uint32_t (&hi)[16])
+{
+    static_assert(FMT == BCN_BC6H, "the RGBA8 formats: the overload above");
+    Bits bs = block_bits(w);
+    return decode_bc6h(bs, lo, hi);
+}
+
+// Block j of a stream whose base is 16-byte aligned (8 for the 8-byte formats) or only 4-byte aligned (the payload of a DDS file).  Callers
+// that guarantee the alignment (measure.hip, refine.hip) load the vector themselves and carry no branch.
+template <int FMT>
+__device__ __forceinline__ uint4 load_block(const uint8_t* __restrict__ blocks, int64_t j)
+{
+    if constexpr (block_bytes(FMT) == 8) {
+        const uint8_t* p = blocks + j * 8;
+        if (((uintptr_t)p & 7) == 0) { const uint2 v = *reinterpret_cast<const uint2*>(p); return make_uint4(v.x, v.y, 0u, 0u); }
+        const uint32_t* q = reinterpret_cast<const uint32_t*>(p);
+        return make_uint4(q[0], q[1], 0u, 0u);
+    } else {
+        const uint8_t* p = blocks + j * 16;
+        if (((uintptr_t)p & 15) == 0) return *reinterpret_cast<const uint4*>(p);
+        const uint32_t* q = reinterpret_cast<const uint32_t*>(p);
+        return make_uint4(q[0], q[1], q[2], q[3]);
+    }
 }
 
 } // namespace itw

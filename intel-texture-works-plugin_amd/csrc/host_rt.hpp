@@ -72,7 +72,7 @@ void* decode_scratch(size_t bytes, hipStream_t st);
 void decode_scratch_done(hipStream_t st);
 
 // One predicate for "the kernels can dereference this pointer": device AND managed allocations (abi.hip and
-// dispatch.hip/decode.hip used to disagree on managed memory).  Unregistered host memory -> false.
+// dispatch.hip and the decode entry used to disagree on managed memory).  Unregistered host memory -> false.
 bool is_device_pointer(const void* p) noexcept;
 
 } // namespace itw

@@ -1,7 +1,7 @@
 // measure.hip -- how far an encoded stream is from its source, on the device (include/itw_decode.h: itwMeasureBlocks, itwMeasureChain,
 // itwStatsPsnr).  Decode, compare and reduce in ONE kernel: the decoded surface never exists in memory.  One lane per block, as in
-// decode_kernel: 8 / 16 B of block in, its up-to-4x4 source texels in as row-wide vector loads (16 B per RGBA8 row, 2 x 16 B per RGBA16F
-// row; rows and columns of partial edge blocks guarded), decoded into registers by the decoders of decode_core.hpp, and compared code by
+// decode_chain_kernel: 8 / 16 B of block in, its up-to-4x4 source texels in as row-wide vector loads (16 B per RGBA8 row, 2 x 16 B per RGBA16F
+// row; rows and columns of partial edge blocks guarded), decoded into registers by decode_core.hpp's decode_block, and compared code by
 // code.  Every quantity is an integer, so the result is the same bits on every run.
 //
 // Reduction.  A workgroup walks the block list with a grid stride (at most MEASURE_MAX_GROUPS workgroups, so that the handful of atomics
@@ -32,14 +32,14 @@ constexpr uint32_t MEASURE_INDEX_MASK = (1u << MEASURE_INDEX_BITS) - 1u;
 constexpr int MEASURE_MAX_GROUPS = 1024;      // 4 workgroups per CU; <= 2^25 / (1024 * 256) = 128 blocks per lane: 128 * 16 * 255^2 < 2^32
 static_assert((uint64_t)ITW_MEASURE_MAX_BLOCKS == (1ull << MEASURE_INDEX_BITS), "the key's index field is what limits the block count");
 
-// FMT: 1 BC1, 3 BC3, 4 BC4, 5 BC5, 14 BC4_SNORM, 15 BC5_SNORM, 7 BC7, 6 BC6H (decode_kernel's numbering).  The SNORM pair compares
-// int8 codes, a source code of -128 read as -127 (both are -1.0; the decoder never emits -128)
+// FMT: a BcnKind (bcn_format.hpp).  `blocks` is 16-byte aligned (8 for the 8-byte formats).  The SNORM pair compares int8 codes, a source
+// code of -128 read as -127 (both are -1.0; the decoder never emits -128)
 template <int FMT>
 __global__ void __launch_bounds__(256)
 measure_kernel(const uint8_t* __restrict__ blocks, int32_t blocks_x, int32_t nblocks, const uint8_t* __restrict__ src, int64_t stride,
                int32_t width, int32_t height, itw_error_stats* __restrict__ stats, unsigned long long* __restrict__ block_sse)
 {
-    using Acc = typename std::conditional<FMT == 6, unsigned long long, uint32_t>::type;   // a lane's per-channel sum: 16 * 0xFFFF^2 > 2^32 for BC6H
+    using Acc = typename std::conditional<FMT == BCN_BC6H, unsigned long long, uint32_t>::type;   // a lane's per-channel sum: 16 * 0xFFFF^2 > 2^32 for BC6H
     __shared__ unsigned long long s_sum[4][4], s_key[4];
     __shared__ uint32_t s_max[4][4], s_hist[17];               // [16]: reserved-prefix blocks
     const int t = threadIdx.x;
@@ -54,12 +54,13 @@ measure_kernel(const uint8_t* __restrict__ blocks, int32_t blocks_x, int32_t nbl
         const int32_t yy = b / blocks_x, xx = b - yy * blocks_x;
         const int ny = min(4, height - yy * 4), nx = min(4, width - xx * 4);
         Acc bs[4] = {0, 0, 0, 0};
-        int mode = 0;
-        if (FMT == 6) {
-            const uint4 w = *reinterpret_cast<const uint4*>(blocks + (int64_t)b * 16);
-            Bits rd{(unsigned long long)w.x | ((unsigned long long)w.y << 32), (unsigned long long)w.z | ((unsigned long long)w.w << 32), 0};
+        uint4 w;
+        if constexpr (block_bytes(FMT) == 8) { const uint2 v = *reinterpret_cast<const uint2*>(blocks + (int64_t)b * 8); w = make_uint4(v.x, v.y, 0u, 0u); }
+        else w = *reinterpret_cast<const uint4*>(blocks + (int64_t)b * 16);
+        int mode;
+        if constexpr (FMT == BCN_BC6H) {
             uint32_t lo[16], hi[16];
-            mode = decode_bc6h(rd, lo, hi);
+            mode = decode_block<FMT>(w, lo, hi);
             const uint8_t* p = src + (int64_t)yy * 4 * stride + (int64_t)xx * 32;
 #pragma unroll
             for (int y = 0; y < 4; y++) {
@@ -81,40 +82,7 @@ measure_kernel(const uint8_t* __restrict__ blocks, int32_t blocks_x, int32_t nbl
             }
         } else {
             uint32_t px[16];
-            if (FMT == 1) {
-                const uint2 w = *reinterpret_cast<const uint2*>(blocks + (int64_t)b * 8);
-                decode_color(w.x, w.y, true, px);
-            } else if (FMT == 3) {
-                const uint4 w = *reinterpret_cast<const uint4*>(blocks + (int64_t)b * 16);
-                decode_color(w.z, w.w, false, px);
-                decode_bc3_alpha(w.x, w.y, px);
-            } else if (FMT == 4) {
-                const uint2 w = *reinterpret_cast<const uint2*>(blocks + (int64_t)b * 8);
-#pragma unroll
-                for (int k = 0; k < 16; k++) px[k] = 0xff000000u;
-                decode_scalar_block<0>(w.x, w.y, px);
-            } else if (FMT == 5) {
-                const uint4 w = *reinterpret_cast<const uint4*>(blocks + (int64_t)b * 16);
-#pragma unroll
-                for (int k = 0; k < 16; k++) px[k] = 0xff000000u;
-                decode_scalar_block<0>(w.x, w.y, px);
-                decode_scalar_block<8>(w.z, w.w, px);
-            } else if (FMT == 14) {
-                const uint2 w = *reinterpret_cast<const uint2*>(blocks + (int64_t)b * 8);
-#pragma unroll
-                for (int k = 0; k < 16; k++) px[k] = 0x7f000000u;
-                decode_scalar_block_snorm<0>(w.x, w.y, px);
-            } else if (FMT == 15) {
-                const uint4 w = *reinterpret_cast<const uint4*>(blocks + (int64_t)b * 16);
-#pragma unroll
-                for (int k = 0; k < 16; k++) px[k] = 0x7f000000u;
-                decode_scalar_block_snorm<0>(w.x, w.y, px);
-                decode_scalar_block_snorm<8>(w.z, w.w, px);
-            } else {
-                const uint4 w = *reinterpret_cast<const uint4*>(blocks + (int64_t)b * 16);
-                Bits rd{(unsigned long long)w.x | ((unsigned long long)w.y << 32), (unsigned long long)w.z | ((unsigned long long)w.w << 32), 0};
-                mode = decode_bc7(rd, px);
-            }
+            mode = decode_block<FMT>(w, px);
             const uint8_t* p = src + (int64_t)yy * 4 * stride + (int64_t)xx * 16;
 #pragma unroll
             for (int y = 0; y < 4; y++) {
@@ -127,7 +95,7 @@ measure_kernel(const uint8_t* __restrict__ blocks, int32_t blocks_x, int32_t nbl
 #pragma unroll
                     for (int c = 0; c < 4; c++) {
                         int a = (int)((s[x] >> (8 * c)) & 255u), e = (int)((px[y * 4 + x] >> (8 * c)) & 255u);
-                        if (FMT == 14 || FMT == 15) { a = max((int)(int8_t)a, -127); e = (int)(int8_t)e; }
+                        if (FMT == BCN_BC4S || FMT == BCN_BC5S) { a = max((int)(int8_t)a, -127); e = (int)(int8_t)e; }
                         const uint32_t df = (uint32_t)abs(a - e);
                         bs[c] += df * df;
                         mx[c] = max(mx[c], df);
@@ -141,7 +109,7 @@ measure_kernel(const uint8_t* __restrict__ blocks, int32_t blocks_x, int32_t nbl
         key = k > key ? k : key;
 #pragma unroll
         for (int c = 0; c < 4; c++) sum[c] += bs[c];
-        if (FMT == 6 || FMT == 7) atomicAdd(&s_hist[mode < 0 ? 16 : mode], 1u);
+        if (FMT == BCN_BC6H || FMT == BCN_BC7) atomicAdd(&s_hist[mode < 0 ? 16 : mode], 1u);
         else mine++;
     }
 
@@ -152,12 +120,12 @@ measure_kernel(const uint8_t* __restrict__ blocks, int32_t blocks_x, int32_t nbl
 #pragma unroll
     for (int c = 0; c < 4; c++) { ws[c] = wave_sum((unsigned long long)sum[c]); wm[c] = wave_max(mx[c]); }
     key = wave_max(key);
-    if (FMT != 6 && FMT != 7) mine = wave_sum(mine);
+    if (FMT != BCN_BC6H && FMT != BCN_BC7) mine = wave_sum(mine);
     if (lane == 0) {
 #pragma unroll
         for (int c = 0; c < 4; c++) { s_sum[wave][c] = ws[c]; s_max[wave][c] = wm[c]; }
         s_key[wave] = key;
-        if (FMT != 6 && FMT != 7) atomicAdd(&s_hist[0], mine);
+        if (FMT != BCN_BC6H && FMT != BCN_BC7) atomicAdd(&s_hist[0], mine);
     }
     __syncthreads();
     if (t < 20) {                                               // lanes 0-3: sse[], 4-19: mode_hist[]
@@ -200,20 +168,12 @@ __global__ void measure_finish_kernel(itw_error_stats* __restrict__ stats, int32
 
 namespace {
 
-int kind_of(int f)
-{
-    return (f == 71 || f == 72) ? 1 : (f == 77 || f == 78) ? 3 : (f == 98 || f == 99) ? 7 : (f == 95 || f == 96) ? 6 : f == 80 ? 4 : f == 83 ? 5 :
-           f == 81 ? 14 : f == 84 ? 15 : 0;
-}
-int64_t blocks_of(const rgba_surface& s) { return (int64_t)((s.width + 3) / 4) * ((s.height + 3) / 4); }
-int block_bytes(int kind) { return (kind == 1 || kind == 4 || kind == 14) ? 8 : 16; }
-
 // the checks that need no device
 bool surface_ok(int kind, const rgba_surface* s)
 {
     if (!s || !s->ptr || s->width < 1 || s->height < 1) return false;
-    if ((int64_t)s->stride < (int64_t)s->width * (kind == 6 ? 8 : 4)) return false;
-    return blocks_of(*s) <= (int64_t)ITW_MEASURE_MAX_BLOCKS;
+    if ((int64_t)s->stride < (int64_t)s->width * itw::texel_bytes(kind)) return false;
+    return itw::image_blocks(*s) <= (int64_t)ITW_MEASURE_MAX_BLOCKS;
 }
 
 // everything on the device: three kernels -- zero, measure, finish -- in stream order; allocates nothing
@@ -221,23 +181,16 @@ void enqueue(int kind, int dxgi_format, const uint8_t* d_blocks, const uint8_t* 
              itw_error_stats* d_stats, uint64_t* d_map, hipStream_t st)
 {
     const int bx = (width + 3) / 4;
-    const int64_t n = (int64_t)bx * ((height + 3) / 4);
+    const int64_t n = (int64_t)bx * ((height + 3) / 4);               // <= ITW_MEASURE_MAX_BLOCKS (surface_ok)
     const int64_t groups = (n + 255) / 256;
     const dim3 grid((unsigned)(groups < itw::MEASURE_MAX_GROUPS ? groups : itw::MEASURE_MAX_GROUPS)), blk(256);
     unsigned long long* map = reinterpret_cast<unsigned long long*>(d_map);
     static_assert(sizeof(itw_error_stats) / 4 <= 64, "measure_begin_kernel: one lane per dword");
     hipLaunchKernelGGL(itw::measure_begin_kernel, dim3(1), dim3(64), 0, st, d_stats);
     ITW_CHECK(hipGetLastError());
-    switch (kind) {
-    case 1: hipLaunchKernelGGL((itw::measure_kernel<1>), grid, blk, 0, st, d_blocks, bx, (int32_t)n, d_src, stride, width, height, d_stats, map); break;
-    case 3: hipLaunchKernelGGL((itw::measure_kernel<3>), grid, blk, 0, st, d_blocks, bx, (int32_t)n, d_src, stride, width, height, d_stats, map); break;
-    case 4: hipLaunchKernelGGL((itw::measure_kernel<4>), grid, blk, 0, st, d_blocks, bx, (int32_t)n, d_src, stride, width, height, d_stats, map); break;
-    case 5: hipLaunchKernelGGL((itw::measure_kernel<5>), grid, blk, 0, st, d_blocks, bx, (int32_t)n, d_src, stride, width, height, d_stats, map); break;
-    case 14: hipLaunchKernelGGL((itw::measure_kernel<14>), grid, blk, 0, st, d_blocks, bx, (int32_t)n, d_src, stride, width, height, d_stats, map); break;
-    case 15: hipLaunchKernelGGL((itw::measure_kernel<15>), grid, blk, 0, st, d_blocks, bx, (int32_t)n, d_src, stride, width, height, d_stats, map); break;
-    case 7: hipLaunchKernelGGL((itw::measure_kernel<7>), grid, blk, 0, st, d_blocks, bx, (int32_t)n, d_src, stride, width, height, d_stats, map); break;
-    default: hipLaunchKernelGGL((itw::measure_kernel<6>), grid, blk, 0, st, d_blocks, bx, (int32_t)n, d_src, stride, width, height, d_stats, map); break;
-    }
+    itw::with_kind(kind, [&](auto K) {
+        hipLaunchKernelGGL((itw::measure_kernel<K.value>), grid, blk, 0, st, d_blocks, bx, (int32_t)n, d_src, stride, width, height, d_stats, map);
+    });
     ITW_CHECK(hipGetLastError());
     hipLaunchKernelGGL(itw::measure_finish_kernel, dim3(1), dim3(64), 0, st, d_stats, (int32_t)dxgi_format, (int32_t)width, (int32_t)height, (unsigned long long)n);
     ITW_CHECK(hipGetLastError());
@@ -273,17 +226,17 @@ struct Staging {
 extern "C" int itwMeasureBlocks(int dxgi_format, const uint8_t* blocks, const rgba_surface* source, itw_error_stats* stats, size_t stats_bytes,
                                 uint64_t* block_sse)
 {
-    const int kind = kind_of(dxgi_format);
+    const int kind = itw::decode_kind(dxgi_format);
     if (!kind || !blocks || !stats || stats_bytes != sizeof(itw_error_stats) || !surface_ok(kind, source)) return -1;
     if (((uintptr_t)stats & 7) || ((uintptr_t)block_sse & 7)) return -1;
     const bool ok = itw::guarded([&] {
         hipStream_t st = (hipStream_t)itwGetStream();
         const bool dblocks = itw::is_device_pointer(blocks), dsrc = itw::is_device_pointer(source->ptr), dstats = itw::is_device_pointer(stats),
                    dmap = !block_sse || itw::is_device_pointer(block_sse);
-        const int64_t n = blocks_of(*source);
-        const size_t row_bytes = (size_t)source->width * (kind == 6 ? 8 : 4);
+        const int64_t n = itw::image_blocks(*source);
+        const size_t row_bytes = (size_t)source->width * itw::texel_bytes(kind);
         Staging tmp;
-        const uint8_t* d_blocks = dblocks ? blocks : tmp.upload(blocks, (size_t)n * block_bytes(kind), st);
+        const uint8_t* d_blocks = dblocks ? blocks : tmp.upload(blocks, (size_t)n * itw::block_bytes(kind), st);
         const uint8_t* d_src = dsrc ? source->ptr : tmp.upload_rows(*source, row_bytes, st);
         itw_error_stats* d_stats = dstats ? stats : static_cast<itw_error_stats*>(tmp.alloc(sizeof(itw_error_stats)));
         uint64_t* d_map = dmap ? block_sse : static_cast<uint64_t*>(tmp.alloc((size_t)n * 8));
@@ -298,12 +251,12 @@ extern "C" int itwMeasureBlocks(int dxgi_format, const uint8_t* blocks, const rg
 
 extern "C" int itwMeasureChain(const rgba_surface* images, int count, const uint8_t* blocks, int dxgi_format, itw_error_stats* stats, size_t stats_bytes)
 {
-    const int kind = kind_of(dxgi_format);
+    const int kind = itw::decode_kind(dxgi_format);
     if (!kind || !images || count < 1 || !blocks || !stats || stats_bytes != sizeof(itw_error_stats) || ((uintptr_t)stats & 7)) return -1;
     int64_t total = 0;
     for (int i = 0; i < count; i++) {
         if (!surface_ok(kind, &images[i])) return -1;
-        total += blocks_of(images[i]);
+        total += itw::image_blocks(images[i]);
     }
     const bool ok = itw::guarded([&] {
         hipStream_t st = (hipStream_t)itwGetStream();
@@ -313,16 +266,16 @@ extern "C" int itwMeasureChain(const rgba_surface* images, int count, const uint
                 itw::fail_msg("itwMeasureChain: image %d is %s memory, image 0 %s: all images must be host or all device pointers", i,
                               dsrc ? "host" : "device", dsrc ? "device" : "host");
         Staging tmp;
-        const uint8_t* d_blocks = dblocks ? blocks : tmp.upload(blocks, (size_t)total * block_bytes(kind), st);
+        const uint8_t* d_blocks = dblocks ? blocks : tmp.upload(blocks, (size_t)total * itw::block_bytes(kind), st);
         itw_error_stats* d_stats = dstats ? stats : static_cast<itw_error_stats*>(tmp.alloc(sizeof(itw_error_stats) * (size_t)count));
         int64_t first = 0;                                      // image i's blocks start where the images before it end (itwChainBytes)
         for (int i = 0; i < count; i++) {
             const rgba_surface& im = images[i];
-            const size_t row_bytes = (size_t)im.width * (kind == 6 ? 8 : 4);
+            const size_t row_bytes = (size_t)im.width * itw::texel_bytes(kind);
             const uint8_t* d_src = dsrc ? im.ptr : tmp.upload_rows(im, row_bytes, st);
-            enqueue(kind, dxgi_format, d_blocks + first * block_bytes(kind), d_src, dsrc ? (int64_t)im.stride : (int64_t)row_bytes, im.width, im.height,
+            enqueue(kind, dxgi_format, d_blocks + first * itw::block_bytes(kind), d_src, dsrc ? (int64_t)im.stride : (int64_t)row_bytes, im.width, im.height,
                     d_stats + i, nullptr, st);
-            first += blocks_of(im);
+            first += itw::image_blocks(im);
         }
         if (dblocks && dsrc && dstats) return;
         if (!dstats) ITW_CHECK(hipMemcpyAsync(stats, d_stats, sizeof(itw_error_stats) * (size_t)count, hipMemcpyDeviceToHost, st));
@@ -334,14 +287,14 @@ extern "C" int itwMeasureChain(const rgba_surface* images, int count, const uint
 extern "C" double itwStatsPsnr(const itw_error_stats* stats, uint32_t channel_mask)
 {
     const double nan = std::numeric_limits<double>::quiet_NaN();
-    if (!stats || !(channel_mask & 15u) || kind_of(stats->dxgi_format) == 6) return nan;
+    const int kind = stats ? itw::decode_kind(stats->dxgi_format) : 0;
+    if (!stats || !(channel_mask & 15u) || kind == itw::BCN_BC6H) return nan;
     double sum = 0.0;
     int channels = 0;
     for (int c = 0; c < 4; c++)
         if (channel_mask & (1u << c)) { sum += (double)stats->sse[c]; channels++; }
     if (sum == 0.0) return std::numeric_limits<double>::infinity();
     const double n = (double)stats->width * (double)stats->height * (double)channels;
-    const int kind = kind_of(stats->dxgi_format);
-    const double peak = (kind == 14 || kind == 15) ? 254.0 : 255.0;      // int8 codes -127..127
+    const double peak = (kind == itw::BCN_BC4S || kind == itw::BCN_BC5S) ? 254.0 : 255.0;      // int8 codes -127..127
     return 10.0 * std::log10(peak * peak * n / sum);
 }

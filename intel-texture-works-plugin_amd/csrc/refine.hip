@@ -48,10 +48,9 @@ static_assert(sizeof(RefineAcc) == 48, "refine_begin_kernel: one lane per dword"
 template <int FMT>
 __device__ __forceinline__ unsigned long long refine_block_error(const uint4 w, const uint8_t* p, int64_t stride, uint32_t mask)
 {
-    Bits rd{(unsigned long long)w.x | ((unsigned long long)w.y << 32), (unsigned long long)w.z | ((unsigned long long)w.w << 32), 0};
-    if (FMT == 6) {
+    if constexpr (FMT == BCN_BC6H) {
         uint32_t lo[16], hi[16];
-        (void)decode_bc6h(rd, lo, hi);
+        (void)decode_block<FMT>(w, lo, hi);
         unsigned long long e = 0ull;
 #pragma unroll
         for (int y = 0; y < 4; y++) {
@@ -71,7 +70,7 @@ __device__ __forceinline__ unsigned long long refine_block_error(const uint4 w, 
         return e;
     } else {
         uint32_t px[16];
-        (void)decode_bc7(rd, px);
+        (void)decode_block<FMT>(w, px);
         uint32_t e = 0u;                                        // 64 * 255^2 < 2^32
 #pragma unroll
         for (int y = 0; y < 4; y++) {
@@ -96,14 +95,14 @@ __global__ void refine_begin_kernel(RefineAcc* __restrict__ acc)
     if (blockIdx.x == 0 && threadIdx.x < sizeof(RefineAcc) / 4) reinterpret_cast<uint32_t*>(acc)[threadIdx.x] = 0u;
 }
 
-// FMT: 7 BC7, 6 BC6H (decode_kernel's numbering).  `blocks`: 16-B aligned.
+// FMT: BCN_BC7 or BCN_BC6H (bcn_format.hpp).  `blocks`: 16-B aligned.
 template <int FMT>
 __global__ void __launch_bounds__(256)
 refine_judge_kernel(const uint8_t* __restrict__ blocks, int32_t blocks_x, int32_t nblocks, const uint8_t* __restrict__ src, int64_t stride,
                     uint32_t mask, unsigned long long budget, unsigned long long* __restrict__ emap, uint8_t* __restrict__ tmap,
                     uint32_t* __restrict__ group_count, RefineAcc* __restrict__ acc)
 {
-    constexpr int PX = FMT == 6 ? 8 : 4;
+    constexpr int PX = texel_bytes(FMT);
     __shared__ unsigned long long s_sum[4], s_max[4], s_stay[4];
     __shared__ uint32_t s_cnt[4];
     const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
@@ -206,7 +205,7 @@ refine_commit_kernel(const uint32_t* __restrict__ list, int32_t n, int32_t packe
                      const uint8_t* __restrict__ refined, uint32_t mask, uint8_t* __restrict__ blocks, unsigned long long* __restrict__ emap,
                      uint8_t* __restrict__ tmap, RefineAcc* __restrict__ acc)
 {
-    constexpr int PX = FMT == 6 ? 8 : 4;
+    constexpr int PX = texel_bytes(FMT);
     __shared__ unsigned long long s_gain[4], s_max[4];
     __shared__ uint32_t s_won[4];
     const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
@@ -272,7 +271,7 @@ void refine(int kind, const rgba_surface& s, uint8_t* target, int dxgi_format, c
 {
     using namespace itw;
     hipStream_t st = (hipStream_t)itwGetStream();
-    const int px = kind == 6 ? 8 : 4;
+    const int px = texel_bytes(kind);
     const int bx = s.width / 4, by = s.height / 4;
     const int64_t nb = (int64_t)bx * by;
     const int32_t groups = (int32_t)((nb + 255) / 256);
@@ -310,9 +309,9 @@ void refine(int kind, const rgba_surface& s, uint8_t* target, int dxgi_format, c
     const dim3 blk(256);
     hipLaunchKernelGGL(refine_begin_kernel, dim3(1), dim3(64), 0, st, acc);
     ITW_CHECK(hipGetLastError());
-    if (kind == 7) hipLaunchKernelGGL((refine_judge_kernel<7>), dim3((unsigned)groups), blk, 0, st, d_tgt, bx, (int32_t)nb, d_src, stride, mask,
+    if (kind == BCN_BC7) hipLaunchKernelGGL((refine_judge_kernel<BCN_BC7>), dim3((unsigned)groups), blk, 0, st, d_tgt, bx, (int32_t)nb, d_src, stride, mask,
                                       (unsigned long long)budget, d_map, d_tier, group_count, acc);
-    else           hipLaunchKernelGGL((refine_judge_kernel<6>), dim3((unsigned)groups), blk, 0, st, d_tgt, bx, (int32_t)nb, d_src, stride, mask,
+    else           hipLaunchKernelGGL((refine_judge_kernel<BCN_BC6H>), dim3((unsigned)groups), blk, 0, st, d_tgt, bx, (int32_t)nb, d_src, stride, mask,
                                       (unsigned long long)budget, d_map, d_tier, group_count, acc);
     ITW_CHECK(hipGetLastError());
     hipLaunchKernelGGL(refine_scan_kernel, dim3(1), blk, 0, st, group_count, groups, group_first, acc);
@@ -334,13 +333,13 @@ void refine(int kind, const rgba_surface& s, uint8_t* target, int dxgi_format, c
         hipLaunchKernelGGL(refine_list_kernel, dim3((unsigned)groups), blk, 0, st, d_map, (int32_t)nb, (unsigned long long)budget, group_first, list);
         ITW_CHECK(hipGetLastError());
         const dim3 ggrid((unsigned)((total + 63) / 64));
-        if (kind == 7) hipLaunchKernelGGL((refine_gather_kernel<4>), ggrid, blk, 0, st, list, (int32_t)n, total, pbx, d_src, stride, bx, packed, pitch);
+        if (kind == BCN_BC7) hipLaunchKernelGGL((refine_gather_kernel<4>), ggrid, blk, 0, st, list, (int32_t)n, total, pbx, d_src, stride, bx, packed, pitch);
         else           hipLaunchKernelGGL((refine_gather_kernel<8>), ggrid, blk, 0, st, list, (int32_t)n, total, pbx, d_src, stride, bx, packed, pitch);
         ITW_CHECK(hipGetLastError());
         encode_resident(dxgi_format, second, packed, pitch, pbx * 4, pby * 4, refined);
         const dim3 cgrid((unsigned)((n + 255) / 256));
-        if (kind == 7) hipLaunchKernelGGL((refine_commit_kernel<7>), cgrid, blk, 0, st, list, (int32_t)n, pbx, packed, pitch, refined, mask, d_tgt, d_map, d_tier, acc);
-        else           hipLaunchKernelGGL((refine_commit_kernel<6>), cgrid, blk, 0, st, list, (int32_t)n, pbx, packed, pitch, refined, mask, d_tgt, d_map, d_tier, acc);
+        if (kind == BCN_BC7) hipLaunchKernelGGL((refine_commit_kernel<BCN_BC7>), cgrid, blk, 0, st, list, (int32_t)n, pbx, packed, pitch, refined, mask, d_tgt, d_map, d_tier, acc);
+        else           hipLaunchKernelGGL((refine_commit_kernel<BCN_BC6H>), cgrid, blk, 0, st, list, (int32_t)n, pbx, packed, pitch, refined, mask, d_tgt, d_map, d_tier, acc);
         ITW_CHECK(hipGetLastError());
     }
     hipLaunchKernelGGL(refine_finish_kernel, dim3(1), dim3(64), 0, st, acc, (unsigned long long)nb, d_stats);
@@ -363,9 +362,8 @@ extern "C" bool itwCompressImageRefined(const rgba_surface* source, uint8_t* tar
     itw::clear_failure();
     return itw::guarded([&] {
         // the checks that need no device
-        const int kind = (dxgi_format == ITW_DXGI_FORMAT_BC7_UNORM || dxgi_format == ITW_DXGI_FORMAT_BC7_UNORM_SRGB) ? 7
-                       : (dxgi_format == ITW_DXGI_FORMAT_BC6H_UF16 || dxgi_format == ITW_DXGI_FORMAT_BC6H_SF16) ? 6 : 0;
-        if (!kind) itw::fail_msg("itwCompressImageRefined: DXGI format %d has one encoder only (BC7 and BC6H have presets to refine with)", dxgi_format);
+        const int kind = itw::decode_kind(dxgi_format);
+        if (kind != itw::BCN_BC7 && kind != itw::BCN_BC6H) itw::fail_msg("itwCompressImageRefined: DXGI format %d has one encoder only (BC7 and BC6H have presets to refine with)", dxgi_format);
         if (!source || !source->ptr || !target) itw::fail_msg("itwCompressImageRefined: null surface, texel or target pointer");
         if (!first_settings || !refine_settings) itw::fail_msg("itwCompressImageRefined: null settings for the %s tier", first_settings ? "refine" : "first");
         if (!stats) itw::fail_msg("itwCompressImageRefined: null stats");
@@ -375,7 +373,7 @@ extern "C" bool itwCompressImageRefined(const rgba_surface* source, uint8_t* tar
         if (channel_mask == 0 || channel_mask > 15) itw::fail_msg("itwCompressImageRefined: channel mask %u (1..15: bit 0 = R .. bit 3 = A)", channel_mask);
         if (source->width < 4 || source->height < 4 || (source->width & 3) || (source->height & 3))
             itw::fail_msg("itwCompressImageRefined: %d x %d: width and height must be multiples of 4 (itwPadToMultipleOf4)", source->width, source->height);
-        const int64_t row = (int64_t)source->width * (kind == 6 ? 8 : 4);
+        const int64_t row = (int64_t)source->width * itw::texel_bytes(kind);
         if ((int64_t)source->stride < row) itw::fail_msg("itwCompressImageRefined: stride %d < %lld bytes per row", source->stride, (long long)row);
         if ((int64_t)(source->width / 4) * (source->height / 4) > (int64_t)ITW_MEASURE_MAX_BLOCKS)
             itw::fail_msg("itwCompressImageRefined: %d x %d is more than %lld blocks", source->width, source->height, (long long)ITW_MEASURE_MAX_BLOCKS);

@@ -6,7 +6,7 @@
  * Windows SDK's DirectXMath).  Used by tests/test_reference_codecs.py:
  *   * D3DXDecodeBC1 / BC3 / BC4U / BC5U / BC6HU / BC7 (BC.cpp:327-, BC4BC5.cpp:373-, BC6HBC7.cpp:2790-) decode the streams
  *     this project's encoders emit -- the reference's reading of every block, against the from-spec decoders in oracle/ and
- *     csrc/decode.hip;
+ *     csrc/decode_core.hpp;
  *   * D3DXEncodeBC4U / BC5U (BC4BC5.cpp:403, 481) -- the encoder the plugin itself calls for these two formats
  *     (IntelPlugin.cpp:271-273) -- against oracle/bc4_bc5.c and csrc/bc4_bc5.hip.
  */

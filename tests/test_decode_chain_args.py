@@ -1,4 +1,5 @@
-"""The argument checks of itwDecodeChain / itwDecodeImage (include/itw_decode.h) and itwDdsImage (include/itw_dds.h): host-only, no GPU needed.
+"""The argument checks of itwDecodeChain / itwDecodeImage / itwDecodeBlocks (include/itw_decode.h) and itwDdsImage (include/itw_dds.h):
+host-only, no GPU needed.
 
 A refused call returns -1 BEFORE any device work, on a box without a GPU as on one with it; count == 0 returns 0.  (The one refusal
 that needs a device pointer to state -- mixed host and device outputs -- is in tests/test_gpu_decode_chain.py.)"""
@@ -59,6 +60,63 @@ def test_unknown_and_refused_formats(itw, fmt):
     assert L.itwDecodeChain(fmt, blocks.ctypes.data, _arr(itw, good), 1, None, None) == -1
     assert L.itwDecodeChain(fmt, blocks.ctypes.data, _arr(itw, good), 0, None, None) == -1        # the format is checked first
     assert L.itwDecodeImage(fmt, blocks.ctypes.data, _arr(itw, good), None, None) == -1
+
+
+# ---- itwDecodeBlocks: its own rules, all before any device work --------------------------------------------------------------------
+
+WHOLE_BLOCKS = (71, 77, 95, 96, 98)                              # width and height must be multiples of 4
+PARTIAL_BLOCKS = (80, 81, 83, 84)                                # BC4 / BC5, UNORM and SNORM: any size >= 1
+
+
+def _decode_blocks(itw, fmt, w, h, stride, texels, blocks):
+    return itw.lib().itwDecodeBlocks(fmt, blocks.ctypes.data, w, h, texels.ctypes.data, stride, None)
+
+
+@pytest.mark.parametrize("fmt", WHOLE_BLOCKS + PARTIAL_BLOCKS + (72, 78, 99))
+def test_decode_blocks_refuses_a_bad_stride(itw, fmt):
+    px = 8 if fmt in (95, 96) else 4
+    texels, blocks = np.zeros(16 * 16 * px, dtype=np.uint8), np.zeros(256, dtype=np.uint8)
+    for stride, what in ((8 * px + 2, "not a multiple of 4"), (8 * px + 1, "odd"), (8 * px - 4, "below the row"), (0, "zero"),
+                         (-8 * px, "negative"), (4, "one texel"), (2 ** 31, "more than an rgba_surface's stride holds")):
+        assert _decode_blocks(itw, fmt, 8, 8, stride, texels, blocks) == -1, (fmt, what)
+    assert not texels.any()
+
+
+@pytest.mark.parametrize("fmt", WHOLE_BLOCKS)
+def test_decode_blocks_refuses_partial_blocks_where_the_format_has_none(itw, fmt):
+    px = 8 if fmt in (95, 96) else 4
+    texels, blocks = np.zeros(16 * 16 * px, dtype=np.uint8), np.zeros(256, dtype=np.uint8)
+    for w, h in ((6, 8), (8, 6), (0, 4), (4, 0), (3, 3), (-4, 4)):
+        assert _decode_blocks(itw, fmt, w, h, 16 * px, texels, blocks) == -1, (fmt, w, h)
+    assert not texels.any()
+
+
+@pytest.mark.parametrize("fmt", WHOLE_BLOCKS + PARTIAL_BLOCKS)
+def test_decode_blocks_refuses_more_blocks_than_one_launch_covers(itw, fmt):
+    """46341^2 blocks > 2^31 - 1: refused, where the (int32_t) cast of the block count used to truncate.  The refusal comes before any
+    pointer is looked at; the largest image that passes (46340^2 blocks, 128 GiB of RGBA8) is not something a test decodes."""
+    px = 8 if fmt in (95, 96) else 4
+    texels, blocks = np.zeros(64, dtype=np.uint8), np.zeros(64, dtype=np.uint8)
+    side = 4 * 46341
+    assert (side // 4) ** 2 > 2 ** 31 - 1 > (side // 4 - 1) ** 2 and side * px < 2 ** 31
+    assert _decode_blocks(itw, fmt, side, side, side * px, texels, blocks) == -1
+    assert not texels.any()
+
+
+@pytest.mark.parametrize("fmt", PARTIAL_BLOCKS)
+def test_decode_blocks_refuses_an_empty_surface(itw, fmt):
+    texels, blocks = np.zeros(16 * 16 * 4, dtype=np.uint8), np.zeros(256, dtype=np.uint8)
+    for w, h in ((0, 4), (4, 0), (-1, 4), (4, -1)):
+        assert _decode_blocks(itw, fmt, w, h, 64, texels, blocks) == -1, (fmt, w, h)
+    assert not texels.any()
+
+
+@pytest.mark.parametrize("fmt", [0, 28, 70, 73, 74, 82, 94, 97, 100, -1])
+def test_decode_blocks_refuses_an_unknown_format(itw, fmt):
+    """(96, BC6H_SF16, is not among them: itwDecodeBlocks reads it as unsigned -- tests/test_gpu_decode_unified.py.)"""
+    texels, blocks = np.zeros(8 * 8 * 8, dtype=np.uint8), np.zeros(64, dtype=np.uint8)
+    assert _decode_blocks(itw, fmt, 8, 8, 64, texels, blocks) == -1
+    assert not texels.any()
 
 
 def _image(itw, d, i):

@@ -39,3 +39,37 @@ def test_a_captured_call_replays_to_the_eager_bytes(itw, gpu, fmt, prof, h, w):
         torch.cuda.synchronize()
         assert torch.equal(out, want), (fmt, prof, replays)
     assert itw.last_error() is None
+
+
+def test_a_captured_decode_replays_to_the_eager_texels(itw, gpu):
+    """itwDecodeBlocks with `blocks`, `out` and `modes` on the device is one kernel launch on the caller's stream -- a graph of one node,
+    a straight chain: it allocates nothing and touches no buffer of the thread.  64 x 64 bc7, captured once, replayed twice into a
+    re-poisoned output; both replays give the eager call's texels and modes (which tests/test_gpu_decode_sweep.py pins to the oracle)."""
+    import torch
+    import _block_sweep as sweep
+    blocks, _, _ = sweep.bc7()
+    d = torch.from_numpy(np.ascontiguousarray(blocks[-256 * 16:])).to(gpu)     # the stream's tail: mode 7, the reserved blocks, mode 0
+    want, want_modes = itw.decode("bc7", d, 64, 64, want_modes=True)
+    torch.cuda.synchronize()
+    assert len(set(want_modes.cpu().tolist())) > 2
+    out = torch.zeros_like(want)
+    modes = torch.zeros_like(want_modes)
+    L = itw.lib()
+    side = torch.cuda.Stream()
+
+    def call():
+        L.itwSetStream(torch.cuda.current_stream(gpu).cuda_stream)
+        assert L.itwDecodeBlocks(itw.DXGI_FORMAT["bc7"], d.data_ptr(), 64, 64, out.data_ptr(), 64 * 4, modes.data_ptr()) == 0
+
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, stream=side):
+        call()
+    torch.cuda.synchronize()
+    for _ in range(2):
+        out.fill_(0x5A)
+        modes.fill_(99)
+        torch.cuda.synchronize()
+        g.replay()
+        torch.cuda.synchronize()
+        assert torch.equal(out, want) and torch.equal(modes, want_modes)
+    assert itw.last_error() is None

@@ -200,7 +200,7 @@ def test_gpu_bc45_encoder_equals_the_reference_encoder(dxtex, itw, gpu, fmt, nch
 
 @pytest.mark.gpu
 def test_gpu_decoders_equal_the_reference_decoders(dxtex, itw, gpu, golden_inputs, golden_blocks):
-    """csrc/decode.hip against D3DXDecodeBC7 / BC6HU compiled from the reference, directly."""
+    """csrc/decode_core.hpp against D3DXDecodeBC7 / BC6HU compiled from the reference, directly."""
     for image, fmt, prof, kind in (("monkey", "bc7", "alpha_slow", 7), ("monkey_hdr", "bc6h", "slow", 6)):
         img = golden_inputs[image]
         h, w = img.shape[0] // 4 * 4, img.shape[1] // 4 * 4

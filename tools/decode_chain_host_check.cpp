@@ -1,6 +1,6 @@
-// decode_chain_host_check.cpp -- the host code behind itwDecodeChain and itwDdsImage that needs no device, as a stand-alone program for a
-// sanitizer run: the argument checks and the descriptor / staging layout (csrc/decode_chain_host.hpp) and the DDS payload walk (csrc/dds.hip,
-// host-only, compiled as C++).  Build and run from the repository root:
+// decode_chain_host_check.cpp -- the host code behind itwDecodeChain, itwDecodeBlocks and itwDdsImage that needs no device, as a stand-alone
+// program for a sanitizer run: the format table (csrc/bcn_format.hpp), the argument checks and the descriptor / staging layout
+// (csrc/decode_chain_host.hpp) and the DDS payload walk (csrc/dds.hip, host-only, compiled as C++).  Build and run from the repository root:
 //   g++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all -Iinclude tools/decode_chain_host_check.cpp \
 //       -x c++ intel-texture-works-plugin_amd/csrc/dds.hip -o /tmp/decode_chain_host_check && /tmp/decode_chain_host_check
 // Prints "ok <checks>" and exits 0, or names the first check that failed.  Not covered: everything behind the checks that talks to the
@@ -22,11 +22,16 @@ int main()
     uint8_t *p = texels.data(), *b = blocks.data();
 
     for (int f : formats) {
-        const int kind = decode_chain_kind(f);
-        CHECK(kind != 0);
-        const int px = decode_chain_texel_bytes(kind);
+        const int kind = decode_kind(f);
+        CHECK(kind != BCN_NONE);
+        int seen = 0;
+        with_kind(kind, [&](auto K) { seen = K.value; });
+        CHECK(seen == kind);
+        const int px = texel_bytes(kind);
         CHECK(px == (f == 95 ? 8 : 4));
-        CHECK(decode_chain_block_bytes(kind) == (int)itwDdsLevelBytes((uint32_t)f, 4, 4));
+        CHECK(block_bytes(kind) == (int)itwDdsLevelBytes((uint32_t)f, 4, 4));
+        CHECK(keeps_partial_blocks(kind) == (f == 80 || f == 81 || f == 83 || f == 84));
+        CHECK(filled_alpha(kind) == (f == 80 || f == 83 ? 255 : f == 81 || f == 84 ? 127 : f == 95 ? 0x3C00 : -1));
         const rgba_surface good{p, 8, 8, 8 * px};
         CHECK(decode_chain_check(kind, b, &good, 1) == 4);
         CHECK(decode_chain_check(kind, b, &good, 0) == 0);
@@ -72,24 +77,46 @@ int main()
                 } else {
                     CHECK(d.ptr == chain[(size_t)i].ptr && d.stride == chain[(size_t)i].stride);
                 }
-                first += decode_chain_blocks(chain[(size_t)i]);
+                first += image_blocks(chain[(size_t)i]);
             }
             CHECK(first == total);
             if (staged) {
                 CHECK(end == L.bytes);
-                CHECK(L.modes >= L.blocks + (size_t)total * (size_t)decode_chain_block_bytes(kind) && L.min_alpha >= L.modes + (size_t)total * 4);
+                CHECK(L.modes >= L.blocks + (size_t)total * (size_t)block_bytes(kind) && L.min_alpha >= L.modes + (size_t)total * 4);
                 CHECK(L.texels >= L.min_alpha + (size_t)n * 4);
             } else {
                 CHECK(L.bytes == decode_chain_up((size_t)n * sizeof(DecodeImage)));
             }
         }
+
+        // itwDecodeBlocks' rules: whole blocks unless the format keeps partial ones; a stride that is a multiple of 4, at least the row, an int32
+        const bool partial = keeps_partial_blocks(kind);
+        CHECK(decode_blocks_check(kind, 8, 8, 8 * px) == 4 && decode_blocks_check(kind, 8, 8, 8 * px + 4) == 4);
+        CHECK(decode_blocks_check(kind, 8, 8, 8 * px + 2) == -1 && decode_blocks_check(kind, 8, 8, 8 * px - 4) == -1);
+        CHECK(decode_blocks_check(kind, 8, 8, 0) == -1 && decode_blocks_check(kind, 8, 8, -8 * px) == -1);
+        CHECK(decode_blocks_check(kind, 8, 8, (int64_t)INT32_MAX - 3) == 4 && decode_blocks_check(kind, 8, 8, (int64_t)INT32_MAX + 1) == -1);
+        CHECK(decode_blocks_check(kind, 6, 8, 8 * px) == (partial ? 4 : -1) && decode_blocks_check(kind, 8, 6, 8 * px) == (partial ? 4 : -1));
+        CHECK(decode_blocks_check(kind, 5, 7, 8 * px) == (partial ? 4 : -1) && decode_blocks_check(kind, 1, 1, 8 * px) == (partial ? 1 : -1));
+        CHECK(decode_blocks_check(kind, 0, 4, 8 * px) == -1 && decode_blocks_check(kind, 4, 0, 8 * px) == -1 && decode_blocks_check(kind, -4, 4, 8 * px) == -1);
+        // no ITW_MEASURE_MAX_BLOCKS cap here: the image the chain entry points refuse passes (8193 x 4096 blocks; only the arithmetic runs)
+        CHECK(decode_blocks_check(kind, 32772, 16384, 32772 * (int64_t)px) == (int64_t)8193 * 4096);
+        // and the bound of one launch, 2^31 - 1 blocks: 46340^2 is the largest square below it
+        CHECK(decode_blocks_check(kind, 4 * 46340, 4 * 46340, 4 * 46340 * (int64_t)px) == (int64_t)46340 * 46340);
+        CHECK(decode_blocks_check(kind, 4 * 46341, 4 * 46341, 4 * 46341 * (int64_t)px) == -1);
     }
-    const int refused[] = {96, 0, 28, 70, 73, 74, 82, 94, 97, 100, -1};
+    CHECK(DECODE_IMAGE_MAX_BLOCKS == 0x7fffffff && image_blocks(rgba_surface{nullptr, INT32_MAX, INT32_MAX, 0}) == ((int64_t)1 << 29) * ((int64_t)1 << 29));
+    CHECK(decode_kind(96) == BCN_BC6H && decode_kind(72) == BCN_BC1 && decode_kind(78) == BCN_BC3 && decode_kind(99) == BCN_BC7);
+    CHECK(decode_blocks_check(decode_kind(96), 8, 8, 64) == 4);      // itwDecodeBlocks reads BC6H_SF16 as unsigned; the chain entry points refuse it
+    const int refused[] = {0, 28, 70, 73, 74, 82, 94, 97, 100, -1};
     for (int f : refused) {
         const rgba_surface good{p, 8, 8, 64};
-        CHECK(decode_chain_kind(f) == 0);
-        CHECK(decode_chain_check(decode_chain_kind(f), b, &good, 1) == -1);
-        CHECK(decode_chain_check(decode_chain_kind(f), b, &good, 0) == -1);
+        CHECK(decode_kind(f) == BCN_NONE);
+        CHECK(decode_chain_check(decode_kind(f), b, &good, 1) == -1);
+        CHECK(decode_chain_check(decode_kind(f), b, &good, 0) == -1);
+        CHECK(decode_blocks_check(decode_kind(f), 8, 8, 64) == -1);
+        int calls = 0;
+        with_kind(decode_kind(f), [&](auto) { calls++; });
+        CHECK(calls == 0);
     }
 
     // itwDdsImage: running sums over 2D, mipped, cube and array descriptions

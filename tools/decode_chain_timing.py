@@ -1,21 +1,23 @@
-"""What decoding a whole file in one call costs (itwDecodeChain / itwDecodeImage) against a loop of itwDecodeBlocks, for bc1, bc7 and bc6h,
-device-resident and from host memory.
+"""What decoding costs through the three entry points (itwDecodeChain, itwDecodeImage, itwDecodeBlocks) against the PARENT commit's
+itwDecodeBlocks, device-resident and from host memory.  All three run one kernel (csrc/decode_chain.hip); the parent's library, built from
+the commit before, is the yardstick and is always needed: --parent-lib=PATH.
 
 Legs, per format and pointer kind, in ONE run, the variants alternating within each repetition:
-  (a) cube    a 1024^2 cube map with mips down to 4x4 (6 x 9 = 54 images, all multiples of 4, so itwDecodeBlocks can decode it):
+  (a) cube    bc1, bc7, bc6h: a 1024^2 cube map with mips down to 4x4 (6 x 9 = 54 images, all multiples of 4, so itwDecodeBlocks can decode it):
                 blocks_loop   one itwDecodeBlocks per image, this build
                 chain         one itwDecodeChain, this build
-                parent_loop   the same loop through the PARENT commit's library (--parent-lib=PATH): the yardstick
-  (b) single  one 4096^2 image:  blocks (itwDecodeBlocks, this build), image (itwDecodeImage), parent_blocks (the parent's itwDecodeBlocks)
-The streams are this library's own encodes of the bench surface (bc7 veryfast, bc6h fast) and its 2x2-mean mips, so the waves see the
-mode mix of real content.  Timing: a host clock around `inner` calls, each followed by a stream synchronise, after a warm-up of every
-variant; best, median and (max - min) / min spread of `reps` repetitions.
-Required, and judged here: (a) chain is faster than parent_loop (medians) for every format and pointer kind -- the tool exits 1 otherwise;
-(b) image is not slower than parent_blocks by more than parent_blocks' own min-max spread (recorded as b_within_parent_spread).
-Recorded, not judged: hbm_fraction of (b) device-resident = (stream + texels) bytes / median time / 8 TB/s.
-Without --parent-lib the parent legs are this build's itwDecodeBlocks (whose code no later commit may change) and the row says so.
+                parent_loop   the same loop through the parent's library
+  (b) single  every format (bc1, bc3, bc4, bc5, bc4_snorm, bc5_snorm, bc7, bc6h), one 4096^2 image:
+                blocks (itwDecodeBlocks, this build), image (itwDecodeImage), parent_blocks (the parent's itwDecodeBlocks)
+The streams are this library's own encodes of the bench surface (bc7 veryfast, bc6h fast; a normal map for the SNORM pair) and its
+2x2-mean mips, so the waves see the mode mix of real content.  Timing: a host clock around `inner` calls, each followed by a stream
+synchronise, after a warm-up of every variant; best, median and (max - min) / min spread of `reps` repetitions.
+Required, and judged here: (a) chain is faster than parent_loop (medians) for every format and pointer kind -- the tool exits 1 otherwise.
+Recorded for the reader to judge: (b) neither blocks nor image is slower than parent_blocks, by medians, by more than parent_blocks' own
+min-max spread (blocks_within_parent_spread, b_within_parent_spread); hbm_fraction of (b) device-resident = (stream + texels) bytes /
+median time / 8 TB/s.
 One JSON object per line (stdout, and appended to profiles/decode_chain_timing.jsonl unless --no-save).
-Usage: python tools/decode_chain_timing.py [reps] [inner] [--parent-lib=PATH] [--no-save] [--out=PATH]"""
+Usage: python tools/decode_chain_timing.py --parent-lib=PATH [reps] [inner] [--no-save] [--out=PATH]"""
 import ctypes as C
 import json
 import os
@@ -28,12 +30,19 @@ import numpy as np                      # noqa: E402
 import itw_amd                          # noqa: E402
 from itw_amd import surfaces           # noqa: E402
 
-FORMATS = [("bc1", None), ("bc7", "veryfast"), ("bc6h", "fast")]
+FORMATS = [("bc1", None, True), ("bc7", "veryfast", True), ("bc6h", "fast", True),                  # (format, profile, has a cube leg)
+           ("bc3", None, False), ("bc4", None, False), ("bc5", None, False), ("bc4_snorm", None, False), ("bc5_snorm", None, False)]
 HBM_BYTES_PER_S = 8e12
 
 
+_sources = {}
+
+
 def _source(fmt, size):
-    return surfaces.hdr_smooth(size, size, seed=surfaces.SEED + 3) if fmt == "bc6h" else surfaces.ldr_smooth(size, size, seed=surfaces.SEED)
+    gen = surfaces.hdr_smooth if fmt == "bc6h" else surfaces.snorm_normal_map if fmt in itw_amd.SIGNED_FORMATS else surfaces.ldr_smooth
+    if (gen, size) not in _sources:
+        _sources[(gen, size)] = gen(size, size)
+    return _sources[(gen, size)]
 
 
 def _bind(L):
@@ -52,14 +61,16 @@ def main():
     save = "--no-save" not in sys.argv
     out_path = next((a[6:] for a in sys.argv if a.startswith("--out=")), os.path.join(ROOT, "profiles", "decode_chain_timing.jsonl"))
     parent_path = next((a[13:] for a in sys.argv if a.startswith("--parent-lib=")), None)
+    if not parent_path:
+        sys.exit("--parent-lib=PATH is required: the parent commit's libispc_texcomp.so is what every leg is measured against")
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
     L = itw_amd.lib()
-    P = _bind(C.CDLL(parent_path)) if parent_path else L
+    P = _bind(C.CDLL(parent_path))
     stream = torch.cuda.current_stream(dev).cuda_stream
     L.itwSetStream(stream)
     P.itwSetStream(stream)
-    parent_note = os.path.basename(parent_path) + " built from the parent commit" if parent_path else "not given: this build's unchanged itwDecodeBlocks"
+    parent_note = os.path.basename(parent_path) + " built from the parent commit"
 
     def timed(fn):
         torch.cuda.synchronize()
@@ -84,36 +95,39 @@ def main():
         return out
 
     rows, failed = [], []
-    for fmt, profile in FORMATS:
+    for fmt, profile, cube in FORMATS:
         key = itw_amd.DXGI_FORMAT[fmt]
         px, bpb = (8 if fmt == "bc6h" else 4), itw_amd.BYTES_PER_BLOCK[fmt]
-        tdtype = torch.int16 if fmt == "bc6h" else torch.uint8
-        ndtype = np.uint16 if fmt == "bc6h" else np.uint8
+        signed = fmt in itw_amd.SIGNED_FORMATS
+        tdtype = torch.int16 if fmt == "bc6h" else torch.int8 if signed else torch.uint8
+        ndtype = np.uint16 if fmt == "bc6h" else np.int8 if signed else np.uint8
 
         # the streams: a face's chain 1024 .. 4, six times; one 4096^2 image
-        levels = [lv for lv in itw_amd.mip_chain(_source(fmt, 1024)) if lv.shape[0] >= 4]
-        face = [torch.from_numpy(lv.view(np.int16) if fmt == "bc6h" else lv).to(dev) for lv in levels]
-        ok, cube_blocks = itw_amd.compress_chain(fmt, face * 6, profile=profile)
-        assert ok
+        sizes, offs, cube_blocks = [], [0], None
+        if cube:
+            levels = [lv for lv in itw_amd.mip_chain(_source(fmt, 1024)) if lv.shape[0] >= 4]
+            face = [torch.from_numpy(lv.view(np.int16) if fmt == "bc6h" else lv).to(dev) for lv in levels]
+            ok, cube_blocks = itw_amd.compress_chain(fmt, face * 6, profile=profile)
+            assert ok
+            sizes = [tuple(lv.shape[:2]) for lv in levels] * 6
+            assert len(sizes) == 54
+            offs = np.concatenate([[0], np.cumsum([(h // 4) * (w // 4) * bpb for h, w in sizes])]).tolist()
         big = _source(fmt, 4096)
         big_blocks = itw_amd.compress(fmt, torch.from_numpy(big.view(np.int16) if fmt == "bc6h" else big).to(dev), profile)
         torch.cuda.synchronize()
-        sizes = [tuple(lv.shape[:2]) for lv in levels] * 6
-        assert len(sizes) == 54
-        offs = np.concatenate([[0], np.cumsum([(h // 4) * (w // 4) * bpb for h, w in sizes])]).tolist()
 
         for kind in ("device", "host"):
             if kind == "device":
-                blocks, single = cube_blocks, big_blocks
+                blocks, single = cube_blocks if cube else big_blocks, big_blocks
                 outs = [torch.empty((h, w, 4), dtype=tdtype, device=dev) for h, w in sizes]
                 one = torch.empty((4096, 4096, 4), dtype=tdtype, device=dev)
                 ptr = lambda t: t.data_ptr()                     # noqa: E731
             else:
-                blocks, single = cube_blocks.cpu().numpy(), big_blocks.cpu().numpy()
+                blocks, single = (cube_blocks if cube else big_blocks).cpu().numpy(), big_blocks.cpu().numpy()
                 outs = [np.empty((h, w, 4), dtype=ndtype) for h, w in sizes]
                 one = np.empty((4096, 4096, 4), dtype=ndtype)
                 ptr = lambda a: a.ctypes.data                    # noqa: E731
-            surfs = (itw_amd.RgbaSurface * 54)(*[itw_amd.RgbaSurface(ptr(o), w, h, w * px) for o, (h, w) in zip(outs, sizes)])
+            surfs = (itw_amd.RgbaSurface * len(sizes))(*[itw_amd.RgbaSurface(ptr(o), w, h, w * px) for o, (h, w) in zip(outs, sizes)])
             one_surf = itw_amd.RgbaSurface(ptr(one), 4096, 4096, 4096 * px)
             bp, sp, optrs = ptr(blocks), ptr(single), [ptr(o) for o in outs]
 
@@ -132,35 +146,49 @@ def main():
             def image():
                 assert L.itwDecodeImage(key, sp, C.byref(one_surf), None, None) == 0
 
-            # what the legs time is one decode: the chain call writes what the loop writes
-            loop(L)()
-            torch.cuda.synchronize()
-            want = [o.clone() if kind == "device" else o.copy() for o in outs]
-            for o in outs:
-                o.zero_() if kind == "device" else o.fill(0)
-            chain()
-            torch.cuda.synchronize()
-            same = all((torch.equal(a, b) if kind == "device" else np.array_equal(a, b)) for a, b in zip(outs, want))
-            assert same, (fmt, kind, "itwDecodeChain and the itwDecodeBlocks loop disagree")
-
-            a = run({"blocks_loop": loop(L), "chain": chain, "parent_loop": loop(P)})
-            b = run({"blocks": blocks_of(L), "image": image, "parent_blocks": blocks_of(P)})
             base = {"format": fmt, "pointers": kind, "reps": reps, "inner": inner, "parent": parent_note,
                     "timing": "host clock around calls that each end in a stream synchronise", "device": itw_amd.device_info()}
-            ra = dict(base, leg="a_cube_1024_mips_to_4", images=54, blocks=offs[-1] // bpb, variants=a,
-                      chain_vs_parent_loop=round(a["chain"]["median_ms"] / a["parent_loop"]["median_ms"], 4),
-                      a_faster_than_parent=a["chain"]["median_ms"] < a["parent_loop"]["median_ms"])
+            found = []
+            if cube:
+                # what the legs time is one decode: the chain call writes what the loop writes
+                loop(L)()
+                torch.cuda.synchronize()
+                want = [o.clone() if kind == "device" else o.copy() for o in outs]
+                for o in outs:
+                    o.zero_() if kind == "device" else o.fill(0)
+                chain()
+                torch.cuda.synchronize()
+                same = all((torch.equal(a, b) if kind == "device" else np.array_equal(a, b)) for a, b in zip(outs, want))
+                assert same, (fmt, kind, "itwDecodeChain and the itwDecodeBlocks loop disagree")
+
+                a = run({"blocks_loop": loop(L), "chain": chain, "parent_loop": loop(P)})
+                ra = dict(base, leg="a_cube_1024_mips_to_4", images=54, blocks=offs[-1] // bpb, variants=a,
+                          chain_vs_parent_loop=round(a["chain"]["median_ms"] / a["parent_loop"]["median_ms"], 4),
+                          a_faster_than_parent=a["chain"]["median_ms"] < a["parent_loop"]["median_ms"])
+                found.append(ra)
+                if not ra["a_faster_than_parent"]:
+                    failed.append((fmt, kind))
+            # ... and this build's itwDecodeBlocks writes what the parent's writes
+            blocks_of(P)()
+            torch.cuda.synchronize()
+            want_one = one.clone() if kind == "device" else one.copy()
+            one.zero_() if kind == "device" else one.fill(0)
+            blocks_of(L)()
+            torch.cuda.synchronize()
+            assert torch.equal(one, want_one) if kind == "device" else np.array_equal(one, want_one), (fmt, kind, "itwDecodeBlocks differs from the parent's")
+
+            b = run({"blocks": blocks_of(L), "image": image, "parent_blocks": blocks_of(P)})
             pb = b["parent_blocks"]
             rb = dict(base, leg="b_single_4096", images=1, blocks=1024 * 1024, variants=b,
+                      blocks_vs_parent_blocks=round(b["blocks"]["median_ms"] / pb["median_ms"], 4),
+                      blocks_within_parent_spread=b["blocks"]["median_ms"] - pb["median_ms"] <= pb["max_ms"] - pb["ms"],
                       image_vs_parent_blocks=round(b["image"]["median_ms"] / pb["median_ms"], 4),
                       b_within_parent_spread=b["image"]["median_ms"] - pb["median_ms"] <= pb["max_ms"] - pb["ms"])
             if kind == "device":
                 rb["hbm_fraction"] = round((1024 * 1024 * bpb + 4096 * 4096 * px) / (b["image"]["median_ms"] * 1e-3) / HBM_BYTES_PER_S, 4)
-            for r in (ra, rb):
+            for r in found + [rb]:
                 print(json.dumps(r), flush=True)
                 rows.append(r)
-            if not ra["a_faster_than_parent"]:
-                failed.append((fmt, kind))
     if save and rows:
         os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
         with open(out_path, "a") as f:
