@@ -2,13 +2,18 @@
 // raw texels -> pad to multiples of 4 -> CompressImageMT through the slice loop -> .DDS file.  Only include/*.h is used;
 // the program links libispc_texcomp.so like the plugin links ispc_texcomp.lib.
 //
-//   encode_dds [--measure] [--refine <profile> <max_block_sse>] <format> <width> <height> <in.raw> <out.dds> [slice_pixels]
+//   encode_dds [--measure] [--refine <profile> <max_block_sse> | --refine-share <profile> <percent> | --refine-psnr <profile> <dB>]
+//              <format> <width> <height> <in.raw> <out.dds> [slice_pixels]
 //     format : bc1 | bc3 | bc4 | bc5 | bc4_snorm | bc5_snorm | bc7_<profile> | bc6h_<profile>      (profiles: the GetProfile_* names)
 //     in.raw : width*height tightly packed RGBA8 texels (RGBA16F bit patterns for bc6h_*; RGBA8_SNORM, int8 codes, for bc4_snorm / bc5_snorm)
 //     --measure : after encoding, one line on stdout per image: what the stream costs against the source (itwMeasureBlocks)
 //     --refine  : bc7_* / bc6h_* only: encode to an error budget (itwCompressImageRefined) -- <format>'s preset everywhere, then <profile>
 //                 (a preset of the same format: `slow`, `alpha_slow`, ...) on the blocks whose error is above <max_block_sse>, kept where
 //                 it is strictly better; one line on stdout with the call's statistics.  The slice loop is not used.
+//     --refine-share : the same with the budget chosen on the device (itwCompressImageRefinedTo): <profile> on at most <percent> % of
+//                 the blocks, the worst ones, in one round
+//     --refine-psnr  : bc7_* only: <profile> on as many of the worst blocks as it takes to reach <dB> over the format's own channels
+//                 (itwPsnrToTotalSse gives the target), in up to five rounds
 //
 //   encode_dds --decode <in.dds> <out.raw>
 //     the load path (IntelPlugin.cpp:2461-2561): header -> every image of the file through ONE itwDecodeChain -> texels.  out.raw holds
@@ -124,6 +129,8 @@ int main(int argc, char** argv)
     bool measure = false;
     const char* refine_profile = nullptr;
     unsigned long long max_block_sse = 0;
+    int refine_to = 0;                                          // 1: --refine-share, 2: --refine-psnr
+    double refine_value = 0.0;                                  // percent / dB
     for (int i = 1; i < argc; i++)
         if (std::strcmp(argv[i], "--measure") == 0) {
             measure = true;
@@ -134,9 +141,16 @@ int main(int argc, char** argv)
             max_block_sse = std::strtoull(argv[i + 2], nullptr, 10);
             for (int k = i; k + 3 < argc; k++) argv[k] = argv[k + 3];
             argc -= 3; i--;
+        } else if ((std::strcmp(argv[i], "--refine-share") == 0 || std::strcmp(argv[i], "--refine-psnr") == 0) && i + 2 < argc) {
+            refine_to = std::strcmp(argv[i], "--refine-share") == 0 ? 1 : 2;
+            refine_profile = argv[i + 1];
+            refine_value = std::atof(argv[i + 2]);
+            for (int k = i; k + 3 < argc; k++) argv[k] = argv[k + 3];
+            argc -= 3; i--;
         }
     if (argc < 6) {
-        std::fprintf(stderr, "usage: %s [--measure] [--refine <profile> <max_block_sse>] <format> <width> <height> <in.raw> <out.dds> [slice_pixels]\n"
+        std::fprintf(stderr, "usage: %s [--measure] [--refine <profile> <max_block_sse> | --refine-share <profile> <percent> | --refine-psnr <profile> <dB>]\n"
+                             "          <format> <width> <height> <in.raw> <out.dds> [slice_pixels]\n"
                              "       %s --decode <in.dds> <out.raw>\n", argv[0], argv[0]);
         return 2;
     }
@@ -168,11 +182,34 @@ int main(int argc, char** argv)
         }
         itw_refine_stats rs;
         itwSetErrorMode(ITW_ON_ERROR_RETURN);
-        ok = itwCompressImageRefined(&padded, blocks.data(), f->dxgi, &first, &second, f->own_channels, max_block_sse, &rs, sizeof rs, nullptr, nullptr);
-        if (!ok) std::fprintf(stderr, "%s\n", itwLastError() ? itwLastError() : "itwCompressImageRefined failed");
-        else std::printf("refined: %s -> %s budget %llu blocks %llu listed %llu replaced %llu sse %llu -> %llu worst %llu -> %llu\n", f->name, refine_profile,
-                         max_block_sse, (unsigned long long)rs.blocks, (unsigned long long)rs.listed, (unsigned long long)rs.replaced,
-                         (unsigned long long)rs.sse_first, (unsigned long long)rs.sse_final, (unsigned long long)rs.worst_first, (unsigned long long)rs.worst_final);
+        if (refine_to) {
+            const unsigned long long nb = (unsigned long long)(padded.width / 4) * (unsigned long long)(padded.height / 4);
+            itw_refine_policy pol = { UINT64_MAX, UINT64_MAX };
+            if (refine_to == 1) {
+                if (!(refine_value >= 0.0 && refine_value <= 100.0)) { std::fprintf(stderr, "--refine-share: a percentage, 0..100\n"); return 2; }
+                pol.max_listed = (uint64_t)(refine_value / 100.0 * (double)nb);
+            } else {
+                pol.target_total_sse = itwPsnrToTotalSse(f->dxgi, width, height, f->own_channels, refine_value);
+                if (pol.target_total_sse == UINT64_MAX) { std::fprintf(stderr, "--refine-psnr needs a bc7_* format and a finite dB\n"); return 2; }
+            }
+            itw_refine_target_stats ts;
+            ok = itwCompressImageRefinedTo(&padded, blocks.data(), f->dxgi, &first, &second, f->own_channels, &pol, sizeof pol, &ts, sizeof ts, nullptr, nullptr);
+            rs = ts.total;
+            if (!ok) std::fprintf(stderr, "%s\n", itwLastError() ? itwLastError() : "itwCompressImageRefinedTo failed");
+            else {
+                std::printf("refined: %s -> %s %s %g rounds %u met %u budgets [%llu, %llu, %llu, %llu, %llu] blocks %llu listed %llu replaced %llu sse %llu -> %llu "
+                            "worst %llu -> %llu\n", f->name, refine_profile, refine_to == 1 ? "share" : "psnr", refine_value, ts.rounds, ts.target_met,
+                            (unsigned long long)ts.budget[0], (unsigned long long)ts.budget[1], (unsigned long long)ts.budget[2], (unsigned long long)ts.budget[3],
+                            (unsigned long long)ts.budget[4], (unsigned long long)rs.blocks, (unsigned long long)rs.listed, (unsigned long long)rs.replaced,
+                            (unsigned long long)rs.sse_first, (unsigned long long)rs.sse_final, (unsigned long long)rs.worst_first, (unsigned long long)rs.worst_final);
+            }
+        } else {
+            ok = itwCompressImageRefined(&padded, blocks.data(), f->dxgi, &first, &second, f->own_channels, max_block_sse, &rs, sizeof rs, nullptr, nullptr);
+            if (!ok) std::fprintf(stderr, "%s\n", itwLastError() ? itwLastError() : "itwCompressImageRefined failed");
+            else std::printf("refined: %s -> %s budget %llu blocks %llu listed %llu replaced %llu sse %llu -> %llu worst %llu -> %llu\n", f->name, refine_profile,
+                             max_block_sse, (unsigned long long)rs.blocks, (unsigned long long)rs.listed, (unsigned long long)rs.replaced,
+                             (unsigned long long)rs.sse_first, (unsigned long long)rs.sse_final, (unsigned long long)rs.worst_first, (unsigned long long)rs.worst_final);
+        }
     } else {
         ok = itwCompressImageSliced(&padded, blocks.data(), pitch, f->fn, f->dxgi, /*multithreaded*/ true,
                                     slice_pixels, slice_pixels ? on_progress : nullptr, nullptr);

@@ -196,6 +196,56 @@ bool itwCompressImageRefined(const rgba_surface* source, uint8_t* target, int dx
                              itw_refine_stats* stats, size_t stats_bytes,
                              uint64_t* block_sse, uint8_t* tier_map);
 
+/* Encode to a number of refined blocks or to a summed error: the device picks the budget.
+ *
+ * itwCompressImageRefinedTo is itwCompressImageRefined for callers who know what they want to spend or reach rather than a per-block
+ * budget, which nobody can know before the first tier has run.  The first tier's error map stays on the device; an exact select over it
+ * gives the budget T, and the rest of a round is itwCompressImageRefined's: list the blocks above T, encode them with `refine_settings`,
+ * keep a second encoding only where it is strictly better.  Formats, source, block error, channel mask, pointer kinds, alignment, scratch
+ * and error mode are itwCompressImageRefined's; the call is synchronous and cannot be captured (the host reads the list length and one
+ * more word per round).
+ *   * select(k) over the CANDIDATES (the blocks still at tier 0): T = the (k+1)-th largest candidate error, counting equal values as
+ *     often as they occur, or 0 when there are at most k candidates -- the smallest T among the candidate errors and 0 that leaves at
+ *     most k candidates above it.  The round lists the candidates with error > T.  So k = 0 lists nothing, a group of equal errors that
+ *     straddles rank k is left off the list as a whole (a round may list fewer than k blocks, never more), and T = 0 lists every candidate
+ *     that is not exact.  Integers only: the same bits on every run.
+ *   * Policy A, target_total_sse == UINT64_MAX: one round with k = max_listed.  `target`, `block_sse`, `tier_map` and `total` are byte
+ *     for byte what itwCompressImageRefined(..., max_block_sse = T, ...) gives; rounds = 1, budget[0] = T, listed[0] = total.listed.
+ *     (max_listed = UINT64_MAX: T = 0, every block that is not exact is listed.)
+ *   * Policy B, a target: up to five rounds j = 0..4.  Before each round the call ends if the stream's summed block error is already
+ *     <= target_total_sse, or if max_listed is used up.  Round j runs select(k_j), k_j = min(max_listed - blocks listed so far, q_j),
+ *     q_j = max(1, blocks >> (4 - j)) for j < 4 and q_4 = blocks: a sixteenth, an eighth, a quarter, a half, then everything.  A block is
+ *     refined at most once (tier_map 1 and 2 are no candidates), so the refine tier encodes at most `blocks` blocks in total; a round that
+ *     lists nothing costs its select only and the next round follows.  Every block of the result is still the reference's block under one
+ *     of the two settings and no block's error is above the first tier's.  An unreachable target runs all five rounds and reports
+ *     target_met = 0.  itwPsnrToTotalSse turns a PSNR into a target.
+ *   * Errors, on top of itwCompressImageRefined's: a null policy or stats, a policy_bytes / stats_bytes other than the sizeof, a misaligned
+ *     stats; before any device work, no device needed. */
+typedef struct itw_refine_policy {
+    uint64_t max_listed;               /* most blocks the refine tier may encode over the whole call; UINT64_MAX = no cap */
+    uint64_t target_total_sse;         /* stop once the stream's summed block error is <= this; UINT64_MAX = single round (policy A) */
+} itw_refine_policy;
+typedef struct itw_refine_target_stats {
+    itw_refine_stats total;            /* as itwCompressImageRefined reports, over the whole call */
+    uint32_t rounds;                   /* refine rounds that ran their select (0..5) */
+    uint32_t target_met;               /* 1 if total.sse_final <= target_total_sse */
+    uint64_t budget[5];                /* T of each round run, else 0 */
+    uint64_t listed[5];                /* blocks listed per round */
+} itw_refine_target_stats;             /* policy_bytes / stats_bytes must be the sizeof */
+
+bool itwCompressImageRefinedTo(const rgba_surface* source, uint8_t* target, int dxgi_format,
+                               const void* first_settings, const void* refine_settings, uint32_t channel_mask,
+                               const itw_refine_policy* policy, size_t policy_bytes,
+                               itw_refine_target_stats* stats, size_t stats_bytes,
+                               uint64_t* block_sse, uint8_t* tier_map);
+
+/* The inverse of itwStatsPsnr (itw_decode.h), host arithmetic in double: the largest summed error at which a width x height image,
+ * measured over the channels of channel_mask, still has at least psnr_db: floor(peak^2 * n / 10^(psnr_db / 10)), n = width * height *
+ * number of selected channels, peak as itwStatsPsnr.  The floor rounds the target DOWN, so a stream that meets it never reports less
+ * than psnr_db.  UINT64_MAX (no target) where itwStatsPsnr has no answer: BC6H or an unknown format, a mask without one of the four
+ * channels, a width or height < 1, a psnr_db that is NaN or infinite; BC6H callers pass a summed error. */
+uint64_t itwPsnrToTotalSse(int dxgi_format, int width, int height, uint32_t channel_mask, double psnr_db);
+
 /* Pad to multiples of 4 by edge replication (IntelPlugin.cpp:893-928): the step immediately before the ABI.
  * pixel_size = 4 (RGBA8) or 8 (RGBA16F).  Host version: returns a surface whose ptr was allocated with malloc()
  * (free with itwFreeSurface); the reference allocates with new[] and leaves ownership to the caller likewise.

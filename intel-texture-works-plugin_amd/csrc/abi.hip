@@ -113,7 +113,7 @@ struct ThreadCtx {
     itw::Bc7Verdict verdict = {nullptr, nullptr, false, nullptr};   // the pilot's estimate of a staged host-pointer call's first run, left for the host (kernels.hpp)
     bool staged_wide = false;                       // what the last staged BC7 call's estimate said (the shape of this call's first run, until its own is in)
     void*  d_refine[2] = {nullptr, nullptr}; size_t refine_cap[2] = {0, 0};   // itwCompressImageRefined (refine.hip): per-surface scratch, per-list scratch
-    uint32_t* refine_count = nullptr;               // ... and the pinned word its list count is read back through
+    uint32_t* refine_count = nullptr;               // ... and the two pinned words its list count (and "target met") are read back through
     void*  d_decode = nullptr; size_t decode_cap = 0;   // itwDecodeChain (decode_chain.hip): descriptor table and, for host pointers, staging
     hipStream_t decode_stream = nullptr; bool decode_used = false;
     hipEvent_t  decode_event = nullptr;             // recorded after each chain decode: orders the table across streams, as ws_event does
@@ -1326,7 +1326,7 @@ uint32_t* refine_count_word()
     bind_thread_to_current_device();
     if (!tls.refine_count) {
         void* h = nullptr;
-        ITW_CHECK(hipHostMalloc(&h, sizeof(uint32_t), hipHostMallocDefault));
+        ITW_CHECK(hipHostMalloc(&h, 2 * sizeof(uint32_t), hipHostMallocDefault));    // the list length; itwCompressImageRefinedTo: and "target met"
         tls.refine_count = static_cast<uint32_t*>(h);
     }
     return tls.refine_count;

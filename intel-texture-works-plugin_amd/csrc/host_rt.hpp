@@ -61,7 +61,7 @@ void chain_check(const rgba_surface* images, int count, const uint8_t* target, i
 // pointer as itwCompressImageChainEx takes them; asynchronous on the thread's stream (itwSetStream).
 void encode_resident(int dxgi_format, const void* settings, const uint8_t* d_src, int64_t stride, int width, int height, uint8_t* d_dst);
 // refine_scratch: the thread's grow-only device scratch `which` (0: sized by the surface, 1: sized by the list), at least `bytes` bytes,
-// 256-B aligned; growing frees the old buffer, which waits for the device.  refine_count_word: the thread's pinned host word.
+// 256-B aligned; growing frees the old buffer, which waits for the device.  refine_count_word: the thread's two pinned host words.
 void* refine_scratch(int which, size_t bytes);
 uint32_t* refine_count_word();
 

@@ -20,7 +20,23 @@
 //   7. refine_commit_kernel: one lane per listed block: decode, compare with the packed texels, apply the rule, store the winner;
 //   8. refine_finish_kernel: one lane completes *stats.
 // n == 0 skips 4. to 7.  Plain vector loads / stores and HIP atomics only.
+//
+// itwCompressImageRefinedTo: the caller gives a number of blocks or a summed error to reach, and the budget is chosen on the device from
+// the error map the judge left there.  The judge runs with budget UINT64_MAX (nothing listed); then, per round:
+//   a. refine_round_begin_kernel: clears the select's histograms and state; for a target, sets acc->met once the stream's summed error
+//      is at or below it -- every kernel of the round up to the scan then returns at once, and the host ends the call on that word;
+//   b. the select: T = the (k+1)-th largest error among the blocks still at tier 0, 0 if there are at most k.  A radix select from the
+//      top digit down, SELECT_BITS per pass: select_hist_kernel counts the digit of the candidates that share the digits chosen so far
+//      (per-workgroup histogram in LDS, one atomic per wave where the wave's candidates agree, non-empty bins flushed with one global
+//      atomic each), select_scan_kernel (ONE workgroup) walks the bins from the top, chooses the digit that holds the rank and leaves the
+//      prefix and the rank inside that bin for the next pass.  Every pass is enqueued up front; a pass whose digit lies above
+//      acc->worst_first returns at once (its digit is 0 for every block).  Counts are integers and T is a value: the order in which the
+//      atomics land cannot change it;
+//   c. refine_count_kernel: the judge's 256 blocks per workgroup; listed = tier 0 and error > T, T read from the device; group counts.
+//      The largest error among the blocks that stay is T itself (refine_finish_to_kernel);
+//   d. 3. to 7. as above, the list kernel taking T by pointer and the tier filter.  The host reads acc->met next to acc->listed.
 #include <hip/hip_runtime.h>
+#include <cmath>
 #include <cstdint>
 #include "../../include/itw_dispatch.h"
 #include "../../include/itw_decode.h"
@@ -30,6 +46,7 @@
 #include "host_rt.hpp"
 
 static_assert(sizeof(itw_refine_stats) == 56, "itw_refine_stats layout");
+static_assert(sizeof(itw_refine_target_stats) == 144, "itw_refine_target_stats layout");
 
 namespace itw {
 
@@ -40,7 +57,7 @@ struct RefineAcc {
     unsigned long long sse_first, worst_first;                  // judge: over every block
     unsigned long long worst_final;                             // judge: blocks off the list; commit: listed blocks, whichever encoding stays
     unsigned long long gained, replaced;                        // commit: sum of eA - eB over, and number of, the blocks that took B
-    uint32_t listed, _pad;                                      // scan
+    uint32_t listed, met;                                       // scan; refine_round_begin_kernel: the target is met (itwCompressImageRefinedTo)
 };
 static_assert(sizeof(RefineAcc) == 48, "refine_begin_kernel: one lane per dword");
 
@@ -255,6 +272,169 @@ __global__ void refine_finish_kernel(const RefineAcc* __restrict__ acc, unsigned
     stats->worst_final = acc->worst_final;
 }
 
+// ---- itwCompressImageRefinedTo: the budget is chosen on the device ----
+
+// Digit width of the select.  Keys are below 2^22 for BC7 (64 * 255^2) and below 2^39 for BC6H (64 * 0xFFFF^2): 11 bits make that two
+// passes and four (22 and 44 bits); 8 bits would need three and five, 16 bits a 256-KiB histogram per pass that no workgroup keeps in LDS.
+constexpr int SELECT_BITS = 11, SELECT_BINS = 1 << SELECT_BITS;
+constexpr int SELECT_MAX_PASSES = 4;
+constexpr int SELECT_PER_LANE = 8;                              // blocks per lane of select_hist_kernel: 2048 per workgroup
+constexpr int REFINE_MAX_ROUNDS = 5;
+__host__ __device__ constexpr int select_passes(int fmt) { return fmt == BCN_BC6H ? 4 : 2; }
+
+struct RefineSelect {
+    unsigned long long prefix, rank;                            // the digits chosen so far; the rank left among the candidates that share them
+    unsigned long long budget[REFINE_MAX_ROUNDS];               // T of each round
+    uint32_t done, _pad;                                        // at most k candidates: T = 0, the remaining passes return at once
+};
+
+struct RefineRounds { uint64_t listed[REFINE_MAX_ROUNDS]; uint64_t total_listed, target; uint32_t rounds; };
+
+// 32 workgroups: clears hist[SELECT_MAX_PASSES][SELECT_BINS]; lane 0 of the first one starts round `round` with rank k.  check != 0: a
+// stream whose summed error is already <= target sets acc->met instead, which turns the rest of the round into no-ops.
+__global__ void __launch_bounds__(256)
+refine_round_begin_kernel(RefineAcc* __restrict__ acc, RefineSelect* __restrict__ sel, uint32_t* __restrict__ hist, int32_t round,
+                          unsigned long long k, unsigned long long target, int32_t check)
+{
+    const int32_t i = (int32_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < SELECT_MAX_PASSES * SELECT_BINS) hist[i] = 0u;
+    if (i != 0) return;
+    sel->prefix = 0ull; sel->rank = k; sel->done = 0u;
+    if (round == 0) for (int j = 0; j < REFINE_MAX_ROUNDS; j++) sel->budget[j] = 0ull;
+    const bool met = check && acc->sse_first - acc->gained <= target;
+    acc->met = met ? 1u : 0u;
+    if (!met && round == 0) acc->worst_final = 0ull;            // the judge's "everything stays"; from here on the commits' maximum
+}
+
+// pass over the digit at `shift`: hist[d] += candidates (tier 0, digits above the pass equal to sel->prefix) whose digit is d
+__global__ void __launch_bounds__(256)
+select_hist_kernel(const unsigned long long* __restrict__ emap, const uint8_t* __restrict__ tmap, int32_t nblocks, int32_t shift,
+                   const RefineAcc* __restrict__ acc, const RefineSelect* __restrict__ sel, uint32_t* __restrict__ hist)
+{
+    __shared__ uint32_t s_hist[SELECT_BINS];
+    if (acc->met || sel->done || (acc->worst_first >> shift) == 0ull) return;
+    const int t = threadIdx.x, lane = t & 63;
+    for (int i = t; i < SELECT_BINS; i += 256) s_hist[i] = 0u;
+    __syncthreads();
+    const unsigned long long prefix = sel->prefix;
+    const int32_t base = (int32_t)blockIdx.x * (256 * SELECT_PER_LANE);
+#pragma unroll
+    for (int i = 0; i < SELECT_PER_LANE; i++) {
+        const int32_t b = base + i * 256 + t;
+        bool cand = b < nblocks && tmap[b] == 0;
+        const unsigned long long e = cand ? emap[b] : 0ull;
+        cand = cand && ((e ^ prefix) >> (shift + SELECT_BITS)) == 0ull;
+        const uint32_t d = (uint32_t)(e >> shift) & (uint32_t)(SELECT_BINS - 1);
+        // one atomic for the wave where its candidates agree on the digit (the upper digits of most maps; flat content in any digit)
+        const unsigned long long who = __ballot(cand);
+        if (who == 0ull) continue;
+        const uint32_t d0 = (uint32_t)__shfl((int)d, __ffsll((long long)who) - 1);
+        if (__ballot(cand && d == d0) == who) {
+            if (lane == 0) atomicAdd(&s_hist[d0], (uint32_t)__popcll(who));
+        } else if (cand) {
+            atomicAdd(&s_hist[d], 1u);
+        }
+    }
+    __syncthreads();
+    for (int i = t; i < SELECT_BINS; i += 256) { const uint32_t v = s_hist[i]; if (v) atomicAdd(&hist[i], v); }
+}
+
+// ONE workgroup, 8 bins per lane from the top bin down: the digit d with #(digits above d) <= rank < #(digits >= d) joins the prefix, and
+// the rank becomes the rank within d.  rank >= the candidates counted: there are at most k of them, T stays 0.  last: T = the prefix.
+__global__ void __launch_bounds__(256)
+select_scan_kernel(const uint32_t* __restrict__ hist, int32_t shift, int32_t last, int32_t round, const RefineAcc* __restrict__ acc,
+                   RefineSelect* __restrict__ sel)
+{
+    constexpr int PER = SELECT_BINS / 256;
+    __shared__ unsigned long long s_wave[4];
+    if (acc->met || sel->done || (acc->worst_first >> shift) == 0ull) return;
+    const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
+    const unsigned long long rank = sel->rank, prefix = sel->prefix;
+    uint32_t v[PER];
+    unsigned long long sum = 0ull;
+#pragma unroll
+    for (int j = 0; j < PER; j++) { v[j] = hist[SELECT_BINS - 1 - (t * PER + j)]; sum += v[j]; }
+    unsigned long long inc = sum;                               // inclusive scan over the wave
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const unsigned long long u = __shfl_up(inc, o); if (lane >= o) inc += u; }
+    if (lane == 63) s_wave[wave] = inc;
+    __syncthreads();                                            // (also: every lane has read sel before one of them writes it)
+    unsigned long long before = 0ull, total = 0ull;
+#pragma unroll
+    for (int k = 0; k < 4; k++) { const unsigned long long wv = s_wave[k]; before += k < wave ? wv : 0ull; total += wv; }
+    if (rank >= total) { if (t == 0) sel->done = 1u; return; }
+    unsigned long long above = before + inc - sum;              // candidates in the bins above this lane's first
+#pragma unroll
+    for (int j = 0; j < PER; j++) {
+        if (above <= rank && rank < above + v[j]) {
+            const unsigned long long p = prefix | ((unsigned long long)(SELECT_BINS - 1 - (t * PER + j)) << shift);
+            sel->prefix = p; sel->rank = rank - above;
+            if (last) sel->budget[round] = p;
+        }
+        above += v[j];
+    }
+}
+
+// The judge's 256 blocks per workgroup over the maps it left: listed = still at tier 0 and above *budget; the workgroup's count.  The judge's
+// other job with a host-known budget, the largest error among the blocks that stay, needs no pass here: of the candidates that stay the
+// largest is T itself (T is a candidate's error, or 0 when every inexact candidate is listed), and the blocks refined in earlier rounds
+// are in acc->worst_final from their commits -- refine_finish_to_kernel puts the two together.  (Measured at 4096^2: one atomic maximum per
+// workgroup on that one word made this kernel 49 us, against 4 us for the loads; the judge hides the same atomics behind its decode.)
+__global__ void __launch_bounds__(256)
+refine_count_kernel(const unsigned long long* __restrict__ emap, const uint8_t* __restrict__ tmap, int32_t nblocks,
+                    const unsigned long long* __restrict__ budget, uint32_t* __restrict__ group_count, const RefineAcc* __restrict__ acc)
+{
+    __shared__ uint32_t s_cnt[4];
+    const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
+    if (acc->met) { if (t == 0) group_count[blockIdx.x] = 0u; return; }
+    const int32_t b = (int32_t)blockIdx.x * 256 + t;
+    const bool listed = b < nblocks && tmap[b] == 0 && emap[b] > *budget;
+    const uint32_t cnt = (uint32_t)__popcll(__ballot(listed));
+    if (lane == 0) s_cnt[wave] = cnt;
+    __syncthreads();
+    if (t == 0) group_count[blockIdx.x] = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+}
+
+// refine_list_kernel with the budget behind a pointer and the tier filter
+__global__ void __launch_bounds__(256)
+refine_list_to_kernel(const unsigned long long* __restrict__ emap, const uint8_t* __restrict__ tmap, int32_t nblocks,
+                      const unsigned long long* __restrict__ budget, const uint32_t* __restrict__ group_first, uint32_t* __restrict__ list)
+{
+    __shared__ uint32_t s_cnt[4];
+    const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
+    const int32_t b = (int32_t)blockIdx.x * 256 + t;
+    const bool listed = b < nblocks && tmap[b] == 0 && emap[b] > *budget;
+    const unsigned long long ballot = __ballot(listed);
+    if (lane == 0) s_cnt[wave] = (uint32_t)__popcll(ballot);
+    __syncthreads();
+    uint32_t before = 0u;
+#pragma unroll
+    for (int k = 0; k < 3; k++) before += k < wave ? s_cnt[k] : 0u;
+    if (listed) list[group_first[blockIdx.x] + before + (uint32_t)__popcll(ballot & ((1ull << lane) - 1ull))] = (uint32_t)b;
+}
+
+__global__ void refine_finish_to_kernel(const RefineAcc* __restrict__ acc, const RefineSelect* __restrict__ sel, unsigned long long nblocks,
+                                        RefineRounds r, itw_refine_target_stats* __restrict__ stats)
+{
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const unsigned long long sse_final = acc->sse_first - acc->gained;
+    stats->total.blocks = nblocks;
+    stats->total.listed = r.total_listed;
+    stats->total.replaced = acc->replaced;
+    stats->total.sse_first = acc->sse_first;
+    stats->total.sse_final = sse_final;
+    stats->total.worst_first = acc->worst_first;
+    // the blocks refined in any round, and the candidates that stayed in the last one: the largest of those is its T
+    const unsigned long long stay = r.rounds ? sel->budget[r.rounds - 1] : 0ull;
+    stats->total.worst_final = acc->worst_final > stay ? acc->worst_final : stay;
+    stats->rounds = r.rounds;
+    stats->target_met = sse_final <= r.target ? 1u : 0u;
+    for (uint32_t j = 0; j < (uint32_t)REFINE_MAX_ROUNDS; j++) {
+        stats->budget[j] = j < r.rounds ? sel->budget[j] : 0ull;
+        stats->listed[j] = r.listed[j];
+    }
+}
+
 } // namespace itw
 
 namespace {
@@ -353,6 +533,146 @@ void refine(int kind, const rgba_surface& s, uint8_t* target, int dxgi_format, c
     unwind.done = true;
 }
 
+// itwCompressImageRefinedTo: refine() with the budget of every round chosen on the device
+void refine_to(int kind, const rgba_surface& s, uint8_t* target, int dxgi_format, const void* first, const void* second, uint32_t mask,
+               const itw_refine_policy& policy, itw_refine_target_stats* stats, uint64_t* block_sse, uint8_t* tier_map)
+{
+    using namespace itw;
+    hipStream_t st = (hipStream_t)itwGetStream();
+    const int px = texel_bytes(kind);
+    const int bx = s.width / 4, by = s.height / 4;
+    const int64_t nb = (int64_t)bx * by;
+    const int32_t groups = (int32_t)((nb + 255) / 256);
+    const size_t row_bytes = (size_t)s.width * px, src_pitch = (row_bytes + 15) & ~(size_t)15;
+    const bool dsrc = is_device_pointer(s.ptr), dtgt = is_device_pointer(target) && ((uintptr_t)target & 15) == 0,
+               dstats = is_device_pointer(stats), dmap = block_sse && is_device_pointer(block_sse), dtier = tier_map && is_device_pointer(tier_map);
+
+    Carve c0;
+    const size_t o_acc = c0.take(sizeof(RefineAcc)), o_stats = c0.take(sizeof(itw_refine_target_stats)), o_sel = c0.take(sizeof(RefineSelect)),
+                 o_hist = c0.take((size_t)SELECT_MAX_PASSES * SELECT_BINS * 4), o_count = c0.take((size_t)groups * 4),
+                 o_first = c0.take((size_t)groups * 4), o_list = c0.take((size_t)nb * 4), o_src = c0.take(dsrc ? 0 : src_pitch * (size_t)s.height),
+                 o_tgt = c0.take(dtgt ? 0 : (size_t)nb * 16), o_map = c0.take(dmap ? 0 : (size_t)nb * 8), o_tier = c0.take(dtier ? 0 : (size_t)nb);
+    uint8_t* base = static_cast<uint8_t*>(refine_scratch(0, c0.used));
+    RefineAcc* acc = reinterpret_cast<RefineAcc*>(base + o_acc);
+    itw_refine_target_stats* d_stats = dstats ? stats : reinterpret_cast<itw_refine_target_stats*>(base + o_stats);
+    RefineSelect* sel = reinterpret_cast<RefineSelect*>(base + o_sel);
+    uint32_t* hist = reinterpret_cast<uint32_t*>(base + o_hist);
+    uint32_t* group_count = reinterpret_cast<uint32_t*>(base + o_count);
+    uint32_t* group_first = reinterpret_cast<uint32_t*>(base + o_first);
+    uint32_t* list = reinterpret_cast<uint32_t*>(base + o_list);
+    uint8_t* d_tgt = dtgt ? target : base + o_tgt;
+    unsigned long long* d_map = reinterpret_cast<unsigned long long*>(dmap ? reinterpret_cast<uint8_t*>(block_sse) : base + o_map);
+    uint8_t* d_tier = dtier ? tier_map : base + o_tier;
+    uint32_t* host_n = refine_count_word();                     // [0] acc->listed, [1] acc->met
+
+    struct Unwind { bool done; hipStream_t st; ~Unwind() { if (!done) { (void)hipStreamSynchronize(st); (void)hipGetLastError(); } } } unwind{false, st};
+
+    const uint8_t* d_src = s.ptr;
+    int64_t stride = s.stride;
+    if (!dsrc) {
+        ITW_CHECK(hipMemcpy2DAsync(base + o_src, src_pitch, s.ptr, (size_t)s.stride, row_bytes, (size_t)s.height, hipMemcpyHostToDevice, st));
+        d_src = base + o_src; stride = (int64_t)src_pitch;
+    }
+    encode_resident(dxgi_format, first, d_src, stride, s.width, s.height, d_tgt);
+
+    // the judge with a budget that lists nothing: the maps, sse_first, worst_first, and worst_final for a call that runs no round
+    const dim3 blk(256);
+    hipLaunchKernelGGL(refine_begin_kernel, dim3(1), dim3(64), 0, st, acc);
+    ITW_CHECK(hipGetLastError());
+    if (kind == BCN_BC7) hipLaunchKernelGGL((refine_judge_kernel<BCN_BC7>), dim3((unsigned)groups), blk, 0, st, d_tgt, bx, (int32_t)nb, d_src, stride, mask,
+                                      ~0ull, d_map, d_tier, group_count, acc);
+    else           hipLaunchKernelGGL((refine_judge_kernel<BCN_BC6H>), dim3((unsigned)groups), blk, 0, st, d_tgt, bx, (int32_t)nb, d_src, stride, mask,
+                                      ~0ull, d_map, d_tier, group_count, acc);
+    ITW_CHECK(hipGetLastError());
+
+    const bool single = policy.target_total_sse == UINT64_MAX;  // policy A
+    const int passes = select_passes(kind);
+    const dim3 hgrid((unsigned)((nb + 256 * SELECT_PER_LANE - 1) / (256 * SELECT_PER_LANE)));
+    RefineRounds r = {};
+    r.target = policy.target_total_sse;
+    uint64_t cap_left = policy.max_listed;
+    for (int j = 0; j < (single ? 1 : REFINE_MAX_ROUNDS); j++) {
+        if (!single && cap_left == 0) break;
+        const uint64_t q = j < 4 ? (uint64_t)((nb >> (4 - j)) > 0 ? (nb >> (4 - j)) : 1) : (uint64_t)nb;
+        const uint64_t k = single ? policy.max_listed : (cap_left < q ? cap_left : q);
+        // the whole round up to its list length goes on the stream at once; what it does is decided by device words
+        hipLaunchKernelGGL(refine_round_begin_kernel, dim3(SELECT_MAX_PASSES * SELECT_BINS / 256), blk, 0, st, acc, sel, hist, (int32_t)j,
+                           (unsigned long long)k, (unsigned long long)policy.target_total_sse, (int32_t)(single ? 0 : 1));
+        ITW_CHECK(hipGetLastError());
+        for (int p = passes - 1; p >= 0; p--) {
+            hipLaunchKernelGGL(select_hist_kernel, hgrid, blk, 0, st, d_map, d_tier, (int32_t)nb, (int32_t)(p * SELECT_BITS), acc, sel, hist + p * SELECT_BINS);
+            ITW_CHECK(hipGetLastError());
+            hipLaunchKernelGGL(select_scan_kernel, dim3(1), blk, 0, st, hist + p * SELECT_BINS, (int32_t)(p * SELECT_BITS), (int32_t)(p == 0), (int32_t)j, acc, sel);
+            ITW_CHECK(hipGetLastError());
+        }
+        hipLaunchKernelGGL(refine_count_kernel, dim3((unsigned)groups), blk, 0, st, d_map, d_tier, (int32_t)nb, &sel->budget[j], group_count, acc);
+        ITW_CHECK(hipGetLastError());
+        hipLaunchKernelGGL(refine_scan_kernel, dim3(1), blk, 0, st, group_count, groups, group_first, acc);
+        ITW_CHECK(hipGetLastError());
+        ITW_CHECK(hipMemcpyAsync(host_n, &acc->listed, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        ITW_CHECK(hipStreamSynchronize(st));
+        if (host_n[1]) break;                                   // the target was met before this round: it ran nothing
+        const int64_t n = (int64_t)host_n[0];
+        if (n < 0 || n > nb || (uint64_t)n > k) fail_msg("itwCompressImageRefinedTo: %lld blocks listed of %lld, rank %llu", (long long)n, (long long)nb, (unsigned long long)k);
+        r.rounds = (uint32_t)j + 1u;
+        r.listed[j] = (uint64_t)n;
+        r.total_listed += (uint64_t)n;
+        if (cap_left != UINT64_MAX) cap_left -= (uint64_t)n;
+        if (n == 0) continue;
+
+        const int32_t pbx = (int32_t)(n < REFINE_PACKED_BLOCKS ? n : REFINE_PACKED_BLOCKS), pby = (int32_t)((n + pbx - 1) / pbx);
+        const int32_t total = pbx * pby;
+        const int64_t pitch = (int64_t)pbx * 4 * px;
+        Carve c1;
+        const size_t o_packed = c1.take((size_t)pitch * 4 * pby), o_refined = c1.take((size_t)total * 16);
+        uint8_t* lbase = static_cast<uint8_t*>(refine_scratch(1, c1.used));
+        uint8_t* packed = lbase + o_packed;
+        uint8_t* refined = lbase + o_refined;
+        hipLaunchKernelGGL(refine_list_to_kernel, dim3((unsigned)groups), blk, 0, st, d_map, d_tier, (int32_t)nb, &sel->budget[j], group_first, list);
+        ITW_CHECK(hipGetLastError());
+        const dim3 ggrid((unsigned)((total + 63) / 64));
+        if (kind == BCN_BC7) hipLaunchKernelGGL((refine_gather_kernel<4>), ggrid, blk, 0, st, list, (int32_t)n, total, pbx, d_src, stride, bx, packed, pitch);
+        else           hipLaunchKernelGGL((refine_gather_kernel<8>), ggrid, blk, 0, st, list, (int32_t)n, total, pbx, d_src, stride, bx, packed, pitch);
+        ITW_CHECK(hipGetLastError());
+        encode_resident(dxgi_format, second, packed, pitch, pbx * 4, pby * 4, refined);
+        const dim3 cgrid((unsigned)((n + 255) / 256));
+        if (kind == BCN_BC7) hipLaunchKernelGGL((refine_commit_kernel<BCN_BC7>), cgrid, blk, 0, st, list, (int32_t)n, pbx, packed, pitch, refined, mask, d_tgt, d_map, d_tier, acc);
+        else           hipLaunchKernelGGL((refine_commit_kernel<BCN_BC6H>), cgrid, blk, 0, st, list, (int32_t)n, pbx, packed, pitch, refined, mask, d_tgt, d_map, d_tier, acc);
+        ITW_CHECK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(refine_finish_to_kernel, dim3(1), dim3(64), 0, st, acc, sel, (unsigned long long)nb, r, d_stats);
+    ITW_CHECK(hipGetLastError());
+
+    if (!dtgt) ITW_CHECK(hipMemcpyAsync(target, d_tgt, (size_t)nb * 16, hipMemcpyDefault, st));
+    if (!dstats) ITW_CHECK(hipMemcpyAsync(stats, d_stats, sizeof(itw_refine_target_stats), hipMemcpyDeviceToHost, st));
+    if (block_sse && !dmap) ITW_CHECK(hipMemcpyAsync(block_sse, d_map, (size_t)nb * 8, hipMemcpyDeviceToHost, st));
+    if (tier_map && !dtier) ITW_CHECK(hipMemcpyAsync(tier_map, d_tier, (size_t)nb, hipMemcpyDeviceToHost, st));
+    ITW_CHECK(hipStreamSynchronize(st));
+    unwind.done = true;
+}
+
+// the checks both entries share, none of which needs a device; returns the block kind
+int check_refined_call(const char* who, const rgba_surface* source, const uint8_t* target, int dxgi_format, const void* first_settings,
+                       const void* refine_settings, uint32_t channel_mask, const void* stats, size_t stats_bytes, size_t stats_size,
+                       const char* stats_type, const uint64_t* block_sse)
+{
+    const int kind = itw::decode_kind(dxgi_format);
+    if (kind != itw::BCN_BC7 && kind != itw::BCN_BC6H) itw::fail_msg("%s: DXGI format %d has one encoder only (BC7 and BC6H have presets to refine with)", who, dxgi_format);
+    if (!source || !source->ptr || !target) itw::fail_msg("%s: null surface, texel or target pointer", who);
+    if (!first_settings || !refine_settings) itw::fail_msg("%s: null settings for the %s tier", who, first_settings ? "refine" : "first");
+    if (!stats) itw::fail_msg("%s: null stats", who);
+    if (stats_bytes != stats_size) itw::fail_msg("%s: stats_bytes %zu != sizeof(%s) = %zu", who, stats_bytes, stats_type, stats_size);
+    if (((uintptr_t)stats & 7) || ((uintptr_t)block_sse & 7)) itw::fail_msg("%s: stats and block_sse must be 8-byte aligned", who);
+    if (channel_mask == 0 || channel_mask > 15) itw::fail_msg("%s: channel mask %u (1..15: bit 0 = R .. bit 3 = A)", who, channel_mask);
+    if (source->width < 4 || source->height < 4 || (source->width & 3) || (source->height & 3))
+        itw::fail_msg("%s: %d x %d: width and height must be multiples of 4 (itwPadToMultipleOf4)", who, source->width, source->height);
+    const int64_t row = (int64_t)source->width * itw::texel_bytes(kind);
+    if ((int64_t)source->stride < row) itw::fail_msg("%s: stride %d < %lld bytes per row", who, source->stride, (long long)row);
+    if ((int64_t)(source->width / 4) * (source->height / 4) > (int64_t)ITW_MEASURE_MAX_BLOCKS)
+        itw::fail_msg("%s: %d x %d is more than %lld blocks", who, source->width, source->height, (long long)ITW_MEASURE_MAX_BLOCKS);
+    return kind;
+}
+
 } // namespace
 
 extern "C" bool itwCompressImageRefined(const rgba_surface* source, uint8_t* target, int dxgi_format, const void* first_settings,
@@ -361,22 +681,34 @@ extern "C" bool itwCompressImageRefined(const rgba_surface* source, uint8_t* tar
 {
     itw::clear_failure();
     return itw::guarded([&] {
-        // the checks that need no device
-        const int kind = itw::decode_kind(dxgi_format);
-        if (kind != itw::BCN_BC7 && kind != itw::BCN_BC6H) itw::fail_msg("itwCompressImageRefined: DXGI format %d has one encoder only (BC7 and BC6H have presets to refine with)", dxgi_format);
-        if (!source || !source->ptr || !target) itw::fail_msg("itwCompressImageRefined: null surface, texel or target pointer");
-        if (!first_settings || !refine_settings) itw::fail_msg("itwCompressImageRefined: null settings for the %s tier", first_settings ? "refine" : "first");
-        if (!stats) itw::fail_msg("itwCompressImageRefined: null stats");
-        if (stats_bytes != sizeof(itw_refine_stats))
-            itw::fail_msg("itwCompressImageRefined: stats_bytes %zu != sizeof(itw_refine_stats) = %zu", stats_bytes, sizeof(itw_refine_stats));
-        if (((uintptr_t)stats & 7) || ((uintptr_t)block_sse & 7)) itw::fail_msg("itwCompressImageRefined: stats and block_sse must be 8-byte aligned");
-        if (channel_mask == 0 || channel_mask > 15) itw::fail_msg("itwCompressImageRefined: channel mask %u (1..15: bit 0 = R .. bit 3 = A)", channel_mask);
-        if (source->width < 4 || source->height < 4 || (source->width & 3) || (source->height & 3))
-            itw::fail_msg("itwCompressImageRefined: %d x %d: width and height must be multiples of 4 (itwPadToMultipleOf4)", source->width, source->height);
-        const int64_t row = (int64_t)source->width * itw::texel_bytes(kind);
-        if ((int64_t)source->stride < row) itw::fail_msg("itwCompressImageRefined: stride %d < %lld bytes per row", source->stride, (long long)row);
-        if ((int64_t)(source->width / 4) * (source->height / 4) > (int64_t)ITW_MEASURE_MAX_BLOCKS)
-            itw::fail_msg("itwCompressImageRefined: %d x %d is more than %lld blocks", source->width, source->height, (long long)ITW_MEASURE_MAX_BLOCKS);
+        const int kind = check_refined_call("itwCompressImageRefined", source, target, dxgi_format, first_settings, refine_settings, channel_mask, stats,
+                                            stats_bytes, sizeof(itw_refine_stats), "itw_refine_stats", block_sse);
         refine(kind, *source, target, dxgi_format, first_settings, refine_settings, channel_mask, max_block_sse, stats, block_sse, tier_map);
     });
+}
+
+extern "C" bool itwCompressImageRefinedTo(const rgba_surface* source, uint8_t* target, int dxgi_format, const void* first_settings,
+                                          const void* refine_settings, uint32_t channel_mask, const itw_refine_policy* policy, size_t policy_bytes,
+                                          itw_refine_target_stats* stats, size_t stats_bytes, uint64_t* block_sse, uint8_t* tier_map)
+{
+    itw::clear_failure();
+    return itw::guarded([&] {
+        if (!policy) itw::fail_msg("itwCompressImageRefinedTo: null policy");
+        if (policy_bytes != sizeof(itw_refine_policy))
+            itw::fail_msg("itwCompressImageRefinedTo: policy_bytes %zu != sizeof(itw_refine_policy) = %zu", policy_bytes, sizeof(itw_refine_policy));
+        const int kind = check_refined_call("itwCompressImageRefinedTo", source, target, dxgi_format, first_settings, refine_settings, channel_mask, stats,
+                                            stats_bytes, sizeof(itw_refine_target_stats), "itw_refine_target_stats", block_sse);
+        refine_to(kind, *source, target, dxgi_format, first_settings, refine_settings, channel_mask, *policy, stats, block_sse, tier_map);
+    });
+}
+
+extern "C" uint64_t itwPsnrToTotalSse(int dxgi_format, int width, int height, uint32_t channel_mask, double psnr_db)
+{
+    const int kind = itw::decode_kind(dxgi_format);
+    int channels = 0;
+    for (int c = 0; c < 4; c++) channels += (channel_mask >> c) & 1u;
+    if (kind == itw::BCN_NONE || kind == itw::BCN_BC6H || channels == 0 || width < 1 || height < 1 || !std::isfinite(psnr_db)) return UINT64_MAX;
+    const double peak = (kind == itw::BCN_BC4S || kind == itw::BCN_BC5S) ? 254.0 : 255.0;      // as itwStatsPsnr
+    const double sse = std::floor(peak * peak * ((double)width * (double)height * (double)channels) / std::pow(10.0, psnr_db / 10.0));
+    return sse >= 18446744073709551615.0 ? UINT64_MAX : (uint64_t)sse;
 }

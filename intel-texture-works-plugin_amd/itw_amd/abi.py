@@ -23,7 +23,7 @@ EXPORTED_SYMBOLS = tuple(
     + ["GetProcessorCount", "InitWin32Threads", "DestroyThreads", "GetBytesPerBlock", "CompressImageMT", "CompressImageST",
        "CompressImageBC1", "CompressImageBC3", "CompressImageBC4", "CompressImageBC5", "CompressImageBC4S", "CompressImageBC5S"]
     + ["CompressImageBC7_" + p for p in BC7_PROFILES] + ["CompressImageBC6H_" + p for p in BC6H_PROFILES]
-    + ["itwCompressImageSliced", "itwCompressImageSlicedEx", "itwChainBytes", "itwCompressImageChain", "itwCompressImageChainEx", "itwCompressImageRefined", "itwSetSliceWindow", "itwSliceWindow", "itwSliceWindowFor", "itwPadToMultipleOf4", "itwFreeSurface", "itwPadToMultipleOf4Device",
+    + ["itwCompressImageSliced", "itwCompressImageSlicedEx", "itwChainBytes", "itwCompressImageChain", "itwCompressImageChainEx", "itwCompressImageRefined", "itwCompressImageRefinedTo", "itwPsnrToTotalSse", "itwSetSliceWindow", "itwSliceWindow", "itwSliceWindowFor", "itwPadToMultipleOf4", "itwFreeSurface", "itwPadToMultipleOf4Device",
        "itwConvertToRGBA8Device", "itwConvertToRGBA16FDevice"]
     # include/itw_multigpu.h: one surface over all GPUs, one process
     + ["itwMultiGpuRanks", "itwMultiGpuTransport", "itwMultiGpuPeerLinks", "itwCompressImageMultiGPU", "itwCompressImageMultiGPUEx", "itwCompressImageMultiGPUBands",
@@ -170,6 +170,26 @@ class RefineStats(C.Structure):
 
 assert C.sizeof(RefineStats) == 56
 
+
+class RefinePolicy(C.Structure):
+    """struct itw_refine_policy (itw_dispatch.h): what itwCompressImageRefinedTo may spend and has to reach."""
+    _fields_ = [("max_listed", C.c_uint64), ("target_total_sse", C.c_uint64)]
+
+
+class RefineTargetStats(C.Structure):
+    """struct itw_refine_target_stats (itw_dispatch.h): itw_refine_stats over the whole call, then what each round chose and listed."""
+    _fields_ = [("total", RefineStats), ("rounds", C.c_uint32), ("target_met", C.c_uint32), ("budget", C.c_uint64 * 5), ("listed", C.c_uint64 * 5)]
+
+    def as_dict(self):
+        d = self.total.as_dict()
+        d.update(rounds=int(self.rounds), target_met=int(self.target_met), budget=[int(v) for v in self.budget],
+                 listed_per_round=[int(v) for v in self.listed])
+        return d
+
+
+assert C.sizeof(RefinePolicy) == 16 and C.sizeof(RefineTargetStats) == 144
+UINT64_MAX = 2 ** 64 - 1
+
 COMPRESSION_FUNC = C.CFUNCTYPE(None, C.POINTER(RgbaSurface), C.c_void_p)
 PROGRESS_FUNC = C.CFUNCTYPE(C.c_bool, C.c_int, C.c_int, C.c_void_p)
 
@@ -279,6 +299,11 @@ def _load(path, hooks):
         L.itwCompressImageRefined.argtypes = [C.POINTER(RgbaSurface), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64,
                                               C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
         L.itwCompressImageRefined.restype = C.c_bool
+        L.itwCompressImageRefinedTo.argtypes = [C.POINTER(RgbaSurface), C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t,
+                                                C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]
+        L.itwCompressImageRefinedTo.restype = C.c_bool
+        L.itwPsnrToTotalSse.argtypes = [C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_double]
+        L.itwPsnrToTotalSse.restype = C.c_uint64
         L.itwSetSliceWindow.argtypes = [C.c_int]
         L.itwSetSliceWindow.restype = None
         L.itwSliceWindow.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int64]
@@ -1024,4 +1049,70 @@ def compress_refined(fmt, img, first, refine, max_block_sse, channels=None, want
                                            C.addressof(st), C.sizeof(RefineStats), ptr(bmap), ptr(tmap))
     if not ok:
         raise ValueError("itwCompressImageRefined: " + (last_error() or "failed"))
+    return (out, st) + ((bmap,) if want_block_map else ()) + ((tmap,) if want_tier_map else ())
+
+
+def psnr_to_total_sse(fmt, width, height, psnr_db, channels=None):
+    """itwPsnrToTotalSse: the largest summed error at which a width x height image still has psnr_db over `channels` (default 'rgb');
+    UINT64_MAX where itwStatsPsnr has no answer (bc6h, a non-finite psnr_db)."""
+    return int(lib().itwPsnrToTotalSse(DXGI_FORMAT[fmt], int(width), int(height), _channel_mask("rgb" if channels is None else channels), float(psnr_db)))
+
+
+def compress_refined_to(fmt, img, first, refine, max_listed=None, share=None, target_sse=None, target_psnr=None, channels=None,
+                        want_block_map=False, want_tier_map=False):
+    """itwCompressImageRefinedTo: compress_refined with the budget chosen on the device (include/itw_dispatch.h).  What to spend: max_listed,
+    the most blocks the refine tier may encode, or share (0..1), which becomes max_listed = floor(share * blocks); neither: no cap.  What to
+    reach: target_sse, the stream's summed block error, or target_psnr in dB over `channels` (bc7 only), which becomes
+    itwPsnrToTotalSse's target; neither: one round that lists the max_listed worst blocks (policy A).  Everything else as compress_refined.
+    Returns (blocks, RefineTargetStats[, block_sse][, tier_map])."""
+    import numpy as np
+    base = fmt.split("_")[0]
+    if base not in ("bc7", "bc6h"):
+        raise ValueError(f"{fmt}: only bc7 and bc6h have presets to refine with")
+    if max_listed is not None and share is not None:
+        raise ValueError("max_listed and share are two ways to say one thing: pass one")
+    if target_sse is not None and target_psnr is not None:
+        raise ValueError("target_sse and target_psnr are two ways to say one thing: pass one")
+    profile, settings_type = (bc7_profile, Bc7Settings) if base == "bc7" else (bc6h_profile, Bc6hSettings)
+    s1 = first if isinstance(first, settings_type) else profile(first)
+    s2 = refine if isinstance(refine, settings_type) else profile(refine)
+    mask = _channel_mask("rgb" if channels is None else channels)
+    h, w = img.shape[:2]
+    nb = (w // 4) * (h // 4)
+    if share is not None:
+        if not 0.0 <= share <= 1.0:
+            raise ValueError(f"share {share}: a fraction of the blocks, 0..1")
+        max_listed = int(share * nb)
+    if target_psnr is not None:
+        if base == "bc6h":
+            raise ValueError("bc6h: no PSNR of half-float codes; pass target_sse")
+        target_sse = psnr_to_total_sse(fmt, w, h, target_psnr, "rgb" if channels is None else channels)
+    pol = RefinePolicy(UINT64_MAX if max_listed is None else int(max_listed), UINT64_MAX if target_sse is None else int(target_sse))
+    st = RefineTargetStats()
+    L = lib()
+    if isinstance(img, np.ndarray):
+        assert img.ndim == 3 and img.shape[2] == 4 and img.strides[2] == img.itemsize and img.strides[1] == 4 * img.itemsize
+        assert img.itemsize == (2 if base == "bc6h" else 1), "texel type does not match the format"
+        out = np.empty(nb * 16, dtype=np.uint8)
+        bmap = np.empty(nb, dtype=np.uint64) if want_block_map else None
+        tmap = np.empty(nb, dtype=np.uint8) if want_tier_map else None
+        surf = RgbaSurface(img.ctypes.data, w, h, img.strides[0])
+        ptr = lambda a: a.ctypes.data if a is not None else None
+        ok = L.itwCompressImageRefinedTo(C.byref(surf), ptr(out), DXGI_FORMAT[fmt], C.addressof(s1), C.addressof(s2), mask, C.addressof(pol),
+                                         C.sizeof(RefinePolicy), C.addressof(st), C.sizeof(RefineTargetStats), ptr(bmap), ptr(tmap))
+    else:
+        import torch
+        assert img.is_cuda and img.dim() == 3 and img.shape[2] == 4 and img.stride(2) == 1 and img.stride(1) == 4
+        assert img.element_size() == (2 if base == "bc6h" else 1), "texel type does not match the format"
+        out = torch.empty(nb * 16, dtype=torch.uint8, device=img.device)
+        bmap = torch.empty(nb, dtype=torch.int64, device=img.device) if want_block_map else None
+        tmap = torch.empty(nb, dtype=torch.uint8, device=img.device) if want_tier_map else None
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        with torch.cuda.device(img.device):
+            L.itwSetStream(torch.cuda.current_stream(img.device).cuda_stream)
+            surf = RgbaSurface(img.data_ptr(), w, h, img.stride(0) * img.element_size())
+            ok = L.itwCompressImageRefinedTo(C.byref(surf), ptr(out), DXGI_FORMAT[fmt], C.addressof(s1), C.addressof(s2), mask, C.addressof(pol),
+                                             C.sizeof(RefinePolicy), C.addressof(st), C.sizeof(RefineTargetStats), ptr(bmap), ptr(tmap))
+    if not ok:
+        raise ValueError("itwCompressImageRefinedTo: " + (last_error() or "failed"))
     return (out, st) + ((bmap,) if want_block_map else ()) + ((tmap,) if want_tier_map else ())
