@@ -246,6 +246,47 @@ bool itwCompressImageRefinedTo(const rgba_surface* source, uint8_t* target, int 
  * channels, a width or height < 1, a psnr_db that is NaN or infinite; BC6H callers pass a summed error. */
 uint64_t itwPsnrToTotalSse(int dxgi_format, int width, int height, uint32_t channel_mask, double psnr_db);
 
+/* A whole mip chain, cube map or texture array to an error budget, in one call.
+ *
+ * itwCompressImageChainRefined / itwCompressImageChainRefinedTo are itwCompressImageRefined / itwCompressImageRefinedTo over the blocks of
+ * a whole chain as ONE population: level 0 and a 2 x 2 tail mip compete for the same budget, the same list and the same select.
+ *   * Images: `images`, `count`, the layout of `target` and its size (itwChainBytes) are itwCompressImageChainEx's: any width and height
+ *     >= 1, any stride >= the row's bytes, RGBA8 or RGBA16F for BC6H, all images host pointers or all device pointers.  Formats and the
+ *     two settings structs as itwCompressImageRefined (95, 96, 98, 99).
+ *   * Encoding: block j of the chain's concatenated block list is the block itwCompressImageChainEx writes for it under one of the two
+ *     settings -- encoded from the edge-replicated image.  With max_block_sse = UINT64_MAX, `target` equals
+ *     itwCompressImageChainEx(first_settings) byte for byte.
+ *   * Block error: itwMeasureBlocks' block_sse for the block's image: squared code differences over the texels INSIDE the image only,
+ *     summed over the channels of channel_mask.  Replicated padding never counts, under either tier (itwMeasureChain of `target` reports
+ *     the same sums).  The rule (tiers 0 / 1 / 2, ties keep the first tier) and every field of itw_refine_stats are
+ *     itwCompressImageRefined's, over all blocks of the chain.
+ *   * Maps and stats: block_sse and tier_map hold one entry per block of the concatenated list, indexed as itwDecodeChain indexes `modes`.
+ *     image_stats (optional; `count` entries, 8-byte aligned) holds the same seven fields over image i's blocks alone: blocks, listed,
+ *     replaced, sse_first and sse_final sum to the totals, the maxima of worst_first / worst_final over i are the totals'.
+ *   * itwCompressImageChainRefinedTo: the select, the quotas (`blocks` = the chain's block count), the rounds, budget[] and listed[] are
+ *     itwCompressImageRefinedTo's, unchanged, over the chain.
+ *   * itwChainPsnrToTotalSse: itwPsnrToTotalSse with n = the sum over images of width * height, times the selected channels; UINT64_MAX in
+ *     the same cases, and for count < 1 or null `images`.
+ *   * Pointers: target, stats, image_stats, block_sse and tier_map may each be a host or a device pointer.  Synchronous and not capturable,
+ *     like the single-image calls; one device, the calling thread's stream.
+ *   * Errors: everything itwCompressImageChainEx and itwCompressImageRefined[To] refuse, a summed block count above ITW_MEASURE_MAX_BLOCKS
+ *     and a misaligned image_stats fail through the library's error mode before any device work starts, and need no device.
+ * How: the whole chain is gathered once into one packed surface of min(1024, n) blocks per row (the copy is the price of one population);
+ * the first tier encodes it into scratch and the first n blocks are copied to `target` at the end. */
+bool itwCompressImageChainRefined(const rgba_surface* images, int count, uint8_t* target, int dxgi_format,
+                                  const void* first_settings, const void* refine_settings,
+                                  uint32_t channel_mask, uint64_t max_block_sse,
+                                  itw_refine_stats* stats, size_t stats_bytes,
+                                  itw_refine_stats* image_stats,
+                                  uint64_t* block_sse, uint8_t* tier_map);
+bool itwCompressImageChainRefinedTo(const rgba_surface* images, int count, uint8_t* target, int dxgi_format,
+                                    const void* first_settings, const void* refine_settings, uint32_t channel_mask,
+                                    const itw_refine_policy* policy, size_t policy_bytes,
+                                    itw_refine_target_stats* stats, size_t stats_bytes,
+                                    itw_refine_stats* image_stats,
+                                    uint64_t* block_sse, uint8_t* tier_map);
+uint64_t itwChainPsnrToTotalSse(const rgba_surface* images, int count, int dxgi_format, uint32_t channel_mask, double psnr_db);
+
 /* Pad to multiples of 4 by edge replication (IntelPlugin.cpp:893-928): the step immediately before the ABI.
  * pixel_size = 4 (RGBA8) or 8 (RGBA16F).  Host version: returns a surface whose ptr was allocated with malloc()
  * (free with itwFreeSurface); the reference allocates with new[] and leaves ownership to the caller likewise.

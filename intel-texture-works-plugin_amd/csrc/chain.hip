@@ -25,10 +25,13 @@ __device__ __forceinline__ uint32_t load_u32(const uint8_t* p)
     return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
 }
 
-// PX: bytes per texel (4 RGBA8, 8 RGBA16F).  FILL45: BC4/BC5's partial-block fill instead of edge replication.
-template <int PX, bool FILL45>
+// PX: bytes per texel (4 RGBA8, 8 RGBA16F).  FILL45: BC4/BC5's partial-block fill instead of edge replication.  EXTENTS: the lane that
+// carries texel row 0 of block j < nblocks also writes extents[j] = (pw - 1) | (ph - 1) << 2, the part of the block that lies inside its
+// image (itwCompressImageChainRefined leaves the padding out of a block's error).
+template <int PX, bool FILL45, bool EXTENTS>
 __global__ void __launch_bounds__(256) chain_gather_kernel(const ChainImage* __restrict__ images, int32_t nimg, int64_t nblocks,
-                                                          int32_t packed_bx, int64_t total, uint8_t* __restrict__ dst, int64_t dst_pitch)
+                                                          int32_t packed_bx, int64_t total, uint8_t* __restrict__ dst, int64_t dst_pitch,
+                                                          uint8_t* __restrict__ extents)
 {
     constexpr int W = PX;                                       // dwords per 4-texel row piece (4 or 8)
     const int r = threadIdx.x >> 6;
@@ -52,6 +55,7 @@ __global__ void __launch_bounds__(256) chain_gather_kernel(const ChainImage* __r
         const int32_t by = (int32_t)(b / bw), bx = (int32_t)(b - (int64_t)by * bw);
         const int32_t x0 = bx * 4, y0 = by * 4;
         const int32_t pw = min(4, im.width - x0), ph = min(4, im.height - y0);
+        if (EXTENTS && r == 0) extents[j] = (uint8_t)((pw - 1) | ((ph - 1) << 2));
         const int32_t y = y0 + (FILL45 ? bc45_fill_index(r, ph) : min(r, ph - 1));
         const uint8_t* p = im.ptr + (int64_t)y * im.stride + (int64_t)x0 * PX;
         if (pw == 4 && ((uintptr_t)p & 15) == 0) {
@@ -78,7 +82,7 @@ __global__ void __launch_bounds__(256) chain_gather_kernel(const ChainImage* __r
 namespace itw {
 
 void launch_chain_gather(const ChainImage* images, int nimg, int64_t nblocks, int packed_bx, int packed_by, int texel_bytes, bool fill45,
-                         uint8_t* dst, int64_t dst_pitch, hipStream_t st)
+                         uint8_t* dst, int64_t dst_pitch, hipStream_t st, uint8_t* extents)
 {
     const int64_t total = (int64_t)packed_bx * packed_by;
     if (total <= 0 || nimg <= 0) return;
@@ -87,11 +91,14 @@ void launch_chain_gather(const ChainImage* images, int nimg, int64_t nblocks, in
     const dim3 grid((unsigned)((total + 63) / 64)), blk(256);
     if (texel_bytes == 8) {
         if (fill45) fail_msg("launch_chain_gather: the BC4/BC5 fill is for RGBA8 surfaces");
-        hipLaunchKernelGGL((chain_gather_kernel<8, false>), grid, blk, 0, st, images, nimg, nblocks, packed_bx, total, dst, dst_pitch);
+        if (extents) hipLaunchKernelGGL((chain_gather_kernel<8, false, true>), grid, blk, 0, st, images, nimg, nblocks, packed_bx, total, dst, dst_pitch, extents);
+        else         hipLaunchKernelGGL((chain_gather_kernel<8, false, false>), grid, blk, 0, st, images, nimg, nblocks, packed_bx, total, dst, dst_pitch, extents);
     } else if (fill45) {
-        hipLaunchKernelGGL((chain_gather_kernel<4, true>), grid, blk, 0, st, images, nimg, nblocks, packed_bx, total, dst, dst_pitch);
+        if (extents) fail_msg("launch_chain_gather: extents go with edge replication");
+        hipLaunchKernelGGL((chain_gather_kernel<4, true, false>), grid, blk, 0, st, images, nimg, nblocks, packed_bx, total, dst, dst_pitch, extents);
     } else {
-        hipLaunchKernelGGL((chain_gather_kernel<4, false>), grid, blk, 0, st, images, nimg, nblocks, packed_bx, total, dst, dst_pitch);
+        if (extents) hipLaunchKernelGGL((chain_gather_kernel<4, false, true>), grid, blk, 0, st, images, nimg, nblocks, packed_bx, total, dst, dst_pitch, extents);
+        else         hipLaunchKernelGGL((chain_gather_kernel<4, false, false>), grid, blk, 0, st, images, nimg, nblocks, packed_bx, total, dst, dst_pitch, extents);
     }
     ITW_CHECK(hipGetLastError());
 }

@@ -76,7 +76,9 @@ struct ChainImage { const uint8_t* ptr; int64_t stride; int32_t width, height; i
 // 4 * packed_by rows, `dst_pitch` bytes apart, 16-B aligned rows), packed block j = block j of the group (j < nblocks; the tail of the last
 // packed row is zero).  `images`: device table of `nimg` descriptors, ascending first_block.  texel_bytes 4 (RGBA8) or 8 (RGBA16F);
 // `fill45`: partial blocks take bc45_fill_index (BC4/BC5) instead of edge replication (the ISPC formats' pad to multiples of 4).
+// `extents` (optional, edge replication only): device memory, one byte per block j < nblocks: (pw - 1) | (ph - 1) << 2, the pw x ph texels
+// of the block that lie inside its image.
 void launch_chain_gather(const ChainImage* images, int nimg, int64_t nblocks, int packed_bx, int packed_by, int texel_bytes, bool fill45,
-                         uint8_t* dst, int64_t dst_pitch, hipStream_t st);
+                         uint8_t* dst, int64_t dst_pitch, hipStream_t st, uint8_t* extents = nullptr);
 
 } // namespace itw

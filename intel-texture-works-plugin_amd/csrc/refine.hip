@@ -35,6 +35,15 @@
 //   c. refine_count_kernel: the judge's 256 blocks per workgroup; listed = tier 0 and error > T, T read from the device; group counts.
 //      The largest error among the blocks that stay is T itself (refine_finish_to_kernel);
 //   d. 3. to 7. as above, the list kernel taking T by pointer and the tier filter.  The host reads acc->met next to acc->listed.
+//
+// itwCompressImageChainRefined[To]: the same core behind a second front door.  The core reads a VIEW -- a device surface, its stride, its
+// blocks per row, a block count and, optionally, one byte of extent per block -- and not an rgba_surface.  A single image is viewed in
+// place, without a table: the path above, the non-CROP kernels.  A chain is gathered once, whole, with edge replication, into one packed
+// surface of min(1024, n) blocks per row (chain.hip: the encoders then see what itwCompressImageChainEx shows them), the gather also
+// writing each block's extent (pw - 1) | (ph - 1) << 2; the first tier encodes the packed surface into scratch (its last row may run
+// past n) and the first n blocks are copied out at the end.  The judge and the commit take the CROP variant of the block error, which
+// leaves the replicated padding out -- itwMeasureBlocks' block_sse of the image.  Everything else runs unchanged over the n-block maps.
+// refine_image_stats_kernel, once behind the judge and once at the end, sums the maps per image (only when the caller asks).
 #include <hip/hip_runtime.h>
 #include <cmath>
 #include <cstdint>
@@ -43,7 +52,9 @@
 #include "../../include/itw_amd.h"
 #include "decode_core.hpp"
 #include "texel_rows.hpp"
+#include "kernels.hpp"
 #include "host_rt.hpp"
+#include <vector>
 
 static_assert(sizeof(itw_refine_stats) == 56, "itw_refine_stats layout");
 static_assert(sizeof(itw_refine_target_stats) == 144, "itw_refine_target_stats layout");
@@ -61,9 +72,11 @@ struct RefineAcc {
 };
 static_assert(sizeof(RefineAcc) == 48, "refine_begin_kernel: one lane per dword");
 
-// the error of the block `w` against the 4 x 4 texels at `p` (rows `stride` bytes apart): measure_kernel's per-block sum over the channels in `mask`
-template <int FMT>
-__device__ __forceinline__ unsigned long long refine_block_error(const uint4 w, const uint8_t* p, int64_t stride, uint32_t mask)
+// the error of the block `w` against the 4 x 4 texels at `p` (rows `stride` bytes apart): measure_kernel's per-block sum over the channels in `mask`.
+// CROP: only texel (x, y) with x < pw and y < ph counts -- the part of a chain's block that lies inside its image; the loads stay whole rows
+// (the packed surface holds the replicated padding), only the accumulation is masked.
+template <int FMT, bool CROP>
+__device__ __forceinline__ unsigned long long refine_block_error(const uint4 w, const uint8_t* p, int64_t stride, uint32_t mask, int pw, int ph)
 {
     if constexpr (FMT == BCN_BC6H) {
         uint32_t lo[16], hi[16];
@@ -80,7 +93,7 @@ __device__ __forceinline__ unsigned long long refine_block_error(const uint4 w, 
                 for (int c = 0; c < 4; c++) {
                     const int a = (int)((s[2 * x + (c >> 1)] >> (16 * (c & 1))) & 0xffffu), v = (int)((d[c >> 1] >> (16 * (c & 1))) & 0xffffu);
                     const uint32_t df = (uint32_t)abs(a - v);
-                    e += ((mask >> c) & 1u) ? (unsigned long long)df * df : 0ull;
+                    e += (((mask >> c) & 1u) && (!CROP || (x < pw && y < ph))) ? (unsigned long long)df * df : 0ull;
                 }
             }
         }
@@ -99,7 +112,7 @@ __device__ __forceinline__ unsigned long long refine_block_error(const uint4 w, 
                 for (int c = 0; c < 4; c++) {
                     const int a = (int)((s[x] >> (8 * c)) & 255u), v = (int)((px[y * 4 + x] >> (8 * c)) & 255u);
                     const uint32_t df = (uint32_t)abs(a - v);
-                    e += ((mask >> c) & 1u) ? df * df : 0u;
+                    e += (((mask >> c) & 1u) && (!CROP || (x < pw && y < ph))) ? df * df : 0u;
                 }
             }
         }
@@ -112,12 +125,12 @@ __global__ void refine_begin_kernel(RefineAcc* __restrict__ acc)
     if (blockIdx.x == 0 && threadIdx.x < sizeof(RefineAcc) / 4) reinterpret_cast<uint32_t*>(acc)[threadIdx.x] = 0u;
 }
 
-// FMT: BCN_BC7 or BCN_BC6H (bcn_format.hpp).  `blocks`: 16-B aligned.
-template <int FMT>
+// FMT: BCN_BC7 or BCN_BC6H (bcn_format.hpp).  `blocks`: 16-B aligned.  CROP: `extents` holds (pw - 1) | (ph - 1) << 2 per block (chain.hip)
+template <int FMT, bool CROP>
 __global__ void __launch_bounds__(256)
 refine_judge_kernel(const uint8_t* __restrict__ blocks, int32_t blocks_x, int32_t nblocks, const uint8_t* __restrict__ src, int64_t stride,
                     uint32_t mask, unsigned long long budget, unsigned long long* __restrict__ emap, uint8_t* __restrict__ tmap,
-                    uint32_t* __restrict__ group_count, RefineAcc* __restrict__ acc)
+                    uint32_t* __restrict__ group_count, RefineAcc* __restrict__ acc, const uint8_t* __restrict__ extents)
 {
     constexpr int PX = texel_bytes(FMT);
     __shared__ unsigned long long s_sum[4], s_max[4], s_stay[4];
@@ -129,7 +142,8 @@ refine_judge_kernel(const uint8_t* __restrict__ blocks, int32_t blocks_x, int32_
     if (b < nblocks) {
         const int32_t yy = b / blocks_x, xx = b - yy * blocks_x;
         const uint4 w = *reinterpret_cast<const uint4*>(blocks + (int64_t)b * 16);
-        e = refine_block_error<FMT>(w, src + (int64_t)yy * 4 * stride + (int64_t)xx * 4 * PX, stride, mask);
+        const int ex = CROP ? (int)extents[b] : 15;
+        e = refine_block_error<FMT, CROP>(w, src + (int64_t)yy * 4 * stride + (int64_t)xx * 4 * PX, stride, mask, (ex & 3) + 1, (ex >> 2) + 1);
         emap[b] = e;
         tmap[b] = 0;
         listed = e > budget;
@@ -215,12 +229,13 @@ refine_gather_kernel(const uint32_t* __restrict__ list, int32_t n, int32_t total
     for (int q = 0; q < PX / 4; q++) out[q] = make_uint4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
 }
 
-// one lane per listed block: B = refined[i] against slot i of the packed surface; the rule; the winner into blocks / emap / tmap
-template <int FMT>
+// one lane per listed block: B = refined[i] against slot i of the packed surface; the rule; the winner into blocks / emap / tmap.
+// CROP: the block's extent is extents[list[i]], as the judge took it.
+template <int FMT, bool CROP>
 __global__ void __launch_bounds__(256)
 refine_commit_kernel(const uint32_t* __restrict__ list, int32_t n, int32_t packed_bx, const uint8_t* __restrict__ packed, int64_t pitch,
                      const uint8_t* __restrict__ refined, uint32_t mask, uint8_t* __restrict__ blocks, unsigned long long* __restrict__ emap,
-                     uint8_t* __restrict__ tmap, RefineAcc* __restrict__ acc)
+                     uint8_t* __restrict__ tmap, RefineAcc* __restrict__ acc, const uint8_t* __restrict__ extents)
 {
     constexpr int PX = texel_bytes(FMT);
     __shared__ unsigned long long s_gain[4], s_max[4];
@@ -233,7 +248,9 @@ refine_commit_kernel(const uint32_t* __restrict__ list, int32_t n, int32_t packe
         const uint32_t b = list[i];
         const uint4 w = *reinterpret_cast<const uint4*>(refined + (int64_t)i * 16);
         const int32_t prow = i / packed_bx, pcol = i - prow * packed_bx;
-        const unsigned long long eb = refine_block_error<FMT>(w, packed + (int64_t)prow * 4 * pitch + (int64_t)pcol * 4 * PX, pitch, mask);
+        const int ex = CROP ? (int)extents[b] : 15;
+        const unsigned long long eb = refine_block_error<FMT, CROP>(w, packed + (int64_t)prow * 4 * pitch + (int64_t)pcol * 4 * PX, pitch, mask,
+                                                                    (ex & 3) + 1, (ex >> 2) + 1);
         const unsigned long long ea = emap[b];
         if (eb < ea) {
             *reinterpret_cast<uint4*>(blocks + (int64_t)b * 16) = w;
@@ -270,6 +287,64 @@ __global__ void refine_finish_kernel(const RefineAcc* __restrict__ acc, unsigned
     stats->sse_final = acc->sse_first - acc->gained;
     stats->worst_first = acc->worst_first;
     stats->worst_final = acc->worst_final;
+}
+
+// ---- itwCompressImageChainRefined[To]: the seven fields per image of the chain ----
+
+__global__ void __launch_bounds__(256) refine_image_begin_kernel(uint32_t* __restrict__ p, int32_t dwords)
+{
+    const int32_t i = (int32_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < dwords) p[i] = 0u;
+}
+
+// The judge's 256 blocks per workgroup over the maps; a lane finds its image by chain_gather_kernel's binary search.  FINAL = false, behind
+// the judge: blocks, sse_first, worst_first from the error map.  FINAL = true, last: listed and replaced from the tier map, sse_final and
+// worst_final from the error map.  A wave inside one image reduces by shuffles and its first lane issues one atomic per field; a wave that
+// spans images leaves the atomics to its lanes.  Integer add and max only: the order of arrival cannot change a field.
+template <bool FINAL>
+__global__ void __launch_bounds__(256)
+refine_image_stats_kernel(const ChainImage* __restrict__ images, int32_t nimg, const unsigned long long* __restrict__ emap,
+                          const uint8_t* __restrict__ tmap, int32_t nblocks, itw_refine_stats* __restrict__ out)
+{
+    const int lane = threadIdx.x & 63;
+    const int32_t b = (int32_t)blockIdx.x * 256 + threadIdx.x;
+    const bool live = b < nblocks;
+    const unsigned long long who = __ballot(live);
+    if (who == 0ull) return;                                    // (no barrier below)
+    int img = 0;
+    unsigned long long e = 0ull;
+    uint32_t listed = 0u, won = 0u;
+    if (live) {
+        int lo = 0, hi = nimg - 1;                              // the last image whose first block is <= b
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (images[mid].first_block <= (int64_t)b) lo = mid; else hi = mid - 1;
+        }
+        img = lo;
+        e = emap[b];
+        if (FINAL) { const uint32_t t = tmap[b]; listed = t != 0u ? 1u : 0u; won = t == 2u ? 1u : 0u; }
+    }
+    const int img0 = __shfl(img, 0);                            // lane 0 is live wherever a lane of its wave is
+    unsigned long long sum = e, mx = e;
+    uint32_t cnt = 1u;
+    bool issue = live;
+    if (__ballot(live && img == img0) == who) {
+        sum = wave_sum(e); mx = wave_max(e); listed = wave_sum(listed); won = wave_sum(won);
+        cnt = (uint32_t)__popcll(who);
+        issue = lane == 0;
+    }
+    if (!issue) return;
+    itw_refine_stats* s = out + img;
+    if (!FINAL) {
+        atomicAdd(reinterpret_cast<unsigned long long*>(&s->blocks), (unsigned long long)cnt);
+        if (sum) atomicAdd(reinterpret_cast<unsigned long long*>(&s->sse_first), sum);
+        if (mx) atomicMax(reinterpret_cast<unsigned long long*>(&s->worst_first), mx);
+    } else {
+        if (listed) atomicAdd(reinterpret_cast<unsigned long long*>(&s->listed), (unsigned long long)listed);
+        if (won) atomicAdd(reinterpret_cast<unsigned long long*>(&s->replaced), (unsigned long long)won);
+        if (sum) atomicAdd(reinterpret_cast<unsigned long long*>(&s->sse_final), sum);
+        if (mx) atomicMax(reinterpret_cast<unsigned long long*>(&s->worst_final), mx);
+    }
 }
 
 // ---- itwCompressImageRefinedTo: the budget is chosen on the device ----
@@ -445,63 +520,205 @@ struct Carve {
     size_t take(size_t bytes) { const size_t at = used; used += (bytes + 255) & ~(size_t)255; return at; }
 };
 
-// everything that needs the device
-void refine(int kind, const rgba_surface& s, uint8_t* target, int dxgi_format, const void* first, const void* second, uint32_t mask,
-            uint64_t budget, itw_refine_stats* stats, uint64_t* block_sse, uint8_t* tier_map)
-{
-    using namespace itw;
-    hipStream_t st = (hipStream_t)itwGetStream();
-    const int px = texel_bytes(kind);
-    const int bx = s.width / 4, by = s.height / 4;
-    const int64_t nb = (int64_t)bx * by;
-    const int32_t groups = (int32_t)((nb + 255) / 256);
-    const size_t row_bytes = (size_t)s.width * px, src_pitch = (row_bytes + 15) & ~(size_t)15;
-    // the kernels take device memory; the judge and the commit load and store whole blocks as 16-B vectors
-    const bool dsrc = is_device_pointer(s.ptr), dtgt = is_device_pointer(target) && ((uintptr_t)target & 15) == 0,
-               dstats = is_device_pointer(stats), dmap = block_sse && is_device_pointer(block_sse), dtier = tier_map && is_device_pointer(tier_map);
+// What the core reads its texels from: block b of the call lies at block row b / blocks_x, column b % blocks_x of a device surface whose
+// rows are `stride` bytes apart.  `extents` (optional): per block, the part of it that lies inside its image (chain.hip); `images` /
+// `nimg` (a chain only): the device table the per-image kernel searches.
+struct RefineView { const uint8_t* src; int64_t stride; int32_t blocks_x; const uint8_t* extents; const itw::ChainImage* images; int32_t nimg; };
 
-    Carve c0;
-    const size_t o_acc = c0.take(sizeof(RefineAcc)), o_stats = c0.take(sizeof(itw_refine_stats)), o_count = c0.take((size_t)groups * 4),
-                 o_first = c0.take((size_t)groups * 4), o_list = c0.take((size_t)nb * 4), o_src = c0.take(dsrc ? 0 : src_pitch * (size_t)s.height),
-                 o_tgt = c0.take(dtgt ? 0 : (size_t)nb * 16), o_map = c0.take(dmap ? 0 : (size_t)nb * 8), o_tier = c0.take(dtier ? 0 : (size_t)nb);
-    uint8_t* base = static_cast<uint8_t*>(refine_scratch(0, c0.used));
-    RefineAcc* acc = reinterpret_cast<RefineAcc*>(base + o_acc);
-    itw_refine_stats* d_stats = dstats ? stats : reinterpret_cast<itw_refine_stats*>(base + o_stats);
-    uint32_t* group_count = reinterpret_cast<uint32_t*>(base + o_count);
-    uint32_t* group_first = reinterpret_cast<uint32_t*>(base + o_first);
-    uint32_t* list = reinterpret_cast<uint32_t*>(base + o_list);
-    uint8_t* d_tgt = dtgt ? target : base + o_tgt;
-    unsigned long long* d_map = reinterpret_cast<unsigned long long*>(dmap ? reinterpret_cast<uint8_t*>(block_sse) : base + o_map);
-    uint8_t* d_tier = dtier ? tier_map : base + o_tier;
-    uint32_t* host_n = refine_count_word();
+// The two front doors.  Each knows, before any device work, how many blocks the call judges (nb), the surface its first tier encodes
+// (bx x by blocks: a chain's last packed row may run past nb) and how much of scratch 0 it wants; prepare() queues whatever makes the
+// texels device-resident and returns the view.
+struct Front {
+    int64_t nb = 0;
+    int32_t bx = 0, by = 0;
+    size_t bytes = 0;
+    int nimg = 0;                                               // images a caller may ask per-image stats for (a chain)
+    bool packed = false;                                        // the first tier writes bx * by >= nb blocks: never straight into the target
+    virtual RefineView prepare(uint8_t* scratch, hipStream_t st) = 0;
+    virtual ~Front() = default;
+};
 
-    // a failure below is a C++ exception: what the call has queued by then is drained, so that the next call finds the scratch idle
-    struct Unwind { bool done; hipStream_t st; ~Unwind() { if (!done) { (void)hipStreamSynchronize(st); (void)hipGetLastError(); } } } unwind{false, st};
-
-    const uint8_t* d_src = s.ptr;
-    int64_t stride = s.stride;
-    if (!dsrc) {
-        ITW_CHECK(hipMemcpy2DAsync(base + o_src, src_pitch, s.ptr, (size_t)s.stride, row_bytes, (size_t)s.height, hipMemcpyHostToDevice, st));
-        d_src = base + o_src; stride = (int64_t)src_pitch;
+// one surface, read in place (a host surface: from its staged copy)
+struct SurfaceFront final : Front {
+    const rgba_surface& s;
+    bool dsrc;
+    size_t row_bytes, pitch;
+    SurfaceFront(int kind, const rgba_surface& surface) : s(surface)
+    {
+        bx = s.width / 4; by = s.height / 4; nb = (int64_t)bx * by;
+        dsrc = itw::is_device_pointer(s.ptr);
+        row_bytes = (size_t)s.width * itw::texel_bytes(kind); pitch = (row_bytes + 15) & ~(size_t)15;
+        bytes = dsrc ? 0 : pitch * (size_t)s.height;
     }
-    encode_resident(dxgi_format, first, d_src, stride, s.width, s.height, d_tgt);
+    RefineView prepare(uint8_t* scratch, hipStream_t st) override
+    {
+        if (dsrc) return RefineView{s.ptr, (int64_t)s.stride, bx, nullptr, nullptr, 0};
+        ITW_CHECK(hipMemcpy2DAsync(scratch, pitch, s.ptr, (size_t)s.stride, row_bytes, (size_t)s.height, hipMemcpyHostToDevice, st));
+        return RefineView{scratch, (int64_t)pitch, bx, nullptr, nullptr, 0};
+    }
+};
 
-    const dim3 blk(256);
-    hipLaunchKernelGGL(refine_begin_kernel, dim3(1), dim3(64), 0, st, acc);
-    ITW_CHECK(hipGetLastError());
-    if (kind == BCN_BC7) hipLaunchKernelGGL((refine_judge_kernel<BCN_BC7>), dim3((unsigned)groups), blk, 0, st, d_tgt, bx, (int32_t)nb, d_src, stride, mask,
-                                      (unsigned long long)budget, d_map, d_tier, group_count, acc);
-    else           hipLaunchKernelGGL((refine_judge_kernel<BCN_BC6H>), dim3((unsigned)groups), blk, 0, st, d_tgt, bx, (int32_t)nb, d_src, stride, mask,
-                                      (unsigned long long)budget, d_map, d_tier, group_count, acc);
-    ITW_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(refine_scan_kernel, dim3(1), blk, 0, st, group_count, groups, group_first, acc);
-    ITW_CHECK(hipGetLastError());
-    ITW_CHECK(hipMemcpyAsync(host_n, &acc->listed, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    ITW_CHECK(hipStreamSynchronize(st));
-    const int64_t n = (int64_t)*host_n;
-    if (n < 0 || n > nb) fail_msg("itwCompressImageRefined: %lld blocks listed of %lld", (long long)n, (long long)nb);
+// a chain: every image gathered, with edge replication, into ONE packed surface of min(1024, nb) blocks per row (chain.hip) -- the chain
+// is one population of blocks, so that the lists, the select and the refine tier see all of it at once
+struct ChainFront final : Front {
+    const rgba_surface* im;
+    int count, px;
+    bool dsrc;
+    int64_t pitch;
+    size_t o_table, o_extents, o_packed;
+    std::vector<size_t> o_stage;
+    std::vector<itw::ChainImage> desc;                          // lives until the call has synchronised
+    ChainFront(const char* who, int kind, const rgba_surface* images, int n) : im(images), count(n), px(itw::texel_bytes(kind))
+    {
+        packed = true; nimg = n;
+        dsrc = itw::is_device_pointer(im[0].ptr);
+        for (int i = 1; i < count; i++)
+            if (itw::is_device_pointer(im[i].ptr) != dsrc)
+                itw::fail_msg("%s: image %d is %s memory, image 0 %s: all images must be host or all device pointers", who, i,
+                              dsrc ? "host" : "device", dsrc ? "device" : "host");
+        if (dsrc) {
+            int cur = 0;
+            ITW_CHECK(hipGetDevice(&cur));
+            for (int i = 0; i < count; i++) {
+                hipPointerAttribute_t a = {};
+                ITW_CHECK(hipPointerGetAttributes(&a, im[i].ptr));
+                if (a.type == hipMemoryTypeDevice && a.device != cur)
+                    itw::fail_msg("%s: image %d lives on device %d, the calling thread's current device is %d", who, i, a.device, cur);
+            }
+        }
+        for (int i = 0; i < count; i++) nb += itw::image_blocks(im[i]);
+        bx = (int32_t)(nb < 1024 ? nb : 1024); by = (int32_t)((nb + bx - 1) / bx);
+        pitch = (int64_t)bx * 4 * px;
+        Carve c;
+        o_table = c.take((size_t)count * sizeof(itw::ChainImage));
+        o_extents = c.take((size_t)nb);
+        o_packed = c.take((size_t)pitch * 4 * (size_t)by);
+        if (!dsrc) {
+            o_stage.resize((size_t)count);
+            for (int i = 0; i < count; i++) o_stage[(size_t)i] = c.take((((size_t)im[i].width * px + 15) & ~(size_t)15) * (size_t)im[i].height);
+        }
+        bytes = c.used;
+    }
+    RefineView prepare(uint8_t* scratch, hipStream_t st) override
+    {
+        desc.resize((size_t)count);
+        int64_t first = 0;
+        for (int i = 0; i < count; i++) {
+            itw::ChainImage& d = desc[(size_t)i];
+            const size_t row_bytes = (size_t)im[i].width * px, row_pitch = (row_bytes + 15) & ~(size_t)15;
+            if (!dsrc) ITW_CHECK(hipMemcpy2DAsync(scratch + o_stage[(size_t)i], row_pitch, im[i].ptr, (size_t)im[i].stride, row_bytes, (size_t)im[i].height,
+                                                  hipMemcpyHostToDevice, st));
+            d.ptr = dsrc ? im[i].ptr : scratch + o_stage[(size_t)i];
+            d.stride = dsrc ? (int64_t)im[i].stride : (int64_t)row_pitch;
+            d.width = im[i].width; d.height = im[i].height;
+            d.first_block = first;
+            first += itw::image_blocks(im[i]);
+        }
+        itw::ChainImage* table = reinterpret_cast<itw::ChainImage*>(scratch + o_table);
+        ITW_CHECK(hipMemcpyAsync(table, desc.data(), desc.size() * sizeof(itw::ChainImage), hipMemcpyHostToDevice, st));
+        itw::launch_chain_gather(table, count, nb, bx, by, px, false, scratch + o_packed, pitch, st, scratch + o_extents);
+        return RefineView{scratch + o_packed, pitch, bx, scratch + o_extents, table, count};
+    }
+};
 
-    if (n > 0) {
+struct Outputs { uint8_t* target; void* stats; size_t stats_size; itw_refine_stats* image_stats; uint64_t* block_sse; uint8_t* tier_map; };
+
+// The core both calls and both front doors share: scratch, the first tier, the judge; one refine tier over a list; the way out.
+// Everything that needs the device.
+struct Call {
+    hipStream_t st;
+    int kind, px, dxgi_format;
+    const void* second;
+    uint32_t mask;
+    int64_t nb;
+    int32_t groups;
+    Outputs out;
+    bool dtgt, dstats, dmap, dtier, dimage;
+    RefineView v;
+    itw::RefineAcc* acc;
+    void* d_stats;
+    itw::RefineSelect* sel;
+    uint32_t *hist, *group_count, *group_first, *list, *host_n;
+    uint8_t *d_tgt, *d_tier, *front_scratch;
+    unsigned long long* d_map;
+    itw_refine_stats* d_image;
+    bool done = false;
+
+    Call(const Call&) = delete;
+    Call& operator=(const Call&) = delete;
+    // a failure is a C++ exception: what the call has queued by then is drained, so that the next call finds the scratch idle
+    ~Call() { if (!done) { (void)hipStreamSynchronize(st); (void)hipGetLastError(); } }
+
+    // `select`: room for the select's state (itwCompressImageRefinedTo).  Carves the scratch; queues nothing (a constructor that throws
+    // runs no destructor: the work starts in open())
+    Call(int kind_, Front& f, const Outputs& o, int dxgi_format_, const void* second_, uint32_t mask_, bool select)
+        : st((hipStream_t)itwGetStream()), kind(kind_), px(itw::texel_bytes(kind_)), dxgi_format(dxgi_format_), second(second_), mask(mask_), nb(f.nb),
+          groups((int32_t)((f.nb + 255) / 256)), out(o)
+    {
+        using namespace itw;
+        // the kernels take device memory; the judge and the commit load and store whole blocks as 16-B vectors
+        dtgt = !f.packed && is_device_pointer(out.target) && ((uintptr_t)out.target & 15) == 0;
+        dstats = is_device_pointer(out.stats);
+        dmap = out.block_sse && is_device_pointer(out.block_sse);
+        dtier = out.tier_map && is_device_pointer(out.tier_map);
+        dimage = out.image_stats && is_device_pointer(out.image_stats);
+        Carve c0;
+        const size_t o_acc = c0.take(sizeof(RefineAcc)), o_stats = c0.take(out.stats_size), o_sel = c0.take(select ? sizeof(RefineSelect) : 0),
+                     o_hist = c0.take(select ? (size_t)SELECT_MAX_PASSES * SELECT_BINS * 4 : 0), o_count = c0.take((size_t)groups * 4),
+                     o_first = c0.take((size_t)groups * 4), o_list = c0.take((size_t)nb * 4), o_front = c0.take(f.bytes),
+                     o_tgt = c0.take(dtgt ? 0 : (size_t)f.bx * f.by * 16), o_map = c0.take(dmap ? 0 : (size_t)nb * 8), o_tier = c0.take(dtier ? 0 : (size_t)nb),
+                     o_image = c0.take(out.image_stats && !dimage ? sizeof(itw_refine_stats) * (size_t)f.nimg : 0);
+        uint8_t* base = static_cast<uint8_t*>(refine_scratch(0, c0.used));
+        acc = reinterpret_cast<RefineAcc*>(base + o_acc);
+        d_stats = dstats ? out.stats : base + o_stats;
+        sel = reinterpret_cast<RefineSelect*>(base + o_sel);
+        hist = reinterpret_cast<uint32_t*>(base + o_hist);
+        group_count = reinterpret_cast<uint32_t*>(base + o_count);
+        group_first = reinterpret_cast<uint32_t*>(base + o_first);
+        list = reinterpret_cast<uint32_t*>(base + o_list);
+        d_tgt = dtgt ? out.target : base + o_tgt;
+        d_map = reinterpret_cast<unsigned long long*>(dmap ? reinterpret_cast<uint8_t*>(out.block_sse) : base + o_map);
+        d_tier = dtier ? out.tier_map : base + o_tier;
+        d_image = dimage ? out.image_stats : reinterpret_cast<itw_refine_stats*>(base + o_image);
+        host_n = refine_count_word();                           // [0] acc->listed, [1] acc->met
+        front_scratch = base + o_front;
+    }
+
+    // queues the texels, the first tier and the judge with `budget`
+    void open(Front& f, const void* first, unsigned long long budget)
+    {
+        using namespace itw;
+        v = f.prepare(front_scratch, st);
+        encode_resident(dxgi_format, first, v.src, v.stride, f.bx * 4, f.by * 4, d_tgt);
+
+        const dim3 grid((unsigned)groups), blk(256);
+        hipLaunchKernelGGL(refine_begin_kernel, dim3(1), dim3(64), 0, st, acc);
+        ITW_CHECK(hipGetLastError());
+        if (v.extents) {
+            if (kind == BCN_BC7) hipLaunchKernelGGL((refine_judge_kernel<BCN_BC7, true>), grid, blk, 0, st, d_tgt, v.blocks_x, (int32_t)nb, v.src, v.stride, mask,
+                                                    budget, d_map, d_tier, group_count, acc, v.extents);
+            else                 hipLaunchKernelGGL((refine_judge_kernel<BCN_BC6H, true>), grid, blk, 0, st, d_tgt, v.blocks_x, (int32_t)nb, v.src, v.stride, mask,
+                                                    budget, d_map, d_tier, group_count, acc, v.extents);
+        } else {
+            if (kind == BCN_BC7) hipLaunchKernelGGL((refine_judge_kernel<BCN_BC7, false>), grid, blk, 0, st, d_tgt, v.blocks_x, (int32_t)nb, v.src, v.stride, mask,
+                                                    budget, d_map, d_tier, group_count, acc, v.extents);
+            else                 hipLaunchKernelGGL((refine_judge_kernel<BCN_BC6H, false>), grid, blk, 0, st, d_tgt, v.blocks_x, (int32_t)nb, v.src, v.stride, mask,
+                                                    budget, d_map, d_tier, group_count, acc, v.extents);
+        }
+        ITW_CHECK(hipGetLastError());
+        if (out.image_stats) {
+            const int32_t dwords = (int32_t)(sizeof(itw_refine_stats) / 4) * v.nimg;
+            hipLaunchKernelGGL(refine_image_begin_kernel, dim3((unsigned)((dwords + 255) / 256)), blk, 0, st, reinterpret_cast<uint32_t*>(d_image), dwords);
+            ITW_CHECK(hipGetLastError());
+            hipLaunchKernelGGL((refine_image_stats_kernel<false>), grid, blk, 0, st, v.images, v.nimg, d_map, d_tier, (int32_t)nb, d_image);
+            ITW_CHECK(hipGetLastError());
+        }
+    }
+
+    // the refine tier over list[0, n), n > 0, which the caller's list kernel has queued: gather, encode, commit
+    void refine_listed(int64_t n)
+    {
+        using namespace itw;
         const int32_t pbx = (int32_t)(n < REFINE_PACKED_BLOCKS ? n : REFINE_PACKED_BLOCKS), pby = (int32_t)((n + pbx - 1) / pbx);
         const int32_t total = pbx * pby;
         const int64_t pitch = (int64_t)pbx * 4 * px;
@@ -510,80 +727,76 @@ void refine(int kind, const rgba_surface& s, uint8_t* target, int dxgi_format, c
         uint8_t* lbase = static_cast<uint8_t*>(refine_scratch(1, c1.used));
         uint8_t* packed = lbase + o_packed;
         uint8_t* refined = lbase + o_refined;
-        hipLaunchKernelGGL(refine_list_kernel, dim3((unsigned)groups), blk, 0, st, d_map, (int32_t)nb, (unsigned long long)budget, group_first, list);
-        ITW_CHECK(hipGetLastError());
-        const dim3 ggrid((unsigned)((total + 63) / 64));
-        if (kind == BCN_BC7) hipLaunchKernelGGL((refine_gather_kernel<4>), ggrid, blk, 0, st, list, (int32_t)n, total, pbx, d_src, stride, bx, packed, pitch);
-        else           hipLaunchKernelGGL((refine_gather_kernel<8>), ggrid, blk, 0, st, list, (int32_t)n, total, pbx, d_src, stride, bx, packed, pitch);
+        const dim3 blk(256), ggrid((unsigned)((total + 63) / 64)), cgrid((unsigned)((n + 255) / 256));
+        if (kind == BCN_BC7) hipLaunchKernelGGL((refine_gather_kernel<4>), ggrid, blk, 0, st, list, (int32_t)n, total, pbx, v.src, v.stride, v.blocks_x, packed, pitch);
+        else                 hipLaunchKernelGGL((refine_gather_kernel<8>), ggrid, blk, 0, st, list, (int32_t)n, total, pbx, v.src, v.stride, v.blocks_x, packed, pitch);
         ITW_CHECK(hipGetLastError());
         encode_resident(dxgi_format, second, packed, pitch, pbx * 4, pby * 4, refined);
-        const dim3 cgrid((unsigned)((n + 255) / 256));
-        if (kind == BCN_BC7) hipLaunchKernelGGL((refine_commit_kernel<BCN_BC7>), cgrid, blk, 0, st, list, (int32_t)n, pbx, packed, pitch, refined, mask, d_tgt, d_map, d_tier, acc);
-        else           hipLaunchKernelGGL((refine_commit_kernel<BCN_BC6H>), cgrid, blk, 0, st, list, (int32_t)n, pbx, packed, pitch, refined, mask, d_tgt, d_map, d_tier, acc);
+        if (v.extents) {
+            if (kind == BCN_BC7) hipLaunchKernelGGL((refine_commit_kernel<BCN_BC7, true>), cgrid, blk, 0, st, list, (int32_t)n, pbx, packed, pitch, refined, mask, d_tgt, d_map, d_tier, acc, v.extents);
+            else                 hipLaunchKernelGGL((refine_commit_kernel<BCN_BC6H, true>), cgrid, blk, 0, st, list, (int32_t)n, pbx, packed, pitch, refined, mask, d_tgt, d_map, d_tier, acc, v.extents);
+        } else {
+            if (kind == BCN_BC7) hipLaunchKernelGGL((refine_commit_kernel<BCN_BC7, false>), cgrid, blk, 0, st, list, (int32_t)n, pbx, packed, pitch, refined, mask, d_tgt, d_map, d_tier, acc, v.extents);
+            else                 hipLaunchKernelGGL((refine_commit_kernel<BCN_BC6H, false>), cgrid, blk, 0, st, list, (int32_t)n, pbx, packed, pitch, refined, mask, d_tgt, d_map, d_tier, acc, v.extents);
+        }
         ITW_CHECK(hipGetLastError());
     }
-    hipLaunchKernelGGL(refine_finish_kernel, dim3(1), dim3(64), 0, st, acc, (unsigned long long)nb, d_stats);
-    ITW_CHECK(hipGetLastError());
 
-    if (!dtgt) ITW_CHECK(hipMemcpyAsync(target, d_tgt, (size_t)nb * 16, hipMemcpyDefault, st));
-    if (!dstats) ITW_CHECK(hipMemcpyAsync(stats, d_stats, sizeof(itw_refine_stats), hipMemcpyDeviceToHost, st));
-    if (block_sse && !dmap) ITW_CHECK(hipMemcpyAsync(block_sse, d_map, (size_t)nb * 8, hipMemcpyDeviceToHost, st));
-    if (tier_map && !dtier) ITW_CHECK(hipMemcpyAsync(tier_map, d_tier, (size_t)nb, hipMemcpyDeviceToHost, st));
-    ITW_CHECK(hipStreamSynchronize(st));
-    unwind.done = true;
-}
+    // behind the caller's finish kernel: the per-image fields of the stream written, then whatever the caller did not pass device memory for
+    void close()
+    {
+        using namespace itw;
+        if (out.image_stats) {
+            hipLaunchKernelGGL((refine_image_stats_kernel<true>), dim3((unsigned)groups), dim3(256), 0, st, v.images, v.nimg, d_map, d_tier, (int32_t)nb, d_image);
+            ITW_CHECK(hipGetLastError());
+        }
+        if (!dtgt) ITW_CHECK(hipMemcpyAsync(out.target, d_tgt, (size_t)nb * 16, hipMemcpyDefault, st));
+        if (!dstats) ITW_CHECK(hipMemcpyAsync(out.stats, d_stats, out.stats_size, hipMemcpyDeviceToHost, st));
+        if (out.image_stats && !dimage) ITW_CHECK(hipMemcpyAsync(out.image_stats, d_image, sizeof(itw_refine_stats) * (size_t)v.nimg, hipMemcpyDeviceToHost, st));
+        if (out.block_sse && !dmap) ITW_CHECK(hipMemcpyAsync(out.block_sse, d_map, (size_t)nb * 8, hipMemcpyDeviceToHost, st));
+        if (out.tier_map && !dtier) ITW_CHECK(hipMemcpyAsync(out.tier_map, d_tier, (size_t)nb, hipMemcpyDeviceToHost, st));
+        ITW_CHECK(hipStreamSynchronize(st));
+        done = true;
+    }
+};
 
-// itwCompressImageRefinedTo: refine() with the budget of every round chosen on the device
-void refine_to(int kind, const rgba_surface& s, uint8_t* target, int dxgi_format, const void* first, const void* second, uint32_t mask,
-               const itw_refine_policy& policy, itw_refine_target_stats* stats, uint64_t* block_sse, uint8_t* tier_map)
+void refine(const char* who, int kind, Front& f, const Outputs& out, int dxgi_format, const void* first, const void* second, uint32_t mask, uint64_t budget)
 {
     using namespace itw;
-    hipStream_t st = (hipStream_t)itwGetStream();
-    const int px = texel_bytes(kind);
-    const int bx = s.width / 4, by = s.height / 4;
-    const int64_t nb = (int64_t)bx * by;
-    const int32_t groups = (int32_t)((nb + 255) / 256);
-    const size_t row_bytes = (size_t)s.width * px, src_pitch = (row_bytes + 15) & ~(size_t)15;
-    const bool dsrc = is_device_pointer(s.ptr), dtgt = is_device_pointer(target) && ((uintptr_t)target & 15) == 0,
-               dstats = is_device_pointer(stats), dmap = block_sse && is_device_pointer(block_sse), dtier = tier_map && is_device_pointer(tier_map);
-
-    Carve c0;
-    const size_t o_acc = c0.take(sizeof(RefineAcc)), o_stats = c0.take(sizeof(itw_refine_target_stats)), o_sel = c0.take(sizeof(RefineSelect)),
-                 o_hist = c0.take((size_t)SELECT_MAX_PASSES * SELECT_BINS * 4), o_count = c0.take((size_t)groups * 4),
-                 o_first = c0.take((size_t)groups * 4), o_list = c0.take((size_t)nb * 4), o_src = c0.take(dsrc ? 0 : src_pitch * (size_t)s.height),
-                 o_tgt = c0.take(dtgt ? 0 : (size_t)nb * 16), o_map = c0.take(dmap ? 0 : (size_t)nb * 8), o_tier = c0.take(dtier ? 0 : (size_t)nb);
-    uint8_t* base = static_cast<uint8_t*>(refine_scratch(0, c0.used));
-    RefineAcc* acc = reinterpret_cast<RefineAcc*>(base + o_acc);
-    itw_refine_target_stats* d_stats = dstats ? stats : reinterpret_cast<itw_refine_target_stats*>(base + o_stats);
-    RefineSelect* sel = reinterpret_cast<RefineSelect*>(base + o_sel);
-    uint32_t* hist = reinterpret_cast<uint32_t*>(base + o_hist);
-    uint32_t* group_count = reinterpret_cast<uint32_t*>(base + o_count);
-    uint32_t* group_first = reinterpret_cast<uint32_t*>(base + o_first);
-    uint32_t* list = reinterpret_cast<uint32_t*>(base + o_list);
-    uint8_t* d_tgt = dtgt ? target : base + o_tgt;
-    unsigned long long* d_map = reinterpret_cast<unsigned long long*>(dmap ? reinterpret_cast<uint8_t*>(block_sse) : base + o_map);
-    uint8_t* d_tier = dtier ? tier_map : base + o_tier;
-    uint32_t* host_n = refine_count_word();                     // [0] acc->listed, [1] acc->met
-
-    struct Unwind { bool done; hipStream_t st; ~Unwind() { if (!done) { (void)hipStreamSynchronize(st); (void)hipGetLastError(); } } } unwind{false, st};
-
-    const uint8_t* d_src = s.ptr;
-    int64_t stride = s.stride;
-    if (!dsrc) {
-        ITW_CHECK(hipMemcpy2DAsync(base + o_src, src_pitch, s.ptr, (size_t)s.stride, row_bytes, (size_t)s.height, hipMemcpyHostToDevice, st));
-        d_src = base + o_src; stride = (int64_t)src_pitch;
-    }
-    encode_resident(dxgi_format, first, d_src, stride, s.width, s.height, d_tgt);
-
-    // the judge with a budget that lists nothing: the maps, sse_first, worst_first, and worst_final for a call that runs no round
+    Call c(kind, f, out, dxgi_format, second, mask, false);
+    c.open(f, first, (unsigned long long)budget);
     const dim3 blk(256);
-    hipLaunchKernelGGL(refine_begin_kernel, dim3(1), dim3(64), 0, st, acc);
+    hipLaunchKernelGGL(refine_scan_kernel, dim3(1), blk, 0, c.st, c.group_count, c.groups, c.group_first, c.acc);
     ITW_CHECK(hipGetLastError());
-    if (kind == BCN_BC7) hipLaunchKernelGGL((refine_judge_kernel<BCN_BC7>), dim3((unsigned)groups), blk, 0, st, d_tgt, bx, (int32_t)nb, d_src, stride, mask,
-                                      ~0ull, d_map, d_tier, group_count, acc);
-    else           hipLaunchKernelGGL((refine_judge_kernel<BCN_BC6H>), dim3((unsigned)groups), blk, 0, st, d_tgt, bx, (int32_t)nb, d_src, stride, mask,
-                                      ~0ull, d_map, d_tier, group_count, acc);
+    ITW_CHECK(hipMemcpyAsync(c.host_n, &c.acc->listed, sizeof(uint32_t), hipMemcpyDeviceToHost, c.st));
+    ITW_CHECK(hipStreamSynchronize(c.st));
+    const int64_t n = (int64_t)*c.host_n;
+    if (n < 0 || n > c.nb) fail_msg("%s: %lld blocks listed of %lld", who, (long long)n, (long long)c.nb);
+    if (n > 0) {
+        hipLaunchKernelGGL(refine_list_kernel, dim3((unsigned)c.groups), blk, 0, c.st, c.d_map, (int32_t)c.nb, (unsigned long long)budget, c.group_first, c.list);
+        ITW_CHECK(hipGetLastError());
+        c.refine_listed(n);
+    }
+    hipLaunchKernelGGL(refine_finish_kernel, dim3(1), dim3(64), 0, c.st, c.acc, (unsigned long long)c.nb, static_cast<itw_refine_stats*>(c.d_stats));
     ITW_CHECK(hipGetLastError());
+    c.close();
+}
+
+// itwCompressImage[Chain]RefinedTo: refine() with the budget of every round chosen on the device
+void refine_to(const char* who, int kind, Front& f, const Outputs& out, int dxgi_format, const void* first, const void* second, uint32_t mask,
+               const itw_refine_policy& policy)
+{
+    using namespace itw;
+    // the judge with a budget that lists nothing: the maps, sse_first, worst_first, and worst_final for a call that runs no round
+    Call c(kind, f, out, dxgi_format, second, mask, true);
+    c.open(f, first, ~0ull);
+    hipStream_t st = c.st;
+    const int64_t nb = c.nb;
+    const int32_t groups = c.groups;
+    RefineAcc* acc = c.acc;
+    RefineSelect* sel = c.sel;
+    uint32_t* host_n = c.host_n;
+    const dim3 blk(256);
 
     const bool single = policy.target_total_sse == UINT64_MAX;  // policy A
     const int passes = select_passes(kind);
@@ -596,59 +809,36 @@ void refine_to(int kind, const rgba_surface& s, uint8_t* target, int dxgi_format
         const uint64_t q = j < 4 ? (uint64_t)((nb >> (4 - j)) > 0 ? (nb >> (4 - j)) : 1) : (uint64_t)nb;
         const uint64_t k = single ? policy.max_listed : (cap_left < q ? cap_left : q);
         // the whole round up to its list length goes on the stream at once; what it does is decided by device words
-        hipLaunchKernelGGL(refine_round_begin_kernel, dim3(SELECT_MAX_PASSES * SELECT_BINS / 256), blk, 0, st, acc, sel, hist, (int32_t)j,
+        hipLaunchKernelGGL(refine_round_begin_kernel, dim3(SELECT_MAX_PASSES * SELECT_BINS / 256), blk, 0, st, acc, sel, c.hist, (int32_t)j,
                            (unsigned long long)k, (unsigned long long)policy.target_total_sse, (int32_t)(single ? 0 : 1));
         ITW_CHECK(hipGetLastError());
         for (int p = passes - 1; p >= 0; p--) {
-            hipLaunchKernelGGL(select_hist_kernel, hgrid, blk, 0, st, d_map, d_tier, (int32_t)nb, (int32_t)(p * SELECT_BITS), acc, sel, hist + p * SELECT_BINS);
+            hipLaunchKernelGGL(select_hist_kernel, hgrid, blk, 0, st, c.d_map, c.d_tier, (int32_t)nb, (int32_t)(p * SELECT_BITS), acc, sel, c.hist + p * SELECT_BINS);
             ITW_CHECK(hipGetLastError());
-            hipLaunchKernelGGL(select_scan_kernel, dim3(1), blk, 0, st, hist + p * SELECT_BINS, (int32_t)(p * SELECT_BITS), (int32_t)(p == 0), (int32_t)j, acc, sel);
+            hipLaunchKernelGGL(select_scan_kernel, dim3(1), blk, 0, st, c.hist + p * SELECT_BINS, (int32_t)(p * SELECT_BITS), (int32_t)(p == 0), (int32_t)j, acc, sel);
             ITW_CHECK(hipGetLastError());
         }
-        hipLaunchKernelGGL(refine_count_kernel, dim3((unsigned)groups), blk, 0, st, d_map, d_tier, (int32_t)nb, &sel->budget[j], group_count, acc);
+        hipLaunchKernelGGL(refine_count_kernel, dim3((unsigned)groups), blk, 0, st, c.d_map, c.d_tier, (int32_t)nb, &sel->budget[j], c.group_count, acc);
         ITW_CHECK(hipGetLastError());
-        hipLaunchKernelGGL(refine_scan_kernel, dim3(1), blk, 0, st, group_count, groups, group_first, acc);
+        hipLaunchKernelGGL(refine_scan_kernel, dim3(1), blk, 0, st, c.group_count, groups, c.group_first, acc);
         ITW_CHECK(hipGetLastError());
         ITW_CHECK(hipMemcpyAsync(host_n, &acc->listed, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         ITW_CHECK(hipStreamSynchronize(st));
         if (host_n[1]) break;                                   // the target was met before this round: it ran nothing
         const int64_t n = (int64_t)host_n[0];
-        if (n < 0 || n > nb || (uint64_t)n > k) fail_msg("itwCompressImageRefinedTo: %lld blocks listed of %lld, rank %llu", (long long)n, (long long)nb, (unsigned long long)k);
+        if (n < 0 || n > nb || (uint64_t)n > k) fail_msg("%s: %lld blocks listed of %lld, rank %llu", who, (long long)n, (long long)nb, (unsigned long long)k);
         r.rounds = (uint32_t)j + 1u;
         r.listed[j] = (uint64_t)n;
         r.total_listed += (uint64_t)n;
         if (cap_left != UINT64_MAX) cap_left -= (uint64_t)n;
         if (n == 0) continue;
-
-        const int32_t pbx = (int32_t)(n < REFINE_PACKED_BLOCKS ? n : REFINE_PACKED_BLOCKS), pby = (int32_t)((n + pbx - 1) / pbx);
-        const int32_t total = pbx * pby;
-        const int64_t pitch = (int64_t)pbx * 4 * px;
-        Carve c1;
-        const size_t o_packed = c1.take((size_t)pitch * 4 * pby), o_refined = c1.take((size_t)total * 16);
-        uint8_t* lbase = static_cast<uint8_t*>(refine_scratch(1, c1.used));
-        uint8_t* packed = lbase + o_packed;
-        uint8_t* refined = lbase + o_refined;
-        hipLaunchKernelGGL(refine_list_to_kernel, dim3((unsigned)groups), blk, 0, st, d_map, d_tier, (int32_t)nb, &sel->budget[j], group_first, list);
+        hipLaunchKernelGGL(refine_list_to_kernel, dim3((unsigned)groups), blk, 0, st, c.d_map, c.d_tier, (int32_t)nb, &sel->budget[j], c.group_first, c.list);
         ITW_CHECK(hipGetLastError());
-        const dim3 ggrid((unsigned)((total + 63) / 64));
-        if (kind == BCN_BC7) hipLaunchKernelGGL((refine_gather_kernel<4>), ggrid, blk, 0, st, list, (int32_t)n, total, pbx, d_src, stride, bx, packed, pitch);
-        else           hipLaunchKernelGGL((refine_gather_kernel<8>), ggrid, blk, 0, st, list, (int32_t)n, total, pbx, d_src, stride, bx, packed, pitch);
-        ITW_CHECK(hipGetLastError());
-        encode_resident(dxgi_format, second, packed, pitch, pbx * 4, pby * 4, refined);
-        const dim3 cgrid((unsigned)((n + 255) / 256));
-        if (kind == BCN_BC7) hipLaunchKernelGGL((refine_commit_kernel<BCN_BC7>), cgrid, blk, 0, st, list, (int32_t)n, pbx, packed, pitch, refined, mask, d_tgt, d_map, d_tier, acc);
-        else           hipLaunchKernelGGL((refine_commit_kernel<BCN_BC6H>), cgrid, blk, 0, st, list, (int32_t)n, pbx, packed, pitch, refined, mask, d_tgt, d_map, d_tier, acc);
-        ITW_CHECK(hipGetLastError());
+        c.refine_listed(n);
     }
-    hipLaunchKernelGGL(refine_finish_to_kernel, dim3(1), dim3(64), 0, st, acc, sel, (unsigned long long)nb, r, d_stats);
+    hipLaunchKernelGGL(refine_finish_to_kernel, dim3(1), dim3(64), 0, st, acc, sel, (unsigned long long)nb, r, static_cast<itw_refine_target_stats*>(c.d_stats));
     ITW_CHECK(hipGetLastError());
-
-    if (!dtgt) ITW_CHECK(hipMemcpyAsync(target, d_tgt, (size_t)nb * 16, hipMemcpyDefault, st));
-    if (!dstats) ITW_CHECK(hipMemcpyAsync(stats, d_stats, sizeof(itw_refine_target_stats), hipMemcpyDeviceToHost, st));
-    if (block_sse && !dmap) ITW_CHECK(hipMemcpyAsync(block_sse, d_map, (size_t)nb * 8, hipMemcpyDeviceToHost, st));
-    if (tier_map && !dtier) ITW_CHECK(hipMemcpyAsync(tier_map, d_tier, (size_t)nb, hipMemcpyDeviceToHost, st));
-    ITW_CHECK(hipStreamSynchronize(st));
-    unwind.done = true;
+    c.close();
 }
 
 // the checks both entries share, none of which needs a device; returns the block kind
@@ -673,6 +863,41 @@ int check_refined_call(const char* who, const rgba_surface* source, const uint8_
     return kind;
 }
 
+// the same for a chain: the refined calls' checks, then itwCompressImageChainEx's, then the chain's block count; returns the block kind
+int check_refined_chain_call(const char* who, const rgba_surface* images, int count, const uint8_t* target, int dxgi_format, const void* first_settings,
+                             const void* refine_settings, uint32_t channel_mask, const void* stats, size_t stats_bytes, size_t stats_size,
+                             const char* stats_type, const itw_refine_stats* image_stats, const uint64_t* block_sse)
+{
+    const int kind = itw::decode_kind(dxgi_format);
+    if (kind != itw::BCN_BC7 && kind != itw::BCN_BC6H) itw::fail_msg("%s: DXGI format %d has one encoder only (BC7 and BC6H have presets to refine with)", who, dxgi_format);
+    if (!first_settings || !refine_settings) itw::fail_msg("%s: null settings for the %s tier", who, first_settings ? "refine" : "first");
+    itw::chain_check(images, count, target, dxgi_format);       // count, null pointers, sizes, strides
+    if (!stats) itw::fail_msg("%s: null stats", who);
+    if (stats_bytes != stats_size) itw::fail_msg("%s: stats_bytes %zu != sizeof(%s) = %zu", who, stats_bytes, stats_type, stats_size);
+    if (((uintptr_t)stats & 7) || ((uintptr_t)image_stats & 7) || ((uintptr_t)block_sse & 7))
+        itw::fail_msg("%s: stats, image_stats and block_sse must be 8-byte aligned", who);
+    if (channel_mask == 0 || channel_mask > 15) itw::fail_msg("%s: channel mask %u (1..15: bit 0 = R .. bit 3 = A)", who, channel_mask);
+    int64_t total = 0;
+    for (int i = 0; i < count; i++) {
+        total += itw::image_blocks(images[i]);
+        if (total > (int64_t)ITW_MEASURE_MAX_BLOCKS)
+            itw::fail_msg("%s: images 0 .. %d are more than %lld blocks", who, i, (long long)ITW_MEASURE_MAX_BLOCKS);
+    }
+    return kind;
+}
+
+// itwPsnrToTotalSse over n = texels x selected channels
+uint64_t psnr_to_total_sse(int dxgi_format, double texels, uint32_t channel_mask, double psnr_db)
+{
+    const int kind = itw::decode_kind(dxgi_format);
+    int channels = 0;
+    for (int c = 0; c < 4; c++) channels += (channel_mask >> c) & 1u;
+    if (kind == itw::BCN_NONE || kind == itw::BCN_BC6H || channels == 0 || !(texels >= 1.0) || !std::isfinite(psnr_db)) return UINT64_MAX;
+    const double peak = (kind == itw::BCN_BC4S || kind == itw::BCN_BC5S) ? 254.0 : 255.0;      // as itwStatsPsnr
+    const double sse = std::floor(peak * peak * (texels * (double)channels) / std::pow(10.0, psnr_db / 10.0));
+    return sse >= 18446744073709551615.0 ? UINT64_MAX : (uint64_t)sse;
+}
+
 } // namespace
 
 extern "C" bool itwCompressImageRefined(const rgba_surface* source, uint8_t* target, int dxgi_format, const void* first_settings,
@@ -681,9 +906,12 @@ extern "C" bool itwCompressImageRefined(const rgba_surface* source, uint8_t* tar
 {
     itw::clear_failure();
     return itw::guarded([&] {
-        const int kind = check_refined_call("itwCompressImageRefined", source, target, dxgi_format, first_settings, refine_settings, channel_mask, stats,
+        const char* who = "itwCompressImageRefined";
+        const int kind = check_refined_call(who, source, target, dxgi_format, first_settings, refine_settings, channel_mask, stats,
                                             stats_bytes, sizeof(itw_refine_stats), "itw_refine_stats", block_sse);
-        refine(kind, *source, target, dxgi_format, first_settings, refine_settings, channel_mask, max_block_sse, stats, block_sse, tier_map);
+        SurfaceFront front(kind, *source);
+        refine(who, kind, front, Outputs{target, stats, sizeof(itw_refine_stats), nullptr, block_sse, tier_map}, dxgi_format, first_settings,
+               refine_settings, channel_mask, max_block_sse);
     });
 }
 
@@ -693,22 +921,65 @@ extern "C" bool itwCompressImageRefinedTo(const rgba_surface* source, uint8_t* t
 {
     itw::clear_failure();
     return itw::guarded([&] {
-        if (!policy) itw::fail_msg("itwCompressImageRefinedTo: null policy");
+        const char* who = "itwCompressImageRefinedTo";
+        if (!policy) itw::fail_msg("%s: null policy", who);
         if (policy_bytes != sizeof(itw_refine_policy))
-            itw::fail_msg("itwCompressImageRefinedTo: policy_bytes %zu != sizeof(itw_refine_policy) = %zu", policy_bytes, sizeof(itw_refine_policy));
-        const int kind = check_refined_call("itwCompressImageRefinedTo", source, target, dxgi_format, first_settings, refine_settings, channel_mask, stats,
+            itw::fail_msg("%s: policy_bytes %zu != sizeof(itw_refine_policy) = %zu", who, policy_bytes, sizeof(itw_refine_policy));
+        const int kind = check_refined_call(who, source, target, dxgi_format, first_settings, refine_settings, channel_mask, stats,
                                             stats_bytes, sizeof(itw_refine_target_stats), "itw_refine_target_stats", block_sse);
-        refine_to(kind, *source, target, dxgi_format, first_settings, refine_settings, channel_mask, *policy, stats, block_sse, tier_map);
+        SurfaceFront front(kind, *source);
+        refine_to(who, kind, front, Outputs{target, stats, sizeof(itw_refine_target_stats), nullptr, block_sse, tier_map}, dxgi_format, first_settings,
+                  refine_settings, channel_mask, *policy);
+    });
+}
+
+extern "C" bool itwCompressImageChainRefined(const rgba_surface* images, int count, uint8_t* target, int dxgi_format, const void* first_settings,
+                                             const void* refine_settings, uint32_t channel_mask, uint64_t max_block_sse, itw_refine_stats* stats,
+                                             size_t stats_bytes, itw_refine_stats* image_stats, uint64_t* block_sse, uint8_t* tier_map)
+{
+    itw::clear_failure();
+    return itw::guarded([&] {
+        const char* who = "itwCompressImageChainRefined";
+        const int kind = check_refined_chain_call(who, images, count, target, dxgi_format, first_settings, refine_settings, channel_mask, stats,
+                                                  stats_bytes, sizeof(itw_refine_stats), "itw_refine_stats", image_stats, block_sse);
+        ChainFront front(who, kind, images, count);
+        refine(who, kind, front, Outputs{target, stats, sizeof(itw_refine_stats), image_stats, block_sse, tier_map}, dxgi_format, first_settings,
+               refine_settings, channel_mask, max_block_sse);
+    });
+}
+
+extern "C" bool itwCompressImageChainRefinedTo(const rgba_surface* images, int count, uint8_t* target, int dxgi_format, const void* first_settings,
+                                               const void* refine_settings, uint32_t channel_mask, const itw_refine_policy* policy,
+                                               size_t policy_bytes, itw_refine_target_stats* stats, size_t stats_bytes,
+                                               itw_refine_stats* image_stats, uint64_t* block_sse, uint8_t* tier_map)
+{
+    itw::clear_failure();
+    return itw::guarded([&] {
+        const char* who = "itwCompressImageChainRefinedTo";
+        if (!policy) itw::fail_msg("%s: null policy", who);
+        if (policy_bytes != sizeof(itw_refine_policy))
+            itw::fail_msg("%s: policy_bytes %zu != sizeof(itw_refine_policy) = %zu", who, policy_bytes, sizeof(itw_refine_policy));
+        const int kind = check_refined_chain_call(who, images, count, target, dxgi_format, first_settings, refine_settings, channel_mask, stats,
+                                                  stats_bytes, sizeof(itw_refine_target_stats), "itw_refine_target_stats", image_stats, block_sse);
+        ChainFront front(who, kind, images, count);
+        refine_to(who, kind, front, Outputs{target, stats, sizeof(itw_refine_target_stats), image_stats, block_sse, tier_map}, dxgi_format,
+                  first_settings, refine_settings, channel_mask, *policy);
     });
 }
 
 extern "C" uint64_t itwPsnrToTotalSse(int dxgi_format, int width, int height, uint32_t channel_mask, double psnr_db)
 {
-    const int kind = itw::decode_kind(dxgi_format);
-    int channels = 0;
-    for (int c = 0; c < 4; c++) channels += (channel_mask >> c) & 1u;
-    if (kind == itw::BCN_NONE || kind == itw::BCN_BC6H || channels == 0 || width < 1 || height < 1 || !std::isfinite(psnr_db)) return UINT64_MAX;
-    const double peak = (kind == itw::BCN_BC4S || kind == itw::BCN_BC5S) ? 254.0 : 255.0;      // as itwStatsPsnr
-    const double sse = std::floor(peak * peak * ((double)width * (double)height * (double)channels) / std::pow(10.0, psnr_db / 10.0));
-    return sse >= 18446744073709551615.0 ? UINT64_MAX : (uint64_t)sse;
+    if (width < 1 || height < 1) return UINT64_MAX;
+    return psnr_to_total_sse(dxgi_format, (double)width * (double)height, channel_mask, psnr_db);
+}
+
+extern "C" uint64_t itwChainPsnrToTotalSse(const rgba_surface* images, int count, int dxgi_format, uint32_t channel_mask, double psnr_db)
+{
+    if (!images || count < 1) return UINT64_MAX;
+    double texels = 0.0;
+    for (int i = 0; i < count; i++) {
+        if (images[i].width < 1 || images[i].height < 1) return UINT64_MAX;
+        texels += (double)images[i].width * (double)images[i].height;
+    }
+    return psnr_to_total_sse(dxgi_format, texels, channel_mask, psnr_db);
 }

@@ -17,4 +17,5 @@ from .abi import (  # noqa: F401
     chain_bytes, compress_chain, mip_chain, decode_chain, decode_image, load_dds, dds_images,
     ErrorStats, OWN_CHANNELS, measure, measure_async, measure_chain, stats_from_tensor,
     RefineStats, compress_refined, RefinePolicy, RefineTargetStats, compress_refined_to, psnr_to_total_sse,
+    compress_chain_refined, compress_chain_refined_to, chain_psnr_to_total_sse,
 )

@@ -23,7 +23,7 @@ EXPORTED_SYMBOLS = tuple(
     + ["GetProcessorCount", "InitWin32Threads", "DestroyThreads", "GetBytesPerBlock", "CompressImageMT", "CompressImageST",
        "CompressImageBC1", "CompressImageBC3", "CompressImageBC4", "CompressImageBC5", "CompressImageBC4S", "CompressImageBC5S"]
     + ["CompressImageBC7_" + p for p in BC7_PROFILES] + ["CompressImageBC6H_" + p for p in BC6H_PROFILES]
-    + ["itwCompressImageSliced", "itwCompressImageSlicedEx", "itwChainBytes", "itwCompressImageChain", "itwCompressImageChainEx", "itwCompressImageRefined", "itwCompressImageRefinedTo", "itwPsnrToTotalSse", "itwSetSliceWindow", "itwSliceWindow", "itwSliceWindowFor", "itwPadToMultipleOf4", "itwFreeSurface", "itwPadToMultipleOf4Device",
+    + ["itwCompressImageSliced", "itwCompressImageSlicedEx", "itwChainBytes", "itwCompressImageChain", "itwCompressImageChainEx", "itwCompressImageRefined", "itwCompressImageRefinedTo", "itwPsnrToTotalSse", "itwCompressImageChainRefined", "itwCompressImageChainRefinedTo", "itwChainPsnrToTotalSse", "itwSetSliceWindow", "itwSliceWindow", "itwSliceWindowFor", "itwPadToMultipleOf4", "itwFreeSurface", "itwPadToMultipleOf4Device",
        "itwConvertToRGBA8Device", "itwConvertToRGBA16FDevice"]
     # include/itw_multigpu.h: one surface over all GPUs, one process
     + ["itwMultiGpuRanks", "itwMultiGpuTransport", "itwMultiGpuPeerLinks", "itwCompressImageMultiGPU", "itwCompressImageMultiGPUEx", "itwCompressImageMultiGPUBands",
@@ -304,6 +304,14 @@ def _load(path, hooks):
         L.itwCompressImageRefinedTo.restype = C.c_bool
         L.itwPsnrToTotalSse.argtypes = [C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_double]
         L.itwPsnrToTotalSse.restype = C.c_uint64
+        L.itwCompressImageChainRefined.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64,
+                                                   C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.itwCompressImageChainRefined.restype = C.c_bool
+        L.itwCompressImageChainRefinedTo.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_size_t,
+                                                     C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.itwCompressImageChainRefinedTo.restype = C.c_bool
+        L.itwChainPsnrToTotalSse.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint32, C.c_double]
+        L.itwChainPsnrToTotalSse.restype = C.c_uint64
         L.itwSetSliceWindow.argtypes = [C.c_int]
         L.itwSetSliceWindow.restype = None
         L.itwSliceWindow.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int64]
@@ -1116,3 +1124,92 @@ def compress_refined_to(fmt, img, first, refine, max_listed=None, share=None, ta
     if not ok:
         raise ValueError("itwCompressImageRefinedTo: " + (last_error() or "failed"))
     return (out, st) + ((bmap,) if want_block_map else ()) + ((tmap,) if want_tier_map else ())
+
+
+def chain_psnr_to_total_sse(fmt, images, psnr_db, channels=None):
+    """itwChainPsnrToTotalSse: psnr_to_total_sse over all texels of a chain (arrays / tensors, or (height, width) tuples)."""
+    arr = (RgbaSurface * max(1, len(images)))(*[RgbaSurface(None, s[1], s[0], 0) if isinstance(s, tuple) else _surfaces([s])[0] for s in images])
+    return int(lib().itwChainPsnrToTotalSse(C.cast(arr, C.c_void_p), len(images), DXGI_FORMAT[fmt], _channel_mask("rgb" if channels is None else channels),
+                                            float(psnr_db)))
+
+
+def _chain_refined(name, fmt, images, first, refine, channels, want_block_map, want_tier_map, want_image_stats, stats, middle):
+    """The two chain calls: `middle(L)` gives the arguments between channel_mask and stats."""
+    import numpy as np
+    base = fmt.split("_")[0]
+    profile, settings_type = (bc7_profile, Bc7Settings) if base == "bc7" else (bc6h_profile, Bc6hSettings)
+    s1 = first if isinstance(first, settings_type) else profile(first)
+    s2 = refine if isinstance(refine, settings_type) else profile(refine)
+    mask = _channel_mask("rgb" if channels is None else channels)
+    for img in images:
+        _check_texel_type(fmt, img)
+    n = len(images)
+    nb = sum(((img.shape[1] + 3) // 4) * ((img.shape[0] + 3) // 4) for img in images)
+    arr = _surfaces(images)
+    L = lib()
+    call = getattr(L, name)
+    if not (images and hasattr(images[0], "data_ptr")):
+        out = np.empty(nb * 16, dtype=np.uint8)
+        bmap = np.empty(nb, dtype=np.uint64) if want_block_map else None
+        tmap = np.empty(nb, dtype=np.uint8) if want_tier_map else None
+        per = (RefineStats * max(1, n))() if want_image_stats else None
+        ptr = lambda a: a.ctypes.data if a is not None else None
+        ok = call(C.cast(arr, C.c_void_p), n, ptr(out), DXGI_FORMAT[fmt], C.addressof(s1), C.addressof(s2), mask, *middle,
+                  C.addressof(stats), C.sizeof(stats), C.addressof(per) if per is not None else None, ptr(bmap), ptr(tmap))
+        per = [RefineStats.from_buffer_copy(bytes(per[i])) for i in range(n)] if want_image_stats else None
+    else:
+        import torch
+        dev = images[0].device
+        out = torch.empty(nb * 16, dtype=torch.uint8, device=dev)
+        bmap = torch.empty(nb, dtype=torch.int64, device=dev) if want_block_map else None
+        tmap = torch.empty(nb, dtype=torch.uint8, device=dev) if want_tier_map else None
+        raw = torch.empty((max(1, n), C.sizeof(RefineStats) // 8), dtype=torch.int64, device=dev) if want_image_stats else None
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        with torch.cuda.device(dev):
+            L.itwSetStream(torch.cuda.current_stream(dev).cuda_stream)
+            ok = call(C.cast(arr, C.c_void_p), n, ptr(out), DXGI_FORMAT[fmt], C.addressof(s1), C.addressof(s2), mask, *middle,
+                      C.addressof(stats), C.sizeof(stats), ptr(raw), ptr(bmap), ptr(tmap))
+        per = None
+        if want_image_stats and ok:
+            host = raw.cpu().numpy()
+            per = [RefineStats.from_buffer_copy(host[i].tobytes()) for i in range(n)]
+    if not ok:
+        raise ValueError(name + ": " + (last_error() or "failed"))
+    return (out, stats) + ((bmap,) if want_block_map else ()) + ((tmap,) if want_tier_map else ()) + ((per,) if want_image_stats else ())
+
+
+def compress_chain_refined(fmt, images, first, refine, max_block_sse, channels=None, want_block_map=False, want_tier_map=False,
+                           want_image_stats=False):
+    """itwCompressImageChainRefined: compress_refined over a whole chain as one population of blocks (include/itw_dispatch.h).  images: list
+    of numpy arrays or of CUDA tensors (H, W, 4), any size >= 1, as compress_chain takes them; the block error leaves the padding of
+    partial blocks out.  Returns (blocks, RefineStats[, block_sse][, tier_map][, image_stats]): blocks, block_sse and tier_map over the
+    chain's concatenated block list (compress_chain's layout), image_stats a list of one RefineStats per image."""
+    base = fmt.split("_")[0]
+    if base not in ("bc7", "bc6h"):
+        raise ValueError(f"{fmt}: only bc7 and bc6h have presets to refine with")
+    return _chain_refined("itwCompressImageChainRefined", fmt, images, first, refine, channels, want_block_map, want_tier_map, want_image_stats,
+                          RefineStats(), (int(max_block_sse),))
+
+
+def compress_chain_refined_to(fmt, images, first, refine, max_listed=None, share=None, target_sse=None, target_psnr=None, channels=None,
+                              want_block_map=False, want_tier_map=False, want_image_stats=False):
+    """itwCompressImageChainRefinedTo: compress_refined_to over a whole chain as one population: share is of the chain's blocks, target_psnr
+    (bc7 only) goes through itwChainPsnrToTotalSse.  Returns (blocks, RefineTargetStats[, block_sse][, tier_map][, image_stats])."""
+    base = fmt.split("_")[0]
+    if base not in ("bc7", "bc6h"):
+        raise ValueError(f"{fmt}: only bc7 and bc6h have presets to refine with")
+    if max_listed is not None and share is not None:
+        raise ValueError("max_listed and share are two ways to say one thing: pass one")
+    if target_sse is not None and target_psnr is not None:
+        raise ValueError("target_sse and target_psnr are two ways to say one thing: pass one")
+    if share is not None:
+        if not 0.0 <= share <= 1.0:
+            raise ValueError(f"share {share}: a fraction of the blocks, 0..1")
+        max_listed = int(share * sum(((img.shape[1] + 3) // 4) * ((img.shape[0] + 3) // 4) for img in images))
+    if target_psnr is not None:
+        if base == "bc6h":
+            raise ValueError("bc6h: no PSNR of half-float codes; pass target_sse")
+        target_sse = chain_psnr_to_total_sse(fmt, [(img.shape[0], img.shape[1]) for img in images], target_psnr, "rgb" if channels is None else channels)
+    pol = RefinePolicy(UINT64_MAX if max_listed is None else int(max_listed), UINT64_MAX if target_sse is None else int(target_sse))
+    return _chain_refined("itwCompressImageChainRefinedTo", fmt, images, first, refine, channels, want_block_map, want_tier_map, want_image_stats,
+                          RefineTargetStats(), (C.addressof(pol), C.sizeof(RefinePolicy)))

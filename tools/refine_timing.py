@@ -22,7 +22,18 @@ profiles/refine_target_timing.jsonl.  At 10 % and 30 % of the blocks, alternatin
               the (k+1)-th largest, and the second call -- which repeats the first tier
 and policy B at two targets a third and two thirds of the way from the first preset's to the refine preset's quality (BC7: in dB through
 itwPsnrToTotalSse; BC6H: in summed error): rounds, blocks listed, what was reached, ms.
-Usage: python tools/refine_timing.py [reps] [inner] [--target] [--no-save] [--out=PATH] [--size=N]"""
+
+--chain: a whole mip chain or cube map to a budget in one call (itwCompressImageChainRefined) against the per-image pattern, same timing
+method, appended to profiles/chain_refine_timing.jsonl.  The chains of tools/chain_timing.py: the 1024^2 BC7 cube map with mips (66
+images) and the 2048^2 BC7 2D chain (12 images), veryfast -> slow, and the 512^2 BC6H cube map (60 images), fast -> slow; budgets that list
+10 % and 30 % of the chain's blocks, from the first tier's map.  Legs, alternating in one run:
+    per_image_P      per image: itwPadToMultipleOf4Device, then itwCompressImageRefined with that budget (the padding counts as error there)
+    chain_P          one itwCompressImageChainRefined call; chain_stats_P: the same with image_stats
+    chain_first / chain_refine   itwCompressImageChainEx with the first / the refine preset alone, for scale
+    level0_single_P / level0_chain_P (the 2048^2 chain): itwCompressImageRefined of level 0 against a chain of that one image -- what the
+                     packed copy and the scratch target cost
+--label=TEXT adds "build": TEXT to every row (which build the lines came from).
+Usage: python tools/refine_timing.py [reps] [inner] [--target | --chain] [--no-save] [--out=PATH] [--size=N] [--label=TEXT]"""
 import ctypes as C
 import json
 import os
@@ -36,6 +47,7 @@ import itw_amd                          # noqa: E402
 from itw_amd import surfaces           # noqa: E402
 
 PAIRS = [("bc7", "veryfast", "slow"), ("bc6h", "fast", "slow")]
+LABEL = next((a[8:] for a in sys.argv if a.startswith("--label=")), None)
 U64_MAX = 2 ** 64 - 1
 
 
@@ -112,6 +124,8 @@ def main():
                     times[name].append(timed(fn))
             row = {"content": content, "format": fmt, "first": first, "refine": refine, "size": size, "blocks": nb, "reps": reps, "inner": inner,
                    "timing": "host clock around calls that each end in a stream synchronise", "device": itw_amd.device_info(), "variants": {}}
+            if LABEL:
+                row["build"] = LABEL
             for name, fn in variants.items():
                 t = sorted(times[name])
                 v = {"ms": round(t[0], 4), "median_ms": round(t[len(t) // 2], 4), "spread": round((t[-1] - t[0]) / t[0], 3)}
@@ -222,6 +236,8 @@ def main_target():
             row = {"content": content, "format": fmt, "first": first, "refine": refine, "size": size, "blocks": nb, "reps": reps, "inner": inner,
                    "timing": "host clock around calls that each end in a stream synchronise", "device": itw_amd.device_info(),
                    "sse_first": sse_hi, "sse_all_refined": sse_lo, "variants": {}}
+            if LABEL:
+                row["build"] = LABEL
             for name, fn in variants.items():
                 t = sorted(times[name])
                 v = {"ms": round(t[0], 4), "median_ms": round(t[len(t) // 2], 4), "spread": round((t[-1] - t[0]) / t[0], 3)}
@@ -247,5 +263,137 @@ def main_target():
                 f.write(json.dumps(r) + "\n")
 
 
+# name, format, first, refine, top size (h, w), faces: the chains of tools/chain_timing.py
+CHAINS = [("bc7_1024_cube", "bc7", "veryfast", "slow", (1024, 1024), 6),
+          ("bc7_2048_2d", "bc7", "veryfast", "slow", (2048, 2048), 1),
+          ("bc6h_512_cube", "bc6h", "fast", "slow", (512, 512), 6)]
+
+
+def main_chain():
+    import torch
+    args = [a for a in sys.argv[1:] if not a.startswith("--")]
+    reps = int(args[0]) if args else 7
+    inner = int(args[1]) if len(args) > 1 else 5
+    save = "--no-save" not in sys.argv
+    out_path = next((a[6:] for a in sys.argv if a.startswith("--out=")), os.path.join(ROOT, "profiles", "chain_refine_timing.jsonl"))
+    label = next((a[8:] for a in sys.argv if a.startswith("--label=")), None)
+    dev = torch.device("cuda:0")
+    torch.cuda.set_device(dev)
+    L = itw_amd.lib()
+    L.itwSetStream(torch.cuda.current_stream(dev).cuda_stream)
+    rows = []
+    for name, fmt, first, refine, (h, w), faces in CHAINS:
+        gen = surfaces.hdr_smooth if fmt == "bc6h" else surfaces.ldr_smooth
+        images = [lv for f in range(faces) for lv in itw_amd.mip_chain(gen(h, w, seed=100 + f))]
+        px = 8 if fmt == "bc6h" else 4
+        fcode = itw_amd.DXGI_FORMAT[fmt]
+        profile = itw_amd.bc7_profile if fmt == "bc7" else itw_amd.bc6h_profile
+        s1, s2 = profile(first), profile(refine)
+        A, B = C.addressof(s1), C.addressof(s2)
+        count = len(images)
+        nblocks = [((lv.shape[0] + 3) // 4) * ((lv.shape[1] + 3) // 4) for lv in images]
+        offs = [int(v) for v in np.cumsum([0] + nblocks)]
+        nb = offs[-1]
+        srcs = [torch.from_numpy(lv.view(np.int16) if lv.dtype == np.uint16 else lv).to(dev) for lv in images]
+        surf_of = lambda t: itw_amd.RgbaSurface(t.data_ptr(), t.shape[1], t.shape[0], t.stride(0) * t.element_size())
+        arr = (itw_amd.RgbaSurface * count)(*[surf_of(t) for t in srcs])
+        ssurf = [surf_of(t) for t in srcs]
+        padded = [torch.empty(((t.shape[0] + 3) // 4 * 4, (t.shape[1] + 3) // 4 * 4, 4), dtype=t.dtype, device=dev) for t in srcs]
+        psurf = [surf_of(t) for t in padded]
+        out = torch.empty(nb * 16, dtype=torch.uint8, device=dev)
+        bmap = torch.empty(nb, dtype=torch.int64, device=dev)
+        per = torch.empty((count, C.sizeof(itw_amd.RefineStats) // 8), dtype=torch.int64, device=dev)
+        st, ist = itw_amd.RefineStats(), itw_amd.RefineStats()
+
+        def chain(budget, bm=None, image_stats=None, arr=arr, n=count):
+            ok = L.itwCompressImageChainRefined(C.cast(arr, C.c_void_p), n, out.data_ptr(), fcode, A, B, 7, budget, C.addressof(st), C.sizeof(st),
+                                                image_stats.data_ptr() if image_stats is not None else None, bm.data_ptr() if bm is not None else None, None)
+            assert ok, itw_amd.last_error()
+
+        listed_loop = [0]
+
+        def per_image(budget):                                   # what a caller does without the chain call
+            total = 0
+            for i in range(count):
+                L.itwPadToMultipleOf4Device(C.byref(ssurf[i]), px, padded[i].data_ptr())
+                ok = L.itwCompressImageRefined(C.byref(psurf[i]), out.data_ptr() + offs[i] * 16, fcode, A, B, 7, budget, C.addressof(ist), C.sizeof(ist), None, None)
+                assert ok, itw_amd.last_error()
+                total += int(ist.listed)
+            listed_loop[0] = total
+
+        def single(budget):
+            ok = L.itwCompressImageRefined(C.byref(ssurf[0]), out.data_ptr(), fcode, A, B, 7, budget, C.addressof(ist), C.sizeof(ist), None, None)
+            assert ok, itw_amd.last_error()
+
+        def plain(settings):
+            assert L.itwCompressImageChainEx(C.cast(arr, C.c_void_p), count, out.data_ptr(), fcode, C.addressof(settings), None, None)
+
+        chain(U64_MAX, bmap)
+        e = bmap.cpu().numpy()
+        s = np.sort(e)
+        budgets = {"10": int(s[nb - nb // 10 - 1]), "30": int(s[nb - (3 * nb) // 10 - 1])}
+        variants = {"chain_first": lambda: plain(s1), "chain_refine": lambda: plain(s2)}
+        for p, b in budgets.items():
+            variants["per_image_" + p] = (lambda v: lambda: per_image(v))(b)
+            variants["chain_" + p] = (lambda v: lambda: chain(v))(b)
+            variants["chain_stats_" + p] = (lambda v: lambda: chain(v, None, per))(b)
+        level0 = {}
+        if faces == 1:                                           # level 0 alone: in place against packed
+            s0 = np.sort(e[:nblocks[0]])
+            n0 = nblocks[0]
+            level0 = {"10": int(s0[n0 - n0 // 10 - 1]), "30": int(s0[n0 - (3 * n0) // 10 - 1])}
+            one = (itw_amd.RgbaSurface * 1)(ssurf[0])
+            for p, b in level0.items():
+                variants["level0_single_" + p] = (lambda v: lambda: single(v))(b)
+                variants["level0_chain_" + p] = (lambda v: lambda: chain(v, None, None, one, 1))(b)
+
+        def timed(fn):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(inner):
+                fn()
+                torch.cuda.synchronize()
+            return (time.perf_counter() - t0) * 1e3 / inner
+
+        for fn in variants.values():
+            fn(); fn()
+        torch.cuda.synchronize()
+        times = {k: [] for k in variants}
+        for _ in range(reps):
+            for k, fn in variants.items():
+                times[k].append(timed(fn))
+        row = {"case": name, "format": fmt, "first": first, "refine": refine, "top": [h, w], "faces": faces, "images": count, "blocks": nb,
+               "reps": reps, "inner": inner, "timing": "host clock around calls that each end in a stream synchronise",
+               "device": itw_amd.device_info(), "variants": {}}
+        if label:
+            row["build"] = label
+        for k, fn in variants.items():
+            t = sorted(times[k])
+            v = {"ms": round(t[0], 4), "median_ms": round(t[len(t) // 2], 4), "spread": round((t[-1] - t[0]) / t[0], 3)}
+            fn()
+            if k.startswith("chain_1") or k.startswith("chain_3") or k.startswith("chain_stats") or k.startswith("level0_chain"):
+                v.update(budget=(level0 if k.startswith("level0") else budgets)[k.rsplit("_", 1)[1]], listed=int(st.listed), replaced=int(st.replaced),
+                         sse_first=int(st.sse_first), sse_final=int(st.sse_final))
+            elif k.startswith("per_image"):
+                v.update(budget=budgets[k.rsplit("_", 1)[1]], listed=listed_loop[0])
+            elif k.startswith("level0_single"):
+                v.update(budget=level0[k.rsplit("_", 1)[1]], listed=int(ist.listed), replaced=int(ist.replaced), sse_first=int(ist.sse_first),
+                         sse_final=int(ist.sse_final))
+            row["variants"][k] = v
+        med = {k: row["variants"][k]["median_ms"] for k in variants}
+        for p in budgets:
+            row["chain_vs_per_image_" + p] = round(med["chain_" + p] / med["per_image_" + p], 3)
+            row["image_stats_cost_ms_" + p] = round(med["chain_stats_" + p] - med["chain_" + p], 4)
+        for p in level0:
+            row["level0_chain_minus_single_ms_" + p] = round(med["level0_chain_" + p] - med["level0_single_" + p], 4)
+        print(json.dumps(row), flush=True)
+        rows.append(row)
+    if save and rows:
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+        with open(out_path, "a") as f:
+            for r in rows:
+                f.write(json.dumps(r) + "\n")
+
+
 if __name__ == "__main__":
-    main_target() if "--target" in sys.argv else main()
+    main_chain() if "--chain" in sys.argv else main_target() if "--target" in sys.argv else main()
