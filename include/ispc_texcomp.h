@@ -9,8 +9,10 @@
  * so that its callers (win32Threads.cpp:289-329 trampolines, IntelPlugin.cpp:816)
  * link against libispc_texcomp.so unchanged.  Layouts are asserted at the end.
  *
- * Not provided (outside the accelerated path):
- * CompressBlocksETC1 / GetProfile_etc_slow / the ASTC declarations.
+ * ETC1 (ispc_texcomp.h:52-55, 86, 107 of the reference) is provided, but NOT under the reference's names: the drop-in symbol set stays
+ * the BC1/BC3/BC7/BC6H one.  The struct etc_enc_settings below has the reference's layout and spelling; the functions are
+ * itwGetProfile_etc_slow / itwCompressBlocksETC1 (include/itw_amd.h), same arguments, same bytes.
+ * Not provided: the ASTC declarations (the reference declares them and never defines them).
  *
  * Contract (same as the reference, ispc_texcomp.h:93-102, corrected where the
  * reference comment is wrong):
@@ -79,10 +81,16 @@ struct bc6h_enc_settings
     int  fastSkipTreshold;
 };
 
+struct etc_enc_settings
+{
+    int fastSkipTreshold;          /* how many luminance-ranked splits of a half each fit tries: 1 .. 165 */
+};
+
 #ifndef __cplusplus
 typedef struct rgba_surface      rgba_surface;
 typedef struct bc7_enc_settings  bc7_enc_settings;
 typedef struct bc6h_enc_settings bc6h_enc_settings;
+typedef struct etc_enc_settings  etc_enc_settings;
 #endif
 
 /* BC7, opaque sources (alpha ignored) -- ispc_texcomp.cpp:20-189 */
@@ -118,6 +126,7 @@ void CompressBlocksBC7 (const rgba_surface* src, uint8_t* dst, bc7_enc_settings*
 static_assert(sizeof(rgba_surface) == 24,      "rgba_surface layout (x86-64)");
 static_assert(sizeof(bc7_enc_settings) == 64,  "bc7_enc_settings layout");
 static_assert(sizeof(bc6h_enc_settings) == 16, "bc6h_enc_settings layout");
+static_assert(sizeof(etc_enc_settings) == 4,   "etc_enc_settings layout");
 #endif
 
 #endif /* ISPC_TEXCOMP_H */

@@ -88,6 +88,18 @@ int64_t itwBandForPart(int32_t width, int32_t height, int32_t bytes_per_block,
 int64_t itwBandForPartEx(int32_t width, int32_t height, int32_t bytes_per_block, int32_t part, int32_t parts,
                          int32_t keep_partial_blocks, int32_t* first_row, int32_t* row_count);
 
+/* ETC1 (GL_ETC1_RGB8_OES): the reference's CompressBlocksETC1 / GetProfile_etc_slow (ispc_texcomp.cpp:412-415, 437-440 -> kernel.ispc:3141-3691)
+ * under this library's prefix; the drop-in symbol set of ispc_texcomp.h stays as it is.  Everything is as for CompressBlocksBC1: RGBA8 source
+ * (alpha ignored), host or device pointers, the thread's stream, the error mode, (width / 4) * (height / 4) blocks of 8 bytes in raster
+ * order, tightly packed; a device-pointer call is one asynchronous launch that allocates nothing.  The bytes are the reference's.
+ *   fastSkipTreshold   1 .. 165 as the reference; above 165 is 165 (every split is tried by then; the reference reads past its list);
+ *                      below 1 the call is refused through the error mode before any device work (the reference packs uninitialised storage).
+ * A device src->ptr and src->stride are multiples of 4 and a device dst is 4-byte aligned (texels are read and blocks written as dwords, as on
+ * CompressBlocksBC1's unaligned path); host pointers are staged and may have any alignment.
+ * ETC1 calls are never joined with other threads' small calls. */
+void itwGetProfile_etc_slow(etc_enc_settings* settings);            /* fastSkipTreshold = 6 */
+void itwCompressBlocksETC1(const rgba_surface* src, uint8_t* dst, const etc_enc_settings* settings);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

@@ -26,7 +26,9 @@ extern "C" {
  * (BC4BC5.cpp:388-400, 465-478) with R = rint(127 * its float).  As integers, with s0, s1 the endpoint bytes and -128 read as -127:
  * levels 0, 1 = s0, s1; if the RAW bytes have r0 > r1, level 1+i = round(((7-i)*s0 + i*s1) / 7), i = 1..6; else level 1+i =
  * round(((5-i)*s0 + i*s1) / 5), i = 1..4, and levels 6, 7 = -127, 127 (round to nearest; no ties with odd divisors).  Never -128.
- * dxgi_format: one of the ITW_DXGI_FORMAT_BC* values of itw_dispatch.h (71,72,77,78,80,81,83,84,95,96,98,99).
+ * dxgi_format: one of the ITW_DXGI_FORMAT_BC* values of itw_dispatch.h (71,72,77,78,80,81,83,84,95,96,98,99), or ITW_FORMAT_ETC1_RGB8 (0x8D64):
+ * ETC1, 8-byte blocks, RGBA8 texels with alpha filled with 255, whole blocks only; modes 0 = individual, 1 = differential, -1 = a differential
+ * block whose base + delta leaves 0..31 (invalid in ETC1; decoded with the sum modulo 32 and counted in reserved_blocks).
  * `blocks`, `out`, `modes` are host or device pointers, in any mix.  With all of them on the device the call is one kernel launch,
  * asynchronous on the calling thread's stream (itwSetStream): it allocates nothing, touches no buffer of the thread and can be captured
  * into a graph.  With any host pointer it stages through the calling thread's grow-only device buffer (the one itwDecodeChain uses;
@@ -50,7 +52,7 @@ int itwDecodeBlocks(int dxgi_format, const uint8_t* blocks, int width, int heigh
  * outs[i]: where image i's texels go -- ptr, width, height (any >= 1), stride (bytes, a multiple of 4, at least the row); RGBA8, int8
  * RGBA8_SNORM for BC4S / BC5S, RGBA16F bit patterns for BC6H_UF16.  ptr is 4-byte aligned (8 for RGBA16F).  Texels outside
  * width x height are never written: edge blocks are cropped on store, for every format.
- * dxgi_format: 71, 72, 77, 78, 80, 81, 83, 84, 95, 98, 99.  BC6H_SF16 (96) is refused: the signed decode is not built.
+ * dxgi_format: 71, 72, 77, 78, 80, 81, 83, 84, 95, 98, 99, 0x8D64 (ETC1).  BC6H_SF16 (96) is refused: the signed decode is not built.
  * modes (optional, may be NULL): one int32 per block of the concatenated block list, numbered as itwDecodeBlocks numbers them.
  * min_alpha (optional, may be NULL): one uint32 per image, the smallest decoded alpha code among the texels actually stored -- the load
  * path's IsAlphaAllOpaque question (255 = opaque) without a second pass.  For the formats that fill alpha it is that constant: BC4 / BC5
@@ -88,7 +90,7 @@ typedef struct itw_error_stats {
     uint64_t worst_block_sse;             /* largest per-block sum of the four channels' squared differences */
     uint32_t worst_block;                 /* raster index of the FIRST block that reaches it */
     uint32_t _pad;
-    uint64_t mode_hist[16];               /* blocks per mode: BC7 0..7, BC6H 0..13 (itwDecodeBlocks' numbering), others all in [0] */
+    uint64_t mode_hist[16];               /* blocks per mode: BC7 0..7, BC6H 0..13, ETC1 0..1 (itwDecodeBlocks' numbering), others all in [0] */
 } itw_error_stats;
 
 /* The most blocks one image may have: the worst block is found with one 64-bit atomic maximum over (block sse, inverted index), and

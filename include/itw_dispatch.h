@@ -32,7 +32,10 @@ enum {
     ITW_DXGI_FORMAT_BC4_UNORM = 80, ITW_DXGI_FORMAT_BC5_UNORM = 83,       /* the DirectXTex formats, itw_bc45.h */
     ITW_DXGI_FORMAT_BC4_SNORM = 81, ITW_DXGI_FORMAT_BC5_SNORM = 84,       /* their signed pair (RGBA8_SNORM sources), itw_bc45.h */
     ITW_DXGI_FORMAT_BC6H_UF16 = 95, ITW_DXGI_FORMAT_BC6H_SF16 = 96,
-    ITW_DXGI_FORMAT_BC7_UNORM = 98, ITW_DXGI_FORMAT_BC7_UNORM_SRGB = 99
+    ITW_DXGI_FORMAT_BC7_UNORM = 98, ITW_DXGI_FORMAT_BC7_UNORM_SRGB = 99,
+    /* ETC1 has no DXGI code: it goes by its GL enum, GL_ETC1_RGB8_OES.  Only the decode and measure entry points of itw_decode.h take it
+     * (the encoder is itwCompressBlocksETC1, itw_amd.h); to everything in this header it is an unknown format. */
+    ITW_FORMAT_ETC1_RGB8 = 0x8D64
 };
 
 /* win32Threads.h:52-55 / win32Threads.cpp:98-190.  GetProcessorCount(): number of workers = visible GPUs (>= 1), or the

@@ -198,13 +198,14 @@ void* grow(void*& buf, size_t& cap, size_t need)
     return buf;
 }
 
-enum class Fmt { BC1, BC3, BC7, BC6H, BC4, BC5 };
+enum class Fmt { BC1, BC3, BC7, BC6H, BC4, BC5, ETC1 };      // ETC1: itwCompressBlocksETC1 only; job_of (slices, chains, the GPU pool) does not know it
 
 struct Job {
     Fmt fmt;
     bool snorm = false;         // BC4 / BC5 only: the SNORM pair (same geometry, block size and staging; its own kernels)
     const bc7_enc_settings*  s7 = nullptr;
     const bc6h_enc_settings* s6 = nullptr;
+    int etc_threshold = 0;      // ETC1 only: fastSkipTreshold, >= 1
 };
 
 // The BC7 workspace is per host thread.  Work already queued on another stream may still be using it, so a change
@@ -314,6 +315,7 @@ void launch(const Job& j, const uint8_t* d_src, int64_t stride, int w, int h, ui
     }
     case Fmt::BC4:  (j.snorm ? itw::launch_bc4s : itw::launch_bc4)(d_src, stride, w, h, d_dst, st); break;
     case Fmt::BC5:  (j.snorm ? itw::launch_bc5s : itw::launch_bc5)(d_src, stride, w, h, d_dst, st); break;
+    case Fmt::ETC1: itw::launch_etc1(d_src, stride, w, h, d_dst, j.etc_threshold, st); break;
     }
     ITW_CHECK(hipGetLastError());
 }
@@ -347,7 +349,7 @@ void compress(const Job& j, const rgba_surface* src, uint8_t* dst, bool may_coal
     const int bx = keep_partial ? (w > 0 ? (w + 3) / 4 : 0) : w / 4, by = keep_partial ? (h > 0 ? (h + 3) / 4 : 0) : h / 4;
     if (bx <= 0 || by <= 0) return;                   // nothing to encode: the reference's loops do not run either
     if (!src->ptr || !dst) itw::fail_msg("null texel or destination pointer");
-    const int bpb = (j.fmt == Fmt::BC1 || j.fmt == Fmt::BC4) ? 8 : 16;
+    const int bpb = (j.fmt == Fmt::BC1 || j.fmt == Fmt::BC4 || j.fmt == Fmt::ETC1) ? 8 : 16;
     const int texel_bytes = (j.fmt == Fmt::BC6H) ? 8 : 4;
     const size_t row_bytes = keep_partial ? (size_t)w * 4 : (size_t)bx * 4 * texel_bytes;
     const size_t rows = keep_partial ? (size_t)h : (size_t)by * 4;
@@ -1396,6 +1398,22 @@ void CompressBlocksBC6H(const rgba_surface* src, uint8_t* dst, bc6h_enc_settings
     itw::guarded([&] {
         if (!settings) itw::fail_msg("null bc6h settings");
         Job j; j.fmt = Fmt::BC6H; j.s6 = settings; compress(j, src, dst);
+    });
+}
+
+// ETC1 under the library's own prefix (include/itw_amd.h).  The call is never offered to the small-call combiner.
+void itwGetProfile_etc_slow(etc_enc_settings* settings) { settings->fastSkipTreshold = 6; }      // ispc_texcomp.cpp:412-415
+void itwCompressBlocksETC1(const rgba_surface* src, uint8_t* dst, const etc_enc_settings* settings)
+{
+    itw::clear_failure();
+    itw::guarded([&] {
+        if (!settings) itw::fail_msg("itwCompressBlocksETC1: null settings");
+        if (settings->fastSkipTreshold < 1)
+            itw::fail_msg("itwCompressBlocksETC1: fastSkipTreshold %d (1 .. 165; the reference emits uninitialised storage below 1)", settings->fastSkipTreshold);
+        if (src && (int64_t)(src->width / 4) * (src->height / 4) > (int64_t)INT32_MAX)
+            itw::fail_msg("itwCompressBlocksETC1: %d x %d is more blocks than one launch covers", src->width, src->height);
+        Job j; j.fmt = Fmt::ETC1; j.etc_threshold = settings->fastSkipTreshold;
+        compress(j, src, dst, false);
     });
 }
 

@@ -267,6 +267,53 @@ __device__ __forceinline__ int decode_bc6h(Bits& bs, uint32_t (&lo)[16], uint32_
     return mode;
 }
 
+// ---- ETC1 (OES_compressed_ETC1_RGB8_texture) -----------------------------------------------------------------------------------------------
+// Bytes 0-2: the two base colours per channel -- individual: two 4-bit values (first sub-block in the high nibble), each x 17; differential: a
+// 5-bit base and a 3-bit signed delta, each 5-bit value v extended (v << 3) | (v >> 2).  Byte 3: table of sub-block 0 in bits 7-5, of sub-block
+// 1 in bits 4-2, diff in bit 1, flip in bit 0.  Bytes 4-7: the MSB and the LSB plane of the selectors, big-endian, texel (x, y) at bit x * 4 + y.
+// flip 0: sub-block 1 is columns 2-3; flip 1: rows 2-3.  Returns the mode: 0 individual, 1 differential, -1 for a differential block whose
+// base + delta leaves 0 .. 31 (invalid in ETC1; decoded with the sum modulo 32).
+__device__ const unsigned char D_ETC1_MODIFIERS[8][2] = {{2, 8}, {5, 17}, {9, 29}, {13, 42}, {18, 60}, {24, 80}, {33, 106}, {47, 183}};
+
+__device__ __forceinline__ int decode_etc1(uint32_t w0, uint32_t w1, uint32_t (&px)[16])
+{
+    const bool flip = (w0 >> 24) & 1u, diff = (w0 >> 25) & 1u;
+    const int table[2] = {(int)((w0 >> 29) & 7u), (int)((w0 >> 26) & 7u)};
+    int base[2][3];
+    bool overflow = false;
+#pragma unroll
+    for (int p = 0; p < 3; p++) {
+        const int byte = (int)((w0 >> (8 * p)) & 255u);
+        if (diff) {
+            const int v = byte >> 3, d = (byte & 7) - ((byte & 4) << 1), sum = v + d;
+            overflow = overflow || sum < 0 || sum > 31;
+            const int u = sum & 31;
+            base[0][p] = (v << 3) | (v >> 2);
+            base[1][p] = (u << 3) | (u >> 2);
+        } else {
+            base[0][p] = (byte >> 4) * 17;
+            base[1][p] = (byte & 15) * 17;
+        }
+    }
+    const uint32_t planes = __builtin_bswap32(w1);              // MSB plane in the high half, LSB plane in the low half
+    int small[2], large[2];
+#pragma unroll
+    for (int i = 0; i < 2; i++) { small[i] = D_ETC1_MODIFIERS[table[i]][0]; large[i] = D_ETC1_MODIFIERS[table[i]][1]; }
+#pragma unroll
+    for (int y = 0; y < 4; y++)
+#pragma unroll
+        for (int x = 0; x < 4; x++) {
+            const int bit = x * 4 + y, sub = flip ? (y >> 1) : (x >> 1);
+            const bool msb = (planes >> (16 + bit)) & 1u, lsb = (planes >> bit) & 1u;
+            const int mag = lsb ? (sub ? large[1] : large[0]) : (sub ? small[1] : small[0]), m = msb ? -mag : mag;
+            uint32_t texel = 255u << 24;
+#pragma unroll
+            for (int p = 0; p < 3; p++) texel |= (uint32_t)min(max((sub ? base[1][p] : base[0][p]) + m, 0), 255) << (8 * p);
+            px[y * 4 + x] = texel;
+        }
+    return overflow ? -1 : (diff ? 1 : 0);
+}
+
 // ---- any format: block words -> 16 texels -------------------------------------------------------------------------------------------
 // the 128 bits of a block as the LSB-first reader takes them
 __device__ __forceinline__ Bits block_bits(const uint4 w)
@@ -275,7 +322,7 @@ __device__ __forceinline__ Bits block_bits(const uint4 w)
 }
 
 // Decodes the block whose words are `w` (the 8-byte formats use .x and .y) into RGBA8 dwords (int8 codes for the SNORM pair) and returns
-// its mode: BC7 0..7 or -1 for the reserved prefix, 0 for the formats without modes.  Alpha is filled where the format has none
+// its mode: BC7 0..7 or -1 for the reserved prefix, ETC1 0 / 1 or -1 (decode_etc1), 0 for the formats without modes.  Alpha is filled where the format has none
 // (filled_alpha): BC4 / BC5 decode to (R, 0, 0, 255) / (R, G, 0, 255) like D3DXDecodeBC4U / BC5U (BC4BC5.cpp:373-385, 449-462), their
 // SNORM forms to int8 (R, 0, 0, 127) / (R, G, 0, 127) (:388-400, :465-478).
 template <int FMT>
@@ -285,6 +332,8 @@ __device__ __forceinline__ int decode_block(const uint4 w, uint32_t (&px)[16])
     if (FMT == BCN_BC7) {
         Bits bs = block_bits(w);
         return decode_bc7(bs, px);
+    } else if (FMT == BCN_ETC1) {
+        return decode_etc1(w.x, w.y, px);
     } else if (FMT == BCN_BC1) {
         decode_color(w.x, w.y, true, px);
     } else if (FMT == BCN_BC3) {

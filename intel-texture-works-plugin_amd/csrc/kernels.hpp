@@ -10,6 +10,9 @@ namespace itw {
 // output tightly packed in raster block order; asynchronous on `st`.
 void launch_bc1 (const uint8_t* src, int64_t stride, int width, int height, uint8_t* dst, hipStream_t st);
 void launch_bc3 (const uint8_t* src, int64_t stride, int width, int height, uint8_t* dst, hipStream_t st);
+// ETC1 of the RGB channels of an RGBA8 surface (etc1.hip): (width / 4) * (height / 4) blocks of 8 bytes; `threshold` >= 1 (fastSkipTreshold,
+// anything above 165 is 165); src and stride 4-byte aligned.  One launch, no workspace.
+void launch_etc1(const uint8_t* src, int64_t stride, int width, int height, uint8_t* dst, int threshold, hipStream_t st);
 // BC4_UNORM / BC5_UNORM of the R (and G) channel of an RGBA8 surface, DirectXTex's encoder (bc4_bc5.hip).  Any
 // width/height >= 1: ceil(width/4) x ceil(height/4) blocks, partial blocks replicated by DirectXTex's rule.
 void launch_bc4 (const uint8_t* src, int64_t stride, int width, int height, uint8_t* dst, hipStream_t st);

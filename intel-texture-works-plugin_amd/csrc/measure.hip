@@ -109,7 +109,7 @@ measure_kernel(const uint8_t* __restrict__ blocks, int32_t blocks_x, int32_t nbl
         key = k > key ? k : key;
 #pragma unroll
         for (int c = 0; c < 4; c++) sum[c] += bs[c];
-        if (FMT == BCN_BC6H || FMT == BCN_BC7) atomicAdd(&s_hist[mode < 0 ? 16 : mode], 1u);
+        if (has_modes(FMT)) atomicAdd(&s_hist[mode < 0 ? 16 : mode], 1u);
         else mine++;
     }
 
@@ -120,12 +120,12 @@ measure_kernel(const uint8_t* __restrict__ blocks, int32_t blocks_x, int32_t nbl
 #pragma unroll
     for (int c = 0; c < 4; c++) { ws[c] = wave_sum((unsigned long long)sum[c]); wm[c] = wave_max(mx[c]); }
     key = wave_max(key);
-    if (FMT != BCN_BC6H && FMT != BCN_BC7) mine = wave_sum(mine);
+    if (!has_modes(FMT)) mine = wave_sum(mine);
     if (lane == 0) {
 #pragma unroll
         for (int c = 0; c < 4; c++) { s_sum[wave][c] = ws[c]; s_max[wave][c] = wm[c]; }
         s_key[wave] = key;
-        if (FMT != BCN_BC6H && FMT != BCN_BC7) atomicAdd(&s_hist[0], mine);
+        if (!has_modes(FMT)) atomicAdd(&s_hist[0], mine);
     }
     __syncthreads();
     if (t < 20) {                                               // lanes 0-3: sse[], 4-19: mode_hist[]

@@ -892,7 +892,7 @@ uint64_t psnr_to_total_sse(int dxgi_format, double texels, uint32_t channel_mask
     const int kind = itw::decode_kind(dxgi_format);
     int channels = 0;
     for (int c = 0; c < 4; c++) channels += (channel_mask >> c) & 1u;
-    if (kind == itw::BCN_NONE || kind == itw::BCN_BC6H || channels == 0 || !(texels >= 1.0) || !std::isfinite(psnr_db)) return UINT64_MAX;
+    if (kind == itw::BCN_NONE || kind == itw::BCN_BC6H || kind == itw::BCN_ETC1 || channels == 0 || !(texels >= 1.0) || !std::isfinite(psnr_db)) return UINT64_MAX;
     const double peak = (kind == itw::BCN_BC4S || kind == itw::BCN_BC5S) ? 254.0 : 255.0;      // as itwStatsPsnr
     const double sse = std::floor(peak * peak * (texels * (double)channels) / std::pow(10.0, psnr_db / 10.0));
     return sse >= 18446744073709551615.0 ? UINT64_MAX : (uint64_t)sse;

@@ -6,7 +6,7 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 _LIB = os.path.normpath(os.path.join(_PKG, "..", "lib", "libispc_texcomp.so"))
 _TEST_LIB = os.path.normpath(os.path.join(_PKG, "..", "lib", "libispc_texcomp_test.so"))
 
-BYTES_PER_BLOCK = {"bc1": 8, "bc3": 16, "bc7": 16, "bc6h": 16, "bc4": 8, "bc5": 16, "bc4_snorm": 8, "bc5_snorm": 16}
+BYTES_PER_BLOCK = {"bc1": 8, "bc3": 16, "bc7": 16, "bc6h": 16, "bc4": 8, "bc5": 16, "bc4_snorm": 8, "bc5_snorm": 16, "etc1": 8}
 KEEPS_PARTIAL_BLOCKS = ("bc4", "bc5", "bc4_snorm", "bc5_snorm")     # DirectXTex formats: ceil(w/4) x ceil(h/4) blocks (include/itw_bc45.h)
 SIGNED_FORMATS = ("bc4_snorm", "bc5_snorm")     # RGBA8_SNORM sources: int8 arrays / tensors, never uint8 (include/itw_bc45.h)
 BC7_PROFILES = ("ultrafast", "veryfast", "fast", "basic", "slow",
@@ -18,7 +18,7 @@ EXPORTED_SYMBOLS = tuple(
     ["CompressBlocksBC1", "CompressBlocksBC3", "CompressBlocksBC6H", "CompressBlocksBC7"]
     + ["GetProfile_" + p for p in BC7_PROFILES] + ["GetProfile_bc6h_" + p for p in BC6H_PROFILES]
     + ["itwSetStream", "itwGetStream", "itwAvailable", "itwSetErrorMode", "itwLastError", "itwClearError", "itwSetBc7Path", "itwSetBc7Pilot",
-       "itwDeviceInfo", "itwVersion", "itwBandForPart", "itwBandForPartEx"]
+       "itwDeviceInfo", "itwVersion", "itwBandForPart", "itwBandForPartEx", "itwGetProfile_etc_slow", "itwCompressBlocksETC1"]
     # include/itw_dispatch.h: the reference's dispatch layer (win32Threads.h), slice loop, pad pre-pass
     + ["GetProcessorCount", "InitWin32Threads", "DestroyThreads", "GetBytesPerBlock", "CompressImageMT", "CompressImageST",
        "CompressImageBC1", "CompressImageBC3", "CompressImageBC4", "CompressImageBC5", "CompressImageBC4S", "CompressImageBC5S"]
@@ -61,9 +61,15 @@ class Bc6hSettings(C.Structure):
                 ("refineIterations_2p", C.c_int), ("fastSkipTreshold", C.c_int)]
 
 
-assert C.sizeof(RgbaSurface) == 24 and C.sizeof(Bc7Settings) == 64 and C.sizeof(Bc6hSettings) == 16
+class EtcSettings(C.Structure):
+    """struct etc_enc_settings (ispc_texcomp.h:52-55): 4 bytes."""
+    _fields_ = [("fastSkipTreshold", C.c_int)]
 
-DXGI_FORMAT = {"bc1": 71, "bc1_srgb": 72, "bc3": 77, "bc3_srgb": 78, "bc4": 80, "bc4_snorm": 81, "bc5": 83, "bc5_snorm": 84, "bc6h": 95, "bc6h_sf16": 96, "bc7": 98, "bc7_srgb": 99}
+
+assert C.sizeof(RgbaSurface) == 24 and C.sizeof(Bc7Settings) == 64 and C.sizeof(Bc6hSettings) == 16 and C.sizeof(EtcSettings) == 4
+
+# "etc1": ITW_FORMAT_ETC1_RGB8, the GL enum (ETC1 has no DXGI code); only decode / measure take it, every other entry point refuses it
+DXGI_FORMAT = {"etc1": 0x8D64, "bc1": 71, "bc1_srgb": 72, "bc3": 77, "bc3_srgb": 78, "bc4": 80, "bc4_snorm": 81, "bc5": 83, "bc5_snorm": 84, "bc6h": 95, "bc6h_sf16": 96, "bc7": 98, "bc7_srgb": 99}
 
 
 class DdsDesc(C.Structure):
@@ -97,9 +103,9 @@ class MultiGpuStats(C.Structure):
 
 
 # the channels of a decoded texel that carry a format's own data (the others are fill values: itw_decode.h)
-OWN_CHANNELS = {"bc1": "rgb", "bc3": "rgba", "bc4": "r", "bc5": "rg", "bc4_snorm": "r", "bc5_snorm": "rg", "bc6h": "rgb", "bc7": "rgba"}
+OWN_CHANNELS = {"bc1": "rgb", "bc3": "rgba", "bc4": "r", "bc5": "rg", "bc4_snorm": "r", "bc5_snorm": "rg", "bc6h": "rgb", "bc7": "rgba", "etc1": "rgb"}
 _DXGI_BASE = {71: "bc1", 72: "bc1", 77: "bc3", 78: "bc3", 80: "bc4", 81: "bc4_snorm", 83: "bc5", 84: "bc5_snorm", 95: "bc6h", 96: "bc6h",
-              98: "bc7", 99: "bc7"}
+              98: "bc7", 99: "bc7", 0x8D64: "etc1"}
 
 
 def _base(fmt):
@@ -240,6 +246,10 @@ def _load(path, hooks):
         L.CompressBlocksBC6H.argtypes = [C.POINTER(RgbaSurface), C.c_void_p, C.POINTER(Bc6hSettings)]
         for n in ("CompressBlocksBC1", "CompressBlocksBC3", "CompressBlocksBC7", "CompressBlocksBC6H"):
             getattr(L, n).restype = None
+        L.itwGetProfile_etc_slow.argtypes = [C.POINTER(EtcSettings)]
+        L.itwGetProfile_etc_slow.restype = None
+        L.itwCompressBlocksETC1.argtypes = [C.POINTER(RgbaSurface), C.c_void_p, C.POINTER(EtcSettings)]
+        L.itwCompressBlocksETC1.restype = None
         L.itwSetStream.argtypes = [C.c_void_p]
         L.itwSetStream.restype = None
         L.itwGetStream.restype = C.c_void_p
@@ -442,6 +452,15 @@ def bc6h_profile(name):
     return s
 
 
+def etc_profile(name="slow"):
+    """itwGetProfile_etc_<name>: the reference has the one preset, `slow` (fastSkipTreshold 6)."""
+    if name != "slow":
+        raise KeyError(name)
+    s = EtcSettings()
+    lib().itwGetProfile_etc_slow(C.byref(s))
+    return s
+
+
 def band_for_part(width, height, fmt, part, parts):
     """(first_texel_row, texel_rows, output_byte_offset) of `part` among `parts` (itwBandForPart)."""
     y0, n = C.c_int32(), C.c_int32()
@@ -471,6 +490,9 @@ def _call(fmt, surf, dst_ptr, settings):
     elif fmt == "bc6h":
         st = settings if isinstance(settings, Bc6hSettings) else bc6h_profile(settings or "slow")
         L.CompressBlocksBC6H(C.byref(surf), dst_ptr, C.byref(st))
+    elif fmt == "etc1":
+        st = settings if isinstance(settings, EtcSettings) else etc_profile(settings or "slow")
+        L.itwCompressBlocksETC1(C.byref(surf), dst_ptr, C.byref(st))
     else:
         raise ValueError(fmt)
 
@@ -755,7 +777,7 @@ def decode(fmt, blocks, width, height, want_modes=False):
     (H, W, 4) uint8 -- uint16 half bit patterns for bc6h, int8 for the signed formats -- in the same kind of container, plus the per-block modes
     (int32) when asked."""
     import numpy as np
-    key = {"bc1": 71, "bc3": 77, "bc7": 98, "bc6h": 95, "bc4": 80, "bc5": 83, "bc4_snorm": 81, "bc5_snorm": 84}[fmt]
+    key = {"bc1": 71, "bc3": 77, "bc7": 98, "bc6h": 95, "bc4": 80, "bc5": 83, "bc4_snorm": 81, "bc5_snorm": 84, "etc1": 0x8D64}[fmt]
     signed = fmt in SIGNED_FORMATS                      # RGBA8_SNORM texels: int8
     nb = block_count(fmt, width, height)
     es = 2 if fmt == "bc6h" else 1
