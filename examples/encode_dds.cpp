@@ -4,7 +4,9 @@
 //
 //   encode_dds [--measure] [--refine <profile> <max_block_sse> | --refine-share <profile> <percent> | --refine-psnr <profile> <dB>]
 //              <format> <width> <height> <in.raw> <out.dds> [slice_pixels]
-//     format : bc1 | bc3 | bc4 | bc5 | bc4_snorm | bc5_snorm | bc7_<profile> | bc6h_<profile>      (profiles: the GetProfile_* names)
+//     format : bc1 | bc3 | bc4 | bc5 | bc4_snorm | bc5_snorm | bc7_<profile> | bc6h_<profile> | etc1_slow      (profiles: the GetProfile_* names)
+//              etc1_slow: DDS has no code for ETC1, so the output is a KTX 1.1 file (itwKtx*, itw_dds.h); the slices go through itwCompressImageSlicedEx
+//              (ETC1 has no trampoline); --refine* is refused: ETC1 has one preset
 //     in.raw : width*height tightly packed RGBA8 texels (RGBA16F bit patterns for bc6h_*; RGBA8_SNORM, int8 codes, for bc4_snorm / bc5_snorm)
 //     --measure : after encoding, one line on stdout per image: what the stream costs against the source (itwMeasureBlocks)
 //     --refine  : bc7_* / bc6h_* only: encode to an error budget (itwCompressImageRefined) -- <format>'s preset everywhere, then <profile>
@@ -15,7 +17,8 @@
 //     --refine-psnr  : bc7_* only: <profile> on as many of the worst blocks as it takes to reach <dB> over the format's own channels
 //                 (itwPsnrToTotalSse gives the target), in up to five rounds
 //
-//   encode_dds --decode <in.dds> <out.raw>
+//   encode_dds --decode <in.dds | in.ktx> <out.raw>
+//     (.dds or .ktx: told apart by the file's first bytes; a KTX file's images come in ITS order, level then face)
 //     the load path (IntelPlugin.cpp:2461-2561): header -> every image of the file through ONE itwDecodeChain -> texels.  out.raw holds
 //     every image's texels one after another in file order, tightly packed (RGBA8; RGBA16F bit patterns for BC6H; int8 codes for the
 //     SNORM pair); one line on stdout per image: index, width, height, min alpha (the smallest decoded alpha code: IsAlphaAllOpaque).
@@ -57,6 +60,7 @@ const Format kFormats[] = {
     {"bc6h_basic", CompressImageBC6H_basic, ITW_DXGI_FORMAT_BC6H_UF16, 8, true, 7},
     {"bc6h_slow", CompressImageBC6H_slow, ITW_DXGI_FORMAT_BC6H_UF16, 8, true, 7},
     {"bc6h_veryslow", CompressImageBC6H_veryslow, ITW_DXGI_FORMAT_BC6H_UF16, 8, true, 7},
+    {"etc1_slow", nullptr, ITW_FORMAT_ETC1_RGB8, 4, true, 7},                  // no trampoline: itwCompressImageSlicedEx; written as .ktx
 };
 
 // GetProfile_<name> / GetProfile_bc6h_<name> into `settings` (room for either struct); false: no such preset
@@ -89,19 +93,30 @@ int decode_file(const char* in_path, const char* out_path)
     uint8_t buf[65536];
     for (size_t n; (n = std::fread(buf, 1, sizeof buf, in)) > 0;) file.insert(file.end(), buf, buf + n);
     std::fclose(in);
-    ItwDdsDesc desc;
-    const size_t first = itwDdsReadHeader(file.data(), file.size(), &desc);
-    if (!first) { std::fprintf(stderr, "%s: not a BCn DDS file this library reads\n", in_path); return 1; }
+    static const uint8_t ktx_id[12] = {0xAB, 0x4B, 0x54, 0x58, 0x20, 0x31, 0x31, 0xBB, 0x0D, 0x0A, 0x1A, 0x0A};
+    const bool ktx = file.size() >= 12 && std::memcmp(file.data(), ktx_id, 12) == 0;
+    ItwDdsDesc desc = {};
+    ItwKtxDesc kdesc = {};
+    size_t first = 0;
+    std::vector<uint8_t> packed;                                   // KTX: the images behind one another (a size word sits in front of each level)
+    if (ktx) {
+        if (!itwKtxReadHeader(file.data(), file.size(), &kdesc)) { std::fprintf(stderr, "%s: not an ETC1 KTX 1.1 file this library reads\n", in_path); return 1; }
+        desc.dxgi_format = kdesc.gl_internal_format;
+    } else {
+        first = itwDdsReadHeader(file.data(), file.size(), &desc);
+        if (!first) { std::fprintf(stderr, "%s: not a BCn DDS file this library reads\n", in_path); return 1; }
+    }
     const int texel_bytes = desc.dxgi_format == ITW_DXGI_FORMAT_BC6H_UF16 ? 8 : 4;
     std::vector<rgba_surface> outs;
     size_t texels_bytes = 0, end = first;
     for (uint32_t i = 0;; i++) {                                   // the payload, image by image
         uint32_t w = 0, h = 0; size_t off = 0;
-        const size_t n = itwDdsImage(&desc, i, &w, &h, &off);
+        const size_t n = ktx ? itwKtxImage(&kdesc, i, &w, &h, &off) : itwDdsImage(&desc, i, &w, &h, &off);
         if (!n) break;
         outs.push_back(rgba_surface{nullptr, (int32_t)w, (int32_t)h, (int32_t)w * texel_bytes});
         texels_bytes += (size_t)w * h * texel_bytes;
         end = off + n;
+        if (ktx) packed.insert(packed.end(), file.begin() + (ptrdiff_t)off, file.begin() + (ptrdiff_t)(off + n));      // (itwKtxReadHeader has checked the file's length)
     }
     if (outs.empty() || file.size() < end) { std::fprintf(stderr, "%s: truncated: %zu bytes, the header describes %zu\n", in_path, file.size(), end); return 1; }
     std::vector<uint8_t> texels(texels_bytes);
@@ -109,7 +124,7 @@ int decode_file(const char* in_path, const char* out_path)
     for (rgba_surface& s : outs) { s.ptr = texels.data() + at; at += (size_t)s.stride * s.height; }
     std::vector<uint32_t> min_alpha(outs.size());
     itwSetErrorMode(ITW_ON_ERROR_RETURN);
-    if (itwDecodeChain((int)desc.dxgi_format, file.data() + first, outs.data(), (int)outs.size(), nullptr, min_alpha.data()) != 0) {
+    if (itwDecodeChain((int)desc.dxgi_format, ktx ? packed.data() : file.data() + first, outs.data(), (int)outs.size(), nullptr, min_alpha.data()) != 0) {
         std::fprintf(stderr, "%s\n", itwLastError() ? itwLastError() : "itwDecodeChain refused the file (BC6H_SF16 is not decoded)");
         return 1;
     }
@@ -151,7 +166,7 @@ int main(int argc, char** argv)
     if (argc < 6) {
         std::fprintf(stderr, "usage: %s [--measure] [--refine <profile> <max_block_sse> | --refine-share <profile> <percent> | --refine-psnr <profile> <dB>]\n"
                              "          <format> <width> <height> <in.raw> <out.dds> [slice_pixels]\n"
-                             "       %s --decode <in.dds> <out.raw>\n", argv[0], argv[0]);
+                             "       %s --decode <in.dds | in.ktx> <out.raw>\n", argv[0], argv[0]);
         return 2;
     }
     const Format* f = nullptr;
@@ -169,8 +184,11 @@ int main(int argc, char** argv)
     rgba_surface padded = source;
     if (f->pad && ((width | height) & 3)) padded = itwPadToMultipleOf4(&source, f->texel_bytes);     // IntelPlugin.cpp:893-928
 
+    const bool etc1 = f->dxgi == ITW_FORMAT_ETC1_RGB8;
+    if (etc1 && refine_profile) { std::fprintf(stderr, "--refine* is for bc7_* and bc6h_*: ETC1 has one preset, there is nothing to refine with\n"); return 2; }
     ItwDdsDesc desc = { (uint32_t)padded.width, (uint32_t)padded.height, 1, (uint32_t)f->dxgi, 0, 1 };
-    std::vector<uint8_t> blocks(itwDdsLevelBytes(desc.dxgi_format, desc.width, desc.height));
+    ItwKtxDesc kdesc = { (uint32_t)padded.width, (uint32_t)padded.height, 1, ITW_FORMAT_ETC1_RGB8, 0, 0 };
+    std::vector<uint8_t> blocks(etc1 ? (size_t)(padded.width / 4) * (padded.height / 4) * 8 : itwDdsLevelBytes(desc.dxgi_format, desc.width, desc.height));
     const int64_t pitch = (int64_t)((padded.width + 3) / 4) * GetBytesPerBlock(f->dxgi);
     bool ok;
     if (refine_profile) {
@@ -210,6 +228,10 @@ int main(int argc, char** argv)
                              max_block_sse, (unsigned long long)rs.blocks, (unsigned long long)rs.listed, (unsigned long long)rs.replaced,
                              (unsigned long long)rs.sse_first, (unsigned long long)rs.sse_final, (unsigned long long)rs.worst_first, (unsigned long long)rs.worst_final);
         }
+    } else if (etc1) {
+        etc_enc_settings se;
+        itwGetProfile_etc_slow(&se);
+        ok = itwCompressImageSlicedEx(&padded, blocks.data(), pitch, f->dxgi, &se, slice_pixels, slice_pixels ? on_progress : nullptr, nullptr);
     } else {
         ok = itwCompressImageSliced(&padded, blocks.data(), pitch, f->fn, f->dxgi, /*multithreaded*/ true,
                                     slice_pixels, slice_pixels ? on_progress : nullptr, nullptr);
@@ -226,9 +248,12 @@ int main(int argc, char** argv)
                     (unsigned long long)st.sse[2], (unsigned long long)st.sse[3], st.max_abs[0], st.max_abs[1], st.max_abs[2], st.max_abs[3]);
     }
 
-    std::vector<uint8_t> file(itwDdsFileBytes(&desc));
+    std::vector<uint8_t> file(etc1 ? itwKtxFileBytes(&kdesc) : itwDdsFileBytes(&desc));
     const uint8_t* levels[1] = { blocks.data() };
-    if (itwDdsWriteFile(&desc, levels, 1, file.data(), file.size()) != file.size()) { std::fprintf(stderr, "DDS assembly failed\n"); return 1; }
+    if ((etc1 ? itwKtxWriteFile(&kdesc, levels, 1, file.data(), file.size()) : itwDdsWriteFile(&desc, levels, 1, file.data(), file.size())) != file.size() || file.empty()) {
+        std::fprintf(stderr, "%s assembly failed\n", etc1 ? "KTX" : "DDS");
+        return 1;
+    }
     FILE* out = std::fopen(argv[5], "wb");
     if (!out || std::fwrite(file.data(), 1, file.size(), out) != file.size()) { std::fprintf(stderr, "cannot write %s\n", argv[5]); return 1; }
     std::fclose(out);

@@ -96,7 +96,10 @@ int64_t itwBandForPartEx(int32_t width, int32_t height, int32_t bytes_per_block,
  *                      below 1 the call is refused through the error mode before any device work (the reference packs uninitialised storage).
  * A device src->ptr and src->stride are multiples of 4 and a device dst is 4-byte aligned (texels are read and blocks written as dwords, as on
  * CompressBlocksBC1's unaligned path); host pointers are staged and may have any alignment.
- * ETC1 calls are never joined with other threads' small calls. */
+ * ETC1 calls are never joined with other threads' small calls.
+ * Above the block call: itwCompressImageSlicedEx (slices, progress, early out) and itwCompressImageChain[Ex] (a whole mip chain or cube map,
+ * any image size) of itw_dispatch.h take ITW_FORMAT_ETC1_RGB8 with `settings` = const etc_enc_settings*; itwKtx* (itw_dds.h) stores the stream in a KTX 1.1 file.  There is
+ * no refined (two-tier) ETC1 call: the threshold buys too little to refine with. */
 void itwGetProfile_etc_slow(etc_enc_settings* settings);            /* fastSkipTreshold = 6 */
 void itwCompressBlocksETC1(const rgba_surface* src, uint8_t* dst, const etc_enc_settings* settings);
 

@@ -5,6 +5,8 @@
  * 'DXT1' / 'DXT5' FourCC header (128 bytes incl. magic), BC4 / BC5 'BC4U' / 'BC5U' (UNORM; 'ATI1' / 'ATI2' are read as these) and
  * 'BC4S' / 'BC5S' (SNORM; DDS.h:83-93, DirectXTexDDS.cpp:64-70, 480-483); the _SRGB variants, BC7 and BC6H carry the 'DX10' extension
  * (148 bytes).  Mip chains: top level first; cube maps: 6 faces, each with its full chain.
+ *
+ * Below the DDS functions: the KTX 1.1 container for ETC1 streams (itwKtx*), which DDS cannot carry.
  */
 #ifndef ITW_DDS_H
 #define ITW_DDS_H
@@ -43,6 +45,51 @@ size_t itwDdsWriteFile(const ItwDdsDesc* desc, const uint8_t* const* levels, siz
  * each be NULL.  The images follow each other without gaps, so image 0's offset to the end of the last image is the packed stream
  * itwDecodeChain (itw_decode.h) takes; host arithmetic only. */
 size_t itwDdsImage(const ItwDdsDesc* desc, uint32_t index, uint32_t* width, uint32_t* height, size_t* offset);
+
+/* ---- KTX 1.1 -------------------------------------------------------------------------------------------------------------------------
+ * KTX 1.1 container for the encoder's ETC1 block streams (Khronos KTX File Format Specification 1.1), the one format DDS has no
+ * code for.  It lives in this header because the set of product headers is fixed (tests/test_abi_boundary.py).  KTX carries the GL enum this library already uses as ETC1's
+ * format code (ITW_FORMAT_ETC1_RGB8 = GL_ETC1_RGB8_OES = 0x8D64, itw_dispatch.h) in glInternalFormat.
+ *
+ * File: a 64-byte header -- the 12-byte identifier AB 4B 54 58 20 31 31 BB 0D 0A 1A 0A, then 13 little-endian uint32:
+ * endianness 0x04030201, glType 0, glTypeSize 1, glFormat 0, glInternalFormat 0x8D64, glBaseInternalFormat 0x1907 (GL_RGB),
+ * pixelWidth, pixelHeight, pixelDepth 0, numberOfArrayElements 0, numberOfFaces 1 or 6, numberOfMipmapLevels >= 1,
+ * bytesOfKeyValueData -- then the key/value data, then the data LEVEL BY LEVEL: a uint32 imageSize (the bytes of one face of a
+ * cube map, of the whole level otherwise) followed by the level's 1 or 6 images in the order +X -X +Y -Y +Z -Z.  Level l is
+ * max(1, w >> l) x max(1, h >> l) texels, ceil(w/4) x ceil(h/4) blocks of 8 bytes; every image is a multiple of 8 bytes, so the
+ * format's cube and mip padding never occurs.
+ *
+ * FILE ORDER IS LEVEL-MAJOR, THEN FACE: image index = level * faces + face.  DDS, above, is face-major.  The images of a KTX
+ * file are not one packed stream either -- a size word sits in front of each level -- so a loader copies them into one before
+ * itwDecodeChain (itw_decode.h).
+ *
+ * Not here: KTX2, PKM, texture arrays, 3D textures, the other byte order, any other internal format.
+ */
+typedef struct ItwKtxDesc {
+    uint32_t width, height;         /* level 0, texels; >= 1 */
+    uint32_t mip_levels;            /* 1 .. 32 */
+    uint32_t gl_internal_format;    /* 0x8D64 (ITW_FORMAT_ETC1_RGB8) */
+    uint32_t is_cubemap;            /* 0 / 1: six faces, width == height */
+    uint32_t key_value_bytes;       /* bytesOfKeyValueData: 0 in what this library writes; reported by itwKtxReadHeader and counted in every offset */
+} ItwKtxDesc;
+
+/* 64, the fixed header; 0 if `desc` is not a texture this library stores (see the struct). */
+size_t itwKtxHeaderBytes(const ItwKtxDesc* desc);
+/* header + key/value data + for every level its size word and images; 0 for a bad desc */
+size_t itwKtxFileBytes(const ItwKtxDesc* desc);
+/* Writes the 64 header bytes into dst; returns 64, or 0 on error (bad desc, key_value_bytes != 0, capacity < 64). */
+size_t itwKtxWriteHeader(const ItwKtxDesc* desc, uint8_t* dst, size_t capacity);
+/* Parses and checks a whole file's bytes; returns the offset of level 0's size word (64 + key_value_bytes), 0 for what this library
+ * does not read: another identifier or byte order, an array, a depth, a height of 0, an internal format other than 0x8D64, faces other
+ * than 1 or 6, a cube that is not square, more than 32 levels, a file shorter than itwKtxFileBytes, or one whose imageSize words
+ * disagree with the sizes.  numberOfMipmapLevels 0 ("generate mips at load") reads as 1.  The key/value data is skipped. */
+size_t itwKtxReadHeader(const uint8_t* src, size_t size, ItwKtxDesc* desc);
+/* Whole file: `levels[i]` points at the blocks of image i in KTX order (level major, then face).  desc->key_value_bytes must be 0.
+ * Returns bytes written (== itwKtxFileBytes) or 0. */
+size_t itwKtxWriteFile(const ItwKtxDesc* desc, const uint8_t* const* levels, size_t nlevels, uint8_t* dst, size_t capacity);
+/* Image `index` in KTX order (level * faces + face): its size in texels and the offset of its blocks from the start of the file.
+ * Returns the image's byte size, 0 when index is out of range or desc is bad.  width, height and offset may each be NULL. */
+size_t itwKtxImage(const ItwKtxDesc* desc, uint32_t index, uint32_t* width, uint32_t* height, size_t* offset);
 
 #pragma GCC visibility pop
 #ifdef __cplusplus

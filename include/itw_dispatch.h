@@ -33,8 +33,11 @@ enum {
     ITW_DXGI_FORMAT_BC4_SNORM = 81, ITW_DXGI_FORMAT_BC5_SNORM = 84,       /* their signed pair (RGBA8_SNORM sources), itw_bc45.h */
     ITW_DXGI_FORMAT_BC6H_UF16 = 95, ITW_DXGI_FORMAT_BC6H_SF16 = 96,
     ITW_DXGI_FORMAT_BC7_UNORM = 98, ITW_DXGI_FORMAT_BC7_UNORM_SRGB = 99,
-    /* ETC1 has no DXGI code: it goes by its GL enum, GL_ETC1_RGB8_OES.  Only the decode and measure entry points of itw_decode.h take it
-     * (the encoder is itwCompressBlocksETC1, itw_amd.h); to everything in this header it is an unknown format. */
+    /* ETC1 has no DXGI code: it goes by its GL enum, GL_ETC1_RGB8_OES (also KTX's glInternalFormat: itwKtx*, itw_dds.h).  Taken by the decode and
+     * measure entry points of itw_decode.h and, with `settings` = const etc_enc_settings*, by itwCompressImageSlicedEx, itwSliceWindow[For],
+     * itwChainBytes and itwCompressImageChain[Ex] below (the block encoder is itwCompressBlocksETC1, itw_amd.h).  It has no CompressImage*
+     * trampoline, so itwCompressImageSliced / itwCompressImageChain run a caller's function as the literal loop; the refined calls, the
+     * multi-GPU calls and DDS do not know it. */
     ITW_FORMAT_ETC1_RGB8 = 0x8D64
 };
 
@@ -108,7 +111,9 @@ typedef bool (ItwProgressFunc)(int done, int total, void* user);
 bool itwCompressImageSliced(const rgba_surface* source, uint8_t* target, int64_t block_row_pitch, CompressionFunc* cmpFunc,
                             int dxgi_format, bool multithreaded, int64_t slice_pixels, ItwProgressFunc* progress, void* user);
 /* The pipeline itself, for callers that hold a settings struct rather than a trampoline: `settings` = bc7_enc_settings* (BC7),
- * bc6h_enc_settings* (BC6H), ignored otherwise.  Same slices, progress contract and return value. */
+ * bc6h_enc_settings* (BC6H), etc_enc_settings* (ITW_FORMAT_ETC1_RGB8: RGBA8 source, alpha ignored, partial blocks dropped, 8-byte blocks;
+ * a null pointer or fastSkipTreshold < 1 fails through the error mode before any device work, a threshold above 165 is 165; the threshold
+ * is copied, the struct need not outlive the call's setup), ignored otherwise.  Same slices, progress contract and return value. */
 bool itwCompressImageSlicedEx(const rgba_surface* source, uint8_t* target, int64_t block_row_pitch, int dxgi_format, const void* settings,
                               int64_t slice_pixels, ItwProgressFunc* progress, void* user);
 /* W: slices per window.  itwSetSliceWindow(n > 0) fixes it process-wide (1 = the reference's early-out granularity exactly), 0 = by
@@ -116,7 +121,7 @@ bool itwCompressImageSlicedEx(const rgba_surface* source, uint8_t* target, int64
  * (also env ITW_SLICED_PIPELINE=0).  itwSliceWindow reports what a call would use (0: the literal loop). */
 void itwSetSliceWindow(int slices);
 int  itwSliceWindow(int dxgi_format, int width, int height, int64_t slice_pixels);
-/* ... for given settings (bc7_enc_settings* / bc6h_enc_settings* / NULL): BC7 settings whose modes 1/3 scan every two-subset shape (`slow`, `alpha_slow`:
+/* ... for given settings (bc7_enc_settings* / bc6h_enc_settings* / etc_enc_settings* / NULL): ETC1 takes BC7's ~131 072 blocks; BC7 settings whose modes 1/3 scan every two-subset shape (`slow`, `alpha_slow`:
  * twice the work per block) take windows twice as large; itwSliceWindow is this with NULL (every preset the plugin selects). */
 int  itwSliceWindowFor(int dxgi_format, const void* settings, int width, int height, int64_t slice_pixels);
 
@@ -130,11 +135,11 @@ int  itwSliceWindowFor(int dxgi_format, const void* settings, int width, int hei
  * another, tightly packed: image i starts at the sum of the sizes of images < i -- for a DirectXTex ScratchImage (array item, face, mip:
  * DDS order) that is exactly imgCompressed[0].pixels and a DDS payload.  Same bytes as, for each image in order, the plugin's
  * DoPaddingToMultiplesOf4 + CompressImageMT (ISPC formats) or DirectX::Compress (BC4/BC5: partial blocks kept).
- *   * Formats: the ten DXGI values above (71, 72, 77, 78, 80, 83, 95, 96, 98, 99).  `settings` as in itwCompressImageSlicedEx:
- *     bc7_enc_settings* (BC7), bc6h_enc_settings* (BC6H), ignored otherwise.
- *   * Pixels: RGBA8, or RGBA16F for BC6H.
+ *   * Formats: the twelve DXGI values above (71, 72, 77, 78, 80, 81, 83, 84, 95, 96, 98, 99) and ITW_FORMAT_ETC1_RGB8.  `settings` as in
+ *     itwCompressImageSlicedEx: bc7_enc_settings* (BC7), bc6h_enc_settings* (BC6H), etc_enc_settings* (ETC1), ignored otherwise.
+ *   * Pixels: RGBA8 (ETC1 ignores alpha), or RGBA16F for BC6H.
  *   * Images: any width and height >= 1, any `stride` >= the row's bytes.  Sizes that are not multiples of 4 are padded as the plugin pads
- *     them: edge replication for BC1, BC3, BC6H and BC7 (itwPadToMultipleOf4's rule), DirectXTex's partial-block fill for BC4 and BC5
+ *     them: edge replication for BC1, BC3, BC6H, BC7 and ETC1 (itwPadToMultipleOf4's rule), DirectXTex's partial-block fill for BC4 and BC5
  *     (CompressBlocksBC4/5's rule).
  *   * Pointers: all images host pointers, or all device pointers of the calling thread's current device; mixing them is an error.
  *     `target` may be either kind.  Synchronous either way, like itwCompressImageSliced.
@@ -142,11 +147,11 @@ int  itwSliceWindowFor(int dxgi_format, const void* settings, int width, int hei
  *   * Progress: progress(i, count, user) is called for i = 1 .. count, in order, each call only once every image < i is in `target`.  A false
  *     return stops the job and the call returns false: images < i stay written, and so may images of work already in flight (as with the
  *     slice pipeline's windows).  `progress` runs on the calling thread while later work is in flight: it must not call back into this library.
- *   * Errors: count <= 0, a null pointer (images, target, an image's texels, null BC7 / BC6H settings), a width or height < 1, a stride below
+ *   * Errors: count <= 0, a null pointer (images, target, an image's texels, null BC7 / BC6H / ETC1 settings), an ETC1 threshold < 1, a width or height < 1, a stride below
  *     the row's bytes, an unknown format, or mixed pointer kinds fail the call through the library's error mode before any device work
  *     starts; under ITW_ON_ERROR_RETURN it returns false and itwLastError() holds the message.
  *   * itwCompressImageChain with one of THIS library's CompressImage* trampolines resolves to the same path as the Ex call with the
- *     trampoline's preset; any other `cmpFunc` gets the plugin's literal loop: pad (host; device images on the device), then `cmpFunc`, per image.
+ *     trampoline's preset; any other `cmpFunc` (for ETC1, which has no trampoline: every one) gets the plugin's literal loop: pad (host; device images on the device), then `cmpFunc`, per image.
  * How: consecutive images are gathered into groups of up to a slice-pipeline window of blocks (itwSliceWindowFor's ~131 072 / 262 144), each
  * group packed into one surface on the device and encoded as one; the groups run as the windows of itwCompressImageSliced do.  An image of
  * at least a window whose width and height are multiples of 4 is encoded in place as one whole-surface call. */

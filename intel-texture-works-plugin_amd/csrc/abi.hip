@@ -198,15 +198,18 @@ void* grow(void*& buf, size_t& cap, size_t need)
     return buf;
 }
 
-enum class Fmt { BC1, BC3, BC7, BC6H, BC4, BC5, ETC1 };      // ETC1: itwCompressBlocksETC1 only; job_of (slices, chains, the GPU pool) does not know it
+enum class Fmt { BC1, BC3, BC7, BC6H, BC4, BC5, ETC1 };      // ETC1: itwCompressBlocksETC1, slices and chains (job_of); no trampoline, no combiner, no refine, no multi-GPU
 
 struct Job {
     Fmt fmt;
     bool snorm = false;         // BC4 / BC5 only: the SNORM pair (same geometry, block size and staging; its own kernels)
     const bc7_enc_settings*  s7 = nullptr;
     const bc6h_enc_settings* s6 = nullptr;
-    int etc_threshold = 0;      // ETC1 only: fastSkipTreshold, >= 1
+    int etc_threshold = 0;      // ETC1 only: fastSkipTreshold, >= 1 (a copy: the caller's etc_enc_settings need not outlive job_of)
 };
+
+// bytes per encoded block: the one place that knows (every stride into a block stream comes from here)
+int block_bytes(const Job& j) { return (j.fmt == Fmt::BC1 || j.fmt == Fmt::BC4 || j.fmt == Fmt::ETC1) ? 8 : 16; }
 
 // The BC7 workspace is per host thread.  Work already queued on another stream may still be using it, so a change
 // of stream makes the new stream wait for a library-owned event recorded behind the previous call (never for the
@@ -315,7 +318,10 @@ void launch(const Job& j, const uint8_t* d_src, int64_t stride, int w, int h, ui
     }
     case Fmt::BC4:  (j.snorm ? itw::launch_bc4s : itw::launch_bc4)(d_src, stride, w, h, d_dst, st); break;
     case Fmt::BC5:  (j.snorm ? itw::launch_bc5s : itw::launch_bc5)(d_src, stride, w, h, d_dst, st); break;
-    case Fmt::ETC1: itw::launch_etc1(d_src, stride, w, h, d_dst, j.etc_threshold, st); break;
+    case Fmt::ETC1:
+        if ((int64_t)(w / 4) * (h / 4) > (int64_t)INT32_MAX) itw::fail_msg("ETC1: %d x %d is more blocks than one launch covers", w, h);
+        itw::launch_etc1(d_src, stride, w, h, d_dst, j.etc_threshold, st);
+        break;
     }
     ITW_CHECK(hipGetLastError());
 }
@@ -349,7 +355,7 @@ void compress(const Job& j, const rgba_surface* src, uint8_t* dst, bool may_coal
     const int bx = keep_partial ? (w > 0 ? (w + 3) / 4 : 0) : w / 4, by = keep_partial ? (h > 0 ? (h + 3) / 4 : 0) : h / 4;
     if (bx <= 0 || by <= 0) return;                   // nothing to encode: the reference's loops do not run either
     if (!src->ptr || !dst) itw::fail_msg("null texel or destination pointer");
-    const int bpb = (j.fmt == Fmt::BC1 || j.fmt == Fmt::BC4 || j.fmt == Fmt::ETC1) ? 8 : 16;
+    const int bpb = block_bytes(j);
     const int texel_bytes = (j.fmt == Fmt::BC6H) ? 8 : 4;
     const size_t row_bytes = keep_partial ? (size_t)w * 4 : (size_t)bx * 4 * texel_bytes;
     const size_t rows = keep_partial ? (size_t)h : (size_t)by * 4;
@@ -582,8 +588,8 @@ int slice_window(Fmt fmt, int64_t slice_blocks, int slices, bool heavy)
     int W = slice_window_setting();
     if (W <= 0) {
         // BC7 / BC6H: a window must fill the chip (131 072 blocks = one block per lane of 2 waves per SIMD; up to three windows are in flight);
-        // BC1 / BC3 / BC4 / BC5 are PCIe-bound: fewer, larger copies
-        const bool compute = fmt == Fmt::BC7 || fmt == Fmt::BC6H;
+        // ETC1 goes with them; BC1 / BC3 / BC4 / BC5 are PCIe-bound: fewer, larger copies
+        const bool compute = fmt == Fmt::BC7 || fmt == Fmt::BC6H || fmt == Fmt::ETC1;
         const int64_t target = (compute && !heavy) ? 131072 : 262144;
         const int64_t per = slice_blocks < 1 ? 1 : slice_blocks;
         W = (int)((target + per / 2) / per);
@@ -630,7 +636,7 @@ bool compress_sliced(const Job& j, const rgba_surface* src, uint8_t* dst, int sl
     };
     if (bx <= 0 || by <= 0) return share ? true : poll(1, slices - 1);   // nothing to encode: the reference's loop still polls
     if (!src->ptr || !dst) itw::fail_msg("null texel or destination pointer");
-    const int bpb = (j.fmt == Fmt::BC1 || j.fmt == Fmt::BC4) ? 8 : 16;
+    const int bpb = block_bytes(j);
     const int texel_bytes = (j.fmt == Fmt::BC6H) ? 8 : 4;
     const size_t row_bytes = keep_partial ? (size_t)w * 4 : (size_t)bx * 4 * texel_bytes;
     const size_t rows = keep_partial ? (size_t)h : (size_t)by * 4;
@@ -748,7 +754,7 @@ bool compress_sliced(const Job& j, const rgba_surface* src, uint8_t* dst, int sl
     return true;
 }
 
-// format code + settings pointer of the dispatch layer -> Job (the settings struct must outlive the job)
+// format code + settings pointer of the dispatch layer -> Job (BC7 / BC6H: the settings struct must outlive the job; ETC1's threshold is copied)
 Job job_of(int dxgi_format, const void* settings)
 {
     Job j;
@@ -761,6 +767,14 @@ Job job_of(int dxgi_format, const void* settings)
     case ITW_DXGI_FORMAT_BC5_SNORM: j.fmt = Fmt::BC5; j.snorm = true; break;
     case ITW_DXGI_FORMAT_BC6H_UF16: case ITW_DXGI_FORMAT_BC6H_SF16: j.fmt = Fmt::BC6H; j.s6 = static_cast<const bc6h_enc_settings*>(settings); break;
     case ITW_DXGI_FORMAT_BC7_UNORM: case ITW_DXGI_FORMAT_BC7_UNORM_SRGB: j.fmt = Fmt::BC7; j.s7 = static_cast<const bc7_enc_settings*>(settings); break;
+    case ITW_FORMAT_ETC1_RGB8: {
+        const etc_enc_settings* se = static_cast<const etc_enc_settings*>(settings);
+        if (!se) itw::fail_msg("null settings for an ETC1 job");
+        if (se->fastSkipTreshold < 1)
+            itw::fail_msg("ETC1: fastSkipTreshold %d (1 .. 165; the reference emits uninitialised storage below 1)", se->fastSkipTreshold);
+        j.fmt = Fmt::ETC1; j.etc_threshold = se->fastSkipTreshold;           // (above 165: launch_etc1 takes 165)
+        break;
+    }
     default: itw::fail_msg("DXGI format %d is not one this library encodes", dxgi_format);
     }
     if ((j.fmt == Fmt::BC7 || j.fmt == Fmt::BC6H) && !settings) itw::fail_msg("null settings for a BC7 / BC6H job");
@@ -787,9 +801,9 @@ constexpr int kChainPackedBlocks = 1024;              // P: blocks per packed ro
 
 int64_t chain_image_blocks(const rgba_surface& s) { return (int64_t)((s.width + 3) / 4) * ((s.height + 3) / 4); }
 
-int64_t chain_budget(const Job& j)                    // slice_window's target: ~131 072 blocks, 262 144 for BC1/3/4/5 and the heavy BC7 settings
+int64_t chain_budget(const Job& j)                    // slice_window's target: ~131 072 blocks (BC7, BC6H, ETC1), 262 144 for BC1/3/4/5 and the heavy BC7 settings
 {
-    return ((j.fmt == Fmt::BC7 && !heavy_job(j)) || j.fmt == Fmt::BC6H) ? 131072 : 262144;
+    return ((j.fmt == Fmt::BC7 && !heavy_job(j)) || j.fmt == Fmt::BC6H || j.fmt == Fmt::ETC1) ? 131072 : 262144;
 }
 
 // everything a bad call can be told by before any device is touched (the pointer kinds come after this)
@@ -816,7 +830,7 @@ bool chain_groups(const Job& j, const rgba_surface* im, uint8_t* target, const s
                   bool src_dev, bool dst_dev, Poll&& poll)
 {
     const int px = j.fmt == Fmt::BC6H ? 8 : 4;
-    const int bpb = (j.fmt == Fmt::BC1 || j.fmt == Fmt::BC4) ? 8 : 16;
+    const int bpb = block_bytes(j);
     const bool fill45 = j.fmt == Fmt::BC4 || j.fmt == Fmt::BC5;
     const int ngroups = (int)(u1 - u0);
     auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
@@ -955,7 +969,7 @@ bool compress_chain(const Job& j, const rgba_surface* im, int count, uint8_t* ta
         }
     }
     const bool dst_dev = is_device_pointer(target);
-    const int bpb = (j.fmt == Fmt::BC1 || j.fmt == Fmt::BC4) ? 8 : 16;
+    const int bpb = block_bytes(j);
 
     // units, in order: in-place images, and groups of consecutive images of up to `budget` blocks
     const int64_t budget = chain_budget(j);
@@ -1097,6 +1111,7 @@ bool same_settings(const Pending& a, const Pending& b)
         return x.slow_mode == y.slow_mode && x.fast_mode == y.fast_mode && x.refineIterations_1p == y.refineIterations_1p &&
                x.refineIterations_2p == y.refineIterations_2p && x.fastSkipTreshold == y.fastSkipTreshold;
     }
+    if (a.job.fmt == Fmt::ETC1) return a.job.etc_threshold == b.job.etc_threshold;
     return true;
 }
 
@@ -1105,7 +1120,7 @@ bool continues(const Pending& a, const Pending& b)
 {
     if (!same_settings(a, b) || a.src.width != b.src.width || a.src.stride != b.src.stride) return false;
     if ((a.src.height & 3) || a.src.stride <= 0) return false;
-    const int bpb = (a.job.fmt == Fmt::BC1 || a.job.fmt == Fmt::BC4) ? 8 : 16;
+    const int bpb = block_bytes(a.job);
     const bool keep = a.job.fmt == Fmt::BC4 || a.job.fmt == Fmt::BC5;
     const int64_t bx = keep ? (a.src.width + 3) / 4 : a.src.width / 4;
     return b.src.ptr == a.src.ptr + (int64_t)a.src.height * a.src.stride && b.dst == a.dst + (int64_t)(a.src.height / 4) * bx * bpb;
@@ -1308,7 +1323,8 @@ bool sliced_part(const rgba_surface* source, uint8_t* target, int dxgi_format, c
 void chain_check(const rgba_surface* images, int count, const uint8_t* target, int dxgi_format)
 {
     alignas(16) static const unsigned char any_settings[sizeof(bc7_enc_settings)] = {0};      // (the caller's own function takes none)
-    (void)chain_job(images, count, target, dxgi_format, any_settings);
+    static const etc_enc_settings any_etc = {1};
+    (void)chain_job(images, count, target, dxgi_format, dxgi_format == ITW_FORMAT_ETC1_RGB8 ? (const void*)&any_etc : (const void*)any_settings);
 }
 
 void encode_resident(int dxgi_format, const void* settings, const uint8_t* d_src, int64_t stride, int width, int height, uint8_t* d_dst)
@@ -1443,7 +1459,7 @@ bool itwCompressImageSlicedEx(const rgba_surface* source, uint8_t* target, int64
         if (!source) itw::fail_msg("null surface");
         const Job j = job_of(dxgi_format, settings);
         const bool keep = j.fmt == Fmt::BC4 || j.fmt == Fmt::BC5;
-        const int64_t tight = (int64_t)(keep ? (source->width + 3) / 4 : source->width / 4) * ((j.fmt == Fmt::BC1 || j.fmt == Fmt::BC4) ? 8 : 16);
+        const int64_t tight = (int64_t)(keep ? (source->width + 3) / 4 : source->width / 4) * block_bytes(j);
         if (block_row_pitch != tight) itw::fail_msg("itwCompressImageSlicedEx: block_row_pitch %lld != %lld (tight)", (long long)block_row_pitch, (long long)tight);
         done = compress_sliced(j, source, target, slices_of(source, slice_pixels), progress, user);
     });
@@ -1477,7 +1493,7 @@ int itwSliceWindowFor(int dxgi_format, const void* settings, int width, int heig
                       dxgi_format == ITW_DXGI_FORMAT_BC4_SNORM || dxgi_format == ITW_DXGI_FORMAT_BC5_SNORM;
     const int64_t blocks = keep ? (int64_t)((width + 3) / 4) * ((height + 3) / 4) : (int64_t)(width / 4) * (height / 4);
     const bool heavy = dxgi_format == ITW_DXGI_FORMAT_BC7_UNORM || dxgi_format == ITW_DXGI_FORMAT_BC7_UNORM_SRGB ||
-                       dxgi_format == ITW_DXGI_FORMAT_BC6H_UF16 || dxgi_format == ITW_DXGI_FORMAT_BC6H_SF16;
+                       dxgi_format == ITW_DXGI_FORMAT_BC6H_UF16 || dxgi_format == ITW_DXGI_FORMAT_BC6H_SF16 || dxgi_format == ITW_FORMAT_ETC1_RGB8;
     const bool bc7 = dxgi_format == ITW_DXGI_FORMAT_BC7_UNORM || dxgi_format == ITW_DXGI_FORMAT_BC7_UNORM_SRGB;
     const bool every_shape = bc7 && settings && itw::bc7_scans_every_shape(*static_cast<const bc7_enc_settings*>(settings));
     return slice_window(heavy ? Fmt::BC7 : Fmt::BC1, blocks / slices, (int)slices, every_shape);

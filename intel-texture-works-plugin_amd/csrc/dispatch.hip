@@ -249,6 +249,7 @@ ITW_BC6H_TRAMPOLINE(veryfast) ITW_BC6H_TRAMPOLINE(fast) ITW_BC6H_TRAMPOLINE(basi
 
 // The library's own trampolines are recognised by address: for them the slice loop runs as a pipeline (abi.hip, compress_sliced) with the
 // format and the preset's settings in hand.  Any other CompressionFunc is opaque -- it can only be called, synchronously, slice by slice.
+// ETC1 (ITW_FORMAT_ETC1_RGB8) has no trampoline: a caller's function around itwCompressBlocksETC1 is such an opaque one; the pipeline is itwCompressImageSlicedEx's.
 static bool resolve_trampoline(CompressionFunc* fn, int dxgi_format, bc7_enc_settings* s7, bc6h_enc_settings* s6, const void** settings)
 {
     *settings = nullptr;
@@ -401,7 +402,7 @@ int64_t itwChainBytes(const rgba_surface* images, int count, int dxgi_format)
     case ITW_DXGI_FORMAT_BC1_UNORM: case ITW_DXGI_FORMAT_BC1_UNORM_SRGB: case ITW_DXGI_FORMAT_BC3_UNORM: case ITW_DXGI_FORMAT_BC3_UNORM_SRGB:
     case ITW_DXGI_FORMAT_BC4_UNORM: case ITW_DXGI_FORMAT_BC5_UNORM: case ITW_DXGI_FORMAT_BC6H_UF16: case ITW_DXGI_FORMAT_BC6H_SF16:
     case ITW_DXGI_FORMAT_BC4_SNORM: case ITW_DXGI_FORMAT_BC5_SNORM:
-    case ITW_DXGI_FORMAT_BC7_UNORM: case ITW_DXGI_FORMAT_BC7_UNORM_SRGB: break;
+    case ITW_DXGI_FORMAT_BC7_UNORM: case ITW_DXGI_FORMAT_BC7_UNORM_SRGB: case ITW_FORMAT_ETC1_RGB8: break;
     default: return -1;
     }
     if (!images || count <= 0) return -1;
@@ -413,7 +414,7 @@ int64_t itwChainBytes(const rgba_surface* images, int count, int dxgi_format)
     return total;
 }
 
-// The library's own trampolines resolve to the one-call chain (abi.hip, compress_chain).  Any other function gets IntelPlugin.cpp:229-255
+// The library's own trampolines resolve to the one-call chain (abi.hip, compress_chain).  Any other function (ETC1 has no trampoline: always) gets IntelPlugin.cpp:229-255
 // literally: per image, DoPaddingToMultiplesOf4 (ISPC formats whose size is not a multiple of 4; the device images of such a call are padded on
 // the device into a scratch buffer), then the function on the padded surface; BC4/BC5 images go to it unpadded, as DirectX::Compress takes them.
 bool itwCompressImageChain(const rgba_surface* images, int count, uint8_t* target, CompressionFunc* cmpFunc, int dxgi_format,

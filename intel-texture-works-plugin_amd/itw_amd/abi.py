@@ -33,7 +33,9 @@ EXPORTED_SYMBOLS = tuple(
     # include/itw_decode.h: device decoders
     + ["itwDecodeBlocks", "itwDecodeChain", "itwDecodeImage", "itwMeasureBlocks", "itwMeasureChain", "itwStatsPsnr"]
     # include/itw_dds.h: DDS container
-    + ["itwDdsLevelBytes", "itwDdsHeaderBytes", "itwDdsFileBytes", "itwDdsWriteHeader", "itwDdsReadHeader", "itwDdsWriteFile", "itwDdsImage"])
+    + ["itwDdsLevelBytes", "itwDdsHeaderBytes", "itwDdsFileBytes", "itwDdsWriteHeader", "itwDdsReadHeader", "itwDdsWriteFile", "itwDdsImage"]
+    # include/itw_dds.h, second part: KTX 1.1 container (ETC1)
+    + ["itwKtxHeaderBytes", "itwKtxFileBytes", "itwKtxWriteHeader", "itwKtxReadHeader", "itwKtxWriteFile", "itwKtxImage"])
 # include/itw_test_hooks.h: exported by libispc_texcomp_test.so only (the same sources built with -DITW_TEST_HOOKS), never by the product
 TEST_HOOK_SYMBOLS = ("itwTestRcp", "itwTestRsqrt", "itwTestF2I", "itwTestBc7TwoSubsetBounds", "itwTestBc45IndexTable", "itwTestBc45ClosestS",
                      "itwMultiGpuTestInjectFailure", "itwTestCombinerHold", "itwTestCombinerCounters")
@@ -68,7 +70,8 @@ class EtcSettings(C.Structure):
 
 assert C.sizeof(RgbaSurface) == 24 and C.sizeof(Bc7Settings) == 64 and C.sizeof(Bc6hSettings) == 16 and C.sizeof(EtcSettings) == 4
 
-# "etc1": ITW_FORMAT_ETC1_RGB8, the GL enum (ETC1 has no DXGI code); only decode / measure take it, every other entry point refuses it
+# "etc1": ITW_FORMAT_ETC1_RGB8, the GL enum (ETC1 has no DXGI code); decode, measure, the slice pipeline and the chain calls take it (with an
+# EtcSettings); the refined calls, the multi-GPU calls and DDS refuse it -- its container is KTX (KtxDesc, ktx_file, load_ktx)
 DXGI_FORMAT = {"etc1": 0x8D64, "bc1": 71, "bc1_srgb": 72, "bc3": 77, "bc3_srgb": 78, "bc4": 80, "bc4_snorm": 81, "bc5": 83, "bc5_snorm": 84, "bc6h": 95, "bc6h_sf16": 96, "bc7": 98, "bc7_srgb": 99}
 
 
@@ -76,6 +79,12 @@ class DdsDesc(C.Structure):
     """struct ItwDdsDesc (itw_dds.h)."""
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("mip_levels", C.c_uint32), ("dxgi_format", C.c_uint32),
                 ("is_cubemap", C.c_uint32), ("array_size", C.c_uint32)]
+
+
+class KtxDesc(C.Structure):
+    """struct ItwKtxDesc (itw_dds.h)."""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("mip_levels", C.c_uint32), ("gl_internal_format", C.c_uint32),
+                ("is_cubemap", C.c_uint32), ("key_value_bytes", C.c_uint32)]
 
 
 class MultiGpuRankStats(C.Structure):
@@ -379,6 +388,18 @@ def _load(path, hooks):
         L.itwDdsWriteFile.restype = C.c_size_t
         L.itwDdsImage.argtypes = [C.POINTER(DdsDesc), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_size_t)]
         L.itwDdsImage.restype = C.c_size_t
+        # KTX 1.1 container (itw_dds.h)
+        for n in ("itwKtxHeaderBytes", "itwKtxFileBytes"):
+            getattr(L, n).argtypes = [C.POINTER(KtxDesc)]
+            getattr(L, n).restype = C.c_size_t
+        L.itwKtxWriteHeader.argtypes = [C.POINTER(KtxDesc), C.c_void_p, C.c_size_t]
+        L.itwKtxWriteHeader.restype = C.c_size_t
+        L.itwKtxReadHeader.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(KtxDesc)]
+        L.itwKtxReadHeader.restype = C.c_size_t
+        L.itwKtxWriteFile.argtypes = [C.POINTER(KtxDesc), C.POINTER(C.c_void_p), C.c_size_t, C.c_void_p, C.c_size_t]
+        L.itwKtxWriteFile.restype = C.c_size_t
+        L.itwKtxImage.argtypes = [C.POINTER(KtxDesc), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_size_t)]
+        L.itwKtxImage.restype = C.c_size_t
     return L
 
 
@@ -570,8 +591,8 @@ def image_func(fmt, profile=None, L=None):
 
 def compress_image(fmt, img, profile=None, multithreaded=True, slice_pixels=0, progress=None, out=None, settings=None):
     """The plugin's save path below the pixel conversion (IntelPlugin.cpp:816-884): slice loop -> CompressImageMT/ST ->
-    trampoline -> CompressBlocks* (itwCompressImageSliced; with `settings` -- a Bc7Settings / Bc6hSettings -- through
-    itwCompressImageSlicedEx).  img: host numpy (H, W, 4) uint8 / uint16 half bits, or a CUDA torch tensor of that shape
+    trampoline -> CompressBlocks* (itwCompressImageSliced; with `settings` -- a Bc7Settings / Bc6hSettings / EtcSettings -- through
+    itwCompressImageSlicedEx; "etc1" has no trampoline and always goes that way, by default with etc_profile("slow")).  img: host numpy (H, W, 4) uint8 / uint16 half bits, or a CUDA torch tensor of that shape
     (then `out` is a CUDA uint8 tensor too unless given).  Returns (ok, blocks)."""
     import numpy as np
     _check_texel_type(fmt, img)
@@ -591,6 +612,8 @@ def compress_image(fmt, img, profile=None, multithreaded=True, slice_pixels=0, p
     dst = out.data_ptr() if hasattr(out, "data_ptr") else out.ctypes.data
     cb = PROGRESS_FUNC(progress) if progress else None
     pitch = block_count(fmt, w, 4) * BYTES_PER_BLOCK[fmt]
+    if fmt == "etc1" and settings is None:
+        settings = etc_profile(profile or "slow")
     if settings is not None:
         ok = lib().itwCompressImageSlicedEx(C.byref(surf), dst, pitch, DXGI_FORMAT[fmt], C.cast(C.byref(settings), C.c_void_p), slice_pixels,
                                             C.cast(cb, C.c_void_p) if cb else None, None)
@@ -622,7 +645,7 @@ def chain_bytes(fmt, images):
 def compress_chain(fmt, images, profile=None, settings=None, progress=None, out=None, cmp_func=None):
     """A whole mip chain / cube map / array in one call (itwCompressImageChainEx; with `cmp_func` -- a CompressionFunc address, e.g.
     image_func(fmt, profile) -- itwCompressImageChain).  images: list of host numpy arrays or CUDA torch tensors (H, W, 4), uint8 or
-    uint16 half bits for bc6h, all of one kind, any size >= 1.  `out` (optional): numpy array or CUDA uint8 tensor of chain_bytes() bytes;
+    uint16 half bits for bc6h, all of one kind, any size >= 1; "etc1" takes settings=EtcSettings (default etc_profile("slow")).  `out` (optional): numpy array or CUDA uint8 tensor of chain_bytes() bytes;
     by default the images' kind.  Returns (ok, blocks): the images' blocks one after another, tightly packed (a DDS payload)."""
     import numpy as np
     fmt_key = fmt
@@ -652,6 +675,8 @@ def compress_chain(fmt, images, profile=None, settings=None, progress=None, out=
             settings = bc7_profile(profile or "slow")
         elif settings is None and base == "bc6h":
             settings = bc6h_profile(profile or "slow")
+        elif settings is None and base == "etc1":
+            settings = etc_profile(profile or "slow")
         sp = C.cast(C.byref(settings), C.c_void_p) if settings is not None else None
         ok = lib().itwCompressImageChainEx(C.cast(arr, C.c_void_p), len(images), dst, DXGI_FORMAT[fmt_key], sp, cbp, None)
     return bool(ok), out
@@ -940,6 +965,59 @@ def load_dds(data, device=None):
         return desc, texels, [int(v) for v in amin]
     import torch
     texels, amin = decode_chain(fmt, torch.from_numpy(payload.copy()).to(device), sizes, want_min_alpha=True)
+    return desc, texels, [int(v) & 0xFFFFFFFF for v in amin.cpu().tolist()]
+
+
+def ktx_file(width, height, levels, mip_levels=1, cubemap=False):
+    """KTX 1.1 file bytes for the ETC1 block arrays `levels` in KTX order: level major, then face (a DDS-ordered chain is face major)."""
+    import numpy as np
+    d = KtxDesc(width, height, mip_levels, DXGI_FORMAT["etc1"], 1 if cubemap else 0, 0)
+    total = lib().itwKtxFileBytes(C.byref(d))
+    if not total:
+        raise ValueError("unsupported KTX description")
+    out = np.empty(total, dtype=np.uint8)
+    keep = [np.ascontiguousarray(np.asarray(l, dtype=np.uint8)) for l in levels]
+    ptrs = (C.c_void_p * max(1, len(keep)))(*[k.ctypes.data for k in keep])
+    sizes = [n for _, _, _, n in ktx_images(d)]
+    if len(keep) != len(sizes) or any(k.size != n for k, n in zip(keep, sizes)):
+        raise ValueError("ktx_file: level count / sizes do not match the description")
+    n = lib().itwKtxWriteFile(C.byref(d), ptrs, len(keep), out.ctypes.data, out.size)
+    if n != total:
+        raise ValueError("itwKtxWriteFile failed")
+    return out
+
+
+def ktx_images(desc):
+    """itwKtxImage over a KtxDesc: [(height, width, offset, bytes)] of every image in file order (level, then face)."""
+    out = []
+    w, h, off = C.c_uint32(), C.c_uint32(), C.c_size_t()
+    i = 0
+    while True:
+        n = lib().itwKtxImage(C.byref(desc), i, C.byref(w), C.byref(h), C.byref(off))
+        if not n:
+            return out
+        out.append((int(h.value), int(w.value), int(off.value), int(n)))
+        i += 1
+
+
+def load_ktx(data, device=None):
+    """load_dds for a .ktx file's bytes: (KtxDesc, [texel arrays in file order: level, then face], [min alpha per image]).
+    itwKtxReadHeader + itwKtxImage; the images are copied into one packed stream on the host (a size word sits in front of each level),
+    then one itwDecodeChain.  device None: numpy arrays through host pointers; a torch device: CUDA tensors.  Raises ValueError for a
+    file this library does not read (itw_dds.h), a truncated one included."""
+    import numpy as np
+    raw = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+    desc = KtxDesc()
+    if not lib().itwKtxReadHeader(raw.ctypes.data, raw.size, C.byref(desc)):
+        raise ValueError("not an ETC1 KTX 1.1 file this library reads")
+    images = ktx_images(desc)
+    payload = np.concatenate([raw[off:off + n] for _, _, off, n in images])
+    sizes = [(h, w) for h, w, _, _ in images]
+    if device is None:
+        texels, amin = decode_chain("etc1", payload, sizes, want_min_alpha=True)
+        return desc, texels, [int(v) for v in amin]
+    import torch
+    texels, amin = decode_chain("etc1", torch.from_numpy(payload).to(device), sizes, want_min_alpha=True)
     return desc, texels, [int(v) & 0xFFFFFFFF for v in amin.cpu().tolist()]
 
 
