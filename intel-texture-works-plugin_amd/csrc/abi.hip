@@ -8,6 +8,13 @@
 // D2H) sits at the same line.  There is no CPU implementation behind this file:
 // a HIP failure is reported on stderr and the process aborts, or -- if the host opted in with itwSetErrorMode -- the
 // call returns and the message waits in itwLastError() (host_rt.hpp).
+//
+// The host layer, top to bottom: ThreadCtx (per-thread streams, staging buffers, the workspace; release() frees all of it) -- Job (a BcnKind
+// of bcn_format.hpp plus the settings; every size and rule that follows from the format is read from that table, the geometry of a surface
+// from its surface_geometry) -- claim_workspace / workspace_used (the one way the workspace changes streams) -- launch() (format -> kernel
+// launcher) -- compress() (one call: resident, combined, windows, or staged runs) -- window_target_blocks / slice_window (the one window
+// size) -- WindowPipeline + run_windows (the one pipeline: compress_sliced's windows and chain_groups' groups) -- the small-call combiner --
+// presets -- the extern "C" entry points.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
@@ -25,6 +32,7 @@
 #include <mutex>
 #include <thread>
 #include <vector>
+#include "bcn_format.hpp"
 #include "host_rt.hpp"
 #include "kernels.hpp"
 #include "x86_math.hpp"
@@ -119,27 +127,31 @@ struct ThreadCtx {
     hipEvent_t  decode_event = nullptr;             // recorded after each chain decode: orders the table across streams, as ws_event does
     int    device = -1;
     char   info[256] = {0};
-    ~ThreadCtx() {
-        // best effort; the runtime may already be gone at process exit
-        if (d_in)  (void)hipFree(d_in);
-        if (d_out) (void)hipFree(d_out);
-        if (d_ws)  (void)hipFree(d_ws);
-        for (void* p : d_refine) if (p) (void)hipFree(p);
+    // Every buffer, stream, event and pinned word of the context, freed and forgotten: the one place a new resource is added to.  Best effort
+    // (the destructor runs it, and the runtime may already be gone at process exit): errors are ignored.  The caller's stream handles
+    // (user_stream, ws_stream, decode_stream) are not the library's to destroy.
+    void release() noexcept
+    {
+        auto free_dev = [](void*& p, size_t& cap) { if (p) (void)hipFree(p); p = nullptr; cap = 0; };
+        auto drop = [](hipStream_t& s) { if (s) (void)hipStreamDestroy(s); s = nullptr; };
+        auto forget = [](hipEvent_t& e) { if (e) (void)hipEventDestroy(e); e = nullptr; };
+        free_dev(d_in, in_cap); free_dev(d_out, out_cap);
+        free_dev(d_ws, ws_cap); ws_used = false;
+        for (int k = 0; k < 2; k++) free_dev(d_refine[k], refine_cap[k]);
         if (refine_count) (void)hipHostFree(refine_count);
-        if (d_decode) (void)hipFree(d_decode);
-        if (decode_event) (void)hipEventDestroy(decode_event);
-        if (own_stream) (void)hipStreamDestroy(own_stream);
-        if (copy_stream) (void)hipStreamDestroy(copy_stream);
-        for (auto e : ev_in) if (e) (void)hipEventDestroy(e);
-        for (auto e : ev_done) if (e) (void)hipEventDestroy(e);
-        if (ws_event) (void)hipEventDestroy(ws_event);
-        if (aux.stream) (void)hipStreamDestroy(aux.stream);
-        if (aux.fork) (void)hipEventDestroy(aux.fork);
-        if (aux.join) (void)hipEventDestroy(aux.join);
-        if (aux.mid) (void)hipEventDestroy(aux.mid);
-        if (verdict.event) (void)hipEventDestroy(verdict.event);
+        refine_count = nullptr;
+        free_dev(d_decode, decode_cap); decode_used = false;
+        forget(decode_event);
+        drop(own_stream); drop(copy_stream);
+        for (auto& e : ev_in) forget(e);
+        for (auto& e : ev_done) forget(e);
+        forget(ws_event);
+        drop(aux.stream); forget(aux.fork); forget(aux.join); forget(aux.mid);
+        forget(verdict.event);
         if (verdict.host_counts) (void)hipHostFree((void*)verdict.host_counts);
+        verdict.host_counts = nullptr; verdict.host_counts_dev = nullptr;
     }
+    ~ThreadCtx() { release(); }
 };
 thread_local ThreadCtx tls_own;
 // A combiner leader (below) works in its DEVICE's shared context instead of its own: whichever of the caller's 8 or 64 pool threads happens to
@@ -155,24 +167,7 @@ void bind_thread_to_current_device()
     int dev = 0;
     ITW_CHECK(hipGetDevice(&dev));
     if (tls.device == dev) return;
-    if (tls.d_in)  { (void)hipFree(tls.d_in);  tls.d_in = nullptr;  tls.in_cap = 0; }
-    if (tls.d_out) { (void)hipFree(tls.d_out); tls.d_out = nullptr; tls.out_cap = 0; }
-    if (tls.d_ws)  { (void)hipFree(tls.d_ws);  tls.d_ws = nullptr;  tls.ws_cap = 0; tls.ws_used = false; }
-    for (int k = 0; k < 2; k++) if (tls.d_refine[k]) { (void)hipFree(tls.d_refine[k]); tls.d_refine[k] = nullptr; tls.refine_cap[k] = 0; }
-    if (tls.refine_count) { (void)hipHostFree(tls.refine_count); tls.refine_count = nullptr; }
-    if (tls.d_decode) { (void)hipFree(tls.d_decode); tls.d_decode = nullptr; tls.decode_cap = 0; tls.decode_used = false; }
-    if (tls.decode_event) { (void)hipEventDestroy(tls.decode_event); tls.decode_event = nullptr; }
-    if (tls.own_stream) { (void)hipStreamDestroy(tls.own_stream); tls.own_stream = nullptr; }
-    if (tls.copy_stream) { (void)hipStreamDestroy(tls.copy_stream); tls.copy_stream = nullptr; }
-    for (auto& e : tls.ev_in) if (e) { (void)hipEventDestroy(e); e = nullptr; }
-    for (auto& e : tls.ev_done) if (e) { (void)hipEventDestroy(e); e = nullptr; }
-    if (tls.ws_event) { (void)hipEventDestroy(tls.ws_event); tls.ws_event = nullptr; }
-    if (tls.aux.stream) { (void)hipStreamDestroy(tls.aux.stream); tls.aux.stream = nullptr; }
-    if (tls.aux.fork) { (void)hipEventDestroy(tls.aux.fork); tls.aux.fork = nullptr; }
-    if (tls.aux.join) { (void)hipEventDestroy(tls.aux.join); tls.aux.join = nullptr; }
-    if (tls.aux.mid) { (void)hipEventDestroy(tls.aux.mid); tls.aux.mid = nullptr; }
-    if (tls.verdict.event) { (void)hipEventDestroy(tls.verdict.event); tls.verdict.event = nullptr; }
-    if (tls.verdict.host_counts) { (void)hipHostFree((void*)tls.verdict.host_counts); tls.verdict.host_counts = nullptr; tls.verdict.host_counts_dev = nullptr; }
+    tls.release();
     tls.device = dev;
 }
 
@@ -198,42 +193,30 @@ void* grow(void*& buf, size_t& cap, size_t need)
     return buf;
 }
 
-enum class Fmt { BC1, BC3, BC7, BC6H, BC4, BC5, ETC1 };      // ETC1: itwCompressBlocksETC1, slices and chains (job_of); no trampoline, no combiner, no refine, no multi-GPU
-
+// What to encode with: the format as the table knows it (bcn_format.hpp: every size and rule that follows from the format is read there) and
+// what the table cannot know -- the settings.  ETC1: itwCompressBlocksETC1, slices and chains; no trampoline, no combiner, no refine, no multi-GPU.
 struct Job {
-    Fmt fmt;
-    bool snorm = false;         // BC4 / BC5 only: the SNORM pair (same geometry, block size and staging; its own kernels)
+    itw::BcnKind kind = itw::BCN_NONE;
     const bc7_enc_settings*  s7 = nullptr;
     const bc6h_enc_settings* s6 = nullptr;
     int etc_threshold = 0;      // ETC1 only: fastSkipTreshold, >= 1 (a copy: the caller's etc_enc_settings need not outlive job_of)
 };
 
-// bytes per encoded block: the one place that knows (every stride into a block stream comes from here)
-int block_bytes(const Job& j) { return (j.fmt == Fmt::BC1 || j.fmt == Fmt::BC4 || j.fmt == Fmt::ETC1) ? 8 : 16; }
-
-// The BC7 workspace is per host thread.  Work already queued on another stream may still be using it, so a change
-// of stream makes the new stream wait for a library-owned event recorded behind the previous call (never for the
+// The workspace (BC7's inter-family one, the wide BC6H shape's) is per host thread.  Work already queued on another stream may still be using
+// it, so a change of stream makes the new stream wait for a library-owned event recorded behind the previous call (never for the
 // caller's old stream handle, which may have been destroyed since -- ADVICE r01); calls on one stream are ordered by
 // the stream itself.  Growing the workspace frees it first, and hipFree waits for the device.
-float* bc7_workspace(int w, int h, hipStream_t st, int64_t wide_max_blocks, const bc7_enc_settings* settings)
+void* claim_workspace(size_t bytes, hipStream_t st)
 {
     bind_thread_to_current_device();
     if (!tls.ws_event) ITW_CHECK(hipEventCreateWithFlags(&tls.ws_event, hipEventDisableTiming));
     if (tls.ws_used && tls.ws_stream != st) ITW_CHECK(hipStreamWaitEvent(st, tls.ws_event, 0));
-    float* ws = (float*)grow(tls.d_ws, tls.ws_cap, itw::bc7_workspace_bytes(w, h, wide_max_blocks, settings));
+    void* ws = grow(tls.d_ws, tls.ws_cap, bytes);
     tls.ws_stream = st; tls.ws_used = true;
     return ws;
 }
-
-// Grows the per-thread workspace to `bytes` under the same ordering rules (used to pre-size it for a multi-run call).
-void reserve_workspace(size_t bytes, hipStream_t st)
-{
-    bind_thread_to_current_device();
-    if (!tls.ws_event) ITW_CHECK(hipEventCreateWithFlags(&tls.ws_event, hipEventDisableTiming));
-    if (tls.ws_used && tls.ws_stream != st) ITW_CHECK(hipStreamWaitEvent(st, tls.ws_event, 0));
-    (void)grow(tls.d_ws, tls.ws_cap, bytes);
-    tls.ws_stream = st; tls.ws_used = true;
-}
+// the workspace is used up to here on `st` (what the next claim from another stream waits for)
+void workspace_used(hipStream_t st) { ITW_CHECK(hipEventRecord(tls.ws_event, st)); }
 
 // `staged`: a run of a host-pointer call.  Its upload / download overlap the neighbouring runs' kernels.  A BC7 run that is not a band
 // (compress() below: round 4's shape, and what content that needs modes 1/3 everywhere still gets) takes the wide shape up to 2^20
@@ -277,10 +260,11 @@ void ensure_bc7_aux()
 void launch(const Job& j, const uint8_t* d_src, int64_t stride, int w, int h, uint8_t* d_dst, hipStream_t st, bool staged = false, int band = -1,
             size_t ws_off = 0)
 {
-    switch (j.fmt) {
-    case Fmt::BC1:  itw::launch_bc1(d_src, stride, w, h, d_dst, st); break;
-    case Fmt::BC3:  itw::launch_bc3(d_src, stride, w, h, d_dst, st); break;
-    case Fmt::BC7:
+    switch (j.kind) {
+    case itw::BCN_NONE: break;                        // (job_of has refused it)
+    case itw::BCN_BC1:  itw::launch_bc1(d_src, stride, w, h, d_dst, st); break;
+    case itw::BCN_BC3:  itw::launch_bc3(d_src, stride, w, h, d_dst, st); break;
+    case itw::BCN_BC7:
         ensure_bc7_aux();
         tls.aux.wide_max_blocks = staged ? staged_wide_max_blocks() : 0;
         {
@@ -295,30 +279,25 @@ void launch(const Job& j, const uint8_t* d_src, int64_t stride, int w, int h, ui
                 if (tls.aux.verdict) tls.verdict.valid = false;
                 itw::launch_bc7(d_src, stride, w, h, d_dst, *j.s7, reinterpret_cast<float*>(static_cast<uint8_t*>(tls.d_ws) + ws_off), st, &tls.aux);
             } else {
-                float* ws = bc7_workspace(w, h, st, tls.aux.wide_max_blocks, j.s7);         // (sized and ordered already when ws_off != 0)
-                itw::launch_bc7(d_src, stride, w, h, d_dst, *j.s7, reinterpret_cast<float*>(reinterpret_cast<uint8_t*>(ws) + ws_off), st, &tls.aux);
-                ITW_CHECK(hipEventRecord(tls.ws_event, st));
+                void* ws = claim_workspace(itw::bc7_workspace_bytes(w, h, tls.aux.wide_max_blocks, j.s7), st);   // (sized and ordered already when ws_off != 0)
+                itw::launch_bc7(d_src, stride, w, h, d_dst, *j.s7, reinterpret_cast<float*>(static_cast<uint8_t*>(ws) + ws_off), st, &tls.aux);
+                workspace_used(st);
             }
         }
         break;
-    case Fmt::BC6H: {
-        // the wide shape's workspace shares the per-thread BC7 workspace buffer (same ordering rules)
+    case itw::BCN_BC6H: {
+        // the wide shape's workspace is the per-thread workspace too (most calls need none)
         const size_t need = itw::bc6h_workspace_bytes(w, h, *j.s6);
-        void* ws = nullptr;
-        if (need) {
-            bind_thread_to_current_device();
-            if (!tls.ws_event) ITW_CHECK(hipEventCreateWithFlags(&tls.ws_event, hipEventDisableTiming));
-            if (tls.ws_used && tls.ws_stream != st) ITW_CHECK(hipStreamWaitEvent(st, tls.ws_event, 0));
-            ws = grow(tls.d_ws, tls.ws_cap, need);
-            tls.ws_stream = st; tls.ws_used = true;
-        }
+        void* ws = need ? claim_workspace(need, st) : nullptr;
         itw::launch_bc6h(d_src, stride, w, h, d_dst, *j.s6, st, ws);
-        if (need) ITW_CHECK(hipEventRecord(tls.ws_event, st));
+        if (need) workspace_used(st);
         break;
     }
-    case Fmt::BC4:  (j.snorm ? itw::launch_bc4s : itw::launch_bc4)(d_src, stride, w, h, d_dst, st); break;
-    case Fmt::BC5:  (j.snorm ? itw::launch_bc5s : itw::launch_bc5)(d_src, stride, w, h, d_dst, st); break;
-    case Fmt::ETC1:
+    case itw::BCN_BC4:  itw::launch_bc4(d_src, stride, w, h, d_dst, st); break;
+    case itw::BCN_BC5:  itw::launch_bc5(d_src, stride, w, h, d_dst, st); break;
+    case itw::BCN_BC4S: itw::launch_bc4s(d_src, stride, w, h, d_dst, st); break;
+    case itw::BCN_BC5S: itw::launch_bc5s(d_src, stride, w, h, d_dst, st); break;
+    case itw::BCN_ETC1:
         if ((int64_t)(w / 4) * (h / 4) > (int64_t)INT32_MAX) itw::fail_msg("ETC1: %d x %d is more blocks than one launch covers", w, h);
         itw::launch_etc1(d_src, stride, w, h, d_dst, j.etc_threshold, st);
         break;
@@ -328,6 +307,7 @@ void launch(const Job& j, const uint8_t* d_src, int64_t stride, int w, int h, ui
 
 bool coalesce_small_call(const Job& j, const rgba_surface* src, uint8_t* dst, int64_t blocks);
 bool heavy_job(const Job& j);
+int64_t window_target_blocks(int kind, bool heavy);
 static int64_t bc7_window_min_blocks() { static const int64_t v = [] { const char* e = std::getenv("ITW_BC7_WINDOW_MIN"); return e ? (int64_t)std::atoll(e) : (int64_t)262144; }(); return v; }   // BC7 host-pointer calls from this size take windows (2048^2 `basic` 1.28 -> 1.17 ms, 2896^2 2.46 -> 1.97, `slow` 4.24 -> 3.13)
 bool compress_sliced(const Job& j, const rgba_surface* src, uint8_t* dst, int slices, ItwProgressFunc* progress, void* user, int fixed_window = 0,
                      const itw::SlicedPart* share = nullptr, bool leave_verdict = false);
@@ -350,16 +330,12 @@ void compress(const Job& j, const rgba_surface* src, uint8_t* dst, bool may_coal
     if (may_coalesce) itw::clear_failure();
     if (!src) itw::fail_msg("null surface");
     const int w = src->width, h = src->height;
-    // ISPC formats drop partial blocks (kernel.ispc:600-601); the DirectXTex formats keep them (DirectXTexCompress.cpp:108-116)
-    const bool keep_partial = (j.fmt == Fmt::BC4 || j.fmt == Fmt::BC5);
-    const int bx = keep_partial ? (w > 0 ? (w + 3) / 4 : 0) : w / 4, by = keep_partial ? (h > 0 ? (h + 3) / 4 : 0) : h / 4;
-    if (bx <= 0 || by <= 0) return;                   // nothing to encode: the reference's loops do not run either
+    const itw::SurfaceGeometry geo = itw::surface_geometry(j.kind, w, h);
+    if (geo.empty()) return;                          // nothing to encode: the reference's loops do not run either
     if (!src->ptr || !dst) itw::fail_msg("null texel or destination pointer");
-    const int bpb = block_bytes(j);
-    const int texel_bytes = (j.fmt == Fmt::BC6H) ? 8 : 4;
-    const size_t row_bytes = keep_partial ? (size_t)w * 4 : (size_t)bx * 4 * texel_bytes;
-    const size_t rows = keep_partial ? (size_t)h : (size_t)by * 4;
-    const size_t out_bytes = (size_t)bx * by * bpb;
+    const bool bc7 = j.kind == itw::BCN_BC7, bc6h = j.kind == itw::BCN_BC6H;
+    const int bx = geo.bx, by = geo.by, bpb = geo.bpb;
+    const size_t row_bytes = geo.row_bytes, rows = geo.rows, out_bytes = geo.out_bytes, pitch = geo.pitch;
 
     const bool src_dev = is_device_pointer(src->ptr);
     const bool dst_dev = is_device_pointer(dst);
@@ -369,22 +345,22 @@ void compress(const Job& j, const rgba_surface* src, uint8_t* dst, bool may_coal
         return;
     }
     // small host-pointer calls made concurrently by several host threads are joined into one (below)
-    if (may_coalesce && !src_dev && !dst_dev && coalesce_small_call(j, src, dst, (int64_t)bx * by)) return;
+    if (may_coalesce && !src_dev && !dst_dev && coalesce_small_call(j, src, dst, geo.blocks())) return;
 
     // Round 6: a large BC6H call, and a large BC7 call of a profile without an order verdict (everything but `slow`), takes the WINDOW pipeline
     // of the slice loop (compress_sliced below) with no callback: windows of ~131 072 blocks alternate between two kernel streams with the
     // neighbours' copies on the third -- measured against the runs below at 4096^2: BC6H `slow` 4.83 -> 4.3 ms, BC7 `alpha_basic` 3.31 -> 2.9,
     // `alpha_veryfast` 2.46 -> 2.0, `basic` 3.93 -> 3.6 (profiles/r06_host_pointer_path.txt, r06_sliced_timing.jsonl).  The tuning knobs of the runs keep the runs.
-    if (!src_dev && !dst_dev && !keep_partial && !std::getenv("ITW_HOST_CHUNKS") && !std::getenv("ITW_HOST_RUNS") && !std::getenv("ITW_HOST_WINDOWS_OFF")) {
-        const int64_t blocks = (int64_t)bx * by;
+    if (!src_dev && !dst_dev && !itw::keeps_partial_blocks(j.kind) && !std::getenv("ITW_HOST_CHUNKS") && !std::getenv("ITW_HOST_RUNS") && !std::getenv("ITW_HOST_WINDOWS_OFF")) {
+        const int64_t blocks = geo.blocks();
         // A profile WITH an order verdict (`slow`) takes the windows while the last estimate says the bounded order pays (each window runs it on one
         // stream: 5.6 against 6.05 ms for the staged runs below on the bench surface) and the staged runs -- whose remaining runs go wide -- while it
         // says nearly every block needs modes 1/3 (photographs: 7.3 against 7.6 ms as windows).  Either way the call leaves a fresh estimate.
-        const bool verdict_profile = j.fmt == Fmt::BC7 && itw::bc7_has_order_verdict(*j.s7);
-        const bool bc7w = j.fmt == Fmt::BC7 && blocks >= bc7_window_min_blocks() && itw::bc7_staged_bands_ok() && (!verdict_profile || !tls.staged_wide);
-        const bool bc6w = j.fmt == Fmt::BC6H && blocks >= 262144 && j.s6->slow_mode;    // (the other BC6H profiles are PCIe-bound: 2.98 vs 3.02 ms, fewer copies win)
+        const bool verdict_profile = bc7 && itw::bc7_has_order_verdict(*j.s7);
+        const bool bc7w = bc7 && blocks >= bc7_window_min_blocks() && itw::bc7_staged_bands_ok() && (!verdict_profile || !tls.staged_wide);
+        const bool bc6w = bc6h && blocks >= 262144 && j.s6->slow_mode;    // (the other BC6H profiles are PCIe-bound: 2.98 vs 3.02 ms, fewer copies win)
         if (bc7w || bc6w) {
-            const int64_t per_window = heavy_job(j) ? 262144 : 131072;
+            const int64_t per_window = window_target_blocks(j.kind, heavy_job(j));
             int64_t windows = (blocks + per_window / 2) / per_window;
             if (windows > by) windows = by;
             if (windows >= 2) { (void)compress_sliced(j, src, dst, (int)windows, nullptr, nullptr, 1, nullptr, bc7w && verdict_profile); return; }
@@ -397,8 +373,6 @@ void compress(const Job& j, const rgba_surface* src, uint8_t* dst, bool may_coal
         // producer of the device surface may still be running on the caller's stream
         ITW_CHECK(hipStreamSynchronize(tls.user_stream));
     }
-    // tight staging pitch, 16-byte aligned rows so the vector load path applies
-    const size_t pitch = (row_bytes + 15) & ~(size_t)15;
     uint8_t* in = src_dev ? nullptr : (uint8_t*)grow(tls.d_in, tls.in_cap, pitch * rows);
     const uint8_t* d_src = src_dev ? src->ptr : in;
     const int64_t d_stride = src_dev ? (int64_t)src->stride : (int64_t)pitch;
@@ -414,9 +388,9 @@ void compress(const Job& j, const rgba_surface* src, uint8_t* dst, bool may_coal
     // and a shorter last run shortens the download nothing can hide (ITW_HOST_RUNS="f0,f1,.." gives the fractions).
     int cut[9] = {0, by, 0, 0, 0, 0, 0, 0, 0};        // run c covers block rows [cut[c], cut[c+1])
     int nch = 1;
-    if (!src_dev && (j.fmt == Fmt::BC7 || j.fmt == Fmt::BC6H)) {
-        if (j.fmt == Fmt::BC7 && (int64_t)bx * by >= 524288)       { nch = 3; cut[1] = by / 8; cut[2] = by / 8 + by / 2; cut[3] = by; }
-        else if (j.fmt == Fmt::BC6H && (int64_t)bx * by >= 262144) { nch = 4; cut[1] = by / 8; cut[2] = by * 3 / 8; cut[3] = by * 11 / 16; cut[4] = by; }
+    if (!src_dev && (bc7 || bc6h)) {
+        if (bc7 && (int64_t)bx * by >= 524288)       { nch = 3; cut[1] = by / 8; cut[2] = by / 8 + by / 2; cut[3] = by; }
+        else if (bc6h && (int64_t)bx * by >= 262144) { nch = 4; cut[1] = by / 8; cut[2] = by * 3 / 8; cut[3] = by * 11 / 16; cut[4] = by; }
     }
     if (const char* e = std::getenv("ITW_HOST_CHUNKS")) {         // tuning / test knob (1..8 equal runs); 1 disables the overlap
         const int v = std::atoi(e);
@@ -440,7 +414,7 @@ void compress(const Job& j, const rgba_surface* src, uint8_t* dst, bool may_coal
     // estimate asked for (successive calls of a save -- mip levels, slices -- hold similar content), later runs this call's as soon as
     // it is in (polled under the uploads), and it is read once more behind the call's last synchronisation for the next call.
     // ITW_STAGED_BANDS=0: round 4's runs, one after the other in the wide shape.
-    const bool bands = j.fmt == Fmt::BC7 && nch > 1 && !src_dev && itw::bc7_staged_bands_ok();
+    const bool bands = bc7 && nch > 1 && !src_dev && itw::bc7_staged_bands_ok();
     size_t band_off[9] = {0}, probe_off = 0;                 // workspace: [wide runs (they follow each other on st)] [probe] [band 0] [band 1] ...
     if (bands) {
         ensure_bc7_aux();
@@ -458,11 +432,11 @@ void compress(const Job& j, const rgba_surface* src, uint8_t* dst, bool may_coal
             const int run_rows = (cut[c + 1] - cut[c]) * 4;
             if (run_rows > 0) total += (itw::bc7_workspace_bytes(w, run_rows, 1, j.s7) + 255) & ~(size_t)255;
         }
-        reserve_workspace(total, st);
+        (void)claim_workspace(total, st);
         ITW_CHECK(hipEventRecord(tls.aux.fork, st));          // the other streams start behind whatever ordered the workspace on the first
         ITW_CHECK(hipStreamWaitEvent(tls.aux.stream, tls.aux.fork, 0));
     } else
-    if (j.fmt == Fmt::BC7 || j.fmt == Fmt::BC6H) {
+    if (bc7 || bc6h) {
         // Size the workspace once for the most demanding run: growing it frees it, and hipFree waits for the runs in flight.
         // "Most demanding" is not "tallest" (ADVICE r02): a staged BC7 run of up to 2^20 blocks takes the wide shape at ~440
         // B/block while a taller one takes the deep shape at 36 B/block, so the maximum is taken over every run's own need.
@@ -471,10 +445,10 @@ void compress(const Job& j, const rgba_surface* src, uint8_t* dst, bool may_coal
         for (int c = 0; c < nch; c++) {
             const int run_rows = (cut[c + 1] - cut[c]) * 4;
             if (run_rows <= 0) continue;
-            const size_t b = (j.fmt == Fmt::BC7) ? itw::bc7_workspace_bytes(w, run_rows, wide_max, j.s7) : itw::bc6h_workspace_bytes(w, run_rows, *j.s6);
+            const size_t b = bc7 ? itw::bc7_workspace_bytes(w, run_rows, wide_max, j.s7) : itw::bc6h_workspace_bytes(w, run_rows, *j.s6);
             if (b > need) need = b;
         }
-        if (need) reserve_workspace(need, st);
+        if (need) (void)claim_workspace(need, st);
     }
     // A failure below is a C++ exception (and under ITW_ON_ERROR_RETURN the thread lives on): whatever this call has queued by then on the
     // thread's streams is drained and the workspace's event recorded, so the next call finds d_in / d_out / d_ws free of work in flight.
@@ -546,7 +520,7 @@ void compress(const Job& j, const rgba_surface* src, uint8_t* dst, bool may_coal
     if (bands) {                                              // everything back into st; the workspace's event behind all of it
         ITW_CHECK(hipEventRecord(tls.aux.join, tls.aux.stream));
         ITW_CHECK(hipStreamWaitEvent(st, tls.aux.join, 0));
-        ITW_CHECK(hipEventRecord(tls.ws_event, st));
+        workspace_used(st);
     }
     ITW_CHECK(hipStreamSynchronize(st));
     unwind.done = true;
@@ -580,17 +554,25 @@ int slice_window_setting()
     return W;
 }
 
+// The blocks a window aims at -- the unit of upload / launch / download of the slice loop, a chain's group budget, the windows of a large
+// host-pointer call.  BC7 / BC6H: a window must fill the chip (131 072 blocks = one block per lane of 2 waves per SIMD; up to three windows are
+// in flight); ETC1 goes with them; BC1 / BC3 / BC4 / BC5 are PCIe-bound: fewer, larger copies.
 // `heavy`: BC7 settings that scan every two-subset shape (`slow`, `alpha_slow`: bc7_scans_every_shape) -- twice the work per block and dependent
 // launch chains twice as long: windows twice as large (4096^2 `slow`, ms per sliced call with 8 / 16 / 32 slices per
 // window: bench surface 5.91 / 5.57 / 5.86, photograph 8.18 / 7.62 / 7.73)
-int slice_window(Fmt fmt, int64_t slice_blocks, int slices, bool heavy)
+int64_t window_target_blocks(int kind, bool heavy)
+{
+    const bool compute = kind == itw::BCN_BC7 || kind == itw::BCN_BC6H || kind == itw::BCN_ETC1;
+    return (compute && !heavy) ? 131072 : 262144;
+}
+bool heavy_job(const Job& j) { return j.kind == itw::BCN_BC7 && j.s7 && itw::bc7_scans_every_shape(*j.s7); }
+
+// W, slices per window
+int slice_window(int kind, int64_t slice_blocks, int slices, bool heavy)
 {
     int W = slice_window_setting();
     if (W <= 0) {
-        // BC7 / BC6H: a window must fill the chip (131 072 blocks = one block per lane of 2 waves per SIMD; up to three windows are in flight);
-        // ETC1 goes with them; BC1 / BC3 / BC4 / BC5 are PCIe-bound: fewer, larger copies
-        const bool compute = fmt == Fmt::BC7 || fmt == Fmt::BC6H || fmt == Fmt::ETC1;
-        const int64_t target = (compute && !heavy) ? 131072 : 262144;
+        const int64_t target = window_target_blocks(kind, heavy);
         const int64_t per = slice_blocks < 1 ? 1 : slice_blocks;
         W = (int)((target + per / 2) / per);
         // No cap by slice count (the first version kept >= 8 windows per job): a window is 0.3-1 ms of work, so a job long enough to show a
@@ -601,7 +583,6 @@ int slice_window(Fmt fmt, int64_t slice_blocks, int slices, bool heavy)
     if (W > slices) W = slices;
     return W;
 }
-bool heavy_job(const Job& j) { return j.fmt == Fmt::BC7 && j.s7 && itw::bc7_scans_every_shape(*j.s7); }
 
 struct SliceRows { int64_t y0, y1; };
 // rows of slice i of `slices` (IntelPlugin.cpp:861-865); the formats that keep partial blocks end the last slice at `height`
@@ -615,6 +596,86 @@ SliceRows slice_rows(int i, int slices, int height, bool keep_partial)
     return r;
 }
 
+// ---- the window pipeline: what the slice loop (compress_sliced) and a chain's gather groups (chain_groups) run on ------------------------
+// Window k's kernels run on kernel stream k % 2 (the thread's own stream and the second stream of the BC7 aux block), its upload and the
+// previous window's download on the copy stream; a BC7 window runs the deep shape in slice k % 2 of the per-thread workspace.  Uploads and
+// kernels are ordered through a ring of 8 event pairs indexed by the caller's LOCAL window number k (at most depth + 1 <= 5 windows are
+// between issue and retire).  The object waits for all three streams when it goes out of scope: however the call ends (a failure is a C++
+// exception here), nothing of it is left in flight on the thread's streams and buffers, and the workspace's event lies behind it.
+struct WindowPipeline {
+    hipStream_t k0, k1, cs;
+    size_t ws_off[2] = {0, 0};
+    bool ws_claimed = false;
+
+    // `bc7_slice_bytes` > 0: two workspace slices of that size (one per kernel stream).  Whatever produced a device surface (or still reads
+    // the destination) on the caller's stream comes first: `wait_for_user`.
+    WindowPipeline(bool wait_for_user, size_t bc7_slice_bytes)
+    {
+        ensure_device_ctx();
+        ensure_bc7_aux();
+        k0 = tls.own_stream; k1 = tls.aux.stream; cs = tls.copy_stream;
+        if (wait_for_user && tls.user_stream != k0) ITW_CHECK(hipStreamSynchronize(tls.user_stream));
+        if (bc7_slice_bytes) {
+            const size_t b = (bc7_slice_bytes + 255) & ~(size_t)255;
+            ws_off[1] = b;
+            (void)claim_workspace(2 * b, k0);
+            ws_claimed = true;
+        }
+    }
+    WindowPipeline(const WindowPipeline&) = delete;
+    ~WindowPipeline()
+    {
+        (void)hipStreamSynchronize(k0); (void)hipStreamSynchronize(k1); (void)hipStreamSynchronize(cs);
+        if (ws_claimed && tls.ws_event) (void)hipEventRecord(tls.ws_event, k0);
+        (void)hipGetLastError();
+    }
+    // the second kernel stream starts behind whatever is on the first by now (the workspace's ordering, a chain's descriptor table)
+    void fork() const
+    {
+        ITW_CHECK(hipEventRecord(tls.aux.fork, k0));
+        ITW_CHECK(hipStreamWaitEvent(k1, tls.aux.fork, 0));
+    }
+    hipStream_t stream(int k) const { return (k & 1) ? k1 : k0; }
+    size_t workspace(int k) const { return ws_off[k & 1]; }
+    void uploaded(int k) const          // window k's texels are queued on the copy stream: its kernels wait for them
+    {
+        ITW_CHECK(hipEventRecord(tls.ev_in[k & 7], cs));
+        ITW_CHECK(hipStreamWaitEvent(stream(k), tls.ev_in[k & 7], 0));
+    }
+    void encoded(int k) const { ITW_CHECK(hipEventRecord(tls.ev_done[k & 7], stream(k))); }      // everything of window k is queued
+    void wait_encoded(int k) const { ITW_CHECK(hipEventSynchronize(tls.ev_done[k & 7])); }       // a window written where it belongs
+    void fetch(int k, void* dst, const void* staged, size_t len, hipMemcpyKind kind) const       // a staged window: returns when it is in `dst`
+    {
+        ITW_CHECK(hipStreamWaitEvent(cs, tls.ev_done[k & 7], 0));
+        ITW_CHECK(hipMemcpyAsync(dst, staged, len, kind, cs));
+        ITW_CHECK(hipStreamSynchronize(cs));
+    }
+};
+
+// The driver: `depth` windows AHEAD of the one being retired are issued.  With two, when window k-1's kernels end, window k is running on the
+// other stream and window k+1 -- same stream as k-1, behind it in stream order -- already has its texels on the device.  (With one window of
+// lookahead the upload of k+1 only started after k-1 had been retired, and for its 0.16 ms the chip ran window k alone.  4096^2, 64 slices, ms
+// per call with a lookahead of 1 / 2 / 3: `basic` 3.81 / 3.58 / 3.59, `alpha_basic` 3.20 / 2.86 / 2.94, `slow` 6.50 / 5.96 / 5.96, BC6H `slow`
+// 4.35 / 4.29 / 4.27, BC1 1.48 / 1.50 / 1.49.)  Per window: stopped()? -> issue the one `depth` ahead -> retire(k) -> report(k).  False when
+// `stopped` or `report` ended the job: the windows behind that one are in flight, ~WindowPipeline waits for them, their bytes are not copied back.
+// Where the two callers differ, on purpose:
+//   lookahead     the slice loop's comes from ITW_SLICE_LOOKAHEAD (1 .. 4, default 2); a chain's is 2
+//   one window    one slice window, and a chain's lone group, run the ordinary call shape (compress() / launch() pick it by size), not a pipeline
+//   the verdict   only the slice loop's first window may leave the pilot's estimate (`leave_verdict`)
+//   stopping      only a share of the slice loop (one pipeline per GPU, dispatch.hip) is stopped from outside
+template <class Stopped, class Issue, class Retire, class Report>
+bool run_windows(int n, int depth, Stopped&& stopped, Issue&& issue, Retire&& retire, Report&& report)
+{
+    for (int k = 0; k < depth && k < n; k++) issue(k);
+    for (int k = 0; k < n; k++) {
+        if (stopped()) return false;
+        if (k + depth < n) issue(k + depth);
+        retire(k);
+        if (!report(k)) return false;
+    }
+    return true;
+}
+
 // returns true when every slice was encoded, false when `progress` stopped the job
 // `fixed_window` > 0 fixes W (compress() passes 1: its "slices" are the windows).
 // `share`: this thread runs only the windows share->part, + share->parts, ... (one pipeline per GPU of the pool, dispatch.hip) and reports them
@@ -626,24 +687,20 @@ bool compress_sliced(const Job& j, const rgba_surface* src, uint8_t* dst, int sl
 {
     if (!src) itw::fail_msg("null surface");
     const int w = src->width, h = src->height;
-    const bool keep_partial = (j.fmt == Fmt::BC4 || j.fmt == Fmt::BC5);
-    const int bx = keep_partial ? (w > 0 ? (w + 3) / 4 : 0) : w / 4, by = keep_partial ? (h > 0 ? (h + 3) / 4 : 0) : h / 4;
+    const itw::SurfaceGeometry geo = itw::surface_geometry(j.kind, w, h);
+    const bool keep_partial = itw::keeps_partial_blocks(j.kind), bc7 = j.kind == itw::BCN_BC7;
     if (slices < 1) slices = 1;
     auto poll = [&](int first, int last) {               // progress(i) for i in [first, last], i < slices; false = stop
         for (int i = first; i <= last && i < slices; i++)
             if (i > 0 && progress && !progress(i, slices, user)) return false;
         return true;
     };
-    if (bx <= 0 || by <= 0) return share ? true : poll(1, slices - 1);   // nothing to encode: the reference's loop still polls
+    if (geo.empty()) return share ? true : poll(1, slices - 1);   // nothing to encode: the reference's loop still polls
     if (!src->ptr || !dst) itw::fail_msg("null texel or destination pointer");
-    const int bpb = block_bytes(j);
-    const int texel_bytes = (j.fmt == Fmt::BC6H) ? 8 : 4;
-    const size_t row_bytes = keep_partial ? (size_t)w * 4 : (size_t)bx * 4 * texel_bytes;
-    const size_t rows = keep_partial ? (size_t)h : (size_t)by * 4;
-    const size_t out_bytes = (size_t)bx * by * bpb;
+    const size_t block_row = (size_t)geo.bx * geo.bpb, pitch = geo.pitch;
     const bool src_dev = is_device_pointer(src->ptr), dst_dev = is_device_pointer(dst);
 
-    const int W = fixed_window > 0 ? (fixed_window < slices ? fixed_window : slices) : slice_window(j.fmt, (int64_t)bx * by / slices, slices, heavy_job(j));
+    const int W = fixed_window > 0 ? (fixed_window < slices ? fixed_window : slices) : slice_window(j.kind, geo.blocks() / slices, slices, heavy_job(j));
     const int nwin = (slices + W - 1) / W;
     const int part = share ? share->part : 0, parts = share ? (share->parts < 1 ? 1 : share->parts) : 1;
     const int nlocal = part < nwin ? (nwin - part + parts - 1) / parts : 0;       // this thread's windows: part, part + parts, ...
@@ -655,48 +712,25 @@ bool compress_sliced(const Job& j, const rgba_surface* src, uint8_t* dst, int sl
         return poll(1, slices - 1);
     }
 
-    ensure_device_ctx();
-    ensure_bc7_aux();
-    hipStream_t k0 = tls.own_stream, k1 = tls.aux.stream, cs = tls.copy_stream;
-    // whatever produced a device surface (or still reads the destination) on the caller's stream comes first
-    if ((src_dev || dst_dev) && tls.user_stream != k0) ITW_CHECK(hipStreamSynchronize(tls.user_stream));
-    const size_t pitch = (row_bytes + 15) & ~(size_t)15;
-    uint8_t* in = src_dev ? nullptr : (uint8_t*)grow(tls.d_in, tls.in_cap, pitch * rows);
+    // BC7: one slice of the per-thread workspace per kernel stream, sized for the tallest window (deep shape: `single` in launch())
+    int64_t tallest = 0;
+    for (int k = 0; bc7 && k < nwin; k++) {
+        const int s1 = (k + 1) * W < slices ? (k + 1) * W : slices;
+        tallest = std::max(tallest, slice_rows(s1 - 1, slices, h, false).y1 - slice_rows(k * W, slices, h, false).y0);
+    }
+    WindowPipeline pipe(src_dev || dst_dev, bc7 ? itw::bc7_workspace_bytes(w, (int)tallest, 1, j.s7) : 0);
+    uint8_t* in = src_dev ? nullptr : (uint8_t*)grow(tls.d_in, tls.in_cap, pitch * geo.rows);
     const uint8_t* d_src = src_dev ? src->ptr : in;
     const int64_t d_stride = src_dev ? (int64_t)src->stride : (int64_t)pitch;
     // A device `target` is written by the kernels themselves -- unless `progress` can stop the job: the windows in flight at that moment must
     // not reach `target` (itw_dispatch.h), so they are encoded into the staging buffer and copied over as they retire, like a host target's.
     const bool direct = dst_dev && !(progress && !share);
-    uint8_t* d_dst = direct ? dst : (uint8_t*)grow(tls.d_out, tls.out_cap, out_bytes);
-
-    // BC7: one slice of the per-thread workspace per kernel stream, sized for the tallest window (deep shape: `single` in launch())
-    size_t ws_off[2] = {0, 0};
-    if (j.fmt == Fmt::BC7) {
-        int64_t tallest = 0;
-        for (int k = 0; k < nwin; k++) {
-            const int s1 = (k + 1) * W < slices ? (k + 1) * W : slices;
-            const int64_t r = slice_rows(s1 - 1, slices, h, false).y1 - slice_rows(k * W, slices, h, false).y0;
-            if (r > tallest) tallest = r;
-        }
-        const size_t b = (itw::bc7_workspace_bytes(w, (int)tallest, 1, j.s7) + 255) & ~(size_t)255;
-        ws_off[1] = b;
-        reserve_workspace(2 * b, k0);
-    }
-    ITW_CHECK(hipEventRecord(tls.aux.fork, k0));          // the second stream starts behind whatever ordered the workspace on the first
-    ITW_CHECK(hipStreamWaitEvent(k1, tls.aux.fork, 0));
-
-    // However this ends, nothing of this call is left in flight on the thread's streams and buffers (a failure is a C++ exception here)
-    struct Drain {
-        hipStream_t a, b, c; bool bc7;
-        ~Drain() {
-            (void)hipStreamSynchronize(a); (void)hipStreamSynchronize(b); (void)hipStreamSynchronize(c);
-            if (bc7 && tls.ws_event) (void)hipEventRecord(tls.ws_event, a);
-            (void)hipGetLastError();
-        }
-    } drain{k0, k1, cs, j.fmt == Fmt::BC7};
+    uint8_t* d_dst = direct ? dst : (uint8_t*)grow(tls.d_out, tls.out_cap, geo.out_bytes);
+    pipe.fork();
 
     struct Window { int s0, s1; int64_t y0, y1; int row0, nb; };
-    auto window = [&](int k) {
+    auto window = [&](int i) {                            // this thread's i-th window: part + i * parts of the call's
+        const int k = part + i * parts;
         Window v;
         v.s0 = k * W; v.s1 = (k + 1) * W < slices ? (k + 1) * W : slices;
         v.y0 = slice_rows(v.s0, slices, h, keep_partial).y0;
@@ -705,47 +739,34 @@ bool compress_sliced(const Job& j, const rgba_surface* src, uint8_t* dst, int sl
         v.nb = (int)((v.y1 - v.y0 + 3) / 4);
         return v;
     };
-    // (issue / retire take the LOCAL index i of this thread's window part + i * parts: streams, workspace slices and events alternate by it)
     auto issue = [&](int i) {
-        const int k = i;
-        const Window v = window(part + i * parts);
+        const Window v = window(i);
         if (v.y1 <= v.y0) return;
-        hipStream_t ks = (k & 1) ? k1 : k0;
         const size_t nrows = (size_t)(v.y1 - v.y0);
         if (!src_dev) {
-            upload_rows(in + (size_t)v.y0 * pitch, pitch, src->ptr + v.y0 * (int64_t)src->stride, src->stride, row_bytes, nrows, cs);
-            ITW_CHECK(hipEventRecord(tls.ev_in[k & 7], cs));
-            ITW_CHECK(hipStreamWaitEvent(ks, tls.ev_in[k & 7], 0));
+            upload_rows(in + (size_t)v.y0 * pitch, pitch, src->ptr + v.y0 * (int64_t)src->stride, src->stride, geo.row_bytes, nrows, pipe.cs);
+            pipe.uploaded(i);
         }
-        launch(j, d_src + v.y0 * d_stride, d_stride, w, (int)nrows, d_dst + (size_t)v.row0 * bx * bpb, ks, true, j.fmt == Fmt::BC7 ? ((leave_verdict && i == 0) ? 0 : 1) : -1,
-               ws_off[k & 1]);
-        ITW_CHECK(hipEventRecord(tls.ev_done[k & 7], ks));
+        launch(j, d_src + v.y0 * d_stride, d_stride, w, (int)nrows, d_dst + (size_t)v.row0 * block_row, pipe.stream(i), true,
+               bc7 ? ((leave_verdict && i == 0) ? 0 : 1) : -1, pipe.workspace(i));
+        pipe.encoded(i);
     };
     auto retire = [&](int i) {                            // the window's bytes into `dst`; returns when they are there
-        const int k = i;
-        const Window v = window(part + i * parts);
+        const Window v = window(i);
         if (v.y1 <= v.y0) return;
-        if (direct) { ITW_CHECK(hipEventSynchronize(tls.ev_done[k & 7])); return; }
-        const size_t off = (size_t)v.row0 * bx * bpb, len = (size_t)v.nb * bx * bpb;
-        ITW_CHECK(hipStreamWaitEvent(cs, tls.ev_done[k & 7], 0));
-        ITW_CHECK(hipMemcpyAsync(dst + off, d_dst + off, len, dst_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, cs));
-        ITW_CHECK(hipStreamSynchronize(cs));
+        const size_t off = (size_t)v.row0 * block_row;
+        if (direct) pipe.wait_encoded(i);
+        else pipe.fetch(i, dst + off, d_dst + off, (size_t)v.nb * block_row, dst_dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost);
     };
-    // Two windows AHEAD of the one being retired are issued: when window k-1's kernels end, window k is running on the other stream and window
-    // k+1 -- same stream as k-1, behind it in stream order -- already has its texels on the device.  (With one window of lookahead the upload of
-    // k+1 only started after k-1 had been retired, and for its 0.16 ms the chip ran window k alone.  4096^2, 64 slices, ms per call with a lookahead of
-    // 1 / 2 / 3: `basic` 3.81 / 3.58 / 3.59, `alpha_basic` 3.20 / 2.86 / 2.94, `slow` 6.50 / 5.96 / 5.96, BC6H `slow` 4.35 / 4.29 / 4.27, BC1 1.48 / 1.50 / 1.49.)
+    auto report = [&](int i) {
+        const Window v = window(i);
+        if (!share) return poll(v.s0 + 1, v.s1);
+        if (share->retired) share->retired(v.s0, v.s1, share->ctx);
+        return true;
+    };
     static const int depth = [] { const char* e = std::getenv("ITW_SLICE_LOOKAHEAD"); const int v = e ? std::atoi(e) : 2; return v < 1 ? 1 : (v > 4 ? 4 : v); }();
     auto stopped = [&] { return share && share->stop && share->stop->load(std::memory_order_acquire); };
-    for (int i = 0; i < depth && i < nlocal; i++) issue(i);
-    for (int i = 0; i < nlocal; i++) {
-        if (stopped()) return false;
-        if (i + depth < nlocal) issue(i + depth);
-        retire(i);
-        const Window v = window(part + i * parts);
-        if (share) { if (share->retired) share->retired(v.s0, v.s1, share->ctx); }
-        else if (!poll(v.s0 + 1, v.s1)) return false;    // the windows behind it are in flight: ~Drain waits for them, their bytes are not copied back
-    }
+    if (!run_windows(nlocal, depth, stopped, issue, retire, report)) return false;
     if (leave_verdict && tls.verdict.valid) {            // the first window's estimate, for the next call (its kernel is long done: every window has been retired)
         ITW_CHECK(hipEventSynchronize(tls.verdict.event));
         const int32_t listed = tls.verdict.host_counts[0], sampled = tls.verdict.host_counts[1];
@@ -758,53 +779,41 @@ bool compress_sliced(const Job& j, const rgba_surface* src, uint8_t* dst, int sl
 Job job_of(int dxgi_format, const void* settings)
 {
     Job j;
-    switch (dxgi_format) {
-    case ITW_DXGI_FORMAT_BC1_UNORM: case ITW_DXGI_FORMAT_BC1_UNORM_SRGB: j.fmt = Fmt::BC1; break;
-    case ITW_DXGI_FORMAT_BC3_UNORM: case ITW_DXGI_FORMAT_BC3_UNORM_SRGB: j.fmt = Fmt::BC3; break;
-    case ITW_DXGI_FORMAT_BC4_UNORM: j.fmt = Fmt::BC4; break;
-    case ITW_DXGI_FORMAT_BC5_UNORM: j.fmt = Fmt::BC5; break;
-    case ITW_DXGI_FORMAT_BC4_SNORM: j.fmt = Fmt::BC4; j.snorm = true; break;
-    case ITW_DXGI_FORMAT_BC5_SNORM: j.fmt = Fmt::BC5; j.snorm = true; break;
-    case ITW_DXGI_FORMAT_BC6H_UF16: case ITW_DXGI_FORMAT_BC6H_SF16: j.fmt = Fmt::BC6H; j.s6 = static_cast<const bc6h_enc_settings*>(settings); break;
-    case ITW_DXGI_FORMAT_BC7_UNORM: case ITW_DXGI_FORMAT_BC7_UNORM_SRGB: j.fmt = Fmt::BC7; j.s7 = static_cast<const bc7_enc_settings*>(settings); break;
-    case ITW_FORMAT_ETC1_RGB8: {
+    j.kind = itw::format_kind(dxgi_format);
+    switch (j.kind) {
+    case itw::BCN_NONE: itw::fail_msg("DXGI format %d is not one this library encodes", dxgi_format);
+    case itw::BCN_BC7:  j.s7 = static_cast<const bc7_enc_settings*>(settings); break;
+    case itw::BCN_BC6H: j.s6 = static_cast<const bc6h_enc_settings*>(settings); break;
+    case itw::BCN_ETC1: {
         const etc_enc_settings* se = static_cast<const etc_enc_settings*>(settings);
         if (!se) itw::fail_msg("null settings for an ETC1 job");
         if (se->fastSkipTreshold < 1)
             itw::fail_msg("ETC1: fastSkipTreshold %d (1 .. 165; the reference emits uninitialised storage below 1)", se->fastSkipTreshold);
-        j.fmt = Fmt::ETC1; j.etc_threshold = se->fastSkipTreshold;           // (above 165: launch_etc1 takes 165)
+        j.etc_threshold = se->fastSkipTreshold;                               // (above 165: launch_etc1 takes 165)
         break;
     }
-    default: itw::fail_msg("DXGI format %d is not one this library encodes", dxgi_format);
+    default: break;                                                           // BC1 / BC3 / BC4 / BC5 and the SNORM pair take no settings
     }
-    if ((j.fmt == Fmt::BC7 || j.fmt == Fmt::BC6H) && !settings) itw::fail_msg("null settings for a BC7 / BC6H job");
+    if ((j.kind == itw::BCN_BC7 || j.kind == itw::BCN_BC6H) && !settings) itw::fail_msg("null settings for a BC7 / BC6H job");
     return j;
 }
 
+// the plugin's slice count; more than 2^24 slices is a bad call here (itwSliceWindowFor, which only reports, clamps instead)
 int slices_of(const rgba_surface* s, int64_t slice_pixels)
 {
-    if (slice_pixels <= 0) slice_pixels = 0x40000;                               // IntelPlugin.cpp:851
-    int64_t slices = ((int64_t)s->width * s->height) / slice_pixels;
-    if (slices < 1) slices = 1;
-    if (slices > (1 << 24)) itw::fail_msg("%lld slices", (long long)slices);
+    const int64_t slices = itw::slice_count(s->width, s->height, slice_pixels);
+    if (slices > itw::kMaxSlices) itw::fail_msg("%lld slices", (long long)slices);
     return (int)slices;
 }
 
 // ---- a whole mip chain / cube map in one call (include/itw_dispatch.h: itwCompressImageChainEx) -----------------------------------
 // IntelPlugin.cpp:229-255 pads and encodes every image of a ScratchImage -- each mip level of each face -- with its own call: upload, a
 // latency-bound launch chain over a few thousand blocks, download, synchronise (66 of them for a 1024^2 cube map with mips).  Here the
-// images are cut into GROUPS of consecutive images of up to a window's worth of blocks (slice_window's target), each group is gathered
-// into one packed surface (chain.hip) and encoded as one surface, and the groups run as the slice pipeline's windows do: group k's
-// kernels on kernel stream k % 2, its upload and the previous group's download on the copy stream.  An image of a window or more whose
-// size is a multiple of 4 needs no gather: it is encoded in place through the whole-surface path (compress() / launch()).
+// images are cut into GROUPS of consecutive images of up to a window's worth of blocks (window_target_blocks), each group is gathered
+// into one packed surface (chain.hip) and encoded as one surface, and the groups are the windows of a WindowPipeline, as the slice loop's
+// are.  An image of a window or more whose size is a multiple of 4 needs no gather: it is encoded in place through the whole-surface path
+// (compress() / launch()).
 constexpr int kChainPackedBlocks = 1024;              // P: blocks per packed row (the tail of the last row is encoded into scratch and dropped)
-
-int64_t chain_image_blocks(const rgba_surface& s) { return (int64_t)((s.width + 3) / 4) * ((s.height + 3) / 4); }
-
-int64_t chain_budget(const Job& j)                    // slice_window's target: ~131 072 blocks (BC7, BC6H, ETC1), 262 144 for BC1/3/4/5 and the heavy BC7 settings
-{
-    return ((j.fmt == Fmt::BC7 && !heavy_job(j)) || j.fmt == Fmt::BC6H || j.fmt == Fmt::ETC1) ? 131072 : 262144;
-}
 
 // everything a bad call can be told by before any device is touched (the pointer kinds come after this)
 Job chain_job(const rgba_surface* images, int count, const uint8_t* target, int dxgi_format, const void* settings)
@@ -812,7 +821,7 @@ Job chain_job(const rgba_surface* images, int count, const uint8_t* target, int 
     if (count <= 0) itw::fail_msg("itwCompressImageChain: %d images", count);
     if (!images || !target) itw::fail_msg("itwCompressImageChain: null images or target pointer");
     const Job j = job_of(dxgi_format, settings);
-    const int px = j.fmt == Fmt::BC6H ? 8 : 4;
+    const int px = itw::texel_bytes(j.kind);
     for (int i = 0; i < count; i++) {
         const rgba_surface& s = images[i];
         if (!s.ptr) itw::fail_msg("itwCompressImageChain: image %d has a null texel pointer", i);
@@ -829,9 +838,8 @@ template <class Poll>
 bool chain_groups(const Job& j, const rgba_surface* im, uint8_t* target, const std::vector<ChainUnit>& units, size_t u0, size_t u1,
                   bool src_dev, bool dst_dev, Poll&& poll)
 {
-    const int px = j.fmt == Fmt::BC6H ? 8 : 4;
-    const int bpb = block_bytes(j);
-    const bool fill45 = j.fmt == Fmt::BC4 || j.fmt == Fmt::BC5;
+    const int px = itw::texel_bytes(j.kind), bpb = itw::block_bytes(j.kind);
+    const bool fill45 = itw::keeps_partial_blocks(j.kind);
     const int ngroups = (int)(u1 - u0);
     auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
 
@@ -863,26 +871,17 @@ bool chain_groups(const Job& j, const rgba_surface* im, uint8_t* target, const s
     const size_t desc_off = in_bytes;
     const int nimg = units[u1 - 1].i1 - units[u0].i0;
     in_bytes += (size_t)nimg * sizeof(itw::ChainImage);
+    std::vector<itw::ChainImage> desc((size_t)nimg);     // (declared ahead of the pipeline: it is still there while the pipeline drains)
 
-    ensure_device_ctx();
-    ensure_bc7_aux();
-    hipStream_t k0 = tls.own_stream, k1 = tls.aux.stream, cs = tls.copy_stream;
-    // whatever produced device images (or still reads the destination) on the caller's stream comes first
-    if ((src_dev || dst_dev) && tls.user_stream != k0) ITW_CHECK(hipStreamSynchronize(tls.user_stream));
+    // one lone group runs the ordinary call (launch shape by size, the second stream for its own parallel parts); several alternate
+    // between the two kernel streams, each BC7 group in its own slice of the workspace (deep shape)
+    const bool lone = ngroups == 1;
+    const bool bc7_slices = j.kind == itw::BCN_BC7 && !lone;
+    WindowPipeline pipe(src_dev || dst_dev, bc7_slices ? itw::bc7_workspace_bytes(widest * 4, tallest * 4, 1, j.s7) : 0);
     uint8_t* d_in = (uint8_t*)grow(tls.d_in, tls.in_cap, in_bytes);
     uint8_t* d_out = (uint8_t*)grow(tls.d_out, tls.out_cap, out_bytes);
 
-    // one lone group runs the ordinary call (launch shape by size, the second stream for its own parallel parts); several alternate
-    // between the two kernel streams, each BC7 group in its own slice of the workspace (deep shape), like the slice pipeline's windows
-    const bool lone = ngroups == 1;
-    size_t ws_off[2] = {0, 0};
-    if (j.fmt == Fmt::BC7 && !lone) {
-        const size_t b = (itw::bc7_workspace_bytes(widest * 4, tallest * 4, 1, j.s7) + 255) & ~(size_t)255;
-        ws_off[1] = b;
-        reserve_workspace(2 * b, k0);
-    }
     // the descriptor table, one copy for every group, ahead of both kernel streams
-    std::vector<itw::ChainImage> desc((size_t)nimg);
     for (int g = 0; g < ngroups; g++) {
         const Group& G = gs[(size_t)g];
         int64_t first = 0;
@@ -892,60 +891,38 @@ bool chain_groups(const Job& j, const rgba_surface* im, uint8_t* target, const s
             d.stride = src_dev ? (int64_t)im[i].stride : (int64_t)(((size_t)im[i].width * px + 15) & ~(size_t)15);
             d.width = im[i].width; d.height = im[i].height;
             d.first_block = first;
-            first += chain_image_blocks(im[i]);
+            first += itw::image_blocks(im[i]);
         }
     }
-    ITW_CHECK(hipMemcpyAsync(d_in + desc_off, desc.data(), desc.size() * sizeof(itw::ChainImage), hipMemcpyHostToDevice, k0));
-    ITW_CHECK(hipEventRecord(tls.aux.fork, k0));          // the second stream starts behind the table and whatever ordered the workspace
-    ITW_CHECK(hipStreamWaitEvent(k1, tls.aux.fork, 0));
-
-    // However this ends, nothing of this call is left in flight on the thread's streams and buffers (a failure is a C++ exception here)
-    struct Drain {
-        hipStream_t a, b, c; bool bc7;
-        ~Drain() {
-            (void)hipStreamSynchronize(a); (void)hipStreamSynchronize(b); (void)hipStreamSynchronize(c);
-            if (bc7 && tls.ws_event) (void)hipEventRecord(tls.ws_event, a);
-            (void)hipGetLastError();
-        }
-    } drain{k0, k1, cs, j.fmt == Fmt::BC7};
+    ITW_CHECK(hipMemcpyAsync(d_in + desc_off, desc.data(), desc.size() * sizeof(itw::ChainImage), hipMemcpyHostToDevice, pipe.k0));
+    pipe.fork();
 
     const itw::ChainImage* d_desc = reinterpret_cast<const itw::ChainImage*>(d_in + desc_off);
     auto issue = [&](int g) {
         const Group& G = gs[(size_t)g];
-        hipStream_t ks = (g & 1) ? k1 : k0;
+        hipStream_t ks = pipe.stream(g);
         if (!src_dev) {
             for (int i = G.i0; i < G.i1; i++) {
                 const size_t row_bytes = (size_t)im[i].width * px;
                 upload_rows(d_in + stage_off[(size_t)(i - units[u0].i0)], (row_bytes + 15) & ~(size_t)15, im[i].ptr, im[i].stride, row_bytes,
-                            (size_t)im[i].height, cs);
+                            (size_t)im[i].height, pipe.cs);
             }
-            ITW_CHECK(hipEventRecord(tls.ev_in[g & 7], cs));
-            ITW_CHECK(hipStreamWaitEvent(ks, tls.ev_in[g & 7], 0));
+            pipe.uploaded(g);
         }
         const int64_t pitch = (int64_t)G.pbx * 4 * px;
         uint8_t* packed = d_in + G.packed_off;
         itw::launch_chain_gather(d_desc + (G.i0 - units[u0].i0), G.i1 - G.i0, G.nb, G.pbx, G.pby, px, fill45, packed, pitch, ks);
         if (lone) launch(j, packed, pitch, G.pbx * 4, G.pby * 4, d_out + G.out_off, ks, !src_dev && !dst_dev);
-        else      launch(j, packed, pitch, G.pbx * 4, G.pby * 4, d_out + G.out_off, ks, true, j.fmt == Fmt::BC7 ? 1 : -1, ws_off[g & 1]);
+        else      launch(j, packed, pitch, G.pbx * 4, G.pby * 4, d_out + G.out_off, ks, true, bc7_slices ? 1 : -1, pipe.workspace(g));
         if (dst_dev) ITW_CHECK(hipMemcpyAsync(target + G.b0 * bpb, d_out + G.out_off, (size_t)G.nb * bpb, hipMemcpyDeviceToDevice, ks));
-        ITW_CHECK(hipEventRecord(tls.ev_done[g & 7], ks));
+        pipe.encoded(g);
     };
     auto retire = [&](int g) {                               // the group's bytes into `target`; returns when they are there
         const Group& G = gs[(size_t)g];
-        if (dst_dev) { ITW_CHECK(hipEventSynchronize(tls.ev_done[g & 7])); return; }
-        ITW_CHECK(hipStreamWaitEvent(cs, tls.ev_done[g & 7], 0));
-        ITW_CHECK(hipMemcpyAsync(target + G.b0 * bpb, d_out + G.out_off, (size_t)G.nb * bpb, hipMemcpyDeviceToHost, cs));
-        ITW_CHECK(hipStreamSynchronize(cs));
+        if (dst_dev) pipe.wait_encoded(g);
+        else pipe.fetch(g, target + G.b0 * bpb, d_out + G.out_off, (size_t)G.nb * bpb, hipMemcpyDeviceToHost);
     };
-    // two groups ahead of the one being retired, as the slice pipeline's windows (compress_sliced)
-    const int depth = 2;
-    for (int g = 0; g < depth && g < ngroups; g++) issue(g);
-    for (int g = 0; g < ngroups; g++) {
-        if (g + depth < ngroups) issue(g + depth);
-        retire(g);
-        if (!poll(gs[(size_t)g].i0, gs[(size_t)g].i1)) return false;   // the groups behind it are in flight: ~Drain waits for them
-    }
-    return true;
+    return run_windows(ngroups, 2, [] { return false; }, issue, retire, [&](int g) { return poll(gs[(size_t)g].i0, gs[(size_t)g].i1); });
 }
 
 // `images` / `count` / `target` checked by chain_job.  Returns true when every image was encoded, false when `progress` stopped the job.
@@ -969,15 +946,15 @@ bool compress_chain(const Job& j, const rgba_surface* im, int count, uint8_t* ta
         }
     }
     const bool dst_dev = is_device_pointer(target);
-    const int bpb = block_bytes(j);
+    const int bpb = itw::block_bytes(j.kind);
 
     // units, in order: in-place images, and groups of consecutive images of up to `budget` blocks
-    const int64_t budget = chain_budget(j);
+    const int64_t budget = window_target_blocks(j.kind, heavy_job(j));
     std::vector<ChainUnit> units;
     int64_t off = 0;
     bool open = false;
     for (int i = 0; i < count; i++) {
-        const int64_t nb = chain_image_blocks(im[i]);
+        const int64_t nb = itw::image_blocks(im[i]);
         if (nb >= budget) {
             const bool aligned = (im[i].width & 3) == 0 && (im[i].height & 3) == 0;
             units.push_back(ChainUnit{i, i + 1, off, nb, aligned});            // in place, or (needs padding) a group of its own
@@ -1093,8 +1070,8 @@ bool coalescing_enabled()
 
 bool same_settings(const Pending& a, const Pending& b)
 {
-    if (a.job.fmt != b.job.fmt || a.job.snorm != b.job.snorm) return false;
-    if (a.job.fmt == Fmt::BC7) {
+    if (a.job.kind != b.job.kind) return false;
+    if (a.job.kind == itw::BCN_BC7) {
         // fields only: padding differs between stack objects, and refineIterations[7] is uninitialised storage in the RGB
         // presets (ispc_texcomp.cpp:20-189 never write it) -- it matters only when mode 7 runs (kernel.ispc:1419)
         const bc7_enc_settings &x = a.s7, &y = b.s7;
@@ -1106,12 +1083,12 @@ bool same_settings(const Pending& a, const Pending& b)
                x.fastSkipTreshold_mode3 == y.fastSkipTreshold_mode3 && x.fastSkipTreshold_mode7 == y.fastSkipTreshold_mode7 &&
                x.mode45_channel0 == y.mode45_channel0 && x.refineIterations_channel == y.refineIterations_channel && x.channels == y.channels;
     }
-    if (a.job.fmt == Fmt::BC6H) {
+    if (a.job.kind == itw::BCN_BC6H) {
         const bc6h_enc_settings &x = a.s6, &y = b.s6;
         return x.slow_mode == y.slow_mode && x.fast_mode == y.fast_mode && x.refineIterations_1p == y.refineIterations_1p &&
                x.refineIterations_2p == y.refineIterations_2p && x.fastSkipTreshold == y.fastSkipTreshold;
     }
-    if (a.job.fmt == Fmt::ETC1) return a.job.etc_threshold == b.job.etc_threshold;
+    if (a.job.kind == itw::BCN_ETC1) return a.job.etc_threshold == b.job.etc_threshold;
     return true;
 }
 
@@ -1120,10 +1097,8 @@ bool continues(const Pending& a, const Pending& b)
 {
     if (!same_settings(a, b) || a.src.width != b.src.width || a.src.stride != b.src.stride) return false;
     if ((a.src.height & 3) || a.src.stride <= 0) return false;
-    const int bpb = block_bytes(a.job);
-    const bool keep = a.job.fmt == Fmt::BC4 || a.job.fmt == Fmt::BC5;
-    const int64_t bx = keep ? (a.src.width + 3) / 4 : a.src.width / 4;
-    return b.src.ptr == a.src.ptr + (int64_t)a.src.height * a.src.stride && b.dst == a.dst + (int64_t)(a.src.height / 4) * bx * bpb;
+    const itw::SurfaceGeometry geo = itw::surface_geometry(a.job.kind, a.src.width, a.src.height);
+    return b.src.ptr == a.src.ptr + (int64_t)a.src.height * a.src.stride && b.dst == a.dst + (int64_t)(a.src.height / 4) * geo.bx * geo.bpb;
 }
 
 void run_batch(std::vector<Pending*>& batch)
@@ -1367,10 +1342,7 @@ int sliced_windows(int dxgi_format, const void* settings, int width, int height,
     const int W = itwSliceWindowFor(dxgi_format, settings, width, height, slice_pixels);
     if (window_slices) *window_slices = W;
     if (W <= 0) return 0;
-    if (slice_pixels <= 0) slice_pixels = 0x40000;
-    int64_t slices = ((int64_t)width * height) / slice_pixels;
-    if (slices < 1) slices = 1;
-    return (int)((slices + W - 1) / W);
+    return (int)((slice_count(width, height, slice_pixels) + W - 1) / W);
 }
 
 } // namespace itw
@@ -1396,24 +1368,24 @@ void GetProfile_bc6h_veryslow(bc6h_enc_settings* s) { apply(Bc6hPreset{true,  fa
 
 void CompressBlocksBC1(const rgba_surface* src, uint8_t* dst)
 {
-    itw::guarded([&] { Job j; j.fmt = Fmt::BC1; compress(j, src, dst); });
+    itw::guarded([&] { Job j; j.kind = itw::BCN_BC1; compress(j, src, dst); });
 }
 void CompressBlocksBC3(const rgba_surface* src, uint8_t* dst)
 {
-    itw::guarded([&] { Job j; j.fmt = Fmt::BC3; compress(j, src, dst); });
+    itw::guarded([&] { Job j; j.kind = itw::BCN_BC3; compress(j, src, dst); });
 }
 void CompressBlocksBC7(const rgba_surface* src, uint8_t* dst, bc7_enc_settings* settings)
 {
     itw::guarded([&] {
         if (!settings) itw::fail_msg("null bc7 settings");
-        Job j; j.fmt = Fmt::BC7; j.s7 = settings; compress(j, src, dst);
+        Job j; j.kind = itw::BCN_BC7; j.s7 = settings; compress(j, src, dst);
     });
 }
 void CompressBlocksBC6H(const rgba_surface* src, uint8_t* dst, bc6h_enc_settings* settings)
 {
     itw::guarded([&] {
         if (!settings) itw::fail_msg("null bc6h settings");
-        Job j; j.fmt = Fmt::BC6H; j.s6 = settings; compress(j, src, dst);
+        Job j; j.kind = itw::BCN_BC6H; j.s6 = settings; compress(j, src, dst);
     });
 }
 
@@ -1428,26 +1400,26 @@ void itwCompressBlocksETC1(const rgba_surface* src, uint8_t* dst, const etc_enc_
             itw::fail_msg("itwCompressBlocksETC1: fastSkipTreshold %d (1 .. 165; the reference emits uninitialised storage below 1)", settings->fastSkipTreshold);
         if (src && (int64_t)(src->width / 4) * (src->height / 4) > (int64_t)INT32_MAX)
             itw::fail_msg("itwCompressBlocksETC1: %d x %d is more blocks than one launch covers", src->width, src->height);
-        Job j; j.fmt = Fmt::ETC1; j.etc_threshold = settings->fastSkipTreshold;
+        Job j; j.kind = itw::BCN_ETC1; j.etc_threshold = settings->fastSkipTreshold;
         compress(j, src, dst, false);
     });
 }
 
 void CompressBlocksBC4(const rgba_surface* src, uint8_t* dst)
 {
-    itw::guarded([&] { Job j; j.fmt = Fmt::BC4; compress(j, src, dst); });
+    itw::guarded([&] { Job j; j.kind = itw::BCN_BC4; compress(j, src, dst); });
 }
 void CompressBlocksBC5(const rgba_surface* src, uint8_t* dst)
 {
-    itw::guarded([&] { Job j; j.fmt = Fmt::BC5; compress(j, src, dst); });
+    itw::guarded([&] { Job j; j.kind = itw::BCN_BC5; compress(j, src, dst); });
 }
 void CompressBlocksBC4S(const rgba_surface* src, uint8_t* dst)
 {
-    itw::guarded([&] { Job j; j.fmt = Fmt::BC4; j.snorm = true; compress(j, src, dst); });
+    itw::guarded([&] { Job j; j.kind = itw::BCN_BC4S; compress(j, src, dst); });
 }
 void CompressBlocksBC5S(const rgba_surface* src, uint8_t* dst)
 {
-    itw::guarded([&] { Job j; j.fmt = Fmt::BC5; j.snorm = true; compress(j, src, dst); });
+    itw::guarded([&] { Job j; j.kind = itw::BCN_BC5S; compress(j, src, dst); });
 }
 
 bool itwCompressImageSlicedEx(const rgba_surface* source, uint8_t* target, int64_t block_row_pitch, int dxgi_format, const void* settings,
@@ -1458,8 +1430,8 @@ bool itwCompressImageSlicedEx(const rgba_surface* source, uint8_t* target, int64
     const bool ok = itw::guarded([&] {
         if (!source) itw::fail_msg("null surface");
         const Job j = job_of(dxgi_format, settings);
-        const bool keep = j.fmt == Fmt::BC4 || j.fmt == Fmt::BC5;
-        const int64_t tight = (int64_t)(keep ? (source->width + 3) / 4 : source->width / 4) * block_bytes(j);
+        const itw::SurfaceGeometry geo = itw::surface_geometry(j.kind, source->width, source->height);
+        const int64_t tight = (int64_t)geo.bx * geo.bpb;
         if (block_row_pitch != tight) itw::fail_msg("itwCompressImageSlicedEx: block_row_pitch %lld != %lld (tight)", (long long)block_row_pitch, (long long)tight);
         done = compress_sliced(j, source, target, slices_of(source, slice_pixels), progress, user);
     });
@@ -1485,18 +1457,11 @@ int itwSliceWindow(int dxgi_format, int width, int height, int64_t slice_pixels)
 int itwSliceWindowFor(int dxgi_format, const void* settings, int width, int height, int64_t slice_pixels)
 {
     if (slice_window_setting() < 0) return 0;
-    if (slice_pixels <= 0) slice_pixels = 0x40000;
-    int64_t slices = ((int64_t)width * height) / slice_pixels;
-    if (slices < 1) slices = 1;
-    if (slices > (1 << 24)) slices = 1 << 24;
-    const bool keep = dxgi_format == ITW_DXGI_FORMAT_BC4_UNORM || dxgi_format == ITW_DXGI_FORMAT_BC5_UNORM ||
-                      dxgi_format == ITW_DXGI_FORMAT_BC4_SNORM || dxgi_format == ITW_DXGI_FORMAT_BC5_SNORM;
-    const int64_t blocks = keep ? (int64_t)((width + 3) / 4) * ((height + 3) / 4) : (int64_t)(width / 4) * (height / 4);
-    const bool heavy = dxgi_format == ITW_DXGI_FORMAT_BC7_UNORM || dxgi_format == ITW_DXGI_FORMAT_BC7_UNORM_SRGB ||
-                       dxgi_format == ITW_DXGI_FORMAT_BC6H_UF16 || dxgi_format == ITW_DXGI_FORMAT_BC6H_SF16 || dxgi_format == ITW_FORMAT_ETC1_RGB8;
-    const bool bc7 = dxgi_format == ITW_DXGI_FORMAT_BC7_UNORM || dxgi_format == ITW_DXGI_FORMAT_BC7_UNORM_SRGB;
-    const bool every_shape = bc7 && settings && itw::bc7_scans_every_shape(*static_cast<const bc7_enc_settings*>(settings));
-    return slice_window(heavy ? Fmt::BC7 : Fmt::BC1, blocks / slices, (int)slices, every_shape);
+    const int kind = itw::format_kind(dxgi_format);         // (a code the library does not encode counts as PCIe-bound, dropping partial blocks)
+    const int64_t slices = std::min(itw::slice_count(width, height, slice_pixels), itw::kMaxSlices);
+    // null settings for BC7: not heavy
+    const bool heavy = kind == itw::BCN_BC7 && settings && itw::bc7_scans_every_shape(*static_cast<const bc7_enc_settings*>(settings));
+    return slice_window(kind, itw::surface_geometry(kind, width, height).blocks() / slices, (int)slices, heavy);
 }
 
 void  itwSetStream(void* s) { tls.user_stream = (hipStream_t)s; }

@@ -1,8 +1,11 @@
-// bcn_format.hpp -- the block formats the decode side reads (decode_chain.hip, measure.hip, refine.hip), described once: the number a format
-// goes by (the FMT template argument of the kernels), what a DXGI code maps to, the sizes that follow from it, and the one place where a
-// runtime kind becomes a compile-time one.  Plain C++, no HIP headers: host-only programs use it too (tools/decode_chain_host_check.cpp).
-// The encode side keeps its own switches (abi.hip job_of, GetBytesPerBlock with the reference's "unknown -> 8", dds.hip).
+// bcn_format.hpp -- the block formats, described once for both sides of the library: the encode host layer (abi.hip, dispatch.hip, multigpu.hip)
+// and the decode side (decode_chain.hip, measure.hip, refine.hip).  The number a format goes by (the FMT template argument of the decode
+// kernels, the `kind` of an encode Job), what a DXGI code maps to, the sizes that follow from it, the geometry of a surface in a format, and
+// the one place where a runtime kind becomes a compile-time one.  Plain C++, no HIP headers: host-only programs use it too
+// (tools/decode_chain_host_check.cpp).  What is NOT a table fact stays with its owner: GetBytesPerBlock's "unknown -> 8" (the reference's),
+// dds.hip's header fields, which settings struct a format takes (abi.hip job_of).
 #pragma once
+#include <cstddef>
 #include <cstdint>
 #include <type_traits>
 #include "../../include/ispc_texcomp.h"
@@ -12,9 +15,10 @@ namespace itw {
 
 enum BcnKind : int { BCN_NONE = 0, BCN_BC1 = 1, BCN_BC3 = 3, BCN_BC4 = 4, BCN_BC5 = 5, BCN_BC6H = 6, BCN_BC7 = 7, BCN_BC4S = 14, BCN_BC5S = 15, BCN_ETC1 = 20 };
 
-// DXGI format code (or ITW_FORMAT_ETC1_RGB8, ETC1's GL enum: it has no DXGI code) -> kind; BCN_NONE for what is not decoded.  BC6H_SF16 (96) reads as unsigned: the signed decode is not built, and the
+// DXGI format code (or ITW_FORMAT_ETC1_RGB8, ETC1's GL enum: it has no DXGI code) -> kind; BCN_NONE for what the library neither encodes nor decodes.
+// BC6H_SF16 (96) reads as unsigned: the encoder is the reference's one BC6H encoder for both codes, the signed decode is not built, and the
 // entry points that must not pretend otherwise (itwDecodeChain, itwDecodeImage) refuse 96 themselves.
-constexpr int decode_kind(int dxgi)
+constexpr BcnKind format_kind(int dxgi)
 {
     switch (dxgi) {
     case 71: case 72: return BCN_BC1;
@@ -40,9 +44,36 @@ constexpr int filled_alpha(int kind)
 }
 // the formats whose blocks have modes (decode_block's return value: 0 .. 15, or -1 for a block the format reserves); the others count as mode 0
 constexpr bool has_modes(int kind) { return kind == BCN_BC7 || kind == BCN_BC6H || kind == BCN_ETC1; }
-inline int64_t image_blocks(const rgba_surface& s) { return (((int64_t)s.width + 3) / 4) * (((int64_t)s.height + 3) / 4); }
+inline int64_t image_blocks(const rgba_surface& s) { return (((int64_t)s.width + 3) / 4) * (((int64_t)s.height + 3) / 4); }   // an image of a chain: padded to whole blocks, whatever the format
 
-// Calls f(std::integral_constant<int, kind>{}) for a kind decode_kind returned: with_kind(kind, [&](auto K) { launch<K.value>(...); })
+// A width x height surface as ONE ENCODE CALL sees it.  The ISPC formats drop partial blocks (kernel.ispc:600-601), the DirectXTex formats
+// keep them (DirectXTexCompress.cpp:108-116): block counts, the texel rows and bytes per row a host surface is staged with, the stream's
+// size, and the staging pitch -- tight, rows 16-byte aligned so that the kernels' vector load path applies.
+struct SurfaceGeometry {
+    int bx = 0, by = 0;                 // blocks across and down; empty(): nothing to encode (the reference's loops do not run either)
+    int bpb = 0, texel_bytes = 0;
+    size_t row_bytes = 0, rows = 0;     // what is read of the surface
+    size_t out_bytes = 0, pitch = 0;
+    bool empty() const { return bx <= 0 || by <= 0; }
+    int64_t blocks() const { return empty() ? 0 : (int64_t)bx * by; }
+};
+inline SurfaceGeometry surface_geometry(int kind, int width, int height)
+{
+    const bool keep = keeps_partial_blocks(kind);
+    SurfaceGeometry g;
+    g.bx = keep ? (width > 0 ? (width + 3) / 4 : 0) : width / 4;
+    g.by = keep ? (height > 0 ? (height + 3) / 4 : 0) : height / 4;
+    g.bpb = block_bytes(kind);
+    g.texel_bytes = texel_bytes(kind);
+    if (g.empty()) return g;
+    g.row_bytes = keep ? (size_t)width * g.texel_bytes : (size_t)g.bx * 4 * g.texel_bytes;
+    g.rows = keep ? (size_t)height : (size_t)g.by * 4;
+    g.out_bytes = (size_t)g.bx * g.by * g.bpb;
+    g.pitch = (g.row_bytes + 15) & ~(size_t)15;
+    return g;
+}
+
+// Calls f(std::integral_constant<int, kind>{}) for a kind format_kind returned: with_kind(kind, [&](auto K) { launch<K.value>(...); })
 template <class F>
 inline void with_kind(int kind, F&& f)
 {

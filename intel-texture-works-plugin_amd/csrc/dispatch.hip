@@ -20,6 +20,7 @@
 #include "../../include/itw_dispatch.h"
 #include "../../include/itw_amd.h"
 #include "../../include/itw_bc45.h"
+#include "bcn_format.hpp"
 #include "host_rt.hpp"
 
 namespace {
@@ -151,23 +152,15 @@ void DestroyThreads(void)
 }
 
 // The DirectXTex formats keep partial blocks (itw_bc45.h); the ISPC formats drop them (kernel.ispc:600-601).
-static bool keeps_partial_blocks(int f)
-{
-    return f == ITW_DXGI_FORMAT_BC4_UNORM || f == ITW_DXGI_FORMAT_BC5_UNORM || f == ITW_DXGI_FORMAT_BC4_SNORM || f == ITW_DXGI_FORMAT_BC5_SNORM;
-}
+static bool keeps_partial_blocks(int f) { return itw::keeps_partial_blocks(itw::format_kind(f)); }
 static int blocks_across(int width, int f) { return keeps_partial_blocks(f) ? (width + 3) / 4 : width / 4; }
 
+// the table's block size (BC5, which never reaches the reference's switch, included); a code that is none of the library's gets the
+// reference's answer: its switch ends in "default: return 8"
 int GetBytesPerBlock(int f)
 {
-    switch (f) {
-    case ITW_DXGI_FORMAT_BC5_UNORM: case ITW_DXGI_FORMAT_BC5_SNORM:   // not in the reference's switch (BC5 never reaches it there)
-    case ITW_DXGI_FORMAT_BC3_UNORM_SRGB: case ITW_DXGI_FORMAT_BC3_UNORM:
-    case ITW_DXGI_FORMAT_BC7_UNORM_SRGB: case ITW_DXGI_FORMAT_BC7_UNORM:
-    case ITW_DXGI_FORMAT_BC6H_UF16: case ITW_DXGI_FORMAT_BC6H_SF16:
-        return 16;
-    default:
-        return 8;
-    }
+    const int kind = itw::format_kind(f);
+    return kind == itw::BCN_NONE ? 8 : itw::block_bytes(kind);
 }
 
 bool CompressImageST(const rgba_surface* input, uint8_t* output, CompressionFunc* cmpFunc, int)
@@ -357,9 +350,7 @@ bool itwCompressImageSliced(const rgba_surface* source, uint8_t* target, int64_t
                             int dxgi_format, bool multithreaded, int64_t slice_pixels, ItwProgressFunc* progress, void* user)
 {
     if (!cmpFunc) return false;
-    if (slice_pixels <= 0) slice_pixels = 0x40000;                                   // IntelPlugin.cpp:851
-    int slices = (int)(((int64_t)source->width * source->height) / slice_pixels);
-    if (slices < 1) slices = 1;
+    const int slices = (int)itw::slice_count(source->width, source->height, slice_pixels);
     // the ABI packs block rows tightly; a wider pitch would need one call per block row
     const int64_t tight = (int64_t)blocks_across(source->width, dxgi_format) * GetBytesPerBlock(dxgi_format);
     if (block_row_pitch != tight) {
@@ -398,18 +389,12 @@ bool itwCompressImageSliced(const rgba_surface* source, uint8_t* target, int64_t
 
 int64_t itwChainBytes(const rgba_surface* images, int count, int dxgi_format)
 {
-    switch (dxgi_format) {
-    case ITW_DXGI_FORMAT_BC1_UNORM: case ITW_DXGI_FORMAT_BC1_UNORM_SRGB: case ITW_DXGI_FORMAT_BC3_UNORM: case ITW_DXGI_FORMAT_BC3_UNORM_SRGB:
-    case ITW_DXGI_FORMAT_BC4_UNORM: case ITW_DXGI_FORMAT_BC5_UNORM: case ITW_DXGI_FORMAT_BC6H_UF16: case ITW_DXGI_FORMAT_BC6H_SF16:
-    case ITW_DXGI_FORMAT_BC4_SNORM: case ITW_DXGI_FORMAT_BC5_SNORM:
-    case ITW_DXGI_FORMAT_BC7_UNORM: case ITW_DXGI_FORMAT_BC7_UNORM_SRGB: case ITW_FORMAT_ETC1_RGB8: break;
-    default: return -1;
-    }
-    if (!images || count <= 0) return -1;
+    const int kind = itw::format_kind(dxgi_format);
+    if (kind == itw::BCN_NONE || !images || count <= 0) return -1;
     int64_t total = 0;
     for (int i = 0; i < count; i++) {
         if (images[i].width < 1 || images[i].height < 1) return -1;
-        total += (int64_t)((images[i].width + 3) / 4) * ((images[i].height + 3) / 4) * GetBytesPerBlock(dxgi_format);
+        total += itw::image_blocks(images[i]) * itw::block_bytes(kind);
     }
     return total;
 }
@@ -433,7 +418,7 @@ bool itwCompressImageChain(const rgba_surface* images, int count, uint8_t* targe
         const bool src_dev = is_device_pointer(images[0].ptr);
         for (int i = 1; i < count; i++)
             if (is_device_pointer(images[i].ptr) != src_dev) itw::fail_msg("itwCompressImageChain: mixed host and device images");
-        const int px = (dxgi_format == ITW_DXGI_FORMAT_BC6H_UF16 || dxgi_format == ITW_DXGI_FORMAT_BC6H_SF16) ? 8 : 4;
+        const int px = itw::texel_bytes(itw::format_kind(dxgi_format));
         const int bpb = GetBytesPerBlock(dxgi_format);
         uint8_t* scratch = nullptr;                         // device images: the largest padded image
         struct Free { uint8_t*& p; ~Free() { if (p) (void)hipFree(p); } } free_scratch{scratch};
@@ -461,7 +446,7 @@ bool itwCompressImageChain(const rgba_surface* images, int count, uint8_t* targe
             }
             if (src_dev && hipStreamSynchronize((hipStream_t)itwGetStream()) != hipSuccess) { (void)hipGetLastError(); itw::fail_msg("itwCompressImageChain: call failed"); }
             if (const char* e = itwLastError()) itw::fail_msg("%s", e);
-            off += (int64_t)((s.width + 3) / 4) * ((s.height + 3) / 4) * bpb;
+            off += itw::image_blocks(s) * bpb;
             if (progress && !progress(i + 1, count, user)) return;
         }
         done = true;

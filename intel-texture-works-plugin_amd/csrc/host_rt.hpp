@@ -8,6 +8,10 @@
 //                     (itwLastError) and the bool-returning dispatch entry points return false.  A plug-in host that
 //                     must not lose the user's document probes itwAvailable() first and checks itwLastError() after.
 // Inside the library a failure is a C++ exception (itw::Failure) that every extern "C" entry point catches.
+//
+// Besides the error model: the slice count of the plugin's save loop (slice_count: one rule for abi.hip and dispatch.hip), a worker's share
+// of a slice pipeline (SlicedPart), and what refine.hip / decode_chain.hip need of the calling thread's context.  Format facts are not here:
+// bcn_format.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <atomic>
@@ -35,6 +39,15 @@ inline bool guarded(F&& body) noexcept
     catch (const Failure& f) { report_failure(f); }
     catch (...) { Failure f; std::snprintf(f.msg, sizeof f.msg, "unexpected C++ exception inside libispc_texcomp"); report_failure(f); }
     return false;
+}
+
+// Slices the plugin's save loop cuts a width x height surface into (IntelPlugin.cpp:851-865): pixels / slice_pixels, by default 0x40000
+// pixels per slice, at least one.  Above kMaxSlices the encode entry points fail and itwSliceWindowFor clamps.
+constexpr int64_t kMaxSlices = 1 << 24;
+inline int64_t slice_count(int64_t width, int64_t height, int64_t slice_pixels)
+{
+    const int64_t slices = width * height / (slice_pixels > 0 ? slice_pixels : 0x40000);
+    return slices < 1 ? 1 : slices;
 }
 
 // One worker's share of a pipelined slice loop (abi.hip compress_sliced; dispatch.hip deals the windows of itwCompressImageSliced to the pool's

@@ -42,6 +42,7 @@
 #ifdef ITW_TEST_HOOKS
 #include "../../include/itw_test_hooks.h"
 #endif
+#include "bcn_format.hpp"
 #include "host_rt.hpp"
 
 namespace {
@@ -608,10 +609,9 @@ bool compress_multi(const rgba_surface* input, uint8_t* output, CompressionFunc*
         if (g.wedged) itw::fail_msg("itwCompressImageMultiGPU: a rank thread never returned from an earlier call (watchdog); restart the process");
         Call k;
         k.input = *input; k.output = output; k.fn = cmpFunc; k.bands = bands;
-        k.keep_partial = dxgi_format == ITW_DXGI_FORMAT_BC4_UNORM || dxgi_format == ITW_DXGI_FORMAT_BC5_UNORM ||
-                         dxgi_format == ITW_DXGI_FORMAT_BC4_SNORM || dxgi_format == ITW_DXGI_FORMAT_BC5_SNORM;
+        k.keep_partial = itw::keeps_partial_blocks(itw::format_kind(dxgi_format));
         k.bpb = GetBytesPerBlock(dxgi_format);
-        k.texel_bytes = (dxgi_format == ITW_DXGI_FORMAT_BC6H_UF16 || dxgi_format == ITW_DXGI_FORMAT_BC6H_SF16) ? 8 : 4;
+        k.texel_bytes = itw::texel_bytes(itw::format_kind(dxgi_format));
         const int by = k.keep_partial ? (input->height + 3) / 4 : input->height / 4;
         if (by <= 0 || input->width < (k.keep_partial ? 1 : 4)) { ok = true; return; }
         int n = ranks > 0 ? ranks : itwMultiGpuRanks();

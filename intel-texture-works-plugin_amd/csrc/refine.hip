@@ -846,7 +846,7 @@ int check_refined_call(const char* who, const rgba_surface* source, const uint8_
                        const void* refine_settings, uint32_t channel_mask, const void* stats, size_t stats_bytes, size_t stats_size,
                        const char* stats_type, const uint64_t* block_sse)
 {
-    const int kind = itw::decode_kind(dxgi_format);
+    const int kind = itw::format_kind(dxgi_format);
     if (kind != itw::BCN_BC7 && kind != itw::BCN_BC6H) itw::fail_msg("%s: DXGI format %d has one encoder only (BC7 and BC6H have presets to refine with)", who, dxgi_format);
     if (!source || !source->ptr || !target) itw::fail_msg("%s: null surface, texel or target pointer", who);
     if (!first_settings || !refine_settings) itw::fail_msg("%s: null settings for the %s tier", who, first_settings ? "refine" : "first");
@@ -868,7 +868,7 @@ int check_refined_chain_call(const char* who, const rgba_surface* images, int co
                              const void* refine_settings, uint32_t channel_mask, const void* stats, size_t stats_bytes, size_t stats_size,
                              const char* stats_type, const itw_refine_stats* image_stats, const uint64_t* block_sse)
 {
-    const int kind = itw::decode_kind(dxgi_format);
+    const int kind = itw::format_kind(dxgi_format);
     if (kind != itw::BCN_BC7 && kind != itw::BCN_BC6H) itw::fail_msg("%s: DXGI format %d has one encoder only (BC7 and BC6H have presets to refine with)", who, dxgi_format);
     if (!first_settings || !refine_settings) itw::fail_msg("%s: null settings for the %s tier", who, first_settings ? "refine" : "first");
     itw::chain_check(images, count, target, dxgi_format);       // count, null pointers, sizes, strides
@@ -889,7 +889,7 @@ int check_refined_chain_call(const char* who, const rgba_surface* images, int co
 // itwPsnrToTotalSse over n = texels x selected channels
 uint64_t psnr_to_total_sse(int dxgi_format, double texels, uint32_t channel_mask, double psnr_db)
 {
-    const int kind = itw::decode_kind(dxgi_format);
+    const int kind = itw::format_kind(dxgi_format);
     int channels = 0;
     for (int c = 0; c < 4; c++) channels += (channel_mask >> c) & 1u;
     if (kind == itw::BCN_NONE || kind == itw::BCN_BC6H || kind == itw::BCN_ETC1 || channels == 0 || !(texels >= 1.0) || !std::isfinite(psnr_db)) return UINT64_MAX;

@@ -243,3 +243,53 @@ def test_mixed_host_and_device_images_are_rejected(itw, gpu):
     finally:
         itw.set_error_mode(itw.ON_ERROR_ABORT)
         itw.lib().itwClearError()
+
+
+def _variants(fmt, size, n):
+    """n distinct images of one size, cheaply: one surface rolled along both axes (a group that read another group's texels would show)."""
+    base = _content(fmt, size, size)
+    return [np.ascontiguousarray(np.roll(base, (37 * k, 91 * k), axis=(0, 1))) for k in range(n)]
+
+
+@pytest.mark.parametrize("fmt,prof,size", [("bc1", None, 1450), ("bc7", "basic", 1026)])
+def test_more_groups_than_the_event_ring(itw, gpu, fmt, prof, size):
+    """Ten images, each a gather group of its own: more than half a window's budget each (BC1: 363^2 = 131 769 blocks, two make 263 538 >
+    262 144; BC7 `basic`: 257^2 = 66 049, two make 132 098 > 131 072), below the budget, and no multiple of 4, so none is encoded in place.
+    Ten groups wrap the ring of 8 input / done events and alternate the two kernel streams and workspace slices five times."""
+    import torch
+    images = _variants(fmt, size, 10)
+    want = _per_image(itw, fmt, images, prof)
+    ok, got = itw.compress_chain(fmt, images, prof)
+    assert ok
+    _check(got, want, fmt, "host")
+    dev = [torch.from_numpy(im).to(gpu) for im in images]
+    ok, got = itw.compress_chain(fmt, dev, prof, out=np.zeros(want.size, np.uint8))  # device images, host target
+    assert ok
+    _check(got, want, fmt, "device -> host")
+
+
+def test_one_workspace_across_formats_and_streams(itw, gpu, oracle):
+    """The per-thread workspace is shared by BC7 and BC6H and ordered across streams by a library-owned event: a device-resident BC7 call on
+    stream A, a BC6H `slow` call on stream B, BC7 on A again, one synchronisation at the end, every stream against the oracle.
+    Surface: 4 x 4 texels, one block -- the smallest for which both bc7_workspace_bytes (non-zero from the first block on: 4 B + 32 B per
+    block in the deep shape) and bc6h_workspace_bytes (non-zero for `slow` settings -- slow_mode with fastSkipTreshold >= 2 -- from one
+    block up to the wide shape's limit) are non-zero; below it there is no block and both are zero."""
+    import torch
+    from itw_amd import surfaces
+    ldr = np.ascontiguousarray(surfaces.ldr_smooth(8, 8)[2:6, 1:5])
+    ldr2 = np.ascontiguousarray(surfaces.ldr_smooth(8, 8, seed=5)[:4, 4:8])
+    hdr = np.ascontiguousarray(surfaces.hdr_smooth(8, 8)[1:5, 3:7])
+    d_ldr, d_ldr2, d_hdr = (torch.from_numpy(a).to(gpu) for a in (ldr, ldr2, hdr))
+    a, b = torch.cuda.Stream(gpu), torch.cuda.Stream(gpu)
+    torch.cuda.synchronize()
+    with torch.cuda.stream(a):
+        first = itw.compress("bc7", d_ldr, "slow")
+    with torch.cuda.stream(b):
+        second = itw.compress("bc6h", d_hdr, "slow")
+    with torch.cuda.stream(a):
+        third = itw.compress("bc7", d_ldr2, "basic")
+    torch.cuda.synchronize()
+    itw.lib().itwSetStream(torch.cuda.current_stream(gpu).cuda_stream)
+    _check(first, oracle.encode("bc7", ldr, "slow").reshape(-1), "bc7", "bc7 on stream A")
+    _check(second, oracle.encode("bc6h", hdr, "slow").reshape(-1), "bc6h", "bc6h on stream B")
+    _check(third, oracle.encode("bc7", ldr2, "basic").reshape(-1), "bc7", "bc7 on stream A again")

@@ -22,7 +22,7 @@ int main()
     uint8_t *p = texels.data(), *b = blocks.data();
 
     for (int f : formats) {
-        const int kind = decode_kind(f);
+        const int kind = format_kind(f);
         CHECK(kind != BCN_NONE);
         int seen = 0;
         with_kind(kind, [&](auto K) { seen = K.value; });
@@ -105,17 +105,17 @@ int main()
         CHECK(decode_blocks_check(kind, 4 * 46341, 4 * 46341, 4 * 46341 * (int64_t)px) == -1);
     }
     CHECK(DECODE_IMAGE_MAX_BLOCKS == 0x7fffffff && image_blocks(rgba_surface{nullptr, INT32_MAX, INT32_MAX, 0}) == ((int64_t)1 << 29) * ((int64_t)1 << 29));
-    CHECK(decode_kind(96) == BCN_BC6H && decode_kind(72) == BCN_BC1 && decode_kind(78) == BCN_BC3 && decode_kind(99) == BCN_BC7);
-    CHECK(decode_blocks_check(decode_kind(96), 8, 8, 64) == 4);      // itwDecodeBlocks reads BC6H_SF16 as unsigned; the chain entry points refuse it
+    CHECK(format_kind(96) == BCN_BC6H && format_kind(72) == BCN_BC1 && format_kind(78) == BCN_BC3 && format_kind(99) == BCN_BC7);
+    CHECK(decode_blocks_check(format_kind(96), 8, 8, 64) == 4);      // itwDecodeBlocks reads BC6H_SF16 as unsigned; the chain entry points refuse it
     const int refused[] = {0, 28, 70, 73, 74, 82, 94, 97, 100, -1};
     for (int f : refused) {
         const rgba_surface good{p, 8, 8, 64};
-        CHECK(decode_kind(f) == BCN_NONE);
-        CHECK(decode_chain_check(decode_kind(f), b, &good, 1) == -1);
-        CHECK(decode_chain_check(decode_kind(f), b, &good, 0) == -1);
-        CHECK(decode_blocks_check(decode_kind(f), 8, 8, 64) == -1);
+        CHECK(format_kind(f) == BCN_NONE);
+        CHECK(decode_chain_check(format_kind(f), b, &good, 1) == -1);
+        CHECK(decode_chain_check(format_kind(f), b, &good, 0) == -1);
+        CHECK(decode_blocks_check(format_kind(f), 8, 8, 64) == -1);
         int calls = 0;
-        with_kind(decode_kind(f), [&](auto) { calls++; });
+        with_kind(format_kind(f), [&](auto) { calls++; });
         CHECK(calls == 0);
     }
 
