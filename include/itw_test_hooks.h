@@ -24,6 +24,11 @@ void itwTestF2I  (const float* d_in, int32_t* d_out, int64_t n);
  * against the oracle's error of every shape (it must never exceed one) and against its CPU restatement (oracle/bc7_bound.c). */
 void itwTestBc7TwoSubsetBounds(const rgba_surface* d_src, float* d_out);
 
+/* The bound that lists modes 4/5's (block, rotation) pairs under an RGB profile (csrc/bc7_exact.hpp rotation_bound): for every 4x4 block
+ * of the device-resident RGBA8 surface, the bound of rotations 0..2, d_out[block * 3 + rotation] (device memory, raster block order).
+ * tests/test_gpu_bc7_rot_tasks.py checks it against the exact value in float64: never above it, and not uselessly below. */
+void itwTestBc7RotationBounds(const rgba_surface* d_src, float* d_out);
+
 /* BC4 / BC5 (tests/test_gpu_parity_bc4_bc5.py).  The encoders evaluate FindClosestUNORM (BC4BC5.cpp:314-337) through a table
  * the current device builds once by running that search, as written, for all 65 536 endpoint pairs: per pair the 7 texel
  * codes where the chosen index changes and the 8 indices of the runs in between (csrc/bc4_bc5.hip).  Copies the table --

@@ -1392,6 +1392,14 @@ constexpr int PAIR_CTR_OVERFLOW = 64, PAIR_CTR_REDO = 65, PAIR_CTR_LIST = 66, PA
 struct PairTarget { PairRegion P; int32_t* redo; };
 static_assert(sizeof(PairTarget) <= (PAIR_CTR_WORDS - PAIR_CTR_TARGET) * sizeof(int32_t) && PAIR_CTR_TARGET % 2 == 0 && PAIR_CTR_WORDS % 4 == 0, "PairTarget behind the counters");
 constexpr int PAIR_MAX_PER_BLOCK = 32;
+// ROT TASKS (bc7_rot_tasks' header).  Per band: three rotation lists of `cap` block ids, their lengths (three consecutive words the call's
+// setup clears), and a payload slot per (rotation, list position); per block of the surface one merged word
+//   error << 32 | mode 5 << 31 | rotation << 29 | list position        (~0: no candidate)
+// whose 64-bit minimum is the reference's first strict minimum over modes 4 then 5, rotations in order.  29 bits of position hold the
+// 8.4 M blocks of a band of a 16 384^2 call (and the 16.8 M of a call without bands).
+struct RotRegion { int32_t* lists; int32_t* counts; unsigned long long* words; uint4* payload; int32_t cap; };
+constexpr int ROT_WORD_ROT_SHIFT = 29, ROT_WORD_MODE5_SHIFT = 31;
+constexpr unsigned long long ROT_WORD_POS_MASK = (1ull << ROT_WORD_ROT_SHIFT) - 1ull;
 constexpr unsigned long long PAIR_WORD_HEAVY = ~0ull - 1ull;        // no merged word takes this value: errors stay below 2^23
 
 struct ScanTasks { int n; int kind[3]; };      // WK_SCAN02 / WK_SCAN13 / WK_SCAN7 in launch order
@@ -1570,17 +1578,18 @@ bc7_finish_all(const uint8_t* __restrict__ src, int64_t stride, int32_t blocks_x
                const uint32_t* __restrict__ wins4, const bc7_enc_settings S, int32_t* __restrict__ inc_err,
                const int32_t* __restrict__ in_list, const int32_t* __restrict__ in_count, int32_t* __restrict__ out_list, int32_t* __restrict__ out_count,
                int32_t* __restrict__ out_list7, int32_t* __restrict__ out_count7, const ChunkSel sel,
-               const uint4* __restrict__ in_compact, uint4* __restrict__ out_compact)
+               const uint4* __restrict__ in_compact, uint4* __restrict__ out_compact, const RotRegion R)
 {
     constexpr bool LISTED = PHASE == 2 || PHASE == 4 || PHASE == 5 || PHASE == 7 || PHASE == 8;   // walks a compacted list of an earlier phase
-    constexpr bool DO02 = PHASE == 0 || PHASE == 2 || PHASE == 3 || PHASE == 5;
+    constexpr bool DO02 = PHASE == 0 || PHASE == 2 || PHASE == 3 || PHASE == 5 || PHASE == 9;
+    constexpr bool TAIL3 = PHASE == 3 || PHASE == 10;                // leaves the incumbent, the list and the pairs of the RGB bounded order
     constexpr bool DO13 = PHASE == 0 || PHASE == 2 || PHASE == 4;
     constexpr bool DO7 = PHASE == 0 || PHASE == 1;
     constexpr bool DO456 = PHASE == 0 || PHASE == 1 || PHASE == 3 || PHASE == 6;
     __shared__ unsigned short s_seed16[2048];
     __shared__ uint32_t s_seed32[2048];
     __shared__ uint2 s_pal[(ITW_BC7_LANE_PAL ? LANE_PAL_LEVELS : 8) * TPB];   // refinement: a palette per subset of the lane's winner
-    __shared__ int32_t s_at[PHASE == 3 ? TPB / 64 : 1][64];         // PAIRS: per (wave, shape) the survivors, then where they go in the bucket (its own
+    __shared__ int32_t s_at[TAIL3 ? TPB / 64 : 1][64];             // PAIRS: per (wave, shape) the survivors, then where they go in the bucket (its own
                                                                     // kilobyte: other waves of the workgroup still use s_pal when the first one gets here)
     if (sel.gate && *sel.gate != sel.want) return;                   // the pilot chose the other order (whole grid: no barrier is pending)
     const int32_t nact = LISTED ? *in_count : nblocks;
@@ -1609,7 +1618,7 @@ bc7_finish_all(const uint8_t* __restrict__ src, int64_t stride, int32_t blocks_x
     const bool on13 = S.mode_selection[1];
     int32_t e_alpha = ERR_MAX;
     if (PHASE == 2 || PHASE == 5) e_alpha = inc_err[b];      // every listed block has opaque_err <= e_alpha: its winners exist
-    if (PHASE == 4 || PHASE == 7 || PHASE == 8) ln.best_err = inc_err[b];  // what modes 1/3 (mode 7) have to get strictly below
+    if (PHASE == 4 || PHASE == 7 || PHASE == 8 || PHASE == 10) ln.best_err = inc_err[b];  // what modes 1/3 (mode 7; PHASE 10: modes 4,5,6) have to get strictly below
     Win w;
     if (DO02 && S.mode_selection[0]) {
         unpack_win(w, wins4[(int64_t)wide_win_slot(0) * nblocks + b]);
@@ -1617,6 +1626,34 @@ bc7_finish_all(const uint8_t* __restrict__ src, int64_t stride, int32_t blocks_x
         if (!S.skip_mode2) { ln.tx.fence(); unpack_win(w, wins4[(int64_t)wide_win_slot(2) * nblocks + b]); refine_and_commit<2>(ln, w, S.refineIterations[2], S.channels); }
     }
     const int32_t e02 = ln.best_err;
+    if (PHASE == 9) {
+        // ROT TASKS (bc7_rot_tasks' header): the block as modes 0/2 leave it is stored below; e02 is what modes 4,5,6 have to get strictly
+        // below; the block's merged word starts empty; and the block goes on the list of every rotation whose exact bound (rotation_bound,
+        // bc7_exact.hpp) is still below e02 - 1/2 (errors are integers, modes 4/5 replace the block only on a strict `<`)
+        if (live) { inc_err[b] = e02; R.words[b] = ~0ull; }
+        ln.tx.fence();
+        IStats<3> full;
+        stats_int<3>(full, ln.tx.pl, whole_block());
+        const float lim = (float)e02 - 0.5f;
+        const bool on45 = live && S.mode_selection[2];
+#pragma unroll
+        for (int r = 0; r < 3; r++) {
+            const bool need = on45 && r >= S.mode45_channel0 && !(rotation_bound(r, full) >= lim);
+            append_to_list(R.lists + (int64_t)r * R.cap, R.counts + r, need, b);
+        }
+    }
+    if (PHASE == 10) {
+        // the one candidate bc7_rot_tasks left for the block, if any: admitted with the reference's strict `<`, then mode 6 in its place
+        const unsigned long long v = R.words[b];
+        const int32_t e = (int32_t)(v >> 32);
+        if (v != ~0ull && e < ln.best_err) {
+            const uint4 p = R.payload[(int64_t)((v >> ROT_WORD_ROT_SHIFT) & 3ull) * R.cap + (int64_t)(v & ROT_WORD_POS_MASK)];
+            ln.best_err = e; ln.improved = true;
+            ln.best[0] = p.x; ln.best[1] = p.y; ln.best[2] = p.z; ln.best[3] = p.w;
+        }
+        ln.tx.fence();
+        if (S.mode_selection[3] && !mode6_cannot_win(ln)) mode_6<3>(ln, S);
+    }
     if (DO13 && PHASE != 4) {
         if (on13 && S.fastSkipTreshold_mode1 > 0) { ln.tx.fence(); unpack_win(w, wins4[(int64_t)wide_win_slot(1) * nblocks + b]); refine_and_commit<1>(ln, w, S.refineIterations[1], S.channels); }
         if (on13 && S.fastSkipTreshold_mode3 > 0) { ln.tx.fence(); unpack_win(w, wins4[(int64_t)wide_win_slot(3) * nblocks + b]); refine_and_commit<3>(ln, w, S.refineIterations[3], S.channels); }
@@ -1682,10 +1719,10 @@ bc7_finish_all(const uint8_t* __restrict__ src, int64_t stride, int32_t blocks_x
         append_to_list(out_list, out_count, live && rgb, b);
         append_to_list(out_list7, out_count7, live && !rgb, b);
     }
-    if (PHASE == 3 || PHASE == 5) {
+    if (TAIL3 || PHASE == 5) {
         // incumbent of modes 1/3 (see the header), then the blocks whose modes 1/3 can still get below it
         int32_t inc;
-        if (PHASE == 3) inc = ln.best_err + (ln.best_err < e02 ? 1 : 0);
+        if (TAIL3) inc = ln.best_err + (ln.best_err < e02 ? 1 : 0);
         else            inc = (e02 <= e_alpha) ? e02 : e_alpha + 1;
         if (live) inc_err[b] = inc;
         ln.tx.fence();
@@ -1699,8 +1736,8 @@ bc7_finish_all(const uint8_t* __restrict__ src, int64_t stride, int32_t blocks_x
         // CONTRACT of PHASE 3: `out_count` is word PAIR_CTR_LIST of a band's counter block that bc7_bounded_setup has filled in this call, so the
         // band's PairTarget lies PAIR_CTR_TARGET - PAIR_CTR_LIST words behind it (launch_bc7's `finish` refuses any other pointer)
         const PairTarget* target = nullptr;
-        if (PHASE == 3) target = reinterpret_cast<const PairTarget*>(out_count + (PAIR_CTR_TARGET - PAIR_CTR_LIST));
-        const bool pairs = PHASE == 3 && target->P.words != nullptr; // grid-uniform
+        if (TAIL3) target = reinterpret_cast<const PairTarget*>(out_count + (PAIR_CTR_TARGET - PAIR_CTR_LIST));
+        const bool pairs = TAIL3 && target->P.words != nullptr;      // grid-uniform
         bool need = !live, need7 = !live || !with7;                  // idle lanes never hold the loop up
         unsigned long long mine = 0, any = 0;                        // shapes whose bound is below `lim`: the lane's, the wave's (scalar)
 #pragma unroll 1
@@ -1773,7 +1810,7 @@ bc7_finish_all(const uint8_t* __restrict__ src, int64_t stride, int32_t blocks_x
     }
     bool store = live;
     if (PHASE == 2 || PHASE == 5) store = store && ln.best_err <= e_alpha;   // else the alpha group's block stands (ties go to the earlier, RGB, group)
-    if (PHASE == 4 || PHASE == 7) store = store && ln.improved;
+    if (PHASE == 4 || PHASE == 7 || PHASE == 10) store = store && ln.improved;   // (PHASE 10: PHASE 9 stored the block modes 0/2 left)
     if (PHASE == 8) store = store && ln.improved && !redo;
     if ((PHASE == 4 || PHASE == 8) && store) inc_err[b] = ln.best_err;         // mode 7 (PHASE 7, RGBA profiles) comes after modes 1/3: strictly below them
     if (store) {
@@ -1919,6 +1956,85 @@ bc7_pair_scan(const uint8_t* __restrict__ src, int64_t stride, int32_t blocks_x,
         const uint32_t key = (uint32_t)rank_key<3>(shape, ln.tx, rfull, ln.T);
         if (live && on_a) atomicMin(reinterpret_cast<unsigned long long*>(P.words + 2 * (int64_t)slot),     ((unsigned long long)(uint32_t)ea << 32) | key);
         if (live && on_b) atomicMin(reinterpret_cast<unsigned long long*>(P.words + 2 * (int64_t)slot + 1), ((unsigned long long)(uint32_t)ec << 32) | key);
+    }
+}
+
+// ---- ROT TASKS: modes 4/5 of the RGB bounded order for the (block, rotation) pairs a bound leaves (round 9) ----------------------
+// bc7_finish_all<3> runs the nine mode 4/5 candidates of every block (3 rotations x {mode 4, mode 4 swapped, mode 5}): 15 % of a `slow`
+// call's instructions.  Under an RGB profile every candidate of rotation p has error >= rotation_bound(p) (bc7_exact.hpp), and modes 4/5
+// replace the block only below the error e02 modes 0/2 left: on the bench surface 0.565 of the (block, rotation) pairs survive, on a
+// photograph 0.81 (profiles/r09_bc7_rotation_survival.txt) -- but no whole wave of blocks agrees, so finish<3> cannot skip in place.
+// As for the pairs of modes 1/3, the survivors are listed and full waves run over the lists.  finish<3> becomes three launches per band:
+//   bc7_finish_all<9>   modes 0/2 refined, the block stored, inc_err = e02, the block's merged word emptied, and the block appended to
+//                       the list of each surviving rotation (one list per rotation: the task kernel's waves stay rotation-uniform);
+//   bc7_rot_tasks       lanes = entries of one rotation list, wave tiles walked by the device-side counts.  The rotation's three
+//                       candidates run through modes_45_scan from bound = e02 -- the arithmetic of the inline route -- and the task
+//                       publishes at most ONE candidate, strictly below e02: its mode 5 if that is strictly below its mode 4, else its
+//                       mode 4.  The reference's result after modes 4 and 5 is the first strict minimum over [mode 4: r0 s0, r0 s1, r1 s0,
+//                       ...; then mode 5: r0, r1, r2] (kernel.ispc:1623-1655): a task whose mode 5 does not beat its own mode 4 cannot
+//                       supply the winner with mode 5 (mode 4's minimum over all rotations is lower still), and one whose mode 5 does
+//                       cannot supply it with mode 4.  The emitted block goes to payload slot (rotation, list position), and a 64-bit
+//                       atomicMin of the merged word (RotRegion) settles the rest: lowest error, then mode 4, then the lower rotation;
+//   bc7_finish_all<10>  admits the word's candidate with a strict `<`, runs mode 6 in its place, then finish<3>'s tail unchanged.
+// A rotation the bound excludes cannot get below e02, so it can neither win nor, by a tie, displace a winner: same bytes.
+// ITW_BC7_ROT_TASKS=0 (read at every call): finish<3> as before.
+// Two waves per SIMD: 246 VGPRs, nothing spilled.  At three (168 VGPRs) 38 registers spill and the call is 1.2 % slower (4.29 against 4.24 ms on
+// the bench surface): the call pays for instructions, and the other band's kernels fill the SIMDs anyway.
+#ifndef ROT_TASK_WAVES
+#define ROT_TASK_WAVES 2
+#endif
+template <bool VEC16>
+__global__ void __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(ROT_TASK_WAVES, ROT_TASK_WAVES)))
+bc7_rot_tasks(const uint8_t* __restrict__ src, int64_t stride, int32_t blocks_x, const bc7_enc_settings S, const int32_t* __restrict__ inc_err, const RotRegion R)
+{
+    __shared__ unsigned short s_seed16[2048];
+    __shared__ uint32_t s_seed32[2048];
+    __shared__ uint2 s_pal[8 * TPB];                                // a candidate's vector palette (<= 8 levels), then its scalar levels
+    __shared__ int32_t s_first[4];                                  // first wave tile of each rotation's list
+    if (threadIdx.x == 0) {
+        int32_t t = 0;
+        for (int r = 0; r < 3; r++) { s_first[r] = t; t += (R.counts[r] + 63) >> 6; }
+        s_first[3] = t;
+    }
+    __syncthreads();
+    const int32_t total = s_first[3];
+    const int32_t wpb = TPB / 64;
+    if ((int32_t)blockIdx.x * wpb >= total) return;                 // whole workgroup: no barrier is pending (empty lists: the other order, or nothing survives)
+    Lane ln;
+    ln.T = stage_seed_tables_fast(s_seed16, s_seed32, threadIdx.x, TPB);
+    __syncthreads();
+    ln.keys = nullptr;
+    ln.pal = s_pal + threadIdx.x;
+    ln.best_err = ERR_MAX; ln.improved = false; ln.opaque_err = 0;
+    ln.best[0] = ln.best[1] = ln.best[2] = ln.best[3] = 0u;
+    const int lane = (int)(threadIdx.x & 63u);
+    const int32_t first1 = s_first[1], first2 = s_first[2];
+#pragma unroll 1
+    for (int32_t tile = (int32_t)blockIdx.x * wpb + (int32_t)(threadIdx.x >> 6); tile < total; tile += (int32_t)gridDim.x * wpb) {
+        const int r = __builtin_amdgcn_readfirstlane((tile >= first1 ? 1 : 0) + (tile >= first2 ? 1 : 0));   // wave-uniform
+        const int32_t len = R.counts[r];
+        const int32_t at = (tile - s_first[r]) * 64 + lane;
+        const bool live = at < len;
+        const int32_t pos = live ? at : len - 1;                    // idle lanes redo the list's last block, publish nothing
+        const int32_t b = R.lists[(int64_t)r * R.cap + pos];
+        load_block<VEC16>(ln.tx, src, stride, blocks_x, b);
+        const int32_t inc = inc_err[b];
+        Dual best4, best5;
+        clear(best4); clear(best5);
+        int32_t err4 = inc, err5 = ERR_MAX;
+        modes_45_scan(ln, S, r, r + 1, best4, err4, best5, err5);
+        const bool five = err5 < err4;                              // err4 <= inc: strictly below the incumbent either way
+        if (five || err4 < inc) {
+            uint32_t blk[4] = {0u, 0u, 0u, 0u};
+            if (five) emit_dual<5>(blk, best5); else emit_dual<4>(blk, best4);
+            if (live) {
+                R.payload[(int64_t)r * R.cap + pos] = make_uint4(blk[0], blk[1], blk[2], blk[3]);
+                const unsigned long long word = ((unsigned long long)(uint32_t)(five ? err5 : err4) << 32) | ((five ? 1ull : 0ull) << ROT_WORD_MODE5_SHIFT) |
+                                                ((unsigned long long)r << ROT_WORD_ROT_SHIFT) | (unsigned long long)pos;
+                atomicMin(R.words + b, word);
+            }
+        }
+        ln.tx.fence();
     }
 }
 
@@ -2173,6 +2289,32 @@ void launch_bc7_test_bounds(const uint8_t* src, int64_t stride, int width, int h
     if (vec) hipLaunchKernelGGL((bc7_test_bounds<true>),  grid, dim3(TPB), 0, st, src, stride, bx, (int32_t)n, out);
     else     hipLaunchKernelGGL((bc7_test_bounds<false>), grid, dim3(TPB), 0, st, src, stride, bx, (int32_t)n, out);
 }
+// test hook (itwTestBc7RotationBounds): rotation_bound of the three rotations of every block, out[block * 3 + rotation]
+template <bool VEC16>
+__global__ void __launch_bounds__(TPB) bc7_test_rot_bounds(const uint8_t* __restrict__ src, int64_t stride, int32_t blocks_x, int32_t nblocks, float* __restrict__ out)
+{
+    const int32_t gid = blockIdx.x * TPB + threadIdx.x;
+    const int32_t b = gid < nblocks ? gid : nblocks - 1;
+    Tex tx;
+    load_block<VEC16>(tx, src, stride, blocks_x, b);
+    IStats<3> full;
+    stats_int<3>(full, tx.pl, whole_block());
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+        const float lb = rotation_bound(r, full);
+        if (gid < nblocks) out[(int64_t)b * 3 + r] = lb;
+    }
+}
+void launch_bc7_test_rot_bounds(const uint8_t* src, int64_t stride, int width, int height, float* out, hipStream_t st)
+{
+    const int bx = width / 4;
+    const int64_t n = (int64_t)bx * (height / 4);
+    if (n <= 0) return;
+    const bool vec = ((reinterpret_cast<uintptr_t>(src) | (uintptr_t)stride) & 15) == 0;
+    const dim3 grid((unsigned)((n + TPB - 1) / TPB));
+    if (vec) hipLaunchKernelGGL((bc7_test_rot_bounds<true>),  grid, dim3(TPB), 0, st, src, stride, bx, (int32_t)n, out);
+    else     hipLaunchKernelGGL((bc7_test_rot_bounds<false>), grid, dim3(TPB), 0, st, src, stride, bx, (int32_t)n, out);
+}
 #endif // ITW_TEST_HOOKS
 
 static std::atomic<int> g_bc7_path{-1};
@@ -2245,6 +2387,13 @@ static bool bc7_pairs_on()
     const char* e = std::getenv("ITW_BC7_PAIRS");
     return !(e && e[0] == '0');
 }
+// ITW_BC7_ROT_TASKS=0: modes 4/5 of the RGB bounded order inline in bc7_finish_all<3>, all nine candidates of every block, instead of the (block, rotation)
+// pairs a bound leaves (bc7_rot_tasks' header).  Read at every call; the workspace layout does not depend on it.
+static bool bc7_rot_tasks_on()
+{
+    const char* e = std::getenv("ITW_BC7_ROT_TASKS");
+    return !(e && e[0] == '0');
+}
 static int32_t bc7_pair_cap(int32_t layout_cap)
 {
     const char* e = std::getenv("ITW_BC7_PAIR_CAP");
@@ -2302,17 +2451,20 @@ static size_t wide_workspace_bytes(size_t n)
 // (rows 2, 3 used: list_scan_parts x listed <= cap), the listed blocks' texels [cap] x 64 B in list order
 // pairs (bc7_pair_scan's header): per band the merged words [cap] x 2 x 8 B, the second list [cap], 64 shape buckets of cap / 8 listed slots and (behind the
 // 16 counters) PAIR_CTR_WORDS counters; each kind's two halves are contiguous, so a call without bands uses them as one
-struct ListRegion { size_t list, wins, compact, cap, pair_words, pair_redo, pair_buckets, pair_ctr, pair_cap; };
-struct FusedLayout { size_t inc, list0, list1, list2, counts, words; ListRegion band[2]; };
+// rot tasks (bc7_rot_tasks' header): per band three rotation lists [3][cap] and their payload slots [3][cap] x 16 B, per block of the surface one merged
+// word of 8 B: 68 B per block in all; each kind's two halves are contiguous again
+struct ListRegion { size_t list, wins, compact, cap, pair_words, pair_redo, pair_buckets, pair_ctr, pair_cap, rot_lists, rot_payload; };
+struct FusedLayout { size_t inc, list0, list1, list2, counts, words, rot_words; ListRegion band[2]; };
 // Which regions a call's settings can touch (a `basic` call was sized like a `slow` one, 124 B per block instead of 36):
 //   lists    the three block lists of the RGBA profiles' alpha-first order (and list13 of an RGB bounded call that runs as one band);
 //   bands    the per-band lists and share winners of the bounded order (modes 1/3, mode 7 scanned over lists);
 //   compact  the listed blocks' texels in list order (the RGB bounded order only);
-//   pairs    the pair route's words, second lists and buckets (the RGB bounded order only, whatever ITW_BC7_PAIRS says).
-struct FusedNeeds { bool lists, bands, compact, pairs; };
+//   pairs    the pair route's words, second lists and buckets (the RGB bounded order only, whatever ITW_BC7_PAIRS says);
+//   rot      the rotation lists, merged words and payload slots of modes 4/5 (the same calls with three channels, whatever ITW_BC7_ROT_TASKS says).
+struct FusedNeeds { bool lists, bands, compact, pairs, rot; };
 static FusedNeeds fused_needs(const bc7_enc_settings* s)
 {
-    if (!s) return FusedNeeds{true, true, true, true};                  // unknown settings: everything
+    if (!s) return FusedNeeds{true, true, true, true, true};                  // unknown settings: everything
     bc7_enc_settings S = *s;
     S.channels = (s->channels == 4) ? 4 : 3;
     auto ranked = [](int t) { return t > 0 && t < 64; };
@@ -2322,7 +2474,7 @@ static FusedNeeds fused_needs(const bc7_enc_settings* s)
     const bool bounded = bc7_bounded_order() && on02 && on13 && !r13;
     const bool alpha = bc7_alpha_first(S);
     const bool on7 = S.mode_selection[1] && S.fastSkipTreshold_mode7 > 0;
-    return FusedNeeds{alpha || bounded, bounded, bounded && !alpha && bc7_compact_lists(), bounded && !alpha && !on7};
+    return FusedNeeds{alpha || bounded, bounded, bounded && !alpha && bc7_compact_lists(), bounded && !alpha && !on7, bounded && !alpha && !on7 && S.channels == 3};
 }
 static FusedLayout fused_layout(size_t n, const FusedNeeds& need)
 {
@@ -2348,6 +2500,9 @@ static FusedLayout fused_layout(size_t n, const FusedNeeds& need)
     for (int k = 0; k < 2; k++) { W.band[k].pair_words = o; o += need.pairs ? 4 * W.band[k].cap : 0; }
     for (int k = 0; k < 2; k++) { W.band[k].pair_redo = o; o += need.pairs ? W.band[k].cap : 0; }
     for (int k = 0; k < 2; k++) { W.band[k].pair_cap = W.band[k].cap / 8; W.band[k].pair_buckets = o; o += need.pairs ? 64 * W.band[k].pair_cap : 0; }
+    W.rot_words = o; o = up4(o + (need.rot ? 2 * n : 0));
+    for (int k = 0; k < 2; k++) { W.band[k].rot_lists = o; o += need.rot ? 3 * W.band[k].cap : 0; }
+    for (int k = 0; k < 2; k++) { W.band[k].rot_payload = o; o += need.rot ? 12 * W.band[k].cap : 0; }
     W.words = o;
     return W;
 }
@@ -2565,17 +2720,18 @@ void launch_bc7(const uint8_t* src, int64_t stride, int width, int height, uint8
             // a finish phase: list phases launch one workgroup per possible list chunk (they return at once behind the list's end)
             auto finish = [&](auto phase, const int32_t* in_list, const int32_t* in_count, int32_t* out_list, int32_t* out_count,
                               int32_t* out_list7 = nullptr, int32_t* out_count7 = nullptr, ChunkSel sel = ChunkSel{0, 1, 0, nullptr, 0}, int32_t cnt = -1,
-                              hipStream_t s = nullptr, const uint32_t* wins = nullptr, int32_t rows = 0, const uint4* in_compact = nullptr, uint4* out_compact = nullptr) {
+                              hipStream_t s = nullptr, const uint32_t* wins = nullptr, int32_t rows = 0, const uint4* in_compact = nullptr, uint4* out_compact = nullptr,
+                              RotRegion rot = RotRegion{nullptr, nullptr, nullptr, nullptr, 0}) {
                 constexpr int PH = decltype(phase)::value;
                 // bc7_finish_all<3> reads its PairTarget at a fixed distance from the list length: only a band's own counter block will do
-                if (PH == 3 && out_count != rgb_count + 16 + PAIR_CTR_LIST && out_count != rgb_count + 16 + PAIR_CTR_WORDS + PAIR_CTR_LIST)
+                if ((PH == 3 || PH == 10) && out_count != rgb_count + 16 + PAIR_CTR_LIST && out_count != rgb_count + 16 + PAIR_CTR_WORDS + PAIR_CTR_LIST)
                     fail_msg("bc7_finish_all<3>: the list length must be word %d of a band's counter block", PAIR_CTR_LIST);
                 if (cnt < 0) cnt = nchunks;
                 if (!s) s = st;
                 if (!wins) { wins = wins4; rows = (int32_t)n; }
                 const dim3 grid((unsigned)cnt);
-                if (L.vec) hipLaunchKernelGGL((bc7_finish_all<true, PH>),  grid, blk, 0, s, src, stride, bx, rows, dst, wins, S, alpha_err, in_list, in_count, out_list, out_count, out_list7, out_count7, sel, in_compact, out_compact);
-                else       hipLaunchKernelGGL((bc7_finish_all<false, PH>), grid, blk, 0, s, src, stride, bx, rows, dst, wins, S, alpha_err, in_list, in_count, out_list, out_count, out_list7, out_count7, sel, in_compact, out_compact);
+                if (L.vec) hipLaunchKernelGGL((bc7_finish_all<true, PH>),  grid, blk, 0, s, src, stride, bx, rows, dst, wins, S, alpha_err, in_list, in_count, out_list, out_count, out_list7, out_count7, sel, in_compact, out_compact, rot);
+                else       hipLaunchKernelGGL((bc7_finish_all<false, PH>), grid, blk, 0, s, src, stride, bx, rows, dst, wins, S, alpha_err, in_list, in_count, out_list, out_count, out_list7, out_count7, sel, in_compact, out_compact, rot);
             };
             // the bounded order (bc7_finish_all's header): profiles whose modes 1/3 scan every shape -- a ranked list already spends
             // a bound's worth of arithmetic per shape on its keys and then fits a few shapes only
@@ -2642,17 +2798,22 @@ void launch_bc7(const uint8_t* src, int64_t stride, int width, int height, uint8
                 //    chip the bands' scans fill, and the verdict arrived late: profiles/history/r05/r05d_bc7_pilot_timeline.txt.)
                 const bool two = bc7_bands() > 1 && aux && !aux->single && aux->stream && nchunks >= 32;
                 const bool pairs = bc7_pairs_on();
+                // the rotation bound is the RGB profiles' (an RGBA profile's fill is alpha); a first rotation outside 0..3 keeps the inline walk
+                const bool rot_tasks = bc7_rot_tasks_on() && S.channels == 3 && S.mode45_channel0 >= 0 && S.mode45_channel0 <= 3;
                 const bool pilot = two && bc7_pilot_threshold() >= 0 && aux->mid;
                 int32_t stripe = nchunks / 16;                               // stripes of 64 chunks (16 block rows of a 4096-wide surface), fewer on small surfaces
                 stripe = stripe < 1 ? 1 : (stripe > 64 ? 64 : stripe);
                 const int32_t stripes = (nchunks + stripe - 1) / stripe;
-                struct Band { ChunkSel sel; int32_t cnt; hipStream_t s; int32_t* list; int32_t* count; uint32_t* wins; int32_t rows; uint4* compact; PairRegion P; int32_t* redo; };
+                struct Band { ChunkSel sel; int32_t cnt; hipStream_t s; int32_t* list; int32_t* count; uint32_t* wins; int32_t rows; uint4* compact; PairRegion P; int32_t* redo; RotRegion R; };
                 auto band = [&](int k, hipStream_t s) {
                     const ListRegion& r = W.band[k];
                     Band B{ChunkSel{two ? 1 : 0, stripe, k, nullptr, 0}, two ? ((stripes + 1 - k) / 2) * stripe : nchunks, s,
                            reinterpret_cast<int32_t*>(wins4 + r.list), nullptr, wins4 + r.wins, 0, compact_on ? reinterpret_cast<uint4*>(wins4 + r.compact) : nullptr,
                            PairRegion{reinterpret_cast<uint64_t*>(wins4 + r.pair_words), reinterpret_cast<int32_t*>(wins4 + r.pair_buckets), reinterpret_cast<int32_t*>(wins4 + r.pair_ctr),
-                                      bc7_pair_cap((int32_t)(two ? r.pair_cap : 2 * r.pair_cap))}, reinterpret_cast<int32_t*>(wins4 + r.pair_redo)};
+                                      bc7_pair_cap((int32_t)(two ? r.pair_cap : 2 * r.pair_cap))}, reinterpret_cast<int32_t*>(wins4 + r.pair_redo),
+                           // one band: both bands' lists and payload slots as one region of twice the capacity; lengths: words 3..5 / 11..13 of the call's counters
+                           RotRegion{reinterpret_cast<int32_t*>(wins4 + r.rot_lists), rgb_count + (k ? 11 : 3), reinterpret_cast<unsigned long long*>(wins4 + W.rot_words),
+                                     reinterpret_cast<uint4*>(wins4 + r.rot_payload), (int32_t)(two ? r.cap : 2 * r.cap)}};
                     B.count = B.P.ctr + PAIR_CTR_LIST;
                     B.rows = B.cnt * TPB;                                    // shares x listed blocks <= rows: the list scan's grid covers them (list_scan_parts)
                     if (!two) { B.list = list13; B.wins = wins4; B.rows = (int32_t)n; }     // one band: the global winner rows, both texel regions as one
@@ -2662,7 +2823,14 @@ void launch_bc7(const uint8_t* src, int64_t stride, int width, int height, uint8
                 auto head = [&](const Band& B) { scan_rgb(nullptr, nullptr, false, true, 0, B.sel, B.cnt, B.s); };
                 auto tail = [&](const Band& B) {
                     // pairs: finish<3> also leaves the (block, shape) pairs the bound cannot exclude, bucketed by shape (header above bc7_pair_scan)
-                    finish(std::integral_constant<int, 3>{}, nullptr, nullptr, B.list, B.count, nullptr, nullptr, gated(B, 1), B.cnt, B.s, nullptr, 0, nullptr, B.compact);
+                    if (rot_tasks) {
+                        // modes 4/5 only for the (block, rotation) pairs a bound leaves (header above bc7_rot_tasks); empty lists where the pilot chose the other order
+                        finish(std::integral_constant<int, 9>{}, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, gated(B, 1), B.cnt, B.s, nullptr, 0, nullptr, nullptr, B.R);
+                        if (L.vec) hipLaunchKernelGGL((bc7_rot_tasks<true>),  dim3((unsigned)B.cnt), blk, 0, B.s, src, stride, bx, S, alpha_err, B.R);
+                        else       hipLaunchKernelGGL((bc7_rot_tasks<false>), dim3((unsigned)B.cnt), blk, 0, B.s, src, stride, bx, S, alpha_err, B.R);
+                        finish(std::integral_constant<int, 10>{}, nullptr, nullptr, B.list, B.count, nullptr, nullptr, gated(B, 1), B.cnt, B.s, nullptr, 0, nullptr, B.compact, B.R);
+                    } else
+                        finish(std::integral_constant<int, 3>{}, nullptr, nullptr, B.list, B.count, nullptr, nullptr, gated(B, 1), B.cnt, B.s, nullptr, 0, nullptr, B.compact);
                     if (pairs) {
                         // the few blocks finish<8> defers take the full list scan behind it
                         int32_t* redo_count = B.P.ctr + PAIR_CTR_REDO;
@@ -2725,6 +2893,7 @@ void launch_bc7(const uint8_t* src, int64_t stride, int width, int height, uint8
                         ITW_CHECK(hipMemcpy(h, rgb_count, sizeof h, hipMemcpyDeviceToHost));
                         std::fprintf(stderr, "bc7 pilot: estimate %d of %d sampled blocks listed -> %s; lists %d + %d of %lld blocks\n", h[8], h[9], h[6] ? "bounded" : "reference order",
                                      h[16 + PAIR_CTR_LIST], h[16 + PAIR_CTR_WORDS + PAIR_CTR_LIST], (long long)n);
+                        if (rot_tasks) std::fprintf(stderr, "bc7 rot tasks: rotation lists %d / %d / %d (band 0) + %d / %d / %d (band 1)\n", h[3], h[4], h[5], h[11], h[12], h[13]);
                         for (int k = 0; k < 2 && pairs; k++) {
                             int32_t c[PAIR_CTR_WORDS];
                             ITW_CHECK(hipMemcpy(c, (k ? Bb : A).P.ctr, sizeof c, hipMemcpyDeviceToHost));

@@ -230,6 +230,33 @@ __device__ __forceinline__ float two_subset_bound(int shape, const uint32_t (&pl
     return (e0 * e0 + e1 * e1) * 0.999999f;
 }
 
+// lower bound of the error of any mode 4 / 5 candidate of rotation `p` (0..2) under an RGB profile (round 9: bc7_rot_tasks, bc7.hip).  The
+// candidate codes the two channels it keeps as rounded points of ONE segment -- the projection of its three-channel segment, whatever the
+// filled channel does -- and channel p on its own (error >= 0): a texel lies within sqrt(2)/2 of a line in the kept plane, so the error is
+// >= (sqrt(R2) - sqrt(2)/2 sqrt(16))_+^2 with R2 = trace - largest eigenvalue of the kept 2x2 part of the whole block's scatter matrix.
+// The 2x2 matrix M = 16 x scatter has exact integer entries below 2^24, so its determinant is an exact 64-bit integer and
+// R2 x 16 = trace - lambda_max = det / lambda_max with lambda_max = (trace + sqrt((m00 - m11)^2 + 4 m01^2)) / 2 in closed form: a sum of
+// non-negative terms, no cancellation, one v_sqrt_f32.  Every float operation on the way is good to an ulp or two (1e-6 relative in all),
+// covered by a RELATIVE margin of 1e-5 on the residual; then 0.999999 factors and the slack constant rounded up, as in two_subset_bound:
+// the value returned never exceeds the true bound (tests/test_bc7_rotation_bound.py restates it in numpy).  (two_subset_bound's margin of
+// 1e-5 of the TRACE would cost up to 5 units of error on a high-contrast block here: the subtraction it covers does not occur.)
+#define BOUND_SLACK2_16 2.82842732f             // sqrt(2)/2 sqrt(16), rounded up
+__device__ __forceinline__ float rotation_bound(int p, const IStats<3>& full)
+{
+    // 16 x scatter matrix: exact integers below 2^24, exact as floats
+    const int32_t c00 = 16 * full.m[0] - full.s[0] * full.s[0], c11 = 16 * full.m[4] - full.s[1] * full.s[1], c22 = 16 * full.m[7] - full.s[2] * full.s[2];
+    const int32_t c01 = 16 * full.m[1] - full.s[0] * full.s[1], c02 = 16 * full.m[2] - full.s[0] * full.s[2], c12 = 16 * full.m[5] - full.s[1] * full.s[2];
+    const int32_t cii = (p == 0) ? c11 : c00, cjj = (p == 2) ? c11 : c22, cij = (p == 0) ? c12 : ((p == 1) ? c02 : c01);
+    const long long det = (long long)cii * (long long)cjj - (long long)cij * (long long)cij;      // >= 0 (Cauchy-Schwarz), exact
+    const float t = (float)(cii + cjj);
+    const float dif = (float)(cii - cjj), b = (float)cij;
+    const float lam = 0.5f * (t + __builtin_amdgcn_sqrtf(dif * dif + 4.0f * (b * b)));             // >= t / 2
+    const float res = ((float)det * __builtin_amdgcn_rcpf(fmaxf(lam, 1.0f))) * 0.99999f;           // 16 x R2, from below (det = 0 where lam = 0)
+    const float dist = __builtin_amdgcn_sqrtf(res * rcp_of_count(16)) * 0.999999f - BOUND_SLACK2_16;
+    const float e = fmaxf(dist, 0.0f);
+    return e * e * 0.999999f;
+}
+
 template <int CH>
 __device__ __forceinline__ void stats_float(Stats<CH>& f, const IStats<CH>& st)
 {

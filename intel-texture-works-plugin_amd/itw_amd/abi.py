@@ -37,7 +37,7 @@ EXPORTED_SYMBOLS = tuple(
     # include/itw_dds.h, second part: KTX 1.1 container (ETC1)
     + ["itwKtxHeaderBytes", "itwKtxFileBytes", "itwKtxWriteHeader", "itwKtxReadHeader", "itwKtxWriteFile", "itwKtxImage"])
 # include/itw_test_hooks.h: exported by libispc_texcomp_test.so only (the same sources built with -DITW_TEST_HOOKS), never by the product
-TEST_HOOK_SYMBOLS = ("itwTestRcp", "itwTestRsqrt", "itwTestF2I", "itwTestBc7TwoSubsetBounds", "itwTestBc45IndexTable", "itwTestBc45ClosestS",
+TEST_HOOK_SYMBOLS = ("itwTestRcp", "itwTestRsqrt", "itwTestF2I", "itwTestBc7TwoSubsetBounds", "itwTestBc7RotationBounds", "itwTestBc45IndexTable", "itwTestBc45ClosestS",
                      "itwMultiGpuTestInjectFailure", "itwTestCombinerHold", "itwTestCombinerCounters")
 
 
@@ -283,6 +283,8 @@ def _load(path, hooks):
                 getattr(L, n).restype = None
             L.itwTestBc7TwoSubsetBounds.argtypes = [C.POINTER(RgbaSurface), C.c_void_p]
             L.itwTestBc7TwoSubsetBounds.restype = None
+            L.itwTestBc7RotationBounds.argtypes = [C.POINTER(RgbaSurface), C.c_void_p]
+            L.itwTestBc7RotationBounds.restype = None
             L.itwTestBc45IndexTable.argtypes = [C.c_void_p]
             L.itwTestBc45IndexTable.restype = C.c_int
             L.itwTestBc45ClosestS.argtypes = [C.c_void_p]
@@ -575,6 +577,25 @@ def bc7_two_subset_bounds(img):
         L.itwSetStream(torch.cuda.current_stream(img.device).cuda_stream)
         surf = RgbaSurface(img.data_ptr(), w, h, img.stride(0))
         L.itwTestBc7TwoSubsetBounds(C.byref(surf), out.data_ptr())
+    e = L.itwLastError()
+    if e:
+        raise RuntimeError(e.decode())
+    return out
+
+
+def bc7_rotation_bounds(img):
+    """Test hook: the lower bound of modes 4/5's candidates of each rotation under an RGB profile (itwTestBc7RotationBounds).
+    img: CUDA tensor (H, W, 4) uint8 -> float32 CUDA tensor (blocks, 3), raster block order."""
+    import torch
+    assert img.is_cuda and img.dim() == 3 and img.shape[2] == 4 and img.element_size() == 1
+    assert img.stride(2) == 1 and img.stride(1) == 4
+    h, w = img.shape[:2]
+    out = torch.empty(((h // 4) * (w // 4), 3), dtype=torch.float32, device=img.device)
+    L = test_lib()
+    with torch.cuda.device(img.device):
+        L.itwSetStream(torch.cuda.current_stream(img.device).cuda_stream)
+        surf = RgbaSurface(img.data_ptr(), w, h, img.stride(0))
+        L.itwTestBc7RotationBounds(C.byref(surf), out.data_ptr())
     e = L.itwLastError()
     if e:
         raise RuntimeError(e.decode())
