@@ -16,6 +16,11 @@
 //                 the blocks, the worst ones, in one round
 //     --refine-psnr  : bc7_* only: <profile> on as many of the worst blocks as it takes to reach <dB> over the format's own channels
 //                 (itwPsnrToTotalSse gives the target), in up to five rounds
+//     --normal flipx,flipy,normalize : the input is a normal map; the named stages of the plugin's save path (FlipXYChannelNormalMap,
+//                 NormalizeNormalMapChain) are applied as the texels are encoded -- bc5 through itwCompressNormalMapBC5 (one kernel), any
+//                 other format through itwCompressNormalMapChain.  The slice loop is not used; not with --refine*.
+//     --cube-cross : the input is a horizontal (4 x 3 faces) or vertical (3 x 4) cube cross; its six faces (itwCubeCrossFaces: views, no
+//                 copy) are encoded by one chain call into a cube-map DDS.  Goes with --normal; not with --refine*, --measure or etc1_slow.
 //
 //   encode_dds --decode <in.dds | in.ktx> <out.raw>
 //     (.dds or .ktx: told apart by the file's first bytes; a KTX file's images come in ITS order, level then face)
@@ -84,6 +89,67 @@ bool on_progress(int done, int total, void*)
     return true;                                                   // false would abort like the plugin's cancel button
 }
 
+// encode_dds --normal / --cube-cross: `source` (or its six cross faces) through ONE call that pads, prepares and encodes
+int encode_normal_or_cross(const Format& f, const rgba_surface& source, uint32_t ops, bool cube_cross, bool measure, const char* out_path)
+{
+    const bool bc7 = std::strncmp(f.name, "bc7_", 4) == 0, bc6h = std::strncmp(f.name, "bc6h_", 5) == 0, etc1 = f.dxgi == ITW_FORMAT_ETC1_RGB8;
+    union { bc7_enc_settings s7; bc6h_enc_settings s6; etc_enc_settings se; } settings;
+    if (etc1) itwGetProfile_etc_slow(&settings.se);
+    else if ((bc7 || bc6h) && !profile_by_name(bc6h, f.name + (bc7 ? 4 : 5), &settings)) return 2;
+    rgba_surface images[6] = {source};
+    int count = 1;
+    if (cube_cross) {
+        if (itwCubeCrossFaces(&source, f.texel_bytes, images) != 0) { std::fprintf(stderr, "%d x %d is too small for a cube cross\n", source.width, source.height); return 2; }
+        count = 6;
+    }
+    const int64_t bytes = itwChainBytes(images, count, f.dxgi);
+    if (bytes <= 0) { std::fprintf(stderr, "bad size\n"); return 2; }
+    std::vector<uint8_t> blocks((size_t)bytes);
+    itwSetErrorMode(ITW_ON_ERROR_RETURN);
+    bool ok;
+    if (f.dxgi == ITW_DXGI_FORMAT_BC5_UNORM && !cube_cross) {      // the plugin's normal-map format: the stages run inside the encoder
+        itwCompressNormalMapBC5(&source, blocks.data(), ops);
+        ok = itwLastError() == nullptr;
+    } else {
+        ok = itwCompressNormalMapChain(images, count, blocks.data(), f.dxgi, &settings, ops, nullptr, nullptr);
+    }
+    if (!ok) { std::fprintf(stderr, "%s\n", itwLastError() ? itwLastError() : "compression failed"); return 1; }
+    if (measure) {
+        // against the PREPARED texels: what the stream was encoded from
+        std::vector<uint8_t> prepared((size_t)source.stride * source.height);
+        std::memcpy(prepared.data(), source.ptr, prepared.size());
+        rgba_surface p = source;
+        p.ptr = prepared.data();
+        itw_error_stats st;
+        if (itwPrepareNormalMapChain(&p, 1, f.texel_bytes, ops) != 0 || itwMeasureBlocks(f.dxgi, blocks.data(), &p, &st, sizeof st, nullptr) != 0) {
+            std::fprintf(stderr, "measurement failed\n");
+            return 1;
+        }
+        std::printf("image 0: %dx%d %s", st.width, st.height, f.name);
+        if (f.texel_bytes == 4) std::printf(" psnr %.4f dB", itwStatsPsnr(&st, f.own_channels));
+        std::printf(" sse [%llu, %llu, %llu, %llu] max_abs [%u, %u, %u, %u]\n", (unsigned long long)st.sse[0], (unsigned long long)st.sse[1],
+                    (unsigned long long)st.sse[2], (unsigned long long)st.sse[3], st.max_abs[0], st.max_abs[1], st.max_abs[2], st.max_abs[3]);
+    }
+    // formats that pad store the padded size, as the save path does; the DirectXTex formats keep the image's own
+    const uint32_t w = f.pad ? (uint32_t)((images[0].width + 3) & ~3) : (uint32_t)images[0].width, h = f.pad ? (uint32_t)((images[0].height + 3) & ~3) : (uint32_t)images[0].height;
+    ItwDdsDesc desc = { w, h, 1, (uint32_t)f.dxgi, cube_cross ? 1u : 0u, 1 };
+    ItwKtxDesc kdesc = { w, h, 1, ITW_FORMAT_ETC1_RGB8, 0, 0 };
+    std::vector<uint8_t> file(etc1 ? itwKtxFileBytes(&kdesc) : itwDdsFileBytes(&desc));
+    const uint8_t* levels[6];
+    for (int i = 0; i < count; i++) levels[i] = blocks.data() + (size_t)i * (blocks.size() / (size_t)count);      // the faces are equal
+    if ((etc1 ? itwKtxWriteFile(&kdesc, levels, 1, file.data(), file.size()) : itwDdsWriteFile(&desc, levels, (size_t)count, file.data(), file.size())) != file.size()
+        || file.empty()) {
+        std::fprintf(stderr, "%s assembly failed\n", etc1 ? "KTX" : "DDS");
+        return 1;
+    }
+    FILE* out = std::fopen(out_path, "wb");
+    if (!out || std::fwrite(file.data(), 1, file.size(), out) != file.size()) { std::fprintf(stderr, "cannot write %s\n", out_path); return 1; }
+    std::fclose(out);
+    DestroyThreads();
+    std::fprintf(stderr, "%s: %ux%u%s -> %zu bytes (%s, normal ops %u)\n", out_path, w, h, cube_cross ? " x 6 faces" : "", file.size(), f.name, ops);
+    return 0;
+}
+
 // encode_dds --decode: the whole file through one call
 int decode_file(const char* in_path, const char* out_path)
 {
@@ -146,6 +212,8 @@ int main(int argc, char** argv)
     unsigned long long max_block_sse = 0;
     int refine_to = 0;                                          // 1: --refine-share, 2: --refine-psnr
     double refine_value = 0.0;                                  // percent / dB
+    bool normal_given = false, cube_cross = false;
+    uint32_t normal_ops = 0;                                    // ITW_NORMAL_*
     for (int i = 1; i < argc; i++)
         if (std::strcmp(argv[i], "--measure") == 0) {
             measure = true;
@@ -162,9 +230,26 @@ int main(int argc, char** argv)
             refine_value = std::atof(argv[i + 2]);
             for (int k = i; k + 3 < argc; k++) argv[k] = argv[k + 3];
             argc -= 3; i--;
+        } else if (std::strcmp(argv[i], "--normal") == 0 && i + 1 < argc) {
+            normal_given = true;
+            for (const char* p = argv[i + 1]; *p;) {
+                const size_t n = std::strcspn(p, ",");
+                if (n == 5 && std::strncmp(p, "flipx", 5) == 0) normal_ops |= ITW_NORMAL_FLIP_X;
+                else if (n == 5 && std::strncmp(p, "flipy", 5) == 0) normal_ops |= ITW_NORMAL_FLIP_Y;
+                else if (n == 9 && std::strncmp(p, "normalize", 9) == 0) normal_ops |= ITW_NORMAL_NORMALIZE;
+                else { std::fprintf(stderr, "--normal takes a list of flipx, flipy, normalize\n"); return 2; }
+                p += n + (p[n] == ',' ? 1 : 0);
+            }
+            for (int k = i; k + 2 < argc; k++) argv[k] = argv[k + 2];
+            argc -= 2; i--;
+        } else if (std::strcmp(argv[i], "--cube-cross") == 0) {
+            cube_cross = true;
+            for (int k = i; k + 1 < argc; k++) argv[k] = argv[k + 1];
+            argc--; i--;
         }
     if (argc < 6) {
         std::fprintf(stderr, "usage: %s [--measure] [--refine <profile> <max_block_sse> | --refine-share <profile> <percent> | --refine-psnr <profile> <dB>]\n"
+                             "          [--normal flipx,flipy,normalize] [--cube-cross]\n"
                              "          <format> <width> <height> <in.raw> <out.dds> [slice_pixels]\n"
                              "       %s --decode <in.dds | in.ktx> <out.raw>\n", argv[0], argv[0]);
         return 2;
@@ -181,6 +266,14 @@ int main(int argc, char** argv)
     std::fclose(in);
 
     rgba_surface source = { texels.data(), width, height, width * f->texel_bytes };
+    if (normal_given || cube_cross) {
+        // the normal-map and cube-cross stages of the save path (IntelPlugin.cpp:2075-2106, 2149-2152): one call over the image or its six faces
+        if (refine_profile || (cube_cross && (measure || f->dxgi == ITW_FORMAT_ETC1_RGB8))) {
+            std::fprintf(stderr, "--normal / --cube-cross do not go with --refine*; --cube-cross not with --measure or etc1_slow\n");
+            return 2;
+        }
+        return encode_normal_or_cross(*f, source, normal_ops, cube_cross, measure, argv[5]);
+    }
     rgba_surface padded = source;
     if (f->pad && ((width | height) & 3)) padded = itwPadToMultipleOf4(&source, f->texel_bytes);     // IntelPlugin.cpp:893-928
 

@@ -50,6 +50,16 @@ void CompressBlocksBC5S(const rgba_surface* src, uint8_t* dst);
  * same rules; itwWarmupBC45() and the UNORM pair neither build nor need it. */
 void itwWarmupBC45S(void);
 
+/* A normal map to BC5 as the plugin saves it -- the only format its NORMAL MAP texture type takes (IntelPlugin.cpp:58 IsCombinationValid) --
+ * in one kernel: FlipXYChannelNormalMap and NormalizeNormalMapChain (IntelPlugin.cpp:2103-2106, 2149-2152) are applied to the texels as the
+ * BC5 encoder loads them.  `ops`: ITW_NORMAL_FLIP_X | ITW_NORMAL_FLIP_Y | ITW_NORMAL_NORMALIZE (itw_dispatch.h, which defines the per-texel
+ * arithmetic).  The stream is byte for byte CompressBlocksBC5 of a copy prepared with itwPrepareNormalMapChain; `src` is not modified;
+ * ops == 0 is CompressBlocksBC5.  CompressBlocksBC5's contract otherwise: any size >= 1, partial blocks kept, host or device pointers,
+ * device pointers asynchronous on the calling thread's stream.  Unknown `ops` bits fail through the library's error mode before any device
+ * work.  The first normalising call on a device uploads a 192 KiB scale table next to the index table, under that table's rules
+ * (itwWarmupBC45() builds both). */
+void itwCompressNormalMapBC5(const rgba_surface* src, uint8_t* dst, uint32_t ops);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

@@ -313,6 +313,40 @@ void itwPadToMultipleOf4Device(const rgba_surface* input, int pixel_size, uint8_
 int itwConvertToRGBA8Device(const void* src, int depth, int planes, int has_alpha, int gamma_correct, int width, int height, uint8_t* dst);
 int itwConvertToRGBA16FDevice(const void* src, int depth, int planes, int has_alpha, int width, int height, uint16_t* dst);
 
+/* The normal-map stages of the save path (IntelPlugin.cpp:2103-2106 FlipXYChannelNormalMap :1506-1545, :2149-2152 NormalizeNormalMapChain
+ * :1550-1613).  `ops` is a bit set; the flips apply first, then the normalise -- the reference's order.  Alpha is never touched, blue only
+ * by the normalise.  Per texel, IEEE fp32 with every operation rounded on its own:
+ *   RGBA8    flip: R = 255 - R and / or G = 255 - G.  normalise: r, g, b = (float)(code - 128); m = sqrtf((r*r + g*g) + b*b); m > 0: s = 127.0f / m and
+ *            each channel becomes (uint8_t)(x*s + 128.0f) (truncation); otherwise the texel becomes (128, 128, 255).
+ *   RGBA16F  flip: half(1.0f - float(h)).  normalise: m as above over the three halves widened to float; m > 0: s = 1.0f / m and each channel
+ *            becomes half(x*s); otherwise (0, 0, 0x3C00).  half() rounds to nearest even, as itwConvertToRGBA16FDevice.  NaN and infinite
+ *            inputs give what IEEE arithmetic gives; which NaN pattern comes out is not specified.
+ *
+ * itwPrepareNormalMapChain: in place over `count` images of any size >= 1 and any stride >= the row's bytes; pixel_size 4 (RGBA8) or 8
+ * (RGBA16F).  All images host pointers or all device pointers.  Device pointers: one launch over the whole chain, asynchronous on the calling
+ * thread's stream.  Host pointers: staged through the thread's buffer; returns synchronised.  Nothing outside width x height of an image is
+ * written: row padding stays as it is.  Returns 0, also for count == 0 or ops == 0; -1, before any device work, for a null pointer,
+ * count < 0, a pixel_size other than 4 or 8, unknown ops bits, a width or height < 1, a stride below the row's bytes, texels that are not
+ * pixel_size aligned, or mixed host and device pointers. */
+enum { ITW_NORMAL_FLIP_X = 1, ITW_NORMAL_FLIP_Y = 2, ITW_NORMAL_NORMALIZE = 4 };
+int itwPrepareNormalMapChain(const rgba_surface* images, int count, int pixel_size, uint32_t ops);
+
+/* itwCompressImageChainEx with the stages above applied to every texel as the chain's gather copies it: the same formats (the texel size
+ * follows from the format: RGBA16F for BC6H, RGBA8 otherwise, the bytes of an RGBA8_SNORM source treated as codes like any other), images,
+ * pointer kinds, progress contract, errors and return value.  The stream is byte for byte itwCompressImageChainEx over copies prepared with
+ * itwPrepareNormalMapChain; the sources are never written.  With ops != 0 an image that itwCompressImageChainEx would encode in place goes
+ * through the gather too (one copy more); ops == 0 is itwCompressImageChainEx.  Unknown ops bits fail through the error mode. */
+bool itwCompressNormalMapChain(const rgba_surface* images, int count, uint8_t* target, int dxgi_format,
+                               const void* settings, uint32_t ops, ItwProgressFunc* progress, void* user);
+
+/* ConvertToCubeMapFromCross (IntelPlugin.cpp:1200-1265) as six VIEWS into `cross`, in the order +X -X +Y -Y +Z -Z: the faces of a horizontal
+ * cross are width/4 x height/3 (truncating quotients) at cells (column, row) {2,1} {0,1} {1,0} {1,2} {1,1} {3,1}; when width < height the
+ * cross is vertical, the faces are width/3 x height/4 and the last cell is {1,3}.  No rotation and no copy, as the reference's CopyRectangle
+ * calls; the views share `cross`'s stride and feed itwCompressImageChainEx / itwCompressNormalMapChain directly (itw_decode.h documents the
+ * inverse).  pixel_size 4 or 8.  Host arithmetic only.  Returns 0; -1 for a null pointer, a pixel_size other than 4 or 8, or a cross smaller
+ * than 4 x 3 (3 x 4 when vertical). */
+int itwCubeCrossFaces(const rgba_surface* cross, int pixel_size, rgba_surface faces[6]);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

@@ -200,6 +200,7 @@ struct Job {
     const bc7_enc_settings*  s7 = nullptr;
     const bc6h_enc_settings* s6 = nullptr;
     int etc_threshold = 0;      // ETC1 only: fastSkipTreshold, >= 1 (a copy: the caller's etc_enc_settings need not outlive job_of)
+    uint32_t normal_ops = 0;    // BC5 only (itwCompressNormalMapBC5): ITW_NORMAL_* applied as the kernel loads its texels; such a job is never offered to the combiner
 };
 
 // The workspace (BC7's inter-family one, the wide BC6H shape's) is per host thread.  Work already queued on another stream may still be using
@@ -294,7 +295,10 @@ void launch(const Job& j, const uint8_t* d_src, int64_t stride, int w, int h, ui
         break;
     }
     case itw::BCN_BC4:  itw::launch_bc4(d_src, stride, w, h, d_dst, st); break;
-    case itw::BCN_BC5:  itw::launch_bc5(d_src, stride, w, h, d_dst, st); break;
+    case itw::BCN_BC5:
+        if (j.normal_ops) itw::launch_bc5_normal(d_src, stride, w, h, d_dst, j.normal_ops, st);
+        else              itw::launch_bc5(d_src, stride, w, h, d_dst, st);
+        break;
     case itw::BCN_BC4S: itw::launch_bc4s(d_src, stride, w, h, d_dst, st); break;
     case itw::BCN_BC5S: itw::launch_bc5s(d_src, stride, w, h, d_dst, st); break;
     case itw::BCN_ETC1:
@@ -836,7 +840,7 @@ struct ChainUnit { int i0, i1; int64_t b0, nb; bool in_place; };   // images [i0
 // The gather groups units[u0, u1) of a chain whose pointer kinds are known, pipelined; `poll(i0, i1)` reports images [i0, i1) as written.
 template <class Poll>
 bool chain_groups(const Job& j, const rgba_surface* im, uint8_t* target, const std::vector<ChainUnit>& units, size_t u0, size_t u1,
-                  bool src_dev, bool dst_dev, Poll&& poll)
+                  bool src_dev, bool dst_dev, Poll&& poll, uint32_t normal_ops = 0)
 {
     const int px = itw::texel_bytes(j.kind), bpb = itw::block_bytes(j.kind);
     const bool fill45 = itw::keeps_partial_blocks(j.kind);
@@ -911,7 +915,7 @@ bool chain_groups(const Job& j, const rgba_surface* im, uint8_t* target, const s
         }
         const int64_t pitch = (int64_t)G.pbx * 4 * px;
         uint8_t* packed = d_in + G.packed_off;
-        itw::launch_chain_gather(d_desc + (G.i0 - units[u0].i0), G.i1 - G.i0, G.nb, G.pbx, G.pby, px, fill45, packed, pitch, ks);
+        itw::launch_chain_gather(d_desc + (G.i0 - units[u0].i0), G.i1 - G.i0, G.nb, G.pbx, G.pby, px, fill45, packed, pitch, ks, nullptr, normal_ops);
         if (lone) launch(j, packed, pitch, G.pbx * 4, G.pby * 4, d_out + G.out_off, ks, !src_dev && !dst_dev);
         else      launch(j, packed, pitch, G.pbx * 4, G.pby * 4, d_out + G.out_off, ks, true, bc7_slices ? 1 : -1, pipe.workspace(g));
         if (dst_dev) ITW_CHECK(hipMemcpyAsync(target + G.b0 * bpb, d_out + G.out_off, (size_t)G.nb * bpb, hipMemcpyDeviceToDevice, ks));
@@ -926,7 +930,8 @@ bool chain_groups(const Job& j, const rgba_surface* im, uint8_t* target, const s
 }
 
 // `images` / `count` / `target` checked by chain_job.  Returns true when every image was encoded, false when `progress` stopped the job.
-bool compress_chain(const Job& j, const rgba_surface* im, int count, uint8_t* target, ItwProgressFunc* progress, void* user)
+// `normal_ops` (itwCompressNormalMapChain): the gather prepares every texel it copies, so no image is encoded in place.
+bool compress_chain(const Job& j, const rgba_surface* im, int count, uint8_t* target, ItwProgressFunc* progress, void* user, uint32_t normal_ops = 0)
 {
     const bool src_dev = is_device_pointer(im[0].ptr);
     for (int i = 1; i < count; i++)
@@ -956,7 +961,7 @@ bool compress_chain(const Job& j, const rgba_surface* im, int count, uint8_t* ta
     for (int i = 0; i < count; i++) {
         const int64_t nb = itw::image_blocks(im[i]);
         if (nb >= budget) {
-            const bool aligned = (im[i].width & 3) == 0 && (im[i].height & 3) == 0;
+            const bool aligned = (im[i].width & 3) == 0 && (im[i].height & 3) == 0 && normal_ops == 0;
             units.push_back(ChainUnit{i, i + 1, off, nb, aligned});            // in place, or (needs padding) a group of its own
             open = false;
         } else if (open && units.back().nb + nb <= budget) {
@@ -993,7 +998,7 @@ bool compress_chain(const Job& j, const rgba_surface* im, int count, uint8_t* ta
         }
         size_t v = u;
         while (v < units.size() && !units[v].in_place) v++;
-        if (!chain_groups(j, im, target, units, u, v, src_dev, dst_dev, poll) || stopped) return false;
+        if (!chain_groups(j, im, target, units, u, v, src_dev, dst_dev, poll, normal_ops) || stopped) return false;
         u = v;
     }
     return true;
@@ -1413,6 +1418,17 @@ void CompressBlocksBC5(const rgba_surface* src, uint8_t* dst)
 {
     itw::guarded([&] { Job j; j.kind = itw::BCN_BC5; compress(j, src, dst); });
 }
+// BC5 of a normal map, the stages applied in the encoder's load (include/itw_bc45.h)
+void itwCompressNormalMapBC5(const rgba_surface* src, uint8_t* dst, uint32_t ops)
+{
+    if (ops == 0) { CompressBlocksBC5(src, dst); return; }
+    itw::clear_failure();
+    itw::guarded([&] {
+        if (ops & ~7u) itw::fail_msg("itwCompressNormalMapBC5: unknown ops bits 0x%x", ops);
+        Job j; j.kind = itw::BCN_BC5; j.normal_ops = ops;
+        compress(j, src, dst, false);
+    });
+}
 void CompressBlocksBC4S(const rgba_surface* src, uint8_t* dst)
 {
     itw::guarded([&] { Job j; j.kind = itw::BCN_BC4S; compress(j, src, dst); });
@@ -1446,6 +1462,19 @@ bool itwCompressImageChainEx(const rgba_surface* images, int count, uint8_t* tar
     const bool ok = itw::guarded([&] {
         const Job j = chain_job(images, count, target, dxgi_format, settings);
         done = compress_chain(j, images, count, target, progress, user);
+    });
+    return ok && done;
+}
+
+bool itwCompressNormalMapChain(const rgba_surface* images, int count, uint8_t* target, int dxgi_format, const void* settings, uint32_t ops,
+                               ItwProgressFunc* progress, void* user)
+{
+    bool done = false;
+    itw::clear_failure();
+    const bool ok = itw::guarded([&] {
+        if (ops & ~7u) itw::fail_msg("itwCompressNormalMapChain: unknown ops bits 0x%x", ops);
+        const Job j = chain_job(images, count, target, dxgi_format, settings);
+        done = compress_chain(j, images, count, target, progress, user, ops);
     });
     return ok && done;
 }

@@ -37,6 +37,7 @@
 // lane that meets one runs FindClosestSNORM as written over its eight levels.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <cmath>
 #include <mutex>
 #include <vector>
 #include "kernels.hpp"
@@ -131,6 +132,15 @@ __global__ void __launch_bounds__(256) bc45_build_index_table(uint4* __restrict_
     table[r0 * 256u + r1] = make_uint4(c[0], c[1] | (min(runs, 255u) << 24), order[0], order[1]);
 }
 
+// ---- the normalise of a normal map, tabulated (itwCompressNormalMapBC5; normal_prep.hpp is the definition) -------------------------------
+// NormalizeNormalMapChain scales a texel by s = 127.0f / sqrtf((r*r + g*g) + b*b), r, g, b = code - 128.  The three squares and their sums
+// are integers below 2^24, so every fp32 operation up to the square root's argument is exact and s is a function of the INTEGER
+// k = r^2 + g^2 + b^2 <= 3 * 128^2 alone: 49 153 floats, computed on the host (IEEE square root and divide) and kept right behind the UNORM
+// run table, so the kernel needs no argument of its own.  Entry 0 is 0: the zero vector's R and G then come out as 0 * 0 + 128 = 128, the
+// default normal's (its blue, 255, is not BC5's business).  One v_dot4_i32_i8 and one 4-byte read replace the square root and the divide.
+constexpr uint32_t NORMAL_SCALE_ENTRIES = 3u * 128u * 128u + 1u;
+constexpr size_t RUN_TABLE_BYTES = 65536 * sizeof(uint4);
+
 struct TableSlot { std::once_flag once; uint4* table = nullptr; };
 TableSlot g_tables[2][64];                                        // [0] UNORM, [1] SNORM: each built by the first call that needs it
 
@@ -149,11 +159,14 @@ const uint4* index_table()
         uint4* t = nullptr;
         hipStream_t own = nullptr;
         ITW_CHECK(hipStreamCreateWithFlags(&own, hipStreamNonBlocking));
-        hipError_t e = hipMalloc(&t, 65536 * sizeof(uint4));
+        std::vector<float> scale(SGN ? 0u : NORMAL_SCALE_ENTRIES, 0.0f);        // the UNORM table carries the normalise scales behind its runs
+        for (uint32_t k = 1; k < (uint32_t)scale.size(); k++) scale[k] = 127.0f / std::sqrt((float)k);
+        hipError_t e = hipMalloc(&t, RUN_TABLE_BYTES + scale.size() * sizeof(float));
         if (e != hipSuccess) { (void)hipStreamDestroy(own); fail_hip("hipMalloc (BC4/BC5 index table)", e, __FILE__, __LINE__); }
         hipLaunchKernelGGL(bc45_build_index_table<SGN>, dim3(256), dim3(256), 0, own, t);
         std::vector<uint4> h(65536);
         e = hipMemcpyAsync(h.data(), t, 65536 * sizeof(uint4), hipMemcpyDeviceToHost, own);
+        if (e == hipSuccess && !scale.empty()) e = hipMemcpyAsync(t + 65536, scale.data(), scale.size() * sizeof(float), hipMemcpyHostToDevice, own);
         if (e == hipSuccess) e = hipStreamSynchronize(own);       // complete before any later launch, on whatever stream
         (void)hipStreamDestroy(own);
         if (e != hipSuccess) { (void)hipFree(t); fail_hip("bc45_build_index_table", e, __FILE__, __LINE__); }
@@ -464,6 +477,29 @@ __device__ __forceinline__ void load_words45(uint32_t (&w)[16], const uint8_t* _
     }
 }
 
+// The packed codes of channel `ch` (0 = R, 1 = G) of sixteen NORMALISED texels (PREP has ITW_NORMAL_NORMALIZE; its flip bits apply first):
+// what the v_perm gather yields for a surface prepared by normal_prep_rgba8.  Per texel: the three signed bytes code - 128 (the code with its
+// top bit flipped), their sum of squares by one v_dot4_i32_i8, the scale from the table, and this lane's channel alone as
+// (uint32_t)(x * s + 128.0f) -- both lanes of a block read the same sixteen scales, neither computes a square root or a divide.
+template <uint32_t PREP>
+__device__ __forceinline__ void normalised_codes(uint32_t (&P)[8], const uint32_t (&w)[16], uint32_t ch, const float* __restrict__ scale)
+{
+    constexpr uint32_t flip = ((PREP & 1u) ? 0x000000ffu : 0u) | ((PREP & 2u) ? 0x0000ff00u : 0u);
+    uint32_t a[16];
+    float s[16];
+#pragma unroll
+    for (int i = 0; i < 16; i++) {
+        a[i] = (w[i] ^ (flip ^ 0x00808080u)) & 0x00ffffffu;       // alpha out of the dot product
+        s[i] = scale[__builtin_amdgcn_sdot4((int)a[i], (int)a[i], 0, false)];
+    }
+    const uint32_t up = 24u - 8u * ch;
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+        const float x0 = (float)((int32_t)(a[2 * j] << up) >> 24), x1 = (float)((int32_t)(a[2 * j + 1] << up) >> 24);
+        P[j] = (uint32_t)(x0 * s[2 * j] + 128.0f) | ((uint32_t)(x1 * s[2 * j + 1] + 128.0f) << 16);
+    }
+}
+
 // Persistent workgroups (round 4): a wave of this kernel executes ~630 VALU instructions per block -- a fifth of it waiting for its
 // own texels if it loads, encodes, stores and exits (measured: 55-62 % of the issue slots used).  So at most BC45_GRID workgroups walk
 // the surface in chunks of 256 channel blocks and request the NEXT chunk's texels before encoding the current one.
@@ -471,7 +507,10 @@ __device__ __forceinline__ void load_words45(uint32_t (&w)[16], const uint8_t* _
 // lane's block position and byte offset incrementally -- one division per workgroup instead of one per chunk, 32-bit offsets from the
 // uniform base instead of four 64-bit row pointers with their source-row / column selects (about 90 of the 630 instructions).
 // SGN (trailing, so that the UNORM instantiations keep their names): the SNORM encoders; the texel codes are biased as they are gathered.
-template <int NCH, bool VEC16, bool WHOLE, bool SGN = false>
+// PREP (trailing likewise; BC5_UNORM only): the normal-map stages ITW_NORMAL_* of normal_prep.hpp applied to the sixteen loaded words as
+// their codes are gathered -- at the top of the loop, so the texels of the first load and of every prefetch take the same path.  A flip is
+// an exclusive-or of the gathered codes; the normalise is normalised_codes above, its scale table behind the run table (`runs` + 65 536).
+template <int NCH, bool VEC16, bool WHOLE, bool SGN = false, uint32_t PREP = 0>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BC45_WAVES, BC45_WAVES)))
 bc45_kernel(const uint8_t* __restrict__ src, int64_t stride, int32_t width, int32_t height, int32_t blocks_x,
             int32_t nlanes, uint8_t* __restrict__ dst, const uint4* __restrict__ runs)
@@ -517,10 +556,15 @@ bc45_kernel(const uint8_t* __restrict__ src, int64_t stride, int32_t width, int3
     const uint32_t off_wrap = 4u * stride32 - (uint32_t)blocks_x * 16u;           // one block row down, blocks_x blocks back
     for (;;) {
         uint32_t P[8];
+        if (PREP & 4u) {
+            normalised_codes<PREP>(P, w, ch, reinterpret_cast<const float*>(runs + 65536));
+        } else {
 #pragma unroll
-        for (int j = 0; j < 8; j++) {
-            P[j] = __builtin_amdgcn_perm(w[2 * j + 1], w[2 * j], sel);
-            if (SGN) P[j] = pk_max_u16(P[j] ^ 0x00800080u, 0x00010001u);   // biased; code 0 (int8 -128) becomes code 1 (-127): the same texel, -1.0f
+            for (int j = 0; j < 8; j++) {
+                P[j] = __builtin_amdgcn_perm(w[2 * j + 1], w[2 * j], sel);
+                if (SGN) P[j] = pk_max_u16(P[j] ^ 0x00800080u, 0x00010001u);   // biased; code 0 (int8 -128) becomes code 1 (-127): the same texel, -1.0f
+                if (PREP != 0u) P[j] ^= ((PREP >> ch) & 1u) ? 0x00ff00ffu : 0u;  // 255 - code, for the channel this lane encodes
+            }
         }
         const int32_t cur = lane;
         lane += step;
@@ -542,9 +586,11 @@ bc45_kernel(const uint8_t* __restrict__ src, int64_t stride, int32_t width, int3
     }
 }
 
-template <int NCH, bool SGN>
+// PREP (BC5_UNORM only): the normal-map stages in the load, itwCompressNormalMapBC5
+template <int NCH, bool SGN, uint32_t PREP = 0>
 void launch_bc45(const uint8_t* src, int64_t stride, int width, int height, uint8_t* dst, hipStream_t st)
 {
+    static_assert(PREP == 0 || (NCH == 2 && !SGN), "the normal-map stages go with BC5_UNORM");
     if (width <= 0 || height <= 0) return;
     const int bx = (width + 3) / 4, by = (height + 3) / 4;       // DirectXTex keeps partial blocks
     const int64_t n = (int64_t)bx * by * NCH;
@@ -555,12 +601,21 @@ void launch_bc45(const uint8_t* src, int64_t stride, int width, int height, uint
     // WHOLE: no partial blocks and every texel offset fits 31 bits (a non-negative stride; 16384^2 RGBA8 is 1 GiB)
     const bool whole = (width % 4 == 0) && (height % 4 == 0) && stride > 0 && (int64_t)height * stride < ((int64_t)1 << 31);
     if (whole) {
-        if (vec) hipLaunchKernelGGL((bc45_kernel<NCH, true, true, SGN>),  grid, blk, 0, st, src, stride, width, height, bx, (int32_t)n, dst, runs);
-        else     hipLaunchKernelGGL((bc45_kernel<NCH, false, true, SGN>), grid, blk, 0, st, src, stride, width, height, bx, (int32_t)n, dst, runs);
+        if (vec) hipLaunchKernelGGL((bc45_kernel<NCH, true, true, SGN, PREP>),  grid, blk, 0, st, src, stride, width, height, bx, (int32_t)n, dst, runs);
+        else     hipLaunchKernelGGL((bc45_kernel<NCH, false, true, SGN, PREP>), grid, blk, 0, st, src, stride, width, height, bx, (int32_t)n, dst, runs);
     } else {
-        if (vec) hipLaunchKernelGGL((bc45_kernel<NCH, true, false, SGN>),  grid, blk, 0, st, src, stride, width, height, bx, (int32_t)n, dst, runs);
-        else     hipLaunchKernelGGL((bc45_kernel<NCH, false, false, SGN>), grid, blk, 0, st, src, stride, width, height, bx, (int32_t)n, dst, runs);
+        if (vec) hipLaunchKernelGGL((bc45_kernel<NCH, true, false, SGN, PREP>),  grid, blk, 0, st, src, stride, width, height, bx, (int32_t)n, dst, runs);
+        else     hipLaunchKernelGGL((bc45_kernel<NCH, false, false, SGN, PREP>), grid, blk, 0, st, src, stride, width, height, bx, (int32_t)n, dst, runs);
     }
+}
+
+// itwCompressNormalMapBC5: PREP is a template argument, so `ops` (1..7) picks one of seven sets of instantiations
+template <uint32_t PREP>
+void launch_bc5_prep(uint32_t ops, const uint8_t* src, int64_t stride, int width, int height, uint8_t* dst, hipStream_t st)
+{
+    if constexpr (PREP > 7u) fail_msg("BC5 normal map: ops %u", ops);
+    else if (ops == PREP) launch_bc45<2, false, PREP>(src, stride, width, height, dst, st);
+    else launch_bc5_prep<PREP + 1>(ops, src, stride, width, height, dst, st);
 }
 
 #ifdef ITW_TEST_HOOKS
@@ -591,6 +646,12 @@ void launch_bc4(const uint8_t* src, int64_t stride, int width, int height, uint8
 void launch_bc5(const uint8_t* src, int64_t stride, int width, int height, uint8_t* dst, hipStream_t st) { launch_bc45<2, false>(src, stride, width, height, dst, st); }
 void launch_bc4s(const uint8_t* src, int64_t stride, int width, int height, uint8_t* dst, hipStream_t st) { launch_bc45<1, true>(src, stride, width, height, dst, st); }
 void launch_bc5s(const uint8_t* src, int64_t stride, int width, int height, uint8_t* dst, hipStream_t st) { launch_bc45<2, true>(src, stride, width, height, dst, st); }
+
+void launch_bc5_normal(const uint8_t* src, int64_t stride, int width, int height, uint8_t* dst, uint32_t ops, hipStream_t st)
+{
+    if (ops == 0u) launch_bc45<2, false>(src, stride, width, height, dst, st);
+    else           launch_bc5_prep<1>(ops, src, stride, width, height, dst, st);
+}
 
 void warmup_bc45() { (void)index_table<false>(); }
 void warmup_bc45s() { (void)index_table<true>(); }

@@ -13,6 +13,7 @@
 #include <stdint.h>
 #include "kernels.hpp"
 #include "host_rt.hpp"
+#include "normal_prep.hpp"
 
 namespace {
 using itw::ChainImage;
@@ -27,8 +28,10 @@ __device__ __forceinline__ uint32_t load_u32(const uint8_t* p)
 
 // PX: bytes per texel (4 RGBA8, 8 RGBA16F).  FILL45: BC4/BC5's partial-block fill instead of edge replication.  EXTENTS: the lane that
 // carries texel row 0 of block j < nblocks also writes extents[j] = (pw - 1) | (ph - 1) << 2, the part of the block that lies inside its
-// image (itwCompressImageChainRefined leaves the padding out of a block's error).
-template <int PX, bool FILL45, bool EXTENTS>
+// image (itwCompressImageChainRefined leaves the padding out of a block's error).  OPS (trailing, so that the instantiations without it
+// stay what they were): the normal-map stages of normal_prep.hpp applied to every texel copied (itwCompressNormalMapChain); a replicated
+// texel is prepared like the one it repeats, so the packed surface is the gather of prepared images.
+template <int PX, bool FILL45, bool EXTENTS, uint32_t OPS = 0>
 __global__ void __launch_bounds__(256) chain_gather_kernel(const ChainImage* __restrict__ images, int32_t nimg, int64_t nblocks,
                                                           int32_t packed_bx, int64_t total, uint8_t* __restrict__ dst, int64_t dst_pitch,
                                                           uint8_t* __restrict__ extents)
@@ -72,9 +75,28 @@ __global__ void __launch_bounds__(256) chain_gather_kernel(const ChainImage* __r
                 for (int q = 0; q < PX / 4; q++) v[c * (PX / 4) + q] = load_u32(p + sx * PX + q * 4);
             }
         }
+        if (OPS != 0) {
+#pragma unroll
+            for (int c = 0; c < 4; c++) {
+                if (PX == 4) v[c] = itw::normal_prep_rgba8(v[c], OPS);
+                else itw::normal_prep_rgba16f(v[2 * c], v[2 * c + 1], OPS);
+            }
+        }
     }
 #pragma unroll
     for (int q = 0; q < W / 4; q++) out[q] = make_uint4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
+}
+
+// the gather with the normal-map stages: OPS is a template argument, so one instantiation per value of the bit set
+template <int PX, bool FILL45, uint32_t OPS>
+void launch_prepared(uint32_t ops, dim3 grid, hipStream_t st, const ChainImage* images, int32_t nimg, int64_t nblocks, int32_t packed_bx, int64_t total,
+                     uint8_t* dst, int64_t dst_pitch)
+{
+    if constexpr (OPS > itw::NORMAL_OPS_ALL) itw::fail_msg("launch_chain_gather: normal-map ops %u", ops);
+    else if (ops == OPS)
+        hipLaunchKernelGGL((chain_gather_kernel<PX, FILL45, false, OPS>), grid, dim3(256), 0, st, images, nimg, nblocks, packed_bx, total, dst, dst_pitch,
+                           (uint8_t*)nullptr);
+    else launch_prepared<PX, FILL45, OPS + 1>(ops, grid, st, images, nimg, nblocks, packed_bx, total, dst, dst_pitch);
 }
 
 } // namespace
@@ -82,13 +104,22 @@ __global__ void __launch_bounds__(256) chain_gather_kernel(const ChainImage* __r
 namespace itw {
 
 void launch_chain_gather(const ChainImage* images, int nimg, int64_t nblocks, int packed_bx, int packed_by, int texel_bytes, bool fill45,
-                         uint8_t* dst, int64_t dst_pitch, hipStream_t st, uint8_t* extents)
+                         uint8_t* dst, int64_t dst_pitch, hipStream_t st, uint8_t* extents, uint32_t normal_ops)
 {
     const int64_t total = (int64_t)packed_bx * packed_by;
     if (total <= 0 || nimg <= 0) return;
     if (nblocks > total || (dst_pitch & 15) || ((uintptr_t)dst & 15) || dst_pitch < (int64_t)packed_bx * 4 * texel_bytes)
         fail_msg("launch_chain_gather: %lld blocks into %d x %d packed blocks, pitch %lld", (long long)nblocks, packed_bx, packed_by, (long long)dst_pitch);
     const dim3 grid((unsigned)((total + 63) / 64)), blk(256);
+    if (normal_ops != 0) {
+        if (extents) fail_msg("launch_chain_gather: extents do not go with the normal-map stages");
+        if (texel_bytes == 8 && fill45) fail_msg("launch_chain_gather: the BC4/BC5 fill is for RGBA8 surfaces");
+        if (texel_bytes == 8) launch_prepared<8, false, 1>(normal_ops, grid, st, images, nimg, nblocks, packed_bx, total, dst, dst_pitch);
+        else if (fill45)      launch_prepared<4, true, 1>(normal_ops, grid, st, images, nimg, nblocks, packed_bx, total, dst, dst_pitch);
+        else                  launch_prepared<4, false, 1>(normal_ops, grid, st, images, nimg, nblocks, packed_bx, total, dst, dst_pitch);
+        ITW_CHECK(hipGetLastError());
+        return;
+    }
     if (texel_bytes == 8) {
         if (fill45) fail_msg("launch_chain_gather: the BC4/BC5 fill is for RGBA8 surfaces");
         if (extents) hipLaunchKernelGGL((chain_gather_kernel<8, false, true>), grid, blk, 0, st, images, nimg, nblocks, packed_bx, total, dst, dst_pitch, extents);

@@ -1,0 +1,161 @@
+// normal_prep.hip -- the normal-map stages of the reference's save path as a pre-pass of their own (include/itw_dispatch.h:
+// itwPrepareNormalMapChain; IntelPlugin.cpp:2103-2106 FlipXYChannelNormalMap, :2149-2152 NormalizeNormalMapChain), and the cube-cross
+// views (itwCubeCrossFaces; :1200-1265 ConvertToCubeMapFromCross).  The arithmetic is normal_prep.hpp's.
+//
+// Every image of a chain in ONE launch, in place: a lane takes four consecutive texels of one row (a "quad": 16 B of RGBA8, 32 B of
+// RGBA16F), lane = quad of the chain's concatenated quad list, its image found by binary search over a small level table as
+// decode_chain_kernel finds its (a chain of one travels as a kernel argument).  A whole quad at a 16-byte address moves as dwordx4, anything
+// else texel by texel, so a pointer or stride that is only texel aligned works and nothing outside width x height is read or written.
+// A stream: HBM bound.
+#include <hip/hip_runtime.h>
+#include <cstdint>
+#include <vector>
+#include "../../include/itw_dispatch.h"
+#include "../../include/itw_amd.h"
+#include "normal_prep.hpp"
+#include "host_rt.hpp"
+
+namespace itw {
+
+// one image: texels at `ptr`, rows `stride` bytes apart, and the index of its first quad in the chain's list (ceil(width / 4) * height each)
+struct PrepLevel { uint8_t* ptr; int64_t stride; int32_t width, height; int64_t first_quad; };
+
+template <int PX>
+__device__ __forceinline__ void normal_prep_quad(const PrepLevel& lv, int64_t q, uint32_t ops)
+{
+    const int32_t qpr = (lv.width + 3) >> 2;
+    int64_t y;
+    int32_t qx;
+    if (q < ((int64_t)1 << 31)) { const uint32_t yy = (uint32_t)q / (uint32_t)qpr; y = yy; qx = (int32_t)((uint32_t)q - yy * (uint32_t)qpr); }
+    else                        { y = q / qpr; qx = (int32_t)(q - y * qpr); }
+    const int32_t n = min(4, lv.width - 4 * qx);                  // texels of this quad inside the row
+    uint8_t* p = lv.ptr + y * lv.stride + (int64_t)qx * 4 * PX;
+    if (n == 4 && ((uintptr_t)p & 15) == 0) {
+        uint4* p4 = reinterpret_cast<uint4*>(p);
+        if (PX == 4) {
+            uint4 t = p4[0];
+            t.x = normal_prep_rgba8(t.x, ops); t.y = normal_prep_rgba8(t.y, ops); t.z = normal_prep_rgba8(t.z, ops); t.w = normal_prep_rgba8(t.w, ops);
+            p4[0] = t;
+        } else {
+            uint4 a = p4[0], b = p4[1];
+            normal_prep_rgba16f(a.x, a.y, ops); normal_prep_rgba16f(a.z, a.w, ops);
+            normal_prep_rgba16f(b.x, b.y, ops); normal_prep_rgba16f(b.z, b.w, ops);
+            p4[0] = a; p4[1] = b;
+        }
+    } else {
+        uint32_t* p1 = reinterpret_cast<uint32_t*>(p);            // texel aligned: 4 bytes (RGBA8), 8 bytes (RGBA16F)
+        for (int x = 0; x < n; x++) {
+            if (PX == 4) p1[x] = normal_prep_rgba8(p1[x], ops);
+            else { uint32_t lo = p1[2 * x], hi = p1[2 * x + 1]; normal_prep_rgba16f(lo, hi, ops); p1[2 * x] = lo; p1[2 * x + 1] = hi; }
+        }
+    }
+}
+
+// ONE: a chain of one image; its descriptor is the kernel argument `one` and there is no table and no search
+template <int PX, bool ONE>
+__global__ void __launch_bounds__(256)
+normal_prep_kernel(const PrepLevel* __restrict__ levels, const PrepLevel one, int32_t nlev, int64_t nquads, uint32_t ops)
+{
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= nquads) return;
+    if (ONE) { normal_prep_quad<PX>(one, j, ops); return; }
+    int lo = 0, hi = nlev - 1;                                    // the last image whose first quad is <= j
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (levels[mid].first_quad <= j) lo = mid; else hi = mid - 1;
+    }
+    const PrepLevel lv = levels[lo];
+    normal_prep_quad<PX>(lv, j - lv.first_quad, ops);
+}
+
+} // namespace itw
+
+namespace {
+
+// everything that needs the device: `count` >= 1 images that passed the checks, all of one pointer kind
+void prepare_chain(const rgba_surface* im, int count, int px, uint32_t ops, bool dev)
+{
+    hipStream_t st = (hipStream_t)itwGetStream();
+    static thread_local std::vector<itw::PrepLevel> desc;         // grow-only, like the device buffer it is copied into
+    desc.resize((size_t)count);
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    // the thread's buffer: [level table] [staged images (host pointers), rows of a 16-byte multiple]
+    size_t bytes = count > 1 ? up((size_t)count * sizeof(itw::PrepLevel)) : 0;
+    int64_t quads = 0;
+    std::vector<size_t> stage_off(dev ? 0 : (size_t)count);
+    for (int i = 0; i < count; i++) {
+        itw::PrepLevel& d = desc[(size_t)i];
+        d.ptr = im[i].ptr; d.stride = im[i].stride; d.width = im[i].width; d.height = im[i].height;
+        d.first_quad = quads;
+        quads += (int64_t)((im[i].width + 3) >> 2) * im[i].height;
+        if (!dev) {
+            d.stride = (int64_t)(((size_t)im[i].width * px + 15) & ~(size_t)15);
+            stage_off[(size_t)i] = bytes;
+            bytes += up((size_t)d.stride * (size_t)im[i].height);
+        }
+    }
+    if ((quads + 255) / 256 > (int64_t)0x7fffffff) itw::fail_msg("itwPrepareNormalMapChain: %lld texel quads are more than one launch covers", (long long)quads);
+    const bool buffer = !dev || count > 1;                        // a resident chain of one touches no buffer of the thread
+    uint8_t* base = buffer ? static_cast<uint8_t*>(itw::decode_scratch(bytes, st)) : nullptr;
+    if (!dev)
+        for (int i = 0; i < count; i++) {
+            desc[(size_t)i].ptr = base + stage_off[(size_t)i];
+            ITW_CHECK(hipMemcpy2DAsync(desc[(size_t)i].ptr, (size_t)desc[(size_t)i].stride, im[i].ptr, (size_t)im[i].stride, (size_t)im[i].width * px,
+                                       (size_t)im[i].height, hipMemcpyHostToDevice, st));
+        }
+    if (count > 1) ITW_CHECK(hipMemcpyAsync(base, desc.data(), (size_t)count * sizeof(itw::PrepLevel), hipMemcpyHostToDevice, st));
+    const itw::PrepLevel* d_desc = count > 1 ? reinterpret_cast<const itw::PrepLevel*>(base) : nullptr;
+    const dim3 grid((unsigned)((quads + 255) / 256)), blk(256);
+    if (px == 4) {
+        if (count == 1) hipLaunchKernelGGL((itw::normal_prep_kernel<4, true>), grid, blk, 0, st, d_desc, desc[0], 1, quads, ops);
+        else            hipLaunchKernelGGL((itw::normal_prep_kernel<4, false>), grid, blk, 0, st, d_desc, desc[0], (int32_t)count, quads, ops);
+    } else {
+        if (count == 1) hipLaunchKernelGGL((itw::normal_prep_kernel<8, true>), grid, blk, 0, st, d_desc, desc[0], 1, quads, ops);
+        else            hipLaunchKernelGGL((itw::normal_prep_kernel<8, false>), grid, blk, 0, st, d_desc, desc[0], (int32_t)count, quads, ops);
+    }
+    ITW_CHECK(hipGetLastError());
+    if (dev) { if (buffer) itw::decode_scratch_done(st); return; }     // resident: asynchronous on the thread's stream
+    for (int i = 0; i < count; i++)                               // width x height only: the caller's row padding is not written
+        ITW_CHECK(hipMemcpy2DAsync(im[i].ptr, (size_t)im[i].stride, desc[(size_t)i].ptr, (size_t)desc[(size_t)i].stride, (size_t)im[i].width * px,
+                                   (size_t)im[i].height, hipMemcpyDeviceToHost, st));
+    ITW_CHECK(hipStreamSynchronize(st));
+    itw::decode_scratch_done(st);
+}
+
+} // namespace
+
+extern "C" int itwPrepareNormalMapChain(const rgba_surface* images, int count, int pixel_size, uint32_t ops)
+{
+    if (count < 0 || (pixel_size != 4 && pixel_size != 8) || (ops & ~itw::NORMAL_OPS_ALL)) return -1;
+    if (count == 0) return 0;
+    if (!images) return -1;
+    for (int i = 0; i < count; i++) {
+        const rgba_surface& s = images[i];
+        if (!s.ptr || s.width < 1 || s.height < 1 || (int64_t)s.stride < (int64_t)s.width * pixel_size) return -1;
+        const uintptr_t row_step = s.height > 1 ? (uintptr_t)(uint32_t)s.stride : 0;
+        if (((uintptr_t)s.ptr | row_step) & (uintptr_t)(pixel_size - 1)) return -1;      // every texel 4 / 8 bytes aligned
+    }
+    if (ops == 0) return 0;
+    const bool dev = itw::is_device_pointer(images[0].ptr);
+    for (int i = 1; i < count; i++)
+        if (itw::is_device_pointer(images[i].ptr) != dev) return -1;     // all host or all device, as the chain encoder asks
+    const bool ok = itw::guarded([&] { prepare_chain(images, count, pixel_size, ops, dev); });
+    return ok ? 0 : -1;
+}
+
+// IntelPlugin.cpp:1206-1233: the six rectangles of a horizontal (4 x 3 cells) or vertical (3 x 4) cross, +X -X +Y -Y +Z -Z; cell sizes are
+// truncating quotients, exactly as the reference's.  Views: no rotation and no copy (its CopyRectangle calls copy the rectangles as they lie)
+extern "C" int itwCubeCrossFaces(const rgba_surface* cross, int pixel_size, rgba_surface faces[6])
+{
+    if (!cross || !faces || !cross->ptr || (pixel_size != 4 && pixel_size != 8)) return -1;
+    int cells[6][2] = {{2, 1}, {0, 1}, {1, 0}, {1, 2}, {1, 1}, {3, 1}};
+    const bool vertical = cross->width < cross->height;
+    if (cross->width < (vertical ? 3 : 4) || cross->height < (vertical ? 4 : 3)) return -1;
+    const int32_t w = cross->width / (vertical ? 3 : 4), h = cross->height / (vertical ? 4 : 3);
+    if (vertical) { cells[5][0] = 1; cells[5][1] = 3; }
+    for (int i = 0; i < 6; i++) {
+        faces[i].ptr = cross->ptr + (int64_t)cells[i][1] * h * cross->stride + (int64_t)cells[i][0] * w * pixel_size;
+        faces[i].width = w; faces[i].height = h; faces[i].stride = cross->stride;
+    }
+    return 0;
+}

@@ -24,12 +24,13 @@ EXPORTED_SYMBOLS = tuple(
        "CompressImageBC1", "CompressImageBC3", "CompressImageBC4", "CompressImageBC5", "CompressImageBC4S", "CompressImageBC5S"]
     + ["CompressImageBC7_" + p for p in BC7_PROFILES] + ["CompressImageBC6H_" + p for p in BC6H_PROFILES]
     + ["itwCompressImageSliced", "itwCompressImageSlicedEx", "itwChainBytes", "itwCompressImageChain", "itwCompressImageChainEx", "itwCompressImageRefined", "itwCompressImageRefinedTo", "itwPsnrToTotalSse", "itwCompressImageChainRefined", "itwCompressImageChainRefinedTo", "itwChainPsnrToTotalSse", "itwSetSliceWindow", "itwSliceWindow", "itwSliceWindowFor", "itwPadToMultipleOf4", "itwFreeSurface", "itwPadToMultipleOf4Device",
-       "itwConvertToRGBA8Device", "itwConvertToRGBA16FDevice"]
+       "itwConvertToRGBA8Device", "itwConvertToRGBA16FDevice",
+       "itwPrepareNormalMapChain", "itwCompressNormalMapChain", "itwCubeCrossFaces"]
     # include/itw_multigpu.h: one surface over all GPUs, one process
     + ["itwMultiGpuRanks", "itwMultiGpuTransport", "itwMultiGpuPeerLinks", "itwCompressImageMultiGPU", "itwCompressImageMultiGPUEx", "itwCompressImageMultiGPUBands",
        "itwMultiGpuSetInterleave", "itwMultiGpuPieces"]
     # include/itw_bc45.h: the DirectXTex formats of the plugin
-    + ["CompressBlocksBC4", "CompressBlocksBC5", "itwWarmupBC45", "CompressBlocksBC4S", "CompressBlocksBC5S", "itwWarmupBC45S"]
+    + ["CompressBlocksBC4", "CompressBlocksBC5", "itwWarmupBC45", "CompressBlocksBC4S", "CompressBlocksBC5S", "itwWarmupBC45S", "itwCompressNormalMapBC5"]
     # include/itw_decode.h: device decoders
     + ["itwDecodeBlocks", "itwDecodeChain", "itwDecodeImage", "itwMeasureBlocks", "itwMeasureChain", "itwStatsPsnr"]
     # include/itw_dds.h: DDS container
@@ -364,6 +365,14 @@ def _load(path, hooks):
         L.itwConvertToRGBA8Device.restype = C.c_int
         L.itwConvertToRGBA16FDevice.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.itwConvertToRGBA16FDevice.restype = C.c_int
+        L.itwPrepareNormalMapChain.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint32]
+        L.itwPrepareNormalMapChain.restype = C.c_int
+        L.itwCompressNormalMapChain.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+        L.itwCompressNormalMapChain.restype = C.c_bool
+        L.itwCompressNormalMapBC5.argtypes = [C.POINTER(RgbaSurface), C.c_void_p, C.c_uint32]
+        L.itwCompressNormalMapBC5.restype = None
+        L.itwCubeCrossFaces.argtypes = [C.POINTER(RgbaSurface), C.c_int, C.POINTER(RgbaSurface)]
+        L.itwCubeCrossFaces.restype = C.c_int
         L.itwDecodeBlocks.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]
         L.itwDecodeBlocks.restype = C.c_int
         L.itwDecodeChain.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
@@ -663,9 +672,10 @@ def chain_bytes(fmt, images):
     return int(lib().itwChainBytes(C.cast(arr, C.c_void_p), len(images), DXGI_FORMAT[fmt]))
 
 
-def compress_chain(fmt, images, profile=None, settings=None, progress=None, out=None, cmp_func=None):
+def compress_chain(fmt, images, profile=None, settings=None, progress=None, out=None, cmp_func=None, normal_ops=None):
     """A whole mip chain / cube map / array in one call (itwCompressImageChainEx; with `cmp_func` -- a CompressionFunc address, e.g.
-    image_func(fmt, profile) -- itwCompressImageChain).  images: list of host numpy arrays or CUDA torch tensors (H, W, 4), uint8 or
+    image_func(fmt, profile) -- itwCompressImageChain; with `normal_ops` -- a bit set of NORMAL_FLIP_X / NORMAL_FLIP_Y / NORMAL_NORMALIZE,
+    see normal_ops() -- itwCompressNormalMapChain: the normal-map stages applied to every texel as it is gathered, sources untouched).  images: list of host numpy arrays or CUDA torch tensors (H, W, 4), uint8 or
     uint16 half bits for bc6h, all of one kind, any size >= 1; "etc1" takes settings=EtcSettings (default etc_profile("slow")).  `out` (optional): numpy array or CUDA uint8 tensor of chain_bytes() bytes;
     by default the images' kind.  Returns (ok, blocks): the images' blocks one after another, tightly packed (a DDS payload)."""
     import numpy as np
@@ -699,8 +709,80 @@ def compress_chain(fmt, images, profile=None, settings=None, progress=None, out=
         elif settings is None and base == "etc1":
             settings = etc_profile(profile or "slow")
         sp = C.cast(C.byref(settings), C.c_void_p) if settings is not None else None
-        ok = lib().itwCompressImageChainEx(C.cast(arr, C.c_void_p), len(images), dst, DXGI_FORMAT[fmt_key], sp, cbp, None)
+        if normal_ops is not None:
+            ok = lib().itwCompressNormalMapChain(C.cast(arr, C.c_void_p), len(images), dst, DXGI_FORMAT[fmt_key], sp, int(normal_ops), cbp, None)
+        else:
+            ok = lib().itwCompressImageChainEx(C.cast(arr, C.c_void_p), len(images), dst, DXGI_FORMAT[fmt_key], sp, cbp, None)
     return bool(ok), out
+
+
+NORMAL_FLIP_X, NORMAL_FLIP_Y, NORMAL_NORMALIZE = 1, 2, 4     # ITW_NORMAL_* (include/itw_dispatch.h)
+
+
+def normal_ops(flip_x=False, flip_y=False, normalize=False):
+    """The `ops` bit set of the normal-map calls: the flips apply first, then the normalise (IntelPlugin.cpp:2103-2106, 2149-2152)."""
+    return (NORMAL_FLIP_X if flip_x else 0) | (NORMAL_FLIP_Y if flip_y else 0) | (NORMAL_NORMALIZE if normalize else 0)
+
+
+def prepare_normal_map(images, flip_x=False, flip_y=False, normalize=False, ops=None):
+    """itwPrepareNormalMapChain: the plugin's normal-map flip / normalise IN PLACE over one image or a list of them (a mip chain), host numpy
+    arrays or CUDA torch tensors (H, W, 4), all of one kind: uint8 (RGBA8) or 2-byte elements (RGBA16F half bits).  Device tensors: one
+    launch, asynchronous on torch's current stream; numpy arrays: synchronous.  Returns the images."""
+    single = hasattr(images, "shape")
+    imgs = [images] if single else list(images)
+    ops = normal_ops(flip_x, flip_y, normalize) if ops is None else int(ops)
+    if imgs:
+        es = imgs[0].element_size() if hasattr(imgs[0], "data_ptr") else imgs[0].itemsize
+        assert es in (1, 2) and all((i.element_size() if hasattr(i, "data_ptr") else i.itemsize) == es for i in imgs), "uint8 or half texels, one kind per call"
+        if hasattr(imgs[0], "data_ptr"):
+            import torch
+            lib().itwSetStream(torch.cuda.current_stream(imgs[0].device).cuda_stream)
+        if lib().itwPrepareNormalMapChain(C.cast(_surfaces(imgs), C.c_void_p), len(imgs), 4 * es, ops) != 0:
+            raise ValueError("itwPrepareNormalMapChain refused the call: " + (last_error() or "bad arguments"))
+    return images
+
+
+def compress_normal_map(img, flip_x=False, flip_y=False, normalize=False, ops=None, out=None):
+    """itwCompressNormalMapBC5: BC5 of a normal map with the plugin's flip / normalise applied in the encoder's load (one kernel; `img` is
+    not modified).  img: CUDA torch tensor (H, W, 4) uint8 (asynchronous on torch's current stream, returns a CUDA uint8 tensor) or a host
+    numpy array (synchronous, returns a numpy array).  Same bytes as compress("bc5", prepared copy)."""
+    ops = normal_ops(flip_x, flip_y, normalize) if ops is None else int(ops)
+    h, w = img.shape[:2]
+    nbytes = block_count("bc5", w, h) * 16
+    if hasattr(img, "data_ptr"):
+        import torch
+        assert img.is_cuda and img.dim() == 3 and img.shape[2] == 4 and img.element_size() == 1 and img.stride(2) == 1 and img.stride(1) == 4
+        if out is None:
+            out = torch.empty(nbytes, dtype=torch.uint8, device=img.device)
+        assert out.is_cuda and out.numel() >= nbytes and out.is_contiguous()
+        with torch.cuda.device(img.device):
+            lib().itwSetStream(torch.cuda.current_stream(img.device).cuda_stream)
+            lib().itwCompressNormalMapBC5(C.byref(RgbaSurface(img.data_ptr(), w, h, img.stride(0))), out.data_ptr(), ops)
+        return out
+    import numpy as np
+    assert img.ndim == 3 and img.shape[2] == 4 and img.dtype == np.uint8 and img.strides[2] == 1 and img.strides[1] == 4
+    if out is None:
+        out = np.empty(nbytes, dtype=np.uint8)
+    lib().itwCompressNormalMapBC5(C.byref(RgbaSurface(img.ctypes.data, w, h, img.strides[0])), out.ctypes.data, ops)
+    return out
+
+
+def cube_cross_faces(img):
+    """itwCubeCrossFaces: the six faces (+X -X +Y -Y +Z -Z) of a horizontal (4 x 3 cells) or vertical (3 x 4, width < height) cube cross as
+    VIEWS into `img` (numpy array or torch tensor (H, W, 4), uint8 or 2-byte half texels): no copy, no rotation.  The views feed
+    compress_chain directly."""
+    es = img.element_size() if hasattr(img, "data_ptr") else img.itemsize
+    row = (img.stride(0) * es) if hasattr(img, "data_ptr") else img.strides[0]
+    base = img.data_ptr() if hasattr(img, "data_ptr") else img.ctypes.data
+    faces = (RgbaSurface * 6)()
+    if lib().itwCubeCrossFaces(C.byref(RgbaSurface(base, img.shape[1], img.shape[0], row)), 4 * es, faces) != 0:
+        raise ValueError(f"not a cube cross: {img.shape[1]} x {img.shape[0]}")
+    views = []
+    for f in faces:
+        y, x = divmod(f.ptr - base, row)
+        x //= 4 * es
+        views.append(img[y:y + f.height, x:x + f.width])
+    return views
 
 
 def mip_chain(img):
