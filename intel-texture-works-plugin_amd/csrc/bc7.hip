@@ -26,7 +26,7 @@
 //     winners; the per-family search / finish kernel pairs of round 1 remain for ranked lists longer than 16 shapes.
 //     The slow profiles (every shape scanned) run the BOUNDED order instead (round 4: modes 1/3/7 last, only for the blocks an
 //     exact lower bound cannot exclude, compacted into lists) as two interleaved bands on two streams, and for the RGB
-//     profile a pilot kernel picks that order or the reference's per call, on the device (round 5; launch_bc7);
+//     profile a pilot kernel picks that order or the reference's per call, on the device (round 5; launch_rgb_bounded);
 //     under the RGB profile the list scan of that order fits only the (block, shape) pairs the bound leaves (PAIRS, above bc7_pair_scan):
 //     bc7_bounded_setup (counters, where the pairs go) -> bc7_scan_all {0,2} per band -> bc7_pilot_estimate -> bc7_finish_all<3> (modes 0,2,4,5,6,
 //     the 64 bounds once, the list, the compact texels and the pairs bucketed by shape) -> bc7_pair_scan -> bc7_finish_all<8> -> the full list
@@ -71,9 +71,7 @@ namespace itw {
 #include "bc7_f02_schedule.h"
 #undef BCN_TABLE_QUAL
 
-#ifndef ITW_BC7_LANE_PAL
-#define ITW_BC7_LANE_PAL 1                // per-lane shapes (refinement, ranked lists <= 16) through per-subset palettes in LDS (bc7_exact.hpp)
-#endif
+// per-lane shapes (refinement, ranked lists <= 16) go through per-subset palettes in LDS (bc7_exact.hpp)
 constexpr int LANE_PAL_LEVELS = 24;       // 3 subsets x 8 levels: the most one mode's refinement decodes (48 KiB per workgroup)
 constexpr int TPB = 256;                  // four waves share one staged seed table
 constexpr float INV255 = 1.0f / 255.0f;   // x/255f under fast-math = x*(1.f/255.f)
@@ -481,16 +479,10 @@ __device__ __forceinline__ void refine_and_commit(Lane& ln, Win& w, int iteratio
     uint32_t wqb[2];
     #pragma unroll
     for (int j = 0; j < 3; j++) for (int i = 0; i < 2; i++) for (int p = 0; p < 4; p++) cq[j][i][p] = 0;
-#if ITW_BC7_LANE_PAL
     constexpr int LEVELS = 1 << M.bits;
     const int32_t tt = block_norm2<M.ch>(ln.tx.pl);
-#endif
     {
-#if ITW_BC7_LANE_PAL
         PalSegment sg0[3];
-#else
-        Segment sg0[3];
-#endif
         #pragma unroll 1
         for (int j = 0; j < M.pairs; j++) {
             const SubsetMask s = subset_of(w.shape, j);       // (selecting among sm[0..2] here made the compiler index them in scratch)
@@ -501,11 +493,7 @@ __device__ __forceinline__ void refine_and_commit(Lane& ln, Win& w, int iteratio
             fit_line<M.ch>(ep, ln.tx, s.bits, st, ispc_rcp((float)s.n, ln.T), ln.T);
             int32_t q[2][4], d[2][4];
             quant_mode<MODE, true>(q, d, ep, M.ch);
-#if ITW_BC7_LANE_PAL
             const PalSegment sgj = build_palette<M.bits, M.ch, TPB>(ln.pal + j * (LEVELS * TPB), d);
-#else
-            const Segment sgj = make_segment<M.bits, M.ch>(d);
-#endif
             #pragma unroll
             for (int i = 0; i < 2; i++) for (int p = 0; p < 4; p++) {
                 if (j == 0) cq[0][i][p] = q[i][p]; else if (j == 1) cq[1][i][p] = q[i][p]; else cq[2][i][p] = q[i][p];
@@ -513,20 +501,12 @@ __device__ __forceinline__ void refine_and_commit(Lane& ln, Win& w, int iteratio
             if (j == 0) sg0[0] = sgj; else if (j == 1) sg0[1] = sgj; else sg0[2] = sgj;
         }
         if (M.pairs == 2) sg0[2] = sg0[1];
-#if ITW_BC7_LANE_PAL
         (void)select_block_lanes_pal<M.bits, M.ch, M.pairs, TPB, true>(wqb, ln.tx, sg0, ln.pal, sh.pattern, tt);
-#else
-        (void)select_block<M.bits, M.ch, M.pairs>(wqb, ln.tx, sg0, sh.pattern);
-#endif
     }
     for (int it = 0; it < iterations; it++) {
         ln.tx.fence();
         int32_t q[3][2][4];
-#if ITW_BC7_LANE_PAL
         PalSegment sg[3];
-#else
-        Segment sg[3];
-#endif
         #pragma unroll
         for (int j = 0; j < M.pairs; j++) {
             float ep[2][4];
@@ -534,19 +514,11 @@ __device__ __forceinline__ void refine_and_commit(Lane& ln, Win& w, int iteratio
             ep[0][3] = 0.f; ep[1][3] = 0.f;
             refit_line<M.bits, M.ch>(ep, ln.tx.pl, wqb, sm[j], ln.T);
             quant_mode<MODE, false>(q[j], d, ep, settings_channels);       // :1343 passes the profile's channel count
-#if ITW_BC7_LANE_PAL
             sg[j] = build_palette<M.bits, M.ch, TPB>(ln.pal + j * (LEVELS * TPB), d);
-#else
-            sg[j] = make_segment<M.bits, M.ch>(d);
-#endif
         }
         if (M.pairs == 2) sg[2] = sg[1];
         uint32_t qb[2];
-#if ITW_BC7_LANE_PAL
         const int32_t err = select_block_lanes_pal<M.bits, M.ch, M.pairs, TPB, true>(qb, ln.tx, sg, ln.pal, sh.pattern, tt);
-#else
-        const int32_t err = select_block<M.bits, M.ch, M.pairs>(qb, ln.tx, sg, sh.pattern);
-#endif
         const bool better = err < w.err;
         if (better) {
             #pragma unroll
@@ -773,7 +745,6 @@ __device__ __forceinline__ void search_two_subset(Lane& ln, const bc7_enc_settin
             ln.tx.fence();
             const int shape = prev & 63;
             const Shape sh = load_shape(shape);
-#if ITW_BC7_LANE_PAL
             if (RANKED == 2) {
                 // lists of at most 16 shapes (every preset): the candidate's subsets decode their palettes into the lane's LDS column
                 // (mode 1: 2 x 8 levels; mode 3 afterwards over the same stretch: 2 x 4) and the texels are scored through them
@@ -815,7 +786,6 @@ __device__ __forceinline__ void search_two_subset(Lane& ln, const bc7_enc_settin
                 }
                 continue;
             }
-#endif
             Segment sa[3], sc[3];
             IStats<FIT_CH> rest = full;
             #pragma unroll
@@ -1097,29 +1067,19 @@ __device__ __forceinline__ void mode_6(Lane& ln, const bc7_enc_settings& S)
     fit_line<CH>(ep, ln.tx, 0xffffu, st, rcp_of_count(16), ln.T);
     if (CH == 3) { ep[0][3] = 255.f; ep[1][3] = 255.f; }
     quant_mode<6, true>(q, d, ep, CH);
-#if ITW_BC7_LANE_PAL
     // the sixteen decoded colours once into the lane's LDS column, then one projection, one 16-byte read and two dot products
     // per texel instead of decoding both neighbouring levels with packed 16-bit math per texel (bc7_exact.hpp)
     const int32_t tt = block_norm2<CH>(ln.tx.pl);
     PalSegment ps = build_palette<4, CH, TPB>(ln.pal, d);
     int32_t err = select_block_pal<4, CH, TPB>(qb, ln.tx, ps, ln.pal, tt);
     (void)sg;
-#else
-    sg[0] = make_segment<4, CH>(d); sg[1] = sg[0]; sg[2] = sg[0];
-    int32_t err = select_block<4, CH, 1>(qb, ln.tx, sg, 0u);
-#endif
     const int iters = S.refineIterations[6];
     for (int it = 0; it < iters; it++) {
         const uint32_t was0 = qb[0], was1 = qb[1];
         refit_line<4, CH>(ep, ln.tx.pl, qb, all, ln.T);
         quant_mode<6, false>(q, d, ep, CH);
-#if ITW_BC7_LANE_PAL
         ps = build_palette<4, CH, TPB>(ln.pal, d);
         err = select_block_pal<4, CH, TPB>(qb, ln.tx, ps, ln.pal, tt);
-#else
-        sg[0] = make_segment<4, CH>(d);
-        err = select_block<4, CH, 1>(qb, ln.tx, sg, 0u);
-#endif
         if (__all(qb[0] == was0 && qb[1] == was1)) break;         // fixed point of the iteration (kernel.ispc:1672-1677)
     }
     if (err < ln.best_err) {
@@ -1216,7 +1176,7 @@ bc7_search_kernel(const uint8_t* __restrict__ src, int64_t stride, int32_t block
     __shared__ uint32_t s_seed32[2048];
     extern __shared__ int32_t s_keys[];            // 64 * TPB keys, only allocated for RANKED == 1
     // per-lane palettes: table-order scans 8 + 4 levels (24 KiB); ranked lists <= 16: 2 subsets x 8 levels (32 KiB); longer lists: none
-    __shared__ uint2 s_pal[RANKED == 0 ? 12 * TPB : (RANKED == 2 && ITW_BC7_LANE_PAL) ? 16 * TPB : 1];
+    __shared__ uint2 s_pal[RANKED == 0 ? 12 * TPB : RANKED == 2 ? 16 * TPB : 1];
     Lane ln;
     ln.T = stage_seed_tables_fast(s_seed16, s_seed32, threadIdx.x, TPB);
     __syncthreads();
@@ -1224,7 +1184,7 @@ bc7_search_kernel(const uint8_t* __restrict__ src, int64_t stride, int32_t block
     const bool live = gid < nblocks;
     const int32_t b = live ? gid : nblocks - 1;    // idle lanes of the last workgroup redo its last block, store nothing
     ln.keys = s_keys + threadIdx.x;
-    ln.pal = s_pal + ((RANKED == 0 || (RANKED == 2 && ITW_BC7_LANE_PAL)) ? threadIdx.x : 0);
+    ln.pal = s_pal + ((RANKED == 0 || RANKED == 2) ? threadIdx.x : 0);
     load_block<VEC16>(ln.tx, src, stride, blocks_x, b);
 
     Win wa, wb;
@@ -1248,7 +1208,7 @@ bc7_finish_kernel(const uint8_t* __restrict__ src, int64_t stride, int32_t block
     __shared__ unsigned short s_seed16[2048];
     __shared__ uint32_t s_seed32[2048];
     // mode 4/5 vector part: one palette per lane (16 KiB); refinement of a family's winners: one per subset (pairs x levels)
-    __shared__ uint2 s_pal[FAMILY == F_MODES456 ? (ITW_BC7_LANE_PAL ? 16 : 8) * TPB : (ITW_BC7_LANE_PAL ? (FAMILY == F_MODES02 ? 24 : 16) * TPB : 1)];
+    __shared__ uint2 s_pal[(FAMILY == F_MODES02 ? 24 : 16) * TPB];
     Lane ln;
     ln.T = stage_seed_tables_fast(s_seed16, s_seed32, threadIdx.x, TPB);
     __syncthreads();
@@ -1256,7 +1216,7 @@ bc7_finish_kernel(const uint8_t* __restrict__ src, int64_t stride, int32_t block
     const bool live = gid < nblocks;
     const int32_t b = live ? gid : nblocks - 1;
     ln.keys = nullptr;
-    ln.pal = s_pal + ((FAMILY == F_MODES456 || ITW_BC7_LANE_PAL) ? threadIdx.x : 0);
+    ln.pal = s_pal + threadIdx.x;
     load_block<VEC16>(ln.tx, src, stride, blocks_x, b);
 
     ln.best_err = first ? ERR_MAX : err_ws[b];
@@ -1392,6 +1352,17 @@ constexpr int PAIR_CTR_OVERFLOW = 64, PAIR_CTR_REDO = 65, PAIR_CTR_LIST = 66, PA
 struct PairTarget { PairRegion P; int32_t* redo; };
 static_assert(sizeof(PairTarget) <= (PAIR_CTR_WORDS - PAIR_CTR_TARGET) * sizeof(int32_t) && PAIR_CTR_TARGET % 2 == 0 && PAIR_CTR_WORDS % 4 == 0, "PairTarget behind the counters");
 constexpr int PAIR_MAX_PER_BLOCK = 32;
+// The call's counter block (FusedLayout::counts): CTR_WORDS words that the call's setup clears, then both bands' pair counters (PAIR_CTR_WORDS each).
+// A band keeps three consecutive list lengths: of the RGBA profiles' block lists (where an RGB mode, modes 1/3, mode 7 can win), or -- the RGB bounded
+// order -- of its three rotation lists.  Band 1's triple is the same words in either order; a call without bands uses band 0's.
+constexpr int CTR_LIST_RGB = 0, CTR_LIST_13 = 1, CTR_LIST_7 = 2;    // band 0 of the alpha-first orders (band 1: CTR_BAND1 + the same)
+constexpr int CTR_ROT = 3;                                          // band 0's rotation lists [3] (band 1: CTR_BAND1)
+constexpr int CTR_PILOT_FLAG = 6;                                   // the pilot's verdict
+constexpr int CTR_PILOT = 8;                                        // the pilot's counters [3]:
+constexpr int PILOT_LISTED = 0, PILOT_SAMPLED = 1, PILOT_DONE = 2;  //   blocks its estimate lists, blocks it looked at, workgroups done
+constexpr int CTR_BAND1 = 11;                                       // band 1's three list lengths
+constexpr int CTR_WORDS = 16;
+static_assert(CTR_ROT + 3 <= CTR_PILOT_FLAG && CTR_PILOT + 3 <= CTR_BAND1 && CTR_BAND1 + 3 <= CTR_WORDS, "the counter words do not overlap");
 // ROT TASKS (bc7_rot_tasks' header).  Per band: three rotation lists of `cap` block ids, their lengths (three consecutive words the call's
 // setup clears), and a payload slot per (rotation, list position); per block of the surface one merged word
 //   error << 32 | mode 5 << 31 | rotation << 29 | list position        (~0: no candidate)
@@ -1404,7 +1375,7 @@ constexpr unsigned long long PAIR_WORD_HEAVY = ~0ull - 1ull;        // no merged
 
 struct ScanTasks { int n; int kind[3]; };      // WK_SCAN02 / WK_SCAN13 / WK_SCAN7 in launch order
 
-// Round 5, the BANDS and the PILOT of the bounded order (launch_bc7): which chunks (runs of TPB blocks) of the surface a launch of
+// Round 5, the BANDS and the PILOT of the bounded order (launch_rgb_bounded, launch_alpha_first_bounded7): which chunks (runs of TPB blocks) of the surface a launch of
 // bc7_scan_all / bc7_finish_all walks, and whether it runs at all.
 //   kind 0  every chunk: workgroup i -> chunk i
 //   kind 2  every eighth chunk (8 i + 3): what bc7_pilot_estimate looks at, for a probe that scans nothing else
@@ -1434,7 +1405,7 @@ bc7_scan_all(const uint8_t* __restrict__ src, int64_t stride, int32_t blocks_x, 
 {
     __shared__ unsigned short s_seed16[2048];
     __shared__ uint32_t s_seed32[2048];
-    __shared__ uint2 s_pal[((RANKED_LISTS && ITW_BC7_LANE_PAL) ? 16 : 12) * TPB];   // ranked lists: 2 subsets x 8 levels (3 waves per SIMD: 3 x 44 KiB)
+    __shared__ uint2 s_pal[(RANKED_LISTS ? 16 : 12) * TPB];   // ranked lists: 2 subsets x 8 levels (3 waves per SIMD: 3 x 44 KiB)
     if (sel.gate && *sel.gate != sel.want) return;                  // the pilot chose the other order (whole grid: no barrier is pending)
     if (!RANKED_LISTS && split) {
         // bounded order: modes 1/3 (or mode 7: FAM7) over the list bc7_finish_all<.., 3 | 5 | 6> left, each listed block's 64 shapes cut
@@ -1588,7 +1559,7 @@ bc7_finish_all(const uint8_t* __restrict__ src, int64_t stride, int32_t blocks_x
     constexpr bool DO456 = PHASE == 0 || PHASE == 1 || PHASE == 3 || PHASE == 6;
     __shared__ unsigned short s_seed16[2048];
     __shared__ uint32_t s_seed32[2048];
-    __shared__ uint2 s_pal[(ITW_BC7_LANE_PAL ? LANE_PAL_LEVELS : 8) * TPB];   // refinement: a palette per subset of the lane's winner
+    __shared__ uint2 s_pal[LANE_PAL_LEVELS * TPB];   // refinement: a palette per subset of the lane's winner
     __shared__ int32_t s_at[TAIL3 ? TPB / 64 : 1][64];             // PAIRS: per (wave, shape) the survivors, then where they go in the bucket (its own
                                                                     // kilobyte: other waves of the workgroup still use s_pal when the first one gets here)
     if (sel.gate && *sel.gate != sel.want) return;                   // the pilot chose the other order (whole grid: no barrier is pending)
@@ -1734,7 +1705,7 @@ bc7_finish_all(const uint8_t* __restrict__ src, int64_t stride, int32_t blocks_x
         // PAIRS (header above bc7_pair_scan): this launch also leaves the (block, shape) pairs of the listed blocks, so every shape is
         // bounded for every lane -- no early exit, no bail -- and the lane keeps a bit per shape instead of `need` alone
         // CONTRACT of PHASE 3: `out_count` is word PAIR_CTR_LIST of a band's counter block that bc7_bounded_setup has filled in this call, so the
-        // band's PairTarget lies PAIR_CTR_TARGET - PAIR_CTR_LIST words behind it (launch_bc7's `finish` refuses any other pointer)
+        // band's PairTarget lies PAIR_CTR_TARGET - PAIR_CTR_LIST words behind it (the launcher's `finish` refuses any other pointer)
         const PairTarget* target = nullptr;
         if (TAIL3) target = reinterpret_cast<const PairTarget*>(out_count + (PAIR_CTR_TARGET - PAIR_CTR_LIST));
         const bool pairs = TAIL3 && target->P.words != nullptr;      // grid-uniform
@@ -1855,31 +1826,31 @@ bc7_pilot_estimate(const uint8_t* __restrict__ src, int64_t stride, int32_t bloc
             need = need || !(two_subset_bound(shape, tx.pl, full) >= lim);
         }
         const unsigned long long ml = __ballot(live && need), mt = __ballot(live);
-        if ((threadIdx.x & 63u) == 0u) { atomicAdd(counters + 0, (int32_t)__popcll(ml)); atomicAdd(counters + 1, (int32_t)__popcll(mt)); }
+        if ((threadIdx.x & 63u) == 0u) { atomicAdd(counters + PILOT_LISTED, (int32_t)__popcll(ml)); atomicAdd(counters + PILOT_SAMPLED, (int32_t)__popcll(mt)); }
     }
     __syncthreads();
     if (threadIdx.x == 0) {
         __threadfence();
-        if (atomicAdd(counters + 2, 1) == (int32_t)gridDim.x - 1) {  // the last workgroup: every count has arrived
+        if (atomicAdd(counters + PILOT_DONE, 1) == (int32_t)gridDim.x - 1) {  // the last workgroup: every count has arrived
             __threadfence();
-            const int64_t listed = atomicAdd(counters + 0, 0), sampled = atomicAdd(counters + 1, 0);
+            const int64_t listed = atomicAdd(counters + PILOT_LISTED, 0), sampled = atomicAdd(counters + PILOT_SAMPLED, 0);
             *flag = (listed * 256 <= (int64_t)thr256 * sampled) ? 1 : 0;
             if (host_counts) { host_counts[0] = (int32_t)listed; host_counts[1] = (int32_t)sampled; __threadfence_system(); }
         }
     }
 }
 
-// start of an RGB bounded call: the list lengths, the pilot's words and both bands' pair counters start at zero (`counters`: 16 words, then
+// start of an RGB bounded call: the list lengths, the pilot's words and both bands' pair counters start at zero (`counters`: CTR_WORDS words, then
 // PAIR_CTR_WORDS per band), and each band's PairTarget goes behind its pair counters
 __global__ void __launch_bounds__(TPB) bc7_bounded_setup(int32_t* __restrict__ counters, const PairTarget t0, const PairTarget t1)
 {
-    for (int i = (int)threadIdx.x; i < 16 + 2 * PAIR_CTR_WORDS; i += TPB) {
-        const int j = i < 16 ? 0 : (i - 16) % PAIR_CTR_WORDS;
-        if (i < 16 || j < PAIR_CTR_TARGET) counters[i] = 0;
+    for (int i = (int)threadIdx.x; i < CTR_WORDS + 2 * PAIR_CTR_WORDS; i += TPB) {
+        const int j = i < CTR_WORDS ? 0 : (i - CTR_WORDS) % PAIR_CTR_WORDS;
+        if (i < CTR_WORDS || j < PAIR_CTR_TARGET) counters[i] = 0;
     }
     if (threadIdx.x == 0) {
-        *reinterpret_cast<PairTarget*>(counters + 16 + PAIR_CTR_TARGET) = t0;
-        *reinterpret_cast<PairTarget*>(counters + 16 + PAIR_CTR_WORDS + PAIR_CTR_TARGET) = t1;
+        *reinterpret_cast<PairTarget*>(counters + CTR_WORDS + PAIR_CTR_TARGET) = t0;
+        *reinterpret_cast<PairTarget*>(counters + CTR_WORDS + PAIR_CTR_WORDS + PAIR_CTR_TARGET) = t1;
     }
 }
 
@@ -2121,7 +2092,7 @@ bc7_wide_phase1(const uint8_t* __restrict__ src, int64_t stride, int32_t blocks_
     const WideDims dims{nblocks, pstride};
     __shared__ unsigned short s_seed16[2048];
     __shared__ uint32_t s_seed32[2048];
-    __shared__ uint2 s_pal[((RANKED_LISTS && ITW_BC7_LANE_PAL) ? 16 : 12) * TPB];
+    __shared__ uint2 s_pal[(RANKED_LISTS ? 16 : 12) * TPB];
     Lane ln;
     ln.T = stage_seed_tables_fast(s_seed16, s_seed32, threadIdx.x, TPB);
     __syncthreads();
@@ -2166,7 +2137,7 @@ bc7_wide_phase2(const uint8_t* __restrict__ src, int64_t stride, int32_t blocks_
     const WideDims dims{nblocks, pstride};
     __shared__ unsigned short s_seed16[2048];
     __shared__ uint32_t s_seed32[2048];
-    __shared__ uint2 s_pal[SINGLES ? (ITW_BC7_LANE_PAL ? 16 : 8) * TPB : (ITW_BC7_LANE_PAL ? LANE_PAL_LEVELS * TPB : 1)];   // mode 4/5 vector part, mode 6 (16 levels) / refinement palettes
+    __shared__ uint2 s_pal[(SINGLES ? 16 : LANE_PAL_LEVELS) * TPB];   // mode 4/5 vector part, mode 6 (16 levels) / refinement palettes
     Lane ln;
     ln.T = stage_seed_tables_fast(s_seed16, s_seed32, threadIdx.x, TPB);
     __syncthreads();
@@ -2174,7 +2145,7 @@ bc7_wide_phase2(const uint8_t* __restrict__ src, int64_t stride, int32_t blocks_
     const bool live = gid < nblocks;
     const int32_t b = live ? gid : nblocks - 1;
     ln.keys = nullptr;
-    ln.pal = s_pal + ((SINGLES || ITW_BC7_LANE_PAL) ? threadIdx.x : 0);
+    ln.pal = s_pal + threadIdx.x;
     load_block<VEC16>(ln.tx, src, stride, blocks_x, b);
     ln.best_err = ERR_MAX; ln.improved = false;
     ln.best[0] = ln.best[1] = ln.best[2] = ln.best[3] = 0u;
@@ -2240,18 +2211,20 @@ struct Bc7Launch {
     uint8_t* dst; int32_t* err; uint4* wins; bc7_enc_settings S; int first;
 };
 
+// A runtime bool as a std::bool_constant for a generic lambda: a kernel launch is written once, and both of its instances exist.
+template <class F> static void with_bool(bool b, F&& f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
+template <class F> static void with_bools(bool a, bool b, F&& f) { with_bool(a, [&](auto A) { with_bool(b, [&](auto B) { f(A, B); }); }); }
+
 template <int FAMILY, int RANKED>
 static void launch_search(const Bc7Launch& L)
 {
     const size_t lds = RANKED == 1 ? (size_t)64 * TPB * sizeof(int32_t) : 0;
-    if (L.vec) hipLaunchKernelGGL((bc7_search_kernel<FAMILY, RANKED, true>),  L.grid, dim3(TPB), lds, L.st, L.src, L.stride, L.bx, L.n, L.wins, L.S);
-    else       hipLaunchKernelGGL((bc7_search_kernel<FAMILY, RANKED, false>), L.grid, dim3(TPB), lds, L.st, L.src, L.stride, L.bx, L.n, L.wins, L.S);
+    with_bool(L.vec, [&](auto V) { hipLaunchKernelGGL((bc7_search_kernel<FAMILY, RANKED, decltype(V)::value>), L.grid, dim3(TPB), lds, L.st, L.src, L.stride, L.bx, L.n, L.wins, L.S); });
 }
 template <int FAMILY>
 static void launch_finish(Bc7Launch& L)
 {
-    if (L.vec) hipLaunchKernelGGL((bc7_finish_kernel<FAMILY, true>),  L.grid, dim3(TPB), 0, L.st, L.src, L.stride, L.bx, L.n, L.dst, L.err, L.wins, L.S, L.first);
-    else       hipLaunchKernelGGL((bc7_finish_kernel<FAMILY, false>), L.grid, dim3(TPB), 0, L.st, L.src, L.stride, L.bx, L.n, L.dst, L.err, L.wins, L.S, L.first);
+    with_bool(L.vec, [&](auto V) { hipLaunchKernelGGL((bc7_finish_kernel<FAMILY, decltype(V)::value>), L.grid, dim3(TPB), 0, L.st, L.src, L.stride, L.bx, L.n, L.dst, L.err, L.wins, L.S, L.first); });
     L.first = 0;
 }
 
@@ -2260,8 +2233,6 @@ static void launch_finish(Bc7Launch& L)
 #define ITW_BC7_WIDE_MAX_BLOCKS 262144
 #endif
 
-// 0 = by size, 1 = deep always, 2 = wide whenever it supports the settings (itwSetBc7Path / ITW_BC7_PATH=deep|wide:
-// tests and probes)
 #ifdef ITW_TEST_HOOKS
 // test hook (itwTestBc7TwoSubsetBounds, libispc_texcomp_test.so only): two_subset_bound of every two-subset shape of every block, out[block * 64 + shape]
 template <bool VEC16>
@@ -2286,8 +2257,7 @@ void launch_bc7_test_bounds(const uint8_t* src, int64_t stride, int width, int h
     if (n <= 0) return;
     const bool vec = ((reinterpret_cast<uintptr_t>(src) | (uintptr_t)stride) & 15) == 0;
     const dim3 grid((unsigned)((n + TPB - 1) / TPB));
-    if (vec) hipLaunchKernelGGL((bc7_test_bounds<true>),  grid, dim3(TPB), 0, st, src, stride, bx, (int32_t)n, out);
-    else     hipLaunchKernelGGL((bc7_test_bounds<false>), grid, dim3(TPB), 0, st, src, stride, bx, (int32_t)n, out);
+    with_bool(vec, [&](auto V) { hipLaunchKernelGGL((bc7_test_bounds<decltype(V)::value>), grid, dim3(TPB), 0, st, src, stride, bx, (int32_t)n, out); });
 }
 // test hook (itwTestBc7RotationBounds): rotation_bound of the three rotations of every block, out[block * 3 + rotation]
 template <bool VEC16>
@@ -2312,130 +2282,145 @@ void launch_bc7_test_rot_bounds(const uint8_t* src, int64_t stride, int width, i
     if (n <= 0) return;
     const bool vec = ((reinterpret_cast<uintptr_t>(src) | (uintptr_t)stride) & 15) == 0;
     const dim3 grid((unsigned)((n + TPB - 1) / TPB));
-    if (vec) hipLaunchKernelGGL((bc7_test_rot_bounds<true>),  grid, dim3(TPB), 0, st, src, stride, bx, (int32_t)n, out);
-    else     hipLaunchKernelGGL((bc7_test_rot_bounds<false>), grid, dim3(TPB), 0, st, src, stride, bx, (int32_t)n, out);
+    with_bool(vec, [&](auto V) { hipLaunchKernelGGL((bc7_test_rot_bounds<decltype(V)::value>), grid, dim3(TPB), 0, st, src, stride, bx, (int32_t)n, out); });
 }
 #endif // ITW_TEST_HOOKS
 
-static std::atomic<int> g_bc7_path{-1};
-static int bc7_path_override()
-{
-    int v = g_bc7_path.load(std::memory_order_relaxed);
-    if (v < 0) {
-        const char* e = std::getenv("ITW_BC7_PATH");
-        v = !e ? 0 : !std::strcmp(e, "deep") ? 1 : !std::strcmp(e, "wide") ? 2 : 0;
-        g_bc7_path.store(v, std::memory_order_relaxed);
-    }
-    return v;
-}
-void set_bc7_path(int v) { g_bc7_path.store(v == 1 || v == 2 ? v : 0, std::memory_order_relaxed); }
-bool bc7_staged_bands_ok()
-{
-    static const bool on = [] { const char* e = std::getenv("ITW_STAGED_BANDS"); return !(e && e[0] == '0'); }();
-    return on && bc7_path_override() != 2;
-}
-
-// RGBA profile with both groups of modes: the fused shape runs the alpha-capable modes first and skips the three-channel
-// modes where they cannot win (bc7_finish_all).  ITW_BC7_ALPHA_PRUNE=0: always the reference's order.
-// ITW_BC7_BOUND=0: modes 1/3 in the reference's place instead of last-and-bounded (same bytes; tools/gpu_env_matrix.sh runs both)
-static bool bc7_bounded_order()
-{
-    static const bool on = [] { const char* e = std::getenv("ITW_BC7_BOUND"); return !(e && e[0] == '0'); }();
-    return on;
-}
-// Round 5.  ITW_BC7_PILOT_THR: the pilot's threshold in percent of the blocks it looks at that its estimate lists for modes 1/3 -- at or below it the rest of
-// the surface takes the bounded order, above it the reference's; -1 = no pilot (always bounded), 0 = pilot, always the reference's order for the
-// rest, 100 = pilot, always bounded (tools/order_timing.py under each setting: profiles/history/r05/r05e_*).  Returned in 1/256.
+// ---- the environment switches: one table, one reader -------------------------------------------------------------------------
+//   ITW_BC7_PATH=deep|wide    force a path (tests and probes; itwSetBc7Path overrides it)
+//   ITW_STAGED_BANDS=0        the staged runs of a host-pointer call do not run as overlapped deep bands
+//   ITW_BC7_BOUND=0           modes 1/3 in the reference's place instead of last-and-bounded (same bytes; tools/gpu_env_matrix.sh runs both)
+//   ITW_BC7_PILOT_THR=<pct>   the pilot's threshold (bc7_pilot_threshold; itwSetBc7Pilot overrides it)
+//   ITW_BC7_PILOT_DEBUG=1     print the pilot's, the pair route's and the rotation lists' counters after a two-band call
+//   ITW_BC7_BANDS=1           one band on the caller's stream, no pilot (round 4's launch order); default 2
+//   ITW_BC7_COMPACT=0         the list scans gather their blocks from the surface (round 4) instead of reading the compact copy
+//   ITW_BC7_FUSED=0           the per-family kernels instead of the two-launch fused shape
+//   ITW_BC7_ALPHA_PRUNE=0     RGBA profiles: always the reference's order
+//   ITW_BC7_PAIRS=0           the RGB bounded order's list scan fits all 64 shapes of every listed block (round 4) instead of the (block, shape)
+//                             pairs the bound leaves (bc7_pair_scan's header)
+//   ITW_BC7_PAIR_CAP=<n>      lowers a shape bucket's capacity (never raises it): a small value forces the overflow route
+//   ITW_BC7_ROT_TASKS=0       modes 4/5 of the RGB bounded order inline in bc7_finish_all<3>, all nine candidates of every block, instead of the
+//                             (block, rotation) pairs a bound leaves (bc7_rot_tasks' header)
+// env_once: the process's first read holds (the workspace layout and the launch shape of later calls may depend on it).
+// env_every_call: read again at every call -- PAIRS, PAIR_CAP and ROT_TASKS, on which the workspace layout does not depend, so that one process
+// (the tests) can compare the routes.
+enum EnvKind { ENV_OFF_AT_0, ENV_ON_AT_1, ENV_NUMBER, ENV_PATH_NAME };
+enum EnvKey { ENV_PATH, ENV_STAGED_BANDS, ENV_BOUND, ENV_PILOT_THR, ENV_PILOT_DEBUG, ENV_BANDS, ENV_COMPACT, ENV_FUSED, ENV_ALPHA_PRUNE, ENV_PAIRS, ENV_PAIR_CAP,
+              ENV_ROT_TASKS, ENV_KEYS };
 #ifndef ITW_BC7_PILOT_THR_DEFAULT
 #define ITW_BC7_PILOT_THR_DEFAULT 90     // forced either way by content (profiles/history/r05/r05l_*): 74 % estimated -> bounded wins by 11 %, 91 % -> equal, 98 % -> reference order by 0.6 %
 #endif
-static std::atomic<int> g_bc7_pilot{-2};           // percent; -2 = not read yet
+struct EnvSwitch { const char* name; EnvKind kind; long unset; };
+static constexpr EnvSwitch ENV_SWITCHES[ENV_KEYS] = {
+    {"ITW_BC7_PATH", ENV_PATH_NAME, 0},      {"ITW_STAGED_BANDS", ENV_OFF_AT_0, 1}, {"ITW_BC7_BOUND", ENV_OFF_AT_0, 1},
+    {"ITW_BC7_PILOT_THR", ENV_NUMBER, ITW_BC7_PILOT_THR_DEFAULT},                   {"ITW_BC7_PILOT_DEBUG", ENV_ON_AT_1, 0},
+    {"ITW_BC7_BANDS", ENV_NUMBER, 2},        {"ITW_BC7_COMPACT", ENV_OFF_AT_0, 1},  {"ITW_BC7_FUSED", ENV_OFF_AT_0, 1},
+    {"ITW_BC7_ALPHA_PRUNE", ENV_OFF_AT_0, 1}, {"ITW_BC7_PAIRS", ENV_OFF_AT_0, 1},   {"ITW_BC7_PAIR_CAP", ENV_NUMBER, 0},
+    {"ITW_BC7_ROT_TASKS", ENV_OFF_AT_0, 1},
+};
+static long env_every_call(EnvKey k)
+{
+    const EnvSwitch& sw = ENV_SWITCHES[k];
+    const char* e = std::getenv(sw.name);
+    if (!e) return sw.unset;
+    if (sw.kind == ENV_NUMBER) return std::atol(e);
+    if (sw.kind == ENV_PATH_NAME) return !std::strcmp(e, "deep") ? 1 : !std::strcmp(e, "wide") ? 2 : 0;
+    return sw.kind == ENV_OFF_AT_0 ? e[0] != '0' : e[0] == '1';
+}
+static long env_once(EnvKey k)
+{
+    static std::atomic<long long> seen[ENV_KEYS];                // 0 = not read yet, else value * 2 + 1
+    long long v = seen[k].load(std::memory_order_relaxed);
+    if (v == 0) seen[k].store(v = (long long)env_every_call(k) * 2 + 1, std::memory_order_relaxed);
+    return (long)((v - 1) / 2);
+}
+
+// 0 = by size, 1 = deep always, 2 = wide whenever it supports the settings (itwSetBc7Path / ITW_BC7_PATH=deep|wide: tests and probes)
+static std::atomic<int> g_bc7_path{-1};            // -1 = not set: the environment's
+static int bc7_path_override()
+{
+    const int v = g_bc7_path.load(std::memory_order_relaxed);
+    return v < 0 ? (int)env_once(ENV_PATH) : v;
+}
+void set_bc7_path(int v) { g_bc7_path.store(v == 1 || v == 2 ? v : 0, std::memory_order_relaxed); }
+bool bc7_staged_bands_ok() { return env_once(ENV_STAGED_BANDS) && bc7_path_override() != 2; }
+
+// Round 5.  ITW_BC7_PILOT_THR: the pilot's threshold in percent of the blocks it looks at that its estimate lists for modes 1/3 -- at or below it the rest of
+// the surface takes the bounded order, above it the reference's; -1 = no pilot (always bounded), 0 = pilot, always the reference's order for the
+// rest, 100 = pilot, always bounded (tools/order_timing.py under each setting: profiles/history/r05/r05e_*).  Returned in 1/256.
+static std::atomic<int> g_bc7_pilot{-2};           // percent; -2 = not set: the environment's
 static int bc7_pilot_threshold()
 {
-    int pct = g_bc7_pilot.load(std::memory_order_relaxed);
-    if (pct == -2) {
-        const char* e = std::getenv("ITW_BC7_PILOT_THR");
-        pct = e ? std::atoi(e) : ITW_BC7_PILOT_THR_DEFAULT;
-        pct = pct < 0 ? -1 : (pct > 100 ? 100 : pct);
-        g_bc7_pilot.store(pct, std::memory_order_relaxed);
-    }
-    return pct < 0 ? -1 : pct * 256 / 100;
+    const int set = g_bc7_pilot.load(std::memory_order_relaxed);
+    const long pct = set == -2 ? env_once(ENV_PILOT_THR) : set;
+    return pct < 0 ? -1 : (int)(pct > 100 ? 100 : pct) * 256 / 100;
 }
 void set_bc7_pilot(int percent) { g_bc7_pilot.store(percent < -1 ? -2 : (percent > 100 ? 100 : percent), std::memory_order_relaxed); }   // < -1: back to ITW_BC7_PILOT_THR / the default
-static bool bc7_pilot_debug()
-{
-    static const bool on = [] { const char* e = std::getenv("ITW_BC7_PILOT_DEBUG"); return e && e[0] == '1'; }();
-    return on;
-}
-// ITW_BC7_BANDS=1: one band on the caller's stream, no pilot (round 4's launch order); default 2
-static int bc7_bands()
-{
-    static const int k = [] { const char* e = std::getenv("ITW_BC7_BANDS"); const int v = e ? std::atoi(e) : 2; return v < 2 ? 1 : 2; }();
-    return k;
-}
-// ITW_BC7_COMPACT=0: the list scans gather their blocks from the surface (round 4) instead of reading the compact copy
-static bool bc7_compact_lists()
-{
-    static const bool on = [] { const char* e = std::getenv("ITW_BC7_COMPACT"); return !(e && e[0] == '0'); }();
-    return on;
-}
-// ITW_BC7_PAIRS=0: the RGB bounded order's list scan fits all 64 shapes of every listed block (round 4) instead of the (block, shape) pairs
-// the bound leaves (bc7_pair_scan's header).  ITW_BC7_PAIR_CAP=<n>: lowers a shape bucket's capacity (never raises it): a small value forces the
-// overflow route.  Both are read at every call -- the workspace layout does not depend on them -- so one process can compare the routes.
-static bool bc7_pairs_on()
-{
-    const char* e = std::getenv("ITW_BC7_PAIRS");
-    return !(e && e[0] == '0');
-}
-// ITW_BC7_ROT_TASKS=0: modes 4/5 of the RGB bounded order inline in bc7_finish_all<3>, all nine candidates of every block, instead of the (block, rotation)
-// pairs a bound leaves (bc7_rot_tasks' header).  Read at every call; the workspace layout does not depend on it.
-static bool bc7_rot_tasks_on()
-{
-    const char* e = std::getenv("ITW_BC7_ROT_TASKS");
-    return !(e && e[0] == '0');
-}
+static int bc7_bands() { return env_once(ENV_BANDS) < 2 ? 1 : 2; }
 static int32_t bc7_pair_cap(int32_t layout_cap)
 {
-    const char* e = std::getenv("ITW_BC7_PAIR_CAP");
-    const long v = e ? std::atol(e) : 0;
+    const long v = env_every_call(ENV_PAIR_CAP);
     return (v > 0 && v < layout_cap) ? (int32_t)v : layout_cap;
 }
-static bool bc7_fused_on()
+
+// ---- what a call's settings switch on: read once, here ---------------------------------------------------------------------------
+// A list length (fastSkipTreshold_mode*) is RANKED when it is a proper prefix of the shape ranking (1..63: the scan computes the 64 keys and
+// fits the best few); LONG when it is ranked and longer than 16 (the keys then live in 64 KiB of LDS: the per-family kernels only).
+// The three orders a call can take instead of the reference's {0,2} -> {1,3} -> {7} -> {4,5} -> {6}:
+//   alpha_first  RGBA profile with both groups of modes: the alpha-capable modes first, the three-channel modes skipped where they cannot win
+//                (bc7_finish_all's header)
+//   bounded      modes 1/3 last and only where an exact bound cannot exclude them: profiles whose modes 1/3 scan every shape -- a ranked list
+//                already spends a bound's worth of arithmetic per shape on its keys and then fits a few shapes only
+//   rgb_bounded  the bounded order of the RGB profiles (`slow`): the one with bands' pair and rotation routes and a pilot's verdict
+struct Bc7Modes {
+    bool on02, on13, on7, on45, on6;
+    bool r13, r7, long13, long7;
+    int len1, len3, len7, channels;
+    bool alpha_first, bounded, rgb_bounded;
+    bool any() const { return on02 || on13 || on7 || on45 || on6; }
+};
+static Bc7Modes bc7_modes(const bc7_enc_settings& S)
 {
-    static const bool on = [] { const char* e = std::getenv("ITW_BC7_FUSED"); return !(e && e[0] == '0'); }();
-    return on;
+    auto ranked = [](int t) { return t > 0 && t < 64; };
+    Bc7Modes M;
+    M.channels = S.channels == 4 ? 4 : 3;
+    M.len1 = S.fastSkipTreshold_mode1; M.len3 = S.fastSkipTreshold_mode3; M.len7 = S.fastSkipTreshold_mode7;
+    M.on02 = S.mode_selection[0]; M.on45 = S.mode_selection[2]; M.on6 = S.mode_selection[3];
+    M.on13 = S.mode_selection[1] && (M.len1 > 0 || M.len3 > 0);
+    M.on7 = S.mode_selection[1] && M.len7 > 0;
+    M.r13 = M.on13 && (ranked(M.len1) || ranked(M.len3));
+    M.long13 = M.r13 && (M.len1 > 16 || M.len3 > 16);
+    M.r7 = M.on7 && ranked(M.len7);
+    M.long7 = M.r7 && M.len7 > 16;
+    M.alpha_first = env_once(ENV_ALPHA_PRUNE) && M.channels == 4 && (M.on02 || M.on13) && (M.on7 || M.on45 || M.on6);
+    M.bounded = env_once(ENV_BOUND) && M.on02 && M.on13 && !M.r13;
+    M.rgb_bounded = M.bounded && !M.alpha_first && !M.on7;
+    return M;
 }
-static bool bc7_alpha_first(const bc7_enc_settings& S)
-{
-    static const bool on = [] { const char* e = std::getenv("ITW_BC7_ALPHA_PRUNE"); return !(e && e[0] == '0'); }();
-    const bool on02 = S.mode_selection[0];
-    const bool on13 = S.mode_selection[1] && (S.fastSkipTreshold_mode1 > 0 || S.fastSkipTreshold_mode3 > 0);
-    const bool on7 = S.mode_selection[1] && S.fastSkipTreshold_mode7 > 0;
-    return on && S.channels == 4 && (on02 || on13) && (on7 || S.mode_selection[2] || S.mode_selection[3]);
-}
+
 // Above this many blocks an alpha-first call takes the fused shape even where the wide one is allowed: on translucent
 // content it is 1.3-2.3x faster from 65536 blocks up, on opaque content (nothing to skip) at most 8 % slower from here
 // (tools/bc7_path_probe.py, profiles/r02c_bc7_path_probe.txt vs r02b: alpha_basic 131072 blocks 0.361 / 0.758 vs 0.681 ms wide)
 #define ITW_BC7_WIDE_MAX_BLOCKS_ALPHA_FIRST 131072
 
-static bool bc7_use_wide(int64_t n, const bc7_enc_settings& S, int64_t wide_max)
+// the most blocks a call may have to take the wide path (-1: none): the forced path, else the caller's limit (0 = the library's), within the
+// workspace bound of the wide layout (1.6 GB)
+static int64_t bc7_wide_block_limit(int64_t wide_max)
 {
-    // lists longer than 16 that are proper prefixes of the ranking keep their keys in 64 KiB of LDS: deep path only
-    auto long_ranked = [](int t) { return t > 16 && t < 64; };
-    if (S.mode_selection[1] && (long_ranked(S.fastSkipTreshold_mode1) || long_ranked(S.fastSkipTreshold_mode3) || long_ranked(S.fastSkipTreshold_mode7))) return false;
-    // the wide ranked scan keeps the 16 smallest keys in registers: a family with a ranked list needs all its lists <= 16
-    auto ranked = [](int t) { return t > 0 && t < 64; };
-    if (S.mode_selection[1]) {
-        const int a = S.fastSkipTreshold_mode1, c = S.fastSkipTreshold_mode3;
-        if ((ranked(a) || ranked(c)) && (a > 16 || c > 16)) return false;
-    }
-    if (S.mode45_channel0 < 0 || S.mode45_channel0 > 3) return false;
+    const int64_t hard_cap = (int64_t)1 << 20;
     const int o = bc7_path_override();
-    if (o == 1) return false;
-    const int64_t hard_cap = (int64_t)1 << 20;                   // workspace bound of the wide layout (1.6 GB)
-    if (o == 2) return n <= hard_cap;
-    if (n >= ITW_BC7_WIDE_MAX_BLOCKS_ALPHA_FIRST && bc7_alpha_first(S)) return false;
-    return n <= (wide_max > 0 ? (wide_max < hard_cap ? wide_max : hard_cap) : ITW_BC7_WIDE_MAX_BLOCKS);
+    if (o == 1) return -1;
+    if (o == 2) return hard_cap;
+    const int64_t limit = wide_max > 0 ? wide_max : ITW_BC7_WIDE_MAX_BLOCKS;
+    return limit < hard_cap ? limit : hard_cap;
+}
+static bool bc7_use_wide(int64_t n, const bc7_enc_settings& S, const Bc7Modes& M, int64_t wide_max)
+{
+    // the wide ranked scan keeps the 16 smallest keys in registers: a family with a ranked list needs all its lists <= 16
+    const bool lists_ok = !M.long13 && !M.long7;
+    const bool rotations_ok = S.mode45_channel0 >= 0 && S.mode45_channel0 <= 3;
+    const bool fused_pays = bc7_path_override() == 0 && n >= ITW_BC7_WIDE_MAX_BLOCKS_ALPHA_FIRST && M.alpha_first;     // (where the size decides)
+    return lists_ok && rotations_ok && !fused_pays && n <= bc7_wide_block_limit(wide_max);
 }
 
 // deep: best error so far (4 B/block) + the winners of one family's two modes (2 x 16 B/block)
@@ -2450,7 +2435,7 @@ static size_t wide_workspace_bytes(size_t n)
 // a list of blocks for modes 1/3 with what its split scan and refinement need: block ids [cap], winners of the scan's shares [5 rows][cap]
 // (rows 2, 3 used: list_scan_parts x listed <= cap), the listed blocks' texels [cap] x 64 B in list order
 // pairs (bc7_pair_scan's header): per band the merged words [cap] x 2 x 8 B, the second list [cap], 64 shape buckets of cap / 8 listed slots and (behind the
-// 16 counters) PAIR_CTR_WORDS counters; each kind's two halves are contiguous, so a call without bands uses them as one
+// CTR_WORDS counters) PAIR_CTR_WORDS counters; each kind's two halves are contiguous, so a call without bands uses them as one
 // rot tasks (bc7_rot_tasks' header): per band three rotation lists [3][cap] and their payload slots [3][cap] x 16 B, per block of the surface one merged
 // word of 8 B: 68 B per block in all; each kind's two halves are contiguous again
 struct ListRegion { size_t list, wins, compact, cap, pair_words, pair_redo, pair_buckets, pair_ctr, pair_cap, rot_lists, rot_payload; };
@@ -2462,19 +2447,10 @@ struct FusedLayout { size_t inc, list0, list1, list2, counts, words, rot_words; 
 //   pairs    the pair route's words, second lists and buckets (the RGB bounded order only, whatever ITW_BC7_PAIRS says);
 //   rot      the rotation lists, merged words and payload slots of modes 4/5 (the same calls with three channels, whatever ITW_BC7_ROT_TASKS says).
 struct FusedNeeds { bool lists, bands, compact, pairs, rot; };
-static FusedNeeds fused_needs(const bc7_enc_settings* s)
+static FusedNeeds fused_needs(const Bc7Modes& M)
 {
-    if (!s) return FusedNeeds{true, true, true, true, true};                  // unknown settings: everything
-    bc7_enc_settings S = *s;
-    S.channels = (s->channels == 4) ? 4 : 3;
-    auto ranked = [](int t) { return t > 0 && t < 64; };
-    const bool on02 = S.mode_selection[0];
-    const bool on13 = S.mode_selection[1] && (S.fastSkipTreshold_mode1 > 0 || S.fastSkipTreshold_mode3 > 0);
-    const bool r13 = on13 && (ranked(S.fastSkipTreshold_mode1) || ranked(S.fastSkipTreshold_mode3));
-    const bool bounded = bc7_bounded_order() && on02 && on13 && !r13;
-    const bool alpha = bc7_alpha_first(S);
-    const bool on7 = S.mode_selection[1] && S.fastSkipTreshold_mode7 > 0;
-    return FusedNeeds{alpha || bounded, bounded, bounded && !alpha && bc7_compact_lists(), bounded && !alpha && !on7, bounded && !alpha && !on7 && S.channels == 3};
+    // (compact: sized with mode 7 on too, where no launch reads it)
+    return FusedNeeds{M.alpha_first || M.bounded, M.bounded, M.bounded && !M.alpha_first && env_once(ENV_COMPACT), M.rgb_bounded, M.rgb_bounded && M.channels == 3};
 }
 static FusedLayout fused_layout(size_t n, const FusedNeeds& need)
 {
@@ -2487,7 +2463,7 @@ static FusedLayout fused_layout(size_t n, const FusedNeeds& need)
     W.list0 = o;    o = up4(o + lcap);
     W.list1 = o;    o = up4(o + lcap);
     W.list2 = o;    o = up4(o + lcap);
-    W.counts = o;   o += 16;                                       // list lengths, the pilot's verdict
+    W.counts = o;   o += CTR_WORDS;                                // list lengths, the pilot's verdict
     for (int k = 0; k < 2; k++) { W.band[k].pair_ctr = o; o += PAIR_CTR_WORDS; }   // (contiguous with them: bc7_bounded_setup clears all of it)
     for (int k = 0; k < 2; k++) {                                  // the two bands: lists and share winners ...
         ListRegion& r = W.band[k];
@@ -2506,79 +2482,68 @@ static FusedLayout fused_layout(size_t n, const FusedNeeds& need)
     W.words = o;
     return W;
 }
-bool bc7_scans_every_shape(const bc7_enc_settings& s) { return fused_needs(&s).bands; }
+bool bc7_scans_every_shape(const bc7_enc_settings& s) { return bc7_modes(s).bounded; }
+// does a call with these settings run the bounded order of the RGB profiles (`slow`: the one order with a pilot)?  Only in the fused shape.
+static bool has_order_verdict(const Bc7Modes& M) { return env_once(ENV_FUSED) && M.rgb_bounded; }
+bool bc7_has_order_verdict(const bc7_enc_settings& s) { return has_order_verdict(bc7_modes(s)); }
 
 size_t bc7_workspace_bytes(int width, int height, int64_t wide_max_blocks, const bc7_enc_settings* settings)
 {
     const size_t n = (size_t)(width / 4) * (size_t)(height / 4);
     size_t deep = ((n * sizeof(int32_t) + 15) & ~(size_t)15) + 2 * n * sizeof(uint4);
-    const size_t fused = fused_layout(n, fused_needs(settings)).words * sizeof(uint32_t);
+    const FusedNeeds everything{true, true, true, true, true};                                  // unknown settings
+    const size_t fused = fused_layout(n, settings ? fused_needs(bc7_modes(*settings)) : everything).words * sizeof(uint32_t);
     if (fused > deep) deep = fused;
-    const size_t limit = bc7_path_override() == 2 ? ((size_t)1 << 20) : (wide_max_blocks > 0 ? (size_t)wide_max_blocks : (size_t)ITW_BC7_WIDE_MAX_BLOCKS);
-    const bool may_wide = bc7_path_override() != 1 && n <= limit && n <= ((size_t)1 << 20);
+    const bool may_wide = (int64_t)n <= bc7_wide_block_limit(wide_max_blocks);     // whatever the settings: they may change between sizing and launching
     const size_t wide = may_wide ? wide_workspace_bytes(n) : 0;
     return deep > wide ? deep : wide;
 }
 
-static void launch_bc7_wide(const uint8_t* src, int64_t stride, int bx, int64_t n, uint8_t* dst, const bc7_enc_settings& S, float* workspace,
-                            hipStream_t st, const Bc7Aux* aux)
+static void launch_bc7_wide(const Bc7Launch& L, const Bc7Modes& M, float* workspace, const Bc7Aux* aux)
 {
+    const uint8_t* src = L.src; const int64_t stride = L.stride, n = L.n; const int bx = L.bx; const bool vec = L.vec; hipStream_t st = L.st; const bc7_enc_settings& S = L.S;
     uint4* wins = reinterpret_cast<uint4*>(workspace);
     int32_t* cerr = reinterpret_cast<int32_t*>(wins + (size_t)5 * wide_win_entries((size_t)n));
     uint4* cblk = reinterpret_cast<uint4*>(reinterpret_cast<uint8_t*>(cerr) + (((size_t)WIDE_SLOTS * n * sizeof(int32_t) + 15) & ~(size_t)15));
-    const bool vec = ((reinterpret_cast<uintptr_t>(src) | (uintptr_t)stride | reinterpret_cast<uintptr_t>(dst)) & 15) == 0;
-    auto ranked = [](int t) { return t > 0 && t < 64; };
-
-    const bool on02 = S.mode_selection[0];
-    const bool on13 = S.mode_selection[1] && (S.fastSkipTreshold_mode1 > 0 || S.fastSkipTreshold_mode3 > 0);
-    const bool on7  = S.mode_selection[1] && S.fastSkipTreshold_mode7 > 0;
-    const bool on45 = S.mode_selection[2], on6 = S.mode_selection[3];
-    const int ranked13 = on13 && (ranked(S.fastSkipTreshold_mode1) || ranked(S.fastSkipTreshold_mode3));
-    const int ranked7 = on7 && ranked(S.fastSkipTreshold_mode7);
-    const bool any_ranked = ranked13 || ranked7;
+    const int ranked13 = M.r13, ranked7 = M.r7;
+    const bool any_ranked = M.r13 || M.r7;
 
     // parts per scan: as many waves as stay resident at once (1024 SIMDs x the scan kernel's waves), within what the
     // candidate lists offer
     const int64_t waves = (n + 63) / 64;
-    const int families = (on02 ? 1 : 0) + (on13 ? 1 : 0) + (on7 ? 1 : 0);
+    const int families = (M.on02 ? 1 : 0) + (M.on13 ? 1 : 0) + (M.on7 ? 1 : 0);
     const int resident = 1024 * (any_ranked ? 3 : WIDE_SCAN_WAVES);
     int want = 1;
     while (want < WIDE_MAX_PARTS && waves * families * want * WIDE_FILL_DIVISOR <= resident) want *= 2;
     auto cap = [&](int limit) { int p = want; while (p > limit) p /= 2; return p < 1 ? 1 : p; };
+    auto parts_of_ranked = [](int len) { return len >= 8 ? 4 : len >= 2 ? 2 : 1; };    // a ranked share recomputes the 64 keys: few parts
     const int p02 = cap(16);                                                        // 16 or 64 shapes
-    const int list13 = ranked13 ? (S.fastSkipTreshold_mode1 > S.fastSkipTreshold_mode3 ? S.fastSkipTreshold_mode1 : S.fastSkipTreshold_mode3) : 64;
-    const int p13 = cap(ranked13 ? (list13 >= 8 ? 4 : list13 >= 2 ? 2 : 1) : 16);   // a ranked share recomputes the 64 keys: few parts
-    const int list7 = ranked7 ? S.fastSkipTreshold_mode7 : 64;
-    const int p7 = cap(ranked7 ? (list7 >= 8 ? 4 : list7 >= 2 ? 2 : 1) : 16);
-    int pstride = 1;                                                               // rows of the winners array per mode
-    if (on02 && p02 > pstride) pstride = p02;
-    if (on13 && p13 > pstride) pstride = p13;
-    if (on7 && p7 > pstride) pstride = p7;
+    const int p13 = cap(M.r13 ? parts_of_ranked(M.len1 > M.len3 ? M.len1 : M.len3) : 16);
+    const int p7 = cap(M.r7 ? parts_of_ranked(M.len7) : 16);
+    auto larger = [](int a, int b) { return a > b ? a : b; };
+    const int pstride = larger(larger(M.on02 ? p02 : 1, M.on13 ? p13 : 1), M.on7 ? p7 : 1);      // rows of the winners array per mode
 
-    WideTasks T;
-    std::memset(&T, 0, sizeof T);
+    WideTasks T{};
     auto add = [&](int kind, int part, int parts) { T.kind[T.n] = (uint8_t)kind; T.part[T.n] = (uint8_t)part; T.parts[T.n] = (uint8_t)parts; T.n++; };
-    WideModes R, G;                                       // refine tasks (after the scans), single-subset tasks (independent)
-    std::memset(&R, 0, sizeof R);
-    std::memset(&G, 0, sizeof G);
+    WideModes R{}, G{};                                   // refine tasks (after the scans), single-subset tasks (independent)
     uint32_t active = 0;
     auto add_refine = [&](int mode, int parts) { R.mode[R.n] = (uint8_t)mode; R.parts[R.n] = (uint8_t)parts; R.n++; active |= 1u << wide_win_slot(mode); };
     auto add_single = [&](int code) { G.mode[G.n] = (uint8_t)code; G.parts[G.n] = 1; G.n++; };
     // longest tasks first: a launch drains in blockIdx order
-    if (on13) { for (int p = 0; p < p13; p++) add(WK_SCAN13, p, p13); if (S.fastSkipTreshold_mode1 > 0) add_refine(1, p13); if (S.fastSkipTreshold_mode3 > 0) add_refine(3, p13); }
-    if (on02) { for (int p = 0; p < p02; p++) add(WK_SCAN02, p, p02); add_refine(0, p02); if (!S.skip_mode2) add_refine(2, p02); }
-    if (on7)  { for (int p = 0; p < p7; p++) add(WK_SCAN7, p, p7); add_refine(7, p7); }
-    if (on45) {
+    if (M.on13) { for (int p = 0; p < p13; p++) add(WK_SCAN13, p, p13); if (M.len1 > 0) add_refine(1, p13); if (M.len3 > 0) add_refine(3, p13); }
+    if (M.on02) { for (int p = 0; p < p02; p++) add(WK_SCAN02, p, p02); add_refine(0, p02); if (!S.skip_mode2) add_refine(2, p02); }
+    if (M.on7)  { for (int p = 0; p < p7; p++) add(WK_SCAN7, p, p7); add_refine(7, p7); }
+    if (M.on45) {
         // one wave per rotation, or one per (rotation, candidate) while all those waves (2 per SIMD) stay resident at once
-        const int rots = (S.channels == 4 ? 4 : 3) - S.mode45_channel0;
-        const bool split = waves * (3 * rots + (on6 ? 1 : 0) + (aux ? 0 : R.n)) <= 2048;
-        for (int r = S.mode45_channel0; r < (S.channels == 4 ? 4 : 3); r++) {
+        const int rots = M.channels - S.mode45_channel0;
+        const bool split = waves * (3 * rots + (M.on6 ? 1 : 0) + (aux ? 0 : R.n)) <= 2048;
+        for (int r = S.mode45_channel0; r < M.channels; r++) {
             if (split) { for (int c = 0; c < 3; c++) add_single(100 + 4 * r + c); active |= 3u << (WIDE_SLOT_M4 + 2 * r); }
             else       { add_single(100 + 4 * r + 3); active |= 1u << (WIDE_SLOT_M4 + 2 * r); }
             active |= 1u << (WIDE_SLOT_M5 + r);
         }
     }
-    if (on6)  { add_single(6); active |= 1u << WIDE_SLOT_M6; }
+    if (M.on6)  { add_single(6); active |= 1u << WIDE_SLOT_M6; }
 
     const unsigned gx = (unsigned)((n + TPB - 1) / TPB);
     const dim3 blk(TPB);
@@ -2589,345 +2554,387 @@ static void launch_bc7_wide(const uint8_t* src, int64_t stride, int bx, int64_t 
         (void)hipStreamWaitEvent(aux->stream, aux->fork, 0);
         gs = aux->stream;
     }
+    auto phase2 = [&](auto singles, const WideModes& tasks, hipStream_t s) {
+        with_bool(vec, [&](auto V) {
+            hipLaunchKernelGGL((bc7_wide_phase2<decltype(V)::value, decltype(singles)::value>), dim3(gx, (unsigned)tasks.n), blk, 0, s, src, stride, bx, (int32_t)n, wins, cerr, cblk, S,
+                               tasks, pstride);
+        });
+    };
     if (G.n > 0) {
-        if (vec) hipLaunchKernelGGL((bc7_wide_phase2<true, true>),  dim3(gx, (unsigned)G.n), blk, 0, gs, src, stride, bx, (int32_t)n, wins, cerr, cblk, S, G, pstride);
-        else     hipLaunchKernelGGL((bc7_wide_phase2<false, true>), dim3(gx, (unsigned)G.n), blk, 0, gs, src, stride, bx, (int32_t)n, wins, cerr, cblk, S, G, pstride);
+        phase2(std::true_type{}, G, gs);
         if (gs != st) (void)hipEventRecord(aux->join, gs);
     }
-    if (T.n > 0) {
-        const dim3 grid(gx, (unsigned)T.n);
-        if (any_ranked) {
-            if (vec) hipLaunchKernelGGL((bc7_wide_phase1<true, true>),  grid, blk, 0, st, src, stride, bx, (int32_t)n, wins, cerr, cblk, S, T, ranked13, ranked7, pstride);
-            else     hipLaunchKernelGGL((bc7_wide_phase1<false, true>), grid, blk, 0, st, src, stride, bx, (int32_t)n, wins, cerr, cblk, S, T, ranked13, ranked7, pstride);
-        } else {
-            if (vec) hipLaunchKernelGGL((bc7_wide_phase1<true, false>),  grid, blk, 0, st, src, stride, bx, (int32_t)n, wins, cerr, cblk, S, T, ranked13, ranked7, pstride);
-            else     hipLaunchKernelGGL((bc7_wide_phase1<false, false>), grid, blk, 0, st, src, stride, bx, (int32_t)n, wins, cerr, cblk, S, T, ranked13, ranked7, pstride);
-        }
-    }
-    if (R.n > 0) {
-        if (vec) hipLaunchKernelGGL((bc7_wide_phase2<true, false>),  dim3(gx, (unsigned)R.n), blk, 0, st, src, stride, bx, (int32_t)n, wins, cerr, cblk, S, R, pstride);
-        else     hipLaunchKernelGGL((bc7_wide_phase2<false, false>), dim3(gx, (unsigned)R.n), blk, 0, st, src, stride, bx, (int32_t)n, wins, cerr, cblk, S, R, pstride);
-    }
+    if (T.n > 0)
+        with_bools(vec, any_ranked, [&](auto V, auto K) {
+            hipLaunchKernelGGL((bc7_wide_phase1<decltype(V)::value, decltype(K)::value>), dim3(gx, (unsigned)T.n), blk, 0, st, src, stride, bx, (int32_t)n, wins, cerr, cblk, S, T,
+                               ranked13, ranked7, pstride);
+        });
+    if (R.n > 0) phase2(std::false_type{}, R, st);
     if (gs != st) (void)hipStreamWaitEvent(st, aux->join, 0);
-    hipLaunchKernelGGL(bc7_wide_commit, dim3(gx), blk, 0, st, cerr, cblk, (int32_t)n, active, reinterpret_cast<uint4*>(dst), vec ? 1 : 0);
+    hipLaunchKernelGGL(bc7_wide_commit, dim3(gx), blk, 0, st, cerr, cblk, (int32_t)n, active, reinterpret_cast<uint4*>(L.dst), vec ? 1 : 0);
 }
 
-// does a call with these settings run the bounded order of the RGB profiles (`slow`: the one order with a pilot)?
-bool bc7_has_order_verdict(const bc7_enc_settings& s)
+// ---- the fused shape: a scan of all families and a refinement of all modes, in one of four mode orders -----------------------------------
+// What launch_bc7 derives from the workspace for a fused call.
+struct Fused {
+    const Bc7Launch& L; const Bc7Modes& M; const Bc7Aux* aux; FusedLayout W; int32_t nchunks;
+    uint32_t* wins4;         // [5 modes][n] x 4 B
+    int32_t* alpha_err;      // [n] x 4 B behind the winner rows: a phase's error / incumbent
+    int32_t* list_rgb;       // [n] block ids (RGBA profiles: where an RGB mode can win)
+    int32_t* list13;         // [n] block ids (RGBA profiles, bounded order; RGB bounded order in one band: where modes 1/3 can win)
+    int32_t* list7;          // [n] block ids (RGBA profiles, bounded order incl. mode 7)
+    int32_t* ctr;            // the call's counter block (CTR_*), both bands' pair counters behind it
+};
+static Fused fused_context(const Bc7Launch& L, const Bc7Modes& M, float* workspace, const Bc7Aux* aux)
 {
-    bc7_enc_settings S = s;
-    S.channels = (s.channels == 4) ? 4 : 3;
-    auto ranked = [](int t) { return t > 0 && t < 64; };
-    const bool on13 = S.mode_selection[1] && (S.fastSkipTreshold_mode1 > 0 || S.fastSkipTreshold_mode3 > 0);
-    return bc7_fused_on() && bc7_bounded_order() && S.mode_selection[0] && on13 && !ranked(S.fastSkipTreshold_mode1) && !ranked(S.fastSkipTreshold_mode3) &&
-           !(S.mode_selection[1] && S.fastSkipTreshold_mode7 > 0) && !bc7_alpha_first(S);
+    Fused C{L, M, aux, fused_layout((size_t)L.n, fused_needs(M)), (int32_t)(((int64_t)L.n + TPB - 1) / TPB)};
+    C.wins4 = reinterpret_cast<uint32_t*>(workspace);
+    auto at = [&](size_t word) { return reinterpret_cast<int32_t*>(C.wins4 + word); };
+    C.alpha_err = at(C.W.inc); C.list_rgb = at(C.W.list0); C.list13 = at(C.W.list1); C.list7 = at(C.W.list2); C.ctr = at(C.W.counts);
+    return C;
 }
 
-// Families run in the reference's order (kernel.ispc:1970-1977): {0,2} -> {1,3} -> {7} -> {4,5} -> {6}.
+// Where a launch runs.  `sel`: which chunks (ChunkSel); `cnt`: how many chunks that is (the grid); `s`: the stream; `wins`, `rows`: the winner rows it
+// writes or reads and their length (n; a band's list scan has its own rows).
+struct Span { ChunkSel sel; int32_t cnt; hipStream_t s; uint32_t* wins; int32_t rows; };
+// A list of blocks to walk instead of the surface: ids, length, and (optional) the listed blocks' texels in list order.
+struct BlockList { const int32_t* list; const int32_t* count; const uint4* compact; };
+static const ChunkSel ALL_CHUNKS{0, 1, 0, nullptr, 0};
+static const BlockList NO_LIST{nullptr, nullptr, nullptr};
+
+// One band of a bounded order (the whole surface where the call runs as one): its chunks, its stream, the list of the blocks whose modes 1/3 a bound
+// cannot exclude with the winner rows of that list's scan, and what the route adds -- the RGBA profiles' two other lists, or the RGB profiles' compact
+// texels, pair route and rotation tasks.
+struct Band {
+    ChunkSel sel; int32_t cnt; hipStream_t s; int32_t* list; int32_t* count; uint32_t* wins; int32_t rows;
+    int32_t* list_rgb; int32_t* count_rgb; int32_t* list7; int32_t* count7;            // alpha-first with mode 7 bounded
+    uint4* compact; PairRegion P; int32_t* redo; RotRegion R;                          // RGB bounded
+};
+// the bounded orders run as two interleaved bands, one per stream, where the caller lends a second stream and the surface is large enough
+static bool two_bands(const Fused& C) { return bc7_bands() > 1 && C.aux && !C.aux->single && C.aux->stream && C.nchunks >= 32; }
+// The geometry both bounded routes share: stripes of 64 chunks (16 block rows of a 4096-wide surface), fewer on small surfaces; even stripes are band 0,
+// odd stripes band 1.  A band's list scan has rows of its own: shares x listed blocks <= rows, so the scan's grid covers them (list_scan_parts).
+static Band make_band(const Fused& C, bool two, int k, hipStream_t s)
+{
+    int32_t stripe = C.nchunks / 16;
+    stripe = stripe < 1 ? 1 : (stripe > 64 ? 64 : stripe);
+    const int32_t stripes = (C.nchunks + stripe - 1) / stripe;
+    Band B{};
+    B.sel = ChunkSel{two ? 1 : 0, stripe, k, nullptr, 0};
+    B.cnt = two ? ((stripes + 1 - k) / 2) * stripe : C.nchunks;
+    B.s = s;
+    B.wins = two ? C.wins4 + C.W.band[k].wins : C.wins4;         // one band: the global winner rows
+    B.rows = two ? B.cnt * TPB : C.L.n;
+    return B;
+}
+static Span surface(const Fused& C) { return Span{ALL_CHUNKS, C.nchunks, C.L.st, C.wins4, C.L.n}; }
+static Span band_chunks(const Fused& C, const Band& B) { return Span{B.sel, B.cnt, B.s, C.wins4, C.L.n}; }       // the band's chunks of the surface
+static Span band_list(const Band& B) { return Span{ALL_CHUNKS, B.cnt, B.s, B.wins, B.rows}; }                   // a list of the band's, the band's own rows
+static Span band_list_surface_rows(const Fused& C, const Band& B) { return Span{ALL_CHUNKS, B.cnt, B.s, C.wins4, C.L.n}; }
+
+enum { SCAN02 = 1, SCAN13 = 2 };
+// the {0,2} and / or {1,3} scan.  Interleave grain, measured at 4096^2 `slow` (scan time / scan FETCH_SIZE): 8 chunks 6.01 ms / 76 MB (two code paths
+// alternate on every CU: instruction cache), 256 chunks 5.36 ms / 76 MB, 1024 chunks 5.38 ms / 166 MB (L2 no longer
+// holds the first family's texels), family-major 5.39 ms / 154 MB; two separate launches 5.45 ms.
+static void scan_rgb(const Fused& C, int families, const Span& sp, const BlockList& in = NO_LIST, int32_t split = 0)
+{
+    const Bc7Launch& L = C.L;
+    ScanTasks T{};
+    if (C.M.on13 && (families & SCAN13)) T.kind[T.n++] = WK_SCAN13;                   // longest first
+    if (C.M.on02 && (families & SCAN02)) T.kind[T.n++] = WK_SCAN02;
+    if (T.n == 0) return;
+    const int32_t c8 = ((sp.cnt + 7) / 8) * 8;
+    const int32_t grain = c8 < 256 ? c8 : 256;
+    const int32_t groups = (c8 + grain - 1) / grain;
+    const dim3 grid((unsigned)(groups * grain * T.n));
+    with_bools(L.vec, C.M.r13, [&](auto V, auto K) {
+        hipLaunchKernelGGL((bc7_scan_all<decltype(V)::value, decltype(K)::value, false>), grid, dim3(TPB), 0, sp.s, L.src, L.stride, L.bx, sp.rows, sp.wins, L.S, T,
+                           C.M.r13 ? 1 : 0, C.M.r7 ? 1 : 0, sp.cnt, grain, in.list, in.count, split, sp.sel, in.compact);
+    });
+}
+// the mode 7 scan: every chunk of the span, never a compact copy
+static void scan_7(const Fused& C, const Span& sp, const BlockList& in = NO_LIST, int32_t split = 0)
+{
+    const Bc7Launch& L = C.L;
+    if (!C.M.on7) return;
+    const ScanTasks T7{1, {WK_SCAN7}};
+    const int32_t chunks8 = ((sp.cnt + 7) / 8) * 8;
+    with_bools(L.vec, C.M.r7, [&](auto V, auto K) {
+        hipLaunchKernelGGL((bc7_scan_all<decltype(V)::value, decltype(K)::value, true>), dim3((unsigned)chunks8), dim3(TPB), 0, sp.s, L.src, L.stride, L.bx, sp.rows, sp.wins, L.S, T7,
+                           C.M.r13 ? 1 : 0, C.M.r7 ? 1 : 0, sp.cnt, chunks8, in.list, in.count, split, ALL_CHUNKS, (const uint4*)nullptr);
+    });
+}
+// What a finish phase reads and leaves besides the output blocks (bc7_finish_all's header says which phase uses what).
+struct FinishIO {
+    const int32_t* in_list = nullptr; const int32_t* in_count = nullptr; const uint4* in_compact = nullptr;
+    int32_t* out_list = nullptr; int32_t* out_count = nullptr; uint4* out_compact = nullptr;
+    int32_t* out_list7 = nullptr; int32_t* out_count7 = nullptr;
+    RotRegion rot{nullptr, nullptr, nullptr, nullptr, 0};
+    FinishIO& in(const int32_t* l, const int32_t* c, const uint4* texels = nullptr) { in_list = l; in_count = c; in_compact = texels; return *this; }
+    FinishIO& out(int32_t* l, int32_t* c, uint4* texels = nullptr) { out_list = l; out_count = c; out_compact = texels; return *this; }
+    FinishIO& out7(int32_t* l, int32_t* c) { out_list7 = l; out_count7 = c; return *this; }
+    FinishIO& rotations(const RotRegion& r) { rot = r; return *this; }
+};
+// a finish phase: list phases launch one workgroup per possible list chunk (they return at once behind the list's end)
+template <int PH>
+static void finish(const Fused& C, const Span& sp, const FinishIO& io = FinishIO())
+{
+    const Bc7Launch& L = C.L;
+    // bc7_finish_all<3> reads its PairTarget at a fixed distance from the list length: only a band's own counter block will do
+    const int32_t* band0 = C.ctr + CTR_WORDS + PAIR_CTR_LIST;
+    if ((PH == 3 || PH == 10) && io.out_count != band0 && io.out_count != band0 + PAIR_CTR_WORDS)
+        fail_msg("bc7_finish_all<3>: the list length must be word %d of a band's counter block", PAIR_CTR_LIST);
+    with_bool(L.vec, [&](auto V) {
+        hipLaunchKernelGGL((bc7_finish_all<decltype(V)::value, PH>), dim3((unsigned)sp.cnt), dim3(TPB), 0, sp.s, L.src, L.stride, L.bx, sp.rows, L.dst, sp.wins, L.S, C.alpha_err,
+                           io.in_list, io.in_count, io.out_list, io.out_count, io.out_list7, io.out_count7, sp.sel, io.in_compact, io.out_compact, io.rot);
+    });
+}
+
+// Alpha-first with mode 7 bounded too: modes 4,5,6 | 0,2 first, then 1,3 and 7 each over its own list.  Round 5: seven dependent launches
+// leave the chip partly empty seven times, so -- as for the RGB profiles below -- the surface is cut into two interleaved
+// bands, each with its own lists and share winners, one per stream.
+static void launch_alpha_first_bounded7(const Fused& C)
+{
+    const Bc7Aux* aux = C.aux;
+    hipStream_t st = C.L.st;
+    ITW_CHECK(hipMemsetAsync(C.ctr, 0, CTR_WORDS * sizeof(int32_t), st));  // the finish phases append to the lists through them
+    const bool two = two_bands(C);
+    auto chain = [&](int k, hipStream_t s) {
+        Band B = make_band(C, two, k, s);
+        const size_t share = two ? k * C.W.band[0].cap : 0;                 // a band's share of each list region
+        int32_t* lengths = C.ctr + (k ? CTR_BAND1 : 0);
+        B.list_rgb = C.list_rgb + share; B.count_rgb = lengths + CTR_LIST_RGB;
+        B.list = C.list13 + share;       B.count = lengths + CTR_LIST_13;
+        B.list7 = C.list7 + share;       B.count7 = lengths + CTR_LIST_7;
+        const BlockList rgb{B.list_rgb, B.count_rgb, nullptr}, l13{B.list, B.count, nullptr}, l7{B.list7, B.count7, nullptr};
+        finish<6>(C, band_chunks(C, B), FinishIO().out(B.list_rgb, B.count_rgb).out7(B.list7, B.count7));
+        scan_rgb(C, SCAN02, band_list_surface_rows(C, B), rgb);
+        finish<5>(C, band_list_surface_rows(C, B), FinishIO().in(B.list_rgb, B.count_rgb).out(B.list, B.count).out7(B.list7, B.count7));
+        scan_rgb(C, SCAN13, band_list(B), l13, 1);
+        finish<4>(C, band_list(B), FinishIO().in(B.list, B.count));
+        scan_7(C, band_list(B), l7, 1);
+        finish<7>(C, band_list(B), FinishIO().in(B.list7, B.count7));
+    };
+    if (!two) { chain(0, st); return; }
+    ITW_CHECK(hipEventRecord(aux->fork, st));
+    ITW_CHECK(hipStreamWaitEvent(aux->stream, aux->fork, 0));
+    chain(1, aux->stream);
+    chain(0, st);
+    ITW_CHECK(hipEventRecord(aux->join, aux->stream));
+    ITW_CHECK(hipStreamWaitEvent(st, aux->join, 0));
+}
+
+// Alpha-first: mode 7 scanned over the surface, modes 4,5,6,7 finished and the blocks where an RGB mode can still win listed; the RGB modes over that
+// list -- bounded (modes 0,2, then 1,3 over what a bound leaves of it) or in one go.
+static void launch_alpha_first(const Fused& C)
+{
+    ITW_CHECK(hipMemsetAsync(C.ctr, 0, CTR_WORDS * sizeof(int32_t), C.L.st));  // the finish phases append to the lists through them
+    const Span all = surface(C);
+    int32_t* count_rgb = C.ctr + CTR_LIST_RGB; int32_t* count13 = C.ctr + CTR_LIST_13;
+    const BlockList rgb{C.list_rgb, count_rgb, nullptr}, l13{C.list13, count13, nullptr};
+    scan_7(C, all);
+    finish<1>(C, all, FinishIO().out(C.list_rgb, count_rgb));
+    if (C.M.bounded) {
+        scan_rgb(C, SCAN02, all, rgb);
+        finish<5>(C, all, FinishIO().in(C.list_rgb, count_rgb).out(C.list13, count13));
+        scan_rgb(C, SCAN13, all, l13, 1);
+        finish<4>(C, all, FinishIO().in(C.list13, count13));
+    } else {
+        scan_rgb(C, SCAN02 | SCAN13, all, rgb);
+        finish<2>(C, all, FinishIO().in(C.list_rgb, count_rgb));
+    }
+}
+
+// ---- the RGB bounded order ------------------------------------------------------------------------------------------------------------
+// RGB profiles whose modes 1/3 scan every shape (`slow`).  Round 4: scan {0,2} -> finish<3> (modes 0,2,4,5,6; lists the blocks
+// whose modes 1/3 an exact bound cannot exclude) -> scan {1,3} over the list -> finish<4>.  Round 5, with a second stream:
+//  * BANDS.  The surface is cut into two interleaved bands (stripes of chunks), one per stream: a band's four dependent
+//    launches leave the chip partly empty at every boundary (a scan wave runs 0.6 ms), and the other band's work fills those
+//    tails (5.23 -> 4.98 ms on the bench surface, 7.30 -> 7.00 on a photograph; four bands are slower again).
+//  * PILOT.  The order pays where few blocks are listed and still costs a little where nearly all are (photographs: 94 %).
+//    Behind band 0's {0,2} scan -- common to both orders -- bc7_pilot_estimate looks at 1/16 of the surface and leaves a
+//    device word; BOTH continuations of each band are enqueued behind it, each gated on that word (ChunkSel.gate): the one
+//    the pilot did not choose returns at once.  No host round trip, no block treated differently from its neighbours.
+//    (A sample encoded ahead on a third stream was measured first: its chain of small launches could not get its share of a
+//    chip the bands' scans fill, and the verdict arrived late: profiles/history/r05/r05d_bc7_pilot_timeline.txt.)
+// `rot_tasks`: the rotation bound is the RGB profiles' (an RGBA profile's fill is alpha); a first rotation outside 0..3 keeps the inline walk
+struct RgbRoute { bool two, pairs, rot_tasks, pilot; };
+
+static Band rgb_band(const Fused& C, const RgbRoute& R, int k, hipStream_t s)
+{
+    const ListRegion& r = C.W.band[k];
+    uint32_t* w = C.wins4;
+    Band B = make_band(C, R.two, k, s);
+    // one band: list13 of the call, and both bands' texels, buckets, rotation lists and payload slots as one region of twice the capacity
+    B.list = R.two ? reinterpret_cast<int32_t*>(w + r.list) : C.list13;
+    B.compact = env_once(ENV_COMPACT) ? reinterpret_cast<uint4*>(w + r.compact) : nullptr;
+    B.P = PairRegion{reinterpret_cast<uint64_t*>(w + r.pair_words), reinterpret_cast<int32_t*>(w + r.pair_buckets), reinterpret_cast<int32_t*>(w + r.pair_ctr),
+                     bc7_pair_cap((int32_t)(R.two ? r.pair_cap : 2 * r.pair_cap))};
+    B.count = B.P.ctr + PAIR_CTR_LIST;
+    B.redo = reinterpret_cast<int32_t*>(w + r.pair_redo);
+    B.R = RotRegion{reinterpret_cast<int32_t*>(w + r.rot_lists), C.ctr + (k ? CTR_BAND1 : CTR_ROT), reinterpret_cast<unsigned long long*>(w + C.W.rot_words),
+                    reinterpret_cast<uint4*>(w + r.rot_payload), (int32_t)(R.two ? r.cap : 2 * r.cap)};
+    return B;
+}
+// the call's counters start at zero, each band's PairTarget behind its pair counters (one small launch where a memset was)
+static void rgb_setup(const Fused& C, const RgbRoute& R, const Band& A, const Band& B)
+{
+    const PairTarget off{PairRegion{nullptr, nullptr, nullptr, 0}, nullptr};
+    hipLaunchKernelGGL(bc7_bounded_setup, dim3(1), dim3(TPB), 0, C.L.st, C.ctr, R.pairs ? PairTarget{A.P, A.redo} : off, R.pairs ? PairTarget{B.P, B.redo} : off);
+}
+static void rgb_head(const Fused& C, const Band& B) { scan_rgb(C, SCAN02, band_chunks(C, B)); }
+// the estimate behind band B's head scan; `host_counts` (optional): pinned host memory, for a host that reads the counts itself
+static void rgb_pilot(const Fused& C, const Band& B, int32_t thr256, int32_t* host_counts)
+{
+    const Bc7Launch& L = C.L;
+    with_bool(L.vec, [&](auto V) {
+        hipLaunchKernelGGL((bc7_pilot_estimate<decltype(V)::value>), dim3((unsigned)((B.cnt + 7) / 8)), dim3(TPB), 0, L.st, L.src, L.stride, L.bx, L.n, C.wins4,
+                           L.S.skip_mode2 ? 1 : 0, B.sel, C.ctr + CTR_PILOT, thr256, C.ctr + CTR_PILOT_FLAG, host_counts);
+    });
+}
+// a band's two continuations behind its head scan: the bounded order (gated on the pilot's 1) and the reference's (gated on its 0)
+static void rgb_tail(const Fused& C, const RgbRoute& R, const Band& B)
+{
+    const Bc7Launch& L = C.L;
+    auto gated = [&](int32_t want) { Span g = band_chunks(C, B); if (R.pilot) { g.sel.gate = C.ctr + CTR_PILOT_FLAG; g.sel.want = want; } return g; };
+    // pairs: finish<3> also leaves the (block, shape) pairs the bound cannot exclude, bucketed by shape (header above bc7_pair_scan)
+    if (R.rot_tasks) {
+        // modes 4/5 only for the (block, rotation) pairs a bound leaves (header above bc7_rot_tasks); empty lists where the pilot chose the other order
+        finish<9>(C, gated(1), FinishIO().rotations(B.R));
+        with_bool(L.vec, [&](auto V) { hipLaunchKernelGGL((bc7_rot_tasks<decltype(V)::value>), dim3((unsigned)B.cnt), dim3(TPB), 0, B.s, L.src, L.stride, L.bx, L.S, C.alpha_err, B.R); });
+        finish<10>(C, gated(1), FinishIO().out(B.list, B.count, B.compact).rotations(B.R));
+    } else
+        finish<3>(C, gated(1), FinishIO().out(B.list, B.count, B.compact));
+    if (R.pairs) {
+        // the few blocks finish<8> defers take the full list scan behind it
+        int32_t* redo_count = B.P.ctr + PAIR_CTR_REDO;
+        const Span pair_words{ALL_CHUNKS, B.cnt, B.s, reinterpret_cast<uint32_t*>(B.P.words), B.rows};
+        hipLaunchKernelGGL(bc7_pair_scan, dim3((unsigned)((B.cnt + 1) / 2)), dim3(TPB), 0, B.s, L.src, L.stride, L.bx, B.list, B.compact, L.S, B.P);
+        finish<8>(C, pair_words, FinishIO().in(B.list, B.count, B.compact).out(B.redo, redo_count).out7(nullptr, B.P.ctr + PAIR_CTR_OVERFLOW));
+        scan_rgb(C, SCAN13, band_list(B), BlockList{B.redo, redo_count, nullptr}, 1);
+        finish<4>(C, band_list(B), FinishIO().in(B.redo, redo_count));
+    } else {
+        scan_rgb(C, SCAN13, band_list(B), BlockList{B.list, B.count, B.compact}, 1);    // an empty list (the other order): returns at once
+        finish<4>(C, band_list(B), FinishIO().in(B.list, B.count, B.compact));
+    }
+    if (R.pilot) {
+        scan_rgb(C, SCAN13, gated(0));
+        finish<0>(C, gated(0));
+    }
+}
+// ITW_BC7_PILOT_DEBUG=1: what the pilot, the rotation lists and the pair route counted in a two-band call (synchronises)
+static void rgb_print_counters(const Fused& C, const RgbRoute& R, const Band& A, const Band& B)
+{
+    int32_t h[CTR_WORDS + 2 * PAIR_CTR_WORDS];
+    ITW_CHECK(hipStreamSynchronize(C.L.st));
+    ITW_CHECK(hipMemcpy(h, C.ctr, sizeof h, hipMemcpyDeviceToHost));
+    const int32_t* p = h + CTR_PILOT; const int32_t* r0 = h + CTR_ROT; const int32_t* r1 = h + CTR_BAND1;
+    std::fprintf(stderr, "bc7 pilot: estimate %d of %d sampled blocks listed -> %s; lists %d + %d of %lld blocks\n", p[PILOT_LISTED], p[PILOT_SAMPLED],
+                 h[CTR_PILOT_FLAG] ? "bounded" : "reference order", h[CTR_WORDS + PAIR_CTR_LIST], h[CTR_WORDS + PAIR_CTR_WORDS + PAIR_CTR_LIST], (long long)C.L.n);
+    if (R.rot_tasks) std::fprintf(stderr, "bc7 rot tasks: rotation lists %d / %d / %d (band 0) + %d / %d / %d (band 1)\n", r0[0], r0[1], r0[2], r1[0], r1[1], r1[2]);
+    for (int k = 0; k < 2 && R.pairs; k++) {
+        const PairRegion& P = (k ? B : A).P;
+        int32_t c[PAIR_CTR_WORDS];
+        ITW_CHECK(hipMemcpy(c, P.ctr, sizeof c, hipMemcpyDeviceToHost));
+        long long sum = 0; int32_t top = 0;
+        for (int i = 0; i < 64; i++) { sum += c[i]; top = c[i] > top ? c[i] : top; }
+        std::fprintf(stderr, "bc7 pairs: band %d: %lld pairs, fullest bucket %d of %d, overflow %d, deferred to the full scan %d\n", k, sum, top, P.cap,
+                     c[PAIR_CTR_OVERFLOW], c[PAIR_CTR_REDO]);
+    }
+}
+static void launch_rgb_bounded(const Fused& C)
+{
+    const Bc7Aux* aux = C.aux;
+    hipStream_t st = C.L.st;
+    const bool two = two_bands(C), rotations_ok = C.M.channels == 3 && C.L.S.mode45_channel0 >= 0 && C.L.S.mode45_channel0 <= 3;
+    const bool pairs = env_every_call(ENV_PAIRS), rot_tasks = env_every_call(ENV_ROT_TASKS) && rotations_ok;
+    const RgbRoute R{two, pairs, rot_tasks, two && bc7_pilot_threshold() >= 0 && aux->mid};
+    if (!R.two) {
+        const Band B = rgb_band(C, R, 0, st);
+        rgb_setup(C, R, B, B);
+        // a staged run of a host-pointer call (abi.hip) wants the same estimate, left for the HOST to read under the next run's upload -- it picks
+        // the launch shape of the remaining runs; a probe scans what the estimate looks at and nothing else
+        const bool verdict = aux && aux->verdict && aux->verdict->event;
+        const bool probe = verdict && aux->probe;
+        if (probe) scan_rgb(C, SCAN02, Span{ChunkSel{2, 1, 0, nullptr, 0}, (C.nchunks + 7) / 8, st, C.wins4, C.L.n});
+        else rgb_head(C, B);
+        if (verdict) {
+            rgb_pilot(C, B, 256, aux->verdict->host_counts_dev);
+            ITW_CHECK(hipEventRecord(aux->verdict->event, st));
+            aux->verdict->valid = true;
+        }
+        if (!probe) rgb_tail(C, R, B);
+        return;
+    }
+    hipStream_t s2 = aux->stream;
+    const Band A = rgb_band(C, R, 0, st), B = rgb_band(C, R, 1, s2);
+    rgb_setup(C, R, A, B);
+    ITW_CHECK(hipEventRecord(aux->fork, st));                // whatever feeds `src` on st (an upload), and the setup above
+    ITW_CHECK(hipStreamWaitEvent(s2, aux->fork, 0));
+    rgb_head(C, B); rgb_head(C, A);
+    if (R.pilot) {
+        rgb_pilot(C, A, bc7_pilot_threshold(), nullptr);
+        ITW_CHECK(hipEventRecord(aux->mid, st));
+        ITW_CHECK(hipStreamWaitEvent(s2, aux->mid, 0));        // band 1's continuations start behind the verdict
+    }
+    rgb_tail(C, R, B); rgb_tail(C, R, A);
+    ITW_CHECK(hipEventRecord(aux->join, s2));
+    ITW_CHECK(hipStreamWaitEvent(st, aux->join, 0));
+    if (env_once(ENV_PILOT_DEBUG)) rgb_print_counters(C, R, A, B);
+}
+
+// The reference's order in two launches: {0,2} and {1,3} scanned together, {7}, then every mode's refinement and {4,5}, {6}.
+static void launch_reference_order(const Fused& C)
+{
+    scan_rgb(C, SCAN02 | SCAN13, surface(C));
+    scan_7(C, surface(C));
+    finish<0>(C, surface(C));
+}
+
+// A family at a time: a ranked list longer than 16 shapes keeps its keys in 64 KiB of LDS (RANKED == 1), or ITW_BC7_FUSED=0.
+template <int FAMILY>
+static void launch_ranked_family(Bc7Launch& L, bool ranked, bool long_list)
+{
+    if (!ranked) launch_search<FAMILY, 0>(L);
+    else if (long_list) launch_search<FAMILY, 1>(L);
+    else launch_search<FAMILY, 2>(L);
+    launch_finish<FAMILY>(L);
+}
+static void launch_per_family(Bc7Launch& L, const Bc7Modes& M)
+{
+    if (M.on02) { launch_search<F_MODES02, 0>(L); launch_finish<F_MODES02>(L); }
+    if (M.on13) launch_ranked_family<F_MODES13>(L, M.r13, M.long13);
+    if (M.on7) launch_ranked_family<F_MODE7>(L, M.r7, M.long7);
+    if (M.on45 || M.on6) launch_finish<F_MODES456>(L);
+    if (L.first) ITW_CHECK(hipMemsetAsync(L.dst, 0, (size_t)L.n * 16, L.st));   // no mode enabled: defined (zero) output
+}
+
+// Families run in the reference's order (kernel.ispc:1970-1977): {0,2} -> {1,3} -> {7} -> {4,5} -> {6}, or in an order that gives the same bytes.
 void launch_bc7(const uint8_t* src, int64_t stride, int width, int height, uint8_t* dst,
                 const bc7_enc_settings& s, float* workspace, hipStream_t st, const Bc7Aux* aux)
 {
     const int bx = width / 4, by = height / 4;
     const int64_t n = (int64_t)bx * by;
     if (n <= 0) return;
+    const Bc7Modes M = bc7_modes(s);
     Bc7Launch L;
     L.S = s;
-    L.S.channels = (s.channels == 4) ? 4 : 3;
-    const bool single = aux && aux->single;
-    if (aux && aux->probe && !bc7_has_order_verdict(L.S)) return;   // only the bounded order of the RGB profiles has a verdict to estimate
-    if (!single && bc7_use_wide(n, L.S, aux ? aux->wide_max_blocks : 0)) { launch_bc7_wide(src, stride, bx, n, dst, L.S, workspace, st, aux); return; }
-    L.err = reinterpret_cast<int32_t*>(workspace);
+    L.S.channels = M.channels;
+    L.err = reinterpret_cast<int32_t*>(workspace);                // (the per-family kernels' layout)
     L.wins = reinterpret_cast<uint4*>(reinterpret_cast<uint8_t*>(workspace) + (((size_t)n * sizeof(int32_t) + 15) & ~(size_t)15));
     L.vec = ((reinterpret_cast<uintptr_t>(src) | (uintptr_t)stride | reinterpret_cast<uintptr_t>(dst)) & 15) == 0;
     L.grid = dim3((unsigned)((n + TPB - 1) / TPB));
     L.st = st; L.src = src; L.stride = stride; L.bx = bx; L.n = (int32_t)n; L.dst = dst; L.first = 1;
-    const bc7_enc_settings& S = L.S;
-    auto ranked = [](int t) { return t > 0 && t < 64; };
-    auto small = [](int t) { return t <= 16; };                  // non-positive thresholds disable the mode
-    {
-        // two launches (scan of all families, refinement of all modes) unless a ranked list is longer than 16 shapes (those
-        // keep their keys in 64 KiB of LDS: the per-family kernels below) or ITW_BC7_FUSED=0
-        const bool fused_on = bc7_fused_on();
-        const bool on02 = S.mode_selection[0];
-        const bool on13 = S.mode_selection[1] && (S.fastSkipTreshold_mode1 > 0 || S.fastSkipTreshold_mode3 > 0);
-        const bool on7 = S.mode_selection[1] && S.fastSkipTreshold_mode7 > 0;
-        const bool r13 = on13 && (ranked(S.fastSkipTreshold_mode1) || ranked(S.fastSkipTreshold_mode3));
-        const bool r7 = on7 && ranked(S.fastSkipTreshold_mode7);
-        const bool long13 = r13 && !(small(S.fastSkipTreshold_mode1) && small(S.fastSkipTreshold_mode3));
-        const bool long7 = r7 && !small(S.fastSkipTreshold_mode7);
-        const bool any_mode = on02 || on13 || on7 || S.mode_selection[2] || S.mode_selection[3];
-        if (fused_on && !long13 && !long7 && any_mode) {
-            uint32_t* wins4 = reinterpret_cast<uint32_t*>(workspace);          // [5 modes][n] x 4 B
-            const int32_t nchunks = (int32_t)((n + TPB - 1) / TPB);
-            // Interleave grain, measured at 4096^2 `slow` (scan time / scan FETCH_SIZE): 8 chunks 6.01 ms / 76 MB (two code paths
-            // alternate on every CU: instruction cache), 256 chunks 5.36 ms / 76 MB, 1024 chunks 5.38 ms / 166 MB (L2 no longer
-            // holds the first family's texels), family-major 5.39 ms / 154 MB; two separate launches 5.45 ms.
-            const int a13 = r13 ? 1 : 0, a7 = r7 ? 1 : 0;
-            const FusedLayout W = fused_layout((size_t)n, fused_needs(&S));
-            int32_t* alpha_err = reinterpret_cast<int32_t*>(wins4 + W.inc);                    // [n] x 4 B behind the winner rows: a phase's error / incumbent
-            int32_t* rgb_list = reinterpret_cast<int32_t*>(wins4 + W.list0);                   // [n] block ids (RGBA profiles: where an RGB mode can win; RGB: where modes 1/3 can)
-            int32_t* list13 = reinterpret_cast<int32_t*>(wins4 + W.list1);                     // [n] block ids (RGBA profiles, bounded order)
-            int32_t* list7 = reinterpret_cast<int32_t*>(wins4 + W.list2);                      // [n] block ids (RGBA profiles, bounded order incl. mode 7)
-            int32_t* rgb_count = reinterpret_cast<int32_t*>(wins4 + W.counts);                 // the lists' lengths, the pilot's list length and verdict
-            int32_t* count13 = rgb_count + 1;
-            int32_t* pilot_flag = rgb_count + 6;                                               // the pilot's verdict
-            int32_t* pilot_ctr = rgb_count + 8;                                                // [3]: its counts (listed, sampled, workgroups done)
-            const bool compact_on = bc7_compact_lists();
-            const dim3 blk(TPB);
-            const ChunkSel ALL{0, 1, 0, nullptr, 0};
-            // `sel`: which chunks (ChunkSel); `cnt`: how many chunks that is; `rows`: length of a winner row (n; a band's list scan has its own rows)
-            auto scan_rgb = [&](const int32_t* list, const int32_t* count, bool do13, bool do02, int32_t split = 0, ChunkSel sel = ChunkSel{0, 1, 0, nullptr, 0},
-                                int32_t cnt = -1, hipStream_t s = nullptr, uint32_t* wins = nullptr, int32_t rows = 0, const uint4* compact = nullptr) {
-                ScanTasks T;
-                T.n = 0;
-                if (on13 && do13) T.kind[T.n++] = WK_SCAN13;                   // longest first
-                if (on02 && do02) T.kind[T.n++] = WK_SCAN02;
-                if (T.n == 0) return;
-                if (cnt < 0) cnt = nchunks;
-                if (!s) s = st;
-                if (!wins) { wins = wins4; rows = (int32_t)n; }
-                const int32_t c8 = ((cnt + 7) / 8) * 8;
-                int32_t grain = 256;
-                if (grain > c8) grain = c8;
-                const int32_t groups = (c8 + grain - 1) / grain;
-                const dim3 grid((unsigned)(groups * grain * T.n));
-                if (r13) {
-                    if (L.vec) hipLaunchKernelGGL((bc7_scan_all<true, true, false>),  grid, blk, 0, s, src, stride, bx, rows, wins, S, T, a13, a7, cnt, grain, list, count, split, sel, compact);
-                    else       hipLaunchKernelGGL((bc7_scan_all<false, true, false>), grid, blk, 0, s, src, stride, bx, rows, wins, S, T, a13, a7, cnt, grain, list, count, split, sel, compact);
-                } else {
-                    if (L.vec) hipLaunchKernelGGL((bc7_scan_all<true, false, false>),  grid, blk, 0, s, src, stride, bx, rows, wins, S, T, a13, a7, cnt, grain, list, count, split, sel, compact);
-                    else       hipLaunchKernelGGL((bc7_scan_all<false, false, false>), grid, blk, 0, s, src, stride, bx, rows, wins, S, T, a13, a7, cnt, grain, list, count, split, sel, compact);
-                }
-            };
-            auto scan_7 = [&](const int32_t* list = nullptr, const int32_t* count = nullptr, int32_t split = 0, int32_t cnt = -1, hipStream_t s = nullptr,
-                              uint32_t* wins = nullptr, int32_t rows = 0) {
-                if (!on7) return;
-                ScanTasks T7;
-                T7.n = 1; T7.kind[0] = WK_SCAN7;
-                if (cnt < 0) cnt = nchunks;
-                if (!s) s = st;
-                if (!wins) { wins = wins4; rows = (int32_t)n; }
-                const int32_t chunks8 = ((cnt + 7) / 8) * 8;
-                const dim3 grid((unsigned)chunks8);
-                if (r7) {
-                    if (L.vec) hipLaunchKernelGGL((bc7_scan_all<true, true, true>),  grid, blk, 0, s, src, stride, bx, rows, wins, S, T7, a13, a7, cnt, chunks8, list, count, split, ALL, (const uint4*)nullptr);
-                    else       hipLaunchKernelGGL((bc7_scan_all<false, true, true>), grid, blk, 0, s, src, stride, bx, rows, wins, S, T7, a13, a7, cnt, chunks8, list, count, split, ALL, (const uint4*)nullptr);
-                } else {
-                    if (L.vec) hipLaunchKernelGGL((bc7_scan_all<true, false, true>),  grid, blk, 0, s, src, stride, bx, rows, wins, S, T7, a13, a7, cnt, chunks8, list, count, split, ALL, (const uint4*)nullptr);
-                    else       hipLaunchKernelGGL((bc7_scan_all<false, false, true>), grid, blk, 0, s, src, stride, bx, rows, wins, S, T7, a13, a7, cnt, chunks8, list, count, split, ALL, (const uint4*)nullptr);
-                }
-            };
-            // a finish phase: list phases launch one workgroup per possible list chunk (they return at once behind the list's end)
-            auto finish = [&](auto phase, const int32_t* in_list, const int32_t* in_count, int32_t* out_list, int32_t* out_count,
-                              int32_t* out_list7 = nullptr, int32_t* out_count7 = nullptr, ChunkSel sel = ChunkSel{0, 1, 0, nullptr, 0}, int32_t cnt = -1,
-                              hipStream_t s = nullptr, const uint32_t* wins = nullptr, int32_t rows = 0, const uint4* in_compact = nullptr, uint4* out_compact = nullptr,
-                              RotRegion rot = RotRegion{nullptr, nullptr, nullptr, nullptr, 0}) {
-                constexpr int PH = decltype(phase)::value;
-                // bc7_finish_all<3> reads its PairTarget at a fixed distance from the list length: only a band's own counter block will do
-                if ((PH == 3 || PH == 10) && out_count != rgb_count + 16 + PAIR_CTR_LIST && out_count != rgb_count + 16 + PAIR_CTR_WORDS + PAIR_CTR_LIST)
-                    fail_msg("bc7_finish_all<3>: the list length must be word %d of a band's counter block", PAIR_CTR_LIST);
-                if (cnt < 0) cnt = nchunks;
-                if (!s) s = st;
-                if (!wins) { wins = wins4; rows = (int32_t)n; }
-                const dim3 grid((unsigned)cnt);
-                if (L.vec) hipLaunchKernelGGL((bc7_finish_all<true, PH>),  grid, blk, 0, s, src, stride, bx, rows, dst, wins, S, alpha_err, in_list, in_count, out_list, out_count, out_list7, out_count7, sel, in_compact, out_compact, rot);
-                else       hipLaunchKernelGGL((bc7_finish_all<false, PH>), grid, blk, 0, s, src, stride, bx, rows, dst, wins, S, alpha_err, in_list, in_count, out_list, out_count, out_list7, out_count7, sel, in_compact, out_compact, rot);
-            };
-            // the bounded order (bc7_finish_all's header): profiles whose modes 1/3 scan every shape -- a ranked list already spends
-            // a bound's worth of arithmetic per shape on its keys and then fits a few shapes only
-            const bool bounded = bc7_bounded_order() && on02 && on13 && !r13;
-            if (bc7_alpha_first(S)) {
-                ITW_CHECK(hipMemsetAsync(rgb_count, 0, 16 * sizeof(int32_t), st));  // the finish phases append to the lists through them
-                if (bounded && on7 && !r7 && (S.mode_selection[2] || S.mode_selection[3])) {
-                    // mode 7 bounded too: modes 4,5,6 | 0,2 first, then 1,3 and 7 each over its own list.  Round 5: seven dependent launches
-                    // leave the chip partly empty seven times, so -- as for the RGB profiles below -- the surface is cut into two interleaved
-                    // bands, each with its own lists and share winners, one per stream.
-                    const bool two = bc7_bands() > 1 && aux && !aux->single && aux->stream && nchunks >= 32;
-                    int32_t stripe = nchunks / 16;
-                    stripe = stripe < 1 ? 1 : (stripe > 64 ? 64 : stripe);
-                    const int32_t stripes = (nchunks + stripe - 1) / stripe;
-                    auto chain = [&](int k, hipStream_t s) {
-                        const ChunkSel sel{two ? 1 : 0, stripe, k, nullptr, 0};
-                        const int32_t cnt = two ? ((stripes + 1 - k) / 2) * stripe : nchunks;
-                        const size_t cap = W.band[0].cap;                       // a band's share of each list region
-                        int32_t* lrgb = rgb_list + (two ? k * cap : 0); int32_t* l13 = list13 + (two ? k * cap : 0); int32_t* l7 = list7 + (two ? k * cap : 0);
-                        int32_t* crgb = rgb_count + (k ? 11 : 0); int32_t* c13 = rgb_count + (k ? 12 : 1); int32_t* c7 = rgb_count + (k ? 13 : 2);
-                        uint32_t* wins = two ? wins4 + W.band[k].wins : wins4;
-                        const int32_t rows = two ? cnt * TPB : (int32_t)n;
-                        finish(std::integral_constant<int, 6>{}, nullptr, nullptr, lrgb, crgb, l7, c7, sel, cnt, s);
-                        scan_rgb(lrgb, crgb, false, true, 0, ALL, cnt, s);
-                        finish(std::integral_constant<int, 5>{}, lrgb, crgb, l13, c13, l7, c7, ALL, cnt, s);
-                        scan_rgb(l13, c13, true, false, 1, ALL, cnt, s, wins, rows);
-                        finish(std::integral_constant<int, 4>{}, l13, c13, nullptr, nullptr, nullptr, nullptr, ALL, cnt, s, wins, rows);
-                        scan_7(l7, c7, 1, cnt, s, wins, rows);
-                        finish(std::integral_constant<int, 7>{}, l7, c7, nullptr, nullptr, nullptr, nullptr, ALL, cnt, s, wins, rows);
-                    };
-                    if (!two) chain(0, st);
-                    else {
-                        ITW_CHECK(hipEventRecord(aux->fork, st));
-                        ITW_CHECK(hipStreamWaitEvent(aux->stream, aux->fork, 0));
-                        chain(1, aux->stream);
-                        chain(0, st);
-                        ITW_CHECK(hipEventRecord(aux->join, aux->stream));
-                        ITW_CHECK(hipStreamWaitEvent(st, aux->join, 0));
-                    }
-                } else {
-                    scan_7();
-                    finish(std::integral_constant<int, 1>{}, nullptr, nullptr, rgb_list, rgb_count);
-                    if (bounded) {
-                        scan_rgb(rgb_list, rgb_count, false, true);
-                        finish(std::integral_constant<int, 5>{}, rgb_list, rgb_count, list13, count13);
-                        scan_rgb(list13, count13, true, false, 1);
-                        finish(std::integral_constant<int, 4>{}, list13, count13, nullptr, nullptr);
-                    } else {
-                        scan_rgb(rgb_list, rgb_count, true, true);
-                        finish(std::integral_constant<int, 2>{}, rgb_list, rgb_count, nullptr, nullptr);
-                    }
-                }
-            } else if (bounded && !on7) {
-                // RGB profiles whose modes 1/3 scan every shape (`slow`).  Round 4: scan {0,2} -> finish<3> (modes 0,2,4,5,6; lists the blocks
-                // whose modes 1/3 an exact bound cannot exclude) -> scan {1,3} over the list -> finish<4>.  Round 5, with a second stream:
-                //  * BANDS.  The surface is cut into two interleaved bands (stripes of chunks), one per stream: a band's four dependent
-                //    launches leave the chip partly empty at every boundary (a scan wave runs 0.6 ms), and the other band's work fills those
-                //    tails (5.23 -> 4.98 ms on the bench surface, 7.30 -> 7.00 on a photograph; four bands are slower again).
-                //  * PILOT.  The order pays where few blocks are listed and still costs a little where nearly all are (photographs: 94 %).
-                //    Behind band 0's {0,2} scan -- common to both orders -- bc7_pilot_estimate looks at 1/16 of the surface and leaves a
-                //    device word; BOTH continuations of each band are enqueued behind it, each gated on that word (ChunkSel.gate): the one
-                //    the pilot did not choose returns at once.  No host round trip, no block treated differently from its neighbours.
-                //    (A sample encoded ahead on a third stream was measured first: its chain of small launches could not get its share of a
-                //    chip the bands' scans fill, and the verdict arrived late: profiles/history/r05/r05d_bc7_pilot_timeline.txt.)
-                const bool two = bc7_bands() > 1 && aux && !aux->single && aux->stream && nchunks >= 32;
-                const bool pairs = bc7_pairs_on();
-                // the rotation bound is the RGB profiles' (an RGBA profile's fill is alpha); a first rotation outside 0..3 keeps the inline walk
-                const bool rot_tasks = bc7_rot_tasks_on() && S.channels == 3 && S.mode45_channel0 >= 0 && S.mode45_channel0 <= 3;
-                const bool pilot = two && bc7_pilot_threshold() >= 0 && aux->mid;
-                int32_t stripe = nchunks / 16;                               // stripes of 64 chunks (16 block rows of a 4096-wide surface), fewer on small surfaces
-                stripe = stripe < 1 ? 1 : (stripe > 64 ? 64 : stripe);
-                const int32_t stripes = (nchunks + stripe - 1) / stripe;
-                struct Band { ChunkSel sel; int32_t cnt; hipStream_t s; int32_t* list; int32_t* count; uint32_t* wins; int32_t rows; uint4* compact; PairRegion P; int32_t* redo; RotRegion R; };
-                auto band = [&](int k, hipStream_t s) {
-                    const ListRegion& r = W.band[k];
-                    Band B{ChunkSel{two ? 1 : 0, stripe, k, nullptr, 0}, two ? ((stripes + 1 - k) / 2) * stripe : nchunks, s,
-                           reinterpret_cast<int32_t*>(wins4 + r.list), nullptr, wins4 + r.wins, 0, compact_on ? reinterpret_cast<uint4*>(wins4 + r.compact) : nullptr,
-                           PairRegion{reinterpret_cast<uint64_t*>(wins4 + r.pair_words), reinterpret_cast<int32_t*>(wins4 + r.pair_buckets), reinterpret_cast<int32_t*>(wins4 + r.pair_ctr),
-                                      bc7_pair_cap((int32_t)(two ? r.pair_cap : 2 * r.pair_cap))}, reinterpret_cast<int32_t*>(wins4 + r.pair_redo),
-                           // one band: both bands' lists and payload slots as one region of twice the capacity; lengths: words 3..5 / 11..13 of the call's counters
-                           RotRegion{reinterpret_cast<int32_t*>(wins4 + r.rot_lists), rgb_count + (k ? 11 : 3), reinterpret_cast<unsigned long long*>(wins4 + W.rot_words),
-                                     reinterpret_cast<uint4*>(wins4 + r.rot_payload), (int32_t)(two ? r.cap : 2 * r.cap)}};
-                    B.count = B.P.ctr + PAIR_CTR_LIST;
-                    B.rows = B.cnt * TPB;                                    // shares x listed blocks <= rows: the list scan's grid covers them (list_scan_parts)
-                    if (!two) { B.list = list13; B.wins = wins4; B.rows = (int32_t)n; }     // one band: the global winner rows, both texel regions as one
-                    return B;
-                };
-                auto gated = [&](const Band& B, int32_t want) { ChunkSel g = B.sel; if (pilot) { g.gate = pilot_flag; g.want = want; } return g; };
-                auto head = [&](const Band& B) { scan_rgb(nullptr, nullptr, false, true, 0, B.sel, B.cnt, B.s); };
-                auto tail = [&](const Band& B) {
-                    // pairs: finish<3> also leaves the (block, shape) pairs the bound cannot exclude, bucketed by shape (header above bc7_pair_scan)
-                    if (rot_tasks) {
-                        // modes 4/5 only for the (block, rotation) pairs a bound leaves (header above bc7_rot_tasks); empty lists where the pilot chose the other order
-                        finish(std::integral_constant<int, 9>{}, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, gated(B, 1), B.cnt, B.s, nullptr, 0, nullptr, nullptr, B.R);
-                        if (L.vec) hipLaunchKernelGGL((bc7_rot_tasks<true>),  dim3((unsigned)B.cnt), blk, 0, B.s, src, stride, bx, S, alpha_err, B.R);
-                        else       hipLaunchKernelGGL((bc7_rot_tasks<false>), dim3((unsigned)B.cnt), blk, 0, B.s, src, stride, bx, S, alpha_err, B.R);
-                        finish(std::integral_constant<int, 10>{}, nullptr, nullptr, B.list, B.count, nullptr, nullptr, gated(B, 1), B.cnt, B.s, nullptr, 0, nullptr, B.compact, B.R);
-                    } else
-                        finish(std::integral_constant<int, 3>{}, nullptr, nullptr, B.list, B.count, nullptr, nullptr, gated(B, 1), B.cnt, B.s, nullptr, 0, nullptr, B.compact);
-                    if (pairs) {
-                        // the few blocks finish<8> defers take the full list scan behind it
-                        int32_t* redo_count = B.P.ctr + PAIR_CTR_REDO;
-                        hipLaunchKernelGGL(bc7_pair_scan, dim3((unsigned)((B.cnt + 1) / 2)), blk, 0, B.s, src, stride, bx, B.list, B.compact, S, B.P);
-                        finish(std::integral_constant<int, 8>{}, B.list, B.count, B.redo, redo_count, nullptr, B.P.ctr + PAIR_CTR_OVERFLOW, ALL, B.cnt, B.s,
-                               reinterpret_cast<const uint32_t*>(B.P.words), B.rows, B.compact);
-                        scan_rgb(B.redo, redo_count, true, false, 1, ALL, B.cnt, B.s, B.wins, B.rows);
-                        finish(std::integral_constant<int, 4>{}, B.redo, redo_count, nullptr, nullptr, nullptr, nullptr, ALL, B.cnt, B.s, B.wins, B.rows);
-                    } else {
-                        scan_rgb(B.list, B.count, true, false, 1, ALL, B.cnt, B.s, B.wins, B.rows, B.compact);    // an empty list (the other order): returns at once
-                        finish(std::integral_constant<int, 4>{}, B.list, B.count, nullptr, nullptr, nullptr, nullptr, ALL, B.cnt, B.s, B.wins, B.rows, B.compact);
-                    }
-                    if (pilot) {
-                        scan_rgb(nullptr, nullptr, true, false, 0, gated(B, 0), B.cnt, B.s);
-                        finish(std::integral_constant<int, 0>{}, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, gated(B, 0), B.cnt, B.s);
-                    }
-                };
-                // the call's counters start at zero, each band's PairTarget behind its pair counters (one small launch where a memset was)
-                auto setup = [&](const Band& A, const Band& Bb) {
-                    const PairTarget off{PairRegion{nullptr, nullptr, nullptr, 0}, nullptr};
-                    hipLaunchKernelGGL(bc7_bounded_setup, dim3(1), blk, 0, st, rgb_count, pairs ? PairTarget{A.P, A.redo} : off, pairs ? PairTarget{Bb.P, Bb.redo} : off);
-                };
-                if (!two) {
-                    const Band B = band(0, st);
-                    setup(B, B);
-                    const bool probe = aux && aux->probe && aux->verdict && aux->verdict->event;
-                    if (probe) scan_rgb(nullptr, nullptr, false, true, 0, ChunkSel{2, 1, 0, nullptr, 0}, (nchunks + 7) / 8, st);
-                    else head(B);
-                    if (aux && aux->verdict && aux->verdict->event) {
-                        // a staged run of a host-pointer call (abi.hip): the same estimate, left for the HOST to read under the next
-                        // run's upload -- it picks the launch shape of the remaining runs
-                        const dim3 grid((unsigned)((B.cnt + 7) / 8));
-                        if (L.vec) hipLaunchKernelGGL((bc7_pilot_estimate<true>),  grid, blk, 0, st, src, stride, bx, (int32_t)n, wins4, S.skip_mode2 ? 1 : 0, B.sel, pilot_ctr, 256, pilot_flag, aux->verdict->host_counts_dev);
-                        else       hipLaunchKernelGGL((bc7_pilot_estimate<false>), grid, blk, 0, st, src, stride, bx, (int32_t)n, wins4, S.skip_mode2 ? 1 : 0, B.sel, pilot_ctr, 256, pilot_flag, aux->verdict->host_counts_dev);
-                        ITW_CHECK(hipEventRecord(aux->verdict->event, st));
-                        aux->verdict->valid = true;
-                    }
-                    if (probe) return;
-                    tail(B);
-                } else {
-                    hipStream_t s2 = aux->stream;
-                    const Band A = band(0, st), Bb = band(1, s2);
-                    setup(A, Bb);
-                    ITW_CHECK(hipEventRecord(aux->fork, st));                // whatever feeds `src` on st (an upload), and the setup above
-                    ITW_CHECK(hipStreamWaitEvent(s2, aux->fork, 0));
-                    head(Bb); head(A);
-                    if (pilot) {
-                        const dim3 grid((unsigned)((A.cnt + 7) / 8));
-                        if (L.vec) hipLaunchKernelGGL((bc7_pilot_estimate<true>),  grid, blk, 0, st, src, stride, bx, (int32_t)n, wins4, S.skip_mode2 ? 1 : 0, A.sel, pilot_ctr, bc7_pilot_threshold(), pilot_flag, (int32_t*)nullptr);
-                        else       hipLaunchKernelGGL((bc7_pilot_estimate<false>), grid, blk, 0, st, src, stride, bx, (int32_t)n, wins4, S.skip_mode2 ? 1 : 0, A.sel, pilot_ctr, bc7_pilot_threshold(), pilot_flag, (int32_t*)nullptr);
-                        ITW_CHECK(hipEventRecord(aux->mid, st));
-                        ITW_CHECK(hipStreamWaitEvent(s2, aux->mid, 0));        // band 1's continuations start behind the verdict
-                    }
-                    tail(Bb); tail(A);
-                    ITW_CHECK(hipEventRecord(aux->join, s2));
-                    ITW_CHECK(hipStreamWaitEvent(st, aux->join, 0));
-                    if (bc7_pilot_debug()) {
-                        int32_t h[16 + 2 * PAIR_CTR_WORDS];
-                        ITW_CHECK(hipStreamSynchronize(st));
-                        ITW_CHECK(hipMemcpy(h, rgb_count, sizeof h, hipMemcpyDeviceToHost));
-                        std::fprintf(stderr, "bc7 pilot: estimate %d of %d sampled blocks listed -> %s; lists %d + %d of %lld blocks\n", h[8], h[9], h[6] ? "bounded" : "reference order",
-                                     h[16 + PAIR_CTR_LIST], h[16 + PAIR_CTR_WORDS + PAIR_CTR_LIST], (long long)n);
-                        if (rot_tasks) std::fprintf(stderr, "bc7 rot tasks: rotation lists %d / %d / %d (band 0) + %d / %d / %d (band 1)\n", h[3], h[4], h[5], h[11], h[12], h[13]);
-                        for (int k = 0; k < 2 && pairs; k++) {
-                            int32_t c[PAIR_CTR_WORDS];
-                            ITW_CHECK(hipMemcpy(c, (k ? Bb : A).P.ctr, sizeof c, hipMemcpyDeviceToHost));
-                            long long sum = 0; int32_t top = 0;
-                            for (int i = 0; i < 64; i++) { sum += c[i]; top = c[i] > top ? c[i] : top; }
-                            std::fprintf(stderr, "bc7 pairs: band %d: %lld pairs, fullest bucket %d of %d, overflow %d, deferred to the full scan %d\n", k, sum, top, (k ? Bb : A).P.cap,
-                                         c[PAIR_CTR_OVERFLOW], c[PAIR_CTR_REDO]);
-                        }
-                    }
-                }
-            } else {
-                scan_rgb(nullptr, nullptr, true, true);
-                scan_7();
-                finish(std::integral_constant<int, 0>{}, nullptr, nullptr, nullptr, nullptr);
-            }
-            return;
-        }
-    }
-    if (S.mode_selection[0]) { launch_search<F_MODES02, 0>(L); launch_finish<F_MODES02>(L); }
-    if (S.mode_selection[1] && (S.fastSkipTreshold_mode1 > 0 || S.fastSkipTreshold_mode3 > 0)) {
-        if (ranked(S.fastSkipTreshold_mode1) || ranked(S.fastSkipTreshold_mode3)) {
-            if (small(S.fastSkipTreshold_mode1) && small(S.fastSkipTreshold_mode3)) launch_search<F_MODES13, 2>(L);
-            else launch_search<F_MODES13, 1>(L);
-        } else launch_search<F_MODES13, 0>(L);
-        launch_finish<F_MODES13>(L);
-    }
-    if (S.mode_selection[1] && S.fastSkipTreshold_mode7 > 0) {
-        if (ranked(S.fastSkipTreshold_mode7)) {
-            if (small(S.fastSkipTreshold_mode7)) launch_search<F_MODE7, 2>(L); else launch_search<F_MODE7, 1>(L);
-        } else launch_search<F_MODE7, 0>(L);
-        launch_finish<F_MODE7>(L);
-    }
-    if (S.mode_selection[2] || S.mode_selection[3]) launch_finish<F_MODES456>(L);
-    if (L.first) ITW_CHECK(hipMemsetAsync(dst, 0, (size_t)n * 16, st));   // no mode enabled: defined (zero) output
+    const bool single = aux && aux->single;
+    if (aux && aux->probe && !has_order_verdict(M)) return;   // only the bounded order of the RGB profiles has a verdict to estimate
+    if (!single && bc7_use_wide(n, L.S, M, aux ? aux->wide_max_blocks : 0)) { launch_bc7_wide(L, M, workspace, aux); return; }
+    // two launches (scan of all families, refinement of all modes) unless a ranked list is longer than 16 shapes or ITW_BC7_FUSED=0
+    if (!env_once(ENV_FUSED) || M.long13 || M.long7 || !M.any()) { launch_per_family(L, M); return; }
+    const Fused C = fused_context(L, M, workspace, aux);
+    if (M.alpha_first && M.bounded && M.on7 && !M.r7 && (M.on45 || M.on6)) launch_alpha_first_bounded7(C);
+    else if (M.alpha_first) launch_alpha_first(C);
+    else if (M.rgb_bounded) launch_rgb_bounded(C);
+    else launch_reference_order(C);
 }
 
 } // namespace itw

@@ -146,6 +146,26 @@ def test_pilot_on_a_strided_surface_and_repeated_calls(itw, gpu, oracle, deep, g
         itw.set_bc7_pilot(None)
 
 
+def test_alpha_slow_in_two_bands_with_a_partial_last_chunk(itw, gpu, oracle, deep, golden_inputs):
+    """the alpha-first order with mode 7 bounded (launch_alpha_first_bounded7) cut into two bands, each with its own three lists: `alpha_slow`
+    through the fused shape on 129 x 151 blocks = 76.1 chunks.  Opaque, translucent (a smooth ramp, noise) and alpha-254 columns over the mixed
+    content; a base of a third of the rows tiled three times, so the oracle encodes the base once.  Two calls in a row: the lists' counters
+    and the workspace are reused."""
+    rng = np.random.default_rng(17)
+    base = _mixed_content(golden_inputs, 172, 604).copy()
+    base[:, 152:300, 3] = np.linspace(0, 255, 148).astype(np.uint8)[None, :]
+    base[:, 300:452, 3] = rng.integers(0, 256, (172, 152))
+    base[:, 452:, 3] = 254
+    want = oracle.encode_mt("bc7", base, "alpha_slow").reshape(43, 151, 16)
+    img, want = np.ascontiguousarray(np.tile(base, (3, 1, 1))), np.ascontiguousarray(np.tile(want, (3, 1, 1))).reshape(-1)
+    assert img.shape[:2] == (516, 604)
+    blocks = (img.shape[0] // 4) * (img.shape[1] // 4)
+    assert -(-blocks // 256) == 77 and blocks % 256 != 0          # at least 32 chunks: two bands; the last one partial
+    for call in (1, 2):
+        got = _encode(itw, gpu, img, "alpha_slow")
+        assert first_mismatch(got, want, 16) is None, (call, first_mismatch(got, want, 16))
+
+
 def test_mode_6_skipped_by_its_bound_changes_nothing(itw, gpu, oracle, deep):
     """content where mode 6 wins most blocks (smooth one-line gradients), content where its bound rules it out everywhere (noise) and flat
     blocks (error 0 everywhere): `slow` and a custom struct with modes 0/2 + 6 only"""

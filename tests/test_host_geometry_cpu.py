@@ -48,6 +48,36 @@ def test_slice_window_for_every_format_size_and_slice_size(itw):
                     assert L.itwSliceWindow(code, w, h, sp) == got, (code, w, h, sp)
 
 
+THRESHOLDS = (0, 1, 16, 17, 63, 64, 70)               # off, ranked (short, 16, long, longest), every shape, beyond
+
+
+def test_slice_window_follows_the_scans_every_shape_rule_for_any_bc7_settings(itw):
+    """the one BC7 route predicate reachable without a device: a BC7 call is `heavy` -- its window half as many slices' worth -- exactly when
+    modes 0/2 are on, modes 1/3 are on with a positive list length, and neither list is a proper prefix of the ranking (1..63)"""
+    if "ITW_SLICE_WINDOW" in os.environ or os.environ.get("ITW_SLICED_PIPELINE") == "0" or os.environ.get("ITW_BC7_BOUND", "1")[:1] == "0":
+        pytest.skip("the environment presets the window or the mode order")
+    L = itw.lib()
+    ranked = lambda t: 1 <= t <= 63
+    seen = set()
+    for bits in range(16):
+        for channels in (3, 4):
+            for t1 in THRESHOLDS:
+                for t3 in THRESHOLDS:
+                    for t7 in THRESHOLDS:
+                        s = itw.bc7_profile("slow")
+                        for i in range(4):
+                            s.mode_selection[i] = bool(bits >> i & 1)
+                        s.fastSkipTreshold_mode1, s.fastSkipTreshold_mode3, s.fastSkipTreshold_mode7, s.channels = t1, t3, t7, channels
+                        heavy = bool(bits & 1) and bool(bits & 2) and (t1 > 0 or t3 > 0) and not ranked(t1) and not ranked(t3)
+                        seen.add(heavy)
+                        for code, w, h, sp in ((98, 4096, 4096, 4096), (99, 2048, 2050, 0)):
+                            got = L.itwSliceWindowFor(code, C.cast(C.byref(s), C.c_void_p), w, h, sp)
+                            assert got == _window(code, heavy, w, h, sp), (bits, channels, t1, t3, t7, code, got)
+    assert seen == {False, True}
+    assert _window(98, True, 4096, 4096, 4096) != _window(98, False, 4096, 4096, 4096)      # the sweep's sizes tell the two apart
+    assert _window(99, True, 2048, 2050, 0) != _window(99, False, 2048, 2050, 0)
+
+
 def test_bytes_per_block_chain_bytes_and_bands_agree_with_the_table(itw):
     L = itw.lib()
     for code in CODES:
