@@ -12,8 +12,9 @@
 // The host layer, top to bottom: ThreadCtx (per-thread streams, staging buffers, the workspace; release() frees all of it) -- Job (a BcnKind
 // of bcn_format.hpp plus the settings; every size and rule that follows from the format is read from that table, the geometry of a surface
 // from its surface_geometry) -- claim_workspace / workspace_used (the one way the workspace changes streams) -- launch() (format -> kernel
-// launcher) -- compress() (one call: resident, combined, windows, or staged runs) -- window_target_blocks / slice_window (the one window
-// size) -- WindowPipeline + run_windows (the one pipeline: compress_sliced's windows and chain_groups' groups) -- the small-call combiner --
+// launcher, in a LaunchShape) -- host_route() + compress() (one call: resident, combined, windows, or staged runs) -- window_target_blocks /
+// slice_window (the one window size) -- WindowPipeline + run_windows (the one pipeline: compress_sliced's windows and chain_groups' groups) --
+// compress_single_run / compress_runs (the staged runs, cut by host_runs.hpp; several runs borrow the pipeline) -- the small-call combiner --
 // presets -- the extern "C" entry points.
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -34,6 +35,7 @@
 #include <vector>
 #include "bcn_format.hpp"
 #include "host_rt.hpp"
+#include "host_runs.hpp"
 #include "kernels.hpp"
 #include "x86_math.hpp"
 
@@ -219,8 +221,8 @@ void* claim_workspace(size_t bytes, hipStream_t st)
 // the workspace is used up to here on `st` (what the next claim from another stream waits for)
 void workspace_used(hipStream_t st) { ITW_CHECK(hipEventRecord(tls.ws_event, st)); }
 
-// `staged`: a run of a host-pointer call.  Its upload / download overlap the neighbouring runs' kernels.  A BC7 run that is not a band
-// (compress() below: round 4's shape, and what content that needs modes 1/3 everywhere still gets) takes the wide shape up to 2^20
+// A staged run of a host-pointer call: its upload / download overlap the neighbouring runs' kernels.  A BC7 run that is not a band
+// (compress_runs() below: round 4's shape, and what content that needs modes 1/3 everywhere still gets) takes the wide shape up to 2^20
 // blocks -- scans and single-subset modes side by side on two streams fill the gaps between runs better than a chain of dependent
 // launches on one stream (8.75 -> 7.89 ms for a 4096^2 `slow` call in round 2).  Device-resident calls keep the deep shape above
 // 262144 blocks (a fifth of the HBM traffic and workspace).
@@ -256,10 +258,18 @@ void ensure_bc7_aux()
     tls.verdict.host_counts_dev = static_cast<int32_t*>(d);
 }
 
-// `band` >= 0: a staged run of a host-pointer BC7 call that compress() overlaps with its neighbours on two streams; it runs in the deep
-// shape on `st` alone, in its own slice of the per-thread workspace (`ws_off`), which compress() has reserved and ordered.
-void launch(const Job& j, const uint8_t* d_src, int64_t stride, int w, int h, uint8_t* d_dst, hipStream_t st, bool staged = false, int band = -1,
-            size_t ws_off = 0)
+// How launch() runs a BC7 surface; every other format ignores it (BC6H claims its own workspace).  WHOLE and STAGED claim the workspace on
+// `st` and record its event behind the kernels; a staged run -- one of a host-pointer call's, above -- takes the wide shape up to
+// staged_wide_max_blocks().  A BAND runs in the deep shape on `st` alone (Bc7Aux::single), in the slice of the workspace at `ws_off`, which the
+// caller has claimed and ordered: a run that compress_runs() overlaps with its neighbours on two streams, a window, a chain's group.
+// VERDICT_BAND also leaves the pilot's estimate for the host (tls.verdict); a PROBE leaves the estimate alone and encodes nothing (the run
+// itself took the wide shape).
+struct LaunchShape {
+    enum Kind { WHOLE, STAGED, BAND, VERDICT_BAND, PROBE } kind = WHOLE;
+    size_t ws_off = 0;
+};
+
+void launch(const Job& j, const uint8_t* d_src, int64_t stride, int w, int h, uint8_t* d_dst, hipStream_t st, LaunchShape shape = {})
 {
     switch (j.kind) {
     case itw::BCN_NONE: break;                        // (job_of has refused it)
@@ -267,23 +277,22 @@ void launch(const Job& j, const uint8_t* d_src, int64_t stride, int w, int h, ui
     case itw::BCN_BC3:  itw::launch_bc3(d_src, stride, w, h, d_dst, st); break;
     case itw::BCN_BC7:
         ensure_bc7_aux();
-        tls.aux.wide_max_blocks = staged ? staged_wide_max_blocks() : 0;
+        tls.aux.wide_max_blocks = shape.kind == LaunchShape::WHOLE ? 0 : staged_wide_max_blocks();
         {
             // the per-call fields of the shared aux block go back to their defaults however this call ends (a failure is a C++ exception here,
             // and under ITW_ON_ERROR_RETURN the thread lives on)
             struct Reset { itw::Bc7Aux& a; ~Reset() { a.single = false; a.verdict = nullptr; a.probe = false; } } reset{tls.aux};
-            tls.aux.single = band >= 0 || band == -2;
+            tls.aux.single = shape.kind >= LaunchShape::BAND;
+            void* ws = tls.d_ws;
             if (tls.aux.single) {
-                // band 0 leaves the pilot's estimate for the host; band -2 is a PROBE: the estimate alone (the run itself takes the wide shape)
-                tls.aux.verdict = (band == 0 || band == -2) ? &tls.verdict : nullptr;
-                tls.aux.probe = band == -2;
+                tls.aux.verdict = shape.kind >= LaunchShape::VERDICT_BAND ? &tls.verdict : nullptr;
+                tls.aux.probe = shape.kind == LaunchShape::PROBE;
                 if (tls.aux.verdict) tls.verdict.valid = false;
-                itw::launch_bc7(d_src, stride, w, h, d_dst, *j.s7, reinterpret_cast<float*>(static_cast<uint8_t*>(tls.d_ws) + ws_off), st, &tls.aux);
             } else {
-                void* ws = claim_workspace(itw::bc7_workspace_bytes(w, h, tls.aux.wide_max_blocks, j.s7), st);   // (sized and ordered already when ws_off != 0)
-                itw::launch_bc7(d_src, stride, w, h, d_dst, *j.s7, reinterpret_cast<float*>(static_cast<uint8_t*>(ws) + ws_off), st, &tls.aux);
-                workspace_used(st);
+                ws = claim_workspace(itw::bc7_workspace_bytes(w, h, tls.aux.wide_max_blocks, j.s7), st);
             }
+            itw::launch_bc7(d_src, stride, w, h, d_dst, *j.s7, reinterpret_cast<float*>(static_cast<uint8_t*>(ws) + shape.ws_off), st, &tls.aux);
+            if (!tls.aux.single) workspace_used(st);
         }
         break;
     case itw::BCN_BC6H: {
@@ -329,206 +338,59 @@ void upload_rows(uint8_t* d_rows, size_t pitch, const uint8_t* hs, int64_t strid
     }
 }
 
+// The route of one call, decided once.  `resident`: both pointers are the device's -- launched on the caller's stream, asynchronous.
+// `combinable`: both are host memory -- the call is first offered to the combiner (below), which joins small calls made concurrently by
+// several host threads into one.  What the combiner does not take, and every mixed call: `windows` >= 2 windows of the window pipeline
+// (compress_sliced with no callback; `leave_verdict`: the first one also counts the pilot's estimate), or, `windows` == 0, the staged runs.
+struct HostRoute { bool resident = false, combinable = false; int windows = 0; bool leave_verdict = false; };
+struct HostKnobs { const char *chunks, *runs, *windows_off; };       // ITW_HOST_CHUNKS, ITW_HOST_RUNS, ITW_HOST_WINDOWS_OFF as the environment has them (null: unset)
+
+HostRoute host_route(const Job& j, const itw::SurfaceGeometry& geo, bool src_dev, bool dst_dev, bool staged_wide, const HostKnobs& env)
+{
+    HostRoute r;
+    r.resident = src_dev && dst_dev;
+    r.combinable = !src_dev && !dst_dev;
+    // Round 6: a large BC6H call, and a large BC7 call of a profile without an order verdict (everything but `slow`), takes the WINDOW pipeline
+    // of the slice loop (compress_sliced below) with no callback: windows of ~131 072 blocks alternate between two kernel streams with the
+    // neighbours' copies on the third -- measured against the staged runs at 4096^2: BC6H `slow` 4.83 -> 4.3 ms, BC7 `alpha_basic` 3.31 -> 2.9,
+    // `alpha_veryfast` 2.46 -> 2.0, `basic` 3.93 -> 3.6 (profiles/r06_host_pointer_path.txt, r06_sliced_timing.jsonl).  The tuning knobs of the runs keep the runs.
+    if (!r.combinable || itw::keeps_partial_blocks(j.kind) || env.chunks || env.runs || env.windows_off) return r;
+    const bool bc7 = j.kind == itw::BCN_BC7, bc6h = j.kind == itw::BCN_BC6H;
+    const int64_t blocks = geo.blocks();
+    // A profile WITH an order verdict (`slow`) takes the windows while the last estimate says the bounded order pays (each window runs it on one
+    // stream: 5.6 against 6.05 ms for the staged runs on the bench surface) and the staged runs -- whose remaining runs go wide -- while it
+    // says nearly every block needs modes 1/3 (photographs: 7.3 against 7.6 ms as windows).  Either way the call leaves a fresh estimate.
+    const bool verdict_profile = bc7 && itw::bc7_has_order_verdict(*j.s7);
+    const bool bc7w = bc7 && blocks >= bc7_window_min_blocks() && itw::bc7_staged_bands_ok() && (!verdict_profile || !staged_wide);
+    const bool bc6w = bc6h && blocks >= 262144 && j.s6->slow_mode;    // (the other BC6H profiles are PCIe-bound: 2.98 vs 3.02 ms, fewer copies win)
+    if (!bc7w && !bc6w) return r;
+    const int64_t per_window = window_target_blocks(j.kind, heavy_job(j));
+    int64_t windows = (blocks + per_window / 2) / per_window;
+    if (windows > geo.by) windows = geo.by;
+    if (windows >= 2) { r.windows = (int)windows; r.leave_verdict = bc7w && verdict_profile; }
+    return r;
+}
+
+void compress_single_run(const Job& j, const rgba_surface* src, uint8_t* dst, const itw::SurfaceGeometry& geo, bool src_dev, bool dst_dev);
+void compress_runs(const Job& j, const rgba_surface* src, uint8_t* dst, const itw::SurfaceGeometry& geo, bool dst_dev, const itw::HostRuns& runs);
+
 void compress(const Job& j, const rgba_surface* src, uint8_t* dst, bool may_coalesce = true)
 {
     if (may_coalesce) itw::clear_failure();
     if (!src) itw::fail_msg("null surface");
-    const int w = src->width, h = src->height;
-    const itw::SurfaceGeometry geo = itw::surface_geometry(j.kind, w, h);
+    const itw::SurfaceGeometry geo = itw::surface_geometry(j.kind, src->width, src->height);
     if (geo.empty()) return;                          // nothing to encode: the reference's loops do not run either
     if (!src->ptr || !dst) itw::fail_msg("null texel or destination pointer");
-    const bool bc7 = j.kind == itw::BCN_BC7, bc6h = j.kind == itw::BCN_BC6H;
-    const int bx = geo.bx, by = geo.by, bpb = geo.bpb;
-    const size_t row_bytes = geo.row_bytes, rows = geo.rows, out_bytes = geo.out_bytes, pitch = geo.pitch;
+    const bool src_dev = is_device_pointer(src->ptr), dst_dev = is_device_pointer(dst);
+    const HostKnobs env{std::getenv("ITW_HOST_CHUNKS"), std::getenv("ITW_HOST_RUNS"), std::getenv("ITW_HOST_WINDOWS_OFF")};
+    const HostRoute route = host_route(j, geo, src_dev, dst_dev, tls.staged_wide, env);
 
-    const bool src_dev = is_device_pointer(src->ptr);
-    const bool dst_dev = is_device_pointer(dst);
-
-    if (src_dev && dst_dev) {                         // resident pipeline: asynchronous
-        launch(j, src->ptr, src->stride, w, h, dst, tls.user_stream);
-        return;
-    }
-    // small host-pointer calls made concurrently by several host threads are joined into one (below)
-    if (may_coalesce && !src_dev && !dst_dev && coalesce_small_call(j, src, dst, geo.blocks())) return;
-
-    // Round 6: a large BC6H call, and a large BC7 call of a profile without an order verdict (everything but `slow`), takes the WINDOW pipeline
-    // of the slice loop (compress_sliced below) with no callback: windows of ~131 072 blocks alternate between two kernel streams with the
-    // neighbours' copies on the third -- measured against the runs below at 4096^2: BC6H `slow` 4.83 -> 4.3 ms, BC7 `alpha_basic` 3.31 -> 2.9,
-    // `alpha_veryfast` 2.46 -> 2.0, `basic` 3.93 -> 3.6 (profiles/r06_host_pointer_path.txt, r06_sliced_timing.jsonl).  The tuning knobs of the runs keep the runs.
-    if (!src_dev && !dst_dev && !itw::keeps_partial_blocks(j.kind) && !std::getenv("ITW_HOST_CHUNKS") && !std::getenv("ITW_HOST_RUNS") && !std::getenv("ITW_HOST_WINDOWS_OFF")) {
-        const int64_t blocks = geo.blocks();
-        // A profile WITH an order verdict (`slow`) takes the windows while the last estimate says the bounded order pays (each window runs it on one
-        // stream: 5.6 against 6.05 ms for the staged runs below on the bench surface) and the staged runs -- whose remaining runs go wide -- while it
-        // says nearly every block needs modes 1/3 (photographs: 7.3 against 7.6 ms as windows).  Either way the call leaves a fresh estimate.
-        const bool verdict_profile = bc7 && itw::bc7_has_order_verdict(*j.s7);
-        const bool bc7w = bc7 && blocks >= bc7_window_min_blocks() && itw::bc7_staged_bands_ok() && (!verdict_profile || !tls.staged_wide);
-        const bool bc6w = bc6h && blocks >= 262144 && j.s6->slow_mode;    // (the other BC6H profiles are PCIe-bound: 2.98 vs 3.02 ms, fewer copies win)
-        if (bc7w || bc6w) {
-            const int64_t per_window = window_target_blocks(j.kind, heavy_job(j));
-            int64_t windows = (blocks + per_window / 2) / per_window;
-            if (windows > by) windows = by;
-            if (windows >= 2) { (void)compress_sliced(j, src, dst, (int)windows, nullptr, nullptr, 1, nullptr, bc7w && verdict_profile); return; }
-        }
-    }
-
-    ensure_device_ctx();
-    hipStream_t st = tls.own_stream, cs = tls.copy_stream;
-    if (src_dev && tls.user_stream != st) {
-        // producer of the device surface may still be running on the caller's stream
-        ITW_CHECK(hipStreamSynchronize(tls.user_stream));
-    }
-    uint8_t* in = src_dev ? nullptr : (uint8_t*)grow(tls.d_in, tls.in_cap, pitch * rows);
-    const uint8_t* d_src = src_dev ? src->ptr : in;
-    const int64_t d_stride = src_dev ? (int64_t)src->stride : (int64_t)pitch;
-    uint8_t* d_dst = dst_dev ? dst : (uint8_t*)grow(tls.d_out, tls.out_cap, out_bytes);
-
-    // BC7 / BC6H spend milliseconds per surface: cut the call into runs of block rows so that the upload of run c+1 and
-    // the download of run c-1 (copy stream; a pageable copy blocks only this host thread) overlap the kernels of run c.
-    // A run must still fill the chip several times over (one block per lane: 1024 workgroups = one round of the BC7
-    // scans), or the kernels' tails cost more than the copies save -- measured at 4096^2 (tools/history/misc/host_chunks_probe.py):
-    // BC7 slow 9.58 / 9.19 / 9.60 / 11.6 ms for 1 / 2 / 4 / 8 runs, BC6H slow 7.61 / 6.15 / 5.64 / 5.57 ms.
-    // BC1/3/4/5 are PCIe-bound: one run.
-    // Runs need not be equal: a SHORT FIRST run starts the kernels after an eighth of the upload instead of half of it,
-    // and a shorter last run shortens the download nothing can hide (ITW_HOST_RUNS="f0,f1,.." gives the fractions).
-    int cut[9] = {0, by, 0, 0, 0, 0, 0, 0, 0};        // run c covers block rows [cut[c], cut[c+1])
-    int nch = 1;
-    if (!src_dev && (bc7 || bc6h)) {
-        if (bc7 && (int64_t)bx * by >= 524288)       { nch = 3; cut[1] = by / 8; cut[2] = by / 8 + by / 2; cut[3] = by; }
-        else if (bc6h && (int64_t)bx * by >= 262144) { nch = 4; cut[1] = by / 8; cut[2] = by * 3 / 8; cut[3] = by * 11 / 16; cut[4] = by; }
-    }
-    if (const char* e = std::getenv("ITW_HOST_CHUNKS")) {         // tuning / test knob (1..8 equal runs); 1 disables the overlap
-        const int v = std::atoi(e);
-        if (v >= 1 && v <= 8 && !src_dev && by >= 4 * v) { nch = v; for (int c = 0; c <= v; c++) cut[c] = (int)((int64_t)by * c / v); }
-    }
-    if (const char* e = std::getenv("ITW_HOST_RUNS")) {           // tuning knob: cumulative fractions "0.125,0.625" -> 3 runs
-        int n = 0; double f[8];
-        for (const char* p = e; *p && n < 7;) { char* q = nullptr; f[n] = std::strtod(p, &q); if (q == p) break; n++; p = (*q == ',') ? q + 1 : q; }
-        if (n > 0 && !src_dev && by >= 64) {
-            nch = n + 1; cut[0] = 0; cut[nch] = by;
-            for (int c = 0; c < n; c++) { int r = (int)(by * f[c]); cut[c + 1] = r < cut[c] + 1 ? cut[c] + 1 : (r > by - (n - c) ? by - (n - c) : r); }
-        }
-    }
-    // Round 5: the runs of a BC7 call are BANDS -- run c's kernels go to stream (c + 1) % 2 (the first, short run to the second stream),
-    // each run in the deep shape with its own slice of the workspace, so that one run's launch tails are filled by its neighbour's work as
-    // soon as that neighbour's texels have arrived (the device-resident path does the same with the two halves of a surface, bc7.hip).
-    // Content where nearly every block still needs modes 1/3 (photographs) gains nothing from the bounded order, and for it the WIDE shape,
-    // one run after the other, overlaps staged runs better (8.1 against 7.4 ms per 4096^2 call, profiles/history/r05/r05c_*).  Which it is comes
-    // from the pilot's estimate (bc7.hip bc7_pilot_estimate): counted behind the first run's {0,2} scan when that run is a band, by a
-    // probe on the second stream when it is wide.  The host never waits for it: the first run takes the shape the PREVIOUS call's
-    // estimate asked for (successive calls of a save -- mip levels, slices -- hold similar content), later runs this call's as soon as
-    // it is in (polled under the uploads), and it is read once more behind the call's last synchronisation for the next call.
-    // ITW_STAGED_BANDS=0: round 4's runs, one after the other in the wide shape.
-    const bool bands = bc7 && nch > 1 && !src_dev && itw::bc7_staged_bands_ok();
-    size_t band_off[9] = {0}, probe_off = 0;                 // workspace: [wide runs (they follow each other on st)] [probe] [band 0] [band 1] ...
-    if (bands) {
-        ensure_bc7_aux();
-        size_t total = 0;
-        for (int c = 0; c < nch; c++) {
-            const int run_rows = (cut[c + 1] - cut[c]) * 4;
-            if (run_rows <= 0) continue;
-            const size_t b = (itw::bc7_workspace_bytes(w, run_rows, staged_wide_max_blocks(), j.s7) + 255) & ~(size_t)255;
-            if (b > total) total = b;
-        }
-        probe_off = total;
-        total += (itw::bc7_workspace_bytes(w, (cut[1] - cut[0]) * 4, 1, j.s7) + 255) & ~(size_t)255;
-        for (int c = 0; c < nch; c++) {
-            band_off[c] = total;
-            const int run_rows = (cut[c + 1] - cut[c]) * 4;
-            if (run_rows > 0) total += (itw::bc7_workspace_bytes(w, run_rows, 1, j.s7) + 255) & ~(size_t)255;
-        }
-        (void)claim_workspace(total, st);
-        ITW_CHECK(hipEventRecord(tls.aux.fork, st));          // the other streams start behind whatever ordered the workspace on the first
-        ITW_CHECK(hipStreamWaitEvent(tls.aux.stream, tls.aux.fork, 0));
-    } else
-    if (bc7 || bc6h) {
-        // Size the workspace once for the most demanding run: growing it frees it, and hipFree waits for the runs in flight.
-        // "Most demanding" is not "tallest" (ADVICE r02): a staged BC7 run of up to 2^20 blocks takes the wide shape at ~440
-        // B/block while a taller one takes the deep shape at 36 B/block, so the maximum is taken over every run's own need.
-        const int64_t wide_max = (!src_dev && !dst_dev) ? staged_wide_max_blocks() : 0;
-        size_t need = 0;
-        for (int c = 0; c < nch; c++) {
-            const int run_rows = (cut[c + 1] - cut[c]) * 4;
-            if (run_rows <= 0) continue;
-            const size_t b = bc7 ? itw::bc7_workspace_bytes(w, run_rows, wide_max, j.s7) : itw::bc6h_workspace_bytes(w, run_rows, *j.s6);
-            if (b > need) need = b;
-        }
-        if (need) (void)claim_workspace(need, st);
-    }
-    // A failure below is a C++ exception (and under ITW_ON_ERROR_RETURN the thread lives on): whatever this call has queued by then on the
-    // thread's streams is drained and the workspace's event recorded, so the next call finds d_in / d_out / d_ws free of work in flight.
-    struct Unwind {
-        bool done; hipStream_t a, b, c;
-        ~Unwind() {
-            if (done) return;
-            (void)hipStreamSynchronize(a); (void)hipStreamSynchronize(b);
-            if (c) (void)hipStreamSynchronize(c);
-            if (tls.ws_event && tls.ws_used) (void)hipEventRecord(tls.ws_event, a);
-            (void)hipGetLastError();
-        }
-    } unwind{false, st, cs, tls.aux.stream};
-    hipStream_t copy = (nch > 1) ? cs : st;
-    bool shape_wide = bands && tls.staged_wide && itw::bc7_has_order_verdict(*j.s7);   // the shape of the next run (profiles without a verdict: bands)
-    bool verdict_pending = false;
-    auto poll_verdict = [&](bool wait) {                      // this call's estimate, if it is in (or, `wait`: now that everything is done)
-        if (!verdict_pending || !tls.verdict.valid) return;
-        if (!wait && hipEventQuery(tls.verdict.event) != hipSuccess) { (void)hipGetLastError(); return; }
-        if (wait) ITW_CHECK(hipEventSynchronize(tls.verdict.event));
-        // the event has fired: the estimate kernel's last workgroup wrote the two counts into this thread's pinned words before it ended
-        const int32_t counts[2] = {tls.verdict.host_counts[0], tls.verdict.host_counts[1]};
-        if (counts[1] > 0) tls.staged_wide = (int64_t)counts[0] * 100 > (int64_t)staged_verdict_percent() * counts[1];
-        verdict_pending = false;
-    };
-    int c = 0;
-    for (c = 0; c < nch; c++) {
-        const int row0 = cut[c], nb = cut[c + 1] - cut[c];
-        const size_t y0 = (size_t)row0 * 4;
-        const size_t nrows = (rows - y0 < (size_t)nb * 4) ? rows - y0 : (size_t)nb * 4;
-        if (bands && c > 0 && verdict_pending) { poll_verdict(false); if (!verdict_pending) shape_wide = tls.staged_wide; }
-        hipStream_t run_st = (bands && !shape_wide && ((c + 1) & 1)) ? tls.aux.stream : st;
-        if (!src_dev) {
-            upload_rows(in + y0 * pitch, pitch, src->ptr + (int64_t)y0 * src->stride, src->stride, row_bytes, nrows, copy);
-            if (nch > 1) {
-                ITW_CHECK(hipEventRecord(tls.ev_in[c], cs));
-                ITW_CHECK(hipStreamWaitEvent(run_st, tls.ev_in[c], 0));
-            }
-        }
-        const uint8_t* run_src = d_src + (int64_t)y0 * d_stride;
-        uint8_t* run_dst = d_dst + (size_t)row0 * bx * bpb;
-        if (bands && !shape_wide) launch(j, run_src, d_stride, w, (int)nrows, run_dst, run_st, true, c, band_off[c]);
-        else                      launch(j, run_src, d_stride, w, (int)nrows, run_dst, run_st, !src_dev && !dst_dev);
-        if (bands && c == 0 && shape_wide) {
-            // the first run went wide: the estimate comes from a probe on the second stream, behind that run's single-subset modes
-            ITW_CHECK(hipStreamWaitEvent(tls.aux.stream, tls.ev_in[0], 0));
-            launch(j, run_src, d_stride, w, (int)nrows, run_dst, tls.aux.stream, true, -2, probe_off);
-        }
-        if (bands && c == 0) verdict_pending = tls.verdict.valid;
-        if (!dst_dev && nch > 1) {
-            ITW_CHECK(hipEventRecord(tls.ev_done[c], run_st));
-            if (c > 0) {                               // download the previous run while this one computes
-                const size_t off = (size_t)cut[c - 1] * bx * bpb, len = (size_t)(cut[c] - cut[c - 1]) * bx * bpb;
-                ITW_CHECK(hipStreamWaitEvent(cs, tls.ev_done[c - 1], 0));
-                ITW_CHECK(hipMemcpyAsync(dst + off, d_dst + off, len, hipMemcpyDeviceToHost, cs));
-            }
-        }
-    }
-    if (!dst_dev) {
-        if (nch > 1) {
-            const size_t off = (size_t)cut[c - 1] * bx * bpb;
-            ITW_CHECK(hipStreamWaitEvent(cs, tls.ev_done[c - 1], 0));
-            ITW_CHECK(hipMemcpyAsync(dst + off, d_dst + off, out_bytes - off, hipMemcpyDeviceToHost, cs));
-            ITW_CHECK(hipStreamSynchronize(cs));
-        } else {
-            ITW_CHECK(hipMemcpyAsync(dst, d_dst, out_bytes, hipMemcpyDeviceToHost, st));
-        }
-    }
-    if (bands) {                                              // everything back into st; the workspace's event behind all of it
-        ITW_CHECK(hipEventRecord(tls.aux.join, tls.aux.stream));
-        ITW_CHECK(hipStreamWaitEvent(st, tls.aux.join, 0));
-        workspace_used(st);
-    }
-    ITW_CHECK(hipStreamSynchronize(st));
-    unwind.done = true;
-    if (bands) poll_verdict(true);                            // for the next call, if it was not in before
+    if (route.resident) { launch(j, src->ptr, src->stride, src->width, src->height, dst, tls.user_stream); return; }
+    if (may_coalesce && route.combinable && coalesce_small_call(j, src, dst, geo.blocks())) return;
+    if (route.windows) { (void)compress_sliced(j, src, dst, route.windows, nullptr, nullptr, 1, nullptr, route.leave_verdict); return; }
+    const itw::HostRuns runs = itw::host_runs(j.kind, geo.bx, geo.by, !src_dev, env.chunks, env.runs);
+    if (runs.n == 1) compress_single_run(j, src, dst, geo, src_dev, dst_dev);
+    else             compress_runs(j, src, dst, geo, dst_dev, runs);
 }
 
 // ---- the plugin's slice loop as a pipeline (include/itw_dispatch.h: itwCompressImageSlicedEx) -----------------------------
@@ -606,6 +468,7 @@ SliceRows slice_rows(int i, int slices, int height, bool keep_partial)
 // kernels are ordered through a ring of 8 event pairs indexed by the caller's LOCAL window number k (at most depth + 1 <= 5 windows are
 // between issue and retire).  The object waits for all three streams when it goes out of scope: however the call ends (a failure is a C++
 // exception here), nothing of it is left in flight on the thread's streams and buffers, and the workspace's event lies behind it.
+// The staged runs of one call (compress_runs) take the same streams, ring and drain, with a workspace layout and a stream per run of their own.
 struct WindowPipeline {
     hipStream_t k0, k1, cs;
     size_t ws_off[2] = {0, 0};
@@ -622,10 +485,10 @@ struct WindowPipeline {
         if (bc7_slice_bytes) {
             const size_t b = (bc7_slice_bytes + 255) & ~(size_t)255;
             ws_off[1] = b;
-            (void)claim_workspace(2 * b, k0);
-            ws_claimed = true;
+            claim(2 * b);
         }
     }
+    void claim(size_t bytes) { (void)claim_workspace(bytes, k0); ws_claimed = true; }   // the workspace in a layout of the caller's, ahead of fork()
     WindowPipeline(const WindowPipeline&) = delete;
     ~WindowPipeline()
     {
@@ -639,22 +502,44 @@ struct WindowPipeline {
         ITW_CHECK(hipEventRecord(tls.aux.fork, k0));
         ITW_CHECK(hipStreamWaitEvent(k1, tls.aux.fork, 0));
     }
+    void join() const                   // ... and everything on it back into the first
+    {
+        ITW_CHECK(hipEventRecord(tls.aux.join, k1));
+        ITW_CHECK(hipStreamWaitEvent(k0, tls.aux.join, 0));
+    }
     hipStream_t stream(int k) const { return (k & 1) ? k1 : k0; }
     size_t workspace(int k) const { return ws_off[k & 1]; }
-    void uploaded(int k) const          // window k's texels are queued on the copy stream: its kernels wait for them
-    {
-        ITW_CHECK(hipEventRecord(tls.ev_in[k & 7], cs));
-        ITW_CHECK(hipStreamWaitEvent(stream(k), tls.ev_in[k & 7], 0));
-    }
-    void encoded(int k) const { ITW_CHECK(hipEventRecord(tls.ev_done[k & 7], stream(k))); }      // everything of window k is queued
+    // Window k's texels are queued on the copy stream: its kernels (on `ks`: the staged runs pick their own stream) wait for them.
+    void after_upload(int k, hipStream_t ks) const { ITW_CHECK(hipStreamWaitEvent(ks, tls.ev_in[k & 7], 0)); }
+    void uploaded(int k, hipStream_t ks) const { ITW_CHECK(hipEventRecord(tls.ev_in[k & 7], cs)); after_upload(k, ks); }
+    void uploaded(int k) const { uploaded(k, stream(k)); }
+    void encoded(int k, hipStream_t ks) const { ITW_CHECK(hipEventRecord(tls.ev_done[k & 7], ks)); }   // everything of window k is queued
+    void encoded(int k) const { encoded(k, stream(k)); }
     void wait_encoded(int k) const { ITW_CHECK(hipEventSynchronize(tls.ev_done[k & 7])); }       // a window written where it belongs
-    void fetch(int k, void* dst, const void* staged, size_t len, hipMemcpyKind kind) const       // a staged window: returns when it is in `dst`
+    void queue_fetch(int k, void* dst, const void* staged, size_t len, hipMemcpyKind kind) const // a staged window's download behind its kernels
     {
         ITW_CHECK(hipStreamWaitEvent(cs, tls.ev_done[k & 7], 0));
         ITW_CHECK(hipMemcpyAsync(dst, staged, len, kind, cs));
+    }
+    void fetch(int k, void* dst, const void* staged, size_t len, hipMemcpyKind kind) const       // ... returns when it is in `dst`
+    {
+        queue_fetch(k, dst, staged, len, kind);
         ITW_CHECK(hipStreamSynchronize(cs));
     }
 };
+
+// The pilot's estimate of the last VERDICT_BAND or PROBE, once its event has fired (`wait`: now; otherwise only if it already has): the estimate
+// kernel's last workgroup wrote the two counts into this thread's pinned words before it ended.  What the next staged BC7 call's first run
+// and route go by (tls.staged_wide).  False while there is nothing to read.
+bool read_verdict(bool wait)
+{
+    if (!tls.verdict.valid) return false;
+    if (wait) ITW_CHECK(hipEventSynchronize(tls.verdict.event));
+    else if (hipEventQuery(tls.verdict.event) != hipSuccess) { (void)hipGetLastError(); return false; }
+    const int32_t listed = tls.verdict.host_counts[0], sampled = tls.verdict.host_counts[1];
+    if (sampled > 0) tls.staged_wide = (int64_t)listed * 100 > (int64_t)staged_verdict_percent() * sampled;
+    return true;
+}
 
 // The driver: `depth` windows AHEAD of the one being retired are issued.  With two, when window k-1's kernels end, window k is running on the
 // other stream and window k+1 -- same stream as k-1, behind it in stream order -- already has its texels on the device.  (With one window of
@@ -667,6 +552,8 @@ struct WindowPipeline {
 //   one window    one slice window, and a chain's lone group, run the ordinary call shape (compress() / launch() pick it by size), not a pipeline
 //   the verdict   only the slice loop's first window may leave the pilot's estimate (`leave_verdict`)
 //   stopping      only a share of the slice loop (one pipeline per GPU, dispatch.hip) is stopped from outside
+//   staged runs   compress_runs (below) takes the pipeline's streams, events and drain but not this driver: nobody is reported to between its
+//                 runs, so the host never waits there -- every run and download is queued, then the call waits once
 template <class Stopped, class Issue, class Retire, class Report>
 bool run_windows(int n, int depth, Stopped&& stopped, Issue&& issue, Retire&& retire, Report&& report)
 {
@@ -678,6 +565,110 @@ bool run_windows(int n, int depth, Stopped&& stopped, Issue&& issue, Retire&& re
         if (!report(k)) return false;
     }
     return true;
+}
+
+// ---- the staged runs of a host-pointer call (compress() above: what is neither resident, combined nor windows) -------------------------
+// One run: BC1/3/4/5 and ETC1 of any size (PCIe-bound), every small BC7 / BC6H call, every call with a device source.  Upload, kernels and
+// download follow each other on the thread's own stream; no second stream, no pinned words: the plug-in's 64 pool threads make such calls.
+void compress_single_run(const Job& j, const rgba_surface* src, uint8_t* dst, const itw::SurfaceGeometry& geo, bool src_dev, bool dst_dev)
+{
+    ensure_device_ctx();
+    hipStream_t st = tls.own_stream;
+    if (src_dev && tls.user_stream != st) ITW_CHECK(hipStreamSynchronize(tls.user_stream));   // the producer of the device surface may still be running on the caller's stream
+    uint8_t* in = src_dev ? nullptr : (uint8_t*)grow(tls.d_in, tls.in_cap, geo.pitch * geo.rows);
+    uint8_t* d_dst = dst_dev ? dst : (uint8_t*)grow(tls.d_out, tls.out_cap, geo.out_bytes);
+    const LaunchShape shape{(!src_dev && !dst_dev) ? LaunchShape::STAGED : LaunchShape::WHOLE};
+    // the workspace ahead of the upload (growing it frees it, and hipFree waits for the device); launch() finds it claimed
+    const size_t need = j.kind == itw::BCN_BC7  ? itw::bc7_workspace_bytes(src->width, geo.by * 4, shape.kind == LaunchShape::STAGED ? staged_wide_max_blocks() : 0, j.s7)
+                      : j.kind == itw::BCN_BC6H ? itw::bc6h_workspace_bytes(src->width, geo.by * 4, *j.s6) : 0;
+    if (need) (void)claim_workspace(need, st);
+    // A failure below is a C++ exception (and under ITW_ON_ERROR_RETURN the thread lives on): whatever this call has queued by then is drained
+    // and the workspace's event recorded, so the next call finds d_in / d_out / d_ws free of work in flight.
+    struct Drain {
+        bool done; hipStream_t st;
+        ~Drain() {
+            if (done) return;
+            (void)hipStreamSynchronize(st);
+            if (tls.aux.stream) (void)hipStreamSynchronize(tls.aux.stream);
+            if (tls.ws_event && tls.ws_used) (void)hipEventRecord(tls.ws_event, st);
+            (void)hipGetLastError();
+        }
+    } drain{false, st};
+    if (!src_dev) upload_rows(in, geo.pitch, src->ptr, src->stride, geo.row_bytes, geo.rows, st);
+    launch(j, src_dev ? src->ptr : in, src_dev ? (int64_t)src->stride : (int64_t)geo.pitch, src->width, (int)geo.rows, d_dst, st, shape);
+    if (!dst_dev) ITW_CHECK(hipMemcpyAsync(dst, d_dst, geo.out_bytes, hipMemcpyDeviceToHost, st));
+    ITW_CHECK(hipStreamSynchronize(st));
+    drain.done = true;
+}
+
+// Several runs (itw::host_runs: large BC7 / BC6H calls from host memory, and what the knobs ask for), on a WindowPipeline's streams, events and
+// drain: run c's upload and run c-1's download on the copy stream overlap run c's kernels.
+// Round 5: the runs of a BC7 call are BANDS -- run c's kernels go to stream (c + 1) % 2 (the first, short run to the second stream),
+// each run in the deep shape with its own slice of the workspace, so that one run's launch tails are filled by its neighbour's work as
+// soon as that neighbour's texels have arrived (the device-resident path does the same with the two halves of a surface, bc7.hip).
+// Content where nearly every block still needs modes 1/3 (photographs) gains nothing from the bounded order, and for it the WIDE shape,
+// one run after the other, overlaps staged runs better (8.1 against 7.4 ms per 4096^2 call, profiles/history/r05/r05c_*).  Which it is comes
+// from the pilot's estimate (bc7.hip bc7_pilot_estimate): counted behind the first run's {0,2} scan when that run is a band, by a
+// probe on the second stream when it is wide.  The host never waits for it: the first run takes the shape the PREVIOUS call's
+// estimate asked for (successive calls of a save -- mip levels, slices -- hold similar content), later runs this call's as soon as
+// it is in (polled under the uploads), and it is read once more behind the call's last synchronisation for the next call.
+// ITW_STAGED_BANDS=0: round 4's runs, one after the other in the wide shape.
+void compress_runs(const Job& j, const rgba_surface* src, uint8_t* dst, const itw::SurfaceGeometry& geo, bool dst_dev, const itw::HostRuns& runs)
+{
+    const int w = src->width;
+    const bool bc7 = j.kind == itw::BCN_BC7, bc6h = j.kind == itw::BCN_BC6H;
+    const size_t pitch = geo.pitch, block_row = (size_t)geo.bx * geo.bpb;
+    const bool bands = bc7 && itw::bc7_staged_bands_ok();
+    const LaunchShape wide{dst_dev ? LaunchShape::WHOLE : LaunchShape::STAGED};
+    const int64_t wide_max = dst_dev ? 0 : staged_wide_max_blocks();
+
+    WindowPipeline pipe(false, 0);                           // (a run's source is host memory: nothing of the caller's to wait for)
+    hipStream_t st = pipe.k0;
+    uint8_t* in = (uint8_t*)grow(tls.d_in, tls.in_cap, pitch * geo.rows);
+    uint8_t* d_dst = dst_dev ? dst : (uint8_t*)grow(tls.d_out, tls.out_cap, geo.out_bytes);
+    itw::BandWorkspace ws;
+    if (bands) {
+        ws = itw::band_workspace(runs, [&](int rows, bool as_wide) { return itw::bc7_workspace_bytes(w, rows, as_wide ? staged_wide_max_blocks() : 1, j.s7); });
+        pipe.claim(ws.total);
+        pipe.fork();                                         // the other streams start behind whatever ordered the workspace on the first
+    } else if (bc7 || bc6h) {
+        // sized once for the most demanding run: growing it frees it, and hipFree waits for the runs in flight
+        const size_t need = itw::host_runs_workspace(runs, [&](int rows) { return bc7 ? itw::bc7_workspace_bytes(w, rows, wide_max, j.s7) : itw::bc6h_workspace_bytes(w, rows, *j.s6); });
+        if (need) pipe.claim(need);
+    }
+    bool shape_wide = bands && tls.staged_wide && itw::bc7_has_order_verdict(*j.s7);   // the shape of the next run (profiles without a verdict: bands)
+    bool verdict_pending = false;
+    for (int c = 0; c < runs.n; c++) {
+        const size_t y0 = (size_t)runs.cut[c] * 4;
+        const size_t nrows = std::min(geo.rows - y0, (size_t)runs.rows(c));
+        if (c > 0 && verdict_pending && read_verdict(false)) { verdict_pending = false; shape_wide = tls.staged_wide; }   // this call's estimate, if it is in
+        const bool band = bands && !shape_wide;
+        hipStream_t run_st = (band && ((c + 1) & 1)) ? pipe.k1 : st;
+        upload_rows(in + y0 * pitch, pitch, src->ptr + (int64_t)y0 * src->stride, src->stride, geo.row_bytes, nrows, pipe.cs);
+        pipe.uploaded(c, run_st);
+        const uint8_t* run_src = in + y0 * pitch;
+        uint8_t* run_dst = d_dst + (size_t)runs.cut[c] * block_row;
+        launch(j, run_src, (int64_t)pitch, w, (int)nrows, run_dst, run_st, band ? LaunchShape{c == 0 ? LaunchShape::VERDICT_BAND : LaunchShape::BAND, ws.band_off[c]} : wide);
+        if (bands && c == 0 && shape_wide) {
+            // the first run went wide: the estimate comes from a probe on the second stream, behind that run's texels
+            pipe.after_upload(0, pipe.k1);
+            launch(j, run_src, (int64_t)pitch, w, (int)nrows, run_dst, pipe.k1, LaunchShape{LaunchShape::PROBE, ws.probe_off});
+        }
+        if (bands && c == 0) verdict_pending = tls.verdict.valid;
+        if (dst_dev) continue;
+        pipe.encoded(c, run_st);
+        if (c > 0) {                                         // download the previous run while this one computes
+            const size_t off = (size_t)runs.cut[c - 1] * block_row;
+            pipe.queue_fetch(c - 1, dst + off, d_dst + off, (size_t)(runs.cut[c] - runs.cut[c - 1]) * block_row, hipMemcpyDeviceToHost);
+        }
+    }
+    if (!dst_dev) {
+        const size_t off = (size_t)runs.cut[runs.n - 1] * block_row;
+        pipe.fetch(runs.n - 1, dst + off, d_dst + off, geo.out_bytes - off, hipMemcpyDeviceToHost);
+    }
+    if (bands) { pipe.join(); workspace_used(st); }          // everything back into the first stream; the workspace's event behind all of it
+    ITW_CHECK(hipStreamSynchronize(st));
+    if (verdict_pending) (void)read_verdict(true);           // for the next call, if it was not in before
 }
 
 // returns true when every slice was encoded, false when `progress` stopped the job
@@ -751,8 +742,8 @@ bool compress_sliced(const Job& j, const rgba_surface* src, uint8_t* dst, int sl
             upload_rows(in + (size_t)v.y0 * pitch, pitch, src->ptr + v.y0 * (int64_t)src->stride, src->stride, geo.row_bytes, nrows, pipe.cs);
             pipe.uploaded(i);
         }
-        launch(j, d_src + v.y0 * d_stride, d_stride, w, (int)nrows, d_dst + (size_t)v.row0 * block_row, pipe.stream(i), true,
-               bc7 ? ((leave_verdict && i == 0) ? 0 : 1) : -1, pipe.workspace(i));
+        launch(j, d_src + v.y0 * d_stride, d_stride, w, (int)nrows, d_dst + (size_t)v.row0 * block_row, pipe.stream(i),
+               LaunchShape{(leave_verdict && i == 0) ? LaunchShape::VERDICT_BAND : LaunchShape::BAND, pipe.workspace(i)});
         pipe.encoded(i);
     };
     auto retire = [&](int i) {                            // the window's bytes into `dst`; returns when they are there
@@ -771,11 +762,7 @@ bool compress_sliced(const Job& j, const rgba_surface* src, uint8_t* dst, int sl
     static const int depth = [] { const char* e = std::getenv("ITW_SLICE_LOOKAHEAD"); const int v = e ? std::atoi(e) : 2; return v < 1 ? 1 : (v > 4 ? 4 : v); }();
     auto stopped = [&] { return share && share->stop && share->stop->load(std::memory_order_acquire); };
     if (!run_windows(nlocal, depth, stopped, issue, retire, report)) return false;
-    if (leave_verdict && tls.verdict.valid) {            // the first window's estimate, for the next call (its kernel is long done: every window has been retired)
-        ITW_CHECK(hipEventSynchronize(tls.verdict.event));
-        const int32_t listed = tls.verdict.host_counts[0], sampled = tls.verdict.host_counts[1];
-        if (sampled > 0) tls.staged_wide = (int64_t)listed * 100 > (int64_t)staged_verdict_percent() * sampled;
-    }
+    if (leave_verdict) (void)read_verdict(true);         // the first window's estimate, for the next call (its kernel is long done: every window has been retired)
     return true;
 }
 
@@ -916,8 +903,8 @@ bool chain_groups(const Job& j, const rgba_surface* im, uint8_t* target, const s
         const int64_t pitch = (int64_t)G.pbx * 4 * px;
         uint8_t* packed = d_in + G.packed_off;
         itw::launch_chain_gather(d_desc + (G.i0 - units[u0].i0), G.i1 - G.i0, G.nb, G.pbx, G.pby, px, fill45, packed, pitch, ks, nullptr, normal_ops);
-        if (lone) launch(j, packed, pitch, G.pbx * 4, G.pby * 4, d_out + G.out_off, ks, !src_dev && !dst_dev);
-        else      launch(j, packed, pitch, G.pbx * 4, G.pby * 4, d_out + G.out_off, ks, true, bc7_slices ? 1 : -1, pipe.workspace(g));
+        launch(j, packed, pitch, G.pbx * 4, G.pby * 4, d_out + G.out_off, ks,
+               lone ? LaunchShape{(!src_dev && !dst_dev) ? LaunchShape::STAGED : LaunchShape::WHOLE} : LaunchShape{LaunchShape::BAND, pipe.workspace(g)});
         if (dst_dev) ITW_CHECK(hipMemcpyAsync(target + G.b0 * bpb, d_out + G.out_off, (size_t)G.nb * bpb, hipMemcpyDeviceToDevice, ks));
         pipe.encoded(g);
     };
