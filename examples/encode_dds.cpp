@@ -27,6 +27,12 @@
 //     the load path (IntelPlugin.cpp:2461-2561): header -> every image of the file through ONE itwDecodeChain -> texels.  out.raw holds
 //     every image's texels one after another in file order, tightly packed (RGBA8; RGBA16F bit patterns for BC6H; int8 codes for the
 //     SNORM pair); one line on stdout per image: index, width, height, min alpha (the smallest decoded alpha code: IsAlphaAllOpaque).
+//
+//   encode_dds --preview <in.dds | in.ktx> <image index> <out.ppm> <w> <h> <x> <y> <zoom> [channels] [exposure] [matte]
+//     the preview path (IntelPlugin::FetchPreviewRGB): a w x h viewport of ONE image of the file (itwDdsImage / itwKtxImage's index), decoded
+//     only where the viewport looks (itwPreviewBlocks), written as a binary PPM.  x, y: the viewport's offset in its own pixels; zoom: source
+//     texels per viewport pixel (the caller divides by 1 << mip level to show a mip at the base image's scale); channels: letters of rgba
+//     (default rgb); exposure: BC6H only (default 1); matte: 0xBBGGRR outside the image (default 0).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -202,11 +208,60 @@ int decode_file(const char* in_path, const char* out_path)
     return 0;
 }
 
+// encode_dds --preview: one image of the file, the part of it a viewport shows; args: index, out.ppm, w, h, x, y, zoom [channels exposure matte]
+int preview_file(const char* in_path, int argc, char** args)
+{
+    FILE* in = std::fopen(in_path, "rb");
+    if (!in) { std::fprintf(stderr, "cannot read %s\n", in_path); return 1; }
+    std::vector<uint8_t> file;
+    uint8_t buf[65536];
+    for (size_t n; (n = std::fread(buf, 1, sizeof buf, in)) > 0;) file.insert(file.end(), buf, buf + n);
+    std::fclose(in);
+    static const uint8_t ktx_id[12] = {0xAB, 0x4B, 0x54, 0x58, 0x20, 0x31, 0x31, 0xBB, 0x0D, 0x0A, 0x1A, 0x0A};
+    const bool ktx = file.size() >= 12 && std::memcmp(file.data(), ktx_id, 12) == 0;
+    ItwDdsDesc desc = {};
+    ItwKtxDesc kdesc = {};
+    if (ktx ? !itwKtxReadHeader(file.data(), file.size(), &kdesc) : !itwDdsReadHeader(file.data(), file.size(), &desc)) {
+        std::fprintf(stderr, "%s: not a DDS / KTX file this library reads\n", in_path);
+        return 1;
+    }
+    const int format = ktx ? (int)kdesc.gl_internal_format : (int)desc.dxgi_format;
+    uint32_t w = 0, h = 0; size_t off = 0;
+    const uint32_t index = (uint32_t)std::strtoul(args[0], nullptr, 10);
+    const size_t n = ktx ? itwKtxImage(&kdesc, index, &w, &h, &off) : itwDdsImage(&desc, index, &w, &h, &off);
+    if (!n) { std::fprintf(stderr, "%s has no image %u\n", in_path, index); return 1; }
+    if (file.size() < off + n) { std::fprintf(stderr, "%s: truncated: %zu bytes, image %u ends at %zu\n", in_path, file.size(), index, off + n); return 1; }
+    itw_preview_view view = {};
+    view.width = std::atoi(args[2]); view.height = std::atoi(args[3]);
+    view.x_offset = std::atoi(args[4]); view.y_offset = std::atoi(args[5]);
+    view.zoom = std::atof(args[6]);
+    for (const char* c = argc > 7 ? args[7] : "rgb"; *c; c++)
+        view.options |= *c == 'r' ? ITW_PREVIEW_CHANNEL_RED : *c == 'g' ? ITW_PREVIEW_CHANNEL_GREEN : *c == 'b' ? ITW_PREVIEW_CHANNEL_BLUE : *c == 'a' ? ITW_PREVIEW_CHANNEL_ALPHA : 0u;
+    view.exposure = argc > 8 ? (float)std::atof(args[8]) : 1.0f;
+    view.matte_color = argc > 9 ? (uint32_t)std::strtoul(args[9], nullptr, 0) : 0u;
+    if (view.width < 1 || view.width > 16384 || view.height < 1 || view.height > 16384) { std::fprintf(stderr, "a viewport is 1 .. 16384 pixels each way\n"); return 2; }
+    std::vector<uint8_t> rgb((size_t)view.width * view.height * 3);
+    itwSetErrorMode(ITW_ON_ERROR_RETURN);
+    if (itwPreviewBlocks(format, file.data() + off, (int)w, (int)h, &view, sizeof view, rgb.data(), (int64_t)view.width * 3) != 0) {
+        std::fprintf(stderr, "%s\n", itwLastError() ? itwLastError() : "itwPreviewBlocks refused the call (a format that is not previewed, an offset or zoom out of range)");
+        return 1;
+    }
+    FILE* out = std::fopen(args[1], "wb");
+    if (!out || std::fprintf(out, "P6\n%d %d\n255\n", view.width, view.height) < 0 || std::fwrite(rgb.data(), 1, rgb.size(), out) != rgb.size()) {
+        std::fprintf(stderr, "cannot write %s\n", args[1]);
+        return 1;
+    }
+    std::fclose(out);
+    std::fprintf(stderr, "%s: image %u (%ux%u) -> %dx%d viewport at (%d, %d), zoom %g\n", args[1], index, w, h, view.width, view.height, view.x_offset, view.y_offset, view.zoom);
+    return 0;
+}
+
 } // namespace
 
 int main(int argc, char** argv)
 {
     if (argc == 4 && std::strcmp(argv[1], "--decode") == 0) return decode_file(argv[2], argv[3]);
+    if (argc >= 10 && argc <= 13 && std::strcmp(argv[1], "--preview") == 0) return preview_file(argv[2], argc - 3, argv + 3);
     bool measure = false;
     const char* refine_profile = nullptr;
     unsigned long long max_block_sse = 0;
@@ -251,7 +306,8 @@ int main(int argc, char** argv)
         std::fprintf(stderr, "usage: %s [--measure] [--refine <profile> <max_block_sse> | --refine-share <profile> <percent> | --refine-psnr <profile> <dB>]\n"
                              "          [--normal flipx,flipy,normalize] [--cube-cross]\n"
                              "          <format> <width> <height> <in.raw> <out.dds> [slice_pixels]\n"
-                             "       %s --decode <in.dds | in.ktx> <out.raw>\n", argv[0], argv[0]);
+                             "       %s --decode <in.dds | in.ktx> <out.raw>\n"
+                             "       %s --preview <in.dds | in.ktx> <image index> <out.ppm> <w> <h> <x> <y> <zoom> [channels] [exposure] [matte]\n", argv[0], argv[0], argv[0]);
         return 2;
     }
     const Format* f = nullptr;

@@ -72,6 +72,70 @@ int itwDecodeChain(int dxgi_format, const uint8_t* blocks, const rgba_surface* o
 /* a chain of one */
 int itwDecodeImage(int dxgi_format, const uint8_t* blocks, const rgba_surface* out, int32_t* modes, uint32_t* min_alpha);
 
+/* ---- a viewport of an image, decoded where it is looked at -----------------------------------------------------------------------------
+ * What the reference's preview dialog asks of IntelPlugin::FetchPreviewRGB (IntelPlugin.cpp:487-739) on every zoom, pan, channel toggle
+ * or exposure change: a width x height RGB8 viewport of an image, nearest sampled.  Only the blocks the viewport looks at are decoded.
+ * With W x H the image and (xt, yt) a viewport pixel, every step integer or IEEE arithmetic:
+ *  1. fx = (double)(xt + x_offset) * zoom, one double multiply.  The pixel is outside when fx <= -1.0 or fx >= W; otherwise x = (int)fx,
+ *     truncated toward zero, so -1 < fx < 0 shows column 0 and not the matte: what the reference's int(...) followed by `x < 0` does
+ *     (:632-639).  The comparison comes first: a product beyond the int range is outside.  y likewise with H.  The bound is W, H and not
+ *     the padded size: padding texels of edge blocks are never shown.
+ *  2. Outside, the three bytes are matte_color & 0xFF, (matte_color >> 8) & 0xFF, (matte_color >> 16) & 0xFF.
+ *  3. Channels (:585-624 with four planes).  m = options & ITW_PREVIEW_CHANNEL_MASK, and m == 0 reads as RED | GREEN | BLUE.  m exactly one
+ *     of RED / GREEN / BLUE / ALPHA: all three bytes show that channel, and for ALPHA alone the exposure is taken as 1.  Any other m: byte 0
+ *     shows R if RED is set, byte 1 G if GREEN is set, byte 2 B if BLUE is set -- and if ALPHA is set byte 2 shows A instead, whether or not
+ *     BLUE is set: the reference's `channelIndex[2] = 3` (:610-611), kept as its behaviour.  A byte with no channel is 0.
+ *  4. Value.  RGBA8 texels: the code itself, no exposure (:732-734).  RGBA16F texels (BC6H, and texel_bytes 8): v = (float)half * exposure as
+ *     one fp32 multiply, d = (double)v, then d > 1 -> 255, d < 0 -> 0, NaN -> 0 (what the reference's cast gives on x86), otherwise
+ *     (uint8_t)(d * 255.0), the product in double, truncated (FloatToByte, IntelPlugin.h:41-48; :676-678).  For BC6H this is also the
+ *     reference's 32-bit-document route (:628-654, ConvertTo8Bit(x, false)), since DirectXTex widens the same halves.
+ *     A decoded texel is exactly what itwDecodeImage stores, filled channels included: BC4 (R,0,0,255), BC6H alpha 0x3C00, ETC1 alpha 255. */
+#define ITW_PREVIEW_CHANNEL_RED   0x04   /* the reference's PREVIEW_OPTIONS values, IntelPlugin.h:248-261 */
+#define ITW_PREVIEW_CHANNEL_GREEN 0x08
+#define ITW_PREVIEW_CHANNEL_BLUE  0x10
+#define ITW_PREVIEW_CHANNEL_ALPHA 0x20
+#define ITW_PREVIEW_CHANNEL_MASK  0x3C
+
+typedef struct itw_preview_view {
+    int32_t  width, height;        /* viewport, pixels: 1 .. 16384 each */
+    int32_t  x_offset, y_offset;   /* the reference's xo, yo: |value| <= 2^30 */
+    double   zoom;                 /* source texels per viewport pixel (the reference passes 1.f / previewZoom, and divides by
+                                      1 << mipLevel when it shows a mip: that division is the caller's); finite, > 0 */
+    uint32_t options;              /* channel bits; bits outside ITW_PREVIEW_CHANNEL_MASK are ignored; no channel bit = RGB */
+    uint32_t matte_color;          /* 0x00BBGGRR */
+    float    exposure;             /* half-float sources only */
+    uint32_t _pad;
+} itw_preview_view;
+
+/* Which of the kernel's two routes a call takes, from view->zoom alone.  zoom <= this: a workgroup owns a 64 x 16 tile of viewport pixels,
+ * decodes each block under the tile once into LDS and samples from there (magnified views and views near 1:1, where a texel is shown
+ * several times or neighbours share a block).  Above it: every lane decodes the block of its own pixel and keeps one texel.  At zoom 2 a
+ * tile's footprint is at most 33 x 9 blocks, which is what the workgroup's LDS holds. */
+#define ITW_PREVIEW_TILE_MAX_ZOOM 2.0
+
+/* itwPreviewBlocks: the compressed pane.  `blocks`: the ceil(width/4) * ceil(height/4) blocks, raster order, of ONE image of any size >= 1
+ * (an image of a chain; of a DDS / KTX payload via itwDdsImage / itwKtxImage).  dxgi_format: 71, 72, 77, 78, 80, 83, 95, 98, 99 or
+ * ITW_FORMAT_ETC1_RGB8; BC4S / BC5S (81, 84) and BC6H_SF16 (96) are refused (the reference previews neither).
+ * itwPreviewSurface: the original pane, through the same sampling code with a plain load in place of the decode.  source: RGBA8
+ * (texel_bytes 4) or RGBA16F bit patterns (texel_bytes 8), any size >= 1, stride >= the row's bytes; a device source has ptr and stride
+ * aligned to the texel (a host source: any).
+ * out_rgb: height rows of width RGB8 pixels, out_stride >= 3 * width bytes apart, at any byte address; exactly 3 * width bytes of each row
+ * are written and nothing else (dword stores where a row's address allows, bytes at a row's ends and for unaligned rows).
+ * `view` is read at call time and travels as kernel arguments.  `blocks` / source->ptr and out_rgb are host or device pointers in any mix
+ * (a device `blocks` is at least 4-byte aligned).  Everything on the device: one launch, asynchronous on the calling thread's stream
+ * (itwSetStream); the call allocates nothing, touches no buffer of the thread and can be captured into a graph.  A host out_rgb is staged
+ * through the thread's decode buffer (the one itwDecodeChain uses) and 3 * width bytes per row are copied back; of a host `blocks` only
+ * the block rows the viewport can reach are uploaded (y is monotone in yt: one contiguous range of the stream), of a host source only those
+ * texel rows, and nothing when the viewport misses the image.  Calls with a host pointer return synchronised.
+ * Returns 0; -1 before any device work for an unknown or refused format, a null pointer, view_bytes != sizeof(itw_preview_view), a viewport
+ * size or offset outside the ranges above, a zoom that is not finite and positive, an image size < 1 or more than ITW_MEASURE_MAX_BLOCKS
+ * blocks, out_stride < 3 * width, a texel_bytes other than 4 or 8, or a source stride below its row; -1 after a device failure (reported
+ * through the library's error mode, itw_amd.h). */
+int itwPreviewBlocks(int dxgi_format, const uint8_t* blocks, int width, int height,
+                     const itw_preview_view* view, size_t view_bytes, uint8_t* out_rgb, int64_t out_stride);
+int itwPreviewSurface(const rgba_surface* source, int texel_bytes, const itw_preview_view* view, size_t view_bytes, uint8_t* out_rgb,
+                      int64_t out_stride);
+
 /* ---- measuring an encoded stream against its source ------------------------------------------------------------------------------
  * What a caller would compute by decoding the stream (the decoders above, at the padded size) and comparing the texels of `source`
  * with the decoded ones, code by code, as integers -- done in one kernel that decodes into registers, so the decoded surface never

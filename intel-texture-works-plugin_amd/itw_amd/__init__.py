@@ -16,6 +16,7 @@ from .abi import (  # noqa: F401
     available, set_error_mode, last_error, ON_ERROR_ABORT, ON_ERROR_RETURN, set_bc7_path, set_bc7_pilot, compress_image_multigpu, multigpu_sub_bands, MultiGpuStats, source_sha256, bc7_two_subset_bounds, bc7_rotation_bounds,
     chain_bytes, compress_chain, mip_chain, decode_chain, decode_image, load_dds, dds_images,
     KtxDesc, ktx_file, ktx_images, load_ktx,
+    PreviewView, PREVIEW_CHANNEL, PREVIEW_CHANNEL_MASK, PREVIEW_TILE_MAX_ZOOM, preview_view, preview, preview_surface,
     ErrorStats, OWN_CHANNELS, measure, measure_async, measure_chain, stats_from_tensor,
     RefineStats, compress_refined, RefinePolicy, RefineTargetStats, compress_refined_to, psnr_to_total_sse,
     compress_chain_refined, compress_chain_refined_to, chain_psnr_to_total_sse,

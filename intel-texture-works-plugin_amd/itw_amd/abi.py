@@ -32,7 +32,7 @@ EXPORTED_SYMBOLS = tuple(
     # include/itw_bc45.h: the DirectXTex formats of the plugin
     + ["CompressBlocksBC4", "CompressBlocksBC5", "itwWarmupBC45", "CompressBlocksBC4S", "CompressBlocksBC5S", "itwWarmupBC45S", "itwCompressNormalMapBC5"]
     # include/itw_decode.h: device decoders
-    + ["itwDecodeBlocks", "itwDecodeChain", "itwDecodeImage", "itwMeasureBlocks", "itwMeasureChain", "itwStatsPsnr"]
+    + ["itwDecodeBlocks", "itwDecodeChain", "itwDecodeImage", "itwMeasureBlocks", "itwMeasureChain", "itwStatsPsnr", "itwPreviewBlocks", "itwPreviewSurface"]
     # include/itw_dds.h: DDS container
     + ["itwDdsLevelBytes", "itwDdsHeaderBytes", "itwDdsFileBytes", "itwDdsWriteHeader", "itwDdsReadHeader", "itwDdsWriteFile", "itwDdsImage"]
     # include/itw_dds.h, second part: KTX 1.1 container (ETC1)
@@ -137,6 +137,17 @@ def _channel_mask(channels):
         mask |= 1 << ("rgba".index(c.lower()) if isinstance(c, str) else int(c))
     assert 0 <= mask < 16
     return mask
+
+
+PREVIEW_CHANNEL = {"r": 0x04, "g": 0x08, "b": 0x10, "a": 0x20}     # ITW_PREVIEW_CHANNEL_* (itw_decode.h)
+PREVIEW_CHANNEL_MASK = 0x3C
+PREVIEW_TILE_MAX_ZOOM = 2.0                                        # ITW_PREVIEW_TILE_MAX_ZOOM: zoom <= this takes the kernel's tile route
+
+
+class PreviewView(C.Structure):
+    """struct itw_preview_view (itw_decode.h): the viewport of itwPreviewBlocks / itwPreviewSurface, 40 bytes."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("x_offset", C.c_int32), ("y_offset", C.c_int32), ("zoom", C.c_double),
+                ("options", C.c_uint32), ("matte_color", C.c_uint32), ("exposure", C.c_float), ("_pad", C.c_uint32)]
 
 
 class ErrorStats(C.Structure):
@@ -385,6 +396,10 @@ def _load(path, hooks):
         L.itwMeasureChain.restype = C.c_int
         L.itwStatsPsnr.argtypes = [C.POINTER(ErrorStats), C.c_uint32]
         L.itwStatsPsnr.restype = C.c_double
+        L.itwPreviewBlocks.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(PreviewView), C.c_size_t, C.c_void_p, C.c_int64]
+        L.itwPreviewBlocks.restype = C.c_int
+        L.itwPreviewSurface.argtypes = [C.POINTER(RgbaSurface), C.c_int, C.POINTER(PreviewView), C.c_size_t, C.c_void_p, C.c_int64]
+        L.itwPreviewSurface.restype = C.c_int
         # DDS container (itw_dds.h)
         L.itwDdsLevelBytes.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
         L.itwDdsLevelBytes.restype = C.c_size_t
@@ -1028,6 +1043,73 @@ def decode_image(fmt, blocks, size_or_out, want_modes=False, want_min_alpha=Fals
         raise ValueError("itwDecodeImage: " + (last_error() or "bad arguments"))
     res = (out,) + ((modes,) if want_modes else ()) + ((amin,) if want_min_alpha else ())
     return res[0] if len(res) == 1 else res
+
+
+def preview_view(view_w, view_h, x=0, y=0, zoom=1.0, channels="rgb", matte=0, exposure=1.0):
+    """A PreviewView.  channels: a string of the letters r, g, b, a (empty: RGB), or the option bits themselves."""
+    options = channels if isinstance(channels, int) else sum({PREVIEW_CHANNEL[c.lower()] for c in channels})
+    return PreviewView(view_w, view_h, x, y, zoom, options, matte, exposure, 0)
+
+
+def _preview_call(call, source, view, out):
+    """Runs call(view pointer, sizeof, out pointer, out stride) into `out` or a new (view_h, view_w, 3) uint8 array of `source`'s kind."""
+    import numpy as np
+    on_device = hasattr(source, "data_ptr")
+    shape = (view.height, view.width, 3)
+    if out is None:
+        if on_device:
+            import torch
+            out = torch.empty(shape, dtype=torch.uint8, device=source.device)
+        else:
+            out = np.empty(shape, dtype=np.uint8)
+    assert hasattr(out, "data_ptr") == on_device and tuple(out.shape) == shape, "the viewport is of the source's kind, (view_h, view_w, 3) uint8"
+    if on_device:
+        import torch
+        assert out.dtype == torch.uint8 and out.stride(2) == 1 and out.stride(1) == 3
+        with torch.cuda.device(source.device):
+            lib().itwSetStream(torch.cuda.current_stream(source.device).cuda_stream)
+            rc = call(C.byref(view), C.sizeof(view), out.data_ptr(), out.stride(0))
+    else:
+        assert out.dtype == np.uint8 and out.strides[2] == 1 and out.strides[1] == 3
+        rc = call(C.byref(view), C.sizeof(view), out.ctypes.data, out.strides[0])
+    return rc, out
+
+
+def preview(fmt, blocks, width, height, view_w, view_h, x=0, y=0, zoom=1.0, channels="rgb", matte=0, exposure=1.0, out=None):
+    """itwPreviewBlocks: a view_w x view_h RGB8 viewport of the width x height image whose blocks are `blocks` (uint8 numpy array: host
+    pointers; CUDA uint8 tensor: device pointers, torch's current stream, asynchronous), decoded only where the viewport looks.  x, y: the
+    viewport's offset in viewport pixels; zoom: source texels per viewport pixel; channels: letters of "rgba"; matte: 0x00BBGGRR; exposure:
+    bc6h only.  The definition is in include/itw_decode.h.  Returns a (view_h, view_w, 3) uint8 array of blocks' kind (`out`, if given; its
+    rows may be strided)."""
+    import numpy as np
+    base = _base(fmt)
+    if hasattr(blocks, "data_ptr"):
+        import torch
+        assert blocks.is_cuda and blocks.dtype == torch.uint8 and blocks.is_contiguous()
+        ptr, have = blocks.data_ptr(), blocks.numel()
+    else:
+        blocks = np.ascontiguousarray(blocks, dtype=np.uint8).reshape(-1)
+        ptr, have = blocks.ctypes.data, blocks.size
+    assert have >= ((width + 3) // 4) * ((height + 3) // 4) * BYTES_PER_BLOCK[base]
+    view = preview_view(view_w, view_h, x, y, zoom, channels, matte, exposure)
+    rc, out = _preview_call(lambda v, n, o, s: lib().itwPreviewBlocks(DXGI_FORMAT[fmt], ptr, width, height, v, n, o, s), blocks, view, out)
+    if rc != 0:
+        raise ValueError("itwPreviewBlocks: " + (last_error() or "bad arguments"))
+    return out
+
+
+def preview_surface(img, view_w, view_h, x=0, y=0, zoom=1.0, channels="rgb", matte=0, exposure=1.0, out=None):
+    """itwPreviewSurface: preview() of an (H, W, 4) surface of texels -- uint8 RGBA8, or uint16 (torch: int16) RGBA16F bit patterns, to which
+    `exposure` applies; numpy or CUDA tensor, rows may be strided."""
+    assert img.ndim == 3 and img.shape[2] == 4
+    texel = 4 * (img.element_size() if hasattr(img, "data_ptr") else img.itemsize)
+    assert texel in (4, 8), "RGBA8 or RGBA16F"
+    surf = _surfaces([img])
+    view = preview_view(view_w, view_h, x, y, zoom, channels, matte, exposure)
+    rc, out = _preview_call(lambda v, n, o, s: lib().itwPreviewSurface(surf, texel, v, n, o, s), img, view, out)
+    if rc != 0:
+        raise ValueError("itwPreviewSurface: " + (last_error() or "bad arguments"))
+    return out
 
 
 def dds_images(desc):
