@@ -3,6 +3,7 @@
 // the program links libispc_texcomp.so like the plugin links ispc_texcomp.lib.
 //
 //   encode_dds [--measure] [--refine <profile> <max_block_sse> | --refine-share <profile> <percent> | --refine-psnr <profile> <dB>]
+//              [--normal flipx,flipy,normalize] [--cube-cross] [--mips [levels]]
 //              <format> <width> <height> <in.raw> <out.dds> [slice_pixels]
 //     format : bc1 | bc3 | bc4 | bc5 | bc4_snorm | bc5_snorm | bc7_<profile> | bc6h_<profile> | etc1_slow      (profiles: the GetProfile_* names)
 //              etc1_slow: DDS has no code for ETC1, so the output is a KTX 1.1 file (itwKtx*, itw_dds.h); the slices go through itwCompressImageSlicedEx
@@ -21,6 +22,10 @@
 //                 other format through itwCompressNormalMapChain.  The slice loop is not used; not with --refine*.
 //     --cube-cross : the input is a horizontal (4 x 3 faces) or vertical (3 x 4) cube cross; its six faces (itwCubeCrossFaces: views, no
 //                 copy) are encoded by one chain call into a cube-map DDS.  Goes with --normal; not with --refine*, --measure or etc1_slow.
+//     --mips [levels] : a mipped file from the base image (or the six cross faces) in one call, itwCompressImageMipped: the save path's
+//                 order -- the flips of --normal on level 0, DirectXTex's box / linear mip filter, the normalise on every level, every image
+//                 encoded.  levels: how many, the base included (default: the full chain).  Every format; goes with --normal and
+//                 --cube-cross; not with --refine* or --measure.  The header carries the image's own size: level l is max(1, w >> l) wide.
 //
 //   encode_dds --decode <in.dds | in.ktx> <out.raw>
 //     (.dds or .ktx: told apart by the file's first bytes; a KTX file's images come in ITS order, level then face)
@@ -156,6 +161,55 @@ int encode_normal_or_cross(const Format& f, const rgba_surface& source, uint32_t
     return 0;
 }
 
+// encode_dds --mips: the base image (or its six cross faces) to a mipped DDS / KTX in one call; levels == 0: the full chain
+int encode_mipped(const Format& f, const rgba_surface& source, uint32_t ops, bool cube_cross, int levels, const char* out_path)
+{
+    const bool bc7 = std::strncmp(f.name, "bc7_", 4) == 0, bc6h = std::strncmp(f.name, "bc6h_", 5) == 0, etc1 = f.dxgi == ITW_FORMAT_ETC1_RGB8;
+    union { bc7_enc_settings s7; bc6h_enc_settings s6; etc_enc_settings se; } settings;
+    if (etc1) itwGetProfile_etc_slow(&settings.se);
+    else if ((bc7 || bc6h) && !profile_by_name(bc6h, f.name + (bc7 ? 4 : 5), &settings)) return 2;
+    rgba_surface bases[6] = {source};
+    int items = 1;
+    if (cube_cross) {
+        if (itwCubeCrossFaces(&source, f.texel_bytes, bases) != 0) { std::fprintf(stderr, "%d x %d is too small for a cube cross\n", source.width, source.height); return 2; }
+        items = 6;
+    }
+    const int w = bases[0].width, h = bases[0].height, full = itwMipLevels(w, h);
+    if (levels < 0 || levels > full) { std::fprintf(stderr, "--mips %d: a full chain of %d x %d has %d levels\n", levels, w, h, full); return 2; }
+    if (levels == 0) levels = full;
+    std::vector<rgba_surface> chain((size_t)items * levels);
+    if (itwMipChainLayout(w, h, items, levels, f.texel_bytes, nullptr, chain.data()) < 0) { std::fprintf(stderr, "bad size\n"); return 2; }
+    const int64_t bytes = itwChainBytes(chain.data(), items * levels, f.dxgi);      // (sizes only: the layout's pointers are offsets)
+    if (bytes <= 0) { std::fprintf(stderr, "bad size\n"); return 2; }
+    std::vector<uint8_t> blocks((size_t)bytes);
+    itwSetErrorMode(ITW_ON_ERROR_RETURN);
+    if (!itwCompressImageMipped(bases, items, levels, ops, blocks.data(), f.dxgi, &settings, nullptr, nullptr)) {
+        std::fprintf(stderr, "%s\n", itwLastError() ? itwLastError() : "compression failed");
+        return 1;
+    }
+    ItwDdsDesc desc = { (uint32_t)w, (uint32_t)h, (uint32_t)levels, (uint32_t)f.dxgi, cube_cross ? 1u : 0u, 1 };
+    ItwKtxDesc kdesc = { (uint32_t)w, (uint32_t)h, (uint32_t)levels, ITW_FORMAT_ETC1_RGB8, 0, 0 };
+    std::vector<uint8_t> file(etc1 ? itwKtxFileBytes(&kdesc) : itwDdsFileBytes(&desc));
+    std::vector<const uint8_t*> images((size_t)items * levels);      // DDS: face-major, then level -- the call's order; KTX here: one face
+    size_t at = 0;
+    for (size_t i = 0; i < images.size(); i++) {
+        images[i] = blocks.data() + at;
+        at += etc1 ? itwKtxImage(&kdesc, (uint32_t)i, nullptr, nullptr, nullptr) : itwDdsImage(&desc, (uint32_t)i, nullptr, nullptr, nullptr);
+    }
+    if (at != blocks.size() || file.empty()
+        || (etc1 ? itwKtxWriteFile(&kdesc, images.data(), images.size(), file.data(), file.size())
+                 : itwDdsWriteFile(&desc, images.data(), images.size(), file.data(), file.size())) != file.size()) {
+        std::fprintf(stderr, "%s assembly failed\n", etc1 ? "KTX" : "DDS");
+        return 1;
+    }
+    FILE* out = std::fopen(out_path, "wb");
+    if (!out || std::fwrite(file.data(), 1, file.size(), out) != file.size()) { std::fprintf(stderr, "cannot write %s\n", out_path); return 1; }
+    std::fclose(out);
+    DestroyThreads();
+    std::fprintf(stderr, "%s: %dx%d%s, %d levels -> %zu bytes (%s, normal ops %u)\n", out_path, w, h, cube_cross ? " x 6 faces" : "", levels, file.size(), f.name, ops);
+    return 0;
+}
+
 // encode_dds --decode: the whole file through one call
 int decode_file(const char* in_path, const char* out_path)
 {
@@ -269,6 +323,8 @@ int main(int argc, char** argv)
     double refine_value = 0.0;                                  // percent / dB
     bool normal_given = false, cube_cross = false;
     uint32_t normal_ops = 0;                                    // ITW_NORMAL_*
+    bool mips = false;
+    int mip_levels = 0;                                         // 0: the full chain
     for (int i = 1; i < argc; i++)
         if (std::strcmp(argv[i], "--measure") == 0) {
             measure = true;
@@ -301,10 +357,17 @@ int main(int argc, char** argv)
             cube_cross = true;
             for (int k = i; k + 1 < argc; k++) argv[k] = argv[k + 1];
             argc--; i--;
+        } else if (std::strcmp(argv[i], "--mips") == 0) {
+            mips = true;
+            const bool count = i + 1 < argc && argv[i + 1][0] != '\0' && std::strspn(argv[i + 1], "0123456789") == std::strlen(argv[i + 1]);
+            if (count) mip_levels = std::atoi(argv[i + 1]);
+            const int used = count ? 2 : 1;
+            for (int k = i; k + used < argc; k++) argv[k] = argv[k + used];
+            argc -= used; i--;
         }
     if (argc < 6) {
         std::fprintf(stderr, "usage: %s [--measure] [--refine <profile> <max_block_sse> | --refine-share <profile> <percent> | --refine-psnr <profile> <dB>]\n"
-                             "          [--normal flipx,flipy,normalize] [--cube-cross]\n"
+                             "          [--normal flipx,flipy,normalize] [--cube-cross] [--mips [levels]]\n"
                              "          <format> <width> <height> <in.raw> <out.dds> [slice_pixels]\n"
                              "       %s --decode <in.dds | in.ktx> <out.raw>\n"
                              "       %s --preview <in.dds | in.ktx> <image index> <out.ppm> <w> <h> <x> <y> <zoom> [channels] [exposure] [matte]\n", argv[0], argv[0], argv[0]);
@@ -322,6 +385,13 @@ int main(int argc, char** argv)
     std::fclose(in);
 
     rgba_surface source = { texels.data(), width, height, width * f->texel_bytes };
+    if (mips) {
+        if (refine_profile || measure || (cube_cross && f->dxgi == ITW_FORMAT_ETC1_RGB8)) {
+            std::fprintf(stderr, "--mips does not go with --refine* or --measure; --cube-cross not with etc1_slow\n");
+            return 2;
+        }
+        return encode_mipped(*f, source, normal_ops, cube_cross, mip_levels, argv[5]);
+    }
     if (normal_given || cube_cross) {
         // the normal-map and cube-cross stages of the save path (IntelPlugin.cpp:2075-2106, 2149-2152): one call over the image or its six faces
         if (refine_profile || (cube_cross && (measure || f->dxgi == ITW_FORMAT_ETC1_RGB8))) {

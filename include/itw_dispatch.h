@@ -347,6 +347,65 @@ bool itwCompressNormalMapChain(const rgba_surface* images, int count, uint8_t* t
  * than 4 x 3 (3 x 4 when vertical). */
 int itwCubeCrossFaces(const rgba_surface* cross, int pixel_size, rgba_surface faces[6]);
 
+/* Mip chains: GenerateMipMaps, the save path's fourth stage (IntelPlugin.cpp:2112-2146), on the device.
+ *
+ * Sizes.  Level l of a w x h base is max(1, w >> l) x max(1, h >> l); a full chain has 1 + floor(log2(max(w, h))) levels (_CountMips).
+ * Level l is filtered from level l-1 AS STORED, that is after rounding to the texel format.
+ * Filter.  The plugin passes TEX_FILTER_DEFAULT | TEX_FILTER_SEPARATE_ALPHA (plus TEX_FILTER_FORCE_NON_WIC for BC6H, :2117-2121); off
+ * the WIC path DEFAULT means BOX when the base's width and height are both powers of two, else LINEAR (DirectXTexMipmaps.cpp:2615, :2803),
+ * chosen once per chain from the base.  All four channels are filtered alike (the non-WIC filters have no premultiplied path, so
+ * SEPARATE_ALPHA changes nothing).  IEEE fp32, every operation rounded on its own, no contraction:
+ *   box     (_Generate2DMipsBoxFilter :715-805; AVERAGE4, Filters.h:33-39)  v = ((p0 + p1) + p2) + p3; v = v * 0.25f, with p0 = (row 2y,
+ *           column 2x), p1 = (2y+1, 2x), p2 = (2y, 2x+1), p3 = (2y+1, 2x+1); when the source height is 1, row 2y+1 is row 2y; when the
+ *           source width is 1, column 2x+1 is column 2x.
+ *   linear  (_Generate2DMipsLinearFilter :809-917; _CreateLinearFilter and BILINEAR_INTERPOLATE, Filters.h:66-106)  per axis, clamped, no
+ *           wrap: scale = float(source) / float(dest); srcB = (float(u) + 0.5f) * scale + 0.5f; isrcB = (ptrdiff_t)srcB; isrcA = isrcB - 1,
+ *           clamped to 0; isrcB clamped to source - 1; weight0 = 1.0f + float(isrcB) - srcB with the clamped isrcB, in the order written;
+ *           weight1 = 1.0f - weight0.  The texel is wy0 * (r0[u0]*wx0 + r0[u1]*wx1) + wy1 * (r1[u0]*wx0 + r1[u1]*wx1).
+ *   RGBA16F -- the pinned case: the reference forces these functions for BC6H.  Load: the half widened exactly.  Store
+ *           (DirectXTexConvert.cpp:1634-1646): clamp to [-65504, 65504], then float -> half by IEEE round to nearest even, the rule of
+ *           itwConvertToRGBA16FDevice.  A NaN result (the reference's XMVectorClamp passes it through) stores the one pattern 0x7E00.
+ *           +-Inf inputs make NaN under both filters (inf - inf, 0 * inf).
+ *   RGBA8   -- THE LIBRARY'S OWN RULE, pinned to no byte of the reference: on Windows the reference sends 8-bit chains through WIC's closed
+ *           Fant scaler, and DirectXMath's XMStoreUByteN4 is not part of its tree.  The same two filters on the raw codes as fp32 values
+ *           0..255 (no division by 255), stored as (uint8_t)min(v + 0.5f, 255.0f); for the box that is exactly (a + b + c + d + 2) >> 2.
+ *           The bytes of an RGBA8_SNORM surface are treated as codes like any other.
+ * Stated divergence.  The reference's box filter sets urow2 / urow3 once before its level loop (:740-741) and, once the height has reached 1,
+ * re-points only urow1 (:746-749): from the level where the height is 1 while the width is still above 1, urow3 reads the second scanline
+ * of an EARLIER level, which is no longer loaded (for a base of height 1: uninitialised storage).  Square and tall chains -- cube faces
+ * among them -- are not affected.  The library takes the evident intent, row 2y+1 is row 2y: p1 = p0 and p3 = p2, ((a + a) + b) + b.
+ *
+ * itwMipLevels: the length of a full chain; 0 for a width or height below 1.
+ * itwMipChainLayout: host arithmetic only.  Fills out[items * levels] in DDS order -- item-major, then level -- with tight rows, the images
+ * packed one after another from `storage`, and returns the bytes needed.  levels == 0 means the full chain.  storage == NULL and out == NULL
+ * is a size query (out alone: the pointers are the offsets).  -1 for a width or height below 1, items < 0, levels < 0 or above the full
+ * chain, a pixel_size other than 4 or 8, or a row above 2^31 - 1 bytes.
+ * itwGenerateMipChain: `images` is items * levels surfaces in that order; level 0 of each item holds the caller's texels and is never
+ * written; levels 1 and up are written, width x height only.  Any stride at least the row's bytes, so levels may be views of a larger
+ * canvas.  All pointers device or all host.  Device: asynchronous on the calling thread's stream.  Host: staged through the thread's
+ * buffer -- only the bases go up, only the written levels come back -- and the call returns synchronised.  Power-of-two chains take the
+ * pyramid route: a 64 x 64 tile of a level gives its part of the next six levels in one launch, a last launch takes a level of at most
+ * 64 x 64 down to 1 x 1 (a 4096^2 chain: two launches); ITW_MIP_PER_LEVEL forces one launch per level, as every other chain takes, for
+ * comparison and measurement.  Both routes write the same bytes.  Returns 0, also for items == 0 or levels <= 1 (nothing to do); -1,
+ * through the library's error mode and before any device work, for a pixel_size other than 4 or 8, an unknown flag bit, items < 0, a
+ * null pointer, a level whose size is not the definition's, items whose bases differ in size, levels above the full chain, a stride
+ * below the row's bytes, texels that are not pixel_size aligned, mixed host and device pointers, or more than one launch covers (more
+ * than 65 535 items, a base of more than 524 280 rows, more than 2^31 - 1 tiles of 64 x 64 over all items).
+ * itwCompressImageMipped: the save path from base images in one call.  `bases` (items of them, one size, host or device) are copied into
+ * level 0 of a device-side chain of `levels` levels (0: the full chain), then, IN THE REFERENCE'S ORDER: the flips of `normal_ops`
+ * (ITW_NORMAL_FLIP_X / _Y) on level 0 only, as FlipXYChannelNormalMap runs before the mips; the chain is generated; ITW_NORMAL_NORMALIZE on
+ * every level, as NormalizeNormalMapChain runs after them; the chain is encoded into `target` exactly as itwCompressImageChainEx encodes
+ * it (items * levels images in DDS order; itwChainBytes / itwDdsFileBytes give the size).  The bases are never written.  Formats, texel
+ * kinds, settings, progress contract (1 .. items * levels), pointer kinds of `target`, errors and return value are the chain call's; on
+ * top of them unknown ops bits, bases of different sizes, levels < 0 or above the full chain, misaligned texels, mixed pointer kinds
+ * and itwGenerateMipChain's launch limits fail through the error mode before any device work.  From host bases only the bases go up and only blocks come down. */
+enum { ITW_MIP_PER_LEVEL = 1 };
+int itwMipLevels(int width, int height);
+int64_t itwMipChainLayout(int width, int height, int items, int levels, int pixel_size, uint8_t* storage, rgba_surface* out);
+int itwGenerateMipChain(const rgba_surface* images, int items, int levels, int pixel_size, uint32_t flags);
+bool itwCompressImageMipped(const rgba_surface* bases, int items, int levels, uint32_t normal_ops, uint8_t* target, int dxgi_format,
+                            const void* settings, ItwProgressFunc* progress, void* user);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

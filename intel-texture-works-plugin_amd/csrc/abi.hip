@@ -1294,6 +1294,11 @@ void chain_check(const rgba_surface* images, int count, const uint8_t* target, i
     (void)chain_job(images, count, target, dxgi_format, dxgi_format == ITW_FORMAT_ETC1_RGB8 ? (const void*)&any_etc : (const void*)any_settings);
 }
 
+void chain_check_with(const rgba_surface* images, int count, const uint8_t* target, int dxgi_format, const void* settings)
+{
+    (void)chain_job(images, count, target, dxgi_format, settings);
+}
+
 void encode_resident(int dxgi_format, const void* settings, const uint8_t* d_src, int64_t stride, int width, int height, uint8_t* d_dst)
 {
     const Job j = job_of(dxgi_format, settings);

@@ -68,6 +68,9 @@ int sliced_windows(int dxgi_format, const void* settings, int width, int height,
 // the checks of itwCompressImageChain that need no device (counts, null pointers, sizes, strides, format), as a Failure; for the literal
 // loop of a caller's own CompressionFunc, which takes no settings
 void chain_check(const rgba_surface* images, int count, const uint8_t* target, int dxgi_format);
+// the same checks with the caller's settings, as itwCompressImageChainEx makes them (null BC7 / BC6H / ETC1 settings, the ETC1 threshold); for
+// itwCompressImageMipped, which must refuse before it builds the chain
+void chain_check_with(const rgba_surface* images, int count, const uint8_t* target, int dxgi_format, const void* settings);
 
 // What itwCompressImageRefined (refine.hip) needs of the calling thread's context.
 // encode_resident: the device-pointer path of CompressBlocksBC7 / BC6H -- same routing, same workspace -- for a format code and settings

@@ -1,0 +1,428 @@
+// mipgen.hip -- the fourth stage of the reference's save path, GenerateMipMaps (IntelPlugin.cpp:2112-2146), on the device: DirectXTex's
+// non-WIC box and linear 2D filters (include/itw_dispatch.h, "Mip chains"; the arithmetic is mipgen.hpp's), and the save path in one call
+// (itwCompressImageMipped).  Level l is filtered from the STORED level l-1, so a chain is a sequence of dependent steps; the work is a
+// stream, HBM bound, and its tail levels are launch latency.  Three kernels, all items (cube faces, array slices) in every launch:
+//   mip_pyramid_kernel  box.  One workgroup owns a 64 x 64 tile of a source level and writes that tile's part of the next six levels
+//                       (32^2 .. 1^2), each rounded to the texel format before the next is formed.  A lane loads a 4 x 4 patch as four row
+//                       reads (dwordx4 where the address allows), forms its 2 x 2 of level +1 and its texel of level +2 in registers; levels
+//                       +3 .. +6 go through LDS (5.3 KiB) with a barrier each.  No workgroup waits on another: the launch boundary is the
+//                       only dependency between tiles.
+//   mip_tail_kernel     box.  One workgroup per item takes a source level of at most 64 x 64 (any power-of-two width and height, 1 and
+//                       non-square included) down to 1 x 1; levels ping-pong between two LDS buffers of stored words (5 KiB).  A level of
+//                       64 x 64 is one tile of the pyramid kernel, so this kernel starts from 64 x 32 or 32 x 64 at the most.
+//   mip_level_kernel    box or linear, any size, one launch per level, one lane per texel written: the only route of the linear filter, the
+//                       comparison route of the box filter (ITW_MIP_PER_LEVEL), and the bridge of a power-of-two chain whose levels are
+//                       neither tileable (an axis below 64) nor small enough for the tail (the other above 64), e.g. 512 x 2.
+// A 4096^2 chain is two launches (4096 -> 64 over 4096 tiles, 64 -> 1 over one) where the per-level route takes twelve.
+#include <hip/hip_runtime.h>
+#include <algorithm>
+#include <cstdint>
+#include <vector>
+#include "../../include/itw_dispatch.h"
+#include "../../include/itw_amd.h"
+#include "mipgen.hpp"
+#include "bcn_format.hpp"
+#include "host_rt.hpp"
+
+namespace itw {
+
+// one image of a chain; the table holds items * levels of them in DDS order (item-major, then level)
+struct MipImage { uint8_t* ptr; int64_t stride; };
+
+// N consecutive texels at `p` (PX aligned): one vector access where the address allows, texel by texel otherwise
+template <int PX, int N>
+__device__ __forceinline__ void mip_load_row(const uint8_t* p, MipTexel* t)
+{
+    constexpr int W = N * PX / 4;
+    uint32_t w[W];
+    if (W >= 4 && ((uintptr_t)p & 15) == 0) {
+#pragma unroll
+        for (int i = 0; i < W / 4; i++) {
+            const uint4 v = reinterpret_cast<const uint4*>(p)[i];
+            w[4 * i] = v.x; w[4 * i + 1] = v.y; w[4 * i + 2] = v.z; w[4 * i + 3] = v.w;
+        }
+    } else if constexpr (PX == 8) {
+#pragma unroll
+        for (int i = 0; i < N; i++) { const uint2 v = reinterpret_cast<const uint2*>(p)[i]; w[2 * i] = v.x; w[2 * i + 1] = v.y; }
+    } else {
+#pragma unroll
+        for (int i = 0; i < N; i++) w[i] = reinterpret_cast<const uint32_t*>(p)[i];
+    }
+#pragma unroll
+    for (int i = 0; i < N; i++) {
+        if constexpr (PX == 4) t[i] = mip_widen<4>(w[i], 0u);
+        else                   t[i] = mip_widen<8>(w[2 * i], w[2 * i + 1]);
+    }
+}
+
+template <int PX>
+__device__ __forceinline__ MipTexel mip_load(const uint8_t* p)
+{
+    MipTexel t;
+    mip_load_row<PX, 1>(p, &t);
+    return t;
+}
+
+// one texel's stored words at `p`
+template <int PX>
+__device__ __forceinline__ void mip_store_words(uint8_t* p, uint32_t lo, uint32_t hi)
+{
+    if constexpr (PX == 4) *reinterpret_cast<uint32_t*>(p) = lo;
+    else                   *reinterpret_cast<uint2*>(p) = make_uint2(lo, hi);
+}
+
+// rounds N (1 or 2) consecutive texels to the format and stores them at `p`; `t` becomes the stored values widened
+template <int PX, int N>
+__device__ __forceinline__ void mip_store_row(uint8_t* p, MipTexel* t)
+{
+    uint32_t lo[N], hi[N];
+#pragma unroll
+    for (int i = 0; i < N; i++) mip_round<PX>(t[i], lo[i], hi[i]);
+    if constexpr (N == 2) {
+        if (PX == 8 && ((uintptr_t)p & 15) == 0) { *reinterpret_cast<uint4*>(p) = make_uint4(lo[0], hi[0], lo[1], hi[1]); return; }
+        if (PX == 4 && ((uintptr_t)p & 7) == 0)  { *reinterpret_cast<uint2*>(p) = make_uint2(lo[0], lo[1]); return; }
+    }
+#pragma unroll
+    for (int i = 0; i < N; i++) mip_store_words<PX>(p + i * PX, lo[i], hi[i]);
+}
+
+// LDS regions of the pyramid kernel, in widened texels: level +2 (16 x 16), +3 (8 x 8), +4 (4 x 4), +5 (2 x 2)
+constexpr int kPyrLds = 256 + 64 + 16 + 4;
+
+template <int PX>
+__global__ void __launch_bounds__(256)
+mip_pyramid_kernel(const MipImage* __restrict__ table, int32_t levels, int32_t src_level, int32_t nout, int32_t tiles_x, int32_t tiles_per_item)
+{
+    __shared__ MipTexel lds[kPyrLds];
+    const int32_t item = (int32_t)(blockIdx.x / (uint32_t)tiles_per_item);
+    const int32_t tile = (int32_t)(blockIdx.x - (uint32_t)item * (uint32_t)tiles_per_item);
+    const int32_t ty = tile / tiles_x, tx = tile - ty * tiles_x;
+    const MipImage* im = table + (int64_t)item * levels + src_level;      // im[k]: level src_level + k, k <= nout
+    const int32_t lx = threadIdx.x & 15, ly = threadIdx.x >> 4;
+
+    MipTexel p[4][4];
+    {
+        const MipImage s = im[0];
+        const uint8_t* src = s.ptr + (int64_t)(ty * 64 + ly * 4) * s.stride + (int64_t)(tx * 64 + lx * 4) * PX;
+#pragma unroll
+        for (int r = 0; r < 4; r++) mip_load_row<PX, 4>(src + r * s.stride, p[r]);
+    }
+    MipTexel q[2][2];
+    {
+        const MipImage d = im[1];
+        uint8_t* dst = d.ptr + (int64_t)(ty * 32 + ly * 2) * d.stride + (int64_t)(tx * 32 + lx * 2) * PX;
+#pragma unroll
+        for (int j = 0; j < 2; j++) {
+#pragma unroll
+            for (int i = 0; i < 2; i++) q[j][i] = mip_box(p[2 * j][2 * i], p[2 * j + 1][2 * i], p[2 * j][2 * i + 1], p[2 * j + 1][2 * i + 1]);
+            mip_store_row<PX, 2>(dst + j * d.stride, q[j]);
+        }
+    }
+    if (nout < 2) return;                                                 // (nout is the launch's: every lane leaves together)
+    {
+        MipTexel t = mip_box(q[0][0], q[1][0], q[0][1], q[1][1]);
+        const MipImage d = im[2];
+        mip_store_row<PX, 1>(d.ptr + (int64_t)(ty * 16 + ly) * d.stride + (int64_t)(tx * 16 + lx) * PX, &t);
+        lds[ly * 16 + lx] = t;
+    }
+    int32_t from = 0, to = 256;                                           // region offsets: the level read, the level written
+#pragma unroll
+    for (int k = 3; k <= 6; k++) {
+        if (nout < k) return;
+        __syncthreads();
+        const int32_t n = 64 >> k;                                        // 8, 4, 2, 1 texels across the tile at level +k
+        if ((int32_t)threadIdx.x < n * n) {
+            const int32_t x = threadIdx.x & (n - 1), y = threadIdx.x / n;
+            const MipTexel* s = lds + from + (2 * y) * (2 * n) + 2 * x;
+            MipTexel t = mip_box(s[0], s[2 * n], s[1], s[2 * n + 1]);
+            const MipImage d = im[k];
+            mip_store_row<PX, 1>(d.ptr + (int64_t)(ty * n + y) * d.stride + (int64_t)(tx * n + x) * PX, &t);
+            if (k < 6) lds[to + y * n + x] = t;
+        }
+        from = to; to += n * n;
+    }
+}
+
+// source level `src_level` of w x h, powers of two, at most 64 x 32 or 32 x 64 (launch_chain gives 64 x 64 to the pyramid kernel); one
+// workgroup per item, `nout` levels down.  Levels live in LDS as stored words: odd ones (+1 <= 512 texels, +3, +5) in buf_a, even ones
+// (+2 <= 128 texels, +4, +6) in buf_b; the barrier that ends a level also ends the reads of the buffer the next level overwrites.
+template <int PX>
+__global__ void __launch_bounds__(256)
+mip_tail_kernel(const MipImage* __restrict__ table, int32_t levels, int32_t src_level, int32_t nout, int32_t w, int32_t h)
+{
+    __shared__ uint2 buf_a[512], buf_b[128];
+    const MipImage* im = table + (int64_t)blockIdx.x * levels + src_level;
+    int32_t sw = w, sh = h;
+    for (int k = 1; k <= nout; k++) {
+        const int32_t ow = sw > 1 ? sw >> 1 : 1, oh = sh > 1 ? sh >> 1 : 1;
+        const uint2* sl = (k & 1) ? buf_b : buf_a;                        // level k - 1 (k >= 2)
+        uint2* dl = (k & 1) ? buf_a : buf_b;                              // level k
+        const MipImage s = im[k - 1], d = im[k];
+        for (int32_t idx = threadIdx.x; idx < ow * oh; idx += 256) {
+            const int32_t y = idx / ow, x = idx - y * ow;
+            const int32_t x0 = 2 * x, x1 = sw > 1 ? x0 + 1 : x0, y0 = 2 * y, y1 = sh > 1 ? y0 + 1 : y0;
+            MipTexel p0, p1, p2, p3;
+            if (k == 1) {
+                const uint8_t* r0 = s.ptr + y0 * s.stride, * r1 = s.ptr + y1 * s.stride;
+                p0 = mip_load<PX>(r0 + (int64_t)x0 * PX); p1 = mip_load<PX>(r1 + (int64_t)x0 * PX);
+                p2 = mip_load<PX>(r0 + (int64_t)x1 * PX); p3 = mip_load<PX>(r1 + (int64_t)x1 * PX);
+            } else {
+                const uint2 a = sl[y0 * sw + x0], b = sl[y1 * sw + x0], c = sl[y0 * sw + x1], e = sl[y1 * sw + x1];
+                p0 = mip_widen<PX>(a.x, a.y); p1 = mip_widen<PX>(b.x, b.y); p2 = mip_widen<PX>(c.x, c.y); p3 = mip_widen<PX>(e.x, e.y);
+            }
+            MipTexel t = mip_box(p0, p1, p2, p3);
+            uint32_t lo, hi;
+            mip_round<PX>(t, lo, hi);
+            mip_store_words<PX>(d.ptr + y * d.stride + (int64_t)x * PX, lo, hi);
+            dl[idx] = make_uint2(lo, hi);
+        }
+        __syncthreads();
+        sw = ow; sh = oh;
+    }
+}
+
+// level `dst_level` (ow x oh) of every item from its level dst_level - 1 (sw x sh); lanes 64 across, 4 down; grid (x tiles, y tiles, items)
+template <int PX, bool LINEAR>
+__global__ void __launch_bounds__(256)
+mip_level_kernel(const MipImage* __restrict__ table, int32_t levels, int32_t dst_level, int32_t sw, int32_t sh, int32_t ow, int32_t oh,
+                 float scale_x, float scale_y)
+{
+    const int32_t x = (int32_t)blockIdx.x * 64 + (threadIdx.x & 63), y = (int32_t)blockIdx.y * 4 + (threadIdx.x >> 6);
+    if (x >= ow || y >= oh) return;
+    const MipImage* im = table + (int64_t)blockIdx.z * levels + dst_level;
+    const MipImage s = im[-1], d = im[0];
+    MipTexel t;
+    if (LINEAR) {
+        const MipTap tx = mip_linear_tap(x, scale_x, sw), ty = mip_linear_tap(y, scale_y, sh);
+        const uint8_t* r0 = s.ptr + (int64_t)ty.u0 * s.stride, * r1 = s.ptr + (int64_t)ty.u1 * s.stride;
+        t = mip_bilinear(mip_load<PX>(r0 + (int64_t)tx.u0 * PX), mip_load<PX>(r0 + (int64_t)tx.u1 * PX),
+                         mip_load<PX>(r1 + (int64_t)tx.u0 * PX), mip_load<PX>(r1 + (int64_t)tx.u1 * PX), tx, ty);
+    } else {
+        const int32_t x0 = 2 * x, x1 = sw > 1 ? x0 + 1 : x0, y0 = 2 * y, y1 = sh > 1 ? y0 + 1 : y0;
+        const uint8_t* r0 = s.ptr + (int64_t)y0 * s.stride, * r1 = s.ptr + (int64_t)y1 * s.stride;
+        t = mip_box(mip_load<PX>(r0 + (int64_t)x0 * PX), mip_load<PX>(r1 + (int64_t)x0 * PX),
+                    mip_load<PX>(r0 + (int64_t)x1 * PX), mip_load<PX>(r1 + (int64_t)x1 * PX));
+    }
+    mip_store_row<PX, 1>(d.ptr + (int64_t)y * d.stride + (int64_t)x * PX, &t);
+}
+
+} // namespace itw
+
+namespace {
+
+inline int mip_dim(int v, int level) { return std::max(1, v >> std::min(level, 30)); }
+inline bool pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
+
+// What one launch covers, checked by the entry points before any device work: the per-level kernel's grid has a block row per 4 texel rows
+// of level 1 and a plane per item (65 535 each), the pyramid kernel a block per tile and item.
+void check_launch_limits(const char* who, int w, int h, int items)
+{
+    if (items > 65535) itw::fail_msg("%s: %d items are more than one launch covers (65 535)", who, items);
+    if (mip_dim(h, 1) > 4 * 65535) itw::fail_msg("%s: a base of %d rows is more than one launch covers (524 280)", who, h);
+    if ((int64_t)(w / 64 + 1) * (h / 64 + 1) * items > (int64_t)0x7fffffff) itw::fail_msg("%s: %d items of %d x %d are more tiles than one launch covers", who, items, w, h);
+}
+
+// the launches of one chain: `table` is on the device, the base is w x h, all `items` alike and within check_launch_limits
+template <int PX>
+void launch_chain(const itw::MipImage* table, int items, int levels, int w, int h, bool per_level, hipStream_t st)
+{
+    const bool box = pow2(w) && pow2(h);
+    int cur = 0;                                                          // the last level that exists
+    while (cur < levels - 1) {
+        const int sw = mip_dim(w, cur), sh = mip_dim(h, cur);
+        if (box && !per_level && sw >= 64 && sh >= 64) {
+            const int nout = std::min(6, levels - 1 - cur), tiles_x = sw / 64, tiles = tiles_x * (sh / 64);
+            hipLaunchKernelGGL((itw::mip_pyramid_kernel<PX>), dim3((unsigned)(tiles * items)), dim3(256), 0, st, table, levels, cur, nout, tiles_x, tiles);
+            cur += nout;
+        } else if (box && !per_level && sw <= 64 && sh <= 64) {       // (not both 64: that was a tile)
+            hipLaunchKernelGGL((itw::mip_tail_kernel<PX>), dim3((unsigned)items), dim3(256), 0, st, table, levels, cur, levels - 1 - cur, sw, sh);
+            cur = levels - 1;
+        } else {
+            const int ow = mip_dim(w, cur + 1), oh = mip_dim(h, cur + 1);
+            const dim3 grid((unsigned)((ow + 63) / 64), (unsigned)((oh + 3) / 4), (unsigned)items);
+            const float scale_x = (float)sw / (float)ow, scale_y = (float)sh / (float)oh;
+            if (box) hipLaunchKernelGGL((itw::mip_level_kernel<PX, false>), grid, dim3(256), 0, st, table, levels, cur + 1, sw, sh, ow, oh, scale_x, scale_y);
+            else     hipLaunchKernelGGL((itw::mip_level_kernel<PX, true>), grid, dim3(256), 0, st, table, levels, cur + 1, sw, sh, ow, oh, scale_x, scale_y);
+            cur += 1;
+        }
+        ITW_CHECK(hipGetLastError());
+    }
+}
+
+size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// everything that needs the device: a chain that passed the checks, all of one pointer kind, levels >= 2
+void generate_chain(const rgba_surface* im, int items, int levels, int px, bool per_level, bool dev)
+{
+    hipStream_t st = (hipStream_t)itwGetStream();
+    const int count = items * levels;
+    static thread_local std::vector<itw::MipImage> desc;                  // grow-only, like the device buffer it is copied into
+    desc.resize((size_t)count);
+    // the thread's buffer: [table] [staged images (host pointers), rows of a 16-byte multiple]
+    size_t bytes = up256((size_t)count * sizeof(itw::MipImage));
+    std::vector<size_t> stage_off(dev ? 0 : (size_t)count);
+    for (int i = 0; i < count; i++) {
+        desc[(size_t)i].ptr = im[i].ptr; desc[(size_t)i].stride = im[i].stride;
+        if (!dev) {
+            desc[(size_t)i].stride = (int64_t)(((size_t)im[i].width * px + 15) & ~(size_t)15);
+            stage_off[(size_t)i] = bytes;
+            bytes += up256((size_t)desc[(size_t)i].stride * (size_t)im[i].height);
+        }
+    }
+    uint8_t* base = static_cast<uint8_t*>(itw::decode_scratch(bytes, st));
+    if (!dev)
+        for (int i = 0; i < count; i++) {
+            desc[(size_t)i].ptr = base + stage_off[(size_t)i];
+            if (i % levels == 0)                                          // only the bases go up
+                ITW_CHECK(hipMemcpy2DAsync(desc[(size_t)i].ptr, (size_t)desc[(size_t)i].stride, im[i].ptr, (size_t)im[i].stride, (size_t)im[i].width * px,
+                                           (size_t)im[i].height, hipMemcpyHostToDevice, st));
+        }
+    ITW_CHECK(hipMemcpyAsync(base, desc.data(), (size_t)count * sizeof(itw::MipImage), hipMemcpyHostToDevice, st));
+    const itw::MipImage* table = reinterpret_cast<const itw::MipImage*>(base);
+    if (px == 4) launch_chain<4>(table, items, levels, im[0].width, im[0].height, per_level, st);
+    else         launch_chain<8>(table, items, levels, im[0].width, im[0].height, per_level, st);
+    if (dev) { itw::decode_scratch_done(st); return; }                    // resident: asynchronous on the thread's stream
+    for (int i = 0; i < count; i++)                                       // only the written levels come back, width x height only
+        if (i % levels != 0)
+            ITW_CHECK(hipMemcpy2DAsync(im[i].ptr, (size_t)im[i].stride, desc[(size_t)i].ptr, (size_t)desc[(size_t)i].stride, (size_t)im[i].width * px,
+                                       (size_t)im[i].height, hipMemcpyDeviceToHost, st));
+    ITW_CHECK(hipStreamSynchronize(st));
+    itw::decode_scratch_done(st);
+}
+
+// the device-side chain of itwCompressImageMipped: the thread's own grow-only buffer (the staging buffer above is in use by the stages the
+// call runs), ordered across streams as host_rt.hpp's decode_scratch is
+struct ChainBuffer {
+    void* ptr = nullptr; size_t cap = 0; hipEvent_t done = nullptr; hipStream_t stream = nullptr; bool used = false;
+    uint8_t* get(size_t bytes, hipStream_t st)
+    {
+        if (!done) ITW_CHECK(hipEventCreateWithFlags(&done, hipEventDisableTiming));
+        if (used && stream != st) ITW_CHECK(hipStreamWaitEvent(st, done, 0));
+        if (bytes > cap) {
+            if (ptr) { void* old = ptr; ptr = nullptr; cap = 0; ITW_CHECK(hipFree(old)); }      // (waits for the device)
+            const size_t want = bytes + bytes / 4 + 4096;
+            ITW_CHECK(hipMalloc(&ptr, want));
+            cap = want;
+        }
+        stream = st; used = true;
+        return static_cast<uint8_t*>(ptr);
+    }
+    void release(hipStream_t st) { ITW_CHECK(hipEventRecord(done, st)); }
+};
+thread_local ChainBuffer t_chain;
+
+} // namespace
+
+extern "C" int itwMipLevels(int width, int height)
+{
+    if (width < 1 || height < 1) return 0;
+    int n = 1;
+    for (int m = std::max(width, height); m > 1; m >>= 1) n++;
+    return n;
+}
+
+extern "C" int64_t itwMipChainLayout(int width, int height, int items, int levels, int pixel_size, uint8_t* storage, rgba_surface* out)
+{
+    const int full = itwMipLevels(width, height);
+    if (full == 0 || items < 0 || levels < 0 || levels > full || (pixel_size != 4 && pixel_size != 8)) return -1;
+    if ((int64_t)width * pixel_size > (int64_t)0x7fffffff) return -1;     // rgba_surface's stride is an int32
+    if (levels == 0) levels = full;
+    int64_t off = 0;
+    for (int i = 0; i < items; i++)
+        for (int l = 0; l < levels; l++) {
+            const int w = mip_dim(width, l), h = mip_dim(height, l);
+            if (out) {
+                rgba_surface& s = out[(size_t)i * levels + l];
+                s.ptr = reinterpret_cast<uint8_t*>(reinterpret_cast<uintptr_t>(storage) + (uintptr_t)off);
+                s.width = w; s.height = h; s.stride = w * pixel_size;
+            }
+            off += (int64_t)w * h * pixel_size;
+        }
+    return off;
+}
+
+extern "C" int itwGenerateMipChain(const rgba_surface* images, int items, int levels, int pixel_size, uint32_t flags)
+{
+    bool dev = false;
+    itw::clear_failure();
+    const bool ok = itw::guarded([&] {
+        if (pixel_size != 4 && pixel_size != 8) itw::fail_msg("itwGenerateMipChain: pixel_size %d (4: RGBA8, 8: RGBA16F)", pixel_size);
+        if (flags & ~(uint32_t)ITW_MIP_PER_LEVEL) itw::fail_msg("itwGenerateMipChain: unknown flag bits 0x%x", flags);
+        if (items < 0) itw::fail_msg("itwGenerateMipChain: %d items", items);
+        if (items == 0 || levels <= 1) return;
+        if (!images) itw::fail_msg("itwGenerateMipChain: null images pointer");
+        if ((int64_t)items * levels > (int64_t)0x7fffffff / 64) itw::fail_msg("itwGenerateMipChain: %d items of %d levels", items, levels);
+        const int w = images[0].width, h = images[0].height, full = itwMipLevels(w, h);
+        if (full == 0) itw::fail_msg("itwGenerateMipChain: the base is %d x %d", w, h);
+        if (levels > full) itw::fail_msg("itwGenerateMipChain: %d levels, a full chain of %d x %d has %d", levels, w, h, full);
+        check_launch_limits("itwGenerateMipChain", w, h, items);
+        for (int i = 0; i < items * levels; i++) {
+            const rgba_surface& s = images[i];
+            const int item = i / levels, l = i % levels;
+            if (!s.ptr) itw::fail_msg("itwGenerateMipChain: item %d level %d has a null texel pointer", item, l);
+            if (l == 0 && (s.width != w || s.height != h))
+                itw::fail_msg("itwGenerateMipChain: the base of item %d is %d x %d, that of item 0 %d x %d", item, s.width, s.height, w, h);
+            if (s.width != mip_dim(w, l) || s.height != mip_dim(h, l))
+                itw::fail_msg("itwGenerateMipChain: item %d level %d is %d x %d, the chain's is %d x %d", item, l, s.width, s.height, mip_dim(w, l), mip_dim(h, l));
+            if ((int64_t)s.stride < (int64_t)s.width * pixel_size)
+                itw::fail_msg("itwGenerateMipChain: item %d level %d: stride %d < %lld bytes per row", item, l, s.stride, (long long)s.width * pixel_size);
+            const uintptr_t row_step = s.height > 1 ? (uintptr_t)(uint32_t)s.stride : 0;
+            if (((uintptr_t)s.ptr | row_step) & (uintptr_t)(pixel_size - 1))
+                itw::fail_msg("itwGenerateMipChain: item %d level %d: texels are not %d-byte aligned", item, l, pixel_size);
+        }
+        dev = itw::is_device_pointer(images[0].ptr);
+        for (int i = 1; i < items * levels; i++)
+            if (itw::is_device_pointer(images[i].ptr) != dev)
+                itw::fail_msg("itwGenerateMipChain: image %d is %s memory, image 0 %s: all images must be host or all device pointers", i,
+                              dev ? "host" : "device", dev ? "device" : "host");
+        generate_chain(images, items, levels, pixel_size, (flags & ITW_MIP_PER_LEVEL) != 0, dev);
+    });
+    return ok ? 0 : -1;
+}
+
+extern "C" bool itwCompressImageMipped(const rgba_surface* bases, int items, int levels, uint32_t normal_ops, uint8_t* target, int dxgi_format,
+                                       const void* settings, ItwProgressFunc* progress, void* user)
+{
+    bool done = false;
+    itw::clear_failure();
+    const bool ok = itw::guarded([&] {
+        if (normal_ops & ~7u) itw::fail_msg("itwCompressImageMipped: unknown ops bits 0x%x", normal_ops);
+        itw::chain_check_with(bases, items, target, dxgi_format, settings);       // counts, null pointers, sizes, strides, format, settings
+        const int px = itw::texel_bytes(itw::format_kind(dxgi_format));
+        const int w = bases[0].width, h = bases[0].height, full = itwMipLevels(w, h);
+        for (int i = 0; i < items; i++) {
+            if (bases[i].width != w || bases[i].height != h)
+                itw::fail_msg("itwCompressImageMipped: base %d is %d x %d, base 0 %d x %d", i, bases[i].width, bases[i].height, w, h);
+            const uintptr_t row_step = h > 1 ? (uintptr_t)(uint32_t)bases[i].stride : 0;
+            if (((uintptr_t)bases[i].ptr | row_step) & (uintptr_t)(px - 1)) itw::fail_msg("itwCompressImageMipped: base %d: texels are not %d-byte aligned", i, px);
+        }
+        if (levels < 0 || levels > full) itw::fail_msg("itwCompressImageMipped: %d levels, a full chain of %d x %d has %d", levels, w, h, full);
+        if (levels == 0) levels = full;
+        if ((int64_t)items * levels > (int64_t)0x7fffffff / 64) itw::fail_msg("itwCompressImageMipped: %d items of %d levels", items, levels);
+        check_launch_limits("itwCompressImageMipped", w, h, items);
+        const bool dev = itw::is_device_pointer(bases[0].ptr);
+        for (int i = 1; i < items; i++)
+            if (itw::is_device_pointer(bases[i].ptr) != dev)
+                itw::fail_msg("itwCompressImageMipped: base %d is %s memory, base 0 %s: all bases must be host or all device pointers", i,
+                              dev ? "host" : "device", dev ? "device" : "host");
+        const int64_t bytes = itwMipChainLayout(w, h, items, levels, px, nullptr, nullptr);
+        if (bytes < 0) itw::fail_msg("itwCompressImageMipped: a %d x %d base is wider than a surface can describe", w, h);
+
+        hipStream_t st = (hipStream_t)itwGetStream();
+        std::vector<rgba_surface> chain((size_t)items * levels), level0((size_t)items);
+        itwMipChainLayout(w, h, items, levels, px, t_chain.get((size_t)bytes, st), chain.data());
+        for (int i = 0; i < items; i++) {
+            level0[(size_t)i] = chain[(size_t)i * levels];
+            ITW_CHECK(hipMemcpy2DAsync(level0[(size_t)i].ptr, (size_t)level0[(size_t)i].stride, bases[i].ptr, (size_t)bases[i].stride, (size_t)w * px, (size_t)h,
+                                       dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+        }
+        auto stage = [](int rc, const char* what) { if (rc != 0) itw::fail_msg("itwCompressImageMipped: %s failed: %s", what, itwLastError()); };
+        // the reference's order (IntelPlugin.cpp:2103-2152): flip level 0, generate the mips, normalise every level, compress every image
+        if (normal_ops & 3u) stage(itwPrepareNormalMapChain(level0.data(), items, px, normal_ops & 3u), "the flip");
+        stage(itwGenerateMipChain(chain.data(), items, levels, px, 0), "the mip chain");
+        if (normal_ops & 4u) stage(itwPrepareNormalMapChain(chain.data(), items * levels, px, 4u), "the normalise");
+        done = itwCompressImageChainEx(chain.data(), items * levels, target, dxgi_format, settings, progress, user);
+        t_chain.release(st);
+    });
+    return ok && done;
+}

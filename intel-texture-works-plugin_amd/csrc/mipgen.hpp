@@ -1,0 +1,98 @@
+// mipgen.hpp -- the arithmetic of the mip filters (include/itw_dispatch.h, "Mip chains"): one definition behind the pyramid kernels and the
+// per-level kernel of mipgen.hip.  DirectXTex's non-WIC 2D filters (DirectXTexMipmaps.cpp:715-805 box, :809-917 linear; Filters.h:33-39
+// AVERAGE4, :66-106 _CreateLinearFilter and BILINEAR_INTERPOLATE) with the R16G16B16A16_FLOAT scanline store (DirectXTexConvert.cpp:1634-1646).
+// IEEE fp32, one rounding per operation (the library is built with -ffp-contract=off).  All four channels alike.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <hip/hip_fp16.h>
+#include <stdint.h>
+
+namespace itw {
+
+struct MipTexel { float c[4]; };                                  // a stored texel, widened: every value is one the texel format holds
+
+// PX = 4: RGBA8, the raw codes as 0..255.  PX = 8: RGBA16F, the halves widened exactly.  `p` is PX aligned.
+template <int PX>
+__device__ __forceinline__ MipTexel mip_widen(uint32_t lo, uint32_t hi)
+{
+    MipTexel t;
+    if (PX == 4) {
+        t.c[0] = (float)(lo & 255u); t.c[1] = (float)((lo >> 8) & 255u); t.c[2] = (float)((lo >> 16) & 255u); t.c[3] = (float)(lo >> 24);
+    } else {
+        t.c[0] = __half2float(__ushort_as_half((unsigned short)(lo & 0xffffu))); t.c[1] = __half2float(__ushort_as_half((unsigned short)(lo >> 16)));
+        t.c[2] = __half2float(__ushort_as_half((unsigned short)(hi & 0xffffu))); t.c[3] = __half2float(__ushort_as_half((unsigned short)(hi >> 16)));
+    }
+    return t;
+}
+
+// RGBA16F store: a NaN stores 0x7E00; anything else is clamped to [-65504, 65504] and rounded to nearest even (convert.hip's to_half_bits).
+// An exact -0 keeps its sign: the clamp stands between the filter's last multiply and the conversion, so the two are not fused into
+// v_fma_mixlo_f16 x, y, +0 as in normal_prep.hpp's trap ((-0) + (+0) is +0).  tests/test_gpu_mipgen.py holds exact -0 sums at every level kind.
+__device__ __forceinline__ uint32_t mip_half_bits(float v)
+{
+    if (v != v) return 0x7e00u;
+    v = fminf(fmaxf(v, -65504.0f), 65504.0f);
+    return (uint32_t)__half_as_ushort(__float2half_rn(v));
+}
+// RGBA8 store: (uint8_t)min(v + 0.5f, 255.0f); v is never negative or NaN here (codes and weights are not)
+__device__ __forceinline__ uint32_t mip_byte(float v) { return (uint32_t)fminf(v + 0.5f, 255.0f); }
+
+// rounds `t` to the texel format: the words to store, and `t` becomes what a later load of them widens to
+template <int PX>
+__device__ __forceinline__ void mip_round(MipTexel& t, uint32_t& lo, uint32_t& hi)
+{
+    if (PX == 4) {
+        lo = mip_byte(t.c[0]) | (mip_byte(t.c[1]) << 8) | (mip_byte(t.c[2]) << 16) | (mip_byte(t.c[3]) << 24);
+        hi = 0;
+    } else {
+        lo = mip_half_bits(t.c[0]) | (mip_half_bits(t.c[1]) << 16);
+        hi = mip_half_bits(t.c[2]) | (mip_half_bits(t.c[3]) << 16);
+    }
+    t = mip_widen<PX>(lo, hi);
+}
+
+// AVERAGE4: p0 = (row 2y, column 2x), p1 = (2y+1, 2x), p2 = (2y, 2x+1), p3 = (2y+1, 2x+1)
+__device__ __forceinline__ MipTexel mip_box(const MipTexel& p0, const MipTexel& p1, const MipTexel& p2, const MipTexel& p3)
+{
+    MipTexel r;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        float v = p0.c[k] + p1.c[k];
+        v = v + p2.c[k];
+        v = v + p3.c[k];
+        r.c[k] = v * 0.25f;
+    }
+    return r;
+}
+
+// one axis of _CreateLinearFilter with clamp addressing: `scale` = float(source) / float(dest), computed by the host
+struct MipTap { int32_t u0, u1; float w0, w1; };
+__device__ __forceinline__ MipTap mip_linear_tap(int32_t u, float scale, int32_t source)
+{
+    const float srcB = ((float)u + 0.5f) * scale + 0.5f;
+    int32_t b = (int32_t)srcB;
+    int32_t a = b - 1;
+    if (a < 0) a = 0;
+    if (b >= source) b = source - 1;
+    if (a >= source) a = source - 1;                              // (only where fp32 no longer holds the coordinate, sources of 2^25 texels and more: no read past the row)
+    MipTap t;
+    t.u0 = a; t.u1 = b;
+    t.w0 = 1.0f + (float)b - srcB;
+    t.w1 = 1.0f - t.w0;
+    return t;
+}
+
+// BILINEAR_INTERPOLATE: r00 = row u0 of y, column u0 of x; r01 = same row, column u1; r10, r11 = row u1
+__device__ __forceinline__ MipTexel mip_bilinear(const MipTexel& r00, const MipTexel& r01, const MipTexel& r10, const MipTexel& r11, const MipTap& x, const MipTap& y)
+{
+    MipTexel r;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        const float top = r00.c[k] * x.w0 + r01.c[k] * x.w1;
+        const float bot = r10.c[k] * x.w0 + r11.c[k] * x.w1;
+        r.c[k] = y.w0 * top + y.w1 * bot;
+    }
+    return r;
+}
+
+} // namespace itw

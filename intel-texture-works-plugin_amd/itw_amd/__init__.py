@@ -21,4 +21,5 @@ from .abi import (  # noqa: F401
     RefineStats, compress_refined, RefinePolicy, RefineTargetStats, compress_refined_to, psnr_to_total_sse,
     compress_chain_refined, compress_chain_refined_to, chain_psnr_to_total_sse,
     NORMAL_FLIP_X, NORMAL_FLIP_Y, NORMAL_NORMALIZE, normal_ops, prepare_normal_map, compress_normal_map, cube_cross_faces,
+    MIP_PER_LEVEL, mip_levels, mip_chain_layout, generate_mips, generate_mips_into, compress_mipped,
 )

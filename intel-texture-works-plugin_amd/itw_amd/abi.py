@@ -25,7 +25,8 @@ EXPORTED_SYMBOLS = tuple(
     + ["CompressImageBC7_" + p for p in BC7_PROFILES] + ["CompressImageBC6H_" + p for p in BC6H_PROFILES]
     + ["itwCompressImageSliced", "itwCompressImageSlicedEx", "itwChainBytes", "itwCompressImageChain", "itwCompressImageChainEx", "itwCompressImageRefined", "itwCompressImageRefinedTo", "itwPsnrToTotalSse", "itwCompressImageChainRefined", "itwCompressImageChainRefinedTo", "itwChainPsnrToTotalSse", "itwSetSliceWindow", "itwSliceWindow", "itwSliceWindowFor", "itwPadToMultipleOf4", "itwFreeSurface", "itwPadToMultipleOf4Device",
        "itwConvertToRGBA8Device", "itwConvertToRGBA16FDevice",
-       "itwPrepareNormalMapChain", "itwCompressNormalMapChain", "itwCubeCrossFaces"]
+       "itwPrepareNormalMapChain", "itwCompressNormalMapChain", "itwCubeCrossFaces",
+       "itwMipLevels", "itwMipChainLayout", "itwGenerateMipChain", "itwCompressImageMipped"]
     # include/itw_multigpu.h: one surface over all GPUs, one process
     + ["itwMultiGpuRanks", "itwMultiGpuTransport", "itwMultiGpuPeerLinks", "itwCompressImageMultiGPU", "itwCompressImageMultiGPUEx", "itwCompressImageMultiGPUBands",
        "itwMultiGpuSetInterleave", "itwMultiGpuPieces"]
@@ -384,6 +385,14 @@ def _load(path, hooks):
         L.itwCompressNormalMapBC5.restype = None
         L.itwCubeCrossFaces.argtypes = [C.POINTER(RgbaSurface), C.c_int, C.POINTER(RgbaSurface)]
         L.itwCubeCrossFaces.restype = C.c_int
+        L.itwMipLevels.argtypes = [C.c_int, C.c_int]
+        L.itwMipLevels.restype = C.c_int
+        L.itwMipChainLayout.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.itwMipChainLayout.restype = C.c_int64
+        L.itwGenerateMipChain.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint32]
+        L.itwGenerateMipChain.restype = C.c_int
+        L.itwCompressImageMipped.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.itwCompressImageMipped.restype = C.c_bool
         L.itwDecodeBlocks.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]
         L.itwDecodeBlocks.restype = C.c_int
         L.itwDecodeChain.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
@@ -798,6 +807,104 @@ def cube_cross_faces(img):
         x //= 4 * es
         views.append(img[y:y + f.height, x:x + f.width])
     return views
+
+
+MIP_PER_LEVEL = 1     # ITW_MIP_PER_LEVEL (include/itw_dispatch.h)
+
+
+def mip_levels(width, height):
+    """itwMipLevels: the length of a full mip chain, 1 + floor(log2(max(width, height))); 0 for a size below 1."""
+    return int(lib().itwMipLevels(width, height))
+
+
+def mip_chain_layout(width, height, items=1, levels=0, pixel_size=4):
+    """itwMipChainLayout without storage: (bytes, [(offset, width, height, stride)] in DDS order -- item-major, then level; levels == 0: the
+    full chain).  Raises ValueError where the call returns -1."""
+    n = int(lib().itwMipChainLayout(width, height, items, levels, pixel_size, None, None))
+    if n < 0:
+        raise ValueError(f"itwMipChainLayout refused {width} x {height}, {items} items, {levels} levels, pixel_size {pixel_size}")
+    count = items * (levels or mip_levels(width, height))
+    out = (RgbaSurface * max(1, count))()
+    lib().itwMipChainLayout(width, height, items, levels, pixel_size, None, C.cast(out, C.c_void_p))
+    return n, [(int(out[i].ptr or 0), out[i].width, out[i].height, out[i].stride) for i in range(count)]
+
+
+def generate_mips(base_or_bases, levels=0, per_level=False):
+    """itwGenerateMipChain: the mip levels of one base image or a list of equally sized ones (cube faces, array items): host numpy arrays or
+    CUDA torch tensors (H, W, 4), uint8 (RGBA8) or 2-byte elements (RGBA16F half bits), all of one kind.  DirectXTex's box filter when width
+    and height are powers of two, else its linear filter (include/itw_dispatch.h).  levels == 0: the full chain.  per_level forces one
+    launch per level.  Returns the list of levels [base, level 1, ...] for one base, a list of such lists for a list; the bases themselves
+    are level 0 and are not copied.  Device tensors: asynchronous on torch's current stream."""
+    single = hasattr(base_or_bases, "shape")
+    bases = [base_or_bases] if single else list(base_or_bases)
+    assert bases, "no base image"
+    h, w = bases[0].shape[:2]
+    n = levels or mip_levels(w, h)
+    on_device = hasattr(bases[0], "data_ptr")
+    es = bases[0].element_size() if on_device else bases[0].itemsize
+    assert es in (1, 2), "uint8 or half texels"
+    chains = []
+    for b in bases:
+        if on_device:
+            import torch
+            chains.append([b] + [torch.empty((max(1, h >> l), max(1, w >> l), 4), dtype=b.dtype, device=b.device) for l in range(1, n)])
+        else:
+            import numpy as np
+            chains.append([b] + [np.empty((max(1, h >> l), max(1, w >> l), 4), dtype=b.dtype) for l in range(1, n)])
+    generate_mips_into(chains, per_level=per_level)
+    return chains[0] if single else chains
+
+
+def generate_mips_into(chains, per_level=False):
+    """itwGenerateMipChain over caller-made levels: `chains` is a list of items, each the list of its levels (level 0 filled in), which may
+    be strided views of larger arrays / tensors.  Raises ValueError where the call returns -1."""
+    flat = [lv for ch in chains for lv in ch]
+    on_device = hasattr(flat[0], "data_ptr")
+    es = flat[0].element_size() if on_device else flat[0].itemsize
+    if on_device:
+        import torch
+        lib().itwSetStream(torch.cuda.current_stream(flat[0].device).cuda_stream)
+    if lib().itwGenerateMipChain(C.cast(_surfaces(flat), C.c_void_p), len(chains), len(chains[0]), 4 * es, MIP_PER_LEVEL if per_level else 0) != 0:
+        raise ValueError("itwGenerateMipChain refused the call: " + (last_error() or "bad arguments"))
+    return chains
+
+
+def compress_mipped(fmt, base_or_bases, levels=0, profile=None, settings=None, normal_ops=0, progress=None, out=None):
+    """itwCompressImageMipped: the save path from base images in one call -- flips of `normal_ops` on level 0, the mip chain, the normalise on
+    every level, then the chain encoder.  One base or a list of equally sized ones (numpy arrays or CUDA torch tensors, as compress_chain
+    takes them); levels == 0: the full chain.  Returns (ok, blocks): the DDS payload, item-major then level."""
+    import numpy as np
+    single = hasattr(base_or_bases, "shape")
+    bases = [base_or_bases] if single else list(base_or_bases)
+    base = _base(fmt)
+    for img in bases:
+        _check_texel_type(fmt, img)
+    h, w = bases[0].shape[:2]
+    n = levels or mip_levels(w, h)
+    nbytes = len(bases) * sum(((max(1, w >> l) + 3) // 4) * ((max(1, h >> l) + 3) // 4) for l in range(n)) * BYTES_PER_BLOCK[base]
+    on_device = hasattr(bases[0], "data_ptr")
+    if out is None:
+        if on_device:
+            import torch
+            out = torch.zeros(nbytes, dtype=torch.uint8, device=bases[0].device)
+        else:
+            out = np.zeros(nbytes, dtype=np.uint8)
+    if on_device or hasattr(out, "data_ptr"):
+        import torch
+        dev = bases[0].device if on_device else out.device
+        lib().itwSetStream(torch.cuda.current_stream(dev).cuda_stream)
+    dst = out.data_ptr() if hasattr(out, "data_ptr") else out.ctypes.data
+    if settings is None and base == "bc7":
+        settings = bc7_profile(profile or "slow")
+    elif settings is None and base == "bc6h":
+        settings = bc6h_profile(profile or "slow")
+    elif settings is None and base == "etc1":
+        settings = etc_profile(profile or "slow")
+    sp = C.cast(C.byref(settings), C.c_void_p) if settings is not None else None
+    cb = PROGRESS_FUNC(progress) if progress else None
+    ok = lib().itwCompressImageMipped(C.cast(_surfaces(bases), C.c_void_p), len(bases), levels, int(normal_ops), dst, DXGI_FORMAT[fmt],
+                                      sp, C.cast(cb, C.c_void_p) if cb else None, None)
+    return bool(ok), out
 
 
 def mip_chain(img):
