@@ -56,6 +56,29 @@ void itwTestCombinerHold(int requests, int timeout_ms);
  * devices, since it was loaded.  The hooks build counts always, not only under ITW_COALESCE_DEBUG. */
 void itwTestCombinerCounters(int64_t out[5]);
 
+/* The route witness (csrc/bc7.hip launch_bc7, csrc/abi.hip launch(); tests/test_gpu_launch_switches.py): which launch shape the BC7 calls of
+ * this library instance took.  Host-side counters only -- no kernel, launch or workspace differs from the product's.
+ *   the branch launch_bc7 took, one count per call:        WIDE .. PROBE_IGNORED (the early return for a probe without an order verdict)
+ *   inside the bounded routes, one count per call where it holds:
+ *     TWO_BANDS     launch_rgb_bounded / launch_alpha_first_bounded7 cut the surface into two bands
+ *     PILOT         both gated continuations were enqueued behind the pilot's estimate
+ *     PAIRS         the pair route (ITW_BC7_PAIRS)                     ROT_TASKS  the rotation lists (ITW_BC7_ROT_TASKS)
+ *     COMPACT       the bands were built with a compact copy of the listed blocks' texels (ITW_BC7_COMPACT)
+ *     HOST_VERDICT  the estimate was left for the host (a VERDICT_BAND or PROBE of a staged call)
+ *     PROBE         only the estimate ran, nothing was encoded
+ *   the LaunchShape::Kind of every BC7 launch() of abi.hip: SHAPE_WHOLE .. SHAPE_PROBE */
+enum itw_test_bc7_route {
+    ITW_ROUTE_WIDE, ITW_ROUTE_PER_FAMILY, ITW_ROUTE_ALPHA_FIRST_BOUNDED7, ITW_ROUTE_ALPHA_FIRST_BOUNDED, ITW_ROUTE_ALPHA_FIRST_PLAIN,
+    ITW_ROUTE_RGB_BOUNDED, ITW_ROUTE_REFERENCE_ORDER, ITW_ROUTE_PROBE_IGNORED,
+    ITW_ROUTE_TWO_BANDS, ITW_ROUTE_PILOT, ITW_ROUTE_PAIRS, ITW_ROUTE_ROT_TASKS, ITW_ROUTE_COMPACT, ITW_ROUTE_HOST_VERDICT, ITW_ROUTE_PROBE,
+    ITW_ROUTE_SHAPE_WHOLE, ITW_ROUTE_SHAPE_STAGED, ITW_ROUTE_SHAPE_BAND, ITW_ROUTE_SHAPE_VERDICT_BAND, ITW_ROUTE_SHAPE_PROBE,
+    ITW_ROUTE_COUNTERS
+};
+/* out[0 .. min(n, ITW_ROUTE_COUNTERS) - 1] = the counters in the enum's order: of this library instance, all threads and devices, since it was
+ * loaded or last reset. */
+void itwTestBc7RouteCounters(int64_t* out, int n);
+void itwTestBc7RouteCountersReset(void);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

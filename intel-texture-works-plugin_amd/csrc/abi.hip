@@ -268,6 +268,9 @@ struct LaunchShape {
     enum Kind { WHOLE, STAGED, BAND, VERDICT_BAND, PROBE } kind = WHOLE;
     size_t ws_off = 0;
 };
+#ifdef ITW_TEST_HOOKS
+static_assert(ITW_ROUTE_SHAPE_WHOLE + LaunchShape::PROBE == ITW_ROUTE_SHAPE_PROBE && ITW_ROUTE_SHAPE_WHOLE + LaunchShape::BAND == ITW_ROUTE_SHAPE_BAND, "itw_test_hooks.h lists the shapes in Kind's order");
+#endif
 
 void launch(const Job& j, const uint8_t* d_src, int64_t stride, int w, int h, uint8_t* d_dst, hipStream_t st, LaunchShape shape = {})
 {
@@ -277,6 +280,7 @@ void launch(const Job& j, const uint8_t* d_src, int64_t stride, int w, int h, ui
     case itw::BCN_BC3:  itw::launch_bc3(d_src, stride, w, h, d_dst, st); break;
     case itw::BCN_BC7:
         ensure_bc7_aux();
+        ITW_ROUTE_SEEN(ITW_ROUTE_SHAPE_WHOLE + (int)shape.kind);                // (the route witness's shapes are in LaunchShape::Kind's order)
         tls.aux.wide_max_blocks = shape.kind == LaunchShape::WHOLE ? 0 : staged_wide_max_blocks();
         {
             // the per-call fields of the shared aux block go back to their defaults however this call ends (a failure is a C++ exception here,
@@ -1626,6 +1630,13 @@ void itwTestCombinerCounters(int64_t out[5])
     out[0] = g_cstats.bursts.load(); out[1] = g_cstats.batches.load(); out[2] = g_cstats.requests.load(); out[3] = g_cstats.calls.load();
     out[4] = g_hold_timeouts.load();
 }
+
+void itwTestBc7RouteCounters(int64_t* out, int n)
+{
+    if (out && n > 0) itw::bc7_route_counters(out, n);
+}
+
+void itwTestBc7RouteCountersReset(void) { itw::bc7_route_counters_reset(); }
 #endif // ITW_TEST_HOOKS
 
 } // extern "C"

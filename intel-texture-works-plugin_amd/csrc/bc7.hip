@@ -64,6 +64,9 @@
 #include "bc7_exact.hpp"
 #include "kernels.hpp"
 #include "host_rt.hpp"
+#ifdef ITW_TEST_HOOKS
+#include "../../include/itw_test_hooks.h"
+#endif
 
 namespace itw {
 
@@ -2284,6 +2287,17 @@ void launch_bc7_test_rot_bounds(const uint8_t* src, int64_t stride, int width, i
     const dim3 grid((unsigned)((n + TPB - 1) / TPB));
     with_bool(vec, [&](auto V) { hipLaunchKernelGGL((bc7_test_rot_bounds<decltype(V)::value>), grid, dim3(TPB), 0, st, src, stride, bx, (int32_t)n, out); });
 }
+// test hook (itwTestBc7RouteCounters): the route witness -- what ITW_ROUTE_SEEN counts, here and in abi.hip's launch()
+static std::atomic<long long> g_route_seen[ITW_ROUTE_COUNTERS];
+void bc7_route_seen(int what) { g_route_seen[what].fetch_add(1, std::memory_order_relaxed); }
+void bc7_route_counters(int64_t* out, int n)
+{
+    for (int i = 0; i < n && i < ITW_ROUTE_COUNTERS; i++) out[i] = g_route_seen[i].load(std::memory_order_relaxed);
+}
+void bc7_route_counters_reset()
+{
+    for (int i = 0; i < ITW_ROUTE_COUNTERS; i++) g_route_seen[i].store(0, std::memory_order_relaxed);
+}
 #endif // ITW_TEST_HOOKS
 
 // ---- the environment switches: one table, one reader -------------------------------------------------------------------------
@@ -2699,6 +2713,7 @@ static void launch_alpha_first_bounded7(const Fused& C)
     hipStream_t st = C.L.st;
     ITW_CHECK(hipMemsetAsync(C.ctr, 0, CTR_WORDS * sizeof(int32_t), st));  // the finish phases append to the lists through them
     const bool two = two_bands(C);
+    if (two) ITW_ROUTE_SEEN(ITW_ROUTE_TWO_BANDS);
     auto chain = [&](int k, hipStream_t s) {
         Band B = make_band(C, two, k, s);
         const size_t share = two ? k * C.W.band[0].cap : 0;                 // a band's share of each list region
@@ -2849,13 +2864,20 @@ static void launch_rgb_bounded(const Fused& C)
     const bool two = two_bands(C), rotations_ok = C.M.channels == 3 && C.L.S.mode45_channel0 >= 0 && C.L.S.mode45_channel0 <= 3;
     const bool pairs = env_every_call(ENV_PAIRS), rot_tasks = env_every_call(ENV_ROT_TASKS) && rotations_ok;
     const RgbRoute R{two, pairs, rot_tasks, two && bc7_pilot_threshold() >= 0 && aux->mid};
+    if (R.two) ITW_ROUTE_SEEN(ITW_ROUTE_TWO_BANDS);
+    if (R.pilot) ITW_ROUTE_SEEN(ITW_ROUTE_PILOT);
+    if (R.pairs) ITW_ROUTE_SEEN(ITW_ROUTE_PAIRS);
+    if (R.rot_tasks) ITW_ROUTE_SEEN(ITW_ROUTE_ROT_TASKS);
     if (!R.two) {
         const Band B = rgb_band(C, R, 0, st);
+        if (B.compact) ITW_ROUTE_SEEN(ITW_ROUTE_COMPACT);
         rgb_setup(C, R, B, B);
         // a staged run of a host-pointer call (abi.hip) wants the same estimate, left for the HOST to read under the next run's upload -- it picks
         // the launch shape of the remaining runs; a probe scans what the estimate looks at and nothing else
         const bool verdict = aux && aux->verdict && aux->verdict->event;
         const bool probe = verdict && aux->probe;
+        if (verdict) ITW_ROUTE_SEEN(ITW_ROUTE_HOST_VERDICT);
+        if (probe) ITW_ROUTE_SEEN(ITW_ROUTE_PROBE);
         if (probe) scan_rgb(C, SCAN02, Span{ChunkSel{2, 1, 0, nullptr, 0}, (C.nchunks + 7) / 8, st, C.wins4, C.L.n});
         else rgb_head(C, B);
         if (verdict) {
@@ -2868,6 +2890,7 @@ static void launch_rgb_bounded(const Fused& C)
     }
     hipStream_t s2 = aux->stream;
     const Band A = rgb_band(C, R, 0, st), B = rgb_band(C, R, 1, s2);
+    if (A.compact && B.compact) ITW_ROUTE_SEEN(ITW_ROUTE_COMPACT);
     rgb_setup(C, R, A, B);
     ITW_CHECK(hipEventRecord(aux->fork, st));                // whatever feeds `src` on st (an upload), and the setup above
     ITW_CHECK(hipStreamWaitEvent(s2, aux->fork, 0));
@@ -2926,15 +2949,15 @@ void launch_bc7(const uint8_t* src, int64_t stride, int width, int height, uint8
     L.grid = dim3((unsigned)((n + TPB - 1) / TPB));
     L.st = st; L.src = src; L.stride = stride; L.bx = bx; L.n = (int32_t)n; L.dst = dst; L.first = 1;
     const bool single = aux && aux->single;
-    if (aux && aux->probe && !has_order_verdict(M)) return;   // only the bounded order of the RGB profiles has a verdict to estimate
-    if (!single && bc7_use_wide(n, L.S, M, aux ? aux->wide_max_blocks : 0)) { launch_bc7_wide(L, M, workspace, aux); return; }
+    if (aux && aux->probe && !has_order_verdict(M)) { ITW_ROUTE_SEEN(ITW_ROUTE_PROBE_IGNORED); return; }   // only the bounded order of the RGB profiles has a verdict to estimate
+    if (!single && bc7_use_wide(n, L.S, M, aux ? aux->wide_max_blocks : 0)) { ITW_ROUTE_SEEN(ITW_ROUTE_WIDE); launch_bc7_wide(L, M, workspace, aux); return; }
     // two launches (scan of all families, refinement of all modes) unless a ranked list is longer than 16 shapes or ITW_BC7_FUSED=0
-    if (!env_once(ENV_FUSED) || M.long13 || M.long7 || !M.any()) { launch_per_family(L, M); return; }
+    if (!env_once(ENV_FUSED) || M.long13 || M.long7 || !M.any()) { ITW_ROUTE_SEEN(ITW_ROUTE_PER_FAMILY); launch_per_family(L, M); return; }
     const Fused C = fused_context(L, M, workspace, aux);
-    if (M.alpha_first && M.bounded && M.on7 && !M.r7 && (M.on45 || M.on6)) launch_alpha_first_bounded7(C);
-    else if (M.alpha_first) launch_alpha_first(C);
-    else if (M.rgb_bounded) launch_rgb_bounded(C);
-    else launch_reference_order(C);
+    if (M.alpha_first && M.bounded && M.on7 && !M.r7 && (M.on45 || M.on6)) { ITW_ROUTE_SEEN(ITW_ROUTE_ALPHA_FIRST_BOUNDED7); launch_alpha_first_bounded7(C); }
+    else if (M.alpha_first) { ITW_ROUTE_SEEN(M.bounded ? ITW_ROUTE_ALPHA_FIRST_BOUNDED : ITW_ROUTE_ALPHA_FIRST_PLAIN); launch_alpha_first(C); }
+    else if (M.rgb_bounded) { ITW_ROUTE_SEEN(ITW_ROUTE_RGB_BOUNDED); launch_rgb_bounded(C); }
+    else { ITW_ROUTE_SEEN(ITW_ROUTE_REFERENCE_ORDER); launch_reference_order(C); }
 }
 
 } // namespace itw

@@ -59,6 +59,16 @@ void launch_bc7 (const uint8_t* src, int64_t stride, int width, int height, uint
 // test hook: bc7_exact.hpp's two_subset_bound of all 64 two-subset shapes of every block, out[block * 64 + shape] (device memory)
 void launch_bc7_test_bounds(const uint8_t* src, int64_t stride, int width, int height, float* out, hipStream_t st);
 void launch_bc7_test_rot_bounds(const uint8_t* src, int64_t stride, int width, int height, float* out, hipStream_t st);
+// test hook (itwTestBc7RouteCounters): the route witness, host-side counters indexed by include/itw_test_hooks.h's itw_test_bc7_route.  The hooks build
+// counts one at ITW_ROUTE_SEEN(what); in the product the macro is empty.
+#ifdef ITW_TEST_HOOKS
+void bc7_route_seen(int what);
+void bc7_route_counters(int64_t* out, int n);
+void bc7_route_counters_reset();
+#define ITW_ROUTE_SEEN(what) ::itw::bc7_route_seen(what)
+#else
+#define ITW_ROUTE_SEEN(what) ((void)0)
+#endif
 // `workspace`: device memory of bc6h_workspace_bytes(width, height, s) bytes (0 for most calls: only small calls of the slow
 // profiles, which take the wide shape, need any); nullptr keeps the one-kernel path.
 size_t bc6h_workspace_bytes(int width, int height, const bc6h_enc_settings& s);

@@ -40,7 +40,11 @@ EXPORTED_SYMBOLS = tuple(
     + ["itwKtxHeaderBytes", "itwKtxFileBytes", "itwKtxWriteHeader", "itwKtxReadHeader", "itwKtxWriteFile", "itwKtxImage"])
 # include/itw_test_hooks.h: exported by libispc_texcomp_test.so only (the same sources built with -DITW_TEST_HOOKS), never by the product
 TEST_HOOK_SYMBOLS = ("itwTestRcp", "itwTestRsqrt", "itwTestF2I", "itwTestBc7TwoSubsetBounds", "itwTestBc7RotationBounds", "itwTestBc45IndexTable", "itwTestBc45ClosestS",
-                     "itwMultiGpuTestInjectFailure", "itwTestCombinerHold", "itwTestCombinerCounters")
+                     "itwMultiGpuTestInjectFailure", "itwTestCombinerHold", "itwTestCombinerCounters", "itwTestBc7RouteCounters", "itwTestBc7RouteCountersReset")
+# enum itw_test_bc7_route (include/itw_test_hooks.h), in its order: what itwTestBc7RouteCounters fills
+BC7_ROUTE_COUNTERS = ("WIDE", "PER_FAMILY", "ALPHA_FIRST_BOUNDED7", "ALPHA_FIRST_BOUNDED", "ALPHA_FIRST_PLAIN", "RGB_BOUNDED", "REFERENCE_ORDER", "PROBE_IGNORED",
+                      "TWO_BANDS", "PILOT", "PAIRS", "ROT_TASKS", "COMPACT", "HOST_VERDICT", "PROBE",
+                      "SHAPE_WHOLE", "SHAPE_STAGED", "SHAPE_BAND", "SHAPE_VERDICT_BAND", "SHAPE_PROBE")
 
 
 
@@ -308,6 +312,10 @@ def _load(path, hooks):
             L.itwTestCombinerHold.restype = None
             L.itwTestCombinerCounters.argtypes = [C.POINTER(C.c_int64)]
             L.itwTestCombinerCounters.restype = None
+            L.itwTestBc7RouteCounters.argtypes = [C.POINTER(C.c_int64), C.c_int]
+            L.itwTestBc7RouteCounters.restype = None
+            L.itwTestBc7RouteCountersReset.argtypes = []
+            L.itwTestBc7RouteCountersReset.restype = None
         # dispatch layer (itw_dispatch.h)
         L.GetProcessorCount.restype = C.c_int
         L.GetBytesPerBlock.argtypes = [C.c_int]

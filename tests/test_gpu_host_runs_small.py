@@ -3,8 +3,9 @@
 BC7 the runs are bands -- each run's kernels on one of two streams, in its own slice of the workspace, the first one leaving the pilot's
 verdict -- and every byte of every call is compared with the oracle: after one another on changing content (slices, events and verdict
 reused), from a pitched and a bottom-up source, into a device destination, as one-row runs; BC6H `fast` runs without bands, and BC1 (one
-run by default) cut by ITW_HOST_CHUNKS.  These tests cannot tell which launch shape a run took: the 2048 x 4096 calls of
-tests/test_gpu_host_pointer_runs.py remain the ones that pin the alternation between bands and wide runs."""
+run by default) cut by ITW_HOST_CHUNKS.  These tests compare bytes only; which launch shape each run took -- bands, wide runs, the probe --
+is pinned at this size by tests/test_gpu_launch_switches.py, which reads the route witness of the hooks build, and at 2048 x 4096 by the
+alternation of tests/test_gpu_host_pointer_runs.py."""
 import contextlib
 import ctypes as C
 import os
