@@ -79,6 +79,20 @@ enum itw_test_bc7_route {
 void itwTestBc7RouteCounters(int64_t* out, int n);
 void itwTestBc7RouteCountersReset(void);
 
+/* What a two-band call of the RGB bounded order counted on the device.  Arm (on != 0), run calls, read: each such call synchronises and leaves
+ * its counters, the last one stands.  out[0 .. min(n, ITW_BC7_CALL_COUNTERS) - 1] in the enum's order; the per-band ones are band 0 then band 1. */
+enum itw_test_bc7_call_counter {
+    ITW_BC7_CC_PILOT_LISTED, ITW_BC7_CC_PILOT_SAMPLED, ITW_BC7_CC_PILOT_FLAG,
+    ITW_BC7_CC_ROT_LISTS,                               /* [2][3]: the rotation lists' lengths */
+    ITW_BC7_CC_LISTED = ITW_BC7_CC_ROT_LISTS + 6,       /* [2]: blocks listed for modes 1/3 */
+    ITW_BC7_CC_PAIRS = ITW_BC7_CC_LISTED + 2,           /* [2]: (block, shape) pairs in the buckets */
+    ITW_BC7_CC_OVERFLOW = ITW_BC7_CC_PAIRS + 2,         /* [2]: a bucket overflowed */
+    ITW_BC7_CC_REDO = ITW_BC7_CC_OVERFLOW + 2,          /* [2]: blocks deferred to the full list scan */
+    ITW_BC7_CALL_COUNTERS = ITW_BC7_CC_REDO + 2
+};
+void itwTestBc7CallCountersArm(int on);
+void itwTestBc7CallCounters(int32_t* out, int n);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

@@ -1637,6 +1637,12 @@ void itwTestBc7RouteCounters(int64_t* out, int n)
 }
 
 void itwTestBc7RouteCountersReset(void) { itw::bc7_route_counters_reset(); }
+
+void itwTestBc7CallCountersArm(int on) { itw::bc7_arm_call_counters(on); }
+void itwTestBc7CallCounters(int32_t* out, int n)
+{
+    if (out && n > 0) itw::bc7_call_counters(out, n);
+}
 #endif // ITW_TEST_HOOKS
 
 } // extern "C"

@@ -1496,6 +1496,32 @@ __device__ __forceinline__ int32_t append_to_list(int32_t* __restrict__ list, in
     }
     return pos;
 }
+// the same for the three rotation lists of a band at once, claimed per WORKGROUP: every wave leaves its three popcounts in `s_cnt`, three lanes
+// of the workgroup add the totals to the three consecutive list lengths in one atomic instruction and turn the popcounts into each wave's
+// base, and the lanes write behind it.  Two barriers and one atomic instruction per workgroup where the per-wave append made twelve atomics, each
+// waited for by its whole wave (the lengths share a cache line that every XCD contends for).  Every thread of the workgroup has to get here, idle
+// lanes included.  `s_cnt` is storage of its own: other waves of the workgroup may still be refining out of s_pal when the first one arrives.
+__device__ __forceinline__ void append_to_rotation_lists(int32_t (*s_cnt)[4], const RotRegion& R, bool need0, bool need1, bool need2, int32_t b)
+{
+    const int lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const unsigned long long m0 = __ballot(need0), m1 = __ballot(need1), m2 = __ballot(need2);
+    if (lane < 3) s_cnt[wave][lane] = (int32_t)__popcll(lane == 0 ? m0 : (lane == 1 ? m1 : m2));
+    __syncthreads();
+    if (threadIdx.x < 3u) {
+        int32_t t = 0;
+#pragma unroll
+        for (int w = 0; w < TPB / 64; w++) t += s_cnt[w][lane];
+        int32_t base = t ? atomicAdd(R.counts + lane, t) : 0;        // nothing to claim (modes 4/5 off, no survivor): no atomic
+#pragma unroll
+        for (int w = 0; w < TPB / 64; w++) { const int32_t c = s_cnt[w][lane]; s_cnt[w][lane] = base; base += c; }
+    }
+    __syncthreads();
+    const unsigned long long below = (1ull << lane) - 1ull;
+    if (need0) R.lists[                      s_cnt[wave][0] + (int32_t)__popcll(m0 & below)] = b;
+    if (need1) R.lists[(int64_t)R.cap     + s_cnt[wave][1] + (int32_t)__popcll(m1 & below)] = b;
+    if (need2) R.lists[(int64_t)R.cap * 2 + s_cnt[wave][2] + (int32_t)__popcll(m2 & below)] = b;
+}
 
 // PHASE 0: every mode, reference order (RGB profiles).  RGBA profiles run in two phases so that the three-channel modes can be
 // skipped where they cannot win: PHASE 1 = the alpha-capable modes 7,4,5,6 (their relative order kept), leaves the block and
@@ -1565,6 +1591,8 @@ bc7_finish_all(const uint8_t* __restrict__ src, int64_t stride, int32_t blocks_x
     __shared__ uint2 s_pal[LANE_PAL_LEVELS * TPB];   // refinement: a palette per subset of the lane's winner
     __shared__ int32_t s_at[TAIL3 ? TPB / 64 : 1][64];             // PAIRS: per (wave, shape) the survivors, then where they go in the bucket (its own
                                                                     // kilobyte: other waves of the workgroup still use s_pal when the first one gets here)
+    __shared__ int32_t s_listed[TPB / 64];                           // PAIRS: per wave the blocks it lists, then its base in the list (the 65th counter)
+    __shared__ int32_t s_rot[PHASE == 9 ? TPB / 64 : 1][4];       // PHASE 9: per (wave, rotation) the listed blocks, then the wave's base in the list
     if (sel.gate && *sel.gate != sel.want) return;                   // the pilot chose the other order (whole grid: no barrier is pending)
     const int32_t nact = LISTED ? *in_count : nblocks;
     const int32_t chunk = LISTED ? (int32_t)blockIdx.x : sel_chunk(sel, (int32_t)blockIdx.x);
@@ -1610,11 +1638,10 @@ bc7_finish_all(const uint8_t* __restrict__ src, int64_t stride, int32_t blocks_x
         stats_int<3>(full, ln.tx.pl, whole_block());
         const float lim = (float)e02 - 0.5f;
         const bool on45 = live && S.mode_selection[2];
+        bool need[3];
 #pragma unroll
-        for (int r = 0; r < 3; r++) {
-            const bool need = on45 && r >= S.mode45_channel0 && !(rotation_bound(r, full) >= lim);
-            append_to_list(R.lists + (int64_t)r * R.cap, R.counts + r, need, b);
-        }
+        for (int r = 0; r < 3; r++) need[r] = on45 && r >= S.mode45_channel0 && !(rotation_bound(r, full) >= lim);
+        append_to_rotation_lists(s_rot, R, need[0], need[1], need[2], b);      // idle lanes arrive too: it holds barriers
     }
     if (PHASE == 10) {
         // the one candidate bc7_rot_tasks left for the block, if any: admitted with the reference's strict `<`, then mode 6 in its place
@@ -1731,26 +1758,22 @@ bc7_finish_all(const uint8_t* __restrict__ src, int64_t stride, int32_t blocks_x
                 any |= __ballot(live && in) ? (1ull << shape) : 0ull;
             }
         }
-        const int32_t pos = append_to_list(out_list, out_count, live && need, b);
-        if (out_compact && pos >= 0) {                              // the listed block's texels, in list order (load_block_compact)
-            uint4* c = out_compact + (int64_t)pos * 4;
-#pragma unroll
-            for (int y = 0; y < 4; y++) c[y] = make_uint4(ln.tx.w[y * 4 + 0], ln.tx.w[y * 4 + 1], ln.tx.w[y * 4 + 2], ln.tx.w[y * 4 + 3]);
-        }
-        if (pairs) {
-            // `pos` is the block's slot: its merged words, its compact texels, what the buckets hold.  Clear the words; a block more than
-            // half of whose shapes survive (photograph-like content inside a surface the pilot gave the bounded order) is cheaper in the
-            // full list scan, which takes the 64 shapes without rank keys: straight to the second list, no pairs, its words say so
+        int32_t pos = -1;                                            // the block's position in the list: its slot
+        if (!pairs) pos = append_to_list(out_list, out_count, live && need, b);
+        else {
+            // `pos` is the block's slot: its merged words, its compact texels, what the buckets hold.  The list's stretch is claimed per
+            // WORKGROUP together with the buckets' -- the list length is the 65th counter of that claim, no atomic per wave that the whole wave
+            // waits for before it can write anything -- so everything that needs `pos` follows the claim.  A block more than half of whose
+            // shapes survive (photograph-like content inside a surface the pilot gave the bounded order) is cheaper in the full list scan,
+            // which takes the 64 shapes without rank keys: straight to the second list, no pairs, its words say so
             // (lane and wave formed here, not from an expression of threadIdx the kernel's head also has: that one would be kept -- spilled --
             // through the refinement)
             const int lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
             const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
             const PairRegion P = target->P;
-            int32_t* pair_redo = target->redo;
             const bool heavy = __popcll(mine) > PAIR_MAX_PER_BLOCK;
-            if (pos >= 0) { P.words[2 * (int64_t)pos] = heavy ? PAIR_WORD_HEAVY : ~0ull; P.words[2 * (int64_t)pos + 1] = ~0ull; }
             if (heavy) mine = 0;
-            append_to_list(pair_redo, P.ctr + PAIR_CTR_REDO, heavy, b);
+            const unsigned long long listed = __ballot(live && need);
             // survivors per (wave, shape): lane s carries shape s's count (shapes nobody in the wave keeps are not visited).  No global
             // atomic per (wave, shape): each one waited for, that made the first builder latency bound (1.0 ms instead of 0.1)
             int32_t k = 0;
@@ -1760,6 +1783,7 @@ bc7_finish_all(const uint8_t* __restrict__ src, int64_t stride, int32_t blocks_x
                 k = (lane == shape) ? c : k;
             }
             s_at[wave][lane] = k;
+            if (lane == 0) s_listed[wave] = (int32_t)__popcll(listed);
             __syncthreads();
             if (threadIdx.x < 64u) {                                 // the workgroup's stretch of each bucket: 64 atomics, one instruction
                 int32_t t = 0;
@@ -1769,8 +1793,18 @@ bc7_finish_all(const uint8_t* __restrict__ src, int64_t stride, int32_t blocks_x
                 if (base + t > P.cap) { P.ctr[PAIR_CTR_OVERFLOW] = 1; base = -1; }
 #pragma unroll
                 for (int w = 0; w < TPB / 64; w++) { const int32_t c = s_at[w][lane]; s_at[w][lane] = base; base = base < 0 ? -1 : base + c; }
+            } else if (threadIdx.x == 64u) {                         // and its stretch of the list: the first wave's 64 lanes are taken, so the
+                int32_t t = 0;                                       // second wave issues this one beside them
+#pragma unroll
+                for (int w = 0; w < TPB / 64; w++) t += s_listed[w];
+                int32_t base = t ? atomicAdd(out_count, t) : 0;
+#pragma unroll
+                for (int w = 0; w < TPB / 64; w++) { const int32_t c = s_listed[w]; s_listed[w] = base; base += c; }
             }
             __syncthreads();
+            if (live && need) { pos = s_listed[wave] + (int32_t)__popcll(listed & ((1ull << lane) - 1ull)); out_list[pos] = b; }
+            if (pos >= 0) { P.words[2 * (int64_t)pos] = heavy ? PAIR_WORD_HEAVY : ~0ull; P.words[2 * (int64_t)pos + 1] = ~0ull; }
+            append_to_list(target->redo, P.ctr + PAIR_CTR_REDO, heavy, b);
             const int32_t at = s_at[wave][lane];                     // lane s: where the wave's survivors of shape s go
             for (unsigned long long rest = any; rest; rest &= rest - 1ull) {
                 const int shape = __builtin_amdgcn_readfirstlane((int)__builtin_ctzll(rest));
@@ -1779,6 +1813,11 @@ bc7_finish_all(const uint8_t* __restrict__ src, int64_t stride, int32_t blocks_x
                 const int32_t base = __builtin_amdgcn_readlane(at, shape);
                 if (in && base >= 0) P.buckets[(int64_t)shape * P.cap + base + (int32_t)__popcll(m & ((1ull << lane) - 1ull))] = pos;
             }
+        }
+        if (out_compact && pos >= 0) {                              // the listed block's texels, in list order (load_block_compact)
+            uint4* c = out_compact + (int64_t)pos * 4;
+#pragma unroll
+            for (int y = 0; y < 4; y++) c[y] = make_uint4(ln.tx.w[y * 4 + 0], ln.tx.w[y * 4 + 1], ln.tx.w[y * 4 + 2], ln.tx.w[y * 4 + 3]);
         }
         if (with7) append_to_list(out_list7, out_count7, live && need7, b);
     }
@@ -2297,6 +2336,15 @@ void bc7_route_counters(int64_t* out, int n)
 void bc7_route_counters_reset()
 {
     for (int i = 0; i < ITW_ROUTE_COUNTERS; i++) g_route_seen[i].store(0, std::memory_order_relaxed);
+}
+// test hook (itwTestBc7CallCounters): what the last two-band call of the RGB bounded order counted on the device (launch_rgb_bounded snapshots it
+// while armed; it synchronises)
+static std::atomic<int> g_counters_armed{0};
+static std::atomic<int32_t> g_call_counters[ITW_BC7_CALL_COUNTERS];
+void bc7_arm_call_counters(int on) { g_counters_armed.store(on ? 1 : 0, std::memory_order_relaxed); }
+void bc7_call_counters(int32_t* out, int n)
+{
+    for (int i = 0; i < n && i < ITW_BC7_CALL_COUNTERS; i++) out[i] = g_call_counters[i].load(std::memory_order_relaxed);
 }
 #endif // ITW_TEST_HOOKS
 
@@ -2904,6 +2952,23 @@ static void launch_rgb_bounded(const Fused& C)
     ITW_CHECK(hipEventRecord(aux->join, s2));
     ITW_CHECK(hipStreamWaitEvent(st, aux->join, 0));
     if (env_once(ENV_PILOT_DEBUG)) rgb_print_counters(C, R, A, B);
+#ifdef ITW_TEST_HOOKS
+    if (g_counters_armed.load(std::memory_order_relaxed)) {          // itwTestBc7CallCounters: the same words, for a test to assert on
+        int32_t h[CTR_WORDS + 2 * PAIR_CTR_WORDS], out[ITW_BC7_CALL_COUNTERS] = {};
+        ITW_CHECK(hipStreamSynchronize(st));
+        ITW_CHECK(hipMemcpy(h, C.ctr, sizeof h, hipMemcpyDeviceToHost));
+        out[ITW_BC7_CC_PILOT_LISTED] = h[CTR_PILOT + PILOT_LISTED]; out[ITW_BC7_CC_PILOT_SAMPLED] = h[CTR_PILOT + PILOT_SAMPLED]; out[ITW_BC7_CC_PILOT_FLAG] = h[CTR_PILOT_FLAG];
+        for (int k = 0; k < 2; k++) {
+            const int32_t* band = h + CTR_WORDS + k * PAIR_CTR_WORDS;
+            for (int r = 0; r < 3; r++) out[ITW_BC7_CC_ROT_LISTS + 3 * k + r] = h[(k ? CTR_BAND1 : CTR_ROT) + r];
+            out[ITW_BC7_CC_LISTED + k] = band[PAIR_CTR_LIST];
+            for (int s = 0; s < 64; s++) out[ITW_BC7_CC_PAIRS + k] += band[s];
+            out[ITW_BC7_CC_OVERFLOW + k] = band[PAIR_CTR_OVERFLOW];
+            out[ITW_BC7_CC_REDO + k] = band[PAIR_CTR_REDO];
+        }
+        for (int i = 0; i < ITW_BC7_CALL_COUNTERS; i++) g_call_counters[i].store(out[i], std::memory_order_relaxed);
+    }
+#endif
 }
 
 // The reference's order in two launches: {0,2} and {1,3} scanned together, {7}, then every mode's refinement and {4,5}, {6}.

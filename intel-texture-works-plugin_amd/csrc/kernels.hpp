@@ -65,6 +65,8 @@ void launch_bc7_test_rot_bounds(const uint8_t* src, int64_t stride, int width, i
 void bc7_route_seen(int what);
 void bc7_route_counters(int64_t* out, int n);
 void bc7_route_counters_reset();
+void bc7_arm_call_counters(int on);                      // test hook (itwTestBc7CallCounters): two-band RGB bounded calls leave their device counters
+void bc7_call_counters(int32_t* out, int n);
 #define ITW_ROUTE_SEEN(what) ::itw::bc7_route_seen(what)
 #else
 #define ITW_ROUTE_SEEN(what) ((void)0)

@@ -40,7 +40,11 @@ EXPORTED_SYMBOLS = tuple(
     + ["itwKtxHeaderBytes", "itwKtxFileBytes", "itwKtxWriteHeader", "itwKtxReadHeader", "itwKtxWriteFile", "itwKtxImage"])
 # include/itw_test_hooks.h: exported by libispc_texcomp_test.so only (the same sources built with -DITW_TEST_HOOKS), never by the product
 TEST_HOOK_SYMBOLS = ("itwTestRcp", "itwTestRsqrt", "itwTestF2I", "itwTestBc7TwoSubsetBounds", "itwTestBc7RotationBounds", "itwTestBc45IndexTable", "itwTestBc45ClosestS",
-                     "itwMultiGpuTestInjectFailure", "itwTestCombinerHold", "itwTestCombinerCounters", "itwTestBc7RouteCounters", "itwTestBc7RouteCountersReset")
+                     "itwMultiGpuTestInjectFailure", "itwTestCombinerHold", "itwTestCombinerCounters", "itwTestBc7RouteCounters", "itwTestBc7RouteCountersReset",
+                     "itwTestBc7CallCountersArm", "itwTestBc7CallCounters")
+# enum itw_test_bc7_call_counter (include/itw_test_hooks.h): what itwTestBc7CallCounters fills; the per-band ones are band 0 then band 1
+BC7_CALL_COUNTERS = ("pilot_listed", "pilot_sampled", "pilot_flag", "rot00", "rot01", "rot02", "rot10", "rot11", "rot12", "listed0", "listed1",
+                     "pairs0", "pairs1", "overflow0", "overflow1", "redo0", "redo1")
 # enum itw_test_bc7_route (include/itw_test_hooks.h), in its order: what itwTestBc7RouteCounters fills
 BC7_ROUTE_COUNTERS = ("WIDE", "PER_FAMILY", "ALPHA_FIRST_BOUNDED7", "ALPHA_FIRST_BOUNDED", "ALPHA_FIRST_PLAIN", "RGB_BOUNDED", "REFERENCE_ORDER", "PROBE_IGNORED",
                       "TWO_BANDS", "PILOT", "PAIRS", "ROT_TASKS", "COMPACT", "HOST_VERDICT", "PROBE",
@@ -316,6 +320,10 @@ def _load(path, hooks):
             L.itwTestBc7RouteCounters.restype = None
             L.itwTestBc7RouteCountersReset.argtypes = []
             L.itwTestBc7RouteCountersReset.restype = None
+            L.itwTestBc7CallCountersArm.argtypes = [C.c_int]
+            L.itwTestBc7CallCountersArm.restype = None
+            L.itwTestBc7CallCounters.argtypes = [C.POINTER(C.c_int32), C.c_int]
+            L.itwTestBc7CallCounters.restype = None
         # dispatch layer (itw_dispatch.h)
         L.GetProcessorCount.restype = C.c_int
         L.GetBytesPerBlock.argtypes = [C.c_int]
