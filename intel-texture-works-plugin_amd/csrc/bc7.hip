@@ -1572,8 +1572,123 @@ __device__ __forceinline__ bool mode6_cannot_win(Lane& ln)
 #ifndef BOUND_BAIL_LANES
 #define BOUND_BAIL_LANES 40
 #endif
+// The TAIL of the bounded orders' first refinement (PHASE 3 and PHASE 5 call it in place; bc7_bound_list, below bc7_finish_all, is PHASE 10's): the
+// one copy of the rules by which a block whose incumbent is `inc` (already in inc_err) gets on the list of modes 1/3 -- the 64 two-subset bounds,
+// the per-wave append or the workgroup's claim, the pairs bucketed by shape, the heavy blocks to the second list, the compact texels -- and,
+// PHASE 5 only (`out_list7`), on mode 7's list.  TAIL3: the RGB order, whose `out_count` has the band's PairTarget behind it.  `s_at` ([TPB / 64][64]
+// under TAIL3) and `s_listed` are the workgroup's LDS for the claim; every lane of the workgroup calls, idle lanes (`live` false) too: the claim
+// holds two barriers.
+template <bool TAIL3, int AT_ROWS>
+__device__ __forceinline__ void bounded_list_tail(Tex& tx, const int32_t inc, const int32_t opaque_err, const bool live, const int32_t b,
+                                                  int32_t (&s_at)[AT_ROWS][64], int32_t (&s_listed)[TPB / 64], int32_t* __restrict__ out_list, int32_t* __restrict__ out_count,
+                                                  int32_t* __restrict__ out_list7, int32_t* __restrict__ out_count7, uint4* __restrict__ out_compact)
+{
+    tx.fence();
+    IStats<3> full;
+    stats_int<3>(full, tx.pl, whole_block());
+    const float lim = (float)(inc - opaque_err) - 0.5f;            // errors are integers: a bound above inc - 1 already rules the shape out
+    const float lim7 = (float)inc - 0.5f;                           // mode 7 carries no opaque term
+    const bool with7 = !TAIL3 && out_list7 != nullptr;              // wave-uniform
+    // PAIRS (header above bc7_pair_scan): this launch also leaves the (block, shape) pairs of the listed blocks, so every shape is
+    // bounded for every lane -- no early exit, no bail -- and the lane keeps a bit per shape instead of `need` alone
+    // CONTRACT of TAIL3: `out_count` is word PAIR_CTR_LIST of a band's counter block that bc7_bounded_setup has filled in this call, so the
+    // band's PairTarget lies PAIR_CTR_TARGET - PAIR_CTR_LIST words behind it (the launcher refuses any other pointer)
+    const PairTarget* target = nullptr;
+    if (TAIL3) target = reinterpret_cast<const PairTarget*>(out_count + (PAIR_CTR_TARGET - PAIR_CTR_LIST));
+    const bool pairs = TAIL3 && target->P.words != nullptr;         // grid-uniform
+    bool need = !live, need7 = !live || !with7;                     // idle lanes never hold the loop up
+    unsigned long long mine = 0, any = 0;                           // shapes whose bound is below `lim`: the lane's, the wave's (scalar)
+#pragma unroll 1
+    for (int shape = 0; shape < 64; shape++) {
+        if (!pairs) {
+            if (__all(need && need7)) break;
+            // a wave most of whose blocks need the modes anyway stops bounding the others (visiting a block is always allowed):
+            // content the bound does not separate pays for a few shapes, not for 64
+            if (shape == BOUND_BAIL_AFTER && __popcll(__ballot(need && need7)) >= BOUND_BAIL_LANES) { need = true; need7 = true; break; }
+        }
+        const float lb = two_subset_bound(shape, tx.pl, full);
+        const bool in = !(lb >= lim);
+        need = need || in;
+        need7 = need7 || !(lb >= lim7);
+        if (pairs) {
+            mine |= (live && in) ? (1ull << shape) : 0ull;
+            any |= __ballot(live && in) ? (1ull << shape) : 0ull;
+        }
+    }
+    int32_t pos = -1;                                               // the block's position in the list: its slot
+    if (!pairs) pos = append_to_list(out_list, out_count, live && need, b);
+    else {
+        // `pos` is the block's slot: its merged words, its compact texels, what the buckets hold.  The list's stretch is claimed per
+        // WORKGROUP together with the buckets' -- the list length is the 65th counter of that claim, no atomic per wave that the whole wave
+        // waits for before it can write anything -- so everything that needs `pos` follows the claim.  A block more than half of whose
+        // shapes survive (photograph-like content inside a surface the pilot gave the bounded order) is cheaper in the full list scan,
+        // which takes the 64 shapes without rank keys: straight to the second list, no pairs, its words say so
+        // (lane and wave formed here, not from an expression of threadIdx the kernel's head also has: that one would be kept -- spilled --
+        // through the refinement)
+        const int lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+        const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+        const PairRegion P = target->P;
+        const bool heavy = __popcll(mine) > PAIR_MAX_PER_BLOCK;
+        if (heavy) mine = 0;
+        const unsigned long long listed = __ballot(live && need);
+        // survivors per (wave, shape): lane s carries shape s's count (shapes nobody in the wave keeps are not visited).  No global
+        // atomic per (wave, shape): each one waited for, that made the first builder latency bound (1.0 ms instead of 0.1)
+        int32_t k = 0;
+        for (unsigned long long rest = any; rest; rest &= rest - 1ull) {
+            const int shape = __builtin_amdgcn_readfirstlane((int)__builtin_ctzll(rest));
+            const int32_t c = (int32_t)__popcll(__ballot((mine >> shape) & 1ull));
+            k = (lane == shape) ? c : k;
+        }
+        s_at[wave][lane] = k;
+        if (lane == 0) s_listed[wave] = (int32_t)__popcll(listed);
+        __syncthreads();
+        if (threadIdx.x < 64u) {                                    // the workgroup's stretch of each bucket: 64 atomics, one instruction
+            int32_t t = 0;
+#pragma unroll
+            for (int w = 0; w < TPB / 64; w++) t += s_at[w][lane];
+            int32_t base = t ? atomicAdd(P.ctr + lane, t) : 0;
+            if (base + t > P.cap) { P.ctr[PAIR_CTR_OVERFLOW] = 1; base = -1; }
+#pragma unroll
+            for (int w = 0; w < TPB / 64; w++) { const int32_t c = s_at[w][lane]; s_at[w][lane] = base; base = base < 0 ? -1 : base + c; }
+        } else if (threadIdx.x == 64u) {                            // and its stretch of the list: the first wave's 64 lanes are taken, so the
+            int32_t t = 0;                                          // second wave issues this one beside them
+#pragma unroll
+            for (int w = 0; w < TPB / 64; w++) t += s_listed[w];
+            int32_t base = t ? atomicAdd(out_count, t) : 0;
+#pragma unroll
+            for (int w = 0; w < TPB / 64; w++) { const int32_t c = s_listed[w]; s_listed[w] = base; base += c; }
+        }
+        __syncthreads();
+        if (live && need) { pos = s_listed[wave] + (int32_t)__popcll(listed & ((1ull << lane) - 1ull)); out_list[pos] = b; }
+        if (pos >= 0) { P.words[2 * (int64_t)pos] = heavy ? PAIR_WORD_HEAVY : ~0ull; P.words[2 * (int64_t)pos + 1] = ~0ull; }
+        append_to_list(target->redo, P.ctr + PAIR_CTR_REDO, heavy, b);
+        const int32_t at = s_at[wave][lane];                        // lane s: where the wave's survivors of shape s go
+        for (unsigned long long rest = any; rest; rest &= rest - 1ull) {
+            const int shape = __builtin_amdgcn_readfirstlane((int)__builtin_ctzll(rest));
+            const bool in = (mine >> shape) & 1ull;
+            const unsigned long long m = __ballot(in);
+            const int32_t base = __builtin_amdgcn_readlane(at, shape);
+            if (in && base >= 0) P.buckets[(int64_t)shape * P.cap + base + (int32_t)__popcll(m & ((1ull << lane) - 1ull))] = pos;
+        }
+    }
+    if (out_compact && pos >= 0) {                                  // the listed block's texels, in list order (load_block_compact)
+        uint4* c = out_compact + (int64_t)pos * 4;
+#pragma unroll
+        for (int y = 0; y < 4; y++) c[y] = make_uint4(tx.w[y * 4 + 0], tx.w[y * 4 + 1], tx.w[y * 4 + 2], tx.w[y * 4 + 3]);
+    }
+    if (with7) append_to_list(out_list7, out_count7, live && need7, b);
+}
+
+// PHASE 10 holds three workgroups per CU (mode 6's 16-level palette leaves 44 KiB of LDS); the refinement phases two (214-256 VGPRs)
+#ifndef FINISH10_WAVES
+#define FINISH10_WAVES 3
+#endif
+#ifndef FINISH10_PAL_LEVELS
+#define FINISH10_PAL_LEVELS 16
+#endif
+__host__ __device__ constexpr int finish_all_waves(int phase) { return phase == 10 ? FINISH10_WAVES : FINISH_ALL_WAVES; }
 template <bool VEC16, int PHASE>
-__global__ void __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(FINISH_ALL_WAVES, FINISH_ALL_WAVES)))
+__global__ void __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(finish_all_waves(PHASE), finish_all_waves(PHASE))))
 bc7_finish_all(const uint8_t* __restrict__ src, int64_t stride, int32_t blocks_x, int32_t nblocks, uint8_t* __restrict__ dst,
                const uint32_t* __restrict__ wins4, const bc7_enc_settings S, int32_t* __restrict__ inc_err,
                const int32_t* __restrict__ in_list, const int32_t* __restrict__ in_count, int32_t* __restrict__ out_list, int32_t* __restrict__ out_count,
@@ -1588,8 +1703,8 @@ bc7_finish_all(const uint8_t* __restrict__ src, int64_t stride, int32_t blocks_x
     constexpr bool DO456 = PHASE == 0 || PHASE == 1 || PHASE == 3 || PHASE == 6;
     __shared__ unsigned short s_seed16[2048];
     __shared__ uint32_t s_seed32[2048];
-    __shared__ uint2 s_pal[LANE_PAL_LEVELS * TPB];   // refinement: a palette per subset of the lane's winner
-    __shared__ int32_t s_at[TAIL3 ? TPB / 64 : 1][64];             // PAIRS: per (wave, shape) the survivors, then where they go in the bucket (its own
+    __shared__ uint2 s_pal[(PHASE == 10 ? FINISH10_PAL_LEVELS : LANE_PAL_LEVELS) * TPB];   // refinement: a palette per subset of the lane's winner (PHASE 10: mode 6's 16 levels)
+    __shared__ int32_t s_at[PHASE == 3 ? TPB / 64 : 1][64];           // PAIRS: per (wave, shape) the survivors, then where they go in the bucket (its own
                                                                     // kilobyte: other waves of the workgroup still use s_pal when the first one gets here)
     __shared__ int32_t s_listed[TPB / 64];                           // PAIRS: per wave the blocks it lists, then its base in the list (the 65th counter)
     __shared__ int32_t s_rot[PHASE == 9 ? TPB / 64 : 1][4];       // PHASE 9: per (wave, rotation) the listed blocks, then the wave's base in the list
@@ -1726,100 +1841,8 @@ bc7_finish_all(const uint8_t* __restrict__ src, int64_t stride, int32_t blocks_x
         if (TAIL3) inc = ln.best_err + (ln.best_err < e02 ? 1 : 0);
         else            inc = (e02 <= e_alpha) ? e02 : e_alpha + 1;
         if (live) inc_err[b] = inc;
-        ln.tx.fence();
-        IStats<3> full;
-        stats_int<3>(full, ln.tx.pl, whole_block());
-        const float lim = (float)(inc - ln.opaque_err) - 0.5f;      // errors are integers: a bound above inc - 1 already rules the shape out
-        const float lim7 = (float)inc - 0.5f;                        // mode 7 carries no opaque term
-        const bool with7 = PHASE == 5 && out_list7 != nullptr;       // wave-uniform
-        // PAIRS (header above bc7_pair_scan): this launch also leaves the (block, shape) pairs of the listed blocks, so every shape is
-        // bounded for every lane -- no early exit, no bail -- and the lane keeps a bit per shape instead of `need` alone
-        // CONTRACT of PHASE 3: `out_count` is word PAIR_CTR_LIST of a band's counter block that bc7_bounded_setup has filled in this call, so the
-        // band's PairTarget lies PAIR_CTR_TARGET - PAIR_CTR_LIST words behind it (the launcher's `finish` refuses any other pointer)
-        const PairTarget* target = nullptr;
-        if (TAIL3) target = reinterpret_cast<const PairTarget*>(out_count + (PAIR_CTR_TARGET - PAIR_CTR_LIST));
-        const bool pairs = TAIL3 && target->P.words != nullptr;      // grid-uniform
-        bool need = !live, need7 = !live || !with7;                  // idle lanes never hold the loop up
-        unsigned long long mine = 0, any = 0;                        // shapes whose bound is below `lim`: the lane's, the wave's (scalar)
-#pragma unroll 1
-        for (int shape = 0; shape < 64; shape++) {
-            if (!pairs) {
-                if (__all(need && need7)) break;
-                // a wave most of whose blocks need the modes anyway stops bounding the others (visiting a block is always allowed):
-                // content the bound does not separate pays for a few shapes, not for 64
-                if (shape == BOUND_BAIL_AFTER && __popcll(__ballot(need && need7)) >= BOUND_BAIL_LANES) { need = true; need7 = true; break; }
-            }
-            const float lb = two_subset_bound(shape, ln.tx.pl, full);
-            const bool in = !(lb >= lim);
-            need = need || in;
-            need7 = need7 || !(lb >= lim7);
-            if (pairs) {
-                mine |= (live && in) ? (1ull << shape) : 0ull;
-                any |= __ballot(live && in) ? (1ull << shape) : 0ull;
-            }
-        }
-        int32_t pos = -1;                                            // the block's position in the list: its slot
-        if (!pairs) pos = append_to_list(out_list, out_count, live && need, b);
-        else {
-            // `pos` is the block's slot: its merged words, its compact texels, what the buckets hold.  The list's stretch is claimed per
-            // WORKGROUP together with the buckets' -- the list length is the 65th counter of that claim, no atomic per wave that the whole wave
-            // waits for before it can write anything -- so everything that needs `pos` follows the claim.  A block more than half of whose
-            // shapes survive (photograph-like content inside a surface the pilot gave the bounded order) is cheaper in the full list scan,
-            // which takes the 64 shapes without rank keys: straight to the second list, no pairs, its words say so
-            // (lane and wave formed here, not from an expression of threadIdx the kernel's head also has: that one would be kept -- spilled --
-            // through the refinement)
-            const int lane = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-            const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-            const PairRegion P = target->P;
-            const bool heavy = __popcll(mine) > PAIR_MAX_PER_BLOCK;
-            if (heavy) mine = 0;
-            const unsigned long long listed = __ballot(live && need);
-            // survivors per (wave, shape): lane s carries shape s's count (shapes nobody in the wave keeps are not visited).  No global
-            // atomic per (wave, shape): each one waited for, that made the first builder latency bound (1.0 ms instead of 0.1)
-            int32_t k = 0;
-            for (unsigned long long rest = any; rest; rest &= rest - 1ull) {
-                const int shape = __builtin_amdgcn_readfirstlane((int)__builtin_ctzll(rest));
-                const int32_t c = (int32_t)__popcll(__ballot((mine >> shape) & 1ull));
-                k = (lane == shape) ? c : k;
-            }
-            s_at[wave][lane] = k;
-            if (lane == 0) s_listed[wave] = (int32_t)__popcll(listed);
-            __syncthreads();
-            if (threadIdx.x < 64u) {                                 // the workgroup's stretch of each bucket: 64 atomics, one instruction
-                int32_t t = 0;
-#pragma unroll
-                for (int w = 0; w < TPB / 64; w++) t += s_at[w][lane];
-                int32_t base = t ? atomicAdd(P.ctr + lane, t) : 0;
-                if (base + t > P.cap) { P.ctr[PAIR_CTR_OVERFLOW] = 1; base = -1; }
-#pragma unroll
-                for (int w = 0; w < TPB / 64; w++) { const int32_t c = s_at[w][lane]; s_at[w][lane] = base; base = base < 0 ? -1 : base + c; }
-            } else if (threadIdx.x == 64u) {                         // and its stretch of the list: the first wave's 64 lanes are taken, so the
-                int32_t t = 0;                                       // second wave issues this one beside them
-#pragma unroll
-                for (int w = 0; w < TPB / 64; w++) t += s_listed[w];
-                int32_t base = t ? atomicAdd(out_count, t) : 0;
-#pragma unroll
-                for (int w = 0; w < TPB / 64; w++) { const int32_t c = s_listed[w]; s_listed[w] = base; base += c; }
-            }
-            __syncthreads();
-            if (live && need) { pos = s_listed[wave] + (int32_t)__popcll(listed & ((1ull << lane) - 1ull)); out_list[pos] = b; }
-            if (pos >= 0) { P.words[2 * (int64_t)pos] = heavy ? PAIR_WORD_HEAVY : ~0ull; P.words[2 * (int64_t)pos + 1] = ~0ull; }
-            append_to_list(target->redo, P.ctr + PAIR_CTR_REDO, heavy, b);
-            const int32_t at = s_at[wave][lane];                     // lane s: where the wave's survivors of shape s go
-            for (unsigned long long rest = any; rest; rest &= rest - 1ull) {
-                const int shape = __builtin_amdgcn_readfirstlane((int)__builtin_ctzll(rest));
-                const bool in = (mine >> shape) & 1ull;
-                const unsigned long long m = __ballot(in);
-                const int32_t base = __builtin_amdgcn_readlane(at, shape);
-                if (in && base >= 0) P.buckets[(int64_t)shape * P.cap + base + (int32_t)__popcll(m & ((1ull << lane) - 1ull))] = pos;
-            }
-        }
-        if (out_compact && pos >= 0) {                              // the listed block's texels, in list order (load_block_compact)
-            uint4* c = out_compact + (int64_t)pos * 4;
-#pragma unroll
-            for (int y = 0; y < 4; y++) c[y] = make_uint4(ln.tx.w[y * 4 + 0], ln.tx.w[y * 4 + 1], ln.tx.w[y * 4 + 2], ln.tx.w[y * 4 + 3]);
-        }
-        if (with7) append_to_list(out_list7, out_count7, live && need7, b);
+        // PHASE 10 stops here: bc7_bound_list, the next launch on the band's stream, reads `inc` back and runs the tail at its own occupancy
+        if (PHASE != 10) bounded_list_tail<PHASE == 3>(ln.tx, inc, ln.opaque_err, live, b, s_at, s_listed, out_list, out_count, out_list7, out_count7, out_compact);
     }
     bool store = live;
     if (PHASE == 2 || PHASE == 5) store = store && ln.best_err <= e_alpha;   // else the alpha group's block stands (ties go to the earlier, RGB, group)
@@ -1831,6 +1854,40 @@ bc7_finish_all(const uint8_t* __restrict__ src, int64_t stride, int32_t blocks_x
         if (VEC16) *reinterpret_cast<uint4*>(d) = make_uint4(ln.best[0], ln.best[1], ln.best[2], ln.best[3]);
         else { d[0] = ln.best[0]; d[1] = ln.best[1]; d[2] = ln.best[2]; d[3] = ln.best[3]; }
     }
+}
+
+// Round 11, the tail of the rotation-task order in a kernel of its own.  Behind bc7_finish_all<10> (which leaves inc in inc_err) the 64 bounds are a
+// dependent chain of integer multiplies, one reciprocal and six square roots per shape that uses no LDS and needs a third of a refinement kernel's
+// registers; inside PHASE 10 it ran at the two waves per SIMD the palette's LDS allows.  Here it has the claim's 1 KiB of LDS and the registers
+// of BOUND_LIST_WAVES waves: 76 VGPRs, nothing spilled, six waves per SIMD (the same code at 4; at 8 two VGPRs spill and nothing is gained:
+// profiles/r11_bc7_insts_valu.txt).  One chunk of the band per workgroup through the same ChunkSel, gate included; the same contract on
+// `out_count` as bounded_list_tail<true>.  4096^2 bench surface 3.996 -> 3.912 ms (profiles/r11_bc7_bound_kernel_ab.txt).
+#ifndef BOUND_LIST_WAVES
+#define BOUND_LIST_WAVES 6
+#endif
+template <bool VEC16>
+__global__ void __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(BOUND_LIST_WAVES, BOUND_LIST_WAVES)))
+bc7_bound_list(const uint8_t* __restrict__ src, int64_t stride, int32_t blocks_x, int32_t nblocks, const int32_t channels, const int32_t* __restrict__ inc_err,
+               int32_t* __restrict__ out_list, int32_t* __restrict__ out_count, const ChunkSel sel, uint4* __restrict__ out_compact)
+{
+    __shared__ int32_t s_at[TPB / 64][64];
+    __shared__ int32_t s_listed[TPB / 64];
+    if (sel.gate && *sel.gate != sel.want) return;                   // the pilot chose the other order (whole grid: no barrier is pending)
+    const int32_t chunk = sel_chunk(sel, (int32_t)blockIdx.x);
+    if (chunk * TPB >= nblocks) return;                              // whole workgroup, before any barrier (a band's grid is whole stripes)
+    const int32_t gid = chunk * TPB + threadIdx.x;
+    const bool live = gid < nblocks;                                 // idle lanes of a ragged last workgroup go on: the tail's claim holds barriers
+    const int32_t b = live ? gid : nblocks - 1;
+    Tex tx;
+    load_block<VEC16>(tx, src, stride, blocks_x, b);
+    int32_t opaque_err = 0;                                          // kernel.ispc:1267-1277
+    if (channels == 4) {
+        uint32_t e = 0;
+#pragma unroll
+        for (int d = 0; d < 4; d++) { const uint32_t x = ~tx.pl[3][d]; e = udot4(x, x, e); }
+        opaque_err = (int32_t)e;
+    }
+    bounded_list_tail<true>(tx, inc_err[b], opaque_err, live, b, s_at, s_listed, out_list, out_count, nullptr, nullptr, out_compact);
 }
 
 // The PILOT of the bounded order (round 5).  Runs behind band 0's {0,2} scan on every eighth chunk of that band (1/16 of the surface, spread
@@ -1988,7 +2045,8 @@ bc7_pair_scan(const uint8_t* __restrict__ src, int64_t stride, int32_t blocks_x,
 //                       supply the winner with mode 5 (mode 4's minimum over all rotations is lower still), and one whose mode 5 does
 //                       cannot supply it with mode 4.  The emitted block goes to payload slot (rotation, list position), and a 64-bit
 //                       atomicMin of the merged word (RotRegion) settles the rest: lowest error, then mode 4, then the lower rotation;
-//   bc7_finish_all<10>  admits the word's candidate with a strict `<`, runs mode 6 in its place, then finish<3>'s tail unchanged.
+//   bc7_finish_all<10>  admits the word's candidate with a strict `<`, runs mode 6 in its place, leaves the incumbent of modes 1/3 in inc_err;
+//   bc7_bound_list      (round 11) finish<3>'s tail from that incumbent, unchanged: one device function (bounded_list_tail) for both.
 // A rotation the bound excludes cannot get below e02, so it can neither win nor, by a tie, displace a winner: same bytes.
 // ITW_BC7_ROT_TASKS=0 (read at every call): finish<3> as before.
 // Two waves per SIMD: 246 VGPRs, nothing spilled.  At three (168 VGPRs) 38 registers spill and the call is 1.2 % slower (4.29 against 4.24 ms on
@@ -2337,7 +2395,7 @@ void bc7_route_counters_reset()
 {
     for (int i = 0; i < ITW_ROUTE_COUNTERS; i++) g_route_seen[i].store(0, std::memory_order_relaxed);
 }
-// test hook (itwTestBc7CallCounters): what the last two-band call of the RGB bounded order counted on the device (launch_rgb_bounded snapshots it
+// test hook (itwTestBc7CallCounters): what the last call of the RGB bounded order counted on the device (launch_rgb_bounded snapshots it
 // while armed; it synchronises)
 static std::atomic<int> g_counters_armed{0};
 static std::atomic<int32_t> g_call_counters[ITW_BC7_CALL_COUNTERS];
@@ -2737,18 +2795,31 @@ struct FinishIO {
     FinishIO& out7(int32_t* l, int32_t* c) { out_list7 = l; out_count7 = c; return *this; }
     FinishIO& rotations(const RotRegion& r) { rot = r; return *this; }
 };
+// bounded_list_tail<true> reads its PairTarget at a fixed distance from the list length: only a band's own counter block will do
+static bool band_list_length(const Fused& C, const int32_t* count)
+{
+    const int32_t* band0 = C.ctr + CTR_WORDS + PAIR_CTR_LIST;
+    return count == band0 || count == band0 + PAIR_CTR_WORDS;
+}
 // a finish phase: list phases launch one workgroup per possible list chunk (they return at once behind the list's end)
 template <int PH>
 static void finish(const Fused& C, const Span& sp, const FinishIO& io = FinishIO())
 {
     const Bc7Launch& L = C.L;
-    // bc7_finish_all<3> reads its PairTarget at a fixed distance from the list length: only a band's own counter block will do
-    const int32_t* band0 = C.ctr + CTR_WORDS + PAIR_CTR_LIST;
-    if ((PH == 3 || PH == 10) && io.out_count != band0 && io.out_count != band0 + PAIR_CTR_WORDS)
-        fail_msg("bc7_finish_all<3>: the list length must be word %d of a band's counter block", PAIR_CTR_LIST);
+    if (PH == 3 && !band_list_length(C, io.out_count)) fail_msg("bc7_finish_all<3>: the list length must be word %d of a band's counter block", PAIR_CTR_LIST);
     with_bool(L.vec, [&](auto V) {
         hipLaunchKernelGGL((bc7_finish_all<decltype(V)::value, PH>), dim3((unsigned)sp.cnt), dim3(TPB), 0, sp.s, L.src, L.stride, L.bx, sp.rows, L.dst, sp.wins, L.S, C.alpha_err,
                            io.in_list, io.in_count, io.out_list, io.out_count, io.out_list7, io.out_count7, sp.sel, io.in_compact, io.out_compact, io.rot);
+    });
+}
+// the tail behind finish<10>: the blocks of the span's chunks whose modes 1/3 a bound cannot exclude, from the incumbents finish<10> left
+static void bound_list(const Fused& C, const Span& sp, const FinishIO& io)
+{
+    const Bc7Launch& L = C.L;
+    if (!band_list_length(C, io.out_count)) fail_msg("bc7_bound_list: the list length must be word %d of a band's counter block", PAIR_CTR_LIST);
+    with_bool(L.vec, [&](auto V) {
+        hipLaunchKernelGGL((bc7_bound_list<decltype(V)::value>), dim3((unsigned)sp.cnt), dim3(TPB), 0, sp.s, L.src, L.stride, L.bx, sp.rows, (int32_t)L.S.channels,
+                           (const int32_t*)C.alpha_err, io.out_list, io.out_count, sp.sel, io.out_compact);
     });
 }
 
@@ -2865,7 +2936,8 @@ static void rgb_tail(const Fused& C, const RgbRoute& R, const Band& B)
         // modes 4/5 only for the (block, rotation) pairs a bound leaves (header above bc7_rot_tasks); empty lists where the pilot chose the other order
         finish<9>(C, gated(1), FinishIO().rotations(B.R));
         with_bool(L.vec, [&](auto V) { hipLaunchKernelGGL((bc7_rot_tasks<decltype(V)::value>), dim3((unsigned)B.cnt), dim3(TPB), 0, B.s, L.src, L.stride, L.bx, L.S, C.alpha_err, B.R); });
-        finish<10>(C, gated(1), FinishIO().out(B.list, B.count, B.compact).rotations(B.R));
+        finish<10>(C, gated(1), FinishIO().rotations(B.R));
+        bound_list(C, gated(1), FinishIO().out(B.list, B.count, B.compact));
     } else
         finish<3>(C, gated(1), FinishIO().out(B.list, B.count, B.compact));
     if (R.pairs) {
@@ -2905,6 +2977,29 @@ static void rgb_print_counters(const Fused& C, const RgbRoute& R, const Band& A,
                      c[PAIR_CTR_OVERFLOW], c[PAIR_CTR_REDO]);
     }
 }
+// itwTestBc7CallCounters: the words ITW_BC7_PILOT_DEBUG prints, for a test to assert on (a call without bands: band 1's stay zero)
+static void rgb_snapshot_counters(const Fused& C)
+{
+#ifdef ITW_TEST_HOOKS
+    if (g_counters_armed.load(std::memory_order_relaxed)) {          // itwTestBc7CallCounters: the same words, for a test to assert on
+        int32_t h[CTR_WORDS + 2 * PAIR_CTR_WORDS], out[ITW_BC7_CALL_COUNTERS] = {};
+        ITW_CHECK(hipStreamSynchronize(C.L.st));
+        ITW_CHECK(hipMemcpy(h, C.ctr, sizeof h, hipMemcpyDeviceToHost));
+        out[ITW_BC7_CC_PILOT_LISTED] = h[CTR_PILOT + PILOT_LISTED]; out[ITW_BC7_CC_PILOT_SAMPLED] = h[CTR_PILOT + PILOT_SAMPLED]; out[ITW_BC7_CC_PILOT_FLAG] = h[CTR_PILOT_FLAG];
+        for (int k = 0; k < 2; k++) {
+            const int32_t* band = h + CTR_WORDS + k * PAIR_CTR_WORDS;
+            for (int r = 0; r < 3; r++) out[ITW_BC7_CC_ROT_LISTS + 3 * k + r] = h[(k ? CTR_BAND1 : CTR_ROT) + r];
+            out[ITW_BC7_CC_LISTED + k] = band[PAIR_CTR_LIST];
+            for (int s = 0; s < 64; s++) out[ITW_BC7_CC_PAIRS + k] += band[s];
+            out[ITW_BC7_CC_OVERFLOW + k] = band[PAIR_CTR_OVERFLOW];
+            out[ITW_BC7_CC_REDO + k] = band[PAIR_CTR_REDO];
+        }
+        for (int i = 0; i < ITW_BC7_CALL_COUNTERS; i++) g_call_counters[i].store(out[i], std::memory_order_relaxed);
+    }
+#else
+    (void)C;
+#endif
+}
 static void launch_rgb_bounded(const Fused& C)
 {
     const Bc7Aux* aux = C.aux;
@@ -2934,6 +3029,7 @@ static void launch_rgb_bounded(const Fused& C)
             aux->verdict->valid = true;
         }
         if (!probe) rgb_tail(C, R, B);
+        rgb_snapshot_counters(C);
         return;
     }
     hipStream_t s2 = aux->stream;
@@ -2952,23 +3048,7 @@ static void launch_rgb_bounded(const Fused& C)
     ITW_CHECK(hipEventRecord(aux->join, s2));
     ITW_CHECK(hipStreamWaitEvent(st, aux->join, 0));
     if (env_once(ENV_PILOT_DEBUG)) rgb_print_counters(C, R, A, B);
-#ifdef ITW_TEST_HOOKS
-    if (g_counters_armed.load(std::memory_order_relaxed)) {          // itwTestBc7CallCounters: the same words, for a test to assert on
-        int32_t h[CTR_WORDS + 2 * PAIR_CTR_WORDS], out[ITW_BC7_CALL_COUNTERS] = {};
-        ITW_CHECK(hipStreamSynchronize(st));
-        ITW_CHECK(hipMemcpy(h, C.ctr, sizeof h, hipMemcpyDeviceToHost));
-        out[ITW_BC7_CC_PILOT_LISTED] = h[CTR_PILOT + PILOT_LISTED]; out[ITW_BC7_CC_PILOT_SAMPLED] = h[CTR_PILOT + PILOT_SAMPLED]; out[ITW_BC7_CC_PILOT_FLAG] = h[CTR_PILOT_FLAG];
-        for (int k = 0; k < 2; k++) {
-            const int32_t* band = h + CTR_WORDS + k * PAIR_CTR_WORDS;
-            for (int r = 0; r < 3; r++) out[ITW_BC7_CC_ROT_LISTS + 3 * k + r] = h[(k ? CTR_BAND1 : CTR_ROT) + r];
-            out[ITW_BC7_CC_LISTED + k] = band[PAIR_CTR_LIST];
-            for (int s = 0; s < 64; s++) out[ITW_BC7_CC_PAIRS + k] += band[s];
-            out[ITW_BC7_CC_OVERFLOW + k] = band[PAIR_CTR_OVERFLOW];
-            out[ITW_BC7_CC_REDO + k] = band[PAIR_CTR_REDO];
-        }
-        for (int i = 0; i < ITW_BC7_CALL_COUNTERS; i++) g_call_counters[i].store(out[i], std::memory_order_relaxed);
-    }
-#endif
+    rgb_snapshot_counters(C);
 }
 
 // The reference's order in two launches: {0,2} and {1,3} scanned together, {7}, then every mode's refinement and {4,5}, {6}.
