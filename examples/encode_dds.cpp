@@ -3,7 +3,7 @@
 // the program links libispc_texcomp.so like the plugin links ispc_texcomp.lib.
 //
 //   encode_dds [--measure] [--refine <profile> <max_block_sse> | --refine-share <profile> <percent> | --refine-psnr <profile> <dB>]
-//              [--normal flipx,flipy,normalize] [--cube-cross] [--mips [levels]]
+//              [--normal flipx,flipy,normalize | --signed-normal int8|half|float[,flipx,flipy,normalize]] [--cube-cross] [--mips [levels]]
 //              <format> <width> <height> <in.raw> <out.dds> [slice_pixels]
 //     format : bc1 | bc3 | bc4 | bc5 | bc4_snorm | bc5_snorm | bc7_<profile> | bc6h_<profile> | etc1_slow      (profiles: the GetProfile_* names)
 //              etc1_slow: DDS has no code for ETC1, so the output is a KTX 1.1 file (itwKtx*, itw_dds.h); the slices go through itwCompressImageSlicedEx
@@ -20,6 +20,12 @@
 //     --normal flipx,flipy,normalize : the input is a normal map; the named stages of the plugin's save path (FlipXYChannelNormalMap,
 //                 NormalizeNormalMapChain) are applied as the texels are encoded -- bc5 through itwCompressNormalMapBC5 (one kernel), any
 //                 other format through itwCompressNormalMapChain.  The slice loop is not used; not with --refine*.
+//     --signed-normal int8|half|float[,flipx,flipy,normalize] : bc4_snorm / bc5_snorm only: the raw file is a SIGNED normal source of the
+//                 named texel kind (RGBA8_SNORM codes, RGBA16F halfs or RGBA32F floats; itw_dispatch.h, "signed normal sources") and the
+//                 stages have their signed meaning: negate x / y, normalise in fp32, quantise with round to nearest even.  bc5_snorm goes
+//                 through itwCompressNormalMapBC5S (one kernel), bc4_snorm through itwCompressSignedNormalMapChain with one image; with
+//                 --cube-cross the six faces through that chain call, with --mips everything through itwCompressSignedNormalMapMipped.
+//                 Not with --normal (whose biased 8-bit behaviour stays), --refine* or --measure; the slice loop is not used.
 //     --cube-cross : the input is a horizontal (4 x 3 faces) or vertical (3 x 4) cube cross; its six faces (itwCubeCrossFaces: views, no
 //                 copy) are encoded by one chain call into a cube-map DDS.  Goes with --normal; not with --refine*, --measure or etc1_slow.
 //     --mips [levels] : a mipped file from the base image (or the six cross faces) in one call, itwCompressImageMipped: the save path's
@@ -210,6 +216,45 @@ int encode_mipped(const Format& f, const rgba_surface& source, uint32_t ops, boo
     return 0;
 }
 
+// encode_dds --signed-normal: a signed normal source of `tb`-byte texels (or its six cross faces) to BC4_SNORM / BC5_SNORM, mipped or not
+int encode_signed_normal(const Format& f, const rgba_surface& source, int tb, uint32_t ops, bool cube_cross, bool mips, int levels, const char* out_path)
+{
+    rgba_surface bases[6] = {source};
+    int items = 1;
+    if (cube_cross) {
+        if (itwCubeCrossFaces(&source, tb, bases) != 0) { std::fprintf(stderr, "%d x %d is too small for a cube cross\n", source.width, source.height); return 2; }
+        items = 6;
+    }
+    const int w = bases[0].width, h = bases[0].height, full = itwMipLevels(w, h);
+    if (!mips) levels = 1;
+    else if (levels < 0 || levels > full) { std::fprintf(stderr, "--mips %d: a full chain of %d x %d has %d levels\n", levels, w, h, full); return 2; }
+    else if (levels == 0) levels = full;
+    ItwDdsDesc desc = { (uint32_t)w, (uint32_t)h, (uint32_t)levels, (uint32_t)f.dxgi, cube_cross ? 1u : 0u, 1 };
+    std::vector<const uint8_t*> images((size_t)items * levels);      // face-major, then level: the calls' order
+    size_t bytes = 0;
+    for (size_t i = 0; i < images.size(); i++) bytes += itwDdsImage(&desc, (uint32_t)i, nullptr, nullptr, nullptr);
+    std::vector<uint8_t> blocks(bytes);
+    itwSetErrorMode(ITW_ON_ERROR_RETURN);
+    bool ok;
+    if (mips) ok = itwCompressSignedNormalMapMipped(bases, items, levels, tb, ops, blocks.data(), f.dxgi, nullptr, nullptr);
+    else if (f.dxgi == ITW_DXGI_FORMAT_BC5_SNORM && !cube_cross) {
+        itwCompressNormalMapBC5S(&source, tb, blocks.data(), ops);   // the stages run inside the encoder
+        ok = itwLastError() == nullptr;
+    } else ok = itwCompressSignedNormalMapChain(bases, items, tb, blocks.data(), f.dxgi, ops, nullptr, nullptr);
+    if (!ok) { std::fprintf(stderr, "%s\n", itwLastError() ? itwLastError() : "compression failed"); return 1; }
+    size_t at = 0;
+    for (size_t i = 0; i < images.size(); i++) { images[i] = blocks.data() + at; at += itwDdsImage(&desc, (uint32_t)i, nullptr, nullptr, nullptr); }
+    std::vector<uint8_t> file(itwDdsFileBytes(&desc));
+    if (file.empty() || itwDdsWriteFile(&desc, images.data(), images.size(), file.data(), file.size()) != file.size()) { std::fprintf(stderr, "DDS assembly failed\n"); return 1; }
+    FILE* out = std::fopen(out_path, "wb");
+    if (!out || std::fwrite(file.data(), 1, file.size(), out) != file.size()) { std::fprintf(stderr, "cannot write %s\n", out_path); return 1; }
+    std::fclose(out);
+    DestroyThreads();
+    std::fprintf(stderr, "%s: %dx%d%s, %d levels -> %zu bytes (%s, signed source of %d-byte texels, ops %u)\n", out_path, w, h, cube_cross ? " x 6 faces" : "", levels,
+                 file.size(), f.name, tb, ops);
+    return 0;
+}
+
 // encode_dds --decode: the whole file through one call
 int decode_file(const char* in_path, const char* out_path)
 {
@@ -325,6 +370,7 @@ int main(int argc, char** argv)
     uint32_t normal_ops = 0;                                    // ITW_NORMAL_*
     bool mips = false;
     int mip_levels = 0;                                         // 0: the full chain
+    int signed_tb = 0;                                          // --signed-normal: texel bytes of the signed source (4, 8 or 16)
     for (int i = 1; i < argc; i++)
         if (std::strcmp(argv[i], "--measure") == 0) {
             measure = true;
@@ -353,6 +399,20 @@ int main(int argc, char** argv)
             }
             for (int k = i; k + 2 < argc; k++) argv[k] = argv[k + 2];
             argc -= 2; i--;
+        } else if (std::strcmp(argv[i], "--signed-normal") == 0 && i + 1 < argc) {
+            for (const char* p = argv[i + 1]; *p;) {
+                const size_t n = std::strcspn(p, ",");
+                if (p == argv[i + 1] && n == 4 && std::strncmp(p, "int8", 4) == 0) signed_tb = 4;
+                else if (p == argv[i + 1] && n == 4 && std::strncmp(p, "half", 4) == 0) signed_tb = 8;
+                else if (p == argv[i + 1] && n == 5 && std::strncmp(p, "float", 5) == 0) signed_tb = 16;
+                else if (signed_tb && n == 5 && std::strncmp(p, "flipx", 5) == 0) normal_ops |= ITW_NORMAL_FLIP_X;
+                else if (signed_tb && n == 5 && std::strncmp(p, "flipy", 5) == 0) normal_ops |= ITW_NORMAL_FLIP_Y;
+                else if (signed_tb && n == 9 && std::strncmp(p, "normalize", 9) == 0) normal_ops |= ITW_NORMAL_NORMALIZE;
+                else { std::fprintf(stderr, "--signed-normal takes int8, half or float, then a list of flipx, flipy, normalize\n"); return 2; }
+                p += n + (p[n] == ',' ? 1 : 0);
+            }
+            for (int k = i; k + 2 < argc; k++) argv[k] = argv[k + 2];
+            argc -= 2; i--;
         } else if (std::strcmp(argv[i], "--cube-cross") == 0) {
             cube_cross = true;
             for (int k = i; k + 1 < argc; k++) argv[k] = argv[k + 1];
@@ -367,7 +427,7 @@ int main(int argc, char** argv)
         }
     if (argc < 6) {
         std::fprintf(stderr, "usage: %s [--measure] [--refine <profile> <max_block_sse> | --refine-share <profile> <percent> | --refine-psnr <profile> <dB>]\n"
-                             "          [--normal flipx,flipy,normalize] [--cube-cross] [--mips [levels]]\n"
+                             "          [--normal flipx,flipy,normalize | --signed-normal int8|half|float[,flipx,flipy,normalize]] [--cube-cross] [--mips [levels]]\n"
                              "          <format> <width> <height> <in.raw> <out.dds> [slice_pixels]\n"
                              "       %s --decode <in.dds | in.ktx> <out.raw>\n"
                              "       %s --preview <in.dds | in.ktx> <image index> <out.ppm> <w> <h> <x> <y> <zoom> [channels] [exposure] [matte]\n", argv[0], argv[0], argv[0]);
@@ -379,12 +439,18 @@ int main(int argc, char** argv)
     if (!f || width < 1 || height < 1) { std::fprintf(stderr, "unknown format or bad size\n"); return 2; }
     const long long slice_pixels = argc > 6 ? std::atoll(argv[6]) : 0;
 
-    std::vector<uint8_t> texels((size_t)width * height * f->texel_bytes);
+    if (signed_tb && (normal_given || refine_profile || measure || (f->dxgi != ITW_DXGI_FORMAT_BC4_SNORM && f->dxgi != ITW_DXGI_FORMAT_BC5_SNORM))) {
+        std::fprintf(stderr, "--signed-normal is for bc4_snorm / bc5_snorm and does not go with --normal, --refine* or --measure\n");
+        return 2;
+    }
+    const int texel_bytes = signed_tb ? signed_tb : f->texel_bytes;
+    std::vector<uint8_t> texels((size_t)width * height * texel_bytes);
     FILE* in = std::fopen(argv[4], "rb");
     if (!in || std::fread(texels.data(), 1, texels.size(), in) != texels.size()) { std::fprintf(stderr, "cannot read %s\n", argv[4]); return 1; }
     std::fclose(in);
 
-    rgba_surface source = { texels.data(), width, height, width * f->texel_bytes };
+    rgba_surface source = { texels.data(), width, height, width * texel_bytes };
+    if (signed_tb) return encode_signed_normal(*f, source, signed_tb, normal_ops, cube_cross, mips, mip_levels, argv[5]);
     if (mips) {
         if (refine_profile || measure || (cube_cross && f->dxgi == ITW_FORMAT_ETC1_RGB8)) {
             std::fprintf(stderr, "--mips does not go with --refine* or --measure; --cube-cross not with etc1_slow\n");

@@ -60,6 +60,15 @@ void itwWarmupBC45S(void);
  * (itwWarmupBC45() builds both). */
 void itwCompressNormalMapBC5(const rgba_surface* src, uint8_t* dst, uint32_t ops);
 
+/* A signed normal source to BC5_SNORM in one kernel.  `src` holds texels of `texel_bytes` 4 (RGBA8_SNORM), 8 (RGBA16F) or 16 (RGBA32F); the
+ * per-texel definition of itw_dispatch.h ("signed normal sources": load, the flips and the normalise of `ops` in fp32, quantise to int8 with
+ * round to nearest even) runs in the BC5S encoder's load.  The stream is byte for byte CompressBlocksBC5S of the RGBA8_SNORM image that
+ * itwQuantizeNormalMapChain makes of `src`; `src` is not modified; texel_bytes 4 with ops 0 is CompressBlocksBC5S.  CompressBlocksBC5S's
+ * contract otherwise: any size >= 1, partial blocks kept, host or device pointers, device calls asynchronous on the calling thread's stream
+ * and capturable once itwWarmupBC45S() has run.  Device texels are 4-byte aligned (pointer and stride).  A texel_bytes other than 4, 8 or
+ * 16 and unknown `ops` bits fail through the library's error mode before any device work. */
+void itwCompressNormalMapBC5S(const rgba_surface* src, int texel_bytes, uint8_t* dst, uint32_t ops);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

@@ -339,11 +339,55 @@ int itwPrepareNormalMapChain(const rgba_surface* images, int count, int pixel_si
 bool itwCompressNormalMapChain(const rgba_surface* images, int count, uint8_t* target, int dxgi_format,
                                const void* settings, uint32_t ops, ItwProgressFunc* progress, void* user);
 
+/* Signed normal sources: what a BC5_SNORM normal map is made from.  (The calls above speak the plugin's biased 8-bit convention only; they
+ * keep it.)  A signed normal source is an image of 4-component texels of one of three kinds, named by the texel's size, `texel_bytes`:
+ *   4   RGBA8_SNORM  int8 codes, each loaded as max((float)v * (1.0f / 127.0f), -1.0f): itw_bc45.h's rule
+ *   8   RGBA16F      halfs, widened exactly
+ *   16  RGBA32F      floats, as they are
+ * The working value is the float vector (x, y, z, a).  `ops` takes ITW_NORMAL_FLIP_X / _FLIP_Y / _NORMALIZE with their SIGNED meaning, the
+ * flips first, then the normalise; IEEE fp32, every operation rounded on its own, no contraction:
+ *   flip       x = -x and / or y = -y (exact)
+ *   normalise  m = sqrtf((x*x + y*y) + z*z); m > 0: s = 1.0f / m and x, y, z become x*s, y*s, z*s; otherwise (a NaN length included)
+ *              (0, 0, 1).  Alpha is never touched.  The RGBA16F normalise above without its rounding to half.
+ *   quantise   per component: NaN -> 0; otherwise c = min(max(v, -1.0f), 1.0f), p = c * 127.0f, code = (int8_t)rintf(p), round to nearest
+ *              even.  DirectXMath is not in the reference tree: this line is the definition, as for the load rule.  -128 never comes out;
+ *              with ops == 0 every int8 code maps to itself (-128 to -127), directly and through a half.
+ *
+ * itwQuantizeNormalMapChain: out of place, `count` sources of any size >= 1 and any stride >= the row's bytes into RGBA8_SNORM targets of
+ * the same sizes, all four components quantised.  targets[i] may be sources[i] itself when texel_bytes == 4.  All pointers host or all
+ * device.  Device pointers: one launch over the whole chain, asynchronous on the calling thread's stream.  Host pointers: staged through the
+ * thread's buffer; returns synchronised.  Nothing outside width x height of a target is written.  Returns 0, also for count == 0; -1,
+ * through the error mode and before any device work, for a null pointer, count < 0, a texel_bytes other than 4, 8 or 16, unknown ops bits,
+ * a width or height < 1, a target whose size differs from its source's, a stride below the row's bytes, source texels that are not
+ * texel_bytes aligned or target texels that are not 4-byte aligned, or mixed host and device pointers.  The fused encoder of such a source
+ * is itwCompressNormalMapBC5S (itw_bc45.h). */
+int itwQuantizeNormalMapChain(const rgba_surface* sources, int texel_bytes, const rgba_surface* targets, int count, uint32_t ops);
+
+/* itwCompressImageChainEx for DXGI formats 81 (BC4_SNORM) and 84 (BC5_SNORM) over signed normal sources of `texel_bytes` 4, 8 or 16: the
+ * chain's gather applies the definition above to every texel it copies, so the stream is byte for byte itwCompressImageChainEx over images
+ * quantised by itwQuantizeNormalMapChain, and no image is encoded in place.  The chain call's images (rows at least width * texel_bytes
+ * bytes apart), pointer kinds, progress contract, errors and return value; the sources are never written.  Any other format, a texel_bytes
+ * other than 4, 8 or 16, and unknown ops bits fail through the error mode before any device work. */
+bool itwCompressSignedNormalMapChain(const rgba_surface* images, int count, int texel_bytes, uint8_t* target, int dxgi_format, uint32_t ops,
+                                     ItwProgressFunc* progress, void* user);
+
+/* The signed normal-map save path from base images in one call (declared here, described with the mip chains below: it takes
+ * itwCompressImageMipped's argument rules and launch limits).  A composition of the stages:
+ *   1. the `items` bases, signed normal sources of `texel_bytes`, are widened into level 0 of a device-side RGBA16F chain: int8 becomes
+ *      half(load rule), half is copied, float takes the mip filter's RGBA16F store rule (clamp to +-65504, round to nearest even, NaN ->
+ *      0x7E00).  The flips of `ops` are folded into this widening: a negation is exact and commutes with both filters;
+ *   2. itwGenerateMipChain over that chain, as it stands (RGBA16F is the texel format whose filters are pinned to the reference);
+ *   3. itwCompressSignedNormalMapChain with texel_bytes 8 and only the NORMALIZE bit of `ops`: the normalise runs in fp32 on every level
+ *      inside the gather, with no pass of its own and no rounding to half between the normalise and the quantisation.
+ * dxgi_format 81 or 84; levels == 0: the full chain; the bases are not written.  Returns as itwCompressImageMipped does. */
+bool itwCompressSignedNormalMapMipped(const rgba_surface* bases, int items, int levels, int texel_bytes, uint32_t ops, uint8_t* target,
+                                      int dxgi_format, ItwProgressFunc* progress, void* user);
+
 /* ConvertToCubeMapFromCross (IntelPlugin.cpp:1200-1265) as six VIEWS into `cross`, in the order +X -X +Y -Y +Z -Z: the faces of a horizontal
  * cross are width/4 x height/3 (truncating quotients) at cells (column, row) {2,1} {0,1} {1,0} {1,2} {1,1} {3,1}; when width < height the
  * cross is vertical, the faces are width/3 x height/4 and the last cell is {1,3}.  No rotation and no copy, as the reference's CopyRectangle
  * calls; the views share `cross`'s stride and feed itwCompressImageChainEx / itwCompressNormalMapChain directly (itw_decode.h documents the
- * inverse).  pixel_size 4 or 8.  Host arithmetic only.  Returns 0; -1 for a null pointer, a pixel_size other than 4 or 8, or a cross smaller
+ * inverse).  pixel_size 4, 8 or 16 (RGBA32F: a signed normal source).  Host arithmetic only.  Returns 0; -1 for a null pointer, a pixel_size other than 4, 8 or 16, or a cross smaller
  * than 4 x 3 (3 x 4 when vertical). */
 int itwCubeCrossFaces(const rgba_surface* cross, int pixel_size, rgba_surface faces[6]);
 

@@ -831,9 +831,10 @@ struct ChainUnit { int i0, i1; int64_t b0, nb; bool in_place; };   // images [i0
 // The gather groups units[u0, u1) of a chain whose pointer kinds are known, pipelined; `poll(i0, i1)` reports images [i0, i1) as written.
 template <class Poll>
 bool chain_groups(const Job& j, const rgba_surface* im, uint8_t* target, const std::vector<ChainUnit>& units, size_t u0, size_t u1,
-                  bool src_dev, bool dst_dev, Poll&& poll, uint32_t normal_ops = 0)
+                  bool src_dev, bool dst_dev, Poll&& poll, uint32_t normal_ops = 0, int signed_source = 0)
 {
     const int px = itw::texel_bytes(j.kind), bpb = itw::block_bytes(j.kind);
+    const int spx = signed_source ? signed_source : px;      // bytes per SOURCE texel (a signed normal source: 4, 8 or 16 into packed RGBA8_SNORM)
     const bool fill45 = itw::keeps_partial_blocks(j.kind);
     const int ngroups = (int)(u1 - u0);
     auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
@@ -847,7 +848,7 @@ bool chain_groups(const Job& j, const rgba_surface* im, uint8_t* target, const s
         stage_off.resize((size_t)(units[u1 - 1].i1 - units[u0].i0));
         for (int i = units[u0].i0; i < units[u1 - 1].i1; i++) {
             stage_off[(size_t)(i - units[u0].i0)] = in_bytes;
-            in_bytes += up((((size_t)im[i].width * px + 15) & ~(size_t)15) * (size_t)im[i].height);
+            in_bytes += up((((size_t)im[i].width * spx + 15) & ~(size_t)15) * (size_t)im[i].height);
         }
     }
     int tallest = 0, widest = 0;
@@ -883,7 +884,7 @@ bool chain_groups(const Job& j, const rgba_surface* im, uint8_t* target, const s
         for (int i = G.i0; i < G.i1; i++) {
             itw::ChainImage& d = desc[(size_t)(i - units[u0].i0)];
             d.ptr = src_dev ? im[i].ptr : d_in + stage_off[(size_t)(i - units[u0].i0)];
-            d.stride = src_dev ? (int64_t)im[i].stride : (int64_t)(((size_t)im[i].width * px + 15) & ~(size_t)15);
+            d.stride = src_dev ? (int64_t)im[i].stride : (int64_t)(((size_t)im[i].width * spx + 15) & ~(size_t)15);
             d.width = im[i].width; d.height = im[i].height;
             d.first_block = first;
             first += itw::image_blocks(im[i]);
@@ -898,7 +899,7 @@ bool chain_groups(const Job& j, const rgba_surface* im, uint8_t* target, const s
         hipStream_t ks = pipe.stream(g);
         if (!src_dev) {
             for (int i = G.i0; i < G.i1; i++) {
-                const size_t row_bytes = (size_t)im[i].width * px;
+                const size_t row_bytes = (size_t)im[i].width * spx;
                 upload_rows(d_in + stage_off[(size_t)(i - units[u0].i0)], (row_bytes + 15) & ~(size_t)15, im[i].ptr, im[i].stride, row_bytes,
                             (size_t)im[i].height, pipe.cs);
             }
@@ -906,7 +907,7 @@ bool chain_groups(const Job& j, const rgba_surface* im, uint8_t* target, const s
         }
         const int64_t pitch = (int64_t)G.pbx * 4 * px;
         uint8_t* packed = d_in + G.packed_off;
-        itw::launch_chain_gather(d_desc + (G.i0 - units[u0].i0), G.i1 - G.i0, G.nb, G.pbx, G.pby, px, fill45, packed, pitch, ks, nullptr, normal_ops);
+        itw::launch_chain_gather(d_desc + (G.i0 - units[u0].i0), G.i1 - G.i0, G.nb, G.pbx, G.pby, px, fill45, packed, pitch, ks, nullptr, normal_ops, signed_source);
         launch(j, packed, pitch, G.pbx * 4, G.pby * 4, d_out + G.out_off, ks,
                lone ? LaunchShape{(!src_dev && !dst_dev) ? LaunchShape::STAGED : LaunchShape::WHOLE} : LaunchShape{LaunchShape::BAND, pipe.workspace(g)});
         if (dst_dev) ITW_CHECK(hipMemcpyAsync(target + G.b0 * bpb, d_out + G.out_off, (size_t)G.nb * bpb, hipMemcpyDeviceToDevice, ks));
@@ -922,7 +923,9 @@ bool chain_groups(const Job& j, const rgba_surface* im, uint8_t* target, const s
 
 // `images` / `count` / `target` checked by chain_job.  Returns true when every image was encoded, false when `progress` stopped the job.
 // `normal_ops` (itwCompressNormalMapChain): the gather prepares every texel it copies, so no image is encoded in place.
-bool compress_chain(const Job& j, const rgba_surface* im, int count, uint8_t* target, ItwProgressFunc* progress, void* user, uint32_t normal_ops = 0)
+// `signed_source` (itwCompressSignedNormalMapChain): the images are signed normal sources of that many bytes per texel, quantised by the gather.
+bool compress_chain(const Job& j, const rgba_surface* im, int count, uint8_t* target, ItwProgressFunc* progress, void* user, uint32_t normal_ops = 0,
+                    int signed_source = 0)
 {
     const bool src_dev = is_device_pointer(im[0].ptr);
     for (int i = 1; i < count; i++)
@@ -952,7 +955,7 @@ bool compress_chain(const Job& j, const rgba_surface* im, int count, uint8_t* ta
     for (int i = 0; i < count; i++) {
         const int64_t nb = itw::image_blocks(im[i]);
         if (nb >= budget) {
-            const bool aligned = (im[i].width & 3) == 0 && (im[i].height & 3) == 0 && normal_ops == 0;
+            const bool aligned = (im[i].width & 3) == 0 && (im[i].height & 3) == 0 && normal_ops == 0 && signed_source == 0;
             units.push_back(ChainUnit{i, i + 1, off, nb, aligned});            // in place, or (needs padding) a group of its own
             open = false;
         } else if (open && units.back().nb + nb <= budget) {
@@ -989,7 +992,7 @@ bool compress_chain(const Job& j, const rgba_surface* im, int count, uint8_t* ta
         }
         size_t v = u;
         while (v < units.size() && !units[v].in_place) v++;
-        if (!chain_groups(j, im, target, units, u, v, src_dev, dst_dev, poll, normal_ops) || stopped) return false;
+        if (!chain_groups(j, im, target, units, u, v, src_dev, dst_dev, poll, normal_ops, signed_source) || stopped) return false;
         u = v;
     }
     return true;
@@ -1434,6 +1437,42 @@ void CompressBlocksBC5S(const rgba_surface* src, uint8_t* dst)
     itw::guarded([&] { Job j; j.kind = itw::BCN_BC5S; compress(j, src, dst); });
 }
 
+// BC5_SNORM of a signed normal source, the definition applied in the encoder's load (include/itw_bc45.h).  A source of 8- or 16-byte texels
+// does not fit the staging of the RGBA8 routes, so a host pointer is staged here: through the thread's buffer, on the caller's stream.
+void itwCompressNormalMapBC5S(const rgba_surface* src, int texel_bytes, uint8_t* dst, uint32_t ops)
+{
+    if (texel_bytes == 4 && ops == 0) { CompressBlocksBC5S(src, dst); return; }
+    itw::clear_failure();
+    itw::guarded([&] {
+        if (texel_bytes != 4 && texel_bytes != 8 && texel_bytes != 16) itw::fail_msg("itwCompressNormalMapBC5S: texel_bytes %d (4, 8 or 16)", texel_bytes);
+        if (ops & ~7u) itw::fail_msg("itwCompressNormalMapBC5S: unknown ops bits 0x%x", ops);
+        if (!src) itw::fail_msg("null surface");
+        const int w = src->width, h = src->height;
+        if (w <= 0 || h <= 0) return;                     // nothing to encode
+        if (!src->ptr || !dst) itw::fail_msg("null texel or destination pointer");
+        const int64_t bx = (w + 3) / 4, by = (h + 3) / 4;
+        if (bx * by * 2 > (int64_t)INT32_MAX) itw::fail_msg("itwCompressNormalMapBC5S: %d x %d is more blocks than one launch covers", w, h);
+        const bool src_dev = is_device_pointer(src->ptr), dst_dev = is_device_pointer(dst);
+        if (src_dev && (((uintptr_t)src->ptr | (uintptr_t)(uint32_t)src->stride) & 3)) itw::fail_msg("itwCompressNormalMapBC5S: device texels not 4-byte aligned");
+        hipStream_t st = tls.user_stream;
+        if (src_dev && dst_dev) {                         // resident: one launch, asynchronous
+            itw::launch_bc5s_normal(src->ptr, texel_bytes, src->stride, w, h, dst, ops, st);
+            ITW_CHECK(hipGetLastError());
+            return;
+        }
+        const size_t row_bytes = (size_t)w * (size_t)texel_bytes, pitch = (row_bytes + 15) & ~(size_t)15, out_bytes = (size_t)(bx * by) * 16;
+        const size_t in_bytes = src_dev ? 0 : (pitch * (size_t)h + 255) & ~(size_t)255;
+        uint8_t* base = static_cast<uint8_t*>(itw::decode_scratch(in_bytes + (dst_dev ? 0 : out_bytes), st));
+        if (!src_dev) upload_rows(base, pitch, src->ptr, src->stride, row_bytes, (size_t)h, st);
+        uint8_t* d_dst = dst_dev ? dst : base + in_bytes;
+        itw::launch_bc5s_normal(src_dev ? src->ptr : base, texel_bytes, src_dev ? (int64_t)src->stride : (int64_t)pitch, w, h, d_dst, ops, st);
+        ITW_CHECK(hipGetLastError());
+        if (!dst_dev) ITW_CHECK(hipMemcpyAsync(dst, d_dst, out_bytes, hipMemcpyDeviceToHost, st));
+        ITW_CHECK(hipStreamSynchronize(st));
+        itw::decode_scratch_done(st);
+    });
+}
+
 bool itwCompressImageSlicedEx(const rgba_surface* source, uint8_t* target, int64_t block_row_pitch, int dxgi_format, const void* settings,
                               int64_t slice_pixels, ItwProgressFunc* progress, void* user)
 {
@@ -1471,6 +1510,26 @@ bool itwCompressNormalMapChain(const rgba_surface* images, int count, uint8_t* t
         if (ops & ~7u) itw::fail_msg("itwCompressNormalMapChain: unknown ops bits 0x%x", ops);
         const Job j = chain_job(images, count, target, dxgi_format, settings);
         done = compress_chain(j, images, count, target, progress, user, ops);
+    });
+    return ok && done;
+}
+
+// itwCompressImageChainEx for BC4_SNORM / BC5_SNORM over signed normal sources: the gather quantises every texel it copies (chain.hip)
+bool itwCompressSignedNormalMapChain(const rgba_surface* images, int count, int texel_bytes, uint8_t* target, int dxgi_format, uint32_t ops,
+                                     ItwProgressFunc* progress, void* user)
+{
+    bool done = false;
+    itw::clear_failure();
+    const bool ok = itw::guarded([&] {
+        if (dxgi_format != 81 && dxgi_format != 84)
+            itw::fail_msg("itwCompressSignedNormalMapChain: DXGI format %d (BC4_SNORM = 81 or BC5_SNORM = 84)", dxgi_format);
+        if (texel_bytes != 4 && texel_bytes != 8 && texel_bytes != 16) itw::fail_msg("itwCompressSignedNormalMapChain: texel_bytes %d (4, 8 or 16)", texel_bytes);
+        if (ops & ~7u) itw::fail_msg("itwCompressSignedNormalMapChain: unknown ops bits 0x%x", ops);
+        const Job j = chain_job(images, count, target, dxgi_format, nullptr);
+        for (int i = 0; i < count; i++)
+            if ((int64_t)images[i].stride < (int64_t)images[i].width * texel_bytes)
+                itw::fail_msg("itwCompressSignedNormalMapChain: image %d: stride %d < %lld bytes per row", i, images[i].stride, (long long)images[i].width * texel_bytes);
+        done = compress_chain(j, images, count, target, progress, user, ops, texel_bytes);
     });
     return ok && done;
 }

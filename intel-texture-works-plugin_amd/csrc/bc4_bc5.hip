@@ -42,6 +42,7 @@
 #include <vector>
 #include "kernels.hpp"
 #include "host_rt.hpp"
+#include "normal_prep.hpp"
 
 namespace itw {
 namespace {
@@ -500,6 +501,85 @@ __device__ __forceinline__ void normalised_codes(uint32_t (&P)[8], const uint32_
     }
 }
 
+// ---- signed normal sources in the BC5_SNORM load (itwCompressNormalMapBC5S; normal_prep.hpp is the definition) ---------------------------
+// A block of a TB-byte source is 16 * TB bytes (RGBA16F 128, RGBA32F 256), so the two lanes of a block do not each load all of it: lane
+// `half` (0: the R lane, 1: the G lane) loads texel rows 2 * half and 2 * half + 1 -- with halfs the sixteen words the RGBA8 kernels
+// prefetch -- runs the definition on its eight texels (eight square roots and divides, not sixteen), and hands the neighbour the four
+// packed dwords of the channel the neighbour encodes.  Of a float texel only x, y, z are kept (alpha is not BC5's business): 24 words.
+template <int TB> constexpr int kept_words() { return TB == 16 ? 3 : TB / 4; }
+
+// four consecutive texels of one row at p into wr[0 .. 4 * kept_words)
+template <int TB, bool VEC16>
+__device__ __forceinline__ void load_row45(uint32_t* wr, const uint8_t* p)
+{
+    if (TB == 16) {
+        const uint32_t* q = reinterpret_cast<const uint32_t*>(VEC16 ? __builtin_assume_aligned(p, 16) : p);
+#pragma unroll
+        for (int x = 0; x < 4; x++) { wr[3 * x] = q[4 * x]; wr[3 * x + 1] = q[4 * x + 1]; wr[3 * x + 2] = q[4 * x + 2]; }
+    } else if (VEC16) {
+#pragma unroll
+        for (int k = 0; k < TB / 4; k++) { const uint4 v = reinterpret_cast<const uint4*>(p)[k]; wr[4 * k] = v.x; wr[4 * k + 1] = v.y; wr[4 * k + 2] = v.z; wr[4 * k + 3] = v.w; }
+    } else {
+#pragma unroll
+        for (int k = 0; k < TB; k++) wr[k] = reinterpret_cast<const uint32_t*>(p)[k];
+    }
+}
+
+// The eight texels of rows 2 * half, 2 * half + 1 of block `b`, any block: partial ones by bc45_fill_index, texel by texel
+template <int TB, bool VEC16>
+__device__ __forceinline__ void load_rows45(uint32_t (&w)[8 * kept_words<TB>()], const uint8_t* __restrict__ src, int64_t stride, int32_t width, int32_t height,
+                                            int32_t blocks_x, int32_t b, int32_t half)
+{
+    constexpr int KW = kept_words<TB>();
+    const int32_t yy = b / blocks_x, xx = b - yy * blocks_x;
+    const int32_t pw = min(4, width - 4 * xx), ph = min(4, height - 4 * yy);
+    const uint8_t* p = src + (int64_t)yy * 4 * stride + (int64_t)xx * 4 * TB;
+    if (pw == 4 && ph == 4) {
+#pragma unroll
+        for (int r = 0; r < 2; r++) load_row45<TB, VEC16>(&w[4 * KW * r], p + (int64_t)(2 * half + r) * stride);
+    } else {
+#pragma unroll
+        for (int r = 0; r < 2; r++) {
+            const int sy = bc45_fill_index(2 * half + r, ph);
+#pragma unroll
+            for (int x = 0; x < 4; x++) {
+                const uint32_t* q = reinterpret_cast<const uint32_t*>(p + (int64_t)sy * stride + bc45_fill_index(x, pw) * TB);
+#pragma unroll
+                for (int k = 0; k < KW; k++) w[(4 * r + x) * KW + k] = q[k];
+            }
+        }
+    }
+}
+
+// The lane's eight texels through the definition: `own` = the biased codes (int8 code + 128, never below 1) of the channel this lane encodes
+// (ch 0: x, 1: y), packed two per dword as encode_channel_snorm takes them, `send` = the other channel's, for the neighbour
+template <int TB>
+__device__ __forceinline__ void signed_normal_codes(uint32_t (&own)[4], uint32_t (&send)[4], const uint32_t (&w)[8 * kept_words<TB>()], uint32_t ch, uint32_t ops)
+{
+    constexpr int KW = kept_words<TB>();
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        uint32_t c[2][2];
+#pragma unroll
+        for (int u = 0; u < 2; u++) {
+            const uint32_t* t = &w[(2 * j + u) * KW];
+            float v[4];
+            if (TB == 16) normal_load_rgba32f(v, t[0], t[1], t[2], 0u);
+            else          normal_load_signed<TB>(v, t);
+            normal_signed_ops(v, ops);
+            c[u][0] = (uint32_t)(normal_quantize_snorm(v[0]) + 128);
+            c[u][1] = (uint32_t)(normal_quantize_snorm(v[1]) + 128);
+        }
+        const uint32_t x = c[0][0] | (c[1][0] << 16), y = c[0][1] | (c[1][1] << 16);
+        own[j] = ch ? y : x;
+        send[j] = ch ? x : y;
+    }
+}
+
+// waves per SIMD of an instantiation: a whole-block float source keeps 24 prefetched words in flight where the others keep 16 or 8, which the
+// 128 registers of four waves do not hold without scratch (16 B spilled); it alone is budgeted for three waves of 168 and takes 139
+constexpr int bc45_waves(uint32_t prep, bool whole) { return (prep == 256u && whole) ? 3 : BC45_WAVES; }
+
 // Persistent workgroups (round 4): a wave of this kernel executes ~630 VALU instructions per block -- a fifth of it waiting for its
 // own texels if it loads, encodes, stores and exits (measured: 55-62 % of the issue slots used).  So at most BC45_GRID workgroups walk
 // the surface in chunks of 256 channel blocks and request the NEXT chunk's texels before encoding the current one.
@@ -510,14 +590,19 @@ __device__ __forceinline__ void normalised_codes(uint32_t (&P)[8], const uint32_
 // PREP (trailing likewise; BC5_UNORM only): the normal-map stages ITW_NORMAL_* of normal_prep.hpp applied to the sixteen loaded words as
 // their codes are gathered -- at the top of the loop, so the texels of the first load and of every prefetch take the same path.  A flip is
 // an exclusive-or of the gathered codes; the normalise is normalised_codes above, its scale table behind the run table (`runs` + 65 536).
+// PREP >= 64 (BC5_SNORM only): PREP / 16 = TB, the texel bytes of a signed normal source (4, 8 or 16); its ops are the trailing argument
+// `sops`, uniform, so each kind is one set of instantiations.  A lane loads two rows of its block (load_rows45 above) and the pair swaps
+// codes through a DPP move; everything from P on is the SNORM encoder as it stands.
 template <int NCH, bool VEC16, bool WHOLE, bool SGN = false, uint32_t PREP = 0>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BC45_WAVES, BC45_WAVES)))
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(bc45_waves(PREP, WHOLE), bc45_waves(PREP, WHOLE))))
 bc45_kernel(const uint8_t* __restrict__ src, int64_t stride, int32_t width, int32_t height, int32_t blocks_x,
-            int32_t nlanes, uint8_t* __restrict__ dst, const uint4* __restrict__ runs)
+            int32_t nlanes, uint8_t* __restrict__ dst, const uint4* __restrict__ runs, uint32_t sops)
 {
+    constexpr int TB = (int)(PREP >> 4);                          // 0: an RGBA8 surface, a whole block per lane
+    constexpr uint32_t BW = TB ? 4u * TB : 16u;                   // bytes of a block's row
     __shared__ StepWeights s_tab[16];                             // [0..7] the 8-step ramp, [8..15] the 6-step ramp
     int32_t lane = blockIdx.x * 256 + threadIdx.x;
-    uint32_t w[16];
+    uint32_t w[TB ? 8 * kept_words<TB ? TB : 4>() : 16];
     // WHOLE: block position of this lane and its byte offset from `src`; per chunk both advance by workgroup-uniform steps
     const int32_t step_blocks = (int32_t)gridDim.x * (NCH == 2 ? 128 : 256);
     const int32_t step_y = step_blocks / blocks_x, step_x = step_blocks - step_y * blocks_x;       // scalar, once
@@ -525,15 +610,21 @@ bc45_kernel(const uint8_t* __restrict__ src, int64_t stride, int32_t width, int3
     int32_t xx = 0;
     uint32_t off = 0;
     auto load_whole = [&](uint32_t o) {
+        if constexpr (TB != 0) {                                  // this lane's two rows
 #pragma unroll
-        for (int y = 0; y < 4; y++) {
-            const uint8_t* p = src + (o + (uint32_t)y * stride32);
-            if (VEC16) {
-                const uint4 v = *reinterpret_cast<const uint4*>(p);
-                w[4 * y] = v.x; w[4 * y + 1] = v.y; w[4 * y + 2] = v.z; w[4 * y + 3] = v.w;
-            } else {
-                const uint32_t* q = reinterpret_cast<const uint32_t*>(p);
-                w[4 * y] = q[0]; w[4 * y + 1] = q[1]; w[4 * y + 2] = q[2]; w[4 * y + 3] = q[3];
+            for (int r = 0; r < 2; r++)
+                load_row45<TB, VEC16>(&w[4 * kept_words<TB>() * r], src + (o + ((threadIdx.x & 1u) * 2u + (uint32_t)r) * stride32));
+        } else {
+#pragma unroll
+            for (int y = 0; y < 4; y++) {
+                const uint8_t* p = src + (o + (uint32_t)y * stride32);
+                if (VEC16) {
+                    const uint4 v = *reinterpret_cast<const uint4*>(p);
+                    w[4 * y] = v.x; w[4 * y + 1] = v.y; w[4 * y + 2] = v.z; w[4 * y + 3] = v.w;
+                } else {
+                    const uint32_t* q = reinterpret_cast<const uint32_t*>(p);
+                    w[4 * y] = q[0]; w[4 * y + 1] = q[1]; w[4 * y + 2] = q[2]; w[4 * y + 3] = q[3];
+                }
             }
         }
     };
@@ -542,9 +633,9 @@ bc45_kernel(const uint8_t* __restrict__ src, int64_t stride, int32_t width, int3
         const int32_t b0 = (NCH == 2) ? (l0 >> 1) : l0;
         const int32_t yy = b0 / blocks_x;
         xx = b0 - yy * blocks_x;
-        off = (uint32_t)yy * 4u * stride32 + (uint32_t)xx * 16u;
+        off = (uint32_t)yy * 4u * stride32 + (uint32_t)xx * BW;
         load_whole(off);
-    } else {
+    } else if constexpr (TB == 0) {
         load_words45<NCH, VEC16>(w, src, stride, width, height, blocks_x, lane < nlanes ? lane : nlanes - 1);
     }
     if (threadIdx.x < 16) s_tab[threadIdx.x] = step_weights(threadIdx.x < 8 ? 8 : 6, threadIdx.x & 7);
@@ -552,11 +643,24 @@ bc45_kernel(const uint8_t* __restrict__ src, int64_t stride, int32_t width, int3
     const uint32_t ch = (NCH == 2) ? (uint32_t)(threadIdx.x & 1) : 0u;   // byte of the RGBA8 word this lane encodes (the grid step is even)
     const uint32_t sel = 0x0c040c00u + ch * 0x00010001u;          // v_perm: byte ch of the first word | byte ch of the second << 16
     const int32_t step = (int32_t)gridDim.x * 256;
-    const uint32_t off_step = (uint32_t)step_y * 4u * stride32 + (uint32_t)step_x * 16u;
-    const uint32_t off_wrap = 4u * stride32 - (uint32_t)blocks_x * 16u;           // one block row down, blocks_x blocks back
+    const uint32_t off_step = (uint32_t)step_y * 4u * stride32 + (uint32_t)step_x * BW;
+    const uint32_t off_wrap = 4u * stride32 - (uint32_t)blocks_x * BW;            // one block row down, blocks_x blocks back
     for (;;) {
         uint32_t P[8];
-        if (PREP & 4u) {
+        if constexpr (TB != 0) {
+            // every lane of the workgroup is here (the loop's exits are uniform), so the neighbour's four dwords arrive by quad_perm [1, 0, 3, 2]
+            // (a surface with partial blocks, rare and small, loads here and prefetches nothing: its 64-bit addresses and the texels in flight
+            // do not both fit the register budget)
+            if (!WHOLE) load_rows45<TB, VEC16>(w, src, stride, width, height, blocks_x, (lane < nlanes ? lane : nlanes - 1) >> 1, (int32_t)ch);
+            uint32_t own[4], send[4];
+            signed_normal_codes<TB>(own, send, w, ch, sops);
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const uint32_t got = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)send[j], 0xb1, 0xf, 0xf, false);
+                P[j] = ch ? got : own[j];                         // rows 0, 1: the R lane's own
+                P[4 + j] = ch ? own[j] : got;                     // rows 2, 3: the G lane's own
+            }
+        } else if (PREP & 4u) {
             normalised_codes<PREP>(P, w, ch, reinterpret_cast<const float*>(runs + 65536));
         } else {
 #pragma unroll
@@ -574,9 +678,9 @@ bc45_kernel(const uint8_t* __restrict__ src, int64_t stride, int32_t width, int3
                 xx += step_x; off += off_step;
                 if (xx >= blocks_x) { xx -= blocks_x; off += off_wrap; }
                 // lanes past the end (last chunk only) re-read the surface's last block: clamp the offset like the lane index
-                const uint32_t last = (uint32_t)(height / 4 - 1) * 4u * stride32 + (uint32_t)(blocks_x - 1) * 16u;
+                const uint32_t last = (uint32_t)(height / 4 - 1) * 4u * stride32 + (uint32_t)(blocks_x - 1) * BW;
                 load_whole(lane < nlanes ? off : last);
-            } else {
+            } else if constexpr (TB == 0) {
                 load_words45<NCH, VEC16>(w, src, stride, width, height, blocks_x, lane < nlanes ? lane : nlanes - 1);
             }
         }
@@ -586,11 +690,13 @@ bc45_kernel(const uint8_t* __restrict__ src, int64_t stride, int32_t width, int3
     }
 }
 
-// PREP (BC5_UNORM only): the normal-map stages in the load, itwCompressNormalMapBC5
+// PREP 1..7 (BC5_UNORM only): the normal-map stages in the load, itwCompressNormalMapBC5; PREP 64 / 128 / 256 (BC5_SNORM only): a signed
+// normal source of 4 / 8 / 16-byte texels with the stages `sops`, itwCompressNormalMapBC5S
 template <int NCH, bool SGN, uint32_t PREP = 0>
-void launch_bc45(const uint8_t* src, int64_t stride, int width, int height, uint8_t* dst, hipStream_t st)
+void launch_bc45(const uint8_t* src, int64_t stride, int width, int height, uint8_t* dst, hipStream_t st, uint32_t sops = 0)
 {
-    static_assert(PREP == 0 || (NCH == 2 && !SGN), "the normal-map stages go with BC5_UNORM");
+    static_assert(PREP == 0 || (PREP < 8u && NCH == 2 && !SGN) || ((PREP == 64u || PREP == 128u || PREP == 256u) && NCH == 2 && SGN),
+                  "the normal-map stages go with BC5_UNORM, a signed normal source with BC5_SNORM");
     if (width <= 0 || height <= 0) return;
     const int bx = (width + 3) / 4, by = (height + 3) / 4;       // DirectXTex keeps partial blocks
     const int64_t n = (int64_t)bx * by * NCH;
@@ -601,11 +707,11 @@ void launch_bc45(const uint8_t* src, int64_t stride, int width, int height, uint
     // WHOLE: no partial blocks and every texel offset fits 31 bits (a non-negative stride; 16384^2 RGBA8 is 1 GiB)
     const bool whole = (width % 4 == 0) && (height % 4 == 0) && stride > 0 && (int64_t)height * stride < ((int64_t)1 << 31);
     if (whole) {
-        if (vec) hipLaunchKernelGGL((bc45_kernel<NCH, true, true, SGN, PREP>),  grid, blk, 0, st, src, stride, width, height, bx, (int32_t)n, dst, runs);
-        else     hipLaunchKernelGGL((bc45_kernel<NCH, false, true, SGN, PREP>), grid, blk, 0, st, src, stride, width, height, bx, (int32_t)n, dst, runs);
+        if (vec) hipLaunchKernelGGL((bc45_kernel<NCH, true, true, SGN, PREP>),  grid, blk, 0, st, src, stride, width, height, bx, (int32_t)n, dst, runs, sops);
+        else     hipLaunchKernelGGL((bc45_kernel<NCH, false, true, SGN, PREP>), grid, blk, 0, st, src, stride, width, height, bx, (int32_t)n, dst, runs, sops);
     } else {
-        if (vec) hipLaunchKernelGGL((bc45_kernel<NCH, true, false, SGN, PREP>),  grid, blk, 0, st, src, stride, width, height, bx, (int32_t)n, dst, runs);
-        else     hipLaunchKernelGGL((bc45_kernel<NCH, false, false, SGN, PREP>), grid, blk, 0, st, src, stride, width, height, bx, (int32_t)n, dst, runs);
+        if (vec) hipLaunchKernelGGL((bc45_kernel<NCH, true, false, SGN, PREP>),  grid, blk, 0, st, src, stride, width, height, bx, (int32_t)n, dst, runs, sops);
+        else     hipLaunchKernelGGL((bc45_kernel<NCH, false, false, SGN, PREP>), grid, blk, 0, st, src, stride, width, height, bx, (int32_t)n, dst, runs, sops);
     }
 }
 
@@ -651,6 +757,15 @@ void launch_bc5_normal(const uint8_t* src, int64_t stride, int width, int height
 {
     if (ops == 0u) launch_bc45<2, false>(src, stride, width, height, dst, st);
     else           launch_bc5_prep<1>(ops, src, stride, width, height, dst, st);
+}
+
+void launch_bc5s_normal(const uint8_t* src, int texel_bytes, int64_t stride, int width, int height, uint8_t* dst, uint32_t ops, hipStream_t st)
+{
+    if (texel_bytes == 4 && ops == 0u) launch_bc45<2, true>(src, stride, width, height, dst, st);      // CompressBlocksBC5S itself
+    else if (texel_bytes == 4)  launch_bc45<2, true, 64u>(src, stride, width, height, dst, st, ops);
+    else if (texel_bytes == 8)  launch_bc45<2, true, 128u>(src, stride, width, height, dst, st, ops);
+    else if (texel_bytes == 16) launch_bc45<2, true, 256u>(src, stride, width, height, dst, st, ops);
+    else fail_msg("BC5S normal map: texel_bytes %d", texel_bytes);
 }
 
 void warmup_bc45() { (void)index_table<false>(); }

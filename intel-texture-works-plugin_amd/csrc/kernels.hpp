@@ -21,7 +21,10 @@ void launch_bc4s(const uint8_t* src, int64_t stride, int width, int height, uint
 void launch_bc5s(const uint8_t* src, int64_t stride, int width, int height, uint8_t* dst, hipStream_t st);
 // BC5_UNORM of a normal map: the stages `ops` (ITW_NORMAL_*, 1..7; normal_prep.hpp) applied to the texels as the kernel loads them
 void launch_bc5_normal(const uint8_t* src, int64_t stride, int width, int height, uint8_t* dst, uint32_t ops, hipStream_t st);
-void warmup_bc45s();                                              // the same for the SNORM encoders' table (FindClosestSNORM)
+// BC5_SNORM of a signed normal source (normal_prep.hpp): texel_bytes 4 (RGBA8_SNORM), 8 (RGBA16F) or 16 (RGBA32F), src and stride 4-byte aligned,
+// the stages `ops` (0..7) and the quantisation applied as the kernel loads the texels; (4, ops 0) is launch_bc5s
+void launch_bc5s_normal(const uint8_t* src, int texel_bytes, int64_t stride, int width, int height, uint8_t* dst, uint32_t ops, hipStream_t st);
+void warmup_bc45s();                                            // the same for the SNORM encoders' table (FindClosestSNORM)
 void copy_bc45_closest_snorm(uint8_t* host_out, hipStream_t st);  // test hook: the SNORM encoders' index for every (endpoint pair, code), 16 MiB
 void warmup_bc45();                                               // builds the current device's FindClosestUNORM run table now (else: first call)
 void copy_bc45_index_table(uint32_t* host_out, hipStream_t st);   // test hook: the FindClosestUNORM run table of the current device
@@ -96,8 +99,10 @@ struct ChainImage { const uint8_t* ptr; int64_t stride; int32_t width, height; i
 // `fill45`: partial blocks take bc45_fill_index (BC4/BC5) instead of edge replication (the ISPC formats' pad to multiples of 4).
 // `extents` (optional, edge replication only): device memory, one byte per block j < nblocks: (pw - 1) | (ph - 1) << 2, the pw x ph texels
 // of the block that lie inside its image.  `normal_ops` (ITW_NORMAL_*, itw_dispatch.h; not with `extents`): the normal-map stages applied
-// to every texel as it is copied (normal_prep.hpp).
+// to every texel as it is copied (normal_prep.hpp).  `signed_source` (4, 8 or 16; texel_bytes 4 and fill45 only): the images are signed
+// normal sources of that many bytes per texel and `normal_ops` (0..7) has its signed meaning: each texel is quantised to its RGBA8_SNORM word
+// as it is copied.
 void launch_chain_gather(const ChainImage* images, int nimg, int64_t nblocks, int packed_bx, int packed_by, int texel_bytes, bool fill45,
-                         uint8_t* dst, int64_t dst_pitch, hipStream_t st, uint8_t* extents = nullptr, uint32_t normal_ops = 0);
+                         uint8_t* dst, int64_t dst_pitch, hipStream_t st, uint8_t* extents = nullptr, uint32_t normal_ops = 0, int signed_source = 0);
 
 } // namespace itw

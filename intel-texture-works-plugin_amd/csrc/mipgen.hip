@@ -21,6 +21,7 @@
 #include "../../include/itw_dispatch.h"
 #include "../../include/itw_amd.h"
 #include "mipgen.hpp"
+#include "normal_prep.hpp"
 #include "bcn_format.hpp"
 #include "host_rt.hpp"
 
@@ -313,6 +314,55 @@ thread_local ChainBuffer t_chain;
 
 } // namespace
 
+namespace itw {
+
+// Level 0 of itwCompressSignedNormalMapMipped: a signed normal base of TB-byte texels (normal_prep.hpp) widened into RGBA16F, the flips of
+// `ops` folded in (a negation: exact, and it commutes with both filters).  int8: half(load rule); half: the bits as they are (a flip is the
+// sign bit); float: the mip filter's store rule (mip_half_bits).  One lane per texel row quad: 4 * TB bytes in, 32 bytes out, whole vectors
+// where the addresses allow.
+template <int TB>
+__global__ void __launch_bounds__(256)
+mip_widen_signed_kernel(const uint8_t* __restrict__ src, int64_t src_stride, uint8_t* __restrict__ dst, int64_t dst_stride, int32_t width, int32_t height, uint32_t ops)
+{
+    const int32_t qpr = (width + 3) >> 2;
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= (int64_t)qpr * height) return;
+    const int32_t y = (int32_t)(j / qpr), qx = (int32_t)(j - (int64_t)y * qpr);
+    const int32_t n = min(4, width - 4 * qx);
+    const uint8_t* s = src + (int64_t)y * src_stride + (int64_t)qx * 4 * TB;
+    uint8_t* d = dst + (int64_t)y * dst_stride + (int64_t)qx * 32;
+    constexpr int WPT = TB / 4;
+    uint32_t w[4 * WPT], o[8];
+    if (n == 4 && ((uintptr_t)s & 15) == 0) {
+#pragma unroll
+        for (int k = 0; k < WPT; k++) { const uint4 t = reinterpret_cast<const uint4*>(s)[k]; w[4 * k] = t.x; w[4 * k + 1] = t.y; w[4 * k + 2] = t.z; w[4 * k + 3] = t.w; }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4 * WPT; k++) w[k] = k < n * WPT ? reinterpret_cast<const uint32_t*>(s)[k] : 0u;
+    }
+    const uint32_t flip = ((ops & NORMAL_FLIP_X) ? 0x00008000u : 0u) | ((ops & NORMAL_FLIP_Y) ? 0x80000000u : 0u);   // the sign bits of x and y in the low word
+#pragma unroll
+    for (int x = 0; x < 4; x++) {
+        if (TB == 8) { o[2 * x] = w[2 * x]; o[2 * x + 1] = w[2 * x + 1]; }
+        else {
+            float v[4];
+            normal_load_signed<TB>(v, w + x * WPT);
+            o[2 * x] = mip_half_bits(v[0]) | (mip_half_bits(v[1]) << 16);
+            o[2 * x + 1] = mip_half_bits(v[2]) | (mip_half_bits(v[3]) << 16);
+        }
+        o[2 * x] ^= flip;
+    }
+    if (n == 4 && ((uintptr_t)d & 15) == 0) {
+        reinterpret_cast<uint4*>(d)[0] = make_uint4(o[0], o[1], o[2], o[3]);
+        reinterpret_cast<uint4*>(d)[1] = make_uint4(o[4], o[5], o[6], o[7]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 8; k++) if (k < 2 * n) reinterpret_cast<uint32_t*>(d)[k] = o[k];
+    }
+}
+
+} // namespace itw
+
 extern "C" int itwMipLevels(int width, int height)
 {
     if (width < 1 || height < 1) return 0;
@@ -422,6 +472,72 @@ extern "C" bool itwCompressImageMipped(const rgba_surface* bases, int items, int
         stage(itwGenerateMipChain(chain.data(), items, levels, px, 0), "the mip chain");
         if (normal_ops & 4u) stage(itwPrepareNormalMapChain(chain.data(), items * levels, px, 4u), "the normalise");
         done = itwCompressImageChainEx(chain.data(), items * levels, target, dxgi_format, settings, progress, user);
+        t_chain.release(st);
+    });
+    return ok && done;
+}
+
+// the signed normal-map save path in one call (include/itw_dispatch.h): a composition of the stages, like itwCompressImageMipped
+extern "C" bool itwCompressSignedNormalMapMipped(const rgba_surface* bases, int items, int levels, int texel_bytes, uint32_t ops, uint8_t* target,
+                                                 int dxgi_format, ItwProgressFunc* progress, void* user)
+{
+    bool done = false;
+    itw::clear_failure();
+    const bool ok = itw::guarded([&] {
+        if (dxgi_format != 81 && dxgi_format != 84)
+            itw::fail_msg("itwCompressSignedNormalMapMipped: DXGI format %d (BC4_SNORM = 81 or BC5_SNORM = 84)", dxgi_format);
+        if (texel_bytes != 4 && texel_bytes != 8 && texel_bytes != 16) itw::fail_msg("itwCompressSignedNormalMapMipped: texel_bytes %d (4, 8 or 16)", texel_bytes);
+        if (ops & ~7u) itw::fail_msg("itwCompressSignedNormalMapMipped: unknown ops bits 0x%x", ops);
+        itw::chain_check_with(bases, items, target, dxgi_format, nullptr);        // counts, null pointers, sizes, format
+        const int w = bases[0].width, h = bases[0].height, full = itwMipLevels(w, h);
+        for (int i = 0; i < items; i++) {
+            if (bases[i].width != w || bases[i].height != h)
+                itw::fail_msg("itwCompressSignedNormalMapMipped: base %d is %d x %d, base 0 %d x %d", i, bases[i].width, bases[i].height, w, h);
+            if ((int64_t)bases[i].stride < (int64_t)w * texel_bytes)
+                itw::fail_msg("itwCompressSignedNormalMapMipped: base %d: stride %d < %lld bytes per row", i, bases[i].stride, (long long)w * texel_bytes);
+            const uintptr_t row_step = h > 1 ? (uintptr_t)(uint32_t)bases[i].stride : 0;
+            if (((uintptr_t)bases[i].ptr | row_step) & (uintptr_t)(texel_bytes - 1))
+                itw::fail_msg("itwCompressSignedNormalMapMipped: base %d: texels are not %d-byte aligned", i, texel_bytes);
+        }
+        if (levels < 0 || levels > full) itw::fail_msg("itwCompressSignedNormalMapMipped: %d levels, a full chain of %d x %d has %d", levels, w, h, full);
+        if (levels == 0) levels = full;
+        if ((int64_t)items * levels > (int64_t)0x7fffffff / 64) itw::fail_msg("itwCompressSignedNormalMapMipped: %d items of %d levels", items, levels);
+        check_launch_limits("itwCompressSignedNormalMapMipped", w, h, items);
+        const bool dev = itw::is_device_pointer(bases[0].ptr);
+        for (int i = 1; i < items; i++)
+            if (itw::is_device_pointer(bases[i].ptr) != dev)
+                itw::fail_msg("itwCompressSignedNormalMapMipped: base %d is %s memory, base 0 %s: all bases must be host or all device pointers", i,
+                              dev ? "host" : "device", dev ? "device" : "host");
+        const int64_t bytes = itwMipChainLayout(w, h, items, levels, 8, nullptr, nullptr);
+        if (bytes < 0) itw::fail_msg("itwCompressSignedNormalMapMipped: a %d x %d base is wider than a surface can describe", w, h);
+
+        // the thread's chain buffer: [RGBA16F chain] [host bases as they are, rows of a 16-byte multiple]
+        hipStream_t st = (hipStream_t)itwGetStream();
+        const size_t chain_bytes = ((size_t)bytes + 255) & ~(size_t)255, pitch = ((size_t)w * texel_bytes + 15) & ~(size_t)15;
+        const size_t base_bytes = dev ? 0 : (pitch * (size_t)h + 255) & ~(size_t)255;
+        uint8_t* buf = t_chain.get(chain_bytes + base_bytes * (size_t)items, st);
+        std::vector<rgba_surface> chain((size_t)items * levels);
+        itwMipChainLayout(w, h, items, levels, 8, buf, chain.data());
+        const int64_t quads = (int64_t)((w + 3) >> 2) * h;                        // (within one launch: check_launch_limits bounds the tiles of 64 x 64)
+        if ((quads + 255) / 256 > (int64_t)0x7fffffff) itw::fail_msg("itwCompressSignedNormalMapMipped: a %d x %d base is more than one launch covers", w, h);
+        const dim3 grid((unsigned)((quads + 255) / 256)), blk(256);
+        for (int i = 0; i < items; i++) {
+            const uint8_t* src = bases[i].ptr;
+            int64_t stride = bases[i].stride;
+            if (!dev) {
+                uint8_t* staged = buf + chain_bytes + base_bytes * (size_t)i;
+                ITW_CHECK(hipMemcpy2DAsync(staged, pitch, bases[i].ptr, (size_t)bases[i].stride, (size_t)w * texel_bytes, (size_t)h, hipMemcpyHostToDevice, st));
+                src = staged; stride = (int64_t)pitch;
+            }
+            const rgba_surface& l0 = chain[(size_t)i * levels];
+            if (texel_bytes == 4)      hipLaunchKernelGGL((itw::mip_widen_signed_kernel<4>), grid, blk, 0, st, src, stride, l0.ptr, (int64_t)l0.stride, w, h, ops & 3u);
+            else if (texel_bytes == 8) hipLaunchKernelGGL((itw::mip_widen_signed_kernel<8>), grid, blk, 0, st, src, stride, l0.ptr, (int64_t)l0.stride, w, h, ops & 3u);
+            else                       hipLaunchKernelGGL((itw::mip_widen_signed_kernel<16>), grid, blk, 0, st, src, stride, l0.ptr, (int64_t)l0.stride, w, h, ops & 3u);
+            ITW_CHECK(hipGetLastError());
+        }
+        if (itwGenerateMipChain(chain.data(), items, levels, 8, 0) != 0) itw::fail_msg("itwCompressSignedNormalMapMipped: the mip chain failed: %s", itwLastError());
+        // the normalise runs in fp32 on every level inside the chain's gather: no pass of its own, no rounding to half before the quantisation
+        done = itwCompressSignedNormalMapChain(chain.data(), items * levels, 8, target, dxgi_format, ops & 4u, progress, user);
         t_chain.release(st);
     });
     return ok && done;

@@ -68,6 +68,72 @@ normal_prep_kernel(const PrepLevel* __restrict__ levels, const PrepLevel one, in
     normal_prep_quad<PX>(lv, j - lv.first_quad, ops);
 }
 
+// ---- itwQuantizeNormalMapChain: signed normal sources (normal_prep.hpp) to RGBA8_SNORM, out of place -----------------------------------------
+// The same walk: a lane takes a quad of one row of one image, 4 * TB source bytes into 16 target bytes.  A target may be its own source when
+// TB == 4: a lane reads its quad before it writes it and no other lane touches those texels.
+struct QuantLevel { const uint8_t* src; uint8_t* dst; int64_t src_stride, dst_stride; int32_t width, height; int64_t first_quad; };
+
+template <int TB>
+__device__ __forceinline__ void normal_quantize_quad(const QuantLevel& lv, int64_t q, uint32_t ops)
+{
+    const int32_t qpr = (lv.width + 3) >> 2;
+    int64_t y;
+    int32_t qx;
+    if (q < ((int64_t)1 << 31)) { const uint32_t yy = (uint32_t)q / (uint32_t)qpr; y = yy; qx = (int32_t)((uint32_t)q - yy * (uint32_t)qpr); }
+    else                        { y = q / qpr; qx = (int32_t)(q - y * qpr); }
+    const int32_t n = min(4, lv.width - 4 * qx);                  // texels of this quad inside the row
+    const uint8_t* s = lv.src + y * lv.src_stride + (int64_t)qx * 4 * TB;
+    uint8_t* d = lv.dst + y * lv.dst_stride + (int64_t)qx * 16;
+    constexpr int WPT = TB / 4;                                   // words per source texel
+    uint32_t w[4 * WPT], o[4];
+    const bool vec_in = n == 4 && ((uintptr_t)s & 15) == 0;
+    if (vec_in) {
+        const uint4* s4 = reinterpret_cast<const uint4*>(s);
+#pragma unroll
+        for (int k = 0; k < WPT; k++) { const uint4 t = s4[k]; w[4 * k] = t.x; w[4 * k + 1] = t.y; w[4 * k + 2] = t.z; w[4 * k + 3] = t.w; }
+    } else {
+        const uint32_t* s1 = reinterpret_cast<const uint32_t*>(s);    // texel aligned, so word aligned
+#pragma unroll
+        for (int k = 0; k < 4 * WPT; k++) w[k] = k < n * WPT ? s1[k] : 0u;
+    }
+#pragma unroll
+    for (int x = 0; x < 4; x++) {
+        float v[4];
+        normal_load_signed<TB>(v, w + x * WPT);
+        o[x] = normal_quantize_texel(v, ops);
+    }
+    if (n == 4 && ((uintptr_t)d & 15) == 0) *reinterpret_cast<uint4*>(d) = make_uint4(o[0], o[1], o[2], o[3]);
+    else {
+        uint32_t* d1 = reinterpret_cast<uint32_t*>(d);
+#pragma unroll
+        for (int x = 0; x < 4; x++) if (x < n) d1[x] = o[x];
+    }
+}
+
+template <int TB, bool ONE>
+__global__ void __launch_bounds__(256)
+normal_quantize_kernel(const QuantLevel* __restrict__ levels, const QuantLevel one, int32_t nlev, int64_t nquads, uint32_t ops)
+{
+    const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (j >= nquads) return;
+    if (ONE) { normal_quantize_quad<TB>(one, j, ops); return; }
+    int lo = 0, hi = nlev - 1;                                    // the last image whose first quad is <= j
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (levels[mid].first_quad <= j) lo = mid; else hi = mid - 1;
+    }
+    const QuantLevel lv = levels[lo];
+    normal_quantize_quad<TB>(lv, j - lv.first_quad, ops);
+}
+
+template <int TB>
+void launch_normal_quantize(const QuantLevel* d_desc, const QuantLevel& first, int count, int64_t quads, uint32_t ops, hipStream_t st)
+{
+    const dim3 grid((unsigned)((quads + 255) / 256)), blk(256);
+    if (count == 1) hipLaunchKernelGGL((normal_quantize_kernel<TB, true>), grid, blk, 0, st, d_desc, first, 1, quads, ops);
+    else            hipLaunchKernelGGL((normal_quantize_kernel<TB, false>), grid, blk, 0, st, d_desc, first, (int32_t)count, quads, ops);
+}
+
 } // namespace itw
 
 namespace {
@@ -122,7 +188,94 @@ void prepare_chain(const rgba_surface* im, int count, int px, uint32_t ops, bool
     itw::decode_scratch_done(st);
 }
 
+// itwQuantizeNormalMapChain's device work: `count` >= 1 pairs that passed the checks, all of one pointer kind
+void quantize_chain(const rgba_surface* src, int tb, const rgba_surface* dst, int count, uint32_t ops, bool dev)
+{
+    hipStream_t st = (hipStream_t)itwGetStream();
+    static thread_local std::vector<itw::QuantLevel> desc;        // grow-only, like the device buffer it is copied into
+    desc.resize((size_t)count);
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    // the thread's buffer: [level table] [staged sources, staged targets (host pointers), rows of a 16-byte multiple]
+    size_t bytes = count > 1 ? up((size_t)count * sizeof(itw::QuantLevel)) : 0;
+    int64_t quads = 0;
+    std::vector<size_t> src_off(dev ? 0 : (size_t)count), dst_off(dev ? 0 : (size_t)count);
+    for (int i = 0; i < count; i++) {
+        itw::QuantLevel& d = desc[(size_t)i];
+        d.src = src[i].ptr; d.src_stride = src[i].stride; d.dst = dst[i].ptr; d.dst_stride = dst[i].stride;
+        d.width = src[i].width; d.height = src[i].height;
+        d.first_quad = quads;
+        quads += (int64_t)((d.width + 3) >> 2) * d.height;
+        if (!dev) {
+            d.src_stride = (int64_t)(((size_t)d.width * tb + 15) & ~(size_t)15);
+            d.dst_stride = (int64_t)(((size_t)d.width * 4 + 15) & ~(size_t)15);
+            src_off[(size_t)i] = bytes;
+            bytes += up((size_t)d.src_stride * (size_t)d.height);
+            dst_off[(size_t)i] = bytes;
+            bytes += up((size_t)d.dst_stride * (size_t)d.height);
+        }
+    }
+    if ((quads + 255) / 256 > (int64_t)0x7fffffff) itw::fail_msg("itwQuantizeNormalMapChain: %lld texel quads are more than one launch covers", (long long)quads);
+    const bool buffer = !dev || count > 1;                        // a resident chain of one touches no buffer of the thread
+    uint8_t* base = buffer ? static_cast<uint8_t*>(itw::decode_scratch(bytes, st)) : nullptr;
+    if (!dev)
+        for (int i = 0; i < count; i++) {
+            itw::QuantLevel& d = desc[(size_t)i];
+            d.src = base + src_off[(size_t)i]; d.dst = base + dst_off[(size_t)i];
+            ITW_CHECK(hipMemcpy2DAsync(const_cast<uint8_t*>(d.src), (size_t)d.src_stride, src[i].ptr, (size_t)src[i].stride, (size_t)d.width * tb,
+                                       (size_t)d.height, hipMemcpyHostToDevice, st));
+        }
+    if (count > 1) ITW_CHECK(hipMemcpyAsync(base, desc.data(), (size_t)count * sizeof(itw::QuantLevel), hipMemcpyHostToDevice, st));
+    const itw::QuantLevel* d_desc = count > 1 ? reinterpret_cast<const itw::QuantLevel*>(base) : nullptr;
+    if (tb == 4)      itw::launch_normal_quantize<4>(d_desc, desc[0], count, quads, ops, st);
+    else if (tb == 8) itw::launch_normal_quantize<8>(d_desc, desc[0], count, quads, ops, st);
+    else              itw::launch_normal_quantize<16>(d_desc, desc[0], count, quads, ops, st);
+    ITW_CHECK(hipGetLastError());
+    if (dev) { if (buffer) itw::decode_scratch_done(st); return; }     // resident: asynchronous on the thread's stream
+    for (int i = 0; i < count; i++)                               // width x height only: the caller's row padding is not written
+        ITW_CHECK(hipMemcpy2DAsync(dst[i].ptr, (size_t)dst[i].stride, desc[(size_t)i].dst, (size_t)desc[(size_t)i].dst_stride, (size_t)dst[i].width * 4,
+                                   (size_t)dst[i].height, hipMemcpyDeviceToHost, st));
+    ITW_CHECK(hipStreamSynchronize(st));
+    itw::decode_scratch_done(st);
+}
+
 } // namespace
+
+extern "C" int itwQuantizeNormalMapChain(const rgba_surface* sources, int texel_bytes, const rgba_surface* targets, int count, uint32_t ops)
+{
+    itw::clear_failure();
+    bool dev = false;
+    // the refusals: through the error mode, before any device work
+    const bool ok = itw::guarded([&] {
+        if (count < 0) itw::fail_msg("itwQuantizeNormalMapChain: count %d", count);
+        if (texel_bytes != 4 && texel_bytes != 8 && texel_bytes != 16) itw::fail_msg("itwQuantizeNormalMapChain: texel_bytes %d (4, 8 or 16)", texel_bytes);
+        if (ops & ~itw::NORMAL_OPS_ALL) itw::fail_msg("itwQuantizeNormalMapChain: unknown ops bits 0x%x", ops);
+        if (count == 0) return;
+        if (!sources || !targets) itw::fail_msg("itwQuantizeNormalMapChain: null image list");
+        for (int i = 0; i < count; i++) {
+            const rgba_surface& s = sources[i];
+            const rgba_surface& t = targets[i];
+            if (!s.ptr || !t.ptr) itw::fail_msg("itwQuantizeNormalMapChain: image %d: null texel pointer", i);
+            if (s.width < 1 || s.height < 1) itw::fail_msg("itwQuantizeNormalMapChain: image %d: %d x %d", i, s.width, s.height);
+            if (t.width != s.width || t.height != s.height)
+                itw::fail_msg("itwQuantizeNormalMapChain: image %d: the target is %d x %d, its source %d x %d", i, t.width, t.height, s.width, s.height);
+            if ((int64_t)s.stride < (int64_t)s.width * texel_bytes || (int64_t)t.stride < (int64_t)t.width * 4)
+                itw::fail_msg("itwQuantizeNormalMapChain: image %d: a stride below the row's bytes", i);
+            const uintptr_t s_step = s.height > 1 ? (uintptr_t)(uint32_t)s.stride : 0, t_step = t.height > 1 ? (uintptr_t)(uint32_t)t.stride : 0;
+            if ((((uintptr_t)s.ptr | s_step) & (uintptr_t)(texel_bytes - 1)) || (((uintptr_t)t.ptr | t_step) & 3))
+                itw::fail_msg("itwQuantizeNormalMapChain: image %d: texels not aligned to their size", i);
+        }
+    });
+    if (!ok) return -1;
+    if (count == 0) return 0;
+    const bool done = itw::guarded([&] {
+        dev = itw::is_device_pointer(sources[0].ptr);
+        for (int i = 0; i < count; i++)
+            if (itw::is_device_pointer(sources[i].ptr) != dev || itw::is_device_pointer(targets[i].ptr) != dev)
+                itw::fail_msg("itwQuantizeNormalMapChain: image %d: host and device pointers in one call", i);
+        quantize_chain(sources, texel_bytes, targets, count, ops, dev);
+    });
+    return done ? 0 : -1;
+}
 
 extern "C" int itwPrepareNormalMapChain(const rgba_surface* images, int count, int pixel_size, uint32_t ops)
 {
@@ -147,7 +300,7 @@ extern "C" int itwPrepareNormalMapChain(const rgba_surface* images, int count, i
 // truncating quotients, exactly as the reference's.  Views: no rotation and no copy (its CopyRectangle calls copy the rectangles as they lie)
 extern "C" int itwCubeCrossFaces(const rgba_surface* cross, int pixel_size, rgba_surface faces[6])
 {
-    if (!cross || !faces || !cross->ptr || (pixel_size != 4 && pixel_size != 8)) return -1;
+    if (!cross || !faces || !cross->ptr || (pixel_size != 4 && pixel_size != 8 && pixel_size != 16)) return -1;
     int cells[6][2] = {{2, 1}, {0, 1}, {1, 0}, {1, 2}, {1, 1}, {3, 1}};
     const bool vertical = cross->width < cross->height;
     if (cross->width < (vertical ? 3 : 4) || cross->height < (vertical ? 4 : 3)) return -1;

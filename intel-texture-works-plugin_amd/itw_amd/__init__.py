@@ -20,6 +20,6 @@ from .abi import (  # noqa: F401
     ErrorStats, OWN_CHANNELS, measure, measure_async, measure_chain, stats_from_tensor,
     RefineStats, compress_refined, RefinePolicy, RefineTargetStats, compress_refined_to, psnr_to_total_sse,
     compress_chain_refined, compress_chain_refined_to, chain_psnr_to_total_sse,
-    NORMAL_FLIP_X, NORMAL_FLIP_Y, NORMAL_NORMALIZE, normal_ops, prepare_normal_map, compress_normal_map, cube_cross_faces,
+    NORMAL_FLIP_X, NORMAL_FLIP_Y, NORMAL_NORMALIZE, normal_ops, prepare_normal_map, compress_normal_map, quantize_normal_map, compress_normal_map_snorm, compress_chain_normal_snorm, compress_mipped_normal_snorm, cube_cross_faces,
     MIP_PER_LEVEL, mip_levels, mip_chain_layout, generate_mips, generate_mips_into, compress_mipped,
 )

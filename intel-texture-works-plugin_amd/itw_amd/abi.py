@@ -25,13 +25,13 @@ EXPORTED_SYMBOLS = tuple(
     + ["CompressImageBC7_" + p for p in BC7_PROFILES] + ["CompressImageBC6H_" + p for p in BC6H_PROFILES]
     + ["itwCompressImageSliced", "itwCompressImageSlicedEx", "itwChainBytes", "itwCompressImageChain", "itwCompressImageChainEx", "itwCompressImageRefined", "itwCompressImageRefinedTo", "itwPsnrToTotalSse", "itwCompressImageChainRefined", "itwCompressImageChainRefinedTo", "itwChainPsnrToTotalSse", "itwSetSliceWindow", "itwSliceWindow", "itwSliceWindowFor", "itwPadToMultipleOf4", "itwFreeSurface", "itwPadToMultipleOf4Device",
        "itwConvertToRGBA8Device", "itwConvertToRGBA16FDevice",
-       "itwPrepareNormalMapChain", "itwCompressNormalMapChain", "itwCubeCrossFaces",
+       "itwPrepareNormalMapChain", "itwCompressNormalMapChain", "itwQuantizeNormalMapChain", "itwCompressSignedNormalMapChain", "itwCompressSignedNormalMapMipped", "itwCubeCrossFaces",
        "itwMipLevels", "itwMipChainLayout", "itwGenerateMipChain", "itwCompressImageMipped"]
     # include/itw_multigpu.h: one surface over all GPUs, one process
     + ["itwMultiGpuRanks", "itwMultiGpuTransport", "itwMultiGpuPeerLinks", "itwCompressImageMultiGPU", "itwCompressImageMultiGPUEx", "itwCompressImageMultiGPUBands",
        "itwMultiGpuSetInterleave", "itwMultiGpuPieces"]
     # include/itw_bc45.h: the DirectXTex formats of the plugin
-    + ["CompressBlocksBC4", "CompressBlocksBC5", "itwWarmupBC45", "CompressBlocksBC4S", "CompressBlocksBC5S", "itwWarmupBC45S", "itwCompressNormalMapBC5"]
+    + ["CompressBlocksBC4", "CompressBlocksBC5", "itwWarmupBC45", "CompressBlocksBC4S", "CompressBlocksBC5S", "itwWarmupBC45S", "itwCompressNormalMapBC5", "itwCompressNormalMapBC5S"]
     # include/itw_decode.h: device decoders
     + ["itwDecodeBlocks", "itwDecodeChain", "itwDecodeImage", "itwMeasureBlocks", "itwMeasureChain", "itwStatsPsnr", "itwPreviewBlocks", "itwPreviewSurface"]
     # include/itw_dds.h: DDS container
@@ -399,6 +399,14 @@ def _load(path, hooks):
         L.itwCompressNormalMapChain.restype = C.c_bool
         L.itwCompressNormalMapBC5.argtypes = [C.POINTER(RgbaSurface), C.c_void_p, C.c_uint32]
         L.itwCompressNormalMapBC5.restype = None
+        L.itwQuantizeNormalMapChain.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_uint32]
+        L.itwQuantizeNormalMapChain.restype = C.c_int
+        L.itwCompressSignedNormalMapChain.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p]
+        L.itwCompressSignedNormalMapChain.restype = C.c_bool
+        L.itwCompressSignedNormalMapMipped.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.itwCompressSignedNormalMapMipped.restype = C.c_bool
+        L.itwCompressNormalMapBC5S.argtypes = [C.POINTER(RgbaSurface), C.c_int, C.c_void_p, C.c_uint32]
+        L.itwCompressNormalMapBC5S.restype = None
         L.itwCubeCrossFaces.argtypes = [C.POINTER(RgbaSurface), C.c_int, C.POINTER(RgbaSurface)]
         L.itwCubeCrossFaces.restype = C.c_int
         L.itwMipLevels.argtypes = [C.c_int, C.c_int]
@@ -805,6 +813,150 @@ def compress_normal_map(img, flip_x=False, flip_y=False, normalize=False, ops=No
         out = np.empty(nbytes, dtype=np.uint8)
     lib().itwCompressNormalMapBC5(C.byref(RgbaSurface(img.ctypes.data, w, h, img.strides[0])), out.ctypes.data, ops)
     return out
+
+
+def _signed_texel_bytes(img):
+    """The texel kind of a signed normal source (include/itw_dispatch.h) from its dtype: int8 -> 4 (RGBA8_SNORM), float16 or any 2-byte
+    element -> 8 (RGBA16F), float32 -> 16 (RGBA32F)."""
+    name = str(img.dtype).replace("torch.", "")
+    es = img.element_size() if hasattr(img, "data_ptr") else img.itemsize
+    if name == "int8":
+        return 4
+    if es == 2:
+        return 8
+    if name == "float32":
+        return 16
+    raise TypeError(f"a signed normal source is int8, float16 (or 2-byte half bits) or float32, not {name}")
+
+
+def _signed_surface(img):
+    """RgbaSurface of an (H, W, 4) numpy array or torch tensor of any element size, texels contiguous."""
+    if hasattr(img, "data_ptr"):
+        assert img.dim() == 3 and img.shape[2] == 4 and img.stride(2) == 1 and img.stride(1) == 4
+        return RgbaSurface(img.data_ptr(), img.shape[1], img.shape[0], img.stride(0) * img.element_size())
+    assert img.ndim == 3 and img.shape[2] == 4 and img.strides[2] == img.itemsize and img.strides[1] == 4 * img.itemsize
+    return RgbaSurface(img.ctypes.data, img.shape[1], img.shape[0], img.strides[0])
+
+
+def quantize_normal_map(images, flip_x=False, flip_y=False, normalize=False, ops=None, out=None):
+    """itwQuantizeNormalMapChain: one signed normal source or a list of them (a mip chain) -- (H, W, 4) numpy arrays or CUDA torch tensors of
+    one dtype: int8, float16 / 2-byte half bits, or float32 -- to RGBA8_SNORM images (int8) of the same sizes: the flips, the normalise in
+    fp32, and the quantisation with round to nearest even.  `out`: the targets (default: new ones; an int8 source may be its own target).
+    Device tensors: one launch, asynchronous on torch's current stream; numpy arrays: synchronous.  Returns the target(s)."""
+    single = hasattr(images, "shape")
+    imgs = [images] if single else list(images)
+    ops = normal_ops(flip_x, flip_y, normalize) if ops is None else int(ops)
+    if not imgs:
+        return []
+    tb = _signed_texel_bytes(imgs[0])
+    assert all(_signed_texel_bytes(i) == tb for i in imgs), "one texel kind per call"
+    on_device = hasattr(imgs[0], "data_ptr")
+    if out is None:
+        if on_device:
+            import torch
+            outs = [torch.empty(tuple(i.shape), dtype=torch.int8, device=i.device) for i in imgs]
+        else:
+            import numpy as np
+            outs = [np.empty(i.shape, dtype=np.int8) for i in imgs]
+    else:
+        outs = [out] if hasattr(out, "shape") else list(out)
+    assert len(outs) == len(imgs)
+    if on_device:
+        import torch
+        lib().itwSetStream(torch.cuda.current_stream(imgs[0].device).cuda_stream)
+    src = (RgbaSurface * len(imgs))(*[_signed_surface(i) for i in imgs])
+    dst = (RgbaSurface * len(outs))(*[_signed_surface(o) for o in outs])
+    if lib().itwQuantizeNormalMapChain(C.cast(src, C.c_void_p), tb, C.cast(dst, C.c_void_p), len(imgs), ops) != 0:
+        raise ValueError("itwQuantizeNormalMapChain refused the call: " + (last_error() or "bad arguments"))
+    return outs[0] if single else outs
+
+
+def compress_normal_map_snorm(img, flip_x=False, flip_y=False, normalize=False, ops=None, out=None):
+    """itwCompressNormalMapBC5S: BC5_SNORM of a signed normal source -- (H, W, 4) int8, float16 / 2-byte half bits, or float32 -- with the
+    flips, the fp32 normalise and the quantisation applied in the encoder's load (one kernel; `img` is not modified).  CUDA torch tensor:
+    asynchronous on torch's current stream, returns a CUDA uint8 tensor; host numpy array: synchronous, returns a numpy array.  Same bytes
+    as compress("bc5_snorm", quantize_normal_map(img, ...))."""
+    ops = normal_ops(flip_x, flip_y, normalize) if ops is None else int(ops)
+    tb = _signed_texel_bytes(img)
+    h, w = img.shape[:2]
+    nbytes = block_count("bc5", w, h) * 16
+    surface = _signed_surface(img)
+    if hasattr(img, "data_ptr"):
+        import torch
+        assert img.is_cuda
+        if out is None:
+            out = torch.empty(nbytes, dtype=torch.uint8, device=img.device)
+        assert out.is_cuda and out.numel() >= nbytes and out.is_contiguous()
+        with torch.cuda.device(img.device):
+            lib().itwSetStream(torch.cuda.current_stream(img.device).cuda_stream)
+            lib().itwCompressNormalMapBC5S(C.byref(surface), tb, out.data_ptr(), ops)
+        return out
+    import numpy as np
+    if out is None:
+        out = np.empty(nbytes, dtype=np.uint8)
+    lib().itwCompressNormalMapBC5S(C.byref(surface), tb, out.ctypes.data, ops)
+    return out
+
+
+def compress_chain_normal_snorm(fmt, images, flip_x=False, flip_y=False, normalize=False, ops=None, progress=None, out=None):
+    """itwCompressSignedNormalMapChain: a whole mip chain / cube map of signed normal sources -- (H, W, 4) numpy arrays or CUDA torch tensors
+    of one dtype: int8, float16 / 2-byte half bits, or float32 -- to "bc4_snorm" or "bc5_snorm" in one call, every texel quantised as the
+    chain's gather copies it.  Returns (ok, blocks) as compress_chain: same bytes as compress_chain(fmt, quantize_normal_map(images, ...))."""
+    assert fmt in SIGNED_FORMATS, fmt
+    images = list(images)
+    ops = normal_ops(flip_x, flip_y, normalize) if ops is None else int(ops)
+    tb = _signed_texel_bytes(images[0])
+    assert all(_signed_texel_bytes(i) == tb for i in images), "one texel kind per call"
+    nbytes = sum(block_count(fmt, i.shape[1], i.shape[0]) for i in images) * BYTES_PER_BLOCK[fmt]
+    on_device = hasattr(images[0], "data_ptr")
+    if out is None:
+        if on_device:
+            import torch
+            out = torch.zeros(nbytes, dtype=torch.uint8, device=images[0].device)
+        else:
+            import numpy as np
+            out = np.zeros(nbytes, dtype=np.uint8)
+    if on_device or hasattr(out, "data_ptr"):
+        import torch
+        lib().itwSetStream(torch.cuda.current_stream(images[0].device if on_device else out.device).cuda_stream)
+    dst = out.data_ptr() if hasattr(out, "data_ptr") else out.ctypes.data
+    arr = (RgbaSurface * len(images))(*[_signed_surface(i) for i in images])
+    cb = PROGRESS_FUNC(progress) if progress else None
+    ok = lib().itwCompressSignedNormalMapChain(C.cast(arr, C.c_void_p), len(images), tb, dst, DXGI_FORMAT[fmt], ops, C.cast(cb, C.c_void_p) if cb else None, None)
+    return bool(ok), out
+
+
+def compress_mipped_normal_snorm(fmt, base_or_bases, levels=0, flip_x=False, flip_y=False, normalize=False, ops=None, progress=None, out=None):
+    """itwCompressSignedNormalMapMipped: the signed normal-map save path from base images in one call -- one signed normal source or a list of
+    equally sized ones (int8, float16 / 2-byte half bits, or float32) widened to RGBA16F with the flips, the mip chain, then
+    compress_chain_normal_snorm with the normalise in fp32 on every level.  fmt "bc4_snorm" or "bc5_snorm"; levels == 0: the full chain.
+    Returns (ok, blocks): the DDS payload, item-major then level."""
+    assert fmt in SIGNED_FORMATS, fmt
+    single = hasattr(base_or_bases, "shape")
+    bases = [base_or_bases] if single else list(base_or_bases)
+    ops = normal_ops(flip_x, flip_y, normalize) if ops is None else int(ops)
+    tb = _signed_texel_bytes(bases[0])
+    assert all(_signed_texel_bytes(b) == tb for b in bases), "one texel kind per call"
+    h, w = bases[0].shape[:2]
+    n = levels or mip_levels(w, h)
+    nbytes = len(bases) * sum(block_count(fmt, max(1, w >> l), max(1, h >> l)) for l in range(n)) * BYTES_PER_BLOCK[fmt]
+    on_device = hasattr(bases[0], "data_ptr")
+    if out is None:
+        if on_device:
+            import torch
+            out = torch.zeros(nbytes, dtype=torch.uint8, device=bases[0].device)
+        else:
+            import numpy as np
+            out = np.zeros(nbytes, dtype=np.uint8)
+    if on_device or hasattr(out, "data_ptr"):
+        import torch
+        lib().itwSetStream(torch.cuda.current_stream(bases[0].device if on_device else out.device).cuda_stream)
+    dst = out.data_ptr() if hasattr(out, "data_ptr") else out.ctypes.data
+    arr = (RgbaSurface * len(bases))(*[_signed_surface(b) for b in bases])
+    cb = PROGRESS_FUNC(progress) if progress else None
+    ok = lib().itwCompressSignedNormalMapMipped(C.cast(arr, C.c_void_p), len(bases), levels, tb, ops, dst, DXGI_FORMAT[fmt],
+                                                C.cast(cb, C.c_void_p) if cb else None, None)
+    return bool(ok), out
 
 
 def cube_cross_faces(img):
