@@ -3,7 +3,7 @@
 // the program links libispc_texcomp.so like the plugin links ispc_texcomp.lib.
 //
 //   encode_dds [--measure] [--refine <profile> <max_block_sse> | --refine-share <profile> <percent> | --refine-psnr <profile> <dB>]
-//              [--normal flipx,flipy,normalize | --signed-normal int8|half|float[,flipx,flipy,normalize]] [--cube-cross] [--mips [levels]]
+//              [--normal flipx,flipy,normalize | --signed-normal int8|half|float[,flipx,flipy,normalize]] [--cube-cross] [--mips [levels] [--srgb-mips]]
 //              <format> <width> <height> <in.raw> <out.dds> [slice_pixels]
 //     format : bc1 | bc3 | bc4 | bc5 | bc4_snorm | bc5_snorm | bc7_<profile> | bc6h_<profile> | etc1_slow      (profiles: the GetProfile_* names)
 //              etc1_slow: DDS has no code for ETC1, so the output is a KTX 1.1 file (itwKtx*, itw_dds.h); the slices go through itwCompressImageSlicedEx
@@ -32,6 +32,8 @@
 //                 order -- the flips of --normal on level 0, DirectXTex's box / linear mip filter, the normalise on every level, every image
 //                 encoded.  levels: how many, the base included (default: the full chain).  Every format; goes with --normal and
 //                 --cube-cross; not with --refine* or --measure.  The header carries the image's own size: level l is max(1, w >> l) wide.
+//     --srgb-mips : with --mips: the texels' R, G, B are sRGB coded and every level is filtered in linear light (itwCompressImageMippedEx with
+//                 ITW_MIP_SRGB; alpha stays linear).  RGBA8 colour formats only: not with bc6h_*, the SNORM pair or --normal.
 //
 //   encode_dds --decode <in.dds | in.ktx> <out.raw>
 //     (.dds or .ktx: told apart by the file's first bytes; a KTX file's images come in ITS order, level then face)
@@ -168,7 +170,7 @@ int encode_normal_or_cross(const Format& f, const rgba_surface& source, uint32_t
 }
 
 // encode_dds --mips: the base image (or its six cross faces) to a mipped DDS / KTX in one call; levels == 0: the full chain
-int encode_mipped(const Format& f, const rgba_surface& source, uint32_t ops, bool cube_cross, int levels, const char* out_path)
+int encode_mipped(const Format& f, const rgba_surface& source, uint32_t ops, uint32_t mip_flags, bool cube_cross, int levels, const char* out_path)
 {
     const bool bc7 = std::strncmp(f.name, "bc7_", 4) == 0, bc6h = std::strncmp(f.name, "bc6h_", 5) == 0, etc1 = f.dxgi == ITW_FORMAT_ETC1_RGB8;
     union { bc7_enc_settings s7; bc6h_enc_settings s6; etc_enc_settings se; } settings;
@@ -189,7 +191,7 @@ int encode_mipped(const Format& f, const rgba_surface& source, uint32_t ops, boo
     if (bytes <= 0) { std::fprintf(stderr, "bad size\n"); return 2; }
     std::vector<uint8_t> blocks((size_t)bytes);
     itwSetErrorMode(ITW_ON_ERROR_RETURN);
-    if (!itwCompressImageMipped(bases, items, levels, ops, blocks.data(), f.dxgi, &settings, nullptr, nullptr)) {
+    if (!itwCompressImageMippedEx(bases, items, levels, ops, mip_flags, blocks.data(), f.dxgi, &settings, nullptr, nullptr)) {
         std::fprintf(stderr, "%s\n", itwLastError() ? itwLastError() : "compression failed");
         return 1;
     }
@@ -368,7 +370,7 @@ int main(int argc, char** argv)
     double refine_value = 0.0;                                  // percent / dB
     bool normal_given = false, cube_cross = false;
     uint32_t normal_ops = 0;                                    // ITW_NORMAL_*
-    bool mips = false;
+    bool mips = false, srgb_mips = false;
     int mip_levels = 0;                                         // 0: the full chain
     int signed_tb = 0;                                          // --signed-normal: texel bytes of the signed source (4, 8 or 16)
     for (int i = 1; i < argc; i++)
@@ -424,10 +426,14 @@ int main(int argc, char** argv)
             const int used = count ? 2 : 1;
             for (int k = i; k + used < argc; k++) argv[k] = argv[k + used];
             argc -= used; i--;
+        } else if (std::strcmp(argv[i], "--srgb-mips") == 0) {
+            srgb_mips = true;
+            for (int k = i; k + 1 < argc; k++) argv[k] = argv[k + 1];
+            argc--; i--;
         }
     if (argc < 6) {
         std::fprintf(stderr, "usage: %s [--measure] [--refine <profile> <max_block_sse> | --refine-share <profile> <percent> | --refine-psnr <profile> <dB>]\n"
-                             "          [--normal flipx,flipy,normalize | --signed-normal int8|half|float[,flipx,flipy,normalize]] [--cube-cross] [--mips [levels]]\n"
+                             "          [--normal flipx,flipy,normalize | --signed-normal int8|half|float[,flipx,flipy,normalize]] [--cube-cross] [--mips [levels] [--srgb-mips]]\n"
                              "          <format> <width> <height> <in.raw> <out.dds> [slice_pixels]\n"
                              "       %s --decode <in.dds | in.ktx> <out.raw>\n"
                              "       %s --preview <in.dds | in.ktx> <image index> <out.ppm> <w> <h> <x> <y> <zoom> [channels] [exposure] [matte]\n", argv[0], argv[0], argv[0]);
@@ -443,6 +449,7 @@ int main(int argc, char** argv)
         std::fprintf(stderr, "--signed-normal is for bc4_snorm / bc5_snorm and does not go with --normal, --refine* or --measure\n");
         return 2;
     }
+    if (srgb_mips && (!mips || signed_tb)) { std::fprintf(stderr, "--srgb-mips goes with --mips, and not with --signed-normal\n"); return 2; }
     const int texel_bytes = signed_tb ? signed_tb : f->texel_bytes;
     std::vector<uint8_t> texels((size_t)width * height * texel_bytes);
     FILE* in = std::fopen(argv[4], "rb");
@@ -456,7 +463,7 @@ int main(int argc, char** argv)
             std::fprintf(stderr, "--mips does not go with --refine* or --measure; --cube-cross not with etc1_slow\n");
             return 2;
         }
-        return encode_mipped(*f, source, normal_ops, cube_cross, mip_levels, argv[5]);
+        return encode_mipped(*f, source, normal_ops, srgb_mips ? (uint32_t)ITW_MIP_SRGB : 0u, cube_cross, mip_levels, argv[5]);
     }
     if (normal_given || cube_cross) {
         // the normal-map and cube-cross stages of the save path (IntelPlugin.cpp:2075-2106, 2149-2152): one call over the image or its six faces

@@ -414,6 +414,19 @@ int itwCubeCrossFaces(const rgba_surface* cross, int pixel_size, rgba_surface fa
  *           Fant scaler, and DirectXMath's XMStoreUByteN4 is not part of its tree.  The same two filters on the raw codes as fp32 values
  *           0..255 (no division by 255), stored as (uint8_t)min(v + 0.5f, 255.0f); for the box that is exactly (a + b + c + d + 2) >> 2.
  *           The bytes of an RGBA8_SNORM surface are treated as codes like any other.
+ *   RGBA8 with sRGB colour (ITW_MIP_SRGB) -- THE LIBRARY'S OWN RULE as well: the reference never passes TEX_FILTER_SRGB, and DirectXMath's
+ *           XMColorSRGBToRGB is not part of its tree.  Without the flag an sRGB texture's codes are averaged as if they were light (a 0 / 255
+ *           checkerboard gives 128 where linear light gives 188); the format code is never read as a request, the flag alone is.
+ *           R, G, B are sRGB coded; A is linear and keeps the RGBA8 rule above exactly.  With f(x) = x / 12.92 for x <= 0.04045, else
+ *           ((x + 0.055) / 1.055)^2.4 (IEC 61966-2-1):
+ *             decode  D[c], c = 0..255, the fp32 nearest to f(c / 255);
+ *             encode  E(v) = the number of k in 1..255 with v >= T[k], T[k] the fp32 nearest to f((k - 0.5) / 255): the nearest code in
+ *                     the encoded domain; a value equal to a threshold goes up; values above 1 (the linear filter's weights can produce
+ *                     them by an ulp) give 255; -0 and 0 give 0.
+ *           The same two filters, unchanged in order and rounding, run on D[code] for R, G, B and the result is stored as E(v); level l is
+ *           filtered from level l-1 as stored, as always.  T is strictly increasing and every constant image keeps its code at every
+ *           level.  Both tables are csrc/srgb_tables.h, generated by tools/gen_srgb_tables.py with `decimal` at 60 digits;
+ *           itwSrgbToLinear(c) is D[c] and itwLinearToSrgb(v) is E(v), on the host, over those tables.
  * Stated divergence.  The reference's box filter sets urow2 / urow3 once before its level loop (:740-741) and, once the height has reached 1,
  * re-points only urow1 (:746-749): from the level where the height is 1 while the width is still above 1, urow3 reads the second scanline
  * of an EARLIER level, which is no longer loaded (for a base of height 1: uninitialised storage).  Square and tall chains -- cube faces
@@ -430,8 +443,11 @@ int itwCubeCrossFaces(const rgba_surface* cross, int pixel_size, rgba_surface fa
  * buffer -- only the bases go up, only the written levels come back -- and the call returns synchronised.  Power-of-two chains take the
  * pyramid route: a 64 x 64 tile of a level gives its part of the next six levels in one launch, a last launch takes a level of at most
  * 64 x 64 down to 1 x 1 (a 4096^2 chain: two launches); ITW_MIP_PER_LEVEL forces one launch per level, as every other chain takes, for
- * comparison and measurement.  Both routes write the same bytes.  Returns 0, also for items == 0 or levels <= 1 (nothing to do); -1,
- * through the library's error mode and before any device work, for a pixel_size other than 4 or 8, an unknown flag bit, items < 0, a
+ * comparison and measurement.  Both routes write the same bytes.  ITW_MIP_SRGB (pixel_size 4 only) selects the sRGB colour kind above; it
+ * combines with ITW_MIP_PER_LEVEL, takes the same routes and launches, and both routes write the same bytes.  Flag value 2 is unassigned and
+ * refused like any unknown bit.  Returns 0, also for items == 0 or levels <= 1 (nothing to do); -1,
+ * through the library's error mode and before any device work, for a pixel_size other than 4 or 8, an unknown flag bit, ITW_MIP_SRGB with
+ * pixel_size 8, items < 0, a
  * null pointer, a level whose size is not the definition's, items whose bases differ in size, levels above the full chain, a stride
  * below the row's bytes, texels that are not pixel_size aligned, mixed host and device pointers, or more than one launch covers (more
  * than 65 535 items, a base of more than 524 280 rows, more than 2^31 - 1 tiles of 64 x 64 over all items).
@@ -442,13 +458,22 @@ int itwCubeCrossFaces(const rgba_surface* cross, int pixel_size, rgba_surface fa
  * it (items * levels images in DDS order; itwChainBytes / itwDdsFileBytes give the size).  The bases are never written.  Formats, texel
  * kinds, settings, progress contract (1 .. items * levels), pointer kinds of `target`, errors and return value are the chain call's; on
  * top of them unknown ops bits, bases of different sizes, levels < 0 or above the full chain, misaligned texels, mixed pointer kinds
- * and itwGenerateMipChain's launch limits fail through the error mode before any device work.  From host bases only the bases go up and only blocks come down. */
-enum { ITW_MIP_PER_LEVEL = 1 };
+ * and itwGenerateMipChain's launch limits fail through the error mode before any device work.  From host bases only the bases go up and only blocks come down.
+ * itwCompressImageMippedEx: the same with `mip_flags` (ITW_MIP_*) handed to the chain's generation; itwCompressImageMipped is this call with
+ * mip_flags == 0, byte for byte.  With ITW_MIP_SRGB the colour of every level is filtered in linear light, whatever `dxgi_format` says --
+ * 72 / 78 / 99 without the flag keep the plain rule's bytes.  Unknown flag bits, and ITW_MIP_SRGB with an RGBA16F format (95 / 96), a signed
+ * format (81 / 84) or normal_ops != 0 (a normal map is not colour), fail through the error mode before any device work.
+ * itwSrgbToLinear, itwLinearToSrgb: D[code] and E(v) of the sRGB colour kind; host arithmetic only. */
+enum { ITW_MIP_PER_LEVEL = 1, ITW_MIP_SRGB = 4 };
 int itwMipLevels(int width, int height);
 int64_t itwMipChainLayout(int width, int height, int items, int levels, int pixel_size, uint8_t* storage, rgba_surface* out);
 int itwGenerateMipChain(const rgba_surface* images, int items, int levels, int pixel_size, uint32_t flags);
 bool itwCompressImageMipped(const rgba_surface* bases, int items, int levels, uint32_t normal_ops, uint8_t* target, int dxgi_format,
                             const void* settings, ItwProgressFunc* progress, void* user);
+bool itwCompressImageMippedEx(const rgba_surface* bases, int items, int levels, uint32_t normal_ops, uint32_t mip_flags, uint8_t* target,
+                              int dxgi_format, const void* settings, ItwProgressFunc* progress, void* user);
+float itwSrgbToLinear(uint8_t code);
+uint8_t itwLinearToSrgb(float v);
 
 #pragma GCC visibility pop
 #ifdef __cplusplus

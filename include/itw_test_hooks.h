@@ -93,6 +93,11 @@ enum itw_test_bc7_call_counter {
 void itwTestBc7CallCountersArm(int on);
 void itwTestBc7CallCounters(int32_t* out, int n);
 
+/* The sRGB mip filter's encode on the device (csrc/mipgen.hpp mip_srgb_encode, the function the mip kernels store R, G, B with under
+ * ITW_MIP_SRGB): d_out[i] = E(d_in[i]) for `n` floats resident in device memory, on the calling thread's stream.
+ * tests/test_gpu_srgb_mips.py compares it with the counting definition of include/itw_dispatch.h around every threshold. */
+void itwTestSrgbEncode(const float* d_in, uint8_t* d_out, int64_t n);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

@@ -14,12 +14,19 @@
 //                       comparison route of the box filter (ITW_MIP_PER_LEVEL), and the bridge of a power-of-two chain whose levels are
 //                       neither tileable (an axis below 64) nor small enough for the tail (the other above 64), e.g. 512 x 2.
 // A 4096^2 chain is two launches (4096 -> 64 over 4096 tiles, 64 -> 1 over one) where the per-level route takes twelve.
+// Every kernel is a template over the texel kind: RGBA8, RGBA16F, and RGBA8 with sRGB colour (ITW_MIP_SRGB; SRGB = true), whose workgroups
+// hold the two tables of mipgen.hpp in 2 KiB of LDS -- 256 lanes load them with two coalesced dwords each -- and otherwise take the same
+// routes, launches and LDS layouts; the levels kept in registers and LDS between the steps are the stored codes' widened values, as for the others.
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdint>
+#include <cstring>
 #include <vector>
 #include "../../include/itw_dispatch.h"
 #include "../../include/itw_amd.h"
+#ifdef ITW_TEST_HOOKS
+#include "../../include/itw_test_hooks.h"
+#endif
 #include "mipgen.hpp"
 #include "normal_prep.hpp"
 #include "bcn_format.hpp"
@@ -31,8 +38,8 @@ namespace itw {
 struct MipImage { uint8_t* ptr; int64_t stride; };
 
 // N consecutive texels at `p` (PX aligned): one vector access where the address allows, texel by texel otherwise
-template <int PX, int N>
-__device__ __forceinline__ void mip_load_row(const uint8_t* p, MipTexel* t)
+template <int PX, bool SRGB, int N>
+__device__ __forceinline__ void mip_load_row(const uint8_t* p, MipTexel* t, const MipSrgbTables* srgb)
 {
     constexpr int W = N * PX / 4;
     uint32_t w[W];
@@ -51,16 +58,16 @@ __device__ __forceinline__ void mip_load_row(const uint8_t* p, MipTexel* t)
     }
 #pragma unroll
     for (int i = 0; i < N; i++) {
-        if constexpr (PX == 4) t[i] = mip_widen<4>(w[i], 0u);
+        if constexpr (PX == 4) t[i] = mip_widen<4, SRGB>(w[i], 0u, srgb);
         else                   t[i] = mip_widen<8>(w[2 * i], w[2 * i + 1]);
     }
 }
 
-template <int PX>
-__device__ __forceinline__ MipTexel mip_load(const uint8_t* p)
+template <int PX, bool SRGB>
+__device__ __forceinline__ MipTexel mip_load(const uint8_t* p, const MipSrgbTables* srgb)
 {
     MipTexel t;
-    mip_load_row<PX, 1>(p, &t);
+    mip_load_row<PX, SRGB, 1>(p, &t, srgb);
     return t;
 }
 
@@ -73,12 +80,12 @@ __device__ __forceinline__ void mip_store_words(uint8_t* p, uint32_t lo, uint32_
 }
 
 // rounds N (1 or 2) consecutive texels to the format and stores them at `p`; `t` becomes the stored values widened
-template <int PX, int N>
-__device__ __forceinline__ void mip_store_row(uint8_t* p, MipTexel* t)
+template <int PX, bool SRGB, int N>
+__device__ __forceinline__ void mip_store_row(uint8_t* p, MipTexel* t, const MipSrgbTables* srgb)
 {
     uint32_t lo[N], hi[N];
 #pragma unroll
-    for (int i = 0; i < N; i++) mip_round<PX>(t[i], lo[i], hi[i]);
+    for (int i = 0; i < N; i++) mip_round<PX, SRGB>(t[i], lo[i], hi[i], srgb);
     if constexpr (N == 2) {
         if (PX == 8 && ((uintptr_t)p & 15) == 0) { *reinterpret_cast<uint4*>(p) = make_uint4(lo[0], hi[0], lo[1], hi[1]); return; }
         if (PX == 4 && ((uintptr_t)p & 7) == 0)  { *reinterpret_cast<uint2*>(p) = make_uint2(lo[0], lo[1]); return; }
@@ -87,14 +94,29 @@ __device__ __forceinline__ void mip_store_row(uint8_t* p, MipTexel* t)
     for (int i = 0; i < N; i++) mip_store_words<PX>(p + i * PX, lo[i], hi[i]);
 }
 
+// The workgroup's sRGB tables (mipgen.hpp), 2 KiB of LDS beside what the kernel holds there; nothing, and a null pointer, for the other kinds.
+// Every lane of the 256 calls it once, before any lane leaves: it ends with a barrier.
+template <bool SRGB>
+__device__ __forceinline__ const MipSrgbTables* mip_srgb_tables()
+{
+    if constexpr (SRGB) {
+        __shared__ MipSrgbTables tables;
+        mip_srgb_fill(&tables);
+        return &tables;
+    } else {
+        return nullptr;
+    }
+}
+
 // LDS regions of the pyramid kernel, in widened texels: level +2 (16 x 16), +3 (8 x 8), +4 (4 x 4), +5 (2 x 2)
 constexpr int kPyrLds = 256 + 64 + 16 + 4;
 
-template <int PX>
+template <int PX, bool SRGB>
 __global__ void __launch_bounds__(256)
 mip_pyramid_kernel(const MipImage* __restrict__ table, int32_t levels, int32_t src_level, int32_t nout, int32_t tiles_x, int32_t tiles_per_item)
 {
     __shared__ MipTexel lds[kPyrLds];
+    const MipSrgbTables* srgb = mip_srgb_tables<SRGB>();
     const int32_t item = (int32_t)(blockIdx.x / (uint32_t)tiles_per_item);
     const int32_t tile = (int32_t)(blockIdx.x - (uint32_t)item * (uint32_t)tiles_per_item);
     const int32_t ty = tile / tiles_x, tx = tile - ty * tiles_x;
@@ -106,7 +128,7 @@ mip_pyramid_kernel(const MipImage* __restrict__ table, int32_t levels, int32_t s
         const MipImage s = im[0];
         const uint8_t* src = s.ptr + (int64_t)(ty * 64 + ly * 4) * s.stride + (int64_t)(tx * 64 + lx * 4) * PX;
 #pragma unroll
-        for (int r = 0; r < 4; r++) mip_load_row<PX, 4>(src + r * s.stride, p[r]);
+        for (int r = 0; r < 4; r++) mip_load_row<PX, SRGB, 4>(src + r * s.stride, p[r], srgb);
     }
     MipTexel q[2][2];
     {
@@ -116,14 +138,14 @@ mip_pyramid_kernel(const MipImage* __restrict__ table, int32_t levels, int32_t s
         for (int j = 0; j < 2; j++) {
 #pragma unroll
             for (int i = 0; i < 2; i++) q[j][i] = mip_box(p[2 * j][2 * i], p[2 * j + 1][2 * i], p[2 * j][2 * i + 1], p[2 * j + 1][2 * i + 1]);
-            mip_store_row<PX, 2>(dst + j * d.stride, q[j]);
+            mip_store_row<PX, SRGB, 2>(dst + j * d.stride, q[j], srgb);
         }
     }
     if (nout < 2) return;                                                 // (nout is the launch's: every lane leaves together)
     {
         MipTexel t = mip_box(q[0][0], q[1][0], q[0][1], q[1][1]);
         const MipImage d = im[2];
-        mip_store_row<PX, 1>(d.ptr + (int64_t)(ty * 16 + ly) * d.stride + (int64_t)(tx * 16 + lx) * PX, &t);
+        mip_store_row<PX, SRGB, 1>(d.ptr + (int64_t)(ty * 16 + ly) * d.stride + (int64_t)(tx * 16 + lx) * PX, &t, srgb);
         lds[ly * 16 + lx] = t;
     }
     int32_t from = 0, to = 256;                                           // region offsets: the level read, the level written
@@ -137,7 +159,7 @@ mip_pyramid_kernel(const MipImage* __restrict__ table, int32_t levels, int32_t s
             const MipTexel* s = lds + from + (2 * y) * (2 * n) + 2 * x;
             MipTexel t = mip_box(s[0], s[2 * n], s[1], s[2 * n + 1]);
             const MipImage d = im[k];
-            mip_store_row<PX, 1>(d.ptr + (int64_t)(ty * n + y) * d.stride + (int64_t)(tx * n + x) * PX, &t);
+            mip_store_row<PX, SRGB, 1>(d.ptr + (int64_t)(ty * n + y) * d.stride + (int64_t)(tx * n + x) * PX, &t, srgb);
             if (k < 6) lds[to + y * n + x] = t;
         }
         from = to; to += n * n;
@@ -147,11 +169,12 @@ mip_pyramid_kernel(const MipImage* __restrict__ table, int32_t levels, int32_t s
 // source level `src_level` of w x h, powers of two, at most 64 x 32 or 32 x 64 (launch_chain gives 64 x 64 to the pyramid kernel); one
 // workgroup per item, `nout` levels down.  Levels live in LDS as stored words: odd ones (+1 <= 512 texels, +3, +5) in buf_a, even ones
 // (+2 <= 128 texels, +4, +6) in buf_b; the barrier that ends a level also ends the reads of the buffer the next level overwrites.
-template <int PX>
+template <int PX, bool SRGB>
 __global__ void __launch_bounds__(256)
 mip_tail_kernel(const MipImage* __restrict__ table, int32_t levels, int32_t src_level, int32_t nout, int32_t w, int32_t h)
 {
     __shared__ uint2 buf_a[512], buf_b[128];
+    const MipSrgbTables* srgb = mip_srgb_tables<SRGB>();
     const MipImage* im = table + (int64_t)blockIdx.x * levels + src_level;
     int32_t sw = w, sh = h;
     for (int k = 1; k <= nout; k++) {
@@ -165,15 +188,16 @@ mip_tail_kernel(const MipImage* __restrict__ table, int32_t levels, int32_t src_
             MipTexel p0, p1, p2, p3;
             if (k == 1) {
                 const uint8_t* r0 = s.ptr + y0 * s.stride, * r1 = s.ptr + y1 * s.stride;
-                p0 = mip_load<PX>(r0 + (int64_t)x0 * PX); p1 = mip_load<PX>(r1 + (int64_t)x0 * PX);
-                p2 = mip_load<PX>(r0 + (int64_t)x1 * PX); p3 = mip_load<PX>(r1 + (int64_t)x1 * PX);
+                p0 = mip_load<PX, SRGB>(r0 + (int64_t)x0 * PX, srgb); p1 = mip_load<PX, SRGB>(r1 + (int64_t)x0 * PX, srgb);
+                p2 = mip_load<PX, SRGB>(r0 + (int64_t)x1 * PX, srgb); p3 = mip_load<PX, SRGB>(r1 + (int64_t)x1 * PX, srgb);
             } else {
                 const uint2 a = sl[y0 * sw + x0], b = sl[y1 * sw + x0], c = sl[y0 * sw + x1], e = sl[y1 * sw + x1];
-                p0 = mip_widen<PX>(a.x, a.y); p1 = mip_widen<PX>(b.x, b.y); p2 = mip_widen<PX>(c.x, c.y); p3 = mip_widen<PX>(e.x, e.y);
+                p0 = mip_widen<PX, SRGB>(a.x, a.y, srgb); p1 = mip_widen<PX, SRGB>(b.x, b.y, srgb);
+                p2 = mip_widen<PX, SRGB>(c.x, c.y, srgb); p3 = mip_widen<PX, SRGB>(e.x, e.y, srgb);
             }
             MipTexel t = mip_box(p0, p1, p2, p3);
             uint32_t lo, hi;
-            mip_round<PX>(t, lo, hi);
+            mip_round<PX, SRGB>(t, lo, hi, srgb);
             mip_store_words<PX>(d.ptr + y * d.stride + (int64_t)x * PX, lo, hi);
             dl[idx] = make_uint2(lo, hi);
         }
@@ -183,11 +207,12 @@ mip_tail_kernel(const MipImage* __restrict__ table, int32_t levels, int32_t src_
 }
 
 // level `dst_level` (ow x oh) of every item from its level dst_level - 1 (sw x sh); lanes 64 across, 4 down; grid (x tiles, y tiles, items)
-template <int PX, bool LINEAR>
+template <int PX, bool LINEAR, bool SRGB>
 __global__ void __launch_bounds__(256)
 mip_level_kernel(const MipImage* __restrict__ table, int32_t levels, int32_t dst_level, int32_t sw, int32_t sh, int32_t ow, int32_t oh,
                  float scale_x, float scale_y)
 {
+    const MipSrgbTables* srgb = mip_srgb_tables<SRGB>();
     const int32_t x = (int32_t)blockIdx.x * 64 + (threadIdx.x & 63), y = (int32_t)blockIdx.y * 4 + (threadIdx.x >> 6);
     if (x >= ow || y >= oh) return;
     const MipImage* im = table + (int64_t)blockIdx.z * levels + dst_level;
@@ -196,15 +221,15 @@ mip_level_kernel(const MipImage* __restrict__ table, int32_t levels, int32_t dst
     if (LINEAR) {
         const MipTap tx = mip_linear_tap(x, scale_x, sw), ty = mip_linear_tap(y, scale_y, sh);
         const uint8_t* r0 = s.ptr + (int64_t)ty.u0 * s.stride, * r1 = s.ptr + (int64_t)ty.u1 * s.stride;
-        t = mip_bilinear(mip_load<PX>(r0 + (int64_t)tx.u0 * PX), mip_load<PX>(r0 + (int64_t)tx.u1 * PX),
-                         mip_load<PX>(r1 + (int64_t)tx.u0 * PX), mip_load<PX>(r1 + (int64_t)tx.u1 * PX), tx, ty);
+        t = mip_bilinear(mip_load<PX, SRGB>(r0 + (int64_t)tx.u0 * PX, srgb), mip_load<PX, SRGB>(r0 + (int64_t)tx.u1 * PX, srgb),
+                         mip_load<PX, SRGB>(r1 + (int64_t)tx.u0 * PX, srgb), mip_load<PX, SRGB>(r1 + (int64_t)tx.u1 * PX, srgb), tx, ty);
     } else {
         const int32_t x0 = 2 * x, x1 = sw > 1 ? x0 + 1 : x0, y0 = 2 * y, y1 = sh > 1 ? y0 + 1 : y0;
         const uint8_t* r0 = s.ptr + (int64_t)y0 * s.stride, * r1 = s.ptr + (int64_t)y1 * s.stride;
-        t = mip_box(mip_load<PX>(r0 + (int64_t)x0 * PX), mip_load<PX>(r1 + (int64_t)x0 * PX),
-                    mip_load<PX>(r0 + (int64_t)x1 * PX), mip_load<PX>(r1 + (int64_t)x1 * PX));
+        t = mip_box(mip_load<PX, SRGB>(r0 + (int64_t)x0 * PX, srgb), mip_load<PX, SRGB>(r1 + (int64_t)x0 * PX, srgb),
+                    mip_load<PX, SRGB>(r0 + (int64_t)x1 * PX, srgb), mip_load<PX, SRGB>(r1 + (int64_t)x1 * PX, srgb));
     }
-    mip_store_row<PX, 1>(d.ptr + (int64_t)y * d.stride + (int64_t)x * PX, &t);
+    mip_store_row<PX, SRGB, 1>(d.ptr + (int64_t)y * d.stride + (int64_t)x * PX, &t, srgb);
 }
 
 } // namespace itw
@@ -224,7 +249,7 @@ void check_launch_limits(const char* who, int w, int h, int items)
 }
 
 // the launches of one chain: `table` is on the device, the base is w x h, all `items` alike and within check_launch_limits
-template <int PX>
+template <int PX, bool SRGB>
 void launch_chain(const itw::MipImage* table, int items, int levels, int w, int h, bool per_level, hipStream_t st)
 {
     const bool box = pow2(w) && pow2(h);
@@ -233,17 +258,17 @@ void launch_chain(const itw::MipImage* table, int items, int levels, int w, int 
         const int sw = mip_dim(w, cur), sh = mip_dim(h, cur);
         if (box && !per_level && sw >= 64 && sh >= 64) {
             const int nout = std::min(6, levels - 1 - cur), tiles_x = sw / 64, tiles = tiles_x * (sh / 64);
-            hipLaunchKernelGGL((itw::mip_pyramid_kernel<PX>), dim3((unsigned)(tiles * items)), dim3(256), 0, st, table, levels, cur, nout, tiles_x, tiles);
+            hipLaunchKernelGGL((itw::mip_pyramid_kernel<PX, SRGB>), dim3((unsigned)(tiles * items)), dim3(256), 0, st, table, levels, cur, nout, tiles_x, tiles);
             cur += nout;
         } else if (box && !per_level && sw <= 64 && sh <= 64) {       // (not both 64: that was a tile)
-            hipLaunchKernelGGL((itw::mip_tail_kernel<PX>), dim3((unsigned)items), dim3(256), 0, st, table, levels, cur, levels - 1 - cur, sw, sh);
+            hipLaunchKernelGGL((itw::mip_tail_kernel<PX, SRGB>), dim3((unsigned)items), dim3(256), 0, st, table, levels, cur, levels - 1 - cur, sw, sh);
             cur = levels - 1;
         } else {
             const int ow = mip_dim(w, cur + 1), oh = mip_dim(h, cur + 1);
             const dim3 grid((unsigned)((ow + 63) / 64), (unsigned)((oh + 3) / 4), (unsigned)items);
             const float scale_x = (float)sw / (float)ow, scale_y = (float)sh / (float)oh;
-            if (box) hipLaunchKernelGGL((itw::mip_level_kernel<PX, false>), grid, dim3(256), 0, st, table, levels, cur + 1, sw, sh, ow, oh, scale_x, scale_y);
-            else     hipLaunchKernelGGL((itw::mip_level_kernel<PX, true>), grid, dim3(256), 0, st, table, levels, cur + 1, sw, sh, ow, oh, scale_x, scale_y);
+            if (box) hipLaunchKernelGGL((itw::mip_level_kernel<PX, false, SRGB>), grid, dim3(256), 0, st, table, levels, cur + 1, sw, sh, ow, oh, scale_x, scale_y);
+            else     hipLaunchKernelGGL((itw::mip_level_kernel<PX, true, SRGB>), grid, dim3(256), 0, st, table, levels, cur + 1, sw, sh, ow, oh, scale_x, scale_y);
             cur += 1;
         }
         ITW_CHECK(hipGetLastError());
@@ -253,7 +278,7 @@ void launch_chain(const itw::MipImage* table, int items, int levels, int w, int 
 size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // everything that needs the device: a chain that passed the checks, all of one pointer kind, levels >= 2
-void generate_chain(const rgba_surface* im, int items, int levels, int px, bool per_level, bool dev)
+void generate_chain(const rgba_surface* im, int items, int levels, int px, bool srgb, bool per_level, bool dev)
 {
     hipStream_t st = (hipStream_t)itwGetStream();
     const int count = items * levels;
@@ -280,8 +305,9 @@ void generate_chain(const rgba_surface* im, int items, int levels, int px, bool 
         }
     ITW_CHECK(hipMemcpyAsync(base, desc.data(), (size_t)count * sizeof(itw::MipImage), hipMemcpyHostToDevice, st));
     const itw::MipImage* table = reinterpret_cast<const itw::MipImage*>(base);
-    if (px == 4) launch_chain<4>(table, items, levels, im[0].width, im[0].height, per_level, st);
-    else         launch_chain<8>(table, items, levels, im[0].width, im[0].height, per_level, st);
+    if (srgb)         launch_chain<4, true>(table, items, levels, im[0].width, im[0].height, per_level, st);     // (the entry point refused it with px 8)
+    else if (px == 4) launch_chain<4, false>(table, items, levels, im[0].width, im[0].height, per_level, st);
+    else              launch_chain<8, false>(table, items, levels, im[0].width, im[0].height, per_level, st);
     if (dev) { itw::decode_scratch_done(st); return; }                    // resident: asynchronous on the thread's stream
     for (int i = 0; i < count; i++)                                       // only the written levels come back, width x height only
         if (i % levels != 0)
@@ -397,7 +423,8 @@ extern "C" int itwGenerateMipChain(const rgba_surface* images, int items, int le
     itw::clear_failure();
     const bool ok = itw::guarded([&] {
         if (pixel_size != 4 && pixel_size != 8) itw::fail_msg("itwGenerateMipChain: pixel_size %d (4: RGBA8, 8: RGBA16F)", pixel_size);
-        if (flags & ~(uint32_t)ITW_MIP_PER_LEVEL) itw::fail_msg("itwGenerateMipChain: unknown flag bits 0x%x", flags);
+        if (flags & ~(uint32_t)(ITW_MIP_PER_LEVEL | ITW_MIP_SRGB)) itw::fail_msg("itwGenerateMipChain: unknown flag bits 0x%x", flags);
+        if ((flags & ITW_MIP_SRGB) && pixel_size != 4) itw::fail_msg("itwGenerateMipChain: ITW_MIP_SRGB is for RGBA8 texels (pixel_size 4): RGBA16F is linear already");
         if (items < 0) itw::fail_msg("itwGenerateMipChain: %d items", items);
         if (items == 0 || levels <= 1) return;
         if (!images) itw::fail_msg("itwGenerateMipChain: null images pointer");
@@ -425,20 +452,69 @@ extern "C" int itwGenerateMipChain(const rgba_surface* images, int items, int le
             if (itw::is_device_pointer(images[i].ptr) != dev)
                 itw::fail_msg("itwGenerateMipChain: image %d is %s memory, image 0 %s: all images must be host or all device pointers", i,
                               dev ? "host" : "device", dev ? "device" : "host");
-        generate_chain(images, items, levels, pixel_size, (flags & ITW_MIP_PER_LEVEL) != 0, dev);
+        generate_chain(images, items, levels, pixel_size, (flags & ITW_MIP_SRGB) != 0, (flags & ITW_MIP_PER_LEVEL) != 0, dev);
     });
     return ok ? 0 : -1;
 }
 
-extern "C" bool itwCompressImageMipped(const rgba_surface* bases, int items, int levels, uint32_t normal_ops, uint8_t* target, int dxgi_format,
-                                       const void* settings, ItwProgressFunc* progress, void* user)
+// the sRGB colour kind on the host (include/itw_dispatch.h): the tables of srgb_tables.h, E as the counting definition's binary search
+extern "C" float itwSrgbToLinear(uint8_t code)
+{
+    float v;
+    std::memcpy(&v, &itw::SRGB_DECODE_BITS[code], sizeof v);
+    return v;
+}
+
+extern "C" uint8_t itwLinearToSrgb(float v)
+{
+    uint32_t lo = 0;
+    for (uint32_t step = 128; step >= 1; step >>= 1) {                    // lo + step <= 255
+        float t;
+        std::memcpy(&t, &itw::SRGB_THR_BITS[lo + step], sizeof t);
+        if (v >= t) lo += step;
+    }
+    return (uint8_t)lo;
+}
+
+#ifdef ITW_TEST_HOOKS
+namespace itw {
+__global__ void __launch_bounds__(256)
+mip_srgb_encode_test_kernel(const float* __restrict__ in, uint8_t* __restrict__ out, int64_t n)
+{
+    const MipSrgbTables* srgb = mip_srgb_tables<true>();
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) out[i] = (uint8_t)mip_srgb_encode(in[i], srgb);
+}
+} // namespace itw
+
+extern "C" void itwTestSrgbEncode(const float* d_in, uint8_t* d_out, int64_t n)
+{
+    itw::clear_failure();
+    itw::guarded([&] {
+        if (n <= 0) return;
+        if (!d_in || !d_out) itw::fail_msg("itwTestSrgbEncode: null pointer");
+        if ((n + 255) / 256 > (int64_t)0x7fffffff) itw::fail_msg("itwTestSrgbEncode: %lld values are more than one launch covers", (long long)n);
+        hipLaunchKernelGGL(itw::mip_srgb_encode_test_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)itwGetStream(), d_in, d_out, n);
+        ITW_CHECK(hipGetLastError());
+    });
+}
+#endif
+
+extern "C" bool itwCompressImageMippedEx(const rgba_surface* bases, int items, int levels, uint32_t normal_ops, uint32_t mip_flags, uint8_t* target,
+                                         int dxgi_format, const void* settings, ItwProgressFunc* progress, void* user)
 {
     bool done = false;
     itw::clear_failure();
     const bool ok = itw::guarded([&] {
         if (normal_ops & ~7u) itw::fail_msg("itwCompressImageMipped: unknown ops bits 0x%x", normal_ops);
+        if (mip_flags & ~(uint32_t)(ITW_MIP_PER_LEVEL | ITW_MIP_SRGB)) itw::fail_msg("itwCompressImageMipped: unknown mip flag bits 0x%x", mip_flags);
         itw::chain_check_with(bases, items, target, dxgi_format, settings);       // counts, null pointers, sizes, strides, format, settings
         const int px = itw::texel_bytes(itw::format_kind(dxgi_format));
+        if (mip_flags & ITW_MIP_SRGB) {                                           // colour in RGBA8 codes, or nothing
+            if (px != 4) itw::fail_msg("itwCompressImageMipped: ITW_MIP_SRGB with DXGI format %d, whose texels are RGBA16F: linear already", dxgi_format);
+            if (dxgi_format == 81 || dxgi_format == 84) itw::fail_msg("itwCompressImageMipped: ITW_MIP_SRGB with DXGI format %d, whose texels are signed codes, not colour", dxgi_format);
+            if (normal_ops) itw::fail_msg("itwCompressImageMipped: ITW_MIP_SRGB with normal ops 0x%x: a normal map is not colour", normal_ops);
+        }
         const int w = bases[0].width, h = bases[0].height, full = itwMipLevels(w, h);
         for (int i = 0; i < items; i++) {
             if (bases[i].width != w || bases[i].height != h)
@@ -469,12 +545,18 @@ extern "C" bool itwCompressImageMipped(const rgba_surface* bases, int items, int
         auto stage = [](int rc, const char* what) { if (rc != 0) itw::fail_msg("itwCompressImageMipped: %s failed: %s", what, itwLastError()); };
         // the reference's order (IntelPlugin.cpp:2103-2152): flip level 0, generate the mips, normalise every level, compress every image
         if (normal_ops & 3u) stage(itwPrepareNormalMapChain(level0.data(), items, px, normal_ops & 3u), "the flip");
-        stage(itwGenerateMipChain(chain.data(), items, levels, px, 0), "the mip chain");
+        stage(itwGenerateMipChain(chain.data(), items, levels, px, mip_flags), "the mip chain");
         if (normal_ops & 4u) stage(itwPrepareNormalMapChain(chain.data(), items * levels, px, 4u), "the normalise");
         done = itwCompressImageChainEx(chain.data(), items * levels, target, dxgi_format, settings, progress, user);
         t_chain.release(st);
     });
     return ok && done;
+}
+
+extern "C" bool itwCompressImageMipped(const rgba_surface* bases, int items, int levels, uint32_t normal_ops, uint8_t* target, int dxgi_format,
+                                       const void* settings, ItwProgressFunc* progress, void* user)
+{
+    return itwCompressImageMippedEx(bases, items, levels, normal_ops, 0, target, dxgi_format, settings, progress, user);
 }
 
 // the signed normal-map save path in one call (include/itw_dispatch.h): a composition of the stages, like itwCompressImageMipped

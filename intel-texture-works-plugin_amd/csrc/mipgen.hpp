@@ -1,22 +1,56 @@
 // mipgen.hpp -- the arithmetic of the mip filters (include/itw_dispatch.h, "Mip chains"): one definition behind the pyramid kernels and the
 // per-level kernel of mipgen.hip.  DirectXTex's non-WIC 2D filters (DirectXTexMipmaps.cpp:715-805 box, :809-917 linear; Filters.h:33-39
 // AVERAGE4, :66-106 _CreateLinearFilter and BILINEAR_INTERPOLATE) with the R16G16B16A16_FLOAT scanline store (DirectXTexConvert.cpp:1634-1646).
-// IEEE fp32, one rounding per operation (the library is built with -ffp-contract=off).  All four channels alike.
+// IEEE fp32, one rounding per operation (the library is built with -ffp-contract=off).  All four channels alike -- but for the sRGB colour
+// kind (ITW_MIP_SRGB), the library's own rule: the same filters over R, G, B decoded to linear light, stored as the nearest sRGB code.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 #include <stdint.h>
+#include "srgb_tables.h"
 
 namespace itw {
 
 struct MipTexel { float c[4]; };                                  // a stored texel, widened: every value is one the texel format holds
 
-// PX = 4: RGBA8, the raw codes as 0..255.  PX = 8: RGBA16F, the halves widened exactly.  `p` is PX aligned.
-template <int PX>
-__device__ __forceinline__ MipTexel mip_widen(uint32_t lo, uint32_t hi)
+// The sRGB colour kind (ITW_MIP_SRGB; RGBA8 texels whose R, G, B are sRGB coded, A linear): the tables of srgb_tables.h as the kernels hold
+// them in LDS.  dec[c] = D[c]; thr[k] = T[k] for k = 1..255, and thr[0] = thr[256] = NaN, which no value is below and none at or above.
+struct MipSrgbTables { float dec[256]; float thr[257]; };
+
+// fills `t` from the tables in memory; every lane of a 256-lane workgroup calls it, and it ends with the barrier that publishes the tables
+__device__ __forceinline__ void mip_srgb_fill(MipSrgbTables* t)
 {
+    t->dec[threadIdx.x] = __uint_as_float(SRGB_DECODE_BITS[threadIdx.x]);
+    t->thr[threadIdx.x] = __uint_as_float(threadIdx.x ? SRGB_THR_BITS[threadIdx.x] : 0x7fc00000u);
+    if (threadIdx.x == 0) t->thr[256] = __uint_as_float(0x7fc00000u);
+    __syncthreads();
+}
+
+// E(v): the number of k in 1..255 with v >= T[k].  A guess g from the curve's inverse, then one compare either side: E = g - (v < T[g]) +
+// (v >= T[g + 1]), which is the count whenever |g - E| <= 1 (T is strictly increasing).  The guess is floor(c + 0.5) of c = 255 * the sRGB
+// encoding of v, through v_log_f32 / v_exp_f32 (1 ulp each: c is off by less than 1e-3 codes, the fp32 operations around them included),
+// while T[k] is the value whose c is k - 0.5 (to an fp32 ulp of T): g and E round the same number, so they differ by one at the most, and only
+// next to a threshold.  tests/test_srgb_mips_cpu.py restates the guess on the host and adds +-0.05 codes of error to c: |g - E| <= 1 holds on
+// every float within 4096 ulps of a threshold; tests/test_gpu_srgb_mips.py runs this function on the floats around every T[k].  Values above 1 give 255 (the
+// clamp, and NaN above T[255]); -0, 0, negative values and NaN give 0.
+__device__ __forceinline__ uint32_t mip_srgb_encode(float v, const MipSrgbTables* t)
+{
+    float c = v * (12.92f * 255.0f);
+    if (v > 0.0031308f) c = 269.025f * __builtin_amdgcn_exp2f(__builtin_amdgcn_logf(v) * (1.0f / 2.4f)) - 14.025f;   // (v_log_f32 is log2; no denormal in or out here)
+    const int32_t g = (int32_t)fminf(fmaxf(c + 0.5f, 0.0f), 255.0f);         // (fmaxf(NaN, 0) is 0)
+    return (uint32_t)(g - (v < t->thr[g] ? 1 : 0) + (v >= t->thr[g + 1] ? 1 : 0));
+}
+
+// PX = 4: RGBA8, the raw codes as 0..255; with SRGB, R, G and B are D[code] and A stays the raw code.  PX = 8: RGBA16F, the halves widened
+// exactly.  `srgb` is the workgroup's tables (SRGB only).
+template <int PX, bool SRGB = false>
+__device__ __forceinline__ MipTexel mip_widen(uint32_t lo, uint32_t hi, const MipSrgbTables* srgb = nullptr)
+{
+    static_assert(!SRGB || PX == 4, "sRGB colour is an RGBA8 kind");
     MipTexel t;
-    if (PX == 4) {
+    if (SRGB) {
+        t.c[0] = srgb->dec[lo & 255u]; t.c[1] = srgb->dec[(lo >> 8) & 255u]; t.c[2] = srgb->dec[(lo >> 16) & 255u]; t.c[3] = (float)(lo >> 24);
+    } else if (PX == 4) {
         t.c[0] = (float)(lo & 255u); t.c[1] = (float)((lo >> 8) & 255u); t.c[2] = (float)((lo >> 16) & 255u); t.c[3] = (float)(lo >> 24);
     } else {
         t.c[0] = __half2float(__ushort_as_half((unsigned short)(lo & 0xffffu))); t.c[1] = __half2float(__ushort_as_half((unsigned short)(lo >> 16)));
@@ -38,17 +72,20 @@ __device__ __forceinline__ uint32_t mip_half_bits(float v)
 __device__ __forceinline__ uint32_t mip_byte(float v) { return (uint32_t)fminf(v + 0.5f, 255.0f); }
 
 // rounds `t` to the texel format: the words to store, and `t` becomes what a later load of them widens to
-template <int PX>
-__device__ __forceinline__ void mip_round(MipTexel& t, uint32_t& lo, uint32_t& hi)
+template <int PX, bool SRGB = false>
+__device__ __forceinline__ void mip_round(MipTexel& t, uint32_t& lo, uint32_t& hi, const MipSrgbTables* srgb = nullptr)
 {
-    if (PX == 4) {
+    if (SRGB) {
+        lo = mip_srgb_encode(t.c[0], srgb) | (mip_srgb_encode(t.c[1], srgb) << 8) | (mip_srgb_encode(t.c[2], srgb) << 16) | (mip_byte(t.c[3]) << 24);
+        hi = 0;
+    } else if (PX == 4) {
         lo = mip_byte(t.c[0]) | (mip_byte(t.c[1]) << 8) | (mip_byte(t.c[2]) << 16) | (mip_byte(t.c[3]) << 24);
         hi = 0;
     } else {
         lo = mip_half_bits(t.c[0]) | (mip_half_bits(t.c[1]) << 16);
         hi = mip_half_bits(t.c[2]) | (mip_half_bits(t.c[3]) << 16);
     }
-    t = mip_widen<PX>(lo, hi);
+    t = mip_widen<PX, SRGB>(lo, hi, srgb);
 }
 
 // AVERAGE4: p0 = (row 2y, column 2x), p1 = (2y+1, 2x), p2 = (2y, 2x+1), p3 = (2y+1, 2x+1)

@@ -26,7 +26,7 @@ EXPORTED_SYMBOLS = tuple(
     + ["itwCompressImageSliced", "itwCompressImageSlicedEx", "itwChainBytes", "itwCompressImageChain", "itwCompressImageChainEx", "itwCompressImageRefined", "itwCompressImageRefinedTo", "itwPsnrToTotalSse", "itwCompressImageChainRefined", "itwCompressImageChainRefinedTo", "itwChainPsnrToTotalSse", "itwSetSliceWindow", "itwSliceWindow", "itwSliceWindowFor", "itwPadToMultipleOf4", "itwFreeSurface", "itwPadToMultipleOf4Device",
        "itwConvertToRGBA8Device", "itwConvertToRGBA16FDevice",
        "itwPrepareNormalMapChain", "itwCompressNormalMapChain", "itwQuantizeNormalMapChain", "itwCompressSignedNormalMapChain", "itwCompressSignedNormalMapMipped", "itwCubeCrossFaces",
-       "itwMipLevels", "itwMipChainLayout", "itwGenerateMipChain", "itwCompressImageMipped"]
+       "itwMipLevels", "itwMipChainLayout", "itwGenerateMipChain", "itwCompressImageMipped", "itwCompressImageMippedEx", "itwSrgbToLinear", "itwLinearToSrgb"]
     # include/itw_multigpu.h: one surface over all GPUs, one process
     + ["itwMultiGpuRanks", "itwMultiGpuTransport", "itwMultiGpuPeerLinks", "itwCompressImageMultiGPU", "itwCompressImageMultiGPUEx", "itwCompressImageMultiGPUBands",
        "itwMultiGpuSetInterleave", "itwMultiGpuPieces"]
@@ -41,7 +41,7 @@ EXPORTED_SYMBOLS = tuple(
 # include/itw_test_hooks.h: exported by libispc_texcomp_test.so only (the same sources built with -DITW_TEST_HOOKS), never by the product
 TEST_HOOK_SYMBOLS = ("itwTestRcp", "itwTestRsqrt", "itwTestF2I", "itwTestBc7TwoSubsetBounds", "itwTestBc7RotationBounds", "itwTestBc45IndexTable", "itwTestBc45ClosestS",
                      "itwMultiGpuTestInjectFailure", "itwTestCombinerHold", "itwTestCombinerCounters", "itwTestBc7RouteCounters", "itwTestBc7RouteCountersReset",
-                     "itwTestBc7CallCountersArm", "itwTestBc7CallCounters")
+                     "itwTestBc7CallCountersArm", "itwTestBc7CallCounters", "itwTestSrgbEncode")
 # enum itw_test_bc7_call_counter (include/itw_test_hooks.h): what itwTestBc7CallCounters fills; the per-band ones are band 0 then band 1
 BC7_CALL_COUNTERS = ("pilot_listed", "pilot_sampled", "pilot_flag", "rot00", "rot01", "rot02", "rot10", "rot11", "rot12", "listed0", "listed1",
                      "pairs0", "pairs1", "overflow0", "overflow1", "redo0", "redo1")
@@ -324,6 +324,8 @@ def _load(path, hooks):
             L.itwTestBc7CallCountersArm.restype = None
             L.itwTestBc7CallCounters.argtypes = [C.POINTER(C.c_int32), C.c_int]
             L.itwTestBc7CallCounters.restype = None
+            L.itwTestSrgbEncode.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+            L.itwTestSrgbEncode.restype = None
         # dispatch layer (itw_dispatch.h)
         L.GetProcessorCount.restype = C.c_int
         L.GetBytesPerBlock.argtypes = [C.c_int]
@@ -417,6 +419,12 @@ def _load(path, hooks):
         L.itwGenerateMipChain.restype = C.c_int
         L.itwCompressImageMipped.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.itwCompressImageMipped.restype = C.c_bool
+        L.itwCompressImageMippedEx.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.itwCompressImageMippedEx.restype = C.c_bool
+        L.itwSrgbToLinear.argtypes = [C.c_uint8]
+        L.itwSrgbToLinear.restype = C.c_float
+        L.itwLinearToSrgb.argtypes = [C.c_float]
+        L.itwLinearToSrgb.restype = C.c_uint8
         L.itwDecodeBlocks.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]
         L.itwDecodeBlocks.restype = C.c_int
         L.itwDecodeChain.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
@@ -978,6 +986,33 @@ def cube_cross_faces(img):
 
 
 MIP_PER_LEVEL = 1     # ITW_MIP_PER_LEVEL (include/itw_dispatch.h)
+MIP_SRGB = 4          # ITW_MIP_SRGB: R, G, B of RGBA8 texels are sRGB coded and filtered in linear light
+
+
+def srgb_to_linear(code):
+    """itwSrgbToLinear: D[code] of the sRGB mip filter (include/itw_dispatch.h), the fp32 nearest to the linear light of sRGB code 0..255."""
+    assert 0 <= int(code) <= 255
+    return float(lib().itwSrgbToLinear(int(code)))
+
+
+def linear_to_srgb(v):
+    """itwLinearToSrgb: E(v) of the sRGB mip filter, the nearest sRGB code of the fp32 value v (host arithmetic, the kernels' definition)."""
+    return int(lib().itwLinearToSrgb(float(v)))
+
+
+def srgb_encode_device(values):
+    """Test hook (itwTestSrgbEncode): the mip kernels' own E over a float32 CUDA tensor -> uint8 CUDA tensor of the same shape."""
+    import torch
+    assert values.is_cuda and values.dtype == torch.float32 and values.is_contiguous()
+    out = torch.empty(values.shape, dtype=torch.uint8, device=values.device)
+    L = test_lib()
+    with torch.cuda.device(values.device):
+        L.itwSetStream(torch.cuda.current_stream(values.device).cuda_stream)
+        L.itwTestSrgbEncode(values.data_ptr(), out.data_ptr(), values.numel())
+    e = L.itwLastError()
+    if e:
+        raise RuntimeError(e.decode())
+    return out
 
 
 def mip_levels(width, height):
@@ -997,11 +1032,11 @@ def mip_chain_layout(width, height, items=1, levels=0, pixel_size=4):
     return n, [(int(out[i].ptr or 0), out[i].width, out[i].height, out[i].stride) for i in range(count)]
 
 
-def generate_mips(base_or_bases, levels=0, per_level=False):
+def generate_mips(base_or_bases, levels=0, per_level=False, srgb=False):
     """itwGenerateMipChain: the mip levels of one base image or a list of equally sized ones (cube faces, array items): host numpy arrays or
     CUDA torch tensors (H, W, 4), uint8 (RGBA8) or 2-byte elements (RGBA16F half bits), all of one kind.  DirectXTex's box filter when width
     and height are powers of two, else its linear filter (include/itw_dispatch.h).  levels == 0: the full chain.  per_level forces one
-    launch per level.  Returns the list of levels [base, level 1, ...] for one base, a list of such lists for a list; the bases themselves
+    launch per level; srgb (uint8 only) filters R, G, B as sRGB codes in linear light (ITW_MIP_SRGB).  Returns the list of levels [base, level 1, ...] for one base, a list of such lists for a list; the bases themselves
     are level 0 and are not copied.  Device tensors: asynchronous on torch's current stream."""
     single = hasattr(base_or_bases, "shape")
     bases = [base_or_bases] if single else list(base_or_bases)
@@ -1019,11 +1054,11 @@ def generate_mips(base_or_bases, levels=0, per_level=False):
         else:
             import numpy as np
             chains.append([b] + [np.empty((max(1, h >> l), max(1, w >> l), 4), dtype=b.dtype) for l in range(1, n)])
-    generate_mips_into(chains, per_level=per_level)
+    generate_mips_into(chains, per_level=per_level, srgb=srgb)
     return chains[0] if single else chains
 
 
-def generate_mips_into(chains, per_level=False):
+def generate_mips_into(chains, per_level=False, srgb=False):
     """itwGenerateMipChain over caller-made levels: `chains` is a list of items, each the list of its levels (level 0 filled in), which may
     be strided views of larger arrays / tensors.  Raises ValueError where the call returns -1."""
     flat = [lv for ch in chains for lv in ch]
@@ -1032,15 +1067,17 @@ def generate_mips_into(chains, per_level=False):
     if on_device:
         import torch
         lib().itwSetStream(torch.cuda.current_stream(flat[0].device).cuda_stream)
-    if lib().itwGenerateMipChain(C.cast(_surfaces(flat), C.c_void_p), len(chains), len(chains[0]), 4 * es, MIP_PER_LEVEL if per_level else 0) != 0:
+    flags = (MIP_PER_LEVEL if per_level else 0) | (MIP_SRGB if srgb else 0)
+    if lib().itwGenerateMipChain(C.cast(_surfaces(flat), C.c_void_p), len(chains), len(chains[0]), 4 * es, flags) != 0:
         raise ValueError("itwGenerateMipChain refused the call: " + (last_error() or "bad arguments"))
     return chains
 
 
-def compress_mipped(fmt, base_or_bases, levels=0, profile=None, settings=None, normal_ops=0, progress=None, out=None):
+def compress_mipped(fmt, base_or_bases, levels=0, profile=None, settings=None, normal_ops=0, progress=None, out=None, srgb=False):
     """itwCompressImageMipped: the save path from base images in one call -- flips of `normal_ops` on level 0, the mip chain, the normalise on
     every level, then the chain encoder.  One base or a list of equally sized ones (numpy arrays or CUDA torch tensors, as compress_chain
-    takes them); levels == 0: the full chain.  Returns (ok, blocks): the DDS payload, item-major then level."""
+    takes them); levels == 0: the full chain.  srgb: the chain's colour is filtered in linear light (itwCompressImageMippedEx with
+    ITW_MIP_SRGB; the format name is not read as a request).  Returns (ok, blocks): the DDS payload, item-major then level."""
     import numpy as np
     single = hasattr(base_or_bases, "shape")
     bases = [base_or_bases] if single else list(base_or_bases)
@@ -1070,8 +1107,12 @@ def compress_mipped(fmt, base_or_bases, levels=0, profile=None, settings=None, n
         settings = etc_profile(profile or "slow")
     sp = C.cast(C.byref(settings), C.c_void_p) if settings is not None else None
     cb = PROGRESS_FUNC(progress) if progress else None
-    ok = lib().itwCompressImageMipped(C.cast(_surfaces(bases), C.c_void_p), len(bases), levels, int(normal_ops), dst, DXGI_FORMAT[fmt],
-                                      sp, C.cast(cb, C.c_void_p) if cb else None, None)
+    if srgb:
+        ok = lib().itwCompressImageMippedEx(C.cast(_surfaces(bases), C.c_void_p), len(bases), levels, int(normal_ops), MIP_SRGB, dst, DXGI_FORMAT[fmt],
+                                            sp, C.cast(cb, C.c_void_p) if cb else None, None)
+    else:
+        ok = lib().itwCompressImageMipped(C.cast(_surfaces(bases), C.c_void_p), len(bases), levels, int(normal_ops), dst, DXGI_FORMAT[fmt],
+                                          sp, C.cast(cb, C.c_void_p) if cb else None, None)
     return bool(ok), out
 
 
