@@ -29,6 +29,13 @@ void itwTestBc7TwoSubsetBounds(const rgba_surface* d_src, float* d_out);
  * tests/test_gpu_bc7_rot_tasks.py checks it against the exact value in float64: never above it, and not uselessly below. */
 void itwTestBc7RotationBounds(const rgba_surface* d_src, float* d_out);
 
+/* The modes 0/2 scan's two cache programs (csrc/bc7.hip search_02, csrc/bc7_f02_schedule.h; tests/test_gpu_bc7_f02_cache.py): for every 4x4
+ * block of the device-resident RGBA8 surface the scan runs twice, order 0 = the scheduled visiting order with both caches (what the head scan
+ * runs), order 1 = table order with nothing cached.  d_out[(block * 2 + order) * 84 + k] (device memory, raster block order):
+ * k = 0, 1 mode 0's winner (error, shape 64..79); 2, 3 mode 2's winner (error, shape 64..127); 4..19 mode 0's error of the shapes with table
+ * index 0..15; 20..83 mode 2's error of the shapes with table index 0..63. */
+void itwTestBc7F02Scan(const rgba_surface* d_src, int32_t* d_out);
+
 /* BC4 / BC5 (tests/test_gpu_parity_bc4_bc5.py).  The encoders evaluate FindClosestUNORM (BC4BC5.cpp:314-337) through a table
  * the current device builds once by running that search, as written, for all 65 536 endpoint pairs: per pair the 7 texel
  * codes where the chosen index changes and the 8 indices of the runs in between (csrc/bc4_bc5.hip).  Copies the table --

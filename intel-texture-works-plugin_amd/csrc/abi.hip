@@ -1653,6 +1653,16 @@ void itwTestBc7RotationBounds(const rgba_surface* d_src, float* d_out)
     });
 }
 
+void itwTestBc7F02Scan(const rgba_surface* d_src, int32_t* d_out)
+{
+    itwClearError();
+    itw::guarded([&] {
+        if (!d_src || !d_src->ptr || !d_out) itw::fail_msg("null pointer");
+        itw::launch_bc7_test_f02_scan(d_src->ptr, d_src->stride, d_src->width, d_src->height, d_out, tls.user_stream);
+        ITW_CHECK(hipGetLastError());
+    });
+}
+
 void itwTestRcp(const float* in, float* out, int64_t n)
 {
     if (n <= 0) return;

@@ -273,7 +273,7 @@ struct Lane {
     bool improved;
     SeedTables T;
     int32_t* keys;            // LDS column (ranked-list path only): keys[i * TPB]
-    uint2* pal;               // LDS column of palettes (table-order scans): 12 levels, pal[level * TPB]
+    uint2* pal;               // LDS column of palettes (table-order scans): 12 levels, pal[level * TPB]; levels 12, 13: search_02<true>'s mode 0 cache
 };
 
 struct Win {                  // winner of one multi-subset mode during the search (its indices are recomputed by the finish kernel)
@@ -551,17 +551,24 @@ __device__ __forceinline__ void take(Win& w, int32_t err, int shape, int32_t key
 // The reference scans the shapes in table order with a strict `<`: the winner is the lowest error and, among equal
 // errors, the lowest table index -- whatever the visiting order.  With mode 2 enabled the scan therefore follows
 // BC7_F02_SCHEDULE (tools/gen_bc7_f02_schedule.py): 192 (shape, subset) pairs use only 140 distinct texel masks and a
-// subset's whole mode 2 result (indices, error) depends on the mask alone, so the order clusters equal masks and a
-// four-entry register cache, driven by the wave-uniform schedule word, turns 39 subset evaluations into loads (9 more
-// keep their fit for mode 0 and skip the mode 2 part).
+// subset's whole result under a mode (indices, error) depends on the mask alone, so the order clusters equal masks and
+// two four-entry caches, driven by the wave-uniform schedule words, turn subset evaluations into loads: mode 2's over all
+// 64 shapes (BC7_F02_SCHEDULE) and, with CACHE0, mode 0's over its 16 (BC7_F02_SCHEDULE_EXT).  A subset with every
+// result it needs loaded is skipped outright -- moments, fit, both modes; one that loads a single mode keeps its fit.
+// The counts are in the header's comment.  Without CACHE0 the primary word alone is run, a valid program by itself.
 // A cached subset result is its error (the scans carry no indices).
-// The cache is four scalars (an indexed aggregate would be demoted to scratch); `slot` is wave-uniform.
+// Mode 2's cache is four scalars (an indexed aggregate would be demoted to scratch); `slot` is wave-uniform.
+// Mode 0's cache is four more words of the lane's LDS column, behind the twelve palette levels (pal[12 * TPB] and
+// pal[13 * TPB]): the head scan has no register to spare, and a lane reads only what it wrote itself, so no barrier.
 #define ITW_CACHE_GET(F, slot) ((slot) == 0u ? F##0 : ((slot) == 1u ? F##1 : ((slot) == 2u ? F##2 : F##3)))
 #define ITW_CACHE_PUT(F, slot, v) do { F##0 = (slot) == 0u ? (v) : F##0; F##1 = (slot) == 1u ? (v) : F##1; F##2 = (slot) == 2u ? (v) : F##2; F##3 = (slot) == 3u ? (v) : F##3; } while (0)
 
 // `first`/`step`: this call visits positions first, first + step, ... (the wide path splits one scan over several waves,
 // WIDE below); a split scan takes the shapes in table order without the cache (any visiting order gives the same winner).
-__device__ __forceinline__ void search_02(Lane& ln, const bc7_enc_settings& S, Win& b0, Win& b2, int first = 0, int step = 1)
+// CACHE0: the caller's LDS column has 14 levels.  SCHEDULED = false (test hook): table order, nothing cached.
+// `trace` (test hook; null = none): the lane's per-shape errors, [0..15] mode 0 and [16..79] mode 2 by table index.
+template <bool CACHE0 = false, bool SCHEDULED = true>
+__device__ __forceinline__ void search_02(Lane& ln, const bc7_enc_settings& S, Win& b0, Win& b2, int first = 0, int step = 1, int32_t* trace = nullptr)
 {
     reset(b0, 64); reset(b2, 64);
     IStats<3> full;
@@ -569,10 +576,12 @@ __device__ __forceinline__ void search_02(Lane& ln, const bc7_enc_settings& S, W
     const int32_t tt = full.m[0] + full.m[4] + full.m[7];          // sum over the block of |texel|^2
     const bool do2 = !S.skip_mode2;
     const int count = do2 ? 64 : 16;
+    const bool scheduled = SCHEDULED && do2 && step == 1;            // mode 0 alone / split scan: table order, nothing cached
     int32_t ce0 = 0, ce1 = 0, ce2 = 0, ce3 = 0;      // cached subset results (mode 2 error of a texel mask)
     for (int pos = first; pos < count; pos += step) {
         ln.tx.fence();
-        const uint32_t sched = (do2 && step == 1) ? BC7_F02_SCHEDULE[pos] : (uint32_t)pos;     // mode 0 alone / split scan: table order, nothing cached
+        const uint32_t sched = scheduled ? BC7_F02_SCHEDULE[pos] : (uint32_t)pos;
+        const uint32_t ext = (CACHE0 && scheduled) ? BC7_F02_SCHEDULE_EXT[pos] : 0u;
         const int part = (int)(sched & 63u);
         const bool do0 = part < 16;
         int32_t e0 = 0, e2 = 0;
@@ -582,11 +591,14 @@ __device__ __forceinline__ void search_02(Lane& ln, const bc7_enc_settings& S, W
         for (int j = 0; j < 3; j++) {
             ln.tx.fence();                                // texel-derived values are used once per shape: do not hoist
             const uint32_t act = (sched >> (8 + 4 * j)) & 3u, slot = (sched >> (10 + 4 * j)) & 3u;
-            const bool load = act == 2u;
-            if (load) {                                   // this mask's mode 2 result is in the cache
-                e2 += ITW_CACHE_GET(ce, slot);
-                if (!do0) { rest_valid = false; continue; }
-            }
+            const uint32_t act0 = (ext >> (4 * j)) & 3u, slot0 = (ext >> (4 * j + 2)) & 3u;
+            int32_t* const c0 = reinterpret_cast<int32_t*>(ln.pal + (12u + (slot0 >> 1)) * TPB) + (slot0 & 1u);
+            const bool load = act == 2u;                  // this mask's mode 2 result is in the cache
+            const bool load0 = CACHE0 && act0 == 2u;      // and its mode 0 result
+            if (load) e2 += ITW_CACHE_GET(ce, slot);
+            if (load0) e0 += *c0;
+            const bool need0 = do0 && !load0;
+            if (load && !need0) { rest_valid = false; continue; }
             const SubsetMask sm = subset_of(64 + part, j);
             IStats<3> st;
             if (j < 2 || !rest_valid) stats_int<3>(st, ln.tx.pl, sm); else st = rest;
@@ -595,10 +607,15 @@ __device__ __forceinline__ void search_02(Lane& ln, const bc7_enc_settings& S, W
             fit[0][3] = 0.f; fit[1][3] = 0.f;            // the reference's unwritten alpha slots, pinned to 0
             fit_line<3>(fit, ln.tx, sm.bits, st, rcp_of_count(sm.n), ln.T);
             int32_t q[2][4], d[2][4];
-            if (do0) {
+            if (need0) {
                 quant_mode<0, true>(q, d, fit, 3);
                 const PalSegment ps = build_palette<3, 3, TPB>(ln.pal, d);
-                subset_error_pal<3, 3, TPB>(e0, ln.tx, ps, ln.pal, sm.bits);
+                int32_t r = 0;
+                subset_error_pal<3, 3, TPB>(CACHE0 ? r : e0, ln.tx, ps, ln.pal, sm.bits);
+                if (CACHE0) {
+                    e0 += r;
+                    if (act0 == 1u) *c0 = r;
+                }
             }
             if (do2 && !load) {
                 quant_mode<2, true>(q, d, fit, 3);
@@ -613,6 +630,9 @@ __device__ __forceinline__ void search_02(Lane& ln, const bc7_enc_settings& S, W
         const int shape = 64 + part;
         if (do0 && (e0 < b0.err || (e0 == b0.err && shape < b0.shape))) take(b0, e0, shape, part);
         if (do2 && (e2 < b2.err || (e2 == b2.err && shape < b2.shape))) take(b2, e2, shape, part);
+#ifdef ITW_TEST_HOOKS
+        if (trace) { if (do0) trace[part] = e0; if (do2) trace[16 + part] = e2; }
+#endif
     }
 }
 
@@ -1408,7 +1428,8 @@ bc7_scan_all(const uint8_t* __restrict__ src, int64_t stride, int32_t blocks_x, 
 {
     __shared__ unsigned short s_seed16[2048];
     __shared__ uint32_t s_seed32[2048];
-    __shared__ uint2 s_pal[(RANKED_LISTS ? 16 : 12) * TPB];   // ranked lists: 2 subsets x 8 levels (3 waves per SIMD: 3 x 44 KiB)
+    // ranked lists: 2 subsets x 8 levels (3 waves per SIMD: 3 x 44 KiB); else 12 levels and, for search_02, its mode 0 cache (4 x 40 KiB)
+    __shared__ uint2 s_pal[(RANKED_LISTS ? 16 : (FAM7 ? 12 : 14)) * TPB];
     if (sel.gate && *sel.gate != sel.want) return;                  // the pilot chose the other order (whole grid: no barrier is pending)
     if (!RANKED_LISTS && split) {
         // bounded order: modes 1/3 (or mode 7: FAM7) over the list bc7_finish_all<.., 3 | 5 | 6> left, each listed block's 64 shapes cut
@@ -1469,7 +1490,7 @@ bc7_scan_all(const uint8_t* __restrict__ src, int64_t stride, int32_t blocks_x, 
     const int kind = tasks.kind[t];                                  // wave-uniform
     Win wa, wb;
     if (!FAM7 && kind == WK_SCAN02) {
-        search_02(ln, S, wa, wb);
+        search_02<true>(ln, S, wa, wb);
         if (live) { wins4[(int64_t)wide_win_slot(0) * nblocks + b] = pack_win(wa); if (!S.skip_mode2) wins4[(int64_t)wide_win_slot(2) * nblocks + b] = pack_win(wb); }
     } else if (!FAM7) {
         if (RANKED_LISTS && ranked13) search_two_subset<false, 3, 2>(ln, S, wa, wb); else search_two_subset<false, 3, 0>(ln, S, wa, wb);
@@ -2383,6 +2404,41 @@ void launch_bc7_test_rot_bounds(const uint8_t* src, int64_t stride, int width, i
     const bool vec = ((reinterpret_cast<uintptr_t>(src) | (uintptr_t)stride) & 15) == 0;
     const dim3 grid((unsigned)((n + TPB - 1) / TPB));
     with_bool(vec, [&](auto V) { hipLaunchKernelGGL((bc7_test_rot_bounds<decltype(V)::value>), grid, dim3(TPB), 0, st, src, stride, bx, (int32_t)n, out); });
+}
+// test hook (itwTestBc7F02Scan): search_02 of every block twice -- in the scheduled order with both caches, as the head scan runs it, and in
+// table order with nothing cached.  out[(block * 2 + order) * 84 + ..]: mode 0's winner (error, shape), mode 2's winner (error, shape), the
+// 16 mode 0 and the 64 mode 2 errors by table index.  The winners alone would hide a stale slot wherever the wrong value does not win.
+template <bool VEC16>
+__global__ void __launch_bounds__(TPB) bc7_test_f02_scan(const uint8_t* __restrict__ src, int64_t stride, int32_t blocks_x, int32_t nblocks, int32_t* __restrict__ out)
+{
+    __shared__ unsigned short s_seed16[2048];
+    __shared__ uint32_t s_seed32[2048];
+    __shared__ uint2 s_pal[14 * TPB];
+    Lane ln;
+    ln.T = stage_seed_tables_fast(s_seed16, s_seed32, threadIdx.x, TPB);
+    __syncthreads();
+    const int32_t gid = blockIdx.x * TPB + threadIdx.x;
+    const bool live = gid < nblocks;
+    const int32_t b = live ? gid : nblocks - 1;
+    ln.keys = nullptr;
+    ln.pal = s_pal + threadIdx.x;
+    load_block<VEC16>(ln.tx, src, stride, blocks_x, b);
+    bc7_enc_settings S = {};                                        // search_02 reads skip_mode2 alone
+    int32_t* const o = live ? out + (int64_t)b * 168 : nullptr;
+    Win w0, w2;
+    search_02<true, true>(ln, S, w0, w2, 0, 1, live ? o + 4 : nullptr);
+    if (live) { o[0] = w0.err; o[1] = w0.shape; o[2] = w2.err; o[3] = w2.shape; }
+    search_02<false, false>(ln, S, w0, w2, 0, 1, live ? o + 88 : nullptr);
+    if (live) { o[84] = w0.err; o[85] = w0.shape; o[86] = w2.err; o[87] = w2.shape; }
+}
+void launch_bc7_test_f02_scan(const uint8_t* src, int64_t stride, int width, int height, int32_t* out, hipStream_t st)
+{
+    const int bx = width / 4;
+    const int64_t n = (int64_t)bx * (height / 4);
+    if (n <= 0) return;
+    const bool vec = ((reinterpret_cast<uintptr_t>(src) | (uintptr_t)stride) & 15) == 0;
+    const dim3 grid((unsigned)((n + TPB - 1) / TPB));
+    with_bool(vec, [&](auto V) { hipLaunchKernelGGL((bc7_test_f02_scan<decltype(V)::value>), grid, dim3(TPB), 0, st, src, stride, bx, (int32_t)n, out); });
 }
 // test hook (itwTestBc7RouteCounters): the route witness -- what ITW_ROUTE_SEEN counts, here and in abi.hip's launch()
 static std::atomic<long long> g_route_seen[ITW_ROUTE_COUNTERS];

@@ -62,6 +62,7 @@ void launch_bc7 (const uint8_t* src, int64_t stride, int width, int height, uint
 // test hook: bc7_exact.hpp's two_subset_bound of all 64 two-subset shapes of every block, out[block * 64 + shape] (device memory)
 void launch_bc7_test_bounds(const uint8_t* src, int64_t stride, int width, int height, float* out, hipStream_t st);
 void launch_bc7_test_rot_bounds(const uint8_t* src, int64_t stride, int width, int height, float* out, hipStream_t st);
+void launch_bc7_test_f02_scan(const uint8_t* src, int64_t stride, int width, int height, int32_t* out, hipStream_t st);
 // test hook (itwTestBc7RouteCounters): the route witness, host-side counters indexed by include/itw_test_hooks.h's itw_test_bc7_route.  The hooks build
 // counts one at ITW_ROUTE_SEEN(what); in the product the macro is empty.
 #ifdef ITW_TEST_HOOKS

@@ -13,7 +13,7 @@ from .abi import (  # noqa: F401
     lib, test_lib, TEST_HOOK_SYMBOLS, BC7_ROUTE_COUNTERS, lib_path, RgbaSurface, Bc7Settings, Bc6hSettings, EtcSettings, BC7_PROFILES, BC6H_PROFILES,
     bc7_profile, bc6h_profile, etc_profile, compress, compress_numpy, band_for_part, version, device_info,
     BYTES_PER_BLOCK, EXPORTED_SYMBOLS, DXGI_FORMAT, DdsDesc, image_func, compress_image, PROGRESS_FUNC, pad_to_multiple_of_4, dds_file, decode, block_count, KEEPS_PARTIAL_BLOCKS, SIGNED_FORMATS,
-    available, set_error_mode, last_error, ON_ERROR_ABORT, ON_ERROR_RETURN, set_bc7_path, set_bc7_pilot, compress_image_multigpu, multigpu_sub_bands, MultiGpuStats, source_sha256, bc7_two_subset_bounds, bc7_rotation_bounds,
+    available, set_error_mode, last_error, ON_ERROR_ABORT, ON_ERROR_RETURN, set_bc7_path, set_bc7_pilot, compress_image_multigpu, multigpu_sub_bands, MultiGpuStats, source_sha256, bc7_two_subset_bounds, bc7_rotation_bounds, bc7_f02_scan,
     chain_bytes, compress_chain, mip_chain, decode_chain, decode_image, load_dds, dds_images,
     KtxDesc, ktx_file, ktx_images, load_ktx,
     PreviewView, PREVIEW_CHANNEL, PREVIEW_CHANNEL_MASK, PREVIEW_TILE_MAX_ZOOM, preview_view, preview, preview_surface,

@@ -39,7 +39,7 @@ EXPORTED_SYMBOLS = tuple(
     # include/itw_dds.h, second part: KTX 1.1 container (ETC1)
     + ["itwKtxHeaderBytes", "itwKtxFileBytes", "itwKtxWriteHeader", "itwKtxReadHeader", "itwKtxWriteFile", "itwKtxImage"])
 # include/itw_test_hooks.h: exported by libispc_texcomp_test.so only (the same sources built with -DITW_TEST_HOOKS), never by the product
-TEST_HOOK_SYMBOLS = ("itwTestRcp", "itwTestRsqrt", "itwTestF2I", "itwTestBc7TwoSubsetBounds", "itwTestBc7RotationBounds", "itwTestBc45IndexTable", "itwTestBc45ClosestS",
+TEST_HOOK_SYMBOLS = ("itwTestRcp", "itwTestRsqrt", "itwTestF2I", "itwTestBc7TwoSubsetBounds", "itwTestBc7RotationBounds", "itwTestBc7F02Scan", "itwTestBc45IndexTable", "itwTestBc45ClosestS",
                      "itwMultiGpuTestInjectFailure", "itwTestCombinerHold", "itwTestCombinerCounters", "itwTestBc7RouteCounters", "itwTestBc7RouteCountersReset",
                      "itwTestBc7CallCountersArm", "itwTestBc7CallCounters", "itwTestSrgbEncode")
 # enum itw_test_bc7_call_counter (include/itw_test_hooks.h): what itwTestBc7CallCounters fills; the per-band ones are band 0 then band 1
@@ -306,6 +306,8 @@ def _load(path, hooks):
             L.itwTestBc7TwoSubsetBounds.restype = None
             L.itwTestBc7RotationBounds.argtypes = [C.POINTER(RgbaSurface), C.c_void_p]
             L.itwTestBc7RotationBounds.restype = None
+            L.itwTestBc7F02Scan.argtypes = [C.POINTER(RgbaSurface), C.c_void_p]
+            L.itwTestBc7F02Scan.restype = None
             L.itwTestBc45IndexTable.argtypes = [C.c_void_p]
             L.itwTestBc45IndexTable.restype = C.c_int
             L.itwTestBc45ClosestS.argtypes = [C.c_void_p]
@@ -661,6 +663,26 @@ def bc7_rotation_bounds(img):
         L.itwSetStream(torch.cuda.current_stream(img.device).cuda_stream)
         surf = RgbaSurface(img.data_ptr(), w, h, img.stride(0))
         L.itwTestBc7RotationBounds(C.byref(surf), out.data_ptr())
+    e = L.itwLastError()
+    if e:
+        raise RuntimeError(e.decode())
+    return out
+
+
+def bc7_f02_scan(img):
+    """Test hook: the modes 0/2 scan of every block in the scheduled, cached order and in table order with nothing cached (itwTestBc7F02Scan).
+    img: CUDA tensor (H, W, 4) uint8 -> int32 CUDA tensor (blocks, 2, 84), raster block order; [:, 0] scheduled, [:, 1] table order;
+    [..., 0:4] mode 0's winner (error, shape) and mode 2's, [..., 4:20] mode 0's per-shape errors, [..., 20:84] mode 2's."""
+    import torch
+    assert img.is_cuda and img.dim() == 3 and img.shape[2] == 4 and img.element_size() == 1
+    assert img.stride(2) == 1 and img.stride(1) == 4
+    h, w = img.shape[:2]
+    out = torch.full(((h // 4) * (w // 4), 2, 84), -1, dtype=torch.int32, device=img.device)
+    L = test_lib()
+    with torch.cuda.device(img.device):
+        L.itwSetStream(torch.cuda.current_stream(img.device).cuda_stream)
+        surf = RgbaSurface(img.data_ptr(), w, h, img.stride(0))
+        L.itwTestBc7F02Scan(C.byref(surf), out.data_ptr())
     e = L.itwLastError()
     if e:
         raise RuntimeError(e.decode())
