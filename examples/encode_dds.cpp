@@ -4,6 +4,7 @@
 //
 //   encode_dds [--measure] [--refine <profile> <max_block_sse> | --refine-share <profile> <percent> | --refine-psnr <profile> <dB>]
 //              [--normal flipx,flipy,normalize | --signed-normal int8|half|float[,flipx,flipy,normalize]] [--cube-cross] [--mips [levels] [--srgb-mips]]
+//              [--alpha-weight] [--alpha-coverage <ref>]
 //              <format> <width> <height> <in.raw> <out.dds> [slice_pixels]
 //     format : bc1 | bc3 | bc4 | bc5 | bc4_snorm | bc5_snorm | bc7_<profile> | bc6h_<profile> | etc1_slow      (profiles: the GetProfile_* names)
 //              etc1_slow: DDS has no code for ETC1, so the output is a KTX 1.1 file (itwKtx*, itw_dds.h); the slices go through itwCompressImageSlicedEx
@@ -34,6 +35,11 @@
 //                 --cube-cross; not with --refine* or --measure.  The header carries the image's own size: level l is max(1, w >> l) wide.
 //     --srgb-mips : with --mips: the texels' R, G, B are sRGB coded and every level is filtered in linear light (itwCompressImageMippedEx with
 //                 ITW_MIP_SRGB; alpha stays linear).  RGBA8 colour formats only: not with bc6h_*, the SNORM pair or --normal.
+//     --alpha-weight, --alpha-coverage <ref> : with --mips: the rules for cut-out textures (itwCompressImageMippedAlpha; itw_dispatch.h,
+//                 "Mip chains of cut-out textures") -- colour weighted by alpha, so what alpha 0 hides stays out of the levels, and the
+//                 share of texels passing `alpha >= ref` (1 .. 255) kept at every level.  With --alpha-coverage one line on stdout per
+//                 image: texels, the count passing before and after, the threshold chosen (itwGenerateMipChainAlpha's report).  RGBA8
+//                 colour formats only, as --srgb-mips; not with --normal.
 //
 //   encode_dds --decode <in.dds | in.ktx> <out.raw>
 //     (.dds or .ktx: told apart by the file's first bytes; a KTX file's images come in ITS order, level then face)
@@ -170,7 +176,8 @@ int encode_normal_or_cross(const Format& f, const rgba_surface& source, uint32_t
 }
 
 // encode_dds --mips: the base image (or its six cross faces) to a mipped DDS / KTX in one call; levels == 0: the full chain
-int encode_mipped(const Format& f, const rgba_surface& source, uint32_t ops, uint32_t mip_flags, bool cube_cross, int levels, const char* out_path)
+int encode_mipped(const Format& f, const rgba_surface& source, uint32_t ops, uint32_t mip_flags, const itw_mip_alpha* alpha, bool cube_cross, int levels,
+                  const char* out_path)
 {
     const bool bc7 = std::strncmp(f.name, "bc7_", 4) == 0, bc6h = std::strncmp(f.name, "bc6h_", 5) == 0, etc1 = f.dxgi == ITW_FORMAT_ETC1_RGB8;
     union { bc7_enc_settings s7; bc6h_enc_settings s6; etc_enc_settings se; } settings;
@@ -191,9 +198,25 @@ int encode_mipped(const Format& f, const rgba_surface& source, uint32_t ops, uin
     if (bytes <= 0) { std::fprintf(stderr, "bad size\n"); return 2; }
     std::vector<uint8_t> blocks((size_t)bytes);
     itwSetErrorMode(ITW_ON_ERROR_RETURN);
-    if (!itwCompressImageMippedEx(bases, items, levels, ops, mip_flags, blocks.data(), f.dxgi, &settings, nullptr, nullptr)) {
+    const bool done = alpha ? itwCompressImageMippedAlpha(bases, items, levels, mip_flags, alpha, blocks.data(), f.dxgi, &settings, nullptr, nullptr)
+                            : itwCompressImageMippedEx(bases, items, levels, ops, mip_flags, blocks.data(), f.dxgi, &settings, nullptr, nullptr);
+    if (!done) {
         std::fprintf(stderr, "%s\n", itwLastError() ? itwLastError() : "compression failed");
         return 1;
+    }
+    if (alpha && alpha->coverage_ref) {                              // the report: the same chain once more, in host memory
+        std::vector<uint8_t> texels((size_t)itwMipChainLayout(w, h, items, levels, 4, nullptr, nullptr));
+        std::vector<itw_mip_coverage> rows((size_t)items * levels);
+        itwMipChainLayout(w, h, items, levels, 4, texels.data(), chain.data());
+        for (int i = 0; i < items; i++)
+            for (int y = 0; y < h; y++) std::memcpy(chain[(size_t)i * levels].ptr + (size_t)y * w * 4, bases[i].ptr + (size_t)y * bases[i].stride, (size_t)w * 4);
+        if (itwGenerateMipChainAlpha(chain.data(), items, levels, mip_flags, alpha, rows.data()) != 0) {
+            std::fprintf(stderr, "%s\n", itwLastError() ? itwLastError() : "the report failed");
+            return 1;
+        }
+        for (size_t i = 0; i < rows.size(); i++)
+            std::printf("coverage item %zu level %zu texels %llu before %llu after %llu threshold %u\n", i / levels, i % levels, (unsigned long long)rows[i].texels,
+                        (unsigned long long)rows[i].covered_plain, (unsigned long long)rows[i].covered, rows[i].threshold);
     }
     ItwDdsDesc desc = { (uint32_t)w, (uint32_t)h, (uint32_t)levels, (uint32_t)f.dxgi, cube_cross ? 1u : 0u, 1 };
     ItwKtxDesc kdesc = { (uint32_t)w, (uint32_t)h, (uint32_t)levels, ITW_FORMAT_ETC1_RGB8, 0, 0 };
@@ -370,7 +393,8 @@ int main(int argc, char** argv)
     double refine_value = 0.0;                                  // percent / dB
     bool normal_given = false, cube_cross = false;
     uint32_t normal_ops = 0;                                    // ITW_NORMAL_*
-    bool mips = false, srgb_mips = false;
+    bool mips = false, srgb_mips = false, alpha_given = false;
+    itw_mip_alpha alpha = { (uint32_t)sizeof(itw_mip_alpha), 0, 0, 0 };
     int mip_levels = 0;                                         // 0: the full chain
     int signed_tb = 0;                                          // --signed-normal: texel bytes of the signed source (4, 8 or 16)
     for (int i = 1; i < argc; i++)
@@ -430,10 +454,19 @@ int main(int argc, char** argv)
             srgb_mips = true;
             for (int k = i; k + 1 < argc; k++) argv[k] = argv[k + 1];
             argc--; i--;
+        } else if (std::strcmp(argv[i], "--alpha-weight") == 0) {
+            alpha_given = true; alpha.weight_colour = 1;
+            for (int k = i; k + 1 < argc; k++) argv[k] = argv[k + 1];
+            argc--; i--;
+        } else if (std::strcmp(argv[i], "--alpha-coverage") == 0 && i + 1 < argc) {
+            alpha_given = true; alpha.coverage_ref = (uint32_t)std::atoi(argv[i + 1]);      // (the call refuses what is not 0 .. 255)
+            for (int k = i; k + 2 < argc; k++) argv[k] = argv[k + 2];
+            argc -= 2; i--;
         }
     if (argc < 6) {
         std::fprintf(stderr, "usage: %s [--measure] [--refine <profile> <max_block_sse> | --refine-share <profile> <percent> | --refine-psnr <profile> <dB>]\n"
                              "          [--normal flipx,flipy,normalize | --signed-normal int8|half|float[,flipx,flipy,normalize]] [--cube-cross] [--mips [levels] [--srgb-mips]]\n"
+                             "          [--alpha-weight] [--alpha-coverage <ref>]\n"
                              "          <format> <width> <height> <in.raw> <out.dds> [slice_pixels]\n"
                              "       %s --decode <in.dds | in.ktx> <out.raw>\n"
                              "       %s --preview <in.dds | in.ktx> <image index> <out.ppm> <w> <h> <x> <y> <zoom> [channels] [exposure] [matte]\n", argv[0], argv[0], argv[0]);
@@ -450,6 +483,10 @@ int main(int argc, char** argv)
         return 2;
     }
     if (srgb_mips && (!mips || signed_tb)) { std::fprintf(stderr, "--srgb-mips goes with --mips, and not with --signed-normal\n"); return 2; }
+    if (alpha_given && (!mips || signed_tb || normal_given)) {
+        std::fprintf(stderr, "--alpha-weight and --alpha-coverage go with --mips, and not with --normal or --signed-normal\n");
+        return 2;
+    }
     const int texel_bytes = signed_tb ? signed_tb : f->texel_bytes;
     std::vector<uint8_t> texels((size_t)width * height * texel_bytes);
     FILE* in = std::fopen(argv[4], "rb");
@@ -463,7 +500,7 @@ int main(int argc, char** argv)
             std::fprintf(stderr, "--mips does not go with --refine* or --measure; --cube-cross not with etc1_slow\n");
             return 2;
         }
-        return encode_mipped(*f, source, normal_ops, srgb_mips ? (uint32_t)ITW_MIP_SRGB : 0u, cube_cross, mip_levels, argv[5]);
+        return encode_mipped(*f, source, normal_ops, srgb_mips ? (uint32_t)ITW_MIP_SRGB : 0u, alpha_given ? &alpha : nullptr, cube_cross, mip_levels, argv[5]);
     }
     if (normal_given || cube_cross) {
         // the normal-map and cube-cross stages of the save path (IntelPlugin.cpp:2075-2106, 2149-2152): one call over the image or its six faces

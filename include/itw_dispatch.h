@@ -475,6 +475,55 @@ bool itwCompressImageMippedEx(const rgba_surface* bases, int items, int levels, 
 float itwSrgbToLinear(uint8_t code);
 uint8_t itwLinearToSrgb(float v);
 
+/* Mip chains of cut-out textures (RGBA8 with an alpha test: foliage, fences, hair, decals): two more of THE LIBRARY'S OWN RULES, pinned to
+ * no byte of the reference (it passes TEX_FILTER_DEFAULT | TEX_FILTER_SEPARATE_ALPHA and has neither).  Both are options of itw_mip_alpha,
+ * both default to off, and with both off not one byte differs from itwGenerateMipChain's.  RGBA8 only; levels, sizes and the choice of
+ * filter are those of "Mip chains" above: box when the base's width and height are powers of two, else linear, level l from level l-1 as
+ * stored, the base never written.
+ *
+ * A. Alpha-weighted colour (weight_colour = 1).  A texel of alpha 0 carries whatever colour the painter left there, and the plain filter
+ *    averages it into its visible neighbours: dark or white fringes from level 1 on.  Per output texel:
+ *      each source tap is widened as always: raw codes, or D[code] for R, G, B under ITW_MIP_SRGB;
+ *      R, G, B of each tap are multiplied by that tap's alpha code, p = c * a, one fp32 multiply;
+ *      the same filter expression, in the same order and rounding, runs over the premultiplied colour and over alpha: P[k] and va, the
+ *      filtered, unrounded alpha;
+ *      if va > 0 the colour is P[k] / va, one correctly rounded fp32 division; otherwise it is what the plain rule gives for that texel;
+ *      alpha is stored from va exactly as always, colour by the kind's own store: (uint8_t)min(v + 0.5f, 255.0f), or E(v) under ITW_MIP_SRGB.
+ *    For the box on raw codes that is (2 * sum(a_i * c_i) + sum(a_i)) / (2 * sum(a_i)) in integers, round-half-up.
+ * B. Coverage kept per level (coverage_ref = r, 1 .. 255; 0: off).  Averaging alpha and then testing it is not averaging the test: the
+ *    share of texels that pass `alpha >= r` drifts from level to level and a thin object dissolves with distance.  The chain is first
+ *    generated whole with coverage off (weighting and sRGB as asked); then, per item, the alpha of every level >= 1 is replaced.  All
+ *    arithmetic is in 64-bit integers:
+ *      level 0 has N0 texels, cov0 of them with a >= r;
+ *      a level of n texels has the target K = (cov0 * n + N0 / 2) / N0, floor;
+ *      ge[t] is the number of its texels with a >= t;
+ *      t* is the t in 1 .. 255 that minimises the triple (|ge[t] - K|, |t - r|, t), compared lexicographically;
+ *      every texel's alpha becomes a' = min(255, (a * r) / t*), floor.
+ *    So #(a' >= r) == ge[t*] exactly, t* == r leaves the level's bytes as they were, alpha 0 stays 0, and R, G, B are never touched.  Every
+ *    count is an integer sum: the same bits on every run.  A base of more than 2^31 texels is refused with coverage on.
+ *
+ * itwGenerateMipChainAlpha: itwGenerateMipChain with pixel_size 4 and the two rules.  `flags` takes ITW_MIP_PER_LEVEL and ITW_MIP_SRGB with
+ * the same meaning, routes and pointer rules; alpha == NULL is both options off.  `report` (host memory, items * levels rows in DDS order, or
+ * NULL) receives per image its texels, the count with a >= r before (covered_plain) and after (covered) the rescale, and t* (threshold);
+ * level 0 rows hold covered_plain = covered = cov0 and threshold = r.  With `report` the call ends with a synchronise of the thread's
+ * stream; without it the call is as asynchronous as itwGenerateMipChain is for the same pointers.  Coverage adds three launches -- the
+ * histograms of every level, the thresholds, the rescale -- and one table upload, whatever the number of items and levels, and nothing on
+ * the host is read between them.  items == 0 or levels <= 1: nothing to do, nothing reported.  Returns 0; -1, through the error mode,
+ * before any device work and with nothing written, for struct_size != 16, reserved != 0, weight_colour > 1, coverage_ref > 255, a report
+ * without coverage_ref, and everything itwGenerateMipChain refuses for pixel_size 4.
+ * itwCompressImageMippedAlpha: itwCompressImageMippedEx with normal_ops 0 and the rules handed to the chain's generation; with both off it
+ * writes that call's payload.  The encode is the same itwCompressImageChainEx.  Refused as ITW_MIP_SRGB is, for the same reason -- the
+ * texels are not RGBA8 colour: DXGI formats 95 / 96 and 81 / 84.
+ * itwAlphaCoverage: per RGBA8 image, the number of texels with alpha >= alpha_ref (0 .. 255) into covered[count] (host memory): the count
+ * the coverage rule uses, so a caller can check a chain or choose r.  Images of any sizes >= 1, any stride at least the row's bytes, all
+ * host or all device pointers; returns synchronised.  0, or -1 through the error mode. */
+typedef struct itw_mip_alpha    { uint32_t struct_size /* 16 */, weight_colour /* 0|1 */, coverage_ref /* 0..255 */, reserved /* 0 */; } itw_mip_alpha;
+typedef struct itw_mip_coverage { uint64_t texels, covered_plain, covered; uint32_t threshold, reserved; } itw_mip_coverage;   /* 32 bytes, one per image, DDS order */
+int itwGenerateMipChainAlpha(const rgba_surface* images, int items, int levels, uint32_t flags, const itw_mip_alpha* alpha, itw_mip_coverage* report);
+bool itwCompressImageMippedAlpha(const rgba_surface* bases, int items, int levels, uint32_t mip_flags, const itw_mip_alpha* alpha, uint8_t* target,
+                                 int dxgi_format, const void* settings, ItwProgressFunc* progress, void* user);
+int itwAlphaCoverage(const rgba_surface* images, int count, int alpha_ref, uint64_t* covered);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

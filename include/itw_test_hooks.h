@@ -105,6 +105,11 @@ void itwTestBc7CallCounters(int32_t* out, int n);
  * tests/test_gpu_srgb_mips.py compares it with the counting definition of include/itw_dispatch.h around every threshold. */
 void itwTestSrgbEncode(const float* d_in, uint8_t* d_out, int64_t n);
 
+/* Which alpha histogram kernel the coverage rule and itwAlphaCoverage launch (csrc/mip_alpha.hip): 0, the product's, takes one
+ * LDS atomic per texel for every bin; 1 counts the 0 and 255 bins per wave (ballot + popcount).  Both give the same counts; tools/alpha_mip_timing.py times them against
+ * each other and tests/test_gpu_alpha_mips.py compares their output.  Process-wide. */
+void itwTestAlphaHistVariant(int spikes);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

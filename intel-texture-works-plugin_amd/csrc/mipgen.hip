@@ -17,6 +17,8 @@
 // Every kernel is a template over the texel kind: RGBA8, RGBA16F, and RGBA8 with sRGB colour (ITW_MIP_SRGB; SRGB = true), whose workgroups
 // hold the two tables of mipgen.hpp in 2 KiB of LDS -- 256 lanes load them with two coalesced dwords each -- and otherwise take the same
 // routes, launches and LDS layouts; the levels kept in registers and LDS between the steps are the stored codes' widened values, as for the others.
+// The kernels' bodies and the launch sequence of a chain are mip_kernels.hpp's, shared with mip_alpha.hip: the alpha-weighted kinds and the
+// coverage passes of itwGenerateMipChainAlpha, whose entry point, checks and staging are this file's (generate_checked, generate_chain).
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdint>
@@ -28,89 +30,17 @@
 #include "../../include/itw_test_hooks.h"
 #endif
 #include "mipgen.hpp"
+#include "mip_kernels.hpp"
 #include "normal_prep.hpp"
 #include "bcn_format.hpp"
 #include "host_rt.hpp"
 
 namespace itw {
 
-// one image of a chain; the table holds items * levels of them in DDS order (item-major, then level)
-struct MipImage { uint8_t* ptr; int64_t stride; };
-
-// N consecutive texels at `p` (PX aligned): one vector access where the address allows, texel by texel otherwise
-template <int PX, bool SRGB, int N>
-__device__ __forceinline__ void mip_load_row(const uint8_t* p, MipTexel* t, const MipSrgbTables* srgb)
-{
-    constexpr int W = N * PX / 4;
-    uint32_t w[W];
-    if (W >= 4 && ((uintptr_t)p & 15) == 0) {
-#pragma unroll
-        for (int i = 0; i < W / 4; i++) {
-            const uint4 v = reinterpret_cast<const uint4*>(p)[i];
-            w[4 * i] = v.x; w[4 * i + 1] = v.y; w[4 * i + 2] = v.z; w[4 * i + 3] = v.w;
-        }
-    } else if constexpr (PX == 8) {
-#pragma unroll
-        for (int i = 0; i < N; i++) { const uint2 v = reinterpret_cast<const uint2*>(p)[i]; w[2 * i] = v.x; w[2 * i + 1] = v.y; }
-    } else {
-#pragma unroll
-        for (int i = 0; i < N; i++) w[i] = reinterpret_cast<const uint32_t*>(p)[i];
-    }
-#pragma unroll
-    for (int i = 0; i < N; i++) {
-        if constexpr (PX == 4) t[i] = mip_widen<4, SRGB>(w[i], 0u, srgb);
-        else                   t[i] = mip_widen<8>(w[2 * i], w[2 * i + 1]);
-    }
-}
-
-template <int PX, bool SRGB>
-__device__ __forceinline__ MipTexel mip_load(const uint8_t* p, const MipSrgbTables* srgb)
-{
-    MipTexel t;
-    mip_load_row<PX, SRGB, 1>(p, &t, srgb);
-    return t;
-}
-
-// one texel's stored words at `p`
-template <int PX>
-__device__ __forceinline__ void mip_store_words(uint8_t* p, uint32_t lo, uint32_t hi)
-{
-    if constexpr (PX == 4) *reinterpret_cast<uint32_t*>(p) = lo;
-    else                   *reinterpret_cast<uint2*>(p) = make_uint2(lo, hi);
-}
-
-// rounds N (1 or 2) consecutive texels to the format and stores them at `p`; `t` becomes the stored values widened
-template <int PX, bool SRGB, int N>
-__device__ __forceinline__ void mip_store_row(uint8_t* p, MipTexel* t, const MipSrgbTables* srgb)
-{
-    uint32_t lo[N], hi[N];
-#pragma unroll
-    for (int i = 0; i < N; i++) mip_round<PX, SRGB>(t[i], lo[i], hi[i], srgb);
-    if constexpr (N == 2) {
-        if (PX == 8 && ((uintptr_t)p & 15) == 0) { *reinterpret_cast<uint4*>(p) = make_uint4(lo[0], hi[0], lo[1], hi[1]); return; }
-        if (PX == 4 && ((uintptr_t)p & 7) == 0)  { *reinterpret_cast<uint2*>(p) = make_uint2(lo[0], lo[1]); return; }
-    }
-#pragma unroll
-    for (int i = 0; i < N; i++) mip_store_words<PX>(p + i * PX, lo[i], hi[i]);
-}
-
-// The workgroup's sRGB tables (mipgen.hpp), 2 KiB of LDS beside what the kernel holds there; nothing, and a null pointer, for the other kinds.
-// Every lane of the 256 calls it once, before any lane leaves: it ends with a barrier.
-template <bool SRGB>
-__device__ __forceinline__ const MipSrgbTables* mip_srgb_tables()
-{
-    if constexpr (SRGB) {
-        __shared__ MipSrgbTables tables;
-        mip_srgb_fill(&tables);
-        return &tables;
-    } else {
-        return nullptr;
-    }
-}
-
-// LDS regions of the pyramid kernel, in widened texels: level +2 (16 x 16), +3 (8 x 8), +4 (4 x 4), +5 (2 x 2)
-constexpr int kPyrLds = 256 + 64 + 16 + 4;
-
+// The plain kinds.  The tail and level kernels' bodies are mip_kernels.hpp's, shared with the alpha-weighted kinds of mip_alpha.hip.  The
+// pyramid kernel keeps its body here and mip_kernels.hpp holds a copy for the weighted kind (the filter call is the one difference): as a
+// wrapper around the shared body mip_pyramid_kernel<4, false> compiled to 32 VGPRs where it has 29, and tests/test_srgb_mips_cpu.py pins
+// the plain kernels' registers, LDS and scratch to what they were.
 template <int PX, bool SRGB>
 __global__ void __launch_bounds__(256)
 mip_pyramid_kernel(const MipImage* __restrict__ table, int32_t levels, int32_t src_level, int32_t nout, int32_t tiles_x, int32_t tiles_per_item)
@@ -166,78 +96,26 @@ mip_pyramid_kernel(const MipImage* __restrict__ table, int32_t levels, int32_t s
     }
 }
 
-// source level `src_level` of w x h, powers of two, at most 64 x 32 or 32 x 64 (launch_chain gives 64 x 64 to the pyramid kernel); one
-// workgroup per item, `nout` levels down.  Levels live in LDS as stored words: odd ones (+1 <= 512 texels, +3, +5) in buf_a, even ones
-// (+2 <= 128 texels, +4, +6) in buf_b; the barrier that ends a level also ends the reads of the buffer the next level overwrites.
 template <int PX, bool SRGB>
 __global__ void __launch_bounds__(256)
 mip_tail_kernel(const MipImage* __restrict__ table, int32_t levels, int32_t src_level, int32_t nout, int32_t w, int32_t h)
 {
-    __shared__ uint2 buf_a[512], buf_b[128];
-    const MipSrgbTables* srgb = mip_srgb_tables<SRGB>();
-    const MipImage* im = table + (int64_t)blockIdx.x * levels + src_level;
-    int32_t sw = w, sh = h;
-    for (int k = 1; k <= nout; k++) {
-        const int32_t ow = sw > 1 ? sw >> 1 : 1, oh = sh > 1 ? sh >> 1 : 1;
-        const uint2* sl = (k & 1) ? buf_b : buf_a;                        // level k - 1 (k >= 2)
-        uint2* dl = (k & 1) ? buf_a : buf_b;                              // level k
-        const MipImage s = im[k - 1], d = im[k];
-        for (int32_t idx = threadIdx.x; idx < ow * oh; idx += 256) {
-            const int32_t y = idx / ow, x = idx - y * ow;
-            const int32_t x0 = 2 * x, x1 = sw > 1 ? x0 + 1 : x0, y0 = 2 * y, y1 = sh > 1 ? y0 + 1 : y0;
-            MipTexel p0, p1, p2, p3;
-            if (k == 1) {
-                const uint8_t* r0 = s.ptr + y0 * s.stride, * r1 = s.ptr + y1 * s.stride;
-                p0 = mip_load<PX, SRGB>(r0 + (int64_t)x0 * PX, srgb); p1 = mip_load<PX, SRGB>(r1 + (int64_t)x0 * PX, srgb);
-                p2 = mip_load<PX, SRGB>(r0 + (int64_t)x1 * PX, srgb); p3 = mip_load<PX, SRGB>(r1 + (int64_t)x1 * PX, srgb);
-            } else {
-                const uint2 a = sl[y0 * sw + x0], b = sl[y1 * sw + x0], c = sl[y0 * sw + x1], e = sl[y1 * sw + x1];
-                p0 = mip_widen<PX, SRGB>(a.x, a.y, srgb); p1 = mip_widen<PX, SRGB>(b.x, b.y, srgb);
-                p2 = mip_widen<PX, SRGB>(c.x, c.y, srgb); p3 = mip_widen<PX, SRGB>(e.x, e.y, srgb);
-            }
-            MipTexel t = mip_box(p0, p1, p2, p3);
-            uint32_t lo, hi;
-            mip_round<PX, SRGB>(t, lo, hi, srgb);
-            mip_store_words<PX>(d.ptr + y * d.stride + (int64_t)x * PX, lo, hi);
-            dl[idx] = make_uint2(lo, hi);
-        }
-        __syncthreads();
-        sw = ow; sh = oh;
-    }
+    mip_tail_body<PX, SRGB, false>(table, levels, src_level, nout, w, h);
 }
 
-// level `dst_level` (ow x oh) of every item from its level dst_level - 1 (sw x sh); lanes 64 across, 4 down; grid (x tiles, y tiles, items)
 template <int PX, bool LINEAR, bool SRGB>
 __global__ void __launch_bounds__(256)
 mip_level_kernel(const MipImage* __restrict__ table, int32_t levels, int32_t dst_level, int32_t sw, int32_t sh, int32_t ow, int32_t oh,
                  float scale_x, float scale_y)
 {
-    const MipSrgbTables* srgb = mip_srgb_tables<SRGB>();
-    const int32_t x = (int32_t)blockIdx.x * 64 + (threadIdx.x & 63), y = (int32_t)blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (x >= ow || y >= oh) return;
-    const MipImage* im = table + (int64_t)blockIdx.z * levels + dst_level;
-    const MipImage s = im[-1], d = im[0];
-    MipTexel t;
-    if (LINEAR) {
-        const MipTap tx = mip_linear_tap(x, scale_x, sw), ty = mip_linear_tap(y, scale_y, sh);
-        const uint8_t* r0 = s.ptr + (int64_t)ty.u0 * s.stride, * r1 = s.ptr + (int64_t)ty.u1 * s.stride;
-        t = mip_bilinear(mip_load<PX, SRGB>(r0 + (int64_t)tx.u0 * PX, srgb), mip_load<PX, SRGB>(r0 + (int64_t)tx.u1 * PX, srgb),
-                         mip_load<PX, SRGB>(r1 + (int64_t)tx.u0 * PX, srgb), mip_load<PX, SRGB>(r1 + (int64_t)tx.u1 * PX, srgb), tx, ty);
-    } else {
-        const int32_t x0 = 2 * x, x1 = sw > 1 ? x0 + 1 : x0, y0 = 2 * y, y1 = sh > 1 ? y0 + 1 : y0;
-        const uint8_t* r0 = s.ptr + (int64_t)y0 * s.stride, * r1 = s.ptr + (int64_t)y1 * s.stride;
-        t = mip_box(mip_load<PX, SRGB>(r0 + (int64_t)x0 * PX, srgb), mip_load<PX, SRGB>(r1 + (int64_t)x0 * PX, srgb),
-                    mip_load<PX, SRGB>(r0 + (int64_t)x1 * PX, srgb), mip_load<PX, SRGB>(r1 + (int64_t)x1 * PX, srgb));
-    }
-    mip_store_row<PX, SRGB, 1>(d.ptr + (int64_t)y * d.stride + (int64_t)x * PX, &t, srgb);
+    mip_level_body<PX, LINEAR, SRGB, false>(table, levels, dst_level, sw, sh, ow, oh, scale_x, scale_y);
 }
 
 } // namespace itw
 
 namespace {
 
-inline int mip_dim(int v, int level) { return std::max(1, v >> std::min(level, 30)); }
-inline bool pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
+using itw::mip_dim;
 
 // What one launch covers, checked by the entry points before any device work: the per-level kernel's grid has a block row per 4 texel rows
 // of level 1 and a plane per item (65 535 each), the pyramid kernel a block per tile and item.
@@ -248,44 +126,31 @@ void check_launch_limits(const char* who, int w, int h, int items)
     if ((int64_t)(w / 64 + 1) * (h / 64 + 1) * items > (int64_t)0x7fffffff) itw::fail_msg("%s: %d items of %d x %d are more tiles than one launch covers", who, items, w, h);
 }
 
-// the launches of one chain: `table` is on the device, the base is w x h, all `items` alike and within check_launch_limits
+// the launches of one plain chain (mip_kernels.hpp launch_chain): `table` is on the device, all `items` alike and within check_launch_limits
 template <int PX, bool SRGB>
-void launch_chain(const itw::MipImage* table, int items, int levels, int w, int h, bool per_level, hipStream_t st)
+void launch_plain_chain(const itw::MipImage* table, int items, int levels, int w, int h, bool per_level, hipStream_t st)
 {
-    const bool box = pow2(w) && pow2(h);
-    int cur = 0;                                                          // the last level that exists
-    while (cur < levels - 1) {
-        const int sw = mip_dim(w, cur), sh = mip_dim(h, cur);
-        if (box && !per_level && sw >= 64 && sh >= 64) {
-            const int nout = std::min(6, levels - 1 - cur), tiles_x = sw / 64, tiles = tiles_x * (sh / 64);
-            hipLaunchKernelGGL((itw::mip_pyramid_kernel<PX, SRGB>), dim3((unsigned)(tiles * items)), dim3(256), 0, st, table, levels, cur, nout, tiles_x, tiles);
-            cur += nout;
-        } else if (box && !per_level && sw <= 64 && sh <= 64) {       // (not both 64: that was a tile)
-            hipLaunchKernelGGL((itw::mip_tail_kernel<PX, SRGB>), dim3((unsigned)items), dim3(256), 0, st, table, levels, cur, levels - 1 - cur, sw, sh);
-            cur = levels - 1;
-        } else {
-            const int ow = mip_dim(w, cur + 1), oh = mip_dim(h, cur + 1);
-            const dim3 grid((unsigned)((ow + 63) / 64), (unsigned)((oh + 3) / 4), (unsigned)items);
-            const float scale_x = (float)sw / (float)ow, scale_y = (float)sh / (float)oh;
-            if (box) hipLaunchKernelGGL((itw::mip_level_kernel<PX, false, SRGB>), grid, dim3(256), 0, st, table, levels, cur + 1, sw, sh, ow, oh, scale_x, scale_y);
-            else     hipLaunchKernelGGL((itw::mip_level_kernel<PX, true, SRGB>), grid, dim3(256), 0, st, table, levels, cur + 1, sw, sh, ow, oh, scale_x, scale_y);
-            cur += 1;
-        }
-        ITW_CHECK(hipGetLastError());
-    }
+    static const itw::MipKernels k = { itw::mip_pyramid_kernel<PX, SRGB>, itw::mip_tail_kernel<PX, SRGB>, itw::mip_level_kernel<PX, false, SRGB>,
+                                       itw::mip_level_kernel<PX, true, SRGB> };
+    itw::launch_chain(k, table, items, levels, w, h, per_level, st);
 }
 
 size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
+// the alpha rules of a call, as its checks left them: both off for every call but itwGenerateMipChainAlpha's
+struct AlphaRules { bool weight = false; int coverage_ref = 0; itw_mip_coverage* report = nullptr; };
+
 // everything that needs the device: a chain that passed the checks, all of one pointer kind, levels >= 2
-void generate_chain(const rgba_surface* im, int items, int levels, int px, bool srgb, bool per_level, bool dev)
+void generate_chain(const rgba_surface* im, int items, int levels, int px, bool srgb, bool per_level, bool dev, const AlphaRules& alpha)
 {
     hipStream_t st = (hipStream_t)itwGetStream();
     const int count = items * levels;
     static thread_local std::vector<itw::MipImage> desc;                  // grow-only, like the device buffer it is copied into
     desc.resize((size_t)count);
-    // the thread's buffer: [table] [staged images (host pointers), rows of a 16-byte multiple]
+    // the thread's buffer: [table] [the coverage passes' work] [staged images (host pointers), rows of a 16-byte multiple]
     size_t bytes = up256((size_t)count * sizeof(itw::MipImage));
+    const size_t work_off = bytes;
+    if (alpha.coverage_ref) bytes += itw::coverage_work_bytes(items, levels);
     std::vector<size_t> stage_off(dev ? 0 : (size_t)count);
     for (int i = 0; i < count; i++) {
         desc[(size_t)i].ptr = im[i].ptr; desc[(size_t)i].stride = im[i].stride;
@@ -305,16 +170,51 @@ void generate_chain(const rgba_surface* im, int items, int levels, int px, bool 
         }
     ITW_CHECK(hipMemcpyAsync(base, desc.data(), (size_t)count * sizeof(itw::MipImage), hipMemcpyHostToDevice, st));
     const itw::MipImage* table = reinterpret_cast<const itw::MipImage*>(base);
-    if (srgb)         launch_chain<4, true>(table, items, levels, im[0].width, im[0].height, per_level, st);     // (the entry point refused it with px 8)
-    else if (px == 4) launch_chain<4, false>(table, items, levels, im[0].width, im[0].height, per_level, st);
-    else              launch_chain<8, false>(table, items, levels, im[0].width, im[0].height, per_level, st);
-    if (dev) { itw::decode_scratch_done(st); return; }                    // resident: asynchronous on the thread's stream
+    const int w = im[0].width, h = im[0].height;
+    if (alpha.weight) itw::launch_chain_weighted(table, items, levels, w, h, srgb, per_level, st);                   // (RGBA8: the entry point takes no other)
+    else if (srgb)    launch_plain_chain<4, true>(table, items, levels, w, h, per_level, st);                        // (the entry point refused it with px 8)
+    else if (px == 4) launch_plain_chain<4, false>(table, items, levels, w, h, per_level, st);
+    else              launch_plain_chain<8, false>(table, items, levels, w, h, per_level, st);
+    if (alpha.coverage_ref) {                                             // over the chain as generated, before anything comes back
+        itw::launch_coverage(desc.data(), items, levels, w, h, alpha.coverage_ref, base + work_off, st);
+        if (alpha.report)
+            ITW_CHECK(hipMemcpyAsync(alpha.report, base + work_off + itw::coverage_report_offset(items, levels), (size_t)count * sizeof(itw_mip_coverage),
+                                     hipMemcpyDeviceToHost, st));
+    }
+    if (dev) {                                                            // resident: asynchronous on the thread's stream, but for a report
+        if (alpha.report) ITW_CHECK(hipStreamSynchronize(st));
+        itw::decode_scratch_done(st);
+        return;
+    }
     for (int i = 0; i < count; i++)                                       // only the written levels come back, width x height only
         if (i % levels != 0)
             ITW_CHECK(hipMemcpy2DAsync(im[i].ptr, (size_t)im[i].stride, desc[(size_t)i].ptr, (size_t)desc[(size_t)i].stride, (size_t)im[i].width * px,
                                        (size_t)im[i].height, hipMemcpyDeviceToHost, st));
     ITW_CHECK(hipStreamSynchronize(st));
     itw::decode_scratch_done(st);
+}
+
+// the checks of a call's itw_mip_alpha, which come before every other: `who` names the entry point
+AlphaRules check_alpha(const char* who, const itw_mip_alpha* alpha, itw_mip_coverage* report)
+{
+    AlphaRules r;
+    if (alpha) {
+        if (alpha->struct_size != sizeof(itw_mip_alpha)) itw::fail_msg("%s: itw_mip_alpha.struct_size %u (%zu)", who, alpha->struct_size, sizeof(itw_mip_alpha));
+        if (alpha->reserved != 0) itw::fail_msg("%s: itw_mip_alpha.reserved is 0x%x, not 0", who, alpha->reserved);
+        if (alpha->weight_colour > 1) itw::fail_msg("%s: itw_mip_alpha.weight_colour %u (0 or 1)", who, alpha->weight_colour);
+        if (alpha->coverage_ref > 255) itw::fail_msg("%s: itw_mip_alpha.coverage_ref %u (1 .. 255, 0: off)", who, alpha->coverage_ref);
+        r.weight = alpha->weight_colour == 1;
+        r.coverage_ref = (int)alpha->coverage_ref;
+    }
+    if (report && !r.coverage_ref) itw::fail_msg("%s: a report without coverage_ref: there is nothing to report", who);
+    r.report = report;
+    return r;
+}
+
+// what the coverage rule's 64-bit arithmetic holds: cov0 * n of a level, n <= N0 / 2
+void check_coverage_size(const char* who, int w, int h)
+{
+    if ((int64_t)w * h > ((int64_t)1 << 31)) itw::fail_msg("%s: coverage over a base of %d x %d: more than 2^31 texels", who, w, h);
 }
 
 // the device-side chain of itwCompressImageMipped: the thread's own grow-only buffer (the staging buffer above is in use by the stages the
@@ -417,44 +317,62 @@ extern "C" int64_t itwMipChainLayout(int width, int height, int items, int level
     return off;
 }
 
-extern "C" int itwGenerateMipChain(const rgba_surface* images, int items, int levels, int pixel_size, uint32_t flags)
+namespace {
+
+// itwGenerateMipChain and itwGenerateMipChainAlpha: one set of checks, `who` names the entry point in every message
+int generate_checked(const char* who, const rgba_surface* images, int items, int levels, int pixel_size, uint32_t flags, const itw_mip_alpha* alpha_in,
+                     itw_mip_coverage* report)
 {
     bool dev = false;
     itw::clear_failure();
     const bool ok = itw::guarded([&] {
-        if (pixel_size != 4 && pixel_size != 8) itw::fail_msg("itwGenerateMipChain: pixel_size %d (4: RGBA8, 8: RGBA16F)", pixel_size);
-        if (flags & ~(uint32_t)(ITW_MIP_PER_LEVEL | ITW_MIP_SRGB)) itw::fail_msg("itwGenerateMipChain: unknown flag bits 0x%x", flags);
-        if ((flags & ITW_MIP_SRGB) && pixel_size != 4) itw::fail_msg("itwGenerateMipChain: ITW_MIP_SRGB is for RGBA8 texels (pixel_size 4): RGBA16F is linear already");
-        if (items < 0) itw::fail_msg("itwGenerateMipChain: %d items", items);
+        const AlphaRules alpha = check_alpha(who, alpha_in, report);
+        if (pixel_size != 4 && pixel_size != 8) itw::fail_msg("%s: pixel_size %d (4: RGBA8, 8: RGBA16F)", who, pixel_size);
+        if (flags & ~(uint32_t)(ITW_MIP_PER_LEVEL | ITW_MIP_SRGB)) itw::fail_msg("%s: unknown flag bits 0x%x", who, flags);
+        if ((flags & ITW_MIP_SRGB) && pixel_size != 4) itw::fail_msg("%s: ITW_MIP_SRGB is for RGBA8 texels (pixel_size 4): RGBA16F is linear already", who);
+        if (items < 0) itw::fail_msg("%s: %d items", who, items);
         if (items == 0 || levels <= 1) return;
-        if (!images) itw::fail_msg("itwGenerateMipChain: null images pointer");
-        if ((int64_t)items * levels > (int64_t)0x7fffffff / 64) itw::fail_msg("itwGenerateMipChain: %d items of %d levels", items, levels);
+        if (!images) itw::fail_msg("%s: null images pointer", who);
+        if ((int64_t)items * levels > (int64_t)0x7fffffff / 64) itw::fail_msg("%s: %d items of %d levels", who, items, levels);
         const int w = images[0].width, h = images[0].height, full = itwMipLevels(w, h);
-        if (full == 0) itw::fail_msg("itwGenerateMipChain: the base is %d x %d", w, h);
-        if (levels > full) itw::fail_msg("itwGenerateMipChain: %d levels, a full chain of %d x %d has %d", levels, w, h, full);
-        check_launch_limits("itwGenerateMipChain", w, h, items);
+        if (full == 0) itw::fail_msg("%s: the base is %d x %d", who, w, h);
+        if (levels > full) itw::fail_msg("%s: %d levels, a full chain of %d x %d has %d", who, levels, w, h, full);
+        check_launch_limits(who, w, h, items);
+        if (alpha.coverage_ref) check_coverage_size(who, w, h);
         for (int i = 0; i < items * levels; i++) {
             const rgba_surface& s = images[i];
             const int item = i / levels, l = i % levels;
-            if (!s.ptr) itw::fail_msg("itwGenerateMipChain: item %d level %d has a null texel pointer", item, l);
+            if (!s.ptr) itw::fail_msg("%s: item %d level %d has a null texel pointer", who, item, l);
             if (l == 0 && (s.width != w || s.height != h))
-                itw::fail_msg("itwGenerateMipChain: the base of item %d is %d x %d, that of item 0 %d x %d", item, s.width, s.height, w, h);
+                itw::fail_msg("%s: the base of item %d is %d x %d, that of item 0 %d x %d", who, item, s.width, s.height, w, h);
             if (s.width != mip_dim(w, l) || s.height != mip_dim(h, l))
-                itw::fail_msg("itwGenerateMipChain: item %d level %d is %d x %d, the chain's is %d x %d", item, l, s.width, s.height, mip_dim(w, l), mip_dim(h, l));
+                itw::fail_msg("%s: item %d level %d is %d x %d, the chain's is %d x %d", who, item, l, s.width, s.height, mip_dim(w, l), mip_dim(h, l));
             if ((int64_t)s.stride < (int64_t)s.width * pixel_size)
-                itw::fail_msg("itwGenerateMipChain: item %d level %d: stride %d < %lld bytes per row", item, l, s.stride, (long long)s.width * pixel_size);
+                itw::fail_msg("%s: item %d level %d: stride %d < %lld bytes per row", who, item, l, s.stride, (long long)s.width * pixel_size);
             const uintptr_t row_step = s.height > 1 ? (uintptr_t)(uint32_t)s.stride : 0;
             if (((uintptr_t)s.ptr | row_step) & (uintptr_t)(pixel_size - 1))
-                itw::fail_msg("itwGenerateMipChain: item %d level %d: texels are not %d-byte aligned", item, l, pixel_size);
+                itw::fail_msg("%s: item %d level %d: texels are not %d-byte aligned", who, item, l, pixel_size);
         }
         dev = itw::is_device_pointer(images[0].ptr);
         for (int i = 1; i < items * levels; i++)
             if (itw::is_device_pointer(images[i].ptr) != dev)
-                itw::fail_msg("itwGenerateMipChain: image %d is %s memory, image 0 %s: all images must be host or all device pointers", i,
+                itw::fail_msg("%s: image %d is %s memory, image 0 %s: all images must be host or all device pointers", who, i,
                               dev ? "host" : "device", dev ? "device" : "host");
-        generate_chain(images, items, levels, pixel_size, (flags & ITW_MIP_SRGB) != 0, (flags & ITW_MIP_PER_LEVEL) != 0, dev);
+        generate_chain(images, items, levels, pixel_size, (flags & ITW_MIP_SRGB) != 0, (flags & ITW_MIP_PER_LEVEL) != 0, dev, alpha);
     });
     return ok ? 0 : -1;
+}
+
+} // namespace
+
+extern "C" int itwGenerateMipChain(const rgba_surface* images, int items, int levels, int pixel_size, uint32_t flags)
+{
+    return generate_checked("itwGenerateMipChain", images, items, levels, pixel_size, flags, nullptr, nullptr);
+}
+
+extern "C" int itwGenerateMipChainAlpha(const rgba_surface* images, int items, int levels, uint32_t flags, const itw_mip_alpha* alpha, itw_mip_coverage* report)
+{
+    return generate_checked("itwGenerateMipChainAlpha", images, items, levels, 4, flags, alpha, report);
 }
 
 // the sRGB colour kind on the host (include/itw_dispatch.h): the tables of srgb_tables.h, E as the counting definition's binary search
@@ -500,12 +418,21 @@ extern "C" void itwTestSrgbEncode(const float* d_in, uint8_t* d_out, int64_t n)
 }
 #endif
 
-extern "C" bool itwCompressImageMippedEx(const rgba_surface* bases, int items, int levels, uint32_t normal_ops, uint32_t mip_flags, uint8_t* target,
-                                         int dxgi_format, const void* settings, ItwProgressFunc* progress, void* user)
+namespace {
+
+// itwCompressImageMippedEx, and itwCompressImageMippedAlpha when `alpha_call`: the same stages, the alpha rules handed to the generation
+bool compress_mipped(const rgba_surface* bases, int items, int levels, uint32_t normal_ops, uint32_t mip_flags, bool alpha_call, const itw_mip_alpha* alpha_in,
+                     uint8_t* target, int dxgi_format, const void* settings, ItwProgressFunc* progress, void* user)
 {
     bool done = false;
     itw::clear_failure();
     const bool ok = itw::guarded([&] {
+        AlphaRules alpha;
+        if (alpha_call) {
+            alpha = check_alpha("itwCompressImageMippedAlpha", alpha_in, nullptr);
+            if (dxgi_format == 95 || dxgi_format == 96) itw::fail_msg("itwCompressImageMippedAlpha: DXGI format %d, whose texels are RGBA16F: the alpha rules are for RGBA8 colour", dxgi_format);
+            if (dxgi_format == 81 || dxgi_format == 84) itw::fail_msg("itwCompressImageMippedAlpha: DXGI format %d, whose texels are signed codes, not colour", dxgi_format);
+        }
         if (normal_ops & ~7u) itw::fail_msg("itwCompressImageMipped: unknown ops bits 0x%x", normal_ops);
         if (mip_flags & ~(uint32_t)(ITW_MIP_PER_LEVEL | ITW_MIP_SRGB)) itw::fail_msg("itwCompressImageMipped: unknown mip flag bits 0x%x", mip_flags);
         itw::chain_check_with(bases, items, target, dxgi_format, settings);       // counts, null pointers, sizes, strides, format, settings
@@ -526,6 +453,7 @@ extern "C" bool itwCompressImageMippedEx(const rgba_surface* bases, int items, i
         if (levels == 0) levels = full;
         if ((int64_t)items * levels > (int64_t)0x7fffffff / 64) itw::fail_msg("itwCompressImageMipped: %d items of %d levels", items, levels);
         check_launch_limits("itwCompressImageMipped", w, h, items);
+        if (alpha.coverage_ref) check_coverage_size("itwCompressImageMippedAlpha", w, h);
         const bool dev = itw::is_device_pointer(bases[0].ptr);
         for (int i = 1; i < items; i++)
             if (itw::is_device_pointer(bases[i].ptr) != dev)
@@ -545,12 +473,27 @@ extern "C" bool itwCompressImageMippedEx(const rgba_surface* bases, int items, i
         auto stage = [](int rc, const char* what) { if (rc != 0) itw::fail_msg("itwCompressImageMipped: %s failed: %s", what, itwLastError()); };
         // the reference's order (IntelPlugin.cpp:2103-2152): flip level 0, generate the mips, normalise every level, compress every image
         if (normal_ops & 3u) stage(itwPrepareNormalMapChain(level0.data(), items, px, normal_ops & 3u), "the flip");
-        stage(itwGenerateMipChain(chain.data(), items, levels, px, mip_flags), "the mip chain");
+        if (alpha.weight || alpha.coverage_ref) stage(itwGenerateMipChainAlpha(chain.data(), items, levels, mip_flags, alpha_in, nullptr), "the mip chain");
+        else                                    stage(itwGenerateMipChain(chain.data(), items, levels, px, mip_flags), "the mip chain");
         if (normal_ops & 4u) stage(itwPrepareNormalMapChain(chain.data(), items * levels, px, 4u), "the normalise");
         done = itwCompressImageChainEx(chain.data(), items * levels, target, dxgi_format, settings, progress, user);
         t_chain.release(st);
     });
     return ok && done;
+}
+
+} // namespace
+
+extern "C" bool itwCompressImageMippedEx(const rgba_surface* bases, int items, int levels, uint32_t normal_ops, uint32_t mip_flags, uint8_t* target,
+                                         int dxgi_format, const void* settings, ItwProgressFunc* progress, void* user)
+{
+    return compress_mipped(bases, items, levels, normal_ops, mip_flags, false, nullptr, target, dxgi_format, settings, progress, user);
+}
+
+extern "C" bool itwCompressImageMippedAlpha(const rgba_surface* bases, int items, int levels, uint32_t mip_flags, const itw_mip_alpha* alpha, uint8_t* target,
+                                            int dxgi_format, const void* settings, ItwProgressFunc* progress, void* user)
+{
+    return compress_mipped(bases, items, levels, 0, mip_flags, true, alpha, target, dxgi_format, settings, progress, user);
 }
 
 extern "C" bool itwCompressImageMipped(const rgba_surface* bases, int items, int levels, uint32_t normal_ops, uint8_t* target, int dxgi_format,

@@ -132,4 +132,49 @@ __device__ __forceinline__ MipTexel mip_bilinear(const MipTexel& r00, const MipT
     return r;
 }
 
+// Alpha-weighted colour (include/itw_dispatch.h, "Mip chains", rule A; RGBA8 kinds): each tap's R, G, B times its alpha code, one fp32
+// multiply; the filter as it stands over that and over alpha; then R, G, B divided by the filtered, unrounded alpha, one correctly rounded
+// fp32 division (the build passes -fhip-fp32-correctly-rounded-divide-sqrt).  Where that alpha is not above 0 no tap is visible and the
+// colour is the plain rule's, formed here from the taps the caller still holds.  Alpha itself is the plain rule's in every case.
+__device__ __forceinline__ MipTexel mip_premultiply(const MipTexel& p)
+{
+    MipTexel r;
+    r.c[0] = p.c[0] * p.c[3]; r.c[1] = p.c[1] * p.c[3]; r.c[2] = p.c[2] * p.c[3]; r.c[3] = p.c[3];
+    return r;
+}
+__device__ __forceinline__ void mip_unpremultiply(MipTexel& r, const MipTexel& plain)
+{
+    const float va = r.c[3];
+    if (va > 0.0f) { r.c[0] = r.c[0] / va; r.c[1] = r.c[1] / va; r.c[2] = r.c[2] / va; }
+    else           { r.c[0] = plain.c[0]; r.c[1] = plain.c[1]; r.c[2] = plain.c[2]; }
+}
+
+// the two filters of either kind: WEIGHT = false is mip_box / mip_bilinear and nothing else
+template <bool WEIGHT>
+__device__ __forceinline__ MipTexel mip_box_kind(const MipTexel& p0, const MipTexel& p1, const MipTexel& p2, const MipTexel& p3)
+{
+    if constexpr (!WEIGHT) {
+        return mip_box(p0, p1, p2, p3);
+    } else {
+        MipTexel r = mip_box(mip_premultiply(p0), mip_premultiply(p1), mip_premultiply(p2), mip_premultiply(p3));
+        if (r.c[3] > 0.0f) mip_unpremultiply(r, r);
+        else               mip_unpremultiply(r, mip_box(p0, p1, p2, p3));
+        return r;
+    }
+}
+
+template <bool WEIGHT>
+__device__ __forceinline__ MipTexel mip_bilinear_kind(const MipTexel& r00, const MipTexel& r01, const MipTexel& r10, const MipTexel& r11, const MipTap& x,
+                                                      const MipTap& y)
+{
+    if constexpr (!WEIGHT) {
+        return mip_bilinear(r00, r01, r10, r11, x, y);
+    } else {
+        MipTexel r = mip_bilinear(mip_premultiply(r00), mip_premultiply(r01), mip_premultiply(r10), mip_premultiply(r11), x, y);
+        if (r.c[3] > 0.0f) mip_unpremultiply(r, r);
+        else               mip_unpremultiply(r, mip_bilinear(r00, r01, r10, r11, x, y));
+        return r;
+    }
+}
+
 } // namespace itw

@@ -26,7 +26,8 @@ EXPORTED_SYMBOLS = tuple(
     + ["itwCompressImageSliced", "itwCompressImageSlicedEx", "itwChainBytes", "itwCompressImageChain", "itwCompressImageChainEx", "itwCompressImageRefined", "itwCompressImageRefinedTo", "itwPsnrToTotalSse", "itwCompressImageChainRefined", "itwCompressImageChainRefinedTo", "itwChainPsnrToTotalSse", "itwSetSliceWindow", "itwSliceWindow", "itwSliceWindowFor", "itwPadToMultipleOf4", "itwFreeSurface", "itwPadToMultipleOf4Device",
        "itwConvertToRGBA8Device", "itwConvertToRGBA16FDevice",
        "itwPrepareNormalMapChain", "itwCompressNormalMapChain", "itwQuantizeNormalMapChain", "itwCompressSignedNormalMapChain", "itwCompressSignedNormalMapMipped", "itwCubeCrossFaces",
-       "itwMipLevels", "itwMipChainLayout", "itwGenerateMipChain", "itwCompressImageMipped", "itwCompressImageMippedEx", "itwSrgbToLinear", "itwLinearToSrgb"]
+       "itwMipLevels", "itwMipChainLayout", "itwGenerateMipChain", "itwCompressImageMipped", "itwCompressImageMippedEx", "itwSrgbToLinear", "itwLinearToSrgb",
+       "itwGenerateMipChainAlpha", "itwCompressImageMippedAlpha", "itwAlphaCoverage"]
     # include/itw_multigpu.h: one surface over all GPUs, one process
     + ["itwMultiGpuRanks", "itwMultiGpuTransport", "itwMultiGpuPeerLinks", "itwCompressImageMultiGPU", "itwCompressImageMultiGPUEx", "itwCompressImageMultiGPUBands",
        "itwMultiGpuSetInterleave", "itwMultiGpuPieces"]
@@ -41,7 +42,7 @@ EXPORTED_SYMBOLS = tuple(
 # include/itw_test_hooks.h: exported by libispc_texcomp_test.so only (the same sources built with -DITW_TEST_HOOKS), never by the product
 TEST_HOOK_SYMBOLS = ("itwTestRcp", "itwTestRsqrt", "itwTestF2I", "itwTestBc7TwoSubsetBounds", "itwTestBc7RotationBounds", "itwTestBc7F02Scan", "itwTestBc45IndexTable", "itwTestBc45ClosestS",
                      "itwMultiGpuTestInjectFailure", "itwTestCombinerHold", "itwTestCombinerCounters", "itwTestBc7RouteCounters", "itwTestBc7RouteCountersReset",
-                     "itwTestBc7CallCountersArm", "itwTestBc7CallCounters", "itwTestSrgbEncode")
+                     "itwTestBc7CallCountersArm", "itwTestBc7CallCounters", "itwTestSrgbEncode", "itwTestAlphaHistVariant")
 # enum itw_test_bc7_call_counter (include/itw_test_hooks.h): what itwTestBc7CallCounters fills; the per-band ones are band 0 then band 1
 BC7_CALL_COUNTERS = ("pilot_listed", "pilot_sampled", "pilot_flag", "rot00", "rot01", "rot02", "rot10", "rot11", "rot12", "listed0", "listed1",
                      "pairs0", "pairs1", "overflow0", "overflow1", "redo0", "redo1")
@@ -328,6 +329,8 @@ def _load(path, hooks):
             L.itwTestBc7CallCounters.restype = None
             L.itwTestSrgbEncode.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
             L.itwTestSrgbEncode.restype = None
+            L.itwTestAlphaHistVariant.argtypes = [C.c_int]
+            L.itwTestAlphaHistVariant.restype = None
         # dispatch layer (itw_dispatch.h)
         L.GetProcessorCount.restype = C.c_int
         L.GetBytesPerBlock.argtypes = [C.c_int]
@@ -423,6 +426,12 @@ def _load(path, hooks):
         L.itwCompressImageMipped.restype = C.c_bool
         L.itwCompressImageMippedEx.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.itwCompressImageMippedEx.restype = C.c_bool
+        L.itwGenerateMipChainAlpha.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p]
+        L.itwGenerateMipChainAlpha.restype = C.c_int
+        L.itwCompressImageMippedAlpha.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.itwCompressImageMippedAlpha.restype = C.c_bool
+        L.itwAlphaCoverage.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.itwAlphaCoverage.restype = C.c_int
         L.itwSrgbToLinear.argtypes = [C.c_uint8]
         L.itwSrgbToLinear.restype = C.c_float
         L.itwLinearToSrgb.argtypes = [C.c_float]
@@ -1011,6 +1020,34 @@ MIP_PER_LEVEL = 1     # ITW_MIP_PER_LEVEL (include/itw_dispatch.h)
 MIP_SRGB = 4          # ITW_MIP_SRGB: R, G, B of RGBA8 texels are sRGB coded and filtered in linear light
 
 
+class MipAlpha(C.Structure):
+    """struct itw_mip_alpha (include/itw_dispatch.h): the two rules for cut-out textures, both off by default.  16 bytes."""
+    _fields_ = [("struct_size", C.c_uint32), ("weight_colour", C.c_uint32), ("coverage_ref", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def __init__(self, weight_colour=0, coverage_ref=0, struct_size=16, reserved=0):
+        super().__init__(struct_size, int(weight_colour), int(coverage_ref), reserved)
+
+
+class MipCoverage(C.Structure):
+    """struct itw_mip_coverage: one report row per image of a chain, DDS order.  32 bytes."""
+    _fields_ = [("texels", C.c_uint64), ("covered_plain", C.c_uint64), ("covered", C.c_uint64), ("threshold", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+def alpha_coverage(images, ref):
+    """itwAlphaCoverage: the number of texels with alpha >= ref in each RGBA8 image of a list (numpy arrays or CUDA torch tensors (H, W, 4)
+    uint8, any sizes, rows may be strided): a list of ints.  One image gives one int."""
+    single = hasattr(images, "shape")
+    imgs = [images] if single else list(images)
+    if imgs and hasattr(imgs[0], "data_ptr"):
+        import torch
+        lib().itwSetStream(torch.cuda.current_stream(imgs[0].device).cuda_stream)
+    out = (C.c_uint64 * max(1, len(imgs)))()
+    if lib().itwAlphaCoverage(C.cast(_surfaces(imgs), C.c_void_p), len(imgs), int(ref), C.cast(out, C.c_void_p)) != 0:
+        raise ValueError("itwAlphaCoverage refused the call: " + (last_error() or "bad arguments"))
+    got = [int(out[i]) for i in range(len(imgs))]
+    return got[0] if single else got
+
+
 def srgb_to_linear(code):
     """itwSrgbToLinear: D[code] of the sRGB mip filter (include/itw_dispatch.h), the fp32 nearest to the linear light of sRGB code 0..255."""
     assert 0 <= int(code) <= 255
@@ -1054,12 +1091,13 @@ def mip_chain_layout(width, height, items=1, levels=0, pixel_size=4):
     return n, [(int(out[i].ptr or 0), out[i].width, out[i].height, out[i].stride) for i in range(count)]
 
 
-def generate_mips(base_or_bases, levels=0, per_level=False, srgb=False):
+def generate_mips(base_or_bases, levels=0, per_level=False, srgb=False, alpha_weight=False, alpha_coverage=0, report=False):
     """itwGenerateMipChain: the mip levels of one base image or a list of equally sized ones (cube faces, array items): host numpy arrays or
     CUDA torch tensors (H, W, 4), uint8 (RGBA8) or 2-byte elements (RGBA16F half bits), all of one kind.  DirectXTex's box filter when width
     and height are powers of two, else its linear filter (include/itw_dispatch.h).  levels == 0: the full chain.  per_level forces one
     launch per level; srgb (uint8 only) filters R, G, B as sRGB codes in linear light (ITW_MIP_SRGB).  Returns the list of levels [base, level 1, ...] for one base, a list of such lists for a list; the bases themselves
-    are level 0 and are not copied.  Device tensors: asynchronous on torch's current stream."""
+    are level 0 and are not copied.  Device tensors: asynchronous on torch's current stream.  alpha_weight / alpha_coverage (uint8 only) are
+    the rules of itwGenerateMipChainAlpha; with report=True the result is (levels, rows), rows the MipCoverage list in DDS order."""
     single = hasattr(base_or_bases, "shape")
     bases = [base_or_bases] if single else list(base_or_bases)
     assert bases, "no base image"
@@ -1076,13 +1114,16 @@ def generate_mips(base_or_bases, levels=0, per_level=False, srgb=False):
         else:
             import numpy as np
             chains.append([b] + [np.empty((max(1, h >> l), max(1, w >> l), 4), dtype=b.dtype) for l in range(1, n)])
-    generate_mips_into(chains, per_level=per_level, srgb=srgb)
+    rows = generate_mips_into(chains, per_level=per_level, srgb=srgb, alpha_weight=alpha_weight, alpha_coverage=alpha_coverage, report=report)
+    if report:
+        return (chains[0] if single else chains), rows[1]
     return chains[0] if single else chains
 
 
-def generate_mips_into(chains, per_level=False, srgb=False):
+def generate_mips_into(chains, per_level=False, srgb=False, alpha_weight=False, alpha_coverage=0, report=False):
     """itwGenerateMipChain over caller-made levels: `chains` is a list of items, each the list of its levels (level 0 filled in), which may
-    be strided views of larger arrays / tensors.  Raises ValueError where the call returns -1."""
+    be strided views of larger arrays / tensors.  Raises ValueError where the call returns -1.  alpha_weight, alpha_coverage or report make
+    it itwGenerateMipChainAlpha (RGBA8); with report=True it returns (chains, [MipCoverage] in DDS order) and is synchronous."""
     flat = [lv for ch in chains for lv in ch]
     on_device = hasattr(flat[0], "data_ptr")
     es = flat[0].element_size() if on_device else flat[0].itemsize
@@ -1090,16 +1131,26 @@ def generate_mips_into(chains, per_level=False, srgb=False):
         import torch
         lib().itwSetStream(torch.cuda.current_stream(flat[0].device).cuda_stream)
     flags = (MIP_PER_LEVEL if per_level else 0) | (MIP_SRGB if srgb else 0)
+    if alpha_weight or alpha_coverage or report:
+        assert es == 1, "the alpha rules are for RGBA8 texels"
+        opts = MipAlpha(1 if alpha_weight else 0, alpha_coverage)
+        rows = (MipCoverage * len(flat))() if report else None
+        if lib().itwGenerateMipChainAlpha(C.cast(_surfaces(flat), C.c_void_p), len(chains), len(chains[0]), flags, C.cast(C.byref(opts), C.c_void_p),
+                                          C.cast(rows, C.c_void_p) if report else None) != 0:
+            raise ValueError("itwGenerateMipChainAlpha refused the call: " + (last_error() or "bad arguments"))
+        return (chains, list(rows)) if report else chains
     if lib().itwGenerateMipChain(C.cast(_surfaces(flat), C.c_void_p), len(chains), len(chains[0]), 4 * es, flags) != 0:
         raise ValueError("itwGenerateMipChain refused the call: " + (last_error() or "bad arguments"))
     return chains
 
 
-def compress_mipped(fmt, base_or_bases, levels=0, profile=None, settings=None, normal_ops=0, progress=None, out=None, srgb=False):
+def compress_mipped(fmt, base_or_bases, levels=0, profile=None, settings=None, normal_ops=0, progress=None, out=None, srgb=False,
+                    alpha_weight=False, alpha_coverage=0):
     """itwCompressImageMipped: the save path from base images in one call -- flips of `normal_ops` on level 0, the mip chain, the normalise on
     every level, then the chain encoder.  One base or a list of equally sized ones (numpy arrays or CUDA torch tensors, as compress_chain
     takes them); levels == 0: the full chain.  srgb: the chain's colour is filtered in linear light (itwCompressImageMippedEx with
-    ITW_MIP_SRGB; the format name is not read as a request).  Returns (ok, blocks): the DDS payload, item-major then level."""
+    ITW_MIP_SRGB; the format name is not read as a request).  alpha_weight / alpha_coverage: the rules for cut-out textures
+    (itwCompressImageMippedAlpha; no normal_ops with them).  Returns (ok, blocks): the DDS payload, item-major then level."""
     import numpy as np
     single = hasattr(base_or_bases, "shape")
     bases = [base_or_bases] if single else list(base_or_bases)
@@ -1129,7 +1180,12 @@ def compress_mipped(fmt, base_or_bases, levels=0, profile=None, settings=None, n
         settings = etc_profile(profile or "slow")
     sp = C.cast(C.byref(settings), C.c_void_p) if settings is not None else None
     cb = PROGRESS_FUNC(progress) if progress else None
-    if srgb:
+    if alpha_weight or alpha_coverage:
+        assert not normal_ops, "the alpha rules are for colour, not normal maps"
+        opts = MipAlpha(1 if alpha_weight else 0, alpha_coverage)
+        ok = lib().itwCompressImageMippedAlpha(C.cast(_surfaces(bases), C.c_void_p), len(bases), levels, MIP_SRGB if srgb else 0,
+                                               C.cast(C.byref(opts), C.c_void_p), dst, DXGI_FORMAT[fmt], sp, C.cast(cb, C.c_void_p) if cb else None, None)
+    elif srgb:
         ok = lib().itwCompressImageMippedEx(C.cast(_surfaces(bases), C.c_void_p), len(bases), levels, int(normal_ops), MIP_SRGB, dst, DXGI_FORMAT[fmt],
                                             sp, C.cast(cb, C.c_void_p) if cb else None, None)
     else:
