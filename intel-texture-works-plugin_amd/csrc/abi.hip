@@ -99,10 +99,89 @@ bool is_device_pointer(const void* p) noexcept
     return a.type == hipMemoryTypeDevice || a.type == hipMemoryTypeManaged;
 }
 
+[[noreturn]] void fail_image(const char* who, ImageFaultKind kind, const rgba_surface& s, int texel_bytes, int align, const char* noun, ...)
+{
+    char what[64];
+    va_list ap;
+    va_start(ap, noun);
+    std::vsnprintf(what, sizeof what, noun, ap);
+    va_end(ap);
+    switch (kind) {
+    case IMAGE_NULL_TEXELS: fail_msg("%s: %s has a null texel pointer", who, what);
+    case IMAGE_SIZE:        fail_msg("%s: %s is %d x %d", who, what, s.width, s.height);
+    case IMAGE_STRIDE:      fail_msg("%s: %s: stride %d < %lld bytes per row", who, what, s.stride, (long long)s.width * texel_bytes);
+    default:                fail_msg("%s: %s: texels are not %d-byte aligned", who, what, align);
+    }
+}
+
+bool all_one_pointer_kind(const char* who, const char* noun, const rgba_surface* images, int count, const rgba_surface* more)
+{
+    const bool dev = is_device_pointer(images[0].ptr);
+    for (int i = 0; i < count; i++)
+        if ((i && is_device_pointer(images[i].ptr) != dev) || (more && is_device_pointer(more[i].ptr) != dev))
+            fail_msg("%s: %s %d is %s memory, %s 0 %s: all images must be host or all device pointers", who, noun, i, dev ? "host" : "device", noun,
+                     dev ? "device" : "host");
+    return dev;
+}
+
+void upload_image(const StagingPlan& p, uint8_t* base, int i, hipStream_t st)
+{
+    if (p.dev) return;
+    const rgba_surface& s = p.images[i];
+    ITW_CHECK(hipMemcpy2DAsync(p.ptr(i, base), (size_t)p.stride(i), s.ptr, (size_t)s.stride, p.row_bytes(i), (size_t)s.height, hipMemcpyHostToDevice, st));
+}
+
+void download_image(const StagingPlan& p, uint8_t* base, int i, hipStream_t st)
+{
+    if (p.dev) return;
+    const rgba_surface& s = p.images[i];
+    ITW_CHECK(hipMemcpy2DAsync(s.ptr, (size_t)s.stride, p.ptr(i, base), (size_t)p.stride(i), p.row_bytes(i), (size_t)s.height, hipMemcpyDeviceToHost, st));
+}
+
+void upload_staged(const StagingPlan& p, uint8_t* base, hipStream_t st) { for (int i = 0; i < p.count; i++) upload_image(p, base, i, st); }
+void download_staged(const StagingPlan& p, uint8_t* base, hipStream_t st) { for (int i = 0; i < p.count; i++) download_image(p, base, i, st); }
+
 } // namespace itw
 
 namespace {
 using itw::is_device_pointer;
+
+void* grow(void*& buf, size_t& cap, size_t need)
+{
+    if (need > cap) {
+        if (buf) { void* old = buf; buf = nullptr; cap = 0; ITW_CHECK(hipFree(old)); }
+        size_t want = need + need / 4 + 4096;
+        void* fresh = nullptr;
+        ITW_CHECK(hipMalloc(&fresh, want));
+        buf = fresh; cap = want;
+    }
+    return buf;
+}
+
+// A grow-only device buffer that is ordered across streams by an event of its own.  Work already queued on another stream may still be
+// using it, so a claim from another stream than the last makes that stream wait for the event done() recorded behind the previous use
+// (never for the caller's old stream handle, which may have been destroyed since -- ADVICE r01); uses on one stream are ordered by the
+// stream itself.  Growing frees the buffer first, and hipFree waits for the device.
+struct OrderedBuffer {
+    void* ptr = nullptr; size_t cap = 0;
+    hipStream_t stream = nullptr; bool used = false;    // of the last claim (the caller's handle: not the library's to destroy)
+    hipEvent_t event = nullptr;
+    void* claim(size_t bytes, hipStream_t st)
+    {
+        if (!event) ITW_CHECK(hipEventCreateWithFlags(&event, hipEventDisableTiming));
+        if (used && stream != st) ITW_CHECK(hipStreamWaitEvent(st, event, 0));
+        grow(ptr, cap, bytes);
+        stream = st; used = true;
+        return ptr;
+    }
+    void done(hipStream_t st) { ITW_CHECK(hipEventRecord(event, st)); }      // the buffer is used up to here on `st`
+    void release() noexcept
+    {
+        if (ptr) (void)hipFree(ptr);
+        if (event) (void)hipEventDestroy(event);
+        *this = OrderedBuffer{};
+    }
+};
 
 // Per host thread: stream for device-resident calls and grow-only staging
 // buffers for host-pointer calls.  The reference is called from up to 64 pool
@@ -115,39 +194,33 @@ struct ThreadCtx {
     hipEvent_t  ev_in[8] = {}, ev_done[8] = {};
     void*  d_in = nullptr;  size_t in_cap = 0;
     void*  d_out = nullptr; size_t out_cap = 0;
-    void*  d_ws = nullptr;  size_t ws_cap = 0;      // BC7 inter-family workspace
-    hipStream_t ws_stream = nullptr; bool ws_used = false;
-    hipEvent_t  ws_event = nullptr;                 // recorded after each BC7 call: orders the workspace across streams
+    OrderedBuffer ws;                               // BC7 inter-family workspace, the wide BC6H shape's
     itw::Bc7Aux aux = {nullptr, nullptr, nullptr, 0, nullptr, false, nullptr, false};   // second stream + fork / join / mid events: the parallel parts of small
                                                     // BC7 calls, the second band of large ones, the second kernel stream of the window pipeline
     itw::Bc7Verdict verdict = {nullptr, nullptr, false, nullptr};   // the pilot's estimate of a staged host-pointer call's first run, left for the host (kernels.hpp)
     bool staged_wide = false;                       // what the last staged BC7 call's estimate said (the shape of this call's first run, until its own is in)
     void*  d_refine[2] = {nullptr, nullptr}; size_t refine_cap[2] = {0, 0};   // itwCompressImageRefined (refine.hip): per-surface scratch, per-list scratch
     uint32_t* refine_count = nullptr;               // ... and the two pinned words its list count (and "target met") are read back through
-    void*  d_decode = nullptr; size_t decode_cap = 0;   // itwDecodeChain (decode_chain.hip): descriptor table and, for host pointers, staging
-    hipStream_t decode_stream = nullptr; bool decode_used = false;
-    hipEvent_t  decode_event = nullptr;             // recorded after each chain decode: orders the table across streams, as ws_event does
+    OrderedBuffer decode;                           // itwDecodeChain and the texel stages: descriptor table and, for host pointers, staging
+    OrderedBuffer chain;                            // the device-side chain of a one-call save (mipgen.hip), alive while its stages use `decode`
     int    device = -1;
     char   info[256] = {0};
     // Every buffer, stream, event and pinned word of the context, freed and forgotten: the one place a new resource is added to.  Best effort
     // (the destructor runs it, and the runtime may already be gone at process exit): errors are ignored.  The caller's stream handles
-    // (user_stream, ws_stream, decode_stream) are not the library's to destroy.
+    // (user_stream, the buffers' last streams) are not the library's to destroy.
     void release() noexcept
     {
         auto free_dev = [](void*& p, size_t& cap) { if (p) (void)hipFree(p); p = nullptr; cap = 0; };
         auto drop = [](hipStream_t& s) { if (s) (void)hipStreamDestroy(s); s = nullptr; };
         auto forget = [](hipEvent_t& e) { if (e) (void)hipEventDestroy(e); e = nullptr; };
         free_dev(d_in, in_cap); free_dev(d_out, out_cap);
-        free_dev(d_ws, ws_cap); ws_used = false;
+        ws.release(); decode.release(); chain.release();
         for (int k = 0; k < 2; k++) free_dev(d_refine[k], refine_cap[k]);
         if (refine_count) (void)hipHostFree(refine_count);
         refine_count = nullptr;
-        free_dev(d_decode, decode_cap); decode_used = false;
-        forget(decode_event);
         drop(own_stream); drop(copy_stream);
         for (auto& e : ev_in) forget(e);
         for (auto& e : ev_done) forget(e);
-        forget(ws_event);
         drop(aux.stream); forget(aux.fork); forget(aux.join); forget(aux.mid);
         forget(verdict.event);
         if (verdict.host_counts) (void)hipHostFree((void*)verdict.host_counts);
@@ -183,18 +256,6 @@ void ensure_device_ctx()
     for (auto& e : tls.ev_done) if (!e) ITW_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
 }
 
-void* grow(void*& buf, size_t& cap, size_t need)
-{
-    if (need > cap) {
-        if (buf) { void* old = buf; buf = nullptr; cap = 0; ITW_CHECK(hipFree(old)); }
-        size_t want = need + need / 4 + 4096;
-        void* fresh = nullptr;
-        ITW_CHECK(hipMalloc(&fresh, want));
-        buf = fresh; cap = want;
-    }
-    return buf;
-}
-
 // What to encode with: the format as the table knows it (bcn_format.hpp: every size and rule that follows from the format is read there) and
 // what the table cannot know -- the settings.  ETC1: itwCompressBlocksETC1, slices and chains; no trampoline, no combiner, no refine, no multi-GPU.
 struct Job {
@@ -205,21 +266,13 @@ struct Job {
     uint32_t normal_ops = 0;    // BC5 only (itwCompressNormalMapBC5): ITW_NORMAL_* applied as the kernel loads its texels; such a job is never offered to the combiner
 };
 
-// The workspace (BC7's inter-family one, the wide BC6H shape's) is per host thread.  Work already queued on another stream may still be using
-// it, so a change of stream makes the new stream wait for a library-owned event recorded behind the previous call (never for the
-// caller's old stream handle, which may have been destroyed since -- ADVICE r01); calls on one stream are ordered by
-// the stream itself.  Growing the workspace frees it first, and hipFree waits for the device.
+// The workspace (BC7's inter-family one, the wide BC6H shape's) is per host thread: claimed on `st`, and used up to workspace_used(st).
 void* claim_workspace(size_t bytes, hipStream_t st)
 {
     bind_thread_to_current_device();
-    if (!tls.ws_event) ITW_CHECK(hipEventCreateWithFlags(&tls.ws_event, hipEventDisableTiming));
-    if (tls.ws_used && tls.ws_stream != st) ITW_CHECK(hipStreamWaitEvent(st, tls.ws_event, 0));
-    void* ws = grow(tls.d_ws, tls.ws_cap, bytes);
-    tls.ws_stream = st; tls.ws_used = true;
-    return ws;
+    return tls.ws.claim(bytes, st);
 }
-// the workspace is used up to here on `st` (what the next claim from another stream waits for)
-void workspace_used(hipStream_t st) { ITW_CHECK(hipEventRecord(tls.ws_event, st)); }
+void workspace_used(hipStream_t st) { tls.ws.done(st); }
 
 // A staged run of a host-pointer call: its upload / download overlap the neighbouring runs' kernels.  A BC7 run that is not a band
 // (compress_runs() below: round 4's shape, and what content that needs modes 1/3 everywhere still gets) takes the wide shape up to 2^20
@@ -287,7 +340,7 @@ void launch(const Job& j, const uint8_t* d_src, int64_t stride, int w, int h, ui
             // and under ITW_ON_ERROR_RETURN the thread lives on)
             struct Reset { itw::Bc7Aux& a; ~Reset() { a.single = false; a.verdict = nullptr; a.probe = false; } } reset{tls.aux};
             tls.aux.single = shape.kind >= LaunchShape::BAND;
-            void* ws = tls.d_ws;
+            void* ws = tls.ws.ptr;
             if (tls.aux.single) {
                 tls.aux.verdict = shape.kind >= LaunchShape::VERDICT_BAND ? &tls.verdict : nullptr;
                 tls.aux.probe = shape.kind == LaunchShape::PROBE;
@@ -497,7 +550,7 @@ struct WindowPipeline {
     ~WindowPipeline()
     {
         (void)hipStreamSynchronize(k0); (void)hipStreamSynchronize(k1); (void)hipStreamSynchronize(cs);
-        if (ws_claimed && tls.ws_event) (void)hipEventRecord(tls.ws_event, k0);
+        if (ws_claimed && tls.ws.event) (void)hipEventRecord(tls.ws.event, k0);
         (void)hipGetLastError();
     }
     // the second kernel stream starts behind whatever is on the first by now (the workspace's ordering, a chain's descriptor table)
@@ -587,14 +640,14 @@ void compress_single_run(const Job& j, const rgba_surface* src, uint8_t* dst, co
                       : j.kind == itw::BCN_BC6H ? itw::bc6h_workspace_bytes(src->width, geo.by * 4, *j.s6) : 0;
     if (need) (void)claim_workspace(need, st);
     // A failure below is a C++ exception (and under ITW_ON_ERROR_RETURN the thread lives on): whatever this call has queued by then is drained
-    // and the workspace's event recorded, so the next call finds d_in / d_out / d_ws free of work in flight.
+    // and the workspace's event recorded, so the next call finds d_in / d_out / the workspace free of work in flight.
     struct Drain {
         bool done; hipStream_t st;
         ~Drain() {
             if (done) return;
             (void)hipStreamSynchronize(st);
             if (tls.aux.stream) (void)hipStreamSynchronize(tls.aux.stream);
-            if (tls.ws_event && tls.ws_used) (void)hipEventRecord(tls.ws_event, st);
+            if (tls.ws.event && tls.ws.used) (void)hipEventRecord(tls.ws.event, st);
             (void)hipGetLastError();
         }
     } drain{false, st};
@@ -816,13 +869,7 @@ Job chain_job(const rgba_surface* images, int count, const uint8_t* target, int 
     if (count <= 0) itw::fail_msg("itwCompressImageChain: %d images", count);
     if (!images || !target) itw::fail_msg("itwCompressImageChain: null images or target pointer");
     const Job j = job_of(dxgi_format, settings);
-    const int px = itw::texel_bytes(j.kind);
-    for (int i = 0; i < count; i++) {
-        const rgba_surface& s = images[i];
-        if (!s.ptr) itw::fail_msg("itwCompressImageChain: image %d has a null texel pointer", i);
-        if (s.width < 1 || s.height < 1) itw::fail_msg("itwCompressImageChain: image %d is %d x %d", i, s.width, s.height);
-        if ((int64_t)s.stride < (int64_t)s.width * px) itw::fail_msg("itwCompressImageChain: image %d: stride %d < %d bytes per row", i, s.stride, s.width * px);
-    }
+    itw::check_images("itwCompressImageChain", "image", images, count, itw::texel_bytes(j.kind), 0);
     return j;
 }
 
@@ -837,20 +884,12 @@ bool chain_groups(const Job& j, const rgba_surface* im, uint8_t* target, const s
     const int spx = signed_source ? signed_source : px;      // bytes per SOURCE texel (a signed normal source: 4, 8 or 16 into packed RGBA8_SNORM)
     const bool fill45 = itw::keeps_partial_blocks(j.kind);
     const int ngroups = (int)(u1 - u0);
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-
     // layout: d_in = [staged texels (host images)] [packed surfaces] [descriptors], d_out = [encoded packed surfaces]
     struct Group { int i0, i1; int64_t b0, nb; int pbx, pby; size_t packed_off, out_off; };
     std::vector<Group> gs((size_t)ngroups);
-    std::vector<size_t> stage_off;
-    size_t in_bytes = 0, out_bytes = 0;
-    if (!src_dev) {
-        stage_off.resize((size_t)(units[u1 - 1].i1 - units[u0].i0));
-        for (int i = units[u0].i0; i < units[u1 - 1].i1; i++) {
-            stage_off[(size_t)(i - units[u0].i0)] = in_bytes;
-            in_bytes += up((((size_t)im[i].width * spx + 15) & ~(size_t)15) * (size_t)im[i].height);
-        }
-    }
+    const int first_image = units[u0].i0, nimg = units[u1 - 1].i1 - first_image;
+    const itw::StagingPlan staged(im + first_image, nimg, spx, src_dev, 0);
+    size_t in_bytes = staged.bytes, out_bytes = 0;
     int tallest = 0, widest = 0;
     for (int g = 0; g < ngroups; g++) {
         const ChainUnit& u = units[u0 + (size_t)g];
@@ -859,13 +898,12 @@ bool chain_groups(const Job& j, const rgba_surface* im, uint8_t* target, const s
         G.pbx = (int)std::min<int64_t>(kChainPackedBlocks, u.nb);
         G.pby = (int)((u.nb + G.pbx - 1) / G.pbx);
         G.packed_off = in_bytes;
-        in_bytes += up((size_t)G.pby * 4 * ((size_t)G.pbx * 4 * px));
+        in_bytes += itw::up256((size_t)G.pby * 4 * ((size_t)G.pbx * 4 * px));
         G.out_off = out_bytes;
-        out_bytes += up((size_t)G.pby * G.pbx * bpb);
+        out_bytes += itw::up256((size_t)G.pby * G.pbx * bpb);
         if (G.pby > tallest || (G.pby == tallest && G.pbx > widest)) { tallest = G.pby; widest = G.pbx; }
     }
     const size_t desc_off = in_bytes;
-    const int nimg = units[u1 - 1].i1 - units[u0].i0;
     in_bytes += (size_t)nimg * sizeof(itw::ChainImage);
     std::vector<itw::ChainImage> desc((size_t)nimg);     // (declared ahead of the pipeline: it is still there while the pipeline drains)
 
@@ -882,11 +920,7 @@ bool chain_groups(const Job& j, const rgba_surface* im, uint8_t* target, const s
         const Group& G = gs[(size_t)g];
         int64_t first = 0;
         for (int i = G.i0; i < G.i1; i++) {
-            itw::ChainImage& d = desc[(size_t)(i - units[u0].i0)];
-            d.ptr = src_dev ? im[i].ptr : d_in + stage_off[(size_t)(i - units[u0].i0)];
-            d.stride = src_dev ? (int64_t)im[i].stride : (int64_t)(((size_t)im[i].width * spx + 15) & ~(size_t)15);
-            d.width = im[i].width; d.height = im[i].height;
-            d.first_block = first;
+            desc[(size_t)(i - first_image)] = itw::ChainImage{staged.ptr(i - first_image, d_in), staged.stride(i - first_image), im[i].width, im[i].height, first};
             first += itw::image_blocks(im[i]);
         }
     }
@@ -898,16 +932,14 @@ bool chain_groups(const Job& j, const rgba_surface* im, uint8_t* target, const s
         const Group& G = gs[(size_t)g];
         hipStream_t ks = pipe.stream(g);
         if (!src_dev) {
-            for (int i = G.i0; i < G.i1; i++) {
-                const size_t row_bytes = (size_t)im[i].width * spx;
-                upload_rows(d_in + stage_off[(size_t)(i - units[u0].i0)], (row_bytes + 15) & ~(size_t)15, im[i].ptr, im[i].stride, row_bytes,
-                            (size_t)im[i].height, pipe.cs);
-            }
+            for (int k = G.i0 - first_image; k < G.i1 - first_image; k++)
+                upload_rows(staged.ptr(k, d_in), (size_t)staged.stride(k), staged.images[k].ptr, staged.images[k].stride, staged.row_bytes(k),
+                            (size_t)staged.images[k].height, pipe.cs);
             pipe.uploaded(g);
         }
         const int64_t pitch = (int64_t)G.pbx * 4 * px;
         uint8_t* packed = d_in + G.packed_off;
-        itw::launch_chain_gather(d_desc + (G.i0 - units[u0].i0), G.i1 - G.i0, G.nb, G.pbx, G.pby, px, fill45, packed, pitch, ks, nullptr, normal_ops, signed_source);
+        itw::launch_chain_gather(d_desc + (G.i0 - first_image), G.i1 - G.i0, G.nb, G.pbx, G.pby, px, fill45, packed, pitch, ks, nullptr, normal_ops, signed_source);
         launch(j, packed, pitch, G.pbx * 4, G.pby * 4, d_out + G.out_off, ks,
                lone ? LaunchShape{(!src_dev && !dst_dev) ? LaunchShape::STAGED : LaunchShape::WHOLE} : LaunchShape{LaunchShape::BAND, pipe.workspace(g)});
         if (dst_dev) ITW_CHECK(hipMemcpyAsync(target + G.b0 * bpb, d_out + G.out_off, (size_t)G.nb * bpb, hipMemcpyDeviceToDevice, ks));
@@ -927,11 +959,7 @@ bool chain_groups(const Job& j, const rgba_surface* im, uint8_t* target, const s
 bool compress_chain(const Job& j, const rgba_surface* im, int count, uint8_t* target, ItwProgressFunc* progress, void* user, uint32_t normal_ops = 0,
                     int signed_source = 0)
 {
-    const bool src_dev = is_device_pointer(im[0].ptr);
-    for (int i = 1; i < count; i++)
-        if (is_device_pointer(im[i].ptr) != src_dev)
-            itw::fail_msg("itwCompressImageChain: image %d is %s memory, image 0 %s: all images must be host or all device pointers", i,
-                          src_dev ? "host" : "device", src_dev ? "device" : "host");
+    const bool src_dev = itw::all_one_pointer_kind("itwCompressImageChain", "image", im, count);
     if (src_dev) {
         int cur = 0, dev = 0;
         ITW_CHECK(hipGetDevice(&cur));
@@ -1332,14 +1360,16 @@ uint32_t* refine_count_word()
 void* decode_scratch(size_t bytes, hipStream_t st)
 {
     bind_thread_to_current_device();
-    if (!tls.decode_event) ITW_CHECK(hipEventCreateWithFlags(&tls.decode_event, hipEventDisableTiming));
-    if (tls.decode_used && tls.decode_stream != st) ITW_CHECK(hipStreamWaitEvent(st, tls.decode_event, 0));
-    void* p = grow(tls.d_decode, tls.decode_cap, bytes);
-    tls.decode_stream = st; tls.decode_used = true;
-    return p;
+    return tls.decode.claim(bytes, st);
 }
+void decode_scratch_done(hipStream_t st) { tls.decode.done(st); }
 
-void decode_scratch_done(hipStream_t st) { ITW_CHECK(hipEventRecord(tls.decode_event, st)); }
+void* chain_scratch(size_t bytes, hipStream_t st)
+{
+    bind_thread_to_current_device();
+    return tls.chain.claim(bytes, st);
+}
+void chain_scratch_done(hipStream_t st) { tls.chain.done(st); }
 
 int sliced_windows(int dxgi_format, const void* settings, int width, int height, int64_t slice_pixels, int* window_slices)
 {
@@ -1526,9 +1556,7 @@ bool itwCompressSignedNormalMapChain(const rgba_surface* images, int count, int 
         if (texel_bytes != 4 && texel_bytes != 8 && texel_bytes != 16) itw::fail_msg("itwCompressSignedNormalMapChain: texel_bytes %d (4, 8 or 16)", texel_bytes);
         if (ops & ~7u) itw::fail_msg("itwCompressSignedNormalMapChain: unknown ops bits 0x%x", ops);
         const Job j = chain_job(images, count, target, dxgi_format, nullptr);
-        for (int i = 0; i < count; i++)
-            if ((int64_t)images[i].stride < (int64_t)images[i].width * texel_bytes)
-                itw::fail_msg("itwCompressSignedNormalMapChain: image %d: stride %d < %lld bytes per row", i, images[i].stride, (long long)images[i].width * texel_bytes);
+        itw::check_images("itwCompressSignedNormalMapChain", "image", images, count, texel_bytes, 0);
         done = compress_chain(j, images, count, target, progress, user, ops, texel_bytes);
     });
     return ok && done;

@@ -19,6 +19,7 @@
 #include <cstdint>
 #include <cstdio>
 #include "../../include/ispc_texcomp.h"
+#include "image_list_host.hpp"
 
 namespace itw {
 
@@ -86,9 +87,34 @@ uint32_t* refine_count_word();
 // decode_scratch_done(st) recorded behind that call's work (the BC7 workspace's rule); growing frees the old buffer, which waits for the device.
 void* decode_scratch(size_t bytes, hipStream_t st);
 void decode_scratch_done(hipStream_t st);
+// What a one-call save (mipgen.hip) keeps its device-side chain in: a buffer of its own with the same rules, since the stages the call runs
+// use the decode scratch while the chain lives.
+void* chain_scratch(size_t bytes, hipStream_t st);
+void chain_scratch_done(hipStream_t st);
 
 // One predicate for "the kernels can dereference this pointer": device AND managed allocations (abi.hip and
 // dispatch.hip and the decode entry used to disagree on managed memory).  Unregistered host memory -> false.
 bool is_device_pointer(const void* p) noexcept;
+
+// The HIP-side half of image_list_host.hpp.
+// A reported fault of image `s` as the entry point `who`'s failure; the noun is the image's name in the message, printf style ("base %d",
+// "item %d level %d"), `texel_bytes` and `align` what image_fault was asked for.
+[[noreturn]] void fail_image(const char* who, ImageFaultKind kind, const rgba_surface& s, int texel_bytes, int align, const char* noun, ...)
+    __attribute__((format(printf, 6, 7)));
+inline void check_images(const char* who, const char* noun, const rgba_surface* images, int count, int texel_bytes, int align)
+{
+    if (const ImageFault f = image_list_fault(images, count, texel_bytes, align))
+        fail_image(who, f.kind, images[f.index], texel_bytes, align, "%s %d", noun, f.index);
+}
+// true when every image of the list is device (or managed) memory, false when every one is host memory, a failure otherwise; `more`: a
+// second list of `count` that must be of the same kind (itwQuantizeNormalMapChain's targets)
+bool all_one_pointer_kind(const char* who, const char* noun, const rgba_surface* images, int count, const rgba_surface* more = nullptr);
+
+// The copies of a plan's host images, width x height each and nothing more, to and from their places in the buffer at `base`; nothing for
+// device images.  upload_staged / download_staged: every image of the plan, in order.
+void upload_image(const StagingPlan& p, uint8_t* base, int i, hipStream_t st);
+void download_image(const StagingPlan& p, uint8_t* base, int i, hipStream_t st);
+void upload_staged(const StagingPlan& p, uint8_t* base, hipStream_t st);
+void download_staged(const StagingPlan& p, uint8_t* base, hipStream_t st);
 
 } // namespace itw

@@ -260,11 +260,8 @@ extern "C" int itwMeasureChain(const rgba_surface* images, int count, const uint
     }
     const bool ok = itw::guarded([&] {
         hipStream_t st = (hipStream_t)itwGetStream();
-        const bool dblocks = itw::is_device_pointer(blocks), dsrc = itw::is_device_pointer(images[0].ptr), dstats = itw::is_device_pointer(stats);
-        for (int i = 1; i < count; i++)
-            if (itw::is_device_pointer(images[i].ptr) != dsrc)
-                itw::fail_msg("itwMeasureChain: image %d is %s memory, image 0 %s: all images must be host or all device pointers", i,
-                              dsrc ? "host" : "device", dsrc ? "device" : "host");
+        const bool dblocks = itw::is_device_pointer(blocks), dsrc = itw::all_one_pointer_kind("itwMeasureChain", "image", images, count),
+                   dstats = itw::is_device_pointer(stats);
         Staging tmp;
         const uint8_t* d_blocks = dblocks ? blocks : tmp.upload(blocks, (size_t)total * itw::block_bytes(kind), st);
         itw_error_stats* d_stats = dstats ? stats : static_cast<itw_error_stats*>(tmp.alloc(sizeof(itw_error_stats) * (size_t)count));

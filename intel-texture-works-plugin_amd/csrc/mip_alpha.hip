@@ -233,8 +233,6 @@ mip_alpha_rescale_kernel(const AlphaImage* __restrict__ table, int32_t count, ui
 
 namespace {
 
-size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // which histogram kernel runs: one LDS atomic per texel, which measured 2-5 % faster per coverage call than the per-wave spike counts on
 // cut-out and on noise alpha alike (DESIGN.md 3.11 has the rows); the hooks build can ask for the other
 bool g_hist_spikes = false;
@@ -306,49 +304,26 @@ extern "C" int itwAlphaCoverage(const rgba_surface* images, int count, int alpha
         if (count == 0) return;
         if (!images || !covered) itw::fail_msg("itwAlphaCoverage: null %s pointer", images ? "covered" : "images");
         if (count > 0x7fffffff / 64) itw::fail_msg("itwAlphaCoverage: %d images", count);
+        itw::check_images("itwAlphaCoverage", "image", images, count, 4, 4);
         uint64_t blocks = 0;
-        for (int i = 0; i < count; i++) {
-            const rgba_surface& s = images[i];
-            if (!s.ptr) itw::fail_msg("itwAlphaCoverage: image %d has a null texel pointer", i);
-            if (s.width < 1 || s.height < 1) itw::fail_msg("itwAlphaCoverage: image %d is %d x %d", i, s.width, s.height);
-            if ((int64_t)s.stride < (int64_t)s.width * 4) itw::fail_msg("itwAlphaCoverage: image %d: stride %d < %lld bytes per row", i, s.stride, (long long)s.width * 4);
-            const uintptr_t row_step = s.height > 1 ? (uintptr_t)(uint32_t)s.stride : 0;
-            if (((uintptr_t)s.ptr | row_step) & 3u) itw::fail_msg("itwAlphaCoverage: image %d: texels are not 4-byte aligned", i);
-            blocks += itw::alpha_blocks(s.width, s.height);
-        }
+        for (int i = 0; i < count; i++) blocks += itw::alpha_blocks(images[i].width, images[i].height);
         if (blocks > 0x7fffffffull) itw::fail_msg("itwAlphaCoverage: %d images are more workgroups than one launch covers", count);
-        const bool dev = itw::is_device_pointer(images[0].ptr);
-        for (int i = 1; i < count; i++)
-            if (itw::is_device_pointer(images[i].ptr) != dev)
-                itw::fail_msg("itwAlphaCoverage: image %d is %s memory, image 0 %s: all images must be host or all device pointers", i,
-                              dev ? "host" : "device", dev ? "device" : "host");
+        const bool dev = itw::all_one_pointer_kind("itwAlphaCoverage", "image", images, count);
 
-        // the thread's buffer: [table] [counts] [staged images (host pointers), rows of a 16-byte multiple]
+        // the thread's buffer: [table] [counts] [staged images (host pointers)]
         hipStream_t st = (hipStream_t)itwGetStream();
-        const size_t counts_off = (size_t)count * sizeof(itw::AlphaImage), head = itw::up256(counts_off + (size_t)count * 8);
+        const size_t counts_off = (size_t)count * sizeof(itw::AlphaImage);
         static thread_local std::vector<uint8_t> host;
         host.assign(counts_off + (size_t)count * 8, 0);
         itw::AlphaImage* t = reinterpret_cast<itw::AlphaImage*>(host.data());
-        size_t bytes = head;
+        const itw::StagingPlan plan(images, count, 4, dev, host.size());
+        uint8_t* base = static_cast<uint8_t*>(itw::decode_scratch(plan.bytes, st));
         uint32_t first = 0;
-        std::vector<size_t> stage_off(dev ? 0 : (size_t)count);
         for (int i = 0; i < count; i++) {
-            t[i].ptr = images[i].ptr; t[i].stride = images[i].stride; t[i].w = images[i].width; t[i].h = images[i].height;
-            t[i].first = first; t[i].first_rescale = 0;
+            t[i] = itw::AlphaImage{plan.ptr(i, base), plan.stride(i), images[i].width, images[i].height, first, 0};
             first += itw::alpha_blocks(images[i].width, images[i].height);
-            if (!dev) {
-                t[i].stride = (int64_t)(((size_t)images[i].width * 4 + 15) & ~(size_t)15);
-                stage_off[(size_t)i] = bytes;
-                bytes += itw::up256((size_t)t[i].stride * (size_t)images[i].height);
-            }
         }
-        uint8_t* base = static_cast<uint8_t*>(itw::decode_scratch(bytes, st));
-        if (!dev)
-            for (int i = 0; i < count; i++) {
-                t[i].ptr = base + stage_off[(size_t)i];
-                ITW_CHECK(hipMemcpy2DAsync(t[i].ptr, (size_t)t[i].stride, images[i].ptr, (size_t)images[i].stride, (size_t)images[i].width * 4,
-                                           (size_t)images[i].height, hipMemcpyHostToDevice, st));
-            }
+        itw::upload_staged(plan, base, st);
         ITW_CHECK(hipMemcpyAsync(base, host.data(), host.size(), hipMemcpyHostToDevice, st));
         unsigned long long* counts = reinterpret_cast<unsigned long long*>(base + counts_off);
         itw::launch_hist(reinterpret_cast<const itw::AlphaImage*>(base), count, 1, alpha_ref, first, counts, counts, st);

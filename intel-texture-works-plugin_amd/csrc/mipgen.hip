@@ -135,8 +135,6 @@ void launch_plain_chain(const itw::MipImage* table, int items, int levels, int w
     itw::launch_chain(k, table, items, levels, w, h, per_level, st);
 }
 
-size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // the alpha rules of a call, as its checks left them: both off for every call but itwGenerateMipChainAlpha's
 struct AlphaRules { bool weight = false; int coverage_ref = 0; itw_mip_coverage* report = nullptr; };
 
@@ -147,27 +145,12 @@ void generate_chain(const rgba_surface* im, int items, int levels, int px, bool 
     const int count = items * levels;
     static thread_local std::vector<itw::MipImage> desc;                  // grow-only, like the device buffer it is copied into
     desc.resize((size_t)count);
-    // the thread's buffer: [table] [the coverage passes' work] [staged images (host pointers), rows of a 16-byte multiple]
-    size_t bytes = up256((size_t)count * sizeof(itw::MipImage));
-    const size_t work_off = bytes;
-    if (alpha.coverage_ref) bytes += itw::coverage_work_bytes(items, levels);
-    std::vector<size_t> stage_off(dev ? 0 : (size_t)count);
-    for (int i = 0; i < count; i++) {
-        desc[(size_t)i].ptr = im[i].ptr; desc[(size_t)i].stride = im[i].stride;
-        if (!dev) {
-            desc[(size_t)i].stride = (int64_t)(((size_t)im[i].width * px + 15) & ~(size_t)15);
-            stage_off[(size_t)i] = bytes;
-            bytes += up256((size_t)desc[(size_t)i].stride * (size_t)im[i].height);
-        }
-    }
-    uint8_t* base = static_cast<uint8_t*>(itw::decode_scratch(bytes, st));
-    if (!dev)
-        for (int i = 0; i < count; i++) {
-            desc[(size_t)i].ptr = base + stage_off[(size_t)i];
-            if (i % levels == 0)                                          // only the bases go up
-                ITW_CHECK(hipMemcpy2DAsync(desc[(size_t)i].ptr, (size_t)desc[(size_t)i].stride, im[i].ptr, (size_t)im[i].stride, (size_t)im[i].width * px,
-                                           (size_t)im[i].height, hipMemcpyHostToDevice, st));
-        }
+    // the thread's buffer: [table] [the coverage passes' work] [staged images (host pointers)]
+    const size_t work_off = itw::up256((size_t)count * sizeof(itw::MipImage));
+    const itw::StagingPlan plan(im, count, px, dev, work_off + (alpha.coverage_ref ? itw::coverage_work_bytes(items, levels) : 0));
+    uint8_t* base = static_cast<uint8_t*>(itw::decode_scratch(plan.bytes, st));
+    for (int i = 0; i < count; i++) desc[(size_t)i] = itw::MipImage{plan.ptr(i, base), plan.stride(i)};
+    for (int i = 0; i < count; i += levels) itw::upload_image(plan, base, i, st);                                     // only the bases go up
     ITW_CHECK(hipMemcpyAsync(base, desc.data(), (size_t)count * sizeof(itw::MipImage), hipMemcpyHostToDevice, st));
     const itw::MipImage* table = reinterpret_cast<const itw::MipImage*>(base);
     const int w = im[0].width, h = im[0].height;
@@ -186,10 +169,7 @@ void generate_chain(const rgba_surface* im, int items, int levels, int px, bool 
         itw::decode_scratch_done(st);
         return;
     }
-    for (int i = 0; i < count; i++)                                       // only the written levels come back, width x height only
-        if (i % levels != 0)
-            ITW_CHECK(hipMemcpy2DAsync(im[i].ptr, (size_t)im[i].stride, desc[(size_t)i].ptr, (size_t)desc[(size_t)i].stride, (size_t)im[i].width * px,
-                                       (size_t)im[i].height, hipMemcpyDeviceToHost, st));
+    for (int i = 0; i < count; i++) if (i % levels) itw::download_image(plan, base, i, st);                           // only the written levels come back
     ITW_CHECK(hipStreamSynchronize(st));
     itw::decode_scratch_done(st);
 }
@@ -216,27 +196,6 @@ void check_coverage_size(const char* who, int w, int h)
 {
     if ((int64_t)w * h > ((int64_t)1 << 31)) itw::fail_msg("%s: coverage over a base of %d x %d: more than 2^31 texels", who, w, h);
 }
-
-// the device-side chain of itwCompressImageMipped: the thread's own grow-only buffer (the staging buffer above is in use by the stages the
-// call runs), ordered across streams as host_rt.hpp's decode_scratch is
-struct ChainBuffer {
-    void* ptr = nullptr; size_t cap = 0; hipEvent_t done = nullptr; hipStream_t stream = nullptr; bool used = false;
-    uint8_t* get(size_t bytes, hipStream_t st)
-    {
-        if (!done) ITW_CHECK(hipEventCreateWithFlags(&done, hipEventDisableTiming));
-        if (used && stream != st) ITW_CHECK(hipStreamWaitEvent(st, done, 0));
-        if (bytes > cap) {
-            if (ptr) { void* old = ptr; ptr = nullptr; cap = 0; ITW_CHECK(hipFree(old)); }      // (waits for the device)
-            const size_t want = bytes + bytes / 4 + 4096;
-            ITW_CHECK(hipMalloc(&ptr, want));
-            cap = want;
-        }
-        stream = st; used = true;
-        return static_cast<uint8_t*>(ptr);
-    }
-    void release(hipStream_t st) { ITW_CHECK(hipEventRecord(done, st)); }
-};
-thread_local ChainBuffer t_chain;
 
 } // namespace
 
@@ -342,22 +301,15 @@ int generate_checked(const char* who, const rgba_surface* images, int items, int
         for (int i = 0; i < items * levels; i++) {
             const rgba_surface& s = images[i];
             const int item = i / levels, l = i % levels;
-            if (!s.ptr) itw::fail_msg("%s: item %d level %d has a null texel pointer", who, item, l);
+            const itw::ImageFaultKind fault = itw::image_fault(s, pixel_size, pixel_size);      // null texels come before the sizes, the rest after
+            if (fault == itw::IMAGE_NULL_TEXELS) itw::fail_image(who, fault, s, pixel_size, pixel_size, "item %d level %d", item, l);
             if (l == 0 && (s.width != w || s.height != h))
                 itw::fail_msg("%s: the base of item %d is %d x %d, that of item 0 %d x %d", who, item, s.width, s.height, w, h);
             if (s.width != mip_dim(w, l) || s.height != mip_dim(h, l))
                 itw::fail_msg("%s: item %d level %d is %d x %d, the chain's is %d x %d", who, item, l, s.width, s.height, mip_dim(w, l), mip_dim(h, l));
-            if ((int64_t)s.stride < (int64_t)s.width * pixel_size)
-                itw::fail_msg("%s: item %d level %d: stride %d < %lld bytes per row", who, item, l, s.stride, (long long)s.width * pixel_size);
-            const uintptr_t row_step = s.height > 1 ? (uintptr_t)(uint32_t)s.stride : 0;
-            if (((uintptr_t)s.ptr | row_step) & (uintptr_t)(pixel_size - 1))
-                itw::fail_msg("%s: item %d level %d: texels are not %d-byte aligned", who, item, l, pixel_size);
+            if (fault) itw::fail_image(who, fault, s, pixel_size, pixel_size, "item %d level %d", item, l);
         }
-        dev = itw::is_device_pointer(images[0].ptr);
-        for (int i = 1; i < items * levels; i++)
-            if (itw::is_device_pointer(images[i].ptr) != dev)
-                itw::fail_msg("%s: image %d is %s memory, image 0 %s: all images must be host or all device pointers", who, i,
-                              dev ? "host" : "device", dev ? "device" : "host");
+        dev = itw::all_one_pointer_kind(who, "image", images, items * levels);
         generate_chain(images, items, levels, pixel_size, (flags & ITW_MIP_SRGB) != 0, (flags & ITW_MIP_PER_LEVEL) != 0, dev, alpha);
     });
     return ok ? 0 : -1;
@@ -420,6 +372,27 @@ extern "C" void itwTestSrgbEncode(const float* d_in, uint8_t* d_out, int64_t n)
 
 namespace {
 
+// What the one-call saves ask of their bases once chain_check_with has passed them: equal sizes, rows of `texel_bytes` texels aligned to
+// their size, `levels` (0: all) within the full chain and the launches' bounds, one pointer kind, and a chain of `chain_px`-byte texels
+// that surfaces can describe.
+struct MippedBases { int levels; bool dev; int64_t chain_bytes; };
+MippedBases check_mipped_bases(const char* who, const rgba_surface* bases, int items, int levels, int texel_bytes, int chain_px)
+{
+    const int w = bases[0].width, h = bases[0].height, full = itwMipLevels(w, h);
+    for (int i = 0; i < items; i++) {
+        if (bases[i].width != w || bases[i].height != h) itw::fail_msg("%s: base %d is %d x %d, base 0 %d x %d", who, i, bases[i].width, bases[i].height, w, h);
+        if (const itw::ImageFaultKind k = itw::image_fault(bases[i], texel_bytes, texel_bytes)) itw::fail_image(who, k, bases[i], texel_bytes, texel_bytes, "base %d", i);
+    }
+    if (levels < 0 || levels > full) itw::fail_msg("%s: %d levels, a full chain of %d x %d has %d", who, levels, w, h, full);
+    if (levels == 0) levels = full;
+    if ((int64_t)items * levels > (int64_t)0x7fffffff / 64) itw::fail_msg("%s: %d items of %d levels", who, items, levels);
+    check_launch_limits(who, w, h, items);
+    const bool dev = itw::all_one_pointer_kind(who, "base", bases, items);
+    const int64_t bytes = itwMipChainLayout(w, h, items, levels, chain_px, nullptr, nullptr);
+    if (bytes < 0) itw::fail_msg("%s: a %d x %d base is wider than a surface can describe", who, w, h);
+    return MippedBases{levels, dev, bytes};
+}
+
 // itwCompressImageMippedEx, and itwCompressImageMippedAlpha when `alpha_call`: the same stages, the alpha rules handed to the generation
 bool compress_mipped(const rgba_surface* bases, int items, int levels, uint32_t normal_ops, uint32_t mip_flags, bool alpha_call, const itw_mip_alpha* alpha_in,
                      uint8_t* target, int dxgi_format, const void* settings, ItwProgressFunc* progress, void* user)
@@ -442,29 +415,15 @@ bool compress_mipped(const rgba_surface* bases, int items, int levels, uint32_t 
             if (dxgi_format == 81 || dxgi_format == 84) itw::fail_msg("itwCompressImageMipped: ITW_MIP_SRGB with DXGI format %d, whose texels are signed codes, not colour", dxgi_format);
             if (normal_ops) itw::fail_msg("itwCompressImageMipped: ITW_MIP_SRGB with normal ops 0x%x: a normal map is not colour", normal_ops);
         }
-        const int w = bases[0].width, h = bases[0].height, full = itwMipLevels(w, h);
-        for (int i = 0; i < items; i++) {
-            if (bases[i].width != w || bases[i].height != h)
-                itw::fail_msg("itwCompressImageMipped: base %d is %d x %d, base 0 %d x %d", i, bases[i].width, bases[i].height, w, h);
-            const uintptr_t row_step = h > 1 ? (uintptr_t)(uint32_t)bases[i].stride : 0;
-            if (((uintptr_t)bases[i].ptr | row_step) & (uintptr_t)(px - 1)) itw::fail_msg("itwCompressImageMipped: base %d: texels are not %d-byte aligned", i, px);
-        }
-        if (levels < 0 || levels > full) itw::fail_msg("itwCompressImageMipped: %d levels, a full chain of %d x %d has %d", levels, w, h, full);
-        if (levels == 0) levels = full;
-        if ((int64_t)items * levels > (int64_t)0x7fffffff / 64) itw::fail_msg("itwCompressImageMipped: %d items of %d levels", items, levels);
-        check_launch_limits("itwCompressImageMipped", w, h, items);
+        const MippedBases b = check_mipped_bases("itwCompressImageMipped", bases, items, levels, px, px);
+        const int w = bases[0].width, h = bases[0].height;
+        const bool dev = b.dev;
+        levels = b.levels;
         if (alpha.coverage_ref) check_coverage_size("itwCompressImageMippedAlpha", w, h);
-        const bool dev = itw::is_device_pointer(bases[0].ptr);
-        for (int i = 1; i < items; i++)
-            if (itw::is_device_pointer(bases[i].ptr) != dev)
-                itw::fail_msg("itwCompressImageMipped: base %d is %s memory, base 0 %s: all bases must be host or all device pointers", i,
-                              dev ? "host" : "device", dev ? "device" : "host");
-        const int64_t bytes = itwMipChainLayout(w, h, items, levels, px, nullptr, nullptr);
-        if (bytes < 0) itw::fail_msg("itwCompressImageMipped: a %d x %d base is wider than a surface can describe", w, h);
 
         hipStream_t st = (hipStream_t)itwGetStream();
         std::vector<rgba_surface> chain((size_t)items * levels), level0((size_t)items);
-        itwMipChainLayout(w, h, items, levels, px, t_chain.get((size_t)bytes, st), chain.data());
+        itwMipChainLayout(w, h, items, levels, px, static_cast<uint8_t*>(itw::chain_scratch((size_t)b.chain_bytes, st)), chain.data());
         for (int i = 0; i < items; i++) {
             level0[(size_t)i] = chain[(size_t)i * levels];
             ITW_CHECK(hipMemcpy2DAsync(level0[(size_t)i].ptr, (size_t)level0[(size_t)i].stride, bases[i].ptr, (size_t)bases[i].stride, (size_t)w * px, (size_t)h,
@@ -477,7 +436,7 @@ bool compress_mipped(const rgba_surface* bases, int items, int levels, uint32_t 
         else                                    stage(itwGenerateMipChain(chain.data(), items, levels, px, mip_flags), "the mip chain");
         if (normal_ops & 4u) stage(itwPrepareNormalMapChain(chain.data(), items * levels, px, 4u), "the normalise");
         done = itwCompressImageChainEx(chain.data(), items * levels, target, dxgi_format, settings, progress, user);
-        t_chain.release(st);
+        itw::chain_scratch_done(st);
     });
     return ok && done;
 }
@@ -514,46 +473,23 @@ extern "C" bool itwCompressSignedNormalMapMipped(const rgba_surface* bases, int 
         if (texel_bytes != 4 && texel_bytes != 8 && texel_bytes != 16) itw::fail_msg("itwCompressSignedNormalMapMipped: texel_bytes %d (4, 8 or 16)", texel_bytes);
         if (ops & ~7u) itw::fail_msg("itwCompressSignedNormalMapMipped: unknown ops bits 0x%x", ops);
         itw::chain_check_with(bases, items, target, dxgi_format, nullptr);        // counts, null pointers, sizes, format
-        const int w = bases[0].width, h = bases[0].height, full = itwMipLevels(w, h);
-        for (int i = 0; i < items; i++) {
-            if (bases[i].width != w || bases[i].height != h)
-                itw::fail_msg("itwCompressSignedNormalMapMipped: base %d is %d x %d, base 0 %d x %d", i, bases[i].width, bases[i].height, w, h);
-            if ((int64_t)bases[i].stride < (int64_t)w * texel_bytes)
-                itw::fail_msg("itwCompressSignedNormalMapMipped: base %d: stride %d < %lld bytes per row", i, bases[i].stride, (long long)w * texel_bytes);
-            const uintptr_t row_step = h > 1 ? (uintptr_t)(uint32_t)bases[i].stride : 0;
-            if (((uintptr_t)bases[i].ptr | row_step) & (uintptr_t)(texel_bytes - 1))
-                itw::fail_msg("itwCompressSignedNormalMapMipped: base %d: texels are not %d-byte aligned", i, texel_bytes);
-        }
-        if (levels < 0 || levels > full) itw::fail_msg("itwCompressSignedNormalMapMipped: %d levels, a full chain of %d x %d has %d", levels, w, h, full);
-        if (levels == 0) levels = full;
-        if ((int64_t)items * levels > (int64_t)0x7fffffff / 64) itw::fail_msg("itwCompressSignedNormalMapMipped: %d items of %d levels", items, levels);
-        check_launch_limits("itwCompressSignedNormalMapMipped", w, h, items);
-        const bool dev = itw::is_device_pointer(bases[0].ptr);
-        for (int i = 1; i < items; i++)
-            if (itw::is_device_pointer(bases[i].ptr) != dev)
-                itw::fail_msg("itwCompressSignedNormalMapMipped: base %d is %s memory, base 0 %s: all bases must be host or all device pointers", i,
-                              dev ? "host" : "device", dev ? "device" : "host");
-        const int64_t bytes = itwMipChainLayout(w, h, items, levels, 8, nullptr, nullptr);
-        if (bytes < 0) itw::fail_msg("itwCompressSignedNormalMapMipped: a %d x %d base is wider than a surface can describe", w, h);
+        const MippedBases b = check_mipped_bases("itwCompressSignedNormalMapMipped", bases, items, levels, texel_bytes, 8);
+        const int w = bases[0].width, h = bases[0].height;
+        levels = b.levels;
 
-        // the thread's chain buffer: [RGBA16F chain] [host bases as they are, rows of a 16-byte multiple]
+        // the thread's chain buffer: [RGBA16F chain] [host bases as they are]
         hipStream_t st = (hipStream_t)itwGetStream();
-        const size_t chain_bytes = ((size_t)bytes + 255) & ~(size_t)255, pitch = ((size_t)w * texel_bytes + 15) & ~(size_t)15;
-        const size_t base_bytes = dev ? 0 : (pitch * (size_t)h + 255) & ~(size_t)255;
-        uint8_t* buf = t_chain.get(chain_bytes + base_bytes * (size_t)items, st);
+        const itw::StagingPlan plan(bases, items, texel_bytes, b.dev, (size_t)b.chain_bytes);
+        uint8_t* buf = static_cast<uint8_t*>(itw::chain_scratch(plan.bytes, st));
         std::vector<rgba_surface> chain((size_t)items * levels);
         itwMipChainLayout(w, h, items, levels, 8, buf, chain.data());
-        const int64_t quads = (int64_t)((w + 3) >> 2) * h;                        // (within one launch: check_launch_limits bounds the tiles of 64 x 64)
-        if ((quads + 255) / 256 > (int64_t)0x7fffffff) itw::fail_msg("itwCompressSignedNormalMapMipped: a %d x %d base is more than one launch covers", w, h);
+        const int64_t quads = itw::texel_quads(w, h);                             // (within one launch: check_launch_limits bounds the tiles of 64 x 64)
+        if (!itw::quads_fit_one_launch(quads)) itw::fail_msg("itwCompressSignedNormalMapMipped: a %d x %d base is more than one launch covers", w, h);
         const dim3 grid((unsigned)((quads + 255) / 256)), blk(256);
         for (int i = 0; i < items; i++) {
-            const uint8_t* src = bases[i].ptr;
-            int64_t stride = bases[i].stride;
-            if (!dev) {
-                uint8_t* staged = buf + chain_bytes + base_bytes * (size_t)i;
-                ITW_CHECK(hipMemcpy2DAsync(staged, pitch, bases[i].ptr, (size_t)bases[i].stride, (size_t)w * texel_bytes, (size_t)h, hipMemcpyHostToDevice, st));
-                src = staged; stride = (int64_t)pitch;
-            }
+            itw::upload_image(plan, buf, i, st);
+            const uint8_t* src = plan.ptr(i, buf);
+            const int64_t stride = plan.stride(i);
             const rgba_surface& l0 = chain[(size_t)i * levels];
             if (texel_bytes == 4)      hipLaunchKernelGGL((itw::mip_widen_signed_kernel<4>), grid, blk, 0, st, src, stride, l0.ptr, (int64_t)l0.stride, w, h, ops & 3u);
             else if (texel_bytes == 8) hipLaunchKernelGGL((itw::mip_widen_signed_kernel<8>), grid, blk, 0, st, src, stride, l0.ptr, (int64_t)l0.stride, w, h, ops & 3u);
@@ -563,7 +499,7 @@ extern "C" bool itwCompressSignedNormalMapMipped(const rgba_surface* bases, int 
         if (itwGenerateMipChain(chain.data(), items, levels, 8, 0) != 0) itw::fail_msg("itwCompressSignedNormalMapMipped: the mip chain failed: %s", itwLastError());
         // the normalise runs in fp32 on every level inside the chain's gather: no pass of its own, no rounding to half before the quantisation
         done = itwCompressSignedNormalMapChain(chain.data(), items * levels, 8, target, dxgi_format, ops & 4u, progress, user);
-        t_chain.release(st);
+        itw::chain_scratch_done(st);
     });
     return ok && done;
 }

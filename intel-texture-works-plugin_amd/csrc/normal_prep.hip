@@ -144,31 +144,18 @@ void prepare_chain(const rgba_surface* im, int count, int px, uint32_t ops, bool
     hipStream_t st = (hipStream_t)itwGetStream();
     static thread_local std::vector<itw::PrepLevel> desc;         // grow-only, like the device buffer it is copied into
     desc.resize((size_t)count);
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    // the thread's buffer: [level table] [staged images (host pointers), rows of a 16-byte multiple]
-    size_t bytes = count > 1 ? up((size_t)count * sizeof(itw::PrepLevel)) : 0;
+    // the thread's buffer: [level table] [staged images (host pointers)]
+    const itw::StagingPlan plan(im, count, px, dev, count > 1 ? (size_t)count * sizeof(itw::PrepLevel) : 0);
     int64_t quads = 0;
-    std::vector<size_t> stage_off(dev ? 0 : (size_t)count);
     for (int i = 0; i < count; i++) {
-        itw::PrepLevel& d = desc[(size_t)i];
-        d.ptr = im[i].ptr; d.stride = im[i].stride; d.width = im[i].width; d.height = im[i].height;
-        d.first_quad = quads;
-        quads += (int64_t)((im[i].width + 3) >> 2) * im[i].height;
-        if (!dev) {
-            d.stride = (int64_t)(((size_t)im[i].width * px + 15) & ~(size_t)15);
-            stage_off[(size_t)i] = bytes;
-            bytes += up((size_t)d.stride * (size_t)im[i].height);
-        }
+        desc[(size_t)i] = itw::PrepLevel{im[i].ptr, plan.stride(i), im[i].width, im[i].height, quads};
+        quads += itw::texel_quads(im[i].width, im[i].height);
     }
-    if ((quads + 255) / 256 > (int64_t)0x7fffffff) itw::fail_msg("itwPrepareNormalMapChain: %lld texel quads are more than one launch covers", (long long)quads);
+    if (!itw::quads_fit_one_launch(quads)) itw::fail_msg("itwPrepareNormalMapChain: %lld texel quads are more than one launch covers", (long long)quads);
     const bool buffer = !dev || count > 1;                        // a resident chain of one touches no buffer of the thread
-    uint8_t* base = buffer ? static_cast<uint8_t*>(itw::decode_scratch(bytes, st)) : nullptr;
-    if (!dev)
-        for (int i = 0; i < count; i++) {
-            desc[(size_t)i].ptr = base + stage_off[(size_t)i];
-            ITW_CHECK(hipMemcpy2DAsync(desc[(size_t)i].ptr, (size_t)desc[(size_t)i].stride, im[i].ptr, (size_t)im[i].stride, (size_t)im[i].width * px,
-                                       (size_t)im[i].height, hipMemcpyHostToDevice, st));
-        }
+    uint8_t* base = buffer ? static_cast<uint8_t*>(itw::decode_scratch(plan.bytes, st)) : nullptr;
+    if (!dev) for (int i = 0; i < count; i++) desc[(size_t)i].ptr = plan.ptr(i, base);
+    itw::upload_staged(plan, base, st);
     if (count > 1) ITW_CHECK(hipMemcpyAsync(base, desc.data(), (size_t)count * sizeof(itw::PrepLevel), hipMemcpyHostToDevice, st));
     const itw::PrepLevel* d_desc = count > 1 ? reinterpret_cast<const itw::PrepLevel*>(base) : nullptr;
     const dim3 grid((unsigned)((quads + 255) / 256)), blk(256);
@@ -181,9 +168,7 @@ void prepare_chain(const rgba_surface* im, int count, int px, uint32_t ops, bool
     }
     ITW_CHECK(hipGetLastError());
     if (dev) { if (buffer) itw::decode_scratch_done(st); return; }     // resident: asynchronous on the thread's stream
-    for (int i = 0; i < count; i++)                               // width x height only: the caller's row padding is not written
-        ITW_CHECK(hipMemcpy2DAsync(im[i].ptr, (size_t)im[i].stride, desc[(size_t)i].ptr, (size_t)desc[(size_t)i].stride, (size_t)im[i].width * px,
-                                   (size_t)im[i].height, hipMemcpyDeviceToHost, st));
+    itw::download_staged(plan, base, st);                         // width x height only: the caller's row padding is not written
     ITW_CHECK(hipStreamSynchronize(st));
     itw::decode_scratch_done(st);
 }
@@ -194,36 +179,18 @@ void quantize_chain(const rgba_surface* src, int tb, const rgba_surface* dst, in
     hipStream_t st = (hipStream_t)itwGetStream();
     static thread_local std::vector<itw::QuantLevel> desc;        // grow-only, like the device buffer it is copied into
     desc.resize((size_t)count);
-    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    // the thread's buffer: [level table] [staged sources, staged targets (host pointers), rows of a 16-byte multiple]
-    size_t bytes = count > 1 ? up((size_t)count * sizeof(itw::QuantLevel)) : 0;
+    // the thread's buffer: [level table] [staged sources] [staged targets] (host pointers)
+    const itw::StagingPlan from(src, count, tb, dev, count > 1 ? (size_t)count * sizeof(itw::QuantLevel) : 0), to(dst, count, 4, dev, from.bytes);
     int64_t quads = 0;
-    std::vector<size_t> src_off(dev ? 0 : (size_t)count), dst_off(dev ? 0 : (size_t)count);
     for (int i = 0; i < count; i++) {
-        itw::QuantLevel& d = desc[(size_t)i];
-        d.src = src[i].ptr; d.src_stride = src[i].stride; d.dst = dst[i].ptr; d.dst_stride = dst[i].stride;
-        d.width = src[i].width; d.height = src[i].height;
-        d.first_quad = quads;
-        quads += (int64_t)((d.width + 3) >> 2) * d.height;
-        if (!dev) {
-            d.src_stride = (int64_t)(((size_t)d.width * tb + 15) & ~(size_t)15);
-            d.dst_stride = (int64_t)(((size_t)d.width * 4 + 15) & ~(size_t)15);
-            src_off[(size_t)i] = bytes;
-            bytes += up((size_t)d.src_stride * (size_t)d.height);
-            dst_off[(size_t)i] = bytes;
-            bytes += up((size_t)d.dst_stride * (size_t)d.height);
-        }
+        desc[(size_t)i] = itw::QuantLevel{src[i].ptr, dst[i].ptr, from.stride(i), to.stride(i), src[i].width, src[i].height, quads};
+        quads += itw::texel_quads(src[i].width, src[i].height);
     }
-    if ((quads + 255) / 256 > (int64_t)0x7fffffff) itw::fail_msg("itwQuantizeNormalMapChain: %lld texel quads are more than one launch covers", (long long)quads);
+    if (!itw::quads_fit_one_launch(quads)) itw::fail_msg("itwQuantizeNormalMapChain: %lld texel quads are more than one launch covers", (long long)quads);
     const bool buffer = !dev || count > 1;                        // a resident chain of one touches no buffer of the thread
-    uint8_t* base = buffer ? static_cast<uint8_t*>(itw::decode_scratch(bytes, st)) : nullptr;
-    if (!dev)
-        for (int i = 0; i < count; i++) {
-            itw::QuantLevel& d = desc[(size_t)i];
-            d.src = base + src_off[(size_t)i]; d.dst = base + dst_off[(size_t)i];
-            ITW_CHECK(hipMemcpy2DAsync(const_cast<uint8_t*>(d.src), (size_t)d.src_stride, src[i].ptr, (size_t)src[i].stride, (size_t)d.width * tb,
-                                       (size_t)d.height, hipMemcpyHostToDevice, st));
-        }
+    uint8_t* base = buffer ? static_cast<uint8_t*>(itw::decode_scratch(to.bytes, st)) : nullptr;
+    if (!dev) for (int i = 0; i < count; i++) { desc[(size_t)i].src = from.ptr(i, base); desc[(size_t)i].dst = to.ptr(i, base); }
+    itw::upload_staged(from, base, st);
     if (count > 1) ITW_CHECK(hipMemcpyAsync(base, desc.data(), (size_t)count * sizeof(itw::QuantLevel), hipMemcpyHostToDevice, st));
     const itw::QuantLevel* d_desc = count > 1 ? reinterpret_cast<const itw::QuantLevel*>(base) : nullptr;
     if (tb == 4)      itw::launch_normal_quantize<4>(d_desc, desc[0], count, quads, ops, st);
@@ -231,9 +198,7 @@ void quantize_chain(const rgba_surface* src, int tb, const rgba_surface* dst, in
     else              itw::launch_normal_quantize<16>(d_desc, desc[0], count, quads, ops, st);
     ITW_CHECK(hipGetLastError());
     if (dev) { if (buffer) itw::decode_scratch_done(st); return; }     // resident: asynchronous on the thread's stream
-    for (int i = 0; i < count; i++)                               // width x height only: the caller's row padding is not written
-        ITW_CHECK(hipMemcpy2DAsync(dst[i].ptr, (size_t)dst[i].stride, desc[(size_t)i].dst, (size_t)desc[(size_t)i].dst_stride, (size_t)dst[i].width * 4,
-                                   (size_t)dst[i].height, hipMemcpyDeviceToHost, st));
+    itw::download_staged(to, base, st);                           // width x height only: the caller's row padding is not written
     ITW_CHECK(hipStreamSynchronize(st));
     itw::decode_scratch_done(st);
 }
@@ -251,27 +216,19 @@ extern "C" int itwQuantizeNormalMapChain(const rgba_surface* sources, int texel_
         if (ops & ~itw::NORMAL_OPS_ALL) itw::fail_msg("itwQuantizeNormalMapChain: unknown ops bits 0x%x", ops);
         if (count == 0) return;
         if (!sources || !targets) itw::fail_msg("itwQuantizeNormalMapChain: null image list");
+        itw::check_images("itwQuantizeNormalMapChain", "source", sources, count, texel_bytes, texel_bytes);
         for (int i = 0; i < count; i++) {
             const rgba_surface& s = sources[i];
             const rgba_surface& t = targets[i];
-            if (!s.ptr || !t.ptr) itw::fail_msg("itwQuantizeNormalMapChain: image %d: null texel pointer", i);
-            if (s.width < 1 || s.height < 1) itw::fail_msg("itwQuantizeNormalMapChain: image %d: %d x %d", i, s.width, s.height);
             if (t.width != s.width || t.height != s.height)
                 itw::fail_msg("itwQuantizeNormalMapChain: image %d: the target is %d x %d, its source %d x %d", i, t.width, t.height, s.width, s.height);
-            if ((int64_t)s.stride < (int64_t)s.width * texel_bytes || (int64_t)t.stride < (int64_t)t.width * 4)
-                itw::fail_msg("itwQuantizeNormalMapChain: image %d: a stride below the row's bytes", i);
-            const uintptr_t s_step = s.height > 1 ? (uintptr_t)(uint32_t)s.stride : 0, t_step = t.height > 1 ? (uintptr_t)(uint32_t)t.stride : 0;
-            if ((((uintptr_t)s.ptr | s_step) & (uintptr_t)(texel_bytes - 1)) || (((uintptr_t)t.ptr | t_step) & 3))
-                itw::fail_msg("itwQuantizeNormalMapChain: image %d: texels not aligned to their size", i);
         }
+        itw::check_images("itwQuantizeNormalMapChain", "target", targets, count, 4, 4);
     });
     if (!ok) return -1;
     if (count == 0) return 0;
     const bool done = itw::guarded([&] {
-        dev = itw::is_device_pointer(sources[0].ptr);
-        for (int i = 0; i < count; i++)
-            if (itw::is_device_pointer(sources[i].ptr) != dev || itw::is_device_pointer(targets[i].ptr) != dev)
-                itw::fail_msg("itwQuantizeNormalMapChain: image %d: host and device pointers in one call", i);
+        dev = itw::all_one_pointer_kind("itwQuantizeNormalMapChain", "image", sources, count, targets);
         quantize_chain(sources, texel_bytes, targets, count, ops, dev);
     });
     return done ? 0 : -1;
@@ -282,12 +239,7 @@ extern "C" int itwPrepareNormalMapChain(const rgba_surface* images, int count, i
     if (count < 0 || (pixel_size != 4 && pixel_size != 8) || (ops & ~itw::NORMAL_OPS_ALL)) return -1;
     if (count == 0) return 0;
     if (!images) return -1;
-    for (int i = 0; i < count; i++) {
-        const rgba_surface& s = images[i];
-        if (!s.ptr || s.width < 1 || s.height < 1 || (int64_t)s.stride < (int64_t)s.width * pixel_size) return -1;
-        const uintptr_t row_step = s.height > 1 ? (uintptr_t)(uint32_t)s.stride : 0;
-        if (((uintptr_t)s.ptr | row_step) & (uintptr_t)(pixel_size - 1)) return -1;      // every texel 4 / 8 bytes aligned
-    }
+    if (itw::image_list_fault(images, count, pixel_size, pixel_size)) return -1;         // silently, like the rest: never through the error mode
     if (ops == 0) return 0;
     const bool dev = itw::is_device_pointer(images[0].ptr);
     for (int i = 1; i < count; i++)

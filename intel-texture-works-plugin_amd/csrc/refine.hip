@@ -571,11 +571,7 @@ struct ChainFront final : Front {
     ChainFront(const char* who, int kind, const rgba_surface* images, int n) : im(images), count(n), px(itw::texel_bytes(kind))
     {
         packed = true; nimg = n;
-        dsrc = itw::is_device_pointer(im[0].ptr);
-        for (int i = 1; i < count; i++)
-            if (itw::is_device_pointer(im[i].ptr) != dsrc)
-                itw::fail_msg("%s: image %d is %s memory, image 0 %s: all images must be host or all device pointers", who, i,
-                              dsrc ? "host" : "device", dsrc ? "device" : "host");
+        dsrc = itw::all_one_pointer_kind(who, "image", im, count);
         if (dsrc) {
             int cur = 0;
             ITW_CHECK(hipGetDevice(&cur));
