@@ -10,7 +10,9 @@
  *   src host, dst host     : staged H2D -> kernel -> D2H, synchronous (reference semantics)
  *   src device, dst device : kernel only, ASYNCHRONOUS on the calling thread's
  *                            stream (itwSetStream); caller synchronises
- *   mixed                  : the host side is staged, call returns synchronised
+ *   mixed                  : the host side is staged, call returns synchronised.  The work runs on a stream of the
+ *                            library's: a call that reads or writes a caller's device buffer from it first waits for
+ *                            the calling thread's stream (the surface's producer, the destination's last reader).
  * Device pointers must belong to the calling thread's current HIP device.
  */
 #ifndef ITW_AMD_H

@@ -631,7 +631,8 @@ void compress_single_run(const Job& j, const rgba_surface* src, uint8_t* dst, co
 {
     ensure_device_ctx();
     hipStream_t st = tls.own_stream;
-    if (src_dev && tls.user_stream != st) ITW_CHECK(hipStreamSynchronize(tls.user_stream));   // the producer of the device surface may still be running on the caller's stream
+    // the producer of a device surface, or a reader of the device destination, may still be running on the caller's stream
+    if ((src_dev || dst_dev) && tls.user_stream != st) ITW_CHECK(hipStreamSynchronize(tls.user_stream));
     uint8_t* in = src_dev ? nullptr : (uint8_t*)grow(tls.d_in, tls.in_cap, geo.pitch * geo.rows);
     uint8_t* d_dst = dst_dev ? dst : (uint8_t*)grow(tls.d_out, tls.out_cap, geo.out_bytes);
     const LaunchShape shape{(!src_dev && !dst_dev) ? LaunchShape::STAGED : LaunchShape::WHOLE};
@@ -679,7 +680,7 @@ void compress_runs(const Job& j, const rgba_surface* src, uint8_t* dst, const it
     const LaunchShape wide{dst_dev ? LaunchShape::WHOLE : LaunchShape::STAGED};
     const int64_t wide_max = dst_dev ? 0 : staged_wide_max_blocks();
 
-    WindowPipeline pipe(false, 0);                           // (a run's source is host memory: nothing of the caller's to wait for)
+    WindowPipeline pipe(dst_dev, 0);                         // (a run's source is host memory; a device destination may still be read on the caller's stream)
     hipStream_t st = pipe.k0;
     uint8_t* in = (uint8_t*)grow(tls.d_in, tls.in_cap, pitch * geo.rows);
     uint8_t* d_dst = dst_dev ? dst : (uint8_t*)grow(tls.d_out, tls.out_cap, geo.out_bytes);
