@@ -40,6 +40,10 @@
 //                 share of texels passing `alpha >= ref` (1 .. 255) kept at every level.  With --alpha-coverage one line on stdout per
 //                 image: texels, the count passing before and after, the threshold chosen (itwGenerateMipChainAlpha's report).  RGBA8
 //                 colour formats only, as --srgb-mips; not with --normal.
+//     --mip-filter cubic|triangle, --mip-wrap u|v|uv : with --mips: DirectXTex's cubic or triangle filter on every level in place of the
+//                 default's box / linear (ITW_MIP_CUBIC / ITW_MIP_TRIANGLE), and wrap addressing along x, y or both for a tiling texture
+//                 (ITW_MIP_WRAP_U / _V; it changes nothing under the default filter).  Every format; go with --srgb-mips,
+//                 --alpha-coverage, --normal and --cube-cross; not with --alpha-weight or --signed-normal.
 //
 //   encode_dds --decode <in.dds | in.ktx> <out.raw>
 //     (.dds or .ktx: told apart by the file's first bytes; a KTX file's images come in ITS order, level then face)
@@ -393,7 +397,8 @@ int main(int argc, char** argv)
     double refine_value = 0.0;                                  // percent / dB
     bool normal_given = false, cube_cross = false;
     uint32_t normal_ops = 0;                                    // ITW_NORMAL_*
-    bool mips = false, srgb_mips = false, alpha_given = false;
+    bool mips = false, srgb_mips = false, alpha_given = false, filter_given = false;
+    uint32_t filter_flags = 0;                                  // ITW_MIP_CUBIC / _TRIANGLE / _WRAP_U / _WRAP_V
     itw_mip_alpha alpha = { (uint32_t)sizeof(itw_mip_alpha), 0, 0, 0 };
     int mip_levels = 0;                                         // 0: the full chain
     int signed_tb = 0;                                          // --signed-normal: texel bytes of the signed source (4, 8 or 16)
@@ -454,6 +459,21 @@ int main(int argc, char** argv)
             srgb_mips = true;
             for (int k = i; k + 1 < argc; k++) argv[k] = argv[k + 1];
             argc--; i--;
+        } else if (std::strcmp(argv[i], "--mip-filter") == 0 && i + 1 < argc) {
+            filter_given = true;
+            if (std::strcmp(argv[i + 1], "cubic") == 0) filter_flags |= ITW_MIP_CUBIC;
+            else if (std::strcmp(argv[i + 1], "triangle") == 0) filter_flags |= ITW_MIP_TRIANGLE;
+            else { std::fprintf(stderr, "--mip-filter takes cubic or triangle\n"); return 2; }
+            for (int k = i; k + 2 < argc; k++) argv[k] = argv[k + 2];
+            argc -= 2; i--;
+        } else if (std::strcmp(argv[i], "--mip-wrap") == 0 && i + 1 < argc) {
+            filter_given = true;
+            if (std::strcmp(argv[i + 1], "u") == 0) filter_flags |= ITW_MIP_WRAP_U;
+            else if (std::strcmp(argv[i + 1], "v") == 0) filter_flags |= ITW_MIP_WRAP_V;
+            else if (std::strcmp(argv[i + 1], "uv") == 0) filter_flags |= ITW_MIP_WRAP_U | ITW_MIP_WRAP_V;
+            else { std::fprintf(stderr, "--mip-wrap takes u, v or uv\n"); return 2; }
+            for (int k = i; k + 2 < argc; k++) argv[k] = argv[k + 2];
+            argc -= 2; i--;
         } else if (std::strcmp(argv[i], "--alpha-weight") == 0) {
             alpha_given = true; alpha.weight_colour = 1;
             for (int k = i; k + 1 < argc; k++) argv[k] = argv[k + 1];
@@ -466,7 +486,7 @@ int main(int argc, char** argv)
     if (argc < 6) {
         std::fprintf(stderr, "usage: %s [--measure] [--refine <profile> <max_block_sse> | --refine-share <profile> <percent> | --refine-psnr <profile> <dB>]\n"
                              "          [--normal flipx,flipy,normalize | --signed-normal int8|half|float[,flipx,flipy,normalize]] [--cube-cross] [--mips [levels] [--srgb-mips]]\n"
-                             "          [--alpha-weight] [--alpha-coverage <ref>]\n"
+                             "          [--alpha-weight] [--alpha-coverage <ref>] [--mip-filter cubic|triangle] [--mip-wrap u|v|uv]\n"
                              "          <format> <width> <height> <in.raw> <out.dds> [slice_pixels]\n"
                              "       %s --decode <in.dds | in.ktx> <out.raw>\n"
                              "       %s --preview <in.dds | in.ktx> <image index> <out.ppm> <w> <h> <x> <y> <zoom> [channels] [exposure] [matte]\n", argv[0], argv[0], argv[0]);
@@ -487,6 +507,7 @@ int main(int argc, char** argv)
         std::fprintf(stderr, "--alpha-weight and --alpha-coverage go with --mips, and not with --normal or --signed-normal\n");
         return 2;
     }
+    if (filter_given && (!mips || signed_tb)) { std::fprintf(stderr, "--mip-filter and --mip-wrap go with --mips, and not with --signed-normal\n"); return 2; }
     const int texel_bytes = signed_tb ? signed_tb : f->texel_bytes;
     std::vector<uint8_t> texels((size_t)width * height * texel_bytes);
     FILE* in = std::fopen(argv[4], "rb");
@@ -500,7 +521,7 @@ int main(int argc, char** argv)
             std::fprintf(stderr, "--mips does not go with --refine* or --measure; --cube-cross not with etc1_slow\n");
             return 2;
         }
-        return encode_mipped(*f, source, normal_ops, srgb_mips ? (uint32_t)ITW_MIP_SRGB : 0u, alpha_given ? &alpha : nullptr, cube_cross, mip_levels, argv[5]);
+        return encode_mipped(*f, source, normal_ops, (srgb_mips ? (uint32_t)ITW_MIP_SRGB : 0u) | filter_flags, alpha_given ? &alpha : nullptr, cube_cross, mip_levels, argv[5]);
     }
     if (normal_given || cube_cross) {
         // the normal-map and cube-cross stages of the save path (IntelPlugin.cpp:2075-2106, 2149-2152): one call over the image or its six faces

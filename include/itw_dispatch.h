@@ -427,6 +427,44 @@ int itwCubeCrossFaces(const rgba_surface* cross, int pixel_size, rgba_surface fa
  *           filtered from level l-1 as stored, as always.  T is strictly increasing and every constant image keeps its code at every
  *           level.  Both tables are csrc/srgb_tables.h, generated by tools/gen_srgb_tables.py with `decimal` at 60 digits;
  *           itwSrgbToLinear(c) is D[c] and itwLinearToSrgb(v) is E(v), on the host, over those tables.
+ * Mip chains: cubic and triangle.  Two further filters of the same file, chosen by a flag bit and then run on EVERY level of every chain,
+ * whatever the base's size (level l from level l-1 as stored, as always); with neither bit the chain is the default's above, byte for byte.
+ * The same arithmetic rules: IEEE fp32, every operation rounded on its own, no contraction, on the host and in the kernels.  RGBA16F is
+ * pinned byte for byte to the reference's own functions (tests/golden/mipfilter_ref.npz); the cited lines are the authority.
+ *   cubic   (ITW_MIP_CUBIC; _Generate2DMipsCubicFilter :921-1103; _CreateCubicFilter, bounduvw, CUBIC_INTERPOLATE, Filters.h:123-205)  per
+ *           axis: scale = float(source) / float(dest); srcB = (float(u) + 0.5f) * scale - 0.5f; iB = bound((ptrdiff_t)srcB) (in range as it
+ *           is at every ratio >= 1); x = srcB - float(iB); the taps are bound(iB - 1), iB, bound(iB + 1), bound(iB + 2), where bound(t) with
+ *           wrap turns t < 0 into t + source and t > source - 1 into t - source, and then, wrap or not, clamps into [0, source - 1].  The
+ *           value over taps p0..p3: a0 = p1; d0 = p0 - a0; d2 = p2 - a0; d3 = p3 - a0; a1 = (d2 - third*d0) - sixth*d3; a2 = half*d0 + half*d2;
+ *           a3 = (sixth*d3 - sixth*d0) - half*d2; res = ((a0 + a1*x) + a2*(x*x)) + a3*((x*x)*x), with the fp32 constants 1.f/3.f, 1.f/6.f and
+ *           0.5f.  A texel is that expression in y over C0..C3, the four row results over the x taps of the four y-tap rows (:1076-1088).
+ *           At the chain's 2:1 ratio x is 0.5 and the weights are (-1, 9, 9, -1) / 16 per axis: sharper than the box, with negative lobes.
+ *   triangle (ITW_MIP_TRIANGLE; _Generate2DMipsTriangleFilter :1107-1313; TriangleFilter::_Create, Filters.h:249-418)  a tent prefilter
+ *           that weights every source texel under the footprint.  Per axis _Create(source, dest, wrap) gives every source index an ordered
+ *           list of (destination, weight), restated on the host as written: the two passes j = 0, 1 over src = float(u + j) - 0.5f, the
+ *           clamp of destMin / destMax to [0, dest] without wrap, the fold of k < 0 and k >= dest with wrap, weight = (d0 + d1) * scaleInv
+ *           - src (1 and 0 at the clamped ends), accumWeight += (d1 - d0) * (j ? 1 - weight : weight), the merging of consecutive equal
+ *           destinations, and the drop of weights not above TF_EPSILON = 0.00001f.  An output texel starts at 0 and receives
+ *           acc = texel * (yweight * xweight) + acc, a multiply then an add (XMVectorMultiplyAdd's SSE form), in the reference's order of
+ *           arrival: source rows ascending; within a row, source columns ascending; within one source texel, its row entries outside and
+ *           its column entries inside.  The device gathers: the host inverts the lists, order preserved, and the lists of all levels
+ *           travel behind the chain's image table in the same single upload; nothing is read back.
+ *   wrap    (ITW_MIP_WRAP_U along x, ITW_MIP_WRAP_V along y: TEX_FILTER_WRAP_U / _V)  for tiling textures, whose clamped border taps would
+ *           otherwise grow a seam at every level.  Under the DEFAULT filter the bits are accepted and change nothing, and that is the
+ *           reference's behaviour, not an omission: for source >= dest the linear filter's `isrcA < 0` and `isrcB >= source` branches
+ *           (Filters.h:66-102) fire only for 1 -> 1, where the wrapped and the clamped answer coincide, and the box filter never looks past
+ *           an edge.  TEX_FILTER_MIRROR_* has no bit: at ratios >= 1 a cubic tap is at most one texel outside, where bounduvw's mirror
+ *           equals its clamp, and the triangle filter never reads the flag, so mirror changes no byte of any mip chain.
+ *   texel kinds  all three, with the loads and stores above: RGBA16F (0x7E00 for a NaN; +-Inf makes NaN under cubic, and under triangle
+ *           where both signs meet in one sum); RGBA8 on raw codes; RGBA8 with ITW_MIP_SRGB, the filter on D[code] and the store E(v), which
+ *           already sends anything below T[1] to 0 and anything above 1 to 255.  The cubic filter's negative lobes give the raw-code
+ *           store its one missing case: (uint8_t)min(max(v, 0.0f) + 0.5f, 255.0f), the rule above for every v >= 0.
+ *   launches  each level is its own launch (the pyramid route is the box filter's); ITW_MIP_PER_LEVEL is accepted and changes nothing.
+ *   alpha options (itwGenerateMipChainAlpha, below)  coverage_ref combines with both filters: it is a pass over the finished chain.
+ *           weight_colour = 1 with either filter bit is refused: a quotient of sums with negative weights is not an average, and the
+ *           weighted triangle kind is left for later.
+ *   refused, through the error mode, before any device work and with nothing written: ITW_MIP_CUBIC | ITW_MIP_TRIANGLE together, and the
+ *           weight_colour combination.  Bits 2, 8, 0x100 and up stay unknown and refused.
  * Stated divergence.  The reference's box filter sets urow2 / urow3 once before its level loop (:740-741) and, once the height has reached 1,
  * re-points only urow1 (:746-749): from the level where the height is 1 while the width is still above 1, urow3 reads the second scanline
  * of an EARLIER level, which is no longer loaded (for a base of height 1: uninitialised storage).  Square and tall chains -- cube faces
@@ -444,7 +482,8 @@ int itwCubeCrossFaces(const rgba_surface* cross, int pixel_size, rgba_surface fa
  * pyramid route: a 64 x 64 tile of a level gives its part of the next six levels in one launch, a last launch takes a level of at most
  * 64 x 64 down to 1 x 1 (a 4096^2 chain: two launches); ITW_MIP_PER_LEVEL forces one launch per level, as every other chain takes, for
  * comparison and measurement.  Both routes write the same bytes.  ITW_MIP_SRGB (pixel_size 4 only) selects the sRGB colour kind above; it
- * combines with ITW_MIP_PER_LEVEL, takes the same routes and launches, and both routes write the same bytes.  Flag value 2 is unassigned and
+ * combines with ITW_MIP_PER_LEVEL, takes the same routes and launches, and both routes write the same bytes.  ITW_MIP_CUBIC, ITW_MIP_TRIANGLE
+ * and ITW_MIP_WRAP_U / _V: "Mip chains: cubic and triangle" above.  Flag value 2 is unassigned and
  * refused like any unknown bit.  Returns 0, also for items == 0 or levels <= 1 (nothing to do); -1,
  * through the library's error mode and before any device work, for a pixel_size other than 4 or 8, an unknown flag bit, ITW_MIP_SRGB with
  * pixel_size 8, items < 0, a
@@ -461,10 +500,12 @@ int itwCubeCrossFaces(const rgba_surface* cross, int pixel_size, rgba_surface fa
  * and itwGenerateMipChain's launch limits fail through the error mode before any device work.  From host bases only the bases go up and only blocks come down.
  * itwCompressImageMippedEx: the same with `mip_flags` (ITW_MIP_*) handed to the chain's generation; itwCompressImageMipped is this call with
  * mip_flags == 0, byte for byte.  With ITW_MIP_SRGB the colour of every level is filtered in linear light, whatever `dxgi_format` says --
- * 72 / 78 / 99 without the flag keep the plain rule's bytes.  Unknown flag bits, and ITW_MIP_SRGB with an RGBA16F format (95 / 96), a signed
+ * 72 / 78 / 99 without the flag keep the plain rule's bytes.  ITW_MIP_CUBIC / ITW_MIP_TRIANGLE and ITW_MIP_WRAP_U / _V choose the chain's
+ * filter and addressing for every format and go with normal_ops.  Unknown flag bits, both filter bits together, and ITW_MIP_SRGB with an RGBA16F format (95 / 96), a signed
  * format (81 / 84) or normal_ops != 0 (a normal map is not colour), fail through the error mode before any device work.
  * itwSrgbToLinear, itwLinearToSrgb: D[code] and E(v) of the sRGB colour kind; host arithmetic only. */
-enum { ITW_MIP_PER_LEVEL = 1, ITW_MIP_SRGB = 4 };
+enum { ITW_MIP_PER_LEVEL = 1, ITW_MIP_SRGB = 4,
+       ITW_MIP_CUBIC = 0x10, ITW_MIP_TRIANGLE = 0x20, ITW_MIP_WRAP_U = 0x40, ITW_MIP_WRAP_V = 0x80 };
 int itwMipLevels(int width, int height);
 int64_t itwMipChainLayout(int width, int height, int items, int levels, int pixel_size, uint8_t* storage, rgba_surface* out);
 int itwGenerateMipChain(const rgba_surface* images, int items, int levels, int pixel_size, uint32_t flags);
@@ -503,7 +544,8 @@ uint8_t itwLinearToSrgb(float v);
  *    count is an integer sum: the same bits on every run.  A base of more than 2^31 texels is refused with coverage on.
  *
  * itwGenerateMipChainAlpha: itwGenerateMipChain with pixel_size 4 and the two rules.  `flags` takes ITW_MIP_PER_LEVEL and ITW_MIP_SRGB with
- * the same meaning, routes and pointer rules; alpha == NULL is both options off.  `report` (host memory, items * levels rows in DDS order, or
+ * the same meaning, routes and pointer rules, and the filter and wrap bits of "Mip chains: cubic and triangle" (coverage_ref goes with
+ * either filter, weight_colour = 1 with neither); alpha == NULL is both options off.  `report` (host memory, items * levels rows in DDS order, or
  * NULL) receives per image its texels, the count with a >= r before (covered_plain) and after (covered) the rescale, and t* (threshold);
  * level 0 rows hold covered_plain = covered = cov0 and threshold = r.  With `report` the call ends with a synchronise of the thread's
  * stream; without it the call is as asynchronous as itwGenerateMipChain is for the same pointers.  Coverage adds three launches -- the

@@ -110,6 +110,18 @@ void itwTestSrgbEncode(const float* d_in, uint8_t* d_out, int64_t n);
  * each other and tests/test_gpu_alpha_mips.py compares their output.  Process-wide. */
 void itwTestAlphaHistVariant(int spikes);
 
+/* Which cubic mip kernel ITW_MIP_CUBIC launches (csrc/mip_filters.hip): 0 reads its 16 taps from memory, 1 stages the workgroup's source
+ * window in LDS first.  Both write the same bytes; tools/mip_filter_timing.py times them against each other and
+ * tests/test_gpu_mip_filters.py runs both.  Process-wide; the product's choice is the library's default. */
+void itwTestMipCubicVariant(int lds);
+
+/* The host's per-axis tables of the cubic and triangle mip filters (csrc/mip_filters.hpp), as tests/golden/mipfilter_ref.npz records the
+ * reference's _CreateCubicFilter and TriangleFilter::_Create.  kind 1, cubic: index[4 * u .. 4 * u + 3] = the four taps of destination u,
+ * weight[u] = its x; returns dest.  kind 2, triangle: entry e in the reference's stored order, index[2 * e] = the source texel,
+ * index[2 * e + 1] = the destination, weight[e] = the weight; returns the number of entries.  `capacity` counts destinations (cubic) or
+ * entries (triangle) the arrays hold; -1 when it is too small or an argument is out of range.  Host arithmetic only. */
+int64_t itwTestMipFilterTable(int kind, int source, int dest, int wrap, int32_t* index, float* weight, int64_t capacity);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdint>
+#include <vector>
 #include "mipgen.hpp"
 #include "host_rt.hpp"
 
@@ -59,12 +60,12 @@ __device__ __forceinline__ void mip_store_words(uint8_t* p, uint32_t lo, uint32_
 }
 
 // rounds N (1 or 2) consecutive texels to the format and stores them at `p`; `t` becomes the stored values widened
-template <int PX, bool SRGB, int N>
+template <int PX, bool SRGB, int N, bool NEG = false>
 __device__ __forceinline__ void mip_store_row(uint8_t* p, MipTexel* t, const MipSrgbTables* srgb)
 {
     uint32_t lo[N], hi[N];
 #pragma unroll
-    for (int i = 0; i < N; i++) mip_round<PX, SRGB>(t[i], lo[i], hi[i], srgb);
+    for (int i = 0; i < N; i++) mip_round<PX, SRGB, NEG>(t[i], lo[i], hi[i], srgb);
     if constexpr (N == 2) {
         if (PX == 8 && ((uintptr_t)p & 15) == 0) { *reinterpret_cast<uint4*>(p) = make_uint4(lo[0], hi[0], lo[1], hi[1]); return; }
         if (PX == 4 && ((uintptr_t)p & 7) == 0)  { *reinterpret_cast<uint2*>(p) = make_uint2(lo[0], lo[1]); return; }
@@ -258,5 +259,23 @@ void launch_chain_weighted(const MipImage* table, int items, int levels, int w, 
 size_t coverage_work_bytes(int items, int levels);
 size_t coverage_report_offset(int items, int levels);
 void launch_coverage(const MipImage* table, int items, int levels, int w, int h, int ref, uint8_t* work, hipStream_t st);
+
+// ---- mip_filters.hip: ITW_MIP_CUBIC / ITW_MIP_TRIANGLE, one filter on every level, one launch per level ------------------------------------
+
+// a call's filter as its checks left it: kind is mip_filters.hpp's MipFilterKind (0: the default's box or linear, and wrap changes nothing)
+struct MipFilter { int kind = 0; bool wrap_u = false, wrap_v = false; };
+
+// The triangle filter's gather lists of every level and both axes, built on the host: `words` goes to the device behind the chain's image
+// table, in the same upload; x_off[l] / y_off[l] are where level l's lists start in it, repeats[l] whether one source reaches one
+// destination twice in either (mip_filters.hpp mip_triangle_gather).  Nothing for the other kinds.
+struct MipTapPlan {
+    std::vector<uint32_t> words, x_off, y_off, repeats;
+    int built_for[5] = { 0, 0, 0, 0, 0 };                                // levels, w, h, wrap_u, wrap_v of the lists `words` holds
+    size_t build(const MipFilter& f, int levels, int w, int h);          // returns the bytes of `words`
+};
+
+// the launches of one filtered chain, any texel kind: `table` and `taps` (the plan's words; unused by the cubic filter) are on the device
+void launch_chain_filtered(const MipImage* table, const uint32_t* taps, const MipTapPlan& plan, const MipFilter& f, int items, int levels, int w, int h, int px,
+                           bool srgb, hipStream_t st);
 
 } // namespace itw

@@ -19,6 +19,8 @@
 // routes, launches and LDS layouts; the levels kept in registers and LDS between the steps are the stored codes' widened values, as for the others.
 // The kernels' bodies and the launch sequence of a chain are mip_kernels.hpp's, shared with mip_alpha.hip: the alpha-weighted kinds and the
 // coverage passes of itwGenerateMipChainAlpha, whose entry point, checks and staging are this file's (generate_checked, generate_chain).
+// With ITW_MIP_CUBIC or ITW_MIP_TRIANGLE the same entry points hand the chain to mip_filters.hip instead: one filter on every level, one
+// launch per level, and for the triangle filter the host-built gather lists uploaded behind the image table (generate_chain).
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdint>
@@ -31,6 +33,7 @@
 #endif
 #include "mipgen.hpp"
 #include "mip_kernels.hpp"
+#include "mip_filters.hpp"
 #include "normal_prep.hpp"
 #include "bcn_format.hpp"
 #include "host_rt.hpp"
@@ -139,27 +142,35 @@ void launch_plain_chain(const itw::MipImage* table, int items, int levels, int w
 struct AlphaRules { bool weight = false; int coverage_ref = 0; itw_mip_coverage* report = nullptr; };
 
 // everything that needs the device: a chain that passed the checks, all of one pointer kind, levels >= 2
-void generate_chain(const rgba_surface* im, int items, int levels, int px, bool srgb, bool per_level, bool dev, const AlphaRules& alpha)
+void generate_chain(const rgba_surface* im, int items, int levels, int px, bool srgb, bool per_level, bool dev, const AlphaRules& alpha,
+                    const itw::MipFilter& filter)
 {
     hipStream_t st = (hipStream_t)itwGetStream();
     const int count = items * levels;
-    static thread_local std::vector<itw::MipImage> desc;                  // grow-only, like the device buffer it is copied into
-    desc.resize((size_t)count);
-    // the thread's buffer: [table] [the coverage passes' work] [staged images (host pointers)]
-    const size_t work_off = itw::up256((size_t)count * sizeof(itw::MipImage));
+    const int w = im[0].width, h = im[0].height;
+    // what one upload carries: the image table, then the triangle filter's lists (mip_filters.hip) 256-B aligned behind it
+    static thread_local std::vector<uint8_t> head;                        // grow-only, like the device buffer it is copied into
+    static thread_local itw::MipTapPlan taps;
+    const size_t table_bytes = (size_t)count * sizeof(itw::MipImage), taps_off = itw::up256(table_bytes);
+    const size_t taps_bytes = taps.build(filter, levels, w, h), head_bytes = taps_bytes ? taps_off + taps_bytes : table_bytes;
+    head.resize(head_bytes);
+    if (taps_bytes) std::memcpy(head.data() + taps_off, taps.words.data(), taps_bytes);
+    itw::MipImage* desc = reinterpret_cast<itw::MipImage*>(head.data());
+    // the thread's buffer: [table, lists] [the coverage passes' work] [staged images (host pointers)]
+    const size_t work_off = itw::up256(head_bytes);
     const itw::StagingPlan plan(im, count, px, dev, work_off + (alpha.coverage_ref ? itw::coverage_work_bytes(items, levels) : 0));
     uint8_t* base = static_cast<uint8_t*>(itw::decode_scratch(plan.bytes, st));
-    for (int i = 0; i < count; i++) desc[(size_t)i] = itw::MipImage{plan.ptr(i, base), plan.stride(i)};
+    for (int i = 0; i < count; i++) desc[i] = itw::MipImage{plan.ptr(i, base), plan.stride(i)};
     for (int i = 0; i < count; i += levels) itw::upload_image(plan, base, i, st);                                     // only the bases go up
-    ITW_CHECK(hipMemcpyAsync(base, desc.data(), (size_t)count * sizeof(itw::MipImage), hipMemcpyHostToDevice, st));
+    ITW_CHECK(hipMemcpyAsync(base, head.data(), head_bytes, hipMemcpyHostToDevice, st));
     const itw::MipImage* table = reinterpret_cast<const itw::MipImage*>(base);
-    const int w = im[0].width, h = im[0].height;
-    if (alpha.weight) itw::launch_chain_weighted(table, items, levels, w, h, srgb, per_level, st);                   // (RGBA8: the entry point takes no other)
+    if (filter.kind)  itw::launch_chain_filtered(table, reinterpret_cast<const uint32_t*>(base + taps_off), taps, filter, items, levels, w, h, px, srgb, st);
+    else if (alpha.weight) itw::launch_chain_weighted(table, items, levels, w, h, srgb, per_level, st);              // (RGBA8: the entry point takes no other)
     else if (srgb)    launch_plain_chain<4, true>(table, items, levels, w, h, per_level, st);                        // (the entry point refused it with px 8)
     else if (px == 4) launch_plain_chain<4, false>(table, items, levels, w, h, per_level, st);
     else              launch_plain_chain<8, false>(table, items, levels, w, h, per_level, st);
     if (alpha.coverage_ref) {                                             // over the chain as generated, before anything comes back
-        itw::launch_coverage(desc.data(), items, levels, w, h, alpha.coverage_ref, base + work_off, st);
+        itw::launch_coverage(desc, items, levels, w, h, alpha.coverage_ref, base + work_off, st);
         if (alpha.report)
             ITW_CHECK(hipMemcpyAsync(alpha.report, base + work_off + itw::coverage_report_offset(items, levels), (size_t)count * sizeof(itw_mip_coverage),
                                      hipMemcpyDeviceToHost, st));
@@ -189,6 +200,21 @@ AlphaRules check_alpha(const char* who, const itw_mip_alpha* alpha, itw_mip_cove
     if (report && !r.coverage_ref) itw::fail_msg("%s: a report without coverage_ref: there is nothing to report", who);
     r.report = report;
     return r;
+}
+
+// The flag bits of a call, after the alpha checks: `what` is "flag" or "mip flag" as the entry point's messages have it.  Returns the filter.
+constexpr uint32_t kMipFlags = ITW_MIP_PER_LEVEL | ITW_MIP_SRGB | ITW_MIP_CUBIC | ITW_MIP_TRIANGLE | ITW_MIP_WRAP_U | ITW_MIP_WRAP_V;
+itw::MipFilter check_filter_flags(const char* who, const char* what, uint32_t flags, const AlphaRules& alpha)
+{
+    if (flags & ~kMipFlags) itw::fail_msg("%s: unknown %s bits 0x%x", who, what, flags);
+    itw::MipFilter f;
+    if ((flags & ITW_MIP_CUBIC) && (flags & ITW_MIP_TRIANGLE)) itw::fail_msg("%s: ITW_MIP_CUBIC and ITW_MIP_TRIANGLE together: a chain takes one filter", who);
+    f.kind = (flags & ITW_MIP_CUBIC) ? itw::MIP_FILTER_CUBIC : (flags & ITW_MIP_TRIANGLE) ? itw::MIP_FILTER_TRIANGLE : itw::MIP_FILTER_DEFAULT;
+    if (f.kind && alpha.weight)
+        itw::fail_msg("%s: weight_colour with ITW_MIP_%s: a quotient of sums with negative weights is no average, and the weighted triangle kind is not built", who,
+                      f.kind == itw::MIP_FILTER_CUBIC ? "CUBIC" : "TRIANGLE");
+    f.wrap_u = (flags & ITW_MIP_WRAP_U) != 0; f.wrap_v = (flags & ITW_MIP_WRAP_V) != 0;
+    return f;
 }
 
 // what the coverage rule's 64-bit arithmetic holds: cov0 * n of a level, n <= N0 / 2
@@ -287,7 +313,7 @@ int generate_checked(const char* who, const rgba_surface* images, int items, int
     const bool ok = itw::guarded([&] {
         const AlphaRules alpha = check_alpha(who, alpha_in, report);
         if (pixel_size != 4 && pixel_size != 8) itw::fail_msg("%s: pixel_size %d (4: RGBA8, 8: RGBA16F)", who, pixel_size);
-        if (flags & ~(uint32_t)(ITW_MIP_PER_LEVEL | ITW_MIP_SRGB)) itw::fail_msg("%s: unknown flag bits 0x%x", who, flags);
+        const itw::MipFilter filter = check_filter_flags(who, "flag", flags, alpha);
         if ((flags & ITW_MIP_SRGB) && pixel_size != 4) itw::fail_msg("%s: ITW_MIP_SRGB is for RGBA8 texels (pixel_size 4): RGBA16F is linear already", who);
         if (items < 0) itw::fail_msg("%s: %d items", who, items);
         if (items == 0 || levels <= 1) return;
@@ -310,7 +336,7 @@ int generate_checked(const char* who, const rgba_surface* images, int items, int
             if (fault) itw::fail_image(who, fault, s, pixel_size, pixel_size, "item %d level %d", item, l);
         }
         dev = itw::all_one_pointer_kind(who, "image", images, items * levels);
-        generate_chain(images, items, levels, pixel_size, (flags & ITW_MIP_SRGB) != 0, (flags & ITW_MIP_PER_LEVEL) != 0, dev, alpha);
+        generate_chain(images, items, levels, pixel_size, (flags & ITW_MIP_SRGB) != 0, (flags & ITW_MIP_PER_LEVEL) != 0, dev, alpha, filter);
     });
     return ok ? 0 : -1;
 }
@@ -407,7 +433,7 @@ bool compress_mipped(const rgba_surface* bases, int items, int levels, uint32_t 
             if (dxgi_format == 81 || dxgi_format == 84) itw::fail_msg("itwCompressImageMippedAlpha: DXGI format %d, whose texels are signed codes, not colour", dxgi_format);
         }
         if (normal_ops & ~7u) itw::fail_msg("itwCompressImageMipped: unknown ops bits 0x%x", normal_ops);
-        if (mip_flags & ~(uint32_t)(ITW_MIP_PER_LEVEL | ITW_MIP_SRGB)) itw::fail_msg("itwCompressImageMipped: unknown mip flag bits 0x%x", mip_flags);
+        check_filter_flags("itwCompressImageMipped", "mip flag", mip_flags, alpha);
         itw::chain_check_with(bases, items, target, dxgi_format, settings);       // counts, null pointers, sizes, strides, format, settings
         const int px = itw::texel_bytes(itw::format_kind(dxgi_format));
         if (mip_flags & ITW_MIP_SRGB) {                                           // colour in RGBA8 codes, or nothing

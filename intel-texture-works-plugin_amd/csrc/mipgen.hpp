@@ -70,16 +70,20 @@ __device__ __forceinline__ uint32_t mip_half_bits(float v)
 }
 // RGBA8 store: (uint8_t)min(v + 0.5f, 255.0f); v is never negative or NaN here (codes and weights are not)
 __device__ __forceinline__ uint32_t mip_byte(float v) { return (uint32_t)fminf(v + 0.5f, 255.0f); }
+// the same store where a filter has negative lobes (ITW_MIP_CUBIC): (uint8_t)min(max(v, 0.0f) + 0.5f, 255.0f), the rule above for every v >= 0
+__device__ __forceinline__ uint32_t mip_byte_signed(float v) { return (uint32_t)fminf(fmaxf(v, 0.0f) + 0.5f, 255.0f); }
+template <bool NEG> __device__ __forceinline__ uint32_t mip_byte_kind(float v) { return NEG ? mip_byte_signed(v) : mip_byte(v); }
 
-// rounds `t` to the texel format: the words to store, and `t` becomes what a later load of them widens to
-template <int PX, bool SRGB = false>
+// rounds `t` to the texel format: the words to store, and `t` becomes what a later load of them widens to; NEG: the values may be negative
+// (mip_filters.hip's cubic kind), which changes the raw-code store alone
+template <int PX, bool SRGB = false, bool NEG = false>
 __device__ __forceinline__ void mip_round(MipTexel& t, uint32_t& lo, uint32_t& hi, const MipSrgbTables* srgb = nullptr)
 {
     if (SRGB) {
-        lo = mip_srgb_encode(t.c[0], srgb) | (mip_srgb_encode(t.c[1], srgb) << 8) | (mip_srgb_encode(t.c[2], srgb) << 16) | (mip_byte(t.c[3]) << 24);
+        lo = mip_srgb_encode(t.c[0], srgb) | (mip_srgb_encode(t.c[1], srgb) << 8) | (mip_srgb_encode(t.c[2], srgb) << 16) | (mip_byte_kind<NEG>(t.c[3]) << 24);
         hi = 0;
     } else if (PX == 4) {
-        lo = mip_byte(t.c[0]) | (mip_byte(t.c[1]) << 8) | (mip_byte(t.c[2]) << 16) | (mip_byte(t.c[3]) << 24);
+        lo = mip_byte_kind<NEG>(t.c[0]) | (mip_byte_kind<NEG>(t.c[1]) << 8) | (mip_byte_kind<NEG>(t.c[2]) << 16) | (mip_byte_kind<NEG>(t.c[3]) << 24);
         hi = 0;
     } else {
         lo = mip_half_bits(t.c[0]) | (mip_half_bits(t.c[1]) << 16);

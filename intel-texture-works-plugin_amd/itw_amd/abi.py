@@ -42,7 +42,8 @@ EXPORTED_SYMBOLS = tuple(
 # include/itw_test_hooks.h: exported by libispc_texcomp_test.so only (the same sources built with -DITW_TEST_HOOKS), never by the product
 TEST_HOOK_SYMBOLS = ("itwTestRcp", "itwTestRsqrt", "itwTestF2I", "itwTestBc7TwoSubsetBounds", "itwTestBc7RotationBounds", "itwTestBc7F02Scan", "itwTestBc45IndexTable", "itwTestBc45ClosestS",
                      "itwMultiGpuTestInjectFailure", "itwTestCombinerHold", "itwTestCombinerCounters", "itwTestBc7RouteCounters", "itwTestBc7RouteCountersReset",
-                     "itwTestBc7CallCountersArm", "itwTestBc7CallCounters", "itwTestSrgbEncode", "itwTestAlphaHistVariant")
+                     "itwTestBc7CallCountersArm", "itwTestBc7CallCounters", "itwTestSrgbEncode", "itwTestAlphaHistVariant", "itwTestMipCubicVariant",
+                     "itwTestMipFilterTable")
 # enum itw_test_bc7_call_counter (include/itw_test_hooks.h): what itwTestBc7CallCounters fills; the per-band ones are band 0 then band 1
 BC7_CALL_COUNTERS = ("pilot_listed", "pilot_sampled", "pilot_flag", "rot00", "rot01", "rot02", "rot10", "rot11", "rot12", "listed0", "listed1",
                      "pairs0", "pairs1", "overflow0", "overflow1", "redo0", "redo1")
@@ -331,6 +332,10 @@ def _load(path, hooks):
             L.itwTestSrgbEncode.restype = None
             L.itwTestAlphaHistVariant.argtypes = [C.c_int]
             L.itwTestAlphaHistVariant.restype = None
+            L.itwTestMipCubicVariant.argtypes = [C.c_int]
+            L.itwTestMipCubicVariant.restype = None
+            L.itwTestMipFilterTable.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64]
+            L.itwTestMipFilterTable.restype = C.c_int64
         # dispatch layer (itw_dispatch.h)
         L.GetProcessorCount.restype = C.c_int
         L.GetBytesPerBlock.argtypes = [C.c_int]
@@ -1018,6 +1023,19 @@ def cube_cross_faces(img):
 
 MIP_PER_LEVEL = 1     # ITW_MIP_PER_LEVEL (include/itw_dispatch.h)
 MIP_SRGB = 4          # ITW_MIP_SRGB: R, G, B of RGBA8 texels are sRGB coded and filtered in linear light
+MIP_CUBIC = 0x10      # ITW_MIP_CUBIC: DirectXTex's cubic filter on every level
+MIP_TRIANGLE = 0x20   # ITW_MIP_TRIANGLE: DirectXTex's triangle filter on every level
+MIP_WRAP_U = 0x40     # ITW_MIP_WRAP_U / _V: the cubic and triangle filters address the source as a tiling texture along x / y
+MIP_WRAP_V = 0x80
+
+
+def mip_filter_flags(filter=None, wrap=""):
+    """The ITW_MIP_* bits of filter=None | "cubic" | "triangle" and wrap="" | "u" | "v" | "uv"."""
+    if filter not in (None, "cubic", "triangle"):
+        raise ValueError(f"filter {filter!r} (None, 'cubic' or 'triangle')")
+    if wrap not in ("", "u", "v", "uv"):
+        raise ValueError(f"wrap {wrap!r} ('', 'u', 'v' or 'uv')")
+    return {None: 0, "cubic": MIP_CUBIC, "triangle": MIP_TRIANGLE}[filter] | (MIP_WRAP_U if "u" in wrap else 0) | (MIP_WRAP_V if "v" in wrap else 0)
 
 
 class MipAlpha(C.Structure):
@@ -1091,13 +1109,15 @@ def mip_chain_layout(width, height, items=1, levels=0, pixel_size=4):
     return n, [(int(out[i].ptr or 0), out[i].width, out[i].height, out[i].stride) for i in range(count)]
 
 
-def generate_mips(base_or_bases, levels=0, per_level=False, srgb=False, alpha_weight=False, alpha_coverage=0, report=False):
+def generate_mips(base_or_bases, levels=0, per_level=False, srgb=False, alpha_weight=False, alpha_coverage=0, report=False, filter=None, wrap=""):
     """itwGenerateMipChain: the mip levels of one base image or a list of equally sized ones (cube faces, array items): host numpy arrays or
     CUDA torch tensors (H, W, 4), uint8 (RGBA8) or 2-byte elements (RGBA16F half bits), all of one kind.  DirectXTex's box filter when width
     and height are powers of two, else its linear filter (include/itw_dispatch.h).  levels == 0: the full chain.  per_level forces one
     launch per level; srgb (uint8 only) filters R, G, B as sRGB codes in linear light (ITW_MIP_SRGB).  Returns the list of levels [base, level 1, ...] for one base, a list of such lists for a list; the bases themselves
     are level 0 and are not copied.  Device tensors: asynchronous on torch's current stream.  alpha_weight / alpha_coverage (uint8 only) are
-    the rules of itwGenerateMipChainAlpha; with report=True the result is (levels, rows), rows the MipCoverage list in DDS order."""
+    the rules of itwGenerateMipChainAlpha; with report=True the result is (levels, rows), rows the MipCoverage list in DDS order.
+    filter="cubic" | "triangle" runs that DirectXTex filter on every level whatever the size (ITW_MIP_CUBIC / ITW_MIP_TRIANGLE), and
+    wrap="u" | "v" | "uv" lets it address the source as a tiling texture; wrap changes nothing under the default filter."""
     single = hasattr(base_or_bases, "shape")
     bases = [base_or_bases] if single else list(base_or_bases)
     assert bases, "no base image"
@@ -1114,23 +1134,24 @@ def generate_mips(base_or_bases, levels=0, per_level=False, srgb=False, alpha_we
         else:
             import numpy as np
             chains.append([b] + [np.empty((max(1, h >> l), max(1, w >> l), 4), dtype=b.dtype) for l in range(1, n)])
-    rows = generate_mips_into(chains, per_level=per_level, srgb=srgb, alpha_weight=alpha_weight, alpha_coverage=alpha_coverage, report=report)
+    rows = generate_mips_into(chains, per_level=per_level, srgb=srgb, alpha_weight=alpha_weight, alpha_coverage=alpha_coverage, report=report, filter=filter, wrap=wrap)
     if report:
         return (chains[0] if single else chains), rows[1]
     return chains[0] if single else chains
 
 
-def generate_mips_into(chains, per_level=False, srgb=False, alpha_weight=False, alpha_coverage=0, report=False):
+def generate_mips_into(chains, per_level=False, srgb=False, alpha_weight=False, alpha_coverage=0, report=False, filter=None, wrap=""):
     """itwGenerateMipChain over caller-made levels: `chains` is a list of items, each the list of its levels (level 0 filled in), which may
     be strided views of larger arrays / tensors.  Raises ValueError where the call returns -1.  alpha_weight, alpha_coverage or report make
-    it itwGenerateMipChainAlpha (RGBA8); with report=True it returns (chains, [MipCoverage] in DDS order) and is synchronous."""
+    it itwGenerateMipChainAlpha (RGBA8); with report=True it returns (chains, [MipCoverage] in DDS order) and is synchronous.  filter and
+    wrap as generate_mips takes them."""
     flat = [lv for ch in chains for lv in ch]
     on_device = hasattr(flat[0], "data_ptr")
     es = flat[0].element_size() if on_device else flat[0].itemsize
     if on_device:
         import torch
         lib().itwSetStream(torch.cuda.current_stream(flat[0].device).cuda_stream)
-    flags = (MIP_PER_LEVEL if per_level else 0) | (MIP_SRGB if srgb else 0)
+    flags = (MIP_PER_LEVEL if per_level else 0) | (MIP_SRGB if srgb else 0) | mip_filter_flags(filter, wrap)
     if alpha_weight or alpha_coverage or report:
         assert es == 1, "the alpha rules are for RGBA8 texels"
         opts = MipAlpha(1 if alpha_weight else 0, alpha_coverage)
@@ -1145,12 +1166,13 @@ def generate_mips_into(chains, per_level=False, srgb=False, alpha_weight=False, 
 
 
 def compress_mipped(fmt, base_or_bases, levels=0, profile=None, settings=None, normal_ops=0, progress=None, out=None, srgb=False,
-                    alpha_weight=False, alpha_coverage=0):
+                    alpha_weight=False, alpha_coverage=0, filter=None, wrap=""):
     """itwCompressImageMipped: the save path from base images in one call -- flips of `normal_ops` on level 0, the mip chain, the normalise on
     every level, then the chain encoder.  One base or a list of equally sized ones (numpy arrays or CUDA torch tensors, as compress_chain
     takes them); levels == 0: the full chain.  srgb: the chain's colour is filtered in linear light (itwCompressImageMippedEx with
     ITW_MIP_SRGB; the format name is not read as a request).  alpha_weight / alpha_coverage: the rules for cut-out textures
-    (itwCompressImageMippedAlpha; no normal_ops with them).  Returns (ok, blocks): the DDS payload, item-major then level."""
+    (itwCompressImageMippedAlpha; no normal_ops with them).  filter / wrap: the chain's filter, as generate_mips takes them
+    (itwCompressImageMippedEx with ITW_MIP_CUBIC / _TRIANGLE / _WRAP_*).  Returns (ok, blocks): the DDS payload, item-major then level."""
     import numpy as np
     single = hasattr(base_or_bases, "shape")
     bases = [base_or_bases] if single else list(base_or_bases)
@@ -1180,13 +1202,14 @@ def compress_mipped(fmt, base_or_bases, levels=0, profile=None, settings=None, n
         settings = etc_profile(profile or "slow")
     sp = C.cast(C.byref(settings), C.c_void_p) if settings is not None else None
     cb = PROGRESS_FUNC(progress) if progress else None
+    mip_flags = (MIP_SRGB if srgb else 0) | mip_filter_flags(filter, wrap)
     if alpha_weight or alpha_coverage:
         assert not normal_ops, "the alpha rules are for colour, not normal maps"
         opts = MipAlpha(1 if alpha_weight else 0, alpha_coverage)
-        ok = lib().itwCompressImageMippedAlpha(C.cast(_surfaces(bases), C.c_void_p), len(bases), levels, MIP_SRGB if srgb else 0,
+        ok = lib().itwCompressImageMippedAlpha(C.cast(_surfaces(bases), C.c_void_p), len(bases), levels, mip_flags,
                                                C.cast(C.byref(opts), C.c_void_p), dst, DXGI_FORMAT[fmt], sp, C.cast(cb, C.c_void_p) if cb else None, None)
-    elif srgb:
-        ok = lib().itwCompressImageMippedEx(C.cast(_surfaces(bases), C.c_void_p), len(bases), levels, int(normal_ops), MIP_SRGB, dst, DXGI_FORMAT[fmt],
+    elif mip_flags:
+        ok = lib().itwCompressImageMippedEx(C.cast(_surfaces(bases), C.c_void_p), len(bases), levels, int(normal_ops), mip_flags, dst, DXGI_FORMAT[fmt],
                                             sp, C.cast(cb, C.c_void_p) if cb else None, None)
     else:
         ok = lib().itwCompressImageMipped(C.cast(_surfaces(bases), C.c_void_p), len(bases), levels, int(normal_ops), dst, DXGI_FORMAT[fmt],
