@@ -4,9 +4,13 @@
 //
 //   encode_dds [--measure] [--refine <profile> <max_block_sse> | --refine-share <profile> <percent> | --refine-psnr <profile> <dB>]
 //              [--normal flipx,flipy,normalize | --signed-normal int8|half|float[,flipx,flipy,normalize]] [--cube-cross] [--mips [levels] [--srgb-mips]]
-//              [--alpha-weight] [--alpha-coverage <ref>]
+//              [--alpha-weight] [--alpha-coverage <ref>] [--bc-dither rgb|a|rgb,a] [--bc-uniform]
 //              <format> <width> <height> <in.raw> <out.dds> [slice_pixels]
-//     format : bc1 | bc3 | bc4 | bc5 | bc4_snorm | bc5_snorm | bc7_<profile> | bc6h_<profile> | etc1_slow      (profiles: the GetProfile_* names)
+//     format : bc1 | bc1a[:<alpha_ref>] | bc3 | bc4 | bc5 | bc4_snorm | bc5_snorm | bc7_<profile> | bc6h_<profile> | etc1_slow      (profiles: the GetProfile_* names)
+//              bc1a: BC1 with 1-bit alpha by DirectXTex's encoder (ITW_FORMAT_BC1A_UNORM, itw_dispatch.h): a texel whose alpha is below <alpha_ref>
+//              (a float, default 0.5) is transparent; --bc-dither and --bc-uniform are its flags (ITW_BC_DITHER_RGB / _A, ITW_BC_UNIFORM).  The file
+//              is a BC1 file (DXGI 71).  It has no trampoline: the slices go through itwCompressImageSlicedEx; goes with --mips, --alpha-weight,
+//              --alpha-coverage (pass alpha_ref = ref / 255), --cube-cross, --measure; --refine* and --normal are refused
 //              etc1_slow: DDS has no code for ETC1, so the output is a KTX 1.1 file (itwKtx*, itw_dds.h); the slices go through itwCompressImageSlicedEx
 //              (ETC1 has no trampoline); --refine* is refused: ETC1 has one preset
 //     in.raw : width*height tightly packed RGBA8 texels (RGBA16F bit patterns for bc6h_*; RGBA8_SNORM, int8 codes, for bc4_snorm / bc5_snorm)
@@ -74,6 +78,7 @@ struct Format { const char* name; CompressionFunc* fn; int dxgi; int texel_bytes
 
 const Format kFormats[] = {
     {"bc1", CompressImageBC1, ITW_DXGI_FORMAT_BC1_UNORM, 4, true, 7},
+    {"bc1a", nullptr, ITW_FORMAT_BC1A_UNORM, 4, false, 15},                     // no trampoline: itwCompressImageSlicedEx; a DirectXTex format, written as 71
     {"bc3", CompressImageBC3, ITW_DXGI_FORMAT_BC3_UNORM, 4, true, 15},
     {"bc4", CompressImageBC4, ITW_DXGI_FORMAT_BC4_UNORM, 4, false, 1},      // DirectXTex formats keep partial blocks
     {"bc5", CompressImageBC5, ITW_DXGI_FORMAT_BC5_UNORM, 4, false, 3},
@@ -112,6 +117,8 @@ bool profile_by_name(bool bc6h, const char* name, void* settings)
     return false;
 }
 
+itw_bc1a_settings g_bc1a = { (uint32_t)sizeof(itw_bc1a_settings), 0.5f, 0, 0 };      // bc1a[:<alpha_ref>], --bc-dither, --bc-uniform
+
 bool on_progress(int done, int total, void*)
 {
     std::fprintf(stderr, "\rslice %d / %d", done, total);
@@ -140,7 +147,8 @@ int encode_normal_or_cross(const Format& f, const rgba_surface& source, uint32_t
         itwCompressNormalMapBC5(&source, blocks.data(), ops);
         ok = itwLastError() == nullptr;
     } else {
-        ok = itwCompressNormalMapChain(images, count, blocks.data(), f.dxgi, &settings, ops, nullptr, nullptr);
+        ok = (f.dxgi == ITW_FORMAT_BC1A_UNORM && !ops) ? itwCompressImageChainEx(images, count, blocks.data(), f.dxgi, &g_bc1a, nullptr, nullptr)
+                                                       : itwCompressNormalMapChain(images, count, blocks.data(), f.dxgi, &settings, ops, nullptr, nullptr);
     }
     if (!ok) { std::fprintf(stderr, "%s\n", itwLastError() ? itwLastError() : "compression failed"); return 1; }
     if (measure) {
@@ -202,8 +210,9 @@ int encode_mipped(const Format& f, const rgba_surface& source, uint32_t ops, uin
     if (bytes <= 0) { std::fprintf(stderr, "bad size\n"); return 2; }
     std::vector<uint8_t> blocks((size_t)bytes);
     itwSetErrorMode(ITW_ON_ERROR_RETURN);
-    const bool done = alpha ? itwCompressImageMippedAlpha(bases, items, levels, mip_flags, alpha, blocks.data(), f.dxgi, &settings, nullptr, nullptr)
-                            : itwCompressImageMippedEx(bases, items, levels, ops, mip_flags, blocks.data(), f.dxgi, &settings, nullptr, nullptr);
+    const void* sp = f.dxgi == ITW_FORMAT_BC1A_UNORM ? (const void*)&g_bc1a : (const void*)&settings;
+    const bool done = alpha ? itwCompressImageMippedAlpha(bases, items, levels, mip_flags, alpha, blocks.data(), f.dxgi, sp, nullptr, nullptr)
+                            : itwCompressImageMippedEx(bases, items, levels, ops, mip_flags, blocks.data(), f.dxgi, sp, nullptr, nullptr);
     if (!done) {
         std::fprintf(stderr, "%s\n", itwLastError() ? itwLastError() : "compression failed");
         return 1;
@@ -474,6 +483,17 @@ int main(int argc, char** argv)
             else { std::fprintf(stderr, "--mip-wrap takes u, v or uv\n"); return 2; }
             for (int k = i; k + 2 < argc; k++) argv[k] = argv[k + 2];
             argc -= 2; i--;
+        } else if (std::strcmp(argv[i], "--bc-dither") == 0 && i + 1 < argc) {
+            if (std::strcmp(argv[i + 1], "rgb") == 0) g_bc1a.flags |= ITW_BC_DITHER_RGB;
+            else if (std::strcmp(argv[i + 1], "a") == 0) g_bc1a.flags |= ITW_BC_DITHER_A;
+            else if (std::strcmp(argv[i + 1], "rgb,a") == 0 || std::strcmp(argv[i + 1], "a,rgb") == 0) g_bc1a.flags |= ITW_BC_DITHER_RGB | ITW_BC_DITHER_A;
+            else { std::fprintf(stderr, "--bc-dither takes rgb, a or rgb,a\n"); return 2; }
+            for (int k = i; k + 2 < argc; k++) argv[k] = argv[k + 2];
+            argc -= 2; i--;
+        } else if (std::strcmp(argv[i], "--bc-uniform") == 0) {
+            g_bc1a.flags |= ITW_BC_UNIFORM;
+            for (int k = i; k + 1 < argc; k++) argv[k] = argv[k + 1];
+            argc--; i--;
         } else if (std::strcmp(argv[i], "--alpha-weight") == 0) {
             alpha_given = true; alpha.weight_colour = 1;
             for (int k = i; k + 1 < argc; k++) argv[k] = argv[k + 1];
@@ -486,18 +506,22 @@ int main(int argc, char** argv)
     if (argc < 6) {
         std::fprintf(stderr, "usage: %s [--measure] [--refine <profile> <max_block_sse> | --refine-share <profile> <percent> | --refine-psnr <profile> <dB>]\n"
                              "          [--normal flipx,flipy,normalize | --signed-normal int8|half|float[,flipx,flipy,normalize]] [--cube-cross] [--mips [levels] [--srgb-mips]]\n"
-                             "          [--alpha-weight] [--alpha-coverage <ref>] [--mip-filter cubic|triangle] [--mip-wrap u|v|uv]\n"
+                             "          [--alpha-weight] [--alpha-coverage <ref>] [--mip-filter cubic|triangle] [--mip-wrap u|v|uv] [--bc-dither rgb|a|rgb,a] [--bc-uniform]\n"
                              "          <format> <width> <height> <in.raw> <out.dds> [slice_pixels]\n"
                              "       %s --decode <in.dds | in.ktx> <out.raw>\n"
                              "       %s --preview <in.dds | in.ktx> <image index> <out.ppm> <w> <h> <x> <y> <zoom> [channels] [exposure] [matte]\n", argv[0], argv[0], argv[0]);
         return 2;
     }
     const Format* f = nullptr;
+    const bool bc1a = std::strcmp(argv[1], "bc1a") == 0 || std::strncmp(argv[1], "bc1a:", 5) == 0;
+    if (bc1a && argv[1][4] == ':') { g_bc1a.alpha_ref = (float)std::atof(argv[1] + 5); argv[1][4] = '\0'; }
     for (const Format& k : kFormats) if (std::strcmp(k.name, argv[1]) == 0) f = &k;
     const int width = std::atoi(argv[2]), height = std::atoi(argv[3]);
     if (!f || width < 1 || height < 1) { std::fprintf(stderr, "unknown format or bad size\n"); return 2; }
     const long long slice_pixels = argc > 6 ? std::atoll(argv[6]) : 0;
 
+    if (g_bc1a.flags && !bc1a) { std::fprintf(stderr, "--bc-dither and --bc-uniform are bc1a's flags\n"); return 2; }
+    if (bc1a && (normal_given || refine_profile)) { std::fprintf(stderr, "bc1a holds colour and has one encoder: not with --normal or --refine*\n"); return 2; }
     if (signed_tb && (normal_given || refine_profile || measure || (f->dxgi != ITW_DXGI_FORMAT_BC4_SNORM && f->dxgi != ITW_DXGI_FORMAT_BC5_SNORM))) {
         std::fprintf(stderr, "--signed-normal is for bc4_snorm / bc5_snorm and does not go with --normal, --refine* or --measure\n");
         return 2;
@@ -578,6 +602,8 @@ int main(int argc, char** argv)
                              max_block_sse, (unsigned long long)rs.blocks, (unsigned long long)rs.listed, (unsigned long long)rs.replaced,
                              (unsigned long long)rs.sse_first, (unsigned long long)rs.sse_final, (unsigned long long)rs.worst_first, (unsigned long long)rs.worst_final);
         }
+    } else if (bc1a) {
+        ok = itwCompressImageSlicedEx(&padded, blocks.data(), pitch, f->dxgi, &g_bc1a, slice_pixels, slice_pixels ? on_progress : nullptr, nullptr);
     } else if (etc1) {
         etc_enc_settings se;
         itwGetProfile_etc_slow(&se);

@@ -29,6 +29,8 @@ extern "C" {
  * dxgi_format: one of the ITW_DXGI_FORMAT_BC* values of itw_dispatch.h (71,72,77,78,80,81,83,84,95,96,98,99), or ITW_FORMAT_ETC1_RGB8 (0x8D64):
  * ETC1, 8-byte blocks, RGBA8 texels with alpha filled with 255, whole blocks only; modes 0 = individual, 1 = differential, -1 = a differential
  * block whose base + delta leaves 0..31 (invalid in ETC1; decoded with the sum modulo 32 and counted in reserved_blocks).
+ * ITW_FORMAT_BC1A_UNORM / _SRGB (0x83F1 / 0x8C4D, BC1 with 1-bit alpha): synonyms of 71 / 72 in every entry point of this header -- the stream
+ * is a BC1 stream, decoded, measured (itw_error_stats.dxgi_format says 71 / 72) and previewed by the same code.
  * `blocks`, `out`, `modes` are host or device pointers, in any mix.  With all of them on the device the call is one kernel launch,
  * asynchronous on the calling thread's stream (itwSetStream): it allocates nothing, touches no buffer of the thread and can be captured
  * into a graph.  With any host pointer it stages through the calling thread's grow-only device buffer (the one itwDecodeChain uses;

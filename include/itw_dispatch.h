@@ -38,8 +38,30 @@ enum {
      * itwChainBytes and itwCompressImageChain[Ex] below (the block encoder is itwCompressBlocksETC1, itw_amd.h).  It has no CompressImage*
      * trampoline, so itwCompressImageSliced / itwCompressImageChain run a caller's function as the literal loop; the refined calls, the
      * multi-GPU calls and DDS do not know it. */
-    ITW_FORMAT_ETC1_RGB8 = 0x8D64
+    ITW_FORMAT_ETC1_RGB8 = 0x8D64,
+    /* BC1 with 1-bit alpha (punch-through, "DXT1A"): DirectXTex's colour-key encoder, D3DXEncodeBC1 (BC.cpp) as DirectX::Compress calls it.
+     * DXGI has no code of its own for it, GL has: GL_COMPRESSED_RGBA_S3TC_DXT1_EXT and GL_COMPRESSED_SRGB_ALPHA_S3TC_DXT1_EXT (the second
+     * only labels the stream, like 72).  The stream IS a BC1 stream: the decode, measure and preview entry points of itw_decode.h take the
+     * two codes as synonyms of 71 / 72, itwDds* writes them with the header of 71 / 72 (a file read back says 71 / 72); KTX does not know them.
+     * Encoded, with `settings` = const itw_bc1a_settings* or NULL (below), by itwCompressImageSlicedEx (one slice is the single-image call),
+     * itwCompressImageChainEx and the itwCompressImageMipped* calls; itwSliceWindow[For], itwChainBytes and GetBytesPerBlock (8) know them.
+     * They are DirectXTex formats (itw_bc45.h): an RGBA8 source of any size >= 1, partial blocks kept and filled by DirectXTexCompress.cpp's
+     * {0, 0, 0, 1} rule.  A texel code v is the float (float)v * (1.0f / 255.0f).  There is no block-level entry point and no CompressImage*
+     * trampoline: itwCompressImageSliced / itwCompressImageChain run a caller's function as the literal loop, CompressImageMT / ST have no
+     * function to call; the refined calls, the multi-GPU calls and the normal-map chain calls refuse the codes.  BC2 (74 / 75) is not built. */
+    ITW_FORMAT_BC1A_UNORM = 0x83F1, ITW_FORMAT_BC1A_UNORM_SRGB = 0x8C4D
 };
+
+/* Settings of the two BC1A codes.  flags: DirectXTex's BC_FLAGS_* values (BC.h) -- error diffusion of the colours, of alpha (the key test
+ * then sees the diffused, rounded alpha, not the source's), uniform instead of perceptual channel weights.
+ * NULL settings mean alpha_ref = 0.5f, flags = 0: TEX_THRESHOLD_DEFAULT, what the plugin passes to DirectX::Compress.  The struct is copied
+ * while the call is set up.  A struct_size other than 16, reserved != 0, unknown flag bits or a non-finite alpha_ref fail the call through
+ * the error mode before any device work.  Any finite alpha_ref behaves as the reference does: a texel is transparent when its alpha
+ * (float) < alpha_ref, so <= 0 makes no texel transparent and > 1 makes every block 00 00 FF FF FF FF FF FF.
+ * A caller who kept alpha-test coverage with coverage_ref = r (itwCompressImageMippedAlpha) passes alpha_ref = (float)r * (1.0f / 255.0f):
+ * that is the texel conversion's own expression, so "transparent" is exactly a < r on the integer codes. */
+enum { ITW_BC_DITHER_RGB = 0x10000, ITW_BC_DITHER_A = 0x20000, ITW_BC_UNIFORM = 0x40000 };
+typedef struct itw_bc1a_settings { uint32_t struct_size /* 16 */; float alpha_ref; uint32_t flags, reserved /* 0 */; } itw_bc1a_settings;
 
 /* win32Threads.h:52-55 / win32Threads.cpp:98-190.  GetProcessorCount(): number of workers = visible GPUs (>= 1), or the
  * value of the environment variable ITW_WORKERS when set (extra workers share the devices round-robin).

@@ -29,6 +29,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #include <mutex>
 #include <thread>
@@ -264,6 +265,8 @@ struct Job {
     const bc6h_enc_settings* s6 = nullptr;
     int etc_threshold = 0;      // ETC1 only: fastSkipTreshold, >= 1 (a copy: the caller's etc_enc_settings need not outlive job_of)
     uint32_t normal_ops = 0;    // BC5 only (itwCompressNormalMapBC5): ITW_NORMAL_* applied as the kernel loads its texels; such a job is never offered to the combiner
+    float alpha_ref = 0.5f;     // BC1A only (slices and chains; no block-level call, so no combiner): the caller's itw_bc1a_settings, copied --
+    uint32_t bc_flags = 0;      // NULL settings: TEX_THRESHOLD_DEFAULT, no flags
 };
 
 // The workspace (BC7's inter-family one, the wide BC6H shape's) is per host thread: claimed on `st`, and used up to workspace_used(st).
@@ -371,6 +374,7 @@ void launch(const Job& j, const uint8_t* d_src, int64_t stride, int w, int h, ui
         if ((int64_t)(w / 4) * (h / 4) > (int64_t)INT32_MAX) itw::fail_msg("ETC1: %d x %d is more blocks than one launch covers", w, h);
         itw::launch_etc1(d_src, stride, w, h, d_dst, j.etc_threshold, st);
         break;
+    case itw::BCN_BC1A: itw::launch_bc1a(d_src, stride, w, h, d_dst, j.alpha_ref, j.bc_flags, st); break;
     }
     ITW_CHECK(hipGetLastError());
 }
@@ -839,6 +843,17 @@ Job job_of(int dxgi_format, const void* settings)
         if (se->fastSkipTreshold < 1)
             itw::fail_msg("ETC1: fastSkipTreshold %d (1 .. 165; the reference emits uninitialised storage below 1)", se->fastSkipTreshold);
         j.etc_threshold = se->fastSkipTreshold;                               // (above 165: launch_etc1 takes 165)
+        break;
+    }
+    case itw::BCN_BC1A: {
+        const itw_bc1a_settings* sb = static_cast<const itw_bc1a_settings*>(settings);
+        if (!sb) break;                                                       // alpha_ref 0.5f, no flags
+        if (sb->struct_size != sizeof(itw_bc1a_settings)) itw::fail_msg("BC1A: itw_bc1a_settings.struct_size %u (16)", sb->struct_size);
+        if (sb->reserved != 0) itw::fail_msg("BC1A: itw_bc1a_settings.reserved %u (0)", sb->reserved);
+        if (sb->flags & ~(uint32_t)(ITW_BC_DITHER_RGB | ITW_BC_DITHER_A | ITW_BC_UNIFORM)) itw::fail_msg("BC1A: unknown flag bits 0x%x", sb->flags);
+        if (!std::isfinite(sb->alpha_ref)) itw::fail_msg("BC1A: alpha_ref is not finite");
+        j.alpha_ref = sb->alpha_ref;
+        j.bc_flags = sb->flags;
         break;
     }
     default: break;                                                           // BC1 / BC3 / BC4 / BC5 and the SNORM pair take no settings
@@ -1327,7 +1342,8 @@ void chain_check(const rgba_surface* images, int count, const uint8_t* target, i
 {
     alignas(16) static const unsigned char any_settings[sizeof(bc7_enc_settings)] = {0};      // (the caller's own function takes none)
     static const etc_enc_settings any_etc = {1};
-    (void)chain_job(images, count, target, dxgi_format, dxgi_format == ITW_FORMAT_ETC1_RGB8 ? (const void*)&any_etc : (const void*)any_settings);
+    const void* any = dxgi_format == ITW_FORMAT_ETC1_RGB8 ? (const void*)&any_etc : format_kind(dxgi_format) == BCN_BC1A ? nullptr : (const void*)any_settings;
+    (void)chain_job(images, count, target, dxgi_format, any);
 }
 
 void chain_check_with(const rgba_surface* images, int count, const uint8_t* target, int dxgi_format, const void* settings)
@@ -1539,6 +1555,7 @@ bool itwCompressNormalMapChain(const rgba_surface* images, int count, uint8_t* t
     itw::clear_failure();
     const bool ok = itw::guarded([&] {
         if (ops & ~7u) itw::fail_msg("itwCompressNormalMapChain: unknown ops bits 0x%x", ops);
+        if (itw::format_kind(dxgi_format) == itw::BCN_BC1A) itw::fail_msg("itwCompressNormalMapChain: format 0x%X (BC1 with 1-bit alpha) holds colour, not normals", dxgi_format);
         const Job j = chain_job(images, count, target, dxgi_format, settings);
         done = compress_chain(j, images, count, target, progress, user, ops);
     });

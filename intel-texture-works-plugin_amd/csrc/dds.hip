@@ -19,9 +19,12 @@ constexpr uint32_t fourcc(char a, char b, char c, char d)
     return (uint32_t)(uint8_t)a | ((uint32_t)(uint8_t)b << 8) | ((uint32_t)(uint8_t)c << 16) | ((uint32_t)(uint8_t)d << 24);
 }
 
+// the two BC1A codes (itw_dispatch.h) are stored as what their streams are: BC1, 71 / 72
+uint32_t stored_format(uint32_t f) { return f == 0x83F1u ? 71u : f == 0x8C4Du ? 72u : f; }
+
 int bytes_per_block(uint32_t f)
 {
-    switch (f) {
+    switch (stored_format(f)) {
     case 71: case 72: case 80: case 81: return 8;           // BC1, BC4_UNORM, BC4_SNORM
     case 77: case 78: case 83: case 84: case 95: case 96: case 98: case 99: return 16;   // BC3, BC5_UNORM, BC5_SNORM, BC6H, BC7
     default: return 0;
@@ -32,7 +35,7 @@ int bytes_per_block(uint32_t f)
 // (DirectXTexDDS.cpp:474-483; DDS.h:71-96: BC4_UNORM -> "BC4U", BC4_SNORM -> "BC4S", BC5_UNORM -> "BC5U", BC5_SNORM -> "BC5S")
 uint32_t legacy_fourcc(uint32_t f)
 {
-    switch (f) {
+    switch (stored_format(f)) {
     case 71: return fourcc('D', 'X', 'T', '1');
     case 77: return fourcc('D', 'X', 'T', '5');
     case 80: return fourcc('B', 'C', '4', 'U');
@@ -108,7 +111,7 @@ size_t itwDdsWriteHeader(const ItwDdsDesc* d, uint8_t* dst, size_t capacity)
     put32(h, 27, caps2);
     if (needs_dx10(*d)) {
         uint8_t* e = h + 124;                               // DDS_HEADER_DXT10
-        put32(e, 0, d->dxgi_format);
+        put32(e, 0, stored_format(d->dxgi_format));
         put32(e, 1, DIMENSION_TEXTURE2D);
         put32(e, 2, d->is_cubemap ? MISC_TEXTURECUBE : 0);
         put32(e, 3, d->array_size ? d->array_size : 1);     // cubes: number of cubes (:646-650)

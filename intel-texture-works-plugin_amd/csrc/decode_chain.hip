@@ -194,6 +194,7 @@ void decode_chain(const char* who, int kind, const uint8_t* blocks, const rgba_s
 
 extern "C" int itwDecodeChain(int dxgi_format, const uint8_t* blocks, const rgba_surface* outs, int count, int32_t* modes, uint32_t* min_alpha)
 {
+    dxgi_format = itw::stream_format(dxgi_format);                                // the BC1A codes: a BC1 stream
     const int kind = dxgi_format == 96 ? 0 : itw::format_kind(dxgi_format);      // BC6H_SF16: the signed decode is not built, and nothing here may pass for it
     const int64_t total = itw::decode_chain_check(kind, blocks, outs, count);
     if (total <= 0) return total < 0 ? -1 : 0;
@@ -212,7 +213,7 @@ extern "C" int itwDecodeImage(int dxgi_format, const uint8_t* blocks, const rgba
 // The older single-image entry: its own argument rules (decode_blocks_check; 96 reads as unsigned), then a chain of one without min_alpha
 extern "C" int itwDecodeBlocks(int dxgi_format, const uint8_t* blocks, int width, int height, uint8_t* out, int64_t out_stride, int32_t* modes)
 {
-    const int kind = itw::format_kind(dxgi_format);
+    const int kind = itw::format_kind(itw::stream_format(dxgi_format));
     const int64_t total = itw::decode_blocks_check(kind, width, height, out_stride);
     if (total < 0) return -1;
     const rgba_surface surface{out, width, height, (int32_t)out_stride};

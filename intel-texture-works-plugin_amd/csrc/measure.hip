@@ -226,6 +226,7 @@ struct Staging {
 extern "C" int itwMeasureBlocks(int dxgi_format, const uint8_t* blocks, const rgba_surface* source, itw_error_stats* stats, size_t stats_bytes,
                                 uint64_t* block_sse)
 {
+    dxgi_format = itw::stream_format(dxgi_format);            // the BC1A codes: a BC1 stream, measured (and reported in `stats`) as 71 / 72
     const int kind = itw::format_kind(dxgi_format);
     if (!kind || !blocks || !stats || stats_bytes != sizeof(itw_error_stats) || !surface_ok(kind, source)) return -1;
     if (((uintptr_t)stats & 7) || ((uintptr_t)block_sse & 7)) return -1;
@@ -251,6 +252,7 @@ extern "C" int itwMeasureBlocks(int dxgi_format, const uint8_t* blocks, const rg
 
 extern "C" int itwMeasureChain(const rgba_surface* images, int count, const uint8_t* blocks, int dxgi_format, itw_error_stats* stats, size_t stats_bytes)
 {
+    dxgi_format = itw::stream_format(dxgi_format);
     const int kind = itw::format_kind(dxgi_format);
     if (!kind || !images || count < 1 || !blocks || !stats || stats_bytes != sizeof(itw_error_stats) || ((uintptr_t)stats & 7)) return -1;
     int64_t total = 0;
@@ -284,7 +286,7 @@ extern "C" int itwMeasureChain(const rgba_surface* images, int count, const uint
 extern "C" double itwStatsPsnr(const itw_error_stats* stats, uint32_t channel_mask)
 {
     const double nan = std::numeric_limits<double>::quiet_NaN();
-    const int kind = stats ? itw::format_kind(stats->dxgi_format) : 0;
+    const int kind = stats ? itw::format_kind(itw::stream_format(stats->dxgi_format)) : 0;
     if (!stats || !(channel_mask & 15u) || kind == itw::BCN_BC6H) return nan;
     double sum = 0.0;
     int channels = 0;

@@ -10,7 +10,7 @@ There is no CPU implementation in this package: if the library is missing or no
 GPU is present, calls raise / the library aborts.  Nothing here imports oracle/.
 """
 from .abi import (  # noqa: F401
-    lib, test_lib, TEST_HOOK_SYMBOLS, BC7_ROUTE_COUNTERS, lib_path, RgbaSurface, Bc7Settings, Bc6hSettings, EtcSettings, BC7_PROFILES, BC6H_PROFILES,
+    lib, test_lib, TEST_HOOK_SYMBOLS, BC7_ROUTE_COUNTERS, lib_path, RgbaSurface, Bc7Settings, Bc6hSettings, EtcSettings, Bc1aSettings, BC_DITHER_RGB, BC_DITHER_A, BC_UNIFORM, BC7_PROFILES, BC6H_PROFILES,
     bc7_profile, bc6h_profile, etc_profile, compress, compress_numpy, band_for_part, version, device_info,
     BYTES_PER_BLOCK, EXPORTED_SYMBOLS, DXGI_FORMAT, DdsDesc, image_func, compress_image, PROGRESS_FUNC, pad_to_multiple_of_4, dds_file, decode, block_count, KEEPS_PARTIAL_BLOCKS, SIGNED_FORMATS,
     available, set_error_mode, last_error, ON_ERROR_ABORT, ON_ERROR_RETURN, set_bc7_path, set_bc7_pilot, compress_image_multigpu, multigpu_sub_bands, MultiGpuStats, source_sha256, bc7_two_subset_bounds, bc7_rotation_bounds, bc7_f02_scan,

@@ -6,8 +6,8 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 _LIB = os.path.normpath(os.path.join(_PKG, "..", "lib", "libispc_texcomp.so"))
 _TEST_LIB = os.path.normpath(os.path.join(_PKG, "..", "lib", "libispc_texcomp_test.so"))
 
-BYTES_PER_BLOCK = {"bc1": 8, "bc3": 16, "bc7": 16, "bc6h": 16, "bc4": 8, "bc5": 16, "bc4_snorm": 8, "bc5_snorm": 16, "etc1": 8}
-KEEPS_PARTIAL_BLOCKS = ("bc4", "bc5", "bc4_snorm", "bc5_snorm")     # DirectXTex formats: ceil(w/4) x ceil(h/4) blocks (include/itw_bc45.h)
+BYTES_PER_BLOCK = {"bc1": 8, "bc3": 16, "bc7": 16, "bc6h": 16, "bc4": 8, "bc5": 16, "bc4_snorm": 8, "bc5_snorm": 16, "etc1": 8, "bc1a": 8, "bc1a_srgb": 8}
+KEEPS_PARTIAL_BLOCKS = ("bc4", "bc5", "bc4_snorm", "bc5_snorm", "bc1a", "bc1a_srgb")     # DirectXTex formats: ceil(w/4) x ceil(h/4) blocks (include/itw_bc45.h)
 SIGNED_FORMATS = ("bc4_snorm", "bc5_snorm")     # RGBA8_SNORM sources: int8 arrays / tensors, never uint8 (include/itw_bc45.h)
 BC7_PROFILES = ("ultrafast", "veryfast", "fast", "basic", "slow",
                 "alpha_ultrafast", "alpha_veryfast", "alpha_fast", "alpha_basic", "alpha_slow")
@@ -80,11 +80,32 @@ class EtcSettings(C.Structure):
     _fields_ = [("fastSkipTreshold", C.c_int)]
 
 
-assert C.sizeof(RgbaSurface) == 24 and C.sizeof(Bc7Settings) == 64 and C.sizeof(Bc6hSettings) == 16 and C.sizeof(EtcSettings) == 4
+BC_DITHER_RGB, BC_DITHER_A, BC_UNIFORM = 0x10000, 0x20000, 0x40000      # ITW_BC_* (itw_dispatch.h): DirectXTex's BC_FLAGS_* values
+
+
+class Bc1aSettings(C.Structure):
+    """struct itw_bc1a_settings (itw_dispatch.h), 16 bytes: the settings of "bc1a" / "bc1a_srgb", BC1 with 1-bit alpha by DirectXTex's encoder.
+    A texel is transparent when its alpha (code * (1/255) in fp32) < alpha_ref; a caller who kept coverage with alpha_coverage=r passes
+    alpha_ref=Bc1aSettings.ref_of(r).  None where settings are taken means Bc1aSettings()."""
+    _fields_ = [("struct_size", C.c_uint32), ("alpha_ref", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def __init__(self, alpha_ref=0.5, dither_rgb=False, dither_a=False, uniform=False):
+        super().__init__(16, alpha_ref, (BC_DITHER_RGB if dither_rgb else 0) | (BC_DITHER_A if dither_a else 0) | (BC_UNIFORM if uniform else 0), 0)
+
+    @staticmethod
+    def ref_of(code):
+        """(float)code * (1.0f / 255.0f): the texel conversion's own expression, so that a < alpha_ref is a < code on the integer codes."""
+        import numpy as np
+        return float(np.float32(code) * (np.float32(1.0) / np.float32(255.0)))
+
+
+assert C.sizeof(RgbaSurface) == 24 and C.sizeof(Bc7Settings) == 64 and C.sizeof(Bc6hSettings) == 16 and C.sizeof(EtcSettings) == 4 and C.sizeof(Bc1aSettings) == 16
 
 # "etc1": ITW_FORMAT_ETC1_RGB8, the GL enum (ETC1 has no DXGI code); decode, measure, the slice pipeline and the chain calls take it (with an
 # EtcSettings); the refined calls, the multi-GPU calls and DDS refuse it -- its container is KTX (KtxDesc, ktx_file, load_ktx)
-DXGI_FORMAT = {"etc1": 0x8D64, "bc1": 71, "bc1_srgb": 72, "bc3": 77, "bc3_srgb": 78, "bc4": 80, "bc4_snorm": 81, "bc5": 83, "bc5_snorm": 84, "bc6h": 95, "bc6h_sf16": 96, "bc7": 98, "bc7_srgb": 99}
+# "bc1a" / "bc1a_srgb": ITW_FORMAT_BC1A_UNORM[_SRGB], GL enums likewise (DXGI has no code for BC1 with alpha): the slice pipeline, the chain and
+# the mipped calls encode them (with a Bc1aSettings or None); decode, measure, preview and DDS take them as synonyms of "bc1" / "bc1_srgb"
+DXGI_FORMAT = {"bc1a": 0x83F1, "bc1a_srgb": 0x8C4D, "etc1": 0x8D64, "bc1": 71, "bc1_srgb": 72, "bc3": 77, "bc3_srgb": 78, "bc4": 80, "bc4_snorm": 81, "bc5": 83, "bc5_snorm": 84, "bc6h": 95, "bc6h_sf16": 96, "bc7": 98, "bc7_srgb": 99}
 
 
 class DdsDesc(C.Structure):
@@ -124,7 +145,7 @@ class MultiGpuStats(C.Structure):
 
 
 # the channels of a decoded texel that carry a format's own data (the others are fill values: itw_decode.h)
-OWN_CHANNELS = {"bc1": "rgb", "bc3": "rgba", "bc4": "r", "bc5": "rg", "bc4_snorm": "r", "bc5_snorm": "rg", "bc6h": "rgb", "bc7": "rgba", "etc1": "rgb"}
+OWN_CHANNELS = {"bc1": "rgb", "bc3": "rgba", "bc4": "r", "bc5": "rg", "bc4_snorm": "r", "bc5_snorm": "rg", "bc6h": "rgb", "bc7": "rgba", "etc1": "rgb", "bc1a": "rgba", "bc1a_srgb": "rgba"}
 _DXGI_BASE = {71: "bc1", 72: "bc1", 77: "bc3", 78: "bc3", 80: "bc4", 81: "bc4_snorm", 83: "bc5", 84: "bc5_snorm", 95: "bc6h", 96: "bc6h",
               98: "bc7", 99: "bc7", 0x8D64: "etc1"}
 
@@ -597,6 +618,13 @@ def _call(fmt, surf, dst_ptr, settings):
     elif fmt == "etc1":
         st = settings if isinstance(settings, EtcSettings) else etc_profile(settings or "slow")
         L.itwCompressBlocksETC1(C.byref(surf), dst_ptr, C.byref(st))
+    elif fmt in ("bc1a", "bc1a_srgb"):
+        # no block-level entry point: the single image is the slice call with one slice (synchronous)
+        assert settings is None or isinstance(settings, Bc1aSettings)
+        pitch = ((surf.width + 3) // 4) * 8
+        if not L.itwCompressImageSlicedEx(C.byref(surf), dst_ptr, pitch, DXGI_FORMAT[fmt], C.cast(C.byref(settings), C.c_void_p) if settings is not None else None,
+                                          1 << 62, None, None) and L.itwLastError():
+            raise RuntimeError(L.itwLastError().decode())
     else:
         raise ValueError(fmt)
 
@@ -736,8 +764,8 @@ def compress_image(fmt, img, profile=None, multithreaded=True, slice_pixels=0, p
     pitch = block_count(fmt, w, 4) * BYTES_PER_BLOCK[fmt]
     if fmt == "etc1" and settings is None:
         settings = etc_profile(profile or "slow")
-    if settings is not None:
-        ok = lib().itwCompressImageSlicedEx(C.byref(surf), dst, pitch, DXGI_FORMAT[fmt], C.cast(C.byref(settings), C.c_void_p), slice_pixels,
+    if settings is not None or _base(fmt) == "bc1a":                    # ("bc1a": no trampoline either; None is Bc1aSettings())
+        ok = lib().itwCompressImageSlicedEx(C.byref(surf), dst, pitch, DXGI_FORMAT[fmt], C.cast(C.byref(settings), C.c_void_p) if settings is not None else None, slice_pixels,
                                             C.cast(cb, C.c_void_p) if cb else None, None)
     else:
         ok = lib().itwCompressImageSliced(C.byref(surf), dst, pitch, image_func(fmt, profile),
@@ -1166,13 +1194,15 @@ def generate_mips_into(chains, per_level=False, srgb=False, alpha_weight=False, 
 
 
 def compress_mipped(fmt, base_or_bases, levels=0, profile=None, settings=None, normal_ops=0, progress=None, out=None, srgb=False,
-                    alpha_weight=False, alpha_coverage=0, filter=None, wrap=""):
+                    alpha_weight=False, alpha_coverage=0, filter=None, wrap="", report=False):
     """itwCompressImageMipped: the save path from base images in one call -- flips of `normal_ops` on level 0, the mip chain, the normalise on
     every level, then the chain encoder.  One base or a list of equally sized ones (numpy arrays or CUDA torch tensors, as compress_chain
     takes them); levels == 0: the full chain.  srgb: the chain's colour is filtered in linear light (itwCompressImageMippedEx with
     ITW_MIP_SRGB; the format name is not read as a request).  alpha_weight / alpha_coverage: the rules for cut-out textures
     (itwCompressImageMippedAlpha; no normal_ops with them).  filter / wrap: the chain's filter, as generate_mips takes them
-    (itwCompressImageMippedEx with ITW_MIP_CUBIC / _TRIANGLE / _WRAP_*).  Returns (ok, blocks): the DDS payload, item-major then level."""
+    (itwCompressImageMippedEx with ITW_MIP_CUBIC / _TRIANGLE / _WRAP_*).  Returns (ok, blocks): the DDS payload, item-major then level.
+    report=True (with the alpha rules): (ok, blocks, rows), rows the MipCoverage list of the same chain in DDS order -- the encode call has no
+    report of its own, so the chain is generated once more for it (generate_mips with the same options, which is deterministic)."""
     import numpy as np
     single = hasattr(base_or_bases, "shape")
     bases = [base_or_bases] if single else list(base_or_bases)
@@ -1214,6 +1244,10 @@ def compress_mipped(fmt, base_or_bases, levels=0, profile=None, settings=None, n
     else:
         ok = lib().itwCompressImageMipped(C.cast(_surfaces(bases), C.c_void_p), len(bases), levels, int(normal_ops), dst, DXGI_FORMAT[fmt],
                                           sp, C.cast(cb, C.c_void_p) if cb else None, None)
+    if report:
+        assert alpha_weight or alpha_coverage, "the report is the alpha rules'"
+        rows = generate_mips(bases, levels=levels, srgb=srgb, alpha_weight=alpha_weight, alpha_coverage=alpha_coverage, report=True, filter=filter, wrap=wrap)[1]
+        return bool(ok), out, rows
     return bool(ok), out
 
 
@@ -1337,7 +1371,7 @@ def decode(fmt, blocks, width, height, want_modes=False):
     (H, W, 4) uint8 -- uint16 half bit patterns for bc6h, int8 for the signed formats -- in the same kind of container, plus the per-block modes
     (int32) when asked."""
     import numpy as np
-    key = {"bc1": 71, "bc3": 77, "bc7": 98, "bc6h": 95, "bc4": 80, "bc5": 83, "bc4_snorm": 81, "bc5_snorm": 84, "etc1": 0x8D64}[fmt]
+    key = {"bc1": 71, "bc3": 77, "bc7": 98, "bc6h": 95, "bc4": 80, "bc5": 83, "bc4_snorm": 81, "bc5_snorm": 84, "etc1": 0x8D64, "bc1a": 0x83F1, "bc1a_srgb": 0x8C4D}[fmt]
     signed = fmt in SIGNED_FORMATS                      # RGBA8_SNORM texels: int8
     nb = block_count(fmt, width, height)
     es = 2 if fmt == "bc6h" else 1
