@@ -4,6 +4,7 @@
 //
 //   encode_dds [--measure] [--refine <profile> <max_block_sse> | --refine-share <profile> <percent> | --refine-psnr <profile> <dB>]
 //              [--normal flipx,flipy,normalize | --signed-normal int8|half|float[,flipx,flipy,normalize]] [--cube-cross] [--mips [levels] [--srgb-mips]]
+//              [--height r|g|b|a|lum[,mirroru,mirrorv,invert,occlusion] [--height-amplitude <A>]]
 //              [--alpha-weight] [--alpha-coverage <ref>] [--bc-dither rgb|a|rgb,a] [--bc-uniform]
 //              <format> <width> <height> <in.raw> <out.dds> [slice_pixels]
 //     format : bc1 | bc1a[:<alpha_ref>] | bc3 | bc4 | bc5 | bc4_snorm | bc5_snorm | bc7_<profile> | bc6h_<profile> | etc1_slow      (profiles: the GetProfile_* names)
@@ -31,6 +32,13 @@
 //                 through itwCompressNormalMapBC5S (one kernel), bc4_snorm through itwCompressSignedNormalMapChain with one image; with
 //                 --cube-cross the six faces through that chain call, with --mips everything through itwCompressSignedNormalMapMipped.
 //                 Not with --normal (whose biased 8-bit behaviour stays), --refine* or --measure; the slice loop is not used.
+//     --height r|g|b|a|lum[,mirroru,mirrorv,invert,occlusion], --height-amplitude <A> : with --normal or --signed-normal: the input is a
+//                 HEIGHT map (bump, displacement), and DirectXTex's ComputeNormalMap (Texconv's -nmap / -nmapamp) makes the normal map from the
+//                 named channel first: ITW_NORMAL_FROM_HEIGHT in the calls' `ops` word (itw_dispatch.h, "height maps").  An axis wraps unless
+//                 mirrored; occlusion puts the occlusion term into alpha; A (default 1) is rounded to a half.  With --mips the one-call saves take
+//                 the word themselves (the stage writes level 0); without, the stage runs first over the image or each cross face --
+//                 itwPrepareNormalMapChain in place for --normal, itwQuantizeNormalMapChain into an int8 map for --signed-normal -- with the
+//                 flips and the normalise, and the encoders then see a finished map.
 //     --cube-cross : the input is a horizontal (4 x 3 faces) or vertical (3 x 4) cube cross; its six faces (itwCubeCrossFaces: views, no
 //                 copy) are encoded by one chain call into a cube-map DDS.  Goes with --normal; not with --refine*, --measure or etc1_slow.
 //     --mips [levels] : a mipped file from the base image (or the six cross faces) in one call, itwCompressImageMipped: the save path's
@@ -254,6 +262,22 @@ int encode_mipped(const Format& f, const rgba_surface& source, uint32_t ops, uin
     return 0;
 }
 
+// --height-amplitude: a float as the bits of the nearest IEEE half (ties to even; overflow gives 0x7C00, which the caller refuses)
+uint32_t half_bits_of(float v)
+{
+    uint32_t x;
+    std::memcpy(&x, &v, sizeof x);
+    if ((x >> 31) || x > 0x7f800000u) return 0;                 // negative or NaN: refused as 0 is
+    if (x >= 0x477ff000u) return 0x7c00u;
+    if (x < 0x33000001u) return 0;
+    const bool tiny = x < 0x38800000u;
+    const uint32_t m = tiny ? ((x & 0x7fffffu) | 0x800000u) : x - 0x38000000u, shift = tiny ? 126u - (x >> 23) : 13u;
+    uint32_t r = m >> shift;
+    const uint32_t rem = m & ((1u << shift) - 1u), halfway = 1u << (shift - 1u);
+    if (rem > halfway || (rem == halfway && (r & 1u))) r++;
+    return r;
+}
+
 // encode_dds --signed-normal: a signed normal source of `tb`-byte texels (or its six cross faces) to BC4_SNORM / BC5_SNORM, mipped or not
 int encode_signed_normal(const Format& f, const rgba_surface& source, int tb, uint32_t ops, bool cube_cross, bool mips, int levels, const char* out_path)
 {
@@ -411,6 +435,7 @@ int main(int argc, char** argv)
     itw_mip_alpha alpha = { (uint32_t)sizeof(itw_mip_alpha), 0, 0, 0 };
     int mip_levels = 0;                                         // 0: the full chain
     int signed_tb = 0;                                          // --signed-normal: texel bytes of the signed source (4, 8 or 16)
+    uint32_t height_ops = 0, height_amplitude = 0x3C00;         // --height: ITW_NORMAL_FROM_HEIGHT and its fields; the amplitude as half bits (1.0)
     for (int i = 1; i < argc; i++)
         if (std::strcmp(argv[i], "--measure") == 0) {
             measure = true;
@@ -451,6 +476,27 @@ int main(int argc, char** argv)
                 else { std::fprintf(stderr, "--signed-normal takes int8, half or float, then a list of flipx, flipy, normalize\n"); return 2; }
                 p += n + (p[n] == ',' ? 1 : 0);
             }
+            for (int k = i; k + 2 < argc; k++) argv[k] = argv[k + 2];
+            argc -= 2; i--;
+        } else if (std::strcmp(argv[i], "--height") == 0 && i + 1 < argc) {
+            height_ops |= ITW_NORMAL_FROM_HEIGHT;
+            for (const char* p = argv[i + 1]; *p;) {
+                const size_t n = std::strcspn(p, ",");
+                const bool first = p == argv[i + 1];
+                if (first && n == 1 && std::strchr("rgba", *p)) height_ops |= ITW_HEIGHT_CHANNEL(1 + (std::strchr("rgba", *p) - "rgba"));
+                else if (first && n == 3 && std::strncmp(p, "lum", 3) == 0) height_ops |= ITW_HEIGHT_CHANNEL(5);
+                else if (!first && n == 7 && std::strncmp(p, "mirroru", 7) == 0) height_ops |= ITW_HEIGHT_MIRROR_U;
+                else if (!first && n == 7 && std::strncmp(p, "mirrorv", 7) == 0) height_ops |= ITW_HEIGHT_MIRROR_V;
+                else if (!first && n == 6 && std::strncmp(p, "invert", 6) == 0) height_ops |= ITW_HEIGHT_INVERT_SIGN;
+                else if (!first && n == 9 && std::strncmp(p, "occlusion", 9) == 0) height_ops |= ITW_HEIGHT_OCCLUSION;
+                else { std::fprintf(stderr, "--height takes r, g, b, a or lum, then a list of mirroru, mirrorv, invert, occlusion\n"); return 2; }
+                p += n + (p[n] == ',' ? 1 : 0);
+            }
+            for (int k = i; k + 2 < argc; k++) argv[k] = argv[k + 2];
+            argc -= 2; i--;
+        } else if (std::strcmp(argv[i], "--height-amplitude") == 0 && i + 1 < argc) {
+            height_amplitude = half_bits_of((float)std::atof(argv[i + 1]));
+            if (height_amplitude == 0 || height_amplitude >= 0x7C00) { std::fprintf(stderr, "--height-amplitude: finite and above 0 once rounded to a half\n"); return 2; }
             for (int k = i; k + 2 < argc; k++) argv[k] = argv[k + 2];
             argc -= 2; i--;
         } else if (std::strcmp(argv[i], "--cube-cross") == 0) {
@@ -506,6 +552,7 @@ int main(int argc, char** argv)
     if (argc < 6) {
         std::fprintf(stderr, "usage: %s [--measure] [--refine <profile> <max_block_sse> | --refine-share <profile> <percent> | --refine-psnr <profile> <dB>]\n"
                              "          [--normal flipx,flipy,normalize | --signed-normal int8|half|float[,flipx,flipy,normalize]] [--cube-cross] [--mips [levels] [--srgb-mips]]\n"
+                             "          [--height r|g|b|a|lum[,mirroru,mirrorv,invert,occlusion] [--height-amplitude <A>]]\n"
                              "          [--alpha-weight] [--alpha-coverage <ref>] [--mip-filter cubic|triangle] [--mip-wrap u|v|uv] [--bc-dither rgb|a|rgb,a] [--bc-uniform]\n"
                              "          <format> <width> <height> <in.raw> <out.dds> [slice_pixels]\n"
                              "       %s --decode <in.dds | in.ktx> <out.raw>\n"
@@ -539,6 +586,31 @@ int main(int argc, char** argv)
     std::fclose(in);
 
     rgba_surface source = { texels.data(), width, height, width * texel_bytes };
+    std::vector<uint8_t> quantised;                             // --height with --signed-normal and no --mips: the RGBA8_SNORM map
+    if (height_ops) {
+        // the input is a height map.  The one-call saves take the bit themselves; the other routes see one texel or one block at a time, so
+        // the stage runs first, over the image or each face of its cross: in place (itwPrepareNormalMapChain) or into an int8 copy
+        // (itwQuantizeNormalMapChain), with the flips and the normalise, which then are done
+        if (!normal_given && !signed_tb) { std::fprintf(stderr, "--height goes with --normal or --signed-normal\n"); return 2; }
+        normal_ops |= height_ops | ITW_HEIGHT_AMPLITUDE(height_amplitude);
+        if (!mips) {
+            rgba_surface faces[6] = {source}, targets[6];
+            const int items = cube_cross ? 6 : 1;
+            if (cube_cross && itwCubeCrossFaces(&source, texel_bytes, faces) != 0) { std::fprintf(stderr, "%d x %d is too small for a cube cross\n", width, height); return 2; }
+            itwSetErrorMode(ITW_ON_ERROR_RETURN);
+            int rc;
+            if (signed_tb) {
+                quantised.resize((size_t)width * height * 4);
+                const rgba_surface map = { quantised.data(), width, height, width * 4 };
+                targets[0] = map;
+                if (cube_cross) itwCubeCrossFaces(&map, 4, targets);
+                rc = itwQuantizeNormalMapChain(faces, signed_tb, targets, items, normal_ops);
+                source = map; signed_tb = 4;
+            } else rc = itwPrepareNormalMapChain(faces, items, texel_bytes, normal_ops);
+            if (rc != 0) { std::fprintf(stderr, "%s\n", itwLastError() ? itwLastError() : "the height stage refused the call"); return 1; }
+            normal_ops = 0;
+        }
+    }
     if (signed_tb) return encode_signed_normal(*f, source, signed_tb, normal_ops, cube_cross, mips, mip_levels, argv[5]);
     if (mips) {
         if (refine_profile || measure || (cube_cross && f->dxgi == ITW_FORMAT_ETC1_RGB8)) {

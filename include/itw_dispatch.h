@@ -349,8 +349,43 @@ int itwConvertToRGBA16FDevice(const void* src, int depth, int planes, int has_al
  * thread's stream.  Host pointers: staged through the thread's buffer; returns synchronised.  Nothing outside width x height of an image is
  * written: row padding stays as it is.  Returns 0, also for count == 0 or ops == 0; -1, before any device work, for a null pointer,
  * count < 0, a pixel_size other than 4 or 8, unknown ops bits, a width or height < 1, a stride below the row's bytes, texels that are not
- * pixel_size aligned, or mixed host and device pointers. */
-enum { ITW_NORMAL_FLIP_X = 1, ITW_NORMAL_FLIP_Y = 2, ITW_NORMAL_NORMALIZE = 4 };
+ * pixel_size aligned, or mixed host and device pointers.
+ *
+ * Height maps.  With ITW_NORMAL_FROM_HEIGHT in `ops` the images handed in are height maps (bump, displacement), and DirectXTex's
+ * ComputeNormalMap (DirectXTexNormalMaps.cpp:22-244, Texconv's -nmap / -nmapamp) turns each into a tangent-space normal map before the bits
+ * above apply with their usual meaning.  The further bits count only together with ITW_NORMAL_FROM_HEIGHT; without it every bit above 7 is
+ * unknown, as it always was:
+ *   ITW_HEIGHT_CHANNEL(c)    0 and 1 red, 2 green, 3 blue, 4 alpha, 5 luminance (r*0.2125f + g*0.7154f) + b*0.0721f; 6..15 are refused
+ *   ITW_HEIGHT_MIRROR_U, _V  the neighbour beyond an edge is the edge's own column (row); without them the axis wraps to the opposite edge
+ *   ITW_HEIGHT_INVERT_SIGN   the normal is negated (CNMAP_INVERT_SIGN)
+ *   ITW_HEIGHT_OCCLUSION     alpha becomes the occlusion term (CNMAP_COMPUTE_OCCLUSION); without it alpha is 1
+ *   ITW_HEIGHT_AMPLITUDE(h)  the amplitude, the bits of an IEEE half, finite and above 0 (0x0001 .. 0x7BFF; 1.0 is 0x3C00), widened to float
+ * Bits 0x8, 0x10, 0x40, 0x80 and bit 31 are unknown.  Red channel, wrap, amplitude 1: 0x3C000120.
+ * Per texel, IEEE fp32, every operation rounded on its own.  The height h of a texel is the chosen component as its kind loads it: an
+ * RGBA8 code c is (float)c * (1.0f / 255.0f), an int8 code max((float)c * (1.0f / 127.0f), -1.0f), a half is widened, a float is taken as
+ * it is.  With v0, v1, v2 the heights of rows y - 1, y, y + 1 and [0], [1], [2] the columns x - 1, x, x + 1 (a 1 x 1 image is its own eight
+ * neighbours):
+ *   dzx = ((((v0[0] - v0[2]) + (v1[0] - v1[2])) + (v2[0] - v2[2])) * amplitude) / 6.0f
+ *   dzy = ((((v0[0] - v2[0]) + (v0[1] - v2[1])) + (v0[2] - v2[2])) * amplitude) / 6.0f
+ *   c = cross((-1, 0, dzx), (0, -1, dzy)) as six products and three differences; m = sqrtf((c.x*c.x + c.y*c.y) + c.z*c.z); n = c / m, true
+ *   divides; an infinite or NaN m gives NaN in all three.  Occlusion: delta sums the positive (neighbour - centre) differences, row by row;
+ *   delta *= 0.125f * amplitude; delta > 0: r = sqrtf(1.0f + delta*delta), alpha = (r - delta) / r.
+ * A biased RGBA8 target stores (+-0.5f * n) + 0.5f, a multiply then an add, each component as (uint8_t)(min(max(v, 0), 1) * 255.0f + 0.5f)
+ * with NaN -> 0: a flat map is (128, 128, 255, 255).  RGBA16F and RGBA8_SNORM targets store n or -n: halves clamped to +-65504 and rounded to
+ * nearest even with NaN -> 0x7E00, int8 codes by the signed sources' rule below.  One divergence from the reference: under MIRROR_V its row
+ * above row 0 is a partial copy for sources narrower than RGBA32F (a memcpy of the source's row pitch over a row of float vectors); here
+ * row -1 is row 0 for every kind.
+ * Calls that take the bit: itwPrepareNormalMapChain (pixel_size 4: RGBA8 heights to a biased RGBA8 map; 8: RGBA16F to RGBA16F; in place
+ * for the caller, the sources are first copied into the thread's buffer), itwQuantizeNormalMapChain (int8, half or float heights to
+ * RGBA8_SNORM; a target that overlaps any source's bytes is refused), itwCompressImageMipped / itwCompressImageMippedEx (RGBA8 formats other
+ * than 81 / 84: the stage writes level 0 of the device-side chain from the bases, then the call's own order follows) and
+ * itwCompressSignedNormalMapMipped (the stage replaces the widening of level 0, heights differenced at the source's own precision).
+ * itwCompressNormalMapChain, itwCompressSignedNormalMapChain, itwCompressNormalMapBC5 and itwCompressNormalMapBC5S refuse it: they see one
+ * texel or one block at a time. */
+enum { ITW_NORMAL_FLIP_X = 1, ITW_NORMAL_FLIP_Y = 2, ITW_NORMAL_NORMALIZE = 4, ITW_NORMAL_FROM_HEIGHT = 0x20,
+       ITW_HEIGHT_MIRROR_U = 0x1000, ITW_HEIGHT_MIRROR_V = 0x2000, ITW_HEIGHT_INVERT_SIGN = 0x4000, ITW_HEIGHT_OCCLUSION = 0x8000 };
+#define ITW_HEIGHT_CHANNEL(c)   ((uint32_t)(c) << 8)
+#define ITW_HEIGHT_AMPLITUDE(h) ((uint32_t)(h) << 16)
 int itwPrepareNormalMapChain(const rgba_surface* images, int count, int pixel_size, uint32_t ops);
 
 /* itwCompressImageChainEx with the stages above applied to every texel as the chain's gather copies it: the same formats (the texel size

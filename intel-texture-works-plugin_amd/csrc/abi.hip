@@ -1470,7 +1470,7 @@ void itwCompressNormalMapBC5(const rgba_surface* src, uint8_t* dst, uint32_t ops
     if (ops == 0) { CompressBlocksBC5(src, dst); return; }
     itw::clear_failure();
     itw::guarded([&] {
-        if (ops & ~7u) itw::fail_msg("itwCompressNormalMapBC5: unknown ops bits 0x%x", ops);
+        itw::check_normal_ops("itwCompressNormalMapBC5", ops, "the fused load reads one block, and a texel's normal needs its neighbours");
         Job j; j.kind = itw::BCN_BC5; j.normal_ops = ops;
         compress(j, src, dst, false);
     });
@@ -1492,7 +1492,7 @@ void itwCompressNormalMapBC5S(const rgba_surface* src, int texel_bytes, uint8_t*
     itw::clear_failure();
     itw::guarded([&] {
         if (texel_bytes != 4 && texel_bytes != 8 && texel_bytes != 16) itw::fail_msg("itwCompressNormalMapBC5S: texel_bytes %d (4, 8 or 16)", texel_bytes);
-        if (ops & ~7u) itw::fail_msg("itwCompressNormalMapBC5S: unknown ops bits 0x%x", ops);
+        itw::check_normal_ops("itwCompressNormalMapBC5S", ops, "the fused load reads one block, and a texel's normal needs its neighbours");
         if (!src) itw::fail_msg("null surface");
         const int w = src->width, h = src->height;
         if (w <= 0 || h <= 0) return;                     // nothing to encode
@@ -1554,7 +1554,7 @@ bool itwCompressNormalMapChain(const rgba_surface* images, int count, uint8_t* t
     bool done = false;
     itw::clear_failure();
     const bool ok = itw::guarded([&] {
-        if (ops & ~7u) itw::fail_msg("itwCompressNormalMapChain: unknown ops bits 0x%x", ops);
+        itw::check_normal_ops("itwCompressNormalMapChain", ops, "the gather works a texel at a time and has no neighbours");
         if (itw::format_kind(dxgi_format) == itw::BCN_BC1A) itw::fail_msg("itwCompressNormalMapChain: format 0x%X (BC1 with 1-bit alpha) holds colour, not normals", dxgi_format);
         const Job j = chain_job(images, count, target, dxgi_format, settings);
         done = compress_chain(j, images, count, target, progress, user, ops);
@@ -1572,7 +1572,7 @@ bool itwCompressSignedNormalMapChain(const rgba_surface* images, int count, int 
         if (dxgi_format != 81 && dxgi_format != 84)
             itw::fail_msg("itwCompressSignedNormalMapChain: DXGI format %d (BC4_SNORM = 81 or BC5_SNORM = 84)", dxgi_format);
         if (texel_bytes != 4 && texel_bytes != 8 && texel_bytes != 16) itw::fail_msg("itwCompressSignedNormalMapChain: texel_bytes %d (4, 8 or 16)", texel_bytes);
-        if (ops & ~7u) itw::fail_msg("itwCompressSignedNormalMapChain: unknown ops bits 0x%x", ops);
+        itw::check_normal_ops("itwCompressSignedNormalMapChain", ops, "the gather works a texel at a time and has no neighbours");
         const Job j = chain_job(images, count, target, dxgi_format, nullptr);
         itw::check_images("itwCompressSignedNormalMapChain", "image", images, count, texel_bytes, 0);
         done = compress_chain(j, images, count, target, progress, user, ops, texel_bytes);

@@ -109,4 +109,28 @@ struct ChainImage { const uint8_t* ptr; int64_t stride; int32_t width, height; i
 void launch_chain_gather(const ChainImage* images, int nimg, int64_t nblocks, int packed_bx, int packed_by, int texel_bytes, bool fill45,
                          uint8_t* dst, int64_t dst_pitch, hipStream_t st, uint8_t* extents = nullptr, uint32_t normal_ops = 0, int signed_source = 0);
 
+// Height maps to normal maps (height_normal.hip; the `ops` word with ITW_NORMAL_FROM_HEIGHT, itw_dispatch.h).
+// One image of a call: heights at `src`, the normal map at `dst` (device memory, disjoint), rows `*_stride` bytes apart, and the index of
+// its first work unit in the call's list: height_units() each, tiles of 64 x 16 texels.  height_units_fit: one launch covers a list of
+// that many.
+int64_t height_units(int width, int height);
+bool height_units_fit(int64_t units);
+struct HeightLevel { const uint8_t* src; uint8_t* dst; int64_t src_stride, dst_stride; int32_t width, height; int64_t first_unit; };
+// One launch over `count` images: `d_levels` their device table (unused for one image, which travels as `first`), `units` the list's
+// length; the kinds are hn::Src / hn::Dst of height_normal_core.hpp.  Bits 0..2 of `ops` apply after the stage, in registers.
+void launch_height_normal(int src_kind, int dst_kind, const HeightLevel* d_levels, const HeightLevel& first, int count, int64_t units, uint32_t ops, hipStream_t st);
+int height_signed_source_kind(int texel_bytes);                  // hn::Src of a signed normal source of 4, 8 or 16 bytes per texel
+// An `ops` word as `who`'s failure when it is not one: unknown bits, a channel above 5, amplitude bits that are no finite half above 0, or --
+// `no_height` given -- ITW_NORMAL_FROM_HEIGHT on a call that cannot take it, with `no_height` as the reason.  normal_ops_fault: the same
+// verdict without a message.
+void check_normal_ops(const char* who, uint32_t ops, const char* no_height = nullptr);
+bool normal_ops_fault(uint32_t ops);
+// the stage from one base (device memory) into level 0 of a device-side chain: one launch
+void height_level0(int src_kind, int dst_kind, const uint8_t* src, int64_t src_stride, const rgba_surface& level0, uint32_t ops, hipStream_t st);
+// no target may overlap a source's bytes (itwQuantizeNormalMapChain with ITW_NORMAL_FROM_HEIGHT): a failure otherwise
+void height_check_disjoint(const char* who, const rgba_surface* sources, int texel_bytes, const rgba_surface* targets, int count);
+// the device work of itwPrepareNormalMapChain / itwQuantizeNormalMapChain with ITW_NORMAL_FROM_HEIGHT: images that passed the checks
+void height_prepare_chain(const rgba_surface* images, int count, int pixel_size, uint32_t ops, bool dev);
+void height_quantize_chain(const rgba_surface* sources, int texel_bytes, const rgba_surface* targets, int count, uint32_t ops, bool dev);
+
 } // namespace itw

@@ -37,6 +37,8 @@
 #include "normal_prep.hpp"
 #include "bcn_format.hpp"
 #include "host_rt.hpp"
+#include "height_normal_core.hpp"
+#include "kernels.hpp"
 
 namespace itw {
 
@@ -432,7 +434,11 @@ bool compress_mipped(const rgba_surface* bases, int items, int levels, uint32_t 
             if (dxgi_format == 95 || dxgi_format == 96) itw::fail_msg("itwCompressImageMippedAlpha: DXGI format %d, whose texels are RGBA16F: the alpha rules are for RGBA8 colour", dxgi_format);
             if (dxgi_format == 81 || dxgi_format == 84) itw::fail_msg("itwCompressImageMippedAlpha: DXGI format %d, whose texels are signed codes, not colour", dxgi_format);
         }
-        if (normal_ops & ~7u) itw::fail_msg("itwCompressImageMipped: unknown ops bits 0x%x", normal_ops);
+        const bool from_height = (normal_ops & ITW_NORMAL_FROM_HEIGHT) != 0;
+        itw::check_normal_ops("itwCompressImageMipped", normal_ops,
+                              !from_height ? nullptr
+                              : (dxgi_format == 95 || dxgi_format == 96) ? "the format's texels are RGBA16F colour"
+                              : (dxgi_format == 81 || dxgi_format == 84) ? "a signed format takes its heights through itwCompressSignedNormalMapMipped" : nullptr);
         if (normal_ops && itw::format_kind(dxgi_format) == itw::BCN_BC1A)
             itw::fail_msg("itwCompressImageMipped: normal ops 0x%x with format 0x%X (BC1 with 1-bit alpha), which holds colour, not normals", normal_ops, dxgi_format);
         check_filter_flags("itwCompressImageMipped", "mip flag", mip_flags, alpha);
@@ -451,9 +457,17 @@ bool compress_mipped(const rgba_surface* bases, int items, int levels, uint32_t 
 
         hipStream_t st = (hipStream_t)itwGetStream();
         std::vector<rgba_surface> chain((size_t)items * levels), level0((size_t)items);
-        itwMipChainLayout(w, h, items, levels, px, static_cast<uint8_t*>(itw::chain_scratch((size_t)b.chain_bytes, st)), chain.data());
+        // with ITW_NORMAL_FROM_HEIGHT the thread's chain buffer is [chain] [host bases as they are]: the height stage writes level 0 from the bases
+        const itw::StagingPlan heights(bases, items, px, dev || !from_height, (size_t)b.chain_bytes);
+        uint8_t* buf = static_cast<uint8_t*>(itw::chain_scratch(from_height ? heights.bytes : (size_t)b.chain_bytes, st));
+        itwMipChainLayout(w, h, items, levels, px, buf, chain.data());
         for (int i = 0; i < items; i++) {
             level0[(size_t)i] = chain[(size_t)i * levels];
+            if (from_height) {
+                itw::upload_image(heights, buf, i, st);
+                itw::height_level0(itw::hn::SRC_UNORM8, itw::hn::DST_RGBA8, heights.ptr(i, buf), heights.stride(i), level0[(size_t)i], normal_ops & ~7u, st);
+                continue;
+            }
             ITW_CHECK(hipMemcpy2DAsync(level0[(size_t)i].ptr, (size_t)level0[(size_t)i].stride, bases[i].ptr, (size_t)bases[i].stride, (size_t)w * px, (size_t)h,
                                        dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
         }
@@ -499,7 +513,7 @@ extern "C" bool itwCompressSignedNormalMapMipped(const rgba_surface* bases, int 
         if (dxgi_format != 81 && dxgi_format != 84)
             itw::fail_msg("itwCompressSignedNormalMapMipped: DXGI format %d (BC4_SNORM = 81 or BC5_SNORM = 84)", dxgi_format);
         if (texel_bytes != 4 && texel_bytes != 8 && texel_bytes != 16) itw::fail_msg("itwCompressSignedNormalMapMipped: texel_bytes %d (4, 8 or 16)", texel_bytes);
-        if (ops & ~7u) itw::fail_msg("itwCompressSignedNormalMapMipped: unknown ops bits 0x%x", ops);
+        itw::check_normal_ops("itwCompressSignedNormalMapMipped", ops);
         itw::chain_check_with(bases, items, target, dxgi_format, nullptr);        // counts, null pointers, sizes, format
         const MippedBases b = check_mipped_bases("itwCompressSignedNormalMapMipped", bases, items, levels, texel_bytes, 8);
         const int w = bases[0].width, h = bases[0].height;
@@ -519,6 +533,10 @@ extern "C" bool itwCompressSignedNormalMapMipped(const rgba_surface* bases, int 
             const uint8_t* src = plan.ptr(i, buf);
             const int64_t stride = plan.stride(i);
             const rgba_surface& l0 = chain[(size_t)i * levels];
+            if (ops & ITW_NORMAL_FROM_HEIGHT) {                                   // the bases are height maps: differenced at their own precision
+                itw::height_level0(itw::height_signed_source_kind(texel_bytes), itw::hn::DST_HALF_SIGNED, src, stride, l0, ops & ~4u, st);
+                continue;
+            }
             if (texel_bytes == 4)      hipLaunchKernelGGL((itw::mip_widen_signed_kernel<4>), grid, blk, 0, st, src, stride, l0.ptr, (int64_t)l0.stride, w, h, ops & 3u);
             else if (texel_bytes == 8) hipLaunchKernelGGL((itw::mip_widen_signed_kernel<8>), grid, blk, 0, st, src, stride, l0.ptr, (int64_t)l0.stride, w, h, ops & 3u);
             else                       hipLaunchKernelGGL((itw::mip_widen_signed_kernel<16>), grid, blk, 0, st, src, stride, l0.ptr, (int64_t)l0.stride, w, h, ops & 3u);

@@ -14,6 +14,7 @@
 #include "../../include/itw_amd.h"
 #include "normal_prep.hpp"
 #include "host_rt.hpp"
+#include "kernels.hpp"
 
 namespace itw {
 
@@ -213,7 +214,7 @@ extern "C" int itwQuantizeNormalMapChain(const rgba_surface* sources, int texel_
     const bool ok = itw::guarded([&] {
         if (count < 0) itw::fail_msg("itwQuantizeNormalMapChain: count %d", count);
         if (texel_bytes != 4 && texel_bytes != 8 && texel_bytes != 16) itw::fail_msg("itwQuantizeNormalMapChain: texel_bytes %d (4, 8 or 16)", texel_bytes);
-        if (ops & ~itw::NORMAL_OPS_ALL) itw::fail_msg("itwQuantizeNormalMapChain: unknown ops bits 0x%x", ops);
+        itw::check_normal_ops("itwQuantizeNormalMapChain", ops);
         if (count == 0) return;
         if (!sources || !targets) itw::fail_msg("itwQuantizeNormalMapChain: null image list");
         itw::check_images("itwQuantizeNormalMapChain", "source", sources, count, texel_bytes, texel_bytes);
@@ -224,19 +225,21 @@ extern "C" int itwQuantizeNormalMapChain(const rgba_surface* sources, int texel_
                 itw::fail_msg("itwQuantizeNormalMapChain: image %d: the target is %d x %d, its source %d x %d", i, t.width, t.height, s.width, s.height);
         }
         itw::check_images("itwQuantizeNormalMapChain", "target", targets, count, 4, 4);
+        if (ops & ITW_NORMAL_FROM_HEIGHT) itw::height_check_disjoint("itwQuantizeNormalMapChain", sources, texel_bytes, targets, count);
     });
     if (!ok) return -1;
     if (count == 0) return 0;
     const bool done = itw::guarded([&] {
         dev = itw::all_one_pointer_kind("itwQuantizeNormalMapChain", "image", sources, count, targets);
-        quantize_chain(sources, texel_bytes, targets, count, ops, dev);
+        if (ops & ITW_NORMAL_FROM_HEIGHT) itw::height_quantize_chain(sources, texel_bytes, targets, count, ops, dev);
+        else                              quantize_chain(sources, texel_bytes, targets, count, ops, dev);
     });
     return done ? 0 : -1;
 }
 
 extern "C" int itwPrepareNormalMapChain(const rgba_surface* images, int count, int pixel_size, uint32_t ops)
 {
-    if (count < 0 || (pixel_size != 4 && pixel_size != 8) || (ops & ~itw::NORMAL_OPS_ALL)) return -1;
+    if (count < 0 || (pixel_size != 4 && pixel_size != 8) || itw::normal_ops_fault(ops)) return -1;
     if (count == 0) return 0;
     if (!images) return -1;
     if (itw::image_list_fault(images, count, pixel_size, pixel_size)) return -1;         // silently, like the rest: never through the error mode
@@ -244,7 +247,10 @@ extern "C" int itwPrepareNormalMapChain(const rgba_surface* images, int count, i
     const bool dev = itw::is_device_pointer(images[0].ptr);
     for (int i = 1; i < count; i++)
         if (itw::is_device_pointer(images[i].ptr) != dev) return -1;     // all host or all device, as the chain encoder asks
-    const bool ok = itw::guarded([&] { prepare_chain(images, count, pixel_size, ops, dev); });
+    const bool ok = itw::guarded([&] {
+        if (ops & ITW_NORMAL_FROM_HEIGHT) itw::height_prepare_chain(images, count, pixel_size, ops, dev);     // every image a height map on entry
+        else                              prepare_chain(images, count, pixel_size, ops, dev);
+    });
     return ok ? 0 : -1;
 }
 

@@ -844,6 +844,49 @@ def normal_ops(flip_x=False, flip_y=False, normalize=False):
     return (NORMAL_FLIP_X if flip_x else 0) | (NORMAL_FLIP_Y if flip_y else 0) | (NORMAL_NORMALIZE if normalize else 0)
 
 
+# ITW_NORMAL_FROM_HEIGHT and ITW_HEIGHT_* (include/itw_dispatch.h, "height maps"): the further fields of the `ops` word
+NORMAL_FROM_HEIGHT = 0x20
+HEIGHT_CHANNEL = {"r": 1, "g": 2, "b": 3, "a": 4, "lum": 5}      # ITW_HEIGHT_CHANNEL(c) = c << 8; 0 is red too
+HEIGHT_MIRROR_U, HEIGHT_MIRROR_V, HEIGHT_INVERT_SIGN, HEIGHT_OCCLUSION = 0x1000, 0x2000, 0x4000, 0x8000
+
+
+def height_ops(channel="r", mirror="", invert=False, occlusion=False, amplitude=1.0, flip_x=False, flip_y=False, normalize=False):
+    """The `ops` word that makes a normal-map call take height maps (DirectXTex's ComputeNormalMap first, then the flips and the normalise
+    with their usual meaning).  channel: "r", "g", "b", "a" or "lum"; mirror: "", "u", "v" or "uv" (an axis not named wraps); amplitude: the
+    bump strength, rounded to an IEEE half -- ValueError unless that half is finite and above 0.  height_amplitude() gives it back."""
+    import numpy as np
+    if channel not in HEIGHT_CHANNEL:
+        raise ValueError(f"height channel {channel!r}: one of {sorted(HEIGHT_CHANNEL)}")
+    if any(c not in "uv" for c in mirror):
+        raise ValueError(f"mirror {mirror!r}: '', 'u', 'v' or 'uv'")
+    with np.errstate(over="ignore"):
+        bits = int(np.array(amplitude, dtype=np.float64).astype(np.float16).view(np.uint16))
+    if not 0 < bits < 0x7C00:
+        raise ValueError(f"amplitude {amplitude!r}: as an IEEE half it must be finite and above 0")
+    return (normal_ops(flip_x, flip_y, normalize) | NORMAL_FROM_HEIGHT | (HEIGHT_CHANNEL[channel] << 8) | (HEIGHT_MIRROR_U if "u" in mirror else 0)
+            | (HEIGHT_MIRROR_V if "v" in mirror else 0) | (HEIGHT_INVERT_SIGN if invert else 0) | (HEIGHT_OCCLUSION if occlusion else 0) | (bits << 16))
+
+
+def height_amplitude(ops):
+    """The amplitude an `ops` word of height_ops() carries, as a float."""
+    import numpy as np
+    return float(np.array((int(ops) >> 16) & 0x7FFF, dtype=np.uint16).view(np.float16))
+
+
+def height_to_normal(images, ops, kind="biased", out=None):
+    """Height maps to normal maps; `ops` is a word of height_ops().  images: one (H, W, 4) host numpy array / CUDA torch tensor or a list of
+    them, all of one dtype.  kind "biased": itwPrepareNormalMapChain IN PLACE, uint8 (RGBA8 heights become a biased RGBA8 map) or 2-byte
+    elements (RGBA16F half bits become an RGBA16F map); returns the images.  kind "snorm": itwQuantizeNormalMapChain, int8, float16 / half
+    bits or float32 heights into RGBA8_SNORM targets (`out`, default new ones, never the sources); returns the targets."""
+    if not int(ops) & NORMAL_FROM_HEIGHT:
+        raise ValueError("height_to_normal: ops without NORMAL_FROM_HEIGHT (see height_ops())")
+    if kind == "biased":
+        return prepare_normal_map(images, ops=ops)
+    if kind == "snorm":
+        return quantize_normal_map(images, ops=ops, out=out)
+    raise ValueError(f"kind {kind!r}: 'biased' or 'snorm'")
+
+
 def prepare_normal_map(images, flip_x=False, flip_y=False, normalize=False, ops=None):
     """itwPrepareNormalMapChain: the plugin's normal-map flip / normalise IN PLACE over one image or a list of them (a mip chain), host numpy
     arrays or CUDA torch tensors (H, W, 4), all of one kind: uint8 (RGBA8) or 2-byte elements (RGBA16F half bits).  Device tensors: one
