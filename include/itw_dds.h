@@ -5,6 +5,12 @@
  * 'DXT1' / 'DXT5' FourCC header (128 bytes incl. magic), BC4 / BC5 'BC4U' / 'BC5U' (UNORM; 'ATI1' / 'ATI2' are read as these) and
  * 'BC4S' / 'BC5S' (SNORM; DDS.h:83-93, DirectXTexDDS.cpp:64-70, 480-483); the _SRGB variants, BC7 and BC6H carry the 'DX10' extension
  * (148 bytes).  Mip chains: top level first; cube maps: 6 faces, each with its full chain.
+ * BC2: a descriptor names it by the library's two codes, ITW_FORMAT_BC2_UNORM = 0x83F2 / ITW_FORMAT_BC2_UNORM_SRGB = 0x8C4E (itw_dispatch.h), as
+ * every entry point does; 74 / 75 as descriptor codes are refused like any code the library does not read.  The FILE holds DXGI's own: 0x83F2
+ * without an array is written with the legacy 'DXT3' FourCC (DirectXTexDDS.cpp:478), otherwise a 'DX10' header with 74; 0x8C4E always 'DX10'
+ * with 75.  Read: 'DXT3' and 'DX10' 74 give 0x83F2, 'DX10' 75 gives 0x8C4E; the premultiplied spellings 'DXT2' and 'DXT4' read as BC2 and BC3
+ * (77), which is DirectXTex's mapping (DirectXTexDDS.cpp:58-62) -- that the file's alpha is premultiplied is NOT reported: the descriptor has
+ * no field for it.  16 bytes per block.
  *
  * Below the DDS functions: the KTX 1.1 container for ETC1 streams (itwKtx*), which DDS cannot carry.
  */
@@ -22,7 +28,7 @@ extern "C" {
 typedef struct ItwDdsDesc {
     uint32_t width, height;     /* top mip, texels */
     uint32_t mip_levels;        /* >= 1 */
-    uint32_t dxgi_format;       /* DXGI_FORMAT_BCn_* value (71,72,77,78,80,81,83,84,95,96,98,99) */
+    uint32_t dxgi_format;       /* DXGI_FORMAT_BCn_* value (71,72,77,78,80,81,83,84,95,96,98,99), or one of the BC1A / BC2 codes of itw_dispatch.h */
     uint32_t is_cubemap;        /* 0 / 1: six faces */
     uint32_t array_size;        /* number of textures (cubes when is_cubemap); >= 1 */
 } ItwDdsDesc;

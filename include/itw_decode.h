@@ -31,6 +31,11 @@ extern "C" {
  * block whose base + delta leaves 0..31 (invalid in ETC1; decoded with the sum modulo 32 and counted in reserved_blocks).
  * ITW_FORMAT_BC1A_UNORM / _SRGB (0x83F1 / 0x8C4D, BC1 with 1-bit alpha): synonyms of 71 / 72 in every entry point of this header -- the stream
  * is a BC1 stream, decoded, measured (itw_error_stats.dxgi_format says 71 / 72) and previewed by the same code.
+ * ITW_FORMAT_BC2_UNORM / _SRGB (0x83F2 / 0x8C4E, BC2 / DXT3): taken by every entry point of this header under these two codes (DXGI's 74 / 75
+ * are refused like any unknown code; itw_dispatch.h says why): 16-byte blocks, RGBA8 texels, any size >= 1 in itwDecodeBlocks too (a
+ * DirectXTex format, like the BC4 / BC5 group); the colour is always the four-colour palette whatever the order of the endpoints -- BC2 has
+ * no 3-colour mode --, alpha is the texel's 4-bit code times 17, which is D3DXDecodeBC2's n / 15 exactly; no modes (0);
+ * itw_error_stats.dxgi_format repeats the code given; own channels RGBA.
  * `blocks`, `out`, `modes` are host or device pointers, in any mix.  With all of them on the device the call is one kernel launch,
  * asynchronous on the calling thread's stream (itwSetStream): it allocates nothing, touches no buffer of the thread and can be captured
  * into a graph.  With any host pointer it stages through the calling thread's grow-only device buffer (the one itwDecodeChain uses;

@@ -48,18 +48,32 @@ enum {
      * They are DirectXTex formats (itw_bc45.h): an RGBA8 source of any size >= 1, partial blocks kept and filled by DirectXTexCompress.cpp's
      * {0, 0, 0, 1} rule.  A texel code v is the float (float)v * (1.0f / 255.0f).  There is no block-level entry point and no CompressImage*
      * trampoline: itwCompressImageSliced / itwCompressImageChain run a caller's function as the literal loop, CompressImageMT / ST have no
-     * function to call; the refined calls, the multi-GPU calls and the normal-map chain calls refuse the codes.  BC2 (74 / 75) is not built. */
-    ITW_FORMAT_BC1A_UNORM = 0x83F1, ITW_FORMAT_BC1A_UNORM_SRGB = 0x8C4D
+     * function to call; the refined calls, the multi-GPU calls and the normal-map chain calls refuse the codes.  BC2 is the two codes below. */
+    ITW_FORMAT_BC1A_UNORM = 0x83F1, ITW_FORMAT_BC1A_UNORM_SRGB = 0x8C4D,
+    /* BC2 (DXT2 / DXT3: 4 bits of explicit alpha per texel beside a four-colour BC1 block, 16 bytes per block): DirectXTex's D3DXEncodeBC2
+     * (BC.cpp) as DirectX::Compress calls it.  It goes by its GL enums, GL_COMPRESSED_RGBA_S3TC_DXT3_EXT and
+     * GL_COMPRESSED_SRGB_ALPHA_S3TC_DXT3_EXT (the second only labels the stream, like 72): DXGI 74 / 75 stay refused codes at every entry
+     * point that takes a format code, and appear only inside DDS descriptors and headers (itw_dds.h), where they are the file's own truth.
+     * Encoded, with `settings` = const itw_bc1a_settings* or NULL (below), by itwCompressImageSlicedEx (one slice is the single-image call),
+     * itwCompressImageChainEx and the itwCompressImageMipped* calls (ITW_MIP_SRGB, the filter and wrap bits, weight_colour and coverage_ref
+     * apply: the texels are RGBA8 colour); itwSliceWindow[For], itwChainBytes and GetBytesPerBlock (16) know the codes.  Decoded, measured
+     * and previewed by the entry points of itw_decode.h under the same two codes.  A DirectXTex format like BC1A: any size >= 1, partial
+     * blocks kept and filled by the {0, 0, 0, 1} rule, the same texel conversion, no block-level entry point and no CompressImage* trampoline
+     * (itwCompressImageSliced / itwCompressImageChain run a caller's function as the literal loop); the refined calls, the multi-GPU calls,
+     * the normal-map chain calls, any normal_ops and KTX refuse the codes. */
+    ITW_FORMAT_BC2_UNORM = 0x83F2, ITW_FORMAT_BC2_UNORM_SRGB = 0x8C4E
 };
 
-/* Settings of the two BC1A codes.  flags: DirectXTex's BC_FLAGS_* values (BC.h) -- error diffusion of the colours, of alpha (the key test
+/* Settings of the two BC1A codes and of the two BC2 codes.  flags: DirectXTex's BC_FLAGS_* values (BC.h) -- error diffusion of the colours, of alpha (the key test
  * then sees the diffused, rounded alpha, not the source's), uniform instead of perceptual channel weights.
  * NULL settings mean alpha_ref = 0.5f, flags = 0: TEX_THRESHOLD_DEFAULT, what the plugin passes to DirectX::Compress.  The struct is copied
  * while the call is set up.  A struct_size other than 16, reserved != 0, unknown flag bits or a non-finite alpha_ref fail the call through
  * the error mode before any device work.  Any finite alpha_ref behaves as the reference does: a texel is transparent when its alpha
  * (float) < alpha_ref, so <= 0 makes no texel transparent and > 1 makes every block 00 00 FF FF FF FF FF FF.
  * A caller who kept alpha-test coverage with coverage_ref = r (itwCompressImageMippedAlpha) passes alpha_ref = (float)r * (1.0f / 255.0f):
- * that is the texel conversion's own expression, so "transparent" is exactly a < r on the integer codes. */
+ * that is the texel conversion's own expression, so "transparent" is exactly a < r on the integer codes.
+ * BC2: the same struct and the same checks.  alpha_ref is checked (finite) but not read -- BC2 has no colour key: D3DXEncodeBC2 calls
+ * EncodeBC1(bColorKey = false), always four colours; ITW_BC_DITHER_A diffuses the error of the 4-bit alpha; NULL means flags 0. */
 enum { ITW_BC_DITHER_RGB = 0x10000, ITW_BC_DITHER_A = 0x20000, ITW_BC_UNIFORM = 0x40000 };
 typedef struct itw_bc1a_settings { uint32_t struct_size /* 16 */; float alpha_ref; uint32_t flags, reserved /* 0 */; } itw_bc1a_settings;
 

@@ -13,11 +13,13 @@
 
 namespace itw {
 
-enum BcnKind : int { BCN_NONE = 0, BCN_BC1 = 1, BCN_BC3 = 3, BCN_BC4 = 4, BCN_BC5 = 5, BCN_BC6H = 6, BCN_BC7 = 7, BCN_BC4S = 14, BCN_BC5S = 15, BCN_ETC1 = 20, BCN_BC1A = 21 };
+enum BcnKind : int { BCN_NONE = 0, BCN_BC1 = 1, BCN_BC2 = 2, BCN_BC3 = 3, BCN_BC4 = 4, BCN_BC5 = 5, BCN_BC6H = 6, BCN_BC7 = 7, BCN_BC4S = 14, BCN_BC5S = 15, BCN_ETC1 = 20, BCN_BC1A = 21 };
 
 // DXGI format code (or ITW_FORMAT_ETC1_RGB8, ETC1's GL enum: it has no DXGI code; or the two BC1A codes, GL enums likewise) -> kind; BCN_NONE
 // for what the library neither encodes nor decodes.  BCN_BC1A is an ENCODE kind (DirectXTex's colour-key BC1 encoder: partial blocks kept, an
 // itw_bc1a_settings); its stream is a BC1 stream, so the decode side never sees the kind: its entry points read a code through stream_format.
+// BCN_BC2 (DirectXTex's D3DXEncodeBC2: partial blocks kept, the same itw_bc1a_settings) is both an encode and a decode kind, and goes by its two
+// GL enums only: DXGI 74 / 75 stay BCN_NONE at every entry point that takes a format code (they appear inside DDS descriptors and headers alone).
 // BC6H_SF16 (96) reads as unsigned: the encoder is the reference's one BC6H encoder for both codes, the signed decode is not built, and the
 // entry points that must not pretend otherwise (itwDecodeChain, itwDecodeImage) refuse 96 themselves.
 constexpr BcnKind format_kind(int dxgi)
@@ -33,6 +35,7 @@ constexpr BcnKind format_kind(int dxgi)
     case 98: case 99: return BCN_BC7;
     case ITW_FORMAT_ETC1_RGB8: return BCN_ETC1;
     case ITW_FORMAT_BC1A_UNORM: case ITW_FORMAT_BC1A_UNORM_SRGB: return BCN_BC1A;
+    case ITW_FORMAT_BC2_UNORM: case ITW_FORMAT_BC2_UNORM_SRGB: return BCN_BC2;
     default: return BCN_NONE;
     }
 }
@@ -41,8 +44,8 @@ constexpr int stream_format(int code) { return code == ITW_FORMAT_BC1A_UNORM ? 7
 constexpr int block_bytes(int kind) { return (kind == BCN_BC1 || kind == BCN_BC4 || kind == BCN_BC4S || kind == BCN_ETC1 || kind == BCN_BC1A) ? 8 : 16; }
 constexpr int texel_bytes(int kind) { return kind == BCN_BC6H ? 8 : 4; }                     // RGBA8 (int8 for the SNORM pair), RGBA16F
 // the DirectXTex formats: their streams keep the partial blocks of a surface that is no multiple of 4 (itw_bc45.h)
-constexpr bool keeps_partial_blocks(int kind) { return kind == BCN_BC4 || kind == BCN_BC5 || kind == BCN_BC4S || kind == BCN_BC5S || kind == BCN_BC1A; }
-// the alpha code of a format whose decoder fills alpha in; -1 where alpha is decoded (BC1, BC1A, BC3, BC7)
+constexpr bool keeps_partial_blocks(int kind) { return kind == BCN_BC4 || kind == BCN_BC5 || kind == BCN_BC4S || kind == BCN_BC5S || kind == BCN_BC1A || kind == BCN_BC2; }
+// the alpha code of a format whose decoder fills alpha in; -1 where alpha is decoded (BC1, BC1A, BC2, BC3, BC7)
 constexpr int filled_alpha(int kind)
 {
     return (kind == BCN_BC4 || kind == BCN_BC5 || kind == BCN_ETC1) ? 255 : (kind == BCN_BC4S || kind == BCN_BC5S) ? 127 : kind == BCN_BC6H ? 0x3C00 : -1;
@@ -84,6 +87,7 @@ inline void with_kind(int kind, F&& f)
 {
     switch (kind) {
     case BCN_BC1:  f(std::integral_constant<int, BCN_BC1>{}); break;
+    case BCN_BC2:  f(std::integral_constant<int, BCN_BC2>{}); break;
     case BCN_BC3:  f(std::integral_constant<int, BCN_BC3>{}); break;
     case BCN_BC4:  f(std::integral_constant<int, BCN_BC4>{}); break;
     case BCN_BC5:  f(std::integral_constant<int, BCN_BC5>{}); break;

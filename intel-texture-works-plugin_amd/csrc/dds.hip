@@ -19,13 +19,17 @@ constexpr uint32_t fourcc(char a, char b, char c, char d)
     return (uint32_t)(uint8_t)a | ((uint32_t)(uint8_t)b << 8) | ((uint32_t)(uint8_t)c << 16) | ((uint32_t)(uint8_t)d << 24);
 }
 
-// the two BC1A codes (itw_dispatch.h) are stored as what their streams are: BC1, 71 / 72
-uint32_t stored_format(uint32_t f) { return f == 0x83F1u ? 71u : f == 0x8C4Du ? 72u : f; }
+// the two BC1A codes (itw_dispatch.h) are stored as what their streams are: BC1, 71 / 72; the two BC2 codes as DXGI's BC2, 74 / 75
+uint32_t stored_format(uint32_t f) { return f == 0x83F1u ? 71u : f == 0x8C4Du ? 72u : f == 0x83F2u ? 74u : f == 0x8C4Eu ? 75u : f; }
+// what itwDdsReadHeader reports for a file's own code: BC2 goes by its two codes in a descriptor as everywhere else (74 / 75 as descriptor codes stay refused)
+uint32_t descriptor_format(uint32_t stored) { return stored == 74u ? 0x83F2u : stored == 75u ? 0x8C4Eu : stored; }
 
 int bytes_per_block(uint32_t f)
 {
+    if (f == 74u || f == 75u) return 0;                     // a descriptor says ITW_FORMAT_BC2_UNORM[_SRGB]
     switch (stored_format(f)) {
     case 71: case 72: case 80: case 81: return 8;           // BC1, BC4_UNORM, BC4_SNORM
+    case 74: case 75:                                       // BC2
     case 77: case 78: case 83: case 84: case 95: case 96: case 98: case 99: return 16;   // BC3, BC5_UNORM, BC5_SNORM, BC6H, BC7
     default: return 0;
     }
@@ -37,6 +41,7 @@ uint32_t legacy_fourcc(uint32_t f)
 {
     switch (stored_format(f)) {
     case 71: return fourcc('D', 'X', 'T', '1');
+    case 74: return fourcc('D', 'X', 'T', '3');
     case 77: return fourcc('D', 'X', 'T', '5');
     case 80: return fourcc('B', 'C', '4', 'U');
     case 81: return fourcc('B', 'C', '4', 'S');
@@ -133,7 +138,8 @@ size_t itwDdsReadHeader(const uint8_t* src, size_t size, ItwDdsDesc* out)
     size_t off = 128;
     const uint32_t cc = get32(h, 20);
     if (cc == fourcc('D', 'X', 'T', '1')) d.dxgi_format = 71;
-    else if (cc == fourcc('D', 'X', 'T', '5')) d.dxgi_format = 77;
+    else if (cc == fourcc('D', 'X', 'T', '3') || cc == fourcc('D', 'X', 'T', '2')) d.dxgi_format = 74;   // DirectXTexDDS.cpp:58-62: the premultiplied
+    else if (cc == fourcc('D', 'X', 'T', '5') || cc == fourcc('D', 'X', 'T', '4')) d.dxgi_format = 77;   // spellings DXT2 / DXT4 read as BC2 / BC3
     else if (cc == fourcc('B', 'C', '4', 'U') || cc == fourcc('A', 'T', 'I', '1')) d.dxgi_format = 80;   // DirectXTexDDS.cpp:64-70
     else if (cc == fourcc('B', 'C', '5', 'U') || cc == fourcc('A', 'T', 'I', '2')) d.dxgi_format = 83;
     else if (cc == fourcc('B', 'C', '4', 'S')) d.dxgi_format = 81;                                         // (the ATI spellings are UNORM only)
@@ -147,6 +153,8 @@ size_t itwDdsReadHeader(const uint8_t* src, size_t size, ItwDdsDesc* out)
         d.array_size = get32(e, 3) ? get32(e, 3) : 1;
         off = 148;
     } else return 0;
+    if (d.dxgi_format == 0x83F2u || d.dxgi_format == 0x8C4Eu) return 0;          // (no file holds the library's own codes)
+    d.dxgi_format = descriptor_format(d.dxgi_format);
     if (!bytes_per_block(d.dxgi_format) || !d.width || !d.height) return 0;
     *out = d;
     return off;

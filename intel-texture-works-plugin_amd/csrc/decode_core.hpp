@@ -339,6 +339,11 @@ __device__ __forceinline__ int decode_block(const uint4 w, uint32_t (&px)[16])
     } else if (FMT == BCN_BC3) {
         decode_color(w.z, w.w, false, px);
         decode_bc3_alpha(w.x, w.y, px);
+    } else if (FMT == BCN_BC2) {
+        decode_color(w.z, w.w, false, px);            // always the four-colour palette, whatever the order of the endpoints (D3DXDecodeBC2, BC.cpp:802)
+#pragma unroll
+        for (int k = 0; k < 16; k++)                  // texel k: nibble k & 7 of word k >> 3; a 4-bit code n is n * 17 (= n / 15 of 255, exactly)
+            px[k] = (px[k] & 0x00ffffffu) | ((((k < 8 ? w.x : w.y) >> (4 * (k & 7))) & 15u) * 17u << 24);
     } else {
         constexpr bool SNORM = FMT == BCN_BC4S || FMT == BCN_BC5S;
 #pragma unroll

@@ -6,8 +6,8 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 _LIB = os.path.normpath(os.path.join(_PKG, "..", "lib", "libispc_texcomp.so"))
 _TEST_LIB = os.path.normpath(os.path.join(_PKG, "..", "lib", "libispc_texcomp_test.so"))
 
-BYTES_PER_BLOCK = {"bc1": 8, "bc3": 16, "bc7": 16, "bc6h": 16, "bc4": 8, "bc5": 16, "bc4_snorm": 8, "bc5_snorm": 16, "etc1": 8, "bc1a": 8, "bc1a_srgb": 8}
-KEEPS_PARTIAL_BLOCKS = ("bc4", "bc5", "bc4_snorm", "bc5_snorm", "bc1a", "bc1a_srgb")     # DirectXTex formats: ceil(w/4) x ceil(h/4) blocks (include/itw_bc45.h)
+BYTES_PER_BLOCK = {"bc1": 8, "bc3": 16, "bc7": 16, "bc6h": 16, "bc4": 8, "bc5": 16, "bc4_snorm": 8, "bc5_snorm": 16, "etc1": 8, "bc1a": 8, "bc1a_srgb": 8, "bc2": 16, "bc2_srgb": 16}
+KEEPS_PARTIAL_BLOCKS = ("bc4", "bc5", "bc4_snorm", "bc5_snorm", "bc1a", "bc1a_srgb", "bc2", "bc2_srgb")     # DirectXTex formats: ceil(w/4) x ceil(h/4) blocks (include/itw_bc45.h)
 SIGNED_FORMATS = ("bc4_snorm", "bc5_snorm")     # RGBA8_SNORM sources: int8 arrays / tensors, never uint8 (include/itw_bc45.h)
 BC7_PROFILES = ("ultrafast", "veryfast", "fast", "basic", "slow",
                 "alpha_ultrafast", "alpha_veryfast", "alpha_fast", "alpha_basic", "alpha_slow")
@@ -86,7 +86,9 @@ BC_DITHER_RGB, BC_DITHER_A, BC_UNIFORM = 0x10000, 0x20000, 0x40000      # ITW_BC
 class Bc1aSettings(C.Structure):
     """struct itw_bc1a_settings (itw_dispatch.h), 16 bytes: the settings of "bc1a" / "bc1a_srgb", BC1 with 1-bit alpha by DirectXTex's encoder.
     A texel is transparent when its alpha (code * (1/255) in fp32) < alpha_ref; a caller who kept coverage with alpha_coverage=r passes
-    alpha_ref=Bc1aSettings.ref_of(r).  None where settings are taken means Bc1aSettings()."""
+    alpha_ref=Bc1aSettings.ref_of(r).  None where settings are taken means Bc1aSettings().
+    "bc2" / "bc2_srgb" take the same struct: BC2 has no colour key, so alpha_ref is checked (finite) but ignored; dither_a diffuses the error
+    of the 4-bit alpha, dither_rgb and uniform mean what they mean for "bc1a"."""
     _fields_ = [("struct_size", C.c_uint32), ("alpha_ref", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
     def __init__(self, alpha_ref=0.5, dither_rgb=False, dither_a=False, uniform=False):
@@ -105,7 +107,9 @@ assert C.sizeof(RgbaSurface) == 24 and C.sizeof(Bc7Settings) == 64 and C.sizeof(
 # EtcSettings); the refined calls, the multi-GPU calls and DDS refuse it -- its container is KTX (KtxDesc, ktx_file, load_ktx)
 # "bc1a" / "bc1a_srgb": ITW_FORMAT_BC1A_UNORM[_SRGB], GL enums likewise (DXGI has no code for BC1 with alpha): the slice pipeline, the chain and
 # the mipped calls encode them (with a Bc1aSettings or None); decode, measure, preview and DDS take them as synonyms of "bc1" / "bc1_srgb"
-DXGI_FORMAT = {"bc1a": 0x83F1, "bc1a_srgb": 0x8C4D, "etc1": 0x8D64, "bc1": 71, "bc1_srgb": 72, "bc3": 77, "bc3_srgb": 78, "bc4": 80, "bc4_snorm": 81, "bc5": 83, "bc5_snorm": 84, "bc6h": 95, "bc6h_sf16": 96, "bc7": 98, "bc7_srgb": 99}
+# "bc2" / "bc2_srgb": ITW_FORMAT_BC2_UNORM[_SRGB], GL enums too -- DXGI's 74 / 75 stay refused codes at the entry points and live in DDS files only;
+# encoded where "bc1a" is (same Bc1aSettings), decoded, measured and previewed under the same two codes, stored by dds_file as DXT3 / DX10 74 / 75
+DXGI_FORMAT = {"bc2": 0x83F2, "bc2_srgb": 0x8C4E, "bc1a": 0x83F1, "bc1a_srgb": 0x8C4D, "etc1": 0x8D64, "bc1": 71, "bc1_srgb": 72, "bc3": 77, "bc3_srgb": 78, "bc4": 80, "bc4_snorm": 81, "bc5": 83, "bc5_snorm": 84, "bc6h": 95, "bc6h_sf16": 96, "bc7": 98, "bc7_srgb": 99}
 
 
 class DdsDesc(C.Structure):
@@ -145,9 +149,9 @@ class MultiGpuStats(C.Structure):
 
 
 # the channels of a decoded texel that carry a format's own data (the others are fill values: itw_decode.h)
-OWN_CHANNELS = {"bc1": "rgb", "bc3": "rgba", "bc4": "r", "bc5": "rg", "bc4_snorm": "r", "bc5_snorm": "rg", "bc6h": "rgb", "bc7": "rgba", "etc1": "rgb", "bc1a": "rgba", "bc1a_srgb": "rgba"}
+OWN_CHANNELS = {"bc1": "rgb", "bc3": "rgba", "bc4": "r", "bc5": "rg", "bc4_snorm": "r", "bc5_snorm": "rg", "bc6h": "rgb", "bc7": "rgba", "etc1": "rgb", "bc1a": "rgba", "bc1a_srgb": "rgba", "bc2": "rgba", "bc2_srgb": "rgba"}
 _DXGI_BASE = {71: "bc1", 72: "bc1", 77: "bc3", 78: "bc3", 80: "bc4", 81: "bc4_snorm", 83: "bc5", 84: "bc5_snorm", 95: "bc6h", 96: "bc6h",
-              98: "bc7", 99: "bc7", 0x8D64: "etc1"}
+              98: "bc7", 99: "bc7", 0x8D64: "etc1", 0x83F2: "bc2", 0x8C4E: "bc2"}
 
 
 def _base(fmt):
@@ -618,10 +622,10 @@ def _call(fmt, surf, dst_ptr, settings):
     elif fmt == "etc1":
         st = settings if isinstance(settings, EtcSettings) else etc_profile(settings or "slow")
         L.itwCompressBlocksETC1(C.byref(surf), dst_ptr, C.byref(st))
-    elif fmt in ("bc1a", "bc1a_srgb"):
+    elif fmt in ("bc1a", "bc1a_srgb", "bc2", "bc2_srgb"):
         # no block-level entry point: the single image is the slice call with one slice (synchronous)
         assert settings is None or isinstance(settings, Bc1aSettings)
-        pitch = ((surf.width + 3) // 4) * 8
+        pitch = ((surf.width + 3) // 4) * BYTES_PER_BLOCK[fmt]
         if not L.itwCompressImageSlicedEx(C.byref(surf), dst_ptr, pitch, DXGI_FORMAT[fmt], C.cast(C.byref(settings), C.c_void_p) if settings is not None else None,
                                           1 << 62, None, None) and L.itwLastError():
             raise RuntimeError(L.itwLastError().decode())
@@ -764,7 +768,7 @@ def compress_image(fmt, img, profile=None, multithreaded=True, slice_pixels=0, p
     pitch = block_count(fmt, w, 4) * BYTES_PER_BLOCK[fmt]
     if fmt == "etc1" and settings is None:
         settings = etc_profile(profile or "slow")
-    if settings is not None or _base(fmt) == "bc1a":                    # ("bc1a": no trampoline either; None is Bc1aSettings())
+    if settings is not None or _base(fmt) in ("bc1a", "bc2"):           # ("bc1a", "bc2": no trampoline either; None is Bc1aSettings())
         ok = lib().itwCompressImageSlicedEx(C.byref(surf), dst, pitch, DXGI_FORMAT[fmt], C.cast(C.byref(settings), C.c_void_p) if settings is not None else None, slice_pixels,
                                             C.cast(cb, C.c_void_p) if cb else None, None)
     else:
@@ -1414,7 +1418,7 @@ def decode(fmt, blocks, width, height, want_modes=False):
     (H, W, 4) uint8 -- uint16 half bit patterns for bc6h, int8 for the signed formats -- in the same kind of container, plus the per-block modes
     (int32) when asked."""
     import numpy as np
-    key = {"bc1": 71, "bc3": 77, "bc7": 98, "bc6h": 95, "bc4": 80, "bc5": 83, "bc4_snorm": 81, "bc5_snorm": 84, "etc1": 0x8D64, "bc1a": 0x83F1, "bc1a_srgb": 0x8C4D}[fmt]
+    key = {"bc1": 71, "bc3": 77, "bc7": 98, "bc6h": 95, "bc4": 80, "bc5": 83, "bc4_snorm": 81, "bc5_snorm": 84, "etc1": 0x8D64, "bc1a": 0x83F1, "bc1a_srgb": 0x8C4D, "bc2": 0x83F2, "bc2_srgb": 0x8C4E}[fmt]
     signed = fmt in SIGNED_FORMATS                      # RGBA8_SNORM texels: int8
     nb = block_count(fmt, width, height)
     es = 2 if fmt == "bc6h" else 1
