@@ -65,6 +65,7 @@
 //     the load path (IntelPlugin.cpp:2461-2561): header -> every image of the file through ONE itwDecodeChain -> texels.  out.raw holds
 //     every image's texels one after another in file order, tightly packed (RGBA8; RGBA16F bit patterns for BC6H; int8 codes for the
 //     SNORM pair); one line on stdout per image: index, width, height, min alpha (the smallest decoded alpha code: IsAlphaAllOpaque).
+//     A BC6H_SF16 file (DX10 format 96) is decoded and previewed by the signed reading, ITW_FORMAT_BC6H_SIGNED: as a GPU shows it.
 //
 //   encode_dds --preview <in.dds | in.ktx> <image index> <out.ppm> <w> <h> <x> <y> <zoom> [channels] [exposure] [matte]
 //     the preview path (IntelPlugin::FetchPreviewRGB): a w x h viewport of ONE image of the file (itwDdsImage / itwKtxImage's index), decoded
@@ -344,7 +345,9 @@ int decode_file(const char* in_path, const char* out_path)
         first = itwDdsReadHeader(file.data(), file.size(), &desc);
         if (!first) { std::fprintf(stderr, "%s: not a BCn DDS file this library reads\n", in_path); return 1; }
     }
-    const int texel_bytes = desc.dxgi_format == ITW_DXGI_FORMAT_BC6H_UF16 ? 8 : 4;
+    // a file labelled BC6H_SF16 is read as a GPU reads it: the signed reading has a code of its own (itw_dispatch.h), 96 is the header's word
+    const int stream_format = desc.dxgi_format == ITW_DXGI_FORMAT_BC6H_SF16 ? (int)ITW_FORMAT_BC6H_SIGNED : (int)desc.dxgi_format;
+    const int texel_bytes = desc.dxgi_format == ITW_DXGI_FORMAT_BC6H_UF16 || desc.dxgi_format == ITW_DXGI_FORMAT_BC6H_SF16 ? 8 : 4;
     std::vector<rgba_surface> outs;
     size_t texels_bytes = 0, end = first;
     for (uint32_t i = 0;; i++) {                                   // the payload, image by image
@@ -362,8 +365,8 @@ int decode_file(const char* in_path, const char* out_path)
     for (rgba_surface& s : outs) { s.ptr = texels.data() + at; at += (size_t)s.stride * s.height; }
     std::vector<uint32_t> min_alpha(outs.size());
     itwSetErrorMode(ITW_ON_ERROR_RETURN);
-    if (itwDecodeChain((int)desc.dxgi_format, ktx ? packed.data() : file.data() + first, outs.data(), (int)outs.size(), nullptr, min_alpha.data()) != 0) {
-        std::fprintf(stderr, "%s\n", itwLastError() ? itwLastError() : "itwDecodeChain refused the file (BC6H_SF16 is not decoded)");
+    if (itwDecodeChain(stream_format, ktx ? packed.data() : file.data() + first, outs.data(), (int)outs.size(), nullptr, min_alpha.data()) != 0) {
+        std::fprintf(stderr, "%s\n", itwLastError() ? itwLastError() : "itwDecodeChain refused the file");
         return 1;
     }
     for (size_t i = 0; i < outs.size(); i++) std::printf("image %zu: %d %d min_alpha %u\n", i, outs[i].width, outs[i].height, min_alpha[i]);
@@ -391,7 +394,8 @@ int preview_file(const char* in_path, int argc, char** args)
         std::fprintf(stderr, "%s: not a DDS / KTX file this library reads\n", in_path);
         return 1;
     }
-    const int format = ktx ? (int)kdesc.gl_internal_format : (int)desc.dxgi_format;
+    const int format = ktx ? (int)kdesc.gl_internal_format
+                     : desc.dxgi_format == ITW_DXGI_FORMAT_BC6H_SF16 ? (int)ITW_FORMAT_BC6H_SIGNED : (int)desc.dxgi_format;      // (as --decode)
     uint32_t w = 0, h = 0; size_t off = 0;
     const uint32_t index = (uint32_t)std::strtoul(args[0], nullptr, 10);
     const size_t n = ktx ? itwKtxImage(&kdesc, index, &w, &h, &off) : itwDdsImage(&desc, index, &w, &h, &off);

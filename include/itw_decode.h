@@ -36,6 +36,22 @@ extern "C" {
  * DirectXTex format, like the BC4 / BC5 group); the colour is always the four-colour palette whatever the order of the endpoints -- BC2 has
  * no 3-colour mode --, alpha is the texel's 4-bit code times 17, which is D3DXDecodeBC2's n / 15 exactly; no modes (0);
  * itw_error_stats.dxgi_format repeats the code given; own channels RGBA.
+ * ITW_FORMAT_BC6H_SIGNED (0x8E8E, itw_dispatch.h): the SIGNED reading of a BC6H stream -- what a GPU shows for a texture labelled BC6H_SF16,
+ * whoever wrote the file -- taken by itwDecodeBlocks (whole blocks), itwDecodeChain / itwDecodeImage (any size >= 1), itwMeasureBlocks,
+ * itwMeasureChain and itwPreviewBlocks; 16-byte blocks, RGBA16F bit patterns, alpha 0x3C00, modes 0..13 and -1 as for 95.  Byte for byte
+ * DirectXTex's D3DXDecodeBC6HS (BC6HBC7.cpp:1077-1235), the halves INTColor::ToF16(.., true) produces:
+ *  1. endpoint 0.A is sign-extended at the base precision, every other endpoint at its own field width (the delta width in the transformed
+ *     modes, the base width otherwise), in transformed and untransformed modes alike (:1143-1159);
+ *  2. transformed modes: each other endpoint becomes (itself + 0.A) & ((1 << base) - 1), sign-extended again at the base precision (:582-594);
+ *  3. Unquantize (:1316-1335): base >= 16 keeps the value; otherwise on the magnitude m: 0 -> 0, m >= (1 << (base - 1)) - 1 -> 0x7FFF, else
+ *     ((m << 15) + 0x4000) >> (base - 1), and the sign is put back;
+ *  4. a texel is (a * (64 - w) + b * w + 32) >> 6 on signed ints, an arithmetic shift;
+ *  5. FinishUnquantize (:1351-1354): x < 0 ? -(((-x) * 31) >> 5) : (x * 31) >> 5;
+ *  6. INT2F16 (BC.h:407-420): 0x8000 | magnitude for a negative value, no clamp, and zero is never -0.
+ *  In the 16-bit mode (13) an endpoint can be -32768, and a texel that interpolates to exactly -32768 is (32768 * 31) >> 5 = 0x7C00 under the
+ *  sign bit: 0xFC00, -Inf (the reference's recorded output has such texels).  +Inf and NaN patterns cannot occur: the largest positive
+ *  result is 0x7BFF.  A reserved prefix gives 0, 0, 0, 0x3C00 and mode -1.  This library's ENCODER under code 96 still writes the reference's
+ *  unsigned-coded blocks, as the reference does; a signed encoder does not exist here (itw_dispatch.h).
  * `blocks`, `out`, `modes` are host or device pointers, in any mix.  With all of them on the device the call is one kernel launch,
  * asynchronous on the calling thread's stream (itwSetStream): it allocates nothing, touches no buffer of the thread and can be captured
  * into a graph.  With any host pointer it stages through the calling thread's grow-only device buffer (the one itwDecodeChain uses;
@@ -57,9 +73,11 @@ int itwDecodeBlocks(int dxgi_format, const uint8_t* blocks, int width, int heigh
  * (IntelPlugin.cpp:2461-2561).  `blocks`: the packed stream of `count` images as itwCompressImageChain lays it out (image i starts at the
  * summed sizes of the images before it, itwChainBytes; ceil(w/4)*ceil(h/4) blocks per image -- a DDS payload, itw_dds.h: itwDdsImage).
  * outs[i]: where image i's texels go -- ptr, width, height (any >= 1), stride (bytes, a multiple of 4, at least the row); RGBA8, int8
- * RGBA8_SNORM for BC4S / BC5S, RGBA16F bit patterns for BC6H_UF16.  ptr is 4-byte aligned (8 for RGBA16F).  Texels outside
+ * RGBA8_SNORM for BC4S / BC5S, RGBA16F bit patterns for BC6H_UF16 and ITW_FORMAT_BC6H_SIGNED.  ptr is 4-byte aligned (8 for RGBA16F).  Texels outside
  * width x height are never written: edge blocks are cropped on store, for every format.
- * dxgi_format: 71, 72, 77, 78, 80, 81, 83, 84, 95, 98, 99, 0x8D64 (ETC1).  BC6H_SF16 (96) is refused: the signed decode is not built.
+ * dxgi_format: 71, 72, 77, 78, 80, 81, 83, 84, 95, 98, 99, 0x8D64 (ETC1), the BC1A / BC2 codes, ITW_FORMAT_BC6H_SIGNED.  BC6H_SF16 (96) itself
+ * stays refused -- at itwDecodeBlocks the code reads as unsigned, and nothing here may pass for that --: a loader that finds 96 in a file's
+ * header passes ITW_FORMAT_BC6H_SIGNED, and the file is then read as a GPU reads it.
  * modes (optional, may be NULL): one int32 per block of the concatenated block list, numbered as itwDecodeBlocks numbers them.
  * min_alpha (optional, may be NULL): one uint32 per image, the smallest decoded alpha code among the texels actually stored -- the load
  * path's IsAlphaAllOpaque question (255 = opaque) without a second pass.  For the formats that fill alpha it is that constant: BC4 / BC5
@@ -96,7 +114,9 @@ int itwDecodeImage(int dxgi_format, const uint8_t* blocks, const rgba_surface* o
  *     one fp32 multiply, d = (double)v, then d > 1 -> 255, d < 0 -> 0, NaN -> 0 (what the reference's cast gives on x86), otherwise
  *     (uint8_t)(d * 255.0), the product in double, truncated (FloatToByte, IntelPlugin.h:41-48; :676-678).  For BC6H this is also the
  *     reference's 32-bit-document route (:628-654, ConvertTo8Bit(x, false)), since DirectXTex widens the same halves.
- *     A decoded texel is exactly what itwDecodeImage stores, filled channels included: BC4 (R,0,0,255), BC6H alpha 0x3C00, ETC1 alpha 255. */
+ *     A decoded texel is exactly what itwDecodeImage stores, filled channels included: BC4 (R,0,0,255), BC6H alpha 0x3C00, ETC1 alpha 255.
+ *     ITW_FORMAT_BC6H_SIGNED: the same step on the halves of the signed reading; a negative value, -Inf included, shows 0 because d < 0.
+ *     This is the library's extension of the float route: the reference never previews a signed stream. */
 #define ITW_PREVIEW_CHANNEL_RED   0x04   /* the reference's PREVIEW_OPTIONS values, IntelPlugin.h:248-261 */
 #define ITW_PREVIEW_CHANNEL_GREEN 0x08
 #define ITW_PREVIEW_CHANNEL_BLUE  0x10
@@ -122,7 +142,8 @@ typedef struct itw_preview_view {
 
 /* itwPreviewBlocks: the compressed pane.  `blocks`: the ceil(width/4) * ceil(height/4) blocks, raster order, of ONE image of any size >= 1
  * (an image of a chain; of a DDS / KTX payload via itwDdsImage / itwKtxImage).  dxgi_format: 71, 72, 77, 78, 80, 83, 95, 98, 99 or
- * ITW_FORMAT_ETC1_RGB8; BC4S / BC5S (81, 84) and BC6H_SF16 (96) are refused (the reference previews neither).
+ * ITW_FORMAT_ETC1_RGB8, the BC1A / BC2 codes or ITW_FORMAT_BC6H_SIGNED; BC4S / BC5S (81, 84) and BC6H_SF16 (96) are refused (the reference
+ * previews neither; a BC6H_SF16 file is previewed under ITW_FORMAT_BC6H_SIGNED).
  * itwPreviewSurface: the original pane, through the same sampling code with a plain load in place of the decode.  source: RGBA8
  * (texel_bytes 4) or RGBA16F bit patterns (texel_bytes 8), any size >= 1, stride >= the row's bytes; a device source has ptr and stride
  * aligned to the texel (a host source: any).
@@ -151,6 +172,10 @@ int itwPreviewSurface(const rgba_surface* source, int texel_bytes, const itw_pre
  * in included (BC4 / BC5: 0 / 0 / 255, BC6H: alpha 0x3C00, BC1: its decoded alpha); the caller picks the channels that mean something.
  * BC4_SNORM / BC5_SNORM: `source` is RGBA8_SNORM and a code is the int8 value, a source code of -128 read as -127 (both mean -1.0);
  * the filled-in channels are 0 / 0 / 127, and max_abs is at most 254.
+ * ITW_FORMAT_BC6H_SIGNED: a code is the integer the signed reading interpolates in: for half bits h, (h & 0x8000) ? -(h & 0x7FFF) :
+ * (h & 0x7FFF) -- F16ToINT's signed map (BC.h:387-398) without its clamp; +0 and -0 are both 0.  Source and decoded texel go through the
+ * same map, alpha included.  max_abs is at most 0xFFFE, so the largest block sum stays below 2^39 and ITW_MEASURE_MAX_BLOCKS holds;
+ * itw_error_stats.dxgi_format repeats 0x8E8E and itwStatsPsnr is NaN, as for 95.
  * Every field is an integer: the same stream and source give the same bits on every run. */
 typedef struct itw_error_stats {
     int32_t  dxgi_format, width, height;  /* what was measured: texels per row / rows actually compared */

@@ -61,7 +61,16 @@ enum {
      * blocks kept and filled by the {0, 0, 0, 1} rule, the same texel conversion, no block-level entry point and no CompressImage* trampoline
      * (itwCompressImageSliced / itwCompressImageChain run a caller's function as the literal loop); the refined calls, the multi-GPU calls,
      * the normal-map chain calls, any normal_ops and KTX refuse the codes. */
-    ITW_FORMAT_BC2_UNORM = 0x83F2, ITW_FORMAT_BC2_UNORM_SRGB = 0x8C4E
+    ITW_FORMAT_BC2_UNORM = 0x83F2, ITW_FORMAT_BC2_UNORM_SRGB = 0x8C4E,
+    /* The SIGNED reading of a BC6H stream (what a GPU shows for a texture labelled DXGI_FORMAT_BC6H_SF16; DirectXTex's D3DXDecodeBC6HS), by its
+     * GL enum, GL_COMPRESSED_RGB_BPTC_SIGNED_FLOAT.  A DECODE code only: itwDecodeBlocks, itwDecodeChain, itwDecodeImage, itwMeasureBlocks,
+     * itwMeasureChain and itwPreviewBlocks take it (itw_decode.h).  DXGI 96 keeps every meaning it has at each entry point (the encoder
+     * writes the reference's unsigned-coded blocks under it, itwDecodeBlocks reads it as unsigned, the chain and preview calls refuse it).
+     * There is no signed BC6H encoder: every call that encodes -- itwCompressImageSlicedEx, itwCompressImageChain[Ex], the mipped, refined,
+     * normal-map and multi-GPU calls -- fails through the error mode before any device work with a message that says so; itwChainBytes
+     * returns -1, itwSliceWindow[For] 0, GetBytesPerBlock 16 (the stream's block size).  It is not a descriptor code:
+     * itwDds* return 0 for it (a file's header says 96, and itwDdsReadHeader reports 96); KTX does not know it. */
+    ITW_FORMAT_BC6H_SIGNED = 0x8E8E
 };
 
 /* Settings of the two BC1A codes and of the two BC2 codes.  flags: DirectXTex's BC_FLAGS_* values (BC.h) -- error diffusion of the colours, of alpha (the key test

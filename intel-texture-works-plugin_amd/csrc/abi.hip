@@ -332,6 +332,7 @@ void launch(const Job& j, const uint8_t* d_src, int64_t stride, int w, int h, ui
 {
     switch (j.kind) {
     case itw::BCN_NONE: break;                        // (job_of has refused it)
+    case itw::BCN_BC6HS: break;                       // (a decode kind: format_kind never gives it to a Job)
     case itw::BCN_BC1:  itw::launch_bc1(d_src, stride, w, h, d_dst, st); break;
     case itw::BCN_BC3:  itw::launch_bc3(d_src, stride, w, h, d_dst, st); break;
     case itw::BCN_BC7:
@@ -833,6 +834,7 @@ bool compress_sliced(const Job& j, const rgba_surface* src, uint8_t* dst, int sl
 Job job_of(int dxgi_format, const void* settings)
 {
     Job j;
+    itw::refuse_signed_bc6h("encode", dxgi_format);
     j.kind = itw::format_kind(dxgi_format);
     switch (j.kind) {
     case itw::BCN_NONE: itw::fail_msg("DXGI format %d is not one this library encodes", dxgi_format);
@@ -1557,6 +1559,7 @@ bool itwCompressNormalMapChain(const rgba_surface* images, int count, uint8_t* t
     bool done = false;
     itw::clear_failure();
     const bool ok = itw::guarded([&] {
+        itw::refuse_signed_bc6h("itwCompressNormalMapChain", dxgi_format);
         itw::check_normal_ops("itwCompressNormalMapChain", ops, "the gather works a texel at a time and has no neighbours");
         if (itw::format_kind(dxgi_format) == itw::BCN_BC1A) itw::fail_msg("itwCompressNormalMapChain: format 0x%X (BC1 with 1-bit alpha) holds colour, not normals", dxgi_format);
         if (itw::format_kind(dxgi_format) == itw::BCN_BC2) itw::fail_msg("itwCompressNormalMapChain: format 0x%X (BC2) holds colour, not normals", dxgi_format);
@@ -1590,7 +1593,7 @@ int itwSliceWindow(int dxgi_format, int width, int height, int64_t slice_pixels)
 
 int itwSliceWindowFor(int dxgi_format, const void* settings, int width, int height, int64_t slice_pixels)
 {
-    if (slice_window_setting() < 0) return 0;
+    if (slice_window_setting() < 0 || dxgi_format == ITW_FORMAT_BC6H_SIGNED) return 0;      // (a decode code: nothing encodes it, so no call has a window)
     const int kind = itw::format_kind(dxgi_format);         // (a code the library does not encode counts as PCIe-bound, dropping partial blocks)
     const int64_t slices = std::min(itw::slice_count(width, height, slice_pixels), itw::kMaxSlices);
     // null settings for BC7: not heavy

@@ -46,7 +46,7 @@ __device__ __forceinline__ uint32_t decode_chain_block(const uint8_t* __restrict
     uint32_t amin = filled_alpha(FMT) < 0 ? 0xFFFFFFFFu : (uint32_t)filled_alpha(FMT);
     uint8_t* o = im.ptr + (int64_t)yy * 4 * im.stride + (int64_t)xx * 4 * texel_bytes(FMT);
     const bool whole = nx == 4 && ny == 4;                      // an inner block: one branch for its four rows
-    if constexpr (FMT == BCN_BC6H) {
+    if constexpr (is_bc6h(FMT)) {
         uint32_t lo16[16], hi16[16];
         mode = decode_block<FMT>(w, lo16, hi16);
         if (whole) {
@@ -195,7 +195,7 @@ void decode_chain(const char* who, int kind, const uint8_t* blocks, const rgba_s
 extern "C" int itwDecodeChain(int dxgi_format, const uint8_t* blocks, const rgba_surface* outs, int count, int32_t* modes, uint32_t* min_alpha)
 {
     dxgi_format = itw::stream_format(dxgi_format);                                // the BC1A codes: a BC1 stream
-    const int kind = dxgi_format == 96 ? 0 : itw::format_kind(dxgi_format);      // BC6H_SF16: the signed decode is not built, and nothing here may pass for it
+    const int kind = dxgi_format == 96 ? 0 : itw::decode_kind(dxgi_format);      // BC6H_SF16 stays refused: the signed reading goes by ITW_FORMAT_BC6H_SIGNED
     const int64_t total = itw::decode_chain_check(kind, blocks, outs, count);
     if (total <= 0) return total < 0 ? -1 : 0;
     const bool douts = itw::is_device_pointer(outs[0].ptr);
@@ -213,7 +213,7 @@ extern "C" int itwDecodeImage(int dxgi_format, const uint8_t* blocks, const rgba
 // The older single-image entry: its own argument rules (decode_blocks_check; 96 reads as unsigned), then a chain of one without min_alpha
 extern "C" int itwDecodeBlocks(int dxgi_format, const uint8_t* blocks, int width, int height, uint8_t* out, int64_t out_stride, int32_t* modes)
 {
-    const int kind = itw::format_kind(itw::stream_format(dxgi_format));
+    const int kind = itw::decode_kind(itw::stream_format(dxgi_format));
     const int64_t total = itw::decode_blocks_check(kind, width, height, out_stride);
     if (total < 0) return -1;
     const rgba_surface surface{out, width, height, (int32_t)out_stride};

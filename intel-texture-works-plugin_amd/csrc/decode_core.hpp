@@ -3,7 +3,7 @@
 // function; under it the per-format decoders (decode_color, decode_scalar_block, decode_bc7, decode_bc6h) and their tables.  Pure integer
 // work.  Written from the format definitions (the readable statement inside the reference tree is its decoder: BC.cpp for BC1/BC3,
 // BC4BC5.cpp for BC4/BC5, BC6HBC7.cpp:35-37 weights, :40 partitions, :247 fix-ups, :537 BC7 mode table, :1937-2140 BC7 decode,
-// :310-500 BC6H mode descriptors, :1077-1210 BC6H decode, :1313-1359 unquantisation).
+// :310-500 BC6H mode descriptors, :1077-1235 BC6H decode, unsigned and signed, :1313-1359 unquantisation).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -202,7 +202,7 @@ __device__ __forceinline__ int decode_bc7(Bits& bs, uint32_t (&px)[16])
     return mode;
 }
 
-// ---- BC6H, unsigned ----------------------------------------------------------------------------------------
+// ---- BC6H, unsigned and signed -----------------------------------------------------------------------------
 __device__ __forceinline__ int unquantize_uf16(int comp, int bits)
 {
     if (bits >= 15) return comp;
@@ -210,7 +210,28 @@ __device__ __forceinline__ int unquantize_uf16(int comp, int bits)
     if (comp == ((1 << bits) - 1)) return 0xFFFF;
     return ((comp << 16) + 0x8000) >> bits;
 }
+// SIGN_EXTEND (BC.h:33): bit nb - 1 of a field of nb bits is its sign
+__device__ __forceinline__ int sign_extend(int x, int nb) { return (x & (1 << (nb - 1))) ? (x | ~((1 << nb) - 1)) : x; }
+// Unquantize(comp, bits, true) (BC6HBC7.cpp:1316-1335): on the magnitude, the sign put back at the end
+__device__ __forceinline__ int unquantize_sf16(int comp, int bits)
+{
+    if (bits >= 16) return comp;
+    const int m = comp < 0 ? -comp : comp;
+    const int unq = m == 0 ? 0 : m >= ((1 << (bits - 1)) - 1) ? 0x7FFF : ((m << 15) + 0x4000) >> (bits - 1);
+    return comp < 0 ? -unq : unq;
+}
+// FinishUnquantize(x, true) (:1351-1354), then INT2F16(.., true) (BC.h:407-420): sign bit | magnitude, no clamp, zero never -0.  An endpoint of
+// -32768 (the 16-bit mode alone) can interpolate to -32768: (32768 * 31) >> 5 = 0x7C00 under the sign bit, -Inf; the largest positive value is 0x7BFF.
+__device__ __forceinline__ uint32_t finish_sf16(int x)
+{
+    const int f = x < 0 ? -(((-x) * 31) >> 5) : (x * 31) >> 5;      // (a small negative x finishes as 0, which takes no sign bit)
+    return f < 0 ? (0x8000u | (uint32_t)(-f)) : (uint32_t)f;
+}
 
+// SIGNED: D3DXDecodeBC6HS (D3DX_BC6H::Decode(true, ..), :1077-1235) -- endpoint 0.A sign-extended at the base precision and every other endpoint
+// at its own field width, in transformed and untransformed modes alike (:1143-1159); TransformInverse masks the sum and sign-extends it again at
+// the base precision (:582-594); interpolation on signed ints with an arithmetic shift.  The unsigned reading is every `if constexpr (!SIGNED)` branch.
+template <bool SIGNED = false>
 __device__ __forceinline__ int decode_bc6h(Bits& bs, uint32_t (&lo)[16], uint32_t (&hi)[16])
 {
     int m = (int)bs.take(2);
@@ -237,15 +258,27 @@ __device__ __forceinline__ int decode_bc6h(Bits& bs, uint32_t (&lo)[16], uint32_
             }
         }
     }
-    if (L.transformed)
+    if constexpr (!SIGNED) {
+        if (L.transformed)
+            for (int ch = 0; ch < 3; ch++) {
+                const int mask = (1 << L.base_bits[ch]) - 1, db = L.delta_bits[ch];
+                for (int k = 1; k < 4; k++)
+                    if (k < (L.two_regions ? 4 : 2)) {
+                        const int d = (e[k][ch] & (1 << (db - 1))) ? (e[k][ch] | ~((1 << db) - 1)) : e[k][ch];
+                        e[k][ch] = (d + e[0][ch]) & mask;
+                    }
+            }
+    } else {
         for (int ch = 0; ch < 3; ch++) {
-            const int mask = (1 << L.base_bits[ch]) - 1, db = L.delta_bits[ch];
+            const int bb = L.base_bits[ch], db = L.delta_bits[ch];       // delta_bits: the field's width, = base_bits in the untransformed modes
+            e[0][ch] = sign_extend(e[0][ch], bb);
             for (int k = 1; k < 4; k++)
                 if (k < (L.two_regions ? 4 : 2)) {
-                    const int d = (e[k][ch] & (1 << (db - 1))) ? (e[k][ch] | ~((1 << db) - 1)) : e[k][ch];
-                    e[k][ch] = (d + e[0][ch]) & mask;
+                    const int d = sign_extend(e[k][ch], db);
+                    e[k][ch] = L.transformed ? sign_extend((d + e[0][ch]) & ((1 << bb) - 1), bb) : d;
                 }
         }
+    }
     const int ib = L.two_regions ? 3 : 4;
     const uint32_t pattern = L.two_regions ? dec::BCN_PATTERN[shape] : 0u;
     const int anchor1 = L.two_regions ? (dec::BCN_ANCHORS[shape] >> 4) : -1;
@@ -253,16 +286,27 @@ __device__ __forceinline__ int decode_bc6h(Bits& bs, uint32_t (&lo)[16], uint32_
         const int region = (int)((pattern >> (2 * k)) & 3u);
         const int n = ib - ((k == 0 || (region == 1 && k == anchor1)) ? 1 : 0);
         const int w = D_WEIGHTS[ib - 2][bs.take(n)];
-        int v[3];
-        for (int ch = 0; ch < 3; ch++) {
-            const int a = unquantize_uf16(region ? e[2][ch] : e[0][ch], L.base_bits[ch]);
-            const int b = unquantize_uf16(region ? e[3][ch] : e[1][ch], L.base_bits[ch]);
-            int x = (a * (64 - w) + b * w + 32) >> 6;
-            x = (x * 31) >> 6;
-            v[ch] = x > 0x7BFF ? 0x7BFF : x;
+        if constexpr (!SIGNED) {
+            int v[3];
+            for (int ch = 0; ch < 3; ch++) {
+                const int a = unquantize_uf16(region ? e[2][ch] : e[0][ch], L.base_bits[ch]);
+                const int b = unquantize_uf16(region ? e[3][ch] : e[1][ch], L.base_bits[ch]);
+                int x = (a * (64 - w) + b * w + 32) >> 6;
+                x = (x * 31) >> 6;
+                v[ch] = x > 0x7BFF ? 0x7BFF : x;
+            }
+            lo[k] = (uint32_t)v[0] | ((uint32_t)v[1] << 16);
+            hi[k] = (uint32_t)v[2] | 0x3C000000u;
+        } else {
+            uint32_t v[3];
+            for (int ch = 0; ch < 3; ch++) {
+                const int a = unquantize_sf16(region ? e[2][ch] : e[0][ch], L.base_bits[ch]);
+                const int b = unquantize_sf16(region ? e[3][ch] : e[1][ch], L.base_bits[ch]);
+                v[ch] = finish_sf16((a * (64 - w) + b * w + 32) >> 6);
+            }
+            lo[k] = v[0] | (v[1] << 16);
+            hi[k] = v[2] | 0x3C000000u;
         }
-        lo[k] = (uint32_t)v[0] | ((uint32_t)v[1] << 16);
-        hi[k] = (uint32_t)v[2] | 0x3C000000u;
     }
     return mode;
 }
@@ -328,7 +372,7 @@ __device__ __forceinline__ Bits block_bits(const uint4 w)
 template <int FMT>
 __device__ __forceinline__ int decode_block(const uint4 w, uint32_t (&px)[16])
 {
-    static_assert(FMT != BCN_BC6H, "BC6H decodes to RGBA16F: the overload below");
+    static_assert(!is_bc6h(FMT), "BC6H decodes to RGBA16F: the overload below");
     if (FMT == BCN_BC7) {
         Bits bs = block_bits(w);
         return decode_bc7(bs, px);
@@ -354,13 +398,13 @@ __device__ __forceinline__ int decode_block(const uint4 w, uint32_t (&px)[16])
     }
     return 0;
 }
-// BC6H: the two dwords of each RGBA16F texel, lo = R | G << 16, hi = B | A << 16 with alpha 1.0; mode 0..13, -1 for a reserved prefix
+// BC6H, either reading: the two dwords of each RGBA16F texel, lo = R | G << 16, hi = B | A << 16 with alpha 1.0; mode 0..13, -1 for a reserved prefix
 template <int FMT>
 __device__ __forceinline__ int decode_block(const uint4 w, uint32_t (&lo)[16], uint32_t (&hi)[16])
 {
-    static_assert(FMT == BCN_BC6H, "the RGBA8 formats: the overload above");
+    static_assert(is_bc6h(FMT), "the RGBA8 formats: the overload above");
     Bits bs = block_bits(w);
-    return decode_bc6h(bs, lo, hi);
+    return decode_bc6h<FMT == BCN_BC6HS>(bs, lo, hi);
 }
 
 // Block j of a stream whose base is 16-byte aligned (8 for the 8-byte formats) or only 4-byte aligned (the payload of a DDS file).  Callers

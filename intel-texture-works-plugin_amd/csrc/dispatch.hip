@@ -159,12 +159,22 @@ static int blocks_across(int width, int f) { return keeps_partial_blocks(f) ? (w
 // reference's answer: its switch ends in "default: return 8"
 int GetBytesPerBlock(int f)
 {
-    const int kind = itw::format_kind(f);
+    const int kind = itw::decode_kind(f);                  // (ITW_FORMAT_BC6H_SIGNED, which only the decode side takes: 16 as well)
     return kind == itw::BCN_NONE ? 8 : itw::block_bytes(kind);
 }
 
-bool CompressImageST(const rgba_surface* input, uint8_t* output, CompressionFunc* cmpFunc, int)
+// ITW_FORMAT_BC6H_SIGNED at a call that runs a caller's function: refused like everywhere else that encodes
+static bool signed_bc6h_refused(const char* who, int dxgi_format)
 {
+    if (dxgi_format != ITW_FORMAT_BC6H_SIGNED) return false;
+    itwClearError();
+    (void)itw::guarded([&] { itw::refuse_signed_bc6h(who, dxgi_format); });
+    return true;
+}
+
+bool CompressImageST(const rgba_surface* input, uint8_t* output, CompressionFunc* cmpFunc, int dxgi_format)
+{
+    if (signed_bc6h_refused("CompressImageST", dxgi_format)) return false;
     itwClearError();
     (*cmpFunc)(input, output);
     return itwLastError() == nullptr;         // always true in the default (abort) error mode, like the reference
@@ -172,6 +182,7 @@ bool CompressImageST(const rgba_surface* input, uint8_t* output, CompressionFunc
 
 bool CompressImageMT(const rgba_surface* input, uint8_t* output, CompressionFunc* cmpFunc, int dxgi_format)
 {
+    if (signed_bc6h_refused("CompressImageMT", dxgi_format)) return false;
     Pool* p = pool();
     const int n = (int)p->threads.size();
     // a surface that already lives on one GPU is encoded there, in one call
@@ -349,7 +360,7 @@ static bool sliced_on_pool(const rgba_surface* source, uint8_t* target, int dxgi
 bool itwCompressImageSliced(const rgba_surface* source, uint8_t* target, int64_t block_row_pitch, CompressionFunc* cmpFunc,
                             int dxgi_format, bool multithreaded, int64_t slice_pixels, ItwProgressFunc* progress, void* user)
 {
-    if (!cmpFunc) return false;
+    if (!cmpFunc || signed_bc6h_refused("itwCompressImageSliced", dxgi_format)) return false;
     const int slices = (int)itw::slice_count(source->width, source->height, slice_pixels);
     // the ABI packs block rows tightly; a wider pitch would need one call per block row
     const int64_t tight = (int64_t)blocks_across(source->width, dxgi_format) * GetBytesPerBlock(dxgi_format);

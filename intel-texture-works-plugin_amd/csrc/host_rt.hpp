@@ -30,6 +30,13 @@ struct Failure { char msg[384]; };
 void report_failure(const Failure& f) noexcept;      // records the message; aborts in abort mode
 void clear_failure() noexcept;
 
+// ITW_FORMAT_BC6H_SIGNED is a decode code: every entry point that encodes says so, before any device work, in place of "unknown format"
+inline void refuse_signed_bc6h(const char* who, int format_code)
+{
+    if (format_code == 0x8E8E)
+        fail_msg("%s: format 0x8E8E (BC6H, signed reading) is a decode code: there is no signed BC6H encoder (DXGI 96 encodes the reference's unsigned-coded blocks)", who);
+}
+
 #define ITW_CHECK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) ::itw::fail_hip(#expr, e_, __FILE__, __LINE__); } while (0)
 
 // Runs `body`; a Failure ends in report_failure().  Returns true on success.

@@ -33,13 +33,14 @@ constexpr int MEASURE_MAX_GROUPS = 1024;      // 4 workgroups per CU; <= 2^25 / 
 static_assert((uint64_t)ITW_MEASURE_MAX_BLOCKS == (1ull << MEASURE_INDEX_BITS), "the key's index field is what limits the block count");
 
 // FMT: a BcnKind (bcn_format.hpp).  `blocks` is 16-byte aligned (8 for the 8-byte formats).  The SNORM pair compares int8 codes, a source
-// code of -128 read as -127 (both are -1.0; the decoder never emits -128)
+// code of -128 read as -127 (both are -1.0; the decoder never emits -128).  BCN_BC6HS compares sign-and-magnitude codes (itw_decode.h): a
+// difference is at most 0xFFFE, so the block sums keep to the unsigned reading's bound
 template <int FMT>
 __global__ void __launch_bounds__(256)
 measure_kernel(const uint8_t* __restrict__ blocks, int32_t blocks_x, int32_t nblocks, const uint8_t* __restrict__ src, int64_t stride,
                int32_t width, int32_t height, itw_error_stats* __restrict__ stats, unsigned long long* __restrict__ block_sse)
 {
-    using Acc = typename std::conditional<FMT == BCN_BC6H, unsigned long long, uint32_t>::type;   // a lane's per-channel sum: 16 * 0xFFFF^2 > 2^32 for BC6H
+    using Acc = typename std::conditional<is_bc6h(FMT), unsigned long long, uint32_t>::type;   // a lane's per-channel sum: 16 * 0xFFFF^2 > 2^32 for BC6H
     __shared__ unsigned long long s_sum[4][4], s_key[4];
     __shared__ uint32_t s_max[4][4], s_hist[17];               // [16]: reserved-prefix blocks
     const int t = threadIdx.x;
@@ -58,7 +59,7 @@ measure_kernel(const uint8_t* __restrict__ blocks, int32_t blocks_x, int32_t nbl
         if constexpr (block_bytes(FMT) == 8) { const uint2 v = *reinterpret_cast<const uint2*>(blocks + (int64_t)b * 8); w = make_uint4(v.x, v.y, 0u, 0u); }
         else w = *reinterpret_cast<const uint4*>(blocks + (int64_t)b * 16);
         int mode;
-        if constexpr (FMT == BCN_BC6H) {
+        if constexpr (is_bc6h(FMT)) {
             uint32_t lo[16], hi[16];
             mode = decode_block<FMT>(w, lo, hi);
             const uint8_t* p = src + (int64_t)yy * 4 * stride + (int64_t)xx * 32;
@@ -73,7 +74,11 @@ measure_kernel(const uint8_t* __restrict__ blocks, int32_t blocks_x, int32_t nbl
                     const uint32_t d[2] = {lo[y * 4 + x], hi[y * 4 + x]};
 #pragma unroll
                     for (int c = 0; c < 4; c++) {
-                        const int a = (int)((s[2 * x + (c >> 1)] >> (16 * (c & 1))) & 0xffffu), e = (int)((d[c >> 1] >> (16 * (c & 1))) & 0xffffu);
+                        int a = (int)((s[2 * x + (c >> 1)] >> (16 * (c & 1))) & 0xffffu), e = (int)((d[c >> 1] >> (16 * (c & 1))) & 0xffffu);
+                        if constexpr (FMT == BCN_BC6HS) {       // the integer the signed reading interpolates in: sign bit and magnitude, both zeros 0
+                            a = (a & 0x8000) ? -(a & 0x7FFF) : a;
+                            e = (e & 0x8000) ? -(e & 0x7FFF) : e;
+                        }
                         const uint32_t df = (uint32_t)abs(a - e);
                         bs[c] += (unsigned long long)df * df;
                         mx[c] = max(mx[c], df);
@@ -227,7 +232,7 @@ extern "C" int itwMeasureBlocks(int dxgi_format, const uint8_t* blocks, const rg
                                 uint64_t* block_sse)
 {
     dxgi_format = itw::stream_format(dxgi_format);            // the BC1A codes: a BC1 stream, measured (and reported in `stats`) as 71 / 72
-    const int kind = itw::format_kind(dxgi_format);
+    const int kind = itw::decode_kind(dxgi_format);
     if (!kind || !blocks || !stats || stats_bytes != sizeof(itw_error_stats) || !surface_ok(kind, source)) return -1;
     if (((uintptr_t)stats & 7) || ((uintptr_t)block_sse & 7)) return -1;
     const bool ok = itw::guarded([&] {
@@ -253,7 +258,7 @@ extern "C" int itwMeasureBlocks(int dxgi_format, const uint8_t* blocks, const rg
 extern "C" int itwMeasureChain(const rgba_surface* images, int count, const uint8_t* blocks, int dxgi_format, itw_error_stats* stats, size_t stats_bytes)
 {
     dxgi_format = itw::stream_format(dxgi_format);
-    const int kind = itw::format_kind(dxgi_format);
+    const int kind = itw::decode_kind(dxgi_format);
     if (!kind || !images || count < 1 || !blocks || !stats || stats_bytes != sizeof(itw_error_stats) || ((uintptr_t)stats & 7)) return -1;
     int64_t total = 0;
     for (int i = 0; i < count; i++) {
@@ -286,8 +291,8 @@ extern "C" int itwMeasureChain(const rgba_surface* images, int count, const uint
 extern "C" double itwStatsPsnr(const itw_error_stats* stats, uint32_t channel_mask)
 {
     const double nan = std::numeric_limits<double>::quiet_NaN();
-    const int kind = stats ? itw::format_kind(itw::stream_format(stats->dxgi_format)) : 0;
-    if (!stats || !(channel_mask & 15u) || kind == itw::BCN_BC6H) return nan;
+    const int kind = stats ? itw::decode_kind(itw::stream_format(stats->dxgi_format)) : 0;
+    if (!stats || !(channel_mask & 15u) || itw::is_bc6h(kind)) return nan;
     double sum = 0.0;
     int channels = 0;
     for (int c = 0; c < 4; c++)

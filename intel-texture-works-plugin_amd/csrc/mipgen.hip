@@ -429,6 +429,7 @@ bool compress_mipped(const rgba_surface* bases, int items, int levels, uint32_t 
     itw::clear_failure();
     const bool ok = itw::guarded([&] {
         AlphaRules alpha;
+        itw::refuse_signed_bc6h(alpha_call ? "itwCompressImageMippedAlpha" : "itwCompressImageMipped", dxgi_format);
         if (alpha_call) {
             alpha = check_alpha("itwCompressImageMippedAlpha", alpha_in, nullptr);
             if (dxgi_format == 95 || dxgi_format == 96) itw::fail_msg("itwCompressImageMippedAlpha: DXGI format %d, whose texels are RGBA16F: the alpha rules are for RGBA8 colour", dxgi_format);

@@ -605,6 +605,7 @@ bool compress_multi(const rgba_surface* input, uint8_t* output, CompressionFunc*
     itw::guarded([&] {
         if (!input || (!input->ptr && !bands) || !output || !cmpFunc) itw::fail_msg("itwCompressImageMultiGPU: null argument");
         if (bands && ranks <= 0) itw::fail_msg("itwCompressImageMultiGPUEx: resident bands need an explicit rank count");
+        itw::refuse_signed_bc6h("itwCompressImageMultiGPU", dxgi_format);
         if (itw::format_kind(dxgi_format) == itw::BCN_BC1A) itw::fail_msg("itwCompressImageMultiGPU: format 0x%X (BC1 with 1-bit alpha) has no block-level function to split over ranks", dxgi_format);
         if (itw::format_kind(dxgi_format) == itw::BCN_BC2) itw::fail_msg("itwCompressImageMultiGPU: format 0x%X (BC2) has no block-level function to split over ranks", dxgi_format);
         std::lock_guard<std::mutex> one(g.submit);

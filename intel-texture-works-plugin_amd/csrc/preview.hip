@@ -26,7 +26,7 @@ namespace itw {
 // what a viewport is taken from: a block format (its BcnKind), or a surface of texels
 enum : int { PREVIEW_RGBA8 = 100, PREVIEW_RGBA16F = 101 };
 constexpr bool preview_is_surface(int src) { return src == PREVIEW_RGBA8 || src == PREVIEW_RGBA16F; }
-constexpr bool preview_is_half(int src) { return src == PREVIEW_RGBA16F || src == BCN_BC6H; }
+constexpr bool preview_is_half(int src) { return src == PREVIEW_RGBA16F || is_bc6h(src); }
 
 struct PreviewArgs {
     const uint8_t* src;          // block row / texel row `row0` of the image starts here (a host source is uploaded from that row on)
@@ -92,6 +92,15 @@ __global__ void __launch_bounds__(256) preview_bc2_kernel(const PreviewArgs a)
 #include "preview_kernel_body.hpp"
 }
 
+// The signed reading of BC6H likewise, for the same reason; tests/test_bc6hs_cpu.py pins the pair's resources.  The tile is the RGBA16F one
+// (96 B a block), and step 4 of the definition shows a negative half, -Inf included, as 0.
+template <bool TILE>
+__global__ void __launch_bounds__(256) preview_bc6hs_kernel(const PreviewArgs a)
+{
+    constexpr int SRC = BCN_BC6HS;
+#include "preview_kernel_body.hpp"
+}
+
 } // namespace itw
 
 namespace {
@@ -152,6 +161,9 @@ void preview(const char* who, int src, const uint8_t* data, int64_t stride, int 
             if constexpr (K.value == itw::BCN_BC2) {
                 if (v.zoom <= ITW_PREVIEW_TILE_MAX_ZOOM) hipLaunchKernelGGL((itw::preview_bc2_kernel<true>), grid, dim3(256), 0, st, a);
                 else hipLaunchKernelGGL((itw::preview_bc2_kernel<false>), grid, dim3(256), 0, st, a);
+            } else if constexpr (K.value == itw::BCN_BC6HS) {
+                if (v.zoom <= ITW_PREVIEW_TILE_MAX_ZOOM) hipLaunchKernelGGL((itw::preview_bc6hs_kernel<true>), grid, dim3(256), 0, st, a);
+                else hipLaunchKernelGGL((itw::preview_bc6hs_kernel<false>), grid, dim3(256), 0, st, a);
             } else if constexpr (K.value != itw::BCN_BC4S && K.value != itw::BCN_BC5S) {      // refused by the checks
                 if (v.zoom <= ITW_PREVIEW_TILE_MAX_ZOOM) hipLaunchKernelGGL((itw::preview_kernel<K.value, true>), grid, dim3(256), 0, st, a);
                 else hipLaunchKernelGGL((itw::preview_kernel<K.value, false>), grid, dim3(256), 0, st, a);

@@ -80,10 +80,11 @@ inline bool preview_view_ok(const itw_preview_view* v, size_t view_bytes, const 
     return out_stride >= (int64_t)3 * v->width;
 }
 
-// itwPreviewBlocks: BCN_NONE to refuse.  The SNORM pair and BC6H_SF16 decode to texels the reference does not preview.
+// itwPreviewBlocks: BCN_NONE to refuse.  The SNORM pair decodes to texels the reference does not preview, and DXGI 96 stays refused: the signed
+// reading of a BC6H stream is previewed under ITW_FORMAT_BC6H_SIGNED (the library's extension of the float route: itw_decode.h).
 inline int preview_blocks_kind(int dxgi_format, const uint8_t* blocks, int width, int height)
 {
-    const int kind = dxgi_format == 96 ? BCN_NONE : format_kind(stream_format(dxgi_format));      // (the BC1A codes: a BC1 stream)
+    const int kind = dxgi_format == 96 ? BCN_NONE : decode_kind(stream_format(dxgi_format));      // (the BC1A codes: a BC1 stream)
     if (kind == BCN_NONE || kind == BCN_BC4S || kind == BCN_BC5S || !blocks || width < 1 || height < 1) return BCN_NONE;
     return image_blocks(rgba_surface{nullptr, width, height, 0}) > (int64_t)ITW_MEASURE_MAX_BLOCKS ? BCN_NONE : kind;
 }

@@ -1,5 +1,5 @@
 // preview_kernel_body.hpp -- the statements of preview.hip's viewport kernel, included into the body of each __global__ function that is one
-// (preview_kernel<SRC, TILE>, preview_bc2_kernel<TILE>; preview.hip says why there are two).  Not a header in its own right: it expects
+// (preview_kernel<SRC, TILE>, preview_bc2_kernel<TILE>, preview_bc6hs_kernel<TILE>; preview.hip says why there are three).  Not a header in its own right: it expects
 // `SRC` (a BcnKind or PREVIEW_RGBA8 / PREVIEW_RGBA16F), `TILE` and the kernel argument `const PreviewArgs a` in scope.
     constexpr bool HALF = preview_is_half(SRC);
     static_assert(!(TILE && preview_is_surface(SRC)), "a surface is sampled with plain loads");

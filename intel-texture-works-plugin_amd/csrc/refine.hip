@@ -842,6 +842,7 @@ int check_refined_call(const char* who, const rgba_surface* source, const uint8_
                        const void* refine_settings, uint32_t channel_mask, const void* stats, size_t stats_bytes, size_t stats_size,
                        const char* stats_type, const uint64_t* block_sse)
 {
+    itw::refuse_signed_bc6h(who, dxgi_format);
     const int kind = itw::format_kind(dxgi_format);
     if (kind != itw::BCN_BC7 && kind != itw::BCN_BC6H) itw::fail_msg("%s: DXGI format %d has one encoder only (BC7 and BC6H have presets to refine with)", who, dxgi_format);
     if (!source || !source->ptr || !target) itw::fail_msg("%s: null surface, texel or target pointer", who);
@@ -864,6 +865,7 @@ int check_refined_chain_call(const char* who, const rgba_surface* images, int co
                              const void* refine_settings, uint32_t channel_mask, const void* stats, size_t stats_bytes, size_t stats_size,
                              const char* stats_type, const itw_refine_stats* image_stats, const uint64_t* block_sse)
 {
+    itw::refuse_signed_bc6h(who, dxgi_format);
     const int kind = itw::format_kind(dxgi_format);
     if (kind != itw::BCN_BC7 && kind != itw::BCN_BC6H) itw::fail_msg("%s: DXGI format %d has one encoder only (BC7 and BC6H have presets to refine with)", who, dxgi_format);
     if (!first_settings || !refine_settings) itw::fail_msg("%s: null settings for the %s tier", who, first_settings ? "refine" : "first");

@@ -109,7 +109,11 @@ assert C.sizeof(RgbaSurface) == 24 and C.sizeof(Bc7Settings) == 64 and C.sizeof(
 # the mipped calls encode them (with a Bc1aSettings or None); decode, measure, preview and DDS take them as synonyms of "bc1" / "bc1_srgb"
 # "bc2" / "bc2_srgb": ITW_FORMAT_BC2_UNORM[_SRGB], GL enums too -- DXGI's 74 / 75 stay refused codes at the entry points and live in DDS files only;
 # encoded where "bc1a" is (same Bc1aSettings), decoded, measured and previewed under the same two codes, stored by dds_file as DXT3 / DX10 74 / 75
-DXGI_FORMAT = {"bc2": 0x83F2, "bc2_srgb": 0x8C4E, "bc1a": 0x83F1, "bc1a_srgb": 0x8C4D, "etc1": 0x8D64, "bc1": 71, "bc1_srgb": 72, "bc3": 77, "bc3_srgb": 78, "bc4": 80, "bc4_snorm": 81, "bc5": 83, "bc5_snorm": 84, "bc6h": 95, "bc6h_sf16": 96, "bc7": 98, "bc7_srgb": 99}
+# "bc6h_signed": ITW_FORMAT_BC6H_SIGNED, the GL enum of the SIGNED reading of a BC6H stream (what a GPU shows for a BC6H_SF16 texture): a decode key
+# only -- decode, decode_chain, decode_image, measure, measure_chain and preview take it (uint16 half bit patterns, like "bc6h"), load_dds decodes
+# a file labelled 96 under it, and every compress* raises ValueError: there is no signed BC6H encoder ("bc6h_sf16" still encodes the
+# reference's unsigned-coded blocks, and decode("bc6h_sf16") is not offered)
+DXGI_FORMAT = {"bc6h_signed": 0x8E8E, "bc2": 0x83F2, "bc2_srgb": 0x8C4E, "bc1a": 0x83F1, "bc1a_srgb": 0x8C4D, "etc1": 0x8D64, "bc1": 71, "bc1_srgb": 72, "bc3": 77, "bc3_srgb": 78, "bc4": 80, "bc4_snorm": 81, "bc5": 83, "bc5_snorm": 84, "bc6h": 95, "bc6h_sf16": 96, "bc7": 98, "bc7_srgb": 99}
 
 
 class DdsDesc(C.Structure):
@@ -151,7 +155,19 @@ class MultiGpuStats(C.Structure):
 # the channels of a decoded texel that carry a format's own data (the others are fill values: itw_decode.h)
 OWN_CHANNELS = {"bc1": "rgb", "bc3": "rgba", "bc4": "r", "bc5": "rg", "bc4_snorm": "r", "bc5_snorm": "rg", "bc6h": "rgb", "bc7": "rgba", "etc1": "rgb", "bc1a": "rgba", "bc1a_srgb": "rgba", "bc2": "rgba", "bc2_srgb": "rgba"}
 _DXGI_BASE = {71: "bc1", 72: "bc1", 77: "bc3", 78: "bc3", 80: "bc4", 81: "bc4_snorm", 83: "bc5", 84: "bc5_snorm", 95: "bc6h", 96: "bc6h",
-              98: "bc7", 99: "bc7", 0x8D64: "etc1", 0x83F2: "bc2", 0x8C4E: "bc2"}
+              98: "bc7", 99: "bc7", 0x8D64: "etc1", 0x83F2: "bc2", 0x8C4E: "bc2", 0x8E8E: "bc6h"}
+
+
+def _encodes(fn):
+    """Decorator of every compress*: "bc6h_signed" names a reading of a stream, not an encoder."""
+    import functools
+
+    @functools.wraps(fn)
+    def checked(fmt, *args, **kwargs):
+        if fmt == "bc6h_signed":
+            raise ValueError(f"{fn.__name__}: 'bc6h_signed' is a decode format: there is no signed BC6H encoder")
+        return fn(fmt, *args, **kwargs)
+    return checked
 
 
 def _base(fmt):
@@ -640,6 +656,7 @@ def block_count(fmt, width, height):
     return (width // 4) * (height // 4)
 
 
+@_encodes
 def compress_numpy(fmt, img, settings=None):
     """Host-pointer path (what the Photoshop plugin does): img (H, W, 4) uint8, or uint16 half bits for bc6h, or int8 for the
     signed formats (TypeError for uint8).  Synchronous; returns a uint8 numpy array of packed blocks."""
@@ -654,6 +671,7 @@ def compress_numpy(fmt, img, settings=None):
     return out
 
 
+@_encodes
 def compress(fmt, img, settings=None, out=None):
     """Device-resident path: img is a CUDA(HIP) torch tensor (H, W, 4) uint8, or int16/uint16/float16 for bc6h, or int8 for the
     signed formats (TypeError for uint8); rows may be strided.  Launches asynchronously on torch's current stream and returns a uint8
@@ -743,6 +761,7 @@ def image_func(fmt, profile=None, L=None):
     return C.cast(getattr(L or lib(), name), C.c_void_p)
 
 
+@_encodes
 def compress_image(fmt, img, profile=None, multithreaded=True, slice_pixels=0, progress=None, out=None, settings=None):
     """The plugin's save path below the pixel conversion (IntelPlugin.cpp:816-884): slice loop -> CompressImageMT/ST ->
     trampoline -> CompressBlocks* (itwCompressImageSliced; with `settings` -- a Bc7Settings / Bc6hSettings / EtcSettings -- through
@@ -796,6 +815,7 @@ def chain_bytes(fmt, images):
     return int(lib().itwChainBytes(C.cast(arr, C.c_void_p), len(images), DXGI_FORMAT[fmt]))
 
 
+@_encodes
 def compress_chain(fmt, images, profile=None, settings=None, progress=None, out=None, cmp_func=None, normal_ops=None):
     """A whole mip chain / cube map / array in one call (itwCompressImageChainEx; with `cmp_func` -- a CompressionFunc address, e.g.
     image_func(fmt, profile) -- itwCompressImageChain; with `normal_ops` -- a bit set of NORMAL_FLIP_X / NORMAL_FLIP_Y / NORMAL_NORMALIZE,
@@ -1017,6 +1037,7 @@ def compress_normal_map_snorm(img, flip_x=False, flip_y=False, normalize=False, 
     return out
 
 
+@_encodes
 def compress_chain_normal_snorm(fmt, images, flip_x=False, flip_y=False, normalize=False, ops=None, progress=None, out=None):
     """itwCompressSignedNormalMapChain: a whole mip chain / cube map of signed normal sources -- (H, W, 4) numpy arrays or CUDA torch tensors
     of one dtype: int8, float16 / 2-byte half bits, or float32 -- to "bc4_snorm" or "bc5_snorm" in one call, every texel quantised as the
@@ -1045,6 +1066,7 @@ def compress_chain_normal_snorm(fmt, images, flip_x=False, flip_y=False, normali
     return bool(ok), out
 
 
+@_encodes
 def compress_mipped_normal_snorm(fmt, base_or_bases, levels=0, flip_x=False, flip_y=False, normalize=False, ops=None, progress=None, out=None):
     """itwCompressSignedNormalMapMipped: the signed normal-map save path from base images in one call -- one signed normal source or a list of
     equally sized ones (int8, float16 / 2-byte half bits, or float32) widened to RGBA16F with the flips, the mip chain, then
@@ -1240,6 +1262,7 @@ def generate_mips_into(chains, per_level=False, srgb=False, alpha_weight=False, 
     return chains
 
 
+@_encodes
 def compress_mipped(fmt, base_or_bases, levels=0, profile=None, settings=None, normal_ops=0, progress=None, out=None, srgb=False,
                     alpha_weight=False, alpha_coverage=0, filter=None, wrap="", report=False):
     """itwCompressImageMipped: the save path from base images in one call -- flips of `normal_ops` on level 0, the mip chain, the normalise on
@@ -1327,6 +1350,7 @@ def multigpu_sub_bands(fmt, width, height, ranks, L=None):
     return out
 
 
+@_encodes
 def compress_image_multigpu(fmt, img, profile=None, ranks=0, out=None, bands=None, stats=None, L=None, interleave=None):
     """itwCompressImageMultiGPU[Ex]: img is a host numpy array or a CUDA torch tensor (H, W, 4); the block stream comes back in
     the same kind of container (or in `out`, which may be the other kind).  Synchronous.
@@ -1415,23 +1439,24 @@ def dds_file(fmt_key, width, height, levels, mip_levels=1, cubemap=False, array_
 
 def decode(fmt, blocks, width, height, want_modes=False):
     """GPU decode (itwDecodeBlocks).  blocks: uint8 numpy array or CUDA torch tensor of packed blocks.  Returns texels as
-    (H, W, 4) uint8 -- uint16 half bit patterns for bc6h, int8 for the signed formats -- in the same kind of container, plus the per-block modes
+    (H, W, 4) uint8 -- uint16 half bit patterns for bc6h and bc6h_signed, int8 for the signed formats -- in the same kind of container, plus the per-block modes
     (int32) when asked."""
     import numpy as np
-    key = {"bc1": 71, "bc3": 77, "bc7": 98, "bc6h": 95, "bc4": 80, "bc5": 83, "bc4_snorm": 81, "bc5_snorm": 84, "etc1": 0x8D64, "bc1a": 0x83F1, "bc1a_srgb": 0x8C4D, "bc2": 0x83F2, "bc2_srgb": 0x8C4E}[fmt]
+    key = {"bc1": 71, "bc3": 77, "bc7": 98, "bc6h": 95, "bc4": 80, "bc5": 83, "bc4_snorm": 81, "bc5_snorm": 84, "etc1": 0x8D64, "bc1a": 0x83F1, "bc1a_srgb": 0x8C4D, "bc2": 0x83F2, "bc2_srgb": 0x8C4E, "bc6h_signed": 0x8E8E}[fmt]
     signed = fmt in SIGNED_FORMATS                      # RGBA8_SNORM texels: int8
     nb = block_count(fmt, width, height)
-    es = 2 if fmt == "bc6h" else 1
+    half = _base(fmt) == "bc6h"                         # "bc6h", "bc6h_signed": RGBA16F bit patterns
+    es = 2 if half else 1
     if isinstance(blocks, np.ndarray):
         blk = np.ascontiguousarray(blocks, dtype=np.uint8).reshape(-1)
-        out = np.empty((height, width, 4), dtype=np.uint16 if fmt == "bc6h" else np.int8 if signed else np.uint8)
+        out = np.empty((height, width, 4), dtype=np.uint16 if half else np.int8 if signed else np.uint8)
         modes = np.empty(nb, dtype=np.int32) if want_modes else None
         rc = lib().itwDecodeBlocks(key, blk.ctypes.data, width, height, out.ctypes.data, width * 4 * es,
                                    modes.ctypes.data if want_modes else None)
     else:
         import torch
         assert blocks.is_cuda and blocks.dtype == torch.uint8 and blocks.is_contiguous()
-        out = torch.empty((height, width, 4), dtype=torch.int16 if fmt == "bc6h" else torch.int8 if signed else torch.uint8, device=blocks.device)
+        out = torch.empty((height, width, 4), dtype=torch.int16 if half else torch.int8 if signed else torch.uint8, device=blocks.device)
         modes = torch.empty(nb, dtype=torch.int32, device=blocks.device) if want_modes else None
         with torch.cuda.device(blocks.device):
             lib().itwSetStream(torch.cuda.current_stream(blocks.device).cuda_stream)
@@ -1626,8 +1651,9 @@ def dds_images(desc):
 def load_dds(data, device=None):
     """The load path: a .dds file's bytes (bytes / uint8 numpy array) -> (DdsDesc, [texel arrays in file order], [min alpha per image]).
     itwDdsReadHeader + itwDdsImage + one itwDecodeChain over the payload.  device None: numpy arrays through host pointers; a torch
-    device: the payload is uploaded and the texels are CUDA tensors.  Raises ValueError for a header this library does not read, a
-    BC6H_SF16 file (not decoded) and a file shorter than its header describes."""
+    device: the payload is uploaded and the texels are CUDA tensors.  A BC6H_SF16 file (DXGI 96) is decoded by the signed reading, "bc6h_signed",
+    whoever wrote it; the descriptor returned still says 96.  Raises ValueError for a header this library does not read and a file shorter
+    than its header describes."""
     import numpy as np
     raw = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
     desc = DdsDesc()
@@ -1636,7 +1662,7 @@ def load_dds(data, device=None):
         raise ValueError("not a BCn DDS file this library reads")
     fmt = {v: k for k, v in DXGI_FORMAT.items()}[int(desc.dxgi_format)]
     if fmt == "bc6h_sf16":
-        raise ValueError("BC6H_SF16 is not decoded")
+        fmt = "bc6h_signed"                               # a file's label 96 is a descriptor code; the entry points read it under 0x8E8E
     images = dds_images(desc)
     end = images[-1][2] + images[-1][3] if images else 0
     if not images or images[0][2] != first or raw.size < end:
@@ -1795,6 +1821,7 @@ def measure_chain(fmt, blocks, levels):
     return res
 
 
+@_encodes
 def compress_refined(fmt, img, first, refine, max_block_sse, channels=None, want_block_map=False, want_tier_map=False):
     """itwCompressImageRefined: encode `img` with the preset `first`, then encode with `refine` only the blocks whose error is above
     max_block_sse, keeping a second encoding only where it is strictly better (include/itw_dispatch.h).  fmt: 'bc7' / 'bc6h' (or another
@@ -1849,6 +1876,7 @@ def psnr_to_total_sse(fmt, width, height, psnr_db, channels=None):
     return int(lib().itwPsnrToTotalSse(DXGI_FORMAT[fmt], int(width), int(height), _channel_mask("rgb" if channels is None else channels), float(psnr_db)))
 
 
+@_encodes
 def compress_refined_to(fmt, img, first, refine, max_listed=None, share=None, target_sse=None, target_psnr=None, channels=None,
                         want_block_map=False, want_tier_map=False):
     """itwCompressImageRefinedTo: compress_refined with the budget chosen on the device (include/itw_dispatch.h).  What to spend: max_listed,
@@ -1961,6 +1989,7 @@ def _chain_refined(name, fmt, images, first, refine, channels, want_block_map, w
     return (out, stats) + ((bmap,) if want_block_map else ()) + ((tmap,) if want_tier_map else ()) + ((per,) if want_image_stats else ())
 
 
+@_encodes
 def compress_chain_refined(fmt, images, first, refine, max_block_sse, channels=None, want_block_map=False, want_tier_map=False,
                            want_image_stats=False):
     """itwCompressImageChainRefined: compress_refined over a whole chain as one population of blocks (include/itw_dispatch.h).  images: list
@@ -1974,6 +2003,7 @@ def compress_chain_refined(fmt, images, first, refine, max_block_sse, channels=N
                           RefineStats(), (int(max_block_sse),))
 
 
+@_encodes
 def compress_chain_refined_to(fmt, images, first, refine, max_listed=None, share=None, target_sse=None, target_psnr=None, channels=None,
                               want_block_map=False, want_tier_map=False, want_image_stats=False):
     """itwCompressImageChainRefinedTo: compress_refined_to over a whole chain as one population: share is of the chain's blocks, target_psnr

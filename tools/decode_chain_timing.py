@@ -17,7 +17,12 @@ Recorded for the reader to judge: (b) neither blocks nor image is slower than pa
 min-max spread (blocks_within_parent_spread, b_within_parent_spread); hbm_fraction of (b) device-resident = (stream + texels) bytes /
 median time / 8 TB/s.
 One JSON object per line (stdout, and appended to profiles/decode_chain_timing.jsonl unless --no-save).
-Usage: python tools/decode_chain_timing.py --parent-lib=PATH [reps] [inner] [--no-save] [--out=PATH]"""
+--bc6hs: the signed reading of BC6H (ITW_FORMAT_BC6H_SIGNED) next to the unsigned one, this build only (the parent does not know the code, so
+no --parent-lib): the same bc6h streams read under 95 and under 0x8E8E, the legs alternating in one run -- (s) one 4096^2 itwDecodeBlocks,
+(c) the 54-image cube through one itwDecodeChain and through the itwDecodeBlocks loop -- device-resident and from host memory; per row
+signed_vs_unsigned by medians with each leg's spread beside it.  Appended to profiles/bc6hs_timing.jsonl.
+Usage: python tools/decode_chain_timing.py --parent-lib=PATH [reps] [inner] [--no-save] [--out=PATH]
+       python tools/decode_chain_timing.py --bc6hs [reps] [inner] [--no-save] [--out=PATH]"""
 import ctypes as C
 import json
 import os
@@ -53,24 +58,82 @@ def _bind(L):
     return L
 
 
+def bc6hs_legs(torch, dev, L, run, reps, inner):
+    """The --bc6hs rows: one bc6h stream (this library's `fast` encode of the bench surface: valid blocks under either reading) decoded under 95
+    and under ITW_FORMAT_BC6H_SIGNED, alternating."""
+    U, S = itw_amd.DXGI_FORMAT["bc6h"], itw_amd.DXGI_FORMAT["bc6h_signed"]
+    levels = [lv for lv in itw_amd.mip_chain(_source("bc6h", 1024)) if lv.shape[0] >= 4]
+    ok, cube_blocks = itw_amd.compress_chain("bc6h", [torch.from_numpy(lv.view(np.int16)).to(dev) for lv in levels] * 6, profile="fast")
+    assert ok
+    sizes = [tuple(lv.shape[:2]) for lv in levels] * 6
+    offs = np.concatenate([[0], np.cumsum([(h // 4) * (w // 4) * 16 for h, w in sizes])]).tolist()
+    big_blocks = itw_amd.compress("bc6h", torch.from_numpy(_source("bc6h", 4096).view(np.int16)).to(dev), "fast")
+    torch.cuda.synchronize()
+    rows = []
+    for kind in ("device", "host"):
+        if kind == "device":
+            blocks, single = cube_blocks, big_blocks
+            outs = [torch.empty((h, w, 4), dtype=torch.int16, device=dev) for h, w in sizes]
+            one = torch.empty((4096, 4096, 4), dtype=torch.int16, device=dev)
+            ptr = lambda t: t.data_ptr()                         # noqa: E731
+        else:
+            blocks, single = cube_blocks.cpu().numpy(), big_blocks.cpu().numpy()
+            outs = [np.empty((h, w, 4), dtype=np.uint16) for h, w in sizes]
+            one = np.empty((4096, 4096, 4), dtype=np.uint16)
+            ptr = lambda a: a.ctypes.data                        # noqa: E731
+        surfs = (itw_amd.RgbaSurface * len(sizes))(*[itw_amd.RgbaSurface(ptr(o), w, h, w * 8) for o, (h, w) in zip(outs, sizes)])
+        bp, sp, optrs = ptr(blocks), ptr(single), [ptr(o) for o in outs]
+
+        def loop(key):
+            def fn():
+                for i, (h, w) in enumerate(sizes):
+                    assert L.itwDecodeBlocks(key, bp + offs[i], w, h, optrs[i], w * 8, None) == 0
+            return fn
+
+        def chain(key):
+            return lambda: L.itwDecodeChain(key, bp, C.cast(surfs, C.c_void_p), 54, None, None)
+
+        def blocks_of(key):
+            return lambda: L.itwDecodeBlocks(key, sp, 4096, 4096, ptr(one), 4096 * 8, None)
+
+        assert chain(S)() == 0 and blocks_of(S)() == 0
+        base = {"format": "bc6h_signed beside bc6h", "pointers": kind, "reps": reps, "inner": inner,
+                "timing": "host clock around calls that each end in a stream synchronise", "device": itw_amd.device_info()}
+        s = run({"unsigned_blocks": blocks_of(U), "signed_blocks": blocks_of(S)})
+        row = dict(base, leg="s_single_4096", images=1, blocks=1024 * 1024, variants=s,
+                   signed_vs_unsigned=round(s["signed_blocks"]["median_ms"] / s["unsigned_blocks"]["median_ms"], 4))
+        if kind == "device":
+            row["hbm_fraction_signed"] = round((1024 * 1024 * 16 + 4096 * 4096 * 8) / (s["signed_blocks"]["median_ms"] * 1e-3) / HBM_BYTES_PER_S, 4)
+        c = run({"unsigned_chain": chain(U), "signed_chain": chain(S), "unsigned_loop": loop(U), "signed_loop": loop(S)})
+        rows += [row, dict(base, leg="c_cube_1024_mips_to_4", images=54, blocks=offs[-1] // 16, variants=c,
+                           signed_vs_unsigned_chain=round(c["signed_chain"]["median_ms"] / c["unsigned_chain"]["median_ms"], 4),
+                           signed_chain_vs_signed_loop=round(c["signed_chain"]["median_ms"] / c["signed_loop"]["median_ms"], 4))]
+        for r in rows[-2:]:
+            print(json.dumps(r), flush=True)
+    return rows
+
+
 def main():
     import torch
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
     reps = int(args[0]) if args else 7
     inner = int(args[1]) if len(args) > 1 else 5
     save = "--no-save" not in sys.argv
-    out_path = next((a[6:] for a in sys.argv if a.startswith("--out=")), os.path.join(ROOT, "profiles", "decode_chain_timing.jsonl"))
+    signed_legs = "--bc6hs" in sys.argv
+    out_path = next((a[6:] for a in sys.argv if a.startswith("--out=")),
+                    os.path.join(ROOT, "profiles", "bc6hs_timing.jsonl" if signed_legs else "decode_chain_timing.jsonl"))
     parent_path = next((a[13:] for a in sys.argv if a.startswith("--parent-lib=")), None)
-    if not parent_path:
+    if not parent_path and not signed_legs:
         sys.exit("--parent-lib=PATH is required: the parent commit's libispc_texcomp.so is what every leg is measured against")
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
     L = itw_amd.lib()
-    P = _bind(C.CDLL(parent_path))
     stream = torch.cuda.current_stream(dev).cuda_stream
     L.itwSetStream(stream)
-    P.itwSetStream(stream)
-    parent_note = os.path.basename(parent_path) + " built from the parent commit"
+    if not signed_legs:
+        P = _bind(C.CDLL(parent_path))
+        P.itwSetStream(stream)
+        parent_note = os.path.basename(parent_path) + " built from the parent commit"
 
     def timed(fn):
         torch.cuda.synchronize()
@@ -95,6 +158,14 @@ def main():
         return out
 
     rows, failed = [], []
+    if signed_legs:
+        rows = bc6hs_legs(torch, dev, L, run, reps, inner)
+        if save and rows:
+            os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+            with open(out_path, "a") as f:
+                for r in rows:
+                    f.write(json.dumps(r) + "\n")
+        return
     for fmt, profile, cube in FORMATS:
         key = itw_amd.DXGI_FORMAT[fmt]
         px, bpb = (8 if fmt == "bc6h" else 4), itw_amd.BYTES_PER_BLOCK[fmt]
