@@ -59,6 +59,12 @@
 //                 default's box / linear (ITW_MIP_CUBIC / ITW_MIP_TRIANGLE), and wrap addressing along x, y or both for a tiling texture
 //                 (ITW_MIP_WRAP_U / _V; it changes nothing under the default filter).  Every format; go with --srgb-mips,
 //                 --alpha-coverage, --normal and --cube-cross; not with --alpha-weight or --signed-normal.
+//     --resize WxH | --fit pow2, --resize-filter point|linear|cubic|triangle : the first stage of a texture pipeline, texconv's -w / -h /
+//                 -pow2: the image is fitted to W x H, or to the power-of-two size nearest its own (the longer axis down to a power of
+//                 two, the other to the one that keeps the aspect best), before everything else -- the normal stages, --mips, the
+//                 encode.  DirectX::Resize on the device (itwGenerateMipChain with ITW_MIP_RESIZE over two levels); without
+//                 --resize-filter the reference's default, box at exactly 2:1 and linear otherwise.  --srgb-mips and --mip-wrap hold
+//                 for this stage too (the linear filter refuses wrap on an axis that grows).  Not with --cube-cross or --signed-normal.
 //
 //   encode_dds --decode <in.dds | in.ktx> <out.raw>
 //     (.dds or .ktx: told apart by the file's first bytes; a KTX file's images come in ITS order, level then face)
@@ -72,6 +78,7 @@
 //     only where the viewport looks (itwPreviewBlocks), written as a binary PPM.  x, y: the viewport's offset in its own pixels; zoom: source
 //     texels per viewport pixel (the caller divides by 1 << mip level to show a mip at the base image's scale); channels: letters of rgba
 //     (default rgb); exposure: BC6H only (default 1); matte: 0xBBGGRR outside the image (default 0).
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -428,6 +435,24 @@ int preview_file(const char* in_path, int argc, char** args)
 
 } // namespace
 
+// --fit pow2, texconv's rule for -pow2 with its default size cap restated: the longer axis becomes the largest of 16384, 8192, ... that
+// is <= itself; the other axis the one of them whose ratio to it is nearest the source's aspect in fp32, the larger on a tie
+static void fit_power_of_two(int w, int h, int* tw, int* th)
+{
+    const int cap = 16384;
+    const float aspect = (float)w / (float)h;
+    int longer = cap;
+    while (longer > 1 && longer > (w > h ? w : h)) longer >>= 1;
+    int other = cap;
+    float best = INFINITY;
+    for (int v = cap; v > 0; v >>= 1) {
+        const float score = std::fabs((w > h ? (float)longer / (float)v : (float)v / (float)longer) - aspect);
+        if (score < best) { best = score; other = v; }
+    }
+    *tw = w > h ? longer : other;
+    *th = w > h ? other : longer;
+}
+
 int main(int argc, char** argv)
 {
     if (argc == 4 && std::strcmp(argv[1], "--decode") == 0) return decode_file(argv[2], argv[3]);
@@ -441,6 +466,9 @@ int main(int argc, char** argv)
     uint32_t normal_ops = 0;                                    // ITW_NORMAL_*
     bool mips = false, srgb_mips = false, alpha_given = false, filter_given = false;
     uint32_t filter_flags = 0;                                  // ITW_MIP_CUBIC / _TRIANGLE / _WRAP_U / _WRAP_V
+    int resize_w = 0, resize_h = 0;                             // --resize WxH
+    bool fit_pow2 = false, resize_filter_given = false;         // --fit pow2, --resize-filter
+    uint32_t resize_filter = 0;                                 // ITW_MIP_POINT / _LINEAR / _CUBIC / _TRIANGLE
     itw_mip_alpha alpha = { (uint32_t)sizeof(itw_mip_alpha), 0, 0, 0 };
     int mip_levels = 0;                                         // 0: the full chain
     int signed_tb = 0;                                          // --signed-normal: texel bytes of the signed source (4, 8 or 16)
@@ -538,6 +566,24 @@ int main(int argc, char** argv)
             else { std::fprintf(stderr, "--mip-wrap takes u, v or uv\n"); return 2; }
             for (int k = i; k + 2 < argc; k++) argv[k] = argv[k + 2];
             argc -= 2; i--;
+        } else if (std::strcmp(argv[i], "--resize") == 0 && i + 1 < argc) {
+            if (std::sscanf(argv[i + 1], "%dx%d", &resize_w, &resize_h) != 2 || resize_w < 1 || resize_h < 1) { std::fprintf(stderr, "--resize takes WxH\n"); return 2; }
+            for (int k = i; k + 2 < argc; k++) argv[k] = argv[k + 2];
+            argc -= 2; i--;
+        } else if (std::strcmp(argv[i], "--fit") == 0 && i + 1 < argc) {
+            if (std::strcmp(argv[i + 1], "pow2") != 0) { std::fprintf(stderr, "--fit takes pow2\n"); return 2; }
+            fit_pow2 = true;
+            for (int k = i; k + 2 < argc; k++) argv[k] = argv[k + 2];
+            argc -= 2; i--;
+        } else if (std::strcmp(argv[i], "--resize-filter") == 0 && i + 1 < argc) {
+            resize_filter_given = true;
+            if (std::strcmp(argv[i + 1], "point") == 0) resize_filter = ITW_MIP_POINT;
+            else if (std::strcmp(argv[i + 1], "linear") == 0) resize_filter = ITW_MIP_LINEAR;
+            else if (std::strcmp(argv[i + 1], "cubic") == 0) resize_filter = ITW_MIP_CUBIC;
+            else if (std::strcmp(argv[i + 1], "triangle") == 0) resize_filter = ITW_MIP_TRIANGLE;
+            else { std::fprintf(stderr, "--resize-filter takes point, linear, cubic or triangle\n"); return 2; }
+            for (int k = i; k + 2 < argc; k++) argv[k] = argv[k + 2];
+            argc -= 2; i--;
         } else if (std::strcmp(argv[i], "--bc-dither") == 0 && i + 1 < argc) {
             if (std::strcmp(argv[i + 1], "rgb") == 0) g_bc1a.flags |= ITW_BC_DITHER_RGB;
             else if (std::strcmp(argv[i + 1], "a") == 0) g_bc1a.flags |= ITW_BC_DITHER_A;
@@ -563,6 +609,7 @@ int main(int argc, char** argv)
                              "          [--normal flipx,flipy,normalize | --signed-normal int8|half|float[,flipx,flipy,normalize]] [--cube-cross] [--mips [levels] [--srgb-mips]]\n"
                              "          [--height r|g|b|a|lum[,mirroru,mirrorv,invert,occlusion] [--height-amplitude <A>]]\n"
                              "          [--alpha-weight] [--alpha-coverage <ref>] [--mip-filter cubic|triangle] [--mip-wrap u|v|uv] [--bc-dither rgb|a|rgb,a] [--bc-uniform]\n"
+                             "          [--resize WxH | --fit pow2] [--resize-filter point|linear|cubic|triangle]\n"
                              "          <format> <width> <height> <in.raw> <out.dds> [slice_pixels]\n"
                              "       %s --decode <in.dds | in.ktx> <out.raw>\n"
                              "       %s --preview <in.dds | in.ktx> <image index> <out.ppm> <w> <h> <x> <y> <zoom> [channels] [exposure] [matte]\n", argv[0], argv[0], argv[0]);
@@ -572,7 +619,7 @@ int main(int argc, char** argv)
     const bool bc1a = std::strcmp(argv[1], "bc1a") == 0 || std::strncmp(argv[1], "bc1a:", 5) == 0 || std::strcmp(argv[1], "bc2") == 0;      // (takes g_bc1a)
     if (bc1a && argv[1][3] == 'a' && argv[1][4] == ':') { g_bc1a.alpha_ref = (float)std::atof(argv[1] + 5); argv[1][4] = '\0'; }
     for (const Format& k : kFormats) if (std::strcmp(k.name, argv[1]) == 0) f = &k;
-    const int width = std::atoi(argv[2]), height = std::atoi(argv[3]);
+    int width = std::atoi(argv[2]), height = std::atoi(argv[3]);
     if (!f || width < 1 || height < 1) { std::fprintf(stderr, "unknown format or bad size\n"); return 2; }
     const long long slice_pixels = argc > 6 ? std::atoll(argv[6]) : 0;
 
@@ -595,6 +642,19 @@ int main(int argc, char** argv)
     std::fclose(in);
 
     rgba_surface source = { texels.data(), width, height, width * texel_bytes };
+    std::vector<uint8_t> resized;                               // --resize / --fit: the image everything after this sees
+    if (resize_w || fit_pow2 || resize_filter_given) {
+        if ((resize_w != 0) == fit_pow2) { std::fprintf(stderr, "--resize-filter goes with --resize WxH or --fit pow2, one of the two\n"); return 2; }
+        if (signed_tb || cube_cross) { std::fprintf(stderr, "--resize and --fit do not go with --signed-normal or --cube-cross\n"); return 2; }
+        if (fit_pow2) fit_power_of_two(width, height, &resize_w, &resize_h);
+        resized.resize((size_t)resize_w * resize_h * texel_bytes);
+        const rgba_surface pair[2] = { source, { resized.data(), resize_w, resize_h, resize_w * texel_bytes } };
+        const uint32_t flags = ITW_MIP_RESIZE | resize_filter | (srgb_mips ? (uint32_t)ITW_MIP_SRGB : 0u) | (filter_flags & (uint32_t)(ITW_MIP_WRAP_U | ITW_MIP_WRAP_V));
+        itwSetErrorMode(ITW_ON_ERROR_RETURN);
+        if (itwGenerateMipChain(pair, 1, 2, texel_bytes, flags) != 0) { std::fprintf(stderr, "%s\n", itwLastError() ? itwLastError() : "the resize refused the call"); return 1; }
+        itwSetErrorMode(ITW_ON_ERROR_ABORT);
+        source = pair[1]; width = resize_w; height = resize_h;
+    }
     std::vector<uint8_t> quantised;                             // --height with --signed-normal and no --mips: the RGBA8_SNORM map
     if (height_ops) {
         // the input is a height map.  The one-call saves take the bit themselves; the other routes see one texel or one block at a time, so

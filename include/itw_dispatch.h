@@ -533,8 +533,9 @@ int itwCubeCrossFaces(const rgba_surface* cross, int pixel_size, rgba_surface fa
  *           otherwise grow a seam at every level.  Under the DEFAULT filter the bits are accepted and change nothing, and that is the
  *           reference's behaviour, not an omission: for source >= dest the linear filter's `isrcA < 0` and `isrcB >= source` branches
  *           (Filters.h:66-102) fire only for 1 -> 1, where the wrapped and the clamped answer coincide, and the box filter never looks past
- *           an edge.  TEX_FILTER_MIRROR_* has no bit: at ratios >= 1 a cubic tap is at most one texel outside, where bounduvw's mirror
- *           equals its clamp, and the triangle filter never reads the flag, so mirror changes no byte of any mip chain.
+ *           an edge.  TEX_FILTER_MIRROR_* changes no byte of a definition-sized chain: at ratios >= 1 a cubic tap is at most one texel
+ *           outside, where bounduvw's mirror equals its clamp, and the triangle filter never reads the flag.  Its bits, ITW_MIP_MIRROR_U /
+ *           _V, therefore belong to the free-size chain below, where an upscale's +2 tap lands two texels outside and the two differ.
  *   texel kinds  all three, with the loads and stores above: RGBA16F (0x7E00 for a NaN; +-Inf makes NaN under cubic, and under triangle
  *           where both signs meet in one sum); RGBA8 on raw codes; RGBA8 with ITW_MIP_SRGB, the filter on D[code] and the store E(v), which
  *           already sends anything below T[1] to 0 and anything above 1 to 255.  The cubic filter's negative lobes give the raw-code
@@ -544,7 +545,37 @@ int itwCubeCrossFaces(const rgba_surface* cross, int pixel_size, rgba_surface fa
  *           weight_colour = 1 with either filter bit is refused: a quotient of sums with negative weights is not an average, and the
  *           weighted triangle kind is left for later.
  *   refused, through the error mode, before any device work and with nothing written: ITW_MIP_CUBIC | ITW_MIP_TRIANGLE together, and the
- *           weight_colour combination.  Bits 2, 8, 0x100 and up stay unknown and refused.
+ *           weight_colour combination.  Bits 2, 8, 0x100, 0x4000 and up stay unknown and refused; 0x200 .. 0x2000 are the free-size chain's.
+ * Mip chains: free sizes (ITW_MIP_RESIZE; itwGenerateMipChain only).  DirectX::Resize's non-WIC filters (DirectXTexResize.cpp:
+ * _ResizePointFilter :242, _ResizeBoxFilter :300, _ResizeLinearFilter :362, _ResizeCubicFilter :448, _ResizeTriangleFilter :608, chosen by
+ * _PerformResizeUsingCustomFilters :784) are the mip functions over a free (source, dest) pair, plus a point filter.  With the bit the
+ * size of every level is whatever its surface says: any width and height >= 1, larger or smaller than the level above, independently per
+ * axis; level l has one size across the items.  Level 0 is read and never written; level l >= 1 is written, filtered from level l-1 as
+ * stored.  levels == 2 is DirectX::Resize (texconv's -w / -h / -pow2); more levels make a chain of the caller's own sizes, for example
+ * 4000 x 3000 -> 4096^2 -> 2048^2.  levels is 2 .. 32; levels <= 1 stays "nothing to do"; the full chain's length is no limit here.
+ * Strides, alignment, pointer kinds, staging and stream behaviour are the call's as always.  Every level pair is its own launch
+ * (ITW_MIP_PER_LEVEL is accepted and changes nothing).  RGBA16F is pinned byte for byte to the reference's own functions
+ * (tests/golden/resize_ref.npz); RGBA8 and RGBA8 with ITW_MIP_SRGB run the same arithmetic between the loads and stores above.
+ *   filter, per pair of levels  no filter bit: box when 2 * dw == sw and 2 * dh == sh, else linear.  Or one of:
+ *   point   (ITW_MIP_POINT)  source column (x * ((sw << 16) / dw)) >> 16 in 64-bit integers (the reference's running sum is that product),
+ *           rows alike.  The texel goes through the kind's own load and store: RGBA8 and sRGB codes are copied, and an RGBA16F texel
+ *           follows the store rule above, +-Inf becomes +-65504 and a NaN 0x7E00.
+ *   linear  (ITW_MIP_LINEAR)  _CreateLinearFilter as written (Filters.h:66-102) WITH its wrap branches: isrcA < 0 becomes source - 1 and
+ *           isrcB >= source becomes 0 under wrap, and weight0 = 1.0f + float(isrcB) - srcB is formed from the folded isrcB.
+ *           Refused: the linear filter, named or chosen by default, with a wrap bit on an axis where dest >= source and source > 1.  There
+ *           the fold fires on the last texels and the weights it leaves are no interpolation (4 -> 8 ends in r[3] * -3.25 + r[0] * 4.25):
+ *           an artefact of the reference that is neither pinned nor "fixed" here; the cubic and triangle filters wrap at any ratio.  On
+ *           axes with dest < source the branches do not fire and the bits change nothing, as in a definition-sized chain.
+ *   cubic, triangle  (ITW_MIP_CUBIC, ITW_MIP_TRIANGLE)  the arithmetic above at any ratio.  (ptrdiff_t)srcB truncates toward zero, so the
+ *           first texels of an upscale have a small negative x: that is the reference's output.  A triangle destination that no list
+ *           entry reaches is written as zeros, what an accumulator that is never added to holds.
+ *   mirror  (ITW_MIP_MIRROR_U / _V: TEX_FILTER_MIRROR_U / _V)  bounduvw's mirror branch (Filters.h:136-146): t < 0 becomes -t - 1 and
+ *           t > source - 1 becomes 2 * source - 1 - t, then the clamp.  Read by the cubic filter only; wrap wins where both are set.
+ *           Accepted and without effect under point, box, linear ("mirror is the same case as clamp for linear") and triangle.
+ *   refused, through the error mode, before any device work and with nothing written: two of POINT / LINEAR / CUBIC / TRIANGLE together;
+ *           POINT, LINEAR or a MIRROR bit without ITW_MIP_RESIZE; the linear-wrap case above; levels > 32; a level below 1 x 1; items that
+ *           disagree on a level's size; a written level of more than 262 140 rows or more than 65 535 items (one launch).
+ *           itwGenerateMipChainAlpha and the itwCompressImageMipped* calls refuse all five bits as unknown.
  * Stated divergence.  The reference's box filter sets urow2 / urow3 once before its level loop (:740-741) and, once the height has reached 1,
  * re-points only urow1 (:746-749): from the level where the height is 1 while the width is still above 1, urow3 reads the second scanline
  * of an EARLIER level, which is no longer loaded (for a base of height 1: uninitialised storage).  Square and tall chains -- cube faces
@@ -563,7 +594,8 @@ int itwCubeCrossFaces(const rgba_surface* cross, int pixel_size, rgba_surface fa
  * 64 x 64 down to 1 x 1 (a 4096^2 chain: two launches); ITW_MIP_PER_LEVEL forces one launch per level, as every other chain takes, for
  * comparison and measurement.  Both routes write the same bytes.  ITW_MIP_SRGB (pixel_size 4 only) selects the sRGB colour kind above; it
  * combines with ITW_MIP_PER_LEVEL, takes the same routes and launches, and both routes write the same bytes.  ITW_MIP_CUBIC, ITW_MIP_TRIANGLE
- * and ITW_MIP_WRAP_U / _V: "Mip chains: cubic and triangle" above.  Flag value 2 is unassigned and
+ * and ITW_MIP_WRAP_U / _V: "Mip chains: cubic and triangle" above.  ITW_MIP_RESIZE and the bits that go with it: "Mip chains: free sizes"
+ * above, whose size rules replace this paragraph's for such a call.  Flag value 2 is unassigned and
  * refused like any unknown bit.  Returns 0, also for items == 0 or levels <= 1 (nothing to do); -1,
  * through the library's error mode and before any device work, for a pixel_size other than 4 or 8, an unknown flag bit, ITW_MIP_SRGB with
  * pixel_size 8, items < 0, a
@@ -586,6 +618,8 @@ int itwCubeCrossFaces(const rgba_surface* cross, int pixel_size, rgba_surface fa
  * itwSrgbToLinear, itwLinearToSrgb: D[code] and E(v) of the sRGB colour kind; host arithmetic only. */
 enum { ITW_MIP_PER_LEVEL = 1, ITW_MIP_SRGB = 4,
        ITW_MIP_CUBIC = 0x10, ITW_MIP_TRIANGLE = 0x20, ITW_MIP_WRAP_U = 0x40, ITW_MIP_WRAP_V = 0x80 };
+/* the free-size chain's bits ("Mip chains: free sizes"): itwGenerateMipChain alone takes them */
+enum { ITW_MIP_RESIZE = 0x200, ITW_MIP_POINT = 0x400, ITW_MIP_LINEAR = 0x800, ITW_MIP_MIRROR_U = 0x1000, ITW_MIP_MIRROR_V = 0x2000 };
 int itwMipLevels(int width, int height);
 int64_t itwMipChainLayout(int width, int height, int items, int levels, int pixel_size, uint8_t* storage, rgba_surface* out);
 int itwGenerateMipChain(const rgba_surface* images, int items, int levels, int pixel_size, uint32_t flags);

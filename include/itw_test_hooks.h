@@ -122,6 +122,14 @@ void itwTestMipCubicVariant(int lds);
  * entries (triangle) the arrays hold; -1 when it is too small or an argument is out of range.  Host arithmetic only. */
 int64_t itwTestMipFilterTable(int kind, int source, int dest, int wrap, int32_t* index, float* weight, int64_t capacity);
 
+/* The host's per-axis tables of the free-size chain (ITW_MIP_RESIZE; csrc/mip_filters.hpp), the functions csrc/resize.hip's kernels run, as
+ * tests/golden/resize_ref.npz records the reference's.  `address`: 0 clamp, 1 wrap, 2 mirror.  kind 1, cubic: as itwTestMipFilterTable's,
+ * under any addressing.  kind 3, point: index[u] = the source texel of destination u, weight[u] = 1.  kind 4, linear
+ * (_CreateLinearFilter as written, wrap branches included; mirror is clamp): index[2 * u], index[2 * u + 1] = u0, u1 and
+ * weight[2 * u], weight[2 * u + 1] = weight0, weight1.  Returns dest; -1 when `capacity` (destinations) is below dest or an argument is
+ * out of range.  The triangle lists of any pair are itwTestMipFilterTable's.  Host arithmetic only. */
+int64_t itwTestResizeTable(int kind, int source, int dest, int address, int32_t* index, float* weight, int64_t capacity);
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

@@ -175,20 +175,23 @@ mip_triangle_kernel(const MipImage* __restrict__ table, int32_t levels, int32_t 
 // which cubic kernel runs; the hooks build can ask for the other (tools/mip_filter_timing.py times them against each other)
 bool g_cubic_lds = false;
 
-size_t MipTapPlan::build(const MipFilter& f, int levels, int w, int h)
+size_t MipTapPlan::build(const MipFilter& f, int levels, const int* lw, const int* lh)
 {
     if (f.kind != MIP_FILTER_TRIANGLE) return 0;
-    const int key[5] = { levels, w, h, f.wrap_u ? 1 : 0, f.wrap_v ? 1 : 0 };       // the lists depend on nothing else: a run of equal chains builds them once
-    if (!words.empty() && std::memcmp(key, built_for, sizeof key) == 0) return words.size() * sizeof(uint32_t);
-    built_for[0] = 0;                                                     // (no chain has 0 levels: a build that fails half way matches nothing)
+    // the lists depend on nothing else: a run of equal chains builds them once.  Every level's size is in the key: under ITW_MIP_RESIZE
+    // two chains of one base and one length may differ in any level below it
+    std::vector<int> key = { f.wrap_u ? 1 : 0, f.wrap_v ? 1 : 0 };
+    for (int l = 0; l < levels; l++) { key.push_back(lw[l]); key.push_back(lh[l]); }
+    if (!words.empty() && key == built_for) return words.size() * sizeof(uint32_t);
+    built_for.clear();                                                    // (no chain has an empty key: a build that fails half way matches nothing)
     words.clear(); x_off.assign((size_t)levels, 0u); y_off.assign((size_t)levels, 0u); repeats.assign((size_t)levels, 0u);
     std::vector<MipTriEntry> lists;
     for (int l = 1; l < levels; l++) {
         for (int axis = 0; axis < 2; axis++) {
-            const int source = mip_dim(axis ? h : w, l - 1), dest = mip_dim(axis ? h : w, l);
+            const int source = axis ? lh[l - 1] : lw[l - 1], dest = axis ? lh[l] : lw[l];
             mip_triangle_lists(source, dest, axis ? f.wrap_v : f.wrap_u, lists);
             if ((words.size() + (size_t)dest + 1) & 1u) words.push_back(0u);      // the entries, two words each, start on 8 bytes
-            if (words.size() + (size_t)dest + 1 + 2 * lists.size() > (size_t)0x7fffffff) fail_msg("mip chain: the triangle filter's lists of a %d x %d base are more than a launch addresses", w, h);
+            if (words.size() + (size_t)dest + 1 + 2 * lists.size() > (size_t)0x7fffffff) fail_msg("mip chain: the triangle filter's lists of a %d x %d base are more than a launch addresses", lw[0], lh[0]);
             (axis ? y_off : x_off)[(size_t)l] = (uint32_t)words.size();
             bool twice = false;
             const bool inside = mip_triangle_gather(lists, dest, words, &twice);
@@ -196,7 +199,7 @@ size_t MipTapPlan::build(const MipFilter& f, int levels, int w, int h)
             if (!inside) fail_msg("mip chain: the triangle filter's lists of %d -> %d name a destination outside the level", source, dest);
         }
     }
-    std::memcpy(built_for, key, sizeof key);
+    built_for = key;
     return words.size() * sizeof(uint32_t);
 }
 
@@ -225,6 +228,24 @@ void launch_chain_filtered(const MipImage* table, const uint32_t* taps, const Mi
     if (srgb)         launch_filtered<4, true>(table, taps, plan, f, items, levels, w, h, st);
     else if (px == 4) launch_filtered<4, false>(table, taps, plan, f, items, levels, w, h, st);
     else              launch_filtered<8, false>(table, taps, plan, f, items, levels, w, h, st);
+}
+
+// (below launch_filtered, so that the kernels keep the order in the object they had before the free-size chain)
+template <int PX, bool SRGB>
+static void launch_triangle(const MipImage* table, const uint32_t* taps, const MipTapPlan& plan, int items, int levels, int l, int ow, int oh, hipStream_t st)
+{
+    const dim3 grid((unsigned)((ow + 63) / 64), (unsigned)((oh + 3) / 4), (unsigned)items);
+    hipLaunchKernelGGL((mip_triangle_kernel<PX, SRGB>), grid, dim3(256), 0, st, table, levels, l, ow, oh, taps, plan.x_off[(size_t)l], plan.y_off[(size_t)l],
+                       plan.repeats[(size_t)l]);
+}
+
+void launch_triangle_level(const MipImage* table, const uint32_t* taps, const MipTapPlan& plan, int items, int levels, int l, int ow, int oh, int px, bool srgb,
+                           hipStream_t st)
+{
+    if (srgb)         launch_triangle<4, true>(table, taps, plan, items, levels, l, ow, oh, st);
+    else if (px == 4) launch_triangle<4, false>(table, taps, plan, items, levels, l, ow, oh, st);
+    else              launch_triangle<8, false>(table, taps, plan, items, levels, l, ow, oh, st);
+    ITW_CHECK(hipGetLastError());
 }
 
 } // namespace itw

@@ -14,7 +14,8 @@
 namespace itw {
 
 // which filter a chain takes: the default's choice between box and linear, or one filter on every level
-enum MipFilterKind { MIP_FILTER_DEFAULT = 0, MIP_FILTER_CUBIC = 1, MIP_FILTER_TRIANGLE = 2 };
+// (point and linear by name are the free-size chain's, ITW_MIP_RESIZE; box is what its default resolves to at exactly 2:1)
+enum MipFilterKind { MIP_FILTER_DEFAULT = 0, MIP_FILTER_CUBIC = 1, MIP_FILTER_TRIANGLE = 2, MIP_FILTER_POINT = 3, MIP_FILTER_LINEAR = 4, MIP_FILTER_BOX = 5 };
 
 // bounduvw with mirror off: wrap folds one period, then the clamp (which alone remains for degenerate sources)
 __host__ __device__ __forceinline__ int32_t mip_bound(int32_t u, int32_t maxu, bool wrap)
@@ -37,6 +38,62 @@ __host__ __device__ __forceinline__ MipCubicTap mip_cubic_tap(int32_t u, float s
     t.b = mip_bound((int32_t)srcB, source - 1, wrap);
     t.x = srcB - (float)t.b;
     return t;
+}
+
+// ---- the free-size chain (ITW_MIP_RESIZE; resize.hip): the same per-axis arithmetic at any (source, dest) pair ------------------------------
+
+// how one axis is addressed past its ends: bounduvw's three cases, wrap before mirror
+enum MipAddress : uint32_t { MIP_ADDR_CLAMP = 0, MIP_ADDR_WRAP = 1, MIP_ADDR_MIRROR = 2 };
+
+// bounduvw as written (Filters.h:123-153): wrap folds one period, mirror reflects about the edge, then the clamp
+__host__ __device__ __forceinline__ int32_t mip_bound_addr(int32_t u, int32_t maxu, uint32_t addr)
+{
+    if (addr == MIP_ADDR_WRAP) {
+        if (u < 0) u = maxu + u + 1;
+        else if (u > maxu) u = u - maxu - 1;
+    } else if (addr == MIP_ADDR_MIRROR) {
+        if (u < 0) u = (-u) - 1;
+        else if (u > maxu) u = maxu - (u - maxu - 1);
+    }
+    u = u < maxu ? u : maxu;
+    return u > 0 ? u : 0;
+}
+
+// one axis of _CreateCubicFilter under any addressing; (int32_t)srcB truncates toward zero, so an upscale's first texels have x < 0
+__host__ __device__ __forceinline__ MipCubicTap mip_cubic_tap_addr(int32_t u, float scale, int32_t source, uint32_t addr)
+{
+    const float srcB = ((float)u + 0.5f) * scale - 0.5f;
+    MipCubicTap t;
+    t.b = mip_bound_addr((int32_t)srcB, source - 1, addr);
+    t.x = srcB - (float)t.b;
+    return t;
+}
+
+// one axis of _CreateLinearFilter as written (Filters.h:66-102), its wrap branches included: weight0 is formed from isrcB AFTER the fold.
+// The two last lines change nothing the reference computes: they keep a read inside the row where fp32 no longer holds the coordinate.
+__host__ __device__ __forceinline__ MipTap mip_linear_tap_wrap(int32_t u, float scale, int32_t source, bool wrap)
+{
+    const float srcB = ((float)u + 0.5f) * scale + 0.5f;
+    int32_t b = (int32_t)srcB;
+    int32_t a = b - 1;
+    if (a < 0) a = wrap ? source - 1 : 0;
+    if (b >= source) b = wrap ? 0 : source - 1;
+    if (a >= source) a = source - 1;
+    if (b < 0) b = 0;
+    MipTap t;
+    t.u0 = a; t.u1 = b;
+    t.w0 = 1.0f + (float)b - srcB;
+    t.w1 = 1.0f - t.w0;
+    return t;
+}
+
+// _ResizePointFilter's step along one axis, (source << 16) / dest in 64 bits, and the source index of destination u: the reference's
+// running sum sx += inc is the product u * inc, and (u * inc) >> 16 < source for every u < dest
+__host__ __device__ __forceinline__ uint64_t mip_point_step(int32_t source, int32_t dest) { return ((uint64_t)source << 16) / (uint64_t)dest; }
+__host__ __device__ __forceinline__ int32_t mip_point_index(int32_t u, uint64_t step, int32_t source)
+{
+    const int32_t s = (int32_t)(((uint64_t)u * step) >> 16);
+    return s < source ? s : source - 1;
 }
 
 // CUBIC_INTERPOLATE on one channel, in C++ operator order

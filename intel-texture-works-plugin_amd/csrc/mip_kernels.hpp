@@ -263,19 +263,34 @@ void launch_coverage(const MipImage* table, int items, int levels, int w, int h,
 // ---- mip_filters.hip: ITW_MIP_CUBIC / ITW_MIP_TRIANGLE, one filter on every level, one launch per level ------------------------------------
 
 // a call's filter as its checks left it: kind is mip_filters.hpp's MipFilterKind (0: the default's box or linear, and wrap changes nothing)
-struct MipFilter { int kind = 0; bool wrap_u = false, wrap_v = false; };
+// resize: the chain's level sizes are the caller's (ITW_MIP_RESIZE), kind may then be point or linear too and mirror_u / _v may be set
+struct MipFilter { int kind = 0; bool wrap_u = false, wrap_v = false, resize = false, mirror_u = false, mirror_v = false; };
 
 // The triangle filter's gather lists of every level and both axes, built on the host: `words` goes to the device behind the chain's image
 // table, in the same upload; x_off[l] / y_off[l] are where level l's lists start in it, repeats[l] whether one source reaches one
 // destination twice in either (mip_filters.hpp mip_triangle_gather).  Nothing for the other kinds.
 struct MipTapPlan {
     std::vector<uint32_t> words, x_off, y_off, repeats;
-    int built_for[5] = { 0, 0, 0, 0, 0 };                                // levels, w, h, wrap_u, wrap_v of the lists `words` holds
-    size_t build(const MipFilter& f, int levels, int w, int h);          // returns the bytes of `words`
+    std::vector<int> built_for;                                         // wrap_u, wrap_v, then every level's width and height: what `words` holds
+    size_t build(const MipFilter& f, int levels, const int* lw, const int* lh);   // lw[l] x lh[l]: level l's size; returns the bytes of `words`
 };
 
 // the launches of one filtered chain, any texel kind: `table` and `taps` (the plan's words; unused by the cubic filter) are on the device
 void launch_chain_filtered(const MipImage* table, const uint32_t* taps, const MipTapPlan& plan, const MipFilter& f, int items, int levels, int w, int h, int px,
                            bool srgb, hipStream_t st);
+
+// one level of the triangle filter's gather over any (source, dest) pair: level l (ow x oh) of every item from its level l - 1
+void launch_triangle_level(const MipImage* table, const uint32_t* taps, const MipTapPlan& plan, int items, int levels, int l, int ow, int oh, int px, bool srgb,
+                           hipStream_t st);
+
+// ---- resize.hip: ITW_MIP_RESIZE, a chain whose level sizes are the caller's ------------------------------------------------------------------
+
+// The filter of the level pair (sw x sh) -> (ow x oh) under `f`: f.kind, or for the default DirectX::Resize's choice, box at exactly 2:1
+// on both axes and linear otherwise (_PerformResizeUsingCustomFilters).  Returns a MipFilterKind.
+int resize_pair_filter(const MipFilter& f, int sw, int sh, int ow, int oh);
+
+// the launches of one free-size chain, any texel kind, one per level: lw[l] x lh[l] is level l's size, `taps` as launch_chain_filtered's
+void launch_chain_resized(const MipImage* table, const uint32_t* taps, const MipTapPlan& plan, const MipFilter& f, int items, int levels, const int* lw,
+                          const int* lh, int px, bool srgb, hipStream_t st);
 
 } // namespace itw

@@ -150,11 +150,13 @@ void generate_chain(const rgba_surface* im, int items, int levels, int px, bool 
     hipStream_t st = (hipStream_t)itwGetStream();
     const int count = items * levels;
     const int w = im[0].width, h = im[0].height;
+    int lw[32], lh[32];                                                   // every level's size, as the checks left item 0's (levels <= 32 in either kind of chain)
+    for (int l = 0; l < levels; l++) { lw[l] = im[l].width; lh[l] = im[l].height; }
     // what one upload carries: the image table, then the triangle filter's lists (mip_filters.hip) 256-B aligned behind it
     static thread_local std::vector<uint8_t> head;                        // grow-only, like the device buffer it is copied into
     static thread_local itw::MipTapPlan taps;
     const size_t table_bytes = (size_t)count * sizeof(itw::MipImage), taps_off = itw::up256(table_bytes);
-    const size_t taps_bytes = taps.build(filter, levels, w, h), head_bytes = taps_bytes ? taps_off + taps_bytes : table_bytes;
+    const size_t taps_bytes = taps.build(filter, levels, lw, lh), head_bytes = taps_bytes ? taps_off + taps_bytes : table_bytes;
     head.resize(head_bytes);
     if (taps_bytes) std::memcpy(head.data() + taps_off, taps.words.data(), taps_bytes);
     itw::MipImage* desc = reinterpret_cast<itw::MipImage*>(head.data());
@@ -166,7 +168,8 @@ void generate_chain(const rgba_surface* im, int items, int levels, int px, bool 
     for (int i = 0; i < count; i += levels) itw::upload_image(plan, base, i, st);                                     // only the bases go up
     ITW_CHECK(hipMemcpyAsync(base, head.data(), head_bytes, hipMemcpyHostToDevice, st));
     const itw::MipImage* table = reinterpret_cast<const itw::MipImage*>(base);
-    if (filter.kind)  itw::launch_chain_filtered(table, reinterpret_cast<const uint32_t*>(base + taps_off), taps, filter, items, levels, w, h, px, srgb, st);
+    if (filter.resize) itw::launch_chain_resized(table, reinterpret_cast<const uint32_t*>(base + taps_off), taps, filter, items, levels, lw, lh, px, srgb, st);
+    else if (filter.kind)  itw::launch_chain_filtered(table, reinterpret_cast<const uint32_t*>(base + taps_off), taps, filter, items, levels, w, h, px, srgb, st);
     else if (alpha.weight) itw::launch_chain_weighted(table, items, levels, w, h, srgb, per_level, st);              // (RGBA8: the entry point takes no other)
     else if (srgb)    launch_plain_chain<4, true>(table, items, levels, w, h, per_level, st);                        // (the entry point refused it with px 8)
     else if (px == 4) launch_plain_chain<4, false>(table, items, levels, w, h, per_level, st);
@@ -206,12 +209,23 @@ AlphaRules check_alpha(const char* who, const itw_mip_alpha* alpha, itw_mip_cove
 
 // The flag bits of a call, after the alpha checks: `what` is "flag" or "mip flag" as the entry point's messages have it.  Returns the filter.
 constexpr uint32_t kMipFlags = ITW_MIP_PER_LEVEL | ITW_MIP_SRGB | ITW_MIP_CUBIC | ITW_MIP_TRIANGLE | ITW_MIP_WRAP_U | ITW_MIP_WRAP_V;
-itw::MipFilter check_filter_flags(const char* who, const char* what, uint32_t flags, const AlphaRules& alpha)
+// the bits of the free-size chain: itwGenerateMipChain alone takes them (`resize_call`), every other call refuses them as unknown
+constexpr uint32_t kResizeFlags = ITW_MIP_RESIZE | ITW_MIP_POINT | ITW_MIP_LINEAR | ITW_MIP_MIRROR_U | ITW_MIP_MIRROR_V;
+itw::MipFilter check_filter_flags(const char* who, const char* what, uint32_t flags, const AlphaRules& alpha, bool resize_call = false)
 {
-    if (flags & ~kMipFlags) itw::fail_msg("%s: unknown %s bits 0x%x", who, what, flags);
+    if (flags & ~(kMipFlags | (resize_call ? kResizeFlags : 0u))) itw::fail_msg("%s: unknown %s bits 0x%x", who, what, flags);
     itw::MipFilter f;
     if ((flags & ITW_MIP_CUBIC) && (flags & ITW_MIP_TRIANGLE)) itw::fail_msg("%s: ITW_MIP_CUBIC and ITW_MIP_TRIANGLE together: a chain takes one filter", who);
-    f.kind = (flags & ITW_MIP_CUBIC) ? itw::MIP_FILTER_CUBIC : (flags & ITW_MIP_TRIANGLE) ? itw::MIP_FILTER_TRIANGLE : itw::MIP_FILTER_DEFAULT;
+    const uint32_t named = flags & (ITW_MIP_POINT | ITW_MIP_LINEAR | ITW_MIP_CUBIC | ITW_MIP_TRIANGLE);
+    if (named & (named - 1))
+        itw::fail_msg("%s: two filter bits together (0x%x): a chain takes one of ITW_MIP_POINT, ITW_MIP_LINEAR, ITW_MIP_CUBIC and ITW_MIP_TRIANGLE", who, named);
+    if (!(flags & ITW_MIP_RESIZE) && (flags & kResizeFlags))
+        itw::fail_msg("%s: ITW_MIP_%s without ITW_MIP_RESIZE: the point and linear filters by name and mirror addressing are the free-size chain's", who,
+                      (flags & ITW_MIP_POINT) ? "POINT" : (flags & ITW_MIP_LINEAR) ? "LINEAR" : "MIRROR_U / _V");
+    f.resize = (flags & ITW_MIP_RESIZE) != 0;
+    f.mirror_u = (flags & ITW_MIP_MIRROR_U) != 0; f.mirror_v = (flags & ITW_MIP_MIRROR_V) != 0;
+    f.kind = (flags & ITW_MIP_CUBIC) ? itw::MIP_FILTER_CUBIC : (flags & ITW_MIP_TRIANGLE) ? itw::MIP_FILTER_TRIANGLE
+           : (flags & ITW_MIP_POINT) ? itw::MIP_FILTER_POINT : (flags & ITW_MIP_LINEAR) ? itw::MIP_FILTER_LINEAR : itw::MIP_FILTER_DEFAULT;
     if (f.kind && alpha.weight)
         itw::fail_msg("%s: weight_colour with ITW_MIP_%s: a quotient of sums with negative weights is no average, and the weighted triangle kind is not built", who,
                       f.kind == itw::MIP_FILTER_CUBIC ? "CUBIC" : "TRIANGLE");
@@ -223,6 +237,35 @@ itw::MipFilter check_filter_flags(const char* who, const char* what, uint32_t fl
 void check_coverage_size(const char* who, int w, int h)
 {
     if ((int64_t)w * h > ((int64_t)1 << 31)) itw::fail_msg("%s: coverage over a base of %d x %d: more than 2^31 texels", who, w, h);
+}
+
+// The image checks of a free-size chain (ITW_MIP_RESIZE; levels >= 2, items >= 1): every level any size >= 1, one size per level across
+// the items, every written level within one launch, and no level pair that would take the linear filter's wrap branches on a growing axis.
+void check_resized_chain(const char* who, const rgba_surface* images, int items, int levels, int pixel_size, const itw::MipFilter& filter)
+{
+    if (levels > 32) itw::fail_msg("%s: %d levels under ITW_MIP_RESIZE (2 .. 32)", who, levels);
+    if (items > 65535) itw::fail_msg("%s: %d items are more than one launch covers (65 535)", who, items);
+    for (int i = 0; i < items * levels; i++) {
+        const rgba_surface& s = images[i];
+        const int item = i / levels, l = i % levels;
+        const itw::ImageFaultKind fault = itw::image_fault(s, pixel_size, pixel_size);          // null texels come before the sizes, the rest after
+        if (fault == itw::IMAGE_NULL_TEXELS) itw::fail_image(who, fault, s, pixel_size, pixel_size, "item %d level %d", item, l);
+        if (s.width < 1 || s.height < 1) itw::fail_msg("%s: item %d level %d is %d x %d: a level has at least one texel", who, item, l, s.width, s.height);
+        if (s.width != images[l].width || s.height != images[l].height)
+            itw::fail_msg("%s: item %d level %d is %d x %d, that of item 0 %d x %d: a level has one size across the items", who, item, l, s.width, s.height,
+                          images[l].width, images[l].height);
+        if (fault) itw::fail_image(who, fault, s, pixel_size, pixel_size, "item %d level %d", item, l);
+    }
+    for (int l = 1; l < levels; l++) {
+        const int sw = images[l - 1].width, sh = images[l - 1].height, ow = images[l].width, oh = images[l].height;
+        if (oh > 4 * 65535) itw::fail_msg("%s: level %d of %d rows is more than one launch covers (262 140)", who, l, oh);
+        if (itw::resize_pair_filter(filter, sw, sh, ow, oh) != itw::MIP_FILTER_LINEAR) continue;
+        const bool grows_u = filter.wrap_u && ow >= sw && sw > 1, grows_v = filter.wrap_v && oh >= sh && sh > 1;
+        if (grows_u || grows_v)
+            itw::fail_msg("%s: level %d takes the linear filter with ITW_MIP_WRAP_%s where %d texels become %d: the reference forms that axis's last weights "
+                          "from the folded index (4 -> 8 ends in r[3] * -3.25 + r[0] * 4.25); ITW_MIP_CUBIC and ITW_MIP_TRIANGLE wrap at any ratio",
+                          who, l, grows_u ? "U" : "V", grows_u ? sw : sh, grows_u ? ow : oh);
+    }
 }
 
 } // namespace
@@ -308,19 +351,25 @@ namespace {
 
 // itwGenerateMipChain and itwGenerateMipChainAlpha: one set of checks, `who` names the entry point in every message
 int generate_checked(const char* who, const rgba_surface* images, int items, int levels, int pixel_size, uint32_t flags, const itw_mip_alpha* alpha_in,
-                     itw_mip_coverage* report)
+                     itw_mip_coverage* report, bool resize_call)
 {
     bool dev = false;
     itw::clear_failure();
     const bool ok = itw::guarded([&] {
         const AlphaRules alpha = check_alpha(who, alpha_in, report);
         if (pixel_size != 4 && pixel_size != 8) itw::fail_msg("%s: pixel_size %d (4: RGBA8, 8: RGBA16F)", who, pixel_size);
-        const itw::MipFilter filter = check_filter_flags(who, "flag", flags, alpha);
+        const itw::MipFilter filter = check_filter_flags(who, "flag", flags, alpha, resize_call);
         if ((flags & ITW_MIP_SRGB) && pixel_size != 4) itw::fail_msg("%s: ITW_MIP_SRGB is for RGBA8 texels (pixel_size 4): RGBA16F is linear already", who);
         if (items < 0) itw::fail_msg("%s: %d items", who, items);
         if (items == 0 || levels <= 1) return;
         if (!images) itw::fail_msg("%s: null images pointer", who);
         if ((int64_t)items * levels > (int64_t)0x7fffffff / 64) itw::fail_msg("%s: %d items of %d levels", who, items, levels);
+        if (filter.resize) {                                                  // the level sizes are the caller's: "Mip chains: free sizes"
+            check_resized_chain(who, images, items, levels, pixel_size, filter);
+            dev = itw::all_one_pointer_kind(who, "image", images, items * levels);
+            generate_chain(images, items, levels, pixel_size, (flags & ITW_MIP_SRGB) != 0, false, dev, alpha, filter);
+            return;
+        }
         const int w = images[0].width, h = images[0].height, full = itwMipLevels(w, h);
         if (full == 0) itw::fail_msg("%s: the base is %d x %d", who, w, h);
         if (levels > full) itw::fail_msg("%s: %d levels, a full chain of %d x %d has %d", who, levels, w, h, full);
@@ -347,12 +396,12 @@ int generate_checked(const char* who, const rgba_surface* images, int items, int
 
 extern "C" int itwGenerateMipChain(const rgba_surface* images, int items, int levels, int pixel_size, uint32_t flags)
 {
-    return generate_checked("itwGenerateMipChain", images, items, levels, pixel_size, flags, nullptr, nullptr);
+    return generate_checked("itwGenerateMipChain", images, items, levels, pixel_size, flags, nullptr, nullptr, true);
 }
 
 extern "C" int itwGenerateMipChainAlpha(const rgba_surface* images, int items, int levels, uint32_t flags, const itw_mip_alpha* alpha, itw_mip_coverage* report)
 {
-    return generate_checked("itwGenerateMipChainAlpha", images, items, levels, 4, flags, alpha, report);
+    return generate_checked("itwGenerateMipChainAlpha", images, items, levels, 4, flags, alpha, report, false);
 }
 
 // the sRGB colour kind on the host (include/itw_dispatch.h): the tables of srgb_tables.h, E as the counting definition's binary search

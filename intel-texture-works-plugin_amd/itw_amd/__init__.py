@@ -22,7 +22,8 @@ from .abi import (  # noqa: F401
     compress_chain_refined, compress_chain_refined_to, chain_psnr_to_total_sse,
     NORMAL_FLIP_X, NORMAL_FLIP_Y, NORMAL_NORMALIZE, normal_ops, prepare_normal_map, compress_normal_map, quantize_normal_map, compress_normal_map_snorm, compress_chain_normal_snorm, compress_mipped_normal_snorm, cube_cross_faces,
     NORMAL_FROM_HEIGHT, HEIGHT_CHANNEL, HEIGHT_MIRROR_U, HEIGHT_MIRROR_V, HEIGHT_INVERT_SIGN, HEIGHT_OCCLUSION, height_ops, height_amplitude, height_to_normal,
-    MIP_PER_LEVEL, MIP_SRGB, MIP_CUBIC, MIP_TRIANGLE, MIP_WRAP_U, MIP_WRAP_V, mip_filter_flags, mip_levels, mip_chain_layout, generate_mips, generate_mips_into, compress_mipped,
+    MIP_PER_LEVEL, MIP_SRGB, MIP_CUBIC, MIP_TRIANGLE, MIP_WRAP_U, MIP_WRAP_V, MIP_RESIZE, MIP_POINT, MIP_LINEAR, MIP_MIRROR_U, MIP_MIRROR_V, mip_filter_flags,
+    resize_flags, fit_size, resize, resize_chain_into, mip_levels, mip_chain_layout, generate_mips, generate_mips_into, compress_mipped,
     srgb_to_linear, linear_to_srgb, srgb_encode_device,
     MipAlpha, MipCoverage, alpha_coverage,
 )

@@ -43,7 +43,7 @@ EXPORTED_SYMBOLS = tuple(
 TEST_HOOK_SYMBOLS = ("itwTestRcp", "itwTestRsqrt", "itwTestF2I", "itwTestBc7TwoSubsetBounds", "itwTestBc7RotationBounds", "itwTestBc7F02Scan", "itwTestBc45IndexTable", "itwTestBc45ClosestS",
                      "itwMultiGpuTestInjectFailure", "itwTestCombinerHold", "itwTestCombinerCounters", "itwTestBc7RouteCounters", "itwTestBc7RouteCountersReset",
                      "itwTestBc7CallCountersArm", "itwTestBc7CallCounters", "itwTestSrgbEncode", "itwTestAlphaHistVariant", "itwTestMipCubicVariant",
-                     "itwTestMipFilterTable")
+                     "itwTestMipFilterTable", "itwTestResizeTable")
 # enum itw_test_bc7_call_counter (include/itw_test_hooks.h): what itwTestBc7CallCounters fills; the per-band ones are band 0 then band 1
 BC7_CALL_COUNTERS = ("pilot_listed", "pilot_sampled", "pilot_flag", "rot00", "rot01", "rot02", "rot10", "rot11", "rot12", "listed0", "listed1",
                      "pairs0", "pairs1", "overflow0", "overflow1", "redo0", "redo1")
@@ -377,6 +377,8 @@ def _load(path, hooks):
             L.itwTestMipCubicVariant.restype = None
             L.itwTestMipFilterTable.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64]
             L.itwTestMipFilterTable.restype = C.c_int64
+            L.itwTestResizeTable.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64]
+            L.itwTestResizeTable.restype = C.c_int64
         # dispatch layer (itw_dispatch.h)
         L.GetProcessorCount.restype = C.c_int
         L.GetBytesPerBlock.argtypes = [C.c_int]
@@ -1262,9 +1264,116 @@ def generate_mips_into(chains, per_level=False, srgb=False, alpha_weight=False, 
     return chains
 
 
+MIP_RESIZE = 0x200    # ITW_MIP_RESIZE: the chain's level sizes are the caller's ("Mip chains: free sizes"); itwGenerateMipChain only
+MIP_POINT = 0x400     # ITW_MIP_POINT / ITW_MIP_LINEAR: DirectX::Resize's point and linear filters by name (with ITW_MIP_RESIZE)
+MIP_LINEAR = 0x800
+MIP_MIRROR_U = 0x1000  # ITW_MIP_MIRROR_U / _V: the cubic filter mirrors the source about its edges along x / y (with ITW_MIP_RESIZE)
+MIP_MIRROR_V = 0x2000
+
+
+def resize_flags(filter=None, wrap="", mirror="", srgb=False):
+    """The ITW_MIP_* bits of a free-size chain: ITW_MIP_RESIZE, filter=None | "point" | "linear" | "cubic" | "triangle", wrap and mirror
+    each "" | "u" | "v" | "uv", and ITW_MIP_SRGB."""
+    kinds = {None: 0, "point": MIP_POINT, "linear": MIP_LINEAR, "cubic": MIP_CUBIC, "triangle": MIP_TRIANGLE}
+    if filter not in kinds:
+        raise ValueError(f"filter {filter!r} (None, 'point', 'linear', 'cubic' or 'triangle')")
+    for name, axes in (("wrap", wrap), ("mirror", mirror)):
+        if axes not in ("", "u", "v", "uv"):
+            raise ValueError(f"{name} {axes!r} ('', 'u', 'v' or 'uv')")
+    return (MIP_RESIZE | kinds[filter] | (MIP_WRAP_U if "u" in wrap else 0) | (MIP_WRAP_V if "v" in wrap else 0)
+            | (MIP_MIRROR_U if "u" in mirror else 0) | (MIP_MIRROR_V if "v" in mirror else 0) | (MIP_SRGB if srgb else 0))
+
+
+def fit_size(w, h, rule, max_size=16384):
+    """The size a w x h source is fitted to before its chain is made; host arithmetic only.  rule "pow2": texconv's FitPowerOf2 restated --
+    the longer axis becomes the largest of max_size, max_size / 2, ... that is <= itself, the other the one of them whose ratio to it is
+    nearest the source's aspect in fp32, the larger on a tie; "pow2_up": the next power of two per axis; "multiple4": each axis rounded up
+    to a multiple of 4.  The last two are capped at max_size."""
+    w, h = int(w), int(h)
+    if w < 1 or h < 1 or max_size < 1:
+        raise ValueError(f"fit_size: {w} x {h}, max_size {max_size}")
+    if rule == "pow2_up":
+        return tuple(min(max_size, 1 << (v - 1).bit_length()) for v in (w, h))
+    if rule == "multiple4":
+        return tuple(min(max_size, (v + 3) // 4 * 4) for v in (w, h))
+    if rule != "pow2":
+        raise ValueError(f"fit rule {rule!r} ('pow2', 'pow2_up' or 'multiple4')")
+    import numpy as np
+    f32 = np.float32
+    aspect = f32(w) / f32(h)
+
+    def below(v):                                    # max_size halved until it is <= v (1 at the least)
+        x = max_size
+        while x > 1 and x > v:
+            x >>= 1
+        return x
+
+    def other(score_of):                             # max_size halved down to 1: the first strictly best score wins, so the larger on a tie
+        best, best_score, x = None, None, max_size
+        while x > 0:
+            s = abs(score_of(x) - aspect)
+            if best_score is None or s < best_score:
+                best, best_score = x, s
+            x >>= 1
+        return best
+
+    if w > h:
+        nw = below(w)
+        return nw, other(lambda y: f32(nw) / f32(y))
+    nh = below(h)
+    return other(lambda x: f32(x) / f32(nh)), nh
+
+
+def _like(img, h, w):
+    if hasattr(img, "data_ptr"):
+        import torch
+        return torch.empty((h, w, 4), dtype=img.dtype, device=img.device)
+    import numpy as np
+    return np.empty((h, w, 4), dtype=img.dtype)
+
+
+def resize(image_or_images, size=None, fit=None, filter=None, wrap="", mirror="", srgb=False, out=None):
+    """DirectX::Resize on the device (itwGenerateMipChain with ITW_MIP_RESIZE, a chain of two levels): one image or a list of equally sized
+    ones -- host numpy arrays or CUDA torch tensors (H, W, 4), uint8 (RGBA8) or 2-byte elements (RGBA16F half bits), as generate_mips takes
+    them -- to size=(w, h), or to fit_size(w, h, fit) with fit="pow2" | "pow2_up" | "multiple4".  filter=None is the reference's default (box
+    at exactly 2:1, else linear); "point", "linear", "cubic", "triangle" name one.  wrap / mirror: "" | "u" | "v" | "uv"; mirror is read by
+    the cubic filter, and linear with wrap on a growing axis is refused (include/itw_dispatch.h, "Mip chains: free sizes").  srgb (uint8
+    only) filters R, G, B in linear light.  out: the target or list of targets, which may be strided views.  Returns the resized image, or
+    the list of them.  Device tensors: asynchronous on torch's current stream."""
+    single = hasattr(image_or_images, "shape")
+    imgs = [image_or_images] if single else list(image_or_images)
+    assert imgs, "no image"
+    h, w = imgs[0].shape[:2]
+    if (size is None) == (fit is None):
+        raise ValueError("resize: give size=(w, h) or fit=, one of them")
+    tw, th = fit_size(w, h, fit) if size is None else (int(size[0]), int(size[1]))
+    outs = [_like(img, th, tw) for img in imgs] if out is None else ([out] if hasattr(out, "shape") else list(out))
+    resize_chain_into([[img, o] for img, o in zip(imgs, outs)], filter=filter, wrap=wrap, mirror=mirror, srgb=srgb)
+    return outs[0] if single else outs
+
+
+_resize_images = resize       # (compress_mipped has a parameter of that name)
+
+
+def resize_chain_into(chains, filter=None, wrap="", mirror="", srgb=False):
+    """itwGenerateMipChain with ITW_MIP_RESIZE over caller-made levels: `chains` is a list of items, each the list of its 2 .. 32 levels
+    (level 0 filled in), of any sizes -- level l alike across the items -- which may be strided views of larger arrays / tensors.  Level l
+    is filtered from level l-1 as stored.  Raises ValueError where the call returns -1.  Options as resize takes them."""
+    flat = [lv for ch in chains for lv in ch]
+    on_device = hasattr(flat[0], "data_ptr")
+    es = flat[0].element_size() if on_device else flat[0].itemsize
+    assert es in (1, 2), "uint8 or half texels"
+    if on_device:
+        import torch
+        lib().itwSetStream(torch.cuda.current_stream(flat[0].device).cuda_stream)
+    if lib().itwGenerateMipChain(C.cast(_surfaces(flat), C.c_void_p), len(chains), len(chains[0]), 4 * es, resize_flags(filter, wrap, mirror, srgb)) != 0:
+        raise ValueError("itwGenerateMipChain refused the call: " + (last_error() or "bad arguments"))
+    return chains
+
+
 @_encodes
 def compress_mipped(fmt, base_or_bases, levels=0, profile=None, settings=None, normal_ops=0, progress=None, out=None, srgb=False,
-                    alpha_weight=False, alpha_coverage=0, filter=None, wrap="", report=False):
+                    alpha_weight=False, alpha_coverage=0, filter=None, wrap="", report=False, resize=None, resize_filter=None):
     """itwCompressImageMipped: the save path from base images in one call -- flips of `normal_ops` on level 0, the mip chain, the normalise on
     every level, then the chain encoder.  One base or a list of equally sized ones (numpy arrays or CUDA torch tensors, as compress_chain
     takes them); levels == 0: the full chain.  srgb: the chain's colour is filtered in linear light (itwCompressImageMippedEx with
@@ -1272,10 +1381,16 @@ def compress_mipped(fmt, base_or_bases, levels=0, profile=None, settings=None, n
     (itwCompressImageMippedAlpha; no normal_ops with them).  filter / wrap: the chain's filter, as generate_mips takes them
     (itwCompressImageMippedEx with ITW_MIP_CUBIC / _TRIANGLE / _WRAP_*).  Returns (ok, blocks): the DDS payload, item-major then level.
     report=True (with the alpha rules): (ok, blocks, rows), rows the MipCoverage list of the same chain in DDS order -- the encode call has no
-    report of its own, so the chain is generated once more for it (generate_mips with the same options, which is deterministic)."""
+    report of its own, so the chain is generated once more for it (generate_mips with the same options, which is deterministic).
+    resize=(w, h) | "pow2" | "pow2_up" | "multiple4" first fits every base to that size with resize(..., filter=resize_filter, wrap=wrap,
+    srgb=srgb) and hands the result on.  The two stages are not fused: from host arrays the resized bases come back to the host and go up
+    again with the save call, a second transfer; pass CUDA tensors to keep both stages resident."""
     import numpy as np
     single = hasattr(base_or_bases, "shape")
     bases = [base_or_bases] if single else list(base_or_bases)
+    if resize is not None:
+        bases = _resize_images(bases, fit=resize, filter=resize_filter, wrap=wrap, srgb=srgb) if isinstance(resize, str) \
+            else _resize_images(bases, size=resize, filter=resize_filter, wrap=wrap, srgb=srgb)
     base = _base(fmt)
     for img in bases:
         _check_texel_type(fmt, img)

@@ -10,8 +10,9 @@ Rows (one JSON object per line; stdout, and appended to profiles/mip_filter_timi
   2d_4000x3000_rgba16f                                    `per_level` is the linear filter (flags 0), then the same filter legs
 Every leg also as a multiple of the row's per_level median, and as a share of 8 TB/s over `bytes_per_level`: every level but the last read
 once and every level but the base written once, what the per-level route moves.
---parent-lib=PATH adds `parent_pyramid` / `parent_per_level` legs to every row: the flags-0 and ITW_MIP_PER_LEVEL calls through another
-build of libispc_texcomp.so (the parent commit's), alternating with this build's in the same run.
+--parent-lib=PATH adds `parent_pyramid` / `parent_per_level` / `parent_cubic` / `parent_triangle` legs to every row: the flags-0,
+ITW_MIP_PER_LEVEL, ITW_MIP_CUBIC and ITW_MIP_TRIANGLE calls through another build of libispc_texcomp.so (the parent commit's, whose
+cubic kernel is its default's, the one `cubic_global` runs), alternating with this build's in the same run.
 Usage: python tools/mip_filter_timing.py [reps] [inner] [--label=TEXT] [--no-save] [--out=PATH] [--only=SUBSTRING] [--parent-lib=PATH]"""
 import ctypes as C
 import json
@@ -125,6 +126,7 @@ def main():
             legs.append(("parent_per_level", checked(parent, arr, items, n, px, itw_amd.MIP_PER_LEVEL if box else 0)))
             if box:
                 legs.append(("parent_pyramid", checked(parent, arr, items, n, px, 0)))
+            legs += [("parent_cubic", checked(parent, arr, items, n, px, itw_amd.MIP_CUBIC)), ("parent_triangle", checked(parent, arr, items, n, px, itw_amd.MIP_TRIANGLE))]
         row = {"row": name, "width": w, "height": h, "items": items, "levels": n, "pixel_size": px, "bytes_per_level": traffic,
                "per_level_filter": "box" if box else "linear"}
         try:
