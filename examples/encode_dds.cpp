@@ -7,7 +7,7 @@
 //              [--height r|g|b|a|lum[,mirroru,mirrorv,invert,occlusion] [--height-amplitude <A>]]
 //              [--alpha-weight] [--alpha-coverage <ref>] [--bc-dither rgb|a|rgb,a] [--bc-uniform]
 //              <format> <width> <height> <in.raw> <out.dds> [slice_pixels]
-//     format : bc1 | bc1a[:<alpha_ref>] | bc2 | bc3 | bc4 | bc5 | bc4_snorm | bc5_snorm | bc7_<profile> | bc6h_<profile> | etc1_slow      (profiles: the GetProfile_* names)
+//     format : bc1 | bc1a[:<alpha_ref>] | bc2 | bc3 | bc3_dxtex | bc4 | bc5 | bc4_snorm | bc5_snorm | bc7_<profile> | bc6h_<profile> | etc1_slow      (profiles: the GetProfile_* names)
 //              bc1a: BC1 with 1-bit alpha by DirectXTex's encoder (ITW_FORMAT_BC1A_UNORM, itw_dispatch.h): a texel whose alpha is below <alpha_ref>
 //              (a float, default 0.5) is transparent; --bc-dither and --bc-uniform are its flags (ITW_BC_DITHER_RGB / _A, ITW_BC_UNIFORM).  The file
 //              is a BC1 file (DXGI 71).  It has no trampoline: the slices go through itwCompressImageSlicedEx; goes with --mips, --alpha-weight,
@@ -15,6 +15,10 @@
 //              bc2: BC2 (DXT3: 4 bits of explicit alpha per texel) by DirectXTex's encoder (ITW_FORMAT_BC2_UNORM, itw_dispatch.h); --bc-dither and
 //              --bc-uniform are its flags too; the file is a DXT3 file (DX10 with 74 for an array).  Like bc1a it goes through
 //              itwCompressImageSlicedEx, with --mips, --alpha-weight, --alpha-coverage, --cube-cross, --measure; --refine* and --normal are refused
+//              bc3_dxtex: BC3 by DirectXTex's encoder, D3DXEncodeBC3 (ITW_FORMAT_BC3_DXTEX, itw_dispatch.h) -- the bytes of `texconv -f DXT5`; bc3 stays
+//              kernel.ispc's encoder.  --bc-dither (a: the alpha indices; rgb: the colour half) and --bc-uniform are its flags too; the file is a
+//              DXT5 file (DX10 with 77 for an array), which --decode reads like any other.  Like bc2 it goes through itwCompressImageSlicedEx, with
+//              --mips, --resize, --alpha-weight, --alpha-coverage, --cube-cross, --measure; --refine* and --normal are refused
 //              etc1_slow: DDS has no code for ETC1, so the output is a KTX 1.1 file (itwKtx*, itw_dds.h); the slices go through itwCompressImageSlicedEx
 //              (ETC1 has no trampoline); --refine* is refused: ETC1 has one preset
 //     in.raw : width*height tightly packed RGBA8 texels (RGBA16F bit patterns for bc6h_*; RGBA8_SNORM, int8 codes, for bc4_snorm / bc5_snorm)
@@ -100,6 +104,7 @@ const Format kFormats[] = {
     {"bc1a", nullptr, ITW_FORMAT_BC1A_UNORM, 4, false, 15},                     // no trampoline: itwCompressImageSlicedEx; a DirectXTex format, written as 71
     {"bc2", nullptr, ITW_FORMAT_BC2_UNORM, 4, false, 15},                       // no trampoline either; a DirectXTex format, written as DXT3 / 74
     {"bc3", CompressImageBC3, ITW_DXGI_FORMAT_BC3_UNORM, 4, true, 15},
+    {"bc3_dxtex", nullptr, ITW_FORMAT_BC3_DXTEX, 4, false, 15},                 // no trampoline either; DirectXTex's BC3 encoder, written as DXT5 / 77
     {"bc4", CompressImageBC4, ITW_DXGI_FORMAT_BC4_UNORM, 4, false, 1},      // DirectXTex formats keep partial blocks
     {"bc5", CompressImageBC5, ITW_DXGI_FORMAT_BC5_UNORM, 4, false, 3},
     {"bc4_snorm", CompressImageBC4S, ITW_DXGI_FORMAT_BC4_SNORM, 4, false, 1},   // the raw file's bytes are int8 codes (normal maps)
@@ -137,8 +142,8 @@ bool profile_by_name(bool bc6h, const char* name, void* settings)
     return false;
 }
 
-itw_bc1a_settings g_bc1a = { (uint32_t)sizeof(itw_bc1a_settings), 0.5f, 0, 0 };      // bc1a[:<alpha_ref>] and bc2, --bc-dither, --bc-uniform
-bool takes_bc_settings(int dxgi) { return dxgi == ITW_FORMAT_BC1A_UNORM || dxgi == ITW_FORMAT_BC2_UNORM; }
+itw_bc1a_settings g_bc1a = { (uint32_t)sizeof(itw_bc1a_settings), 0.5f, 0, 0 };      // bc1a[:<alpha_ref>], bc2 and bc3_dxtex, --bc-dither, --bc-uniform
+bool takes_bc_settings(int dxgi) { return dxgi == ITW_FORMAT_BC1A_UNORM || dxgi == ITW_FORMAT_BC2_UNORM || dxgi == ITW_FORMAT_BC3_DXTEX; }
 
 bool on_progress(int done, int total, void*)
 {
@@ -616,14 +621,14 @@ int main(int argc, char** argv)
         return 2;
     }
     const Format* f = nullptr;
-    const bool bc1a = std::strcmp(argv[1], "bc1a") == 0 || std::strncmp(argv[1], "bc1a:", 5) == 0 || std::strcmp(argv[1], "bc2") == 0;      // (takes g_bc1a)
+    const bool bc1a = std::strcmp(argv[1], "bc1a") == 0 || std::strncmp(argv[1], "bc1a:", 5) == 0 || std::strcmp(argv[1], "bc2") == 0 || std::strcmp(argv[1], "bc3_dxtex") == 0;      // (takes g_bc1a)
     if (bc1a && argv[1][3] == 'a' && argv[1][4] == ':') { g_bc1a.alpha_ref = (float)std::atof(argv[1] + 5); argv[1][4] = '\0'; }
     for (const Format& k : kFormats) if (std::strcmp(k.name, argv[1]) == 0) f = &k;
     int width = std::atoi(argv[2]), height = std::atoi(argv[3]);
     if (!f || width < 1 || height < 1) { std::fprintf(stderr, "unknown format or bad size\n"); return 2; }
     const long long slice_pixels = argc > 6 ? std::atoll(argv[6]) : 0;
 
-    if (g_bc1a.flags && !bc1a) { std::fprintf(stderr, "--bc-dither and --bc-uniform are bc1a's flags (and bc2's)\n"); return 2; }
+    if (g_bc1a.flags && !bc1a) { std::fprintf(stderr, "--bc-dither and --bc-uniform are bc1a's flags (and bc2's), and bc3_dxtex's\n"); return 2; }
     if (bc1a && (normal_given || refine_profile)) { std::fprintf(stderr, "%s holds colour and has one encoder: not with --normal or --refine*\n", argv[1]); return 2; }
     if (signed_tb && (normal_given || refine_profile || measure || (f->dxgi != ITW_DXGI_FORMAT_BC4_SNORM && f->dxgi != ITW_DXGI_FORMAT_BC5_SNORM))) {
         std::fprintf(stderr, "--signed-normal is for bc4_snorm / bc5_snorm and does not go with --normal, --refine* or --measure\n");

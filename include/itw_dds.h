@@ -11,6 +11,8 @@
  * with 75.  Read: 'DXT3' and 'DX10' 74 give 0x83F2, 'DX10' 75 gives 0x8C4E; the premultiplied spellings 'DXT2' and 'DXT4' read as BC2 and BC3
  * (77), which is DirectXTex's mapping (DirectXTexDDS.cpp:58-62) -- that the file's alpha is premultiplied is NOT reported: the descriptor has
  * no field for it.  16 bytes per block.
+ * BC3 by DirectXTex's encoder: ITW_FORMAT_BC3_DXTEX = 0x83F3 / ITW_FORMAT_BC3_DXTEX_SRGB = 0x8C4F as descriptor codes write the header of
+ * 77 / 78 ('DXT5', or 'DX10' for an array and for 0x8C4F); a header read back says 77 / 78, as the BC1A codes read back as 71 / 72.
  *
  * Below the DDS functions: the KTX 1.1 container for ETC1 streams (itwKtx*), which DDS cannot carry.
  */
@@ -28,7 +30,7 @@ extern "C" {
 typedef struct ItwDdsDesc {
     uint32_t width, height;     /* top mip, texels */
     uint32_t mip_levels;        /* >= 1 */
-    uint32_t dxgi_format;       /* DXGI_FORMAT_BCn_* value (71,72,77,78,80,81,83,84,95,96,98,99), or one of the BC1A / BC2 codes of itw_dispatch.h */
+    uint32_t dxgi_format;       /* DXGI_FORMAT_BCn_* value (71,72,77,78,80,81,83,84,95,96,98,99), or one of the BC1A / BC2 / BC3_DXTEX codes of itw_dispatch.h */
     uint32_t is_cubemap;        /* 0 / 1: six faces */
     uint32_t array_size;        /* number of textures (cubes when is_cubemap); >= 1 */
 } ItwDdsDesc;

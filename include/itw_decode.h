@@ -31,6 +31,8 @@ extern "C" {
  * block whose base + delta leaves 0..31 (invalid in ETC1; decoded with the sum modulo 32 and counted in reserved_blocks).
  * ITW_FORMAT_BC1A_UNORM / _SRGB (0x83F1 / 0x8C4D, BC1 with 1-bit alpha): synonyms of 71 / 72 in every entry point of this header -- the stream
  * is a BC1 stream, decoded, measured (itw_error_stats.dxgi_format says 71 / 72) and previewed by the same code.
+ * ITW_FORMAT_BC3_DXTEX / _SRGB (0x83F3 / 0x8C4F, BC3 by DirectXTex's encoder): synonyms of 77 / 78 in every entry point of this header -- the
+ * stream is a BC3 stream, decoded, measured (itw_error_stats.dxgi_format says 77 / 78) and previewed by the same code.
  * ITW_FORMAT_BC2_UNORM / _SRGB (0x83F2 / 0x8C4E, BC2 / DXT3): taken by every entry point of this header under these two codes (DXGI's 74 / 75
  * are refused like any unknown code; itw_dispatch.h says why): 16-byte blocks, RGBA8 texels, any size >= 1 in itwDecodeBlocks too (a
  * DirectXTex format, like the BC4 / BC5 group); the colour is always the four-colour palette whatever the order of the endpoints -- BC2 has

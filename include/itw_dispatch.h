@@ -62,6 +62,18 @@ enum {
      * (itwCompressImageSliced / itwCompressImageChain run a caller's function as the literal loop); the refined calls, the multi-GPU calls,
      * the normal-map chain calls, any normal_ops and KTX refuse the codes. */
     ITW_FORMAT_BC2_UNORM = 0x83F2, ITW_FORMAT_BC2_UNORM_SRGB = 0x8C4E,
+    /* BC3 (DXT4 / DXT5) by DirectXTex's encoder, D3DXEncodeBC3 (BC.cpp) as DirectX::Compress calls it -- what `texconv -f DXT5 [-bcdither]
+     * [-bcuniform]` writes, byte for byte -- beside kernel.ispc's CompressBlocksBC3, which stays the encoder of DXGI 77 / 78 at every entry
+     * point.  The codes are the GL enums GL_COMPRESSED_RGBA_S3TC_DXT5_EXT and GL_COMPRESSED_SRGB_ALPHA_S3TC_DXT5_EXT (the second only labels
+     * the stream, like 78).  The stream IS a BC3 stream: the decode, measure and preview entry points of itw_decode.h take the two codes as
+     * synonyms of 77 / 78, itwDds* writes them with the header of 77 / 78 (a file read back says 77 / 78); KTX does not know them.
+     * Encoded, with `settings` = const itw_bc1a_settings* or NULL (below), by itwCompressImageSlicedEx (one slice is the single-image call),
+     * itwCompressImageChainEx and the itwCompressImageMipped* calls (ITW_MIP_SRGB, the filter, wrap and resize bits, weight_colour and
+     * coverage_ref apply: the texels are RGBA8 colour); itwSliceWindow[For], itwChainBytes and GetBytesPerBlock (16) know the codes.  A
+     * DirectXTex format like BC1A and BC2: any size >= 1, partial blocks kept and filled by the {0, 0, 0, 1} rule, the same texel conversion,
+     * no block-level entry point and no CompressImage* trampoline (itwCompressImageSliced / itwCompressImageChain run a caller's function as
+     * the literal loop); the refined calls, the multi-GPU calls, the normal-map chain calls, any normal_ops and KTX refuse the codes. */
+    ITW_FORMAT_BC3_DXTEX = 0x83F3, ITW_FORMAT_BC3_DXTEX_SRGB = 0x8C4F,
     /* The SIGNED reading of a BC6H stream (what a GPU shows for a texture labelled DXGI_FORMAT_BC6H_SF16; DirectXTex's D3DXDecodeBC6HS), by its
      * GL enum, GL_COMPRESSED_RGB_BPTC_SIGNED_FLOAT.  A DECODE code only: itwDecodeBlocks, itwDecodeChain, itwDecodeImage, itwMeasureBlocks,
      * itwMeasureChain and itwPreviewBlocks take it (itw_decode.h).  DXGI 96 keeps every meaning it has at each entry point (the encoder
@@ -82,7 +94,10 @@ enum {
  * A caller who kept alpha-test coverage with coverage_ref = r (itwCompressImageMippedAlpha) passes alpha_ref = (float)r * (1.0f / 255.0f):
  * that is the texel conversion's own expression, so "transparent" is exactly a < r on the integer codes.
  * BC2: the same struct and the same checks.  alpha_ref is checked (finite) but not read -- BC2 has no colour key: D3DXEncodeBC2 calls
- * EncodeBC1(bColorKey = false), always four colours; ITW_BC_DITHER_A diffuses the error of the 4-bit alpha; NULL means flags 0. */
+ * EncodeBC1(bColorKey = false), always four colours; ITW_BC_DITHER_A diffuses the error of the 4-bit alpha; NULL means flags 0.
+ * The two BC3_DXTEX codes: the same struct and the same checks, alpha_ref checked (finite) but not read like BC2's.  ITW_BC_DITHER_A diffuses
+ * the error of the 3-bit alpha indices inside the block (D3DXEncodeBC3 also diffuses where it rounds alpha to 8 bits before it chooses the
+ * endpoints; an RGBA8 source leaves nothing to diffuse there); ITW_BC_DITHER_RGB and ITW_BC_UNIFORM act on the colour half. */
 enum { ITW_BC_DITHER_RGB = 0x10000, ITW_BC_DITHER_A = 0x20000, ITW_BC_UNIFORM = 0x40000 };
 typedef struct itw_bc1a_settings { uint32_t struct_size /* 16 */; float alpha_ref; uint32_t flags, reserved /* 0 */; } itw_bc1a_settings;
 

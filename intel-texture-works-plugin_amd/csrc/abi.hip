@@ -265,7 +265,7 @@ struct Job {
     const bc6h_enc_settings* s6 = nullptr;
     int etc_threshold = 0;      // ETC1 only: fastSkipTreshold, >= 1 (a copy: the caller's etc_enc_settings need not outlive job_of)
     uint32_t normal_ops = 0;    // BC5 only (itwCompressNormalMapBC5): ITW_NORMAL_* applied as the kernel loads its texels; such a job is never offered to the combiner
-    float alpha_ref = 0.5f;     // BC1A, BC2 (which reads the flags only) (slices and chains; no block-level call, so no combiner): the caller's itw_bc1a_settings, copied --
+    float alpha_ref = 0.5f;     // BC1A, BC2 and BC3_DXTEX (which read the flags only) (slices and chains; no block-level call, so no combiner): the caller's itw_bc1a_settings, copied --
     uint32_t bc_flags = 0;      // NULL settings: TEX_THRESHOLD_DEFAULT, no flags
 };
 
@@ -377,6 +377,7 @@ void launch(const Job& j, const uint8_t* d_src, int64_t stride, int w, int h, ui
         break;
     case itw::BCN_BC1A: itw::launch_bc1a(d_src, stride, w, h, d_dst, j.alpha_ref, j.bc_flags, st); break;
     case itw::BCN_BC2:  itw::launch_bc2(d_src, stride, w, h, d_dst, j.bc_flags, st); break;
+    case itw::BCN_BC3DX: itw::launch_bc3_dxtex(d_src, stride, w, h, d_dst, j.bc_flags, st); break;
     }
     ITW_CHECK(hipGetLastError());
 }
@@ -849,8 +850,9 @@ Job job_of(int dxgi_format, const void* settings)
         break;
     }
     case itw::BCN_BC1A:
-    case itw::BCN_BC2: {                                                      // the same struct and checks; BC2 has no colour key: alpha_ref is checked, not read
-        const char* who = j.kind == itw::BCN_BC2 ? "BC2" : "BC1A";
+    case itw::BCN_BC2:
+    case itw::BCN_BC3DX: {                                                    // the same struct and checks; BC2 and BC3 have no colour key: alpha_ref is checked, not read
+        const char* who = j.kind == itw::BCN_BC2 ? "BC2" : j.kind == itw::BCN_BC3DX ? "BC3 (DirectXTex)" : "BC1A";
         const itw_bc1a_settings* sb = static_cast<const itw_bc1a_settings*>(settings);
         if (!sb) break;                                                       // alpha_ref 0.5f, no flags
         if (sb->struct_size != sizeof(itw_bc1a_settings)) itw::fail_msg("%s: itw_bc1a_settings.struct_size %u (16)", who, sb->struct_size);
@@ -1347,7 +1349,7 @@ void chain_check(const rgba_surface* images, int count, const uint8_t* target, i
 {
     alignas(16) static const unsigned char any_settings[sizeof(bc7_enc_settings)] = {0};      // (the caller's own function takes none)
     static const etc_enc_settings any_etc = {1};
-    const void* any = dxgi_format == ITW_FORMAT_ETC1_RGB8 ? (const void*)&any_etc : (format_kind(dxgi_format) == BCN_BC1A || format_kind(dxgi_format) == BCN_BC2) ? nullptr : (const void*)any_settings;
+    const void* any = dxgi_format == ITW_FORMAT_ETC1_RGB8 ? (const void*)&any_etc : (format_kind(dxgi_format) == BCN_BC1A || format_kind(dxgi_format) == BCN_BC2 || format_kind(dxgi_format) == BCN_BC3DX) ? nullptr : (const void*)any_settings;
     (void)chain_job(images, count, target, dxgi_format, any);
 }
 
@@ -1563,6 +1565,7 @@ bool itwCompressNormalMapChain(const rgba_surface* images, int count, uint8_t* t
         itw::check_normal_ops("itwCompressNormalMapChain", ops, "the gather works a texel at a time and has no neighbours");
         if (itw::format_kind(dxgi_format) == itw::BCN_BC1A) itw::fail_msg("itwCompressNormalMapChain: format 0x%X (BC1 with 1-bit alpha) holds colour, not normals", dxgi_format);
         if (itw::format_kind(dxgi_format) == itw::BCN_BC2) itw::fail_msg("itwCompressNormalMapChain: format 0x%X (BC2) holds colour, not normals", dxgi_format);
+        if (itw::format_kind(dxgi_format) == itw::BCN_BC3DX) itw::fail_msg("itwCompressNormalMapChain: format 0x%X (BC3 by DirectXTex's encoder) holds colour, not normals", dxgi_format);
         const Job j = chain_job(images, count, target, dxgi_format, settings);
         done = compress_chain(j, images, count, target, progress, user, ops);
     });

@@ -13,13 +13,15 @@
 
 namespace itw {
 
-enum BcnKind : int { BCN_NONE = 0, BCN_BC1 = 1, BCN_BC2 = 2, BCN_BC3 = 3, BCN_BC4 = 4, BCN_BC5 = 5, BCN_BC6H = 6, BCN_BC7 = 7, BCN_BC4S = 14, BCN_BC5S = 15, BCN_ETC1 = 20, BCN_BC1A = 21, BCN_BC6HS = 22 };
+enum BcnKind : int { BCN_NONE = 0, BCN_BC1 = 1, BCN_BC2 = 2, BCN_BC3 = 3, BCN_BC4 = 4, BCN_BC5 = 5, BCN_BC6H = 6, BCN_BC7 = 7, BCN_BC4S = 14, BCN_BC5S = 15, BCN_ETC1 = 20, BCN_BC1A = 21, BCN_BC6HS = 22, BCN_BC3DX = 23 };
 
 // DXGI format code (or ITW_FORMAT_ETC1_RGB8, ETC1's GL enum: it has no DXGI code; or the two BC1A codes, GL enums likewise) -> kind; BCN_NONE
 // for what the library neither encodes nor decodes.  BCN_BC1A is an ENCODE kind (DirectXTex's colour-key BC1 encoder: partial blocks kept, an
 // itw_bc1a_settings); its stream is a BC1 stream, so the decode side never sees the kind: its entry points read a code through stream_format.
 // BCN_BC2 (DirectXTex's D3DXEncodeBC2: partial blocks kept, the same itw_bc1a_settings) is both an encode and a decode kind, and goes by its two
 // GL enums only: DXGI 74 / 75 stay BCN_NONE at every entry point that takes a format code (they appear inside DDS descriptors and headers alone).
+// BCN_BC3DX (DirectXTex's D3DXEncodeBC3 under ITW_FORMAT_BC3_DXTEX[_SRGB]: 16 bytes, partial blocks kept, the same itw_bc1a_settings) is an ENCODE
+// kind like BCN_BC1A: its stream is a BC3 stream, which the decode side reads as 77 / 78 through stream_format; 77 / 78 stay BCN_BC3, kernel.ispc's encoder.
 // BC6H_SF16 (96) reads as unsigned here: the encoder is the reference's one BC6H encoder for both codes, and the entry points that must not
 // pretend otherwise (itwDecodeChain, itwDecodeImage, itwPreviewBlocks) refuse 96 themselves.  The signed reading of a BC6H stream
 // (D3DXDecodeBC6HS) goes by ITW_FORMAT_BC6H_SIGNED and is a DECODE kind only, BCN_BC6HS: format_kind, which every encode entry point asks, does
@@ -38,18 +40,22 @@ constexpr BcnKind format_kind(int dxgi)
     case ITW_FORMAT_ETC1_RGB8: return BCN_ETC1;
     case ITW_FORMAT_BC1A_UNORM: case ITW_FORMAT_BC1A_UNORM_SRGB: return BCN_BC1A;
     case ITW_FORMAT_BC2_UNORM: case ITW_FORMAT_BC2_UNORM_SRGB: return BCN_BC2;
+    case ITW_FORMAT_BC3_DXTEX: case ITW_FORMAT_BC3_DXTEX_SRGB: return BCN_BC3DX;
     default: return BCN_NONE;
     }
 }
-// the code a stream is decoded, measured, previewed and stored under: the BC1A codes are synonyms of 71 / 72 there
-constexpr int stream_format(int code) { return code == ITW_FORMAT_BC1A_UNORM ? 71 : code == ITW_FORMAT_BC1A_UNORM_SRGB ? 72 : code; }
+// the code a stream is decoded, measured, previewed and stored under: the BC1A codes are synonyms of 71 / 72 there, the BC3_DXTEX codes of 77 / 78
+constexpr int stream_format(int code)
+{
+    return code == ITW_FORMAT_BC1A_UNORM ? 71 : code == ITW_FORMAT_BC1A_UNORM_SRGB ? 72 : code == ITW_FORMAT_BC3_DXTEX ? 77 : code == ITW_FORMAT_BC3_DXTEX_SRGB ? 78 : code;
+}
 // what the decode, measure and preview entry points read a stream_format code as: format_kind, and the signed BC6H reading under its own code
 constexpr BcnKind decode_kind(int code) { return code == ITW_FORMAT_BC6H_SIGNED ? BCN_BC6HS : format_kind(code); }
 constexpr bool is_bc6h(int kind) { return kind == BCN_BC6H || kind == BCN_BC6HS; }           // either reading: 16-byte blocks to RGBA16F texels
 constexpr int block_bytes(int kind) { return (kind == BCN_BC1 || kind == BCN_BC4 || kind == BCN_BC4S || kind == BCN_ETC1 || kind == BCN_BC1A) ? 8 : 16; }
 constexpr int texel_bytes(int kind) { return is_bc6h(kind) ? 8 : 4; }                        // RGBA8 (int8 for the SNORM pair), RGBA16F
 // the DirectXTex formats: their streams keep the partial blocks of a surface that is no multiple of 4 (itw_bc45.h)
-constexpr bool keeps_partial_blocks(int kind) { return kind == BCN_BC4 || kind == BCN_BC5 || kind == BCN_BC4S || kind == BCN_BC5S || kind == BCN_BC1A || kind == BCN_BC2; }
+constexpr bool keeps_partial_blocks(int kind) { return kind == BCN_BC4 || kind == BCN_BC5 || kind == BCN_BC4S || kind == BCN_BC5S || kind == BCN_BC1A || kind == BCN_BC2 || kind == BCN_BC3DX; }
 // the alpha code of a format whose decoder fills alpha in; -1 where alpha is decoded (BC1, BC1A, BC2, BC3, BC7)
 constexpr int filled_alpha(int kind)
 {
@@ -102,7 +108,7 @@ inline void with_kind(int kind, F&& f)
     case BCN_BC6H: f(std::integral_constant<int, BCN_BC6H>{}); break;
     case BCN_BC6HS: f(std::integral_constant<int, BCN_BC6HS>{}); break;
     case BCN_ETC1: f(std::integral_constant<int, BCN_ETC1>{}); break;
-    default: break;                                              // BCN_NONE: every entry point has refused it by now (BCN_BC1A: an encode kind, never decoded)
+    default: break;                                              // BCN_NONE: every entry point has refused it by now (BCN_BC1A, BCN_BC3DX: encode kinds, never decoded)
     }
 }
 

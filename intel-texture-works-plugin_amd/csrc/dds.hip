@@ -19,8 +19,12 @@ constexpr uint32_t fourcc(char a, char b, char c, char d)
     return (uint32_t)(uint8_t)a | ((uint32_t)(uint8_t)b << 8) | ((uint32_t)(uint8_t)c << 16) | ((uint32_t)(uint8_t)d << 24);
 }
 
-// the two BC1A codes (itw_dispatch.h) are stored as what their streams are: BC1, 71 / 72; the two BC2 codes as DXGI's BC2, 74 / 75
-uint32_t stored_format(uint32_t f) { return f == 0x83F1u ? 71u : f == 0x8C4Du ? 72u : f == 0x83F2u ? 74u : f == 0x8C4Eu ? 75u : f; }
+// the two BC1A codes (itw_dispatch.h) are stored as what their streams are: BC1, 71 / 72; the two BC2 codes as DXGI's BC2, 74 / 75; the two
+// BC3_DXTEX codes as what their streams are: BC3, 77 / 78
+uint32_t stored_format(uint32_t f)
+{
+    return f == 0x83F1u ? 71u : f == 0x8C4Du ? 72u : f == 0x83F2u ? 74u : f == 0x8C4Eu ? 75u : f == 0x83F3u ? 77u : f == 0x8C4Fu ? 78u : f;
+}
 // what itwDdsReadHeader reports for a file's own code: BC2 goes by its two codes in a descriptor as everywhere else (74 / 75 as descriptor codes stay refused)
 uint32_t descriptor_format(uint32_t stored) { return stored == 74u ? 0x83F2u : stored == 75u ? 0x8C4Eu : stored; }
 
@@ -153,7 +157,7 @@ size_t itwDdsReadHeader(const uint8_t* src, size_t size, ItwDdsDesc* out)
         d.array_size = get32(e, 3) ? get32(e, 3) : 1;
         off = 148;
     } else return 0;
-    if (d.dxgi_format == 0x83F2u || d.dxgi_format == 0x8C4Eu) return 0;          // (no file holds the library's own codes)
+    if (d.dxgi_format == 0x83F2u || d.dxgi_format == 0x8C4Eu || d.dxgi_format == 0x83F3u || d.dxgi_format == 0x8C4Fu) return 0;          // (no file holds the library's own codes)
     d.dxgi_format = descriptor_format(d.dxgi_format);
     if (!bytes_per_block(d.dxgi_format) || !d.width || !d.height) return 0;
     *out = d;

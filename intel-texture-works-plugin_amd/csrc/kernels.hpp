@@ -23,6 +23,9 @@ void launch_bc1a(const uint8_t* src, int64_t stride, int width, int height, uint
 // BC2 of an RGBA8 surface, DirectXTex's D3DXEncodeBC2 (bc2.hip): ceil(width/4) x ceil(height/4) blocks of 16 bytes, partial blocks filled as
 // BC4 / BC5's; `flags`: ITW_BC_* (itw_dispatch.h).  src and stride 4-byte aligned, dst 16-byte aligned.
 void launch_bc2(const uint8_t* src, int64_t stride, int width, int height, uint8_t* dst, uint32_t flags, hipStream_t st);
+// BC3 of an RGBA8 surface by DirectXTex's D3DXEncodeBC3 (bc3_dxtex.hip; launch_bc3 above is kernel.ispc's encoder): ceil(width/4) x ceil(height/4)
+// blocks of 16 bytes, partial blocks filled as BC4 / BC5's; `flags`: ITW_BC_* (itw_dispatch.h).  src, stride and dst 4-byte aligned.
+void launch_bc3_dxtex(const uint8_t* src, int64_t stride, int width, int height, uint8_t* dst, uint32_t flags, hipStream_t st);
 void launch_bc4s(const uint8_t* src, int64_t stride, int width, int height, uint8_t* dst, hipStream_t st);   // BC4_SNORM / BC5_SNORM of an RGBA8_SNORM surface
 void launch_bc5s(const uint8_t* src, int64_t stride, int width, int height, uint8_t* dst, hipStream_t st);
 // BC5_UNORM of a normal map: the stages `ops` (ITW_NORMAL_*, 1..7; normal_prep.hpp) applied to the texels as the kernel loads them

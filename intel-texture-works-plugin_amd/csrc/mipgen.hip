@@ -491,6 +491,8 @@ bool compress_mipped(const rgba_surface* bases, int items, int levels, uint32_t 
                               : (dxgi_format == 81 || dxgi_format == 84) ? "a signed format takes its heights through itwCompressSignedNormalMapMipped" : nullptr);
         if (normal_ops && itw::format_kind(dxgi_format) == itw::BCN_BC1A)
             itw::fail_msg("itwCompressImageMipped: normal ops 0x%x with format 0x%X (BC1 with 1-bit alpha), which holds colour, not normals", normal_ops, dxgi_format);
+        if (normal_ops && itw::format_kind(dxgi_format) == itw::BCN_BC3DX)
+            itw::fail_msg("itwCompressImageMipped: normal ops 0x%x with format 0x%X (BC3 by DirectXTex's encoder), which holds colour, not normals", normal_ops, dxgi_format);
         if (normal_ops && itw::format_kind(dxgi_format) == itw::BCN_BC2)
             itw::fail_msg("itwCompressImageMipped: normal ops 0x%x with format 0x%X (BC2), which holds colour, not normals", normal_ops, dxgi_format);
         check_filter_flags("itwCompressImageMipped", "mip flag", mip_flags, alpha);

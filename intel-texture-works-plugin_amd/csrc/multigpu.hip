@@ -608,6 +608,7 @@ bool compress_multi(const rgba_surface* input, uint8_t* output, CompressionFunc*
         itw::refuse_signed_bc6h("itwCompressImageMultiGPU", dxgi_format);
         if (itw::format_kind(dxgi_format) == itw::BCN_BC1A) itw::fail_msg("itwCompressImageMultiGPU: format 0x%X (BC1 with 1-bit alpha) has no block-level function to split over ranks", dxgi_format);
         if (itw::format_kind(dxgi_format) == itw::BCN_BC2) itw::fail_msg("itwCompressImageMultiGPU: format 0x%X (BC2) has no block-level function to split over ranks", dxgi_format);
+        if (itw::format_kind(dxgi_format) == itw::BCN_BC3DX) itw::fail_msg("itwCompressImageMultiGPU: format 0x%X (BC3 by DirectXTex's encoder) has no block-level function to split over ranks", dxgi_format);
         std::lock_guard<std::mutex> one(g.submit);
         if (g.wedged) itw::fail_msg("itwCompressImageMultiGPU: a rank thread never returned from an earlier call (watchdog); restart the process");
         Call k;

@@ -6,8 +6,8 @@ _PKG = os.path.dirname(os.path.abspath(__file__))
 _LIB = os.path.normpath(os.path.join(_PKG, "..", "lib", "libispc_texcomp.so"))
 _TEST_LIB = os.path.normpath(os.path.join(_PKG, "..", "lib", "libispc_texcomp_test.so"))
 
-BYTES_PER_BLOCK = {"bc1": 8, "bc3": 16, "bc7": 16, "bc6h": 16, "bc4": 8, "bc5": 16, "bc4_snorm": 8, "bc5_snorm": 16, "etc1": 8, "bc1a": 8, "bc1a_srgb": 8, "bc2": 16, "bc2_srgb": 16}
-KEEPS_PARTIAL_BLOCKS = ("bc4", "bc5", "bc4_snorm", "bc5_snorm", "bc1a", "bc1a_srgb", "bc2", "bc2_srgb")     # DirectXTex formats: ceil(w/4) x ceil(h/4) blocks (include/itw_bc45.h)
+BYTES_PER_BLOCK = {"bc1": 8, "bc3": 16, "bc7": 16, "bc6h": 16, "bc4": 8, "bc5": 16, "bc4_snorm": 8, "bc5_snorm": 16, "etc1": 8, "bc1a": 8, "bc1a_srgb": 8, "bc2": 16, "bc2_srgb": 16, "bc3_dxtex": 16, "bc3_dxtex_srgb": 16}
+KEEPS_PARTIAL_BLOCKS = ("bc4", "bc5", "bc4_snorm", "bc5_snorm", "bc1a", "bc1a_srgb", "bc2", "bc2_srgb", "bc3_dxtex", "bc3_dxtex_srgb")     # DirectXTex formats: ceil(w/4) x ceil(h/4) blocks (include/itw_bc45.h)
 SIGNED_FORMATS = ("bc4_snorm", "bc5_snorm")     # RGBA8_SNORM sources: int8 arrays / tensors, never uint8 (include/itw_bc45.h)
 BC7_PROFILES = ("ultrafast", "veryfast", "fast", "basic", "slow",
                 "alpha_ultrafast", "alpha_veryfast", "alpha_fast", "alpha_basic", "alpha_slow")
@@ -88,7 +88,8 @@ class Bc1aSettings(C.Structure):
     A texel is transparent when its alpha (code * (1/255) in fp32) < alpha_ref; a caller who kept coverage with alpha_coverage=r passes
     alpha_ref=Bc1aSettings.ref_of(r).  None where settings are taken means Bc1aSettings().
     "bc2" / "bc2_srgb" take the same struct: BC2 has no colour key, so alpha_ref is checked (finite) but ignored; dither_a diffuses the error
-    of the 4-bit alpha, dither_rgb and uniform mean what they mean for "bc1a"."""
+    of the 4-bit alpha, dither_rgb and uniform mean what they mean for "bc1a".
+    "bc3_dxtex" / "bc3_dxtex_srgb" take it too, alpha_ref ignored likewise: dither_a diffuses the error of the 3-bit alpha indices."""
     _fields_ = [("struct_size", C.c_uint32), ("alpha_ref", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
     def __init__(self, alpha_ref=0.5, dither_rgb=False, dither_a=False, uniform=False):
@@ -113,7 +114,9 @@ assert C.sizeof(RgbaSurface) == 24 and C.sizeof(Bc7Settings) == 64 and C.sizeof(
 # only -- decode, decode_chain, decode_image, measure, measure_chain and preview take it (uint16 half bit patterns, like "bc6h"), load_dds decodes
 # a file labelled 96 under it, and every compress* raises ValueError: there is no signed BC6H encoder ("bc6h_sf16" still encodes the
 # reference's unsigned-coded blocks, and decode("bc6h_sf16") is not offered)
-DXGI_FORMAT = {"bc6h_signed": 0x8E8E, "bc2": 0x83F2, "bc2_srgb": 0x8C4E, "bc1a": 0x83F1, "bc1a_srgb": 0x8C4D, "etc1": 0x8D64, "bc1": 71, "bc1_srgb": 72, "bc3": 77, "bc3_srgb": 78, "bc4": 80, "bc4_snorm": 81, "bc5": 83, "bc5_snorm": 84, "bc6h": 95, "bc6h_sf16": 96, "bc7": 98, "bc7_srgb": 99}
+# "bc3_dxtex" / "bc3_dxtex_srgb": ITW_FORMAT_BC3_DXTEX[_SRGB], BC3 by DirectXTex's D3DXEncodeBC3 ("bc3" stays kernel.ispc's encoder): encoded where
+# "bc1a" is (same Bc1aSettings); decode, measure, preview and DDS take them as synonyms of "bc3" / "bc3_srgb" (load_dds reports 77 / 78)
+DXGI_FORMAT = {"bc3_dxtex": 0x83F3, "bc3_dxtex_srgb": 0x8C4F, "bc6h_signed": 0x8E8E, "bc2": 0x83F2, "bc2_srgb": 0x8C4E, "bc1a": 0x83F1, "bc1a_srgb": 0x8C4D, "etc1": 0x8D64, "bc1": 71, "bc1_srgb": 72, "bc3": 77, "bc3_srgb": 78, "bc4": 80, "bc4_snorm": 81, "bc5": 83, "bc5_snorm": 84, "bc6h": 95, "bc6h_sf16": 96, "bc7": 98, "bc7_srgb": 99}
 
 
 class DdsDesc(C.Structure):
@@ -153,7 +156,7 @@ class MultiGpuStats(C.Structure):
 
 
 # the channels of a decoded texel that carry a format's own data (the others are fill values: itw_decode.h)
-OWN_CHANNELS = {"bc1": "rgb", "bc3": "rgba", "bc4": "r", "bc5": "rg", "bc4_snorm": "r", "bc5_snorm": "rg", "bc6h": "rgb", "bc7": "rgba", "etc1": "rgb", "bc1a": "rgba", "bc1a_srgb": "rgba", "bc2": "rgba", "bc2_srgb": "rgba"}
+OWN_CHANNELS = {"bc1": "rgb", "bc3": "rgba", "bc4": "r", "bc5": "rg", "bc4_snorm": "r", "bc5_snorm": "rg", "bc6h": "rgb", "bc7": "rgba", "etc1": "rgb", "bc1a": "rgba", "bc1a_srgb": "rgba", "bc2": "rgba", "bc2_srgb": "rgba", "bc3_dxtex": "rgba", "bc3_dxtex_srgb": "rgba"}
 _DXGI_BASE = {71: "bc1", 72: "bc1", 77: "bc3", 78: "bc3", 80: "bc4", 81: "bc4_snorm", 83: "bc5", 84: "bc5_snorm", 95: "bc6h", 96: "bc6h",
               98: "bc7", 99: "bc7", 0x8D64: "etc1", 0x83F2: "bc2", 0x8C4E: "bc2", 0x8E8E: "bc6h"}
 
@@ -171,8 +174,8 @@ def _encodes(fn):
 
 
 def _base(fmt):
-    """Key of BYTES_PER_BLOCK for a key of DXGI_FORMAT: 'bc7_srgb' -> 'bc7'; the signed formats are their own base."""
-    return fmt if fmt in SIGNED_FORMATS else fmt.split("_")[0]
+    """Key of BYTES_PER_BLOCK for a key of DXGI_FORMAT: 'bc7_srgb' -> 'bc7'; the signed formats and 'bc3_dxtex' are their own base."""
+    return fmt if fmt in SIGNED_FORMATS else "bc3_dxtex" if fmt.startswith("bc3_dxtex") else fmt.split("_")[0]
 
 
 def _check_texel_type(fmt, img):
@@ -640,7 +643,7 @@ def _call(fmt, surf, dst_ptr, settings):
     elif fmt == "etc1":
         st = settings if isinstance(settings, EtcSettings) else etc_profile(settings or "slow")
         L.itwCompressBlocksETC1(C.byref(surf), dst_ptr, C.byref(st))
-    elif fmt in ("bc1a", "bc1a_srgb", "bc2", "bc2_srgb"):
+    elif fmt in ("bc1a", "bc1a_srgb", "bc2", "bc2_srgb", "bc3_dxtex", "bc3_dxtex_srgb"):
         # no block-level entry point: the single image is the slice call with one slice (synchronous)
         assert settings is None or isinstance(settings, Bc1aSettings)
         pitch = ((surf.width + 3) // 4) * BYTES_PER_BLOCK[fmt]
@@ -789,7 +792,7 @@ def compress_image(fmt, img, profile=None, multithreaded=True, slice_pixels=0, p
     pitch = block_count(fmt, w, 4) * BYTES_PER_BLOCK[fmt]
     if fmt == "etc1" and settings is None:
         settings = etc_profile(profile or "slow")
-    if settings is not None or _base(fmt) in ("bc1a", "bc2"):           # ("bc1a", "bc2": no trampoline either; None is Bc1aSettings())
+    if settings is not None or _base(fmt) in ("bc1a", "bc2", "bc3_dxtex"):           # ("bc1a", "bc2", "bc3_dxtex": no trampoline either; None is Bc1aSettings())
         ok = lib().itwCompressImageSlicedEx(C.byref(surf), dst, pitch, DXGI_FORMAT[fmt], C.cast(C.byref(settings), C.c_void_p) if settings is not None else None, slice_pixels,
                                             C.cast(cb, C.c_void_p) if cb else None, None)
     else:
@@ -1557,7 +1560,7 @@ def decode(fmt, blocks, width, height, want_modes=False):
     (H, W, 4) uint8 -- uint16 half bit patterns for bc6h and bc6h_signed, int8 for the signed formats -- in the same kind of container, plus the per-block modes
     (int32) when asked."""
     import numpy as np
-    key = {"bc1": 71, "bc3": 77, "bc7": 98, "bc6h": 95, "bc4": 80, "bc5": 83, "bc4_snorm": 81, "bc5_snorm": 84, "etc1": 0x8D64, "bc1a": 0x83F1, "bc1a_srgb": 0x8C4D, "bc2": 0x83F2, "bc2_srgb": 0x8C4E, "bc6h_signed": 0x8E8E}[fmt]
+    key = {"bc1": 71, "bc3": 77, "bc7": 98, "bc6h": 95, "bc4": 80, "bc5": 83, "bc4_snorm": 81, "bc5_snorm": 84, "etc1": 0x8D64, "bc1a": 0x83F1, "bc1a_srgb": 0x8C4D, "bc2": 0x83F2, "bc2_srgb": 0x8C4E, "bc3_dxtex": 0x83F3, "bc3_dxtex_srgb": 0x8C4F, "bc6h_signed": 0x8E8E}[fmt]
     signed = fmt in SIGNED_FORMATS                      # RGBA8_SNORM texels: int8
     nb = block_count(fmt, width, height)
     half = _base(fmt) == "bc6h"                         # "bc6h", "bc6h_signed": RGBA16F bit patterns
