@@ -49,6 +49,12 @@ int itwTestBc45IndexTable(uint32_t* host_out);
  * bytes, 16 MiB of host memory.  Returns 0, or -1 on failure (error mode "return"). */
 int itwTestBc45ClosestS(uint8_t* host_out);
 
+/* Which loaders a BC1 / BC3 / BC4 / BC5 call takes (csrc/offset32_host.hpp; tests/test_gpu_large_offsets.py, tests/test_offset32_cpu.py):
+ * 1 when the launcher walks a surface of this stride, width and height with 32-bit byte offsets, 0 when it forms 64-bit row addresses.
+ * kind 1: BC1, 3: BC3; 4, 8, 16: the BC4 / BC5 family by the bytes of a source texel (4: every RGBA8 source, 8 / 16: the half and float
+ * sources of itwCompressNormalMapBC5S).  -1 for any other kind.  The function the launchers call; host arithmetic only. */
+int itwTestWalks32(int kind, int64_t stride, int width, int height);
+
 /* Multi-GPU (tests/test_gpu_multigpu_cpp.py): the NEXT itwCompressImageMultiGPU[Ex] call of this process fails inside rank `rank` at `stage`
  * (1 = while preparing, before any transfer is posted; 2 = after its first half-band was posted; 3 = the rank stalls for
  * `stall_ms` before posting anything, which is what the watchdog is for).  One-shot; nothing in the environment can set it. */

@@ -1689,6 +1689,13 @@ int itwTestBc45ClosestS(uint8_t* host_out)
     return itw::guarded([&] { if (!host_out) itw::fail_msg("null pointer"); itw::copy_bc45_closest_snorm(host_out, tls.user_stream); }) ? 0 : -1;
 }
 
+int itwTestWalks32(int kind, int64_t stride, int width, int height)
+{
+    if (kind == 1 || kind == 3) return itw::bc13_walks_32(kind == 3, stride, width, height) ? 1 : 0;
+    if (kind == 4 || kind == 8 || kind == 16) return itw::bc45_walks_32(kind, stride, width, height) ? 1 : 0;
+    return -1;
+}
+
 void itwTestBc7TwoSubsetBounds(const rgba_surface* d_src, float* d_out)
 {
     itwClearError();

@@ -16,6 +16,7 @@
 // texel order k = 0..15 inside the lane, exactly like one ISPC program instance.
 #include "x86_math.hpp"
 #include "kernels.hpp"
+#include "offset32_host.hpp"
 
 // Register allocation target: four waves per SIMD (measured round 3: 5 waves = 96 VGPRs + spills is 16 % slower, 3 and 2 waves
 // change nothing -- the kernel is bound by the issue cycles of its own instruction stream).  The A/B switches and
@@ -531,10 +532,13 @@ static unsigned bc13_grid(int64_t n)
     return (unsigned)(chunks < bound ? chunks : bound);
 }
 
-// SMALL: positive stride and every texel row below 2 GiB from the base (16384^2 RGBA8 is 1 GiB): 32-bit offsets.  The output offset is
-// 32-bit on that path too: with rows that overlap (a positive stride below 4 * width, which the ABI tolerates) the block stream can
-// outgrow the texels, so it is bounded separately.
-static bool bc13_small(int64_t stride, int height, int64_t nblocks) { return stride > 0 && (int64_t)height * stride < ((int64_t)1 << 31) && nblocks * 16 < ((int64_t)1 << 32); }
+// SMALL: the 32-bit walk, where offset32_host.hpp's rule allows it (16384^2 RGBA8 is 1 GiB).  The output offset is 32-bit on that path too:
+// with rows that overlap (a positive stride below 4 * width, which the ABI tolerates) the block stream can outgrow the texels, so it is
+// bounded separately, and so is the column term of the last row's offset.
+bool bc13_walks_32(bool bc3, int64_t stride, int width, int height)
+{
+    return walk_fits_32(stride, width, height, 16, (int64_t)(width / 4) * (height / 4) * (bc3 ? 16 : 8));
+}
 
 // VEC16 requires: src base and stride multiples of 16, dst multiple of 16 (BC3) / 8 (BC1).
 void launch_bc1(const uint8_t* src, int64_t stride, int width, int height, uint8_t* dst, hipStream_t st)
@@ -544,7 +548,7 @@ void launch_bc1(const uint8_t* src, int64_t stride, int width, int height, uint8
     if (n <= 0) return;
     const bool vec = ((reinterpret_cast<uintptr_t>(src) | (uintptr_t)stride) & 15) == 0 && (reinterpret_cast<uintptr_t>(dst) & 7) == 0;
     const dim3 grid(bc13_grid(n)), blk(256);
-    if (bc13_small(stride, height, n)) {
+    if (bc13_walks_32(false, stride, width, height)) {
         if (vec) hipLaunchKernelGGL((bc13_kernel<false, true, true>),  grid, blk, 0, st, src, stride, bx, (int32_t)n, dst);
         else     hipLaunchKernelGGL((bc13_kernel<false, false, true>), grid, blk, 0, st, src, stride, bx, (int32_t)n, dst);
     } else {
@@ -560,7 +564,7 @@ void launch_bc3(const uint8_t* src, int64_t stride, int width, int height, uint8
     if (n <= 0) return;
     const bool vec = ((reinterpret_cast<uintptr_t>(src) | (uintptr_t)stride | reinterpret_cast<uintptr_t>(dst)) & 15) == 0;
     const dim3 grid(bc13_grid(n)), blk(256);
-    if (bc13_small(stride, height, n)) {
+    if (bc13_walks_32(true, stride, width, height)) {
         if (vec) hipLaunchKernelGGL((bc13_kernel<true, true, true>),  grid, blk, 0, st, src, stride, bx, (int32_t)n, dst);
         else     hipLaunchKernelGGL((bc13_kernel<true, false, true>), grid, blk, 0, st, src, stride, bx, (int32_t)n, dst);
     } else {

@@ -42,6 +42,7 @@
 #include <vector>
 #include "kernels.hpp"
 #include "host_rt.hpp"
+#include "offset32_host.hpp"
 #include "normal_prep.hpp"
 
 namespace itw {
@@ -704,8 +705,9 @@ void launch_bc45(const uint8_t* src, int64_t stride, int width, int height, uint
     const uint4* runs = index_table<SGN>();
     const int64_t chunks = (n + 255) / 256;
     const dim3 grid((unsigned)(chunks < BC45_GRID ? chunks : BC45_GRID)), blk(256);
-    // WHOLE: no partial blocks and every texel offset fits 31 bits (a non-negative stride; 16384^2 RGBA8 is 1 GiB)
-    const bool whole = (width % 4 == 0) && (height % 4 == 0) && stride > 0 && (int64_t)height * stride < ((int64_t)1 << 31);
+    // WHOLE: no partial blocks and every texel offset fits 31 bits, the column term of overlapping rows included (offset32_host.hpp; a
+    // positive stride; 16384^2 RGBA8 is 1 GiB).  The stores take 64-bit offsets.
+    const bool whole = bc45_walks_32(PREP >= 64u ? (int)(PREP >> 4) : 4, stride, width, height);
     if (whole) {
         if (vec) hipLaunchKernelGGL((bc45_kernel<NCH, true, true, SGN, PREP>),  grid, blk, 0, st, src, stride, width, height, bx, (int32_t)n, dst, runs, sops);
         else     hipLaunchKernelGGL((bc45_kernel<NCH, false, true, SGN, PREP>), grid, blk, 0, st, src, stride, width, height, bx, (int32_t)n, dst, runs, sops);
@@ -747,6 +749,11 @@ __global__ void __launch_bounds__(256) bc45_closest_snorm_kernel(uint8_t* __rest
 #endif
 
 } // namespace
+
+bool bc45_walks_32(int texel_bytes, int64_t stride, int width, int height)
+{
+    return (width % 4 == 0) && (height % 4 == 0) && walk_fits_32(stride, width, height, 4 * texel_bytes, 0);
+}
 
 void launch_bc4(const uint8_t* src, int64_t stride, int width, int height, uint8_t* dst, hipStream_t st) { launch_bc45<1, false>(src, stride, width, height, dst, st); }
 void launch_bc5(const uint8_t* src, int64_t stride, int width, int height, uint8_t* dst, hipStream_t st) { launch_bc45<2, false>(src, stride, width, height, dst, st); }

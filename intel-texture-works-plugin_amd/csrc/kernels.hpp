@@ -37,6 +37,10 @@ void warmup_bc45s();                                            // the same for 
 void copy_bc45_closest_snorm(uint8_t* host_out, hipStream_t st);  // test hook: the SNORM encoders' index for every (endpoint pair, code), 16 MiB
 void warmup_bc45();                                               // builds the current device's FindClosestUNORM run table now (else: first call)
 void copy_bc45_index_table(uint32_t* host_out, hipStream_t st);   // test hook: the FindClosestUNORM run table of the current device
+// which surfaces launch_bc1 / launch_bc3 (bc3) and launch_bc4 .. launch_bc5s_normal (texel_bytes: 4 for RGBA8) walk with 32-bit byte offsets:
+// offset32_host.hpp's rule with each launcher's block row and output.  A pure function of these arguments.
+bool bc13_walks_32(bool bc3, int64_t stride, int width, int height);
+bool bc45_walks_32(int texel_bytes, int64_t stride, int width, int height);
 // BC7 runs as up to seven kernels (search + finish per multi-subset mode family, one for modes 4/5/6) that hand
 // "best error so far" and the search winners to each other through
 // `workspace`: device memory, bc7_workspace_bytes(width, height) bytes, 16 B aligned, contents irrelevant on entry.

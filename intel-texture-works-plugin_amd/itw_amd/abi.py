@@ -43,7 +43,7 @@ EXPORTED_SYMBOLS = tuple(
 TEST_HOOK_SYMBOLS = ("itwTestRcp", "itwTestRsqrt", "itwTestF2I", "itwTestBc7TwoSubsetBounds", "itwTestBc7RotationBounds", "itwTestBc7F02Scan", "itwTestBc45IndexTable", "itwTestBc45ClosestS",
                      "itwMultiGpuTestInjectFailure", "itwTestCombinerHold", "itwTestCombinerCounters", "itwTestBc7RouteCounters", "itwTestBc7RouteCountersReset",
                      "itwTestBc7CallCountersArm", "itwTestBc7CallCounters", "itwTestSrgbEncode", "itwTestAlphaHistVariant", "itwTestMipCubicVariant",
-                     "itwTestMipFilterTable", "itwTestResizeTable")
+                     "itwTestMipFilterTable", "itwTestResizeTable", "itwTestWalks32")
 # enum itw_test_bc7_call_counter (include/itw_test_hooks.h): what itwTestBc7CallCounters fills; the per-band ones are band 0 then band 1
 BC7_CALL_COUNTERS = ("pilot_listed", "pilot_sampled", "pilot_flag", "rot00", "rot01", "rot02", "rot10", "rot11", "rot12", "listed0", "listed1",
                      "pairs0", "pairs1", "overflow0", "overflow1", "redo0", "redo1")
@@ -382,6 +382,8 @@ def _load(path, hooks):
             L.itwTestMipFilterTable.restype = C.c_int64
             L.itwTestResizeTable.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int64]
             L.itwTestResizeTable.restype = C.c_int64
+            L.itwTestWalks32.argtypes = [C.c_int, C.c_int64, C.c_int, C.c_int]
+            L.itwTestWalks32.restype = C.c_int
         # dispatch layer (itw_dispatch.h)
         L.GetProcessorCount.restype = C.c_int
         L.GetBytesPerBlock.argtypes = [C.c_int]
