@@ -69,6 +69,13 @@
 //                 encode.  DirectX::Resize on the device (itwGenerateMipChain with ITW_MIP_RESIZE over two levels); without
 //                 --resize-filter the reference's default, box at exactly 2:1 and linear otherwise.  --srgb-mips and --mip-wrap hold
 //                 for this stage too (the linear filter refuses wrap on an axis that grows).  Not with --cube-cross or --signed-normal.
+//     --volume <depth> : a volume texture (3D LUT, fog or cloud density, 3D noise).  in.raw holds <depth> slices of width x height, one
+//                 after another, and the output is a volume DDS (ITW_DDS_VOLUME, itw_dds.h: slices level-major) from one call,
+//                 itwCompressImageMippedEx with ITW_MIP_VOLUME.  --mips [levels] builds the 3D chain by DirectXTex's default, box for power-of-two sizes and
+//                 triangle otherwise; --mip-filter point|linear|cubic|triangle names the filter (point and linear are the volume's alone) and
+//                 --mip-wrap takes the letters u, v, w in that order (w is the volume's alone); --srgb-mips as for an image.  --measure prints
+//                 one line per slice of every level (itwMeasureChain over the generated chain).  Not with --normal, --signed-normal,
+//                 --height, --cube-cross, --refine*, --alpha-weight, --alpha-coverage, --resize, --fit, etc1_slow or a slice size.
 //
 //   encode_dds --decode <in.dds | in.ktx> <out.raw>
 //     (.dds or .ktx: told apart by the file's first bytes; a KTX file's images come in ITS order, level then face)
@@ -76,6 +83,7 @@
 //     every image's texels one after another in file order, tightly packed (RGBA8; RGBA16F bit patterns for BC6H; int8 codes for the
 //     SNORM pair); one line on stdout per image: index, width, height, min alpha (the smallest decoded alpha code: IsAlphaAllOpaque).
 //     A BC6H_SF16 file (DX10 format 96) is decoded and previewed by the signed reading, ITW_FORMAT_BC6H_SIGNED: as a GPU shows it.
+//     A volume DDS is read in its own order, level-major; its lines end in the slice's level and number.
 //
 //   encode_dds --preview <in.dds | in.ktx> <image index> <out.ppm> <w> <h> <x> <y> <zoom> [channels] [exposure] [matte]
 //     the preview path (IntelPlugin::FetchPreviewRGB): a w x h viewport of ONE image of the file (itwDdsImage / itwKtxImage's index), decoded
@@ -280,6 +288,80 @@ int encode_mipped(const Format& f, const rgba_surface& source, uint32_t ops, uin
     return 0;
 }
 
+// encode_dds --volume: `depth` slices of width x height to a volume DDS in one call; levels == 0: the full chain, 1: no mips
+int encode_volume(const Format& f, uint8_t* texels, int w, int h, int depth, int levels, uint32_t mip_flags, bool measure, const char* out_path)
+{
+    const bool bc7 = std::strncmp(f.name, "bc7_", 4) == 0, bc6h = std::strncmp(f.name, "bc6h_", 5) == 0;
+    union { bc7_enc_settings s7; bc6h_enc_settings s6; } settings;
+    if ((bc7 || bc6h) && !profile_by_name(bc6h, f.name + (bc7 ? 4 : 5), &settings)) return 2;
+    const int full = itwMipLevels(w > h ? w : h, depth);            // 1 + floor(log2(max(w, h, d)))
+    if (levels < 0 || levels > full) { std::fprintf(stderr, "--mips %d: a full chain of %d x %d x %d has %d levels\n", levels, w, h, depth, full); return 2; }
+    if (levels == 0) levels = full;
+    // the slice list, level-major, packed with tight rows; `storage` null: sizes and offsets only
+    std::vector<rgba_surface> chain;
+    auto layout = [&](uint8_t* storage) {
+        size_t at = 0;
+        chain.clear();
+        for (int l = 0; l < levels; l++) {
+            const int lw = (w >> l) ? (w >> l) : 1, lh = (h >> l) ? (h >> l) : 1, ld = (depth >> l) ? (depth >> l) : 1;
+            for (int z = 0; z < ld; z++) {
+                chain.push_back(rgba_surface{storage ? storage + at : nullptr, lw, lh, lw * f.texel_bytes});
+                at += (size_t)lw * lh * f.texel_bytes;
+            }
+        }
+        return at;
+    };
+    const size_t texel_bytes = layout(nullptr);
+    const int count = (int)chain.size();
+    const int64_t bytes = itwChainBytes(chain.data(), count, f.dxgi);
+    if (bytes <= 0) { std::fprintf(stderr, "bad size\n"); return 2; }
+    std::vector<rgba_surface> bases((size_t)depth);
+    for (int z = 0; z < depth; z++) bases[(size_t)z] = rgba_surface{texels + (size_t)z * w * h * f.texel_bytes, w, h, w * f.texel_bytes};
+    std::vector<uint8_t> blocks((size_t)bytes);
+    itwSetErrorMode(ITW_ON_ERROR_RETURN);
+    const void* sp = takes_bc_settings(f.dxgi) ? (const void*)&g_bc1a : (const void*)&settings;
+    if (!itwCompressImageMippedEx(bases.data(), depth, levels, 0, mip_flags | ITW_MIP_VOLUME, blocks.data(), f.dxgi, sp, nullptr, nullptr)) {
+        std::fprintf(stderr, "%s\n", itwLastError() ? itwLastError() : "compression failed");
+        return 1;
+    }
+    if (measure) {                                                  // the same chain once more, in host memory, and the stream against it
+        std::vector<uint8_t> levels_texels(texel_bytes);
+        layout(levels_texels.data());
+        std::memcpy(levels_texels.data(), texels, (size_t)depth * w * h * f.texel_bytes);
+        std::vector<itw_error_stats> st((size_t)count);
+        if (itwGenerateMipChain(chain.data(), depth, levels, f.texel_bytes, mip_flags | ITW_MIP_VOLUME) != 0
+            || itwMeasureChain(chain.data(), count, blocks.data(), f.dxgi, st.data(), sizeof(itw_error_stats)) != 0) {
+            std::fprintf(stderr, "%s\n", itwLastError() ? itwLastError() : "measurement failed");
+            return 1;
+        }
+        for (int i = 0; i < count; i++) {
+            std::printf("image %d: %dx%d %s", i, st[(size_t)i].width, st[(size_t)i].height, f.name);
+            if (f.texel_bytes == 4) std::printf(" psnr %.4f dB", itwStatsPsnr(&st[(size_t)i], f.own_channels));
+            std::printf(" sse [%llu, %llu, %llu, %llu] max_abs [%u, %u, %u, %u]\n", (unsigned long long)st[(size_t)i].sse[0], (unsigned long long)st[(size_t)i].sse[1],
+                        (unsigned long long)st[(size_t)i].sse[2], (unsigned long long)st[(size_t)i].sse[3], st[(size_t)i].max_abs[0], st[(size_t)i].max_abs[1],
+                        st[(size_t)i].max_abs[2], st[(size_t)i].max_abs[3]);
+        }
+    }
+    ItwDdsDesc desc = { (uint32_t)w, (uint32_t)h, (uint32_t)levels, (uint32_t)f.dxgi, ITW_DDS_VOLUME, (uint32_t)depth };
+    std::vector<uint8_t> file(itwDdsFileBytes(&desc));
+    std::vector<const uint8_t*> slices((size_t)count);              // level-major: the call's order
+    size_t at = 0;
+    for (size_t i = 0; i < slices.size(); i++) {
+        slices[i] = blocks.data() + at;
+        at += itwDdsImage(&desc, (uint32_t)i, nullptr, nullptr, nullptr);
+    }
+    if (at != blocks.size() || file.empty() || itwDdsWriteFile(&desc, slices.data(), slices.size(), file.data(), file.size()) != file.size()) {
+        std::fprintf(stderr, "DDS assembly failed\n");
+        return 1;
+    }
+    FILE* out = std::fopen(out_path, "wb");
+    if (!out || std::fwrite(file.data(), 1, file.size(), out) != file.size()) { std::fprintf(stderr, "cannot write %s\n", out_path); return 1; }
+    std::fclose(out);
+    DestroyThreads();
+    std::fprintf(stderr, "%s: %dx%dx%d, %d levels, %d slices -> %zu bytes (%s)\n", out_path, w, h, depth, levels, count, file.size(), f.name);
+    return 0;
+}
+
 // --height-amplitude: a float as the bits of the nearest IEEE half (ties to even; overflow gives 0x7C00, which the caller refuses)
 uint32_t half_bits_of(float v)
 {
@@ -348,6 +430,8 @@ int decode_file(const char* in_path, const char* out_path)
     const bool ktx = file.size() >= 12 && std::memcmp(file.data(), ktx_id, 12) == 0;
     ItwDdsDesc desc = {};
     ItwKtxDesc kdesc = {};
+    bool volume = false;                                           // a volume DDS: slices level-major, the depth in array_size
+    std::vector<uint32_t> level_of, slice_of;
     size_t first = 0;
     std::vector<uint8_t> packed;                                   // KTX: the images behind one another (a size word sits in front of each level)
     if (ktx) {
@@ -355,6 +439,7 @@ int decode_file(const char* in_path, const char* out_path)
         desc.dxgi_format = kdesc.gl_internal_format;
     } else {
         first = itwDdsReadHeader(file.data(), file.size(), &desc);
+        volume = first && desc.is_cubemap == ITW_DDS_VOLUME;
         if (!first) { std::fprintf(stderr, "%s: not a BCn DDS file this library reads\n", in_path); return 1; }
     }
     // a file labelled BC6H_SF16 is read as a GPU reads it: the signed reading has a code of its own (itw_dispatch.h), 96 is the header's word
@@ -366,6 +451,11 @@ int decode_file(const char* in_path, const char* out_path)
         uint32_t w = 0, h = 0; size_t off = 0;
         const size_t n = ktx ? itwKtxImage(&kdesc, i, &w, &h, &off) : itwDdsImage(&desc, i, &w, &h, &off);
         if (!n) break;
+        if (volume) {                                              // index i is slice i - (slices of the levels before) of its level
+            uint32_t lv = 0, before = 0;
+            for (uint32_t ld = desc.array_size; i - before >= ld; lv++, ld = ld > 1 ? ld / 2 : 1) before += ld;
+            level_of.push_back(lv); slice_of.push_back(i - before);
+        }
         outs.push_back(rgba_surface{nullptr, (int32_t)w, (int32_t)h, (int32_t)w * texel_bytes});
         texels_bytes += (size_t)w * h * texel_bytes;
         end = off + n;
@@ -381,7 +471,11 @@ int decode_file(const char* in_path, const char* out_path)
         std::fprintf(stderr, "%s\n", itwLastError() ? itwLastError() : "itwDecodeChain refused the file");
         return 1;
     }
-    for (size_t i = 0; i < outs.size(); i++) std::printf("image %zu: %d %d min_alpha %u\n", i, outs[i].width, outs[i].height, min_alpha[i]);
+    for (size_t i = 0; i < outs.size(); i++) {
+        std::printf("image %zu: %d %d min_alpha %u", i, outs[i].width, outs[i].height, min_alpha[i]);
+        if (volume) std::printf(" level %u slice %u", level_of[i], slice_of[i]);
+        std::printf("\n");
+    }
     FILE* out = std::fopen(out_path, "wb");
     if (!out || std::fwrite(texels.data(), 1, texels.size(), out) != texels.size()) { std::fprintf(stderr, "cannot write %s\n", out_path); return 1; }
     std::fclose(out);
@@ -477,6 +571,8 @@ int main(int argc, char** argv)
     itw_mip_alpha alpha = { (uint32_t)sizeof(itw_mip_alpha), 0, 0, 0 };
     int mip_levels = 0;                                         // 0: the full chain
     int signed_tb = 0;                                          // --signed-normal: texel bytes of the signed source (4, 8 or 16)
+    int volume_depth = 0;                                       // --volume <depth>
+    bool volume_given = false, volume_filter = false, volume_wrap = false;      // --mip-filter point|linear, --mip-wrap with w: the volume's alone
     uint32_t height_ops = 0, height_amplitude = 0x3C00;         // --height: ITW_NORMAL_FROM_HEIGHT and its fields; the amplitude as half bits (1.0)
     for (int i = 1; i < argc; i++)
         if (std::strcmp(argv[i], "--measure") == 0) {
@@ -560,6 +656,8 @@ int main(int argc, char** argv)
             filter_given = true;
             if (std::strcmp(argv[i + 1], "cubic") == 0) filter_flags |= ITW_MIP_CUBIC;
             else if (std::strcmp(argv[i + 1], "triangle") == 0) filter_flags |= ITW_MIP_TRIANGLE;
+            else if (std::strcmp(argv[i + 1], "point") == 0) { filter_flags |= ITW_MIP_POINT; volume_filter = true; }
+            else if (std::strcmp(argv[i + 1], "linear") == 0) { filter_flags |= ITW_MIP_LINEAR; volume_filter = true; }
             else { std::fprintf(stderr, "--mip-filter takes cubic or triangle\n"); return 2; }
             for (int k = i; k + 2 < argc; k++) argv[k] = argv[k + 2];
             argc -= 2; i--;
@@ -568,7 +666,17 @@ int main(int argc, char** argv)
             if (std::strcmp(argv[i + 1], "u") == 0) filter_flags |= ITW_MIP_WRAP_U;
             else if (std::strcmp(argv[i + 1], "v") == 0) filter_flags |= ITW_MIP_WRAP_V;
             else if (std::strcmp(argv[i + 1], "uv") == 0) filter_flags |= ITW_MIP_WRAP_U | ITW_MIP_WRAP_V;
+            else if (std::strcmp(argv[i + 1], "w") == 0 || std::strcmp(argv[i + 1], "uw") == 0 || std::strcmp(argv[i + 1], "vw") == 0 || std::strcmp(argv[i + 1], "uvw") == 0) {
+                volume_wrap = true;
+                filter_flags |= ITW_MIP_WRAP_W | (std::strchr(argv[i + 1], 'u') ? (uint32_t)ITW_MIP_WRAP_U : 0u) | (std::strchr(argv[i + 1], 'v') ? (uint32_t)ITW_MIP_WRAP_V : 0u);
+            }
             else { std::fprintf(stderr, "--mip-wrap takes u, v or uv\n"); return 2; }
+            for (int k = i; k + 2 < argc; k++) argv[k] = argv[k + 2];
+            argc -= 2; i--;
+        } else if (std::strcmp(argv[i], "--volume") == 0 && i + 1 < argc) {
+            volume_given = true;
+            volume_depth = std::atoi(argv[i + 1]);
+            if (volume_depth < 1) { std::fprintf(stderr, "--volume takes a depth of at least 1\n"); return 2; }
             for (int k = i; k + 2 < argc; k++) argv[k] = argv[k + 2];
             argc -= 2; i--;
         } else if (std::strcmp(argv[i], "--resize") == 0 && i + 1 < argc) {
@@ -615,6 +723,7 @@ int main(int argc, char** argv)
                              "          [--height r|g|b|a|lum[,mirroru,mirrorv,invert,occlusion] [--height-amplitude <A>]]\n"
                              "          [--alpha-weight] [--alpha-coverage <ref>] [--mip-filter cubic|triangle] [--mip-wrap u|v|uv] [--bc-dither rgb|a|rgb,a] [--bc-uniform]\n"
                              "          [--resize WxH | --fit pow2] [--resize-filter point|linear|cubic|triangle]\n"
+                             "          [--volume <depth> [--mips [levels]] [--mip-filter point|linear|cubic|triangle] [--mip-wrap u|v|w|uv|uw|vw|uvw] [--srgb-mips] [--measure]]\n"
                              "          <format> <width> <height> <in.raw> <out.dds> [slice_pixels]\n"
                              "       %s --decode <in.dds | in.ktx> <out.raw>\n"
                              "       %s --preview <in.dds | in.ktx> <image index> <out.ppm> <w> <h> <x> <y> <zoom> [channels] [exposure] [matte]\n", argv[0], argv[0], argv[0]);
@@ -628,6 +737,8 @@ int main(int argc, char** argv)
     if (!f || width < 1 || height < 1) { std::fprintf(stderr, "unknown format or bad size\n"); return 2; }
     const long long slice_pixels = argc > 6 ? std::atoll(argv[6]) : 0;
 
+    if (!volume_given && volume_filter) { std::fprintf(stderr, "--mip-filter takes cubic or triangle\n"); return 2; }      // (point and linear are --volume's)
+    if (!volume_given && volume_wrap) { std::fprintf(stderr, "--mip-wrap takes u, v or uv\n"); return 2; }
     if (g_bc1a.flags && !bc1a) { std::fprintf(stderr, "--bc-dither and --bc-uniform are bc1a's flags (and bc2's), and bc3_dxtex's\n"); return 2; }
     if (bc1a && (normal_given || refine_profile)) { std::fprintf(stderr, "%s holds colour and has one encoder: not with --normal or --refine*\n", argv[1]); return 2; }
     if (signed_tb && (normal_given || refine_profile || measure || (f->dxgi != ITW_DXGI_FORMAT_BC4_SNORM && f->dxgi != ITW_DXGI_FORMAT_BC5_SNORM))) {
@@ -640,6 +751,20 @@ int main(int argc, char** argv)
         return 2;
     }
     if (filter_given && (!mips || signed_tb)) { std::fprintf(stderr, "--mip-filter and --mip-wrap go with --mips, and not with --signed-normal\n"); return 2; }
+    if (volume_given) {
+        if (normal_given || signed_tb || height_ops || cube_cross || refine_profile || alpha_given || resize_w || fit_pow2 || resize_filter_given || argc > 6
+            || f->dxgi == ITW_FORMAT_ETC1_RGB8) {
+            std::fprintf(stderr, "--volume does not go with --normal, --signed-normal, --height, --cube-cross, --refine*, --alpha-weight, --alpha-coverage, --resize, --fit, "
+                                 "etc1_slow or a slice size: a volume has mips, a filter, wrap addressing and sRGB colour\n");
+            return 2;
+        }
+        if ((srgb_mips || filter_given) && !mips) { std::fprintf(stderr, "--srgb-mips, --mip-filter and --mip-wrap go with --mips\n"); return 2; }
+        std::vector<uint8_t> slices((size_t)width * height * volume_depth * f->texel_bytes);
+        FILE* vin = std::fopen(argv[4], "rb");
+        if (!vin || std::fread(slices.data(), 1, slices.size(), vin) != slices.size()) { std::fprintf(stderr, "cannot read %s\n", argv[4]); return 1; }
+        std::fclose(vin);
+        return encode_volume(*f, slices.data(), width, height, volume_depth, mips ? mip_levels : 1, (srgb_mips ? (uint32_t)ITW_MIP_SRGB : 0u) | filter_flags, measure, argv[5]);
+    }
     const int texel_bytes = signed_tb ? signed_tb : f->texel_bytes;
     std::vector<uint8_t> texels((size_t)width * height * texel_bytes);
     FILE* in = std::fopen(argv[4], "rb");

@@ -31,9 +31,19 @@ typedef struct ItwDdsDesc {
     uint32_t width, height;     /* top mip, texels */
     uint32_t mip_levels;        /* >= 1 */
     uint32_t dxgi_format;       /* DXGI_FORMAT_BCn_* value (71,72,77,78,80,81,83,84,95,96,98,99), or one of the BC1A / BC2 / BC3_DXTEX codes of itw_dispatch.h */
-    uint32_t is_cubemap;        /* 0 / 1: six faces */
-    uint32_t array_size;        /* number of textures (cubes when is_cubemap); >= 1 */
+    uint32_t is_cubemap;        /* 0 / 1: six faces; ITW_DDS_VOLUME: a volume texture (below) */
+    uint32_t array_size;        /* number of textures (cubes when is_cubemap); >= 1.  The DEPTH of a volume */
 } ItwDdsDesc;
+
+/* Volume textures (3D LUTs, fog and cloud density, 3D noise): is_cubemap = ITW_DDS_VOLUME and array_size = the depth of level 0, through the
+ * same seven functions.  The header is what _EncodeDDSHeader writes for TEX_DIMENSION_TEXTURE3D (DirectXTexDDS.cpp:585-597):
+ * dwFlags |= DDS_HEADER_FLAGS_VOLUME (0x00800000), dwCaps2 |= DDS_FLAGS_VOLUME (0x00200000), dwDepth = depth; the legacy FourCC where the
+ * format has one (the 2D rule and format-code mapping, the BC1A / BC2 / BC3_DXTEX codes included), otherwise 'DX10' with
+ * resourceDimension 4, arraySize 1 and miscFlag 0.  Payload (:1167-1200): LEVEL-MAJOR, the max(1, depth >> l) slices of level l one after
+ * another, each max(1, w >> l) x max(1, h >> l), without gaps -- the packed stream of the chain calls over the slice list of
+ * itwGenerateMipChain with ITW_MIP_VOLUME (itw_dispatch.h).  itwDdsImage's index and itwDdsWriteFile's `levels` run over the slices in that
+ * order: index i is slice i - (slices of the levels before) of the level it falls in.  A volume is never an array or a cube. */
+enum { ITW_DDS_VOLUME = 2 };
 
 /* bytes of one mip level: max(1,(w+3)/4) * max(1,(h+3)/4) * bytes-per-block */
 size_t itwDdsLevelBytes(uint32_t dxgi_format, uint32_t width, uint32_t height);
@@ -43,7 +53,11 @@ size_t itwDdsHeaderBytes(const ItwDdsDesc* desc);
 size_t itwDdsFileBytes(const ItwDdsDesc* desc);
 /* Writes the header into dst (capacity >= itwDdsHeaderBytes); returns bytes written, 0 on error. */
 size_t itwDdsWriteHeader(const ItwDdsDesc* desc, uint8_t* dst, size_t capacity);
-/* Parses a header; returns its size (offset of the first block), 0 if not a BCn DDS this library writes. */
+/* Parses a header; returns its size (offset of the first block), 0 if not a BCn DDS this library writes.  A header with
+ * DDS_HEADER_FLAGS_VOLUME (0x00800000 in dwFlags) is a volume, by DirectXTex's own test (DirectXTexDDS.cpp:323-328): it reads as
+ * is_cubemap = ITW_DDS_VOLUME with the depth in array_size.  Earlier versions never looked at the flag and read a legacy-header volume
+ * as a 2D texture, whose every level after the first then came from the wrong bytes; a caller that handles 2D files only checks
+ * is_cubemap.  Refused: a volume flag with a DX10 dimension other than 3D (or the reverse), a DX10 volume with arraySize > 1, a depth of 0. */
 size_t itwDdsReadHeader(const uint8_t* src, size_t size, ItwDdsDesc* desc);
 /* Whole file: `levels[i]` points at the blocks of image i in file order (array item major, then face, then mip).
  * Returns bytes written (== itwDdsFileBytes) or 0. */
@@ -71,7 +85,7 @@ size_t itwDdsImage(const ItwDdsDesc* desc, uint32_t index, uint32_t* width, uint
  * file are not one packed stream either -- a size word sits in front of each level -- so a loader copies them into one before
  * itwDecodeChain (itw_decode.h).
  *
- * Not here: KTX2, PKM, texture arrays, 3D textures, the other byte order, any other internal format.
+ * Not here: KTX2, PKM, texture arrays, 3D textures (DDS has them, above), the other byte order, any other internal format.
  */
 typedef struct ItwKtxDesc {
     uint32_t width, height;         /* level 0, texels; >= 1 */

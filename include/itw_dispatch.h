@@ -695,6 +695,68 @@ bool itwCompressImageMippedAlpha(const rgba_surface* bases, int items, int level
                                  int dxgi_format, const void* settings, ItwProgressFunc* progress, void* user);
 int itwAlphaCoverage(const rgba_surface* images, int count, int alpha_ref, uint64_t* covered);
 
+/* Mip chains: volumes.  GenerateMipMaps3D (DirectXTexMipmaps.cpp:2884-2983) and its five _Generate3DMips*Filter functions (:1371-2497) on
+ * the device: 3D LUTs, fog and cloud density, 3D noise.  Level l of a w x h x d base is max(1, w >> l) x max(1, h >> l) x max(1, d >> l); a
+ * full chain has 1 + floor(log2(max(w, h, d))) levels.  A chain is a list of SLICES (rgba_surface images) in DDS volume order, LEVEL-MAJOR:
+ * the d slices of level 0, then the max(1, d >> 1) slices of level 1, and so on.  That order is a
+ * volume .dds file's payload (itw_dds.h, ITW_DDS_VOLUME), and the list is what itwCompressImageChainEx, itwDecodeChain and itwMeasureChain
+ * take as it is.  Level l is filtered from level l-1 AS STORED.  IEEE fp32, every operation rounded on its own, no contraction; the per-axis
+ * arithmetic, the three texel kinds and their loads and stores are those of "Mip chains" and "Mip chains: cubic and triangle" above.
+ * RGBA16F is pinned byte for byte to the reference's own functions (tests/golden/mip3d_ref.npz); RGBA8 and RGBA8 with ITW_MIP_SRGB run the
+ * same fp32 arithmetic between the library's loads and stores.  Once the depth has reached 1 every filter takes the reference's 2D branch
+ * of the same function, which is the 2D chain's expression for that filter over the one slice.
+ *   no filter bit  GenerateMipMaps3D's default (:2921-2926): BOX when width, height and depth are all powers of two, TRIANGLE otherwise.
+ *           THIS DIFFERS FROM THE 2D CALL, whose default for other sizes is linear.
+ *   box     (_Generate3DMipsBoxFilter :1517-1685; only reachable by the default)  AVERAGE8 in its written order (Filters.h:41-51): the taps
+ *           (2x, 2y), (2x, 2y+1), (2x+1, 2y), (2x+1, 2y+1) of slice 2z, then the same four of slice 2z+1, summed left to right, times
+ *           0.125f.  Once the depth is 1, AVERAGE4 as the 2D chain.  An axis of size 1 gives the second tap = the first.
+ *   point   (ITW_MIP_POINT; :1371-1513)  source index (u * ((source << 16) / dest)) >> 16 per axis in 64-bit integers; the texel goes
+ *           through the kind's own load and store (RGBA16F: +-Inf becomes +-65504, a NaN 0x7E00).
+ *   linear  (ITW_MIP_LINEAR; :1689-1878)  _CreateLinearFilter on three axes and TRILINEAR_INTERPOLATE's written association
+ *           (Filters.h:108-112): z.w0 * (y.w0 * (a*x.w0 + b*x.w1) + y.w1 * (c*x.w0 + d*x.w1)) over slice z.u0, plus z.w1 * the same over
+ *           slice z.u1.  Here the two bits select the filter WITHOUT ITW_MIP_RESIZE.
+ *   cubic   (ITW_MIP_CUBIC; :1882-2258)  _CreateCubicFilter per axis; CUBIC_INTERPOLATE along x for the four y-tap rows of each of the four
+ *           z-tap slices, then along y per slice, then along z over the four slice values, in the written order.
+ *   triangle (ITW_MIP_TRIANGLE; :2261-2497)  TriangleFilter::_Create per axis.  A destination texel starts at 0 and receives
+ *           acc = texel * ((zweight * yweight) * xweight) + acc, a multiply then an add, over source slices ascending, then rows, then
+ *           texels; within one source texel its z entries outside, its y entries next, its x entries inside.  The device gathers over the
+ *           three inverted lists, which gives the same order.  A depth of 1 has the one z weight 1.0f, so a depth-1 volume writes the 2D
+ *           triangle chain's bytes.
+ *   wrap    (ITW_MIP_WRAP_U / _V / _W: TEX_FILTER_WRAP_U / _V / _W)  read by the cubic and triangle filters' table builders.  Box, point and
+ *           linear accept the bits and write the same bytes: at ratios >= 2 they never reach past an edge.  ITW_MIP_WRAP_W is read beside
+ *           ITW_MIP_VOLUME only; without that bit every call keeps refusing 0x100 as unknown.
+ *   launches  one per level for every filter: lanes along x, grid (x tiles, y tiles, destination slices).  ITW_MIP_PER_LEVEL is accepted and
+ *           changes nothing.
+ * Stated divergence, the one.  The reference's box filter keeps urow3 / vrow3 pointing into the old urow1 / vrow1 once the height has
+ * reached 1 while the width has not (:1552-1564): it reads a stale scanline, the defect stated for the 2D box above.  The library takes its
+ * 2D rule in every axis: an axis of size 1 gives the second tap = the first.
+ *
+ * No new entry point: a volume goes through the calls above with ITW_MIP_VOLUME (0x8000) in their flags, which changes what two
+ * arguments mean and nothing else about the calls.  Without the bit every call is what it was, and ITW_MIP_VOLUME and ITW_MIP_WRAP_W stay
+ * unknown bits to itwGenerateMipChainAlpha and itwCompressImageMippedAlpha (alpha weighting and coverage are not offered for volumes).
+ * Host arithmetic a caller does itself: a full chain has itwMipLevels(max(width, height), depth) levels; the first `levels` levels have
+ * the sum over l < levels of max(1, depth >> l) slices; a packed chain is those slices one after another, each
+ * max(1, w >> l) x max(1, h >> l) texels with tight rows (itwChainBytes over such a list gives the encoded size).
+ * itwGenerateMipChain(slices, depth, levels, pixel_size, flags | ITW_MIP_VOLUME): `images` is the slice list in that order and `items` the
+ * DEPTH of level 0; the `depth` slices of level 0 hold the caller's texels and are never written; levels 1 and up are written, width x
+ * height only.  Any stride at least the row's bytes, so slices may be views of a larger canvas.  All pointers device or all host.  Device:
+ * asynchronous on the calling thread's stream.  Host: staged through the thread's buffer -- only level 0 goes up, only the written levels
+ * come back -- and the call returns synchronised.  pixel_size 4 (RGBA8; with ITW_MIP_SRGB the sRGB colour kind) or 8 (RGBA16F).  Returns
+ * 0, also for depth == 0 or levels <= 1 (nothing to do); -1, through the library's error mode, before any device work and with nothing
+ * written, for a pixel_size other than 4 or 8; two filter bits together; ITW_MIP_RESIZE or a mirror bit (DirectXTex has no 3D resize); an
+ * unknown flag bit; ITW_MIP_SRGB with pixel_size 8; depth < 0; a null pointer; a slice whose size is not the definition's; levels above the
+ * full chain; a stride below the row's bytes; texels that are not pixel_size aligned; mixed host and device pointers; or more than one
+ * launch covers: a base of more than 131 071 slices (level 1 is a grid plane per slice, 65 535) or of more than 524 280 rows.
+ * itwCompressImageMippedEx(base_slices, depth, levels, 0, mip_flags | ITW_MIP_VOLUME, target, ...): the volume save path in one call.
+ * `bases` are the `items` = depth base slices (one size, host or device); they are copied into level 0 of a device-side chain of `levels`
+ * levels (0: the full chain), the chain is generated as above under `mip_flags`, and the slice list is encoded into `target` exactly as
+ * itwCompressImageChainEx encodes it: a volume .dds file's payload (itw_dds.h).  The bases are never written.  Formats, texel kinds,
+ * settings, padding rules, progress contract (1 .. slices), pointer kinds of `target`, errors and return value are the chain call's; on
+ * top of them everything the generation refuses, normal_ops != 0, and ITW_MIP_SRGB with an RGBA16F (95 / 96) or signed (81 / 84) format,
+ * fail before any device work.  itwCompressImageMipped (no flags word), the Alpha call and itwCompressSignedNormalMapMipped take no volume. */
+enum { ITW_MIP_WRAP_W = 0x100,       /* TEX_FILTER_WRAP_W; read only beside ITW_MIP_VOLUME, unknown and refused without it */
+       ITW_MIP_VOLUME = 0x8000 };    /* itwGenerateMipChain, itwCompressImageMippedEx: the image list is a volume's slices, `items` its depth */
+
 #pragma GCC visibility pop
 #ifdef __cplusplus
 }

@@ -34,6 +34,7 @@
 #include "mipgen.hpp"
 #include "mip_kernels.hpp"
 #include "mip_filters.hpp"
+#include "mip3d.hpp"
 #include "normal_prep.hpp"
 #include "bcn_format.hpp"
 #include "host_rt.hpp"
@@ -396,6 +397,8 @@ int generate_checked(const char* who, const rgba_surface* images, int items, int
 
 extern "C" int itwGenerateMipChain(const rgba_surface* images, int items, int levels, int pixel_size, uint32_t flags)
 {
+    if (flags & ITW_MIP_VOLUME)                                           // a volume: `items` is its depth, `images` its slices level-major (mip3d.hip)
+        return itw::generate_mip_chain_3d("itwGenerateMipChain", images, items, levels, pixel_size, flags & ~(uint32_t)ITW_MIP_VOLUME);
     return generate_checked("itwGenerateMipChain", images, items, levels, pixel_size, flags, nullptr, nullptr, true);
 }
 
@@ -542,6 +545,14 @@ bool compress_mipped(const rgba_surface* bases, int items, int levels, uint32_t 
 extern "C" bool itwCompressImageMippedEx(const rgba_surface* bases, int items, int levels, uint32_t normal_ops, uint32_t mip_flags, uint8_t* target,
                                          int dxgi_format, const void* settings, ItwProgressFunc* progress, void* user)
 {
+    if (mip_flags & ITW_MIP_VOLUME) {                                     // a volume: `bases` are its `items` slices (mip3d.hip)
+        if (normal_ops) {
+            itw::clear_failure();
+            itw::guarded([&] { itw::fail_msg("itwCompressImageMipped: normal ops 0x%x with ITW_MIP_VOLUME: a volume holds no normal map the stages know", normal_ops); });
+            return false;
+        }
+        return itw::compress_volume_mipped("itwCompressImageMipped", bases, items, levels, mip_flags & ~(uint32_t)ITW_MIP_VOLUME, target, dxgi_format, settings, progress, user);
+    }
     return compress_mipped(bases, items, levels, normal_ops, mip_flags, false, nullptr, target, dxgi_format, settings, progress, user);
 }
 

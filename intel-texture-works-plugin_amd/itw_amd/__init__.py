@@ -26,4 +26,6 @@ from .abi import (  # noqa: F401
     resize_flags, fit_size, resize, resize_chain_into, mip_levels, mip_chain_layout, generate_mips, generate_mips_into, compress_mipped,
     srgb_to_linear, linear_to_srgb, srgb_encode_device,
     MipAlpha, MipCoverage, alpha_coverage,
+    MIP_WRAP_W, MIP_VOLUME, DDS_VOLUME, mip_filter_flags_3d, mip_levels_3d, mip_slices_3d, mip_chain_layout_3d, generate_mips_3d, generate_mips_3d_into, compress_volume,
+    DdsVolumeDesc, dds_volume_file, dds_volume_images, load_dds_volume,
 )

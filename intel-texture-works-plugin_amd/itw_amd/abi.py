@@ -125,6 +125,14 @@ class DdsDesc(C.Structure):
                 ("is_cubemap", C.c_uint32), ("array_size", C.c_uint32)]
 
 
+DDS_VOLUME = 2        # ITW_DDS_VOLUME (itw_dds.h): DdsDesc.is_cubemap of a volume texture, whose array_size is the depth of level 0
+
+
+def DdsVolumeDesc(width, height, depth, mip_levels, dxgi_format):
+    """The DdsDesc of a volume texture: is_cubemap = ITW_DDS_VOLUME, array_size = depth; slices level-major."""
+    return DdsDesc(width, height, mip_levels, dxgi_format, DDS_VOLUME, depth)
+
+
 class KtxDesc(C.Structure):
     """struct ItwKtxDesc (itw_dds.h)."""
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("mip_levels", C.c_uint32), ("gl_internal_format", C.c_uint32),
@@ -1441,6 +1449,122 @@ def compress_mipped(fmt, base_or_bases, levels=0, profile=None, settings=None, n
     return bool(ok), out
 
 
+MIP_WRAP_W = 0x100    # ITW_MIP_WRAP_W: a volume's third wrap axis (beside MIP_VOLUME only)
+MIP_VOLUME = 0x8000   # ITW_MIP_VOLUME: itwGenerateMipChain / itwCompressImageMippedEx take the image list as a volume's slices, `items` as its depth
+
+
+def mip_filter_flags_3d(filter=None, wrap="", srgb=False, per_level=False):
+    """The ITW_MIP_* bits of a volume call: filter=None | "point" | "linear" | "cubic" | "triangle", wrap a string of the letters u, v, w."""
+    if filter not in (None, "point", "linear", "cubic", "triangle"):
+        raise ValueError(f"filter {filter!r} (None, 'point', 'linear', 'cubic' or 'triangle')")
+    if any(c not in "uvw" for c in wrap):
+        raise ValueError(f"wrap {wrap!r} (letters of 'uvw')")
+    return {None: 0, "point": MIP_POINT, "linear": MIP_LINEAR, "cubic": MIP_CUBIC, "triangle": MIP_TRIANGLE}[filter] \
+        | (MIP_WRAP_U if "u" in wrap else 0) | (MIP_WRAP_V if "v" in wrap else 0) | (MIP_WRAP_W if "w" in wrap else 0) \
+        | (MIP_SRGB if srgb else 0) | (MIP_PER_LEVEL if per_level else 0)
+
+
+def mip_levels_3d(width, height, depth):
+    """The length of a volume's full mip chain, 1 + floor(log2(max(width, height, depth))): itwMipLevels(max(width, height), depth); 0 for a
+    size below 1."""
+    return int(lib().itwMipLevels(max(width, height), depth)) if min(width, height, depth) >= 1 else 0
+
+
+def mip_slices_3d(depth, levels):
+    """The slices of a volume chain's first `levels` levels: the sum over l < levels of max(1, depth >> l)."""
+    return sum(max(1, depth >> l) for l in range(levels))
+
+
+def mip_chain_layout_3d(width, height, depth, levels=0, pixel_size=4):
+    """A packed volume chain: (bytes, [(offset, width, height, stride)] of every slice in volume order -- level-major, tight rows, the slices
+    one after another; levels == 0: the full chain).  Host arithmetic, as include/itw_dispatch.h ("Mip chains: volumes") states it.  Raises
+    ValueError for a size below 1, levels above the full chain, a pixel_size other than 4 or 8 or a row above 2^31 - 1 bytes."""
+    full = mip_levels_3d(width, height, depth)
+    if full == 0 or levels < 0 or levels > full or pixel_size not in (4, 8) or width * pixel_size > 0x7fffffff:
+        raise ValueError(f"no volume chain of {width} x {height} x {depth}, {levels} levels, pixel_size {pixel_size}")
+    out, at = [], 0
+    for l in range(levels or full):
+        w, h = max(1, width >> l), max(1, height >> l)
+        for _ in range(max(1, depth >> l)):
+            out.append((at, w, h, w * pixel_size))
+            at += w * h * pixel_size
+    return at, out
+
+
+def generate_mips_3d(volume, levels=0, filter=None, wrap="", srgb=False, per_level=False):
+    """itwGenerateMipChain with ITW_MIP_VOLUME: the mip levels of a volume, a (D, H, W, 4) numpy array or CUDA torch tensor, uint8 (RGBA8) or 2-byte elements
+    (RGBA16F half bits).  filter None: DirectXTex's 3D default, box when all three sizes are powers of two, else TRIANGLE (the 2D call's
+    default is linear there); or "point", "linear", "cubic", "triangle".  wrap: letters of "uvw", read by cubic and triangle.  srgb (uint8
+    only): ITW_MIP_SRGB.  levels == 0: the full chain.  Returns [volume, level 1, ...], each (d, h, w, 4); the volume itself is level 0 and
+    is not copied.  Device tensors: asynchronous on torch's current stream."""
+    d, h, w = volume.shape[:3]
+    n = levels or mip_levels_3d(w, h, d)
+    out = [volume]
+    for l in range(1, n):
+        shape = (max(1, d >> l), max(1, h >> l), max(1, w >> l), 4)
+        if hasattr(volume, "data_ptr"):
+            import torch
+            out.append(torch.empty(shape, dtype=volume.dtype, device=volume.device))
+        else:
+            import numpy as np
+            out.append(np.empty(shape, dtype=volume.dtype))
+    return generate_mips_3d_into(out, filter=filter, wrap=wrap, srgb=srgb, per_level=per_level)
+
+
+def generate_mips_3d_into(levels, filter=None, wrap="", srgb=False, per_level=False, flags=None):
+    """itwGenerateMipChain with ITW_MIP_VOLUME over caller-made levels: `levels` is the list of a chain's levels, each a (d, h, w, 4) array / tensor or a
+    list of d (h, w, 4) slices, which may be strided views of larger arrays / tensors; level 0 filled in.  `flags`: the raw bit set in
+    place of the named options.  Raises ValueError where the call returns -1."""
+    flat = [lv[z] for lv in levels for z in range(len(lv))]
+    on_device = hasattr(flat[0], "data_ptr")
+    es = flat[0].element_size() if on_device else flat[0].itemsize
+    if on_device:
+        import torch
+        lib().itwSetStream(torch.cuda.current_stream(flat[0].device).cuda_stream)
+    if flags is None:
+        flags = mip_filter_flags_3d(filter, wrap, srgb, per_level)
+    if lib().itwGenerateMipChain(C.cast(_surfaces(flat), C.c_void_p), len(levels[0]), len(levels), 4 * es, flags | MIP_VOLUME) != 0:
+        raise ValueError("itwGenerateMipChain refused the volume: " + (last_error() or "bad arguments"))
+    return levels
+
+
+def compress_volume(fmt, volume, levels=0, profile=None, settings=None, filter=None, wrap="", srgb=False, progress=None, out=None):
+    """itwCompressImageMippedEx with ITW_MIP_VOLUME: the volume save path in one call -- the base slices into level 0 of a device-side chain, the 3D mip chain
+    (filter / wrap / srgb as generate_mips_3d takes them), then the chain encoder over the slice list.  volume: a (D, H, W, 4) numpy array
+    or CUDA torch tensor, or a list of D (H, W, 4) slices.  Returns (ok, blocks): a volume .dds file's payload, level-major."""
+    import numpy as np
+    base = _base(fmt)
+    slices = [volume[z] for z in range(len(volume))]
+    for img in slices:
+        _check_texel_type(fmt, img)
+    d, (h, w) = len(slices), slices[0].shape[:2]
+    n = levels or mip_levels_3d(w, h, d)
+    nbytes = sum(max(1, d >> l) * ((max(1, w >> l) + 3) // 4) * ((max(1, h >> l) + 3) // 4) for l in range(n)) * BYTES_PER_BLOCK[base]
+    on_device = hasattr(slices[0], "data_ptr")
+    if out is None:
+        if on_device:
+            import torch
+            out = torch.zeros(nbytes, dtype=torch.uint8, device=slices[0].device)
+        else:
+            out = np.zeros(nbytes, dtype=np.uint8)
+    if on_device or hasattr(out, "data_ptr"):
+        import torch
+        dev = slices[0].device if on_device else out.device
+        lib().itwSetStream(torch.cuda.current_stream(dev).cuda_stream)
+    dst = out.data_ptr() if hasattr(out, "data_ptr") else out.ctypes.data
+    if settings is None and base == "bc7":
+        settings = bc7_profile(profile or "slow")
+    elif settings is None and base == "bc6h":
+        settings = bc6h_profile(profile or "slow")
+    elif settings is None and base == "etc1":
+        settings = etc_profile(profile or "slow")
+    sp = C.cast(C.byref(settings), C.c_void_p) if settings is not None else None
+    cb = PROGRESS_FUNC(progress) if progress else None
+    ok = lib().itwCompressImageMippedEx(C.cast(_surfaces(slices), C.c_void_p), d, levels, 0, mip_filter_flags_3d(filter, wrap, srgb) | MIP_VOLUME, dst,
+                                        DXGI_FORMAT[fmt], sp, C.cast(cb, C.c_void_p) if cb else None, None)
+    return bool(ok), out
+
+
 def mip_chain(img):
     """Test / tool content: the level list of a full mip chain of `img` (numpy (H, W, 4)), level l+1 of max(1, w >> 1) x max(1, h >> 1)
     from level l by a plain 2x2 mean (an odd last row / column is repeated).  uint8 levels average as integers, uint16 half bits as float16.
@@ -1780,6 +1904,8 @@ def load_dds(data, device=None):
     first = lib().itwDdsReadHeader(raw.ctypes.data, raw.size, C.byref(desc))
     if not first:
         raise ValueError("not a BCn DDS file this library reads")
+    if desc.is_cubemap == DDS_VOLUME:
+        raise ValueError("a volume DDS file: its slices are level-major, load_dds_volume reads it")
     fmt = {v: k for k, v in DXGI_FORMAT.items()}[int(desc.dxgi_format)]
     if fmt == "bc6h_sf16":
         fmt = "bc6h_signed"                               # a file's label 96 is a descriptor code; the entry points read it under 0x8E8E
@@ -1795,6 +1921,68 @@ def load_dds(data, device=None):
     import torch
     texels, amin = decode_chain(fmt, torch.from_numpy(payload.copy()).to(device), sizes, want_min_alpha=True)
     return desc, texels, [int(v) & 0xFFFFFFFF for v in amin.cpu().tolist()]
+
+
+def dds_volume_file(fmt_key, width, height, depth, slices, mip_levels=1):
+    """Volume DDS file bytes for the block arrays `slices` in file order (level-major).  fmt_key: a key of DXGI_FORMAT."""
+    import numpy as np
+    d = DdsVolumeDesc(width, height, depth, mip_levels, DXGI_FORMAT[fmt_key])
+    total = lib().itwDdsFileBytes(C.byref(d))
+    if not total:
+        raise ValueError("unsupported volume DDS description")
+    out = np.empty(total, dtype=np.uint8)
+    keep = [np.ascontiguousarray(np.asarray(s, dtype=np.uint8)) for s in slices]
+    ptrs = (C.c_void_p * max(1, len(keep)))(*[k.ctypes.data for k in keep])
+    n = lib().itwDdsWriteFile(C.byref(d), ptrs, len(keep), out.ctypes.data, out.size)
+    if n != total:
+        raise ValueError("itwDdsWriteFile failed (slice count / sizes)")
+    return out
+
+
+def dds_volume_images(desc):
+    """itwDdsImage over a volume's DdsDesc: [(height, width, level, slice, offset, bytes)] of every slice in file order (level-major)."""
+    assert desc.is_cubemap == DDS_VOLUME
+    out, level, first = [], 0, 0
+    for h, w, off, n in dds_images(desc):
+        while len(out) - first >= max(1, desc.array_size >> level):
+            first += max(1, desc.array_size >> level)
+            level += 1
+        out.append((h, w, level, len(out) - first, off, n))
+    return out
+
+
+def load_dds_volume(data, device=None):
+    """The load path of a volume: a .dds file's bytes -> (DdsDesc, [texels per level as (d, h, w, 4)], [min alpha per slice]).
+    itwDdsReadHeader + itwDdsImage + one itwDecodeChain over the payload, every level decoded into one array / tensor; the descriptor
+    says is_cubemap = ITW_DDS_VOLUME and holds the depth in array_size.  device as load_dds takes it.  Raises ValueError for a header that
+    is no volume this library reads and for a truncated file."""
+    import numpy as np
+    raw = np.frombuffer(data, dtype=np.uint8) if isinstance(data, (bytes, bytearray, memoryview)) else np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+    desc = DdsDesc()
+    first = lib().itwDdsReadHeader(raw.ctypes.data, raw.size, C.byref(desc))
+    if not first or desc.is_cubemap != DDS_VOLUME:
+        raise ValueError("not a BCn volume DDS file this library reads")
+    fmt = {v: k for k, v in DXGI_FORMAT.items()}[int(desc.dxgi_format)]
+    if fmt == "bc6h_sf16":
+        fmt = "bc6h_signed"
+    images = dds_volume_images(desc)
+    end = images[-1][4] + images[-1][5] if images else 0
+    if not images or images[0][4] != first or raw.size < end:
+        raise ValueError(f"truncated DDS file: {raw.size} bytes, the header describes {end}")
+    payload = raw[first:end]
+    depth = desc.array_size
+    if device is None:
+        blocks = payload
+        levels = [np.empty((max(1, depth >> l), max(1, desc.height >> l), max(1, desc.width >> l), 4), dtype=_texel_dtype(fmt)) for l in range(desc.mip_levels)]
+    else:
+        import torch
+        blocks = torch.from_numpy(payload.copy()).to(device)
+        levels = [torch.empty((max(1, depth >> l), max(1, desc.height >> l), max(1, desc.width >> l), 4), dtype=_texel_dtype(fmt, torch), device=device)
+                  for l in range(desc.mip_levels)]
+    _, amin = decode_chain(fmt, blocks, [levels[lv][sl] for _, _, lv, sl, _, _ in images], want_min_alpha=True)
+    if device is None:
+        return desc, levels, [int(v) for v in amin]
+    return desc, levels, [int(v) & 0xFFFFFFFF for v in amin.cpu().tolist()]
 
 
 def ktx_file(width, height, levels, mip_levels=1, cubemap=False):
